@@ -67,6 +67,9 @@ def parse():
     ap.add_argument("--no-config3", action="store_true", help="N > 1: skip the configs[3] object (256 ragged molecules per GPU)")
     ap.add_argument("--no-x6-probe", action="store_true",
                     help="skip the extra (untimed-for-`value`) pass in the opt-in f32x6 mode that is reported beside the fp32 line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0: its batch and the molecules "
+                         "returned) as float32 DIR/<name>.npy, at most 64 MB")
     ap.add_argument("--fragment", action="store_true",
                     help="configs[4] sampler: inpainting around a fixed 8-atom fragment (6 C + 2 Cl), resample_steps=1, "
                          "inertial_fragment_matching=False -> 2 denoiser calls per step + 1")
@@ -242,7 +245,7 @@ def make_generator(args, dev, dtype, sd, gsd):
 
 
 def timed_passes(gen, ctx, n_total, n_atoms, variance, frag_kw, steps, warmup, fence, seed=7, ref_conformer=None,
-                 vary_sizes=False):
+                 vary_sizes=False, last_out=None):
     """`steps` timed calls of the public sharded path after `warmup` untimed ones.
     `vary_sizes`: every pass (warm-up included) draws its molecule sizes from seed + pass index, the way a caller of a
     ragged workload runs it (the reference's protocol generates for 1 000 different references,
@@ -250,11 +253,13 @@ def timed_passes(gen, ctx, n_total, n_atoms, variance, frag_kw, steps, warmup, f
     the plan for it - host tables, uploads, workspace, HIP-graph capture - inside the timed region.  Otherwise every pass
     re-draws the SAME sizes (fixed-size workloads: the draw is constant anyway).
     Returns (elapsed seconds on this rank, mean sampler ms per pass, whether EVERY coordinate this rank generated in the
-    timed passes is finite - checked after the clock stops, last valid fraction)."""
+    timed passes is finite - checked after the clock stops, last valid fraction).  `last_out` (a dict): receives the
+    molecules the last timed pass returned ("molecules") and the tensors of its whole batch ("batch")."""
     from ml_conformer_generator_amd.conformer_generator import HAVE_RDKIT     # (MMFF94 runs only where RDKit exists)
     sampler_ms = []
     kept = []
     pass_index = [0]
+    mols = None
 
     def one_pass():
         # sizes: CPU generator only (torch.manual_seed would also reseed every device generator and give all ranks
@@ -281,9 +286,11 @@ def timed_passes(gen, ctx, n_total, n_atoms, variance, frag_kw, steps, warmup, f
     fence()
     t0 = time.perf_counter()
     for _ in range(steps):
-        one_pass()
+        mols = one_pass()
     fence()
     elapsed = time.perf_counter() - t0
+    if last_out is not None and mols is not None:
+        last_out.update(molecules=mols, batch=gen.last_batch)
     finite = all(bool(torch.isfinite(x).all()) for x in kept)
     return elapsed, sum(sampler_ms) / max(1, len(sampler_ms)), finite, gen.last_valid_fraction
 
@@ -322,6 +329,60 @@ def cold_call_cost(gen, dev, n_samples=256, n_atoms=27, variance=12, seed=9001):
             "warm_call_ms": warm_ms, "plans_cached": len(dyn._plans),
             "what": "first denoiser call over a never-seen size vector minus a warm one: plan (host tables, uploads, "
                     "workspace) + HIP-graph capture; mean of 3 fresh vectors"}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(last, out_dir):
+    """What the last timed step computed, as float32 arrays DIR/<name>.npy (64 MB in all at most):
+      batch_<key>    every tensor of the whole generated batch (`gen.last_batch`, this rank's: sampled coordinates `x`,
+                     features `h`, `n_nodes`, GCN element types / bond orders, coordinates in GCN order `x_ordered`) -
+                     with synthetic weights the validity gate may drop every molecule, this is what was computed;
+      returned_<f>   the molecule records the call returned (those that passed the validity gate), padded:
+                     coords [K, n, 3], atomic_numbers [K, n], bond_orders [K, n, n] (padding 0), n_atoms [K], and
+                     batch_row [K] (the record's row in the batch, -1 if it does not name one) - only when K > 0: with
+                     synthetic weights the gate may return nothing, and then no returned_* file is written.
+    Past the limit, both are a fixed seeded sample of their molecules in order, named by `*_molecule_index`."""
+    import numpy as np
+    mols, batch = last.get("molecules") or [], last.get("batch") or {}
+    batch = {k: v.detach().float().cpu().numpy() for k, v in batch.items() if torch.is_tensor(v)}
+    B = min((a.shape[0] for a in batch.values()), default=0)
+    n_max = max((m.GetNumAtoms() for m in mols), default=0)
+    batch_bytes = sum(a.nbytes for a in batch.values())
+    rec_per_mol = 4 * (3 * n_max + n_max + n_max * n_max + 2)
+    frac = min(1.0, DUMP_LIMIT_BYTES / max(1, batch_bytes + B * 4 + len(mols) * rec_per_mol))
+
+    def sample(n, seed):
+        idx = np.arange(n)
+        if frac < 1.0:
+            idx = np.sort(np.random.default_rng(seed).choice(n, max(1, int(n * frac)), replace=False))
+        return idx
+    arrs = {}
+    bi = sample(B, 0)
+    for k, a in batch.items():
+        arrs["batch_" + k] = np.ascontiguousarray(a[bi] if a.shape[0] == B else a)
+    arrs["batch_molecule_index"] = bi.astype(np.float32)
+    ri = sample(len(mols), 1) if mols else np.zeros(0, np.int64)
+    k = len(ri)
+    rec = {"coords": np.zeros((k, n_max, 3), np.float32), "atomic_numbers": np.zeros((k, n_max), np.float32),
+           "bond_orders": np.zeros((k, n_max, n_max), np.float32), "n_atoms": np.zeros(k, np.float32),
+           "molecule_index": ri.astype(np.float32), "batch_row": np.full(k, -1.0, np.float32)}
+    for j, b in enumerate(ri):
+        m = mols[b]
+        n = m.GetNumAtoms()
+        row = getattr(m, "_b", None)               # a record's row in the host batch it views (generation order)
+        if row is not None and row >= 0:
+            rec["batch_row"][j] = row
+        rec["coords"][j, :n] = m.coords.numpy()
+        rec["atomic_numbers"][j, :n] = m.atomic_numbers
+        rec["bond_orders"][j, :n, :n] = m.bond_orders.numpy()
+        rec["n_atoms"][j] = n
+    if k and n_max:
+        arrs.update({"returned_" + name: a for name, a in rec.items()})
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32, copy=False))
 
 
 def synthetic_fragment():
@@ -762,8 +823,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
+    last_step = {}
     elapsed, sampler_ms, finite, valid_frac = timed_passes(gen, ctx, B * world, args.n_atoms, args.variance, frag_kw,
-                                                           args.steps, args.warmup, fence)
+                                                           args.steps, args.warmup, fence, last_out=last_step)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_step, args.dump_outputs)
     head_assembly_ms = gen.last_host_assembly_ms          # D2H of the (gathered) result tensors + molecule records, last pass
     if use_dist:
         tt = torch.tensor([elapsed, 0.0 if finite else 1.0], dtype=torch.float64,
