@@ -59,7 +59,10 @@ int mcg_egnn_set_precision(mcg_egnn* m, int mode);
  *                            2 = whenever its shape limits allow (results are bit-identical either way)
  *   MCG_OPT_NODE_FUSED  [0]  bf16 mode: the node phase of a GCL layer (node MLP + the next edge layer's first-layer projections) as ONE
  *                            launch: 0 = from 32 row blocks (1 024 atoms) on, 1 = never (three launches),
- *                            2 = whenever the bf16 gather path runs (results are bit-identical either way) */
+ *                            2 = whenever the fused launch can run (results are bit-identical either way).  It can run only on
+ *                            plans of 64-row units (edge_mt = 4) whose atoms span at most 2 units, with MCG_OPT_GEMM_BF16_LDS != 1,
+ *                            on the bf16 gather path (the node GEMM sums an atom's per-unit partial rows itself: not in
+ *                            mcg_egnn_gcl_debug, which materialises the aggregate) */
 enum { MCG_OPT_X6_GEMM = 1, MCG_OPT_GEMM_RN = 2, MCG_OPT_GEMM_X6_RN = 3, MCG_OPT_GEMM_BF16_LDS = 4, MCG_OPT_NODE_FUSED = 5 };
 /* Both setters may be called at any time between denoiser calls: a plan that has already captured its launches as a HIP
  * graph re-captures on its next call (the graph is keyed by the model's option epoch). */

@@ -278,14 +278,12 @@ __global__ __launch_bounds__(256, 2) void k_edge_bf16_w64(EdgeArgs p) {
     long long rawij = -1;
     if (tile < p.n_mtiles) rawij = reinterpret_cast<const long long*>(p.row_ij)[tile * 16 + c];
     float stg[8];
-#ifndef MCG_ABL_NOPARAM      // (ablation switch: parameters never staged - wrong results)
     {
         const int t0 = threadIdx.x, t1 = threadIdx.x + 256;
         const int h1 = t1 < HP ? t1 : HP - 1, k1 = t1 < W64_KP ? t1 : W64_KP - 1;
         stg[0] = p.b2[t0]; stg[1] = p.wv[t0]; stg[2] = p.b2[h1]; stg[3] = p.wv[h1];
         stg[4] = p.wd[t0]; stg[5] = p.wd0[t0]; stg[6] = p.wd[k1]; stg[7] = p.wd0[k1];
     }
-#endif
     __builtin_amdgcn_sched_barrier(0);
     {
         const int ix = (int)rawij, iy = (int)(rawij >> 32);
@@ -332,24 +330,15 @@ __global__ __launch_bounds__(256, 2) void k_edge_bf16_w64(EdgeArgs p) {
     const unsigned ov = (unsigned)(wid * 64 + lane) * 16u;
     const unsigned ov6 = (unsigned)((wid + 24 < NT ? wid + 24 : NT - 1) * 64 + lane) * 16u;
     bf16x8 Bq[2][NS_T];
-#ifndef MCG_W64_B_AUX
-#define MCG_W64_B_AUX 0          // (measurement switch: cache-policy bits of the weight-fragment loads - 1 sc0, 2 nt, 16 sc1)
-#endif
-#ifndef MCG_W64_A_AUX
-#define MCG_W64_A_AUX 0          // (same for the layer-1 input loads)
-#endif
     auto ld16 = [](const __amdgpu_buffer_rsrc_t& r, unsigned voff, int soff) {
-        return __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, MCG_W64_A_AUX);
-    };
-    auto ld16w = [](const __amdgpu_buffer_rsrc_t& r, unsigned voff, int soff) {
-        return __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, MCG_W64_B_AUX);
+        return __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, 0);
     };
     auto load_b = [&](bf16x8 (&dst)[NS_T], int stage) {
         stage = stage < NSTAGE ? stage : NSTAGE - 1;
         const int base = stage * STAGE_BYTES;
 #pragma unroll
-        for (int i = 0; i < NS_T - 1; ++i) dst[i] = __builtin_bit_cast(bf16x8, ld16w(rs_b, ov, base + i * 4 * 64 * 16));
-        dst[NS_T - 1] = __builtin_bit_cast(bf16x8, ld16w(rs_b, ov6, base));
+        for (int i = 0; i < NS_T - 1; ++i) dst[i] = __builtin_bit_cast(bf16x8, ld16(rs_b, ov, base + i * 4 * 64 * 16));
+        dst[NS_T - 1] = __builtin_bit_cast(bf16x8, ld16(rs_b, ov6, base));
     };
     auto load_a = [&](int kb, f32x4 (&v)[4]) {
         kb = kb < KB16 ? kb : KB16 - 1;
@@ -412,20 +401,14 @@ __global__ __launch_bounds__(256, 2) void k_edge_bf16_w64(EdgeArgs p) {
         for (int mt = 0; mt < 4; ++mt) af[mt] = a_lds[(half * 4 + mt) * 64 + lane];
         const int st = next_stage < NSTAGE ? next_stage : NSTAGE - 1;
         const int base = st * STAGE_BYTES;
-#ifndef MCG_W64_AGEN_POS
-#define MCG_W64_AGEN_POS 3
-#endif
-        if (MCG_W64_AGEN_POS < 0) { __builtin_amdgcn_sched_barrier(0); mid(); }      // (measurement switch: generation in front of the block's first MFMA)
 #pragma unroll
         for (int i = 0; i < NS_T; ++i) {
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) acc[mt][i] = mcg_mfma_bf16(af[mt], Bc[i], acc[mt][i]);
             __builtin_amdgcn_sched_barrier(0);
-#ifndef MCG_ABL_NOB          // (ablation switch: no weight refills - wrong results, an upper bound for any better weight delivery)
-            Bc[i] = __builtin_bit_cast(bf16x8, i < NS_T - 1 ? ld16w(rs_b, ov, base + i * 4 * 64 * 16) : ld16w(rs_b, ov6, base));
-#endif
+            Bc[i] = __builtin_bit_cast(bf16x8, i < NS_T - 1 ? ld16(rs_b, ov, base + i * 4 * 64 * 16) : ld16(rs_b, ov6, base));
             __builtin_amdgcn_sched_barrier(0);
-            if (i == MCG_W64_AGEN_POS) mid();          // (position 0 / 1 / 3 / 5 measured: no difference)
+            if (i == 3) mid();                         // (position 0 / 1 / 3 / 5 measured: no difference)
         }
     };
     // one k-block: [barrier] A-operand loads of block kb+1 | per weight part: MFMAs, then the B loads two stages
@@ -445,13 +428,9 @@ __global__ __launch_bounds__(256, 2) void k_edge_bf16_w64(EdgeArgs p) {
         constexpr int SET = decltype(set_tag)::value;       // SPLIT = 1: the set that receives block kb + 2; the other holds kb + 1
         const int half = kb & 1;
         // (bf16: the request for block kb + 2 goes out BEFORE the rendezvous - it depends on nothing the barrier orders)
-#ifndef MCG_ABL_NOA          // (ablation switch: layer-1 inputs never reloaded)
         if (SPLIT == 1) { load_a(kb + 2, vset[SET]); __builtin_amdgcn_sched_barrier(0); }
-#endif
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // my A-tile writes of the previous block
-#ifndef MCG_ABL_NOBAR        // (ablation switch: no rendezvous)
         asm volatile("s_barrier" ::: "memory");                      // A(kb) visible; A ring half^1 free
-#endif
         f32x4 v[4];
 #pragma unroll
         for (int part = 0; part < SPLIT; ++part) {
@@ -490,7 +469,6 @@ __global__ __launch_bounds__(256, 2) void k_edge_bf16_w64(EdgeArgs p) {
     load_b(Bq[1], 1);
     __builtin_amdgcn_sched_barrier(0);
     // (everything of round trip 2 is in flight; now the work that only needs round trip 1 and the coordinates)
-#ifndef MCG_ABL_NOPARAM
     {
         const int t0 = threadIdx.x, t1 = threadIdx.x + 256;
         par[t0] = stg[0]; par[HP + t0] = stg[1];
@@ -498,7 +476,6 @@ __global__ __launch_bounds__(256, 2) void k_edge_bf16_w64(EdgeArgs p) {
         wdl[t0] = stg[4]; wdl[W64_KP + t0] = stg[5];
         if (t1 < W64_KP) { wdl[t1] = stg[6]; wdl[W64_KP + t1] = stg[7]; }
     }
-#endif
     {
         const float dx = xi[0] - xj[0], dy = xi[1] - xj[1], dz = xi[2] - xj[2];
         const float ex = yi[0] - yj[0], ey = yi[1] - yj[1], ez = yi[2] - yj[2];

@@ -1,8 +1,7 @@
 // One denoiser call (EGNNDynamics.forward, egnn.py:472-513) on a plan: embedding, 9 x EquivariantBlock
-// (egnn.py:188-222: two GCL layers + the coordinate update; node GEMMs of mcg_gemm.h around the fused edge kernels of
+// (egnn.py:188-222: two GCL layers + the coordinate update; node GEMMs of mcg_gemm.hip around the fused edge kernels of
 // mcg_edge_*.hip), output head; captured once per plan as a HIP graph and replayed.  Debug / measurement hooks.
 #include "mcg_gemm.h"
-#include "mcg_node_fused.h"
 #include "mcg_egnn_internal.h"
 
 #include <atomic>
@@ -169,56 +168,6 @@ __global__ __launch_bounds__(256) void k_output(const float* __restrict__ h, con
     }
 }
 
-// exact-fp32 throughput kernel with workgroup-level sums (writes pl->U / pl->Ux); plans without unit tables
-// (atoms whose rows span more than four units, N > ~50) and latency mode 1 take k_edge_ns with per-unit partial sums
-static bool edge_latency_kernel(const mcg_plan* pl) {
-    return pl->MT == 1 && (pl->latency_mode == 1 || !pl->wgc);
-}
-static bool edge_wgc(const mcg_egnn* m, const mcg_plan* pl) {
-    return pl->wgc && pl->MT == 1 && !m->bf16 && !m->x6 && !edge_latency_kernel(pl);
-}
-
-#ifndef MCG_PAB_BLOCKED
-#define MCG_PAB_BLOCKED 1          // (measurement switch: 0 = row-major layer-1 inputs in the bf16 mode too)
-#endif
-int run_edge(const mcg_plan* pl, const EdgeLayer& L, bool equiv, float* P, hipStream_t s, bool bf16 = false, bool x6 = false,
-             bool wgc = false) {
-    if (pl->n_waves == 0) return MCG_OK;
-    EdgeArgs a;
-    a.pab = pl->pab; a.x = pl->x; a.x0 = pl->x0; a.wd = L.wd; a.wd0 = L.wd0; a.Bp = L.w2_Bp; a.b2 = L.b2;
-    a.wv = L.wv; a.bv = L.bv; a.row_ij = pl->row_ij; a.wave_poff = pl->wave_poff;
-    a.n_mtiles = pl->n_mtiles; a.n_waves = pl->n_waves; a.P = P;
-    const mcg_plan::UnitTables& T = pl->units();
-    a.wg_info = T.wg_info; a.U = equiv ? pl->Ux : pl->U;
-    a.n_full_wg = T.n_full_wg; a.Bp4 = L.w2_Bp4;
-    a.M = pl->M;
-    a.pab_blocked = (bf16 && pl->MT == 4 && MCG_PAB_BLOCKED) ? 1 : 0;      // the bf16 first-layer GEMM wrote pab blocked for these plans (run_gcl / run_equiv)
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    if (pl->edge_timing && *pl->edge_timing_next < pl->edge_timing->size()) {     // mcg_bench_edge_incall
-        mcg_plan::EdgeTiming& e = (*pl->edge_timing)[(*pl->edge_timing_next)++];
-        t0 = e.t0; t1 = e.t1; e.equiv = equiv; e.used = true;
-    }
-    if (wgc) {
-        MCG_HIP(mcg_launch_edge_exact(a, equiv, T.n_units, s, t0, t1));
-        return MCG_OK;
-    }
-    if (x6 && pl->MT == 4) {       // (plans with 16-row tiles - molecules below 6 atoms - run the exact fp32 kernels)
-        a.Bp = reinterpret_cast<const float*>(L.w2_Bp16x3);
-        MCG_HIP(mcg_launch_edge_w64(a, equiv, true, s, t0, t1));
-        return MCG_OK;
-    }
-    if (bf16) {
-        a.Bp = reinterpret_cast<const float*>(L.w2_Bp16);
-        if (pl->MT == 4) MCG_HIP(mcg_launch_edge_w64(a, equiv, false, s, t0, t1));
-        else MCG_HIP(mcg_launch_edge_bf16_16(a, equiv, s, t0, t1));
-        return MCG_OK;
-    }
-    if (pl->MT == 4) { mcg_set_error("edge_mt = 4 plans are for the bf16 / f32x6 modes only"); return MCG_ERR_STATE; }
-    // column-split kernel with per-unit partial sums (one workgroup per 16-row tile): any batch, any molecule size
-    MCG_HIP(mcg_launch_edge_ns(a, equiv, s, t0, t1));
-    return MCG_OK;
-}
-
 // SIMDs of the CURRENT device (4 per compute unit), queried once per device: one process may drive several devices
 static long mcg_simd_count() {
     static std::atomic<long> n[64];
@@ -236,49 +185,135 @@ static long mcg_simd_count() {
     return v;
 }
 
-// `side` (optional): plan whose pending coordinate update rides along as the launch's side job (fp32 kernels only).
-// `rows16` > 0: the 16-row wave-tile kernel with that many column tiles per wave; `a2_rows`: two-row gather of A2.
-int gemm(const float* A1, int lda1, int K1, const float* A2, int lda2, int K2, const float* Bp, const float* bias,
-         const float* resid, int ldr, float* C, int ldc, int M, int n_tiles, int n_store, int act, hipStream_t s,
-         const uint16_t* Bp16 = nullptr, const uint16_t* Bp16x3 = nullptr, mcg_plan* side = nullptr, int rows16 = 0,
-         const int4* a2_rows = nullptr, int a2_nsum = 2, const mcg_egnn* opt = nullptr, bool c_blocked = false) {
-    McgGemmArgs g{};
-    g.A1 = A1; g.lda1 = lda1; g.K1 = K1; g.A2 = A2; g.lda2 = lda2; g.K2 = K2; g.Bp = Bp; g.bias = bias;
-    g.resid = resid; g.ldr = ldr; g.C = C; g.ldc = ldc; g.M = M; g.n_tiles = n_tiles; g.n_store = n_store; g.act = act;
-    if (side && side->x_pending && !Bp16x3) {       // fp32 and bf16 kernels carry the side job; the split-operand one does not
-        g.side_u = side->pending_u; g.side_slots = side->pending_slots; g.side_x = side->x; g.side_M = side->M;
-        side->x_pending = false;
+// ------------------------------------------------------------------------------ route
+// Which kernels the layers of a denoiser call run, decided in ONE place (route()) from the model's precision and options, the
+// plan's geometry and the debug hook's keep_agg.  run_gcl / run_equiv / run_edge / mcg_bench_edge only read it.
+// Edge kernel: Exact = throughput kernel with workgroup-level sums in U / Ux (k_edge_lds), Ns = column-split kernel with per-unit
+// partial sums (k_edge_ns: any batch, any molecule size), bf16 16-row tiles, bf16 / f32x6 64-row units; Invalid = 64-row plan, fp32.
+enum class EdgeKernel { Exact, Ns, Bf16Rows16, W64Bf16, W64X6, Invalid };
+enum class GemmFamily { F32, F32Rows16, Bf16, X6 };     // mcg_gemm_launch / mcg_gemm16_launch / mcg_gemm_bf16_launch / mcg_gemm_x6_launch
+struct GemmRoute { GemmFamily family; int rn = 0, mr = 1; bool deep = false; };     // rn / mr / deep: the 16-row tile
+// W3's aggregate half: summed from an atom's rows of U (fp32 16-row kernel) or of P (/ 100, bf16 kernels) in the GEMM's A-loader,
+// or materialised first by k_gather_agg2 (from U) / k_combine_agg_t (from P)
+enum class AggSource { GatherU, GatherP, GatherAgg2, Combine };
+// coordinate update: pending on Ux (workgroup-level sums) or Px (bf16 per-unit partial sums) for the side job of the next block's
+// first GEMM (after the last block: k_output), or applied by k_coord_update_t right behind the edge launch
+enum class CoordUpdate { PendingU, PendingP, Kernel };
+struct Route {
+    EdgeKernel edge;
+    bool pab_blocked;       // layer-1 inputs in the blocked layout the 64-row bf16 edge kernel reads (mcg_gemm.h c_blocked)
+    GemmRoute pab;          // first-layer projections of both layer kinds; every family but X6 can carry a pending coordinate
+                            // update as its side job (an X6 launch has it applied by k_coord_apply2 first)
+    AggSource agg;          // GCL
+    bool fused;             // GCL: W3 + W4 + the next layer's projections in one launch (mcg_node_fused_launch)
+    GemmRoute node;         // GCL: W3 and W4 when not fused
+    CoordUpdate coord;      // coordinate layer
+};
+
+// 16-row tile of up to `rows16` column tiles per wave.  Small batches: narrower wave tiles (1 or 2 column tiles) as long as
+// every wave still gets a SIMD of its own - these launches are one serial MFMA chain per wave, and a third of the chain is a
+// third of the latency (4 molecules of 19 atoms: W3 18.6 -> ~9 us), with the deep operand ring (mcg_gemm16_launch).  Same k
+// order per output element: bit-identical results.  16-row wave tiles while they fit one wave per SIMD (972 waves at
+// config 2), two of them per wave beyond.
+static GemmRoute rows16_tile(int M, int n_tiles, int rows16) {
+    GemmRoute t{GemmFamily::F32Rows16, rows16};
+    const long rt = (M + 15) / 16;
+    for (int cand : {1, 2, 3})
+        if (cand < rows16 && rt * ((n_tiles + cand - 1) / cand) <= mcg_simd_count()) { t.rn = cand; break; }
+    t.mr = rt * ((n_tiles + t.rn - 1) / t.rn) <= 1280 ? 1 : 2;
+    t.deep = t.rn < rows16 && t.rn <= 2;
+    return t;
+}
+
+static Route route(const mcg_egnn* m, const mcg_plan* pl, bool keep_agg) {
+    Route r{};
+    const int M = pl->M;
+    const bool x6g = m->x6 && m->x6_gemm;
+    // exact-fp32 throughput kernel while the plan has unit tables (atoms whose rows span at most four units, N <= ~50) and
+    // latency mode 1 is off
+    const bool wgc = pl->wgc && pl->MT == 1 && !m->bf16 && !m->x6 && pl->latency_mode != 1;
+    if (wgc) r.edge = EdgeKernel::Exact;
+    else if (m->x6 && pl->MT == 4) r.edge = EdgeKernel::W64X6;      // (plans with 16-row tiles - molecules below 6 atoms - run the fp32 kernels)
+    else if (m->bf16) r.edge = pl->MT == 4 ? EdgeKernel::W64Bf16 : EdgeKernel::Bf16Rows16;
+    else r.edge = pl->MT == 4 ? EdgeKernel::Invalid : EdgeKernel::Ns;
+    r.pab_blocked = m->bf16 && pl->MT == 4;
+    // First-layer GEMM (N = 864): the 32-row kernel from ~900 atoms on (14.2 vs 14.8 us at configs[1]); below that the 16-row
+    // kernel with as few column tiles per wave as still give every wave its own SIMD (1 .. 6)
+    const bool pab16 = (long)((M + 15) / 16) * ((2 * NT + 2) / 3) <= mcg_simd_count();
+    r.pab = x6g ? GemmRoute{GemmFamily::X6} : m->bf16 ? GemmRoute{GemmFamily::Bf16}
+          : pab16 ? rows16_tile(M, 2 * NT, 6) : GemmRoute{GemmFamily::F32};
+    // node_mlp: wave tiles of 3 column tiles x 16 rows balance the two GEMMs on 1024 SIMDs at config 2 (972 waves)
+    r.node = x6g ? GemmRoute{GemmFamily::X6} : m->bf16 ? GemmRoute{GemmFamily::Bf16} : rows16_tile(M, NT, 3);
+    // bf16 mode: the node GEMM gathers an atom's per-unit partial sums (<= 4 rows of P) itself - no combine launch.
+    // (Reading the per-wave partials directly in the fp32 node GEMM's A-loader was tried: the 4-way gather costs the GEMM as
+    //  much as the ~6 us combine launch it saves at config 2 and more at config 3.)
+    const bool pgather = m->bf16 && pl->pslots4 && pl->pspan <= 4;
+    r.agg = wgc ? (keep_agg ? AggSource::GatherAgg2 : AggSource::GatherU)
+          : pgather && !keep_agg ? AggSource::GatherP : AggSource::Combine;
+    // bf16 mode, large batches (round 6): W3 -> SiLU -> W4 -> + h -> the NEXT edge layer's first-layer projections in ONE launch
+    // where the three launches would all be the LDS-staged 9-wave kernel; bit-identical h and Pab.  It needs 64-row units,
+    // atoms that span at most two of them, and MCG_OPT_GEMM_BF16_LDS != 1 (from MCG_NF_MIN_ROWBLOCKS row blocks on: ms per
+    // denoiser call, three launches -> one, 27-atom molecules, profiles/round6_probes.txt: 4 .. 16 molecules 1.08 -> 1.11,
+    // 32 (27 row blocks) 1.29 -> 1.29, 48 (41) 1.70 -> 1.63, 64 1.72 -> 1.64, 128 2.48 -> 2.35, 256 ragged 4.18 -> 3.89)
+    r.fused = r.agg == AggSource::GatherP && pl->MT == 4 && pl->pspan <= 2 && m->gemm_bf16_lds != 1 &&
+              (m->node_fused == 2 || (m->node_fused == 0 && (M + 31) / 32 >= MCG_NF_MIN_ROWBLOCKS));
+    r.coord = wgc ? CoordUpdate::PendingU : pgather ? CoordUpdate::PendingP : CoordUpdate::Kernel;
+    return r;
+}
+
+int run_edge(const mcg_plan* pl, const Route& r, const EdgeLayer& L, bool equiv, float* P, hipStream_t s) {
+    if (pl->n_waves == 0) return MCG_OK;
+    EdgeArgs a;
+    a.pab = pl->pab; a.x = pl->x; a.x0 = pl->x0; a.wd = L.wd; a.wd0 = L.wd0; a.Bp = L.w2_Bp; a.b2 = L.b2;
+    a.wv = L.wv; a.bv = L.bv; a.row_ij = pl->row_ij; a.wave_poff = pl->wave_poff;
+    a.n_mtiles = pl->n_mtiles; a.n_waves = pl->n_waves; a.P = P;
+    const mcg_plan::UnitTables& T = pl->units();
+    a.wg_info = T.wg_info; a.U = equiv ? pl->Ux : pl->U;
+    a.n_full_wg = T.n_full_wg; a.Bp4 = L.w2_Bp4;
+    a.M = pl->M;
+    a.pab_blocked = r.pab_blocked ? 1 : 0;
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (pl->edge_timing && *pl->edge_timing_next < pl->edge_timing->size()) {     // mcg_bench_edge_incall
+        mcg_plan::EdgeTiming& e = (*pl->edge_timing)[(*pl->edge_timing_next)++];
+        t0 = e.t0; t1 = e.t1; e.equiv = equiv; e.used = true;
     }
-    if (rows16 > 0 && !Bp16 && !Bp16x3) {
-        g.a2_rows = a2_rows; g.a2_nsum = a2_nsum;
-        // Small batches: narrower wave tiles (1 or 2 column tiles) as long as every wave still gets a SIMD of its own -
-        // these launches are one serial MFMA chain per wave, and a third of the chain is a third of the latency
-        // (4 molecules of 19 atoms: W3 18.6 -> ~9 us).  Same k order per output element: bit-identical results.
-        int rn = rows16;
-        const long rt = (M + 15) / 16;
-        for (int cand : {1, 2, 3})
-            if (cand < rows16 && rt * ((n_tiles + cand - 1) / cand) <= mcg_simd_count()) { rn = cand; break; }
-        // 16-row wave tiles while they fit one wave per SIMD (972 waves at config 2), 32-row ones beyond
-        const long w16 = rt * ((n_tiles + rn - 1) / rn);
-#ifndef MCG_G16_DEEP
-#define MCG_G16_DEEP 1          // (measurement switch: 0 = the 3-deep operand ring for small batches too)
-#endif
-        MCG_HIP(mcg_gemm16_launch(g, rn, s, w16 <= 1280 ? 1 : 2, MCG_G16_DEEP && rn < rows16 && rn <= 2));
-        return MCG_OK;
+    switch (r.edge) {
+        case EdgeKernel::Exact: MCG_HIP(mcg_launch_edge_exact(a, equiv, T.n_units, s, t0, t1)); break;
+        case EdgeKernel::Ns: MCG_HIP(mcg_launch_edge_ns(a, equiv, s, t0, t1)); break;
+        case EdgeKernel::Bf16Rows16:
+            a.Bp = reinterpret_cast<const float*>(L.w2_Bp16);
+            MCG_HIP(mcg_launch_edge_bf16_16(a, equiv, s, t0, t1));
+            break;
+        case EdgeKernel::W64Bf16:
+            a.Bp = reinterpret_cast<const float*>(L.w2_Bp16);
+            MCG_HIP(mcg_launch_edge_w64(a, equiv, false, s, t0, t1));
+            break;
+        case EdgeKernel::W64X6:
+            a.Bp = reinterpret_cast<const float*>(L.w2_Bp16x3);
+            MCG_HIP(mcg_launch_edge_w64(a, equiv, true, s, t0, t1));
+            break;
+        case EdgeKernel::Invalid: mcg_set_error("edge_mt = 4 plans are for the bf16 / f32x6 modes only"); return MCG_ERR_STATE;
     }
-    if (Bp16x3) {            // f32x6: three-part operands on the bf16 pipe, fp32-accurate
-        g.Bp = reinterpret_cast<const float*>(Bp16x3);
-        MCG_HIP(mcg_gemm_x6_launch(g, s, opt ? opt->gemm_x6_rn : 0));
-        return MCG_OK;
-    }
-    if (Bp16) { g.Bp = reinterpret_cast<const float*>(Bp16); g.a2_rows = a2_rows; g.a2_nsum = a2_nsum; g.c_blocked = c_blocked ? 1 : 0; }
-    MCG_HIP(mcg_gemm_launch(g, s, Bp16 != nullptr, opt ? opt->gemm_rn : 0, opt ? opt->gemm_bf16_lds : 0));
     return MCG_OK;
 }
 
-// First-layer GEMM (N = 864): the 32-row kernel from ~900 atoms on (14.2 vs 14.8 us at configs[1]); below that the
-// 16-row kernel with as few column tiles per wave as still give every wave its own SIMD (gemm() picks 1 .. 6)
-static int pab_rows16(int M) { return (long)((M + 15) / 16) * ((2 * NT + 2) / 3) <= mcg_simd_count() ? 6 : 0; }
+// launch of one node GEMM on the route's family, with the weight pack that family reads
+int launch_gemm(const mcg_egnn* m, const GemmRoute& r, McgGemmArgs g, const float* Bp, const uint16_t* Bp16,
+                const uint16_t* Bp16x3, hipStream_t s) {
+    switch (r.family) {
+        case GemmFamily::F32: g.Bp = Bp; MCG_HIP(mcg_gemm_launch(g, m->gemm_rn, s)); break;
+        case GemmFamily::F32Rows16: g.Bp = Bp; MCG_HIP(mcg_gemm16_launch(g, r.rn, r.mr, r.deep, s)); break;
+        case GemmFamily::Bf16:
+            g.Bp = reinterpret_cast<const float*>(Bp16);
+            MCG_HIP(mcg_gemm_bf16_launch(g, m->gemm_rn, m->gemm_bf16_lds, s));
+            break;
+        case GemmFamily::X6:
+            g.Bp = reinterpret_cast<const float*>(Bp16x3);
+            MCG_HIP(mcg_gemm_x6_launch(g, m->gemm_x6_rn, s));
+            break;
+    }
+    return MCG_OK;
+}
 
 // pending coordinate update (workgroup-level sums in pl->Ux) applied by a stand-alone launch
 int apply_pending_x(mcg_plan* pl, hipStream_t s) {
@@ -289,94 +324,81 @@ int apply_pending_x(mcg_plan* pl, hipStream_t s) {
     return MCG_OK;
 }
 
+// The first-layer projections of an edge layer, Pab = h [Wa | Wb] + (b1 | 0) (unless the previous layer's fused node launch
+// already wrote them), and the place where a pending coordinate update of the previous block is consumed: as the side job of
+// this GEMM, or by k_coord_apply2 when there is no GEMM that can carry it.
+int run_pab(const mcg_egnn* m, mcg_plan* pl, const Route& r, const EdgeLayer& E, hipStream_t s) {
+    if (pl->pab_ready || r.pab.family == GemmFamily::X6) {
+        if (int e = apply_pending_x(pl, s)) return e;
+    }
+    if (pl->pab_ready) { pl->pab_ready = false; return MCG_OK; }
+    McgGemmArgs g{};
+    g.A1 = pl->h; g.lda1 = HP; g.K1 = H; g.bias = E.pab_bias; g.C = pl->pab; g.ldc = 2 * HP;
+    g.M = pl->M; g.n_tiles = 2 * NT; g.n_store = 2 * HP; g.act = MCG_ACT_NONE; g.c_blocked = r.pab_blocked ? 1 : 0;
+    if (pl->x_pending) {
+        g.side_u = pl->pending_u; g.side_slots = pl->pending_slots; g.side_x = pl->x; g.side_M = pl->M;
+        pl->x_pending = false;
+    }
+    return launch_gemm(m, r.pab, g, E.pab_Bp, E.pab_Bp16, E.pab_Bp16x3, s);
+}
+
 // One GCL layer on the plan's compact state: h (in pl->h) -> pl->h  (egnn.py:70-85)
 int run_gcl(const mcg_egnn* m, mcg_plan* pl, int layer, hipStream_t s, bool keep_agg = false) {
+    const Route r = route(m, pl, keep_agg);
     const EdgeLayer& E = m->gcl_edge[layer];
     const NodeLayer& Nl = m->gcl_node[layer];
     const int M = pl->M;
-    const bool lp = m->bf16;
-    const bool x6g = m->x6 && m->x6_gemm;
-    const bool wgc = edge_wgc(m, pl);
-    const bool f32 = !lp && !x6g;
-    // bf16 mode: the node GEMM gathers an atom's per-unit partial sums (<= 4 rows of P) itself - no combine launch
-    const bool pgather = lp && !wgc && pl->pslots4 && pl->pspan <= 4 && !keep_agg;
-    // (a pending coordinate update of the previous block rides along with this launch; the split-operand GEMM kernel has
-    //  no side job: apply it first)
-    if (x6g) { if (int e = apply_pending_x(pl, s)) return e; }
-    const bool blocked = lp && pl->MT == 4 && MCG_PAB_BLOCKED;   // (bf16, 64-row units: pab in the blocked layout the edge kernel reads)
-    // bf16 mode, large batches (round 6): W3 -> SiLU -> W4 -> + h -> the NEXT edge layer's first-layer projections in ONE launch
-    // (mcg_node_fused.h) where the three launches would all be the LDS-staged 9-wave kernel; bit-identical h and Pab
-    // (from MCG_NF_MIN_ROWBLOCKS row blocks on: ms per denoiser call, three launches -> one, 27-atom molecules, profiles/round6_probes.txt:
-    //  4 .. 16 molecules 1.08 -> 1.11, 32 (27 row blocks) 1.29 -> 1.29, 48 (41) 1.70 -> 1.63, 64 1.72 -> 1.64, 128 2.48 -> 2.35, 256 ragged 4.18 -> 3.89)
-    const bool fused = pgather && pl->MT == 4 && pl->pspan <= 2 && m->node_fused != 1 && m->gemm_bf16_lds != 1 && Nl.w3_Bp16 && Nl.w4_Bp16 &&
-                       (m->node_fused == 2 || (M + 31) / 32 >= MCG_NF_MIN_ROWBLOCKS);
-    if (pl->pab_ready) {
-        pl->pab_ready = false;                                   // this layer's projections came out of the previous layer's fused launch
-    } else if (int e = gemm(pl->h, HP, H, nullptr, 0, 0, E.pab_Bp, E.pab_bias, nullptr, 0, pl->pab, 2 * HP, M, 2 * NT, 2 * HP,
-                            MCG_ACT_NONE, s, lp ? E.pab_Bp16 : nullptr, x6g ? E.pab_Bp16x3 : nullptr, pl, pab_rows16(M), nullptr, 2, m,
-                            blocked)) return e;
-    if (int e = apply_pending_x(pl, s)) return e;              // (only if the GEMM above could not carry it)
-    if (int e = run_edge(pl, E, false, pl->P, s, lp, m->x6, wgc)) return e;
-    if (fused) {
+    if (int e = run_pab(m, pl, r, E, s)) return e;
+    if (int e = run_edge(pl, r, E, false, pl->P, s)) return e;
+    if (r.fused) {
         const EdgeLayer& Nx = (layer & 1) ? m->equiv[layer >> 1] : m->gcl_edge[layer + 1];     // whose first layer reads h' next
         McgNodeFusedArgs a{};
         a.h = pl->h; a.ldh = HP; a.P = pl->P; a.ldp = HP; a.a2_rows = pl->pslots4; a.a2_nsum = pl->pspan;
         a.w3 = Nl.w3_Bp16; a.b3 = Nl.b3; a.w4 = Nl.w4_Bp16; a.b4 = Nl.b4; a.h_out = pl->h2; a.ldo = HP;
-        a.wab = Nx.pab_Bp16; a.bab = Nx.pab_bias; a.pab = pl->pab; a.ldpab = 2 * HP; a.pab_blocked = blocked ? 1 : 0; a.M = M;
+        a.wab = Nx.pab_Bp16; a.bab = Nx.pab_bias; a.pab = pl->pab; a.ldpab = 2 * HP; a.pab_blocked = r.pab_blocked ? 1 : 0; a.M = M;
         MCG_HIP(mcg_node_fused_launch(a, s));
         pl->pab_ready = true;
         std::swap(pl->h, pl->h2);
         return MCG_OK;
     }
-    const int4* gather = nullptr;
-    if (wgc && f32 && !keep_agg) {
-        gather = pl->units().node_slots;                        // the node GEMM adds an atom's rows of U itself
-    } else if (wgc) {
-        hipLaunchKernelGGL(k_gather_agg2, dim3(M), dim3(128), 0, s, pl->U, pl->units().node_slots, pl->agg);
-        MCG_HIP(hipGetLastError());
-    } else if (pgather) {
-        gather = pl->pslots4;                                   // rows of P, summed and divided by 100 in the bf16 GEMM's A-loader
-    } else {
-        // (reading the per-wave partials directly in the node GEMM's A-loader was tried: the 4-way gather costs the
-        //  GEMM as much as the ~6 us combine launch it saves at config 2 and more at config 3)
-        hipLaunchKernelGGL(k_combine_agg_t, dim3(M), dim3(128), 0, s, pl->P, pl->node_slots, pl->agg);
-        MCG_HIP(hipGetLastError());
+    // node_mlp: h + W4 silu(W3 [h | agg] + b3) + b4   (egnn.py:30-34,66-67)
+    McgGemmArgs g{};
+    g.A1 = pl->h; g.lda1 = HP; g.K1 = H; g.A2 = pl->agg; g.lda2 = HP; g.K2 = H; g.bias = Nl.b3;
+    g.C = pl->t1; g.ldc = HP; g.M = M; g.n_tiles = NT; g.n_store = HP; g.act = MCG_ACT_SILU;
+    switch (r.agg) {
+        case AggSource::GatherU: g.A2 = pl->U; g.a2_rows = pl->units().node_slots; g.a2_nsum = pl->units().max_span; break;
+        case AggSource::GatherP: g.A2 = pl->P; g.a2_rows = pl->pslots4; g.a2_nsum = pl->pspan; break;
+        case AggSource::GatherAgg2:
+            hipLaunchKernelGGL(k_gather_agg2, dim3(M), dim3(128), 0, s, pl->U, pl->units().node_slots, pl->agg);
+            MCG_HIP(hipGetLastError());
+            break;
+        case AggSource::Combine:
+            hipLaunchKernelGGL(k_combine_agg_t, dim3(M), dim3(128), 0, s, pl->P, pl->node_slots, pl->agg);
+            MCG_HIP(hipGetLastError());
+            break;
     }
-    // node_mlp: h + W4 silu(W3 [h | agg] + b3) + b4   (egnn.py:30-34,66-67).  Wave tiles of 3 column tiles x 16 rows
-    // balance these two GEMMs on 1024 SIMDs at config 2 (972 waves); larger batches take 32-row tiles (gemm()).
-    const int r16 = f32 ? 3 : 0;
-    if (int e = gemm(pl->h, HP, H, pgather ? pl->P : gather ? pl->U : pl->agg, HP, H, Nl.w3_Bp, Nl.b3, nullptr, 0, pl->t1, HP, M, NT, HP,
-                     MCG_ACT_SILU, s, lp ? Nl.w3_Bp16 : nullptr, x6g ? Nl.w3_Bp16x3 : nullptr, nullptr, (gather && !pgather) ? 3 : r16, gather,
-                     pgather ? pl->pspan : pl->units().max_span, m)) return e;
-    if (int e = gemm(pl->t1, HP, H, nullptr, 0, 0, Nl.w4_Bp, Nl.b4, pl->h, HP, pl->h2, HP, M, NT, HP, MCG_ACT_NONE, s,
-                     lp ? Nl.w4_Bp16 : nullptr, x6g ? Nl.w4_Bp16x3 : nullptr, nullptr, r16, nullptr, 2, m)) return e;
+    if (int e = launch_gemm(m, r.node, g, Nl.w3_Bp, Nl.w3_Bp16, Nl.w3_Bp16x3, s)) return e;
+    g = McgGemmArgs{};
+    g.A1 = pl->t1; g.lda1 = HP; g.K1 = H; g.bias = Nl.b4; g.resid = pl->h; g.ldr = HP;
+    g.C = pl->h2; g.ldc = HP; g.M = M; g.n_tiles = NT; g.n_store = HP; g.act = MCG_ACT_NONE;
+    if (int e = launch_gemm(m, r.node, g, Nl.w4_Bp, Nl.w4_Bp16, Nl.w4_Bp16x3, s)) return e;
     std::swap(pl->h, pl->h2);
     return MCG_OK;
 }
 
 int run_equiv(const mcg_egnn* m, mcg_plan* pl, int block, hipStream_t s) {
+    const Route r = route(m, pl, false);
     const EdgeLayer& E = m->equiv[block];
-    const int M = pl->M;
-    const bool wgc = edge_wgc(m, pl);
-    if (pl->pab_ready) {
-        pl->pab_ready = false;                                   // (came out of gcl_1's fused node launch)
-    } else if (int e = gemm(pl->h, HP, H, nullptr, 0, 0, E.pab_Bp, E.pab_bias, nullptr, 0, pl->pab, 2 * HP, M, 2 * NT, 2 * HP,
-                            MCG_ACT_NONE, s, m->bf16 ? E.pab_Bp16 : nullptr, (m->x6 && m->x6_gemm) ? E.pab_Bp16x3 : nullptr, nullptr,
-                            pab_rows16(M), nullptr, 2, m, m->bf16 && pl->MT == 4 && MCG_PAB_BLOCKED)) return e;
-    if (int e = run_edge(pl, E, true, pl->Px, s, m->bf16, m->x6, wgc)) return e;
-    if (wgc) {
-        pl->x_pending = true;          // applied by the next launch that can carry it (next block's first GEMM / k_output)
-        pl->pending_u = pl->Ux; pl->pending_slots = pl->units().node_slots;
-        return MCG_OK;
+    if (int e = run_pab(m, pl, r, E, s)) return e;
+    if (int e = run_edge(pl, r, E, true, pl->Px, s)) return e;
+    switch (r.coord) {
+        case CoordUpdate::PendingU: pl->x_pending = true; pl->pending_u = pl->Ux; pl->pending_slots = pl->units().node_slots; break;
+        case CoordUpdate::PendingP: pl->x_pending = true; pl->pending_u = pl->Px; pl->pending_slots = pl->pslots4; break;
+        case CoordUpdate::Kernel:
+            hipLaunchKernelGGL(k_coord_update_t, dim3((pl->M * 4 + 255) / 256), dim3(256), 0, s, pl->Px, pl->node_slots, pl->M, pl->x);
+            MCG_HIP(hipGetLastError());
+            break;
     }
-    if (m->bf16 && pl->pslots4 && pl->pspan <= 4) {     // bf16 mode: the same, on the per-unit partial sums
-        pl->x_pending = true;
-        pl->pending_u = pl->Px; pl->pending_slots = pl->pslots4;
-        return MCG_OK;
-    }
-    const int threads = M * 4;
-    hipLaunchKernelGGL(k_coord_update_t, dim3((threads + 255) / 256), dim3(256), 0, s, pl->Px, pl->node_slots, M, pl->x);
-    MCG_HIP(hipGetLastError());
     return MCG_OK;
 }
 
@@ -525,8 +547,8 @@ int mcg_bench_edge(const mcg_egnn* m, mcg_plan* pl, int layer, int equiv, int it
     if (!m || !pl || iters < 1 || layer < 0 || layer >= (equiv ? m->n_blocks : 2 * m->n_blocks)) return MCG_ERR_ARG;
     mcg_plan_mark_guard done{pl, (hipStream_t)stream};
     for (int i = 0; i < iters; ++i)
-        if (int e = run_edge(pl, equiv ? m->equiv[layer] : m->gcl_edge[layer], equiv != 0, equiv ? pl->Px : pl->P,
-                             (hipStream_t)stream, m->bf16, m->x6, edge_wgc(m, pl))) return e;
+        if (int e = run_edge(pl, route(m, pl, false), equiv ? m->equiv[layer] : m->gcl_edge[layer], equiv != 0,
+                             equiv ? pl->Px : pl->P, (hipStream_t)stream)) return e;
     return MCG_OK;
 }
 

@@ -4,6 +4,7 @@
 //   mcg_egnn_plan.hip    device half of a plan: uploads, workspace, molecule ranges / streams
 //   mcg_edge_exact.hip   exact-fp32 fused edge-MLP kernels (four-tile / quarter-tile units, k_edge_ns)
 //   mcg_edge_bf16.hip    bf16-operand and f32x6 split-operand edge kernels
+//   mcg_gemm.hip         node GEMM kernels, the fused node kernel and their launchers (declared in mcg_gemm.h)
 //   mcg_egnn_api.hip     one denoiser call: embedding, 9 blocks (node GEMMs + edge kernels), output head, HIP graph
 //
 // Data layout in HBM (all fp32):

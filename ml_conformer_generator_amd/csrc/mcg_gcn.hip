@@ -1,6 +1,6 @@
 // AdjMatSeer GCN adjacency pass (reference adj_mat_seer.py:104-165) for gfx950:
 //   GraphConv(x) = L (x W^T + b),  L = D^-1/2 A D^-1/2  -> the A.X.W pass.
-// Linear layers run on the fp32 MFMA row-tile GEMM (mcg_gemm.h); the 42x42 propagation
+// Linear layers run on the fp32 MFMA row-tile GEMM (mcg_gemm.hip); the 42x42 propagation
 // L.(.) + ReLU is a separate streaming kernel with L staged in LDS.
 #include "mcg_gemm.h"
 #include "mcg_api_internal.h"
@@ -237,7 +237,7 @@ int lin(const Lin& L, const float* A, int lda, float* C, int ldc, int M, int n_s
     a.A1 = A; a.lda1 = lda; a.K1 = L.K; a.A2 = nullptr; a.lda2 = 0; a.K2 = 0; a.Bp = L.Bp; a.bias = L.bias;
     a.resid = nullptr; a.ldr = 0; a.C = C; a.ldc = ldc; a.M = M; a.n_tiles = L.n_tiles; a.n_store = n_store;
     a.act = MCG_ACT_NONE;
-    MCG_HIP(mcg_gemm_launch(a, s));
+    MCG_HIP(mcg_gemm_launch(a, 0, s));
     return MCG_OK;
 }
 

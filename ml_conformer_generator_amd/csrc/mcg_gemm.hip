@@ -1,4 +1,14 @@
-// bf16 mode, large batches: the node phase of ONE GCL layer in ONE launch (round 6).
+// The node / GCN GEMM kernels (mcg_gemm_kernels.h) and the fused node kernel, each compiled once, and their launchers: the
+// mapping from runtime shape to template instantiation.
+#include "mcg_gemm_kernels.h"
+
+// Launch-shape counters (measurement / test hook, mcg_debug_gemm_launches): how many node / GCN GEMM launches were ISSUED
+// (plain or into a graph capture) per kernel family and wave-tile width since the last reset.
+// [family 0: 32-row fp32, 1: 32-row bf16 (slot 6: fused node kernel, 7: LDS-staged kernel), 2: 16-row-tile fp32, 3: split-operand][rn 0..7]
+extern "C" void mcg_count_gemm_launch(int family, int rn);
+
+// ---------------------------------------------------------------------------------------------
+// bf16 mode, large batches: the node phase of ONE GCL layer in ONE launch (round 6, mcg_node_fused_bf16_kernel).
 //
 // The node MLP of a GCL is row-local (egnn.py:53-68):  h' = h + W4 SiLU(W3 [h | agg] + b3) + b4,  and so is the first edge-MLP
 // layer of the NEXT layer, factorised per node:  Pab' = h' [Wa | Wb] + (b1 | 0).  Until round 5 these were three
@@ -21,41 +31,20 @@
 // element are those of the three launches: `h'` and `Pab'` are BIT-IDENTICAL to the three-launch path
 // (tests/test_hip_parity.py::test_bf16_mode_gathers_partial_sums_in_the_node_gemm).  56 KiB of LDS like the kernel it is made of;
 // 216 workgroups at 6 895 atoms are one partial pass over the chip either way.
-#pragma once
-#include "mcg_gemm.h"
-
-struct McgNodeFusedArgs {
-    const float* h; int ldh;                    // [M][ldh] fp32, K = 420 real columns
-    const float* P; int ldp;                    // per-unit partial sums (NOT divided by 100) or a materialised aggregate
-    const int4* a2_rows; int a2_nsum;           // the atom's partial rows (GATHER 2 / 4)
-    const uint16_t* w3; const float* b3;        // B-pack16 of W3: [28 k-blocks][27 tiles][64][8]
-    const uint16_t* w4; const float* b4;        // [14][27][64][8]
-    float* h_out; int ldo;                      // h' (fp32)
-    const uint16_t* wab; const float* bab;      // next layer's first edge layer: [14][54][64][8], bias [864] (b1 | 0)
-    float* pab; int ldpab; int pab_blocked;     // Pab' in the edge kernel's layout
-    int M;
-};
 
 constexpr int MCG_NF_K = 420;
 constexpr int MCG_NF_B1 = 14;                                           // k-blocks of 32 per 420-wide segment
-constexpr int MCG_NF_MIN_ROWBLOCKS = 32;                                // automatic choice: from 32 row blocks (1 024 atoms) on
 
 template <int GATHER>
 __global__ __launch_bounds__(MCG_LDSG_THREADS) void mcg_node_fused_bf16_kernel(McgNodeFusedArgs p) {
     __shared__ bf16x8 sA[2 * MCG_NF_B1 * 2 * 64];                       // [28 k-blocks][2 row tiles][64 lanes] x 16 B = 56 KiB
     bf16x8* const sH = sA;                                              // blocks 0..13: h, later SiLU(hidden)
     bf16x8* const sG = sA + MCG_NF_B1 * 2 * 64;                         // blocks 14..27: agg, later h'
-#ifndef MCG_NF_RING
-#define MCG_NF_RING 3
-#endif
-#ifndef MCG_NF_OVERLAP2
-#define MCG_NF_OVERLAP2 1
-#endif
-    constexpr int RN = MCG_LDSG_RN, RING = MCG_NF_RING, B1 = MCG_NF_B1, NTL = 27;
+    constexpr int RN = MCG_LDSG_RN, RING = 3, B1 = MCG_NF_B1, NTL = 27;
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
     const int g = lane >> 4, c = lane & 15;
-    const int wg = MCG_GEMM_BLOCK(blockIdx.x, (int)gridDim.x);
+    const int wg = mcg_xcd_remap(blockIdx.x, (int)gridDim.x);
     const int row0 = wg * 32;
     const int nt0 = wid * RN;                                            // this wave's three column tiles of a 27-tile output
 
@@ -142,7 +131,7 @@ __global__ __launch_bounds__(MCG_LDSG_THREADS) void mcg_node_fused_bf16_kernel(M
             park_quarter(sA, B1 + kb, i, v, 32 * kb + 4 * piece);
         }
     };
-    constexpr bool OVERLAP2 = GATHER <= 2 && MCG_NF_OVERLAP2;
+    constexpr bool OVERLAP2 = GATHER <= 2;
     if constexpr (OVERLAP2) {
 #pragma unroll
         for (int j = 0; j < S2P; ++j) seg2_issue(j);
@@ -286,9 +275,155 @@ __global__ __launch_bounds__(MCG_LDSG_THREADS) void mcg_node_fused_bf16_kernel(M
     }
 }
 
+// ---------------------------------------------------------------------------------------------- launchers
+namespace {
+
+// workgroups of `threads` threads behind the GEMM's own that run the coordinate-update side job (none without one)
+unsigned side_blocks(const McgGemmArgs& a, int threads) { return a.side_x ? (unsigned)((a.side_M * 4 + threads - 1) / threads) : 0u; }
+
+// rows of A2 summed per row of segment 2 (0: plain rows)
+int gather_rows(const McgGemmArgs& a) { return (a.a2_rows != nullptr && a.K2 > 0) ? (a.a2_nsum > 2 ? 4 : 2) : 0; }
+
+template <int RN, int MR, int RING>
+void launch16(const McgGemmArgs& a, int gather, dim3 grid, hipStream_t s) {
+    switch (gather) {
+        case 4: hipLaunchKernelGGL((mcg_gemm16_kernel<RN, 4, MR, RING>), grid, dim3(256), 0, s, a); break;
+        case 3: hipLaunchKernelGGL((mcg_gemm16_kernel<RN, 3, MR, RING>), grid, dim3(256), 0, s, a); break;
+        case 2: hipLaunchKernelGGL((mcg_gemm16_kernel<RN, 2, MR, RING>), grid, dim3(256), 0, s, a); break;
+        default: hipLaunchKernelGGL((mcg_gemm16_kernel<RN, 0, MR, RING>), grid, dim3(256), 0, s, a); break;
+    }
+}
+
+template <int RN>
+void launch_bf16(const McgGemmArgs& a, dim3 grid, hipStream_t s) {
+    switch (gather_rows(a)) {
+        case 4: hipLaunchKernelGGL((mcg_gemm_bf16_kernel<RN, 4>), grid, dim3(256), 0, s, a); break;
+        case 2: hipLaunchKernelGGL((mcg_gemm_bf16_kernel<RN, 2>), grid, dim3(256), 0, s, a); break;
+        default: hipLaunchKernelGGL((mcg_gemm_bf16_kernel<RN, 0>), grid, dim3(256), 0, s, a); break;
+    }
+}
+
+// (ring depth 3: 4 / 6 stages measured no gain / spills at the 256-ragged shape - the K loop is not what these launches wait for)
+template <int GATHER, bool SEG2>
+void launch_lds(const McgGemmArgs& a, dim3 grid, hipStream_t s) {
+    if (a.resid) hipLaunchKernelGGL((mcg_gemm_bf16_lds_kernel<GATHER, true, SEG2, 3>), grid, dim3(MCG_LDSG_THREADS), 0, s, a);
+    else hipLaunchKernelGGL((mcg_gemm_bf16_lds_kernel<GATHER, false, SEG2, 3>), grid, dim3(MCG_LDSG_THREADS), 0, s, a);
+}
+
+// bf16 kernel choice (MCG_OPT_GEMM_BF16_LDS 0): the LDS-staged kernel from MCG_LDSG_MIN_ROWBLOCKS row blocks on.
+// measured per denoiser call, 32-row kernel -> LDS-staged kernel (ms; 27-atom molecules, profiles/round5_probes.txt):
+// 64 molecules (54 row blocks) 1.80 -> 1.89, 96 (81) 2.79 -> 2.42, 128 (108) 2.83 -> 2.72, 160 3.60 -> 3.19, 192 4.09 -> 3.70,
+// 256 ragged (216) 5.16 -> 4.60
+constexpr int MCG_LDSG_MIN_ROWBLOCKS = 80;
+
+bool bf16_lds_fits(const McgGemmArgs& a) {
+    const int b2 = a.K2 > 0 ? mcg_kblocks16(a.K2) : 0;
+    const int blocks = (a.K1 > 0 ? mcg_kblocks16(a.K1) : 0) + b2;
+    // (the second segment is parked by 9 waves x S2P blocks: a longer one would leave fragments unparked and the K loop
+    //  would read uninitialised LDS - no EGNN shape comes near (b2 = 14), but "forced on" must stay within what is parked)
+    return blocks >= 1 && blocks <= MCG_LDSG_MAX_BLOCKS && b2 <= MCG_LDSG_S2P * MCG_LDSG_WAVES && a.n_tiles % MCG_LDSG_RN == 0;
+}
+
+}  // namespace
+
+// Wave tile width RN in {1,2,3} from a measured cost model (tools/native/gemm_bench.hip, MI355X; us of loop time per wave and
+// per 420 of K): with at most one wave per SIMD a wave costs u1[RN]; with many waves per SIMD the SIMD retires one wave per
+// uinf[RN] (the 3-wide tile degrades most when waves share a SIMD).  cost = u1 for r <= 1, else max(ceil(r) * u1, r * uinf),
+// r = waves / 1024 SIMDs.  It reproduces the measured-best width for M = 1.7k .. 13k on all three node-GEMM shapes (the old
+// "rounds x RN" rule picked RN = 3 at config 3: 80 us instead of 62 us for the Pab GEMM).
+hipError_t mcg_gemm_launch(McgGemmArgs a, int rn_override, hipStream_t s) {
+    if (a.M <= 0) return hipSuccess;
+    const int rowblocks = (a.M + 31) / 32;
+    static const double u1[4] = {0, 3.4, 5.2, 9.0}, uinf[4] = {0, 4.8, 8.0, 12.5};
+    int rn = 1;
+    double best = -1;
+    for (int cand = 1; cand <= 3; ++cand) {
+        const double r = (double)rowblocks * ((a.n_tiles + cand - 1) / cand) / 1024.0;
+        const double up = (double)(long)(r + 0.999999);
+        const double c1 = up * u1[cand], c2 = r * uinf[cand];
+        const double cost = (r <= 1.0 || c1 > c2) ? c1 : c2;      // one wave per SIMD or less: no sharing penalty
+        if (best < 0 || cost < best) { best = cost; rn = cand; }
+    }
+    if (rn_override >= 1 && rn_override <= 3) rn = rn_override;
+    a.gemm_blocks = (int)(((long)rowblocks * ((a.n_tiles + rn - 1) / rn) + 3) / 4);
+    const dim3 grid((unsigned)a.gemm_blocks + side_blocks(a, 256));
+    mcg_count_gemm_launch(0, rn);
+    if (rn == 3) hipLaunchKernelGGL(mcg_gemm_kernel<3>, grid, dim3(256), 0, s, a);
+    else if (rn == 2) hipLaunchKernelGGL(mcg_gemm_kernel<2>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(mcg_gemm_kernel<1>, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// rn in {1, 2, 3, 6} column tiles and mr in {1, 2} row tiles of 16 per wave.
+// `deep` (small batches, rn = 1 or 2, mr = 1): an operand ring of 8 / 6 k-groups instead of 3.  With fewer waves than SIMDs a
+// launch is ONE latency-bound chain per wave - a k-group is 4 x RN MFMAs (53 ns at RN = 1) against an L2 round trip of ~0.6 us
+// shared by the groups in flight: three in flight cost ~200 ns per group, eight ~75.  Same k order: bit-identical results.
+hipError_t mcg_gemm16_launch(McgGemmArgs a, int rn, int mr, bool deep, hipStream_t s) {
+    if (a.M <= 0) return hipSuccess;
+    // the EFFECTIVE tile shape - the one an instantiation exists for - sizes the grid: a width the kernel was not built
+    // with would leave the kernel's wave_cols and the grid disagreeing (output columns silently unwritten)
+    mr = mr == 2 ? 2 : 1;
+    rn = mr == 2 ? (rn == 3 ? 3 : 2) : (rn == 6 || rn == 3 || rn == 1) ? rn : 2;
+    const long waves = (long)((a.M + 16 * mr - 1) / (16 * mr)) * ((a.n_tiles + rn - 1) / rn);
+    a.gemm_blocks = (int)((waves + 3) / 4);
+    mcg_count_gemm_launch(2, rn);
+    const dim3 grid((unsigned)a.gemm_blocks + side_blocks(a, 256));
+    const int gather = (a.a2_rows != nullptr && a.K2 > 0) ? (a.a2_nsum >= 4 ? 4 : a.a2_nsum == 3 ? 3 : 2) : 0;
+    if (mr == 2) { if (rn == 3) launch16<3, 2, 3>(a, gather, grid, s); else launch16<2, 2, 3>(a, gather, grid, s); }
+    else if (rn == 6) launch16<6, 1, 3>(a, gather, grid, s);
+    else if (rn == 3) launch16<3, 1, 3>(a, gather, grid, s);
+    else if (rn == 1) { if (deep) launch16<1, 1, 8>(a, gather, grid, s); else launch16<1, 1, 3>(a, gather, grid, s); }
+    else { if (deep) launch16<2, 1, 6>(a, gather, grid, s); else launch16<2, 1, 3>(a, gather, grid, s); }
+    return hipGetLastError();
+}
+
+hipError_t mcg_gemm_bf16_launch(McgGemmArgs a, int rn_override, int lds, hipStream_t s) {
+    if (a.M <= 0) return hipSuccess;
+    const int rowblocks = (a.M + 31) / 32;
+    if (lds != 1 && bf16_lds_fits(a) && (lds == 2 || rowblocks >= MCG_LDSG_MIN_ROWBLOCKS)) {
+        a.gemm_blocks = rowblocks * ((a.n_tiles + MCG_LDSG_TILES - 1) / MCG_LDSG_TILES);
+        const dim3 grid((unsigned)a.gemm_blocks + side_blocks(a, MCG_LDSG_THREADS));
+        mcg_count_gemm_launch(1, 7);             // family 1 (bf16), slot 7 = the LDS-staged 9-wave kernel
+        switch (gather_rows(a)) {
+            case 4: launch_lds<4, true>(a, grid, s); break;
+            case 2: launch_lds<2, true>(a, grid, s); break;
+            default: if (a.K2 > 0) launch_lds<0, true>(a, grid, s); else launch_lds<0, false>(a, grid, s); break;
+        }
+        return hipGetLastError();
+    }
+    // minimise (rounds of 256 four-wave workgroups) x (work per wave ~ RN); ties go to the wider tile
+    int rn = 1;
+    long best = -1;
+    for (int cand = 1; cand <= 3; ++cand) {
+        const long wgs = ((long)rowblocks * ((a.n_tiles + cand - 1) / cand) + 3) / 4;
+        const long cost = ((wgs + 255) / 256) * cand;
+        if (best < 0 || cost <= best) { best = cost; rn = cand; }
+    }
+    if (rn_override >= 1 && rn_override <= 3) rn = rn_override;
+    a.gemm_blocks = (int)(((long)rowblocks * ((a.n_tiles + rn - 1) / rn) + 3) / 4);
+    const dim3 grid((unsigned)a.gemm_blocks + side_blocks(a, 256));
+    mcg_count_gemm_launch(1, rn);
+    if (rn == 3) launch_bf16<3>(a, grid, s); else if (rn == 2) launch_bf16<2>(a, grid, s); else launch_bf16<1>(a, grid, s);
+    return hipGetLastError();
+}
+
+hipError_t mcg_gemm_x6_launch(const McgGemmArgs& a, int rn_override, hipStream_t s) {
+    if (a.M <= 0) return hipSuccess;
+    const int rowblocks = (a.M + 31) / 32;
+    int rn = a.M > 4096 ? 2 : 1;          // measured: RN = 1 at config 2 (3.43 vs 3.66 ms per call for RN = 3), RN = 2 at config 3
+    if (rn_override >= 1 && rn_override <= 3) rn = rn_override;
+    const int wave_cols = (a.n_tiles + rn - 1) / rn;
+    const dim3 grid((unsigned)(rowblocks * ((wave_cols + 3) / 4)));
+    mcg_count_gemm_launch(3, rn);
+    if (rn == 3) hipLaunchKernelGGL(mcg_gemm_x6_kernel<3>, grid, dim3(256), 0, s, a);
+    else if (rn == 2) hipLaunchKernelGGL(mcg_gemm_x6_kernel<2>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(mcg_gemm_x6_kernel<1>, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 // (only the two-row gather is instantiated: an atom of <= 42 atoms' molecule owns <= 41 edge rows, i.e. at most two 64-row units;
-//  plans whose atoms span more take the three-launch path - run_gcl)
-static inline hipError_t mcg_node_fused_launch(const McgNodeFusedArgs& a, hipStream_t s) {
+//  plans whose atoms span more take the three-launch path - route() in mcg_egnn_api.hip)
+hipError_t mcg_node_fused_launch(const McgNodeFusedArgs& a, hipStream_t s) {
     if (a.M <= 0) return hipSuccess;
     if (!a.a2_rows || a.a2_nsum > 2) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((a.M + 31) / 32));

@@ -21,7 +21,7 @@ extern "C" const char* mcg_last_error(void) { return g_err; }
 
 extern "C" int mcg_abi_version(void) { return 4; }      // 2: mcg_plan_opts / mcg_plan_create_ex / mcg_egnn_set_option; 3: mcg_handoff_ex; 4: cov_factor is a double (fp64 hand-off distances)
 
-// launch-shape counters of the GEMM launchers (mcg_gemm.h); relaxed atomics: a measurement hook, not a synchronisation point
+// launch-shape counters of the GEMM launchers (mcg_gemm.hip); relaxed atomics: a measurement hook, not a synchronisation point
 static std::atomic<int64_t> g_gemm_launches[4][8];
 extern "C" void mcg_count_gemm_launch(int family, int rn) {
     if (family >= 0 && family < 4) g_gemm_launches[family][rn & 7].fetch_add(1, std::memory_order_relaxed);

@@ -2124,7 +2124,7 @@ def test_bf16_mode_gathers_partial_sums_in_the_node_gemm(edm_sd):
         if n_ranges == 1:
             assert int(c[1][7]) == 63, c                  # ~4 400 atoms in one range: the automatic choice is the LDS kernel
         # round 6: the node phase of a GCL layer as ONE launch (W3 -> SiLU -> W4 -> + h -> the next edge layer's first-layer
-        # projections, mcg_node_fused.h): forced, then the automatic choice - 18 fused launches + one first-layer GEMM per block
+        # projections, mcg_gemm.hip): forced, then the automatic choice - 18 fused launches + one first-layer GEMM per block
         # (it carries the coordinate update) instead of 63 GEMM launches, and not a bit of difference
         for fused in (2, 0):
             _lib.check(L.mcg_egnn_set_option(d.handle, _lib.OPT_NODE_FUSED, fused), "mcg_egnn_set_option")

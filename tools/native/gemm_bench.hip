@@ -1,7 +1,7 @@
-// Measurement tool: the three node-GEMM shapes of one GCL layer (mcg_gemm.h), timed the way the denoiser
+// Measurement tool: the three node-GEMM shapes of one GCL layer (mcg_gemm_kernels.h), timed the way the denoiser
 // runs them - a different weight set every launch (63 sets per call: L2-cold, Infinity-Cache-warm) and the
 // A operand freshly written by the previous launch.   ./gemm_bench [M]
-#include "../../ml_conformer_generator_amd/csrc/mcg_gemm.h"
+#include "../../ml_conformer_generator_amd/csrc/mcg_gemm_kernels.h"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -87,7 +87,7 @@ int main(int argc, char** argv) {
                         for (int i = 0; i < n; ++i) {
                             McgGemmArgs g = args(which, i % SETS);
                             if (gather) { g.a2_rows = slots; g.a2_nsum = gather; }
-                            mcg_gemm16_launch(g, rn, s, MR16);
+                            mcg_gemm16_launch(g, rn, MR16, false, s);
                         }
                     };
                     run(SETS);
