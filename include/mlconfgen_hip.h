@@ -215,13 +215,25 @@ int mcg_handoff(const float* x, const float* h, const int32_t* n_nodes_dev, int 
 int mcg_handoff_ex(const float* x, const float* h, const int32_t* n_nodes_dev, int B, int N, double cov_factor,
                    const int32_t* order, const uint8_t* conn_in, int64_t* elements, float* dist_mat, float* adj_mat,
                    float* x_out, int32_t* bad_order_flag, void* stream);
+/* The same with the caller's atom decoder (`MLConformerGenerator(atom_decoder=)`): the reference writes
+ * atom_decoder[argmax(h)] into the XYZ block of `samples_to_rdkit_mol` (utils/mol_utils.py:41-45), and the atomic number
+ * RDKit reads from it is what `MolGraph.elements_vector` embeds and what DetermineConnectivity works from.
+ *   class_z[8] int32 (HOST; NULL = the default decoder C N O F P S Cl Br, i.e. mcg_handoff_ex): atomic number of each atom
+ *                class.  Every entry must be an element the library knows - B C N O F Si P S Cl As Se Br, each Z < 36 (the
+ *                GCN's element embedding) - else MCG_ERR_ARG before any device work.  Two classes may share an element.
+ * elements carries these atomic numbers; the covalent-radius rule (conn_in NULL) uses each element's single-bond radius
+ * (Cordero 2008). */
+int mcg_handoff_elements(const float* x, const float* h, const int32_t* n_nodes_dev, int B, int N, double cov_factor,
+                         const int32_t* order, const uint8_t* conn_in, int64_t* elements, float* dist_mat, float* adj_mat,
+                         float* x_out, int32_t* bad_order_flag, const int32_t* class_z, void* stream);
 
 /* Bond write-back + validity pre-filter behind the GCN (replaces the tensor half of `redefine_bonds`,
  * utils/mol_utils.py:197-223, and stands in for `standardize_mol(...) is not None`, conformer_generator.py:362-366 /
  * utils/standardizer.py:83-111, which is RDKit sanitisation + MMFF and cannot run without RDKit):
  * bond[B,42,42] int8 = argmax bond classes from mcg_gcn_forward; bond_sym[B,42,42] int8 = its strict lower triangle
  * mirrored, zero outside the molecule's n x n block; valid[B] uint8 = 1 when no atom exceeds its maximum valence and
- * the bond graph is one connected fragment (a labelled PROXY, not RDKit's gate). */
+ * the bond graph is one connected fragment (a labelled PROXY, not RDKit's gate).  Maximum valences by atomic number:
+ * B 3, C 4, N 4, O 2, F 1, Si 4, P 5, S 6, Cl 1, As 5, Se 6, Br 1; any other element 0. */
 int mcg_bond_writeback(const int8_t* bond, const int64_t* elements, const int32_t* n_nodes_dev, int B, int8_t* bond_sym,
                        uint8_t* valid, void* stream);
 /* Inertial fragment matching, the tensor work between its two sampler runs (`inverse_coord_transform`,

@@ -21,6 +21,26 @@ ATOM_DECODER = {0: "C", 1: "N", 2: "O", 3: "F", 4: "P", 5: "S", 6: "Cl", 7: "Br"
 ATOMIC_NUMBERS = (6, 7, 8, 9, 15, 16, 17, 35)
 PERMITTED_ELEMENTS = ATOMIC_NUMBERS
 
+# Elements an `atom_decoder` may name (heavy main-group atoms up to Z = 35; `elements.class_z_from_decoder`):
+# Z -> (symbol, single-bond covalent radius in Angstrom (Cordero et al. 2008, Dalton Trans. 2832), maximum valence).
+# The radius feeds the covalent-radius connectivity substitute of the hand-off, the valence the validity proxy behind the
+# GCN - both labelled substitutes for RDKit; the non-default rows are literature values, not pinned against RDKit.
+# The device keeps the same table by Z: csrc/mcg_elements.h.
+ELEMENTS = {
+    5: ("B", 0.84, 3),
+    6: ("C", 0.76, 4),
+    7: ("N", 0.71, 4),       # N may carry a charged fourth bond
+    8: ("O", 0.66, 2),
+    9: ("F", 0.57, 1),
+    14: ("Si", 1.11, 4),
+    15: ("P", 1.07, 5),
+    16: ("S", 1.05, 6),
+    17: ("Cl", 1.02, 1),
+    33: ("As", 1.19, 5),
+    34: ("Se", 1.20, 6),
+    35: ("Br", 1.20, 1),
+}
+
 # generated molecule size range (heavy atoms)  (config.py:31-32)
 MIN_N_NODES = 15
 MAX_N_NODES = 39

@@ -45,6 +45,7 @@ from .adj_mat_seer import AdjMatSeer
 from .config import (ATOM_DECODER, CONTEXT_NORMS, DIMENSION, MAX_N_NODES, MIN_N_NODES, NOISE_PRECISION,
                      NUM_BOND_TYPES)
 from .egnn import EGNNDynamics
+from .elements import class_z_from_decoder
 from .equivariant_diffusion import EquivariantDiffusion, PredefinedNoiseSchedule
 from . import distributed as mcg_dist
 from . import host_pool
@@ -100,7 +101,21 @@ class MLConformerGenerator(torch.nn.Module):
                  adj_mat_seer_weights: Union[str, dict] = "./adj_mat_seer_chembl_15_39.pt",
                  compute_dtype: str = "f32", atom_order_provider="auto", n_host_workers: Optional[int] = None,
                  finisher="auto", task_timeout_s: Optional[float] = host_pool.DEFAULT_TASK_TIMEOUT_S, cpu_affinity=None):
+        """The reference's constructor (conformer_generator.py:29-113) plus the options of this package.
+
+        `atom_decoder` {class index 0..7: element symbol} decides which element each generated atom becomes, as in the
+        reference (`samples_to_rdkit_mol` writes atom_decoder[argmax(h)], utils/mol_utils.py:41-45): the atomic numbers the
+        GCN embeds, the covalent-radius connectivity, the validity proxy, an atom-order provider's input and the returned
+        molecules all follow it.  Any element of `config.ELEMENTS` (B C N O F Si P S Cl As Se Br) may be named, two classes
+        may name the same one.  Refused with ValueError, here, before any device work: other keys than exactly 0..7,
+        hydrogen (every count of this API is heavy atoms), an unknown symbol and Z >= 36 (outside the GCN's element
+        embedding, where the reference fails later with an IndexError).  The radii and valences of the non-default
+        elements feed only the labelled substitutes (covalent-radius connectivity, validity proxy); they are literature
+        values, not pinned against RDKit.  A `fixed_fragment` keeps the reference's FIXED class encoding
+        (`elements_decoder` of sorted PERMITTED_ELEMENTS, utils/molgraph.py:10,236-252), not `atom_decoder` - the
+        reference's own behaviour.  `dimension` and `num_bond_types` other than the defaults are refused."""
         super().__init__()
+        class_z = class_z_from_decoder(atom_decoder)        # a bad decoder fails before anything else is set up
         _lib.lib()       # fail loudly if the HIP library is not built
         device = torch.device("cuda:0" if device is None else device)
         if device.type != "cuda":
@@ -120,6 +135,7 @@ class MLConformerGenerator(torch.nn.Module):
         self.dimension = dimension
         self.context_norms = {k: torch.tensor(v) for k, v in context_norms.items()}
         self.atom_decoder = atom_decoder
+        self.class_z = class_z           # atomic number of each atom class: what the device hand-off decodes with
         self.min_n_nodes, self.max_n_nodes = min_n_nodes, max_n_nodes
 
         net_dynamics = EGNNDynamics(in_node_nf=9, context_node_nf=3, hidden_nf=420, device=device)
@@ -215,7 +231,7 @@ class MLConformerGenerator(torch.nn.Module):
                                            fixed_fragment, inertial_fragment_matching, blend_power,
                                            ifm_diffusion_level)
         n_nodes = node_mask.sum(1).reshape(-1).to(torch.long)
-        el, _, _ = prepare_adj_mat_seer_input_hip(x, h, n_nodes, self.dimension)
+        el, _, _ = prepare_adj_mat_seer_input_hip(x, h, n_nodes, self.dimension, class_z=self.class_z)
         no_bonds = torch.zeros(x.shape[0], self.dimension, self.dimension, dtype=torch.int8, device=x.device)
         mols = assemble_molecules(x, el, no_bonds, n_nodes)
         for m in mols:
@@ -297,7 +313,8 @@ class MLConformerGenerator(torch.nn.Module):
         groups = rdkit_order.launch_groups(n_samples) if staged else [(0, n_samples)]
         t0 = time.perf_counter()
         # host: RDKit's (or the caller's) order + connectivity - every task of the batch goes out now
-        stage = rdkit_order.OrderStage(provider, x, h, n_nodes, executor, groups) if provider is not None else None
+        stage = (rdkit_order.OrderStage(provider, x, h, n_nodes, executor, groups, self.class_z)
+                 if provider is not None else None)
         fin = None
         if finisher is not None:
             from . import rdkit_finish
@@ -310,7 +327,7 @@ class MLConformerGenerator(torch.nn.Module):
             ng = n_nodes[lo:hi]
             # atoms, distances, connectivity AND coordinates come out in the order the GCN sees (canonicalised_samples)
             el, dm, am, x_out = prepare_adj_mat_seer_input_hip(x[lo:hi], h[lo:hi], ng, D, order=order, connectivity=conn,
-                                                               with_coords=True)
+                                                               with_coords=True, class_z=self.class_z)
             bond = self.adj_mat_seer.bond_orders(el, dm, am)
             sym, valid = bond_writeback_hip(bond, el, ng)
             if built is not None and not all(built):          # `MolFromXYZBlock` returned None: the reference drops it

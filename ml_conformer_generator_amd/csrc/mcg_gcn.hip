@@ -4,6 +4,7 @@
 // L.(.) + ReLU is a separate streaming kernel with L staged in LDS.
 #include "mcg_gemm.h"
 #include "mcg_api_internal.h"
+#include "mcg_elements.h"
 
 #include <vector>
 
@@ -118,8 +119,13 @@ __global__ __launch_bounds__(256) void k_symm(const float* __restrict__ res, flo
 // returns for the decimal k * 1e-9.  No FMA contraction anywhere in this arithmetic.
 __device__ __forceinline__ double text_round_trip_9(float v) { return __ddiv_rn(rint(__dmul_rn((double)v, 1e9)), 1e9); }
 
+// single-bond covalent radius by atomic number (mcg_elements.h); the host checks every Z of a class map against it
+__constant__ McgElementTable c_elements = MCG_ELEMENTS;
+
+// `class_z`: atomic number of each of the 8 atom classes - the caller's `atom_decoder` (`samples_to_rdkit_mol` writes
+// atom_decoder[argmax(h)], mol_utils.py:41-45); every entry has a radius in c_elements (checked on the host).
 __global__ __launch_bounds__(256) void k_handoff(const float* __restrict__ x, const float* __restrict__ h,
-                                                  const int* __restrict__ n_nodes, int N, double cov_factor,
+                                                  const int* __restrict__ n_nodes, int N, double cov_factor, McgClassZ class_z,
                                                   const int* __restrict__ order, const uint8_t* __restrict__ conn_in,
                                                   int64_t* __restrict__ elements, float* __restrict__ dist,
                                                   float* __restrict__ adj, float* __restrict__ x_out,
@@ -130,9 +136,6 @@ __global__ __launch_bounds__(256) void k_handoff(const float* __restrict__ x, co
     __shared__ int ssrc[D];
     const int b = blockIdx.x;
     const int n = min(n_nodes[b], min(D, N));
-    // class -> atomic number (config.py:20-29) and single-bond covalent radius (Cordero 2008)
-    const int zt[8] = {6, 7, 8, 9, 15, 16, 17, 35};
-    const double rt[8] = {0.76, 0.71, 0.66, 0.57, 1.07, 1.05, 1.02, 1.20};
     for (int i = threadIdx.x; i < D; i += 256) {
         int z = 0; double r = 0.0; float px = 0.f, py = 0.f, pz = 0.f; int src = i;
         if (i < n) {
@@ -141,10 +144,11 @@ __global__ __launch_bounds__(256) void k_handoff(const float* __restrict__ x, co
                 if (src < 0 || src >= n) { if (bad) atomicExch(bad, 1); src = min(max(src, 0), n - 1); }
             }
             const float* hr = h + ((size_t)b * N + src) * 8;
-            int best = 0; float bv = hr[0];
+            float bv = hr[0];
+            z = class_z.z[0];
 #pragma unroll
-            for (int k = 1; k < 8; ++k) if (hr[k] > bv) { bv = hr[k]; best = k; }    // argmax(one_hot) (mol_utils.py:41)
-            z = zt[best]; r = rt[best];
+            for (int k = 1; k < 8; ++k) if (hr[k] > bv) { bv = hr[k]; z = class_z.z[k]; }    // argmax(one_hot) (mol_utils.py:41)
+            r = c_elements.rcov[z];
             const float* xr = x + ((size_t)b * N + src) * 3;
             px = xr[0]; py = xr[1]; pz = xr[2];
         }
@@ -329,7 +333,34 @@ int mcg_gcn_forward(mcg_gcn* g, const int64_t* elements, const float* dist_mat, 
     return MCG_OK;
 }
 
-// elements[B,42] i64, dist_mat[B,42,42], adj_mat[B,42,42] from sampler outputs x[B,N,3], h[B,N,8] (one-hot)
+// elements[B,42] i64, dist_mat[B,42,42], adj_mat[B,42,42] from sampler outputs x[B,N,3], h[B,N,8] (one-hot), with the
+// atom classes decoded through class_z (host, 8 entries; NULL = the default decoder)
+int mcg_handoff_elements(const float* x, const float* h, const int32_t* n_nodes_dev, int B, int N, double cov_factor,
+                         const int32_t* order, const uint8_t* conn_in, int64_t* elements, float* dist_mat, float* adj_mat,
+                         float* x_out, int32_t* bad_order_flag, const int32_t* class_z, void* stream) {
+    McgClassZ cz = MCG_DEFAULT_CLASS_Z;
+    if (class_z) {
+        for (int k = 0; k < MCG_N_ATOM_CLASSES; ++k) {
+            const int z = class_z[k];
+            if (z < 0 || z >= MCG_N_ELEMENT_Z || MCG_ELEMENTS.rcov[z] == 0.0) {
+                mcg_set_error("mcg_handoff_elements: class_z[%d] = %d is not a supported element (need a covalent radius and "
+                              "Z < %d)", k, z, MCG_N_ELEMENT_Z);
+                return MCG_ERR_ARG;
+            }
+            cz.z[k] = z;
+        }
+    }
+    if (!x || !h || !n_nodes_dev || !elements || !dist_mat || !adj_mat || B < 1 || N < 1) {
+        mcg_set_error("mcg_handoff_elements: bad arguments");
+        return MCG_ERR_ARG;
+    }
+    if (x_out == x) { mcg_set_error("mcg_handoff_elements: x_out may not alias x"); return MCG_ERR_ARG; }
+    hipLaunchKernelGGL(k_handoff, dim3(B), dim3(256), 0, (hipStream_t)stream, x, h, n_nodes_dev, N, cov_factor, cz, order,
+                       conn_in, elements, dist_mat, adj_mat, x_out, bad_order_flag);
+    MCG_HIP(hipGetLastError());
+    return MCG_OK;
+}
+
 int mcg_handoff_ex(const float* x, const float* h, const int32_t* n_nodes_dev, int B, int N, double cov_factor,
                    const int32_t* order, const uint8_t* conn_in, int64_t* elements, float* dist_mat, float* adj_mat,
                    float* x_out, int32_t* bad_order_flag, void* stream) {
@@ -338,10 +369,8 @@ int mcg_handoff_ex(const float* x, const float* h, const int32_t* n_nodes_dev, i
         return MCG_ERR_ARG;
     }
     if (x_out == x) { mcg_set_error("mcg_handoff_ex: x_out may not alias x"); return MCG_ERR_ARG; }
-    hipLaunchKernelGGL(k_handoff, dim3(B), dim3(256), 0, (hipStream_t)stream, x, h, n_nodes_dev, N, cov_factor, order, conn_in,
-                       elements, dist_mat, adj_mat, x_out, bad_order_flag);
-    MCG_HIP(hipGetLastError());
-    return MCG_OK;
+    return mcg_handoff_elements(x, h, n_nodes_dev, B, N, cov_factor, order, conn_in, elements, dist_mat, adj_mat, x_out,
+                                bad_order_flag, nullptr, stream);
 }
 
 int mcg_handoff(const float* x, const float* h, const int32_t* n_nodes_dev, int B, int N, double cov_factor,

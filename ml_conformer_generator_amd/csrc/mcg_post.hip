@@ -6,10 +6,14 @@
 // Byte / index work and a handful of FMAs per atom: latency-bound launches, nothing here is near a roofline.
 #include "mcg_common.h"
 #include "mcg_api_internal.h"
+#include "mcg_elements.h"
 
 namespace {
 
 constexpr int D = 42;             // GCN pad width (utils/config.py:3)
+
+// maximum valence of the validity proxy by atomic number (mcg_elements.h); 0 for every Z outside the table
+__constant__ McgElementTable c_elements = MCG_ELEMENTS;
 
 // One workgroup per molecule.
 //   sym[i][j] = argmax-bond of the STRICT LOWER triangle, mirrored (mol_utils.py:210-211: tril(argmax) with the
@@ -49,8 +53,7 @@ __global__ __launch_bounds__(256) void k_bond_writeback(const int8_t* __restrict
         adj[i] = m;
         if (i < n) {
             const int z = (int)elements[(size_t)b * D + i];
-            // maximum valences of the permitted elements (N may carry a charged fourth bond)
-            const int maxv = z == 6 ? 4 : z == 7 ? 4 : z == 8 ? 2 : z == 9 ? 1 : z == 15 ? 5 : z == 16 ? 6 : z == 17 ? 1 : z == 35 ? 1 : 0;
+            const int maxv = z >= 0 && z < MCG_N_ELEMENT_Z ? c_elements.max_valence[z] : 0;
             if (val2 > 2 * maxv) atomicOr(&over[0], 1);
         }
     }

@@ -4,7 +4,7 @@ The reference goes through RDKit here (`samples_to_rdkit_mol`, `canonicalise`,
 `prepare_adj_mat_seer_input`, `redefine_bonds`, `standardize_mol`;
 mol_utils.py:18-57,110-223, standardizer.py).  The tensor halves (atom decode, distances + I,
 connectivity + I, pad 42, lower-triangle bond write-back) run in two HIP launches
-(`mcg_handoff_ex`, `mcg_bond_writeback`), follow the reference and are checked against
+(`mcg_handoff_elements`, `mcg_bond_writeback`), follow the reference and are checked against
 `oracle/host_oracle.py` and reference-generated fixtures; one D2H copy at the end.
 The two decisions RDKit OWNS in front of the GCN - the canonical-SMILES atom order and the
 1-order connectivity (`canonicalise`, mol_utils.py:110-126) - are INPUTS of the hand-off launch
@@ -14,13 +14,15 @@ parity unpinned against RDKit).  "valid" without RDKit is a valence / connectivi
 """
 from __future__ import annotations
 
+import ctypes
 from typing import List, Optional, Tuple
 
 import torch
 
-from .config import ATOM_DECODER, ATOMIC_NUMBERS, DIMENSION
+from .config import DIMENSION, N_ATOM_CLASSES
+from .elements import Z_TO_SYMBOL
 
-_COV_FACTOR = 1.3          # RDKit DetermineConnectivity's default covFactor (radii: csrc/mcg_gcn.hip k_handoff)
+_COV_FACTOR = 1.3          # RDKit DetermineConnectivity's default covFactor (radii: config.ELEMENTS, csrc/mcg_elements.h)
 
 
 class _HostBatch:
@@ -85,8 +87,8 @@ class GeneratedMolecule:
 
     @property
     def symbols(self) -> List[str]:
-        z2s = {z: ATOM_DECODER[i] for i, z in enumerate(ATOMIC_NUMBERS)}
-        return [z2s[z] for z in self.atomic_numbers]
+        """Element symbols of the atoms (`config.ELEMENTS`: the atomic numbers already follow the generator's decoder)."""
+        return [Z_TO_SYMBOL[z] for z in self.atomic_numbers]
 
     def GetNumAtoms(self) -> int:          # RDKit-like convenience
         return len(self._z) if self._z is not None else int(self._batch.n[self._b])
@@ -150,9 +152,12 @@ def _conn_tensor(conn, n_host: List[int], dimension: int) -> torch.Tensor:
 
 
 def prepare_adj_mat_seer_input_hip(x: torch.Tensor, h: torch.Tensor, n_nodes: torch.Tensor,
-                                   dimension: int = DIMENSION, order=None, connectivity=None, with_coords: bool = False):
+                                   dimension: int = DIMENSION, order=None, connectivity=None, with_coords: bool = False,
+                                   class_z=None):
     """elements[B,42] i64, dist_mat[B,42,42] (+I, zero padded), adj_mat[B,42,42] {0,1} (+I) - the tensors
-    `prepare_adj_mat_seer_input` (mol_utils.py:146-194) builds, by ONE HIP launch (`mcg_handoff_ex`).
+    `prepare_adj_mat_seer_input` (mol_utils.py:146-194) builds, by ONE HIP launch (`mcg_handoff_elements`).
+    `class_z`: atomic number of each of the 8 atom classes (`elements.class_z_from_decoder` of the caller's
+    `atom_decoder`, mol_utils.py:41-45); None = the default decoder.  An unsupported element raises before any launch.
     `order` (per-molecule permutations: position p holds generation atom order[b][p] - the reference's canonical SMILES
     order, `canonicalise` :110-126) and `connectivity` (per-molecule {0,1} matrices in GENERATION order - RDKit's
     `DetermineConnectivity`, :117) are the two RDKit-owned decisions; None = generation order / covalent-radius rule.
@@ -176,9 +181,15 @@ def prepare_adj_mat_seer_input_hip(x: torch.Tensor, h: torch.Tensor, n_nodes: to
             od = _order_tensor(order, n_host, dimension).to(dev)
         if connectivity is not None:
             cd = _conn_tensor(connectivity, n_host, dimension).to(dev)
-    _lib.check(_lib.lib().mcg_handoff_ex(_lib.dptr(x.contiguous()), _lib.dptr(h.to(torch.float32).contiguous()), _lib.dptr(nn),
-                                         B, N, _COV_FACTOR, _lib.dptr(od), _lib.dptr(cd), _lib.dptr(el), _lib.dptr(dm),
-                                         _lib.dptr(am), _lib.dptr(xo), None, _lib.current_stream_ptr(dev)), "mcg_handoff_ex")
+    cz = None
+    if class_z is not None:
+        if len(class_z) != N_ATOM_CLASSES:
+            raise ValueError(f"class_z must hold {N_ATOM_CLASSES} atomic numbers, got {len(class_z)}")
+        cz = (ctypes.c_int32 * N_ATOM_CLASSES)(*[int(z) for z in class_z])
+    _lib.check(_lib.lib().mcg_handoff_elements(_lib.dptr(x.contiguous()), _lib.dptr(h.to(torch.float32).contiguous()),
+                                               _lib.dptr(nn), B, N, _COV_FACTOR, _lib.dptr(od), _lib.dptr(cd), _lib.dptr(el),
+                                               _lib.dptr(dm), _lib.dptr(am), _lib.dptr(xo), None, cz,
+                                               _lib.current_stream_ptr(dev)), "mcg_handoff_elements")
     return (el, dm, am, xo) if with_coords else (el, dm, am)
 
 

@@ -12,8 +12,8 @@ from typing import Dict, List, Sequence, Tuple
 import torch
 
 from .config import ATOMIC_NUMBERS, DIMENSION
+from .elements import SYMBOL_TO_Z
 
-_SYMBOL_TO_Z = {"H": 1, "C": 6, "N": 7, "O": 8, "F": 9, "P": 15, "S": 16, "Cl": 17, "Br": 35}
 _Z_TO_CLASS = {z: i for i, z in enumerate(ATOMIC_NUMBERS)}
 
 
@@ -87,7 +87,8 @@ def distance_matrix(coordinates: torch.Tensor) -> torch.Tensor:
 def parse_molblock_heavy_atoms(text: str) -> Tuple[torch.Tensor, List[int]]:
     """Heavy-atom coordinates [n,3] (float32) and atomic numbers of a V2000 MOL
     block - the subset of `Chem.RemoveHs(mol).GetConformer().GetPositions()`
-    (conformer_generator.py:302-307) the path needs."""
+    (conformer_generator.py:302-307) the path needs.  A reference conformer only contributes its coordinates, so any
+    element of `config.ELEMENTS` is read; another symbol raises KeyError."""
     lines = text.splitlines()
     counts = lines[3]
     n_atoms = int(counts[0:3])
@@ -97,12 +98,13 @@ def parse_molblock_heavy_atoms(text: str) -> Tuple[torch.Tensor, List[int]]:
         if sym == "H":
             continue
         xyz.append([float(ln[0:10]), float(ln[10:20]), float(ln[20:30])])
-        zs.append(_SYMBOL_TO_Z[sym])
+        zs.append(SYMBOL_TO_Z[sym])
     return torch.tensor(xyz, dtype=torch.float32), zs
 
 
 def one_hot_classes(atomic_numbers: Sequence[int]) -> torch.Tensor:
-    """Atom-class one-hot [n,8] int64 (molgraph.py:10,236-252)."""
+    """Atom-class one-hot [n,8] int64 (molgraph.py:10,236-252).  The fixed class encoding of the reference's
+    `elements_decoder` (sorted PERMITTED_ELEMENTS), NOT the generator's `atom_decoder` - as in the reference."""
     oh = torch.zeros(len(atomic_numbers), len(ATOMIC_NUMBERS), dtype=torch.long)
     for i, z in enumerate(atomic_numbers):
         oh[i, _Z_TO_CLASS[int(z)]] = 1

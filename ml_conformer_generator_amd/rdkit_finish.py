@@ -29,9 +29,9 @@ from typing import List, Optional, Sequence, Tuple
 
 from . import _rdkit_tasks as _tasks
 from . import host_pool
-from .config import ATOM_DECODER, ATOMIC_NUMBERS
+from .elements import Z_TO_SYMBOL
 
-_Z2SYMBOL = {z: ATOM_DECODER[i] for i, z in enumerate(ATOMIC_NUMBERS)}
+_Z2SYMBOL = dict(Z_TO_SYMBOL)          # travels to the pool's workers with every finish / samples task (`config.ELEMENTS`)
 
 
 def have_rdkit() -> bool:

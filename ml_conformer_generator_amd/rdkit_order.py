@@ -33,11 +33,12 @@ import torch
 
 from . import _rdkit_tasks as _tasks
 from . import host_pool
-from .config import ATOM_DECODER, ATOMIC_NUMBERS
+from .config import ATOMIC_NUMBERS
+from .elements import Z_TO_SYMBOL
 
 Provider = Callable[[List[int], np.ndarray], Optional[Tuple[Optional[Sequence[int]], Optional[np.ndarray]]]]
 
-_Z2SYMBOL = {z: ATOM_DECODER[i] for i, z in enumerate(ATOMIC_NUMBERS)}
+_Z2SYMBOL = dict(Z_TO_SYMBOL)          # travels to the pool's workers with every order task (`config.ELEMENTS`)
 
 
 def have_rdkit() -> bool:
@@ -98,14 +99,15 @@ class OrderStage:
 
     Construction copies x, h, n_nodes to the host (ONE D2H copy each) and - for a poolable provider - submits every
     task right away; `result(g)` blocks until group g's molecules are done and returns what
-    `prepare_adj_mat_seer_input_hip` takes for x[lo:hi]: (order, connectivity, built)."""
+    `prepare_adj_mat_seer_input_hip` takes for x[lo:hi]: (order, connectivity, built).  `class_z`: atomic number of each
+    atom class (the generator's `atom_decoder`, mol_utils.py:41-45); the provider sees these atomic numbers."""
 
     def __init__(self, provider, x: torch.Tensor, h: torch.Tensor, n_nodes: torch.Tensor, executor=None,
-                 groups: Optional[List[Tuple[int, int]]] = None):
+                 groups: Optional[List[Tuple[int, int]]] = None, class_z: Sequence[int] = ATOMIC_NUMBERS):
         xc = x.detach().to("cpu", torch.float64).numpy()
         cls = torch.argmax(h.detach(), dim=2).to("cpu").tolist()          # argmax(one_hot) (mol_utils.py:41)
         self.ns = [int(v) for v in n_nodes.detach().to("cpu").reshape(-1).tolist()]
-        self.items = [([ATOMIC_NUMBERS[k] for k in cls[b][:n]], xc[b, :n]) for b, n in enumerate(self.ns)]
+        self.items = [([class_z[k] for k in cls[b][:n]], xc[b, :n]) for b, n in enumerate(self.ns)]
         self.groups = groups if groups is not None else [(0, len(self.ns))]
         self.provider = provider
         self._given = None                     # did the provider supply connectivities?  one answer per batch
