@@ -168,6 +168,19 @@ int mcg_sampler_decode(const mcg_egnn* m, mcg_plan* p, const float* z0, const fl
  * mode 1: re-noise z_known, align the fixed fragment's centre of mass (:79-105), blend (:489-493) */
 int mcg_sampler_blend(const mcg_plan* p, float* z, const float* z_known, const float* fixed_mask, const float* randn_x,
                       const float* randn_h, float alpha_s, float sigma_s, float blend, int mode, void* stream);
+/* Keyed raw draws (opt-in `sample_seed`): randn_x[B,N,3], randn_h[B,N,8] of one draw, for the four consumers above, as a
+ * function of (seed, sample id, run, draw, atom) only - independent of the molecule's row, B, N or rank.
+ * Philox4x32-10 (Salmon et al., SC'11), key (seed & 0xffffffff, seed >> 32), counter
+ * (sample_ids_dev[b], draw, atom i within molecule b, (run << 8) | block), block 0..2.  Each block's words (w0,w1,w2,w3)
+ * give 4 normals by Box-Muller on (w0,w1) and (w2,w3):
+ *   u1 = ((w_even >> 8) + 1) * 2^-24,  u2 = (w_odd >> 8) * 2^-24,  r = sqrt(-2 ln u1),
+ *   z_even = r cos(2 pi u2),  z_odd = r sin(2 pi u2);
+ * normal q = 4*block + j is channel q (0..2 = x, 3..10 = h; the 12th is discarded).  Padded slots (i >= n_b) are 0.
+ * sample_ids_dev: B int64 ids in [0, 2^32), device memory.  `draw` counts the draws of one sampler run from 0 (initial
+ * latent), `run` the sampler runs of one generation call (< 2^24).  Null plan / ids / outputs or run >= 2^24:
+ * MCG_ERR_ARG, nothing launched.  (Molecule sizes use counter (sample_id, 0, 0, 0xffffffff) on the host.) */
+int mcg_sampler_noise_keyed(const mcg_plan* p, uint64_t seed, const int64_t* sample_ids_dev, uint32_t run, uint32_t draw,
+                            float* randn_x, float* randn_h, void* stream);
 
 /* ---- Stand-alone aggregate (unsorted_segment_sum of gate*m, egnn.py:49-64,418-437) over the compact
  * real-edge list: node v owns n_rows[v] consecutive rows of m[E_r, D] starting at first_row[v];

@@ -43,6 +43,7 @@ SIGNATURES: Dict[str, tuple] = {
     "mcg_sampler_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp]),
     "mcg_sampler_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "mcg_sampler_blend": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _vp]),
+    "mcg_sampler_noise_keyed": (_i, [_vp, C.c_uint64, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "mcg_egnn_aggregate": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "mcg_gcn_create": (_i, [_pp, _i, _pp]),
     "mcg_gcn_destroy": (None, [_vp]),

@@ -29,10 +29,14 @@ forced by the scope of this build:
     pool's workers, which inherit the mask - to the cores of its GPU's NUMA node, shared between the ranks of the node:
     `affinity.py`, sysfs only, no HIP call; or an explicit list of cores);
   * `generate_conformers_sharded(...)`: the same call, batch-sharded over the ranks of an
-    initialised `torch.distributed` group (one process per GPU, one gather at the end).
+    initialised `torch.distributed` group (one process per GPU, one gather at the end);
+  * `sample_seed` (opt-in, every generation entry): molecule i's size and every noise draw are a function of
+    (sample_seed, i) alone - the same molecule in any batch, at any row, on any rank.  Seeded calls
+    consume neither the CPU nor the device torch RNG.  Default (None): the reference's torch draw order, unchanged.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import time
 import warnings
@@ -41,6 +45,7 @@ from typing import List, Optional, Union
 import torch
 
 from . import _lib
+from . import seeding
 from .adj_mat_seer import AdjMatSeer
 from .config import (ATOM_DECODER, CONTEXT_NORMS, DIMENSION, MAX_N_NODES, MIN_N_NODES, NOISE_PRECISION,
                      NUM_BOND_TYPES)
@@ -183,20 +188,38 @@ class MLConformerGenerator(torch.nn.Module):
     def edm_tensors(self, reference_context: torch.Tensor, n_samples: int = 100, max_n_nodes: int = 32,
                     min_n_nodes: int = 25, resample_steps: int = 0, fixed_fragment=None,
                     inertial_fragment_matching: bool = True, blend_power: int = 3, ifm_diffusion_level: int = 50,
-                    sizes: Optional[torch.Tensor] = None):
+                    sizes: Optional[torch.Tensor] = None, sample_seed: Optional[int] = None,
+                    sample_ids: Optional[torch.Tensor] = None):
         """Tensor form of `edm_samples` (conformer_generator.py:125-266): x[B,N,3], h[B,N,8], node_mask.
-        `sizes`: molecule sizes drawn by the caller (the sharded path) instead of here."""
+        `sizes`: molecule sizes drawn by the caller (the sharded path) instead of here.
+        `sample_seed` in [0, 2^64): row b is sample `sample_ids[b]` (default arange(n_samples)) of the keyed stream - its
+        size (unless `sizes` is given) and every noise draw of every sampler run depend on (sample_seed, sample_ids[b])
+        only (DESIGN.md section 6), and neither torch generator is consumed.  `sample_ids` regenerates chosen molecules;
+        it needs a `sample_seed`.  A recorded noise tape (`generative_model.noise_fn`) and a seed are refused."""
+        gm = self.generative_model
+        if sample_seed is None:
+            if sample_ids is not None:
+                raise ValueError("sample_ids needs a sample_seed")
+            keyed = lambda run: contextlib.nullcontext()              # noqa: E731
+        else:
+            seeding.check_seed(sample_seed)
+            if gm.noise_fn is not None:
+                raise ValueError("a recorded noise tape (noise_fn) and a sample_seed cannot be combined")
+            sample_ids = seeding.check_sample_ids(torch.arange(n_samples) if sample_ids is None else sample_ids, n_samples)
+            ids_dev = sample_ids.to(self.device)                      # the call's one H2D copy of the ids
+            keyed = lambda run: gm.keyed(sample_seed, ids_dev, run)   # noqa: E731
         min_n_nodes = max(min_n_nodes, self.min_n_nodes)            # :156-160
         max_n_nodes = min(max_n_nodes, self.max_n_nodes)
         node_mask, edge_mask, batch_context = prepare_edm_input(
             n_samples=n_samples, reference_context=reference_context, context_norms=self.context_norms,
-            min_n_nodes=min_n_nodes, max_n_nodes=max_n_nodes, device=self.device, sizes=sizes)
-        gm = self.generative_model
+            min_n_nodes=min_n_nodes, max_n_nodes=max_n_nodes, device=self.device, sizes=sizes,
+            sample_seed=sample_seed, sample_ids=sample_ids)
         ev = self._timing
         if ev is not None:
             ev["sampler_start"].record()
         if fixed_fragment is None:
-            x, h = gm(node_mask, edge_mask, batch_context, resample_steps)
+            with keyed(0):
+                x, h = gm(node_mask, edge_mask, batch_context, resample_steps)
         elif inertial_fragment_matching:
             # generate the complementary fragments separately, then merge (:179-240)
             n_nodes = torch.sum(node_mask, dim=1).to(torch.long)
@@ -205,17 +228,20 @@ class MLConformerGenerator(torch.nn.Module):
                 fixed_fragment_x=ff_x, reference_context=reference_context, n_nodes=n_nodes,
                 context_norms=self.context_norms, max_n_nodes=max_n_nodes, min_n_nodes=min_n_nodes,
                 device=self.device)
-            xg, hg = gm(f_nm, f_em, f_ctx, resample_steps)
+            with keyed(0):
+                xg, hg = gm(f_nm, f_em, f_ctx, resample_steps)
             # inverse_coord_transform + ifm_prepare_fragments_for_merge: one HIP launch on the device outputs
             z_known, fixed_mask = ifm_merge_hip(ff_x, ff_h, xg, hg, shift, rotation, self.device, max_n_nodes)
-            x, h = gm.merge_fragments(node_mask=node_mask, edge_mask=edge_mask, fixed_mask=fixed_mask,
-                                      context=batch_context, z_known=z_known, diffusion_level=ifm_diffusion_level,
-                                      resample_steps=resample_steps, blend_power=blend_power)
+            with keyed(1):
+                x, h = gm.merge_fragments(node_mask=node_mask, edge_mask=edge_mask, fixed_mask=fixed_mask,
+                                          context=batch_context, z_known=z_known, diffusion_level=ifm_diffusion_level,
+                                          resample_steps=resample_steps, blend_power=blend_power)
         else:
             z_known, fixed_mask = prepare_fragment(n_samples=n_samples, fixed_fragment=fixed_fragment,
                                                    max_n_nodes=max_n_nodes, min_n_nodes=min_n_nodes,
                                                    device=self.device)
-            x, h = gm.inpaint(node_mask, edge_mask, batch_context, z_known, fixed_mask, resample_steps, blend_power)
+            with keyed(0):
+                x, h = gm.inpaint(node_mask, edge_mask, batch_context, z_known, fixed_mask, resample_steps, blend_power)
         if ev is not None:
             ev["sampler_end"].record()
         return x, h, node_mask
@@ -223,13 +249,15 @@ class MLConformerGenerator(torch.nn.Module):
     @torch.no_grad()
     def edm_samples(self, reference_context: torch.Tensor, n_samples: int = 100, max_n_nodes: int = 32,
                     min_n_nodes: int = 25, resample_steps: int = 0, fixed_fragment=None,
-                    inertial_fragment_matching: bool = True, blend_power: int = 3, ifm_diffusion_level: int = 50):
+                    inertial_fragment_matching: bool = True, blend_power: int = 3, ifm_diffusion_level: int = 50,
+                    sample_seed: Optional[int] = None):
         """Samples without bonds (conformer_generator.py:125-266): `List[Chem.Mol]` through `samples_to_rdkit_mol`'s XYZ
         route where RDKit imports (`rdkit_finish.samples`, untested offline), else `GeneratedMolecule` records.  Atoms in
-        generation order, as in the reference (canonicalisation happens later, in `generate_conformers`)."""
+        generation order, as in the reference (canonicalisation happens later, in `generate_conformers`).
+        `sample_seed`: as in `edm_tensors`; the Mols then carry the int property `sample_id`."""
         x, h, node_mask = self.edm_tensors(reference_context, n_samples, max_n_nodes, min_n_nodes, resample_steps,
                                            fixed_fragment, inertial_fragment_matching, blend_power,
-                                           ifm_diffusion_level)
+                                           ifm_diffusion_level, sample_seed=sample_seed)
         n_nodes = node_mask.sum(1).reshape(-1).to(torch.long)
         el, _, _ = prepare_adj_mat_seer_input_hip(x, h, n_nodes, self.dimension, class_z=self.class_z)
         no_bonds = torch.zeros(x.shape[0], self.dimension, self.dimension, dtype=torch.int8, device=x.device)
@@ -238,7 +266,8 @@ class MLConformerGenerator(torch.nn.Module):
             m.valid = True          # no bonds yet: the connectivity proxy does not apply
         if HAVE_RDKIT:
             from . import rdkit_finish
-            return rdkit_finish.samples(mols, self._executor())
+            return rdkit_finish.samples(mols, self._executor(),
+                                        sample_ids=None if sample_seed is None else range(len(mols)))
         return mols
 
     # ------------------------------------------------------------------ full pipeline
@@ -270,9 +299,12 @@ class MLConformerGenerator(torch.nn.Module):
 
     def _generate_shard(self, ref_context, ref_n_atoms: int, variance: int, sizes: Optional[torch.Tensor],
                         n_samples: int, resample_steps, fixed_fragment, inertial_fragment_matching, blend_power,
-                        ifm_diffusion_level, optimise_geometry: bool = True):
+                        ifm_diffusion_level, optimise_geometry: bool = True, sample_seed: Optional[int] = None,
+                        sample_ids: Optional[torch.Tensor] = None):
         """Sampler -> hand-off -> GCN -> bond write-back + validity proxy for `n_samples` molecules on THIS device.
         Returns per-sample DEVICE tensors (dim 0 = n_samples; n_samples may be 0 for an empty shard).
+        `sample_seed`, `sample_ids`: the keyed stream of `edm_tensors`; `sample_ids` (default arange) also names the
+        records handed to the finisher.
 
         With an atom-order provider and / or a finisher (RDKit's where RDKit imports) the part behind the sampler is a
         pipeline over groups of molecules (conformer_generator.py:343-366 runs it one molecule at a time): every order
@@ -308,8 +340,9 @@ class MLConformerGenerator(torch.nn.Module):
             reference_context=ref_context, n_samples=n_samples, min_n_nodes=ref_n_atoms - variance,
             max_n_nodes=ref_n_atoms + variance, resample_steps=resample_steps, fixed_fragment=fixed_fragment,
             inertial_fragment_matching=inertial_fragment_matching, blend_power=blend_power,
-            ifm_diffusion_level=ifm_diffusion_level, sizes=sizes)
+            ifm_diffusion_level=ifm_diffusion_level, sizes=sizes, sample_seed=sample_seed, sample_ids=sample_ids)
         n_nodes = node_mask.sum(1).reshape(-1).to(torch.long)
+        ids = list(range(n_samples)) if sample_ids is None else [int(i) for i in torch.as_tensor(sample_ids).tolist()]
         groups = rdkit_order.launch_groups(n_samples) if staged else [(0, n_samples)]
         t0 = time.perf_counter()
         # host: RDKit's (or the caller's) order + connectivity - every task of the batch goes out now
@@ -335,7 +368,8 @@ class MLConformerGenerator(torch.nn.Module):
             parts.append((x_out, el, bond, sym, valid))
             orders.append(order if order is not None else [None] * (hi - lo))
             if fin is not None:                               # this group's records -> the pool, behind the order tasks
-                fin.add(molecules_from_tensors(x_out, el.to(torch.int8), sym, ng.to(torch.int32), valid.to(torch.uint8)))
+                fin.add(molecules_from_tensors(x_out, el.to(torch.int8), sym, ng.to(torch.int32), valid.to(torch.uint8),
+                                               sample_ids=ids[lo:hi]))
         if stage is not None:
             self.last_host_order_ms = (time.perf_counter() - t0) * 1e3
         cat = (lambda k: parts[0][k]) if len(parts) == 1 else (lambda k: torch.cat([p[k] for p in parts], dim=0))
@@ -359,17 +393,29 @@ class MLConformerGenerator(torch.nn.Module):
                             reference_context: torch.Tensor = None, n_atoms: int = None,
                             optimise_geometry: bool = True, resample_steps: int = 0, fixed_fragment=None,
                             inertial_fragment_matching: bool = True, blend_power: int = 3,
-                            ifm_diffusion_level: int = 50) -> List:
+                            ifm_diffusion_level: int = 50, sample_seed: Optional[int] = None) -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
-        records that pass the labelled valence / single-fragment proxy of `mcg_bond_writeback` (no MMFF: warned once)."""
+        records that pass the labelled valence / single-fragment proxy of `mcg_bond_writeback` (no MMFF: warned once).
+        Each record says which sample it is (`GeneratedMolecule.sample_id`).  `sample_seed`: the keyed stream of
+        `edm_tensors` - sample i is the same molecule whatever `n_samples`; the Mols carry the int property `sample_id`."""
+        if sample_seed is not None:
+            seeding.check_seed(sample_seed)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
-        res = self._generate_shard(ref_context, ref_n_atoms, variance, None, n_samples, resample_steps, fixed_fragment,
-                                   inertial_fragment_matching, blend_power, ifm_diffusion_level, optimise_geometry)
+        if sample_seed is None:       # the positional call of before: a stub of `_generate_shard` need not know the seed
+            res = self._generate_shard(ref_context, ref_n_atoms, variance, None, n_samples, resample_steps, fixed_fragment,
+                                       inertial_fragment_matching, blend_power, ifm_diffusion_level, optimise_geometry)
+        else:
+            res = self._generate_shard(ref_context, ref_n_atoms, variance, None, n_samples, resample_steps, fixed_fragment,
+                                       inertial_fragment_matching, blend_power, ifm_diffusion_level, optimise_geometry,
+                                       sample_seed, None)
         stage, self._finish_stage = getattr(self, "_finish_stage", None), None
         if stage is not None:                     # finished per group while the later groups were still on their way
             done = self._collect_finish(stage)
+            if sample_seed is not None:
+                from . import rdkit_finish
+                rdkit_finish.tag_sample_ids(done, range(len(done)))
             kept = [m for m in done if m is not None]
             self.last_valid_fraction = len(kept) / len(done) if done else 0.0
             return kept
@@ -383,7 +429,8 @@ class MLConformerGenerator(torch.nn.Module):
                                     optimise_geometry: bool = True, resample_steps: int = 0, fixed_fragment=None,
                                     inertial_fragment_matching: bool = True, blend_power: int = 3,
                                     ifm_diffusion_level: int = 50, group=None, seed: Optional[int] = None,
-                                    gather: str = "all", balance: str = "cost") -> List:
+                                    gather: str = "all", balance: str = "cost",
+                                    sample_seed: Optional[int] = None) -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -395,9 +442,16 @@ class MLConformerGenerator(torch.nn.Module):
         every rank raise `distributed.ShardError`.  `gather="rank0"`: only rank 0 of the group receives (and returns) the
         whole batch - one `gather` instead of the all-gather - and every other rank returns its own shard's molecules.
         Where a finisher runs (RDKit's), every rank finishes ITS OWN shard in its own host pool and the finished Mols are
-        gathered as objects.  Without an initialised group this is `generate_conformers`."""
+        gathered as objects.  Without an initialised group this is `generate_conformers`.
+        `sample_seed` (instead of `seed`): the keyed stream of `edm_tensors` - every rank computes the keyed sizes of all
+        `n_samples` itself (no broadcast), generates its shard with the shard's global indices as `sample_ids` and seeds
+        no generator, so sample i is the same molecule on any world size and under either `balance`."""
         if gather not in ("all", "rank0"):
             raise ValueError("gather must be 'all' or 'rank0'")
+        if sample_seed is not None:
+            if seed is not None:
+                raise ValueError("pass either seed (per-rank device generator) or sample_seed (keyed stream), not both")
+            seeding.check_seed(sample_seed)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)
         hi_n = min(ref_n_atoms + variance, self.max_n_nodes)
@@ -408,9 +462,10 @@ class MLConformerGenerator(torch.nn.Module):
         finished: List = [None]
 
         def run_shard(sizes_shard, index):
+            keyed = () if sample_seed is None else (sample_seed, index)
             res = self._generate_shard(ref_context, ref_n_atoms, variance, sizes_shard, int(index.numel()), resample_steps,
                                        fixed_fragment, inertial_fragment_matching, blend_power, ifm_diffusion_level,
-                                       optimise_geometry)
+                                       optimise_geometry, *keyed)
             if finishing:
                 # collected HERE, in front of the status exchange: a finish that raises on one rank (a dead worker, a custom
                 # finisher's exception, a result-count mismatch) makes EVERY rank raise ShardError instead of leaving the
@@ -429,13 +484,24 @@ class MLConformerGenerator(torch.nn.Module):
                     torch.cuda.manual_seed(s)
 
         dst = 0 if gather == "rank0" else None
+        if sample_seed is None:
+            draw_sizes, seed_fn = (lambda: mcg_dist.draw_global_sizes(n_samples, lo_n, hi_n, group)), seed_device
+        else:       # identical on every rank by construction: no broadcast, and no generator is seeded
+            draw_sizes, seed_fn = (lambda: mcg_dist.keyed_global_sizes(n_samples, lo_n, hi_n, sample_seed)), None
         _, res, shards = mcg_dist.sharded_generate(
-            n_samples, lambda: mcg_dist.draw_global_sizes(n_samples, lo_n, hi_n, group), run_shard, group=group,
-            seed=seed, seed_fn=seed_device, gather_dst=dst, balance=balance, gather_tensors=not finishing)
+            n_samples, draw_sizes, run_shard, group=group,
+            seed=seed, seed_fn=seed_fn, gather_dst=dst, balance=balance, gather_tensors=not finishing)
         self.last_shards = shards
         self._finish_stage = None
+        # the sample ids of the rows this rank returns: the whole batch in sample order, or (gather="rank0", rank > 0)
+        # its own shard
+        _, rank = mcg_dist.world_and_rank(group)
+        row_ids = shards[rank] if (dst is not None and rank != dst and len(shards) > 1) else None
         if finishing:                         # RDKit's gate: this rank's shard was finished above, the Mols travel as objects
             done = mcg_dist.gather_objects(finished[0], shards, group, dst)
+            if sample_seed is not None:
+                from . import rdkit_finish
+                rdkit_finish.tag_sample_ids(done, range(len(done)) if row_ids is None else row_ids.tolist())
             self.last_host_assembly_ms = 0.0
             kept = [m for m in done if m is not None]
             self.last_valid_fraction = len(kept) / len(done) if done else 0.0
@@ -443,7 +509,8 @@ class MLConformerGenerator(torch.nn.Module):
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)       # (the D2H copies below would wait for the device anyway: keep that out of the figure)
         t0 = time.perf_counter()
-        mols = molecules_from_tensors(res["x"], res["elements"], res["bond"], res["n_nodes"], res["valid"])
+        mols = molecules_from_tensors(res["x"], res["elements"], res["bond"], res["n_nodes"], res["valid"],
+                                      sample_ids=row_ids)
         self.last_host_assembly_ms = (time.perf_counter() - t0) * 1e3      # D2H of the gathered tensors + record views
         kept, self.last_valid_fraction = _finish(mols, optimise_geometry, use_rdkit=False)    # no finisher: the proxy
         return kept
@@ -452,7 +519,8 @@ class MLConformerGenerator(torch.nn.Module):
     def forward(self, reference_conformer=None, n_samples: int = 10, variance: int = 2,
                 reference_context: torch.Tensor = None, n_atoms: int = None, optimise_geometry: bool = True,
                 resample_steps: int = 0, fixed_fragment=None, inertial_fragment_matching: bool = True,
-                blend_power: int = 3, ifm_diffusion_level: int = 50) -> List:
+                blend_power: int = 3, ifm_diffusion_level: int = 50, sample_seed: Optional[int] = None) -> List:
         return self.generate_conformers(reference_conformer, n_samples, variance, reference_context, n_atoms,
                                         optimise_geometry, resample_steps, fixed_fragment,
-                                        inertial_fragment_matching, blend_power, ifm_diffusion_level)
+                                        inertial_fragment_matching, blend_power, ifm_diffusion_level,
+                                        sample_seed=sample_seed)

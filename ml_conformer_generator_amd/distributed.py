@@ -13,9 +13,15 @@ reference's own draw (`torch.randint(min, max + 1, (n_samples,))`, mol_utils.py:
 ragged batch (15..39 atoms: a 7x spread in cost) loads the ranks within ~1 % of each other instead of the +-5 % of equal
 COUNTS; the gathered results are put back into sample order.  A seeded single-process run and a sharded run therefore
 generate the same molecule sizes in the same order.
-Noise: per-rank device generator, seed `seed + rank` (with `seed=None` the base seed is drawn on rank 0 and
+Noise (default): per-rank device generator, seed `seed + rank` (with `seed=None` the base seed is drawn on rank 0 and
 broadcast - ranks never share a noise stream); bit-identity of the NOISE with an unsharded run is not promised
 (the reference draws it as one [B,N,*] tensor).
+Keyed mode (`sample_seed`): sizes and noise of sample i are functions of (sample_seed, i) alone.
+Every rank computes the keyed size vector of the whole batch itself (`keyed_global_sizes`: no broadcast, the same
+vector everywhere by construction), derives the same `assign_shards`, and generates its shard with the shard's GLOBAL
+sample indices as the keyed stream's sample ids; no generator is seeded (`seed_fn` / `rank_seed` are skipped).  The
+noise of every molecule is then bit-identical to an unsharded seeded run's, on any world size and under either
+balance mode; the outputs agree to the denoiser's arithmetic (its kernel route depends on the shard's geometry).
 Failure: a rank whose shard raises does not leave the others parked in the gather - one status byte per rank is
 exchanged first and EVERY rank raises `ShardError`.
 """
@@ -107,6 +113,13 @@ def draw_global_sizes(n_samples: int, min_n_nodes: int, max_n_nodes: int, group=
     src = dist.get_global_rank(group, 0) if group is not None else 0
     dist.broadcast(sizes, src=src, group=group)
     return sizes.cpu()
+
+
+def keyed_global_sizes(n_samples: int, min_n_nodes: int, max_n_nodes: int, sample_seed: int) -> torch.Tensor:
+    """The keyed sizes of the WHOLE batch [n_samples] int64 (CPU) - `seeding.keyed_sizes` of ids 0..n_samples-1, computed
+    locally: identical on every rank without a collective, and touching no RNG."""
+    from .seeding import keyed_sizes
+    return keyed_sizes(sample_seed, torch.arange(n_samples), min_n_nodes, max_n_nodes)
 
 
 def gather_results(local: Dict[str, torch.Tensor], n_samples: int, group=None, dst: Optional[int] = None,

@@ -6,10 +6,15 @@ method names, argument order and RNG draw order (one `randn[B,N,3]` then one
 evaluated once on the host with the reference's fp32 expressions; everything that
 touches a [B,N,*] tensor runs in libmlconfgen_hip.so (one network call + one fused
 update launch per step).
+
+Keyed mode (`sample_seed`): while `keyed(...)` is active, every `_draw` of a run is ONE launch of
+`mcg_sampler_noise_keyed` instead of the two `torch.randn` calls - the raw normals of molecule b are a function of
+(seed, sample_ids[b], run ordinal, draw ordinal, atom) alone, and neither the CPU nor the device torch generator is used.
 """
 from __future__ import annotations
 
-from typing import Callable, List, Optional, Tuple
+import contextlib
+from typing import Callable, List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -18,6 +23,13 @@ from . import _lib
 from .config import N_ATOM_CLASSES, NORM_VALUES
 from .egnn import BatchPlan, EGNNDynamics, sizes_from_node_mask
 from .schedule import gamma_table, step_scalars
+
+
+class NoiseKey(NamedTuple):
+    """Key of the keyed noise stream of one sampler run (include/mlconfgen_hip.h `mcg_sampler_noise_keyed`)."""
+    seed: int               # sample_seed, [0, 2^64)
+    ids: torch.Tensor       # [B] int64 global sample ids, on the device
+    run: int                # sampler run within the generation call (inertial fragment matching: 0 fragment, 1 merge)
 
 
 class PredefinedNoiseSchedule(torch.nn.Module):
@@ -46,6 +58,7 @@ class EquivariantDiffusion(torch.nn.Module):
         self.noise_fn: Optional[Callable] = None     # tests inject a recorded noise tape here
         self.trace: Optional[List[torch.Tensor]] = None
         self._scalar_cache = {}
+        self._key: Optional[NoiseKey] = None     # keyed noise of the current generation call (`keyed`)
 
     @property
     def device(self) -> torch.device:
@@ -89,11 +102,31 @@ class EquivariantDiffusion(torch.nn.Module):
             return self.noise_fn(shape).to(self.device, torch.float32).contiguous()
         return torch.randn(shape, device=self.device)
 
-    def _draw(self, B: int, N: int):
-        """Raw draws in the reference's order: x block first, then h block (:347-361)."""
-        rx = self._randn((B, N, self.n_dims))
-        rh = self._randn((B, N, self.in_node_nf))
+    def _draw(self, run: "_Run"):
+        """Raw draws of one noise sample.  Default: the reference's order, x block first, then h block (:347-361).
+        Keyed run: one `mcg_sampler_noise_keyed` launch into the plan's draw buffers at this run's next draw ordinal."""
+        key = run.key
+        if key is None:
+            rx = self._randn((run.B, run.N, self.n_dims))
+            rh = self._randn((run.B, run.N, self.in_node_nf))
+            return rx, rh
+        rx, rh = run.keyed_x, run.keyed_h
+        _lib.check(_lib.lib().mcg_sampler_noise_keyed(run.plan.handle, key.seed, _lib.dptr(key.ids), key.run, run.draw,
+                                                      _lib.dptr(rx), _lib.dptr(rh), run.stream), "mcg_sampler_noise_keyed")
+        run.draw += 1
         return rx, rh
+
+    @contextlib.contextmanager
+    def keyed(self, seed: int, ids: torch.Tensor, run: int = 0):
+        """Sampler runs started inside draw keyed noise: `seed` in [0, 2^64), `ids` the [B] int64 sample ids ON THE
+        DEVICE (one copy per generation call), `run` the ordinal of the sampler run within the call."""
+        if self.noise_fn is not None:
+            raise ValueError("a recorded noise tape (noise_fn) and a sample_seed cannot be combined")
+        prev, self._key = self._key, NoiseKey(int(seed), ids, int(run))
+        try:
+            yield
+        finally:
+            self._key = prev
 
     class _Run:
         """State of one sampling call: plan, device context, time table, scratch.
@@ -126,6 +159,18 @@ class EquivariantDiffusion(torch.nn.Module):
             self.t_table = levels.unsqueeze(1).repeat(1, self.B).to(dev).contiguous()   # [T+1, B]
             self.eps_hat = sc["eps"]
             self.stream = _lib.current_stream_ptr(dev)
+            self.key: Optional[NoiseKey] = model._key
+            self.draw = 0
+            if self.key is not None:
+                if model.noise_fn is not None:
+                    raise ValueError("a recorded noise tape (noise_fn) and a sample_seed cannot be combined")
+                if int(self.key.ids.numel()) != self.B or self.key.ids.device != dev:
+                    raise ValueError(f"keyed noise needs {self.B} sample ids on {dev}")
+                kx = getattr(self.plan, "_keyed_draws", None)
+                if kx is None:      # written and consumed in stream order, draw after draw: one pair per plan
+                    kx = tuple(torch.empty((self.B, self.N, w), device=dev, dtype=torch.float32) for w in (3, 8))
+                    self.plan._keyed_draws = kx
+                self.keyed_x, self.keyed_h = kx
 
     def sample_combined_position_feature_noise(self, n_samples: int, n_nodes: int, node_mask) -> torch.Tensor:
         """Mean-centred x noise + plain h noise, masked (:341-363)."""
@@ -133,7 +178,7 @@ class EquivariantDiffusion(torch.nn.Module):
         return self._noise(run)
 
     def _noise(self, run: "_Run", out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        rx, rh = self._draw(run.B, run.N)
+        rx, rh = self._draw(run)
         eps = out if out is not None else torch.empty((run.B, run.N, 11), device=self.device, dtype=torch.float32)
         _lib.check(_lib.lib().mcg_sampler_noise(run.plan.handle, _lib.dptr(rx), _lib.dptr(rh), _lib.dptr(eps),
                                                 run.stream), "mcg_sampler_noise")
@@ -146,7 +191,7 @@ class EquivariantDiffusion(torch.nn.Module):
     def _step(self, run: "_Run", z: torch.Tensor, s_int: int) -> torch.Tensor:
         """In-place z_t -> z_s for t = (s+1)/T (:295-339)."""
         alpha_ts, c_eps, c_noise = self._step_scalars(s_int)
-        rx, rh = self._draw(run.B, run.N)
+        rx, rh = self._draw(run)
         _lib.check(_lib.lib().mcg_sampler_step(
             self.dynamics.handle, run.plan.handle, _lib.dptr(z), _lib.dptr(run.context),
             run.t_table[s_int + 1].data_ptr(), _lib.dptr(rx), _lib.dptr(rh), alpha_ts, c_eps, c_noise,
@@ -161,7 +206,7 @@ class EquivariantDiffusion(torch.nn.Module):
         sigma_x = float(torch.exp(-(-0.5 * g0)))
         alpha0, sigma0 = float(torch.sqrt(torch.sigmoid(-g0))), float(torch.sqrt(torch.sigmoid(g0)))
         inv_alpha0 = float(1.0 / torch.sqrt(torch.sigmoid(-g0)))
-        rx, _rh = self._draw(run.B, run.N)      # the h block is drawn (RNG parity) but unused (:277-285)
+        rx, _rh = self._draw(run)      # the h block is drawn (RNG parity) but unused (:277-285)
         x = torch.empty((run.B, run.N, 3), device=self.device, dtype=torch.float32)
         h = torch.empty((run.B, run.N, self.num_classes), device=self.device, dtype=torch.float32)
         _lib.check(_lib.lib().mcg_sampler_decode(
@@ -174,7 +219,7 @@ class EquivariantDiffusion(torch.nn.Module):
         alpha_s, sigma_s = self._alpha_sigma(s_int)
         s_arr = torch.full([1, 1], fill_value=s_int) / self.T
         blend = float(torch.pow((1 - s_arr), blend_power)) if mode == 1 else 0.0
-        rx, rh = self._draw(run.B, run.N)
+        rx, rh = self._draw(run)
         _lib.check(_lib.lib().mcg_sampler_blend(
             run.plan.handle, _lib.dptr(z), _lib.dptr(z_known), _lib.dptr(fixed_mask) if fixed_mask is not None else None,
             _lib.dptr(rx), _lib.dptr(rh), alpha_s, sigma_s, blend, mode, run.stream), "mcg_sampler_blend")

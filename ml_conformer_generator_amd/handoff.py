@@ -15,7 +15,7 @@ parity unpinned against RDKit).  "valid" without RDKit is a valence / connectivi
 from __future__ import annotations
 
 import ctypes
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -40,19 +40,28 @@ class GeneratedMolecule:
     `atomic_numbers` List[int]; `coords` [n,3] float32 (CPU); `bond_orders` [n,n] int8, symmetric, 0 none / 1 / 2 / 3 /
     4 aromatic; `valid` bool.  Records built by `molecules_from_tensors` are LAZY views into the batch's host tensors: the
     per-molecule slices are taken on first access, so assembling a batch costs one object per molecule (2 048 molecules:
-    a few ms instead of 70-170 ms of slicing + cloning on every rank of a sharded call)."""
-    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b")
+    a few ms instead of 70-170 ms of slicing + cloning on every rank of a sharded call).  `sample_id`: which sample of
+    its generation call the record is (invalid molecules are dropped, so a kept record's position says nothing)."""
+    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid")
 
-    def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True):
+    def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True,
+                 sample_id: Optional[int] = None):
         self._z, self._coords, self._bonds, self.valid = list(atomic_numbers), coords, bond_orders, bool(valid)
-        self._batch, self._b = None, -1
+        self._batch, self._b, self._sid = None, -1, sample_id
 
     @classmethod
-    def _view(cls, batch: _HostBatch, b: int, valid: bool) -> "GeneratedMolecule":
+    def _view(cls, batch: _HostBatch, b: int, valid: bool, sample_id: Optional[int] = None) -> "GeneratedMolecule":
         m = cls.__new__(cls)
         m._z = m._coords = m._bonds = None
         m.valid, m._batch, m._b = valid, batch, b
+        m._sid = b if sample_id is None else sample_id
         return m
+
+    @property
+    def sample_id(self) -> Optional[int]:
+        """Global sample index of this molecule in its generation call (with `sample_seed`: what its noise and size are
+        keyed on, so `edm_tensors(..., sample_ids=[sample_id])` regenerates it); None for a record built by hand."""
+        return self._sid
 
     @property
     def atomic_numbers(self) -> List[int]:
@@ -213,12 +222,16 @@ def bond_writeback_hip(bond: torch.Tensor, elements: torch.Tensor, n_nodes: torc
 
 
 def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: torch.Tensor, n_nodes: torch.Tensor,
-                           valid: torch.Tensor) -> List[GeneratedMolecule]:
+                           valid: torch.Tensor, sample_ids: Optional[Sequence[int]] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
-    (no per-molecule slicing or cloning here: `GeneratedMolecule._view`)."""
+    (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
+    (default: b, the row IS the sample index)."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
     view = GeneratedMolecule._view
-    return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
+    if sample_ids is None:
+        return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
+    ids = [int(i) for i in (sample_ids.tolist() if torch.is_tensor(sample_ids) else sample_ids)]
+    return [view(batch, b, bool(v), ids[b]) for b, v in enumerate(valid.cpu().tolist())]
 
 
 def assemble_molecules(x: torch.Tensor, elements: torch.Tensor, bond: torch.Tensor, n_nodes: torch.Tensor

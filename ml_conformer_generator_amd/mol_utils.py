@@ -7,9 +7,11 @@ numbers) so that the path runs on a box without RDKit.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
+
+from . import seeding
 
 from .config import ATOMIC_NUMBERS, DIMENSION
 from .elements import SYMBOL_TO_Z
@@ -42,12 +44,18 @@ def tag_canonical_masks(node_mask: torch.Tensor, edge_mask: torch.Tensor, sizes:
 
 
 def prepare_edm_input(n_samples: int, reference_context: torch.Tensor, context_norms: Dict[str, torch.Tensor],
-                      min_n_nodes: int, max_n_nodes: int, device, sizes: torch.Tensor = None):
+                      min_n_nodes: int, max_n_nodes: int, device, sizes: torch.Tensor = None,
+                      sample_seed: Optional[int] = None, sample_ids: Optional[torch.Tensor] = None):
     """mol_utils.py:255-295.  Molecule sizes come from the CPU global RNG
     (`torch.randint`), exactly like the reference, so `torch.manual_seed` gives
     identical size draws.  `sizes` (optional, [n_samples] integers in [min, max]) hands in sizes drawn
-    elsewhere - the sharded path draws the global vector once and gives every rank its slice."""
-    if sizes is None:
+    elsewhere - the sharded path draws the global vector once and gives every rank its slice.
+    `sample_seed` (with `sizes` None): the keyed sizes of `sample_ids` (default arange(n_samples)), a function of
+    (seed, id) alone (`seeding.keyed_sizes`) - the global RNG is not touched."""
+    if sizes is None and sample_seed is not None:
+        ids = seeding.check_sample_ids(torch.arange(n_samples) if sample_ids is None else sample_ids, n_samples)
+        sizes = seeding.keyed_sizes(sample_seed, ids, min_n_nodes, max_n_nodes)
+    elif sizes is None:
         sizes = torch.randint(min_n_nodes, max_n_nodes + 1, (n_samples,))
     else:
         sizes = sizes.reshape(-1).to("cpu", torch.long)

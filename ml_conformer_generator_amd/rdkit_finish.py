@@ -125,16 +125,23 @@ def finish(molecules: List, optimise_geometry: bool = True, executor=None) -> Li
     return stage.results()
 
 
-def samples(molecules: List, executor=None) -> List[object]:
+def samples(molecules: List, executor=None, sample_ids: Optional[Sequence[int]] = None) -> List[object]:
     """`edm_samples`' return value (conformer_generator.py:262-266): bond-free Mols; unbuildable ones are skipped
-    (mol_utils.py:53-55)."""
+    (mol_utils.py:53-55).  `sample_ids` (seeded calls): each Mol gets the int property `sample_id` of its record."""
     if executor is not None and getattr(executor, "n_workers", 0) > 0:
         from rdkit import Chem
         raw = host_pool.map_ordered(executor, host_pool.SAMPLES_TASK, [record_item(r) for r in molecules], (_Z2SYMBOL,))
-        return [Chem.Mol(b) for b in raw if b is not None]
-    out = []
-    for rec in molecules:
-        mol = mol_without_bonds(rec)
-        if mol is not None:
-            out.append(mol)
-    return out
+        mols = [Chem.Mol(b) if b is not None else None for b in raw]
+    else:
+        mols = [mol_without_bonds(rec) for rec in molecules]
+    if sample_ids is not None:
+        tag_sample_ids(mols, sample_ids)
+    return [m for m in mols if m is not None]
+
+
+def tag_sample_ids(mols: Sequence, sample_ids: Sequence[int]) -> None:
+    """Set the int property `sample_id` (the molecule's global sample index) on every Mol of `mols` (None = dropped);
+    `sample_ids[k]` belongs to `mols[k]`; what a custom finisher returns is tagged only if it is a Mol."""
+    for m, sid in zip(mols, sample_ids):
+        if m is not None and hasattr(m, "SetIntProp"):
+            m.SetIntProp("sample_id", int(sid))
