@@ -266,6 +266,28 @@ int mcg_shape_tanimoto(const float* ref, int n_ref, const float* cand, const int
                        const float* rot, int R, const float* axes, int n, float alpha, float amplitude,
                        float* f_scratch, float* score, void* stream);
 
+/* ---- Evaluation (frame half): principal shape frames of B padded molecules of N <= 64 atoms -
+ * `get_shape_quadrupole_for_molecule` (cheminformatics/shape_similarity.py:18-202), two launches around the host's 3x3
+ * eigen-decomposition (its LAPACK eigenvector signs choose between a frame and its mirror image):
+ *   mcg_shape_moments: pass 1 on the input points -> shape centre[B,3] (fp32) and volume[B] (fp64 sum); pass 2 on the
+ *                      centred points -> second-moment tensor[B,9] (row-major, fp32, divided by the volume);
+ *                      clique_counts[B, n_terms-1] (optional, NULL = not wanted): cliques of order 2..n_terms per molecule.
+ *   mcg_shape_frames:  eigvecs[B,9] = V row-major (column j = eigenvector j, as torch.linalg.eigh returns it) of that
+ *                      tensor; pass 3 on the rotated points -> main moments[B,3] (descending) and frames[B,N,3] (the
+ *                      rotated points, axes permuted to match; zero on padded rows).
+ * coords[B,N,3] with n_nodes_dev[b] real atoms (device memory, clamped to [0, N] on the device); both launches build the
+ * same neighbour graph (0 < d < neighbour_threshold) from coords.  centre_atoms != 0: the real atoms' mean is subtracted
+ * from coords first (evaluate_shape's centring).  Terms in fp32, sums in fp64 per molecule, fixed lane assignment and
+ * reduction order: every output is bit-identical run to run and whatever the batch, row or padded width.
+ * MCG_ERR_ARG, nothing launched: a null buffer, B < 1, N outside 1..64, n_terms outside 2..8, alpha, amplitude or
+ * neighbour_threshold not > 0. */
+int mcg_shape_moments(const float* coords, const int32_t* n_nodes_dev, int B, int N, double alpha, double amplitude,
+                      float neighbour_threshold, int n_terms, int centre_atoms, float* centre, float* tensor,
+                      double* volume, int64_t* clique_counts, void* stream);
+int mcg_shape_frames(const float* coords, const int32_t* n_nodes_dev, int B, int N, const float* centre,
+                     const float* eigvecs, const double* volume, double alpha, double amplitude, float neighbour_threshold,
+                     int n_terms, int centre_atoms, float* moments, float* frames, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

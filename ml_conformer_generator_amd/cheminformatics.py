@@ -7,12 +7,14 @@ and `tanimoto_score` (:448-492), batched over all candidates on the device.  The
 level by level as index tensors, Gaussian inclusion-exclusion moments accumulated per molecule), with the 3x3
 eigen-decomposition on the host in the reference's own LAPACK path so that eigenvector signs - which decide
 between a frame and its mirror image - are the reference's.  The RDKit fingerprint similarity and mol-block
-output of `evaluate_samples` are outside this build.
+output of `evaluate_samples` are outside this build.  `shape_frames_hip` / `shape_scores` are the device scoring path of the
+generation entries: the same frames by two HIP launches (`mcg_shape_moments`, `mcg_shape_frames`: cliques enumerated in
+LDS, never stored) around the same host `eigh`, bit-identical for a molecule whatever its batch.
 """
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -204,6 +206,125 @@ def evaluate_shape(reference_coord: torch.Tensor, sample_coords: torch.Tensor, n
     results = [{"coords": aligned_c[b, : int(nn_c[b])].clone(), "shape_tanimoto": float(best_c[b]),
                 "orientation": int(which_c[b])} for b in range(B)]
     return ref_pf, results
+
+
+# ----------------------------------------------------------------------------- device scoring path (HIP frames)
+MAX_SCORED_ATOMS = 64          # csrc/mcg_shape_frames.hip: one 64-bit neighbour mask per atom
+
+
+@torch.no_grad()
+def shape_frames_hip(coords: torch.Tensor, n_nodes: torch.Tensor, device=None, amplitude: float = AMPLITUDE,
+                     atom_radius: float = ATOM_RADIUS, n_terms: int = 6, neighbour_threshold: float = 2 * AMPLITUDE,
+                     centre_atoms: bool = False, with_counts: bool = False):
+    """`shape_quadrupole_batch` through the HIP kernels (`mcg_shape_moments` -> host `eigh` -> `mcg_shape_frames`):
+    principal moments [B,3] and frames [B,N,3] on the device, bit-identical for a molecule whatever its batch, row or
+    padded width.  `centre_atoms`: subtract the real atoms' mean first (what `evaluate_shape` does to its inputs).
+    `with_counts`: also the exact number of cliques of order 2..n_terms per molecule, int64 [B, n_terms-1].
+    A molecule whose moment tensor is not finite (non-finite coordinates, no atoms) gets NaN moments and frames; the
+    other molecules of the batch are unaffected.  `n_nodes` outside [0, N] is refused with ValueError."""
+    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
+    x = coords.to(dev, torch.float32).contiguous()
+    B, N, _ = x.shape
+    if N > MAX_SCORED_ATOMS:
+        raise ValueError(f"the shape kernels take at most {MAX_SCORED_ATOMS} atoms per molecule, got a padded width of {N}")
+    check_n_nodes(n_nodes, B, N)
+    moments = torch.empty(B, 3, device=dev)
+    frames = torch.empty(B, N, 3, device=dev)
+    counts = torch.empty(B, n_terms - 1, dtype=torch.int64, device=dev) if with_counts else None
+    if B == 0 or N == 0:
+        frames.zero_()
+        return (moments, frames, counts) if with_counts else (moments, frames)
+    nn = n_nodes.to(dev, torch.int32).reshape(B).contiguous()
+    alpha = get_alpha(atom_radius, amplitude)
+    centre = torch.empty(B, 3, device=dev)
+    tensor = torch.empty(B, 9, device=dev)
+    volume = torch.empty(B, dtype=torch.float64, device=dev)
+    L, stream = _lib.lib(), _lib.current_stream_ptr(dev)
+    _lib.check(L.mcg_shape_moments(_lib.dptr(x), _lib.dptr(nn), B, N, alpha, float(amplitude), float(neighbour_threshold),
+                                   int(n_terms), int(bool(centre_atoms)), _lib.dptr(centre), _lib.dptr(tensor),
+                                   _lib.dptr(volume), _lib.dptr(counts), stream), "mcg_shape_moments")
+    t = tensor.reshape(B, 3, 3).cpu()
+    bad = ~torch.isfinite(t).all(dim=2).all(dim=1)           # LAPACK refuses the whole batch for one NaN matrix
+    if bool(bad.any()):
+        t[bad] = torch.eye(3)          # placeholder: such a molecule's centre and volume are NaN, so are its frames
+    _, vecs = torch.linalg.eigh(t)                                       # the reference's host LAPACK path (:143-144)
+    vecs = vecs.contiguous().to(dev)
+    _lib.check(L.mcg_shape_frames(_lib.dptr(x), _lib.dptr(nn), B, N, _lib.dptr(centre), _lib.dptr(vecs), _lib.dptr(volume),
+                                  alpha, float(amplitude), float(neighbour_threshold), int(n_terms), int(bool(centre_atoms)),
+                                  _lib.dptr(moments), _lib.dptr(frames), stream), "mcg_shape_frames")
+    return (moments, frames, counts) if with_counts else (moments, frames)
+
+
+def check_n_nodes(n_nodes: torch.Tensor, B: int, N: int) -> None:
+    """B atom counts, each in [0, N] (the kernels read them from device memory and cannot report a bad one)."""
+    n = torch.as_tensor(n_nodes).reshape(-1)
+    if n.numel() != B:
+        raise ValueError(f"n_nodes holds {n.numel()} counts for a batch of {B}")
+    if B and (int(n.min()) < 0 or int(n.max()) > N):
+        raise ValueError(f"n_nodes must lie in [0, {N}] (the padded width), got {int(n.min())}..{int(n.max())}")
+
+
+def check_reference_atoms(n_ref: int) -> None:
+    if n_ref < 3 or n_ref > MAX_SCORED_ATOMS:
+        raise ValueError(f"shape scoring needs a reference of 3 to {MAX_SCORED_ATOMS} heavy atoms, got {n_ref}")
+
+
+@torch.no_grad()
+def shape_scores(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor, device=None
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(best [B], orientation [B]) on the device: the shape Tanimoto `evaluate_shape` reports for every sample
+    (`evaluate_samples`, cheminformatics/pipeline.py:30-85), with the principal frames of the reference and of the samples
+    from the HIP kernels (`shape_frames_hip`, reference = row 0 of the same launch) and the four-orientation search of
+    `mcg_shape_tanimoto`.  A sample's score depends on its own coordinates and the reference only."""
+    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
+    ref = torch.as_tensor(reference_coord, dtype=torch.float32).cpu()
+    n_ref = int(ref.shape[0])
+    check_reference_atoms(n_ref)
+    B = int(coords.shape[0])
+    if B == 0:
+        return torch.empty(0, device=dev), torch.empty(0, dtype=torch.long, device=dev)
+    check_n_nodes(n_nodes, B, int(coords.shape[1]))         # before the reference widens the batch
+    N = max(int(coords.shape[1]), n_ref)
+    if N > MAX_SCORED_ATOMS:
+        raise ValueError(f"shape scoring takes at most {MAX_SCORED_ATOMS} atoms per molecule, got a padded width of {N}")
+    x = torch.zeros(B + 1, N, 3, device=dev)
+    x[0, :n_ref] = ref.to(dev)
+    x[1:, : coords.shape[1]] = coords.to(dev, torch.float32)
+    nn = torch.cat([torch.tensor([n_ref], dtype=torch.int32, device=dev), n_nodes.to(dev, torch.int32).reshape(B)])
+    _, frames = shape_frames_hip(x, nn, dev, centre_atoms=True)
+    _, best, which = shape_tanimoto_batch(frames[0, :n_ref], frames[1:], nn[1:], dev)
+    return best, which
+
+
+def select_scored(scores: List[float], sample_ids: List[int], top_k: Optional[int] = None,
+                  min_shape_tanimoto: Optional[float] = None) -> List[int]:
+    """Positions of the molecules to keep: score >= `min_shape_tanimoto`, then the `top_k` best, in descending score
+    order with ties going to the lower sample id.  A NaN score (a molecule with no overlap with the reference grid at all)
+    ranks last and passes no threshold."""
+    keep = [i for i, s in enumerate(scores) if min_shape_tanimoto is None or s >= min_shape_tanimoto]
+    keep.sort(key=lambda i: (-scores[i] if scores[i] == scores[i] else math.inf, sample_ids[i]))
+    return keep if top_k is None else keep[:top_k]
+
+
+def mol_heavy_coords(mol) -> torch.Tensor:
+    """Heavy-atom coordinates [n,3] fp32 of an RDKit Mol (or anything with `GetConformer().GetPositions()`), as
+    `evaluate_samples` reads them after `RemoveHs`."""
+    import numpy as np
+    pos = torch.as_tensor(np.asarray(mol.GetConformer().GetPositions(), dtype=np.float64)).to(torch.float32)
+    if hasattr(mol, "GetAtoms"):
+        heavy = [a.GetAtomicNum() != 1 for a in mol.GetAtoms()]
+        if not all(heavy):
+            pos = pos[torch.tensor(heavy)]
+    return pos.reshape(-1, 3)
+
+
+def padded_coords(coord_list: List[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-molecule [n_i,3] coordinates -> (padded [B, max n, 3], n_nodes [B])."""
+    n = torch.tensor([int(c.shape[0]) for c in coord_list], dtype=torch.int32)
+    out = torch.zeros(len(coord_list), int(n.max()) if len(coord_list) else 0, 3)
+    for b, c in enumerate(coord_list):
+        out[b, : c.shape[0]] = c
+    return out, n
 
 
 def evaluate_samples(reference, samples, generator=None, device=None):

@@ -32,11 +32,16 @@ forced by the scope of this build:
     initialised `torch.distributed` group (one process per GPU, one gather at the end);
   * `sample_seed` (opt-in, every generation entry): molecule i's size and every noise draw are a function of
     (sample_seed, i) alone - the same molecule in any batch, at any row, on any rank.  Seeded calls
-    consume neither the CPU nor the device torch RNG.  Default (None): the reference's torch draw order, unchanged.
+    consume neither the CPU nor the device torch RNG.  Default (None): the reference's torch draw order, unchanged;
+  * `shape_scores`, `top_k`, `min_shape_tanimoto` (opt-in, every generation entry): every returned molecule carries the
+    Gaussian-volume shape Tanimoto of its returned heavy-atom coordinates against the reference (what `evaluate_samples`
+    reports), computed on the GPU without RDKit (`cheminformatics.shape_scores`); `top_k` / `min_shape_tanimoto` keep
+    the best / those above a threshold.  Off by default: nothing changes.
 """
 from __future__ import annotations
 
 import contextlib
+import operator
 import os
 import time
 import warnings
@@ -271,15 +276,19 @@ class MLConformerGenerator(torch.nn.Module):
         return mols
 
     # ------------------------------------------------------------------ full pipeline
+    @staticmethod
+    def _reference_coord(reference_conformer) -> torch.Tensor:
+        """Heavy-atom coordinates [n,3] fp32 of a reference conformer (RDKit Mol, mol block or tensor)."""
+        if HAVE_RDKIT and not isinstance(reference_conformer, (str, torch.Tensor)):
+            mol = Chem.RemoveHs(reference_conformer)                           # :302-307
+            return torch.tensor(mol.GetConformer().GetPositions(), dtype=torch.float32)
+        if isinstance(reference_conformer, str):
+            return parse_molblock_heavy_atoms(reference_conformer)[0]
+        return torch.as_tensor(reference_conformer, dtype=torch.float32)
+
     def _reference_context(self, reference_conformer, reference_context, n_atoms):
         if reference_conformer is not None and reference_conformer is not False:
-            if HAVE_RDKIT and not isinstance(reference_conformer, (str, torch.Tensor)):
-                mol = Chem.RemoveHs(reference_conformer)                       # :302-307
-                ref_coord = torch.tensor(mol.GetConformer().GetPositions(), dtype=torch.float32)
-            elif isinstance(reference_conformer, str):
-                ref_coord, _ = parse_molblock_heavy_atoms(reference_conformer)
-            else:
-                ref_coord = torch.as_tensor(reference_conformer, dtype=torch.float32)
+            ref_coord = self._reference_coord(reference_conformer)
             ref_n_atoms = int(ref_coord.shape[0])
             ref_coord = ref_coord - torch.mean(ref_coord, dim=0)              # :310-311
             ref_context, _ = get_context_shape(ref_coord)
@@ -291,6 +300,57 @@ class MLConformerGenerator(torch.nn.Module):
             return reference_context, n_atoms
         raise ValueError(
             "Either a reference RDkit Mol object or context as torch.Tensor should be provided for generation.")
+
+    def _scoring_reference(self, reference_conformer, shape_scores: bool, top_k: Optional[int],
+                           min_shape_tanimoto: Optional[float]) -> Optional[torch.Tensor]:
+        """The reference's heavy-atom coordinates when the call scores (`shape_scores`, or `top_k` / `min_shape_tanimoto`,
+        which imply it), else None.  Every refusal happens here, before any device work."""
+        if not (shape_scores or top_k is not None or min_shape_tanimoto is not None):
+            return None
+        if top_k is not None:
+            try:
+                k = operator.index(top_k)          # any integer type (numpy.int64 ...); not bool, not float
+            except TypeError:
+                k = None
+            if k is None or isinstance(top_k, bool) or k < 1:
+                raise ValueError(f"top_k must be an integer >= 1, got {top_k!r}")
+        if min_shape_tanimoto is not None and not (0.0 <= float(min_shape_tanimoto) <= 1.0):
+            raise ValueError(f"min_shape_tanimoto must lie in [0, 1], got {min_shape_tanimoto!r}")
+        if reference_conformer is None or reference_conformer is False:
+            raise ValueError("shape scores need a reference conformer to score against; a bare reference_context has "
+                             "no coordinates")
+        if isinstance(getattr(self, "finisher", None), host_pool.TaskRef):
+            raise ValueError("shape scores cannot be combined with a custom finisher: its results carry no coordinates "
+                             "this package can read")
+        ref_coord = self._reference_coord(reference_conformer)
+        from .cheminformatics import check_reference_atoms
+        check_reference_atoms(int(ref_coord.shape[0]))
+        return ref_coord
+
+    def _score_coords(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
+        """Shape Tanimoto [B] (device) of padded heavy-atom coordinates against the reference."""
+        from .cheminformatics import shape_scores
+        return shape_scores(ref_coord, coords, n_nodes, self.device)[0]
+
+    def _score_mols(self, ref_coord: torch.Tensor, mols: List) -> List[Optional[float]]:
+        """Shape Tanimoto of finished Mols' heavy-atom conformer positions (None where a molecule was dropped), in ONE
+        batched device call."""
+        from .cheminformatics import mol_heavy_coords, padded_coords
+        live = [k for k, m in enumerate(mols) if m is not None]
+        out: List[Optional[float]] = [None] * len(mols)
+        if live:
+            coords, n = padded_coords([mol_heavy_coords(mols[k]) for k in live])
+            for k, v in zip(live, self._score_coords(ref_coord, coords, n).cpu().tolist()):
+                out[k] = float(v)
+        return out
+
+    @staticmethod
+    def _select(mols: List, scores: List[float], sample_ids: List[int], top_k: Optional[int],
+                min_shape_tanimoto: Optional[float]) -> List:
+        if top_k is None and min_shape_tanimoto is None:
+            return mols
+        from .cheminformatics import select_scored
+        return [mols[i] for i in select_scored(scores, sample_ids, top_k, min_shape_tanimoto)]
 
     def _executor(self):
         """Where the poolable host tasks run: the process-wide `HostPool` with `n_host_workers` workers and this generator's
@@ -393,15 +453,24 @@ class MLConformerGenerator(torch.nn.Module):
                             reference_context: torch.Tensor = None, n_atoms: int = None,
                             optimise_geometry: bool = True, resample_steps: int = 0, fixed_fragment=None,
                             inertial_fragment_matching: bool = True, blend_power: int = 3,
-                            ifm_diffusion_level: int = 50, sample_seed: Optional[int] = None) -> List:
+                            ifm_diffusion_level: int = 50, sample_seed: Optional[int] = None, shape_scores: bool = False,
+                            top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None) -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
         records that pass the labelled valence / single-fragment proxy of `mcg_bond_writeback` (no MMFF: warned once).
         Each record says which sample it is (`GeneratedMolecule.sample_id`).  `sample_seed`: the keyed stream of
-        `edm_tensors` - sample i is the same molecule whatever `n_samples`; the Mols carry the int property `sample_id`."""
+        `edm_tensors` - sample i is the same molecule whatever `n_samples`; the Mols carry the int property `sample_id`.
+        `shape_scores=True`: every returned molecule carries the shape Tanimoto of its RETURNED heavy-atom coordinates
+        against the reference (`GeneratedMolecule.shape_tanimoto`, the Mols' double property `shape_tanimoto`) - what
+        `evaluate_samples(reference, [mol])` reports, computed on the GPU (`cheminformatics.shape_scores`); sample order.
+        `min_shape_tanimoto` / `top_k` (either implies scoring): keep the molecules scoring >= the threshold, then the k
+        best, in descending score order (ties: lower sample id); `last_valid_fraction` is taken before this selection.
+        Refused with ValueError before any device work: scoring without a reference conformer, a reference outside 3..64
+        heavy atoms, top_k < 1, a threshold outside [0, 1], and a custom finisher."""
         if sample_seed is not None:
             seeding.check_seed(sample_seed)
+        ref_coord = self._scoring_reference(reference_conformer, shape_scores, top_k, min_shape_tanimoto)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
         if sample_seed is None:       # the positional call of before: a stub of `_generate_shard` need not know the seed
             res = self._generate_shard(ref_context, ref_n_atoms, variance, None, n_samples, resample_steps, fixed_fragment,
@@ -416,12 +485,22 @@ class MLConformerGenerator(torch.nn.Module):
             if sample_seed is not None:
                 from . import rdkit_finish
                 rdkit_finish.tag_sample_ids(done, range(len(done)))
-            kept = [m for m in done if m is not None]
-            self.last_valid_fraction = len(kept) / len(done) if done else 0.0
-            return kept
-        mols = molecules_from_tensors(res["x"], res["elements"], res["bond"], res["n_nodes"], res["valid"])   # single D2H
+            live = [i for i, m in enumerate(done) if m is not None]
+            self.last_valid_fraction = len(live) / len(done) if done else 0.0
+            if ref_coord is None:
+                return [done[i] for i in live]
+            from . import rdkit_finish
+            scores = self._score_mols(ref_coord, done)
+            rdkit_finish.tag_shape_scores(done, scores)
+            return self._select([done[i] for i in live], [scores[i] for i in live], live, top_k, min_shape_tanimoto)
+        scores = None if ref_coord is None else self._score_coords(ref_coord, res["x"], res["n_nodes"])
+        mols = molecules_from_tensors(res["x"], res["elements"], res["bond"], res["n_nodes"], res["valid"],
+                                      shape_tanimoto=scores)                                            # single D2H
         kept, self.last_valid_fraction = _finish(mols, optimise_geometry, use_rdkit=False)    # no finisher: the proxy
-        return kept
+        if ref_coord is None:
+            return kept
+        return self._select(kept, [m.shape_tanimoto for m in kept], [m.sample_id for m in kept], top_k,
+                            min_shape_tanimoto)
 
     @torch.no_grad()
     def generate_conformers_sharded(self, reference_conformer=None, n_samples: int = 10, variance: int = 2,
@@ -430,7 +509,8 @@ class MLConformerGenerator(torch.nn.Module):
                                     inertial_fragment_matching: bool = True, blend_power: int = 3,
                                     ifm_diffusion_level: int = 50, group=None, seed: Optional[int] = None,
                                     gather: str = "all", balance: str = "cost",
-                                    sample_seed: Optional[int] = None) -> List:
+                                    sample_seed: Optional[int] = None, shape_scores: bool = False,
+                                    top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None) -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -445,13 +525,18 @@ class MLConformerGenerator(torch.nn.Module):
         gathered as objects.  Without an initialised group this is `generate_conformers`.
         `sample_seed` (instead of `seed`): the keyed stream of `edm_tensors` - every rank computes the keyed sizes of all
         `n_samples` itself (no broadcast), generates its shard with the shard's global indices as `sample_ids` and seeds
-        no generator, so sample i is the same molecule on any world size and under either `balance`."""
+        no generator, so sample i is the same molecule on any world size and under either `balance`.
+        `shape_scores`, `top_k`, `min_shape_tanimoto`: as in `generate_conformers`.  Every rank scores ITS OWN shard on its
+        own GPU before the gather (the scores travel with the result tensors, or next to the finished Mols); the
+        selection runs on what each rank returns: with gather="all" every rank returns the same selection, with
+        gather="rank0" rank 0 selects from the whole batch and every other rank within its own shard."""
         if gather not in ("all", "rank0"):
             raise ValueError("gather must be 'all' or 'rank0'")
         if sample_seed is not None:
             if seed is not None:
                 raise ValueError("pass either seed (per-rank device generator) or sample_seed (keyed stream), not both")
             seeding.check_seed(sample_seed)
+        ref_coord = self._scoring_reference(reference_conformer, shape_scores, top_k, min_shape_tanimoto)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)
         hi_n = min(ref_n_atoms + variance, self.max_n_nodes)
@@ -460,6 +545,7 @@ class MLConformerGenerator(torch.nn.Module):
         # path through the collectives (an EMPTY shard has no stage of its own making)
         finishing = getattr(self, "finisher", None) is not None
         finished: List = [None]
+        finished_scores: List = [None]
 
         def run_shard(sizes_shard, index):
             keyed = () if sample_seed is None else (sample_seed, index)
@@ -475,6 +561,10 @@ class MLConformerGenerator(torch.nn.Module):
                 if len(done) != int(index.numel()):
                     raise ValueError(f"the finish returned {len(done)} results for a shard of {int(index.numel())}")
                 finished[0] = done
+                if ref_coord is not None:
+                    finished_scores[0] = self._score_mols(ref_coord, done)
+            elif ref_coord is not None:       # one more per-sample tensor for the gather
+                res = dict(res, shape_tanimoto=self._score_coords(ref_coord, res["x"], res["n_nodes"]))
             return res
 
         def seed_device(s):
@@ -498,29 +588,45 @@ class MLConformerGenerator(torch.nn.Module):
         _, rank = mcg_dist.world_and_rank(group)
         row_ids = shards[rank] if (dst is not None and rank != dst and len(shards) > 1) else None
         if finishing:                         # RDKit's gate: this rank's shard was finished above, the Mols travel as objects
-            done = mcg_dist.gather_objects(finished[0], shards, group, dst)
+            if ref_coord is None:
+                done = mcg_dist.gather_objects(finished[0], shards, group, dst)
+            else:                             # the scores travel next to the Mols and are attached after the gather
+                pairs = mcg_dist.gather_objects(list(zip(finished[0], finished_scores[0])), shards, group, dst)
+                done, scores = [p[0] for p in pairs], [p[1] for p in pairs]
+            ids = list(range(len(done))) if row_ids is None else row_ids.tolist()
             if sample_seed is not None:
                 from . import rdkit_finish
-                rdkit_finish.tag_sample_ids(done, range(len(done)) if row_ids is None else row_ids.tolist())
+                rdkit_finish.tag_sample_ids(done, ids)
             self.last_host_assembly_ms = 0.0
-            kept = [m for m in done if m is not None]
-            self.last_valid_fraction = len(kept) / len(done) if done else 0.0
-            return kept
+            live = [i for i, m in enumerate(done) if m is not None]
+            self.last_valid_fraction = len(live) / len(done) if done else 0.0
+            if ref_coord is None:
+                return [done[i] for i in live]
+            from . import rdkit_finish
+            rdkit_finish.tag_shape_scores(done, scores)
+            return self._select([done[i] for i in live], [scores[i] for i in live], [ids[i] for i in live], top_k,
+                                min_shape_tanimoto)
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)       # (the D2H copies below would wait for the device anyway: keep that out of the figure)
         t0 = time.perf_counter()
         mols = molecules_from_tensors(res["x"], res["elements"], res["bond"], res["n_nodes"], res["valid"],
-                                      sample_ids=row_ids)
+                                      sample_ids=row_ids, shape_tanimoto=res.get("shape_tanimoto"))
         self.last_host_assembly_ms = (time.perf_counter() - t0) * 1e3      # D2H of the gathered tensors + record views
         kept, self.last_valid_fraction = _finish(mols, optimise_geometry, use_rdkit=False)    # no finisher: the proxy
-        return kept
+        if ref_coord is None:
+            return kept
+        return self._select(kept, [m.shape_tanimoto for m in kept], [m.sample_id for m in kept], top_k,
+                            min_shape_tanimoto)
 
     @torch.no_grad()
     def forward(self, reference_conformer=None, n_samples: int = 10, variance: int = 2,
                 reference_context: torch.Tensor = None, n_atoms: int = None, optimise_geometry: bool = True,
                 resample_steps: int = 0, fixed_fragment=None, inertial_fragment_matching: bool = True,
-                blend_power: int = 3, ifm_diffusion_level: int = 50, sample_seed: Optional[int] = None) -> List:
+                blend_power: int = 3, ifm_diffusion_level: int = 50, sample_seed: Optional[int] = None,
+                shape_scores: bool = False, top_k: Optional[int] = None,
+                min_shape_tanimoto: Optional[float] = None) -> List:
         return self.generate_conformers(reference_conformer, n_samples, variance, reference_context, n_atoms,
                                         optimise_geometry, resample_steps, fixed_fragment,
                                         inertial_fragment_matching, blend_power, ifm_diffusion_level,
-                                        sample_seed=sample_seed)
+                                        sample_seed=sample_seed, shape_scores=shape_scores, top_k=top_k,
+                                        min_shape_tanimoto=min_shape_tanimoto)

@@ -41,21 +41,32 @@ class GeneratedMolecule:
     4 aromatic; `valid` bool.  Records built by `molecules_from_tensors` are LAZY views into the batch's host tensors: the
     per-molecule slices are taken on first access, so assembling a batch costs one object per molecule (2 048 molecules:
     a few ms instead of 70-170 ms of slicing + cloning on every rank of a sharded call).  `sample_id`: which sample of
-    its generation call the record is (invalid molecules are dropped, so a kept record's position says nothing)."""
-    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid")
+    its generation call the record is (invalid molecules are dropped, so a kept record's position says nothing).
+    `shape_tanimoto`: its shape score against the reference when the call asked for scores, else None."""
+    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_score")
 
     def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True,
                  sample_id: Optional[int] = None):
         self._z, self._coords, self._bonds, self.valid = list(atomic_numbers), coords, bond_orders, bool(valid)
         self._batch, self._b, self._sid = None, -1, sample_id
+        self._score = None
 
     @classmethod
-    def _view(cls, batch: _HostBatch, b: int, valid: bool, sample_id: Optional[int] = None) -> "GeneratedMolecule":
+    def _view(cls, batch: _HostBatch, b: int, valid: bool, sample_id: Optional[int] = None,
+              score: Optional[float] = None) -> "GeneratedMolecule":
         m = cls.__new__(cls)
         m._z = m._coords = m._bonds = None
         m.valid, m._batch, m._b = valid, batch, b
         m._sid = b if sample_id is None else sample_id
+        m._score = score
         return m
+
+    @property
+    def shape_tanimoto(self) -> Optional[float]:
+        """Gaussian-volume shape Tanimoto of these coordinates against the call's reference - what
+        `evaluate_samples(reference, [mol])` reports - when the call scored (`shape_scores`, `top_k`,
+        `min_shape_tanimoto`); None otherwise."""
+        return self._score
 
     @property
     def sample_id(self) -> Optional[int]:
@@ -222,16 +233,20 @@ def bond_writeback_hip(bond: torch.Tensor, elements: torch.Tensor, n_nodes: torc
 
 
 def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: torch.Tensor, n_nodes: torch.Tensor,
-                           valid: torch.Tensor, sample_ids: Optional[Sequence[int]] = None) -> List[GeneratedMolecule]:
+                           valid: torch.Tensor, sample_ids: Optional[Sequence[int]] = None,
+                           shape_tanimoto: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
     (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
-    (default: b, the row IS the sample index)."""
+    (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records)."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
     view = GeneratedMolecule._view
-    if sample_ids is None:
+    if sample_ids is None and shape_tanimoto is None:
         return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
-    ids = [int(i) for i in (sample_ids.tolist() if torch.is_tensor(sample_ids) else sample_ids)]
-    return [view(batch, b, bool(v), ids[b]) for b, v in enumerate(valid.cpu().tolist())]
+    flags = valid.cpu().tolist()
+    ids = list(range(len(flags))) if sample_ids is None else \
+        [int(i) for i in (sample_ids.tolist() if torch.is_tensor(sample_ids) else sample_ids)]
+    scores = [None] * len(flags) if shape_tanimoto is None else [float(v) for v in shape_tanimoto.cpu().tolist()]
+    return [view(batch, b, bool(v), ids[b], scores[b]) for b, v in enumerate(flags)]
 
 
 def assemble_molecules(x: torch.Tensor, elements: torch.Tensor, bond: torch.Tensor, n_nodes: torch.Tensor

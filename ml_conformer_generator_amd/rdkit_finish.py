@@ -145,3 +145,11 @@ def tag_sample_ids(mols: Sequence, sample_ids: Sequence[int]) -> None:
     for m, sid in zip(mols, sample_ids):
         if m is not None and hasattr(m, "SetIntProp"):
             m.SetIntProp("sample_id", int(sid))
+
+
+def tag_shape_scores(mols: Sequence, scores: Sequence[Optional[float]]) -> None:
+    """Set the double property `shape_tanimoto` on every Mol of `mols` (None = dropped); `scores[k]` belongs to `mols[k]`.
+    Set after the object gather: RDKit does not pickle Mol properties by default."""
+    for m, sc in zip(mols, scores):
+        if m is not None and sc is not None and hasattr(m, "SetDoubleProp"):
+            m.SetDoubleProp("shape_tanimoto", float(sc))
