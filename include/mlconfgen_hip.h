@@ -288,6 +288,32 @@ int mcg_shape_frames(const float* coords, const int32_t* n_nodes_dev, int B, int
                      const float* eigvecs, const double* volume, double alpha, double amplitude, float neighbour_threshold,
                      int n_terms, int centre_atoms, float* moments, float* frames, void* stream);
 
+/* ---- Pose on the reference: the rigid, proper transform that puts each candidate onto the
+ * reference conformer's own coordinates, from the frames above and the four-orientation search.
+ *   mcg_shape_frames_tf: mcg_shape_frames (same outputs, bit for bit) plus xform[B,12] = M row-major (M = V P: the
+ *                        eigenvectors, then the descending-moment axis permutation), then t (atom mean + shape centre):
+ *                        frames = (coords - t) @ M on the real rows.  det(M) = +-1.
+ *   mcg_shape_overlay:   ref_frame[n_ref,3] / ref_xform[12] (M_r, t_r) and frames[B,N,3] / xform[B,12] (M_s, t_s) from
+ *                        mcg_shape_frames_tf.  Handedness: M_s' = M_s diag(1,1,-1) where det(M_s) det(M_r) < 0
+ *                        (flipped[b] = 1), else M_s' = M_s.  The frame (coords - t_s) @ M_s' is scored in the four
+ *                        orientations rot[4,9] (identity, pi about x, y, z: proper) on the grid axes[3,n] of ref_frame,
+ *                        as mcg_shape_tanimoto does (score[B*4], optional: NULL = not wanted; bit-identical to
+ *                        mcg_shape_tanimoto on the handedness-fixed frames); best[b] / which[b] = the first maximum.
+ *                        pose[B,12] = Q row-major, then d, with Q = M_s' R_which M_r^T (det +1) and d = t_r - t_s @ Q;
+ *                        posed[B,N,3] = z_best @ M_r^T + t_r (= coords @ Q + d) on the real rows, zero on padded rows.
+ *                        A row whose frame or xform is not finite: NaN best, which = -1, NaN pose and posed rows; the
+ *                        other rows are unaffected.  f_scratch[n^3]; one 256-lane workgroup per candidate.
+ * MCG_ERR_ARG, nothing launched: a null required buffer, B < 1, N outside 1..64, n_ref outside 3..64 (overlay), n < 2,
+ * and the argument errors of mcg_shape_frames. */
+int mcg_shape_frames_tf(const float* coords, const int32_t* n_nodes_dev, int B, int N, const float* centre,
+                        const float* eigvecs, const double* volume, double alpha, double amplitude,
+                        float neighbour_threshold, int n_terms, int centre_atoms, float* moments, float* frames,
+                        float* xform, void* stream);
+int mcg_shape_overlay(const float* ref_frame, int n_ref, const float* ref_xform, const float* frames, const float* xform,
+                      const int32_t* n_nodes_dev, int B, int N, const float* rot, const float* axes, int n, float alpha,
+                      float amplitude, float* f_scratch, float* score, float* best, int32_t* which, int32_t* flipped,
+                      float* pose, float* posed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

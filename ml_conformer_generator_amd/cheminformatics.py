@@ -215,13 +215,15 @@ MAX_SCORED_ATOMS = 64          # csrc/mcg_shape_frames.hip: one 64-bit neighbour
 @torch.no_grad()
 def shape_frames_hip(coords: torch.Tensor, n_nodes: torch.Tensor, device=None, amplitude: float = AMPLITUDE,
                      atom_radius: float = ATOM_RADIUS, n_terms: int = 6, neighbour_threshold: float = 2 * AMPLITUDE,
-                     centre_atoms: bool = False, with_counts: bool = False):
+                     centre_atoms: bool = False, with_counts: bool = False, xform_out: Optional[torch.Tensor] = None):
     """`shape_quadrupole_batch` through the HIP kernels (`mcg_shape_moments` -> host `eigh` -> `mcg_shape_frames`):
     principal moments [B,3] and frames [B,N,3] on the device, bit-identical for a molecule whatever its batch, row or
     padded width.  `centre_atoms`: subtract the real atoms' mean first (what `evaluate_shape` does to its inputs).
     `with_counts`: also the exact number of cliques of order 2..n_terms per molecule, int64 [B, n_terms-1].
     A molecule whose moment tensor is not finite (non-finite coordinates, no atoms) gets NaN moments and frames; the
-    other molecules of the batch are unaffected.  `n_nodes` outside [0, N] is refused with ValueError."""
+    other molecules of the batch are unaffected.  `n_nodes` outside [0, N] is refused with ValueError.
+    `xform_out` (float32 [B,12] on the device): also the frame transform (`mcg_shape_frames_tf`): M [3,3] row-major, then
+    t [3], with frames = (coords - t) @ M on the real rows."""
     dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
     x = coords.to(dev, torch.float32).contiguous()
     B, N, _ = x.shape
@@ -249,9 +251,13 @@ def shape_frames_hip(coords: torch.Tensor, n_nodes: torch.Tensor, device=None, a
         t[bad] = torch.eye(3)          # placeholder: such a molecule's centre and volume are NaN, so are its frames
     _, vecs = torch.linalg.eigh(t)                                       # the reference's host LAPACK path (:143-144)
     vecs = vecs.contiguous().to(dev)
-    _lib.check(L.mcg_shape_frames(_lib.dptr(x), _lib.dptr(nn), B, N, _lib.dptr(centre), _lib.dptr(vecs), _lib.dptr(volume),
-                                  alpha, float(amplitude), float(neighbour_threshold), int(n_terms), int(bool(centre_atoms)),
-                                  _lib.dptr(moments), _lib.dptr(frames), stream), "mcg_shape_frames")
+    args = (_lib.dptr(x), _lib.dptr(nn), B, N, _lib.dptr(centre), _lib.dptr(vecs), _lib.dptr(volume), alpha,
+            float(amplitude), float(neighbour_threshold), int(n_terms), int(bool(centre_atoms)), _lib.dptr(moments),
+            _lib.dptr(frames))
+    if xform_out is None:
+        _lib.check(L.mcg_shape_frames(*args, stream), "mcg_shape_frames")
+    else:
+        _lib.check(L.mcg_shape_frames_tf(*args, _lib.dptr(xform_out), stream), "mcg_shape_frames_tf")
     return (moments, frames, counts) if with_counts else (moments, frames)
 
 
@@ -294,6 +300,121 @@ def shape_scores(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: t
     _, frames = shape_frames_hip(x, nn, dev, centre_atoms=True)
     _, best, which = shape_tanimoto_batch(frames[0, :n_ref], frames[1:], nn[1:], dev)
     return best, which
+
+
+def _orientations() -> torch.Tensor:
+    """The four orientations of `evaluate_samples`' search: identity, pi about x, y, z (all proper), [4,3,3] fp32."""
+    pi = torch.pi
+    return torch.stack([rotation_matrix(a) for a in (torch.zeros(3), torch.tensor([pi, 0, 0]), torch.tensor([0, pi, 0]),
+                                                     torch.tensor([0, 0, pi]))]).to(torch.float32)
+
+
+@torch.no_grad()
+def shape_overlay(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor, device=None,
+                  with_scores: bool = False) -> Dict[str, torch.Tensor]:
+    """Every sample posed onto the reference conformer, in the reference's own coordinates.
+    The principal frames of the reference (row 0) and of the samples come from one `mcg_shape_frames_tf` launch; the
+    sample frame's handedness is made to match the reference's (so the pose is a rotation, never a mirror), the four
+    orientations of `evaluate_samples` are scored on the reference's grid and the best becomes a rigid pose, all in one
+    `mcg_shape_overlay` launch.  Returns device tensors:
+      coords [B,N,3]       posed: coords @ rotation + translation on the real rows (zero on padded rows);
+      rotation [B,3,3]     proper (det +1), applied to row vectors;  translation [B,3];
+      tanimoto [B]         the shape Tanimoto of the pose as placed;
+      orientation [B]      which of the four orientations won (-1: failed row);
+      flipped [B] bool     whether the frame's smallest-moment axis was flipped to match the reference's handedness;
+      (with_scores) scores [B,4]  the four orientations' scores.
+    A sample whose frame is not finite (non-finite coordinates, no atoms) keeps its input coordinates and gets a NaN
+    rotation, translation and tanimoto and orientation -1; the other samples are unaffected and bit-identical whatever
+    their batch.  Refuses what `shape_scores` refuses."""
+    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
+    ref = torch.as_tensor(reference_coord, dtype=torch.float32).cpu()
+    n_ref = int(ref.shape[0])
+    check_reference_atoms(n_ref)
+    B, W = int(coords.shape[0]), int(coords.shape[1])
+    if B == 0:
+        out = dict(coords=torch.zeros(0, W, 3, device=dev), rotation=torch.zeros(0, 3, 3, device=dev),
+                   translation=torch.zeros(0, 3, device=dev), tanimoto=torch.zeros(0, device=dev),
+                   orientation=torch.zeros(0, dtype=torch.long, device=dev),
+                   flipped=torch.zeros(0, dtype=torch.bool, device=dev))
+        if with_scores:
+            out["scores"] = torch.zeros(0, 4, device=dev)
+        return out
+    check_n_nodes(n_nodes, B, W)
+    N = max(W, n_ref)
+    if N > MAX_SCORED_ATOMS:
+        raise ValueError(f"shape scoring takes at most {MAX_SCORED_ATOMS} atoms per molecule, got a padded width of {N}")
+    cand = coords.to(dev, torch.float32)
+    x = torch.zeros(B + 1, N, 3, device=dev)
+    x[0, :n_ref] = ref.to(dev)
+    x[1:, :W] = cand
+    nn = torch.cat([torch.tensor([n_ref], dtype=torch.int32, device=dev), n_nodes.to(dev, torch.int32).reshape(B)])
+    xform = torch.empty(B + 1, 12, device=dev)
+    _, frames = shape_frames_hip(x, nn, dev, centre_atoms=True, xform_out=xform)
+    ref_frame = frames[0, :n_ref].contiguous()
+    axes = _grid_axes(ref_frame.cpu(), 40).to(dev).contiguous()
+    rots = _orientations().reshape(4, 9).to(dev).contiguous()
+    f = torch.empty(40 ** 3, device=dev)
+    scores = torch.empty(B, 4, device=dev) if with_scores else None
+    best = torch.empty(B, device=dev)
+    which = torch.empty(B, dtype=torch.int32, device=dev)
+    flipped = torch.empty(B, dtype=torch.int32, device=dev)
+    pose = torch.empty(B, 12, device=dev)
+    posed = torch.empty(B, N, 3, device=dev)
+    _lib.check(_lib.lib().mcg_shape_overlay(_lib.dptr(ref_frame), n_ref, _lib.dptr(xform), _lib.dptr(frames[1:]),
+                                            _lib.dptr(xform[1:]), _lib.dptr(nn[1:]), B, N, _lib.dptr(rots),
+                                            _lib.dptr(axes), 40, float(ALPHA), float(AMPLITUDE), _lib.dptr(f),
+                                            _lib.dptr(scores), _lib.dptr(best), _lib.dptr(which), _lib.dptr(flipped),
+                                            _lib.dptr(pose), _lib.dptr(posed), _lib.current_stream_ptr(dev)),
+               "mcg_shape_overlay")
+    failed = (which < 0).view(B, 1, 1)
+    out = dict(coords=torch.where(failed, cand, posed[:, :W]), rotation=pose[:, :9].reshape(B, 3, 3),
+               translation=pose[:, 9:], tanimoto=best, orientation=which.long(), flipped=flipped.bool())
+    if with_scores:
+        out["scores"] = scores
+    return out
+
+
+def pose_mols(reference_coord: torch.Tensor, mols: List, device=None, overlay_fn=None) -> List:
+    """Pose finished Mols onto the reference in ONE batched `shape_overlay` call: the pose comes from each Mol's heavy-atom
+    conformer positions (`mol_heavy_coords`) and is applied to EVERY conformer position, hydrogens included; each Mol
+    gets the double property `overlay_tanimoto`.  Works on anything with `GetConformer()` whose conformer has
+    `GetPositions()` and `SetAtomPosition(i, point)`.  Returns per Mol (overlay_tanimoto, rotation [3,3],
+    translation [3]) on the host, or None for a dropped Mol (None in `mols`); a Mol whose pose failed is left where it
+    was, with a NaN score and a None pose: (nan, None, None).  `overlay_fn(reference, coords, n_nodes)`: what poses the
+    padded coordinates (default: `shape_overlay` on `device`)."""
+    live = [k for k, m in enumerate(mols) if m is not None]
+    out: List = [None] * len(mols)
+    if not live:
+        return out
+    coords, n = padded_coords([mol_heavy_coords(mols[k]) for k in live])
+    res = overlay_fn(reference_coord, coords, n) if overlay_fn is not None else \
+        shape_overlay(reference_coord, coords, n, device)
+    rot, trans, tan, which = (res["rotation"].cpu().double(), res["translation"].cpu().double(), res["tanimoto"].cpu(),
+                              res["orientation"].cpu())
+    for j, k in enumerate(live):
+        score = float(tan[j])
+        if int(which[j]) < 0:
+            out[k] = (score, None, None)
+        else:
+            apply_pose(mols[k], rot[j], trans[j])
+            out[k] = (score, rot[j].float(), trans[j].float())
+        if hasattr(mols[k], "SetDoubleProp"):
+            mols[k].SetDoubleProp("overlay_tanimoto", score)
+    return out
+
+
+def apply_pose(mol, rotation: torch.Tensor, translation: torch.Tensor) -> None:
+    """Move every conformer position p of `mol` to p @ rotation + translation (in fp64)."""
+    import numpy as np
+    conf = mol.GetConformer()
+    pos = np.asarray(conf.GetPositions(), dtype=np.float64).reshape(-1, 3)
+    new = pos @ rotation.double().numpy() + translation.double().numpy()
+    try:
+        from rdkit.Geometry import Point3D
+    except ImportError:          # a stand-in Mol: any 3-sequence
+        Point3D = None
+    for i, p in enumerate(new.tolist()):
+        conf.SetAtomPosition(i, Point3D(*p) if Point3D is not None else tuple(p))
 
 
 def select_scored(scores: List[float], sample_ids: List[int], top_k: Optional[int] = None,

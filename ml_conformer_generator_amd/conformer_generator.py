@@ -36,7 +36,10 @@ forced by the scope of this build:
   * `shape_scores`, `top_k`, `min_shape_tanimoto` (opt-in, every generation entry): every returned molecule carries the
     Gaussian-volume shape Tanimoto of its returned heavy-atom coordinates against the reference (what `evaluate_samples`
     reports), computed on the GPU without RDKit (`cheminformatics.shape_scores`); `top_k` / `min_shape_tanimoto` keep
-    the best / those above a threshold.  Off by default: nothing changes.
+    the best / those above a threshold.  Off by default: nothing changes;
+  * `overlay` (opt-in, every generation entry): every returned molecule is posed onto the reference conformer, in the
+    reference's own coordinates, by a proper rigid transform found on the GPU (`cheminformatics.shape_overlay`).  Off
+    by default: nothing changes.
 """
 from __future__ import annotations
 
@@ -302,11 +305,12 @@ class MLConformerGenerator(torch.nn.Module):
             "Either a reference RDkit Mol object or context as torch.Tensor should be provided for generation.")
 
     def _scoring_reference(self, reference_conformer, shape_scores: bool, top_k: Optional[int],
-                           min_shape_tanimoto: Optional[float]) -> Optional[torch.Tensor]:
+                           min_shape_tanimoto: Optional[float], overlay: bool = False) -> Optional[torch.Tensor]:
         """The reference's heavy-atom coordinates when the call scores (`shape_scores`, or `top_k` / `min_shape_tanimoto`,
-        which imply it), else None.  Every refusal happens here, before any device work."""
-        if not (shape_scores or top_k is not None or min_shape_tanimoto is not None):
+        which imply it) or poses (`overlay`), else None.  Every refusal happens here, before any device work."""
+        if not (shape_scores or top_k is not None or min_shape_tanimoto is not None or overlay):
             return None
+        what = "shape scores" if not overlay else "overlay"
         if top_k is not None:
             try:
                 k = operator.index(top_k)          # any integer type (numpy.int64 ...); not bool, not float
@@ -317,10 +321,10 @@ class MLConformerGenerator(torch.nn.Module):
         if min_shape_tanimoto is not None and not (0.0 <= float(min_shape_tanimoto) <= 1.0):
             raise ValueError(f"min_shape_tanimoto must lie in [0, 1], got {min_shape_tanimoto!r}")
         if reference_conformer is None or reference_conformer is False:
-            raise ValueError("shape scores need a reference conformer to score against; a bare reference_context has "
-                             "no coordinates")
+            raise ValueError(f"a reference conformer is needed for {what}; a bare reference_context has no "
+                             "coordinates")
         if isinstance(getattr(self, "finisher", None), host_pool.TaskRef):
-            raise ValueError("shape scores cannot be combined with a custom finisher: its results carry no coordinates "
+            raise ValueError(f"{what} cannot be combined with a custom finisher: its results carry no coordinates "
                              "this package can read")
         ref_coord = self._reference_coord(reference_conformer)
         from .cheminformatics import check_reference_atoms
@@ -343,6 +347,22 @@ class MLConformerGenerator(torch.nn.Module):
             for k, v in zip(live, self._score_coords(ref_coord, coords, n).cpu().tolist()):
                 out[k] = float(v)
         return out
+
+    def _pose_coords(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor) -> dict:
+        """Padded heavy-atom coordinates posed onto the reference (`cheminformatics.shape_overlay`, device tensors)."""
+        from .cheminformatics import shape_overlay
+        return shape_overlay(ref_coord, coords, n_nodes, self.device)
+
+    def _pose_mols(self, ref_coord: torch.Tensor, mols: List) -> List:
+        """Finished Mols posed onto the reference in ONE batched device call, every conformer position moved (None where a
+        molecule was dropped); per Mol (overlay_tanimoto, rotation, translation)."""
+        from .cheminformatics import pose_mols
+        return pose_mols(ref_coord, mols, overlay_fn=self._pose_coords)
+
+    @staticmethod
+    def _pose_rows(ov: dict) -> torch.Tensor:
+        """[B,12]: rotation row-major, then translation (NaN where posing failed)."""
+        return torch.cat([ov["rotation"].reshape(-1, 9), ov["translation"].reshape(-1, 3)], dim=1)
 
     @staticmethod
     def _select(mols: List, scores: List[float], sample_ids: List[int], top_k: Optional[int],
@@ -454,7 +474,8 @@ class MLConformerGenerator(torch.nn.Module):
                             optimise_geometry: bool = True, resample_steps: int = 0, fixed_fragment=None,
                             inertial_fragment_matching: bool = True, blend_power: int = 3,
                             ifm_diffusion_level: int = 50, sample_seed: Optional[int] = None, shape_scores: bool = False,
-                            top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None) -> List:
+                            top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None,
+                            overlay: bool = False) -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
@@ -466,11 +487,22 @@ class MLConformerGenerator(torch.nn.Module):
         `evaluate_samples(reference, [mol])` reports, computed on the GPU (`cheminformatics.shape_scores`); sample order.
         `min_shape_tanimoto` / `top_k` (either implies scoring): keep the molecules scoring >= the threshold, then the k
         best, in descending score order (ties: lower sample id); `last_valid_fraction` is taken before this selection.
-        Refused with ValueError before any device work: scoring without a reference conformer, a reference outside 3..64
-        heavy atoms, top_k < 1, a threshold outside [0, 1], and a custom finisher."""
+        `overlay=True`: every returned molecule is posed onto the reference conformer, in the coordinates the reference
+        was given in, by a proper rigid transform (a rotation, never a mirror) found on the GPU from the principal shape
+        frames and the four-orientation search (`cheminformatics.shape_overlay`).  Records: `coords` are the posed
+        coordinates, `pose` = (rotation, translation) with returned = generated @ rotation + translation, and
+        `overlay_tanimoto` the shape Tanimoto of that pose (a molecule whose pose failed keeps its generated coordinates,
+        `pose` None, `overlay_tanimoto` NaN).  Mols: every conformer position, hydrogens included, moved by the pose of
+        the heavy atoms; double property `overlay_tanimoto`.  With scoring the molecules are posed first, then scored:
+        `shape_tanimoto` stays the score of the RETURNED coordinates, and since `evaluate_samples` takes the reference's
+        frame with whatever handedness LAPACK gives it, it can differ from the un-posed call's score for the same
+        molecule; `overlay_tanimoto` is the score of the proper pose.
+        Refused with ValueError before any device work: scoring or posing without a reference conformer, a reference
+        outside 3..64 heavy atoms, top_k < 1, a threshold outside [0, 1], and a custom finisher."""
         if sample_seed is not None:
             seeding.check_seed(sample_seed)
-        ref_coord = self._scoring_reference(reference_conformer, shape_scores, top_k, min_shape_tanimoto)
+        ref_coord = self._scoring_reference(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay)
+        scoring = shape_scores or top_k is not None or min_shape_tanimoto is not None
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
         if sample_seed is None:       # the positional call of before: a stub of `_generate_shard` need not know the seed
             res = self._generate_shard(ref_context, ref_n_atoms, variance, None, n_samples, resample_steps, fixed_fragment,
@@ -487,17 +519,24 @@ class MLConformerGenerator(torch.nn.Module):
                 rdkit_finish.tag_sample_ids(done, range(len(done)))
             live = [i for i, m in enumerate(done) if m is not None]
             self.last_valid_fraction = len(live) / len(done) if done else 0.0
-            if ref_coord is None:
+            if overlay:
+                self._pose_mols(ref_coord, done)
+            if not scoring:
                 return [done[i] for i in live]
             from . import rdkit_finish
             scores = self._score_mols(ref_coord, done)
             rdkit_finish.tag_shape_scores(done, scores)
             return self._select([done[i] for i in live], [scores[i] for i in live], live, top_k, min_shape_tanimoto)
-        scores = None if ref_coord is None else self._score_coords(ref_coord, res["x"], res["n_nodes"])
-        mols = molecules_from_tensors(res["x"], res["elements"], res["bond"], res["n_nodes"], res["valid"],
-                                      shape_tanimoto=scores)                                            # single D2H
+        x, ov = res["x"], None
+        if overlay:                           # pose first: a score is the score of the returned coordinates
+            ov = self._pose_coords(ref_coord, x, res["n_nodes"])
+            x = ov["coords"]
+        scores = self._score_coords(ref_coord, x, res["n_nodes"]) if scoring else None
+        mols = molecules_from_tensors(x, res["elements"], res["bond"], res["n_nodes"], res["valid"],
+                                      shape_tanimoto=scores, overlay_tanimoto=None if ov is None else ov["tanimoto"],
+                                      pose=None if ov is None else self._pose_rows(ov))                 # single D2H
         kept, self.last_valid_fraction = _finish(mols, optimise_geometry, use_rdkit=False)    # no finisher: the proxy
-        if ref_coord is None:
+        if not scoring:
             return kept
         return self._select(kept, [m.shape_tanimoto for m in kept], [m.sample_id for m in kept], top_k,
                             min_shape_tanimoto)
@@ -510,7 +549,8 @@ class MLConformerGenerator(torch.nn.Module):
                                     ifm_diffusion_level: int = 50, group=None, seed: Optional[int] = None,
                                     gather: str = "all", balance: str = "cost",
                                     sample_seed: Optional[int] = None, shape_scores: bool = False,
-                                    top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None) -> List:
+                                    top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None,
+                                    overlay: bool = False) -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -529,14 +569,18 @@ class MLConformerGenerator(torch.nn.Module):
         `shape_scores`, `top_k`, `min_shape_tanimoto`: as in `generate_conformers`.  Every rank scores ITS OWN shard on its
         own GPU before the gather (the scores travel with the result tensors, or next to the finished Mols); the
         selection runs on what each rank returns: with gather="all" every rank returns the same selection, with
-        gather="rank0" rank 0 selects from the whole batch and every other rank within its own shard."""
+        gather="rank0" rank 0 selects from the whole batch and every other rank within its own shard.
+        `overlay`: as in `generate_conformers`; every rank poses its own shard on its own GPU before the gather (the
+        posed coordinates travel in the result tensors, the pose and its score as two more per-sample tensors, or the
+        posed Mols with their scores next to them)."""
         if gather not in ("all", "rank0"):
             raise ValueError("gather must be 'all' or 'rank0'")
         if sample_seed is not None:
             if seed is not None:
                 raise ValueError("pass either seed (per-rank device generator) or sample_seed (keyed stream), not both")
             seeding.check_seed(sample_seed)
-        ref_coord = self._scoring_reference(reference_conformer, shape_scores, top_k, min_shape_tanimoto)
+        ref_coord = self._scoring_reference(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay)
+        scoring = shape_scores or top_k is not None or min_shape_tanimoto is not None
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)
         hi_n = min(ref_n_atoms + variance, self.max_n_nodes)
@@ -546,6 +590,7 @@ class MLConformerGenerator(torch.nn.Module):
         finishing = getattr(self, "finisher", None) is not None
         finished: List = [None]
         finished_scores: List = [None]
+        finished_poses: List = [None]
 
         def run_shard(sizes_shard, index):
             keyed = () if sample_seed is None else (sample_seed, index)
@@ -561,10 +606,16 @@ class MLConformerGenerator(torch.nn.Module):
                 if len(done) != int(index.numel()):
                     raise ValueError(f"the finish returned {len(done)} results for a shard of {int(index.numel())}")
                 finished[0] = done
-                if ref_coord is not None:
+                if overlay:                   # pose first: a score is the score of the returned coordinates
+                    finished_poses[0] = self._pose_mols(ref_coord, done)
+                if scoring:
                     finished_scores[0] = self._score_mols(ref_coord, done)
-            elif ref_coord is not None:       # one more per-sample tensor for the gather
-                res = dict(res, shape_tanimoto=self._score_coords(ref_coord, res["x"], res["n_nodes"]))
+            elif ref_coord is not None:       # more per-sample tensors for the gather
+                if overlay:
+                    ov = self._pose_coords(ref_coord, res["x"], res["n_nodes"])
+                    res = dict(res, x=ov["coords"], overlay_tanimoto=ov["tanimoto"], pose=self._pose_rows(ov))
+                if scoring:
+                    res = dict(res, shape_tanimoto=self._score_coords(ref_coord, res["x"], res["n_nodes"]))
             return res
 
         def seed_device(s):
@@ -590,9 +641,12 @@ class MLConformerGenerator(torch.nn.Module):
         if finishing:                         # RDKit's gate: this rank's shard was finished above, the Mols travel as objects
             if ref_coord is None:
                 done = mcg_dist.gather_objects(finished[0], shards, group, dst)
-            else:                             # the scores travel next to the Mols and are attached after the gather
-                pairs = mcg_dist.gather_objects(list(zip(finished[0], finished_scores[0])), shards, group, dst)
-                done, scores = [p[0] for p in pairs], [p[1] for p in pairs]
+            else:                             # scores and poses travel next to the Mols, attached after the gather
+                n_local = len(finished[0])
+                local_scores = finished_scores[0] if scoring else [None] * n_local
+                local_poses = finished_poses[0] if overlay else [None] * n_local
+                triples = mcg_dist.gather_objects(list(zip(finished[0], local_scores, local_poses)), shards, group, dst)
+                done, scores, poses = [p[0] for p in triples], [p[1] for p in triples], [p[2] for p in triples]
             ids = list(range(len(done))) if row_ids is None else row_ids.tolist()
             if sample_seed is not None:
                 from . import rdkit_finish
@@ -603,6 +657,10 @@ class MLConformerGenerator(torch.nn.Module):
             if ref_coord is None:
                 return [done[i] for i in live]
             from . import rdkit_finish
+            if overlay:
+                rdkit_finish.tag_overlay_scores(done, [None if p is None else p[0] for p in poses])
+            if not scoring:
+                return [done[i] for i in live]
             rdkit_finish.tag_shape_scores(done, scores)
             return self._select([done[i] for i in live], [scores[i] for i in live], [ids[i] for i in live], top_k,
                                 min_shape_tanimoto)
@@ -610,10 +668,11 @@ class MLConformerGenerator(torch.nn.Module):
             torch.cuda.synchronize(self.device)       # (the D2H copies below would wait for the device anyway: keep that out of the figure)
         t0 = time.perf_counter()
         mols = molecules_from_tensors(res["x"], res["elements"], res["bond"], res["n_nodes"], res["valid"],
-                                      sample_ids=row_ids, shape_tanimoto=res.get("shape_tanimoto"))
+                                      sample_ids=row_ids, shape_tanimoto=res.get("shape_tanimoto"),
+                                      overlay_tanimoto=res.get("overlay_tanimoto"), pose=res.get("pose"))
         self.last_host_assembly_ms = (time.perf_counter() - t0) * 1e3      # D2H of the gathered tensors + record views
         kept, self.last_valid_fraction = _finish(mols, optimise_geometry, use_rdkit=False)    # no finisher: the proxy
-        if ref_coord is None:
+        if not scoring:
             return kept
         return self._select(kept, [m.shape_tanimoto for m in kept], [m.sample_id for m in kept], top_k,
                             min_shape_tanimoto)
@@ -624,9 +683,9 @@ class MLConformerGenerator(torch.nn.Module):
                 resample_steps: int = 0, fixed_fragment=None, inertial_fragment_matching: bool = True,
                 blend_power: int = 3, ifm_diffusion_level: int = 50, sample_seed: Optional[int] = None,
                 shape_scores: bool = False, top_k: Optional[int] = None,
-                min_shape_tanimoto: Optional[float] = None) -> List:
+                min_shape_tanimoto: Optional[float] = None, overlay: bool = False) -> List:
         return self.generate_conformers(reference_conformer, n_samples, variance, reference_context, n_atoms,
                                         optimise_geometry, resample_steps, fixed_fragment,
                                         inertial_fragment_matching, blend_power, ifm_diffusion_level,
                                         sample_seed=sample_seed, shape_scores=shape_scores, top_k=top_k,
-                                        min_shape_tanimoto=min_shape_tanimoto)
+                                        min_shape_tanimoto=min_shape_tanimoto, overlay=overlay)

@@ -15,7 +15,9 @@
 //   k_shape_moments: pass 1 (input points: volume, first moments -> shape centre), pass 2 (centred points: second-moment
 //                    tensor / volume), optional exact clique counts per order.
 //   k_shape_frames:  pass 3 on the centred points rotated by the host's eigenvectors: diagonal second moments, sorted
-//                    descending, frame axes permuted to match (:143-202).
+//                    descending, frame axes permuted to match (:143-202).  Optionally (`mcg_shape_frames_tf`) the rigid
+//                    transform of the frame: M = V P (eigenvectors, then the axis permutation) and t = atom mean + shape
+//                    centre, so that frames = (coords - t) @ M on the real rows.
 #include "mcg_common.h"
 #include "mcg_api_internal.h"
 
@@ -55,6 +57,7 @@ struct Shared {
     unsigned long long cred[SF_WAVES][SF_MAX_TERMS - 1];
     double sums[6];
     unsigned long long counts[SF_MAX_TERMS - 1];
+    float mean[3];                               // the atoms' mean subtracted first (centre_atoms), else 0
     int n_edges;
 };
 
@@ -175,8 +178,9 @@ __device__ int load_and_build(Shared& s, const float* __restrict__ coords, const
     const float* x = coords + (size_t)b * N * 3;
     if (tid < n) { s.px[tid] = x[tid * 3]; s.py[tid] = x[tid * 3 + 1]; s.pz[tid] = x[tid * 3 + 2]; }
     __syncthreads();
+    if (tid < 3) s.mean[tid] = 0.f;
     if (T.centre_atoms) {               // evaluate_shape's (x - mean) of the real atoms, summed in atom order
-        __shared__ float mean[3];
+        float* mean = s.mean;
         if (tid < 3) {
             const float* p = tid == 0 ? s.px : tid == 1 ? s.py : s.pz;
             float acc = 0.f;
@@ -277,7 +281,8 @@ __global__ __launch_bounds__(SF_THREADS) void k_shape_frames(const float* __rest
                                                             const float* __restrict__ centre,
                                                             const float* __restrict__ eigvecs,
                                                             const double* __restrict__ volume,
-                                                            float* __restrict__ moments, float* __restrict__ frames) {
+                                                            float* __restrict__ moments, float* __restrict__ frames,
+                                                            float* __restrict__ xform) {
     __shared__ Shared s;
     __shared__ int order[3];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -304,6 +309,12 @@ __global__ __launch_bounds__(SF_THREADS) void k_shape_frames(const float* __rest
         for (int i = 1; i < 3; ++i)                // stable descending sort of the three main moments
             for (int k = i; k > 0 && m[o[k]] > m[o[k - 1]]; --k) { const int t = o[k]; o[k] = o[k - 1]; o[k - 1] = t; }
         for (int d = 0; d < 3; ++d) { moments[b * 3 + d] = m[o[d]]; order[d] = o[d]; }
+        if (xform != nullptr) {             // M[i][d] = V[i][o[d]], t = mean + centre
+            const float* V = eigvecs + (size_t)b * 9;
+            for (int i = 0; i < 3; ++i)
+                for (int d = 0; d < 3; ++d) xform[(size_t)b * 12 + i * 3 + d] = V[i * 3 + o[d]];
+            for (int d = 0; d < 3; ++d) xform[(size_t)b * 12 + 9 + d] = s.mean[d] + centre[b * 3 + d];
+        }
     }
     __syncthreads();
     for (int i = tid; i < N; i += SF_THREADS) {
@@ -337,6 +348,17 @@ int make_terms(double alpha, double amplitude, float threshold, int n_terms, int
     return MCG_OK;
 }
 
+int launch_frames(const float* coords, const int32_t* n_nodes_dev, int B, int N, const float* centre, const float* eigvecs,
+                  const double* volume, double alpha, double amplitude, float neighbour_threshold, int n_terms,
+                  int centre_atoms, float* moments, float* frames, float* xform, void* stream, const char* who) {
+    ShapeTerms T;
+    if (int rc = make_terms(alpha, amplitude, neighbour_threshold, n_terms, centre_atoms, &T, who)) return rc;
+    hipLaunchKernelGGL(k_shape_frames, dim3(B), dim3(SF_THREADS), 0, (hipStream_t)stream, coords, n_nodes_dev, N, T, centre,
+                       eigvecs, volume, moments, frames, xform);
+    MCG_HIP(hipGetLastError());
+    return MCG_OK;
+}
+
 }  // namespace
 
 extern "C" int mcg_shape_moments(const float* coords, const int32_t* n_nodes_dev, int B, int N, double alpha,
@@ -363,10 +385,19 @@ extern "C" int mcg_shape_frames(const float* coords, const int32_t* n_nodes_dev,
         mcg_set_error("mcg_shape_frames: bad arguments (non-null buffers, B >= 1, 1 <= N <= %d)", SF_MAX_ATOMS);
         return MCG_ERR_ARG;
     }
-    ShapeTerms T;
-    if (int rc = make_terms(alpha, amplitude, neighbour_threshold, n_terms, centre_atoms, &T, "mcg_shape_frames")) return rc;
-    hipLaunchKernelGGL(k_shape_frames, dim3(B), dim3(SF_THREADS), 0, (hipStream_t)stream, coords, n_nodes_dev, N, T, centre,
-                       eigvecs, volume, moments, frames);
-    MCG_HIP(hipGetLastError());
-    return MCG_OK;
+    return launch_frames(coords, n_nodes_dev, B, N, centre, eigvecs, volume, alpha, amplitude, neighbour_threshold, n_terms,
+                         centre_atoms, moments, frames, nullptr, stream, "mcg_shape_frames");
+}
+
+extern "C" int mcg_shape_frames_tf(const float* coords, const int32_t* n_nodes_dev, int B, int N, const float* centre,
+                                   const float* eigvecs, const double* volume, double alpha, double amplitude,
+                                   float neighbour_threshold, int n_terms, int centre_atoms, float* moments, float* frames,
+                                   float* xform, void* stream) {
+    if (!coords || !n_nodes_dev || !centre || !eigvecs || !volume || !moments || !frames || !xform || B < 1 || N < 1 ||
+        N > SF_MAX_ATOMS) {
+        mcg_set_error("mcg_shape_frames_tf: bad arguments (non-null buffers, B >= 1, 1 <= N <= %d)", SF_MAX_ATOMS);
+        return MCG_ERR_ARG;
+    }
+    return launch_frames(coords, n_nodes_dev, B, N, centre, eigvecs, volume, alpha, amplitude, neighbour_threshold, n_terms,
+                         centre_atoms, moments, frames, xform, stream, "mcg_shape_frames_tf");
 }

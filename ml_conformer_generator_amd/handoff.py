@@ -42,24 +42,42 @@ class GeneratedMolecule:
     per-molecule slices are taken on first access, so assembling a batch costs one object per molecule (2 048 molecules:
     a few ms instead of 70-170 ms of slicing + cloning on every rank of a sharded call).  `sample_id`: which sample of
     its generation call the record is (invalid molecules are dropped, so a kept record's position says nothing).
-    `shape_tanimoto`: its shape score against the reference when the call asked for scores, else None."""
-    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_score")
+    `shape_tanimoto`: its shape score against the reference when the call asked for scores, else None.
+    `overlay_tanimoto` / `pose`: the score and rigid pose of a call that posed its molecules onto the reference
+    (`overlay=True`), else None."""
+    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_score", "_overlay")
 
     def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True,
                  sample_id: Optional[int] = None):
         self._z, self._coords, self._bonds, self.valid = list(atomic_numbers), coords, bond_orders, bool(valid)
         self._batch, self._b, self._sid = None, -1, sample_id
-        self._score = None
+        self._score = self._overlay = None
 
     @classmethod
     def _view(cls, batch: _HostBatch, b: int, valid: bool, sample_id: Optional[int] = None,
-              score: Optional[float] = None) -> "GeneratedMolecule":
+              score: Optional[float] = None, overlay: Optional[tuple] = None) -> "GeneratedMolecule":
         m = cls.__new__(cls)
         m._z = m._coords = m._bonds = None
         m.valid, m._batch, m._b = valid, batch, b
         m._sid = b if sample_id is None else sample_id
         m._score = score
+        m._overlay = overlay
         return m
+
+    @property
+    def overlay_tanimoto(self) -> Optional[float]:
+        """Shape Tanimoto of the pose onto the reference (`overlay=True`: the returned coordinates ARE that pose; NaN
+        where posing failed and the generated coordinates were kept); None when the call did not pose."""
+        return None if self._overlay is None else self._overlay[0]
+
+    @property
+    def pose(self) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+        """(rotation [3,3], translation [3]) with returned = generated @ rotation + translation (rotation proper, det +1)
+        when the call posed the molecule (`overlay=True`); None otherwise, and where posing failed."""
+        if self._overlay is None or self._overlay[1] is None:
+            return None
+        p = self._overlay[1]
+        return p[:9].reshape(3, 3), p[9:]
 
     @property
     def shape_tanimoto(self) -> Optional[float]:
@@ -234,19 +252,27 @@ def bond_writeback_hip(bond: torch.Tensor, elements: torch.Tensor, n_nodes: torc
 
 def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: torch.Tensor, n_nodes: torch.Tensor,
                            valid: torch.Tensor, sample_ids: Optional[Sequence[int]] = None,
-                           shape_tanimoto: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
+                           shape_tanimoto: Optional[torch.Tensor] = None, overlay_tanimoto: Optional[torch.Tensor] = None,
+                           pose: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
     (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
-    (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records)."""
+    (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records).
+    `overlay_tanimoto[b]` / `pose[b]` (rotation row-major, then translation: [B,12], NaN where posing failed): row b's
+    pose onto the reference (None: records of a call that did not pose)."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
     view = GeneratedMolecule._view
-    if sample_ids is None and shape_tanimoto is None:
+    if sample_ids is None and shape_tanimoto is None and overlay_tanimoto is None:
         return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
     flags = valid.cpu().tolist()
     ids = list(range(len(flags))) if sample_ids is None else \
         [int(i) for i in (sample_ids.tolist() if torch.is_tensor(sample_ids) else sample_ids)]
     scores = [None] * len(flags) if shape_tanimoto is None else [float(v) for v in shape_tanimoto.cpu().tolist()]
-    return [view(batch, b, bool(v), ids[b], scores[b]) for b, v in enumerate(flags)]
+    overlays = [None] * len(flags)
+    if overlay_tanimoto is not None:
+        tan, poses = overlay_tanimoto.cpu().tolist(), pose.cpu().to(torch.float32)
+        ok = torch.isfinite(poses).all(dim=1).tolist()
+        overlays = [(float(t), poses[b] if ok[b] else None) for b, t in enumerate(tan)]
+    return [view(batch, b, bool(v), ids[b], scores[b], overlays[b]) for b, v in enumerate(flags)]
 
 
 def assemble_molecules(x: torch.Tensor, elements: torch.Tensor, bond: torch.Tensor, n_nodes: torch.Tensor

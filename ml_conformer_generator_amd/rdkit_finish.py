@@ -153,3 +153,11 @@ def tag_shape_scores(mols: Sequence, scores: Sequence[Optional[float]]) -> None:
     for m, sc in zip(mols, scores):
         if m is not None and sc is not None and hasattr(m, "SetDoubleProp"):
             m.SetDoubleProp("shape_tanimoto", float(sc))
+
+
+def tag_overlay_scores(mols: Sequence, scores: Sequence[Optional[float]]) -> None:
+    """Set the double property `overlay_tanimoto` (the score of the Mol's pose onto the reference) on every Mol of `mols`
+    (None = dropped); set again after the object gather, which does not carry Mol properties."""
+    for m, sc in zip(mols, scores):
+        if m is not None and sc is not None and hasattr(m, "SetDoubleProp"):
+            m.SetDoubleProp("overlay_tanimoto", float(sc))
