@@ -314,6 +314,26 @@ int mcg_shape_overlay(const float* ref_frame, int n_ref, const float* ref_xform,
                       float amplitude, float* f_scratch, float* score, float* best, int32_t* which, int32_t* flipped,
                       float* pose, float* posed, void* stream);
 
+/* ---- Pairwise shape Tanimoto ("shape diversity"): every pair of B molecules that already share
+ * one frame (posed onto the reference by mcg_shape_overlay), compared as placed, with no orientation search.
+ *   coords[B,N,3] with n_nodes_dev[b] real atoms (device memory, clamped to [0, N] on the device), in the reference's
+ *   own coordinates; ref_xform[12] = the reference's M_r row-major, then t_r (mcg_shape_frames_tf), which maps every
+ *   molecule into the reference's frame, y = (x - t_r) @ M_r; axes[3,n] = the reference frame's grid (atoms off the grid
+ *   are cut off).  density_ws[B * Gp] with Gp = n^3 rounded up to a multiple of MCG_SHAPE_PAIR_KALIGN: the densities
+ *   F (as mcg_shape_tanimoto evaluates them); gram_ws[B * B]: G = F F^T (exact fp32 MFMA); tanimoto[B * B], row-major:
+ *   T_ij = G_ij / (G_ii + G_jj - G_ij).  T is exactly symmetric, T_ii is exactly 1 where the density is finite and not
+ *   zero, and T_ij depends only on molecules i and j and the reference: the k order of every sum is fixed by n alone, so
+ *   an entry has the same bits whatever the batch, row order or padded width.  A molecule with no atoms or a non-finite
+ *   coordinate has a NaN density and so a NaN row and column; the other entries are unaffected.
+ * MCG_ERR_ARG, nothing launched: a null buffer, B outside 1..MCG_SHAPE_PAIR_MAX_B, N outside 1..64, n outside
+ * 2..MCG_SHAPE_PAIR_MAX_N. */
+#define MCG_SHAPE_PAIR_MAX_B 16384
+#define MCG_SHAPE_PAIR_MAX_N 256
+#define MCG_SHAPE_PAIR_KALIGN 128
+int mcg_shape_pair_tanimoto(const float* coords, const int32_t* n_nodes_dev, int B, int N, const float* ref_xform,
+                            const float* axes, int n, float alpha, float amplitude, float* density_ws, float* gram_ws,
+                            float* tanimoto, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

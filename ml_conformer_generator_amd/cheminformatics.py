@@ -14,6 +14,7 @@ LDS, never stored) around the same host `eigh`, bit-identical for a molecule wha
 from __future__ import annotations
 
 import math
+import numbers
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -417,14 +418,89 @@ def apply_pose(mol, rotation: torch.Tensor, translation: torch.Tensor) -> None:
         conf.SetAtomPosition(i, Point3D(*p) if Point3D is not None else tuple(p))
 
 
+MAX_PAIR_BATCH = 16384        # include/mlconfgen_hip.h MCG_SHAPE_PAIR_MAX_B: F [B, 64 000] and T [B, B] stay addressable
+_PAIR_KALIGN = 128            # MCG_SHAPE_PAIR_KALIGN: the density rows are padded to this many grid points
+
+
+@torch.no_grad()
+def pairwise_shape_tanimoto(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor,
+                            device=None) -> torch.Tensor:
+    """[B,B] fp32 on the device: the Gaussian-volume shape Tanimoto of every pair of molecules AS PLACED (no orientation
+    search), for molecules that share the reference conformer's own coordinates (what `shape_overlay` returns).  Both
+    molecules are evaluated on the grid `shape_overlay` scores on: the reference's principal frame (`shape_frames_hip`,
+    `xform_out=`), `_grid_axes(ref_frame, 40)`, each molecule mapped into that frame by y = (x - t_r) @ M_r; atoms off
+    the grid are cut off ("shape diversity").  One `mcg_shape_pair_tanimoto` call: the densities,
+    their Gram matrix on the exact-fp32 matrix cores, and T_ij = G_ij / (G_ii + G_jj - G_ij).
+    The matrix is exactly symmetric, its diagonal exactly 1 where a molecule's density is finite and not zero, and entry
+    (i, j) has the same bits whatever the batch, row order or padded width.  A molecule with no atoms or a non-finite
+    coordinate gets a NaN row and column; the other entries are unaffected.  Refuses, before any device work, what
+    `shape_scores` refuses and more than `MAX_PAIR_BATCH` molecules."""
+    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
+    ref = torch.as_tensor(reference_coord, dtype=torch.float32).cpu()
+    n_ref = int(ref.shape[0])
+    check_reference_atoms(n_ref)
+    B, W = int(coords.shape[0]), int(coords.shape[1])
+    if B > MAX_PAIR_BATCH:
+        raise ValueError(f"pairwise shape Tanimoto takes at most {MAX_PAIR_BATCH} molecules, got {B}")
+    if B == 0:
+        return torch.zeros(0, 0, device=dev)
+    check_n_nodes(n_nodes, B, W)
+    if W > MAX_SCORED_ATOMS:
+        raise ValueError(f"shape scoring takes at most {MAX_SCORED_ATOMS} atoms per molecule, got a padded width of {W}")
+    x = coords.to(dev, torch.float32).contiguous()
+    nn = n_nodes.to(dev, torch.int32).reshape(B).contiguous()
+    xform = torch.empty(1, 12, device=dev)
+    _, frames = shape_frames_hip(ref.to(dev).unsqueeze(0), torch.tensor([n_ref], dtype=torch.int32, device=dev), dev,
+                                 centre_atoms=True, xform_out=xform)
+    n = 40
+    axes = _grid_axes(frames[0].cpu(), n).to(dev).contiguous()
+    gp = -(-n ** 3 // _PAIR_KALIGN) * _PAIR_KALIGN
+    density = torch.empty(B, gp, device=dev)
+    gram = torch.empty(B, B, device=dev)
+    out = torch.empty(B, B, device=dev)
+    _lib.check(_lib.lib().mcg_shape_pair_tanimoto(_lib.dptr(x), _lib.dptr(nn), B, W, _lib.dptr(xform), _lib.dptr(axes), n,
+                                                  float(ALPHA), float(AMPLITUDE), _lib.dptr(density), _lib.dptr(gram),
+                                                  _lib.dptr(out), _lib.current_stream_ptr(dev)),
+               "mcg_shape_pair_tanimoto")
+    return out
+
+
+def check_max_pairwise_tanimoto(value) -> float:
+    """`max_pairwise_tanimoto` as a float: a real number in (0, 1] (not a bool, not NaN), else ValueError."""
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not (0.0 < float(value) <= 1.0):
+        raise ValueError(f"max_pairwise_tanimoto must be a real number in (0, 1], got {value!r}")
+    return float(value)
+
+
+def select_diverse(scores: List[float], sample_ids: List[int], pair, max_pairwise_tanimoto: Optional[float],
+                   top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None) -> List[int]:
+    """Positions of the molecules to keep, by sphere exclusion in ranking order: the molecules scoring >=
+    `min_shape_tanimoto`, walked in descending score order (ties: the lower sample id; a NaN score ranks last and passes
+    no threshold); a molecule is kept unless its `pair` Tanimoto with an already kept molecule is >=
+    `max_pairwise_tanimoto` (a NaN pair entry excludes nothing); then the first `top_k`.  `pair[i][j]`: the [B,B] pair
+    matrix over the same positions as `scores` (`pairwise_shape_tanimoto`; any array-like), not read when
+    `max_pairwise_tanimoto` is None, which gives the plain ranking selection (`select_scored`)."""
+    keep = [i for i, s in enumerate(scores) if min_shape_tanimoto is None or s >= min_shape_tanimoto]
+    keep.sort(key=lambda i: (-scores[i] if scores[i] == scores[i] else math.inf, sample_ids[i]))
+    if max_pairwise_tanimoto is not None:
+        import numpy as np
+        p = np.asarray(pair.cpu() if torch.is_tensor(pair) else pair, dtype=np.float64)    # fp32 entries, exactly
+        kept: List[int] = []
+        for i in keep:
+            if top_k is not None and len(kept) >= top_k:
+                break                        # later molecules cannot change what is already kept
+            if not kept or not bool((p[i, kept] >= max_pairwise_tanimoto).any()):
+                kept.append(i)
+        keep = kept
+    return keep if top_k is None else keep[:top_k]
+
+
 def select_scored(scores: List[float], sample_ids: List[int], top_k: Optional[int] = None,
                   min_shape_tanimoto: Optional[float] = None) -> List[int]:
     """Positions of the molecules to keep: score >= `min_shape_tanimoto`, then the `top_k` best, in descending score
     order with ties going to the lower sample id.  A NaN score (a molecule with no overlap with the reference grid at all)
-    ranks last and passes no threshold."""
-    keep = [i for i, s in enumerate(scores) if min_shape_tanimoto is None or s >= min_shape_tanimoto]
-    keep.sort(key=lambda i: (-scores[i] if scores[i] == scores[i] else math.inf, sample_ids[i]))
-    return keep if top_k is None else keep[:top_k]
+    ranks last and passes no threshold.  (`select_diverse` without the exclusion.)"""
+    return select_diverse(scores, sample_ids, None, None, top_k, min_shape_tanimoto)
 
 
 def mol_heavy_coords(mol) -> torch.Tensor:

@@ -39,7 +39,10 @@ forced by the scope of this build:
     the best / those above a threshold.  Off by default: nothing changes;
   * `overlay` (opt-in, every generation entry): every returned molecule is posed onto the reference conformer, in the
     reference's own coordinates, by a proper rigid transform found on the GPU (`cheminformatics.shape_overlay`).  Off
-    by default: nothing changes.
+    by default: nothing changes;
+  * `max_pairwise_tanimoto` (opt-in, every generation entry, with `overlay`): a shape-diverse selection by sphere
+    exclusion in ranking order on the pairwise shape Tanimoto of the posed molecules
+    (`cheminformatics.pairwise_shape_tanimoto`).  Off by default: nothing changes.
 """
 from __future__ import annotations
 
@@ -305,11 +308,20 @@ class MLConformerGenerator(torch.nn.Module):
             "Either a reference RDkit Mol object or context as torch.Tensor should be provided for generation.")
 
     def _scoring_reference(self, reference_conformer, shape_scores: bool, top_k: Optional[int],
-                           min_shape_tanimoto: Optional[float], overlay: bool = False) -> Optional[torch.Tensor]:
-        """The reference's heavy-atom coordinates when the call scores (`shape_scores`, or `top_k` / `min_shape_tanimoto`,
-        which imply it) or poses (`overlay`), else None.  Every refusal happens here, before any device work."""
-        if not (shape_scores or top_k is not None or min_shape_tanimoto is not None or overlay):
+                           min_shape_tanimoto: Optional[float], overlay: bool = False,
+                           max_pairwise_tanimoto: Optional[float] = None) -> Optional[torch.Tensor]:
+        """The reference's heavy-atom coordinates when the call scores (`shape_scores`, or `top_k` / `min_shape_tanimoto` /
+        `max_pairwise_tanimoto`, which imply it) or poses (`overlay`), else None.  Every refusal happens here, before any
+        device work."""
+        if not (shape_scores or top_k is not None or min_shape_tanimoto is not None or overlay or
+                max_pairwise_tanimoto is not None):
             return None
+        if max_pairwise_tanimoto is not None:
+            from .cheminformatics import check_max_pairwise_tanimoto
+            check_max_pairwise_tanimoto(max_pairwise_tanimoto)
+            if not overlay:
+                raise ValueError("max_pairwise_tanimoto needs overlay=True: molecules that are not posed onto the reference "
+                                 "share no frame to compare them in")
         what = "shape scores" if not overlay else "overlay"
         if top_k is not None:
             try:
@@ -364,13 +376,39 @@ class MLConformerGenerator(torch.nn.Module):
         """[B,12]: rotation row-major, then translation (NaN where posing failed)."""
         return torch.cat([ov["rotation"].reshape(-1, 9), ov["translation"].reshape(-1, 3)], dim=1)
 
+    def _pair_coords(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
+        """[B,B] pairwise shape Tanimoto (device) of padded heavy-atom coordinates posed onto the reference
+        (`cheminformatics.pairwise_shape_tanimoto`)."""
+        from .cheminformatics import pairwise_shape_tanimoto
+        return pairwise_shape_tanimoto(ref_coord, coords, n_nodes, self.device)
+
+    def _pair_rows(self, ref_coord: torch.Tensor, x: torch.Tensor, n_nodes: torch.Tensor, mols: List,
+                   kept: List) -> torch.Tensor:
+        """The pair matrix of the records `kept` (a subset of `mols`, whose record b is row b of x / n_nodes), in the
+        order of `kept`, from the posed device coordinates."""
+        row = {id(m): b for b, m in enumerate(mols)}
+        idx = torch.tensor([row[id(m)] for m in kept], dtype=torch.long, device=x.device)
+        return self._pair_coords(ref_coord, x.index_select(0, idx),
+                                 n_nodes.reshape(-1).to(x.device).index_select(0, idx))
+
+    def _pair_mols(self, ref_coord: torch.Tensor, mols: List) -> torch.Tensor:
+        """The pair matrix of finished, posed Mols (none of them None) from their heavy-atom conformer positions."""
+        from .cheminformatics import mol_heavy_coords, padded_coords
+        coords, n = padded_coords([mol_heavy_coords(m) for m in mols])
+        return self._pair_coords(ref_coord, coords, n)
+
     @staticmethod
     def _select(mols: List, scores: List[float], sample_ids: List[int], top_k: Optional[int],
-                min_shape_tanimoto: Optional[float]) -> List:
-        if top_k is None and min_shape_tanimoto is None:
+                min_shape_tanimoto: Optional[float], max_pairwise_tanimoto: Optional[float] = None,
+                pair_fn=None) -> List:
+        """Threshold, then sphere exclusion at `max_pairwise_tanimoto` (`pair_fn()`: the pair matrix of `mols`, only
+        called when it is set), then `top_k` (`cheminformatics.select_diverse`)."""
+        if top_k is None and min_shape_tanimoto is None and max_pairwise_tanimoto is None:
             return mols
-        from .cheminformatics import select_scored
-        return [mols[i] for i in select_scored(scores, sample_ids, top_k, min_shape_tanimoto)]
+        from .cheminformatics import select_diverse
+        pair = pair_fn() if max_pairwise_tanimoto is not None else None
+        return [mols[i] for i in select_diverse(scores, sample_ids, pair, max_pairwise_tanimoto, top_k,
+                                                min_shape_tanimoto)]
 
     def _executor(self):
         """Where the poolable host tasks run: the process-wide `HostPool` with `n_host_workers` workers and this generator's
@@ -475,7 +513,7 @@ class MLConformerGenerator(torch.nn.Module):
                             inertial_fragment_matching: bool = True, blend_power: int = 3,
                             ifm_diffusion_level: int = 50, sample_seed: Optional[int] = None, shape_scores: bool = False,
                             top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None,
-                            overlay: bool = False) -> List:
+                            overlay: bool = False, max_pairwise_tanimoto: Optional[float] = None) -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
@@ -497,12 +535,18 @@ class MLConformerGenerator(torch.nn.Module):
         `shape_tanimoto` stays the score of the RETURNED coordinates, and since `evaluate_samples` takes the reference's
         frame with whatever handedness LAPACK gives it, it can differ from the un-posed call's score for the same
         molecule; `overlay_tanimoto` is the score of the proper pose.
+        `max_pairwise_tanimoto` (needs `overlay=True`; implies scoring): a shape-diverse selection.  After the threshold,
+        the molecules are walked in ranking order and one is kept unless its shape Tanimoto, as posed, with an already
+        kept molecule is >= the value (`cheminformatics.pairwise_shape_tanimoto` on the GPU, `select_diverse`); then
+        `top_k`.
         Refused with ValueError before any device work: scoring or posing without a reference conformer, a reference
-        outside 3..64 heavy atoms, top_k < 1, a threshold outside [0, 1], and a custom finisher."""
+        outside 3..64 heavy atoms, top_k < 1, a threshold outside [0, 1], max_pairwise_tanimoto outside (0, 1] or without
+        overlay, and a custom finisher."""
         if sample_seed is not None:
             seeding.check_seed(sample_seed)
-        ref_coord = self._scoring_reference(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay)
-        scoring = shape_scores or top_k is not None or min_shape_tanimoto is not None
+        ref_coord = self._scoring_reference(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
+                                            max_pairwise_tanimoto)
+        scoring = shape_scores or top_k is not None or min_shape_tanimoto is not None or max_pairwise_tanimoto is not None
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
         if sample_seed is None:       # the positional call of before: a stub of `_generate_shard` need not know the seed
             res = self._generate_shard(ref_context, ref_n_atoms, variance, None, n_samples, resample_steps, fixed_fragment,
@@ -526,7 +570,9 @@ class MLConformerGenerator(torch.nn.Module):
             from . import rdkit_finish
             scores = self._score_mols(ref_coord, done)
             rdkit_finish.tag_shape_scores(done, scores)
-            return self._select([done[i] for i in live], [scores[i] for i in live], live, top_k, min_shape_tanimoto)
+            picked = [done[i] for i in live]
+            return self._select(picked, [scores[i] for i in live], live, top_k, min_shape_tanimoto, max_pairwise_tanimoto,
+                                lambda: self._pair_mols(ref_coord, picked))
         x, ov = res["x"], None
         if overlay:                           # pose first: a score is the score of the returned coordinates
             ov = self._pose_coords(ref_coord, x, res["n_nodes"])
@@ -539,7 +585,8 @@ class MLConformerGenerator(torch.nn.Module):
         if not scoring:
             return kept
         return self._select(kept, [m.shape_tanimoto for m in kept], [m.sample_id for m in kept], top_k,
-                            min_shape_tanimoto)
+                            min_shape_tanimoto, max_pairwise_tanimoto,
+                            lambda: self._pair_rows(ref_coord, x, res["n_nodes"], mols, kept))
 
     @torch.no_grad()
     def generate_conformers_sharded(self, reference_conformer=None, n_samples: int = 10, variance: int = 2,
@@ -550,7 +597,7 @@ class MLConformerGenerator(torch.nn.Module):
                                     gather: str = "all", balance: str = "cost",
                                     sample_seed: Optional[int] = None, shape_scores: bool = False,
                                     top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None,
-                                    overlay: bool = False) -> List:
+                                    overlay: bool = False, max_pairwise_tanimoto: Optional[float] = None) -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -572,15 +619,19 @@ class MLConformerGenerator(torch.nn.Module):
         gather="rank0" rank 0 selects from the whole batch and every other rank within its own shard.
         `overlay`: as in `generate_conformers`; every rank poses its own shard on its own GPU before the gather (the
         posed coordinates travel in the result tensors, the pose and its score as two more per-sample tensors, or the
-        posed Mols with their scores next to them)."""
+        posed Mols with their scores next to them).
+        `max_pairwise_tanimoto`: as in `generate_conformers`; the selection runs where the ranking selection runs, on the
+        rows a rank returns (gather="all": every rank computes the pair matrix of the whole batch on its own GPU and
+        returns the same list)."""
         if gather not in ("all", "rank0"):
             raise ValueError("gather must be 'all' or 'rank0'")
         if sample_seed is not None:
             if seed is not None:
                 raise ValueError("pass either seed (per-rank device generator) or sample_seed (keyed stream), not both")
             seeding.check_seed(sample_seed)
-        ref_coord = self._scoring_reference(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay)
-        scoring = shape_scores or top_k is not None or min_shape_tanimoto is not None
+        ref_coord = self._scoring_reference(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
+                                            max_pairwise_tanimoto)
+        scoring = shape_scores or top_k is not None or min_shape_tanimoto is not None or max_pairwise_tanimoto is not None
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)
         hi_n = min(ref_n_atoms + variance, self.max_n_nodes)
@@ -662,8 +713,9 @@ class MLConformerGenerator(torch.nn.Module):
             if not scoring:
                 return [done[i] for i in live]
             rdkit_finish.tag_shape_scores(done, scores)
-            return self._select([done[i] for i in live], [scores[i] for i in live], [ids[i] for i in live], top_k,
-                                min_shape_tanimoto)
+            picked = [done[i] for i in live]
+            return self._select(picked, [scores[i] for i in live], [ids[i] for i in live], top_k, min_shape_tanimoto,
+                                max_pairwise_tanimoto, lambda: self._pair_mols(ref_coord, picked))
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)       # (the D2H copies below would wait for the device anyway: keep that out of the figure)
         t0 = time.perf_counter()
@@ -675,7 +727,8 @@ class MLConformerGenerator(torch.nn.Module):
         if not scoring:
             return kept
         return self._select(kept, [m.shape_tanimoto for m in kept], [m.sample_id for m in kept], top_k,
-                            min_shape_tanimoto)
+                            min_shape_tanimoto, max_pairwise_tanimoto,
+                            lambda: self._pair_rows(ref_coord, res["x"], res["n_nodes"], mols, kept))
 
     @torch.no_grad()
     def forward(self, reference_conformer=None, n_samples: int = 10, variance: int = 2,
@@ -683,9 +736,11 @@ class MLConformerGenerator(torch.nn.Module):
                 resample_steps: int = 0, fixed_fragment=None, inertial_fragment_matching: bool = True,
                 blend_power: int = 3, ifm_diffusion_level: int = 50, sample_seed: Optional[int] = None,
                 shape_scores: bool = False, top_k: Optional[int] = None,
-                min_shape_tanimoto: Optional[float] = None, overlay: bool = False) -> List:
+                min_shape_tanimoto: Optional[float] = None, overlay: bool = False,
+                max_pairwise_tanimoto: Optional[float] = None) -> List:
         return self.generate_conformers(reference_conformer, n_samples, variance, reference_context, n_atoms,
                                         optimise_geometry, resample_steps, fixed_fragment,
                                         inertial_fragment_matching, blend_power, ifm_diffusion_level,
                                         sample_seed=sample_seed, shape_scores=shape_scores, top_k=top_k,
-                                        min_shape_tanimoto=min_shape_tanimoto, overlay=overlay)
+                                        min_shape_tanimoto=min_shape_tanimoto, overlay=overlay,
+                                        max_pairwise_tanimoto=max_pairwise_tanimoto)
