@@ -42,6 +42,13 @@ def rotation_matrix(angles: torch.Tensor) -> torch.Tensor:
     return rx @ ry @ rz
 
 
+def _orientations() -> torch.Tensor:
+    """The four orientations of `evaluate_samples`' search: identity, pi about x, y, z (all proper), [4,3,3] fp32."""
+    pi = torch.pi
+    return torch.stack([rotation_matrix(a) for a in (torch.zeros(3), torch.tensor([pi, 0, 0]), torch.tensor([0, pi, 0]),
+                                                     torch.tensor([0, 0, pi]))]).to(torch.float32)
+
+
 def _grid_axes(ref_coord: torch.Tensor, n: int, bounds_scale: float = 6.0, max_sigma: float = ATOM_RADIUS):
     """The reference's `Grid` axes.  Its min/max run over the xyz axis of cat(ref, cand), so the bounds are
     the per-atom extrema of the first three atoms - which belong to the reference (shape_similarity.py:476-480,
@@ -62,13 +69,10 @@ def shape_tanimoto_batch(ref_coord: torch.Tensor, cand_coords: torch.Tensor, n_n
     dev = torch.device(device if device is not None else (cand_coords.device if cand_coords.is_cuda else "cuda:0"))
     ref = ref_coord.to(torch.float32).cpu().contiguous()
     B, N, _ = cand_coords.shape
-    pi = torch.pi
-    rots = torch.stack([rotation_matrix(a) for a in (torch.zeros(3), torch.tensor([pi, 0, 0]),
-                                                     torch.tensor([0, pi, 0]), torch.tensor([0, 0, pi]))])
     axes = _grid_axes(ref, n)
     ref_d, cand_d = ref.to(dev), cand_coords.to(dev, torch.float32).contiguous()
     nn = n_nodes.to(dev, torch.int32).contiguous()
-    rots_d, axes_d = rots.to(dev, torch.float32).contiguous(), axes.to(dev).contiguous()
+    rots_d, axes_d = _orientations().to(dev).contiguous(), axes.to(dev).contiguous()
     f = torch.empty(n ** 3, device=dev)
     score = torch.empty(B * 4, device=dev)
     _lib.check(_lib.lib().mcg_shape_tanimoto(_lib.dptr(ref_d), ref.shape[0], _lib.dptr(cand_d), _lib.dptr(nn), B, N,
@@ -199,10 +203,7 @@ def evaluate_shape(reference_coord: torch.Tensor, sample_coords: torch.Tensor, n
     com = (x * real).sum(1, keepdim=True) / nn.view(B, 1, 1).clamp(min=1)             # :66-67
     _, frames = shape_quadrupole_batch((x - com) * real, nn, dev)
     scores, best, which = shape_tanimoto_batch(ref_pf, frames, nn, dev)
-    pi = torch.pi
-    rots = torch.stack([rotation_matrix(a) for a in (torch.zeros(3), torch.tensor([pi, 0, 0]),
-                                                     torch.tensor([0, pi, 0]), torch.tensor([0, 0, pi]))]).to(dev)
-    aligned = torch.einsum("bnk,bkj->bnj", frames, rots[which])
+    aligned = torch.einsum("bnk,bkj->bnj", frames, _orientations().to(dev)[which])
     aligned_c, best_c, which_c, nn_c = aligned.cpu(), best.cpu(), which.cpu(), nn.cpu()
     results = [{"coords": aligned_c[b, : int(nn_c[b])].clone(), "shape_tanimoto": float(best_c[b]),
                 "orientation": int(which_c[b])} for b in range(B)]
@@ -276,6 +277,35 @@ def check_reference_atoms(n_ref: int) -> None:
         raise ValueError(f"shape scoring needs a reference of 3 to {MAX_SCORED_ATOMS} heavy atoms, got {n_ref}")
 
 
+def _shape_inputs(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor, device,
+                  with_reference: bool, max_batch: Optional[int] = None):
+    """The common preamble of `shape_scores`, `shape_overlay` and `pairwise_shape_tanimoto`: (device, reference [n_ref,3]
+    fp32 on the host, batch x, counts nn), with x = nn = None for an empty batch.  `with_reference`: the reference is row
+    0 of x [B+1, max(W, n_ref), 3] and of nn, the samples follow; else x, nn are the samples as they are.  Refuses, before
+    any device work: a reference outside 3..MAX_SCORED_ATOMS heavy atoms, more than `max_batch` molecules and, for a
+    batch that is not empty, atom counts outside [0, W] and a padded width W above MAX_SCORED_ATOMS."""
+    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
+    ref = torch.as_tensor(reference_coord, dtype=torch.float32).cpu()
+    n_ref = int(ref.shape[0])
+    check_reference_atoms(n_ref)
+    B = int(coords.shape[0])
+    if max_batch is not None and B > max_batch:
+        raise ValueError(f"pairwise shape Tanimoto takes at most {max_batch} molecules, got {B}")
+    if B == 0:
+        return dev, ref, None, None
+    W = int(coords.shape[1])
+    check_n_nodes(n_nodes, B, W)         # before the reference widens the batch
+    if W > MAX_SCORED_ATOMS:
+        raise ValueError(f"shape scoring takes at most {MAX_SCORED_ATOMS} atoms per molecule, got a padded width of {W}")
+    nn = n_nodes.to(dev, torch.int32).reshape(B)
+    if not with_reference:
+        return dev, ref, coords.to(dev, torch.float32).contiguous(), nn.contiguous()
+    x = torch.zeros(B + 1, max(W, n_ref), 3, device=dev)
+    x[0, :n_ref] = ref.to(dev)
+    x[1:, :W] = coords.to(dev, torch.float32)
+    return dev, ref, x, torch.cat([torch.tensor([n_ref], dtype=torch.int32, device=dev), nn])
+
+
 @torch.no_grad()
 def shape_scores(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor, device=None
                  ) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -283,31 +313,13 @@ def shape_scores(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: t
     (`evaluate_samples`, cheminformatics/pipeline.py:30-85), with the principal frames of the reference and of the samples
     from the HIP kernels (`shape_frames_hip`, reference = row 0 of the same launch) and the four-orientation search of
     `mcg_shape_tanimoto`.  A sample's score depends on its own coordinates and the reference only."""
-    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
-    ref = torch.as_tensor(reference_coord, dtype=torch.float32).cpu()
-    n_ref = int(ref.shape[0])
-    check_reference_atoms(n_ref)
-    B = int(coords.shape[0])
-    if B == 0:
+    dev, ref, x, nn = _shape_inputs(reference_coord, coords, n_nodes, device, with_reference=True)
+    if x is None:
         return torch.empty(0, device=dev), torch.empty(0, dtype=torch.long, device=dev)
-    check_n_nodes(n_nodes, B, int(coords.shape[1]))         # before the reference widens the batch
-    N = max(int(coords.shape[1]), n_ref)
-    if N > MAX_SCORED_ATOMS:
-        raise ValueError(f"shape scoring takes at most {MAX_SCORED_ATOMS} atoms per molecule, got a padded width of {N}")
-    x = torch.zeros(B + 1, N, 3, device=dev)
-    x[0, :n_ref] = ref.to(dev)
-    x[1:, : coords.shape[1]] = coords.to(dev, torch.float32)
-    nn = torch.cat([torch.tensor([n_ref], dtype=torch.int32, device=dev), n_nodes.to(dev, torch.int32).reshape(B)])
+    n_ref = int(ref.shape[0])
     _, frames = shape_frames_hip(x, nn, dev, centre_atoms=True)
     _, best, which = shape_tanimoto_batch(frames[0, :n_ref], frames[1:], nn[1:], dev)
     return best, which
-
-
-def _orientations() -> torch.Tensor:
-    """The four orientations of `evaluate_samples`' search: identity, pi about x, y, z (all proper), [4,3,3] fp32."""
-    pi = torch.pi
-    return torch.stack([rotation_matrix(a) for a in (torch.zeros(3), torch.tensor([pi, 0, 0]), torch.tensor([0, pi, 0]),
-                                                     torch.tensor([0, 0, pi]))]).to(torch.float32)
 
 
 @torch.no_grad()
@@ -327,12 +339,9 @@ def shape_overlay(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: 
     A sample whose frame is not finite (non-finite coordinates, no atoms) keeps its input coordinates and gets a NaN
     rotation, translation and tanimoto and orientation -1; the other samples are unaffected and bit-identical whatever
     their batch.  Refuses what `shape_scores` refuses."""
-    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
-    ref = torch.as_tensor(reference_coord, dtype=torch.float32).cpu()
-    n_ref = int(ref.shape[0])
-    check_reference_atoms(n_ref)
+    dev, ref, x, nn = _shape_inputs(reference_coord, coords, n_nodes, device, with_reference=True)
     B, W = int(coords.shape[0]), int(coords.shape[1])
-    if B == 0:
+    if x is None:
         out = dict(coords=torch.zeros(0, W, 3, device=dev), rotation=torch.zeros(0, 3, 3, device=dev),
                    translation=torch.zeros(0, 3, device=dev), tanimoto=torch.zeros(0, device=dev),
                    orientation=torch.zeros(0, dtype=torch.long, device=dev),
@@ -340,15 +349,7 @@ def shape_overlay(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: 
         if with_scores:
             out["scores"] = torch.zeros(0, 4, device=dev)
         return out
-    check_n_nodes(n_nodes, B, W)
-    N = max(W, n_ref)
-    if N > MAX_SCORED_ATOMS:
-        raise ValueError(f"shape scoring takes at most {MAX_SCORED_ATOMS} atoms per molecule, got a padded width of {N}")
-    cand = coords.to(dev, torch.float32)
-    x = torch.zeros(B + 1, N, 3, device=dev)
-    x[0, :n_ref] = ref.to(dev)
-    x[1:, :W] = cand
-    nn = torch.cat([torch.tensor([n_ref], dtype=torch.int32, device=dev), n_nodes.to(dev, torch.int32).reshape(B)])
+    n_ref, N = int(ref.shape[0]), int(x.shape[1])
     xform = torch.empty(B + 1, 12, device=dev)
     _, frames = shape_frames_hip(x, nn, dev, centre_atoms=True, xform_out=xform)
     ref_frame = frames[0, :n_ref].contiguous()
@@ -368,7 +369,7 @@ def shape_overlay(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: 
                                             _lib.dptr(pose), _lib.dptr(posed), _lib.current_stream_ptr(dev)),
                "mcg_shape_overlay")
     failed = (which < 0).view(B, 1, 1)
-    out = dict(coords=torch.where(failed, cand, posed[:, :W]), rotation=pose[:, :9].reshape(B, 3, 3),
+    out = dict(coords=torch.where(failed, x[1:, :W], posed[:, :W]), rotation=pose[:, :9].reshape(B, 3, 3),
                translation=pose[:, 9:], tanimoto=best, orientation=which.long(), flipped=flipped.bool())
     if with_scores:
         out["scores"] = scores
@@ -435,23 +436,14 @@ def pairwise_shape_tanimoto(reference_coord: torch.Tensor, coords: torch.Tensor,
     (i, j) has the same bits whatever the batch, row order or padded width.  A molecule with no atoms or a non-finite
     coordinate gets a NaN row and column; the other entries are unaffected.  Refuses, before any device work, what
     `shape_scores` refuses and more than `MAX_PAIR_BATCH` molecules."""
-    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
-    ref = torch.as_tensor(reference_coord, dtype=torch.float32).cpu()
-    n_ref = int(ref.shape[0])
-    check_reference_atoms(n_ref)
-    B, W = int(coords.shape[0]), int(coords.shape[1])
-    if B > MAX_PAIR_BATCH:
-        raise ValueError(f"pairwise shape Tanimoto takes at most {MAX_PAIR_BATCH} molecules, got {B}")
-    if B == 0:
+    dev, ref, x, nn = _shape_inputs(reference_coord, coords, n_nodes, device, with_reference=False,
+                                    max_batch=MAX_PAIR_BATCH)
+    if x is None:
         return torch.zeros(0, 0, device=dev)
-    check_n_nodes(n_nodes, B, W)
-    if W > MAX_SCORED_ATOMS:
-        raise ValueError(f"shape scoring takes at most {MAX_SCORED_ATOMS} atoms per molecule, got a padded width of {W}")
-    x = coords.to(dev, torch.float32).contiguous()
-    nn = n_nodes.to(dev, torch.int32).reshape(B).contiguous()
+    B, W = x.shape[0], x.shape[1]
     xform = torch.empty(1, 12, device=dev)
-    _, frames = shape_frames_hip(ref.to(dev).unsqueeze(0), torch.tensor([n_ref], dtype=torch.int32, device=dev), dev,
-                                 centre_atoms=True, xform_out=xform)
+    _, frames = shape_frames_hip(ref.to(dev).unsqueeze(0), torch.tensor([ref.shape[0]], dtype=torch.int32, device=dev),
+                                 dev, centre_atoms=True, xform_out=xform)
     n = 40
     axes = _grid_axes(frames[0].cpu(), n).to(dev).contiguous()
     gp = -(-n ** 3 // _PAIR_KALIGN) * _PAIR_KALIGN

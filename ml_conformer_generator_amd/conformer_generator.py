@@ -47,6 +47,7 @@ forced by the scope of this build:
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import operator
 import os
 import time
@@ -56,6 +57,7 @@ from typing import List, Optional, Union
 import torch
 
 from . import _lib
+from . import cheminformatics
 from . import seeding
 from .adj_mat_seer import AdjMatSeer
 from .config import (ATOM_DECODER, CONTEXT_NORMS, DIMENSION, MAX_N_NODES, MIN_N_NODES, NOISE_PRECISION,
@@ -97,7 +99,7 @@ def _finish(mols: List, optimise_geometry: bool, use_rdkit: Optional[bool] = Non
         _WARNED_NO_MMFF[0] = True
         warnings.warn("ml_conformer_generator_amd: RDKit is not installed - optimise_geometry=True (MMFF94) is NOT applied and "
                       "validity is the labelled valence / single-fragment proxy; pass optimise_geometry=False to silence this",
-                      RuntimeWarning, stacklevel=3)
+                      RuntimeWarning, stacklevel=4)
     kept = [m for m in mols if m.valid]
     return kept, len(kept) / len(mols)
 
@@ -106,6 +108,22 @@ def _load_state_dict(src, device) -> dict:
     if isinstance(src, dict):
         return src["state_dict"] if "state_dict" in src else src
     return torch.load(src, map_location="cpu")["state_dict"]      # conformer_generator.py:90-102
+
+
+def _heavy_coords(mols: List):
+    """(padded [B, max n, 3], n_nodes [B]) of Mols' heavy-atom conformer positions."""
+    return cheminformatics.padded_coords([cheminformatics.mol_heavy_coords(m) for m in mols])
+
+
+@dataclasses.dataclass(frozen=True)
+class _ShapeRequest:
+    """The shape options of one generation call (`MLConformerGenerator._shape_request`): pose, then score, then select."""
+    ref_coord: torch.Tensor                       # the reference's heavy-atom coordinates [n,3] fp32, host
+    overlay: bool
+    scoring: bool                                 # `shape_scores`, or implied by any of the three selection options
+    top_k: Optional[int]
+    min_shape_tanimoto: Optional[float]
+    max_pairwise_tanimoto: Optional[float]
 
 
 class MLConformerGenerator(torch.nn.Module):
@@ -182,7 +200,7 @@ class MLConformerGenerator(torch.nn.Module):
         self.last_order = None
         self.last_valid_fraction = None   # share of the last batch that passed the validity proxy
         self.last_noise_seed = None       # device-generator seed of the last sharded call on this rank
-        self.last_host_assembly_ms = None # host time of the last sharded call's D2H + molecule records
+        self.last_host_assembly_ms = None # host time of the last call's D2H + molecule records (0.0 through a finisher)
         self._timing = None          # bench.py: {"sampler_start", "sampler_end"} events recorded around the sampler
 
     def set_diffusion_steps(self, diffusion_steps: int) -> None:
@@ -307,18 +325,16 @@ class MLConformerGenerator(torch.nn.Module):
         raise ValueError(
             "Either a reference RDkit Mol object or context as torch.Tensor should be provided for generation.")
 
-    def _scoring_reference(self, reference_conformer, shape_scores: bool, top_k: Optional[int],
-                           min_shape_tanimoto: Optional[float], overlay: bool = False,
-                           max_pairwise_tanimoto: Optional[float] = None) -> Optional[torch.Tensor]:
-        """The reference's heavy-atom coordinates when the call scores (`shape_scores`, or `top_k` / `min_shape_tanimoto` /
-        `max_pairwise_tanimoto`, which imply it) or poses (`overlay`), else None.  Every refusal happens here, before any
-        device work."""
-        if not (shape_scores or top_k is not None or min_shape_tanimoto is not None or overlay or
-                max_pairwise_tanimoto is not None):
+    def _shape_request(self, reference_conformer, shape_scores: bool, top_k: Optional[int],
+                       min_shape_tanimoto: Optional[float], overlay: bool = False,
+                       max_pairwise_tanimoto: Optional[float] = None) -> Optional[_ShapeRequest]:
+        """The call's shape options, or None when it asked for none of them (`top_k` / `min_shape_tanimoto` /
+        `max_pairwise_tanimoto` imply scoring).  Every refusal happens here, before any device work."""
+        scoring = shape_scores or top_k is not None or min_shape_tanimoto is not None or max_pairwise_tanimoto is not None
+        if not (scoring or overlay):
             return None
         if max_pairwise_tanimoto is not None:
-            from .cheminformatics import check_max_pairwise_tanimoto
-            check_max_pairwise_tanimoto(max_pairwise_tanimoto)
+            cheminformatics.check_max_pairwise_tanimoto(max_pairwise_tanimoto)
             if not overlay:
                 raise ValueError("max_pairwise_tanimoto needs overlay=True: molecules that are not posed onto the reference "
                                  "share no frame to compare them in")
@@ -339,76 +355,109 @@ class MLConformerGenerator(torch.nn.Module):
             raise ValueError(f"{what} cannot be combined with a custom finisher: its results carry no coordinates "
                              "this package can read")
         ref_coord = self._reference_coord(reference_conformer)
-        from .cheminformatics import check_reference_atoms
-        check_reference_atoms(int(ref_coord.shape[0]))
-        return ref_coord
+        cheminformatics.check_reference_atoms(int(ref_coord.shape[0]))
+        return _ShapeRequest(ref_coord, bool(overlay), bool(scoring), top_k, min_shape_tanimoto, max_pairwise_tanimoto)
 
+    # device seams of the shape step (stubbed by the host tests)
     def _score_coords(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
         """Shape Tanimoto [B] (device) of padded heavy-atom coordinates against the reference."""
-        from .cheminformatics import shape_scores
-        return shape_scores(ref_coord, coords, n_nodes, self.device)[0]
-
-    def _score_mols(self, ref_coord: torch.Tensor, mols: List) -> List[Optional[float]]:
-        """Shape Tanimoto of finished Mols' heavy-atom conformer positions (None where a molecule was dropped), in ONE
-        batched device call."""
-        from .cheminformatics import mol_heavy_coords, padded_coords
-        live = [k for k, m in enumerate(mols) if m is not None]
-        out: List[Optional[float]] = [None] * len(mols)
-        if live:
-            coords, n = padded_coords([mol_heavy_coords(mols[k]) for k in live])
-            for k, v in zip(live, self._score_coords(ref_coord, coords, n).cpu().tolist()):
-                out[k] = float(v)
-        return out
+        return cheminformatics.shape_scores(ref_coord, coords, n_nodes, self.device)[0]
 
     def _pose_coords(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor) -> dict:
         """Padded heavy-atom coordinates posed onto the reference (`cheminformatics.shape_overlay`, device tensors)."""
-        from .cheminformatics import shape_overlay
-        return shape_overlay(ref_coord, coords, n_nodes, self.device)
-
-    def _pose_mols(self, ref_coord: torch.Tensor, mols: List) -> List:
-        """Finished Mols posed onto the reference in ONE batched device call, every conformer position moved (None where a
-        molecule was dropped); per Mol (overlay_tanimoto, rotation, translation)."""
-        from .cheminformatics import pose_mols
-        return pose_mols(ref_coord, mols, overlay_fn=self._pose_coords)
-
-    @staticmethod
-    def _pose_rows(ov: dict) -> torch.Tensor:
-        """[B,12]: rotation row-major, then translation (NaN where posing failed)."""
-        return torch.cat([ov["rotation"].reshape(-1, 9), ov["translation"].reshape(-1, 3)], dim=1)
+        return cheminformatics.shape_overlay(ref_coord, coords, n_nodes, self.device)
 
     def _pair_coords(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
         """[B,B] pairwise shape Tanimoto (device) of padded heavy-atom coordinates posed onto the reference
         (`cheminformatics.pairwise_shape_tanimoto`)."""
-        from .cheminformatics import pairwise_shape_tanimoto
-        return pairwise_shape_tanimoto(ref_coord, coords, n_nodes, self.device)
+        return cheminformatics.pairwise_shape_tanimoto(ref_coord, coords, n_nodes, self.device)
 
-    def _pair_rows(self, ref_coord: torch.Tensor, x: torch.Tensor, n_nodes: torch.Tensor, mols: List,
-                   kept: List) -> torch.Tensor:
-        """The pair matrix of the records `kept` (a subset of `mols`, whose record b is row b of x / n_nodes), in the
-        order of `kept`, from the posed device coordinates."""
-        row = {id(m): b for b, m in enumerate(mols)}
-        idx = torch.tensor([row[id(m)] for m in kept], dtype=torch.long, device=x.device)
-        return self._pair_coords(ref_coord, x.index_select(0, idx),
-                                 n_nodes.reshape(-1).to(x.device).index_select(0, idx))
+    def _shape_tensors(self, req: Optional[_ShapeRequest], res: dict) -> dict:
+        """The shape step of one shard's result tensors: pose, then score (a score is the score of the returned
+        coordinates).  `res` with `x` posed and the per-sample tensors `overlay_tanimoto`, `pose` [B,12] (rotation
+        row-major, then translation; NaN where posing failed) and `shape_tanimoto` added, as far as the call asked."""
+        if req is None:
+            return res
+        if req.overlay:
+            ov = self._pose_coords(req.ref_coord, res["x"], res["n_nodes"])
+            res = dict(res, x=ov["coords"], overlay_tanimoto=ov["tanimoto"],
+                       pose=torch.cat([ov["rotation"].reshape(-1, 9), ov["translation"].reshape(-1, 3)], dim=1))
+        if req.scoring:
+            res = dict(res, shape_tanimoto=self._score_coords(req.ref_coord, res["x"], res["n_nodes"]))
+        return res
 
-    def _pair_mols(self, ref_coord: torch.Tensor, mols: List) -> torch.Tensor:
-        """The pair matrix of finished, posed Mols (none of them None) from their heavy-atom conformer positions."""
-        from .cheminformatics import mol_heavy_coords, padded_coords
-        coords, n = padded_coords([mol_heavy_coords(m) for m in mols])
-        return self._pair_coords(ref_coord, coords, n)
+    def _score_mols(self, ref_coord: torch.Tensor, mols: List) -> List[Optional[float]]:
+        """Shape Tanimoto of finished Mols' heavy-atom conformer positions (None where a molecule was dropped), in ONE
+        batched device call."""
+        live = [k for k, m in enumerate(mols) if m is not None]
+        out: List[Optional[float]] = [None] * len(mols)
+        if live:
+            for k, v in zip(live, self._score_coords(ref_coord, *_heavy_coords([mols[k] for k in live])).cpu().tolist()):
+                out[k] = float(v)
+        return out
+
+    def _shape_objects(self, req: Optional[_ShapeRequest], done: List):
+        """The shape step of one shard's finished Mols (None = dropped), each stage in ONE batched device call: pose, every
+        conformer position moved (`cheminformatics.pose_mols`), then score (`_score_mols`).  Per Mol (scores, poses):
+        the shape Tanimoto and (overlay_tanimoto, rotation, translation); None where the call did not ask or the Mol
+        was dropped."""
+        none = [None] * len(done)
+        poses = (cheminformatics.pose_mols(req.ref_coord, done, overlay_fn=self._pose_coords)
+                 if req is not None and req.overlay else none)
+        scores = self._score_mols(req.ref_coord, done) if req is not None and req.scoring else list(none)
+        return scores, poses
 
     @staticmethod
-    def _select(mols: List, scores: List[float], sample_ids: List[int], top_k: Optional[int],
-                min_shape_tanimoto: Optional[float], max_pairwise_tanimoto: Optional[float] = None,
-                pair_fn=None) -> List:
-        """Threshold, then sphere exclusion at `max_pairwise_tanimoto` (`pair_fn()`: the pair matrix of `mols`, only
-        called when it is set), then `top_k` (`cheminformatics.select_diverse`)."""
-        if top_k is None and min_shape_tanimoto is None and max_pairwise_tanimoto is None:
+    def _select(req: Optional[_ShapeRequest], mols: List, scores: List[float], sample_ids: List[int], pair_fn) -> List:
+        """`mols` through the call's selection: threshold, then sphere exclusion at `max_pairwise_tanimoto` (`pair_fn()`:
+        the pair matrix of `mols`, only called when it is set), then `top_k` (`cheminformatics.select_diverse`); all of
+        them when the call selects nothing."""
+        if req is None or (req.top_k is None and req.min_shape_tanimoto is None and req.max_pairwise_tanimoto is None):
             return mols
-        from .cheminformatics import select_diverse
-        pair = pair_fn() if max_pairwise_tanimoto is not None else None
-        return [mols[i] for i in select_diverse(scores, sample_ids, pair, max_pairwise_tanimoto, top_k,
-                                                min_shape_tanimoto)]
+        pair = pair_fn() if req.max_pairwise_tanimoto is not None else None
+        keep = cheminformatics.select_diverse(scores, sample_ids, pair, req.max_pairwise_tanimoto, req.top_k,
+                                              req.min_shape_tanimoto)
+        return [mols[i] for i in keep]
+
+    def _return_records(self, req: Optional[_ShapeRequest], res: dict, row_ids: Optional[torch.Tensor],
+                        optimise_geometry: bool) -> List:
+        """What a call returns without a finisher: the `GeneratedMolecule` records of the rows this rank returns (sample
+        ids `row_ids`, default 0..B-1; one D2H), filtered by the validity proxy, then selected, the pair matrix taken
+        from the posed rows."""
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)       # (the D2H copies below would wait for the device anyway: keep that out of the figure)
+        t0 = time.perf_counter()
+        mols = molecules_from_tensors(res["x"], res["elements"], res["bond"], res["n_nodes"], res["valid"],
+                                      sample_ids=row_ids, shape_tanimoto=res.get("shape_tanimoto"),
+                                      overlay_tanimoto=res.get("overlay_tanimoto"), pose=res.get("pose"))
+        self.last_host_assembly_ms = (time.perf_counter() - t0) * 1e3      # D2H of the result tensors + record views
+        kept, self.last_valid_fraction = _finish(mols, optimise_geometry, use_rdkit=False)    # no finisher: the proxy
+
+        def pair():
+            row = {id(m): b for b, m in enumerate(mols)}
+            idx = torch.tensor([row[id(m)] for m in kept], dtype=torch.long, device=res["x"].device)
+            return self._pair_coords(req.ref_coord, res["x"].index_select(0, idx),
+                                     res["n_nodes"].reshape(-1).to(res["x"].device).index_select(0, idx))
+        return self._select(req, kept, [m.shape_tanimoto for m in kept], [m.sample_id for m in kept], pair)
+
+    def _return_objects(self, req: Optional[_ShapeRequest], done: List, scores: List, poses: List,
+                        row_ids: Optional[torch.Tensor], sample_seed: Optional[int]) -> List:
+        """What a call returns through a finisher: the finished Mols of the rows this rank returns (None = dropped; sample
+        ids `row_ids`, default 0..B-1) get their properties - `sample_id` (seeded calls), `overlay_tanimoto`,
+        `shape_tanimoto`: set here, behind the object gather, which does not carry Mol properties - then the live ones
+        are selected, the pair matrix taken from their posed heavy atoms."""
+        from . import rdkit_finish
+        ids = list(range(len(done))) if row_ids is None else row_ids.tolist()
+        if sample_seed is not None:
+            rdkit_finish.tag_sample_ids(done, ids)
+        self.last_host_assembly_ms = 0.0
+        live = [i for i, m in enumerate(done) if m is not None]
+        self.last_valid_fraction = len(live) / len(done) if done else 0.0
+        rdkit_finish.tag_scores(done, "overlay_tanimoto", [None if p is None else p[0] for p in poses])
+        rdkit_finish.tag_scores(done, "shape_tanimoto", scores)
+        picked = [done[i] for i in live]
+        return self._select(req, picked, [scores[i] for i in live], [ids[i] for i in live],
+                            lambda: self._pair_coords(req.ref_coord, *_heavy_coords(picked)))
 
     def _executor(self):
         """Where the poolable host tasks run: the process-wide `HostPool` with `n_host_workers` workers and this generator's
@@ -499,11 +548,16 @@ class MLConformerGenerator(torch.nn.Module):
         return dict(x=x_out, elements=el.to(torch.int8), bond=sym, n_nodes=n_nodes.to(torch.int32),
                     valid=valid.to(torch.uint8))
 
-    def _collect_finish(self, stage):
-        """The pending finish of the shard generated last -> per-sample results (None = dropped)."""
-        t0 = time.perf_counter()
-        done = stage.results()
-        self.last_host_finish_ms = (time.perf_counter() - t0) * 1e3
+    def _collect_finish(self, n_samples: int) -> List:
+        """The pending finish of the shard generated last -> its `n_samples` per-sample results (None = dropped)."""
+        stage, self._finish_stage = getattr(self, "_finish_stage", None), None
+        done = []
+        if stage is not None:
+            t0 = time.perf_counter()
+            done = stage.results()
+            self.last_host_finish_ms = (time.perf_counter() - t0) * 1e3
+        if len(done) != n_samples:
+            raise ValueError(f"the finish returned {len(done)} results for a shard of {n_samples}")
         return done
 
     @torch.no_grad()
@@ -544,49 +598,16 @@ class MLConformerGenerator(torch.nn.Module):
         overlay, and a custom finisher."""
         if sample_seed is not None:
             seeding.check_seed(sample_seed)
-        ref_coord = self._scoring_reference(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
-                                            max_pairwise_tanimoto)
-        scoring = shape_scores or top_k is not None or min_shape_tanimoto is not None or max_pairwise_tanimoto is not None
+        req = self._shape_request(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
+                                  max_pairwise_tanimoto)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
-        if sample_seed is None:       # the positional call of before: a stub of `_generate_shard` need not know the seed
-            res = self._generate_shard(ref_context, ref_n_atoms, variance, None, n_samples, resample_steps, fixed_fragment,
-                                       inertial_fragment_matching, blend_power, ifm_diffusion_level, optimise_geometry)
-        else:
-            res = self._generate_shard(ref_context, ref_n_atoms, variance, None, n_samples, resample_steps, fixed_fragment,
-                                       inertial_fragment_matching, blend_power, ifm_diffusion_level, optimise_geometry,
-                                       sample_seed, None)
-        stage, self._finish_stage = getattr(self, "_finish_stage", None), None
-        if stage is not None:                     # finished per group while the later groups were still on their way
-            done = self._collect_finish(stage)
-            if sample_seed is not None:
-                from . import rdkit_finish
-                rdkit_finish.tag_sample_ids(done, range(len(done)))
-            live = [i for i, m in enumerate(done) if m is not None]
-            self.last_valid_fraction = len(live) / len(done) if done else 0.0
-            if overlay:
-                self._pose_mols(ref_coord, done)
-            if not scoring:
-                return [done[i] for i in live]
-            from . import rdkit_finish
-            scores = self._score_mols(ref_coord, done)
-            rdkit_finish.tag_shape_scores(done, scores)
-            picked = [done[i] for i in live]
-            return self._select(picked, [scores[i] for i in live], live, top_k, min_shape_tanimoto, max_pairwise_tanimoto,
-                                lambda: self._pair_mols(ref_coord, picked))
-        x, ov = res["x"], None
-        if overlay:                           # pose first: a score is the score of the returned coordinates
-            ov = self._pose_coords(ref_coord, x, res["n_nodes"])
-            x = ov["coords"]
-        scores = self._score_coords(ref_coord, x, res["n_nodes"]) if scoring else None
-        mols = molecules_from_tensors(x, res["elements"], res["bond"], res["n_nodes"], res["valid"],
-                                      shape_tanimoto=scores, overlay_tanimoto=None if ov is None else ov["tanimoto"],
-                                      pose=None if ov is None else self._pose_rows(ov))                 # single D2H
-        kept, self.last_valid_fraction = _finish(mols, optimise_geometry, use_rdkit=False)    # no finisher: the proxy
-        if not scoring:
-            return kept
-        return self._select(kept, [m.shape_tanimoto for m in kept], [m.sample_id for m in kept], top_k,
-                            min_shape_tanimoto, max_pairwise_tanimoto,
-                            lambda: self._pair_rows(ref_coord, x, res["n_nodes"], mols, kept))
+        keyed = () if sample_seed is None else (sample_seed, None)   # unseeded: the positional call of before
+        res = self._generate_shard(ref_context, ref_n_atoms, variance, None, n_samples, resample_steps, fixed_fragment,
+                                   inertial_fragment_matching, blend_power, ifm_diffusion_level, optimise_geometry, *keyed)
+        if getattr(self, "finisher", None) is None:
+            return self._return_records(req, self._shape_tensors(req, res), None, optimise_geometry)
+        done = self._collect_finish(n_samples)    # finished per group while the later groups were still on their way
+        return self._return_objects(req, done, *self._shape_objects(req, done), None, sample_seed)
 
     @torch.no_grad()
     def generate_conformers_sharded(self, reference_conformer=None, n_samples: int = 10, variance: int = 2,
@@ -613,60 +634,39 @@ class MLConformerGenerator(torch.nn.Module):
         `sample_seed` (instead of `seed`): the keyed stream of `edm_tensors` - every rank computes the keyed sizes of all
         `n_samples` itself (no broadcast), generates its shard with the shard's global indices as `sample_ids` and seeds
         no generator, so sample i is the same molecule on any world size and under either `balance`.
-        `shape_scores`, `top_k`, `min_shape_tanimoto`: as in `generate_conformers`.  Every rank scores ITS OWN shard on its
-        own GPU before the gather (the scores travel with the result tensors, or next to the finished Mols); the
-        selection runs on what each rank returns: with gather="all" every rank returns the same selection, with
-        gather="rank0" rank 0 selects from the whole batch and every other rank within its own shard.
-        `overlay`: as in `generate_conformers`; every rank poses its own shard on its own GPU before the gather (the
-        posed coordinates travel in the result tensors, the pose and its score as two more per-sample tensors, or the
-        posed Mols with their scores next to them).
-        `max_pairwise_tanimoto`: as in `generate_conformers`; the selection runs where the ranking selection runs, on the
-        rows a rank returns (gather="all": every rank computes the pair matrix of the whole batch on its own GPU and
-        returns the same list)."""
+        `shape_scores`, `top_k`, `min_shape_tanimoto`, `overlay`, `max_pairwise_tanimoto`: as in `generate_conformers`.
+        Every rank poses and scores ITS OWN shard on its own GPU before the gather (posed coordinates, poses and scores
+        travel as per-sample result tensors, or next to the finished Mols).  The selection runs on the rows a rank
+        returns: with gather="all" every rank selects from the whole batch (the pair matrix of the whole batch on its own
+        GPU) and returns the same list; with gather="rank0" every other rank selects within its own shard."""
         if gather not in ("all", "rank0"):
             raise ValueError("gather must be 'all' or 'rank0'")
         if sample_seed is not None:
             if seed is not None:
                 raise ValueError("pass either seed (per-rank device generator) or sample_seed (keyed stream), not both")
             seeding.check_seed(sample_seed)
-        ref_coord = self._scoring_reference(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
-                                            max_pairwise_tanimoto)
-        scoring = shape_scores or top_k is not None or min_shape_tanimoto is not None or max_pairwise_tanimoto is not None
+        req = self._shape_request(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
+                                  max_pairwise_tanimoto)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)
         hi_n = min(ref_n_atoms + variance, self.max_n_nodes)
-        self._finish_stage = None
         # decided from the configuration, not from what this rank's shard happened to produce: every rank takes the same
         # path through the collectives (an EMPTY shard has no stage of its own making)
         finishing = getattr(self, "finisher", None) is not None
-        finished: List = [None]
-        finished_scores: List = [None]
-        finished_poses: List = [None]
+        finished: List = []       # (Mol, score, pose) per sample of this rank's shard, where a finisher runs
 
         def run_shard(sizes_shard, index):
             keyed = () if sample_seed is None else (sample_seed, index)
             res = self._generate_shard(ref_context, ref_n_atoms, variance, sizes_shard, int(index.numel()), resample_steps,
                                        fixed_fragment, inertial_fragment_matching, blend_power, ifm_diffusion_level,
                                        optimise_geometry, *keyed)
-            if finishing:
-                # collected HERE, in front of the status exchange: a finish that raises on one rank (a dead worker, a custom
-                # finisher's exception, a result-count mismatch) makes EVERY rank raise ShardError instead of leaving the
-                # others parked in the object gather
-                stage, self._finish_stage = getattr(self, "_finish_stage", None), None
-                done = self._collect_finish(stage) if stage is not None else []
-                if len(done) != int(index.numel()):
-                    raise ValueError(f"the finish returned {len(done)} results for a shard of {int(index.numel())}")
-                finished[0] = done
-                if overlay:                   # pose first: a score is the score of the returned coordinates
-                    finished_poses[0] = self._pose_mols(ref_coord, done)
-                if scoring:
-                    finished_scores[0] = self._score_mols(ref_coord, done)
-            elif ref_coord is not None:       # more per-sample tensors for the gather
-                if overlay:
-                    ov = self._pose_coords(ref_coord, res["x"], res["n_nodes"])
-                    res = dict(res, x=ov["coords"], overlay_tanimoto=ov["tanimoto"], pose=self._pose_rows(ov))
-                if scoring:
-                    res = dict(res, shape_tanimoto=self._score_coords(ref_coord, res["x"], res["n_nodes"]))
+            if not finishing:
+                return self._shape_tensors(req, res)      # posed / scored on this rank's GPU, gathered with the rest
+            # collected HERE, in front of the status exchange: a finish that raises on one rank (a dead worker, a custom
+            # finisher's exception, a result-count mismatch) makes EVERY rank raise ShardError instead of leaving the
+            # others parked in the object gather
+            done = self._collect_finish(int(index.numel()))
+            finished[:] = zip(done, *self._shape_objects(req, done))
             return res
 
         def seed_device(s):
@@ -684,51 +684,15 @@ class MLConformerGenerator(torch.nn.Module):
             n_samples, draw_sizes, run_shard, group=group,
             seed=seed, seed_fn=seed_fn, gather_dst=dst, balance=balance, gather_tensors=not finishing)
         self.last_shards = shards
-        self._finish_stage = None
         # the sample ids of the rows this rank returns: the whole batch in sample order, or (gather="rank0", rank > 0)
         # its own shard
         _, rank = mcg_dist.world_and_rank(group)
         row_ids = shards[rank] if (dst is not None and rank != dst and len(shards) > 1) else None
-        if finishing:                         # RDKit's gate: this rank's shard was finished above, the Mols travel as objects
-            if ref_coord is None:
-                done = mcg_dist.gather_objects(finished[0], shards, group, dst)
-            else:                             # scores and poses travel next to the Mols, attached after the gather
-                n_local = len(finished[0])
-                local_scores = finished_scores[0] if scoring else [None] * n_local
-                local_poses = finished_poses[0] if overlay else [None] * n_local
-                triples = mcg_dist.gather_objects(list(zip(finished[0], local_scores, local_poses)), shards, group, dst)
-                done, scores, poses = [p[0] for p in triples], [p[1] for p in triples], [p[2] for p in triples]
-            ids = list(range(len(done))) if row_ids is None else row_ids.tolist()
-            if sample_seed is not None:
-                from . import rdkit_finish
-                rdkit_finish.tag_sample_ids(done, ids)
-            self.last_host_assembly_ms = 0.0
-            live = [i for i, m in enumerate(done) if m is not None]
-            self.last_valid_fraction = len(live) / len(done) if done else 0.0
-            if ref_coord is None:
-                return [done[i] for i in live]
-            from . import rdkit_finish
-            if overlay:
-                rdkit_finish.tag_overlay_scores(done, [None if p is None else p[0] for p in poses])
-            if not scoring:
-                return [done[i] for i in live]
-            rdkit_finish.tag_shape_scores(done, scores)
-            picked = [done[i] for i in live]
-            return self._select(picked, [scores[i] for i in live], [ids[i] for i in live], top_k, min_shape_tanimoto,
-                                max_pairwise_tanimoto, lambda: self._pair_mols(ref_coord, picked))
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)       # (the D2H copies below would wait for the device anyway: keep that out of the figure)
-        t0 = time.perf_counter()
-        mols = molecules_from_tensors(res["x"], res["elements"], res["bond"], res["n_nodes"], res["valid"],
-                                      sample_ids=row_ids, shape_tanimoto=res.get("shape_tanimoto"),
-                                      overlay_tanimoto=res.get("overlay_tanimoto"), pose=res.get("pose"))
-        self.last_host_assembly_ms = (time.perf_counter() - t0) * 1e3      # D2H of the gathered tensors + record views
-        kept, self.last_valid_fraction = _finish(mols, optimise_geometry, use_rdkit=False)    # no finisher: the proxy
-        if not scoring:
-            return kept
-        return self._select(kept, [m.shape_tanimoto for m in kept], [m.sample_id for m in kept], top_k,
-                            min_shape_tanimoto, max_pairwise_tanimoto,
-                            lambda: self._pair_rows(ref_coord, res["x"], res["n_nodes"], mols, kept))
+        if not finishing:
+            return self._return_records(req, res, row_ids, optimise_geometry)
+        rows = mcg_dist.gather_objects(finished, shards, group, dst)      # the Mols travel as objects, with their scores
+        return self._return_objects(req, [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows], row_ids,
+                                    sample_seed)
 
     @torch.no_grad()
     def forward(self, reference_conformer=None, n_samples: int = 10, variance: int = 2,

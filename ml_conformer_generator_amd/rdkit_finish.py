@@ -147,17 +147,10 @@ def tag_sample_ids(mols: Sequence, sample_ids: Sequence[int]) -> None:
             m.SetIntProp("sample_id", int(sid))
 
 
-def tag_shape_scores(mols: Sequence, scores: Sequence[Optional[float]]) -> None:
-    """Set the double property `shape_tanimoto` on every Mol of `mols` (None = dropped); `scores[k]` belongs to `mols[k]`.
-    Set after the object gather: RDKit does not pickle Mol properties by default."""
+def tag_scores(mols: Sequence, prop: str, scores: Sequence[Optional[float]]) -> None:
+    """Set the double property `prop` (`shape_tanimoto`, `overlay_tanimoto`) on every Mol of `mols` (None = dropped);
+    `scores[k]` belongs to `mols[k]`, None = no score.  Set after the object gather: RDKit does not pickle Mol properties
+    by default."""
     for m, sc in zip(mols, scores):
         if m is not None and sc is not None and hasattr(m, "SetDoubleProp"):
-            m.SetDoubleProp("shape_tanimoto", float(sc))
-
-
-def tag_overlay_scores(mols: Sequence, scores: Sequence[Optional[float]]) -> None:
-    """Set the double property `overlay_tanimoto` (the score of the Mol's pose onto the reference) on every Mol of `mols`
-    (None = dropped); set again after the object gather, which does not carry Mol properties."""
-    for m, sc in zip(mols, scores):
-        if m is not None and sc is not None and hasattr(m, "SetDoubleProp"):
-            m.SetDoubleProp("overlay_tanimoto", float(sc))
+            m.SetDoubleProp(prop, float(sc))

@@ -70,8 +70,8 @@ def test_select_diverse_edge_cases():
 def test_diversity_refusals_happen_before_any_device_work(entry):
     from ml_conformer_generator_amd import host_pool as HP
     gen = _shell_generator()
-    gen._generate_shard = gen._score_coords = gen._score_mols = gen._pose_coords = gen._pose_mols = _no_device
-    gen._pair_coords = gen._pair_rows = gen._pair_mols = _no_device
+    gen._generate_shard = gen._score_coords = gen._score_mols = gen._pose_coords = _no_device
+    gen._pair_coords = _no_device
     call = getattr(gen, entry)
     ctx = torch.tensor([50.0, 100.0, 130.0])
     for kw in (dict(reference_conformer=_ref(), max_pairwise_tanimoto=0.5),               # not posed: no common frame
