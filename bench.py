@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the mlconfgen denoising hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is ONE call of the public path `MLConformerGenerator.generate_conformers_sharded` over one batch of
 synthetic input: the full ancestral sampler (T = 100 denoising steps = 101 EGNN calls), the device-side
@@ -11,10 +11,13 @@ Workload at N = 1: BASELINE.json configs[1] (n_samples = 64, 27 heavy atoms, dif
 fp32).  For N > 1 every rank generates its contiguous shard of 64 x N molecules (weak scaling, 64 per GPU)
 on its own weight replica; the results are gathered once with RCCL at the end of each step.
 
-The default (N = 1) line also carries, each timed in the same run: `config2_ragged256` (BASELINE configs[2] shape),
-`config0_plumbing` (configs[0]: ceyyag context, 4 samples, T = 20, with the CPU oracle run IN FULL beside it),
-`config4_share_bf16_inpaint` (one GPU's share of configs[4]: 256 ragged, bf16 operands, fixed fragment, rs = 1, T = 250)
-and `cpu_baseline`.  For N > 1 it carries `config3_ragged256_per_gpu` (configs[3]: 256 ragged molecules per rank).
+A plain run does only what the headline needs: set-up, the W warm-up and K timed steps, `--dump-outputs`, the line.
+`--full` adds everything else, measured after the timed steps: the edge-kernel `roofline`, `aggregate_roofline` and the
+host-stage probe; at N = 1 `cpu_baseline` and (fp32) `f32x6_candidate`, and with the default workload, each timed in the
+same run, `config2_ragged256` (BASELINE configs[2] shape), `config0_plumbing` (configs[0]: ceyyag context, 4 samples,
+T = 20, with the CPU oracle run IN FULL beside it) and `config4_share_bf16_inpaint` (one GPU's share of configs[4]: 256
+ragged, bf16 operands, fixed fragment, rs = 1, T = 250); for N > 1 `config3_ragged256_per_gpu` (configs[3]: 256 ragged
+molecules per rank).  The `--no-*` and `--cpu-*` options narrow what `--full` adds.
 
 `--gpus N` with N > 1 and no launcher environment (WORLD_SIZE unset): this process never touches a GPU (devices are
 counted from the KFD topology in sysfs, no HIP call); it starts N child ranks of itself (RANK / LOCAL_RANK /
@@ -51,6 +54,10 @@ def parse():
     ap.add_argument("--n-atoms", type=int, default=27)
     ap.add_argument("--variance", type=int, default=0, help=">0: ragged batch n_atoms +- variance (config 3: 27 +- 12)")
     ap.add_argument("--diffusion-steps", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline: rooflines, host-stage probe, "
+                         "f32x6 probe, the configs[0] / [2] / [4] objects and the CPU baseline (N = 1), configs[3] (N > 1); "
+                         "the --no-* and --cpu-* options narrow it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-phi-calls", type=int, default=3)
     ap.add_argument("--cpu-threads", type=int, default=0,
@@ -541,8 +548,13 @@ def time_edge_kernel_in_call(gen, plan, dev, calls=8):
     return float(us[0]) * 1e-6, float(us[1]) * 1e-6, int(us[2]), plan.n_ranges
 
 
+def last_plan(gen):
+    """The denoiser plan the generator used last (its plan cache is ordered by recency)."""
+    return next(reversed(gen.generative_model.dynamics._plans.values()))
+
+
 def edge_roofline(args, gen, dev, dtype, traffic=None, traffic_source=None):
-    plan = next(reversed(gen.generative_model.dynamics._plans.values()))
+    plan = last_plan(gen)
     sa_mean, sa_best = time_edge_kernel(gen, plan, dev)
     edge_s, equiv_s, n_timed, n_ranges = time_edge_kernel_in_call(gen, plan, dev)
     timing = ("mean of the GCL edge launches of 8 whole denoiser calls issued as plain launches, each launch's own begin / end "
@@ -579,12 +591,12 @@ def edge_roofline(args, gen, dev, dtype, traffic=None, traffic_source=None):
                   "flops_per_launch": fl}
 
 
-def host_stage_report(gen):
+def host_stage_report(gen, probe=True):
     """The two RDKit-owned host stages around the GCN (canonical order + connectivity before it, `redefine_bonds` +
     `standardize_mol` / MMFF behind it; `host_pool.py`).  Where RDKit imports they run inside the timed region, fanned out
     over `n_host_workers` worker processes, and their wall times are reported; RDKit exists on none of this project's
-    boxes, so there the object carries a labelled PROBE instead: the same pipeline (`rdkit_order.OrderStage` ->
-    per-group 'launch' -> `rdkit_finish.FinishStage`) over 256 molecules with a fake 2 ms-per-molecule function in each
+    boxes, so there (with `probe`) the object carries a labelled PROBE instead: the same pipeline (`rdkit_order.OrderStage`
+    -> per-group 'launch' -> `rdkit_finish.FinishStage`) over 256 molecules with a fake 2 ms-per-molecule function in each
     stage (tests/fake_host_tasks.py), pooled against serial, warm."""
     from ml_conformer_generator_amd import host_pool as HP
     from ml_conformer_generator_amd import rdkit_finish as RF
@@ -594,7 +606,7 @@ def host_stage_report(gen):
     out = {"rdkit": HAVE_RDKIT, "n_host_workers": gen.n_host_workers,
            "host_order_ms": gen.last_host_order_ms, "host_finish_ms": gen.last_host_finish_ms}
     fake = os.path.join(REPO, "tests", "fake_host_tasks.py")
-    if HAVE_RDKIT or not os.path.exists(fake):
+    if not probe or HAVE_RDKIT or not os.path.exists(fake):
         return out
     try:
         B, N = 256, 27
@@ -839,7 +851,7 @@ def main():
     headline_default = (B == 64 and args.variance == 0 and args.n_atoms == 27 and args.dtype == "f32" and not args.fragment
                         and args.diffusion_steps == 100)
     head_roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # dominant kernel of the HEADLINE workload, timed now: later sub-runs add plans of other shapes
         # HBM bytes per launch of the dominant kernel come from separate rocprofv3 --pmc passes (they cannot be taken
         # inside this run); quoted from the committed summary only for the exact workload it was measured on, and tagged
@@ -854,7 +866,7 @@ def main():
             pass
         head_roof = edge_roofline(args, gen, dev, args.dtype, traffic, traffic_source)
     c3 = None
-    if world > 1 and headline_default and not args.no_config3:
+    if args.full and world > 1 and headline_default and not args.no_config3:
         # BASELINE configs[3]: 256 ragged molecules PER GPU (n_samples = 256 x N in total), every rank, 1 warm-up + 2 passes
         el3, ms3, fin3, vf3 = timed_passes(gen, ctx, 256 * world, 27, 12, {}, 2, 1, fence, vary_sizes=True)
         asm3 = gen.last_host_assembly_ms
@@ -869,8 +881,11 @@ def main():
         value = total_mols / elapsed
         n_calls = (2 * args.diffusion_steps if args.fragment else args.diffusion_steps) + 1
         egnn_step_ms = sampler_ms / n_calls
-        plan, roof = head_roof
-        agg_s, agg_b = time_aggregate_kernel(plan, dev)
+        if args.full:
+            plan, roof = head_roof
+            agg_s, agg_b = time_aggregate_kernel(plan, dev)
+        else:
+            plan = last_plan(gen)
         if B == 64 and args.variance == 0 and args.n_atoms == 27:
             cfg_label = "configs[1]"
         elif B == 256 and args.variance == 12 and args.n_atoms == 27:
@@ -919,15 +934,16 @@ def main():
                                     "how": "pinned to the cores of this rank's GPU's NUMA node, shared between the ranks of the node "
                                            "(affinity.py, sysfs only); rank 0 shown"}
                                    if rank_cpus else {"count": (os.cpu_count() or 1) // max(1, world), "how": "not pinned"}),
-            "host_stages": host_stage_report(gen),
+            "host_stages": host_stage_report(gen, probe=args.full),
             "outputs_finite": finite,
-            "roofline": roof,
-            "aggregate_roofline": {"kernel": "k_aggregate (stand-alone gate*mask*segment-sum probe)", "bound": "hbm",
-                                   "achieved": agg_b / agg_s / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                   "frac": agg_b / agg_s / 1e9 / PEAK_HBM_GBS, "avg_launch_us": agg_s * 1e6,
-                                   "bytes_per_launch": agg_b},
         }
-        default_line = headline_default and world == 1
+        if args.full:
+            out["roofline"] = roof
+            out["aggregate_roofline"] = {"kernel": "k_aggregate (stand-alone gate*mask*segment-sum probe)", "bound": "hbm",
+                                         "achieved": agg_b / agg_s / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                         "frac": agg_b / agg_s / 1e9 / PEAK_HBM_GBS, "avg_launch_us": agg_s * 1e6,
+                                         "bytes_per_launch": agg_b}
+        default_line = args.full and headline_default and world == 1
         if c3 is not None:
             _, roof3 = edge_roofline(args, gen, dev, args.dtype)
             out["config3_ragged256_per_gpu"] = {
@@ -966,9 +982,9 @@ def main():
         if default_line and not args.no_config4:
             out["config4_share_bf16_inpaint"] = config4_share(args, gsd, ctx, dev, fence)
             finite = finite and out["config4_share_bf16_inpaint"]["outputs_finite"]
-        if args.dtype == "f32" and world == 1 and not args.no_x6_probe and not args.fragment:
+        if args.full and args.dtype == "f32" and world == 1 and not args.no_x6_probe and not args.fragment:
             out["f32x6_candidate"] = x6_probe(args, gen, sd, gsd, ctx, dev)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, sd, gsd)
             out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
         line = json.dumps(out)
