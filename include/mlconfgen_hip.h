@@ -314,6 +314,30 @@ int mcg_shape_overlay(const float* ref_frame, int n_ref, const float* ref_xform,
                       float amplitude, float* f_scratch, float* score, float* best, int32_t* which, int32_t* flipped,
                       float* pose, float* posed, void* stream);
 
+/* ---- Refined pose on the reference ("Refined pose"): mcg_shape_overlay, then each of its four
+ * starts moved as a rigid body to maximise the first-order Gaussian overlap with the reference,
+ * O(y, z) = sum_ij A^2 (pi / (2 alpha))^1.5 exp(-(alpha / 2) |y_i - z_j|^2), by `steps` (0..1024) steps of a
+ * normalised-gradient ascent (rotation about the atom centroid along the torque, translation along the force; a step is
+ * kept only if O strictly increases).  Takes mcg_shape_overlay's arguments (same meaning) and writes its outputs; then
+ *   refine_ws[B*4*12]   work space: per (candidate, start) G row-major, then t, with z' = z @ G + t;
+ *   objective[B*4*2]    optional (NULL = not wanted): O before and after the ascent, per start;
+ *   start_best[B]       the unrefined best score (mcg_shape_overlay's best, bit for bit);
+ *   refined[B]          1 where a refined candidate replaced the start pose: the four refined candidates are scored on
+ *                       the reference's grid exactly as mcg_shape_overlay scores the starts (refined_score[B*4],
+ *                       optional), and the first maximum replaces the start only if strictly better.  Then best / which /
+ *                       pose / posed describe the refined pose: Q = M_s' R_which G M_r^T, d = t_r + t @ M_r^T - t_s @ Q.
+ *                       A row that failed in mcg_shape_overlay keeps that entry's outputs (refined 0, NaN objective).
+ * Four launches on `stream` (density, overlay, one 256-lane workgroup per (candidate, start), one per candidate); every
+ * output is bit-identical whatever the batch, row or padded width.  steps = 0 gives mcg_shape_overlay's outputs bit for bit.
+ * MCG_ERR_ARG, nothing launched: mcg_shape_overlay's argument errors, a null refine_ws / start_best / refined, steps
+ * outside 0..1024, alpha not > 0. */
+int mcg_shape_overlay_refined(const float* ref_frame, int n_ref, const float* ref_xform, const float* frames,
+                              const float* xform, const int32_t* n_nodes_dev, int B, int N, const float* rot,
+                              const float* axes, int n, float alpha, float amplitude, float* f_scratch, float* score,
+                              float* best, int32_t* which, int32_t* flipped, float* pose, float* posed, int steps,
+                              float* refine_ws, float* objective, float* start_best, int32_t* refined,
+                              float* refined_score, void* stream);
+
 /* ---- Pairwise shape Tanimoto ("shape diversity"): every pair of B molecules that already share
  * one frame (posed onto the reference by mcg_shape_overlay), compared as placed, with no orientation search.
  *   coords[B,N,3] with n_nodes_dev[b] real atoms (device memory, clamped to [0, N] on the device), in the reference's

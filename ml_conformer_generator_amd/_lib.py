@@ -55,6 +55,8 @@ SIGNATURES: Dict[str, tuple] = {
     "mcg_shape_frames_tf": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _d, _d, _f, _i, _i, _vp, _vp, _vp, _vp]),
     "mcg_shape_overlay": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp,
                                _vp, _vp]),
+    "mcg_shape_overlay_refined": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcg_shape_pair_tanimoto": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp]),
     "mcg_handoff": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp]),
     "mcg_handoff_ex": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import math
 import numbers
+import operator
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -322,9 +323,23 @@ def shape_scores(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: t
     return best, which
 
 
+MAX_REFINE_STEPS = 1024       # csrc/mcg_shape_refine.hip RF_MAX_STEPS
+
+
+def check_refine_steps(value) -> int:
+    """`refine_steps` as an int in 0..MAX_REFINE_STEPS (an integer type, not a bool), else ValueError."""
+    try:
+        k = None if isinstance(value, bool) else operator.index(value)
+    except TypeError:
+        k = None
+    if k is None or not (0 <= k <= MAX_REFINE_STEPS):
+        raise ValueError(f"refine_steps must be an integer in 0..{MAX_REFINE_STEPS}, got {value!r}")
+    return int(k)
+
+
 @torch.no_grad()
 def shape_overlay(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor, device=None,
-                  with_scores: bool = False) -> Dict[str, torch.Tensor]:
+                  with_scores: bool = False, refine_steps: int = 0) -> Dict[str, torch.Tensor]:
     """Every sample posed onto the reference conformer, in the reference's own coordinates.
     The principal frames of the reference (row 0) and of the samples come from one `mcg_shape_frames_tf` launch; the
     sample frame's handedness is made to match the reference's (so the pose is a rotation, never a mirror), the four
@@ -338,7 +353,23 @@ def shape_overlay(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: 
       (with_scores) scores [B,4]  the four orientations' scores.
     A sample whose frame is not finite (non-finite coordinates, no atoms) keeps its input coordinates and gets a NaN
     rotation, translation and tanimoto and orientation -1; the other samples are unaffected and bit-identical whatever
-    their batch.  Refuses what `shape_scores` refuses."""
+    their batch.  Refuses what `shape_scores` refuses.
+    `refine_steps` >= 1 (`mcg_shape_overlay_refined`, DESIGN.md section 6 "Refined pose"): each of the four starts is
+    then moved as a rigid body to maximise its Gaussian overlap with the reference for that many ascent steps, and the
+    best refined candidate replaces the start pose where its grid Tanimoto is strictly better; the keys above describe
+    the returned pose, and
+      start_tanimoto [B]   the unrefined pose's tanimoto (what refine_steps=0 returns, bit for bit);
+      refined [B] bool     whether the refined pose replaced it;
+      (with_scores) refined_scores [B,4]  the refined candidates' scores; objective [B,4,2]  the Gaussian overlap of
+                           each start before and after its ascent.
+    0 (the default) is the unrefined path, unchanged.  A value outside 0..1024, a bool or a non-integer is refused with
+    ValueError before any device work."""
+    steps = check_refine_steps(refine_steps)
+    return _overlay(reference_coord, coords, n_nodes, device, with_scores, steps, steps > 0)
+
+
+def _overlay(reference_coord, coords, n_nodes, device, with_scores: bool, steps: int, refined_entry: bool):
+    """`shape_overlay` through `mcg_shape_overlay` or (`refined_entry`) `mcg_shape_overlay_refined` with `steps`."""
     dev, ref, x, nn = _shape_inputs(reference_coord, coords, n_nodes, device, with_reference=True)
     B, W = int(coords.shape[0]), int(coords.shape[1])
     if x is None:
@@ -348,6 +379,10 @@ def shape_overlay(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: 
                    flipped=torch.zeros(0, dtype=torch.bool, device=dev))
         if with_scores:
             out["scores"] = torch.zeros(0, 4, device=dev)
+        if refined_entry:
+            out.update(start_tanimoto=torch.zeros(0, device=dev), refined=torch.zeros(0, dtype=torch.bool, device=dev))
+            if with_scores:
+                out.update(refined_scores=torch.zeros(0, 4, device=dev), objective=torch.zeros(0, 4, 2, device=dev))
         return out
     n_ref, N = int(ref.shape[0]), int(x.shape[1])
     xform = torch.empty(B + 1, 12, device=dev)
@@ -362,17 +397,29 @@ def shape_overlay(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: 
     flipped = torch.empty(B, dtype=torch.int32, device=dev)
     pose = torch.empty(B, 12, device=dev)
     posed = torch.empty(B, N, 3, device=dev)
-    _lib.check(_lib.lib().mcg_shape_overlay(_lib.dptr(ref_frame), n_ref, _lib.dptr(xform), _lib.dptr(frames[1:]),
-                                            _lib.dptr(xform[1:]), _lib.dptr(nn[1:]), B, N, _lib.dptr(rots),
-                                            _lib.dptr(axes), 40, float(ALPHA), float(AMPLITUDE), _lib.dptr(f),
-                                            _lib.dptr(scores), _lib.dptr(best), _lib.dptr(which), _lib.dptr(flipped),
-                                            _lib.dptr(pose), _lib.dptr(posed), _lib.current_stream_ptr(dev)),
-               "mcg_shape_overlay")
+    args = (_lib.dptr(ref_frame), n_ref, _lib.dptr(xform), _lib.dptr(frames[1:]), _lib.dptr(xform[1:]), _lib.dptr(nn[1:]),
+            B, N, _lib.dptr(rots), _lib.dptr(axes), 40, float(ALPHA), float(AMPLITUDE), _lib.dptr(f), _lib.dptr(scores),
+            _lib.dptr(best), _lib.dptr(which), _lib.dptr(flipped), _lib.dptr(pose), _lib.dptr(posed))
+    if refined_entry:
+        ws = torch.empty(B, 4, 12, device=dev)
+        objective = torch.empty(B, 4, 2, device=dev) if with_scores else None
+        refined_scores = torch.empty(B, 4, device=dev) if with_scores else None
+        start = torch.empty(B, device=dev)
+        refined = torch.empty(B, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().mcg_shape_overlay_refined(*args, int(steps), _lib.dptr(ws), _lib.dptr(objective),
+                                                        _lib.dptr(start), _lib.dptr(refined), _lib.dptr(refined_scores),
+                                                        _lib.current_stream_ptr(dev)), "mcg_shape_overlay_refined")
+    else:
+        _lib.check(_lib.lib().mcg_shape_overlay(*args, _lib.current_stream_ptr(dev)), "mcg_shape_overlay")
     failed = (which < 0).view(B, 1, 1)
     out = dict(coords=torch.where(failed, x[1:, :W], posed[:, :W]), rotation=pose[:, :9].reshape(B, 3, 3),
                translation=pose[:, 9:], tanimoto=best, orientation=which.long(), flipped=flipped.bool())
     if with_scores:
         out["scores"] = scores
+    if refined_entry:
+        out.update(start_tanimoto=start, refined=refined.bool())
+        if with_scores:
+            out.update(refined_scores=refined_scores, objective=objective)
     return out
 
 

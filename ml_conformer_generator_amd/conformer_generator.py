@@ -42,7 +42,10 @@ forced by the scope of this build:
     by default: nothing changes;
   * `max_pairwise_tanimoto` (opt-in, every generation entry, with `overlay`): a shape-diverse selection by sphere
     exclusion in ranking order on the pairwise shape Tanimoto of the posed molecules
-    (`cheminformatics.pairwise_shape_tanimoto`).  Off by default: nothing changes.
+    (`cheminformatics.pairwise_shape_tanimoto`).  Off by default: nothing changes;
+  * `refine_overlay` (opt-in, every generation entry, with `overlay`): the pose is refined on the GPU by a rigid-body
+    ascent of the Gaussian overlap from each of the four principal-frame starts, kept where its shape Tanimoto is
+    strictly better (`cheminformatics.shape_overlay(refine_steps=...)`).  Off by default: nothing changes.
 """
 from __future__ import annotations
 
@@ -124,6 +127,7 @@ class _ShapeRequest:
     top_k: Optional[int]
     min_shape_tanimoto: Optional[float]
     max_pairwise_tanimoto: Optional[float]
+    refine_steps: int = 0                         # `refine_overlay`: ascent steps of the refined pose, 0 = not refined
 
 
 class MLConformerGenerator(torch.nn.Module):
@@ -327,9 +331,15 @@ class MLConformerGenerator(torch.nn.Module):
 
     def _shape_request(self, reference_conformer, shape_scores: bool, top_k: Optional[int],
                        min_shape_tanimoto: Optional[float], overlay: bool = False,
-                       max_pairwise_tanimoto: Optional[float] = None) -> Optional[_ShapeRequest]:
+                       max_pairwise_tanimoto: Optional[float] = None,
+                       refine_overlay: Union[bool, int] = False) -> Optional[_ShapeRequest]:
         """The call's shape options, or None when it asked for none of them (`top_k` / `min_shape_tanimoto` /
         `max_pairwise_tanimoto` imply scoring).  Every refusal happens here, before any device work."""
+        refine_steps = 0
+        if refine_overlay is not False:
+            refine_steps = self._refine_steps(refine_overlay)
+            if not overlay:
+                raise ValueError("refine_overlay needs overlay=True: it refines the pose onto the reference")
         scoring = shape_scores or top_k is not None or min_shape_tanimoto is not None or max_pairwise_tanimoto is not None
         if not (scoring or overlay):
             return None
@@ -356,7 +366,22 @@ class MLConformerGenerator(torch.nn.Module):
                              "this package can read")
         ref_coord = self._reference_coord(reference_conformer)
         cheminformatics.check_reference_atoms(int(ref_coord.shape[0]))
-        return _ShapeRequest(ref_coord, bool(overlay), bool(scoring), top_k, min_shape_tanimoto, max_pairwise_tanimoto)
+        return _ShapeRequest(ref_coord, bool(overlay), bool(scoring), top_k, min_shape_tanimoto, max_pairwise_tanimoto,
+                             refine_steps)
+
+    @staticmethod
+    def _refine_steps(refine_overlay) -> int:
+        """`refine_overlay` as a step budget: True = 64, an integer 1..1024 = itself; anything else is a ValueError."""
+        if refine_overlay is True:
+            return 64
+        try:
+            k = None if isinstance(refine_overlay, bool) else operator.index(refine_overlay)
+        except TypeError:
+            k = None
+        if k is None or not (1 <= k <= cheminformatics.MAX_REFINE_STEPS):
+            raise ValueError(f"refine_overlay must be True or an integer step budget in 1.."
+                             f"{cheminformatics.MAX_REFINE_STEPS}, got {refine_overlay!r}")
+        return int(k)
 
     # device seams of the shape step (stubbed by the host tests)
     def _score_coords(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
@@ -366,6 +391,17 @@ class MLConformerGenerator(torch.nn.Module):
     def _pose_coords(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor) -> dict:
         """Padded heavy-atom coordinates posed onto the reference (`cheminformatics.shape_overlay`, device tensors)."""
         return cheminformatics.shape_overlay(ref_coord, coords, n_nodes, self.device)
+
+    def _pose_coords_refined(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor,
+                             steps: int) -> dict:
+        """`_pose_coords` with the refined pose (`cheminformatics.shape_overlay(refine_steps=steps)`, device tensors)."""
+        return cheminformatics.shape_overlay(ref_coord, coords, n_nodes, self.device, refine_steps=steps)
+
+    def _overlay_fn(self, req: _ShapeRequest):
+        """The posing seam of the call: `_pose_coords`, or `_pose_coords_refined` when it asked for refinement."""
+        if req.refine_steps > 0:
+            return lambda ref, coords, n: self._pose_coords_refined(ref, coords, n, req.refine_steps)
+        return self._pose_coords
 
     def _pair_coords(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
         """[B,B] pairwise shape Tanimoto (device) of padded heavy-atom coordinates posed onto the reference
@@ -379,7 +415,7 @@ class MLConformerGenerator(torch.nn.Module):
         if req is None:
             return res
         if req.overlay:
-            ov = self._pose_coords(req.ref_coord, res["x"], res["n_nodes"])
+            ov = self._overlay_fn(req)(req.ref_coord, res["x"], res["n_nodes"])
             res = dict(res, x=ov["coords"], overlay_tanimoto=ov["tanimoto"],
                        pose=torch.cat([ov["rotation"].reshape(-1, 9), ov["translation"].reshape(-1, 3)], dim=1))
         if req.scoring:
@@ -402,7 +438,7 @@ class MLConformerGenerator(torch.nn.Module):
         the shape Tanimoto and (overlay_tanimoto, rotation, translation); None where the call did not ask or the Mol
         was dropped."""
         none = [None] * len(done)
-        poses = (cheminformatics.pose_mols(req.ref_coord, done, overlay_fn=self._pose_coords)
+        poses = (cheminformatics.pose_mols(req.ref_coord, done, overlay_fn=self._overlay_fn(req))
                  if req is not None and req.overlay else none)
         scores = self._score_mols(req.ref_coord, done) if req is not None and req.scoring else list(none)
         return scores, poses
@@ -567,7 +603,8 @@ class MLConformerGenerator(torch.nn.Module):
                             inertial_fragment_matching: bool = True, blend_power: int = 3,
                             ifm_diffusion_level: int = 50, sample_seed: Optional[int] = None, shape_scores: bool = False,
                             top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None,
-                            overlay: bool = False, max_pairwise_tanimoto: Optional[float] = None) -> List:
+                            overlay: bool = False, max_pairwise_tanimoto: Optional[float] = None,
+                            refine_overlay: Union[bool, int] = False) -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
@@ -593,13 +630,18 @@ class MLConformerGenerator(torch.nn.Module):
         the molecules are walked in ranking order and one is kept unless its shape Tanimoto, as posed, with an already
         kept molecule is >= the value (`cheminformatics.pairwise_shape_tanimoto` on the GPU, `select_diverse`); then
         `top_k`.
+        `refine_overlay` (needs `overlay=True`): True (64 steps) or a step budget 1..1024.  Each molecule's pose is
+        refined on the GPU: from each of the four principal-frame starts a rigid-body ascent of the Gaussian overlap with
+        the reference, the best refined candidate kept where its shape Tanimoto is strictly better than the start's
+        (`cheminformatics.shape_overlay(refine_steps=...)`).  `pose` and `overlay_tanimoto` describe the returned pose;
+        ranking and selection are unchanged, and the pair matrix of `max_pairwise_tanimoto` reads the refined poses.
         Refused with ValueError before any device work: scoring or posing without a reference conformer, a reference
         outside 3..64 heavy atoms, top_k < 1, a threshold outside [0, 1], max_pairwise_tanimoto outside (0, 1] or without
-        overlay, and a custom finisher."""
+        overlay, refine_overlay other than True or an integer in 1..1024 or without overlay, and a custom finisher."""
         if sample_seed is not None:
             seeding.check_seed(sample_seed)
         req = self._shape_request(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
-                                  max_pairwise_tanimoto)
+                                  max_pairwise_tanimoto, refine_overlay)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
         keyed = () if sample_seed is None else (sample_seed, None)   # unseeded: the positional call of before
         res = self._generate_shard(ref_context, ref_n_atoms, variance, None, n_samples, resample_steps, fixed_fragment,
@@ -618,7 +660,8 @@ class MLConformerGenerator(torch.nn.Module):
                                     gather: str = "all", balance: str = "cost",
                                     sample_seed: Optional[int] = None, shape_scores: bool = False,
                                     top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None,
-                                    overlay: bool = False, max_pairwise_tanimoto: Optional[float] = None) -> List:
+                                    overlay: bool = False, max_pairwise_tanimoto: Optional[float] = None,
+                                    refine_overlay: Union[bool, int] = False) -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -634,7 +677,8 @@ class MLConformerGenerator(torch.nn.Module):
         `sample_seed` (instead of `seed`): the keyed stream of `edm_tensors` - every rank computes the keyed sizes of all
         `n_samples` itself (no broadcast), generates its shard with the shard's global indices as `sample_ids` and seeds
         no generator, so sample i is the same molecule on any world size and under either `balance`.
-        `shape_scores`, `top_k`, `min_shape_tanimoto`, `overlay`, `max_pairwise_tanimoto`: as in `generate_conformers`.
+        `shape_scores`, `top_k`, `min_shape_tanimoto`, `overlay`, `max_pairwise_tanimoto`, `refine_overlay`: as in
+        `generate_conformers`.
         Every rank poses and scores ITS OWN shard on its own GPU before the gather (posed coordinates, poses and scores
         travel as per-sample result tensors, or next to the finished Mols).  The selection runs on the rows a rank
         returns: with gather="all" every rank selects from the whole batch (the pair matrix of the whole batch on its own
@@ -646,7 +690,7 @@ class MLConformerGenerator(torch.nn.Module):
                 raise ValueError("pass either seed (per-rank device generator) or sample_seed (keyed stream), not both")
             seeding.check_seed(sample_seed)
         req = self._shape_request(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
-                                  max_pairwise_tanimoto)
+                                  max_pairwise_tanimoto, refine_overlay)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)
         hi_n = min(ref_n_atoms + variance, self.max_n_nodes)
@@ -701,10 +745,10 @@ class MLConformerGenerator(torch.nn.Module):
                 blend_power: int = 3, ifm_diffusion_level: int = 50, sample_seed: Optional[int] = None,
                 shape_scores: bool = False, top_k: Optional[int] = None,
                 min_shape_tanimoto: Optional[float] = None, overlay: bool = False,
-                max_pairwise_tanimoto: Optional[float] = None) -> List:
+                max_pairwise_tanimoto: Optional[float] = None, refine_overlay: Union[bool, int] = False) -> List:
         return self.generate_conformers(reference_conformer, n_samples, variance, reference_context, n_atoms,
                                         optimise_geometry, resample_steps, fixed_fragment,
                                         inertial_fragment_matching, blend_power, ifm_diffusion_level,
                                         sample_seed=sample_seed, shape_scores=shape_scores, top_k=top_k,
                                         min_shape_tanimoto=min_shape_tanimoto, overlay=overlay,
-                                        max_pairwise_tanimoto=max_pairwise_tanimoto)
+                                        max_pairwise_tanimoto=max_pairwise_tanimoto, refine_overlay=refine_overlay)

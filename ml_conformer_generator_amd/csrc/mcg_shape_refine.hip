@@ -1,0 +1,339 @@
+// Refined pose on the reference ("Refined pose"): `mcg_shape_overlay`'s four principal-frame starts,
+// each moved as a rigid body to maximise its first-order Gaussian overlap with the reference, then scored on the
+// reference's grid; a refined candidate replaces the start pose only where its grid Tanimoto is strictly better.
+//   k_overlay_refine:      one 256-lane workgroup per (candidate, orientation).  The start z_w is rebuilt exactly as
+//                          `k_shape_overlay` builds it; the reference y and the start sit in LDS.  Objective
+//                          O(y, z) = sum_ij A^2 (pi / 2 alpha)^1.5 exp(-(alpha / 2) |y_i - z_j|^2), rigid motion
+//                          z' = (z - c) @ G + p (c the start's atom centroid, p where it is now).  Every step takes a
+//                          normalised-gradient move (angle s_r about the torque, length s_t along the force), keeps it
+//                          only if O strictly increases (then both lengths x 1.2; else both x 0.5), for `steps` steps.
+//                          Lane l owns the pairs q = l + 256 k of q = i * n + j; the seven sums (O, force, torque) are
+//                          reduced by a fixed butterfly per wave and the tree (w0 + w1) + (w2 + w3), read by every lane,
+//                          so every lane holds the same state and takes the same branch.  No atomics.
+//   k_overlay_refine_pick: one 256-lane workgroup per candidate.  The four refined candidates z_w @ G_w + t_w are scored
+//                          with `k_shape_overlay`'s grid walk, lane assignment and reduction tree, so a candidate with
+//                          G = I, t = 0 scores the bits its start scored.  The first maximum replaces the start only if
+//                          strictly better; the pose is then Q = M_s' R_w G M_r^T, d = t_r + t_w @ M_r^T - t_s @ Q.
+// Everything depends on the candidate's own atoms and the reference only: bit-identical whatever the batch, row or width.
+#include "mcg_common.h"
+#include "mcg_api_internal.h"
+#include "mcg_shape_grid.h"
+
+#include <math.h>
+
+#pragma clang fp contract(off)      // every product and sum rounded on its own: the compiler has no choice left
+
+namespace {
+
+using mcg_shape::MAX_ATOMS;
+using mcg_shape::density_at;
+using mcg_shape::rotate_row;
+
+constexpr int RF_THREADS = 256;
+constexpr int RF_WAVES = RF_THREADS / 64;
+constexpr int RF_MAX_STEPS = 1024;
+constexpr float RF_STEP_ROT = 0.2f;       // initial rotation step, rad
+constexpr float RF_STEP_TRANS = 0.5f;     // initial translation step, Angstrom
+constexpr float RF_GROW = 1.2f, RF_SHRINK = 0.5f;
+
+// ws per (candidate, orientation): G row-major [9], then t [3] with z' = z @ G + t
+constexpr int RF_WS = 12;
+
+// c = a @ b (row-major 3x3)
+__device__ __forceinline__ void mat3_mul(const float* a, const float* b, float* c) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            c[i * 3 + j] = __builtin_fmaf(a[i * 3 + 2], b[6 + j], __builtin_fmaf(a[i * 3], b[j], a[i * 3 + 1] * b[3 + j]));
+}
+
+// Row-vector form (r' = r @ D) of the rotation by theta about the unit axis n: D = R^T with Rodrigues'
+// R = I + sin(theta) K + (1 - cos(theta)) K^2, K v = n x v.
+__device__ __forceinline__ void rodrigues_row(float nx, float ny, float nz, float theta, float* D) {
+    const float s = sinf(theta), c1 = 1.f - cosf(theta);
+    const float K[9] = {0.f, -nz, ny, nz, 0.f, -nx, -ny, nx, 0.f};
+    const float K2[9] = {-(ny * ny + nz * nz), nx * ny, nx * nz, nx * ny, -(nx * nx + nz * nz), ny * nz,
+                         nx * nz, ny * nz, -(nx * nx + ny * ny)};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            D[j * 3 + i] = ((i == j ? 1.f : 0.f) + s * K[i * 3 + j]) + c1 * K2[i * 3 + j];
+}
+
+// Rows of G made orthonormal (Gram-Schmidt, third row = first x second: det +1).  The identity stays exactly the identity.
+__device__ __forceinline__ void orthonormalise(float* G) {
+    float a[3] = {G[0], G[1], G[2]}, b[3] = {G[3], G[4], G[5]};
+    const float na = sqrtf((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
+    for (int k = 0; k < 3; ++k) a[k] = a[k] / na;
+    const float ab = (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
+    for (int k = 0; k < 3; ++k) b[k] = b[k] - ab * a[k];
+    const float nb = sqrtf((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2]);
+    for (int k = 0; k < 3; ++k) b[k] = b[k] / nb;
+    G[0] = a[0]; G[1] = a[1]; G[2] = a[2];
+    G[3] = b[0]; G[4] = b[1]; G[5] = b[2];
+    G[6] = a[1] * b[2] - a[2] * b[1];
+    G[7] = a[2] * b[0] - a[0] * b[2];
+    G[8] = a[0] * b[1] - a[1] * b[0];
+}
+
+struct RefineShared {
+    float y[MAX_ATOMS][3];        // the reference frame
+    float r[MAX_ATOMS][3];        // the start minus its atom centroid
+    float rr[MAX_ATOMS][3];       // r @ G of the pose being evaluated
+    float red[RF_WAVES][7];
+    float c[3];
+};
+
+// O / force / torque sums of the pose (G, p) into v[7]: sum e, sum e d, sum e (rr x (y - p)), d = y - p - rr; identical
+// in every lane.
+__device__ void evaluate(RefineShared& s, int n_ref, int na, const float* G, const float* p, float half_alpha, float* v) {
+    const int tid = threadIdx.x;
+    if (tid < na) rotate_row(s.r[tid][0], s.r[tid][1], s.r[tid][2], G, s.rr[tid]);
+    __syncthreads();
+    float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const int total = n_ref * na;
+    for (int q = tid; q < total; q += RF_THREADS) {
+        const int i = q / na, j = q - i * na;
+        const float yx = s.y[i][0] - p[0], yy = s.y[i][1] - p[1], yz = s.y[i][2] - p[2];
+        const float rx = s.rr[j][0], ry = s.rr[j][1], rz = s.rr[j][2];
+        const float dx = yx - rx, dy = yy - ry, dz = yz - rz;
+        const float d2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+        const float e = __expf(-half_alpha * d2);
+        acc[0] += e;
+        acc[1] = __builtin_fmaf(e, dx, acc[1]);
+        acc[2] = __builtin_fmaf(e, dy, acc[2]);
+        acc[3] = __builtin_fmaf(e, dz, acc[3]);
+        acc[4] = __builtin_fmaf(e, ry * yz - rz * yy, acc[4]);
+        acc[5] = __builtin_fmaf(e, rz * yx - rx * yz, acc[5]);
+        acc[6] = __builtin_fmaf(e, rx * yy - ry * yx, acc[6]);
+    }
+#pragma unroll
+    for (int k = 0; k < 7; ++k)
+        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) s.red[tid >> 6][k] = acc[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 7; ++k) v[k] = (s.red[0][k] + s.red[1][k]) + (s.red[2][k] + s.red[3][k]);
+}
+
+__global__ __launch_bounds__(RF_THREADS) void k_overlay_refine(const float* __restrict__ ref_frame, int n_ref,
+                                                               const float* __restrict__ frames,
+                                                               const int* __restrict__ n_nodes, int N,
+                                                               const float* __restrict__ rot /*[4][9]*/,
+                                                               const int* __restrict__ flipped,
+                                                               const int* __restrict__ which, int steps,
+                                                               float half_alpha, float pref, float* __restrict__ ws,
+                                                               float* __restrict__ objective) {
+    __shared__ RefineShared s;
+    const int b = blockIdx.x >> 2, w = blockIdx.x & 3, tid = threadIdx.x;
+    float* out = ws + (size_t)blockIdx.x * RF_WS;
+    if (which[b] < 0) {                       // failed in k_shape_overlay: the pick leaves the row alone
+        if (tid < RF_WS) out[tid] = __builtin_nanf("");
+        if (objective != nullptr && tid < 2) objective[(size_t)blockIdx.x * 2 + tid] = __builtin_nanf("");
+        return;
+    }
+    const int na = min(max(n_nodes[b], 0), min(N, MAX_ATOMS));
+    const bool flip = flipped[b] != 0;
+    for (int i = tid; i < n_ref * 3; i += RF_THREADS) s.y[i / 3][i % 3] = ref_frame[i];
+    if (tid < na) {                           // z_w as k_shape_overlay builds it
+        const float* x = frames + ((size_t)b * N + tid) * 3;
+        rotate_row(x[0], x[1], flip ? -x[2] : x[2], rot + w * 9, s.r[tid]);
+    }
+    __syncthreads();
+    if (tid < 3) {                            // atom centroid, summed in atom order
+        float acc = 0.f;
+        for (int i = 0; i < na; ++i) acc += s.r[i][tid];
+        s.c[tid] = acc / (float)max(na, 1);
+    }
+    __syncthreads();
+    const float c[3] = {s.c[0], s.c[1], s.c[2]};
+    __syncthreads();
+    if (tid < na) {
+        for (int k = 0; k < 3; ++k) s.r[tid][k] = s.r[tid][k] - c[k];
+    }
+    float G[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, p[3] = {c[0], c[1], c[2]};
+    float cur[7];
+    evaluate(s, n_ref, na, G, p, half_alpha, cur);
+    const float o_start = cur[0];
+    float sr = RF_STEP_ROT, st = RF_STEP_TRANS;
+    for (int it = 0; it < steps; ++it) {
+        float Gn[9], pn[3];
+        const float fn = sqrtf((cur[1] * cur[1] + cur[2] * cur[2]) + cur[3] * cur[3]);
+        const float tn = sqrtf((cur[4] * cur[4] + cur[5] * cur[5]) + cur[6] * cur[6]);
+        if (tn > 0.f) {
+            float D[9];
+            rodrigues_row(cur[4] / tn, cur[5] / tn, cur[6] / tn, sr, D);
+            mat3_mul(G, D, Gn);
+        } else {
+            for (int k = 0; k < 9; ++k) Gn[k] = G[k];
+        }
+        for (int k = 0; k < 3; ++k) pn[k] = fn > 0.f ? p[k] + st * (cur[1 + k] / fn) : p[k];
+        float nxt[7];
+        evaluate(s, n_ref, na, Gn, pn, half_alpha, nxt);
+        if (nxt[0] > cur[0]) {
+            for (int k = 0; k < 9; ++k) G[k] = Gn[k];
+            for (int k = 0; k < 3; ++k) p[k] = pn[k];
+            for (int k = 0; k < 7; ++k) cur[k] = nxt[k];
+            sr *= RF_GROW; st *= RF_GROW;
+        } else {
+            sr *= RF_SHRINK; st *= RF_SHRINK;
+        }
+    }
+    orthonormalise(G);
+    if (tid == 0) {                           // z' = (z - c) @ G + p = z @ G + (p - c @ G)
+        float cg[3];
+        rotate_row(c[0], c[1], c[2], G, cg);
+        for (int k = 0; k < 9; ++k) out[k] = G[k];
+        for (int k = 0; k < 3; ++k) out[9 + k] = p[k] - cg[k];
+        if (objective != nullptr) {
+            objective[(size_t)blockIdx.x * 2] = pref * o_start;
+            objective[(size_t)blockIdx.x * 2 + 1] = pref * cur[0];
+        }
+    }
+}
+
+// xform = M row-major [9], then t [3]: frames = (coords - t) @ M on the real rows (mcg_shape_frames_tf).
+__global__ __launch_bounds__(RF_THREADS) void k_overlay_refine_pick(
+    const float* __restrict__ f, const float* __restrict__ ref_xform, const float* __restrict__ frames,
+    const float* __restrict__ xform, const int* __restrict__ n_nodes, int N, const float* __restrict__ rot /*[4][9]*/,
+    const float* __restrict__ axes, int n, float alpha, float amp, const float* __restrict__ ws,
+    const int* __restrict__ flipped, int* __restrict__ which, float* __restrict__ best, float* __restrict__ pose,
+    float* __restrict__ posed, float* __restrict__ start_best, int* __restrict__ refined,
+    float* __restrict__ refined_score) {
+    __shared__ float c[4][MAX_ATOMS][3];      // the four refined candidates
+    __shared__ float red[9][4];               // per wave: fg[4], gg[4], ff
+    __shared__ float sc[4];
+    __shared__ float zr[12];                  // M_r row-major, then t_r
+    __shared__ int s_pick;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (which[b] < 0) {                       // failed in k_shape_overlay: left exactly as it was
+        if (tid == 0) { start_best[b] = best[b]; refined[b] = 0; }
+        if (refined_score != nullptr && tid < 4) refined_score[b * 4 + tid] = __builtin_nanf("");
+        return;
+    }
+    const int na = min(max(n_nodes[b], 0), min(N, MAX_ATOMS));
+    const bool flip = flipped[b] != 0;
+    if (tid < 12) zr[tid] = ref_xform[tid];
+    for (int i = tid; i < na; i += RF_THREADS) {
+        const float* x = frames + ((size_t)b * N + i) * 3;
+        const float x0 = x[0], x1 = x[1], x2 = flip ? -x[2] : x[2];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const float* gt = ws + ((size_t)b * 4 + w) * RF_WS;
+            float z[3], g[3];
+            rotate_row(x0, x1, x2, rot + w * 9, z);
+            rotate_row(z[0], z[1], z[2], gt, g);
+            c[w][i][0] = g[0] + gt[9]; c[w][i][1] = g[1] + gt[10]; c[w][i][2] = g[2] + gt[11];
+        }
+    }
+    __syncthreads();
+    const int total = n * n * n;              // k_shape_overlay's walk, lane assignment and tree
+    float fg[4] = {0.f, 0.f, 0.f, 0.f}, gg[4] = {0.f, 0.f, 0.f, 0.f}, ff = 0.f;
+    for (int idx = tid; idx < total; idx += RF_THREADS) {
+        const int ix = idx / (n * n), iy = (idx / n) % n, iz = idx % n;
+        const float px = axes[ix], py = axes[n + iy], pz = axes[2 * n + iz];
+        const float fv = f[idx];
+        ff = fmaf(fv, fv, ff);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const float g = density_at(px, py, pz, c[w], na, alpha, amp);
+            fg[w] = fmaf(fv, g, fg[w]); gg[w] = fmaf(g, g, gg[w]);
+        }
+    }
+    float v[9] = {fg[0], fg[1], fg[2], fg[3], gg[0], gg[1], gg[2], gg[3], ff};
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
+    const int wid = tid >> 6;
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) red[k][wid] = v[k];
+    }
+    __syncthreads();
+    if (tid < 4) {
+        const float sfg = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+        const float sff = (red[8][0] + red[8][1]) + (red[8][2] + red[8][3]);
+        const float sgg = (red[4 + tid][0] + red[4 + tid][1]) + (red[4 + tid][2] + red[4 + tid][3]);
+        sc[tid] = sfg / (sff + sgg - sfg);
+        if (refined_score != nullptr) refined_score[b * 4 + tid] = sc[tid];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int wb = 0;
+        float sb = sc[0];
+        for (int w = 1; w < 4; ++w)
+            if (sc[w] > sb) { sb = sc[w]; wb = w; }                 // the first maximum
+        const float start = best[b];
+        const bool take = sb > start;                               // strictly better (NaN never is)
+        start_best[b] = start;
+        refined[b] = take ? 1 : 0;
+        if (take) {
+            const float* xs = xform + (size_t)b * 12;
+            const float* gt = ws + ((size_t)b * 4 + wb) * RF_WS;
+            const float* R = rot + wb * 9;
+            float A[9], RG[9], Q[9], d[3];
+            for (int i = 0; i < 3; ++i)                             // A = M_s' (diag(1, 1, -1) on the flipped rows)
+                for (int k = 0; k < 3; ++k) A[i * 3 + k] = k == 2 && flip ? -xs[i * 3 + k] : xs[i * 3 + k];
+            mat3_mul(R, gt, RG);
+            float ARG[9];
+            mat3_mul(A, RG, ARG);
+            for (int i = 0; i < 3; ++i)                             // Q = A R G M_r^T
+                for (int j = 0; j < 3; ++j)
+                    Q[i * 3 + j] = __builtin_fmaf(ARG[i * 3 + 2], zr[j * 3 + 2],
+                                                  __builtin_fmaf(ARG[i * 3], zr[j * 3], ARG[i * 3 + 1] * zr[j * 3 + 1]));
+            for (int j = 0; j < 3; ++j) {                           // d = t_r + t_w @ M_r^T - t_s @ Q
+                const float tw = __builtin_fmaf(gt[11], zr[j * 3 + 2], __builtin_fmaf(gt[9], zr[j * 3], gt[10] * zr[j * 3 + 1]));
+                const float ts = __builtin_fmaf(xs[11], Q[6 + j], __builtin_fmaf(xs[9], Q[j], xs[10] * Q[3 + j]));
+                d[j] = (zr[9 + j] + tw) - ts;
+            }
+            best[b] = sb;
+            which[b] = wb;
+            for (int k = 0; k < 9; ++k) pose[(size_t)b * 12 + k] = Q[k];
+            for (int k = 0; k < 3; ++k) pose[(size_t)b * 12 + 9 + k] = d[k];
+        }
+        s_pick = take ? wb : -1;
+    }
+    __syncthreads();
+    const int wb = s_pick;
+    if (wb < 0) return;
+    for (int i = tid; i < na; i += RF_THREADS) {   // x_out = z' @ M_r^T + t_r; padded rows stay zero
+        float* out = posed + ((size_t)b * N + i) * 3;
+        const float* z = c[wb][i];
+        for (int k = 0; k < 3; ++k) out[k] = ((z[0] * zr[k * 3] + z[1] * zr[k * 3 + 1]) + z[2] * zr[k * 3 + 2]) + zr[9 + k];
+    }
+}
+
+}  // namespace
+
+extern "C" int mcg_shape_overlay_refined(const float* ref_frame, int n_ref, const float* ref_xform, const float* frames,
+                                         const float* xform, const int32_t* n_nodes_dev, int B, int N, const float* rot,
+                                         const float* axes, int n, float alpha, float amplitude, float* f_scratch,
+                                         float* score, float* best, int32_t* which, int32_t* flipped, float* pose,
+                                         float* posed, int steps, float* refine_ws, float* objective, float* start_best,
+                                         int32_t* refined, float* refined_score, void* stream) {
+    if (!ref_frame || !ref_xform || !frames || !xform || !n_nodes_dev || !rot || !axes || !f_scratch || !best || !which ||
+        !flipped || !pose || !posed || !refine_ws || !start_best || !refined || B < 1 || N < 1 || N > MAX_ATOMS ||
+        n_ref < 3 || n_ref > MAX_ATOMS || n < 2 || steps < 0 || steps > RF_MAX_STEPS || !(alpha > 0.f)) {
+        mcg_set_error("mcg_shape_overlay_refined: bad arguments (non-null buffers, B >= 1, 1 <= N <= %d, "
+                      "3 <= n_ref <= %d, n >= 2, 0 <= steps <= %d, alpha > 0)", MAX_ATOMS, MAX_ATOMS, RF_MAX_STEPS);
+        return MCG_ERR_ARG;
+    }
+    if (int rc = mcg_shape_overlay(ref_frame, n_ref, ref_xform, frames, xform, n_nodes_dev, B, N, rot, axes, n, alpha,
+                                   amplitude, f_scratch, score, best, which, flipped, pose, posed, stream))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const double a = (double)alpha, amp = (double)amplitude;
+    const float pref = (float)(amp * amp * pow(M_PI / (2.0 * a), 1.5));
+    hipLaunchKernelGGL(k_overlay_refine, dim3(B * 4), dim3(RF_THREADS), 0, s, ref_frame, n_ref, frames, n_nodes_dev, N, rot,
+                       flipped, which, steps, (float)(0.5 * a), pref, refine_ws, objective);
+    hipLaunchKernelGGL(k_overlay_refine_pick, dim3(B), dim3(RF_THREADS), 0, s, f_scratch, ref_xform, frames, xform,
+                       n_nodes_dev, N, rot, axes, n, alpha, amplitude, refine_ws, flipped, which, best, pose, posed,
+                       start_best, refined, refined_score);
+    MCG_HIP(hipGetLastError());
+    return MCG_OK;
+}
