@@ -372,18 +372,14 @@ def _overlay(reference_coord, coords, n_nodes, device, with_scores: bool, steps:
     """`shape_overlay` through `mcg_shape_overlay` or (`refined_entry`) `mcg_shape_overlay_refined` with `steps`."""
     dev, ref, x, nn = _shape_inputs(reference_coord, coords, n_nodes, device, with_reference=True)
     B, W = int(coords.shape[0]), int(coords.shape[1])
+    f32 = torch.float32
+    keys = (("coords", (W, 3), f32, True), ("rotation", (3, 3), f32, True), ("translation", (3,), f32, True),
+            ("tanimoto", (), f32, True), ("orientation", (), torch.long, True), ("flipped", (), torch.bool, True),
+            ("scores", (4,), f32, with_scores), ("start_tanimoto", (), f32, refined_entry),
+            ("refined", (), torch.bool, refined_entry), ("refined_scores", (4,), f32, refined_entry and with_scores),
+            ("objective", (4, 2), f32, refined_entry and with_scores))          # (key, per-row shape, dtype, returned)
     if x is None:
-        out = dict(coords=torch.zeros(0, W, 3, device=dev), rotation=torch.zeros(0, 3, 3, device=dev),
-                   translation=torch.zeros(0, 3, device=dev), tanimoto=torch.zeros(0, device=dev),
-                   orientation=torch.zeros(0, dtype=torch.long, device=dev),
-                   flipped=torch.zeros(0, dtype=torch.bool, device=dev))
-        if with_scores:
-            out["scores"] = torch.zeros(0, 4, device=dev)
-        if refined_entry:
-            out.update(start_tanimoto=torch.zeros(0, device=dev), refined=torch.zeros(0, dtype=torch.bool, device=dev))
-            if with_scores:
-                out.update(refined_scores=torch.zeros(0, 4, device=dev), objective=torch.zeros(0, 4, 2, device=dev))
-        return out
+        return {k: torch.zeros(0, *shape, dtype=dtype, device=dev) for k, shape, dtype, on in keys if on}
     n_ref, N = int(ref.shape[0]), int(x.shape[1])
     xform = torch.empty(B + 1, 12, device=dev)
     _, frames = shape_frames_hip(x, nn, dev, centre_atoms=True, xform_out=xform)
@@ -400,27 +396,23 @@ def _overlay(reference_coord, coords, n_nodes, device, with_scores: bool, steps:
     args = (_lib.dptr(ref_frame), n_ref, _lib.dptr(xform), _lib.dptr(frames[1:]), _lib.dptr(xform[1:]), _lib.dptr(nn[1:]),
             B, N, _lib.dptr(rots), _lib.dptr(axes), 40, float(ALPHA), float(AMPLITUDE), _lib.dptr(f), _lib.dptr(scores),
             _lib.dptr(best), _lib.dptr(which), _lib.dptr(flipped), _lib.dptr(pose), _lib.dptr(posed))
+    out = dict(scores=scores)
     if refined_entry:
         ws = torch.empty(B, 4, 12, device=dev)
-        objective = torch.empty(B, 4, 2, device=dev) if with_scores else None
-        refined_scores = torch.empty(B, 4, device=dev) if with_scores else None
-        start = torch.empty(B, device=dev)
-        refined = torch.empty(B, dtype=torch.int32, device=dev)
-        _lib.check(_lib.lib().mcg_shape_overlay_refined(*args, int(steps), _lib.dptr(ws), _lib.dptr(objective),
-                                                        _lib.dptr(start), _lib.dptr(refined), _lib.dptr(refined_scores),
-                                                        _lib.current_stream_ptr(dev)), "mcg_shape_overlay_refined")
+        out.update(objective=torch.empty(B, 4, 2, device=dev) if with_scores else None,
+                   refined_scores=torch.empty(B, 4, device=dev) if with_scores else None,
+                   start_tanimoto=torch.empty(B, device=dev), refined=torch.empty(B, dtype=torch.int32, device=dev))
+        _lib.check(_lib.lib().mcg_shape_overlay_refined(*args, int(steps), _lib.dptr(ws), _lib.dptr(out["objective"]),
+                                                        _lib.dptr(out["start_tanimoto"]), _lib.dptr(out["refined"]),
+                                                        _lib.dptr(out["refined_scores"]), _lib.current_stream_ptr(dev)),
+                   "mcg_shape_overlay_refined")
+        out["refined"] = out["refined"].bool()
     else:
         _lib.check(_lib.lib().mcg_shape_overlay(*args, _lib.current_stream_ptr(dev)), "mcg_shape_overlay")
     failed = (which < 0).view(B, 1, 1)
-    out = dict(coords=torch.where(failed, x[1:, :W], posed[:, :W]), rotation=pose[:, :9].reshape(B, 3, 3),
+    out.update(coords=torch.where(failed, x[1:, :W], posed[:, :W]), rotation=pose[:, :9].reshape(B, 3, 3),
                translation=pose[:, 9:], tanimoto=best, orientation=which.long(), flipped=flipped.bool())
-    if with_scores:
-        out["scores"] = scores
-    if refined_entry:
-        out.update(start_tanimoto=start, refined=refined.bool())
-        if with_scores:
-            out.update(refined_scores=refined_scores, objective=objective)
-    return out
+    return {k: out[k] for k, _, _, on in keys if on}
 
 
 def pose_mols(reference_coord: torch.Tensor, mols: List, device=None, overlay_fn=None) -> List:

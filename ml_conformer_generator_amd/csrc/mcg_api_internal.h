@@ -9,3 +9,11 @@ const int* mcg_plan_n_nodes(const mcg_plan* p);   // device pointer
 // "everything enqueued on this plan so far" -> the plan's completion event, recorded on the caller's stream
 // (mcg_plan_destroy waits for it before the plan's blocks return to the pool)
 void mcg_plan_mark_done(const mcg_plan* p, void* stream);
+
+// mcg_shape_overlay behind both overlay entries (mcg_shape.hip): checks its arguments and the calling entry's own
+// conditions `more_ok` (the message names `who` and ends with `more`), then launches k_shape_density and k_shape_overlay.
+int mcg_shape_overlay_launch(const char* who, bool more_ok, const char* more, const float* ref_frame, int n_ref,
+                             const float* ref_xform, const float* frames, const float* xform, const int32_t* n_nodes_dev,
+                             int B, int N, const float* rot, const float* axes, int n, float alpha, float amplitude,
+                             float* f_scratch, float* score, float* best, int32_t* which, int32_t* flipped, float* pose,
+                             float* posed, void* stream);

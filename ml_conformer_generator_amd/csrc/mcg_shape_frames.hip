@@ -20,6 +20,7 @@
 //                    centre, so that frames = (coords - t) @ M on the real rows.
 #include "mcg_common.h"
 #include "mcg_api_internal.h"
+#include "mcg_shape_grid.h"
 
 #include <math.h>
 
@@ -27,9 +28,11 @@
 
 namespace {
 
-constexpr int SF_MAX_ATOMS = 64;
+using mcg_shape::MAX_ATOMS;
+static_assert(MAX_ATOMS <= 64, "one 64-bit neighbour mask per atom");
+
 constexpr int SF_MAX_TERMS = 8;
-constexpr int SF_MAX_EDGES = SF_MAX_ATOMS * (SF_MAX_ATOMS - 1) / 2;
+constexpr int SF_MAX_EDGES = MAX_ATOMS * (MAX_ATOMS - 1) / 2;
 constexpr int SF_THREADS = 1024;
 constexpr int SF_WAVES = SF_THREADS / 64;
 
@@ -47,12 +50,12 @@ struct ShapeTerms {
 };
 
 struct Shared {
-    float px[SF_MAX_ATOMS], py[SF_MAX_ATOMS], pz[SF_MAX_ATOMS], pq[SF_MAX_ATOMS];   // points of the pass, |p|^2
-    unsigned long long nbr[SF_MAX_ATOMS];
+    float px[MAX_ATOMS], py[MAX_ATOMS], pz[MAX_ATOMS], pq[MAX_ATOMS];   // points of the pass, |p|^2
+    unsigned long long nbr[MAX_ATOMS];
     unsigned long long cand[SF_MAX_EDGES];       // per edge (i, j): neighbours of both above j
     unsigned int tri_start[SF_MAX_EDGES + 1];    // exclusive prefix of popcount(cand)
     unsigned short edge[SF_MAX_EDGES];           // i | j << 8
-    int row_start[SF_MAX_ATOMS + 1];
+    int row_start[MAX_ATOMS + 1];
     double red[SF_WAVES][6];
     unsigned long long cred[SF_WAVES][SF_MAX_TERMS - 1];
     double sums[6];
@@ -191,7 +194,7 @@ __device__ int load_and_build(Shared& s, const float* __restrict__ coords, const
         if (tid < n) { s.px[tid] -= mean[0]; s.py[tid] -= mean[1]; s.pz[tid] -= mean[2]; }
         __syncthreads();
     }
-    if (tid < SF_MAX_ATOMS) {
+    if (tid < MAX_ATOMS) {
         unsigned long long m = 0;
         if (tid < n) {
             for (int j = 0; j < n; ++j) {
@@ -206,8 +209,8 @@ __device__ int load_and_build(Shared& s, const float* __restrict__ coords, const
     __syncthreads();
     if (tid == 0) {
         int acc = 0;
-        for (int i = 0; i < SF_MAX_ATOMS; ++i) { s.row_start[i] = acc; acc += __popcll(s.nbr[i] & above(i)); }
-        s.row_start[SF_MAX_ATOMS] = acc;
+        for (int i = 0; i < MAX_ATOMS; ++i) { s.row_start[i] = acc; acc += __popcll(s.nbr[i] & above(i)); }
+        s.row_start[MAX_ATOMS] = acc;
         s.n_edges = acc;
     }
     __syncthreads();
@@ -364,8 +367,8 @@ int launch_frames(const float* coords, const int32_t* n_nodes_dev, int B, int N,
 extern "C" int mcg_shape_moments(const float* coords, const int32_t* n_nodes_dev, int B, int N, double alpha,
                                  double amplitude, float neighbour_threshold, int n_terms, int centre_atoms, float* centre,
                                  float* tensor, double* volume, int64_t* clique_counts, void* stream) {
-    if (!coords || !n_nodes_dev || !centre || !tensor || !volume || B < 1 || N < 1 || N > SF_MAX_ATOMS) {
-        mcg_set_error("mcg_shape_moments: bad arguments (non-null buffers, B >= 1, 1 <= N <= %d)", SF_MAX_ATOMS);
+    if (!coords || !n_nodes_dev || !centre || !tensor || !volume || B < 1 || N < 1 || N > MAX_ATOMS) {
+        mcg_set_error("mcg_shape_moments: bad arguments (non-null buffers, B >= 1, 1 <= N <= %d)", MAX_ATOMS);
         return MCG_ERR_ARG;
     }
     ShapeTerms T;
@@ -381,8 +384,8 @@ extern "C" int mcg_shape_frames(const float* coords, const int32_t* n_nodes_dev,
                                 float neighbour_threshold, int n_terms, int centre_atoms, float* moments, float* frames,
                                 void* stream) {
     if (!coords || !n_nodes_dev || !centre || !eigvecs || !volume || !moments || !frames || B < 1 || N < 1 ||
-        N > SF_MAX_ATOMS) {
-        mcg_set_error("mcg_shape_frames: bad arguments (non-null buffers, B >= 1, 1 <= N <= %d)", SF_MAX_ATOMS);
+        N > MAX_ATOMS) {
+        mcg_set_error("mcg_shape_frames: bad arguments (non-null buffers, B >= 1, 1 <= N <= %d)", MAX_ATOMS);
         return MCG_ERR_ARG;
     }
     return launch_frames(coords, n_nodes_dev, B, N, centre, eigvecs, volume, alpha, amplitude, neighbour_threshold, n_terms,
@@ -394,8 +397,8 @@ extern "C" int mcg_shape_frames_tf(const float* coords, const int32_t* n_nodes_d
                                    float neighbour_threshold, int n_terms, int centre_atoms, float* moments, float* frames,
                                    float* xform, void* stream) {
     if (!coords || !n_nodes_dev || !centre || !eigvecs || !volume || !moments || !frames || !xform || B < 1 || N < 1 ||
-        N > SF_MAX_ATOMS) {
-        mcg_set_error("mcg_shape_frames_tf: bad arguments (non-null buffers, B >= 1, 1 <= N <= %d)", SF_MAX_ATOMS);
+        N > MAX_ATOMS) {
+        mcg_set_error("mcg_shape_frames_tf: bad arguments (non-null buffers, B >= 1, 1 <= N <= %d)", MAX_ATOMS);
         return MCG_ERR_ARG;
     }
     return launch_frames(coords, n_nodes_dev, B, N, centre, eigvecs, volume, alpha, amplitude, neighbour_threshold, n_terms,

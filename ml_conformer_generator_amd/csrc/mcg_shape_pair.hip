@@ -21,7 +21,9 @@
 namespace {
 
 using mcg_shape::MAX_ATOMS;
+using mcg_shape::atom_count;
 using mcg_shape::density_at;
+using mcg_shape::grid_point;
 using mcg_shape::rotate_row;
 
 constexpr int PAIR_KSPLIT = 4;                                   // k ranges = waves per Gram workgroup
@@ -37,7 +39,7 @@ __global__ __launch_bounds__(256) void k_pair_density(const float* __restrict__ 
     __shared__ float c[MAX_ATOMS][3];
     __shared__ float m[12];
     const int b = blockIdx.y, tid = threadIdx.x;
-    const int na = min(max(n_nodes[b], 0), min(N, MAX_ATOMS));
+    const int na = atom_count(n_nodes[b], N);
     if (tid < 12) m[tid] = ref_xform[tid];
     __syncthreads();
     bool bad = false;
@@ -54,8 +56,8 @@ __global__ __launch_bounds__(256) void k_pair_density(const float* __restrict__ 
     for (int idx = blockIdx.x * DENS_POINTS + tid; idx < end; idx += 256) {
         float v = 0.f;
         if (idx < total) {
-            const int ix = idx / (n * n), iy = (idx / n) % n, iz = idx % n;   // meshgrid(indexing="ij") flatten order
-            v = row_bad ? __builtin_nanf("") : density_at(axes[ix], axes[n + iy], axes[2 * n + iz], c, na, alpha, amp);
+            const float3 p = grid_point(axes, n, idx);
+            v = row_bad ? __builtin_nanf("") : density_at(p.x, p.y, p.z, c, na, alpha, amp);
         }
         out[idx] = v;
     }

@@ -1,8 +1,8 @@
 // Refined pose on the reference ("Refined pose"): `mcg_shape_overlay`'s four principal-frame starts,
 // each moved as a rigid body to maximise its first-order Gaussian overlap with the reference, then scored on the
 // reference's grid; a refined candidate replaces the start pose only where its grid Tanimoto is strictly better.
-//   k_overlay_refine:      one 256-lane workgroup per (candidate, orientation).  The start z_w is rebuilt exactly as
-//                          `k_shape_overlay` builds it; the reference y and the start sit in LDS.  Objective
+//   k_overlay_refine:      one 256-lane workgroup per (candidate, orientation).  The start z_w is `mcg_shape::frame_start`,
+//                          as `k_shape_overlay` builds it; the reference y and the start sit in LDS.  Objective
 //                          O(y, z) = sum_ij A^2 (pi / 2 alpha)^1.5 exp(-(alpha / 2) |y_i - z_j|^2), rigid motion
 //                          z' = (z - c) @ G + p (c the start's atom centroid, p where it is now).  Every step takes a
 //                          normalised-gradient move (angle s_r about the torque, length s_t along the force), keeps it
@@ -11,7 +11,7 @@
 //                          reduced by a fixed butterfly per wave and the tree (w0 + w1) + (w2 + w3), read by every lane,
 //                          so every lane holds the same state and takes the same branch.  No atomics.
 //   k_overlay_refine_pick: one 256-lane workgroup per candidate.  The four refined candidates z_w @ G_w + t_w are scored
-//                          with `k_shape_overlay`'s grid walk, lane assignment and reduction tree, so a candidate with
+//                          by `mcg_shape::overlap_scores<4>`, as `k_shape_overlay` scores the starts, so a candidate with
 //                          G = I, t = 0 scores the bits its start scored.  The first maximum replaces the start only if
 //                          strictly better; the pose is then Q = M_s' R_w G M_r^T, d = t_r + t_w @ M_r^T - t_s @ Q.
 // Everything depends on the candidate's own atoms and the reference only: bit-identical whatever the batch, row or width.
@@ -25,11 +25,9 @@
 
 namespace {
 
-using mcg_shape::MAX_ATOMS;
-using mcg_shape::density_at;
-using mcg_shape::rotate_row;
+using namespace mcg_shape;
 
-constexpr int RF_THREADS = 256;
+constexpr int RF_THREADS = GRID_THREADS;
 constexpr int RF_WAVES = RF_THREADS / 64;
 constexpr int RF_MAX_STEPS = 1024;
 constexpr float RF_STEP_ROT = 0.2f;       // initial rotation step, rad
@@ -137,12 +135,12 @@ __global__ __launch_bounds__(RF_THREADS) void k_overlay_refine(const float* __re
         if (objective != nullptr && tid < 2) objective[(size_t)blockIdx.x * 2 + tid] = __builtin_nanf("");
         return;
     }
-    const int na = min(max(n_nodes[b], 0), min(N, MAX_ATOMS));
+    const int na = atom_count(n_nodes[b], N);
     const bool flip = flipped[b] != 0;
     for (int i = tid; i < n_ref * 3; i += RF_THREADS) s.y[i / 3][i % 3] = ref_frame[i];
-    if (tid < na) {                           // z_w as k_shape_overlay builds it
+    if (tid < na) {                           // z_w
         const float* x = frames + ((size_t)b * N + tid) * 3;
-        rotate_row(x[0], x[1], flip ? -x[2] : x[2], rot + w * 9, s.r[tid]);
+        frame_start(x[0], x[1], x[2], flip, rot + w * 9, s.r[tid]);
     }
     __syncthreads();
     if (tid < 3) {                            // atom centroid, summed in atom order
@@ -216,58 +214,31 @@ __global__ __launch_bounds__(RF_THREADS) void k_overlay_refine_pick(
         if (refined_score != nullptr && tid < 4) refined_score[b * 4 + tid] = __builtin_nanf("");
         return;
     }
-    const int na = min(max(n_nodes[b], 0), min(N, MAX_ATOMS));
+    const int na = atom_count(n_nodes[b], N);
     const bool flip = flipped[b] != 0;
     if (tid < 12) zr[tid] = ref_xform[tid];
     for (int i = tid; i < na; i += RF_THREADS) {
         const float* x = frames + ((size_t)b * N + i) * 3;
-        const float x0 = x[0], x1 = x[1], x2 = flip ? -x[2] : x[2];
+        const float x0 = x[0], x1 = x[1], x2 = x[2];
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
             const float* gt = ws + ((size_t)b * 4 + w) * RF_WS;
             float z[3], g[3];
-            rotate_row(x0, x1, x2, rot + w * 9, z);
+            frame_start(x0, x1, x2, flip, rot + w * 9, z);
             rotate_row(z[0], z[1], z[2], gt, g);
             c[w][i][0] = g[0] + gt[9]; c[w][i][1] = g[1] + gt[10]; c[w][i][2] = g[2] + gt[11];
         }
     }
     __syncthreads();
-    const int total = n * n * n;              // k_shape_overlay's walk, lane assignment and tree
-    float fg[4] = {0.f, 0.f, 0.f, 0.f}, gg[4] = {0.f, 0.f, 0.f, 0.f}, ff = 0.f;
-    for (int idx = tid; idx < total; idx += RF_THREADS) {
-        const int ix = idx / (n * n), iy = (idx / n) % n, iz = idx % n;
-        const float px = axes[ix], py = axes[n + iy], pz = axes[2 * n + iz];
-        const float fv = f[idx];
-        ff = fmaf(fv, fv, ff);
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const float g = density_at(px, py, pz, c[w], na, alpha, amp);
-            fg[w] = fmaf(fv, g, fg[w]); gg[w] = fmaf(g, g, gg[w]);
-        }
-    }
-    float v[9] = {fg[0], fg[1], fg[2], fg[3], gg[0], gg[1], gg[2], gg[3], ff};
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-    const int wid = tid >> 6;
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) red[k][wid] = v[k];
-    }
-    __syncthreads();
+    const float sw = overlap_scores<4>(f, axes, n, c, na, alpha, amp, red);
     if (tid < 4) {
-        const float sfg = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
-        const float sff = (red[8][0] + red[8][1]) + (red[8][2] + red[8][3]);
-        const float sgg = (red[4 + tid][0] + red[4 + tid][1]) + (red[4 + tid][2] + red[4 + tid][3]);
-        sc[tid] = sfg / (sff + sgg - sfg);
-        if (refined_score != nullptr) refined_score[b * 4 + tid] = sc[tid];
+        sc[tid] = sw;
+        if (refined_score != nullptr) refined_score[b * 4 + tid] = sw;
     }
     __syncthreads();
     if (tid == 0) {
-        int wb = 0;
-        float sb = sc[0];
-        for (int w = 1; w < 4; ++w)
-            if (sc[w] > sb) { sb = sc[w]; wb = w; }                 // the first maximum
+        float sb;
+        const int wb = first_max4(sc, &sb);
         const float start = best[b];
         const bool take = sb > start;                               // strictly better (NaN never is)
         start_best[b] = start;
@@ -301,11 +272,8 @@ __global__ __launch_bounds__(RF_THREADS) void k_overlay_refine_pick(
     __syncthreads();
     const int wb = s_pick;
     if (wb < 0) return;
-    for (int i = tid; i < na; i += RF_THREADS) {   // x_out = z' @ M_r^T + t_r; padded rows stay zero
-        float* out = posed + ((size_t)b * N + i) * 3;
-        const float* z = c[wb][i];
-        for (int k = 0; k < 3; ++k) out[k] = ((z[0] * zr[k * 3] + z[1] * zr[k * 3 + 1]) + z[2] * zr[k * 3 + 2]) + zr[9 + k];
-    }
+    for (int i = tid; i < na; i += RF_THREADS)     // x_out = z' @ M_r^T + t_r; padded rows stay zero
+        posed_row_pick(c[wb][i], zr, posed + ((size_t)b * N + i) * 3);
 }
 
 }  // namespace
@@ -316,15 +284,11 @@ extern "C" int mcg_shape_overlay_refined(const float* ref_frame, int n_ref, cons
                                          float* score, float* best, int32_t* which, int32_t* flipped, float* pose,
                                          float* posed, int steps, float* refine_ws, float* objective, float* start_best,
                                          int32_t* refined, float* refined_score, void* stream) {
-    if (!ref_frame || !ref_xform || !frames || !xform || !n_nodes_dev || !rot || !axes || !f_scratch || !best || !which ||
-        !flipped || !pose || !posed || !refine_ws || !start_best || !refined || B < 1 || N < 1 || N > MAX_ATOMS ||
-        n_ref < 3 || n_ref > MAX_ATOMS || n < 2 || steps < 0 || steps > RF_MAX_STEPS || !(alpha > 0.f)) {
-        mcg_set_error("mcg_shape_overlay_refined: bad arguments (non-null buffers, B >= 1, 1 <= N <= %d, "
-                      "3 <= n_ref <= %d, n >= 2, 0 <= steps <= %d, alpha > 0)", MAX_ATOMS, MAX_ATOMS, RF_MAX_STEPS);
-        return MCG_ERR_ARG;
-    }
-    if (int rc = mcg_shape_overlay(ref_frame, n_ref, ref_xform, frames, xform, n_nodes_dev, B, N, rot, axes, n, alpha,
-                                   amplitude, f_scratch, score, best, which, flipped, pose, posed, stream))
+    static_assert(RF_MAX_STEPS == 1024, "the bound the message below states");
+    const bool own_ok = refine_ws && start_best && refined && steps >= 0 && steps <= RF_MAX_STEPS && alpha > 0.f;
+    if (int rc = mcg_shape_overlay_launch("mcg_shape_overlay_refined", own_ok, ", 0 <= steps <= 1024, alpha > 0",
+                                          ref_frame, n_ref, ref_xform, frames, xform, n_nodes_dev, B, N, rot, axes, n,
+                                          alpha, amplitude, f_scratch, score, best, which, flipped, pose, posed, stream))
         return rc;
     hipStream_t s = (hipStream_t)stream;
     const double a = (double)alpha, amp = (double)amplitude;

@@ -40,6 +40,24 @@ def test_shape_overlay_refuses_bad_step_counts_before_any_device_work(monkeypatc
     assert CH.check_refine_steps(0) == 0 and CH.check_refine_steps(np.int64(1024)) == 1024
 
 
+def test_an_empty_batch_returns_every_key_of_the_call():
+    from ml_conformer_generator_amd import cheminformatics as CH
+    per_row = dict(coords=((20, 3), torch.float32), rotation=((3, 3), torch.float32), translation=((3,), torch.float32),
+                   tanimoto=((), torch.float32), orientation=((), torch.long), flipped=((), torch.bool),
+                   scores=((4,), torch.float32), start_tanimoto=((), torch.float32), refined=((), torch.bool),
+                   refined_scores=((4,), torch.float32), objective=((4, 2), torch.float32))
+    plain = ["coords", "rotation", "translation", "tanimoto", "orientation", "flipped"]
+    for with_scores in (False, True):
+        for refined_entry in (False, True):
+            want = plain + (["scores"] if with_scores else []) + (["start_tanimoto", "refined"] if refined_entry else []) \
+                + (["refined_scores", "objective"] if with_scores and refined_entry else [])
+            out = CH._overlay(_ref(), torch.zeros(0, 20, 3), torch.zeros(0, dtype=torch.int32), "cpu", with_scores, 5,
+                              refined_entry)
+            assert list(out) == want
+            for key, t in out.items():
+                assert t.shape == (0,) + per_row[key][0] and t.dtype == per_row[key][1], key
+
+
 def test_the_request_carries_the_step_budget():
     gen = _shell_generator()
     gen._reference_coord = lambda r: torch.as_tensor(r, dtype=torch.float32)
