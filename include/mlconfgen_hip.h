@@ -358,6 +358,26 @@ int mcg_shape_pair_tanimoto(const float* coords, const int32_t* n_nodes_dev, int
                             const float* axes, int n, float alpha, float amplitude, float* density_ws, float* gram_ws,
                             float* tanimoto, void* stream);
 
+/* ---- Receptor contacts ("Receptor clashes"): the steric overlap of every ligand heavy atom with a
+ * receptor, by brute force over all receptor atoms.
+ *   lig_xyz[B,N,3] with n_nodes_dev[b] real atoms (device memory, clamped to [0, N] on the device), lig_radius[B,N] their
+ *   van der Waals radii; rec_xyz[R,3], rec_radius[R] the receptor's heavy atoms (finite: the caller's check).
+ *   overlap_out[B,N]: max_j (r_i + r_j) - sqrt(dx*dx + dy*dy + dz*dz), d = x_i - y_j, in fp32 in exactly that order
+ *   (no contraction, correctly rounded sqrt); -inf on padded atoms; NaN for an atom with a non-finite coordinate (the
+ *   other atoms are unaffected).
+ *   splits: the receptor is cut into min(splits, ceil(R / 256)) ranges walked by different workgroups, their maxima
+ *   combined by a second launch in partial_ws[splits * B * N] (not read, and may be NULL, when splits = 1).  A maximum is
+ *   exact, so every output has the same bits whatever the splits, batch, row, padded width or receptor atom order.
+ * MCG_ERR_ARG (1, the value of hipErrorInvalidValue), nothing launched: a null buffer, B outside 1..MCG_RECEPTOR_MAX_B,
+ * N outside 1..64, R outside 1..MCG_RECEPTOR_MAX_ATOMS, splits outside 1..MCG_RECEPTOR_MAX_SPLITS, or splits > 1 without
+ * partial_ws. */
+#define MCG_RECEPTOR_MAX_B 16384
+#define MCG_RECEPTOR_MAX_ATOMS 131072
+#define MCG_RECEPTOR_MAX_SPLITS 256
+int mcg_receptor_overlap(const float* lig_xyz, const float* lig_radius, const int32_t* n_nodes_dev, int B, int N,
+                         const float* rec_xyz, const float* rec_radius, int R, int splits, float* partial_ws,
+                         float* overlap_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

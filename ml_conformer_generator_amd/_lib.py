@@ -58,6 +58,7 @@ SIGNATURES: Dict[str, tuple] = {
     "mcg_shape_overlay_refined": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp,
                                        _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcg_shape_pair_tanimoto": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp]),
+    "mcg_receptor_overlap": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "mcg_handoff": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp]),
     "mcg_handoff_ex": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcg_handoff_elements": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -45,7 +45,10 @@ forced by the scope of this build:
     (`cheminformatics.pairwise_shape_tanimoto`).  Off by default: nothing changes;
   * `refine_overlay` (opt-in, every generation entry, with `overlay`): the pose is refined on the GPU by a rigid-body
     ascent of the Gaussian overlap from each of the four principal-frame starts, kept where its shape Tanimoto is
-    strictly better (`cheminformatics.shape_overlay(refine_steps=...)`).  Off by default: nothing changes.
+    strictly better (`cheminformatics.shape_overlay(refine_steps=...)`).  Off by default: nothing changes;
+  * `receptor`, `max_receptor_clashes` (opt-in, every generation entry, with `overlay`): the steric contacts of every
+    posed molecule with the receptor the reference ligand came from, measured on the GPU (`receptor.receptor_overlap`),
+    and a filter on the number of clashing atoms.  Off by default: nothing changes.
 """
 from __future__ import annotations
 
@@ -71,6 +74,7 @@ from .equivariant_diffusion import EquivariantDiffusion, PredefinedNoiseSchedule
 from . import distributed as mcg_dist
 from . import host_pool
 from . import rdkit_order
+from . import receptor as mcg_receptor
 from .handoff import (GeneratedMolecule, assemble_molecules, bond_writeback_hip, molecules_from_tensors,
                       prepare_adj_mat_seer_input_hip)
 from .mol_utils import (get_context_shape, ifm_get_xh_from_fragment, ifm_merge_hip,
@@ -128,6 +132,8 @@ class _ShapeRequest:
     min_shape_tanimoto: Optional[float]
     max_pairwise_tanimoto: Optional[float]
     refine_steps: int = 0                         # `refine_overlay`: ascent steps of the refined pose, 0 = not refined
+    receptor: Optional[tuple] = None              # (coords [R,3] fp32, atomic numbers [R]) of its heavy atoms, host
+    max_receptor_clashes: Optional[int] = None
 
 
 class MLConformerGenerator(torch.nn.Module):
@@ -332,9 +338,17 @@ class MLConformerGenerator(torch.nn.Module):
     def _shape_request(self, reference_conformer, shape_scores: bool, top_k: Optional[int],
                        min_shape_tanimoto: Optional[float], overlay: bool = False,
                        max_pairwise_tanimoto: Optional[float] = None,
-                       refine_overlay: Union[bool, int] = False) -> Optional[_ShapeRequest]:
+                       refine_overlay: Union[bool, int] = False, receptor=None,
+                       max_receptor_clashes: Optional[int] = None) -> Optional[_ShapeRequest]:
         """The call's shape options, or None when it asked for none of them (`top_k` / `min_shape_tanimoto` /
         `max_pairwise_tanimoto` imply scoring).  Every refusal happens here, before any device work."""
+        if max_receptor_clashes is not None:
+            mcg_receptor.check_max_receptor_clashes(max_receptor_clashes)
+            if receptor is None:
+                raise ValueError("max_receptor_clashes needs a receptor")
+        if receptor is not None and not overlay:
+            raise ValueError("receptor needs overlay=True: molecules that are not posed onto the reference are not in "
+                             "the receptor's frame")
         refine_steps = 0
         if refine_overlay is not False:
             refine_steps = self._refine_steps(refine_overlay)
@@ -366,8 +380,12 @@ class MLConformerGenerator(torch.nn.Module):
                              "this package can read")
         ref_coord = self._reference_coord(reference_conformer)
         cheminformatics.check_reference_atoms(int(ref_coord.shape[0]))
+        rec = None
+        if receptor is not None:
+            rec = mcg_receptor.load_receptor(receptor)
+            mcg_receptor.check_clear_of_reference(rec[0], ref_coord)
         return _ShapeRequest(ref_coord, bool(overlay), bool(scoring), top_k, min_shape_tanimoto, max_pairwise_tanimoto,
-                             refine_steps)
+                             refine_steps, rec, max_receptor_clashes)
 
     @staticmethod
     def _refine_steps(refine_overlay) -> int:
@@ -408,10 +426,17 @@ class MLConformerGenerator(torch.nn.Module):
         (`cheminformatics.pairwise_shape_tanimoto`)."""
         return cheminformatics.pairwise_shape_tanimoto(ref_coord, coords, n_nodes, self.device)
 
+    def _receptor_coords(self, rec: tuple, coords: torch.Tensor, n_nodes: torch.Tensor,
+                         atomic_numbers: torch.Tensor) -> torch.Tensor:
+        """Per-atom receptor overlap [B,N] (device) of padded posed heavy-atom coordinates (`receptor.receptor_overlap`)."""
+        return mcg_receptor.receptor_overlap(rec, coords, n_nodes, atomic_numbers, self.device)
+
     def _shape_tensors(self, req: Optional[_ShapeRequest], res: dict) -> dict:
         """The shape step of one shard's result tensors: pose, then score (a score is the score of the returned
-        coordinates).  `res` with `x` posed and the per-sample tensors `overlay_tanimoto`, `pose` [B,12] (rotation
-        row-major, then translation; NaN where posing failed) and `shape_tanimoto` added, as far as the call asked."""
+        coordinates), then the receptor contacts of the returned coordinates.  `res` with `x` posed and the per-sample
+        tensors `overlay_tanimoto`, `pose` [B,12] (rotation row-major, then translation; NaN where posing failed),
+        `shape_tanimoto`, `receptor_clashes` (-1 where posing failed) and `receptor_max_overlap` (NaN there) added, as far
+        as the call asked."""
         if req is None:
             return res
         if req.overlay:
@@ -420,6 +445,12 @@ class MLConformerGenerator(torch.nn.Module):
                        pose=torch.cat([ov["rotation"].reshape(-1, 9), ov["translation"].reshape(-1, 3)], dim=1))
         if req.scoring:
             res = dict(res, shape_tanimoto=self._score_coords(req.ref_coord, res["x"], res["n_nodes"]))
+        if req.receptor is not None:
+            clashes, worst = mcg_receptor.clash_summary(
+                self._receptor_coords(req.receptor, res["x"], res["n_nodes"], res["elements"]))
+            posed = torch.isfinite(res["pose"]).all(dim=1).to(clashes.device)
+            res = dict(res, receptor_clashes=torch.where(posed, clashes, torch.full_like(clashes, -1)),
+                       receptor_max_overlap=torch.where(posed, worst, torch.full_like(worst, float("nan"))))
         return res
 
     def _score_mols(self, ref_coord: torch.Tensor, mols: List) -> List[Optional[float]]:
@@ -432,6 +463,22 @@ class MLConformerGenerator(torch.nn.Module):
                 out[k] = float(v)
         return out
 
+    def _contact_mols(self, rec: tuple, mols: List, poses: List) -> List[Optional[tuple]]:
+        """(receptor_clashes, receptor_max_overlap) of posed Mols' heavy atoms (elements from `GetAtomicNum()`), in ONE
+        batched device call; None where a Mol was dropped or its pose failed (it is not in the receptor's frame)."""
+        live = [k for k, m in enumerate(mols) if m is not None and poses[k] is not None and poses[k][1] is not None]
+        out: List[Optional[tuple]] = [None] * len(mols)
+        if live:
+            coords, n = _heavy_coords([mols[k] for k in live])
+            z = torch.zeros(coords.shape[0], coords.shape[1], dtype=torch.long)
+            for j, k in enumerate(live):
+                heavy = [a.GetAtomicNum() for a in mols[k].GetAtoms() if a.GetAtomicNum() != 1]
+                z[j, : len(heavy)] = torch.tensor(heavy, dtype=torch.long)
+            clashes, worst = mcg_receptor.clash_summary(self._receptor_coords(rec, coords, n, z))
+            for j, (c, w) in enumerate(zip(clashes.cpu().tolist(), worst.cpu().tolist())):
+                out[live[j]] = (int(c), float(w))
+        return out
+
     def _shape_objects(self, req: Optional[_ShapeRequest], done: List):
         """The shape step of one shard's finished Mols (None = dropped), each stage in ONE batched device call: pose, every
         conformer position moved (`cheminformatics.pose_mols`), then score (`_score_mols`).  Per Mol (scores, poses):
@@ -442,6 +489,22 @@ class MLConformerGenerator(torch.nn.Module):
                  if req is not None and req.overlay else none)
         scores = self._score_mols(req.ref_coord, done) if req is not None and req.scoring else list(none)
         return scores, poses
+
+    def _finished_shape(self, req: Optional[_ShapeRequest], done: List):
+        """(scores, poses, contacts) of one shard's finished Mols: `_shape_objects`, then the receptor contacts of the
+        posed Mols (`_contact_mols`; None per Mol where the call passed no receptor)."""
+        scores, poses = self._shape_objects(req, done)
+        contacts = (self._contact_mols(req.receptor, done, poses) if req is not None and req.receptor is not None
+                    else [None] * len(done))
+        return scores, poses, contacts
+
+    @staticmethod
+    def _clash_filter(req: Optional[_ShapeRequest], mols: List, contacts: List[Optional[tuple]]) -> List[int]:
+        """Positions of `mols` that pass `max_receptor_clashes` (all of them when the call set none): at most that many
+        clashing atoms; a molecule without contacts (its pose failed) does not pass."""
+        if req is None or req.max_receptor_clashes is None:
+            return list(range(len(mols)))
+        return [i for i, c in enumerate(contacts) if c is not None and c[0] <= req.max_receptor_clashes]
 
     @staticmethod
     def _select(req: Optional[_ShapeRequest], mols: List, scores: List[float], sample_ids: List[int], pair_fn) -> List:
@@ -465,9 +528,12 @@ class MLConformerGenerator(torch.nn.Module):
         t0 = time.perf_counter()
         mols = molecules_from_tensors(res["x"], res["elements"], res["bond"], res["n_nodes"], res["valid"],
                                       sample_ids=row_ids, shape_tanimoto=res.get("shape_tanimoto"),
-                                      overlay_tanimoto=res.get("overlay_tanimoto"), pose=res.get("pose"))
+                                      overlay_tanimoto=res.get("overlay_tanimoto"), pose=res.get("pose"),
+                                      receptor_clashes=res.get("receptor_clashes"),
+                                      receptor_max_overlap=res.get("receptor_max_overlap"))
         self.last_host_assembly_ms = (time.perf_counter() - t0) * 1e3      # D2H of the result tensors + record views
         kept, self.last_valid_fraction = _finish(mols, optimise_geometry, use_rdkit=False)    # no finisher: the proxy
+        kept = [kept[i] for i in self._clash_filter(req, kept, [m.receptor_contacts for m in kept])]
 
         def pair():
             row = {id(m): b for b, m in enumerate(mols)}
@@ -476,12 +542,13 @@ class MLConformerGenerator(torch.nn.Module):
                                      res["n_nodes"].reshape(-1).to(res["x"].device).index_select(0, idx))
         return self._select(req, kept, [m.shape_tanimoto for m in kept], [m.sample_id for m in kept], pair)
 
-    def _return_objects(self, req: Optional[_ShapeRequest], done: List, scores: List, poses: List,
+    def _return_objects(self, req: Optional[_ShapeRequest], done: List, scores: List, poses: List, contacts: List,
                         row_ids: Optional[torch.Tensor], sample_seed: Optional[int]) -> List:
         """What a call returns through a finisher: the finished Mols of the rows this rank returns (None = dropped; sample
         ids `row_ids`, default 0..B-1) get their properties - `sample_id` (seeded calls), `overlay_tanimoto`,
-        `shape_tanimoto`: set here, behind the object gather, which does not carry Mol properties - then the live ones
-        are selected, the pair matrix taken from their posed heavy atoms."""
+        `shape_tanimoto`, `receptor_clashes`, `receptor_max_overlap`: set here, behind the object gather, which does not
+        carry Mol properties - then the live ones pass the clash filter and are selected, the pair matrix taken from
+        their posed heavy atoms."""
         from . import rdkit_finish
         ids = list(range(len(done))) if row_ids is None else row_ids.tolist()
         if sample_seed is not None:
@@ -491,6 +558,8 @@ class MLConformerGenerator(torch.nn.Module):
         self.last_valid_fraction = len(live) / len(done) if done else 0.0
         rdkit_finish.tag_scores(done, "overlay_tanimoto", [None if p is None else p[0] for p in poses])
         rdkit_finish.tag_scores(done, "shape_tanimoto", scores)
+        rdkit_finish.tag_contacts(done, contacts)
+        live = [live[i] for i in self._clash_filter(req, live, [contacts[i] for i in live])]
         picked = [done[i] for i in live]
         return self._select(req, picked, [scores[i] for i in live], [ids[i] for i in live],
                             lambda: self._pair_coords(req.ref_coord, *_heavy_coords(picked)))
@@ -604,7 +673,8 @@ class MLConformerGenerator(torch.nn.Module):
                             ifm_diffusion_level: int = 50, sample_seed: Optional[int] = None, shape_scores: bool = False,
                             top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None,
                             overlay: bool = False, max_pairwise_tanimoto: Optional[float] = None,
-                            refine_overlay: Union[bool, int] = False) -> List:
+                            refine_overlay: Union[bool, int] = False, receptor=None,
+                            max_receptor_clashes: Optional[int] = None) -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
@@ -635,13 +705,22 @@ class MLConformerGenerator(torch.nn.Module):
         the reference, the best refined candidate kept where its shape Tanimoto is strictly better than the start's
         (`cheminformatics.shape_overlay(refine_steps=...)`).  `pose` and `overlay_tanimoto` describe the returned pose;
         ranking and selection are unchanged, and the pair matrix of `max_pairwise_tanimoto` reads the refined poses.
+        `receptor` (needs `overlay=True`): the receptor the reference ligand was taken from - an RDKit Mol, a PDB-format
+        string or a (coords, atomic_numbers) pair (`receptor.load_receptor`), in the reference's coordinates.  The
+        returned (posed, possibly refined) heavy atoms are measured against its heavy atoms on the GPU
+        (`receptor.receptor_overlap`; DESIGN.md section 6, "Receptor clashes"): records carry `receptor_clashes` (atoms
+        overlapping a receptor atom by >= 0.6 A) and `receptor_max_overlap` (A), the Mols the int / double properties of
+        the same names; None (no property) where posing failed.  `max_receptor_clashes=k`: drop the molecules with more
+        than k clashing atoms, and those whose pose failed, before the threshold / diversity / `top_k` selection.
         Refused with ValueError before any device work: scoring or posing without a reference conformer, a reference
         outside 3..64 heavy atoms, top_k < 1, a threshold outside [0, 1], max_pairwise_tanimoto outside (0, 1] or without
-        overlay, refine_overlay other than True or an integer in 1..1024 or without overlay, and a custom finisher."""
+        overlay, refine_overlay other than True or an integer in 1..1024 or without overlay, a receptor without overlay,
+        one `load_receptor` refuses or one that holds the reference (a reference heavy atom within 0.5 A of a receptor
+        heavy atom), max_receptor_clashes other than an integer >= 0 or without a receptor, and a custom finisher."""
         if sample_seed is not None:
             seeding.check_seed(sample_seed)
         req = self._shape_request(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
-                                  max_pairwise_tanimoto, refine_overlay)
+                                  max_pairwise_tanimoto, refine_overlay, receptor, max_receptor_clashes)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
         keyed = () if sample_seed is None else (sample_seed, None)   # unseeded: the positional call of before
         res = self._generate_shard(ref_context, ref_n_atoms, variance, None, n_samples, resample_steps, fixed_fragment,
@@ -649,7 +728,7 @@ class MLConformerGenerator(torch.nn.Module):
         if getattr(self, "finisher", None) is None:
             return self._return_records(req, self._shape_tensors(req, res), None, optimise_geometry)
         done = self._collect_finish(n_samples)    # finished per group while the later groups were still on their way
-        return self._return_objects(req, done, *self._shape_objects(req, done), None, sample_seed)
+        return self._return_objects(req, done, *self._finished_shape(req, done), None, sample_seed)
 
     @torch.no_grad()
     def generate_conformers_sharded(self, reference_conformer=None, n_samples: int = 10, variance: int = 2,
@@ -661,7 +740,8 @@ class MLConformerGenerator(torch.nn.Module):
                                     sample_seed: Optional[int] = None, shape_scores: bool = False,
                                     top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None,
                                     overlay: bool = False, max_pairwise_tanimoto: Optional[float] = None,
-                                    refine_overlay: Union[bool, int] = False) -> List:
+                                    refine_overlay: Union[bool, int] = False, receptor=None,
+                                    max_receptor_clashes: Optional[int] = None) -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -677,10 +757,11 @@ class MLConformerGenerator(torch.nn.Module):
         `sample_seed` (instead of `seed`): the keyed stream of `edm_tensors` - every rank computes the keyed sizes of all
         `n_samples` itself (no broadcast), generates its shard with the shard's global indices as `sample_ids` and seeds
         no generator, so sample i is the same molecule on any world size and under either `balance`.
-        `shape_scores`, `top_k`, `min_shape_tanimoto`, `overlay`, `max_pairwise_tanimoto`, `refine_overlay`: as in
-        `generate_conformers`.
-        Every rank poses and scores ITS OWN shard on its own GPU before the gather (posed coordinates, poses and scores
-        travel as per-sample result tensors, or next to the finished Mols).  The selection runs on the rows a rank
+        `shape_scores`, `top_k`, `min_shape_tanimoto`, `overlay`, `max_pairwise_tanimoto`, `refine_overlay`, `receptor`,
+        `max_receptor_clashes`: as in `generate_conformers`.
+        Every rank poses, scores and measures the receptor contacts of ITS OWN shard on its own GPU before the gather
+        (posed coordinates, poses, scores and contacts travel as per-sample result tensors, or next to the finished
+        Mols).  The selection runs on the rows a rank
         returns: with gather="all" every rank selects from the whole batch (the pair matrix of the whole batch on its own
         GPU) and returns the same list; with gather="rank0" every other rank selects within its own shard."""
         if gather not in ("all", "rank0"):
@@ -690,14 +771,14 @@ class MLConformerGenerator(torch.nn.Module):
                 raise ValueError("pass either seed (per-rank device generator) or sample_seed (keyed stream), not both")
             seeding.check_seed(sample_seed)
         req = self._shape_request(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
-                                  max_pairwise_tanimoto, refine_overlay)
+                                  max_pairwise_tanimoto, refine_overlay, receptor, max_receptor_clashes)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)
         hi_n = min(ref_n_atoms + variance, self.max_n_nodes)
         # decided from the configuration, not from what this rank's shard happened to produce: every rank takes the same
         # path through the collectives (an EMPTY shard has no stage of its own making)
         finishing = getattr(self, "finisher", None) is not None
-        finished: List = []       # (Mol, score, pose) per sample of this rank's shard, where a finisher runs
+        finished: List = []       # (Mol, score, pose, contacts) per sample of this rank's shard, where a finisher runs
 
         def run_shard(sizes_shard, index):
             keyed = () if sample_seed is None else (sample_seed, index)
@@ -710,7 +791,7 @@ class MLConformerGenerator(torch.nn.Module):
             # finisher's exception, a result-count mismatch) makes EVERY rank raise ShardError instead of leaving the
             # others parked in the object gather
             done = self._collect_finish(int(index.numel()))
-            finished[:] = zip(done, *self._shape_objects(req, done))
+            finished[:] = zip(done, *self._finished_shape(req, done))
             return res
 
         def seed_device(s):
@@ -735,8 +816,8 @@ class MLConformerGenerator(torch.nn.Module):
         if not finishing:
             return self._return_records(req, res, row_ids, optimise_geometry)
         rows = mcg_dist.gather_objects(finished, shards, group, dst)      # the Mols travel as objects, with their scores
-        return self._return_objects(req, [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows], row_ids,
-                                    sample_seed)
+        return self._return_objects(req, [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows],
+                                    [r[3] for r in rows], row_ids, sample_seed)
 
     @torch.no_grad()
     def forward(self, reference_conformer=None, n_samples: int = 10, variance: int = 2,
@@ -745,10 +826,12 @@ class MLConformerGenerator(torch.nn.Module):
                 blend_power: int = 3, ifm_diffusion_level: int = 50, sample_seed: Optional[int] = None,
                 shape_scores: bool = False, top_k: Optional[int] = None,
                 min_shape_tanimoto: Optional[float] = None, overlay: bool = False,
-                max_pairwise_tanimoto: Optional[float] = None, refine_overlay: Union[bool, int] = False) -> List:
+                max_pairwise_tanimoto: Optional[float] = None, refine_overlay: Union[bool, int] = False, receptor=None,
+                max_receptor_clashes: Optional[int] = None) -> List:
         return self.generate_conformers(reference_conformer, n_samples, variance, reference_context, n_atoms,
                                         optimise_geometry, resample_steps, fixed_fragment,
                                         inertial_fragment_matching, blend_power, ifm_diffusion_level,
                                         sample_seed=sample_seed, shape_scores=shape_scores, top_k=top_k,
                                         min_shape_tanimoto=min_shape_tanimoto, overlay=overlay,
-                                        max_pairwise_tanimoto=max_pairwise_tanimoto, refine_overlay=refine_overlay)
+                                        max_pairwise_tanimoto=max_pairwise_tanimoto, refine_overlay=refine_overlay,
+                                        receptor=receptor, max_receptor_clashes=max_receptor_clashes)

@@ -44,25 +44,45 @@ class GeneratedMolecule:
     its generation call the record is (invalid molecules are dropped, so a kept record's position says nothing).
     `shape_tanimoto`: its shape score against the reference when the call asked for scores, else None.
     `overlay_tanimoto` / `pose`: the score and rigid pose of a call that posed its molecules onto the reference
-    (`overlay=True`), else None."""
-    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_score", "_overlay")
+    (`overlay=True`), else None.  `receptor_clashes` / `receptor_max_overlap`: its steric contacts with the call's
+    receptor, else None."""
+    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_score", "_overlay", "_contacts")
 
     def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True,
                  sample_id: Optional[int] = None):
         self._z, self._coords, self._bonds, self.valid = list(atomic_numbers), coords, bond_orders, bool(valid)
         self._batch, self._b, self._sid = None, -1, sample_id
-        self._score = self._overlay = None
+        self._score = self._overlay = self._contacts = None
 
     @classmethod
     def _view(cls, batch: _HostBatch, b: int, valid: bool, sample_id: Optional[int] = None,
-              score: Optional[float] = None, overlay: Optional[tuple] = None) -> "GeneratedMolecule":
+              score: Optional[float] = None, overlay: Optional[tuple] = None,
+              contacts: Optional[tuple] = None) -> "GeneratedMolecule":
         m = cls.__new__(cls)
         m._z = m._coords = m._bonds = None
         m.valid, m._batch, m._b = valid, batch, b
         m._sid = b if sample_id is None else sample_id
         m._score = score
         m._overlay = overlay
+        m._contacts = contacts
         return m
+
+    @property
+    def receptor_contacts(self) -> Optional[Tuple[int, float]]:
+        """(receptor_clashes, receptor_max_overlap), or None."""
+        return self._contacts
+
+    @property
+    def receptor_clashes(self) -> Optional[int]:
+        """Heavy atoms overlapping a receptor heavy atom by >= 0.6 A (`receptor.CLASH_OVERLAP`) when the call passed a
+        `receptor`; None otherwise, and where posing failed (the molecule is not in the receptor's frame)."""
+        return None if self._contacts is None else self._contacts[0]
+
+    @property
+    def receptor_max_overlap(self) -> Optional[float]:
+        """The largest overlap (r_i + r_j) - d_ij of a heavy atom with a receptor heavy atom, in A (negative when nothing
+        touches), when the call passed a `receptor`; None otherwise, and where posing failed."""
+        return None if self._contacts is None else self._contacts[1]
 
     @property
     def overlay_tanimoto(self) -> Optional[float]:
@@ -253,12 +273,15 @@ def bond_writeback_hip(bond: torch.Tensor, elements: torch.Tensor, n_nodes: torc
 def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: torch.Tensor, n_nodes: torch.Tensor,
                            valid: torch.Tensor, sample_ids: Optional[Sequence[int]] = None,
                            shape_tanimoto: Optional[torch.Tensor] = None, overlay_tanimoto: Optional[torch.Tensor] = None,
-                           pose: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
+                           pose: Optional[torch.Tensor] = None, receptor_clashes: Optional[torch.Tensor] = None,
+                           receptor_max_overlap: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
     (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
     (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records).
     `overlay_tanimoto[b]` / `pose[b]` (rotation row-major, then translation: [B,12], NaN where posing failed): row b's
-    pose onto the reference (None: records of a call that did not pose)."""
+    pose onto the reference (None: records of a call that did not pose).  `receptor_clashes[b]` / `receptor_max_overlap[b]`:
+    row b's receptor contacts (a negative clash count: not measured, the record gets None; None: a call without a
+    receptor)."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
     view = GeneratedMolecule._view
     if sample_ids is None and shape_tanimoto is None and overlay_tanimoto is None:
@@ -272,7 +295,11 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
         tan, poses = overlay_tanimoto.cpu().tolist(), pose.cpu().to(torch.float32)
         ok = torch.isfinite(poses).all(dim=1).tolist()
         overlays = [(float(t), poses[b] if ok[b] else None) for b, t in enumerate(tan)]
-    return [view(batch, b, bool(v), ids[b], scores[b], overlays[b]) for b, v in enumerate(flags)]
+    contacts = [None] * len(flags)
+    if receptor_clashes is not None:
+        contacts = [None if c < 0 else (int(c), float(w)) for c, w in
+                    zip(receptor_clashes.cpu().tolist(), receptor_max_overlap.cpu().tolist())]
+    return [view(batch, b, bool(v), ids[b], scores[b], overlays[b], contacts[b]) for b, v in enumerate(flags)]
 
 
 def assemble_molecules(x: torch.Tensor, elements: torch.Tensor, bond: torch.Tensor, n_nodes: torch.Tensor

@@ -147,6 +147,15 @@ def tag_sample_ids(mols: Sequence, sample_ids: Sequence[int]) -> None:
             m.SetIntProp("sample_id", int(sid))
 
 
+def tag_contacts(mols: Sequence, contacts: Sequence[Optional[tuple]]) -> None:
+    """Set the int property `receptor_clashes` and the double property `receptor_max_overlap` on every Mol of `mols`
+    (None = dropped) from `contacts[k]` = (clashes, max overlap), None = not measured.  Set after the object gather."""
+    for m, c in zip(mols, contacts):
+        if m is not None and c is not None and hasattr(m, "SetIntProp"):
+            m.SetIntProp("receptor_clashes", int(c[0]))
+            m.SetDoubleProp("receptor_max_overlap", float(c[1]))
+
+
 def tag_scores(mols: Sequence, prop: str, scores: Sequence[Optional[float]]) -> None:
     """Set the double property `prop` (`shape_tanimoto`, `overlay_tanimoto`) on every Mol of `mols` (None = dropped);
     `scores[k]` belongs to `mols[k]`, None = no score.  Set after the object gather: RDKit does not pickle Mol properties

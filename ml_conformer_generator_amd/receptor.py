@@ -1,0 +1,221 @@
+"""Steric contacts of posed molecules with a receptor, on the GPU ("Receptor clashes").
+
+Only heavy atoms count, on both sides.  For ligand atom i (posed coordinates x_i, van der Waals radius r_i) and receptor
+atom j (y_j, r_j) the overlap is (r_i + r_j) - |x_i - y_j|, in fp32 in that order; an atom's overlap is its largest over
+all receptor atoms, and it clashes when that is >= CLASH_OVERLAP (UCSF ChimeraX's default clash criterion; no H-bond
+allowance: no donors or acceptors are typed).  Per molecule: `receptor_clashes` = the number of clashing atoms,
+`receptor_max_overlap` = the largest atom overlap in angstrom (negative when nothing touches).
+
+The radii are one table keyed by atomic number (`VDW_RADII`): Bondi (1964) where Bondi gives a value, Mantina et al.
+(2009) for boron, DEFAULT_RADIUS for every other element.  The kernel (`mcg_receptor_overlap`) sees radii only.
+"""
+from __future__ import annotations
+
+import math
+import operator
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib
+
+CLASH_OVERLAP = 0.6            # angstrom: UCSF ChimeraX `clashes` default overlap cutoff
+SELF_CONTACT = 0.5             # angstrom: a receptor atom this close to a reference atom means the ligand is in it
+MAX_RECEPTOR_ATOMS = 1 << 17   # include/mlconfgen_hip.h MCG_RECEPTOR_MAX_ATOMS (heavy atoms)
+MAX_BATCH = 16384              # MCG_RECEPTOR_MAX_B
+MAX_LIGAND_ATOMS = 64          # the kernel's N limit (the shape kernels' MAX_ATOMS)
+_MAX_SPLITS = 256              # MCG_RECEPTOR_MAX_SPLITS
+_TILE = 256                    # receptor atoms per LDS tile of the kernel
+_TARGET_WORKGROUPS = 1024      # four 256-lane workgroups per CU of the MI355X
+DEFAULT_RADIUS = 2.00
+
+# Z -> van der Waals radius (angstrom).  A. Bondi, J. Phys. Chem. 68, 441 (1964), Table I, for every element it lists;
+# boron (the one element of config.ELEMENTS Bondi lacks): M. Mantina et al., J. Phys. Chem. A 113, 5806 (2009).
+VDW_RADII = {
+    1: 1.20, 2: 1.40, 3: 1.82, 5: 1.92, 6: 1.70, 7: 1.55, 8: 1.52, 9: 1.47, 10: 1.54, 11: 2.27, 12: 1.73, 14: 2.10,
+    15: 1.80, 16: 1.80, 17: 1.75, 18: 1.88, 19: 2.75, 28: 1.63, 29: 1.40, 30: 1.39, 31: 1.87, 33: 1.85, 34: 1.90,
+    35: 1.85, 36: 2.02, 46: 1.63, 47: 1.72, 48: 1.58, 49: 1.93, 50: 2.17, 52: 2.06, 53: 1.98, 54: 2.16, 78: 1.72,
+    79: 1.66, 80: 1.55, 81: 1.96, 82: 2.02, 92: 1.86,
+}
+
+_SYMBOLS = ("H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr Rb Sr Y "
+            "Zr Nb Mo Tc Ru Rh Pd Ag Cd In Sn Sb Te I Xe Cs Ba La Ce Pr Nd Pm Sm Eu Gd Tb Dy Ho Er Tm Yb Lu Hf Ta W Re "
+            "Os Ir Pt Au Hg Tl Pb Bi Po At Rn Fr Ra Ac Th Pa U Np Pu Am Cm Bk Cf Es Fm Md No Lr Rf Db Sg Bh Hs Mt Ds Rg "
+            "Cn Nh Fl Mc Lv Ts Og").split()
+_Z_OF = {s.upper(): z for z, s in enumerate(_SYMBOLS, 1)}
+_Z_OF["D"] = 1                 # deuterium: a hydrogen
+_RADIUS_TABLE = torch.tensor([VDW_RADII.get(z, DEFAULT_RADIUS) for z in range(len(_SYMBOLS) + 1)], dtype=torch.float32)
+
+
+def vdw_radius(z: int) -> float:
+    """The van der Waals radius (angstrom) of atomic number `z`: `VDW_RADII`, else DEFAULT_RADIUS."""
+    return VDW_RADII.get(int(z), DEFAULT_RADIUS)
+
+
+def vdw_radii(atomic_numbers: torch.Tensor) -> torch.Tensor:
+    """fp32 radii of a tensor of atomic numbers (same shape, on its device); Z outside 1..118 gets DEFAULT_RADIUS."""
+    z = torch.as_tensor(atomic_numbers).to(torch.long)
+    z = torch.where((z >= 1) & (z <= len(_SYMBOLS)), z, torch.zeros_like(z))
+    return _RADIUS_TABLE.to(z.device)[z]
+
+
+# ----------------------------------------------------------------------------------------------- loading
+def _pdb_element(line: str) -> str:
+    """The element symbol (upper case) of an ATOM / HETATM line: columns 77-78, else from the atom name (columns 13-16)
+    by the PDB convention - a one-letter element sits in column 14, a two-letter one starts in column 13, and a
+    four-character name starting with H or D is a hydrogen."""
+    el = line[76:78].strip()
+    if el:
+        return el.upper()
+    name = line[12:16].ljust(4)
+    if name[0] in "HD" and name.strip() == name and name.isalnum():
+        return name[0]
+    if name[0] == " " or name[0].isdigit():
+        rest = [c for c in name[1:] if c.isalpha()]
+        return rest[0].upper() if rest else ""
+    two = name[:2].upper()
+    return two if two.isalpha() and two in _Z_OF else name[0].upper()
+
+
+def parse_pdb(text: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(coords [R,3] fp32, atomic numbers [R] int64) of the heavy atoms of a PDB-format string: the ATOM / HETATM
+    records of the first model (reading stops at the first ENDMDL), alternate location blank or A, hydrogens and
+    deuteriums skipped.  A record whose coordinates or element cannot be read is a ValueError."""
+    xyz, zs = [], []
+    for k, line in enumerate(text.splitlines(), 1):
+        rec = line[:6].rstrip()
+        if rec == "ENDMDL":
+            break
+        if rec not in ("ATOM", "HETATM") or line[16:17] not in ("", " ", "A"):
+            continue
+        sym = _pdb_element(line)
+        z = _Z_OF.get(sym)
+        if z is None:
+            raise ValueError(f"receptor PDB line {k}: unreadable element {sym!r}: {line!r}")
+        if z == 1:
+            continue
+        try:
+            xyz.append((float(line[30:38]), float(line[38:46]), float(line[46:54])))
+        except ValueError:
+            raise ValueError(f"receptor PDB line {k}: unreadable coordinates: {line!r}") from None
+        zs.append(z)
+    return torch.tensor(xyz, dtype=torch.float32).reshape(-1, 3), torch.tensor(zs, dtype=torch.long)
+
+
+def load_receptor(receptor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(coords [R,3] fp32, atomic numbers [R] int64) on the host: the heavy atoms of `receptor`, which is an RDKit Mol
+    (or anything with `GetConformer().GetPositions()` and `GetAtoms()`), a PDB-format string (`parse_pdb`), or a
+    `(coords [R,3], atomic_numbers [R])` pair (hydrogens, Z = 1, are dropped).  Refused with ValueError: no heavy atoms,
+    more than MAX_RECEPTOR_ATOMS, a non-finite coordinate, an unreadable record."""
+    if isinstance(receptor, str):
+        coords, z = parse_pdb(receptor)
+    elif hasattr(receptor, "GetConformer") and hasattr(receptor, "GetAtoms"):
+        import numpy as np
+        pos = torch.as_tensor(np.asarray(receptor.GetConformer().GetPositions(), dtype=np.float64)).reshape(-1, 3)
+        z = torch.tensor([a.GetAtomicNum() for a in receptor.GetAtoms()], dtype=torch.long)
+        if z.numel() != pos.shape[0]:
+            raise ValueError(f"receptor Mol: {z.numel()} atoms but {pos.shape[0]} conformer positions")
+        coords, z = pos[z != 1].to(torch.float32), z[z != 1]
+    elif isinstance(receptor, (tuple, list)) and len(receptor) == 2:
+        try:
+            coords = torch.as_tensor(receptor[0], dtype=torch.float32).cpu().reshape(-1, 3)
+            z = torch.as_tensor(receptor[1]).cpu().reshape(-1)
+        except (TypeError, RuntimeError, ValueError) as e:
+            raise ValueError(f"receptor (coords, atomic_numbers): unreadable: {e}") from None
+        if z.dtype.is_floating_point or z.dtype == torch.bool or z.numel() != coords.shape[0]:
+            raise ValueError("receptor (coords [R,3], atomic_numbers [R]): R integer atomic numbers are needed, got "
+                             f"{z.numel()} of type {z.dtype} for {coords.shape[0]} coordinates")
+        z = z.to(torch.long)
+        if z.numel() and int(z.min()) < 1:
+            raise ValueError(f"receptor atomic numbers must be >= 1, got {int(z.min())}")
+        coords, z = coords[z != 1], z[z != 1]
+    else:
+        raise ValueError("receptor must be an RDKit Mol, a PDB-format string or a (coords, atomic_numbers) pair, got "
+                         f"{type(receptor).__name__}")
+    R = int(z.numel())
+    if R == 0:
+        raise ValueError("the receptor has no heavy atoms")
+    if R > MAX_RECEPTOR_ATOMS:
+        raise ValueError(f"the receptor has {R} heavy atoms; at most {MAX_RECEPTOR_ATOMS} are supported")
+    if not bool(torch.isfinite(coords).all()):
+        raise ValueError("the receptor has a non-finite coordinate")
+    return coords.contiguous(), z.contiguous()
+
+
+def check_clear_of_reference(rec_coords: torch.Tensor, ref_coord: torch.Tensor) -> None:
+    """ValueError if any reference heavy atom lies within SELF_CONTACT of a receptor heavy atom: the receptor holds
+    the reference ligand itself (a whole complex), and every molecule posed onto it would clash."""
+    ref = torch.as_tensor(ref_coord, dtype=torch.float64).reshape(-1, 3)
+    d = torch.cdist(ref, rec_coords.to(torch.float64), compute_mode="donot_use_mm_for_euclid_dist")
+    close = d <= SELF_CONTACT
+    if bool(close.any()):
+        i, j = (int(v) for v in close.nonzero()[0])
+        raise ValueError(f"the receptor contains the reference ligand: reference atom {i} lies {float(d[i, j]):.3f} A "
+                         f"from receptor atom {j} (<= {SELF_CONTACT} A); remove the ligand from the receptor")
+
+
+def check_max_receptor_clashes(value) -> int:
+    """`max_receptor_clashes` as an int >= 0 (an integer type, not a bool), else ValueError."""
+    try:
+        k = None if isinstance(value, bool) else operator.index(value)
+    except TypeError:
+        k = None
+    if k is None or k < 0:
+        raise ValueError(f"max_receptor_clashes must be an integer >= 0, got {value!r}")
+    return int(k)
+
+
+# ----------------------------------------------------------------------------------------------- device
+def default_splits(B: int, N: int, R: int) -> int:
+    """Receptor ranges per ligand block: enough workgroups to fill the GPU, at least one tile each."""
+    blocks = -(-B * N // _TILE)
+    return max(1, min(-(-R // _TILE), -(-_TARGET_WORKGROUPS // blocks), _MAX_SPLITS))
+
+
+@torch.no_grad()
+def receptor_overlap(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_numbers: torch.Tensor, device=None,
+                     splits: Optional[int] = None) -> torch.Tensor:
+    """Per-atom overlap [B,N] fp32 on the device: max over the receptor's heavy atoms of (r_i + r_j) - |x_i - y_j| for
+    each atom of the padded ligand coordinates `coords` [B,N,3] with `n_nodes` [B] real atoms and `atomic_numbers`
+    [B, >= N]; -inf on padded atoms, NaN for an atom with a non-finite coordinate.  `receptor`: what `load_receptor`
+    takes.  One `mcg_receptor_overlap` call; `splits` (default `default_splits`) only decides how the receptor is cut
+    across workgroups, never a bit of the result.  Refused before any device work: what `load_receptor` refuses, atom
+    counts outside [0, N], N > 64, B > MAX_BATCH, atomic numbers narrower than N."""
+    from .cheminformatics import check_n_nodes
+    rec_xyz, rec_z = load_receptor(receptor)
+    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
+    B, N = int(coords.shape[0]), int(coords.shape[1])
+    check_n_nodes(n_nodes, B, N)
+    if N > MAX_LIGAND_ATOMS or B > MAX_BATCH:
+        raise ValueError(f"receptor contacts take at most {MAX_BATCH} molecules of at most {MAX_LIGAND_ATOMS} atoms, got "
+                         f"[{B}, {N}]")
+    z = torch.as_tensor(atomic_numbers)
+    if z.dim() != 2 or z.shape[0] != B or z.shape[1] < N:
+        raise ValueError(f"atomic_numbers must be [B, >= N] = [{B}, >= {N}], got {list(z.shape)}")
+    if B == 0 or N == 0:
+        return torch.full((B, N), -math.inf, device=dev)
+    R = int(rec_z.numel())
+    S = default_splits(B, N, R) if splits is None else int(splits)
+    x = coords.to(dev, torch.float32).contiguous()
+    lig_r = vdw_radii(z[:, :N].to(dev)).contiguous()
+    nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B).contiguous()
+    rec = rec_xyz.to(dev)
+    rec_r = vdw_radii(rec_z).to(dev)
+    ws = torch.empty(S * B * N if S > 1 else 0, device=dev)
+    out = torch.empty(B, N, device=dev)
+    _lib.check(_lib.lib().mcg_receptor_overlap(_lib.dptr(x), _lib.dptr(lig_r), _lib.dptr(nn), B, N, _lib.dptr(rec),
+                                               _lib.dptr(rec_r), R, S, _lib.dptr(ws) if S > 1 else None,
+                                               _lib.dptr(out), _lib.current_stream_ptr(dev)),
+               "mcg_receptor_overlap")
+    return out
+
+
+def clash_summary(overlap: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(receptor_clashes [B] int32, receptor_max_overlap [B] fp32) of a per-atom overlap [B,N] (on its device): the
+    atoms with an overlap >= CLASH_OVERLAP, and the largest overlap (-inf for a molecule without atoms, NaN for one
+    with a non-finite atom)."""
+    B = int(overlap.shape[0])
+    if overlap.shape[1] == 0:
+        return (torch.zeros(B, dtype=torch.int32, device=overlap.device),
+                torch.full((B,), -math.inf, device=overlap.device))
+    return (overlap >= CLASH_OVERLAP).sum(dim=1, dtype=torch.int32), overlap.amax(dim=1)
