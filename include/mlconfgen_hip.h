@@ -75,6 +75,75 @@ int mcg_egnn_set_option(mcg_egnn* m, int option, int value);
  * test sees that an option changed launch shapes. */
 int mcg_debug_gemm_launches(int64_t* counts_host, int reset);
 
+/* ---- Kernel-level pin of the node / GCN GEMMs (csrc/mcg_gemm.hip): ONE launch of one launcher on the caller's data.
+ *   C[M, n_store] = act(A1[M,K1] W1^T + G(A2)[M,K2] W2^T + bias) + resid,  W = [W1 | W2] = w_host[n_out][K1 + K2] (nn.Linear
+ * layout, HOST memory); rows >= M and columns >= n_store of C are not written.  G = identity, or (a2_rows set) the sum of the
+ * first a2_nsum (2..4) of rows a2_rows[r][0..3] of A2 in slot order, ((a + b) + c) + d in fp32, followed in the Bf16 family
+ * only by an fp32 division by 100.  Side job (side_x set): side_x[v][0..2] += (((u[s0] + u[s1]) + u[s2]) + u[s3]) / 100 with
+ * s = side_slots[v][0..3] and u = side_u[.][4], v < side_M; component 3 is not touched.
+ * mcg_debug_gemm packs the weight with the library's own packer for the family, pads the bias to 16 * n_tiles
+ * (n_tiles = ceil(n_out / 16)), uploads both through the library's device-memory pool, calls the real launcher with
+ * (rn, mr, deep, lds) exactly as given, synchronises `stream`, frees, and reports in *ran_host the template instantiation
+ * that ran.  Every contract of the kernels is checked on the HOST first (MCG_ERR_ARG and mcg_last_error() text, no device
+ * call made), so a caller cannot launch out of contract:
+ *   - d, ran_host, w_host, A1, C not NULL; family, act, c_blocked, deep, lds in range; reserved zero;
+ *   - M >= 1, n_out >= 1, 1 <= n_store <= 16 * n_tiles; K1 >= 4, K1 % 4 == 0, K2 >= 0, K2 % 4 == 0, A2 set iff K2 > 0;
+ *     every buffer below 2^29 floats (32-bit byte offsets inside the kernels);
+ *   - leading dimensions are multiples of 4 and cover what the chosen kernel reads, checked against the buffer sizes the
+ *     descriptor states (in floats): lda >= K and a_floats >= (rows - 1) * lda + R(K), rows = M (a2_src_rows for a gathered
+ *     A2), with R(K) = K for the fp32 families and R(K) = 32 * ceil(K / 32) for MCG_GEMM_BF16 / MCG_GEMM_X6, whose kernels
+ *     read every row up to the next multiple of 32: the caller provides up to 28 FINITE floats behind the K real ones of
+ *     every row (the next row's data will do; the last row needs them inside the buffer), which zero weights cancel;
+ *     resid: n_store % 4 == 0, ldr >= n_store, resid_floats >= (M - 1) * ldr + n_store;  C: ldc >= n_store and
+ *     c_floats >= (M - 1) * ldc + n_store, or c_blocked (below) and c_floats >= 896 * M;
+ *   - a gather only with K2 > 0, a2_nsum in 2..4 and a2_src_rows >= 1, and only on MCG_GEMM_F32ROWS16 (sums 2, 3 or 4 rows)
+ *     and MCG_GEMM_BF16 (sums 2, or 4 for a2_nsum 3 and 4: the unused slots must name a zero row); a2_nsum = 0 without one;
+ *   - a side job (side_x, side_u, side_slots all set, side_M >= 1, side_u_rows >= 1) on every family but MCG_GEMM_X6;
+ *   - c_blocked (C[part][14 k-blocks][8 pieces][M rows][4], column = 432 part + 32 k-block + 4 piece + (0..3)) only on
+ *     MCG_GEMM_F32 / MCG_GEMM_BF16 and only with n_tiles == 54;
+ *   - rn: 0 (the launcher's own choice) .. 3 for MCG_GEMM_F32 / MCG_GEMM_BF16 / MCG_GEMM_X6 (mr = deep = 0 there); for
+ *     MCG_GEMM_F32ROWS16 a tile the launcher has an instantiation for: mr 1 with rn 1, 2, 3 or 6, mr 2 with rn 2 or 3, deep
+ *     only with mr 1 and rn 1 or 2;  lds (MCG_OPT_GEMM_BF16_LDS: 0 automatic, 1 never, 2 = the LDS-staged kernel if the shape
+ *     fits it, else the 32-row kernel) only on MCG_GEMM_BF16.
+ * Then, still before the launch, the slot tables are read back and every slot a kernel will read (all four of a side-job
+ * entry, the summed ones of a gather) must name a row inside its buffer. */
+enum { MCG_GEMM_F32 = 0, MCG_GEMM_F32ROWS16 = 1, MCG_GEMM_BF16 = 2, MCG_GEMM_X6 = 3 };                 /* family = launcher */
+enum { MCG_GEMM_KERNEL_F32 = 1, MCG_GEMM_KERNEL_F32ROWS16 = 2, MCG_GEMM_KERNEL_BF16 = 3, MCG_GEMM_KERNEL_BF16_LDS = 4,
+       MCG_GEMM_KERNEL_X6 = 5 };
+enum { MCG_GEMM_PACK4 = 0, MCG_GEMM_PACK16 = 1, MCG_GEMM_PACK16X3 = 2 };
+typedef struct mcg_gemm_desc {
+    const float* A1;             /* device [M][lda1] */
+    const float* A2;             /* device [M or a2_src_rows][lda2], NULL when K2 = 0 */
+    const float* bias;           /* device [n_out] or NULL */
+    const float* resid;          /* device [M][ldr] or NULL */
+    float* C;                    /* device */
+    const int32_t* a2_rows;      /* device [M][4] or NULL */
+    const float* side_u;         /* device [side_u_rows][4] */
+    const int32_t* side_slots;   /* device [side_M][4] */
+    float* side_x;               /* device [side_M][4] */
+    const float* w_host;         /* HOST [n_out][K1 + K2] */
+    int64_t a1_floats, a2_floats, resid_floats, c_floats;      /* sizes of the buffers behind A1, A2, resid, C */
+    int32_t lda1, lda2, ldr, ldc;
+    int32_t M, K1, K2, n_out, n_store;
+    int32_t act;                 /* 0 none, 1 SiLU, 2 ReLU */
+    int32_t a2_nsum, a2_src_rows, side_M, side_u_rows, c_blocked;
+    int32_t family, rn, mr, deep, lds;
+    int32_t reserved[4];         /* must be zero */
+} mcg_gemm_desc;
+/* kernel = MCG_GEMM_KERNEL_*, then its template arguments (0 where the template has none): mcg_gemm_kernel<RN, RING>,
+ * mcg_gemm16_kernel<RN, GATHER, MR, RING>, mcg_gemm_bf16_kernel<RN, GATHER>, mcg_gemm_bf16_lds_kernel<GATHER, RESID, SEG2,
+ * RING>, mcg_gemm_x6_kernel<RN> */
+typedef struct mcg_gemm_ran {
+    int32_t kernel, rn, mr, ring, gather, resid, seg2, reserved;
+} mcg_gemm_ran;
+int mcg_debug_gemm(const mcg_gemm_desc* d, mcg_gemm_ran* ran_host, void* stream);
+/* Host only: the operand pack of W = w_host[n_out][K1 + K2] that family reads - `kind` MCG_GEMM_PACK4 (float elements:
+ * mcg_gemm_launch / mcg_gemm16_launch), MCG_GEMM_PACK16 (uint16 bf16 bits: mcg_gemm_bf16_launch) or MCG_GEMM_PACK16X3
+ * (uint16: mcg_gemm_x6_launch) - segment 1 (columns 0 .. K1-1) followed by segment 2, rows >= n_out zero.  *n_elems_host
+ * receives the element count; dst_host (NULL = count only) must hold dst_capacity >= that many elements. */
+int mcg_debug_gemm_pack(const float* w_host, int n_out, int K1, int K2, int kind, void* dst_host, int64_t dst_capacity,
+                        int64_t* n_elems_host);
+
 /* ---- Batch plan.  Replaces the per-call `get_adj_matrix` edge-list rebuild (egnn.py:475,515-541)
  * and the node/edge masks (mol_utils.py:226-252): node_mask[b] is the prefix of n_nodes_host[b]
  * ones, edge_mask = outer product minus diagonal.  edge_mt: 0 = auto, 1 = 16-row edge tiles (exact-fp32 kernels,

@@ -25,6 +25,8 @@ SIGNATURES: Dict[str, tuple] = {
     "mcg_egnn_set_precision": (_i, [_vp, _i]),
     "mcg_egnn_set_option": (_i, [_vp, _i, _i]),
     "mcg_debug_gemm_launches": (_i, [_vp, _i]),
+    "mcg_debug_gemm": (_i, [_vp, _vp, _vp]),
+    "mcg_debug_gemm_pack": (_i, [_vp, _i, _i, _i, _i, _vp, C.c_int64, _vp]),
     "mcg_plan_create": (_i, [_i, _i, _vp, _i, _pp]),
     "mcg_plan_create_ex": (_i, [_i, _i, _vp, _vp, _pp]),
     "mcg_plan_destroy": (None, [_vp]),
@@ -73,6 +75,23 @@ class PlanOpts(C.Structure):
     _fields_ = [("edge_mt", C.c_int32), ("n_ranges", C.c_int32), ("four_tile_units", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+class GemmDesc(C.Structure):
+    """`mcg_gemm_desc` (include/mlconfgen_hip.h): one node-GEMM launch of `mcg_debug_gemm`; zero-initialised = unused."""
+    _fields_ = ([(n, C.c_void_p) for n in ("A1", "A2", "bias", "resid", "C", "a2_rows", "side_u", "side_slots", "side_x", "w_host")]
+                + [(n, C.c_int64) for n in ("a1_floats", "a2_floats", "resid_floats", "c_floats")]
+                + [(n, C.c_int32) for n in ("lda1", "lda2", "ldr", "ldc", "M", "K1", "K2", "n_out", "n_store", "act", "a2_nsum",
+                                            "a2_src_rows", "side_M", "side_u_rows", "c_blocked", "family", "rn", "mr", "deep", "lds")]
+                + [("reserved", C.c_int32 * 4)])
+
+
+class GemmRan(C.Structure):
+    """`mcg_gemm_ran`: the kernel template (GEMM_KERNEL_*) and template arguments `mcg_debug_gemm` ran."""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "rn", "mr", "ring", "gather", "resid", "seg2", "reserved")]
+
+
+GEMM_F32, GEMM_F32ROWS16, GEMM_BF16, GEMM_X6 = 0, 1, 2, 3                    # mcg_gemm_desc.family
+GEMM_KERNEL_F32, GEMM_KERNEL_F32ROWS16, GEMM_KERNEL_BF16, GEMM_KERNEL_BF16_LDS, GEMM_KERNEL_X6 = 1, 2, 3, 4, 5
+GEMM_PACK4, GEMM_PACK16, GEMM_PACK16X3 = 0, 1, 2
 ALL_FOUR_TILE = 0x3fffffff          # MCG_ALL_FOUR_TILE
 OPT_X6_GEMM, OPT_GEMM_RN, OPT_GEMM_X6_RN, OPT_GEMM_BF16_LDS, OPT_NODE_FUSED = 1, 2, 3, 4, 5
 

@@ -9,6 +9,7 @@
 // the 16-byte load of 4 consecutive k of its A row (k permutation: mcg_common.h).
 #pragma once
 #include "mcg_common.h"
+#include "../../include/mlconfgen_hip.h"
 
 #include <vector>
 
@@ -19,7 +20,8 @@ struct McgGemmArgs {
     const float* A2; int lda2; int K2;      // optional second segment (concat along K), K2 may be 0
     const float* Bp;                        // B-pack4 of segment 1 followed by B-pack4 of segment 2
     const float* bias;                      // [n_tiles*16] (padded) or nullptr
-    const float* resid; int ldr;            // optional residual added after activation
+    const float* resid; int ldr;            // optional residual added after activation; ONLY with n_store % 4 == 0: the kernels load it in
+                                            // 16-byte pieces and a ragged last piece would lose it (the launchers refuse the combination)
     float* C; int ldc;
     int M; int n_tiles; int n_store;        // columns >= n_store are not written
     int act;
@@ -30,7 +32,8 @@ struct McgGemmArgs {
     // x[v][0..2] += (side_u[s.x] + side_u[s.y] + side_u[s.z] + side_u[s.w]) / 100 - the coordinate update of the previous block (egnn.py:128-148)
     const float* side_u; const int4* side_slots; float* side_x; int side_M;
     int gemm_blocks;                        // workgroups of the GEMM proper (set by the launcher)
-    // bf16 kernels only: C is the BLOCKED layer-1 input layout of the bf16 edge kernel, C[part][k-block][piece][row][4] with
+    // mcg_gemm_launch and mcg_gemm_bf16_launch only (the 16-row and split-operand launchers refuse it), and only with n_tiles == 54
+    // (two parts of 27 column tiles): C is the BLOCKED layer-1 input layout of the bf16 edge kernel, C[part][k-block][piece][row][4] with
     // column = part * 432 + 32 * k-block + 4 * piece + (0..3): a 16-byte piece of 16 consecutive rows is 256 contiguous bytes,
     // so the 16 rows (i, j .. j+15) of an edge tile read their gathered half with ADJACENT LANES ON ADJACENT ADDRESSES
     // (mcg_edge_bf16.hip, BLK; tools/native/gather_probe.hip: 88 ns instead of 224 per instruction and wave)
@@ -121,7 +124,17 @@ struct McgNodeFusedArgs {
 };
 constexpr int MCG_NF_MIN_ROWBLOCKS = 32;        // automatic choice of the fused node launch: from 32 row blocks (1 024 atoms) on
 
-// Launchers (each returns hipGetLastError(); M <= 0 launches nothing).  `rn_override` 1..3 fixes the wave tile width
+// The template instantiation a launcher dispatched: the kernel and its template arguments (0 where the template has none).
+struct McgGemmRan { int kernel /* MCG_GEMM_KERNEL_* (mlconfgen_hip.h) */, rn, mr, ring, gather, resid, seg2; };
+const McgGemmRan& mcg_gemm_last_launch();      // of the calling thread (mcg_debug_gemm)
+
+// What no kernel implements and every launcher refuses: a residual on a ragged right edge (n_store % 4 != 0), and the blocked C
+// layout outside the kernels that store through mcg_gemm_c_ptr (`blocked_ok`: mcg_gemm_launch, mcg_gemm_bf16_launch) or with
+// another width than its 2 x 27 column tiles.
+bool mcg_gemm_out_of_contract(const McgGemmArgs& a, bool blocked_ok);
+
+// Launchers (each returns hipGetLastError(); M <= 0 launches nothing; hipErrorInvalidValue, nothing launched, for a residual with
+// n_store % 4 != 0 and for c_blocked where it is not implemented).  `rn_override` 1..3 fixes the wave tile width
 // (MCG_OPT_GEMM_RN / MCG_OPT_GEMM_X6_RN), 0 = the launcher's cost model.  A launcher whose kernel carries the coordinate-update
 // side job (side_x set) adds its workgroups behind the GEMM's own.
 hipError_t mcg_gemm_launch(McgGemmArgs a, int rn_override, hipStream_t s);               // fp32, 32-row wave tiles

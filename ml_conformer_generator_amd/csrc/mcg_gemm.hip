@@ -7,6 +7,11 @@
 // [family 0: 32-row fp32, 1: 32-row bf16 (slot 6: fused node kernel, 7: LDS-staged kernel), 2: 16-row-tile fp32, 3: split-operand][rn 0..7]
 extern "C" void mcg_count_gemm_launch(int family, int rn);
 
+// The instantiation the calling thread's last launcher call dispatched (mcg_debug_gemm reports it; one thread-local store
+// per launch on the host, nothing on the device).
+static thread_local McgGemmRan g_last_launch{};
+const McgGemmRan& mcg_gemm_last_launch() { return g_last_launch; }
+
 // ---------------------------------------------------------------------------------------------
 // bf16 mode, large batches: the node phase of ONE GCL layer in ONE launch (round 6, mcg_node_fused_bf16_kernel).
 //
@@ -286,6 +291,7 @@ int gather_rows(const McgGemmArgs& a) { return (a.a2_rows != nullptr && a.K2 > 0
 
 template <int RN, int MR, int RING>
 void launch16(const McgGemmArgs& a, int gather, dim3 grid, hipStream_t s) {
+    g_last_launch = McgGemmRan{MCG_GEMM_KERNEL_F32ROWS16, RN, MR, RING, gather, 0, 0};
     switch (gather) {
         case 4: hipLaunchKernelGGL((mcg_gemm16_kernel<RN, 4, MR, RING>), grid, dim3(256), 0, s, a); break;
         case 3: hipLaunchKernelGGL((mcg_gemm16_kernel<RN, 3, MR, RING>), grid, dim3(256), 0, s, a); break;
@@ -296,6 +302,7 @@ void launch16(const McgGemmArgs& a, int gather, dim3 grid, hipStream_t s) {
 
 template <int RN>
 void launch_bf16(const McgGemmArgs& a, dim3 grid, hipStream_t s) {
+    g_last_launch = McgGemmRan{MCG_GEMM_KERNEL_BF16, RN, 0, 0, gather_rows(a), 0, 0};
     switch (gather_rows(a)) {
         case 4: hipLaunchKernelGGL((mcg_gemm_bf16_kernel<RN, 4>), grid, dim3(256), 0, s, a); break;
         case 2: hipLaunchKernelGGL((mcg_gemm_bf16_kernel<RN, 2>), grid, dim3(256), 0, s, a); break;
@@ -306,6 +313,7 @@ void launch_bf16(const McgGemmArgs& a, dim3 grid, hipStream_t s) {
 // (ring depth 3: 4 / 6 stages measured no gain / spills at the 256-ragged shape - the K loop is not what these launches wait for)
 template <int GATHER, bool SEG2>
 void launch_lds(const McgGemmArgs& a, dim3 grid, hipStream_t s) {
+    g_last_launch = McgGemmRan{MCG_GEMM_KERNEL_BF16_LDS, 0, 0, 3, GATHER, a.resid ? 1 : 0, SEG2 ? 1 : 0};
     if (a.resid) hipLaunchKernelGGL((mcg_gemm_bf16_lds_kernel<GATHER, true, SEG2, 3>), grid, dim3(MCG_LDSG_THREADS), 0, s, a);
     else hipLaunchKernelGGL((mcg_gemm_bf16_lds_kernel<GATHER, false, SEG2, 3>), grid, dim3(MCG_LDSG_THREADS), 0, s, a);
 }
@@ -326,6 +334,10 @@ bool bf16_lds_fits(const McgGemmArgs& a) {
 
 }  // namespace
 
+bool mcg_gemm_out_of_contract(const McgGemmArgs& a, bool blocked_ok) {
+    return (a.resid && a.n_store % 4 != 0) || (a.c_blocked && (!blocked_ok || a.n_tiles != 54));
+}
+
 // Wave tile width RN in {1,2,3} from a measured cost model (tools/native/gemm_bench.hip, MI355X; us of loop time per wave and
 // per 420 of K): with at most one wave per SIMD a wave costs u1[RN]; with many waves per SIMD the SIMD retires one wave per
 // uinf[RN] (the 3-wide tile degrades most when waves share a SIMD).  cost = u1 for r <= 1, else max(ceil(r) * u1, r * uinf),
@@ -333,6 +345,7 @@ bool bf16_lds_fits(const McgGemmArgs& a) {
 // "rounds x RN" rule picked RN = 3 at config 3: 80 us instead of 62 us for the Pab GEMM).
 hipError_t mcg_gemm_launch(McgGemmArgs a, int rn_override, hipStream_t s) {
     if (a.M <= 0) return hipSuccess;
+    if (mcg_gemm_out_of_contract(a, true)) return hipErrorInvalidValue;
     const int rowblocks = (a.M + 31) / 32;
     static const double u1[4] = {0, 3.4, 5.2, 9.0}, uinf[4] = {0, 4.8, 8.0, 12.5};
     int rn = 1;
@@ -348,6 +361,7 @@ hipError_t mcg_gemm_launch(McgGemmArgs a, int rn_override, hipStream_t s) {
     a.gemm_blocks = (int)(((long)rowblocks * ((a.n_tiles + rn - 1) / rn) + 3) / 4);
     const dim3 grid((unsigned)a.gemm_blocks + side_blocks(a, 256));
     mcg_count_gemm_launch(0, rn);
+    g_last_launch = McgGemmRan{MCG_GEMM_KERNEL_F32, rn, 0, 3, 0, 0, 0};
     if (rn == 3) hipLaunchKernelGGL(mcg_gemm_kernel<3>, grid, dim3(256), 0, s, a);
     else if (rn == 2) hipLaunchKernelGGL(mcg_gemm_kernel<2>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(mcg_gemm_kernel<1>, grid, dim3(256), 0, s, a);
@@ -360,6 +374,7 @@ hipError_t mcg_gemm_launch(McgGemmArgs a, int rn_override, hipStream_t s) {
 // shared by the groups in flight: three in flight cost ~200 ns per group, eight ~75.  Same k order: bit-identical results.
 hipError_t mcg_gemm16_launch(McgGemmArgs a, int rn, int mr, bool deep, hipStream_t s) {
     if (a.M <= 0) return hipSuccess;
+    if (mcg_gemm_out_of_contract(a, false)) return hipErrorInvalidValue;
     // the EFFECTIVE tile shape - the one an instantiation exists for - sizes the grid: a width the kernel was not built
     // with would leave the kernel's wave_cols and the grid disagreeing (output columns silently unwritten)
     mr = mr == 2 ? 2 : 1;
@@ -379,6 +394,7 @@ hipError_t mcg_gemm16_launch(McgGemmArgs a, int rn, int mr, bool deep, hipStream
 
 hipError_t mcg_gemm_bf16_launch(McgGemmArgs a, int rn_override, int lds, hipStream_t s) {
     if (a.M <= 0) return hipSuccess;
+    if (mcg_gemm_out_of_contract(a, true)) return hipErrorInvalidValue;
     const int rowblocks = (a.M + 31) / 32;
     if (lds != 1 && bf16_lds_fits(a) && (lds == 2 || rowblocks >= MCG_LDSG_MIN_ROWBLOCKS)) {
         a.gemm_blocks = rowblocks * ((a.n_tiles + MCG_LDSG_TILES - 1) / MCG_LDSG_TILES);
@@ -409,12 +425,14 @@ hipError_t mcg_gemm_bf16_launch(McgGemmArgs a, int rn_override, int lds, hipStre
 
 hipError_t mcg_gemm_x6_launch(const McgGemmArgs& a, int rn_override, hipStream_t s) {
     if (a.M <= 0) return hipSuccess;
+    if (mcg_gemm_out_of_contract(a, false)) return hipErrorInvalidValue;
     const int rowblocks = (a.M + 31) / 32;
     int rn = a.M > 4096 ? 2 : 1;          // measured: RN = 1 at config 2 (3.43 vs 3.66 ms per call for RN = 3), RN = 2 at config 3
     if (rn_override >= 1 && rn_override <= 3) rn = rn_override;
     const int wave_cols = (a.n_tiles + rn - 1) / rn;
     const dim3 grid((unsigned)(rowblocks * ((wave_cols + 3) / 4)));
     mcg_count_gemm_launch(3, rn);
+    g_last_launch = McgGemmRan{MCG_GEMM_KERNEL_X6, rn, 0, 0, 0, 0, 0};
     if (rn == 3) hipLaunchKernelGGL(mcg_gemm_x6_kernel<3>, grid, dim3(256), 0, s, a);
     else if (rn == 2) hipLaunchKernelGGL(mcg_gemm_x6_kernel<2>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(mcg_gemm_x6_kernel<1>, grid, dim3(256), 0, s, a);
