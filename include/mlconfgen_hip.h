@@ -447,6 +447,29 @@ int mcg_receptor_overlap(const float* lig_xyz, const float* lig_radius, const in
                          const float* rec_xyz, const float* rec_radius, int R, int splits, float* partial_ws,
                          float* overlap_out, void* stream);
 
+/* ---- Chemical fingerprints ("Chemical fingerprints"): a circular, Morgan-type fingerprint (radius
+ * 2, 2 048 bits, bond types on, chirality off) and a graph identity key of B molecular graphs.  The definition is this
+ * package's own (DESIGN.md states it in full): a SUBSTITUTE for RDKit's Morgan fingerprint, not bit-compatible with it.
+ *   mcg_graph_fingerprint: z[B,W] atomic numbers, bonds[B,W,W] symmetric bond codes (0 none / 1 / 2 / 3 / 4 aromatic),
+ *                          n_nodes_dev[b] real atoms (device memory, clamped to [0, W] on the device; the diagonal and
+ *                          everything at or beyond n_b is ignored, whatever it holds).  fp_out[B, MCG_FP_WORDS]: bit k in
+ *                          word k >> 5 at position k & 31; key_out[B]: the 64-bit graph key - equal for isomorphic graphs
+ *                          (the converse can fail: graphs colour refinement cannot tell apart, or a hash collision);
+ *                          popcount_out[B] (optional, NULL = not wanted): the set bits.  One 64-lane workgroup per
+ *                          molecule; integer arithmetic only, so every output has the same bits whatever the batch, the
+ *                          row and the padded width, and fingerprint and key do not depend on the atom numbering.
+ *   mcg_fingerprint_tanimoto:      out[b] = T(fp[b], ref_fp), ref_fp[MCG_FP_WORDS].
+ *   mcg_fingerprint_pair_tanimoto: out[B,B], row-major: T(fp[i], fp[j]); exactly symmetric, diagonal exactly 1.
+ *   T(A, B) = float(c) / float(u), c = popcount(A & B), u = popcount(A | B), one correctly rounded fp32 division; NaN
+ *   where A or B has no bit set (a molecule without atoms: its whole row and column), the other entries unaffected.
+ * B = 0 launches nothing.  MCG_ERR_ARG, nothing launched: a null required buffer, B < 0, W outside 1..64, B above
+ * MCG_SHAPE_PAIR_MAX_B (pair matrix). */
+#define MCG_FP_WORDS 64
+int mcg_graph_fingerprint(const int32_t* z, const int8_t* bonds, const int32_t* n_nodes_dev, int B, int W,
+                          uint32_t* fp_out, uint64_t* key_out, int32_t* popcount_out, void* stream);
+int mcg_fingerprint_tanimoto(const uint32_t* fp, const uint32_t* ref_fp, int B, float* out, void* stream);
+int mcg_fingerprint_pair_tanimoto(const uint32_t* fp, int B, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,8 +8,10 @@ without the built library raises.
 from .config import (ATOM_DECODER, CONTEXT_NORMS, DIMENSION, MAX_N_NODES,
                      MIN_N_NODES, NUM_BOND_TYPES)
 
+_FINGERPRINT = ("graph_fingerprints", "fingerprint_tanimoto", "pairwise_fingerprint_tanimoto", "mol_graph", "select_unique")
+
 __all__ = ["MLConformerGenerator", "evaluate_samples", "ATOM_DECODER", "CONTEXT_NORMS", "DIMENSION",
-           "MAX_N_NODES", "MIN_N_NODES", "NUM_BOND_TYPES"]
+           "MAX_N_NODES", "MIN_N_NODES", "NUM_BOND_TYPES", *_FINGERPRINT]
 
 
 def __getattr__(name):
@@ -20,4 +22,7 @@ def __getattr__(name):
     if name == "evaluate_samples":
         from .cheminformatics import evaluate_samples
         return evaluate_samples
+    if name in _FINGERPRINT:             # chemical fingerprints and graph keys (fingerprint.py: a substitute for RDKit's)
+        from . import fingerprint
+        return getattr(fingerprint, name)
     raise AttributeError(name)

@@ -504,23 +504,31 @@ def check_max_pairwise_tanimoto(value) -> float:
 
 
 def select_diverse(scores: List[float], sample_ids: List[int], pair, max_pairwise_tanimoto: Optional[float],
-                   top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None) -> List[int]:
+                   top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None, chemical_pair=None,
+                   max_pairwise_chemical_tanimoto: Optional[float] = None) -> List[int]:
     """Positions of the molecules to keep, by sphere exclusion in ranking order: the molecules scoring >=
     `min_shape_tanimoto`, walked in descending score order (ties: the lower sample id; a NaN score ranks last and passes
     no threshold); a molecule is kept unless its `pair` Tanimoto with an already kept molecule is >=
     `max_pairwise_tanimoto` (a NaN pair entry excludes nothing); then the first `top_k`.  `pair[i][j]`: the [B,B] pair
     matrix over the same positions as `scores` (`pairwise_shape_tanimoto`; any array-like), not read when
-    `max_pairwise_tanimoto` is None, which gives the plain ranking selection (`select_scored`)."""
+    `max_pairwise_tanimoto` is None, which gives the plain ranking selection (`select_scored`).
+    `chemical_pair` / `max_pairwise_chemical_tanimoto`: a second pair matrix (`fingerprint.pairwise_fingerprint_tanimoto`)
+    and threshold in the same walk; with both given a molecule is excluded if EITHER matrix reaches its threshold
+    against an already kept molecule.  A score of None (a call that does not score shape) ranks like every other None:
+    the walk is then in sample-id order."""
     keep = [i for i, s in enumerate(scores) if min_shape_tanimoto is None or s >= min_shape_tanimoto]
-    keep.sort(key=lambda i: (-scores[i] if scores[i] == scores[i] else math.inf, sample_ids[i]))
-    if max_pairwise_tanimoto is not None:
+    keep.sort(key=lambda i: (0.0 if scores[i] is None else -scores[i] if scores[i] == scores[i] else math.inf,
+                             sample_ids[i]))
+    walks = [(m, t) for m, t in ((pair, max_pairwise_tanimoto), (chemical_pair, max_pairwise_chemical_tanimoto))
+             if t is not None]
+    if walks:
         import numpy as np
-        p = np.asarray(pair.cpu() if torch.is_tensor(pair) else pair, dtype=np.float64)    # fp32 entries, exactly
+        walks = [(np.asarray(m.cpu() if torch.is_tensor(m) else m, dtype=np.float64), t) for m, t in walks]  # fp32 entries, exactly
         kept: List[int] = []
         for i in keep:
             if top_k is not None and len(kept) >= top_k:
                 break                        # later molecules cannot change what is already kept
-            if not kept or not bool((p[i, kept] >= max_pairwise_tanimoto).any()):
+            if not kept or not any(bool((p[i, kept] >= t).any()) for p, t in walks):
                 kept.append(i)
         keep = kept
     return keep if top_k is None else keep[:top_k]

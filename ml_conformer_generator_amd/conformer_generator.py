@@ -48,7 +48,12 @@ forced by the scope of this build:
     strictly better (`cheminformatics.shape_overlay(refine_steps=...)`).  Off by default: nothing changes;
   * `receptor`, `max_receptor_clashes` (opt-in, every generation entry, with `overlay`): the steric contacts of every
     posed molecule with the receptor the reference ligand came from, measured on the GPU (`receptor.receptor_overlap`),
-    and a filter on the number of clashing atoms.  Off by default: nothing changes.
+    and a filter on the number of clashing atoms.  Off by default: nothing changes;
+  * `chemical_scores`, `reference_graph`, `max_chemical_tanimoto`, `unique`, `max_pairwise_chemical_tanimoto` (opt-in,
+    every generation entry): the chemical half of `evaluate_samples`, RDKit-free - every returned molecule's chemical
+    fingerprint and graph identity key computed on the GPU (`fingerprint.py`: the package's own Morgan-type
+    fingerprint, a labelled SUBSTITUTE for RDKit's, not bit-compatible with it), its Tanimoto to the reference's graph,
+    a filter on it, one molecule per graph, and a chemically diverse selection.  Off by default: nothing changes.
 """
 from __future__ import annotations
 
@@ -75,6 +80,7 @@ from . import distributed as mcg_dist
 from . import host_pool
 from . import rdkit_order
 from . import receptor as mcg_receptor
+from . import fingerprint as mcg_fp
 from .handoff import (GeneratedMolecule, assemble_molecules, bond_writeback_hip, molecules_from_tensors,
                       prepare_adj_mat_seer_input_hip)
 from .mol_utils import (get_context_shape, ifm_get_xh_from_fragment, ifm_merge_hip,
@@ -134,6 +140,21 @@ class _ShapeRequest:
     refine_steps: int = 0                         # `refine_overlay`: ascent steps of the refined pose, 0 = not refined
     receptor: Optional[tuple] = None              # (coords [R,3] fp32, atomic numbers [R]) of its heavy atoms, host
     max_receptor_clashes: Optional[int] = None
+
+
+@dataclasses.dataclass(frozen=True)
+class _ChemRequest:
+    """The chemical options of one generation call (`MLConformerGenerator._chem_request`)."""
+    ref_graph: Optional[tuple]                    # (atomic numbers, bond codes [n,n] int8) of the reference, when it scores
+    scoring: bool                                 # `chemical_scores`, or implied by `max_chemical_tanimoto`
+    max_chemical_tanimoto: Optional[float]
+    unique: bool
+    max_pairwise_chemical_tanimoto: Optional[float]
+
+
+def _ranking_key(score: Optional[float], sample_id: int):
+    """`select_diverse`'s order: descending score, ties to the lower sample id, NaN last; unscored: the sample id."""
+    return (0.0 if score is None else -score if score == score else float("inf"), sample_id)
 
 
 class MLConformerGenerator(torch.nn.Module):
@@ -401,6 +422,81 @@ class MLConformerGenerator(torch.nn.Module):
                              f"{cheminformatics.MAX_REFINE_STEPS}, got {refine_overlay!r}")
         return int(k)
 
+    def _chem_request(self, reference_conformer, chemical_scores=False, reference_graph=None,
+                      max_chemical_tanimoto: Optional[float] = None, unique=False,
+                      max_pairwise_chemical_tanimoto: Optional[float] = None) -> Optional[_ChemRequest]:
+        """The call's chemical options, or None when it asked for none of them (`max_chemical_tanimoto` implies the
+        score).  Every refusal happens here, before any device work."""
+        mcg_fp.check_flag("chemical_scores", chemical_scores)
+        mcg_fp.check_flag("unique", unique)
+        if max_chemical_tanimoto is not None:
+            mcg_fp.check_threshold("max_chemical_tanimoto", max_chemical_tanimoto)
+        if max_pairwise_chemical_tanimoto is not None:
+            mcg_fp.check_threshold("max_pairwise_chemical_tanimoto", max_pairwise_chemical_tanimoto)
+        scoring = chemical_scores or max_chemical_tanimoto is not None
+        if reference_graph is not None and not scoring:
+            raise ValueError("reference_graph is only read with chemical_scores or max_chemical_tanimoto")
+        if not (scoring or unique or max_pairwise_chemical_tanimoto is not None):
+            return None
+        if isinstance(getattr(self, "finisher", None), host_pool.TaskRef):
+            raise ValueError("chemical scores cannot be combined with a custom finisher: its results carry no graph this "
+                             "package can read")
+        graph = None
+        if scoring:
+            src = reference_graph
+            if src is None and hasattr(reference_conformer, "GetAtoms") and hasattr(reference_conformer, "GetBonds"):
+                src = reference_conformer
+            if src is None:
+                raise ValueError("chemical scores need the reference's molecular graph: pass reference_graph= (a Mol, a "
+                                 "GeneratedMolecule or an (atomic_numbers, bond_orders) pair) or a reference conformer "
+                                 "with bonds; coordinates and a bare reference_context have none")
+            graph = mcg_fp.mol_graph(src)
+            if not 1 <= len(graph[0]) <= mcg_fp.MAX_GRAPH_ATOMS:
+                raise ValueError(f"the reference graph must have 1 to {mcg_fp.MAX_GRAPH_ATOMS} heavy atoms, got "
+                                 f"{len(graph[0])}")
+        return _ChemRequest(graph, bool(scoring), max_chemical_tanimoto, bool(unique), max_pairwise_chemical_tanimoto)
+
+    # device seams of the chemical step (stubbed by the host tests)
+    def _graph_fingerprints(self, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor):
+        """(fingerprint [B,64] int32, graph key [B] int64, set bits [B]) of padded graphs (`fingerprint.graph_fingerprints`,
+        unchecked: the codes come from the bond write-back or from `mol_graph`)."""
+        return mcg_fp.graph_fingerprints(atomic_numbers, bond_orders, n_nodes, self.device, check=False)
+
+    def _chem_tanimoto(self, fp: torch.Tensor, ref_fp: torch.Tensor) -> torch.Tensor:
+        """Tanimoto [B] of fingerprints against the reference's (`fingerprint.fingerprint_tanimoto`)."""
+        return mcg_fp.fingerprint_tanimoto(fp, ref_fp)
+
+    def _chem_pair(self, fp: torch.Tensor) -> torch.Tensor:
+        """[B,B] pairwise Tanimoto of fingerprints (`fingerprint.pairwise_fingerprint_tanimoto`)."""
+        return mcg_fp.pairwise_fingerprint_tanimoto(fp)
+
+    def _chem_graphs(self, chem: _ChemRequest, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
+                     n_nodes: torch.Tensor):
+        """The chemical step of padded graphs, one fingerprint launch: (fingerprints [B,64], graph keys [B] int64,
+        chemical Tanimoto [B] to the reference's graph or None when the call does not score)."""
+        fp, key, _ = self._graph_fingerprints(atomic_numbers, bond_orders, n_nodes)
+        sim = None
+        if chem.scoring:
+            ref_fp = self._graph_fingerprints(*mcg_fp.pad_graphs([chem.ref_graph]))[0][0]
+            sim = self._chem_tanimoto(fp, ref_fp.to(fp.device))
+        return fp, key, sim
+
+    @staticmethod
+    def _chem_filter(chem: Optional[_ChemRequest], sims: List, keys: List, scores: List, sample_ids: List[int]
+                     ) -> List[int]:
+        """Positions that pass the call's chemical filters, in the input's order: `max_chemical_tanimoto` (a similarity
+        >= the value, or NaN, does not pass), then `unique` - of the molecules with one graph key the first in ranking
+        order (`_ranking_key`: by shape score where the call scores shape, else the lowest sample id)."""
+        pos = list(range(len(sample_ids)))
+        if chem is None:
+            return pos
+        if chem.max_chemical_tanimoto is not None:
+            pos = [i for i in pos if sims[i] < chem.max_chemical_tanimoto]
+        if chem.unique:
+            order = sorted(pos, key=lambda i: _ranking_key(scores[i], sample_ids[i]))
+            pos = mcg_fp.select_unique(keys, order)
+        return pos
+
     # device seams of the shape step (stubbed by the host tests)
     def _score_coords(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
         """Shape Tanimoto [B] (device) of padded heavy-atom coordinates against the reference."""
@@ -507,22 +603,34 @@ class MLConformerGenerator(torch.nn.Module):
         return [i for i, c in enumerate(contacts) if c is not None and c[0] <= req.max_receptor_clashes]
 
     @staticmethod
-    def _select(req: Optional[_ShapeRequest], mols: List, scores: List[float], sample_ids: List[int], pair_fn) -> List:
+    def _select(req: Optional[_ShapeRequest], mols: List, scores: List[float], sample_ids: List[int], pair_fn,
+                chem: Optional[_ChemRequest] = None, chem_pair_fn=None) -> List:
         """`mols` through the call's selection: threshold, then sphere exclusion at `max_pairwise_tanimoto` (`pair_fn()`:
-        the pair matrix of `mols`, only called when it is set), then `top_k` (`cheminformatics.select_diverse`); all of
-        them when the call selects nothing."""
-        if req is None or (req.top_k is None and req.min_shape_tanimoto is None and req.max_pairwise_tanimoto is None):
+        the pair matrix of `mols`, only called when it is set) and at `max_pairwise_chemical_tanimoto` (`chem_pair_fn()`,
+        likewise) in one walk, then `top_k` (`cheminformatics.select_diverse`); all of them when the call selects
+        nothing."""
+        shape_sel = req is not None and not (req.top_k is None and req.min_shape_tanimoto is None
+                                             and req.max_pairwise_tanimoto is None)
+        chem_t = None if chem is None else chem.max_pairwise_chemical_tanimoto
+        if not shape_sel and chem_t is None:
             return mols
-        pair = pair_fn() if req.max_pairwise_tanimoto is not None else None
-        keep = cheminformatics.select_diverse(scores, sample_ids, pair, req.max_pairwise_tanimoto, req.top_k,
-                                              req.min_shape_tanimoto)
+        pair_t = req.max_pairwise_tanimoto if shape_sel else None
+        keep = cheminformatics.select_diverse(scores, sample_ids, pair_fn() if pair_t is not None else None, pair_t,
+                                              req.top_k if shape_sel else None,
+                                              req.min_shape_tanimoto if shape_sel else None,
+                                              chem_pair_fn() if chem_t is not None else None, chem_t)
         return [mols[i] for i in keep]
 
     def _return_records(self, req: Optional[_ShapeRequest], res: dict, row_ids: Optional[torch.Tensor],
-                        optimise_geometry: bool) -> List:
+                        optimise_geometry: bool, chem: Optional[_ChemRequest] = None) -> List:
         """What a call returns without a finisher: the `GeneratedMolecule` records of the rows this rank returns (sample
-        ids `row_ids`, default 0..B-1; one D2H), filtered by the validity proxy, then selected, the pair matrix taken
-        from the posed rows."""
+        ids `row_ids`, default 0..B-1; one D2H), filtered by the validity proxy, the clash filter and the chemical
+        filters (fingerprints of the rows this rank returns: one launch behind the gather), then selected, the pair
+        matrices taken from the posed rows and from their fingerprints."""
+        chem_kw, fp = {}, None
+        if chem is not None:
+            fp, key, sim = self._chem_graphs(chem, res["elements"], res["bond"], res["n_nodes"])
+            chem_kw = dict(chemical_tanimoto=sim, graph_key=key if chem.scoring or chem.unique else None)
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)       # (the D2H copies below would wait for the device anyway: keep that out of the figure)
         t0 = time.perf_counter()
@@ -530,25 +638,38 @@ class MLConformerGenerator(torch.nn.Module):
                                       sample_ids=row_ids, shape_tanimoto=res.get("shape_tanimoto"),
                                       overlay_tanimoto=res.get("overlay_tanimoto"), pose=res.get("pose"),
                                       receptor_clashes=res.get("receptor_clashes"),
-                                      receptor_max_overlap=res.get("receptor_max_overlap"))
+                                      receptor_max_overlap=res.get("receptor_max_overlap"), **chem_kw)
         self.last_host_assembly_ms = (time.perf_counter() - t0) * 1e3      # D2H of the result tensors + record views
         kept, self.last_valid_fraction = _finish(mols, optimise_geometry, use_rdkit=False)    # no finisher: the proxy
         kept = [kept[i] for i in self._clash_filter(req, kept, [m.receptor_contacts for m in kept])]
+        if chem is not None:                          # a record view knows its row of the batch (`_b`)
+            keys = key.cpu().tolist() if chem.unique else None
+            kept = [kept[i] for i in self._chem_filter(chem, [m.chemical_tanimoto for m in kept],
+                                                       [keys[m._b] for m in kept] if chem.unique else None,
+                                                       [m.shape_tanimoto for m in kept], [m.sample_id for m in kept])]
 
         def pair():
             row = {id(m): b for b, m in enumerate(mols)}
             idx = torch.tensor([row[id(m)] for m in kept], dtype=torch.long, device=res["x"].device)
             return self._pair_coords(req.ref_coord, res["x"].index_select(0, idx),
                                      res["n_nodes"].reshape(-1).to(res["x"].device).index_select(0, idx))
-        return self._select(req, kept, [m.shape_tanimoto for m in kept], [m.sample_id for m in kept], pair)
+
+        def chem_pair():
+            return self._chem_pair(fp.index_select(0, torch.tensor([m._b for m in kept], dtype=torch.long,
+                                                                   device=fp.device)))
+        return self._select(req, kept, [m.shape_tanimoto for m in kept], [m.sample_id for m in kept], pair, chem,
+                            chem_pair)
 
     def _return_objects(self, req: Optional[_ShapeRequest], done: List, scores: List, poses: List, contacts: List,
-                        row_ids: Optional[torch.Tensor], sample_seed: Optional[int]) -> List:
+                        row_ids: Optional[torch.Tensor], sample_seed: Optional[int],
+                        chem: Optional[_ChemRequest] = None) -> List:
         """What a call returns through a finisher: the finished Mols of the rows this rank returns (None = dropped; sample
         ids `row_ids`, default 0..B-1) get their properties - `sample_id` (seeded calls), `overlay_tanimoto`,
         `shape_tanimoto`, `receptor_clashes`, `receptor_max_overlap`: set here, behind the object gather, which does not
         carry Mol properties - then the live ones pass the clash filter and are selected, the pair matrix taken from
-        their posed heavy atoms."""
+        their posed heavy atoms.  The chemical step reads the finished Mols' own graphs (`fingerprint.mol_graph`), all in
+        one batched device call: double property `chemical_tanimoto`, string property `graph_key` (the unsigned 64-bit
+        key in decimal: it does not fit an int property)."""
         from . import rdkit_finish
         ids = list(range(len(done))) if row_ids is None else row_ids.tolist()
         if sample_seed is not None:
@@ -559,10 +680,30 @@ class MLConformerGenerator(torch.nn.Module):
         rdkit_finish.tag_scores(done, "overlay_tanimoto", [None if p is None else p[0] for p in poses])
         rdkit_finish.tag_scores(done, "shape_tanimoto", scores)
         rdkit_finish.tag_contacts(done, contacts)
+        fp = None
+        if chem is not None and live:
+            fp, key, sim = self._chem_graphs(chem, *mcg_fp.pad_graphs([mcg_fp.mol_graph(done[i]) for i in live]))
+            fp_row = {i: k for k, i in enumerate(live)}
+            keys = [int(k) & 0xFFFFFFFFFFFFFFFF for k in key.cpu().tolist()]
+            sims = [None] * len(live) if sim is None else [float(v) for v in sim.cpu().tolist()]
+            if chem.scoring:
+                rdkit_finish.tag_scores([done[i] for i in live], "chemical_tanimoto", sims)
+            if chem.scoring or chem.unique:
+                rdkit_finish.tag_graph_keys([done[i] for i in live], keys)
         live = [live[i] for i in self._clash_filter(req, live, [contacts[i] for i in live])]
+        if fp is not None:
+            live = [live[i] for i in self._chem_filter(chem, [sims[fp_row[i]] for i in live],
+                                                       [keys[fp_row[i]] for i in live], [scores[i] for i in live],
+                                                       [ids[i] for i in live])]
         picked = [done[i] for i in live]
+
+        def chem_pair():
+            if fp is None:                        # nothing left to compare
+                return torch.zeros(0, 0)
+            return self._chem_pair(fp.index_select(0, torch.tensor([fp_row[i] for i in live], dtype=torch.long,
+                                                                   device=fp.device)))
         return self._select(req, picked, [scores[i] for i in live], [ids[i] for i in live],
-                            lambda: self._pair_coords(req.ref_coord, *_heavy_coords(picked)))
+                            lambda: self._pair_coords(req.ref_coord, *_heavy_coords(picked)), chem, chem_pair)
 
     def _executor(self):
         """Where the poolable host tasks run: the process-wide `HostPool` with `n_host_workers` workers and this generator's
@@ -674,7 +815,9 @@ class MLConformerGenerator(torch.nn.Module):
                             top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None,
                             overlay: bool = False, max_pairwise_tanimoto: Optional[float] = None,
                             refine_overlay: Union[bool, int] = False, receptor=None,
-                            max_receptor_clashes: Optional[int] = None) -> List:
+                            max_receptor_clashes: Optional[int] = None, chemical_scores: bool = False,
+                            reference_graph=None, max_chemical_tanimoto: Optional[float] = None, unique: bool = False,
+                            max_pairwise_chemical_tanimoto: Optional[float] = None) -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
@@ -712,7 +855,29 @@ class MLConformerGenerator(torch.nn.Module):
         overlapping a receptor atom by >= 0.6 A) and `receptor_max_overlap` (A), the Mols the int / double properties of
         the same names; None (no property) where posing failed.  `max_receptor_clashes=k`: drop the molecules with more
         than k clashing atoms, and those whose pose failed, before the threshold / diversity / `top_k` selection.
-        Refused with ValueError before any device work: scoring or posing without a reference conformer, a reference
+        `chemical_scores=True`: the chemical half of `evaluate_samples`, RDKit-free.  Every returned molecule carries
+        `chemical_tanimoto` - the Tanimoto of its chemical fingerprint with the reference graph's - and `graph_key`, the
+        unsigned 64-bit identity key of its molecular graph (records: the properties of those names; Mols: the double
+        property `chemical_tanimoto` and the STRING property `graph_key`, the key in decimal).  The fingerprint is this
+        package's own Morgan-type fingerprint (radius 2, 2 048 bits, bond types on, chirality off; `fingerprint.py`,
+        DESIGN.md section 6): a labelled SUBSTITUTE for RDKit's, not bit-compatible with it, computed on the GPU from the
+        returned heavy-atom graphs.  Equal keys: the same graph, up to what colour refinement can tell apart and hash
+        collisions.  The reference's graph is `reference_graph` (a Mol, a `GeneratedMolecule` or an (atomic_numbers,
+        bond_orders) pair: `fingerprint.mol_graph`), else `reference_conformer` where it is a Mol with bonds.  No
+        aromaticity is perceived: both sides must use one convention (generated aromatic bonds carry code 4).
+        `max_chemical_tanimoto=t` (implies the score): drop the molecules whose `chemical_tanimoto` is >= t, or NaN;
+        1.0 drops exactly those whose fingerprint equals the reference's.
+        `unique=True`: of the molecules with equal `graph_key` keep one - the first in ranking order where the call
+        scores shape (descending `shape_tanimoto`, ties to the lower sample id, NaN last), else the lowest sample id.
+        `max_pairwise_chemical_tanimoto=t`: sphere exclusion on the pairwise fingerprint Tanimoto
+        (`fingerprint.pairwise_fingerprint_tanimoto`), in the same walk as `max_pairwise_tanimoto` - a molecule is
+        excluded if either matrix reaches its threshold against an already kept one; the walk is in ranking order, or
+        in sample order where the call does not score shape.
+        Order of the stages: validity, `max_receptor_clashes`, `max_chemical_tanimoto`, `unique`, then the selection
+        (threshold, exclusion, `top_k`).  The filters only remove molecules.
+        Refused with ValueError before any device work: a chemical option that is not a bool / a real number in (0, 1],
+        a chemical score without a reference graph, a `reference_graph` that `fingerprint.mol_graph` refuses or that has no
+        or more than 64 heavy atoms, scoring or posing without a reference conformer, a reference
         outside 3..64 heavy atoms, top_k < 1, a threshold outside [0, 1], max_pairwise_tanimoto outside (0, 1] or without
         overlay, refine_overlay other than True or an integer in 1..1024 or without overlay, a receptor without overlay,
         one `load_receptor` refuses or one that holds the reference (a reference heavy atom within 0.5 A of a receptor
@@ -721,14 +886,16 @@ class MLConformerGenerator(torch.nn.Module):
             seeding.check_seed(sample_seed)
         req = self._shape_request(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
                                   max_pairwise_tanimoto, refine_overlay, receptor, max_receptor_clashes)
+        chem = self._chem_request(reference_conformer, chemical_scores, reference_graph, max_chemical_tanimoto, unique,
+                                  max_pairwise_chemical_tanimoto)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
         keyed = () if sample_seed is None else (sample_seed, None)   # unseeded: the positional call of before
         res = self._generate_shard(ref_context, ref_n_atoms, variance, None, n_samples, resample_steps, fixed_fragment,
                                    inertial_fragment_matching, blend_power, ifm_diffusion_level, optimise_geometry, *keyed)
         if getattr(self, "finisher", None) is None:
-            return self._return_records(req, self._shape_tensors(req, res), None, optimise_geometry)
+            return self._return_records(req, self._shape_tensors(req, res), None, optimise_geometry, chem)
         done = self._collect_finish(n_samples)    # finished per group while the later groups were still on their way
-        return self._return_objects(req, done, *self._finished_shape(req, done), None, sample_seed)
+        return self._return_objects(req, done, *self._finished_shape(req, done), None, sample_seed, chem)
 
     @torch.no_grad()
     def generate_conformers_sharded(self, reference_conformer=None, n_samples: int = 10, variance: int = 2,
@@ -741,7 +908,10 @@ class MLConformerGenerator(torch.nn.Module):
                                     top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None,
                                     overlay: bool = False, max_pairwise_tanimoto: Optional[float] = None,
                                     refine_overlay: Union[bool, int] = False, receptor=None,
-                                    max_receptor_clashes: Optional[int] = None) -> List:
+                                    max_receptor_clashes: Optional[int] = None, chemical_scores: bool = False,
+                                    reference_graph=None, max_chemical_tanimoto: Optional[float] = None,
+                                    unique: bool = False,
+                                    max_pairwise_chemical_tanimoto: Optional[float] = None) -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -758,7 +928,10 @@ class MLConformerGenerator(torch.nn.Module):
         `n_samples` itself (no broadcast), generates its shard with the shard's global indices as `sample_ids` and seeds
         no generator, so sample i is the same molecule on any world size and under either `balance`.
         `shape_scores`, `top_k`, `min_shape_tanimoto`, `overlay`, `max_pairwise_tanimoto`, `refine_overlay`, `receptor`,
-        `max_receptor_clashes`: as in `generate_conformers`.
+        `max_receptor_clashes`, `chemical_scores`, `reference_graph`, `max_chemical_tanimoto`, `unique`,
+        `max_pairwise_chemical_tanimoto`: as in `generate_conformers`.  The fingerprints are computed behind the gather,
+        on the rows a rank returns: with gather="all" uniqueness and chemical diversity hold over the whole batch, with
+        gather="rank0" within each other rank's own shard, like the rest of the selection.
         Every rank poses, scores and measures the receptor contacts of ITS OWN shard on its own GPU before the gather
         (posed coordinates, poses, scores and contacts travel as per-sample result tensors, or next to the finished
         Mols).  The selection runs on the rows a rank
@@ -772,6 +945,8 @@ class MLConformerGenerator(torch.nn.Module):
             seeding.check_seed(sample_seed)
         req = self._shape_request(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
                                   max_pairwise_tanimoto, refine_overlay, receptor, max_receptor_clashes)
+        chem = self._chem_request(reference_conformer, chemical_scores, reference_graph, max_chemical_tanimoto, unique,
+                                  max_pairwise_chemical_tanimoto)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)
         hi_n = min(ref_n_atoms + variance, self.max_n_nodes)
@@ -814,10 +989,10 @@ class MLConformerGenerator(torch.nn.Module):
         _, rank = mcg_dist.world_and_rank(group)
         row_ids = shards[rank] if (dst is not None and rank != dst and len(shards) > 1) else None
         if not finishing:
-            return self._return_records(req, res, row_ids, optimise_geometry)
+            return self._return_records(req, res, row_ids, optimise_geometry, chem)
         rows = mcg_dist.gather_objects(finished, shards, group, dst)      # the Mols travel as objects, with their scores
         return self._return_objects(req, [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows],
-                                    [r[3] for r in rows], row_ids, sample_seed)
+                                    [r[3] for r in rows], row_ids, sample_seed, chem)
 
     @torch.no_grad()
     def forward(self, reference_conformer=None, n_samples: int = 10, variance: int = 2,
@@ -827,11 +1002,16 @@ class MLConformerGenerator(torch.nn.Module):
                 shape_scores: bool = False, top_k: Optional[int] = None,
                 min_shape_tanimoto: Optional[float] = None, overlay: bool = False,
                 max_pairwise_tanimoto: Optional[float] = None, refine_overlay: Union[bool, int] = False, receptor=None,
-                max_receptor_clashes: Optional[int] = None) -> List:
+                max_receptor_clashes: Optional[int] = None, chemical_scores: bool = False, reference_graph=None,
+                max_chemical_tanimoto: Optional[float] = None, unique: bool = False,
+                max_pairwise_chemical_tanimoto: Optional[float] = None) -> List:
         return self.generate_conformers(reference_conformer, n_samples, variance, reference_context, n_atoms,
                                         optimise_geometry, resample_steps, fixed_fragment,
                                         inertial_fragment_matching, blend_power, ifm_diffusion_level,
                                         sample_seed=sample_seed, shape_scores=shape_scores, top_k=top_k,
                                         min_shape_tanimoto=min_shape_tanimoto, overlay=overlay,
                                         max_pairwise_tanimoto=max_pairwise_tanimoto, refine_overlay=refine_overlay,
-                                        receptor=receptor, max_receptor_clashes=max_receptor_clashes)
+                                        receptor=receptor, max_receptor_clashes=max_receptor_clashes,
+                                        chemical_scores=chemical_scores, reference_graph=reference_graph,
+                                        max_chemical_tanimoto=max_chemical_tanimoto, unique=unique,
+                                        max_pairwise_chemical_tanimoto=max_pairwise_chemical_tanimoto)

@@ -45,19 +45,20 @@ class GeneratedMolecule:
     `shape_tanimoto`: its shape score against the reference when the call asked for scores, else None.
     `overlay_tanimoto` / `pose`: the score and rigid pose of a call that posed its molecules onto the reference
     (`overlay=True`), else None.  `receptor_clashes` / `receptor_max_overlap`: its steric contacts with the call's
-    receptor, else None."""
-    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_score", "_overlay", "_contacts")
+    receptor, else None.  `chemical_tanimoto` / `graph_key`: its chemical similarity to the reference and its graph
+    identity key (`fingerprint.py`: the package's own Morgan-type fingerprint, a substitute for RDKit's), else None."""
+    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_score", "_overlay", "_contacts", "_chem")
 
     def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True,
                  sample_id: Optional[int] = None):
         self._z, self._coords, self._bonds, self.valid = list(atomic_numbers), coords, bond_orders, bool(valid)
         self._batch, self._b, self._sid = None, -1, sample_id
-        self._score = self._overlay = self._contacts = None
+        self._score = self._overlay = self._contacts = self._chem = None
 
     @classmethod
     def _view(cls, batch: _HostBatch, b: int, valid: bool, sample_id: Optional[int] = None,
               score: Optional[float] = None, overlay: Optional[tuple] = None,
-              contacts: Optional[tuple] = None) -> "GeneratedMolecule":
+              contacts: Optional[tuple] = None, chem: Optional[tuple] = None) -> "GeneratedMolecule":
         m = cls.__new__(cls)
         m._z = m._coords = m._bonds = None
         m.valid, m._batch, m._b = valid, batch, b
@@ -65,7 +66,22 @@ class GeneratedMolecule:
         m._score = score
         m._overlay = overlay
         m._contacts = contacts
+        m._chem = chem
         return m
+
+    @property
+    def chemical_tanimoto(self) -> Optional[float]:
+        """Tanimoto of this molecule's chemical fingerprint with the reference graph's (`fingerprint.py`: radius 2, 2 048
+        bits, the package's own definition - NOT RDKit's Morgan fingerprint) when the call asked for `chemical_scores` or
+        `max_chemical_tanimoto`; None otherwise."""
+        return None if self._chem is None else self._chem[0]
+
+    @property
+    def graph_key(self) -> Optional[int]:
+        """The unsigned 64-bit identity key of the molecular graph (`fingerprint.graph_fingerprints`) when the call asked
+        for `chemical_scores` or `unique`; None otherwise.  Isomorphic graphs have equal keys; unequal graphs with equal
+        keys are possible (colour refinement's blind spots, hash collisions)."""
+        return None if self._chem is None else self._chem[1]
 
     @property
     def receptor_contacts(self) -> Optional[Tuple[int, float]]:
@@ -274,17 +290,21 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                            valid: torch.Tensor, sample_ids: Optional[Sequence[int]] = None,
                            shape_tanimoto: Optional[torch.Tensor] = None, overlay_tanimoto: Optional[torch.Tensor] = None,
                            pose: Optional[torch.Tensor] = None, receptor_clashes: Optional[torch.Tensor] = None,
-                           receptor_max_overlap: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
+                           receptor_max_overlap: Optional[torch.Tensor] = None,
+                           chemical_tanimoto: Optional[torch.Tensor] = None,
+                           graph_key: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
     (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
     (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records).
     `overlay_tanimoto[b]` / `pose[b]` (rotation row-major, then translation: [B,12], NaN where posing failed): row b's
     pose onto the reference (None: records of a call that did not pose).  `receptor_clashes[b]` / `receptor_max_overlap[b]`:
     row b's receptor contacts (a negative clash count: not measured, the record gets None; None: a call without a
-    receptor)."""
+    receptor).  `chemical_tanimoto[b]` (fp32) / `graph_key[b]` (int64 holding the unsigned bit pattern): row b's chemical
+    similarity to the reference and graph identity key (either may be None: not asked for)."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
     view = GeneratedMolecule._view
-    if sample_ids is None and shape_tanimoto is None and overlay_tanimoto is None:
+    if sample_ids is None and shape_tanimoto is None and overlay_tanimoto is None and chemical_tanimoto is None \
+            and graph_key is None:
         return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
     flags = valid.cpu().tolist()
     ids = list(range(len(flags))) if sample_ids is None else \
@@ -299,7 +319,12 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     if receptor_clashes is not None:
         contacts = [None if c < 0 else (int(c), float(w)) for c, w in
                     zip(receptor_clashes.cpu().tolist(), receptor_max_overlap.cpu().tolist())]
-    return [view(batch, b, bool(v), ids[b], scores[b], overlays[b], contacts[b]) for b, v in enumerate(flags)]
+    chem = [None] * len(flags)
+    if chemical_tanimoto is not None or graph_key is not None:
+        sim = [None] * len(flags) if chemical_tanimoto is None else [float(v) for v in chemical_tanimoto.cpu().tolist()]
+        keys = [None] * len(flags) if graph_key is None else [int(k) & 0xFFFFFFFFFFFFFFFF for k in graph_key.cpu().tolist()]
+        chem = list(zip(sim, keys))
+    return [view(batch, b, bool(v), ids[b], scores[b], overlays[b], contacts[b], chem[b]) for b, v in enumerate(flags)]
 
 
 def assemble_molecules(x: torch.Tensor, elements: torch.Tensor, bond: torch.Tensor, n_nodes: torch.Tensor

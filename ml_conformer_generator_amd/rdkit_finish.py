@@ -156,6 +156,14 @@ def tag_contacts(mols: Sequence, contacts: Sequence[Optional[tuple]]) -> None:
             m.SetDoubleProp("receptor_max_overlap", float(c[1]))
 
 
+def tag_graph_keys(mols: Sequence, keys: Sequence[Optional[int]]) -> None:
+    """Set the string property `graph_key` - the unsigned 64-bit graph identity key in decimal; it does not fit RDKit's
+    int property - on every Mol of `mols` (None = dropped); `keys[k]` belongs to `mols[k]`, None = no key."""
+    for m, k in zip(mols, keys):
+        if m is not None and k is not None and hasattr(m, "SetProp"):
+            m.SetProp("graph_key", str(int(k)))
+
+
 def tag_scores(mols: Sequence, prop: str, scores: Sequence[Optional[float]]) -> None:
     """Set the double property `prop` (`shape_tanimoto`, `overlay_tanimoto`) on every Mol of `mols` (None = dropped);
     `scores[k]` belongs to `mols[k]`, None = no score.  Set after the object gather: RDKit does not pickle Mol properties
