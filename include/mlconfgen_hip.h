@@ -166,6 +166,13 @@ typedef struct mcg_plan_opts {
     int32_t reserved[5];          /* must be zero */
 } mcg_plan_opts;
 #define MCG_ALL_FOUR_TILE 0x3fffffff
+/* Accepted molecule sizes.  An atom's n - 1 edge rows may run through at most 8 units of 16 * edge_mt rows, which every
+ * molecule of up to 7 * 16 * edge_mt + 3 atoms satisfies wherever it stands in the batch:
+ *   edge_mt 1 (and 0 = auto, which is 1): 0 .. 115 atoms per molecule;
+ *   edge_mt 4:                            0 .. 451 atoms, and no 64-row unit may hold rows of more than 16 atoms (batches
+ *                                         with molecules below 6 atoms need edge_mt 1).
+ * A larger molecule is refused with MCG_ERR_ARG and a message that names it, before any device call, also where its rows
+ * would happen to fit behind the molecules in front of it.  (Which kernels serve which sizes: mcg_debug_route.) */
 int mcg_plan_create_ex(int B, int N, const int32_t* n_nodes_host, const mcg_plan_opts* opts, mcg_plan** out);
 void mcg_plan_destroy(mcg_plan* p);
 /* Plans take their device memory (one block of tables, one of workspace) from a per-device pool inside the library: the
@@ -207,6 +214,32 @@ int mcg_egnn_block_debug(const mcg_egnn* m, mcg_plan* p, int block, float* h_io,
 int mcg_egnn_gcl_debug(const mcg_egnn* m, mcg_plan* p, int layer, const float* h_in, const float* x_in,
                        const float* x0, void* stream);
 int mcg_plan_peek(const mcg_plan* p, int which, float* dst, void* stream);
+/* Test hook: the kernels a denoiser call of model `m` on plan `p` would run, read from the same routing function the
+ * launchers use (keep_agg != 0: as mcg_egnn_gcl_debug runs a layer).  Host only: nothing is launched, nothing is written
+ * on the device.  A plan cut into molecule ranges reports its first range.  info_host[8] =
+ *   [0] edge kernel:            MCG_ROUTE_EDGE_*
+ *   [1] first-layer GEMM family: MCG_GEMM_F32 (32-row fp32), MCG_GEMM_F32ROWS16, MCG_GEMM_BF16, MCG_GEMM_X6
+ *   [2] aggregate source:       MCG_ROUTE_AGG_*
+ *   [3] 1 = the node phase of a GCL layer is the one fused launch (MCG_OPT_NODE_FUSED)
+ *   [4] node GEMM family (as [1])
+ *   [5] coordinate update:      MCG_ROUTE_COORD_*
+ *   [6] most per-unit partial-sum slots any atom has (units of 16 * edge_mt rows; the gathers need <= 4)
+ *   [7] most rows of the workgroup-level sums any atom has in the unit tables the route uses; 0 = it uses none (the plan
+ *       has no unit tables, or the edge kernel is not MCG_ROUTE_EDGE_EXACT - latency mode 1, bf16, f32x6)
+ * MCG_ERR_ARG on a null argument. */
+enum { MCG_ROUTE_EDGE_EXACT = 0,       /* exact-fp32 throughput kernel on unit tables (four-tile / quarter-tile units) */
+       MCG_ROUTE_EDGE_NS = 1,          /* exact-fp32 column-split kernel, per-tile partial sums: any molecule size */
+       MCG_ROUTE_EDGE_BF16ROWS16 = 2,  /* bf16 operands, 16-row tiles */
+       MCG_ROUTE_EDGE_W64BF16 = 3,     /* bf16 operands, 64-row units */
+       MCG_ROUTE_EDGE_W64X6 = 4,       /* f32x6 split operands, 64-row units */
+       MCG_ROUTE_EDGE_INVALID = 5 };   /* exact fp32 on a 64-row plan: the call fails with MCG_ERR_STATE */
+enum { MCG_ROUTE_AGG_GATHER_U = 0,     /* node GEMM sums an atom's rows of the workgroup-level sums itself */
+       MCG_ROUTE_AGG_GATHER_P = 1,     /* node GEMM sums an atom's (<= 4) per-unit partial rows itself (bf16) */
+       MCG_ROUTE_AGG_GATHER_AGG2 = 2,  /* workgroup-level sums materialised by a launch of their own (keep_agg) */
+       MCG_ROUTE_AGG_COMBINE = 3 };    /* an atom's (<= 8) per-unit partial rows summed by a launch of their own */
+enum { MCG_ROUTE_COORD_PENDING_U = 0, MCG_ROUTE_COORD_PENDING_P = 1,   /* side job of the next first-layer GEMM / output head */
+       MCG_ROUTE_COORD_KERNEL = 2 };   /* a launch of its own right behind the edge kernel */
+int mcg_debug_route(const mcg_egnn* m, const mcg_plan* p, int keep_agg, int32_t info_host[8]);
 
 /* Measurement hook: the edge-MLP kernel of GCL layer `layer` (equiv = 0, 0..2*n_blocks-1) or of the
  * coordinate update of block `layer` (equiv = 1) launched `iters` times on the plan's current state. */

@@ -39,6 +39,7 @@ SIGNATURES: Dict[str, tuple] = {
     "mcg_egnn_block_debug": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "mcg_egnn_gcl_debug": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "mcg_plan_peek": (_i, [_vp, _i, _vp, _vp]),
+    "mcg_debug_route": (_i, [_vp, _vp, _i, _vp]),
     "mcg_bench_edge": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "mcg_bench_edge_incall": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "mcg_sampler_noise": (_i, [_vp, _vp, _vp, _vp, _vp]),
@@ -98,6 +99,12 @@ GEMM_PACK4, GEMM_PACK16, GEMM_PACK16X3 = 0, 1, 2
 ALL_FOUR_TILE = 0x3fffffff          # MCG_ALL_FOUR_TILE
 OPT_X6_GEMM, OPT_GEMM_RN, OPT_GEMM_X6_RN, OPT_GEMM_BF16_LDS, OPT_NODE_FUSED = 1, 2, 3, 4, 5
 
+# mcg_debug_route: info[0] edge kernel, info[2] aggregate source, info[5] coordinate update (info[1] / info[4]: GEMM_* families)
+ROUTE_EDGE = ("Exact", "Ns", "Bf16Rows16", "W64Bf16", "W64X6", "Invalid")
+ROUTE_GEMM = ("F32", "F32Rows16", "Bf16", "X6")
+ROUTE_AGG = ("GatherU", "GatherP", "GatherAgg2", "Combine")
+ROUTE_COORD = ("PendingU", "PendingP", "Kernel")
+
 _lib = None
 
 
@@ -125,6 +132,14 @@ def lib():
         fn.argtypes = args
     _lib = handle
     return handle
+
+
+def debug_route(model_handle, plan_handle, keep_agg: bool = False) -> dict:
+    """`mcg_debug_route` by name: what the library's routing function decides for this model and plan (no launch)."""
+    info = (C.c_int32 * 8)()
+    check(lib().mcg_debug_route(model_handle, plan_handle, 1 if keep_agg else 0, info), "mcg_debug_route")
+    return {"edge": ROUTE_EDGE[info[0]], "pab": ROUTE_GEMM[info[1]], "agg": ROUTE_AGG[info[2]], "fused": bool(info[3]),
+            "node": ROUTE_GEMM[info[4]], "coord": ROUTE_COORD[info[5]], "pspan": int(info[6]), "unit_span": int(info[7])}
 
 
 def check(code: int, what: str) -> None:

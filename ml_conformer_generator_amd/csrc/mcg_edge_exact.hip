@@ -4,7 +4,9 @@
 //                round of the chip, quarter-tile units (one tile per workgroup, columns split over the waves) for the
 //                rest; workgroup-level sums written once per (workgroup, atom)
 //   k_edge_ns    stand-alone column-split kernel with per-unit partial sums: plans without unit tables
-//                (atoms whose rows span more than four units, N > ~50) and mcg_plan_set_latency_mode(1)
+//                (atoms whose rows span more than four quarter-tile and more than two four-tile units: never up to
+//                51 atoms, mostly from ~68 on, always from 116 on - where the plan is refused; route() in
+//                mcg_egnn_api.hip) and mcg_plan_set_latency_mode(1)
 #include "mcg_edge_common.h"
 
 #include <type_traits>

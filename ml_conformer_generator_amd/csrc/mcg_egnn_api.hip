@@ -46,8 +46,8 @@ __global__ __launch_bounds__(128) void k_prep_embed(const float* __restrict__ xh
 
 // agg[v] = (sum of the per-wave partials that cover node v) / 100   (egnn.py:429-435), and the coordinate
 // update below: driven by a per-node table of partial-slot indices built once per plan (node_slots[v][0..7],
-// -1 = unused; a node's rows span at most ceil((n-2)/16) + 1 <= 4 tiles for n <= 42), summed in ascending
-// slot order - deterministic, no atomics.
+// -1 = unused; a node's rows span at most ceil((n-2)/16) + 1 tiles: <= 4 for n <= 42, <= 8 up to the plan's limit of 115
+// atoms), summed in ascending slot order - deterministic, no atomics.
 __global__ __launch_bounds__(128) void k_combine_agg_t(const float* __restrict__ P, const int* __restrict__ node_slots,
                                                         float* __restrict__ agg) {
     const int v = blockIdx.x;
@@ -229,8 +229,11 @@ static Route route(const mcg_egnn* m, const mcg_plan* pl, bool keep_agg) {
     Route r{};
     const int M = pl->M;
     const bool x6g = m->x6 && m->x6_gemm;
-    // exact-fp32 throughput kernel while the plan has unit tables (atoms whose rows span at most four units, N <= ~50) and
-    // latency mode 1 is off
+    // exact-fp32 throughput kernel while the plan has unit tables and latency mode 1 is off.  Tables need every atom's rows to
+    // span at most four quarter-tile units or two four-tile units: always up to 42 atoms; 43..51 by either rule; ~52..67 by the
+    // four-tile set alone (65 rows can start a third 64-row unit: 67 is not a hard edge); beyond that only where the large
+    // molecules fall into complete rounds of four-tile units (span <= 4 of those) with small molecules in the quarter-tile tail.
+    // Everything else, up to the plan's limit of 115 atoms, runs k_edge_ns (tests/test_large_molecules_host.py pins these)
     const bool wgc = pl->wgc && pl->MT == 1 && !m->bf16 && !m->x6 && pl->latency_mode != 1;
     if (wgc) r.edge = EdgeKernel::Exact;
     else if (m->x6 && pl->MT == 4) r.edge = EdgeKernel::W64X6;      // (plans with 16-row tiles - molecules below 6 atoms - run the fp32 kernels)
@@ -549,6 +552,24 @@ int mcg_bench_edge(const mcg_egnn* m, mcg_plan* pl, int layer, int equiv, int it
     for (int i = 0; i < iters; ++i)
         if (int e = run_edge(pl, route(m, pl, false), equiv ? m->equiv[layer] : m->gcl_edge[layer], equiv != 0,
                              equiv ? pl->Px : pl->P, (hipStream_t)stream)) return e;
+    return MCG_OK;
+}
+
+// Test hook: what route() decides for this model and plan, as small integers (the enumerators above, in declaration order).
+// Host only: no launch, nothing written on the device.  A plan cut into molecule ranges reports its first range, whose
+// launches are the ones that run.
+int mcg_debug_route(const mcg_egnn* m, const mcg_plan* pl, int keep_agg, int32_t info[8]) {
+    static_assert((int)EdgeKernel::Exact == MCG_ROUTE_EDGE_EXACT && (int)EdgeKernel::Invalid == MCG_ROUTE_EDGE_INVALID &&
+                  (int)GemmFamily::F32 == MCG_GEMM_F32 && (int)GemmFamily::X6 == MCG_GEMM_X6 &&
+                  (int)AggSource::GatherU == MCG_ROUTE_AGG_GATHER_U && (int)AggSource::Combine == MCG_ROUTE_AGG_COMBINE &&
+                  (int)CoordUpdate::PendingU == MCG_ROUTE_COORD_PENDING_U && (int)CoordUpdate::Kernel == MCG_ROUTE_COORD_KERNEL,
+                  "include/mlconfgen_hip.h numbers the route in declaration order");
+    if (!m || !pl || !info) { mcg_set_error("mcg_debug_route: null argument"); return MCG_ERR_ARG; }
+    const mcg_plan* q = pl->subs.empty() ? pl : pl->subs[0];
+    const Route r = route(m, q, keep_agg != 0);
+    info[0] = (int32_t)r.edge; info[1] = (int32_t)r.pab.family; info[2] = (int32_t)r.agg; info[3] = r.fused ? 1 : 0;
+    info[4] = (int32_t)r.node.family; info[5] = (int32_t)r.coord; info[6] = q->pspan;
+    info[7] = r.edge == EdgeKernel::Exact ? q->units().max_span : 0;        // (tables the route does not use are not reported)
     return MCG_OK;
 }
 

@@ -25,6 +25,7 @@ static int plan_create_single(int B, int N, const int32_t* n_nodes_host, const m
     (void)hipGetLastError();
     McgPlanHost H;
     if (int e = mcg_plan_build_host(B, N, n_nodes_host, opts, cus, H)) return e;
+    if (int e = mcg_plan_host_refusal(H, "mcg_plan_create")) return e;          // (before the first device call)
     if (!*ss_io) MCG_HIP(hipStreamCreateWithFlags(ss_io, hipStreamNonBlocking));
     const hipStream_t ss = *ss_io;
     mcg_plan* p = new mcg_plan();
@@ -33,19 +34,7 @@ static int plan_create_single(int B, int N, const int32_t* n_nodes_host, const m
     std::vector<int>&nn = H.nn, &node_off = H.node_off, &node_mol = H.node_mol, &wave_poff = H.wave_poff, &ij = H.ij,
                     &node_slots = H.node_slots;
     McgPlanHost::Set (&ht)[2] = H.ht;
-    const int n_sets = H.n_sets, best = H.MT, R = 16 * H.MT;
-    const bool slots_ok = H.slots_ok, segs_ok = H.segs_ok;
-    if (!segs_ok) {
-        mcg_set_error("mcg_plan_create: edge_mt = %d puts more than 16 atoms' rows into one %d-row unit (molecules this "
-                      "small need edge_mt = 1)", best, R);
-        delete p;
-        return MCG_ERR_ARG;
-    }
-    if (!slots_ok) {
-        mcg_set_error("mcg_plan_create: a molecule's edge rows span more than 8 tiles per atom (N > 114 is not supported)");
-        delete p;
-        return MCG_ERR_ARG;
-    }
+    const int n_sets = H.n_sets;
     int max_uslots = 0;
     for (int k = 0; k < n_sets; ++k) max_uslots = std::max(max_uslots, ht[k].n_uslots);
     for (int k = 0; k < n_sets; ++k)

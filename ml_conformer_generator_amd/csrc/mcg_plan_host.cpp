@@ -77,6 +77,10 @@ int mcg_plan_build_host(int B, int N, const int32_t* n_nodes_host, const mcg_pla
         p->n_pslots = wave_poff[p->n_waves];
         for (int b = 0; b < B && slots_ok; ++b) {
             const int n = nn[b];
+            // one size limit wherever the molecule stands (mcg_plan_host.h): up to MCG_PLAN_MAX_ATOMS(R) atoms always fit the
+            // eight slots; a larger molecule would fit behind some prefixes only (117 atoms: 116 rows, first rows on four
+            // residues mod 16) and is refused behind all of them
+            if (n > MCG_PLAN_MAX_ATOMS(R)) { slots_ok = false; break; }
             for (int i = 0; i < n && n > 1; ++i) {
                 const int v = node_off[b] + i;
                 const int first = row_off[b] + i * (n - 1);
@@ -200,6 +204,23 @@ int mcg_plan_build_host(int B, int N, const int32_t* n_nodes_host, const mcg_pla
     return MCG_OK;
 }
 
+int mcg_plan_host_refusal(const McgPlanHost& H, const char* who) {
+    const int R = 16 * H.MT;
+    if (!H.segs_ok) {
+        mcg_set_error("%s: edge_mt = %d puts more than 16 atoms' rows into one %d-row unit (molecules this small need edge_mt = 1)",
+                      who, H.MT, R);
+        return MCG_ERR_ARG;
+    }
+    if (!H.slots_ok) {
+        int worst = 0;
+        for (int n : H.nn) worst = std::max(worst, n);
+        mcg_set_error("%s: a molecule of %d atoms: an atom's edge rows would span more than 8 units of %d rows (edge_mt = %d plans "
+                      "take molecules of up to %d atoms)", who, worst, R, H.MT, MCG_PLAN_MAX_ATOMS(R));
+        return MCG_ERR_ARG;
+    }
+    return MCG_OK;
+}
+
 // Host-only self-check of a plan's tables (no GPU call: it runs on a CPU-only box and is what the CPU tests drive):
 // builds them as mcg_plan_create_ex would for a device with `cus` compute units and verifies, independently of how they
 // were built, that every edge row's (unit, tile, segment) lands in a slot that its atom lists, that no slot is shared
@@ -212,7 +233,7 @@ extern "C" int mcg_plan_check_tables(int B, int N, const int32_t* n_nodes_host, 
     const bool wgc = H.wgc;
     for (int k = 0; k < 8; ++k) info[k] = 0;
     info[0] = H.n_sets;
-    if (!H.segs_ok || !H.slots_ok) { mcg_set_error("mcg_plan_check_tables: the batch does not fit the requested edge_mt"); return MCG_ERR_ARG; }
+    if (int e = mcg_plan_host_refusal(H, "mcg_plan_check_tables")) return e;
     auto fail = [&](const char* what, int a, int b2) { mcg_set_error("mcg_plan_check_tables: %s (%d, %d)", what, a, b2); return MCG_ERR_STATE; };
     // the row table
     for (int b = 0; b < B; ++b) {

@@ -281,8 +281,9 @@ def test_model_options_and_measurement_hooks(edm_sd):
         _lib.check(L.mcg_debug_gemm_launches(c.ctypes.data, 1 if reset else 0), "mcg_debug_gemm_launches")
         return c.reshape(4, 8)
 
-    # fp32 at 114 atoms: every node GEMM takes the 16-row-tile kernel, which MCG_OPT_GEMM_RN does not steer (round-3
-    # advisor: the old loop over this option in fp32 mode tested nothing) - said here, with the launch counters
+    # fp32 at 114 atoms in all (five molecules of 15..33, N = 33): every node GEMM takes the 16-row-tile kernel, which
+    # MCG_OPT_GEMM_RN does not steer (round-3 advisor: the old loop over this option in fp32 mode tested nothing) - said here,
+    # with the launch counters
     launches()
     ok, err, sc = close(d(t.to(DEV), z.to(DEV), nm.to(DEV), em.to(DEV), ctx.to(DEV)), ref)
     c = launches()

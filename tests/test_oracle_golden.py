@@ -51,7 +51,7 @@ def test_context_kats():
     assert torch.allclose(g["ceyyag_context"], torch.tensor([50.589699, 105.313202, 133.522293]), atol=2e-3)
 
 
-@pytest.mark.parametrize("tag", ["b2n20", "b4n19", "b3n39", "b3n27_x30"])
+@pytest.mark.parametrize("tag", ["b2n20", "b4n19", "b3n39", "b3n27_x30", "b3n114"])
 def test_dynamics_seam(edm_sd, tag):
     g = load_golden(f"dynamics_{tag}.npz")
     out = EO.egnn_dynamics(edm_sd, g["t"], g["xh"], g["node_mask"], edge_mask_of(g["node_mask"]), g["context"])
@@ -78,7 +78,7 @@ def test_single_block(edm_sd):
     assert torch.allclose(x, g["x_out"], rtol=1e-5, atol=1e-6)
 
 
-@pytest.mark.parametrize("name", ["sampler_T20_b4n19.npz", "sampler_T8_rs1.npz"])
+@pytest.mark.parametrize("name", ["sampler_T20_b4n19.npz", "sampler_T8_rs1.npz", "sampler_T8_b3n101.npz"])
 def test_sampler_trajectory(name):
     g = load_golden(name)
     assert bool(torch.isfinite(g["z_trace"]).all())
@@ -93,8 +93,9 @@ def test_sampler_trajectory(name):
     assert torch.equal(h.to(torch.int64), g["h"].to(torch.int64))
 
 
-def test_inpaint():
-    g = load_golden("inpaint_T5.npz")
+@pytest.mark.parametrize("name", ["inpaint_T5.npz", "inpaint_T5_rs1_b2n80.npz"])
+def test_inpaint(name):
+    g = load_golden(name)
     assert bool(torch.isfinite(g["z_trace"]).all())
     nm = g["node_mask"]
     s = DO.SamplerOracle(sd_for(g), int(g["T"]), noise_fn=TapeNoise(g["noise"]))
@@ -104,6 +105,44 @@ def test_inpaint():
     assert traj_violation(torch.stack(s.trace), g["z_trace"], rel=2e-5) <= 1.0
     assert violation(x, g["x"]) <= 1.0
     assert torch.equal(h.to(torch.int64), g["h"].to(torch.int64))
+
+
+def test_large_trajectory_fixtures_are_what_they_say():
+    """The fixtures above 42 atoms (tools/make_golden.py section 11): explicit sizes, the recipe each one records."""
+    g = load_golden("dynamics_b3n114.npz")
+    assert g["node_mask"].sum(1).reshape(-1).tolist() == [114, 68, 9] and str(g["weight_recipe"]) == "v2"
+    assert g["t"].unique().numel() == 3
+    g = load_golden("sampler_T8_b3n101.npz")
+    assert g["node_mask"].sum(1).reshape(-1).tolist() == [70, 101, 9] and str(g["weight_recipe"]) == "v2d"
+    assert g["z_trace"].shape == (8, 3, 101, 11) and g["noise"].numel() == 10 * 3 * 101 * 11
+    g = load_golden("inpaint_T5_rs1_b2n80.npz")
+    assert g["node_mask"].sum(1).reshape(-1).tolist() == [80, 61] and str(g["weight_recipe"]) == "v2dd"
+    assert g["fixed_mask"].sum(1).reshape(-1).tolist() == [7, 7] and g["z_trace"].shape == (10, 2, 80, 11)
+    assert g["noise"].numel() == (1 + 10 + 5 + 1) * 2 * 80 * 11
+
+
+@pytest.mark.parametrize("name", ["sampler_T8_b3n101.npz", "inpaint_T5_rs1_b2n80.npz"])
+def test_large_trajectory_fixtures_do_not_amplify_rounding(name):
+    """What a trajectory fixture can pin depends on its weights: the fp32 and the fp64 oracle on the fixture's own tape must
+    stay within 0.2 x TRAJ_REL of each other at every recorded step, or a correct fp32 implementation could be anywhere
+    inside the tolerance by rounding alone.  Measured (printed per step): at most 0.007 for the forward run under "v2d",
+    0.09 for the inpainting run under "v2dd".  (Recipes that fail here or overflow: tools/make_golden.py section 11.)"""
+    g = load_golden(name)
+    nm = g["node_mask"]
+    traces = {}
+    for dt in (torch.float32, torch.float64):
+        s = DO.SamplerOracle({k: v.to(dt) for k, v in sd_for(g).items()}, int(g["T"]), noise_fn=TapeNoise(g["noise"]))
+        s.trace = []
+        args = (nm.to(dt), edge_mask_of(nm).to(dt), g["context"].to(dt))
+        if name.startswith("inpaint"):
+            s.inpaint(*args, g["z_known"].to(dt), g["fixed_mask"].to(dt), int(g["resample_steps"]), int(g["blend_power"]))
+        else:
+            s.forward(*args, int(g["resample_steps"]))
+        traces[dt] = torch.stack(s.trace)
+    assert traces[torch.float64].dtype == torch.float64 and bool(torch.isfinite(traces[torch.float64]).all())
+    per_step = [traj_violation(traces[torch.float32][k:k + 1], traces[torch.float64][k:k + 1]) for k in range(len(s.trace))]
+    print(name, "fp32 vs fp64 oracle per step, x TRAJ_REL:", [round(v, 4) for v in per_step])
+    assert max(per_step) <= 0.2, per_step
 
 
 def test_sampler_at_the_judged_step_counts():

@@ -95,11 +95,86 @@ def record_steps(gm):
 from ml_conformer_generator_amd.synthetic import synth_gcn_inputs  # noqa: E402
 
 
+def large_molecule_section(egnn, ed, mu, save, norms, dummy_ctx):
+    """11. Molecules above 42 atoms (the reference's own pad width): the oracle was anchored to the reference at n <= 39 only.
+    Self-seeding - every fixture seeds torch itself and shares no RNG state with the sections above - and explicit sizes,
+    built into masks by the reference's `prepare_masks` and into a context the way `prepare_edm_input` builds it.
+    `--large-only` runs this section alone (no T = 250 trajectories, no other fixture file touched).
+    Weights: the single call uses "v2" like every dynamics_* fixture.  The trajectories cannot: at 70..101 atoms the untrained
+    "v2" network sends the latent to inf within three steps of T = 8 in the reference's arithmetic, fp32 and fp64 alike.  The
+    forward run takes "v2d".  The inpainting run is harder: T = 5 with resampling divides the latent by alpha_ts twice per
+    level, |z| reaches 6e4 whatever the network does, and at 80 atoms the coordinate feedback x -> d^2 ~ x^2 -> x overflows
+    under "v2d" (fourth step) and under the contractive gains 0.3 and 0.2 - in fp64 as well; gains 0.15 and below stay finite
+    but leave tools/parity_sensitivity.py blind to every GCL mutation.  It takes "v2dd" (weights.py: distance columns damped
+    further, every other layer at full gain).  How far fp32 rounding alone moves each trajectory - the fp32 against the fp64
+    oracle on the fixture's own tape, bound 0.2 x TRAJ_REL - is measured by
+    tests/test_oracle_golden.py::test_large_trajectory_fixtures_do_not_amplify_rounding: at most 0.007 (forward), 0.09
+    (inpainting)."""
+    dev = torch.device("cpu")
+
+    def inputs(sizes, N):
+        n_nodes = torch.tensor(sizes)
+        nm, em = mu.prepare_masks(n_nodes=n_nodes, max_n_nodes=N, device=dev)
+        ctx = ((dummy_ctx - norms["mean"]) / norms["mad"]).unsqueeze(0).repeat(len(sizes), 1).unsqueeze(1).repeat(1, N, 1) * nm
+        return nm, em, ctx
+
+    # 11a. one call of `dynamics` at 114 / 68 / 9 atoms, a different t per molecule
+    sd = W.synth_edm_state_dict(1234)
+    gm = build_edm(egnn, ed, 100, sd)
+    torch.manual_seed(1114)
+    nm, em, ctx = inputs([114, 68, 9], 114)
+    z = gm.sample_combined_position_feature_noise(3, 114, nm)
+    t = torch.tensor([[51.0], [30.0], [77.0]]) / 100
+    with torch.no_grad():
+        out = gm.dynamics(t, z, nm, em, ctx)
+    assert bool(torch.isfinite(out).all())
+    save("dynamics_b3n114.npz", t=t, xh=z, node_mask=nm, context=ctx, out=out, weight_seed=1234, weight_recipe=np.array("v2"))
+
+    # 11b. forward trajectory at 70 / 101 / 9 atoms: T = 8, every z_s, recorded noise tape
+    sd_d = W.synth_edm_state_dict(1234, recipe="v2d")
+    gm = build_edm(egnn, ed, 8, sd_d)
+    torch.manual_seed(1101)
+    nm, em, ctx = inputs([70, 101, 9], 101)
+    trace = record_steps(gm)
+    with NoiseTape() as tape, torch.no_grad():
+        x, h = gm(nm, em, ctx, 0)
+    assert bool(torch.isfinite(torch.stack(trace)).all()) and bool(torch.isfinite(x).all())
+    save("sampler_T8_b3n101.npz", node_mask=nm, context=ctx, noise=tape.flat(), z_trace=torch.stack(trace),
+         x=x, h=h, T=8, resample_steps=0, weight_seed=1234, weight_recipe=np.array("v2d"))
+
+    # 11c. inpainting at 80 / 61 atoms with a fixed fragment of 7 atoms (the first 7 heavy atoms of frag_yibfeu), T = 5,
+    #      resampling 1 - layout of inpaint_T5.npz
+    fxyz, fz = parse_molblock_heavy_atoms(open("/root/reference/assets/demo_files/frag_yibfeu.mol").read())
+    fxyz, fz = fxyz[:7], fz[:7]
+    fxyz = fxyz - fxyz.mean(0)
+    cls = {6: 0, 7: 1, 8: 2, 9: 3, 15: 4, 16: 5, 17: 6, 35: 7}
+    B, N, n_f = 2, 80, 7
+    gm = build_edm(egnn, ed, 5, W.synth_edm_state_dict(1234, recipe="v2dd"))
+    torch.manual_seed(1180)
+    nm, em, ctx = inputs([80, 61], N)
+    z_known = torch.zeros(B, N, 11)
+    z_known[:, :n_f, :3] = fxyz
+    for i, zz in enumerate(fz):
+        z_known[:, i, 3 + cls[zz]] = 1.0
+    fixed = torch.zeros(B, N, 1)
+    fixed[:, :n_f] = 1.0
+    trace = record_steps(gm)
+    with NoiseTape() as tape, torch.no_grad():
+        x, h = gm.inpaint(nm, em, ctx, z_known, fixed, 1, 3)
+    assert bool(torch.isfinite(torch.stack(trace)).all()) and bool(torch.isfinite(x).all())
+    save("inpaint_T5_rs1_b2n80.npz", node_mask=nm, context=ctx, z_known=z_known, fixed_mask=fixed, noise=tape.flat(),
+         z_trace=torch.stack(trace), x=x, h=h, T=5, resample_steps=1, blend_power=3, weight_seed=1234,
+         weight_recipe=np.array("v2dd"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
     ap.add_argument("--only", default="", help="write only the fixtures whose file name contains this substring "
                                                "(everything is still computed: the fixtures share RNG state and models)")
+    ap.add_argument("--large-only", action="store_true",
+                    help="section 11 alone (molecules above 42 atoms: dynamics_b3n114, sampler_T8_b3n101, "
+                         "inpaint_T5_rs1_b2n80); it seeds itself and leaves every other fixture file untouched")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     torch.set_num_threads(8)
@@ -113,6 +188,10 @@ def main():
         np.savez_compressed(os.path.join(args.out, name), **{k: (v.numpy() if torch.is_tensor(v) else np.asarray(v))
                                                               for k, v in kw.items()})
         print("wrote", name, {k: tuple(np.asarray(v.numpy() if torch.is_tensor(v) else v).shape) for k, v in kw.items()})
+
+    if args.large_only:
+        large_molecule_section(egnn, ed, mu, save, norms, dummy_ctx)
+        return
 
     # 1. noise-schedule tables (a4)
     save("schedule.npz", **{f"gamma_T{T}": ed.PredefinedNoiseSchedule(T, 1e-5).gamma.detach() for T in (20, 100, 250, 1000)})
@@ -510,6 +589,8 @@ def main():
          noise=k250["tape"], z_trace=k250["trace"][idx], z_trace_index=np.array(idx), n_sampler_steps=n_tr, x=x, h=k250["h"],
          T=250, resample_steps=1, blend_power=3, weight_seed=1234, weight_recipe=np.array("gain0.3"),
          one_ulp_context_rel_dev=amp_i)
+
+    large_molecule_section(egnn, ed, mu, save, norms, dummy_ctx)
 
 
 if __name__ == "__main__":

@@ -155,9 +155,11 @@ def main():
                          "its deviations peak; 10 = all of it, 3.3 x the time); e2e_T100 always runs in full")
     args = ap.parse_args()
     torch.set_num_threads(args.threads)
-    names = ["dynamics_b2n20.npz", "dynamics_b4n19.npz", "dynamics_b3n39.npz", "dynamics_b3n27_x30.npz", "block3_b2n20.npz"]
+    names = ["dynamics_b2n20.npz", "dynamics_b4n19.npz", "dynamics_b3n39.npz", "dynamics_b3n27_x30.npz", "block3_b2n20.npz",
+             "dynamics_b3n114.npz"]
     if not args.fast:
-        names += ["sampler_T20_b4n19.npz", "sampler_T8_rs1.npz", "inpaint_T5.npz", "merge_T10_L10.npz"]
+        names += ["sampler_T20_b4n19.npz", "sampler_T8_rs1.npz", "inpaint_T5.npz", "merge_T10_L10.npz",
+                  "sampler_T8_b3n101.npz", "inpaint_T5_rs1_b2n80.npz"]
     if args.long:
         names = ["e2e_T100_b2n27.npz", "inpaint_T250_rs1_b2.npz"]
     if args.only:
