@@ -326,14 +326,19 @@ def shape_scores(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: t
 MAX_REFINE_STEPS = 1024       # csrc/mcg_shape_refine.hip RF_MAX_STEPS
 
 
-def check_refine_steps(value) -> int:
-    """`refine_steps` as an int in 0..MAX_REFINE_STEPS (an integer type, not a bool), else ValueError."""
+def check_refine_steps(value, name: str = "refine_steps", lowest: int = 0, if_true: Optional[int] = None) -> int:
+    """An ascent step budget as an int in `lowest`..MAX_REFINE_STEPS (an integer type, not a bool), else a ValueError that
+    names `name`.  `if_true`: the budget True stands for, where the option accepts True (`refine_overlay`: 64, with
+    `lowest` 1); the default is the rule of `shape_overlay(refine_steps=...)`."""
+    if value is True and if_true is not None:
+        return if_true
     try:
         k = None if isinstance(value, bool) else operator.index(value)
     except TypeError:
         k = None
-    if k is None or not (0 <= k <= MAX_REFINE_STEPS):
-        raise ValueError(f"refine_steps must be an integer in 0..{MAX_REFINE_STEPS}, got {value!r}")
+    if k is None or not (lowest <= k <= MAX_REFINE_STEPS):
+        what = "an integer" if if_true is None else "True or an integer step budget"
+        raise ValueError(f"{name} must be {what} in {lowest}..{MAX_REFINE_STEPS}, got {value!r}")
     return int(k)
 
 
@@ -503,6 +508,30 @@ def check_max_pairwise_tanimoto(value) -> float:
     return float(value)
 
 
+def check_top_k(value) -> int:
+    """`top_k` as an int >= 1 (any integer type, numpy.int64 ...; not a bool, not a float), else ValueError."""
+    try:
+        k = None if isinstance(value, bool) else operator.index(value)
+    except TypeError:
+        k = None
+    if k is None or k < 1:
+        raise ValueError(f"top_k must be an integer >= 1, got {value!r}")
+    return int(k)
+
+
+def check_min_shape_tanimoto(value) -> float:
+    """`min_shape_tanimoto` as a float in [0, 1] (not NaN), else ValueError."""
+    if not (0.0 <= float(value) <= 1.0):
+        raise ValueError(f"min_shape_tanimoto must lie in [0, 1], got {value!r}")
+    return float(value)
+
+
+def ranking_key(score: Optional[float], sample_id: int):
+    """The sort key of the ranking order: descending score, ties to the lower sample id, a NaN score last; a score of
+    None (a call that does not score shape) ranks like every other None, which leaves the sample-id order."""
+    return (0.0 if score is None else -score if score == score else math.inf, sample_id)
+
+
 def select_diverse(scores: List[float], sample_ids: List[int], pair, max_pairwise_tanimoto: Optional[float],
                    top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None, chemical_pair=None,
                    max_pairwise_chemical_tanimoto: Optional[float] = None) -> List[int]:
@@ -517,8 +546,7 @@ def select_diverse(scores: List[float], sample_ids: List[int], pair, max_pairwis
     against an already kept molecule.  A score of None (a call that does not score shape) ranks like every other None:
     the walk is then in sample-id order."""
     keep = [i for i, s in enumerate(scores) if min_shape_tanimoto is None or s >= min_shape_tanimoto]
-    keep.sort(key=lambda i: (0.0 if scores[i] is None else -scores[i] if scores[i] == scores[i] else math.inf,
-                             sample_ids[i]))
+    keep.sort(key=lambda i: ranking_key(scores[i], sample_ids[i]))
     walks = [(m, t) for m, t in ((pair, max_pairwise_tanimoto), (chemical_pair, max_pairwise_chemical_tanimoto))
              if t is not None]
     if walks:

@@ -33,33 +33,18 @@ forced by the scope of this build:
   * `sample_seed` (opt-in, every generation entry): molecule i's size and every noise draw are a function of
     (sample_seed, i) alone - the same molecule in any batch, at any row, on any rank.  Seeded calls
     consume neither the CPU nor the device torch RNG.  Default (None): the reference's torch draw order, unchanged;
-  * `shape_scores`, `top_k`, `min_shape_tanimoto` (opt-in, every generation entry): every returned molecule carries the
-    Gaussian-volume shape Tanimoto of its returned heavy-atom coordinates against the reference (what `evaluate_samples`
-    reports), computed on the GPU without RDKit (`cheminformatics.shape_scores`); `top_k` / `min_shape_tanimoto` keep
-    the best / those above a threshold.  Off by default: nothing changes;
-  * `overlay` (opt-in, every generation entry): every returned molecule is posed onto the reference conformer, in the
-    reference's own coordinates, by a proper rigid transform found on the GPU (`cheminformatics.shape_overlay`).  Off
-    by default: nothing changes;
-  * `max_pairwise_tanimoto` (opt-in, every generation entry, with `overlay`): a shape-diverse selection by sphere
-    exclusion in ranking order on the pairwise shape Tanimoto of the posed molecules
-    (`cheminformatics.pairwise_shape_tanimoto`).  Off by default: nothing changes;
-  * `refine_overlay` (opt-in, every generation entry, with `overlay`): the pose is refined on the GPU by a rigid-body
-    ascent of the Gaussian overlap from each of the four principal-frame starts, kept where its shape Tanimoto is
-    strictly better (`cheminformatics.shape_overlay(refine_steps=...)`).  Off by default: nothing changes;
-  * `receptor`, `max_receptor_clashes` (opt-in, every generation entry, with `overlay`): the steric contacts of every
-    posed molecule with the receptor the reference ligand came from, measured on the GPU (`receptor.receptor_overlap`),
-    and a filter on the number of clashing atoms.  Off by default: nothing changes;
-  * `chemical_scores`, `reference_graph`, `max_chemical_tanimoto`, `unique`, `max_pairwise_chemical_tanimoto` (opt-in,
-    every generation entry): the chemical half of `evaluate_samples`, RDKit-free - every returned molecule's chemical
-    fingerprint and graph identity key computed on the GPU (`fingerprint.py`: the package's own Morgan-type
-    fingerprint, a labelled SUBSTITUTE for RDKit's, not bit-compatible with it), its Tanimoto to the reference's graph,
-    a filter on it, one molecule per graph, and a chemically diverse selection.  Off by default: nothing changes.
+  * opt-in keywords of every generation entry, all off by default (nothing changes); their meaning is stated once, in
+    `generate_conformers`' docstring, and what they do behind the generation lives in `postprocess.py`:
+      `shape_scores`, `top_k`, `min_shape_tanimoto`: score every returned molecule's shape against the reference; select;
+      `overlay`, `refine_overlay`: pose every returned molecule onto the reference conformer; refine that pose;
+      `max_pairwise_tanimoto`: a shape-diverse selection of the posed molecules;
+      `receptor`, `max_receptor_clashes`: steric contacts of the posed molecules with a receptor; a filter on them;
+      `chemical_scores`, `reference_graph`, `max_chemical_tanimoto`: chemical similarity to the reference; a filter;
+      `unique`, `max_pairwise_chemical_tanimoto`: one molecule per graph; a chemically diverse selection.
 """
 from __future__ import annotations
 
 import contextlib
-import dataclasses
-import operator
 import os
 import time
 import warnings
@@ -78,6 +63,7 @@ from .elements import class_z_from_decoder
 from .equivariant_diffusion import EquivariantDiffusion, PredefinedNoiseSchedule
 from . import distributed as mcg_dist
 from . import host_pool
+from . import postprocess
 from . import rdkit_order
 from . import receptor as mcg_receptor
 from . import fingerprint as mcg_fp
@@ -121,40 +107,6 @@ def _load_state_dict(src, device) -> dict:
     if isinstance(src, dict):
         return src["state_dict"] if "state_dict" in src else src
     return torch.load(src, map_location="cpu")["state_dict"]      # conformer_generator.py:90-102
-
-
-def _heavy_coords(mols: List):
-    """(padded [B, max n, 3], n_nodes [B]) of Mols' heavy-atom conformer positions."""
-    return cheminformatics.padded_coords([cheminformatics.mol_heavy_coords(m) for m in mols])
-
-
-@dataclasses.dataclass(frozen=True)
-class _ShapeRequest:
-    """The shape options of one generation call (`MLConformerGenerator._shape_request`): pose, then score, then select."""
-    ref_coord: torch.Tensor                       # the reference's heavy-atom coordinates [n,3] fp32, host
-    overlay: bool
-    scoring: bool                                 # `shape_scores`, or implied by any of the three selection options
-    top_k: Optional[int]
-    min_shape_tanimoto: Optional[float]
-    max_pairwise_tanimoto: Optional[float]
-    refine_steps: int = 0                         # `refine_overlay`: ascent steps of the refined pose, 0 = not refined
-    receptor: Optional[tuple] = None              # (coords [R,3] fp32, atomic numbers [R]) of its heavy atoms, host
-    max_receptor_clashes: Optional[int] = None
-
-
-@dataclasses.dataclass(frozen=True)
-class _ChemRequest:
-    """The chemical options of one generation call (`MLConformerGenerator._chem_request`)."""
-    ref_graph: Optional[tuple]                    # (atomic numbers, bond codes [n,n] int8) of the reference, when it scores
-    scoring: bool                                 # `chemical_scores`, or implied by `max_chemical_tanimoto`
-    max_chemical_tanimoto: Optional[float]
-    unique: bool
-    max_pairwise_chemical_tanimoto: Optional[float]
-
-
-def _ranking_key(score: Optional[float], sample_id: int):
-    """`select_diverse`'s order: descending score, ties to the lower sample id, NaN last; unscored: the sample id."""
-    return (0.0 if score is None else -score if score == score else float("inf"), sample_id)
 
 
 class MLConformerGenerator(torch.nn.Module):
@@ -356,107 +308,8 @@ class MLConformerGenerator(torch.nn.Module):
         raise ValueError(
             "Either a reference RDkit Mol object or context as torch.Tensor should be provided for generation.")
 
-    def _shape_request(self, reference_conformer, shape_scores: bool, top_k: Optional[int],
-                       min_shape_tanimoto: Optional[float], overlay: bool = False,
-                       max_pairwise_tanimoto: Optional[float] = None,
-                       refine_overlay: Union[bool, int] = False, receptor=None,
-                       max_receptor_clashes: Optional[int] = None) -> Optional[_ShapeRequest]:
-        """The call's shape options, or None when it asked for none of them (`top_k` / `min_shape_tanimoto` /
-        `max_pairwise_tanimoto` imply scoring).  Every refusal happens here, before any device work."""
-        if max_receptor_clashes is not None:
-            mcg_receptor.check_max_receptor_clashes(max_receptor_clashes)
-            if receptor is None:
-                raise ValueError("max_receptor_clashes needs a receptor")
-        if receptor is not None and not overlay:
-            raise ValueError("receptor needs overlay=True: molecules that are not posed onto the reference are not in "
-                             "the receptor's frame")
-        refine_steps = 0
-        if refine_overlay is not False:
-            refine_steps = self._refine_steps(refine_overlay)
-            if not overlay:
-                raise ValueError("refine_overlay needs overlay=True: it refines the pose onto the reference")
-        scoring = shape_scores or top_k is not None or min_shape_tanimoto is not None or max_pairwise_tanimoto is not None
-        if not (scoring or overlay):
-            return None
-        if max_pairwise_tanimoto is not None:
-            cheminformatics.check_max_pairwise_tanimoto(max_pairwise_tanimoto)
-            if not overlay:
-                raise ValueError("max_pairwise_tanimoto needs overlay=True: molecules that are not posed onto the reference "
-                                 "share no frame to compare them in")
-        what = "shape scores" if not overlay else "overlay"
-        if top_k is not None:
-            try:
-                k = operator.index(top_k)          # any integer type (numpy.int64 ...); not bool, not float
-            except TypeError:
-                k = None
-            if k is None or isinstance(top_k, bool) or k < 1:
-                raise ValueError(f"top_k must be an integer >= 1, got {top_k!r}")
-        if min_shape_tanimoto is not None and not (0.0 <= float(min_shape_tanimoto) <= 1.0):
-            raise ValueError(f"min_shape_tanimoto must lie in [0, 1], got {min_shape_tanimoto!r}")
-        if reference_conformer is None or reference_conformer is False:
-            raise ValueError(f"a reference conformer is needed for {what}; a bare reference_context has no "
-                             "coordinates")
-        if isinstance(getattr(self, "finisher", None), host_pool.TaskRef):
-            raise ValueError(f"{what} cannot be combined with a custom finisher: its results carry no coordinates "
-                             "this package can read")
-        ref_coord = self._reference_coord(reference_conformer)
-        cheminformatics.check_reference_atoms(int(ref_coord.shape[0]))
-        rec = None
-        if receptor is not None:
-            rec = mcg_receptor.load_receptor(receptor)
-            mcg_receptor.check_clear_of_reference(rec[0], ref_coord)
-        return _ShapeRequest(ref_coord, bool(overlay), bool(scoring), top_k, min_shape_tanimoto, max_pairwise_tanimoto,
-                             refine_steps, rec, max_receptor_clashes)
-
-    @staticmethod
-    def _refine_steps(refine_overlay) -> int:
-        """`refine_overlay` as a step budget: True = 64, an integer 1..1024 = itself; anything else is a ValueError."""
-        if refine_overlay is True:
-            return 64
-        try:
-            k = None if isinstance(refine_overlay, bool) else operator.index(refine_overlay)
-        except TypeError:
-            k = None
-        if k is None or not (1 <= k <= cheminformatics.MAX_REFINE_STEPS):
-            raise ValueError(f"refine_overlay must be True or an integer step budget in 1.."
-                             f"{cheminformatics.MAX_REFINE_STEPS}, got {refine_overlay!r}")
-        return int(k)
-
-    def _chem_request(self, reference_conformer, chemical_scores=False, reference_graph=None,
-                      max_chemical_tanimoto: Optional[float] = None, unique=False,
-                      max_pairwise_chemical_tanimoto: Optional[float] = None) -> Optional[_ChemRequest]:
-        """The call's chemical options, or None when it asked for none of them (`max_chemical_tanimoto` implies the
-        score).  Every refusal happens here, before any device work."""
-        mcg_fp.check_flag("chemical_scores", chemical_scores)
-        mcg_fp.check_flag("unique", unique)
-        if max_chemical_tanimoto is not None:
-            mcg_fp.check_threshold("max_chemical_tanimoto", max_chemical_tanimoto)
-        if max_pairwise_chemical_tanimoto is not None:
-            mcg_fp.check_threshold("max_pairwise_chemical_tanimoto", max_pairwise_chemical_tanimoto)
-        scoring = chemical_scores or max_chemical_tanimoto is not None
-        if reference_graph is not None and not scoring:
-            raise ValueError("reference_graph is only read with chemical_scores or max_chemical_tanimoto")
-        if not (scoring or unique or max_pairwise_chemical_tanimoto is not None):
-            return None
-        if isinstance(getattr(self, "finisher", None), host_pool.TaskRef):
-            raise ValueError("chemical scores cannot be combined with a custom finisher: its results carry no graph this "
-                             "package can read")
-        graph = None
-        if scoring:
-            src = reference_graph
-            if src is None and hasattr(reference_conformer, "GetAtoms") and hasattr(reference_conformer, "GetBonds"):
-                src = reference_conformer
-            if src is None:
-                raise ValueError("chemical scores need the reference's molecular graph: pass reference_graph= (a Mol, a "
-                                 "GeneratedMolecule or an (atomic_numbers, bond_orders) pair) or a reference conformer "
-                                 "with bonds; coordinates and a bare reference_context have none")
-            graph = mcg_fp.mol_graph(src)
-            if not 1 <= len(graph[0]) <= mcg_fp.MAX_GRAPH_ATOMS:
-                raise ValueError(f"the reference graph must have 1 to {mcg_fp.MAX_GRAPH_ATOMS} heavy atoms, got "
-                                 f"{len(graph[0])}")
-        return _ChemRequest(graph, bool(scoring), max_chemical_tanimoto, bool(unique), max_pairwise_chemical_tanimoto)
-
-    # device seams of the chemical step (stubbed by the host tests)
+    # device seams of the opt-in stages: `postprocess.py` calls them through the instance, the host tests stub them there
+    # the chemical step
     def _graph_fingerprints(self, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor):
         """(fingerprint [B,64] int32, graph key [B] int64, set bits [B]) of padded graphs (`fingerprint.graph_fingerprints`,
         unchecked: the codes come from the bond write-back or from `mol_graph`)."""
@@ -470,34 +323,7 @@ class MLConformerGenerator(torch.nn.Module):
         """[B,B] pairwise Tanimoto of fingerprints (`fingerprint.pairwise_fingerprint_tanimoto`)."""
         return mcg_fp.pairwise_fingerprint_tanimoto(fp)
 
-    def _chem_graphs(self, chem: _ChemRequest, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
-                     n_nodes: torch.Tensor):
-        """The chemical step of padded graphs, one fingerprint launch: (fingerprints [B,64], graph keys [B] int64,
-        chemical Tanimoto [B] to the reference's graph or None when the call does not score)."""
-        fp, key, _ = self._graph_fingerprints(atomic_numbers, bond_orders, n_nodes)
-        sim = None
-        if chem.scoring:
-            ref_fp = self._graph_fingerprints(*mcg_fp.pad_graphs([chem.ref_graph]))[0][0]
-            sim = self._chem_tanimoto(fp, ref_fp.to(fp.device))
-        return fp, key, sim
-
-    @staticmethod
-    def _chem_filter(chem: Optional[_ChemRequest], sims: List, keys: List, scores: List, sample_ids: List[int]
-                     ) -> List[int]:
-        """Positions that pass the call's chemical filters, in the input's order: `max_chemical_tanimoto` (a similarity
-        >= the value, or NaN, does not pass), then `unique` - of the molecules with one graph key the first in ranking
-        order (`_ranking_key`: by shape score where the call scores shape, else the lowest sample id)."""
-        pos = list(range(len(sample_ids)))
-        if chem is None:
-            return pos
-        if chem.max_chemical_tanimoto is not None:
-            pos = [i for i in pos if sims[i] < chem.max_chemical_tanimoto]
-        if chem.unique:
-            order = sorted(pos, key=lambda i: _ranking_key(scores[i], sample_ids[i]))
-            pos = mcg_fp.select_unique(keys, order)
-        return pos
-
-    # device seams of the shape step (stubbed by the host tests)
+    # the shape step
     def _score_coords(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
         """Shape Tanimoto [B] (device) of padded heavy-atom coordinates against the reference."""
         return cheminformatics.shape_scores(ref_coord, coords, n_nodes, self.device)[0]
@@ -511,12 +337,6 @@ class MLConformerGenerator(torch.nn.Module):
         """`_pose_coords` with the refined pose (`cheminformatics.shape_overlay(refine_steps=steps)`, device tensors)."""
         return cheminformatics.shape_overlay(ref_coord, coords, n_nodes, self.device, refine_steps=steps)
 
-    def _overlay_fn(self, req: _ShapeRequest):
-        """The posing seam of the call: `_pose_coords`, or `_pose_coords_refined` when it asked for refinement."""
-        if req.refine_steps > 0:
-            return lambda ref, coords, n: self._pose_coords_refined(ref, coords, n, req.refine_steps)
-        return self._pose_coords
-
     def _pair_coords(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
         """[B,B] pairwise shape Tanimoto (device) of padded heavy-atom coordinates posed onto the reference
         (`cheminformatics.pairwise_shape_tanimoto`)."""
@@ -526,184 +346,6 @@ class MLConformerGenerator(torch.nn.Module):
                          atomic_numbers: torch.Tensor) -> torch.Tensor:
         """Per-atom receptor overlap [B,N] (device) of padded posed heavy-atom coordinates (`receptor.receptor_overlap`)."""
         return mcg_receptor.receptor_overlap(rec, coords, n_nodes, atomic_numbers, self.device)
-
-    def _shape_tensors(self, req: Optional[_ShapeRequest], res: dict) -> dict:
-        """The shape step of one shard's result tensors: pose, then score (a score is the score of the returned
-        coordinates), then the receptor contacts of the returned coordinates.  `res` with `x` posed and the per-sample
-        tensors `overlay_tanimoto`, `pose` [B,12] (rotation row-major, then translation; NaN where posing failed),
-        `shape_tanimoto`, `receptor_clashes` (-1 where posing failed) and `receptor_max_overlap` (NaN there) added, as far
-        as the call asked."""
-        if req is None:
-            return res
-        if req.overlay:
-            ov = self._overlay_fn(req)(req.ref_coord, res["x"], res["n_nodes"])
-            res = dict(res, x=ov["coords"], overlay_tanimoto=ov["tanimoto"],
-                       pose=torch.cat([ov["rotation"].reshape(-1, 9), ov["translation"].reshape(-1, 3)], dim=1))
-        if req.scoring:
-            res = dict(res, shape_tanimoto=self._score_coords(req.ref_coord, res["x"], res["n_nodes"]))
-        if req.receptor is not None:
-            clashes, worst = mcg_receptor.clash_summary(
-                self._receptor_coords(req.receptor, res["x"], res["n_nodes"], res["elements"]))
-            posed = torch.isfinite(res["pose"]).all(dim=1).to(clashes.device)
-            res = dict(res, receptor_clashes=torch.where(posed, clashes, torch.full_like(clashes, -1)),
-                       receptor_max_overlap=torch.where(posed, worst, torch.full_like(worst, float("nan"))))
-        return res
-
-    def _score_mols(self, ref_coord: torch.Tensor, mols: List) -> List[Optional[float]]:
-        """Shape Tanimoto of finished Mols' heavy-atom conformer positions (None where a molecule was dropped), in ONE
-        batched device call."""
-        live = [k for k, m in enumerate(mols) if m is not None]
-        out: List[Optional[float]] = [None] * len(mols)
-        if live:
-            for k, v in zip(live, self._score_coords(ref_coord, *_heavy_coords([mols[k] for k in live])).cpu().tolist()):
-                out[k] = float(v)
-        return out
-
-    def _contact_mols(self, rec: tuple, mols: List, poses: List) -> List[Optional[tuple]]:
-        """(receptor_clashes, receptor_max_overlap) of posed Mols' heavy atoms (elements from `GetAtomicNum()`), in ONE
-        batched device call; None where a Mol was dropped or its pose failed (it is not in the receptor's frame)."""
-        live = [k for k, m in enumerate(mols) if m is not None and poses[k] is not None and poses[k][1] is not None]
-        out: List[Optional[tuple]] = [None] * len(mols)
-        if live:
-            coords, n = _heavy_coords([mols[k] for k in live])
-            z = torch.zeros(coords.shape[0], coords.shape[1], dtype=torch.long)
-            for j, k in enumerate(live):
-                heavy = [a.GetAtomicNum() for a in mols[k].GetAtoms() if a.GetAtomicNum() != 1]
-                z[j, : len(heavy)] = torch.tensor(heavy, dtype=torch.long)
-            clashes, worst = mcg_receptor.clash_summary(self._receptor_coords(rec, coords, n, z))
-            for j, (c, w) in enumerate(zip(clashes.cpu().tolist(), worst.cpu().tolist())):
-                out[live[j]] = (int(c), float(w))
-        return out
-
-    def _shape_objects(self, req: Optional[_ShapeRequest], done: List):
-        """The shape step of one shard's finished Mols (None = dropped), each stage in ONE batched device call: pose, every
-        conformer position moved (`cheminformatics.pose_mols`), then score (`_score_mols`).  Per Mol (scores, poses):
-        the shape Tanimoto and (overlay_tanimoto, rotation, translation); None where the call did not ask or the Mol
-        was dropped."""
-        none = [None] * len(done)
-        poses = (cheminformatics.pose_mols(req.ref_coord, done, overlay_fn=self._overlay_fn(req))
-                 if req is not None and req.overlay else none)
-        scores = self._score_mols(req.ref_coord, done) if req is not None and req.scoring else list(none)
-        return scores, poses
-
-    def _finished_shape(self, req: Optional[_ShapeRequest], done: List):
-        """(scores, poses, contacts) of one shard's finished Mols: `_shape_objects`, then the receptor contacts of the
-        posed Mols (`_contact_mols`; None per Mol where the call passed no receptor)."""
-        scores, poses = self._shape_objects(req, done)
-        contacts = (self._contact_mols(req.receptor, done, poses) if req is not None and req.receptor is not None
-                    else [None] * len(done))
-        return scores, poses, contacts
-
-    @staticmethod
-    def _clash_filter(req: Optional[_ShapeRequest], mols: List, contacts: List[Optional[tuple]]) -> List[int]:
-        """Positions of `mols` that pass `max_receptor_clashes` (all of them when the call set none): at most that many
-        clashing atoms; a molecule without contacts (its pose failed) does not pass."""
-        if req is None or req.max_receptor_clashes is None:
-            return list(range(len(mols)))
-        return [i for i, c in enumerate(contacts) if c is not None and c[0] <= req.max_receptor_clashes]
-
-    @staticmethod
-    def _select(req: Optional[_ShapeRequest], mols: List, scores: List[float], sample_ids: List[int], pair_fn,
-                chem: Optional[_ChemRequest] = None, chem_pair_fn=None) -> List:
-        """`mols` through the call's selection: threshold, then sphere exclusion at `max_pairwise_tanimoto` (`pair_fn()`:
-        the pair matrix of `mols`, only called when it is set) and at `max_pairwise_chemical_tanimoto` (`chem_pair_fn()`,
-        likewise) in one walk, then `top_k` (`cheminformatics.select_diverse`); all of them when the call selects
-        nothing."""
-        shape_sel = req is not None and not (req.top_k is None and req.min_shape_tanimoto is None
-                                             and req.max_pairwise_tanimoto is None)
-        chem_t = None if chem is None else chem.max_pairwise_chemical_tanimoto
-        if not shape_sel and chem_t is None:
-            return mols
-        pair_t = req.max_pairwise_tanimoto if shape_sel else None
-        keep = cheminformatics.select_diverse(scores, sample_ids, pair_fn() if pair_t is not None else None, pair_t,
-                                              req.top_k if shape_sel else None,
-                                              req.min_shape_tanimoto if shape_sel else None,
-                                              chem_pair_fn() if chem_t is not None else None, chem_t)
-        return [mols[i] for i in keep]
-
-    def _return_records(self, req: Optional[_ShapeRequest], res: dict, row_ids: Optional[torch.Tensor],
-                        optimise_geometry: bool, chem: Optional[_ChemRequest] = None) -> List:
-        """What a call returns without a finisher: the `GeneratedMolecule` records of the rows this rank returns (sample
-        ids `row_ids`, default 0..B-1; one D2H), filtered by the validity proxy, the clash filter and the chemical
-        filters (fingerprints of the rows this rank returns: one launch behind the gather), then selected, the pair
-        matrices taken from the posed rows and from their fingerprints."""
-        chem_kw, fp = {}, None
-        if chem is not None:
-            fp, key, sim = self._chem_graphs(chem, res["elements"], res["bond"], res["n_nodes"])
-            chem_kw = dict(chemical_tanimoto=sim, graph_key=key if chem.scoring or chem.unique else None)
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)       # (the D2H copies below would wait for the device anyway: keep that out of the figure)
-        t0 = time.perf_counter()
-        mols = molecules_from_tensors(res["x"], res["elements"], res["bond"], res["n_nodes"], res["valid"],
-                                      sample_ids=row_ids, shape_tanimoto=res.get("shape_tanimoto"),
-                                      overlay_tanimoto=res.get("overlay_tanimoto"), pose=res.get("pose"),
-                                      receptor_clashes=res.get("receptor_clashes"),
-                                      receptor_max_overlap=res.get("receptor_max_overlap"), **chem_kw)
-        self.last_host_assembly_ms = (time.perf_counter() - t0) * 1e3      # D2H of the result tensors + record views
-        kept, self.last_valid_fraction = _finish(mols, optimise_geometry, use_rdkit=False)    # no finisher: the proxy
-        kept = [kept[i] for i in self._clash_filter(req, kept, [m.receptor_contacts for m in kept])]
-        if chem is not None:                          # a record view knows its row of the batch (`_b`)
-            keys = key.cpu().tolist() if chem.unique else None
-            kept = [kept[i] for i in self._chem_filter(chem, [m.chemical_tanimoto for m in kept],
-                                                       [keys[m._b] for m in kept] if chem.unique else None,
-                                                       [m.shape_tanimoto for m in kept], [m.sample_id for m in kept])]
-
-        def pair():
-            row = {id(m): b for b, m in enumerate(mols)}
-            idx = torch.tensor([row[id(m)] for m in kept], dtype=torch.long, device=res["x"].device)
-            return self._pair_coords(req.ref_coord, res["x"].index_select(0, idx),
-                                     res["n_nodes"].reshape(-1).to(res["x"].device).index_select(0, idx))
-
-        def chem_pair():
-            return self._chem_pair(fp.index_select(0, torch.tensor([m._b for m in kept], dtype=torch.long,
-                                                                   device=fp.device)))
-        return self._select(req, kept, [m.shape_tanimoto for m in kept], [m.sample_id for m in kept], pair, chem,
-                            chem_pair)
-
-    def _return_objects(self, req: Optional[_ShapeRequest], done: List, scores: List, poses: List, contacts: List,
-                        row_ids: Optional[torch.Tensor], sample_seed: Optional[int],
-                        chem: Optional[_ChemRequest] = None) -> List:
-        """What a call returns through a finisher: the finished Mols of the rows this rank returns (None = dropped; sample
-        ids `row_ids`, default 0..B-1) get their properties - `sample_id` (seeded calls), `overlay_tanimoto`,
-        `shape_tanimoto`, `receptor_clashes`, `receptor_max_overlap`: set here, behind the object gather, which does not
-        carry Mol properties - then the live ones pass the clash filter and are selected, the pair matrix taken from
-        their posed heavy atoms.  The chemical step reads the finished Mols' own graphs (`fingerprint.mol_graph`), all in
-        one batched device call: double property `chemical_tanimoto`, string property `graph_key` (the unsigned 64-bit
-        key in decimal: it does not fit an int property)."""
-        from . import rdkit_finish
-        ids = list(range(len(done))) if row_ids is None else row_ids.tolist()
-        if sample_seed is not None:
-            rdkit_finish.tag_sample_ids(done, ids)
-        self.last_host_assembly_ms = 0.0
-        live = [i for i, m in enumerate(done) if m is not None]
-        self.last_valid_fraction = len(live) / len(done) if done else 0.0
-        rdkit_finish.tag_scores(done, "overlay_tanimoto", [None if p is None else p[0] for p in poses])
-        rdkit_finish.tag_scores(done, "shape_tanimoto", scores)
-        rdkit_finish.tag_contacts(done, contacts)
-        fp = None
-        if chem is not None and live:
-            fp, key, sim = self._chem_graphs(chem, *mcg_fp.pad_graphs([mcg_fp.mol_graph(done[i]) for i in live]))
-            fp_row = {i: k for k, i in enumerate(live)}
-            keys = [int(k) & 0xFFFFFFFFFFFFFFFF for k in key.cpu().tolist()]
-            sims = [None] * len(live) if sim is None else [float(v) for v in sim.cpu().tolist()]
-            if chem.scoring:
-                rdkit_finish.tag_scores([done[i] for i in live], "chemical_tanimoto", sims)
-            if chem.scoring or chem.unique:
-                rdkit_finish.tag_graph_keys([done[i] for i in live], keys)
-        live = [live[i] for i in self._clash_filter(req, live, [contacts[i] for i in live])]
-        if fp is not None:
-            live = [live[i] for i in self._chem_filter(chem, [sims[fp_row[i]] for i in live],
-                                                       [keys[fp_row[i]] for i in live], [scores[i] for i in live],
-                                                       [ids[i] for i in live])]
-        picked = [done[i] for i in live]
-
-        def chem_pair():
-            if fp is None:                        # nothing left to compare
-                return torch.zeros(0, 0)
-            return self._chem_pair(fp.index_select(0, torch.tensor([fp_row[i] for i in live], dtype=torch.long,
-                                                                   device=fp.device)))
-        return self._select(req, picked, [scores[i] for i in live], [ids[i] for i in live],
-                            lambda: self._pair_coords(req.ref_coord, *_heavy_coords(picked)), chem, chem_pair)
 
     def _executor(self):
         """Where the poolable host tasks run: the process-wide `HostPool` with `n_host_workers` workers and this generator's
@@ -884,18 +526,19 @@ class MLConformerGenerator(torch.nn.Module):
         heavy atom), max_receptor_clashes other than an integer >= 0 or without a receptor, and a custom finisher."""
         if sample_seed is not None:
             seeding.check_seed(sample_seed)
-        req = self._shape_request(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
-                                  max_pairwise_tanimoto, refine_overlay, receptor, max_receptor_clashes)
-        chem = self._chem_request(reference_conformer, chemical_scores, reference_graph, max_chemical_tanimoto, unique,
-                                  max_pairwise_chemical_tanimoto)
+        req = postprocess.parse_request(self, reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
+                                        max_pairwise_tanimoto, refine_overlay, receptor, max_receptor_clashes,
+                                        chemical_scores, reference_graph, max_chemical_tanimoto, unique,
+                                        max_pairwise_chemical_tanimoto)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
         keyed = () if sample_seed is None else (sample_seed, None)   # unseeded: the positional call of before
         res = self._generate_shard(ref_context, ref_n_atoms, variance, None, n_samples, resample_steps, fixed_fragment,
                                    inertial_fragment_matching, blend_power, ifm_diffusion_level, optimise_geometry, *keyed)
         if getattr(self, "finisher", None) is None:
-            return self._return_records(req, self._shape_tensors(req, res), None, optimise_geometry, chem)
+            return postprocess.return_records(self, req, postprocess.measure_tensors(self, req, res), None,
+                                              optimise_geometry)
         done = self._collect_finish(n_samples)    # finished per group while the later groups were still on their way
-        return self._return_objects(req, done, *self._finished_shape(req, done), None, sample_seed, chem)
+        return postprocess.return_finished(self, req, postprocess.measure_finished(self, req, done), None, sample_seed)
 
     @torch.no_grad()
     def generate_conformers_sharded(self, reference_conformer=None, n_samples: int = 10, variance: int = 2,
@@ -943,17 +586,17 @@ class MLConformerGenerator(torch.nn.Module):
             if seed is not None:
                 raise ValueError("pass either seed (per-rank device generator) or sample_seed (keyed stream), not both")
             seeding.check_seed(sample_seed)
-        req = self._shape_request(reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
-                                  max_pairwise_tanimoto, refine_overlay, receptor, max_receptor_clashes)
-        chem = self._chem_request(reference_conformer, chemical_scores, reference_graph, max_chemical_tanimoto, unique,
-                                  max_pairwise_chemical_tanimoto)
+        req = postprocess.parse_request(self, reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
+                                        max_pairwise_tanimoto, refine_overlay, receptor, max_receptor_clashes,
+                                        chemical_scores, reference_graph, max_chemical_tanimoto, unique,
+                                        max_pairwise_chemical_tanimoto)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)
         hi_n = min(ref_n_atoms + variance, self.max_n_nodes)
         # decided from the configuration, not from what this rank's shard happened to produce: every rank takes the same
         # path through the collectives (an EMPTY shard has no stage of its own making)
         finishing = getattr(self, "finisher", None) is not None
-        finished: List = []       # (Mol, score, pose, contacts) per sample of this rank's shard, where a finisher runs
+        finished: List = []       # `postprocess.measure_finished` of this rank's shard, where a finisher runs
 
         def run_shard(sizes_shard, index):
             keyed = () if sample_seed is None else (sample_seed, index)
@@ -961,12 +604,12 @@ class MLConformerGenerator(torch.nn.Module):
                                        fixed_fragment, inertial_fragment_matching, blend_power, ifm_diffusion_level,
                                        optimise_geometry, *keyed)
             if not finishing:
-                return self._shape_tensors(req, res)      # posed / scored on this rank's GPU, gathered with the rest
+                return postprocess.measure_tensors(self, req, res)      # on this rank's GPU, gathered with the rest
             # collected HERE, in front of the status exchange: a finish that raises on one rank (a dead worker, a custom
             # finisher's exception, a result-count mismatch) makes EVERY rank raise ShardError instead of leaving the
             # others parked in the object gather
             done = self._collect_finish(int(index.numel()))
-            finished[:] = zip(done, *self._finished_shape(req, done))
+            finished[:] = postprocess.measure_finished(self, req, done)
             return res
 
         def seed_device(s):
@@ -989,29 +632,8 @@ class MLConformerGenerator(torch.nn.Module):
         _, rank = mcg_dist.world_and_rank(group)
         row_ids = shards[rank] if (dst is not None and rank != dst and len(shards) > 1) else None
         if not finishing:
-            return self._return_records(req, res, row_ids, optimise_geometry, chem)
-        rows = mcg_dist.gather_objects(finished, shards, group, dst)      # the Mols travel as objects, with their scores
-        return self._return_objects(req, [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows],
-                                    [r[3] for r in rows], row_ids, sample_seed, chem)
+            return postprocess.return_records(self, req, res, row_ids, optimise_geometry)
+        samples = mcg_dist.gather_objects(finished, shards, group, dst)   # the Mols travel as objects, with their scores
+        return postprocess.return_finished(self, req, samples, row_ids, sample_seed)
 
-    @torch.no_grad()
-    def forward(self, reference_conformer=None, n_samples: int = 10, variance: int = 2,
-                reference_context: torch.Tensor = None, n_atoms: int = None, optimise_geometry: bool = True,
-                resample_steps: int = 0, fixed_fragment=None, inertial_fragment_matching: bool = True,
-                blend_power: int = 3, ifm_diffusion_level: int = 50, sample_seed: Optional[int] = None,
-                shape_scores: bool = False, top_k: Optional[int] = None,
-                min_shape_tanimoto: Optional[float] = None, overlay: bool = False,
-                max_pairwise_tanimoto: Optional[float] = None, refine_overlay: Union[bool, int] = False, receptor=None,
-                max_receptor_clashes: Optional[int] = None, chemical_scores: bool = False, reference_graph=None,
-                max_chemical_tanimoto: Optional[float] = None, unique: bool = False,
-                max_pairwise_chemical_tanimoto: Optional[float] = None) -> List:
-        return self.generate_conformers(reference_conformer, n_samples, variance, reference_context, n_atoms,
-                                        optimise_geometry, resample_steps, fixed_fragment,
-                                        inertial_fragment_matching, blend_power, ifm_diffusion_level,
-                                        sample_seed=sample_seed, shape_scores=shape_scores, top_k=top_k,
-                                        min_shape_tanimoto=min_shape_tanimoto, overlay=overlay,
-                                        max_pairwise_tanimoto=max_pairwise_tanimoto, refine_overlay=refine_overlay,
-                                        receptor=receptor, max_receptor_clashes=max_receptor_clashes,
-                                        chemical_scores=chemical_scores, reference_graph=reference_graph,
-                                        max_chemical_tanimoto=max_chemical_tanimoto, unique=unique,
-                                        max_pairwise_chemical_tanimoto=max_pairwise_chemical_tanimoto)
+    forward = generate_conformers      # `__call__`: the same signature, defaults and `no_grad` by construction

@@ -129,6 +129,12 @@ class GeneratedMolecule:
         return self._sid
 
     @property
+    def batch_row(self) -> int:
+        """The row of its call's result tensors that a record built by `molecules_from_tensors` views - what indexes the
+        device tensors of the same batch (posed coordinates, fingerprints); -1 for a record built by hand."""
+        return self._b
+
+    @property
     def atomic_numbers(self) -> List[int]:
         if self._z is None:
             self._z = self._batch.elements[self._b, : self._batch.n[self._b]].tolist()

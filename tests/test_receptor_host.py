@@ -167,7 +167,7 @@ def _pocket(n=40):
 @pytest.mark.parametrize("entry", ["generate_conformers", "generate_conformers_sharded", "forward"])
 def test_receptor_refusals_happen_before_any_device_work(entry):
     gen = _shell_generator()
-    gen._generate_shard = gen._score_coords = gen._score_mols = gen._pose_coords = _no_device
+    gen._generate_shard = gen._score_coords = gen._pose_coords = _no_device
     gen._pair_coords = gen._receptor_coords = _no_device
     call = getattr(gen, entry)
     pocket = _pocket()

@@ -70,7 +70,7 @@ def test_select_diverse_edge_cases():
 def test_diversity_refusals_happen_before_any_device_work(entry):
     from ml_conformer_generator_amd import host_pool as HP
     gen = _shell_generator()
-    gen._generate_shard = gen._score_coords = gen._score_mols = gen._pose_coords = _no_device
+    gen._generate_shard = gen._score_coords = gen._pose_coords = _no_device
     gen._pair_coords = _no_device
     call = getattr(gen, entry)
     ctx = torch.tensor([50.0, 100.0, 130.0])

@@ -65,7 +65,7 @@ def _stub_overlay(shift_of):
 def test_overlay_refusals_happen_before_any_device_work(entry):
     from ml_conformer_generator_amd import host_pool as HP
     gen = _shell_generator()
-    gen._generate_shard = gen._score_coords = gen._score_mols = gen._pose_coords = _no_device
+    gen._generate_shard = gen._score_coords = gen._pose_coords = _no_device
     call = getattr(gen, entry)
     ctx = torch.tensor([50.0, 100.0, 130.0])
     for kw in (dict(reference_context=ctx, n_atoms=17, overlay=True),            # nothing to pose onto

@@ -9,6 +9,7 @@ import torch
 
 import overlay_refine_ref as RR
 from conftest import load_golden
+from ml_conformer_generator_amd import postprocess
 from test_shape_overlay_host import PosedMol, _no_device, _ref, _rot_z, _shell_generator, _stub_overlay, _stub_shard
 
 BAD_BUDGETS = (0, -3, 2.5, 64.0, "64", None, 1025)
@@ -18,7 +19,7 @@ BAD_BUDGETS = (0, -3, 2.5, 64.0, "64", None, 1025)
 @pytest.mark.parametrize("entry", ["generate_conformers", "generate_conformers_sharded", "forward"])
 def test_refine_refusals_happen_before_any_device_work(entry):
     gen = _shell_generator()
-    gen._generate_shard = gen._score_coords = gen._score_mols = gen._pose_coords = _no_device
+    gen._generate_shard = gen._score_coords = gen._pose_coords = _no_device
     gen._pose_coords_refined = gen._pair_coords = _no_device
     call = getattr(gen, entry)
     with pytest.raises(ValueError, match="overlay=True"):
@@ -61,11 +62,11 @@ def test_an_empty_batch_returns_every_key_of_the_call():
 def test_the_request_carries_the_step_budget():
     gen = _shell_generator()
     gen._reference_coord = lambda r: torch.as_tensor(r, dtype=torch.float32)
-    req = gen._shape_request(_ref(), False, None, None, overlay=True)
+    req = postprocess.parse_request(gen, _ref(), False, None, None, overlay=True)
     assert req.refine_steps == 0
-    assert gen._shape_request(_ref(), False, None, None, True, None, True).refine_steps == 64
-    assert gen._shape_request(_ref(), False, None, None, True, None, np.int32(5)).refine_steps == 5
-    assert gen._shape_request(_ref(), False, None, None, True, None, 1024).refine_steps == 1024
+    assert postprocess.parse_request(gen, _ref(), False, None, None, True, None, True).refine_steps == 64
+    assert postprocess.parse_request(gen, _ref(), False, None, None, True, None, np.int32(5)).refine_steps == 5
+    assert postprocess.parse_request(gen, _ref(), False, None, None, True, None, 1024).refine_steps == 1024
 
 
 # ----------------------------------------------------------------------------------------------- C entry
@@ -148,9 +149,10 @@ def test_object_path_takes_the_refined_seam_only_when_asked():
         return [PosedMol([[0.5, 0, 0]] * 4 + [[0, 0, 1.0]], z=[6] * 4 + [1]), None]
     for refine, want_call, shift in ((False, ("plain",), 1.5), (True, ("refined", 64), 2.5), (3, ("refined", 3), 2.5)):
         calls.clear()
-        req = gen._shape_request(_ref(), False, None, None, True, None, refine)
+        req = postprocess.parse_request(gen, _ref(), False, None, None, True, None, refine)
         done = mols()
-        scores, poses = gen._shape_objects(req, done)
+        samples = postprocess.measure_finished(gen, req, done)
+        scores, poses = [s[1] for s in samples], [s[2] for s in samples]
         assert calls == [want_call] and scores == [None, None] and poses[1] is None
         score, rot, trans = poses[0]
         assert score == pytest.approx(shift) and torch.allclose(rot, _rot_z(90.0)) and trans.tolist() == [shift, 0, 0]

@@ -10,6 +10,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from ml_conformer_generator_amd import postprocess
 from ml_conformer_generator_amd.cheminformatics import mol_heavy_coords, padded_coords, select_scored
 from ml_conformer_generator_amd.handoff import GeneratedMolecule, molecules_from_tensors
 
@@ -56,7 +57,7 @@ def _no_device(*args, **kwargs):
 def test_refusals_happen_before_any_device_work(entry):
     from ml_conformer_generator_amd import host_pool as HP
     gen = _shell_generator()
-    gen._generate_shard = gen._score_coords = gen._score_mols = _no_device
+    gen._generate_shard = gen._score_coords = _no_device
     call = getattr(gen, entry)
     ctx = torch.tensor([50.0, 100.0, 130.0])
     cases = [
@@ -183,7 +184,7 @@ def test_coordinates_come_from_the_conformer_heavy_atoms_only():
         seen.append((coords.clone(), n.clone()))
         return coords[:, 0, 0] / 10.0
     gen._score_coords = score
-    out = gen._score_mols(_ref(), [m, None, FakeMol([[7.0, 0, 0]] * 3)])
+    out = postprocess.score_mols(gen, _ref(), [m, None, FakeMol([[7.0, 0, 0]] * 3)])
     assert out == [0.0, None, pytest.approx(0.7)] and len(seen) == 1 and seen[0][1].tolist() == [2, 3]
 
 
