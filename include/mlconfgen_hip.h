@@ -503,6 +503,48 @@ int mcg_graph_fingerprint(const int32_t* z, const int8_t* bonds, const int32_t* 
 int mcg_fingerprint_tanimoto(const uint32_t* fp, const uint32_t* ref_fp, int B, float* out, void* stream);
 int mcg_fingerprint_pair_tanimoto(const uint32_t* fp, int B, float* out, void* stream);
 
+/* ---- Solid references ("Solid references"): a watertight triangle mesh as the reference shape.
+ * tri[F,9] = the corners a, b, c of every face (outward normals: counter-clockwise seen from outside), device memory.
+ *   w(p) = (1 / 4 pi) sum_f 2 atan2(a . (b x c), |a||b||c| + (a . b)|c| + (b . c)|a| + (c . a)|b|),  a, b, c = corner - p
+ * the generalized winding number: +1 inside a closed outward mesh, 0 outside; an open mesh is a legal input.  fp32, one
+ * lane per point, the triangles staged in tiles of 256.  The triangle range is cut into mcg_mesh_splits(F) parts (a
+ * function of F alone: 4 tiles per part, at most 64 parts) walked by different workgroups, their sums added in part order
+ * by a second launch through partial_ws[mcg_mesh_splits(F) * P] (not read, and may be NULL, when there is one part).
+ * Every sum has one order, so w of a point has the same bits whatever P, its place among the points, array or grid
+ * mode, and in mcg_mesh_atoms_outside.  A point on a corner of the mesh contributes atan2(0, 0) = 0, not NaN; the value
+ * at a point exactly ON the surface is unspecified.  A non-finite point gets NaN, the other points are unaffected.
+ *   mcg_mesh_winding:   w_out[P] of points[P,3], or - points NULL - w_out[n^3] of the grid points of axes[3,n] in
+ *                       meshgrid(indexing="ij") flatten order (the grid of the shape kernels).  Exactly one of points / axes.
+ *   mcg_mesh_occupancy: grid mode, writing f_out[idx] = |w| > 0.5 ? 1 : 0 - the density of the solid, for
+ *                       mcg_shape_tanimoto_field / mcg_shape_overlay_field.  The indicator function as the density of a solid
+ *                       is this package's own choice (the reference scores molecules against molecules only).
+ *   mcg_mesh_atoms_outside: posed[B,N,3] with n_nodes_dev[b] real atoms (clamped to [0, N] on the device): outside[b] = the
+ *                       real atoms with |w| <= 0.5, or -1 for a row with a non-finite real coordinate; w_out[B,N] (optional,
+ *                       NULL = not wanted): the atoms' winding numbers, 0 on padded atoms.  One launch, one 64-lane
+ *                       workgroup per row, no work space.
+ *   mcg_shape_tanimoto_field / mcg_shape_overlay_field: mcg_shape_tanimoto / mcg_shape_overlay with the density launch
+ *                       skipped and f[n^3] supplied by the caller: the same kernels, outputs and failure rows; with f = what
+ *                       the density launch would have written (their f_scratch), the same bits.
+ * MCG_ERR_ARG, nothing launched: a null required buffer, F outside 1..MCG_MESH_MAX_FACES, P outside 1..MCG_MESH_MAX_POINTS,
+ * n outside 2..MCG_MESH_MAX_N, both or neither of points / axes, partial_ws NULL when mcg_mesh_splits(F) > 1, B < 1,
+ * N outside 1..64 (atoms_outside, overlay_field; B * 64 <= MCG_MESH_MAX_POINTS), N < 1 or R < 1 (tanimoto_field).
+ * mcg_mesh_splits returns 0 for an F outside the range. */
+#define MCG_MESH_MAX_FACES 1048576
+#define MCG_MESH_MAX_POINTS 16777216
+#define MCG_MESH_MAX_N 256
+int mcg_mesh_splits(int F);
+int mcg_mesh_winding(const float* tri, int F, const float* points, int P, const float* axes, int n, float* w_out,
+                     float* partial_ws, void* stream);
+int mcg_mesh_occupancy(const float* tri, int F, const float* axes, int n, float* f_out, float* partial_ws, void* stream);
+int mcg_mesh_atoms_outside(const float* tri, int F, const float* posed, const int32_t* n_nodes_dev, int B, int N,
+                           int32_t* outside, float* w_out, void* stream);
+int mcg_shape_tanimoto_field(const float* f, const float* cand, const int32_t* n_nodes_dev, int B, int N, const float* rot,
+                             int R, const float* axes, int n, float alpha, float amplitude, float* score, void* stream);
+int mcg_shape_overlay_field(const float* f, const float* ref_xform, const float* frames, const float* xform,
+                            const int32_t* n_nodes_dev, int B, int N, const float* rot, const float* axes, int n,
+                            float alpha, float amplitude, float* score, float* best, int32_t* which, int32_t* flipped,
+                            float* pose, float* posed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,9 +9,10 @@ from .config import (ATOM_DECODER, CONTEXT_NORMS, DIMENSION, MAX_N_NODES,
                      MIN_N_NODES, NUM_BOND_TYPES)
 
 _FINGERPRINT = ("graph_fingerprints", "fingerprint_tanimoto", "pairwise_fingerprint_tanimoto", "mol_graph", "select_unique")
+_MESH = ("load_mesh", "mass_properties", "mesh_context", "solid_frame")
 
 __all__ = ["MLConformerGenerator", "evaluate_samples", "ATOM_DECODER", "CONTEXT_NORMS", "DIMENSION",
-           "MAX_N_NODES", "MIN_N_NODES", "NUM_BOND_TYPES", *_FINGERPRINT]
+           "MAX_N_NODES", "MIN_N_NODES", "NUM_BOND_TYPES", *_FINGERPRINT, *_MESH]
 
 
 def __getattr__(name):
@@ -25,4 +26,7 @@ def __getattr__(name):
     if name in _FINGERPRINT:             # chemical fingerprints and graph keys (fingerprint.py: a substitute for RDKit's)
         from . import fingerprint
         return getattr(fingerprint, name)
+    if name in _MESH:                    # watertight meshes as reference shapes (mesh.py: host side, no trimesh)
+        from . import mesh
+        return getattr(mesh, name)
     raise AttributeError(name)

@@ -65,6 +65,13 @@ SIGNATURES: Dict[str, tuple] = {
     "mcg_graph_fingerprint": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "mcg_fingerprint_tanimoto": (_i, [_vp, _vp, _i, _vp, _vp]),
     "mcg_fingerprint_pair_tanimoto": (_i, [_vp, _i, _vp, _vp]),
+    "mcg_mesh_splits": (_i, [_i]),
+    "mcg_mesh_winding": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "mcg_mesh_occupancy": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "mcg_mesh_atoms_outside": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "mcg_shape_tanimoto_field": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _f, _f, _vp, _vp]),
+    "mcg_shape_overlay_field": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp]),
     "mcg_handoff": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp]),
     "mcg_handoff_ex": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcg_handoff_elements": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -501,6 +501,262 @@ def pairwise_shape_tanimoto(reference_coord: torch.Tensor, coords: torch.Tensor,
     return out
 
 
+# ----------------------------------------------------------------------------- solid references (watertight meshes)
+MAX_MESH_POINTS = 1 << 24     # include/mlconfgen_hip.h MCG_MESH_MAX_POINTS
+
+
+def _winding_ws(F: int, P: int, dev) -> Optional[torch.Tensor]:
+    """The partial-sum work space of a winding launch over F triangles and P points (None: one part, none needed)."""
+    S = int(_lib.lib().mcg_mesh_splits(int(F)))
+    if S < 1:
+        raise ValueError(f"a mesh of {F} faces is outside what the winding kernel takes")
+    return torch.empty(S * P, device=dev) if S > 1 else None
+
+
+def _triangles(triangles, dev) -> torch.Tensor:
+    tri = torch.as_tensor(triangles, dtype=torch.float32).reshape(-1, 9).to(dev).contiguous()
+    if tri.shape[0] < 1:
+        raise ValueError("no triangles")
+    return tri
+
+
+@torch.no_grad()
+def mesh_winding(triangles, points: Optional[torch.Tensor] = None, axes: Optional[torch.Tensor] = None, device=None
+                 ) -> torch.Tensor:
+    """Generalized winding number (`mcg_mesh_winding`, fp32, on the device) of `triangles` [F,3,3] (or [F,9]: corners a, b,
+    c per face, outward) at `points` [P,3], or - `axes` [3,n] - at the n^3 grid points in meshgrid(indexing="ij") flatten
+    order: +-1 inside a closed mesh, 0 outside; an open mesh is legal.  A point's value has the same bits whatever P, its
+    position and the mode; a non-finite point gets NaN; exactly on the surface the value is unspecified."""
+    if (points is None) == (axes is None):
+        raise ValueError("pass either points or axes")
+    src = points if points is not None else axes
+    dev = torch.device(device if device is not None else (src.device if src.is_cuda else "cuda:0"))
+    tri = _triangles(triangles, dev)
+    F = int(tri.shape[0])
+    if points is not None:
+        pts = points.to(dev, torch.float32).reshape(-1, 3).contiguous()
+        P = int(pts.shape[0])
+        out = torch.empty(P, device=dev)
+        if P == 0:
+            return out
+        args = (_lib.dptr(pts), P, None, 0)
+    else:
+        ax = axes.to(dev, torch.float32).contiguous()
+        n = int(ax.shape[1])
+        P = n ** 3
+        out = torch.empty(P, device=dev)
+        args = (None, 0, _lib.dptr(ax), n)
+    ws = _winding_ws(F, P, dev)
+    _lib.check(_lib.lib().mcg_mesh_winding(_lib.dptr(tri), F, *args, _lib.dptr(out), _lib.dptr(ws),
+                                           _lib.current_stream_ptr(dev)), "mcg_mesh_winding")
+    return out
+
+
+@torch.no_grad()
+def mesh_occupancy(triangles, axes: torch.Tensor, device=None) -> torch.Tensor:
+    """f [n^3] fp32 on the device: 1 where |winding number| > 0.5 at the grid points of `axes` [3,n], else 0
+    (`mcg_mesh_occupancy`): the density of the solid the mesh bounds, on the grid the shape kernels score on."""
+    dev = torch.device(device if device is not None else (axes.device if axes.is_cuda else "cuda:0"))
+    tri = _triangles(triangles, dev)
+    ax = axes.to(dev, torch.float32).contiguous()
+    n = int(ax.shape[1])
+    f = torch.empty(n ** 3, device=dev)
+    ws = _winding_ws(int(tri.shape[0]), n ** 3, dev)
+    _lib.check(_lib.lib().mcg_mesh_occupancy(_lib.dptr(tri), int(tri.shape[0]), _lib.dptr(ax), n, _lib.dptr(f),
+                                             _lib.dptr(ws), _lib.current_stream_ptr(dev)), "mcg_mesh_occupancy")
+    return f
+
+
+@torch.no_grad()
+def mesh_atoms_outside(triangles, coords: torch.Tensor, n_nodes: torch.Tensor, device=None, with_winding: bool = False):
+    """outside [B] int32 on the device: how many real atoms of each row of `coords` [B,N,3] have |winding number| <= 0.5
+    with respect to `triangles` (`mcg_mesh_atoms_outside`); -1 for a row with a non-finite real coordinate.
+    `with_winding`: also the atoms' winding numbers [B,N] (0 on padded atoms)."""
+    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
+    B, N = int(coords.shape[0]), int(coords.shape[1])
+    outside = torch.zeros(B, dtype=torch.int32, device=dev)
+    w = torch.zeros(B, N, device=dev) if with_winding else None
+    if B and N:
+        if N > MAX_SCORED_ATOMS:
+            raise ValueError(f"the shape kernels take at most {MAX_SCORED_ATOMS} atoms per molecule, got a padded width of {N}")
+        check_n_nodes(n_nodes, B, N)
+        tri = _triangles(triangles, dev)
+        x = coords.to(dev, torch.float32).contiguous()
+        nn = n_nodes.to(dev, torch.int32).reshape(B).contiguous()
+        _lib.check(_lib.lib().mcg_mesh_atoms_outside(_lib.dptr(tri), int(tri.shape[0]), _lib.dptr(x), _lib.dptr(nn), B, N,
+                                                     _lib.dptr(outside), _lib.dptr(w), _lib.current_stream_ptr(dev)),
+                   "mcg_mesh_atoms_outside")
+    return (outside, w) if with_winding else outside
+
+
+class SolidReference:
+    """A watertight mesh prepared as the reference of the shape kernels (`solid_reference`).  Host side, built at once:
+      mesh            the loaded `mesh.Mesh` (own coordinates);
+      M_r, t_r        `mesh.solid_frame`: frame = (x - t_r) @ M_r, M_r proper;  xform [12] fp32 = M_r row-major, then t_r
+                      (the layout of `mcg_shape_frames_tf`);
+      triangles       [F,9] fp32, in the solid's frame;  triangles_own [F,9] fp32, in the mesh's own coordinates;
+      axes            [3,n] fp32: linspace(bbox_min - 6 ATOM_RADIUS, bbox_max + 6 ATOM_RADIUS, n) per axis of the framed solid.
+    Device side, built on first use and kept per device (`on(device)`): the tensors above and the occupancy f [n^3]."""
+
+    def __init__(self, mesh, n: int = 40):
+        import numpy as np
+        from . import mesh as mcg_mesh
+        self.mesh = mcg_mesh.load_mesh(mesh)
+        self.n = int(n)
+        if not 2 <= self.n <= 256:
+            raise ValueError(f"the grid takes 2 to 256 points per axis, got {n}")
+        self.M_r, self.t_r = mcg_mesh.solid_frame(self.mesh)
+        v = self.mesh.vertices.astype(np.float64)
+        framed = (v - self.t_r) @ self.M_r
+        self.triangles = torch.from_numpy(framed[self.mesh.faces].reshape(-1, 9)).to(torch.float32)
+        self.triangles_own = torch.from_numpy(self.mesh.vertices[self.mesh.faces].reshape(-1, 9).copy())
+        self.xform = torch.from_numpy(np.concatenate([self.M_r.reshape(-1), self.t_r])).to(torch.float32)
+        fv = torch.from_numpy(framed).to(torch.float32)
+        lo, hi = fv.min(dim=0).values - 6.0 * ATOM_RADIUS, fv.max(dim=0).values + 6.0 * ATOM_RADIUS
+        self.axes = torch.stack([torch.linspace(lo[k], hi[k], self.n) for k in range(3)])
+        self._on = {}
+
+    def on(self, device) -> Dict[str, torch.Tensor]:
+        """{triangles, triangles_own, xform, axes, f} on `device`; the occupancy launch runs the first time."""
+        dev = torch.device(device)
+        if dev not in self._on:
+            d = dict(triangles=self.triangles.to(dev), triangles_own=self.triangles_own.to(dev),
+                     xform=self.xform.to(dev).contiguous(), axes=self.axes.to(dev).contiguous())
+            d["f"] = mesh_occupancy(d["triangles"], d["axes"], dev)
+            self._on[dev] = d
+        return self._on[dev]
+
+
+def solid_reference(mesh, n: int = 40) -> SolidReference:
+    """`mesh` (anything `mesh.load_mesh` takes) as a `SolidReference` on an n^3 grid, prepared once per call."""
+    return mesh if isinstance(mesh, SolidReference) else SolidReference(mesh, n)
+
+
+def _solid_inputs(solid, coords: torch.Tensor, n_nodes: torch.Tensor, device, max_batch: Optional[int] = None):
+    """(SolidReference, device, x, nn) with x = nn = None for an empty batch; the refusals of `_shape_inputs`."""
+    solid = solid_reference(solid)
+    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
+    B = int(coords.shape[0])
+    if max_batch is not None and B > max_batch:
+        raise ValueError(f"pairwise shape Tanimoto takes at most {max_batch} molecules, got {B}")
+    if B == 0:
+        return solid, dev, None, None
+    W = int(coords.shape[1])
+    check_n_nodes(n_nodes, B, W)
+    if W > MAX_SCORED_ATOMS:
+        raise ValueError(f"shape scoring takes at most {MAX_SCORED_ATOMS} atoms per molecule, got a padded width of {W}")
+    return solid, dev, coords.to(dev, torch.float32).contiguous(), n_nodes.to(dev, torch.int32).reshape(B).contiguous()
+
+
+@torch.no_grad()
+def shape_scores_solid(solid, coords: torch.Tensor, n_nodes: torch.Tensor, device=None
+                       ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`shape_scores` against a solid: (best [B], orientation [B]) on the device.  Every sample's principal frame
+    (`shape_frames_hip`, as `shape_scores` takes it) is scored in the four orientations against the solid's occupancy on
+    the solid's grid (`mcg_shape_tanimoto_field`): <f,g> / (<f,f> + <g,g> - <f,g>) with f the indicator function of the
+    solid and g the sample's Gaussian density.  The indicator function as the density of a solid is this package's own
+    choice, not the reference's (which scores molecules against molecules)."""
+    solid, dev, x, nn = _solid_inputs(solid, coords, n_nodes, device)
+    if x is None:
+        return torch.empty(0, device=dev), torch.empty(0, dtype=torch.long, device=dev)
+    d = solid.on(dev)
+    B, N = int(x.shape[0]), int(x.shape[1])
+    _, frames = shape_frames_hip(x, nn, dev, centre_atoms=True)
+    rots = _orientations().reshape(4, 9).to(dev).contiguous()
+    score = torch.empty(B * 4, device=dev)
+    _lib.check(_lib.lib().mcg_shape_tanimoto_field(_lib.dptr(d["f"]), _lib.dptr(frames), _lib.dptr(nn), B, N, _lib.dptr(rots),
+                                                   4, _lib.dptr(d["axes"]), solid.n, float(ALPHA), float(AMPLITUDE),
+                                                   _lib.dptr(score), _lib.current_stream_ptr(dev)),
+               "mcg_shape_tanimoto_field")
+    best, which = score.reshape(B, 4).max(dim=1)
+    return best, which
+
+
+def _overlay_field(f: torch.Tensor, ref_xform: torch.Tensor, axes: torch.Tensor, x: torch.Tensor, nn: torch.Tensor, dev,
+                   with_scores: bool) -> Dict[str, torch.Tensor]:
+    """`mcg_shape_overlay_field` on samples x [B,N,3] (device): the body of `_overlay` behind the reference's part, with
+    the reference given as its density f [n^3] on `axes` [3,n] and its frame transform `ref_xform` [12]."""
+    B, N, n = int(x.shape[0]), int(x.shape[1]), int(axes.shape[1])
+    xform = torch.empty(B, 12, device=dev)
+    _, frames = shape_frames_hip(x, nn, dev, centre_atoms=True, xform_out=xform)
+    rots = _orientations().reshape(4, 9).to(dev).contiguous()
+    scores = torch.empty(B, 4, device=dev) if with_scores else None
+    best = torch.empty(B, device=dev)
+    which = torch.empty(B, dtype=torch.int32, device=dev)
+    flipped = torch.empty(B, dtype=torch.int32, device=dev)
+    pose = torch.empty(B, 12, device=dev)
+    posed = torch.empty(B, N, 3, device=dev)
+    _lib.check(_lib.lib().mcg_shape_overlay_field(_lib.dptr(f), _lib.dptr(ref_xform), _lib.dptr(frames), _lib.dptr(xform),
+                                                  _lib.dptr(nn), B, N, _lib.dptr(rots), _lib.dptr(axes), n, float(ALPHA),
+                                                  float(AMPLITUDE), _lib.dptr(scores), _lib.dptr(best), _lib.dptr(which),
+                                                  _lib.dptr(flipped), _lib.dptr(pose), _lib.dptr(posed),
+                                                  _lib.current_stream_ptr(dev)), "mcg_shape_overlay_field")
+    failed = (which < 0).view(B, 1, 1)
+    out = dict(coords=torch.where(failed, x, posed), rotation=pose[:, :9].reshape(B, 3, 3), translation=pose[:, 9:],
+               tanimoto=best, orientation=which.long(), flipped=flipped.bool())
+    if with_scores:
+        out["scores"] = scores
+    return out
+
+
+@torch.no_grad()
+def shape_overlay_solid(solid, coords: torch.Tensor, n_nodes: torch.Tensor, device=None, with_scores: bool = False
+                        ) -> Dict[str, torch.Tensor]:
+    """`shape_overlay` onto a solid: every sample posed into the mesh's own coordinates by a proper rigid transform - its
+    principal frame, made to match the handedness of the solid's frame (`mesh.solid_frame`, proper), in the best of the
+    four orientations scored against the solid's occupancy (`mcg_shape_overlay_field`).  `shape_overlay`'s keys with the
+    same meaning and failure rows, plus
+      atoms_outside [B] int32   the real atoms of the pose with |winding number| <= 0.5 (`mcg_mesh_atoms_outside`, against
+                                the mesh in its own coordinates); -1 where the pose failed."""
+    solid, dev, x, nn = _solid_inputs(solid, coords, n_nodes, device)
+    if x is None:
+        W = int(coords.shape[1])
+        out = dict(coords=torch.zeros(0, W, 3, device=dev), rotation=torch.zeros(0, 3, 3, device=dev),
+                   translation=torch.zeros(0, 3, device=dev), tanimoto=torch.zeros(0, device=dev),
+                   orientation=torch.zeros(0, dtype=torch.long, device=dev),
+                   flipped=torch.zeros(0, dtype=torch.bool, device=dev))
+        if with_scores:
+            out["scores"] = torch.zeros(0, 4, device=dev)
+        out["atoms_outside"] = torch.zeros(0, dtype=torch.int32, device=dev)
+        return out
+    d = solid.on(dev)
+    out = _overlay_field(d["f"], d["xform"], d["axes"], x, nn, dev, with_scores)
+    counts = mesh_atoms_outside(d["triangles_own"], out["coords"], nn, dev)
+    out["atoms_outside"] = torch.where(out["orientation"] < 0, torch.full_like(counts, -1), counts)
+    return out
+
+
+@torch.no_grad()
+def pairwise_shape_tanimoto_solid(solid, coords: torch.Tensor, n_nodes: torch.Tensor, device=None) -> torch.Tensor:
+    """`pairwise_shape_tanimoto` of molecules posed into a solid's coordinates (`shape_overlay_solid`): one
+    `mcg_shape_pair_tanimoto` call with the solid's frame transform and grid in place of a reference conformer's."""
+    solid, dev, x, nn = _solid_inputs(solid, coords, n_nodes, device, max_batch=MAX_PAIR_BATCH)
+    if x is None:
+        return torch.zeros(0, 0, device=dev)
+    d = solid.on(dev)
+    B, W, n = x.shape[0], x.shape[1], solid.n
+    gp = -(-n ** 3 // _PAIR_KALIGN) * _PAIR_KALIGN
+    density = torch.empty(B, gp, device=dev)
+    gram = torch.empty(B, B, device=dev)
+    out = torch.empty(B, B, device=dev)
+    _lib.check(_lib.lib().mcg_shape_pair_tanimoto(_lib.dptr(x), _lib.dptr(nn), B, W, _lib.dptr(d["xform"]),
+                                                  _lib.dptr(d["axes"]), n, float(ALPHA), float(AMPLITUDE),
+                                                  _lib.dptr(density), _lib.dptr(gram), _lib.dptr(out),
+                                                  _lib.current_stream_ptr(dev)), "mcg_shape_pair_tanimoto")
+    return out
+
+
+def check_max_atoms_outside(value) -> int:
+    """`max_atoms_outside` as an int >= 0 (an integer type, not a bool), else ValueError."""
+    try:
+        k = None if isinstance(value, bool) else operator.index(value)
+    except TypeError:
+        k = None
+    if k is None or k < 0:
+        raise ValueError(f"max_atoms_outside must be an integer >= 0, got {value!r}")
+    return int(k)
+
+
 def check_max_pairwise_tanimoto(value) -> float:
     """`max_pairwise_tanimoto` as a float: a real number in (0, 1] (not a bool, not NaN), else ValueError."""
     if isinstance(value, bool) or not isinstance(value, numbers.Real) or not (0.0 < float(value) <= 1.0):

@@ -40,7 +40,11 @@ forced by the scope of this build:
       `max_pairwise_tanimoto`: a shape-diverse selection of the posed molecules;
       `receptor`, `max_receptor_clashes`: steric contacts of the posed molecules with a receptor; a filter on them;
       `chemical_scores`, `reference_graph`, `max_chemical_tanimoto`: chemical similarity to the reference; a filter;
-      `unique`, `max_pairwise_chemical_tanimoto`: one molecule per graph; a chemically diverse selection.
+      `unique`, `max_pairwise_chemical_tanimoto`: one molecule per graph; a chemically diverse selection;
+  * `reference_shape`, `shape_density` (every generation entry): a watertight triangle mesh - an STL file, a (vertices,
+    faces) pair - as the reference, what the reference's notebook does with `trimesh` (`mesh.py`, no `trimesh` needed);
+    the shape options then score, pose and select against the solid, and `max_atoms_outside` filters on the posed atoms
+    that lie outside it.
 """
 from __future__ import annotations
 
@@ -293,7 +297,14 @@ class MLConformerGenerator(torch.nn.Module):
             return parse_molblock_heavy_atoms(reference_conformer)[0]
         return torch.as_tensor(reference_conformer, dtype=torch.float32)
 
-    def _reference_context(self, reference_conformer, reference_context, n_atoms):
+    def _reference_context(self, reference_conformer, reference_context, n_atoms, ref_solid=None,
+                           shape_density: float = 0.02):
+        if ref_solid is not None:          # a mesh: the notebook's principal_inertia_components at `density`, with n_atoms
+            if not n_atoms:
+                raise ValueError(
+                    "Reference Number of Atoms should be provided, when generating samples using context.")
+            from . import mesh as mcg_mesh
+            return mcg_mesh.mesh_context(ref_solid.mesh, shape_density), n_atoms
         if reference_conformer is not None and reference_conformer is not False:
             ref_coord = self._reference_coord(reference_conformer)
             ref_n_atoms = int(ref_coord.shape[0])
@@ -341,6 +352,20 @@ class MLConformerGenerator(torch.nn.Module):
         """[B,B] pairwise shape Tanimoto (device) of padded heavy-atom coordinates posed onto the reference
         (`cheminformatics.pairwise_shape_tanimoto`)."""
         return cheminformatics.pairwise_shape_tanimoto(ref_coord, coords, n_nodes, self.device)
+
+    def _score_solid(self, solid, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
+        """Shape Tanimoto [B] (device) of padded heavy-atom coordinates against a solid (`shape_scores_solid`)."""
+        return cheminformatics.shape_scores_solid(solid, coords, n_nodes, self.device)[0]
+
+    def _pose_solid(self, solid, coords: torch.Tensor, n_nodes: torch.Tensor) -> dict:
+        """Padded heavy-atom coordinates posed into a solid's own coordinates, with `atoms_outside`
+        (`cheminformatics.shape_overlay_solid`, device tensors)."""
+        return cheminformatics.shape_overlay_solid(solid, coords, n_nodes, self.device)
+
+    def _pair_solid(self, solid, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
+        """[B,B] pairwise shape Tanimoto (device) of padded heavy-atom coordinates posed into a solid
+        (`cheminformatics.pairwise_shape_tanimoto_solid`)."""
+        return cheminformatics.pairwise_shape_tanimoto_solid(solid, coords, n_nodes, self.device)
 
     def _receptor_coords(self, rec: tuple, coords: torch.Tensor, n_nodes: torch.Tensor,
                          atomic_numbers: torch.Tensor) -> torch.Tensor:
@@ -459,7 +484,8 @@ class MLConformerGenerator(torch.nn.Module):
                             refine_overlay: Union[bool, int] = False, receptor=None,
                             max_receptor_clashes: Optional[int] = None, chemical_scores: bool = False,
                             reference_graph=None, max_chemical_tanimoto: Optional[float] = None, unique: bool = False,
-                            max_pairwise_chemical_tanimoto: Optional[float] = None) -> List:
+                            max_pairwise_chemical_tanimoto: Optional[float] = None, reference_shape=None,
+                            shape_density: float = 0.02, max_atoms_outside: Optional[int] = None) -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
@@ -515,22 +541,40 @@ class MLConformerGenerator(torch.nn.Module):
         (`fingerprint.pairwise_fingerprint_tanimoto`), in the same walk as `max_pairwise_tanimoto` - a molecule is
         excluded if either matrix reaches its threshold against an already kept one; the walk is in ranking order, or
         in sample order where the call does not score shape.
-        Order of the stages: validity, `max_receptor_clashes`, `max_chemical_tanimoto`, `unique`, then the selection
-        (threshold, exclusion, `top_k`).  The filters only remove molecules.
+        `reference_shape` (instead of `reference_conformer` / `reference_context`; needs `n_atoms`): a watertight triangle
+        mesh as the reference - a path, bytes or file object holding a binary or ASCII STL, a (vertices, faces) pair or
+        an object with `.vertices` and `.faces` (`mesh.load_mesh`; no `trimesh`).  The context is the solid's principal
+        inertia components at `shape_density` (`mesh.mesh_context`: the reference notebook's
+        `principal_inertia_components` with `density = 0.02`); generation itself is unchanged.  `shape_scores`, `overlay`,
+        `top_k`, `min_shape_tanimoto` and `max_pairwise_tanimoto` then work as with a conformer, the solid standing in for
+        it: its density is the indicator function of its inside (generalized winding number |w| > 0.5) on the grid of its
+        own principal frame - this package's own definition, the reference scores molecules against molecules only
+        (`cheminformatics.shape_scores_solid`, `shape_overlay_solid`, `pairwise_shape_tanimoto_solid`; DESIGN.md section 6,
+        "Solid references").  The pose is in the mesh's own coordinates, and posed records / Mols carry `atoms_outside` (the
+        int property of that name): the heavy atoms of the pose outside the mesh; None (no property) where posing failed.
+        `max_atoms_outside=k` (needs `overlay=True` and `reference_shape`): drop the molecules with more than k atoms
+        outside, and those whose pose failed, beside `max_receptor_clashes`.
+        Order of the stages: validity, `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`, `unique`, then
+        the selection (threshold, exclusion, `top_k`).  The filters only remove molecules.
         Refused with ValueError before any device work: a chemical option that is not a bool / a real number in (0, 1],
         a chemical score without a reference graph, a `reference_graph` that `fingerprint.mol_graph` refuses or that has no
         or more than 64 heavy atoms, scoring or posing without a reference conformer, a reference
         outside 3..64 heavy atoms, top_k < 1, a threshold outside [0, 1], max_pairwise_tanimoto outside (0, 1] or without
         overlay, refine_overlay other than True or an integer in 1..1024 or without overlay, a receptor without overlay,
         one `load_receptor` refuses or one that holds the reference (a reference heavy atom within 0.5 A of a receptor
-        heavy atom), max_receptor_clashes other than an integer >= 0 or without a receptor, and a custom finisher."""
+        heavy atom), max_receptor_clashes other than an integer >= 0 or without a receptor, a custom finisher, a
+        `reference_shape` together with another reference, with `refine_overlay` or with a `receptor`, or without
+        `n_atoms`, a mesh `load_mesh` refuses ("The mesh needs to be watertight."), a `shape_density` that is not a positive
+        real number, and max_atoms_outside other than an integer >= 0, without a `reference_shape` or without overlay."""
         if sample_seed is not None:
             seeding.check_seed(sample_seed)
         req = postprocess.parse_request(self, reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
                                         max_pairwise_tanimoto, refine_overlay, receptor, max_receptor_clashes,
                                         chemical_scores, reference_graph, max_chemical_tanimoto, unique,
-                                        max_pairwise_chemical_tanimoto)
-        ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
+                                        max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
+                                        reference_context)
+        ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.ref_solid,
+                                                           shape_density)
         keyed = () if sample_seed is None else (sample_seed, None)   # unseeded: the positional call of before
         res = self._generate_shard(ref_context, ref_n_atoms, variance, None, n_samples, resample_steps, fixed_fragment,
                                    inertial_fragment_matching, blend_power, ifm_diffusion_level, optimise_geometry, *keyed)
@@ -554,7 +598,8 @@ class MLConformerGenerator(torch.nn.Module):
                                     max_receptor_clashes: Optional[int] = None, chemical_scores: bool = False,
                                     reference_graph=None, max_chemical_tanimoto: Optional[float] = None,
                                     unique: bool = False,
-                                    max_pairwise_chemical_tanimoto: Optional[float] = None) -> List:
+                                    max_pairwise_chemical_tanimoto: Optional[float] = None, reference_shape=None,
+                                    shape_density: float = 0.02, max_atoms_outside: Optional[int] = None) -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -572,7 +617,8 @@ class MLConformerGenerator(torch.nn.Module):
         no generator, so sample i is the same molecule on any world size and under either `balance`.
         `shape_scores`, `top_k`, `min_shape_tanimoto`, `overlay`, `max_pairwise_tanimoto`, `refine_overlay`, `receptor`,
         `max_receptor_clashes`, `chemical_scores`, `reference_graph`, `max_chemical_tanimoto`, `unique`,
-        `max_pairwise_chemical_tanimoto`: as in `generate_conformers`.  The fingerprints are computed behind the gather,
+        `max_pairwise_chemical_tanimoto`, `reference_shape`, `shape_density`, `max_atoms_outside`: as in
+        `generate_conformers` (every rank loads the mesh and computes its occupancy itself).  The fingerprints are computed behind the gather,
         on the rows a rank returns: with gather="all" uniqueness and chemical diversity hold over the whole batch, with
         gather="rank0" within each other rank's own shard, like the rest of the selection.
         Every rank poses, scores and measures the receptor contacts of ITS OWN shard on its own GPU before the gather
@@ -589,8 +635,10 @@ class MLConformerGenerator(torch.nn.Module):
         req = postprocess.parse_request(self, reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
                                         max_pairwise_tanimoto, refine_overlay, receptor, max_receptor_clashes,
                                         chemical_scores, reference_graph, max_chemical_tanimoto, unique,
-                                        max_pairwise_chemical_tanimoto)
-        ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms)
+                                        max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
+                                        reference_context)
+        ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.ref_solid,
+                                                           shape_density)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)
         hi_n = min(ref_n_atoms + variance, self.max_n_nodes)
         # decided from the configuration, not from what this rank's shard happened to produce: every rank takes the same

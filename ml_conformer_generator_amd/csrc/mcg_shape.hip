@@ -195,3 +195,33 @@ extern "C" int mcg_shape_overlay(const float* ref_frame, int n_ref, const float*
                                     B, N, rot, axes, n, alpha, amplitude, f_scratch, score, best, which, flipped, pose,
                                     posed, stream);
 }
+
+// The two entries above with the density launch skipped: f[n^3] is the caller's (the occupancy of a solid, mcg_mesh.hip, or
+// anything else on the grid of `axes`).  The same kernels: with f = what k_shape_density would have written, the same bits.
+extern "C" int mcg_shape_tanimoto_field(const float* f, const float* cand, const int32_t* n_nodes_dev, int B, int N,
+                                        const float* rot, int R, const float* axes, int n, float alpha, float amplitude,
+                                        float* score, void* stream) {
+    if (!f || !cand || !n_nodes_dev || !rot || !axes || !score || B < 1 || N < 1 || R < 1 || n < 2) {
+        mcg_set_error("mcg_shape_tanimoto_field: bad arguments (non-null buffers, B >= 1, N >= 1, R >= 1, n >= 2)");
+        return MCG_ERR_ARG;
+    }
+    hipLaunchKernelGGL(k_shape_overlap, dim3(B * R), dim3(256), 0, (hipStream_t)stream, f, cand, n_nodes_dev, N, rot, R, axes,
+                       n, alpha, amplitude, score);
+    MCG_HIP(hipGetLastError());
+    return MCG_OK;
+}
+
+extern "C" int mcg_shape_overlay_field(const float* f, const float* ref_xform, const float* frames, const float* xform,
+                                       const int32_t* n_nodes_dev, int B, int N, const float* rot, const float* axes, int n,
+                                       float alpha, float amplitude, float* score, float* best, int32_t* which,
+                                       int32_t* flipped, float* pose, float* posed, void* stream) {
+    if (!f || !ref_xform || !frames || !xform || !n_nodes_dev || !rot || !axes || !best || !which || !flipped || !pose ||
+        !posed || B < 1 || N < 1 || N > MAX_ATOMS || n < 2) {
+        mcg_set_error("mcg_shape_overlay_field: bad arguments (non-null buffers, B >= 1, 1 <= N <= %d, n >= 2)", MAX_ATOMS);
+        return MCG_ERR_ARG;
+    }
+    hipLaunchKernelGGL(k_shape_overlay, dim3(B), dim3(256), 0, (hipStream_t)stream, f, ref_xform, frames, xform, n_nodes_dev,
+                       N, rot, axes, n, alpha, amplitude, score, best, which, flipped, pose, posed);
+    MCG_HIP(hipGetLastError());
+    return MCG_OK;
+}

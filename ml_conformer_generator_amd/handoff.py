@@ -46,19 +46,22 @@ class GeneratedMolecule:
     `overlay_tanimoto` / `pose`: the score and rigid pose of a call that posed its molecules onto the reference
     (`overlay=True`), else None.  `receptor_clashes` / `receptor_max_overlap`: its steric contacts with the call's
     receptor, else None.  `chemical_tanimoto` / `graph_key`: its chemical similarity to the reference and its graph
-    identity key (`fingerprint.py`: the package's own Morgan-type fingerprint, a substitute for RDKit's), else None."""
-    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_score", "_overlay", "_contacts", "_chem")
+    identity key (`fingerprint.py`: the package's own Morgan-type fingerprint, a substitute for RDKit's), else None.
+    `atoms_outside`: how many of its atoms lie outside the mesh of a call posed into a `reference_shape`, else None."""
+    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_score", "_overlay", "_contacts", "_chem",
+                 "_outside")
 
     def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True,
                  sample_id: Optional[int] = None):
         self._z, self._coords, self._bonds, self.valid = list(atomic_numbers), coords, bond_orders, bool(valid)
         self._batch, self._b, self._sid = None, -1, sample_id
-        self._score = self._overlay = self._contacts = self._chem = None
+        self._score = self._overlay = self._contacts = self._chem = self._outside = None
 
     @classmethod
     def _view(cls, batch: _HostBatch, b: int, valid: bool, sample_id: Optional[int] = None,
               score: Optional[float] = None, overlay: Optional[tuple] = None,
-              contacts: Optional[tuple] = None, chem: Optional[tuple] = None) -> "GeneratedMolecule":
+              contacts: Optional[tuple] = None, chem: Optional[tuple] = None,
+              outside: Optional[int] = None) -> "GeneratedMolecule":
         m = cls.__new__(cls)
         m._z = m._coords = m._bonds = None
         m.valid, m._batch, m._b = valid, batch, b
@@ -67,7 +70,15 @@ class GeneratedMolecule:
         m._overlay = overlay
         m._contacts = contacts
         m._chem = chem
+        m._outside = outside
         return m
+
+    @property
+    def atoms_outside(self) -> Optional[int]:
+        """How many heavy atoms of the returned pose lie outside the call's `reference_shape` mesh (generalized winding
+        number |w| <= 0.5) when the call posed the molecule into it (`overlay=True`); None otherwise, and where posing
+        failed."""
+        return self._outside
 
     @property
     def chemical_tanimoto(self) -> Optional[float]:
@@ -298,7 +309,8 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                            pose: Optional[torch.Tensor] = None, receptor_clashes: Optional[torch.Tensor] = None,
                            receptor_max_overlap: Optional[torch.Tensor] = None,
                            chemical_tanimoto: Optional[torch.Tensor] = None,
-                           graph_key: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
+                           graph_key: Optional[torch.Tensor] = None,
+                           atoms_outside: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
     (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
     (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records).
@@ -306,7 +318,8 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     pose onto the reference (None: records of a call that did not pose).  `receptor_clashes[b]` / `receptor_max_overlap[b]`:
     row b's receptor contacts (a negative clash count: not measured, the record gets None; None: a call without a
     receptor).  `chemical_tanimoto[b]` (fp32) / `graph_key[b]` (int64 holding the unsigned bit pattern): row b's chemical
-    similarity to the reference and graph identity key (either may be None: not asked for)."""
+    similarity to the reference and graph identity key (either may be None: not asked for).  `atoms_outside[b]`: row b's
+    atoms outside the call's mesh (negative: its pose failed, the record gets None; None: a call without a mesh)."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
     view = GeneratedMolecule._view
     if sample_ids is None and shape_tanimoto is None and overlay_tanimoto is None and chemical_tanimoto is None \
@@ -330,7 +343,10 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
         sim = [None] * len(flags) if chemical_tanimoto is None else [float(v) for v in chemical_tanimoto.cpu().tolist()]
         keys = [None] * len(flags) if graph_key is None else [int(k) & 0xFFFFFFFFFFFFFFFF for k in graph_key.cpu().tolist()]
         chem = list(zip(sim, keys))
-    return [view(batch, b, bool(v), ids[b], scores[b], overlays[b], contacts[b], chem[b]) for b, v in enumerate(flags)]
+    outside = [None] * len(flags) if atoms_outside is None else \
+        [None if c < 0 else int(c) for c in atoms_outside.cpu().tolist()]
+    return [view(batch, b, bool(v), ids[b], scores[b], overlays[b], contacts[b], chem[b], outside[b])
+            for b, v in enumerate(flags)]
 
 
 def assemble_molecules(x: torch.Tensor, elements: torch.Tensor, bond: torch.Tensor, n_nodes: torch.Tensor

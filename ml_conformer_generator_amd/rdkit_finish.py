@@ -156,6 +156,14 @@ def tag_contacts(mols: Sequence, contacts: Sequence[Optional[tuple]]) -> None:
             m.SetDoubleProp("receptor_max_overlap", float(c[1]))
 
 
+def tag_atoms_outside(mols: Sequence, counts: Sequence[Optional[int]]) -> None:
+    """Set the int property `atoms_outside` (heavy atoms of the pose outside the call's `reference_shape` mesh) on every Mol
+    of `mols` (None = dropped); `counts[k]` belongs to `mols[k]`, None = not measured.  Set after the object gather."""
+    for m, c in zip(mols, counts):
+        if m is not None and c is not None and hasattr(m, "SetIntProp"):
+            m.SetIntProp("atoms_outside", int(c))
+
+
 def tag_graph_keys(mols: Sequence, keys: Sequence[Optional[int]]) -> None:
     """Set the string property `graph_key` - the unsigned 64-bit graph identity key in decimal; it does not fit RDKit's
     int property - on every Mol of `mols` (None = dropped); `keys[k]` belongs to `mols[k]`, None = no key."""
