@@ -606,26 +606,41 @@ __global__ __launch_bounds__(256) void mcg_gemm_x6_kernel(McgGemmArgs p) {
     }
 }
 
-template <int RN, int RING = 3>
-__global__ __launch_bounds__(256) void mcg_gemm_kernel(McgGemmArgs p) {
+// ---------------------------------------------------------------------------------------------
+// One wave tile of the fp32 node GEMMs: MR row tiles of 16 x RN column tiles, both K segments, epilogue.  Shared by
+// mcg_gemm_kernel (MR = 2, no gather, C through mcg_gemm_c_ptr) and mcg_gemm16_kernel.
+//
+// ONE operand pipeline per launch.  There is at most one wave per SIMD on the small node GEMMs, so nothing but the wave's own
+// MFMAs covers a load: every operand that is first asked for at a K seam (the K % 16 tail steps, the first groups of
+// segment 2, the gather table) costs a whole round trip to a cold L2 with the matrix pipe idle.  So
+//   * a2_rows is read next to the row clamp, the tail steps' operands (MR x NS A scalars and RN B scalars per step, at most
+//     three steps per segment) are requested at the head of the kernel and wait in registers for their seam;
+//   * the ring is RING 16-k groups deep (slot = a compile-time constant: a runtime slot turns the ring into a scratch
+//     array).  Segment 1 is FRONT-padded to a whole number of ring trips: group j sits in slot (j + s0) % RING with
+//     s0 = (RING - G1 % RING) % RING, so only the first trip has empty slots (their MFMAs are skipped, their loads are not:
+//     a branch around MFMAs costs nothing, a branch around loads makes the wait-count pass assume the shorter queue and wait
+//     for younger loads) and segment 1 always ends on slot RING - 1.  Its LAST trip therefore refills slot i with group i of
+//     segment 2 right behind compute(i): segment 2 starts on a full ring, RING - 1 compute blocks ahead as in the steady
+//     state.  The trips are peeled explicitly (first | steady loop | last, with and without a segment 2);
+//   * bias and residual are requested BEHIND the initial ring fill: the vector-memory counter retires in order, so in front
+//     of it they sat between the first MFMA and its operands.
+// The k order of every output element is unchanged: segment 1 groups ascending, its tail steps, segment 2 groups, its tail
+// steps; the gather sum is ((a + b) + c) + d; bias after the accumulation, SiLU / ReLU, then the residual.
+template <int RN, int GATHER, int MR, int RING, bool C_PTR>
+__device__ __forceinline__ void mcg_gemm_f32_tile(const McgGemmArgs& p, int row0, int nt0) {
+    constexpr int NS = GATHER >= 2 ? GATHER : 1;          // rows of A2 summed per row of segment 2
     const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
     const int g = lane >> 4, c = lane & 15;
-    // waves are numbered linearly over (row block, wave column) so that the grid is exactly
-    // ceil(waves / 4) workgroups - a 2-D grid rounds each row block up to whole workgroups and
-    // can push a 243-workgroup problem over the 256-CU edge into a second round.
-    const int wave_cols = (p.n_tiles + RN - 1) / RN;
-    const int nblk = p.gemm_blocks > 0 ? p.gemm_blocks : (int)gridDim.x;        // (+ side-job workgroups behind them)
-    if ((int)blockIdx.x >= nblk) { mcg_gemm_side_job(p, (int)blockIdx.x - nblk); return; }
-    const int wlin = mcg_xcd_remap(blockIdx.x, nblk) * 4 + wid;
-    if (wlin >= ((p.M + 31) / 32) * wave_cols) return;
-    const int row0 = (wlin / wave_cols) * 32;
-    const int nt0 = (wlin % wave_cols) * RN;
-    int rA[2];
+    int orow[MR], rA[MR];
 #pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        const int r = row0 + 16 * m + c;
-        rA[m] = r < p.M ? r : p.M - 1;          // clamp: results of padded rows are dropped
+    for (int m = 0; m < MR; ++m) {
+        orow[m] = row0 + 16 * m + c;
+        rA[m] = orow[m] < p.M ? orow[m] : p.M - 1;        // clamp: results of padded rows are dropped
+    }
+    int4 sl[MR];                                          // the gather table, a whole segment 1 ahead of its use
+    if constexpr (GATHER >= 2) {
+#pragma unroll
+        for (int m = 0; m < MR; ++m) sl[m] = p.a2_rows[rA[m]];
     }
     bool nvalid[RN];
     int ncl[RN];            // column-tile offset clamped into range (results of invalid tiles are dropped)
@@ -634,179 +649,120 @@ __global__ __launch_bounds__(256) void mcg_gemm_kernel(McgGemmArgs p) {
         nvalid[n] = nt0 + n < p.n_tiles;
         ncl[n] = nvalid[n] ? n : 0;
     }
-
-    f32x4 acc[2][RN];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < RN; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
     // Accumulators are kept TRANSPOSED (weights as the MFMA A operand, activations as B: the two operands have
     // the same lane layout, so this is just the argument order): lane (c, g) of tile (m, n) then holds output
     // row row0 + 16m + c, columns 16(nt0+n) + 4g .. +3 - four consecutive floats, so bias, residual and the
     // result move as 16-byte vectors (6 stores per wave tile instead of 24 dword stores).
-    // Epilogue operands are fetched NOW so their latency hides under the K loop.
-    f32x4 ebias[RN];
-    f32x4 eres[2][RN];
-#pragma unroll
-    for (int n = 0; n < RN; ++n) {
-        const int col = (nt0 + ncl[n]) * 16 + 4 * g;
-        ebias[n] = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + col) : (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            const int orow = row0 + 16 * m + c;
-            eres[m][n] = (p.resid && orow < p.M && col + 3 < p.n_store) ? *reinterpret_cast<const f32x4*>(p.resid + (size_t)orow * p.ldr + col)
-                                                                        : (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-    }
-
-    const float* bseg = p.Bp;
-#pragma unroll 1
-    for (int seg = 0; seg < 2; ++seg) {
-        const float* A = seg == 0 ? p.A1 : p.A2;
-        const int K = seg == 0 ? p.K1 : p.K2;
-        const int lda = seg == 0 ? p.lda1 : p.lda2;
-        if (K == 0) continue;
-        const float* a0 = A + (size_t)rA[0] * lda + 4 * g;
-        const float* a1 = A + (size_t)rA[1] * lda + 4 * g;
-        const int groups = K / 16;
-        const size_t gstride = (size_t)p.n_tiles * 256;
-        const float* bq = bseg + (size_t)nt0 * 256 + lane * 4;
-        if (groups == 0) goto tail_steps;
-        {
-
-        // 3-deep register ring: the loads of group q+3 are issued right after group q's MFMAs
-        // and are consumed two compute blocks (>= 1k cycles of MFMA work) later - there is
-        // less than one wave per SIMD on the small node GEMMs, so latency is hidden by ILP.
-        f32x4 Ar[RING][2], Br[RING][RN];
-        // loads are UNCONDITIONAL (group index and column tile clamped): a runtime "load or zero"
-        // select makes hipcc branch around every load and drain vmcnt(0) behind it.
-        // operand addresses = buffer descriptor (SGPRs) + one 32-bit lane offset + a scalar group offset: with
-        // 64-bit per-lane pointers every load of the loop costs a 64-bit VALU add, and on gfx950 VALU issue time
-        // adds to fp32-MFMA time
-        const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), 0, 0xffffffff, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bseg), 0, 0xffffffff, 0x00020000);
-        const unsigned oa0 = (unsigned)(rA[0] * lda + 4 * g) * 4u, oa1 = (unsigned)(rA[1] * lda + 4 * g) * 4u;
-        unsigned obn[RN];
-#pragma unroll
-        for (int n = 0; n < RN; ++n) obn[n] = (unsigned)((nt0 + ncl[n]) * 256 + lane * 4) * 4u;
-        const int gbytes = p.n_tiles * 256 * 4;
-        auto load_group = [&](int slot, int q) {
-            q = q < groups ? q : groups - 1;
-            Ar[slot][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_a, (int)oa0, 64 * q, 0));
-            Ar[slot][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_a, (int)oa1, 64 * q, 0));
-#pragma unroll
-            for (int n = 0; n < RN; ++n)
-                Br[slot][n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_b, (int)obn[n], q * gbytes, 0));
-        };
-        auto compute = [&](int slot) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int m = 0; m < 2; ++m)
-#pragma unroll
-                    for (int n = 0; n < RN; ++n) acc[m][n] = mcg_mfma(Br[slot][n][s], Ar[slot][m][s], acc[m][n]);
-        };
-#pragma unroll
-        for (int i = 0; i < RING; ++i) load_group(i, i);
-        // branch-free body (control flow inside the loop makes hipcc's wait-count pass fall back to
-        // vmcnt(0) at the loop head, draining the ring); the <= RING-1 leftover groups are peeled.
-        int q = 0;
-#pragma unroll 1
-        for (; q + RING <= groups; q += RING) {
-            // sched_barrier pins "MFMAs of group q | loads of group q+RING": left alone, hipcc clusters all
-            // the loads at the loop bottom and the first MFMA block then waits for every one of them.
-#pragma unroll
-            for (int i = 0; i < RING; ++i) {
-                compute(i); __builtin_amdgcn_sched_barrier(0); load_group(i, q + RING + i); __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < RING - 1; ++i)
-            if (q + i < groups) compute(i);
-        }
-    tail_steps:
-        const int tail = (K - groups * 16) / 4;
-        const float* bt = bseg + (size_t)groups * gstride + (size_t)nt0 * 64 + lane;
-        for (int st = 0; st < tail; ++st) {
-            const float av0 = a0[groups * 16 + 4 * st - 4 * g + g];   // k = 16Q + 4st + g
-            const float av1 = a1[groups * 16 + 4 * st - 4 * g + g];
-#pragma unroll
-            for (int n = 0; n < RN; ++n) {
-                const float b = bt[(size_t)st * p.n_tiles * 64 + ncl[n] * 64];
-                acc[0][n] = mcg_mfma(b, av0, acc[0][n]);
-                acc[1][n] = mcg_mfma(b, av1, acc[1][n]);
-            }
-        }
-        bseg += mcg_pack4_floats(K, p.n_tiles);
-    }
-
-#pragma unroll
-    for (int n = 0; n < RN; ++n) {
-        if (!nvalid[n]) continue;
-        const int col = (nt0 + n) * 16 + 4 * g;
-        if (col >= p.n_store) continue;
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            const int orow = row0 + 16 * m + c;
-            if (orow >= p.M) continue;
-            f32x4 v = acc[m][n] + ebias[n];
-            if (p.act == MCG_ACT_SILU) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = mcg_silu(v[r]);
-            } else if (p.act == MCG_ACT_RELU) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-            }
-            v += eres[m][n];
-            float* dst = mcg_gemm_c_ptr(p, orow, nt0 + n, g);
-            if (col + 3 < p.n_store) {
-                *reinterpret_cast<f32x4*>(dst) = v;       // (4-byte aligned is enough for a global dwordx4 store)
-            } else {                                       // ragged right edge (GCN: 210 columns)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (col + r < p.n_store) dst[r] = v[r];
-            }
-        }
-    }
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// 16-row variant for the node GEMMs (M = 1.7k .. 7k rows): a wave owns ONE 16-row tile x RN column tiles.
-// With 32-row wave tiles the three GEMMs of a GCL layer quantise badly on 1024 SIMDs at M = 1728 (K = 840,
-// N = 432: 756 waves of 840 MFMAs = 11.2 us of serial chain on 74 % of the SIMDs); 16 x 3 tiles give 972 waves
-// of 630 MFMAs (8.4 us), 16 x 6 the same for N = 864.  Same operand packs, ring discipline and transposed
-// accumulators as mcg_gemm_kernel.  GATHER: segment-2 rows are read as the sum of two rows (see a2_rows).
-template <int RN, int GATHER, int MR = 1, int RING = 3>       // GATHER 0 / 2 / 3 / 4 rows summed per A2 row; MR row tiles of 16 per wave
-__global__ __launch_bounds__(256) void mcg_gemm16_kernel(McgGemmArgs p) {
-    if ((int)blockIdx.x >= p.gemm_blocks) { mcg_gemm_side_job(p, (int)blockIdx.x - p.gemm_blocks); return; }
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    const int g = lane >> 4, c = lane & 15;
-    const int wave_cols = (p.n_tiles + RN - 1) / RN;
-    const int wlin = mcg_xcd_remap(blockIdx.x, p.gemm_blocks) * 4 + wid;
-    if (wlin >= ((p.M + 16 * MR - 1) / (16 * MR)) * wave_cols) return;
-    const int row0 = (wlin / wave_cols) * 16 * MR;
-    const int nt0 = (wlin % wave_cols) * RN;
-    int orow[MR], rA[MR];
-#pragma unroll
-    for (int m = 0; m < MR; ++m) {
-        orow[m] = row0 + 16 * m + c;
-        rA[m] = orow[m] < p.M ? orow[m] : p.M - 1;        // clamp: results of padded rows are dropped
-    }
-    bool nvalid[RN];
-    int ncl[RN];
-#pragma unroll
-    for (int n = 0; n < RN; ++n) {
-        nvalid[n] = nt0 + n < p.n_tiles;
-        ncl[n] = nvalid[n] ? n : 0;
-    }
     f32x4 acc[MR][RN];
 #pragma unroll
     for (int m = 0; m < MR; ++m)
 #pragma unroll
         for (int n = 0; n < RN; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    const int G1 = p.K1 / 16, T1 = (p.K1 - 16 * G1) / 4;  // full 16-k groups and 4-k tail steps of each segment
+    const int G2 = p.K2 / 16, T2 = (p.K2 - 16 * G2) / 4;
+    const int gbytes = p.n_tiles * 1024;                  // one group of the pack; a tail step is a quarter of it
+    const int b2off = (p.K1 / 4) * p.n_tiles * 256;       // segment 2's pack behind segment 1's (mcg_pack4_floats, in bytes)
+    // operand addresses = buffer descriptor (SGPRs) + one 32-bit lane offset + a scalar group offset: with
+    // 64-bit per-lane pointers every load of the loop costs a 64-bit VALU add, and on gfx950 VALU issue time
+    // adds to fp32-MFMA time
+    const __amdgpu_buffer_rsrc_t rs_a1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.A1), 0, 0xffffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.A2), 0, 0xffffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.Bp), 0, 0xffffffff, 0x00020000);
+    // the RING's descriptors: zero records for a segment without a full group - its (still unconditional) loads then fetch
+    // nothing and return 0.  A branch around ring loads instead would leave the ring with one definition per path: the
+    // copies that join them wait for every load in flight, i.e. drain the ring at the seam.
+    // (all ones or zero, by one scalar shift of -G written as asm: however it is spelled in C++, hipcc makes it a select and builds the
+    //  word in a VGPR, and a descriptor that is not in SGPRs turns every load into a waterfall loop)
+    int n1, n2;
+    asm("s_ashr_i32 %0, %1, 31" : "=s"(n1) : "s"(-G1) : "scc");
+    asm("s_ashr_i32 %0, %1, 31" : "=s"(n2) : "s"(-G2) : "scc");
+    const __amdgpu_buffer_rsrc_t rg_a1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.A1), 0, n1, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rg_b1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.Bp), 0, n1, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rg_a2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.A2), 0, n2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rg_b2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.Bp), 0, n2, 0x00020000);
+    auto ld4 = [](const __amdgpu_buffer_rsrc_t& r, unsigned v, int so) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)v, so, 0)); };
+    auto ld1 = [](const __amdgpu_buffer_rsrc_t& r, unsigned v, int so) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)v, so, 0)); };
+    unsigned oa1[MR], ob[RN];
+#pragma unroll
+    for (int m = 0; m < MR; ++m) oa1[m] = (unsigned)(rA[m] * p.lda1 + 4 * g) * 4u;
+#pragma unroll
+    for (int n = 0; n < RN; ++n) ob[n] = (unsigned)((nt0 + ncl[n]) * 256 + lane * 4) * 4u;
+
+    // ---- tail steps: lane group g holds k = 16 G + 4 st + g (scalar operands; the B line of step st is a quarter group)
+    float ta1[3][MR], tb1[3][RN], ta2[3][MR][NS], tb2[3][RN];
+#pragma unroll
+    for (int st = 0; st < 3; ++st) {
+#pragma unroll
+        for (int n = 0; n < RN; ++n) tb1[st][n] = tb2[st][n] = 0.f;
+#pragma unroll
+        for (int m = 0; m < MR; ++m) {
+            ta1[st][m] = 0.f;
+#pragma unroll
+            for (int q = 0; q < NS; ++q) ta2[st][m][q] = 0.f;
+        }
+    }
+#pragma unroll
+    for (int st = 0; st < 3; ++st)
+        if (st < T1) {
+#pragma unroll
+            for (int m = 0; m < MR; ++m) ta1[st][m] = ld1(rs_a1, oa1[m] - 12u * g, (16 * G1 + 4 * st) * 4);
+#pragma unroll
+            for (int n = 0; n < RN; ++n) tb1[st][n] = ld1(rs_b, ob[n] >> 2, G1 * gbytes + st * (gbytes >> 2));
+        }
+
+    // ---- the ring.  Loads are UNCONDITIONAL (group index and column tile clamped): a runtime "load or zero" select makes
+    //      hipcc branch around every load and drain vmcnt(0) behind it.
+    f32x4 Ar[RING][MR][NS], Br[RING][RN];
+    unsigned oa2[MR][NS];
+    auto load1 = [&](int slot, int q) {
+#pragma unroll
+        for (int m = 0; m < MR; ++m) Ar[slot][m][0] = ld4(rg_a1, oa1[m], 64 * q);
+#pragma unroll
+        for (int n = 0; n < RN; ++n) Br[slot][n] = ld4(rg_b1, ob[n], q * gbytes);
+    };
+    auto load2 = [&](int slot, int q) {
+        q = q < G2 ? q : G2 - 1;
+#pragma unroll
+        for (int m = 0; m < MR; ++m)
+#pragma unroll
+            for (int s = 0; s < NS; ++s) Ar[slot][m][s] = ld4(rg_a2, oa2[m][s], 64 * q);
+#pragma unroll
+        for (int n = 0; n < RN; ++n) Br[slot][n] = ld4(rg_b2, ob[n], b2off + q * gbytes);
+    };
+    auto mfmas = [&](int slot, const f32x4 (&a)[MR]) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int m = 0; m < MR; ++m)
+#pragma unroll
+                for (int n = 0; n < RN; ++n) acc[m][n] = mcg_mfma(Br[slot][n][s], a[m][s], acc[m][n]);
+    };
+    auto compute1 = [&](int slot) {
+        f32x4 a[MR];
+#pragma unroll
+        for (int m = 0; m < MR; ++m) a[m] = Ar[slot][m][0];
+        mfmas(slot, a);
+    };
+    auto compute2 = [&](int slot) {
+        f32x4 a[MR];
+#pragma unroll
+        for (int m = 0; m < MR; ++m) {
+            a[m] = Ar[slot][m][0];
+#pragma unroll
+            for (int s = 1; s < NS; ++s) a[m] = a[m] + Ar[slot][m][s];        // ((a + b) + c) + d: slot order, fixed
+        }
+        mfmas(slot, a);
+    };
+    const int s0 = G1 > 0 ? (RING - G1 % RING) % RING : RING;         // empty slots in front of segment 1's first trip
+    // (readfirstlane: hipcc takes this clamp through the VALU - a saturating subtract - and would then walk every load of the
+    //  fill in a waterfall loop.  Slot by slot: the wait counts in front of the last trip's MFMAs are the worst case over the
+    //  paths that reach it, one of them straight from here - the fill keeps the load order of a trip)
+#pragma unroll
+    for (int i = 0; i < RING; ++i) { load1(i, __builtin_amdgcn_readfirstlane(i > s0 ? i - s0 : 0)); __builtin_amdgcn_sched_barrier(0); }
+    __builtin_amdgcn_sched_barrier(0);
+
+    // ---- epilogue operands: behind the ring fill, a whole K loop ahead of their use
     f32x4 ebias[RN], eres[MR][RN];
 #pragma unroll
     for (int n = 0; n < RN; ++n) {
@@ -817,100 +773,100 @@ __global__ __launch_bounds__(256) void mcg_gemm16_kernel(McgGemmArgs p) {
             eres[m][n] = (p.resid && orow[m] < p.M && col + 3 < p.n_store) ? *reinterpret_cast<const f32x4*>(p.resid + (size_t)orow[m] * p.ldr + col)
                                                                             : (f32x4){0.f, 0.f, 0.f, 0.f};
     }
-    const float* bseg = p.Bp;
-    // one K segment; NSUM = 1: plain rows ra; 2 / 3 / 4: activation rows are the sum of rows ra, rb (, rc (, rd))
-    auto segment = [&](auto nsum_tag, const float* A, int K, int lda, const int (&ra)[MR], const int (&rb)[MR], const int (&rc)[MR],
-                       const int (&rd)[MR]) {
-        constexpr int NSUM = decltype(nsum_tag)::value;
-        constexpr bool TWO = NSUM >= 2, THREE = NSUM >= 3, FOUR = NSUM >= 4;
-        const int groups = K / 16;
-        const size_t gstride = (size_t)p.n_tiles * 256;
-        if (groups > 0) {
-            f32x4 Ar[RING][MR], Ar2[RING][MR], Ar3[RING][MR], Ar4[RING][MR], Br[RING][RN];
-            const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), 0, 0xffffffff, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bseg), 0, 0xffffffff, 0x00020000);
-            unsigned oa[MR], oa2[MR], oa3[MR], oa4[MR];
+    __builtin_amdgcn_sched_barrier(0);
+
+    // ---- segment 2's rows (the first use of the gather table: it was the first load of the kernel) and its tail steps
 #pragma unroll
-            for (int m = 0; m < MR; ++m) {
-                oa[m] = (unsigned)(ra[m] * lda + 4 * g) * 4u; oa2[m] = (unsigned)(rb[m] * lda + 4 * g) * 4u; oa3[m] = (unsigned)(rc[m] * lda + 4 * g) * 4u;
-                oa4[m] = (unsigned)(rd[m] * lda + 4 * g) * 4u;
+    for (int m = 0; m < MR; ++m) {
+        if constexpr (GATHER >= 2) {
+            const int rows[4] = {sl[m].x, sl[m].y, sl[m].z, sl[m].w};
+#pragma unroll
+            for (int s = 0; s < NS; ++s) oa2[m][s] = (unsigned)(rows[s] * p.lda2 + 4 * g) * 4u;
+        } else {
+            oa2[m][0] = (unsigned)(rA[m] * p.lda2 + 4 * g) * 4u;
+        }
+    }
+#pragma unroll
+    for (int st = 0; st < 3; ++st)
+        if (st < T2) {
+#pragma unroll
+            for (int m = 0; m < MR; ++m)
+#pragma unroll
+                for (int s = 0; s < NS; ++s) ta2[st][m][s] = ld1(rs_a2, oa2[m][s] - 12u * g, (16 * G2 + 4 * st) * 4);
+#pragma unroll
+            for (int n = 0; n < RN; ++n) tb2[st][n] = ld1(rs_b, ob[n] >> 2, b2off + G2 * gbytes + st * (gbytes >> 2));
+        }
+    __builtin_amdgcn_sched_barrier(0);
+
+    // ---- segment 1
+    {
+        int b = -s0;                                      // group in slot 0 of the current trip
+        // sched_barrier pins "MFMAs of slot i | loads into slot i": left alone, hipcc clusters all the loads at the
+        // loop bottom and the first MFMA block then waits for every one of them.
+        if (G1 > RING) {
+#pragma unroll
+            for (int i = 0; i < RING; ++i) {              // first trip: slots below s0 are empty
+                if (b + i >= 0) compute1(i);
+                __builtin_amdgcn_sched_barrier(0); load1(i, b + RING + i); __builtin_amdgcn_sched_barrier(0);
             }
-            unsigned obn[RN];
-#pragma unroll
-            for (int n = 0; n < RN; ++n) obn[n] = (unsigned)((nt0 + ncl[n]) * 256 + lane * 4) * 4u;
-            const int gbytes = p.n_tiles * 256 * 4;
-            auto load_group = [&](int slot, int q) {
-                q = q < groups ? q : groups - 1;
-#pragma unroll
-                for (int m = 0; m < MR; ++m) {
-                    Ar[slot][m] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_a, (int)oa[m], 64 * q, 0));
-                    if (TWO) Ar2[slot][m] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_a, (int)oa2[m], 64 * q, 0));
-                    if (THREE) Ar3[slot][m] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_a, (int)oa3[m], 64 * q, 0));
-                    if (FOUR) Ar4[slot][m] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_a, (int)oa4[m], 64 * q, 0));
-                }
-#pragma unroll
-                for (int n = 0; n < RN; ++n)
-                    Br[slot][n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_b, (int)obn[n], q * gbytes, 0));
-            };
-            auto compute = [&](int slot) {
-                f32x4 a[MR];
-#pragma unroll
-                for (int m = 0; m < MR; ++m)
-                    a[m] = FOUR ? ((Ar[slot][m] + Ar2[slot][m]) + Ar3[slot][m]) + Ar4[slot][m]
-                         : THREE ? (Ar[slot][m] + Ar2[slot][m]) + Ar3[slot][m] : TWO ? Ar[slot][m] + Ar2[slot][m] : Ar[slot][m];
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-#pragma unroll
-                    for (int m = 0; m < MR; ++m)
-#pragma unroll
-                        for (int n = 0; n < RN; ++n) acc[m][n] = mcg_mfma(Br[slot][n][s], a[m][s], acc[m][n]);
-            };
-#pragma unroll
-            for (int i = 0; i < RING; ++i) load_group(i, i);
-            int q = 0;
+            b += RING;
+            // branch-free body (control flow inside the loop makes hipcc's wait-count pass fall back to
+            // vmcnt(0) at the loop head, draining the ring); every group it asks for exists
 #pragma unroll 1
-            for (; q + RING <= groups; q += RING) {
+            for (; b + RING < G1; b += RING) {
 #pragma unroll
                 for (int i = 0; i < RING; ++i) {
-                    compute(i); __builtin_amdgcn_sched_barrier(0); load_group(i, q + RING + i); __builtin_amdgcn_sched_barrier(0);
+                    compute1(i); __builtin_amdgcn_sched_barrier(0); load1(i, b + RING + i); __builtin_amdgcn_sched_barrier(0);
                 }
             }
-#pragma unroll
-            for (int i = 0; i < RING - 1; ++i)
-                if (q + i < groups) compute(i);
         }
-        const int tail = (K - groups * 16) / 4;
-        const float* bt = bseg + (size_t)groups * gstride + (size_t)nt0 * 64 + lane;
-        for (int st = 0; st < tail; ++st) {
-            const int k = groups * 16 + 4 * st + g;                    // k = 16Q + 4st + g
+        // last trip (b = G1 - RING; the first one too when G1 <= RING, every slot empty when G1 = 0): the ring moves on to
+        // segment 2, slot i to its group i
+#pragma unroll
+        for (int i = 0; i < RING; ++i) {
+            if (b + i >= 0) compute1(i);
+            __builtin_amdgcn_sched_barrier(0); load2(i, i); __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+#pragma unroll
+    for (int st = 0; st < 3; ++st)
+        if (st < T1) {
+#pragma unroll
+            for (int n = 0; n < RN; ++n)
+#pragma unroll
+                for (int m = 0; m < MR; ++m) acc[m][n] = mcg_mfma(tb1[st][n], ta1[st][m], acc[m][n]);
+        }
+
+    // ---- segment 2: the ring holds its groups 0 .. RING - 1
+    if (G2 > 0) {
+        int q = 0;
+#pragma unroll 1
+        for (; q + RING <= G2; q += RING) {
+#pragma unroll
+            for (int i = 0; i < RING; ++i) {
+                compute2(i); __builtin_amdgcn_sched_barrier(0); load2(i, q + RING + i); __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < RING - 1; ++i)
+            if (q + i < G2) compute2(i);
+    }
+#pragma unroll
+    for (int st = 0; st < 3; ++st)
+        if (st < T2) {
             float av[MR];
 #pragma unroll
             for (int m = 0; m < MR; ++m) {
-                av[m] = A[(size_t)ra[m] * lda + k];
-                if (TWO) av[m] += A[(size_t)rb[m] * lda + k];
-                if (THREE) av[m] += A[(size_t)rc[m] * lda + k];
-                if (FOUR) av[m] += A[(size_t)rd[m] * lda + k];
+                av[m] = ta2[st][m][0];
+#pragma unroll
+                for (int s = 1; s < NS; ++s) av[m] += ta2[st][m][s];
             }
 #pragma unroll
-            for (int n = 0; n < RN; ++n) {
-                const float b = bt[(size_t)st * p.n_tiles * 64 + ncl[n] * 64];
+            for (int n = 0; n < RN; ++n)
 #pragma unroll
-                for (int m = 0; m < MR; ++m) acc[m][n] = mcg_mfma(b, av[m], acc[m][n]);
-            }
+                for (int m = 0; m < MR; ++m) acc[m][n] = mcg_mfma(tb2[st][n], av[m], acc[m][n]);
         }
-        bseg += mcg_pack4_floats(K, p.n_tiles);
-    };
-    if (p.K1 > 0) segment(std::integral_constant<int, 1>{}, p.A1, p.K1, p.lda1, rA, rA, rA, rA);
-    if (p.K2 > 0) {
-        if (GATHER) {
-            int sa[MR], sb[MR], sc[MR], sd[MR];
-#pragma unroll
-            for (int m = 0; m < MR; ++m) { const int4 sl = p.a2_rows[rA[m]]; sa[m] = sl.x; sb[m] = sl.y; sc[m] = sl.z; sd[m] = sl.w; }
-            segment(std::integral_constant<int, (GATHER >= 2 ? GATHER : 1)>{}, p.A2, p.K2, p.lda2, sa, sb, sc, sd);
-        } else {
-            segment(std::integral_constant<int, 1>{}, p.A2, p.K2, p.lda2, rA, rA, rA, rA);
-        }
-    }
+
 #pragma unroll
     for (int n = 0; n < RN; ++n) {
         if (!nvalid[n]) continue;
@@ -928,14 +884,45 @@ __global__ __launch_bounds__(256) void mcg_gemm16_kernel(McgGemmArgs p) {
                 for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
             }
             v += eres[m][n];
-            float* dst = p.C + (size_t)orow[m] * p.ldc + col;
+            float* dst = C_PTR ? mcg_gemm_c_ptr(p, orow[m], nt0 + n, g) : p.C + (size_t)orow[m] * p.ldc + col;
             if (col + 3 < p.n_store) {
-                *reinterpret_cast<f32x4*>(dst) = v;
-            } else {
+                *reinterpret_cast<f32x4*>(dst) = v;       // (4-byte aligned is enough for a global dwordx4 store)
+            } else {                                       // ragged right edge (GCN: 210 columns)
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (col + r < p.n_store) dst[r] = v[r];
             }
         }
     }
+}
+
+// 32-row wave tiles: a 256-thread workgroup owns 32 rows x (4 waves x RN column tiles); C row-major or blocked (mcg_gemm_c_ptr).
+template <int RN, int RING = 3>
+__global__ __launch_bounds__(256) void mcg_gemm_kernel(McgGemmArgs p) {
+    const int wid = threadIdx.x >> 6;
+    // waves are numbered linearly over (row block, wave column) so that the grid is exactly
+    // ceil(waves / 4) workgroups - a 2-D grid rounds each row block up to whole workgroups and
+    // can push a 243-workgroup problem over the 256-CU edge into a second round.
+    const int wave_cols = (p.n_tiles + RN - 1) / RN;
+    const int nblk = p.gemm_blocks > 0 ? p.gemm_blocks : (int)gridDim.x;        // (+ side-job workgroups behind them)
+    if ((int)blockIdx.x >= nblk) { mcg_gemm_side_job(p, (int)blockIdx.x - nblk); return; }
+    const int wlin = mcg_xcd_remap(blockIdx.x, nblk) * 4 + wid;
+    if (wlin >= ((p.M + 31) / 32) * wave_cols) return;
+    mcg_gemm_f32_tile<RN, 0, 2, RING, true>(p, (wlin / wave_cols) * 32, (wlin % wave_cols) * RN);
+}
+
+// ---------------------------------------------------------------------------------------------
+// 16-row variant for the node GEMMs (M = 1.7k .. 7k rows): a wave owns MR 16-row tiles x RN column tiles.
+// With 32-row wave tiles the three GEMMs of a GCL layer quantise badly on 1024 SIMDs at M = 1728 (K = 840,
+// N = 432: 756 waves of 840 MFMAs = 11.2 us of serial chain on 74 % of the SIMDs); 16 x 3 tiles give 972 waves
+// of 630 MFMAs (8.4 us), 16 x 6 the same for N = 864.  Same operand packs, ring discipline and transposed
+// accumulators as mcg_gemm_kernel.  GATHER: segment-2 rows are read as the sum of 2 / 3 / 4 rows (see a2_rows).
+template <int RN, int GATHER, int MR = 1, int RING = 3>       // GATHER 0 / 2 / 3 / 4 rows summed per A2 row; MR row tiles of 16 per wave
+__global__ __launch_bounds__(256) void mcg_gemm16_kernel(McgGemmArgs p) {
+    if ((int)blockIdx.x >= p.gemm_blocks) { mcg_gemm_side_job(p, (int)blockIdx.x - p.gemm_blocks); return; }
+    const int wid = threadIdx.x >> 6;
+    const int wave_cols = (p.n_tiles + RN - 1) / RN;
+    const int wlin = mcg_xcd_remap(blockIdx.x, p.gemm_blocks) * 4 + wid;
+    if (wlin >= ((p.M + 16 * MR - 1) / (16 * MR)) * wave_cols) return;
+    mcg_gemm_f32_tile<RN, GATHER, MR, RING, false>(p, (wlin / wave_cols) * 16 * MR, (wlin % wave_cols) * RN);
 }
