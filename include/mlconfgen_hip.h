@@ -545,6 +545,38 @@ int mcg_shape_overlay_field(const float* f, const float* ref_xform, const float*
                             float alpha, float amplitude, float* score, float* best, int32_t* which, int32_t* flipped,
                             float* pose, float* posed, void* stream);
 
+/* ---- Relaxed geometry ("Relaxed geometry"): the heavy atoms of B molecules moved downhill on a
+ * small restrained valence force field.  The force field is this package's OWN (DESIGN.md states it in full): a SUBSTITUTE
+ * for the reference's MMFF94 clean-up, NOT MMFF94 - harmonic bond, 1-3 distance and one-sided non-bonded terms plus the
+ * reference's position restraint (flat to 0.2 A, then 800 kcal/mol/A^2); no torsions, impropers, charges or hydrogens.
+ *   coords[B,N,3] the start coordinates; z[B,W] atomic numbers, bonds[B,W,W] symmetric bond codes (0 none / 1 / 2 / 3 /
+ *   4 aromatic; the diagonal, other codes and everything at or beyond n_b are read as 0), n_nodes_dev[b] real atoms
+ *   (device memory, clamped to [0, min(W, N)] on the device).  N and W are independent: N is the row width of the
+ *   coordinate buffers, W that of z and bonds.
+ *   steps trial steps of x' = x - (s / max_i |g_i|) g from s = 0.02 A: accepted only if E(x') < E(x) (then s *= 1.2, else
+ *   s *= 0.5); it stops early only where max_i |g_i| == 0.  steps = 0 copies the real atoms' coordinates bit for bit.
+ *   coords_out[B,N,3] (zero on padded atoms; may not alias coords); energy_out[B,2] = E at the start, E at the end;
+ *   grad_out[B,N,3] (optional, NULL = not wanted): dE/dx at the START coordinates, zero on padded atoms; stats_out[B,2]
+ *   (optional): accepted steps, largest distance of an atom from where it started.  n = 0 and n = 1 change nothing and
+ *   have E = 0.  A row with an element the library has no covalent radius for is copied unchanged with NaN energies (the
+ *   Python layer refuses it before the launch).
+ *   mcg_geometry_relax_ex: the same with restraint_ref[B,N,3] (optional, NULL = coords) as the positions the restraint
+ *   holds every atom to - a relaxation continued from moved coordinates stays restrained to the original ones.
+ * One 64-lane workgroup per molecule, no atomics, every sum in one order: a molecule's outputs have the same bits whatever
+ * the batch, its row and the two padded widths.
+ * MCG_ERR_ARG, nothing launched: a null required buffer, B < 0, N < 1, W outside 1..MCG_RELAX_MAX_ATOMS, steps outside
+ * 0..MCG_RELAX_MAX_STEPS.  B = 0 launches nothing. */
+#define MCG_RELAX_MAX_ATOMS 64
+#define MCG_RELAX_MAX_STEPS 4096
+int mcg_geometry_relax(const float* coords, const int32_t* z, const int8_t* bonds, const int32_t* n_nodes_dev,
+                       int B, int N /*coords row width*/, int W /*z, bonds width*/, int steps,
+                       float* coords_out, float* energy_out /*[B,2] start, end*/,
+                       float* grad_out /*optional [B,N,3]: gradient at the START coordinates*/,
+                       float* stats_out /*optional [B,2]: accepted steps, max atom displacement*/, void* stream);
+int mcg_geometry_relax_ex(const float* coords, const float* restraint_ref, const int32_t* z, const int8_t* bonds,
+                          const int32_t* n_nodes_dev, int B, int N, int W, int steps, float* coords_out,
+                          float* energy_out, float* grad_out, float* stats_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

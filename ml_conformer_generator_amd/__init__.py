@@ -10,9 +10,10 @@ from .config import (ATOM_DECODER, CONTEXT_NORMS, DIMENSION, MAX_N_NODES,
 
 _FINGERPRINT = ("graph_fingerprints", "fingerprint_tanimoto", "pairwise_fingerprint_tanimoto", "mol_graph", "select_unique")
 _MESH = ("load_mesh", "mass_properties", "mesh_context", "solid_frame")
+_GEOMETRY = ("relax_geometry", "strain_energy")
 
 __all__ = ["MLConformerGenerator", "evaluate_samples", "ATOM_DECODER", "CONTEXT_NORMS", "DIMENSION",
-           "MAX_N_NODES", "MIN_N_NODES", "NUM_BOND_TYPES", *_FINGERPRINT, *_MESH]
+           "MAX_N_NODES", "MIN_N_NODES", "NUM_BOND_TYPES", *_FINGERPRINT, *_MESH, *_GEOMETRY]
 
 
 def __getattr__(name):
@@ -29,4 +30,7 @@ def __getattr__(name):
     if name in _MESH:                    # watertight meshes as reference shapes (mesh.py: host side, no trimesh)
         from . import mesh
         return getattr(mesh, name)
+    if name in _GEOMETRY:                # restrained relaxation on the package's own force field (geometry.py: not MMFF94)
+        from . import geometry
+        return getattr(geometry, name)
     raise AttributeError(name)

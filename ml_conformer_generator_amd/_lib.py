@@ -72,6 +72,8 @@ SIGNATURES: Dict[str, tuple] = {
     "mcg_shape_tanimoto_field": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _f, _f, _vp, _vp]),
     "mcg_shape_overlay_field": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp]),
+    "mcg_geometry_relax": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mcg_geometry_relax_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mcg_handoff": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp]),
     "mcg_handoff_ex": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcg_handoff_elements": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -44,7 +44,11 @@ forced by the scope of this build:
   * `reference_shape`, `shape_density` (every generation entry): a watertight triangle mesh - an STL file, a (vertices,
     faces) pair - as the reference, what the reference's notebook does with `trimesh` (`mesh.py`, no `trimesh` needed);
     the shape options then score, pose and select against the solid, and `max_atoms_outside` filters on the posed atoms
-    that lie outside it.
+    that lie outside it;
+  * `relax_geometry` (every generation entry; off by default): every generated molecule's heavy atoms are relaxed on the
+    GPU, right behind the bond write-back, on the package's OWN restrained valence force field (`geometry.py`; NOT MMFF94),
+    and everything downstream reads the relaxed coordinates.  Independent of `optimise_geometry`, whose meaning and
+    warning are unchanged.
 """
 from __future__ import annotations
 
@@ -71,6 +75,7 @@ from . import postprocess
 from . import rdkit_order
 from . import receptor as mcg_receptor
 from . import fingerprint as mcg_fp
+from . import geometry as mcg_geometry
 from .handoff import (GeneratedMolecule, assemble_molecules, bond_writeback_hip, molecules_from_tensors,
                       prepare_adj_mat_seer_input_hip)
 from .mol_utils import (get_context_shape, ifm_get_xh_from_fragment, ifm_merge_hip,
@@ -334,6 +339,13 @@ class MLConformerGenerator(torch.nn.Module):
         """[B,B] pairwise Tanimoto of fingerprints (`fingerprint.pairwise_fingerprint_tanimoto`)."""
         return mcg_fp.pairwise_fingerprint_tanimoto(fp)
 
+    # the geometry step
+    def _relax_coords(self, coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
+                      n_nodes: torch.Tensor, steps: int) -> dict:
+        """Padded heavy-atom coordinates relaxed on the package's own force field (`geometry.relax_geometry`, unchecked:
+        the elements come from the validated decoder, the codes from the bond write-back; device tensors)."""
+        return mcg_geometry.relax_geometry(coords, atomic_numbers, bond_orders, n_nodes, steps, self.device, check=False)
+
     # the shape step
     def _score_coords(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
         """Shape Tanimoto [B] (device) of padded heavy-atom coordinates against the reference."""
@@ -380,9 +392,12 @@ class MLConformerGenerator(torch.nn.Module):
     def _generate_shard(self, ref_context, ref_n_atoms: int, variance: int, sizes: Optional[torch.Tensor],
                         n_samples: int, resample_steps, fixed_fragment, inertial_fragment_matching, blend_power,
                         ifm_diffusion_level, optimise_geometry: bool = True, sample_seed: Optional[int] = None,
-                        sample_ids: Optional[torch.Tensor] = None):
+                        sample_ids: Optional[torch.Tensor] = None, relax_steps: int = 0):
         """Sampler -> hand-off -> GCN -> bond write-back + validity proxy for `n_samples` molecules on THIS device.
         Returns per-sample DEVICE tensors (dim 0 = n_samples; n_samples may be 0 for an empty shard).
+        `relax_steps` > 0 (`relax_geometry`): every group's coordinates are relaxed right behind its bond write-back
+        (`_relax_coords`, one launch per group, all rows); the relaxed coordinates are what `x`, the finisher's records and
+        everything downstream hold, and `strain_before` / `strain_after` [n_samples] join the returned tensors.
         `sample_seed`, `sample_ids`: the keyed stream of `edm_tensors`; `sample_ids` (default arange) also names the
         records handed to the finisher.
 
@@ -412,10 +427,12 @@ class MLConformerGenerator(torch.nn.Module):
             if finisher is not None:      # an empty shard still takes part in the object gather of the finished molecules
                 from . import rdkit_finish
                 self._finish_stage = rdkit_finish.FinishStage(finisher, optimise_geometry, executor)
+            strain = dict(strain_before=torch.zeros(0, device=dev), strain_after=torch.zeros(0, device=dev)) \
+                if relax_steps else {}
             return dict(x=torch.zeros(0, N, 3, device=dev), elements=torch.zeros(0, D, dtype=torch.int8, device=dev),
                         bond=torch.zeros(0, D, D, dtype=torch.int8, device=dev),
                         n_nodes=torch.zeros(0, dtype=torch.int32, device=dev),
-                        valid=torch.zeros(0, dtype=torch.uint8, device=dev))
+                        valid=torch.zeros(0, dtype=torch.uint8, device=dev), **strain)
         x, h, node_mask = self.edm_tensors(
             reference_context=ref_context, n_samples=n_samples, min_n_nodes=ref_n_atoms - variance,
             max_n_nodes=ref_n_atoms + variance, resample_steps=resample_steps, fixed_fragment=fixed_fragment,
@@ -445,7 +462,12 @@ class MLConformerGenerator(torch.nn.Module):
             sym, valid = bond_writeback_hip(bond, el, ng)
             if built is not None and not all(built):          # `MolFromXYZBlock` returned None: the reference drops it
                 valid = valid & torch.tensor(built, dtype=torch.bool, device=valid.device)
-            parts.append((x_out, el, bond, sym, valid))
+            extra = ()
+            if relax_steps:                                   # all rows, valid or not: the finisher judges for itself
+                rel = self._relax_coords(x_out, el, sym, ng, relax_steps)
+                extra = (x_out, rel["energy_before"], rel["energy_after"])
+                x_out = rel["coords"]
+            parts.append((x_out, el, bond, sym, valid) + extra)
             orders.append(order if order is not None else [None] * (hi - lo))
             if fin is not None:                               # this group's records -> the pool, behind the order tasks
                 fin.add(molecules_from_tensors(x_out, el.to(torch.int8), sym, ng.to(torch.int32), valid.to(torch.uint8),
@@ -456,10 +478,14 @@ class MLConformerGenerator(torch.nn.Module):
         x_out, el, bond, sym, valid = (cat(k) for k in range(5))
         self._finish_stage = fin
         self.last_batch = dict(x=x, h=h, n_nodes=n_nodes, elements=el, bond=bond, x_ordered=x_out)     # tensors only
+        strain = {}
+        if relax_steps:           # `x_ordered` stays what the hand-off wrote; the relaxed coordinates are a key of their own
+            self.last_batch.update(x_ordered=cat(5), x_relaxed=x_out)
+            strain = dict(strain_before=cat(6), strain_after=cat(7))
         flat = [o for grp in orders for o in grp]
         self.last_order = None if all(o is None for o in flat) else flat    # per-molecule atom orders (None: generation order)
         return dict(x=x_out, elements=el.to(torch.int8), bond=sym, n_nodes=n_nodes.to(torch.int32),
-                    valid=valid.to(torch.uint8))
+                    valid=valid.to(torch.uint8), **strain)
 
     def _collect_finish(self, n_samples: int) -> List:
         """The pending finish of the shard generated last -> its `n_samples` per-sample results (None = dropped)."""
@@ -485,7 +511,8 @@ class MLConformerGenerator(torch.nn.Module):
                             max_receptor_clashes: Optional[int] = None, chemical_scores: bool = False,
                             reference_graph=None, max_chemical_tanimoto: Optional[float] = None, unique: bool = False,
                             max_pairwise_chemical_tanimoto: Optional[float] = None, reference_shape=None,
-                            shape_density: float = 0.02, max_atoms_outside: Optional[int] = None) -> List:
+                            shape_density: float = 0.02, max_atoms_outside: Optional[int] = None,
+                            relax_geometry: Union[bool, int] = False) -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
@@ -554,6 +581,18 @@ class MLConformerGenerator(torch.nn.Module):
         int property of that name): the heavy atoms of the pose outside the mesh; None (no property) where posing failed.
         `max_atoms_outside=k` (needs `overlay=True` and `reference_shape`): drop the molecules with more than k atoms
         outside, and those whose pose failed, beside `max_receptor_clashes`.
+        `relax_geometry`: True (200 steps) or a step budget 1..4096.  Every generated molecule's heavy atoms are relaxed on
+        the GPU right behind the bond write-back, one launch per group of molecules (`geometry.relax_geometry`; DESIGN.md
+        section 6, "Relaxed geometry"), on the package's OWN restrained valence force field - NOT MMFF94, heavy atoms
+        only: harmonic bond, 1-3 distance and one-sided non-bonded terms under the reference's position restraint (flat to
+        0.2 A, then 800 kcal/mol/A^2, `standardize_mol`), so no atom ends far from where the sampler put it.  The
+        relaxed coordinates are what everything behind it reads - the records handed to a finisher (RDKit's MMFF94, where
+        RDKit imports and `optimise_geometry` asks for it, then starts from them; the two are independent), posing,
+        scoring, receptor and mesh contacts - and what is returned.  Records carry `strain_before` / `strain_after`, the
+        force field's energy (kcal/mol by its constants) before and after, the Mols the double properties of those
+        names; None (no property) in a call that did not relax.  `last_batch["x_ordered"]` keeps the unrelaxed
+        coordinates, `last_batch["x_relaxed"]` holds the relaxed ones.  `optimise_geometry` and its warning mean what
+        they meant.
         Order of the stages: validity, `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`, `unique`, then
         the selection (threshold, exclusion, `top_k`).  The filters only remove molecules.
         Refused with ValueError before any device work: a chemical option that is not a bool / a real number in (0, 1],
@@ -565,24 +604,28 @@ class MLConformerGenerator(torch.nn.Module):
         heavy atom), max_receptor_clashes other than an integer >= 0 or without a receptor, a custom finisher, a
         `reference_shape` together with another reference, with `refine_overlay` or with a `receptor`, or without
         `n_atoms`, a mesh `load_mesh` refuses ("The mesh needs to be watertight."), a `shape_density` that is not a positive
-        real number, and max_atoms_outside other than an integer >= 0, without a `reference_shape` or without overlay."""
+        real number, max_atoms_outside other than an integer >= 0, without a `reference_shape` or without overlay, and
+        relax_geometry other than False, True or an integer in 1..4096 (a float, None, 0, a negative or larger number)."""
         if sample_seed is not None:
             seeding.check_seed(sample_seed)
         req = postprocess.parse_request(self, reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
                                         max_pairwise_tanimoto, refine_overlay, receptor, max_receptor_clashes,
                                         chemical_scores, reference_graph, max_chemical_tanimoto, unique,
                                         max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
-                                        reference_context)
+                                        reference_context, relax_geometry)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.ref_solid,
                                                            shape_density)
         keyed = () if sample_seed is None else (sample_seed, None)   # unseeded: the positional call of before
+        relax = dict(relax_steps=req.relax_steps) if req.relax_steps else {}
         res = self._generate_shard(ref_context, ref_n_atoms, variance, None, n_samples, resample_steps, fixed_fragment,
-                                   inertial_fragment_matching, blend_power, ifm_diffusion_level, optimise_geometry, *keyed)
+                                   inertial_fragment_matching, blend_power, ifm_diffusion_level, optimise_geometry, *keyed,
+                                   **relax)
         if getattr(self, "finisher", None) is None:
             return postprocess.return_records(self, req, postprocess.measure_tensors(self, req, res), None,
                                               optimise_geometry)
         done = self._collect_finish(n_samples)    # finished per group while the later groups were still on their way
-        return postprocess.return_finished(self, req, postprocess.measure_finished(self, req, done), None, sample_seed)
+        return postprocess.return_finished(self, req, postprocess.measure_finished(self, req, done, res), None,
+                                           sample_seed)
 
     @torch.no_grad()
     def generate_conformers_sharded(self, reference_conformer=None, n_samples: int = 10, variance: int = 2,
@@ -599,7 +642,8 @@ class MLConformerGenerator(torch.nn.Module):
                                     reference_graph=None, max_chemical_tanimoto: Optional[float] = None,
                                     unique: bool = False,
                                     max_pairwise_chemical_tanimoto: Optional[float] = None, reference_shape=None,
-                                    shape_density: float = 0.02, max_atoms_outside: Optional[int] = None) -> List:
+                                    shape_density: float = 0.02, max_atoms_outside: Optional[int] = None,
+                                    relax_geometry: Union[bool, int] = False) -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -617,7 +661,7 @@ class MLConformerGenerator(torch.nn.Module):
         no generator, so sample i is the same molecule on any world size and under either `balance`.
         `shape_scores`, `top_k`, `min_shape_tanimoto`, `overlay`, `max_pairwise_tanimoto`, `refine_overlay`, `receptor`,
         `max_receptor_clashes`, `chemical_scores`, `reference_graph`, `max_chemical_tanimoto`, `unique`,
-        `max_pairwise_chemical_tanimoto`, `reference_shape`, `shape_density`, `max_atoms_outside`: as in
+        `max_pairwise_chemical_tanimoto`, `reference_shape`, `shape_density`, `max_atoms_outside`, `relax_geometry`: as in
         `generate_conformers` (every rank loads the mesh and computes its occupancy itself).  The fingerprints are computed behind the gather,
         on the rows a rank returns: with gather="all" uniqueness and chemical diversity hold over the whole batch, with
         gather="rank0" within each other rank's own shard, like the rest of the selection.
@@ -636,7 +680,7 @@ class MLConformerGenerator(torch.nn.Module):
                                         max_pairwise_tanimoto, refine_overlay, receptor, max_receptor_clashes,
                                         chemical_scores, reference_graph, max_chemical_tanimoto, unique,
                                         max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
-                                        reference_context)
+                                        reference_context, relax_geometry)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.ref_solid,
                                                            shape_density)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)
@@ -648,16 +692,17 @@ class MLConformerGenerator(torch.nn.Module):
 
         def run_shard(sizes_shard, index):
             keyed = () if sample_seed is None else (sample_seed, index)
+            relax = dict(relax_steps=req.relax_steps) if req.relax_steps else {}
             res = self._generate_shard(ref_context, ref_n_atoms, variance, sizes_shard, int(index.numel()), resample_steps,
                                        fixed_fragment, inertial_fragment_matching, blend_power, ifm_diffusion_level,
-                                       optimise_geometry, *keyed)
+                                       optimise_geometry, *keyed, **relax)
             if not finishing:
                 return postprocess.measure_tensors(self, req, res)      # on this rank's GPU, gathered with the rest
             # collected HERE, in front of the status exchange: a finish that raises on one rank (a dead worker, a custom
             # finisher's exception, a result-count mismatch) makes EVERY rank raise ShardError instead of leaving the
             # others parked in the object gather
             done = self._collect_finish(int(index.numel()))
-            finished[:] = postprocess.measure_finished(self, req, done)
+            finished[:] = postprocess.measure_finished(self, req, done, res)
             return res
 
         def seed_device(s):

@@ -47,21 +47,23 @@ class GeneratedMolecule:
     (`overlay=True`), else None.  `receptor_clashes` / `receptor_max_overlap`: its steric contacts with the call's
     receptor, else None.  `chemical_tanimoto` / `graph_key`: its chemical similarity to the reference and its graph
     identity key (`fingerprint.py`: the package's own Morgan-type fingerprint, a substitute for RDKit's), else None.
-    `atoms_outside`: how many of its atoms lie outside the mesh of a call posed into a `reference_shape`, else None."""
+    `atoms_outside`: how many of its atoms lie outside the mesh of a call posed into a `reference_shape`, else None.
+    `strain_before` / `strain_after`: the energy of the package's own force field (`geometry.py`, NOT MMFF94) before and
+    after the relaxation of a call with `relax_geometry`, else None."""
     __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_score", "_overlay", "_contacts", "_chem",
-                 "_outside")
+                 "_outside", "_strain")
 
     def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True,
                  sample_id: Optional[int] = None):
         self._z, self._coords, self._bonds, self.valid = list(atomic_numbers), coords, bond_orders, bool(valid)
         self._batch, self._b, self._sid = None, -1, sample_id
-        self._score = self._overlay = self._contacts = self._chem = self._outside = None
+        self._score = self._overlay = self._contacts = self._chem = self._outside = self._strain = None
 
     @classmethod
     def _view(cls, batch: _HostBatch, b: int, valid: bool, sample_id: Optional[int] = None,
               score: Optional[float] = None, overlay: Optional[tuple] = None,
               contacts: Optional[tuple] = None, chem: Optional[tuple] = None,
-              outside: Optional[int] = None) -> "GeneratedMolecule":
+              outside: Optional[int] = None, strain: Optional[tuple] = None) -> "GeneratedMolecule":
         m = cls.__new__(cls)
         m._z = m._coords = m._bonds = None
         m.valid, m._batch, m._b = valid, batch, b
@@ -71,7 +73,20 @@ class GeneratedMolecule:
         m._contacts = contacts
         m._chem = chem
         m._outside = outside
+        m._strain = strain
         return m
+
+    @property
+    def strain_before(self) -> Optional[float]:
+        """The energy of the package's own restrained valence force field (`geometry.py`: NOT MMFF94; kcal/mol by its
+        constants) at the coordinates the sampler produced, when the call relaxed (`relax_geometry`); None otherwise."""
+        return None if self._strain is None else self._strain[0]
+
+    @property
+    def strain_after(self) -> Optional[float]:
+        """That energy at the returned, relaxed coordinates (restraint included; <= `strain_before`) when the call
+        relaxed (`relax_geometry`); None otherwise."""
+        return None if self._strain is None else self._strain[1]
 
     @property
     def atoms_outside(self) -> Optional[int]:
@@ -310,7 +325,8 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                            receptor_max_overlap: Optional[torch.Tensor] = None,
                            chemical_tanimoto: Optional[torch.Tensor] = None,
                            graph_key: Optional[torch.Tensor] = None,
-                           atoms_outside: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
+                           atoms_outside: Optional[torch.Tensor] = None, strain_before: Optional[torch.Tensor] = None,
+                           strain_after: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
     (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
     (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records).
@@ -319,11 +335,13 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     row b's receptor contacts (a negative clash count: not measured, the record gets None; None: a call without a
     receptor).  `chemical_tanimoto[b]` (fp32) / `graph_key[b]` (int64 holding the unsigned bit pattern): row b's chemical
     similarity to the reference and graph identity key (either may be None: not asked for).  `atoms_outside[b]`: row b's
-    atoms outside the call's mesh (negative: its pose failed, the record gets None; None: a call without a mesh)."""
+    atoms outside the call's mesh (negative: its pose failed, the record gets None; None: a call without a mesh).
+    `strain_before[b]` / `strain_after[b]`: row b's force-field energy before and after the relaxation of a call with
+    `relax_geometry` (both or neither; None: a call that did not relax)."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
     view = GeneratedMolecule._view
     if sample_ids is None and shape_tanimoto is None and overlay_tanimoto is None and chemical_tanimoto is None \
-            and graph_key is None:
+            and graph_key is None and strain_before is None:
         return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
     flags = valid.cpu().tolist()
     ids = list(range(len(flags))) if sample_ids is None else \
@@ -345,7 +363,9 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
         chem = list(zip(sim, keys))
     outside = [None] * len(flags) if atoms_outside is None else \
         [None if c < 0 else int(c) for c in atoms_outside.cpu().tolist()]
-    return [view(batch, b, bool(v), ids[b], scores[b], overlays[b], contacts[b], chem[b], outside[b])
+    strain = [None] * len(flags) if strain_before is None else \
+        [(float(e0), float(e1)) for e0, e1 in zip(strain_before.cpu().tolist(), strain_after.cpu().tolist())]
+    return [view(batch, b, bool(v), ids[b], scores[b], overlays[b], contacts[b], chem[b], outside[b], strain[b])
             for b, v in enumerate(flags)]
 
 

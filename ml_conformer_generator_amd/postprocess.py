@@ -35,6 +35,7 @@ import torch
 
 from . import cheminformatics
 from . import fingerprint as mcg_fp
+from . import geometry as mcg_geometry
 from . import host_pool
 from . import receptor as mcg_receptor
 from .handoff import molecules_from_tensors
@@ -59,6 +60,7 @@ class Request:
     max_pairwise_chemical_tanimoto: Optional[float] = None
     ref_solid: Optional[object] = None            # `cheminformatics.SolidReference` of a `reference_shape` call
     max_atoms_outside: Optional[int] = None
+    relax_steps: int = 0                          # `relax_geometry`: trial steps of the relaxation, 0 = not relaxed
 
     @property
     def selects_by_shape(self) -> bool:
@@ -92,12 +94,14 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
                   max_chemical_tanimoto: Optional[float] = None, unique=False,
                   max_pairwise_chemical_tanimoto: Optional[float] = None, reference_shape=None,
                   shape_density: float = 0.02, max_atoms_outside: Optional[int] = None,
-                  reference_context=None) -> Request:
+                  reference_context=None, relax_geometry: Union[bool, int] = False) -> Request:
     """The public option keywords of a generation entry of `gen` as a `Request`: the shape options first, then the chemical
     ones (`top_k` / `min_shape_tanimoto` / `max_pairwise_tanimoto` imply the shape score, `max_chemical_tanimoto` the
     chemical one).  `reference_shape`: a watertight mesh in place of the reference conformer (`mesh.load_mesh`); the
     request then carries its `cheminformatics.SolidReference` (host side only: nothing is launched here), whether or not an
-    option is on.  Every refusal happens here, before any device work."""
+    option is on.  `relax_geometry`: `geometry.check_steps`; it works with every other option and every finisher.
+    Every refusal happens here, before any device work."""
+    relax_steps = mcg_geometry.check_steps(relax_geometry)
     custom_finisher = isinstance(getattr(gen, "finisher", None), host_pool.TaskRef)
     shape = {}
     solid = None
@@ -122,7 +126,7 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
         if not overlay:
             raise ValueError("max_atoms_outside needs overlay=True: molecules that are not posed into the mesh are not "
                              "in its coordinates")
-    solid_kw = dict(ref_solid=solid, max_atoms_outside=max_atoms_outside)
+    solid_kw = dict(ref_solid=solid, max_atoms_outside=max_atoms_outside, relax_steps=relax_steps)
     if max_receptor_clashes is not None:
         mcg_receptor.check_max_receptor_clashes(max_receptor_clashes)
         if receptor is None:
@@ -323,7 +327,8 @@ def return_records(gen, req: Request, res: dict, row_ids: Optional[torch.Tensor]
                                   overlay_tanimoto=res.get("overlay_tanimoto"), pose=res.get("pose"),
                                   receptor_clashes=res.get("receptor_clashes"),
                                   receptor_max_overlap=res.get("receptor_max_overlap"),
-                                  atoms_outside=res.get("atoms_outside"), **chem_kw)
+                                  atoms_outside=res.get("atoms_outside"), strain_before=res.get("strain_before"),
+                                  strain_after=res.get("strain_after"), **chem_kw)
     gen.last_host_assembly_ms = (time.perf_counter() - t0) * 1e3      # D2H of the result tensors + record views
     kept, gen.last_valid_fraction = _finish(mols, optimise_geometry, use_rdkit=False)    # no finisher: the proxy
     if not req.removes:
@@ -375,13 +380,17 @@ def _contact_mols(gen, rec: tuple, mols: List, poses: List) -> List[Optional[tup
     return out
 
 
-def measure_finished(gen, req: Request, done: List) -> List[tuple]:
+def measure_finished(gen, req: Request, done: List, res: Optional[dict] = None) -> List[tuple]:
     """Stages 1-3 on one shard's finished Mols (None = dropped), each in ONE batched device call: pose, every conformer
     position moved (`cheminformatics.pose_mols`), then score (`score_mols`), then the receptor contacts of the posed
     Mols.  Per sample (Mol, shape Tanimoto, (overlay_tanimoto, rotation, translation), (receptor_clashes,
     receptor_max_overlap), atoms outside the mesh), None where the call did not ask, the Mol was dropped or - the last
-    two - its pose failed: the one value per sample that crosses the object gather."""
+    two - its pose failed: the one value per sample that crosses the object gather.  `res`: the shard's result tensors;
+    where the call relaxed (`strain_before` / `strain_after` in it) a sixth value follows, that pair as floats."""
     none = [None] * len(done)
+    extra = ()
+    if res is not None and "strain_before" in res:
+        extra = (list(zip(res["strain_before"].cpu().tolist(), res["strain_after"].cpu().tolist())),)
     pose_fn, counts = _pose_fn(gen, req), []
     if req.overlay and req.ref_solid is not None:
         def pose_fn(ref, coords, n, _solid=pose_fn):        # the one batched call of `pose_mols`: keep its counts
@@ -394,7 +403,7 @@ def measure_finished(gen, req: Request, done: List) -> List[tuple]:
         outside[k] = None if c < 0 else int(c)
     scores = score_mols(gen, req.ref_coord, done, _score_fn(gen, req)) if req.scores_shape else none
     contacts = _contact_mols(gen, req.receptor, done, poses) if req.receptor is not None else none
-    return list(zip(done, scores, poses, contacts, outside))
+    return list(zip(done, scores, poses, contacts, outside, *extra))
 
 
 def return_finished(gen, req: Request, samples: List[tuple], row_ids: Optional[torch.Tensor],
@@ -402,7 +411,8 @@ def return_finished(gen, req: Request, samples: List[tuple], row_ids: Optional[t
     """What a call returns through a finisher, from the (gathered) `measure_finished` values of the rows this rank returns
     (sample ids `row_ids`, default 0..B-1): stages 4-6.  The Mols get their properties here, behind the object gather,
     which does not carry them - `sample_id` (seeded calls), `overlay_tanimoto`, `shape_tanimoto`, `receptor_clashes`,
-    `receptor_max_overlap`, `atoms_outside`, and from the chemical step, which reads the live Mols' own graphs
+    `receptor_max_overlap`, `atoms_outside`, `strain_before` / `strain_after` (a call that relaxed), and from the chemical
+    step, which reads the live Mols' own graphs
     (`fingerprint.mol_graph`) in one batched device call, the double property `chemical_tanimoto` and the string property
     `graph_key` (the unsigned 64-bit key in decimal: it does not fit an int property).  Then `select`, the shape pair
     matrix taken from the surviving Mols' posed heavy atoms."""
@@ -414,6 +424,10 @@ def return_finished(gen, req: Request, samples: List[tuple], row_ids: Optional[t
     gen.last_host_assembly_ms = 0.0
     live = [i for i, m in enumerate(mols) if m is not None]
     gen.last_valid_fraction = len(live) / len(mols) if mols else 0.0
+    if req.relax_steps:
+        strain = [samples[i][5] if len(samples[i]) > 5 else None for i in live]
+        rdkit_finish.tag_scores([mols[i] for i in live], "strain_before", [None if s is None else s[0] for s in strain])
+        rdkit_finish.tag_scores([mols[i] for i in live], "strain_after", [None if s is None else s[1] for s in strain])
     if not req.measures:
         return [mols[i] for i in live]
     rows = Rows([mols[i] for i in live], [ids[i] for i in live], [samples[i][1] for i in live],
