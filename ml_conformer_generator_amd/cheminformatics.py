@@ -278,49 +278,97 @@ def check_reference_atoms(n_ref: int) -> None:
         raise ValueError(f"shape scoring needs a reference of 3 to {MAX_SCORED_ATOMS} heavy atoms, got {n_ref}")
 
 
-def _shape_inputs(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor, device,
-                  with_reference: bool, max_batch: Optional[int] = None):
-    """The common preamble of `shape_scores`, `shape_overlay` and `pairwise_shape_tanimoto`: (device, reference [n_ref,3]
-    fp32 on the host, batch x, counts nn), with x = nn = None for an empty batch.  `with_reference`: the reference is row
-    0 of x [B+1, max(W, n_ref), 3] and of nn, the samples follow; else x, nn are the samples as they are.  Refuses, before
-    any device work: a reference outside 3..MAX_SCORED_ATOMS heavy atoms, more than `max_batch` molecules and, for a
-    batch that is not empty, atom counts outside [0, W] and a padded width W above MAX_SCORED_ATOMS."""
+class ConformerReference:
+    """A reference conformer of the shape kernels: `coords` [n_ref,3] fp32, its heavy atoms, on the host.  It rides as row 0
+    of the samples' `shape_frames_hip` launch, which gives its frame, transform and grid axes anew on every call."""
+    refinable = True
+    pose_keys = ()                # what its pose adds to `shape_overlay`'s keys: (key, per-row shape, dtype)
+
+    def __init__(self, coords):
+        self.coords = torch.as_tensor(coords, dtype=torch.float32).cpu()
+        check_reference_atoms(int(self.coords.shape[0]))
+
+    def rows(self, x: torch.Tensor, nn: torch.Tensor, dev):
+        """The rows of the frames launch: the reference as row 0 of [B+1, max(W, n_ref), 3], then the samples."""
+        B, W = x.shape[:2]
+        n_ref = int(self.coords.shape[0])
+        out = torch.zeros(B + 1, max(W, n_ref), 3, device=dev)
+        out[0, :n_ref] = self.coords.to(dev)
+        out[1:, :W] = x
+        return out, torch.cat([torch.tensor([n_ref], dtype=torch.int32, device=dev), nn])
+
+    def score_frames(self, frames: torch.Tensor, nn: torch.Tensor, dev):
+        """(best [B], orientation [B]) of the samples' frames against the reference's (`mcg_shape_tanimoto`)."""
+        return shape_tanimoto_batch(frames[0, : self.coords.shape[0]], frames[1:], nn[1:], dev)[1:]
+
+    def launch_overlay(self, frames: torch.Tensor, xform: torch.Tensor, nn: torch.Tensor, rots: torch.Tensor, outputs: list,
+                       refine: list, dev) -> None:
+        """The pose launch over the rows of `rows`: `mcg_shape_overlay`, or `mcg_shape_overlay_refined` with its further
+        arguments `refine`; `outputs`: the pointers score, best, which, flipped, pose, posed of `_overlay`."""
+        n_ref = int(self.coords.shape[0])
+        B, N = int(frames.shape[0]) - 1, int(frames.shape[1])
+        ref_frame = frames[0, :n_ref].contiguous()
+        axes = _grid_axes(ref_frame.cpu(), 40).to(dev).contiguous()
+        f = torch.empty(40 ** 3, device=dev)
+        entry = "mcg_shape_overlay_refined" if refine else "mcg_shape_overlay"
+        _lib.check(getattr(_lib.lib(), entry)(
+            _lib.dptr(ref_frame), n_ref, _lib.dptr(xform), _lib.dptr(frames[1:]), _lib.dptr(xform[1:]), _lib.dptr(nn[1:]),
+            B, N, _lib.dptr(rots), _lib.dptr(axes), 40, float(ALPHA), float(AMPLITUDE), _lib.dptr(f), *outputs, *refine,
+            _lib.current_stream_ptr(dev)), entry)
+
+    def pose_extras(self, out: Dict[str, torch.Tensor], nn: torch.Tensor, dev) -> Dict[str, torch.Tensor]:
+        return {}
+
+    def grid(self, dev):
+        """(frame transform [12], grid axes [3,n]) of the pair matrix: one frames launch over the reference alone."""
+        xform = torch.empty(1, 12, device=dev)
+        _, frames = shape_frames_hip(self.coords.to(dev).unsqueeze(0),
+                                     torch.tensor([self.coords.shape[0]], dtype=torch.int32, device=dev), dev,
+                                     centre_atoms=True, xform_out=xform)
+        return xform, _grid_axes(frames[0].cpu(), 40).to(dev).contiguous()
+
+
+def _reference(reference):
+    """`reference` as a reference object: a `ConformerReference`, a `SolidReference`, or a conformer's raw coordinates."""
+    if isinstance(reference, (ConformerReference, SolidReference)):
+        return reference
+    return ConformerReference(reference)
+
+
+def _shape_inputs(reference, coords: torch.Tensor, n_nodes: torch.Tensor, device, max_batch: Optional[int] = None):
+    """The common preamble of `shape_scores`, `shape_overlay` and `pairwise_shape_tanimoto`: (reference object, device,
+    samples x [B,W,3] fp32 and counts nn [B] int32 on the device), with x = nn = None for an empty batch.  `reference`: a
+    `ConformerReference`, a `SolidReference` or a conformer's raw coordinates.  Refuses, before any device work: a
+    conformer outside 3..MAX_SCORED_ATOMS heavy atoms, more than `max_batch` molecules and, for a batch that is not empty,
+    atom counts outside [0, W] and a padded width W above MAX_SCORED_ATOMS."""
+    reference = _reference(reference)
     dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
-    ref = torch.as_tensor(reference_coord, dtype=torch.float32).cpu()
-    n_ref = int(ref.shape[0])
-    check_reference_atoms(n_ref)
     B = int(coords.shape[0])
     if max_batch is not None and B > max_batch:
         raise ValueError(f"pairwise shape Tanimoto takes at most {max_batch} molecules, got {B}")
     if B == 0:
-        return dev, ref, None, None
+        return reference, dev, None, None
     W = int(coords.shape[1])
-    check_n_nodes(n_nodes, B, W)         # before the reference widens the batch
+    check_n_nodes(n_nodes, B, W)         # before a conformer widens the batch
     if W > MAX_SCORED_ATOMS:
         raise ValueError(f"shape scoring takes at most {MAX_SCORED_ATOMS} atoms per molecule, got a padded width of {W}")
-    nn = n_nodes.to(dev, torch.int32).reshape(B)
-    if not with_reference:
-        return dev, ref, coords.to(dev, torch.float32).contiguous(), nn.contiguous()
-    x = torch.zeros(B + 1, max(W, n_ref), 3, device=dev)
-    x[0, :n_ref] = ref.to(dev)
-    x[1:, :W] = coords.to(dev, torch.float32)
-    return dev, ref, x, torch.cat([torch.tensor([n_ref], dtype=torch.int32, device=dev), nn])
+    return reference, dev, coords.to(dev, torch.float32).contiguous(), n_nodes.to(dev, torch.int32).reshape(B).contiguous()
 
 
 @torch.no_grad()
-def shape_scores(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor, device=None
+def shape_scores(reference_coord, coords: torch.Tensor, n_nodes: torch.Tensor, device=None
                  ) -> Tuple[torch.Tensor, torch.Tensor]:
     """(best [B], orientation [B]) on the device: the shape Tanimoto `evaluate_shape` reports for every sample
     (`evaluate_samples`, cheminformatics/pipeline.py:30-85), with the principal frames of the reference and of the samples
     from the HIP kernels (`shape_frames_hip`, reference = row 0 of the same launch) and the four-orientation search of
-    `mcg_shape_tanimoto`.  A sample's score depends on its own coordinates and the reference only."""
-    dev, ref, x, nn = _shape_inputs(reference_coord, coords, n_nodes, device, with_reference=True)
+    `mcg_shape_tanimoto`.  A sample's score depends on its own coordinates and the reference only.
+    `reference_coord`: the conformer's coordinates or a `ConformerReference`; a `SolidReference`: `shape_scores_solid`."""
+    ref, dev, x, nn = _shape_inputs(reference_coord, coords, n_nodes, device)
     if x is None:
         return torch.empty(0, device=dev), torch.empty(0, dtype=torch.long, device=dev)
-    n_ref = int(ref.shape[0])
+    x, nn = ref.rows(x, nn, dev)
     _, frames = shape_frames_hip(x, nn, dev, centre_atoms=True)
-    _, best, which = shape_tanimoto_batch(frames[0, :n_ref], frames[1:], nn[1:], dev)
-    return best, which
+    return ref.score_frames(frames, nn, dev)
 
 
 MAX_REFINE_STEPS = 1024       # csrc/mcg_shape_refine.hip RF_MAX_STEPS
@@ -345,7 +393,8 @@ def check_refine_steps(value, name: str = "refine_steps", lowest: int = 0, if_tr
 @torch.no_grad()
 def shape_overlay(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor, device=None,
                   with_scores: bool = False, refine_steps: int = 0) -> Dict[str, torch.Tensor]:
-    """Every sample posed onto the reference conformer, in the reference's own coordinates.
+    """Every sample posed onto the reference, in the reference's own coordinates.  `reference_coord`:
+    a conformer's coordinates or a `ConformerReference`, described here; a `SolidReference`: `shape_overlay_solid`.
     The principal frames of the reference (row 0) and of the samples come from one `mcg_shape_frames_tf` launch; the
     sample frame's handedness is made to match the reference's (so the pose is a rotation, never a mirror), the four
     orientations of `evaluate_samples` are scored on the reference's grid and the best becomes a rigid pose, all in one
@@ -368,55 +417,57 @@ def shape_overlay(reference_coord: torch.Tensor, coords: torch.Tensor, n_nodes: 
       (with_scores) refined_scores [B,4]  the refined candidates' scores; objective [B,4,2]  the Gaussian overlap of
                            each start before and after its ascent.
     0 (the default) is the unrefined path, unchanged.  A value outside 0..1024, a bool or a non-integer is refused with
-    ValueError before any device work."""
+    ValueError before any device work, and so is refining the pose into a solid."""
     steps = check_refine_steps(refine_steps)
     return _overlay(reference_coord, coords, n_nodes, device, with_scores, steps, steps > 0)
 
 
-def _overlay(reference_coord, coords, n_nodes, device, with_scores: bool, steps: int, refined_entry: bool):
-    """`shape_overlay` through `mcg_shape_overlay` or (`refined_entry`) `mcg_shape_overlay_refined` with `steps`."""
-    dev, ref, x, nn = _shape_inputs(reference_coord, coords, n_nodes, device, with_reference=True)
+def _overlay(reference, coords, n_nodes, device, with_scores: bool, steps: int, refined_entry: bool):
+    """`shape_overlay` through the reference's C entry: `mcg_shape_overlay`, (`refined_entry`) `mcg_shape_overlay_refined`
+    with `steps`, or a solid's `mcg_shape_overlay_field`."""
+    ref = _reference(reference)
+    if refined_entry and not ref.refinable:
+        raise ValueError("a pose into a solid cannot be refined: the ascent's objective is the overlap with the "
+                         "reference's atoms, and a mesh has none")
+    ref, dev, x, nn = _shape_inputs(ref, coords, n_nodes, device)
     B, W = int(coords.shape[0]), int(coords.shape[1])
     f32 = torch.float32
     keys = (("coords", (W, 3), f32, True), ("rotation", (3, 3), f32, True), ("translation", (3,), f32, True),
             ("tanimoto", (), f32, True), ("orientation", (), torch.long, True), ("flipped", (), torch.bool, True),
             ("scores", (4,), f32, with_scores), ("start_tanimoto", (), f32, refined_entry),
             ("refined", (), torch.bool, refined_entry), ("refined_scores", (4,), f32, refined_entry and with_scores),
-            ("objective", (4, 2), f32, refined_entry and with_scores))          # (key, per-row shape, dtype, returned)
+            ("objective", (4, 2), f32, refined_entry and with_scores)
+            ) + tuple(k + (True,) for k in ref.pose_keys)                       # (key, per-row shape, dtype, returned)
     if x is None:
         return {k: torch.zeros(0, *shape, dtype=dtype, device=dev) for k, shape, dtype, on in keys if on}
-    n_ref, N = int(ref.shape[0]), int(x.shape[1])
-    xform = torch.empty(B + 1, 12, device=dev)
+    x, nn = ref.rows(x, nn, dev)
+    first, N = int(x.shape[0]) - B, int(x.shape[1])                             # the samples' first row of the launch
+    xform = torch.empty(B + first, 12, device=dev)
     _, frames = shape_frames_hip(x, nn, dev, centre_atoms=True, xform_out=xform)
-    ref_frame = frames[0, :n_ref].contiguous()
-    axes = _grid_axes(ref_frame.cpu(), 40).to(dev).contiguous()
     rots = _orientations().reshape(4, 9).to(dev).contiguous()
-    f = torch.empty(40 ** 3, device=dev)
     scores = torch.empty(B, 4, device=dev) if with_scores else None
     best = torch.empty(B, device=dev)
     which = torch.empty(B, dtype=torch.int32, device=dev)
     flipped = torch.empty(B, dtype=torch.int32, device=dev)
     pose = torch.empty(B, 12, device=dev)
     posed = torch.empty(B, N, 3, device=dev)
-    args = (_lib.dptr(ref_frame), n_ref, _lib.dptr(xform), _lib.dptr(frames[1:]), _lib.dptr(xform[1:]), _lib.dptr(nn[1:]),
-            B, N, _lib.dptr(rots), _lib.dptr(axes), 40, float(ALPHA), float(AMPLITUDE), _lib.dptr(f), _lib.dptr(scores),
-            _lib.dptr(best), _lib.dptr(which), _lib.dptr(flipped), _lib.dptr(pose), _lib.dptr(posed))
     out = dict(scores=scores)
+    refine = []
     if refined_entry:
         ws = torch.empty(B, 4, 12, device=dev)
         out.update(objective=torch.empty(B, 4, 2, device=dev) if with_scores else None,
                    refined_scores=torch.empty(B, 4, device=dev) if with_scores else None,
                    start_tanimoto=torch.empty(B, device=dev), refined=torch.empty(B, dtype=torch.int32, device=dev))
-        _lib.check(_lib.lib().mcg_shape_overlay_refined(*args, int(steps), _lib.dptr(ws), _lib.dptr(out["objective"]),
-                                                        _lib.dptr(out["start_tanimoto"]), _lib.dptr(out["refined"]),
-                                                        _lib.dptr(out["refined_scores"]), _lib.current_stream_ptr(dev)),
-                   "mcg_shape_overlay_refined")
+        refine = [int(steps), _lib.dptr(ws), _lib.dptr(out["objective"]), _lib.dptr(out["start_tanimoto"]),
+                  _lib.dptr(out["refined"]), _lib.dptr(out["refined_scores"])]
+    outputs = [_lib.dptr(t) for t in (scores, best, which, flipped, pose, posed)]
+    ref.launch_overlay(frames, xform, nn, rots, outputs, refine, dev)
+    if refined_entry:
         out["refined"] = out["refined"].bool()
-    else:
-        _lib.check(_lib.lib().mcg_shape_overlay(*args, _lib.current_stream_ptr(dev)), "mcg_shape_overlay")
     failed = (which < 0).view(B, 1, 1)
-    out.update(coords=torch.where(failed, x[1:, :W], posed[:, :W]), rotation=pose[:, :9].reshape(B, 3, 3),
+    out.update(coords=torch.where(failed, x[first:, :W], posed[:, :W]), rotation=pose[:, :9].reshape(B, 3, 3),
                translation=pose[:, 9:], tanimoto=best, orientation=which.long(), flipped=flipped.bool())
+    out.update(ref.pose_extras(out, nn, dev))
     return {k: out[k] for k, _, _, on in keys if on}
 
 
@@ -479,17 +530,15 @@ def pairwise_shape_tanimoto(reference_coord: torch.Tensor, coords: torch.Tensor,
     The matrix is exactly symmetric, its diagonal exactly 1 where a molecule's density is finite and not zero, and entry
     (i, j) has the same bits whatever the batch, row order or padded width.  A molecule with no atoms or a non-finite
     coordinate gets a NaN row and column; the other entries are unaffected.  Refuses, before any device work, what
-    `shape_scores` refuses and more than `MAX_PAIR_BATCH` molecules."""
-    dev, ref, x, nn = _shape_inputs(reference_coord, coords, n_nodes, device, with_reference=False,
-                                    max_batch=MAX_PAIR_BATCH)
+    `shape_scores` refuses and more than `MAX_PAIR_BATCH` molecules.
+    `reference_coord`: a conformer's coordinates or a `ConformerReference`; a `SolidReference`:
+    `pairwise_shape_tanimoto_solid`."""
+    ref, dev, x, nn = _shape_inputs(reference_coord, coords, n_nodes, device, max_batch=MAX_PAIR_BATCH)
     if x is None:
         return torch.zeros(0, 0, device=dev)
     B, W = x.shape[0], x.shape[1]
-    xform = torch.empty(1, 12, device=dev)
-    _, frames = shape_frames_hip(ref.to(dev).unsqueeze(0), torch.tensor([ref.shape[0]], dtype=torch.int32, device=dev),
-                                 dev, centre_atoms=True, xform_out=xform)
-    n = 40
-    axes = _grid_axes(frames[0].cpu(), n).to(dev).contiguous()
+    xform, axes = ref.grid(dev)
+    n = int(axes.shape[1])
     gp = -(-n ** 3 // _PAIR_KALIGN) * _PAIR_KALIGN
     density = torch.empty(B, gp, device=dev)
     gram = torch.empty(B, B, device=dev)
@@ -626,29 +675,53 @@ class SolidReference:
             self._on[dev] = d
         return self._on[dev]
 
+    # what the shape bodies ask of a reference (`ConformerReference` has the same five)
+    refinable = False
+    pose_keys = (("atoms_outside", (), torch.int32),)
+
+    def rows(self, x: torch.Tensor, nn: torch.Tensor, dev):
+        """The rows of the frames launch: the samples as they are (the solid's device side is built in front of it)."""
+        self.on(dev)
+        return x, nn
+
+    def score_frames(self, frames: torch.Tensor, nn: torch.Tensor, dev):
+        """(best [B], orientation [B]) of the samples' frames against the occupancy (`mcg_shape_tanimoto_field`)."""
+        d = self.on(dev)
+        B, N = frames.shape[:2]
+        rots = _orientations().reshape(4, 9).to(dev).contiguous()
+        score = torch.empty(B * 4, device=dev)
+        _lib.check(_lib.lib().mcg_shape_tanimoto_field(_lib.dptr(d["f"]), _lib.dptr(frames), _lib.dptr(nn), B, N,
+                                                       _lib.dptr(rots), 4, _lib.dptr(d["axes"]), self.n, float(ALPHA),
+                                                       float(AMPLITUDE), _lib.dptr(score), _lib.current_stream_ptr(dev)),
+                   "mcg_shape_tanimoto_field")
+        return tuple(score.reshape(B, 4).max(dim=1))
+
+    def launch_overlay(self, frames: torch.Tensor, xform: torch.Tensor, nn: torch.Tensor, rots: torch.Tensor, outputs: list,
+                       refine: list, dev) -> None:
+        """The pose launch over the rows of `rows`: `mcg_shape_overlay_field` (`refine` is empty: `refinable`); `outputs`:
+        the pointers score, best, which, flipped, pose, posed of `_overlay`."""
+        d = self.on(dev)
+        B, N = int(frames.shape[0]), int(frames.shape[1])
+        _lib.check(_lib.lib().mcg_shape_overlay_field(
+            _lib.dptr(d["f"]), _lib.dptr(d["xform"]), _lib.dptr(frames), _lib.dptr(xform), _lib.dptr(nn), B, N,
+            _lib.dptr(rots), _lib.dptr(d["axes"]), self.n, float(ALPHA), float(AMPLITUDE), *outputs,
+            _lib.current_stream_ptr(dev)), "mcg_shape_overlay_field")
+
+    def pose_extras(self, out: Dict[str, torch.Tensor], nn: torch.Tensor, dev) -> Dict[str, torch.Tensor]:
+        counts = mesh_atoms_outside(self.on(dev)["triangles_own"], out["coords"], nn, dev)
+        return dict(atoms_outside=torch.where(out["orientation"] < 0, torch.full_like(counts, -1), counts))
+
+    def grid(self, dev):
+        """(frame transform [12], grid axes [3,n]) of the pair matrix: the solid's own."""
+        d = self.on(dev)
+        return d["xform"], d["axes"]
+
 
 def solid_reference(mesh, n: int = 40) -> SolidReference:
     """`mesh` (anything `mesh.load_mesh` takes) as a `SolidReference` on an n^3 grid, prepared once per call."""
     return mesh if isinstance(mesh, SolidReference) else SolidReference(mesh, n)
 
 
-def _solid_inputs(solid, coords: torch.Tensor, n_nodes: torch.Tensor, device, max_batch: Optional[int] = None):
-    """(SolidReference, device, x, nn) with x = nn = None for an empty batch; the refusals of `_shape_inputs`."""
-    solid = solid_reference(solid)
-    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
-    B = int(coords.shape[0])
-    if max_batch is not None and B > max_batch:
-        raise ValueError(f"pairwise shape Tanimoto takes at most {max_batch} molecules, got {B}")
-    if B == 0:
-        return solid, dev, None, None
-    W = int(coords.shape[1])
-    check_n_nodes(n_nodes, B, W)
-    if W > MAX_SCORED_ATOMS:
-        raise ValueError(f"shape scoring takes at most {MAX_SCORED_ATOMS} atoms per molecule, got a padded width of {W}")
-    return solid, dev, coords.to(dev, torch.float32).contiguous(), n_nodes.to(dev, torch.int32).reshape(B).contiguous()
-
-
-@torch.no_grad()
 def shape_scores_solid(solid, coords: torch.Tensor, n_nodes: torch.Tensor, device=None
                        ) -> Tuple[torch.Tensor, torch.Tensor]:
     """`shape_scores` against a solid: (best [B], orientation [B]) on the device.  Every sample's principal frame
@@ -656,50 +729,9 @@ def shape_scores_solid(solid, coords: torch.Tensor, n_nodes: torch.Tensor, devic
     the solid's grid (`mcg_shape_tanimoto_field`): <f,g> / (<f,f> + <g,g> - <f,g>) with f the indicator function of the
     solid and g the sample's Gaussian density.  The indicator function as the density of a solid is this package's own
     choice, not the reference's (which scores molecules against molecules)."""
-    solid, dev, x, nn = _solid_inputs(solid, coords, n_nodes, device)
-    if x is None:
-        return torch.empty(0, device=dev), torch.empty(0, dtype=torch.long, device=dev)
-    d = solid.on(dev)
-    B, N = int(x.shape[0]), int(x.shape[1])
-    _, frames = shape_frames_hip(x, nn, dev, centre_atoms=True)
-    rots = _orientations().reshape(4, 9).to(dev).contiguous()
-    score = torch.empty(B * 4, device=dev)
-    _lib.check(_lib.lib().mcg_shape_tanimoto_field(_lib.dptr(d["f"]), _lib.dptr(frames), _lib.dptr(nn), B, N, _lib.dptr(rots),
-                                                   4, _lib.dptr(d["axes"]), solid.n, float(ALPHA), float(AMPLITUDE),
-                                                   _lib.dptr(score), _lib.current_stream_ptr(dev)),
-               "mcg_shape_tanimoto_field")
-    best, which = score.reshape(B, 4).max(dim=1)
-    return best, which
+    return shape_scores(solid_reference(solid), coords, n_nodes, device)
 
 
-def _overlay_field(f: torch.Tensor, ref_xform: torch.Tensor, axes: torch.Tensor, x: torch.Tensor, nn: torch.Tensor, dev,
-                   with_scores: bool) -> Dict[str, torch.Tensor]:
-    """`mcg_shape_overlay_field` on samples x [B,N,3] (device): the body of `_overlay` behind the reference's part, with
-    the reference given as its density f [n^3] on `axes` [3,n] and its frame transform `ref_xform` [12]."""
-    B, N, n = int(x.shape[0]), int(x.shape[1]), int(axes.shape[1])
-    xform = torch.empty(B, 12, device=dev)
-    _, frames = shape_frames_hip(x, nn, dev, centre_atoms=True, xform_out=xform)
-    rots = _orientations().reshape(4, 9).to(dev).contiguous()
-    scores = torch.empty(B, 4, device=dev) if with_scores else None
-    best = torch.empty(B, device=dev)
-    which = torch.empty(B, dtype=torch.int32, device=dev)
-    flipped = torch.empty(B, dtype=torch.int32, device=dev)
-    pose = torch.empty(B, 12, device=dev)
-    posed = torch.empty(B, N, 3, device=dev)
-    _lib.check(_lib.lib().mcg_shape_overlay_field(_lib.dptr(f), _lib.dptr(ref_xform), _lib.dptr(frames), _lib.dptr(xform),
-                                                  _lib.dptr(nn), B, N, _lib.dptr(rots), _lib.dptr(axes), n, float(ALPHA),
-                                                  float(AMPLITUDE), _lib.dptr(scores), _lib.dptr(best), _lib.dptr(which),
-                                                  _lib.dptr(flipped), _lib.dptr(pose), _lib.dptr(posed),
-                                                  _lib.current_stream_ptr(dev)), "mcg_shape_overlay_field")
-    failed = (which < 0).view(B, 1, 1)
-    out = dict(coords=torch.where(failed, x, posed), rotation=pose[:, :9].reshape(B, 3, 3), translation=pose[:, 9:],
-               tanimoto=best, orientation=which.long(), flipped=flipped.bool())
-    if with_scores:
-        out["scores"] = scores
-    return out
-
-
-@torch.no_grad()
 def shape_overlay_solid(solid, coords: torch.Tensor, n_nodes: torch.Tensor, device=None, with_scores: bool = False
                         ) -> Dict[str, torch.Tensor]:
     """`shape_overlay` onto a solid: every sample posed into the mesh's own coordinates by a proper rigid transform - its
@@ -708,42 +740,13 @@ def shape_overlay_solid(solid, coords: torch.Tensor, n_nodes: torch.Tensor, devi
     same meaning and failure rows, plus
       atoms_outside [B] int32   the real atoms of the pose with |winding number| <= 0.5 (`mcg_mesh_atoms_outside`, against
                                 the mesh in its own coordinates); -1 where the pose failed."""
-    solid, dev, x, nn = _solid_inputs(solid, coords, n_nodes, device)
-    if x is None:
-        W = int(coords.shape[1])
-        out = dict(coords=torch.zeros(0, W, 3, device=dev), rotation=torch.zeros(0, 3, 3, device=dev),
-                   translation=torch.zeros(0, 3, device=dev), tanimoto=torch.zeros(0, device=dev),
-                   orientation=torch.zeros(0, dtype=torch.long, device=dev),
-                   flipped=torch.zeros(0, dtype=torch.bool, device=dev))
-        if with_scores:
-            out["scores"] = torch.zeros(0, 4, device=dev)
-        out["atoms_outside"] = torch.zeros(0, dtype=torch.int32, device=dev)
-        return out
-    d = solid.on(dev)
-    out = _overlay_field(d["f"], d["xform"], d["axes"], x, nn, dev, with_scores)
-    counts = mesh_atoms_outside(d["triangles_own"], out["coords"], nn, dev)
-    out["atoms_outside"] = torch.where(out["orientation"] < 0, torch.full_like(counts, -1), counts)
-    return out
+    return shape_overlay(solid_reference(solid), coords, n_nodes, device, with_scores)
 
 
-@torch.no_grad()
 def pairwise_shape_tanimoto_solid(solid, coords: torch.Tensor, n_nodes: torch.Tensor, device=None) -> torch.Tensor:
     """`pairwise_shape_tanimoto` of molecules posed into a solid's coordinates (`shape_overlay_solid`): one
     `mcg_shape_pair_tanimoto` call with the solid's frame transform and grid in place of a reference conformer's."""
-    solid, dev, x, nn = _solid_inputs(solid, coords, n_nodes, device, max_batch=MAX_PAIR_BATCH)
-    if x is None:
-        return torch.zeros(0, 0, device=dev)
-    d = solid.on(dev)
-    B, W, n = x.shape[0], x.shape[1], solid.n
-    gp = -(-n ** 3 // _PAIR_KALIGN) * _PAIR_KALIGN
-    density = torch.empty(B, gp, device=dev)
-    gram = torch.empty(B, B, device=dev)
-    out = torch.empty(B, B, device=dev)
-    _lib.check(_lib.lib().mcg_shape_pair_tanimoto(_lib.dptr(x), _lib.dptr(nn), B, W, _lib.dptr(d["xform"]),
-                                                  _lib.dptr(d["axes"]), n, float(ALPHA), float(AMPLITUDE),
-                                                  _lib.dptr(density), _lib.dptr(gram), _lib.dptr(out),
-                                                  _lib.current_stream_ptr(dev)), "mcg_shape_pair_tanimoto")
-    return out
+    return pairwise_shape_tanimoto(solid_reference(solid), coords, n_nodes, device)
 
 
 def check_max_atoms_outside(value) -> int:

@@ -302,14 +302,14 @@ class MLConformerGenerator(torch.nn.Module):
             return parse_molblock_heavy_atoms(reference_conformer)[0]
         return torch.as_tensor(reference_conformer, dtype=torch.float32)
 
-    def _reference_context(self, reference_conformer, reference_context, n_atoms, ref_solid=None,
+    def _reference_context(self, reference_conformer, reference_context, n_atoms, reference=None,
                            shape_density: float = 0.02):
-        if ref_solid is not None:          # a mesh: the notebook's principal_inertia_components at `density`, with n_atoms
+        if isinstance(reference, cheminformatics.SolidReference):          # a mesh: the notebook's principal_inertia_components at `density`, with n_atoms
             if not n_atoms:
                 raise ValueError(
                     "Reference Number of Atoms should be provided, when generating samples using context.")
             from . import mesh as mcg_mesh
-            return mcg_mesh.mesh_context(ref_solid.mesh, shape_density), n_atoms
+            return mcg_mesh.mesh_context(reference.mesh, shape_density), n_atoms
         if reference_conformer is not None and reference_conformer is not False:
             ref_coord = self._reference_coord(reference_conformer)
             ref_n_atoms = int(ref_coord.shape[0])
@@ -347,37 +347,20 @@ class MLConformerGenerator(torch.nn.Module):
         return mcg_geometry.relax_geometry(coords, atomic_numbers, bond_orders, n_nodes, steps, self.device, check=False)
 
     # the shape step
-    def _score_coords(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
-        """Shape Tanimoto [B] (device) of padded heavy-atom coordinates against the reference."""
-        return cheminformatics.shape_scores(ref_coord, coords, n_nodes, self.device)[0]
+    def _score(self, reference, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
+        """Shape Tanimoto [B] (device) of padded heavy-atom coordinates against the call's reference object
+        (`cheminformatics.shape_scores`)."""
+        return cheminformatics.shape_scores(reference, coords, n_nodes, self.device)[0]
 
-    def _pose_coords(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor) -> dict:
-        """Padded heavy-atom coordinates posed onto the reference (`cheminformatics.shape_overlay`, device tensors)."""
-        return cheminformatics.shape_overlay(ref_coord, coords, n_nodes, self.device)
+    def _pose(self, reference, coords: torch.Tensor, n_nodes: torch.Tensor, refine_steps: int = 0) -> dict:
+        """Padded heavy-atom coordinates posed onto the call's reference object, the pose refined when `refine_steps` > 0
+        (`cheminformatics.shape_overlay`, device tensors; a solid's result also holds `atoms_outside`)."""
+        return cheminformatics.shape_overlay(reference, coords, n_nodes, self.device, refine_steps=refine_steps)
 
-    def _pose_coords_refined(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor,
-                             steps: int) -> dict:
-        """`_pose_coords` with the refined pose (`cheminformatics.shape_overlay(refine_steps=steps)`, device tensors)."""
-        return cheminformatics.shape_overlay(ref_coord, coords, n_nodes, self.device, refine_steps=steps)
-
-    def _pair_coords(self, ref_coord: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
-        """[B,B] pairwise shape Tanimoto (device) of padded heavy-atom coordinates posed onto the reference
+    def _pair(self, reference, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
+        """[B,B] pairwise shape Tanimoto (device) of padded heavy-atom coordinates posed onto the call's reference object
         (`cheminformatics.pairwise_shape_tanimoto`)."""
-        return cheminformatics.pairwise_shape_tanimoto(ref_coord, coords, n_nodes, self.device)
-
-    def _score_solid(self, solid, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
-        """Shape Tanimoto [B] (device) of padded heavy-atom coordinates against a solid (`shape_scores_solid`)."""
-        return cheminformatics.shape_scores_solid(solid, coords, n_nodes, self.device)[0]
-
-    def _pose_solid(self, solid, coords: torch.Tensor, n_nodes: torch.Tensor) -> dict:
-        """Padded heavy-atom coordinates posed into a solid's own coordinates, with `atoms_outside`
-        (`cheminformatics.shape_overlay_solid`, device tensors)."""
-        return cheminformatics.shape_overlay_solid(solid, coords, n_nodes, self.device)
-
-    def _pair_solid(self, solid, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
-        """[B,B] pairwise shape Tanimoto (device) of padded heavy-atom coordinates posed into a solid
-        (`cheminformatics.pairwise_shape_tanimoto_solid`)."""
-        return cheminformatics.pairwise_shape_tanimoto_solid(solid, coords, n_nodes, self.device)
+        return cheminformatics.pairwise_shape_tanimoto(reference, coords, n_nodes, self.device)
 
     def _receptor_coords(self, rec: tuple, coords: torch.Tensor, n_nodes: torch.Tensor,
                          atomic_numbers: torch.Tensor) -> torch.Tensor:
@@ -613,7 +596,7 @@ class MLConformerGenerator(torch.nn.Module):
                                         chemical_scores, reference_graph, max_chemical_tanimoto, unique,
                                         max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
                                         reference_context, relax_geometry)
-        ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.ref_solid,
+        ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         keyed = () if sample_seed is None else (sample_seed, None)   # unseeded: the positional call of before
         relax = dict(relax_steps=req.relax_steps) if req.relax_steps else {}
@@ -681,7 +664,7 @@ class MLConformerGenerator(torch.nn.Module):
                                         chemical_scores, reference_graph, max_chemical_tanimoto, unique,
                                         max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
                                         reference_context, relax_geometry)
-        ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.ref_solid,
+        ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)
         hi_n = min(ref_n_atoms + variance, self.max_n_nodes)

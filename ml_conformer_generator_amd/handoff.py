@@ -15,7 +15,8 @@ parity unpinned against RDKit).  "valid" without RDKit is a valence / connectivi
 from __future__ import annotations
 
 import ctypes
-from typing import List, Optional, Sequence, Tuple
+import dataclasses
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -34,6 +35,45 @@ class _HostBatch:
         self.x, self.elements, self.bonds, self.n = x, elements, bonds, n
 
 
+@dataclasses.dataclass
+class Measured:
+    """What a generation call measured of one molecule; None = not measured (`GeneratedMolecule`'s properties of the same
+    names say what each value is)."""
+    shape_tanimoto: Optional[float] = None
+    overlay_tanimoto: Optional[float] = None
+    pose: Optional[torch.Tensor] = None           # [12] fp32: rotation row-major, then translation
+    receptor_clashes: Optional[int] = None
+    receptor_max_overlap: Optional[float] = None
+    atoms_outside: Optional[int] = None
+    chemical_tanimoto: Optional[float] = None
+    graph_key: Optional[int] = None               # unsigned 64-bit
+    strain_before: Optional[float] = None
+    strain_after: Optional[float] = None
+
+
+_UNMEASURED = Measured()          # shared by every record that carries no values: never written to
+
+
+def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> List[Measured]:
+    """The records of n samples from per-sample tensors by field name of `Measured` (a name left out or None: not
+    measured), one D2H copy each.  The one place that reads the tensors' spellings of "not measured": a negative
+    `receptor_clashes` (both contact values None), a negative `atoms_outside`, a `pose` row [12] with a non-finite entry
+    (`overlay_tanimoto` keeps its NaN); `graph_key` is int64 holding the unsigned bit pattern."""
+    cols = {k: v.cpu().tolist() for k, v in values.items() if v is not None and k != "pose"}
+    if values.get("pose") is not None:
+        poses = values["pose"].cpu().to(torch.float32)
+        cols["pose"] = [poses[b] if ok else None for b, ok in enumerate(torch.isfinite(poses).all(dim=1).tolist())]
+    if "receptor_clashes" in cols:
+        missing = [c < 0 for c in cols["receptor_clashes"]]
+        for k in ("receptor_clashes", "receptor_max_overlap"):
+            cols[k] = [None if gone else v for gone, v in zip(missing, cols[k])]
+    if "atoms_outside" in cols:
+        cols["atoms_outside"] = [None if c < 0 else c for c in cols["atoms_outside"]]
+    if "graph_key" in cols:
+        cols["graph_key"] = [k & 0xFFFFFFFFFFFFFFFF for k in cols["graph_key"]]
+    return [Measured(**{k: col[b] for k, col in cols.items()}) for b in range(n)]
+
+
 class GeneratedMolecule:
     """RDKit-free result record: heavy atoms, coordinates and bond orders.
 
@@ -50,103 +90,93 @@ class GeneratedMolecule:
     `atoms_outside`: how many of its atoms lie outside the mesh of a call posed into a `reference_shape`, else None.
     `strain_before` / `strain_after`: the energy of the package's own force field (`geometry.py`, NOT MMFF94) before and
     after the relaxation of a call with `relax_geometry`, else None."""
-    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_score", "_overlay", "_contacts", "_chem",
-                 "_outside", "_strain")
+    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_measured")
 
     def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True,
                  sample_id: Optional[int] = None):
         self._z, self._coords, self._bonds, self.valid = list(atomic_numbers), coords, bond_orders, bool(valid)
-        self._batch, self._b, self._sid = None, -1, sample_id
-        self._score = self._overlay = self._contacts = self._chem = self._outside = self._strain = None
+        self._batch, self._b, self._sid, self._measured = None, -1, sample_id, _UNMEASURED
 
     @classmethod
     def _view(cls, batch: _HostBatch, b: int, valid: bool, sample_id: Optional[int] = None,
-              score: Optional[float] = None, overlay: Optional[tuple] = None,
-              contacts: Optional[tuple] = None, chem: Optional[tuple] = None,
-              outside: Optional[int] = None, strain: Optional[tuple] = None) -> "GeneratedMolecule":
+              measured: Measured = _UNMEASURED) -> "GeneratedMolecule":
         m = cls.__new__(cls)
         m._z = m._coords = m._bonds = None
         m.valid, m._batch, m._b = valid, batch, b
         m._sid = b if sample_id is None else sample_id
-        m._score = score
-        m._overlay = overlay
-        m._contacts = contacts
-        m._chem = chem
-        m._outside = outside
-        m._strain = strain
+        m._measured = measured
         return m
 
     @property
     def strain_before(self) -> Optional[float]:
         """The energy of the package's own restrained valence force field (`geometry.py`: NOT MMFF94; kcal/mol by its
         constants) at the coordinates the sampler produced, when the call relaxed (`relax_geometry`); None otherwise."""
-        return None if self._strain is None else self._strain[0]
+        return self._measured.strain_before
 
     @property
     def strain_after(self) -> Optional[float]:
         """That energy at the returned, relaxed coordinates (restraint included; <= `strain_before`) when the call
         relaxed (`relax_geometry`); None otherwise."""
-        return None if self._strain is None else self._strain[1]
+        return self._measured.strain_after
 
     @property
     def atoms_outside(self) -> Optional[int]:
         """How many heavy atoms of the returned pose lie outside the call's `reference_shape` mesh (generalized winding
         number |w| <= 0.5) when the call posed the molecule into it (`overlay=True`); None otherwise, and where posing
         failed."""
-        return self._outside
+        return self._measured.atoms_outside
 
     @property
     def chemical_tanimoto(self) -> Optional[float]:
         """Tanimoto of this molecule's chemical fingerprint with the reference graph's (`fingerprint.py`: radius 2, 2 048
         bits, the package's own definition - NOT RDKit's Morgan fingerprint) when the call asked for `chemical_scores` or
         `max_chemical_tanimoto`; None otherwise."""
-        return None if self._chem is None else self._chem[0]
+        return self._measured.chemical_tanimoto
 
     @property
     def graph_key(self) -> Optional[int]:
         """The unsigned 64-bit identity key of the molecular graph (`fingerprint.graph_fingerprints`) when the call asked
         for `chemical_scores` or `unique`; None otherwise.  Isomorphic graphs have equal keys; unequal graphs with equal
         keys are possible (colour refinement's blind spots, hash collisions)."""
-        return None if self._chem is None else self._chem[1]
+        return self._measured.graph_key
 
     @property
     def receptor_contacts(self) -> Optional[Tuple[int, float]]:
         """(receptor_clashes, receptor_max_overlap), or None."""
-        return self._contacts
+        c = self._measured.receptor_clashes
+        return None if c is None else (c, self._measured.receptor_max_overlap)
 
     @property
     def receptor_clashes(self) -> Optional[int]:
         """Heavy atoms overlapping a receptor heavy atom by >= 0.6 A (`receptor.CLASH_OVERLAP`) when the call passed a
         `receptor`; None otherwise, and where posing failed (the molecule is not in the receptor's frame)."""
-        return None if self._contacts is None else self._contacts[0]
+        return self._measured.receptor_clashes
 
     @property
     def receptor_max_overlap(self) -> Optional[float]:
         """The largest overlap (r_i + r_j) - d_ij of a heavy atom with a receptor heavy atom, in A (negative when nothing
         touches), when the call passed a `receptor`; None otherwise, and where posing failed."""
-        return None if self._contacts is None else self._contacts[1]
+        return self._measured.receptor_max_overlap
 
     @property
     def overlay_tanimoto(self) -> Optional[float]:
         """Shape Tanimoto of the pose onto the reference (`overlay=True`: the returned coordinates ARE that pose; NaN
         where posing failed and the generated coordinates were kept); None when the call did not pose."""
-        return None if self._overlay is None else self._overlay[0]
+        return self._measured.overlay_tanimoto
 
     @property
     def pose(self) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
         """(rotation [3,3], translation [3]) with returned = generated @ rotation + translation (rotation proper, det +1)
         when the call posed the molecule (`overlay=True`); None otherwise, and where posing failed."""
-        if self._overlay is None or self._overlay[1] is None:
-            return None
-        p = self._overlay[1]
-        return p[:9].reshape(3, 3), p[9:]
+        p = self._measured.pose
+        return None if p is None else (p[:9].reshape(3, 3), p[9:])
 
     @property
     def shape_tanimoto(self) -> Optional[float]:
         """Gaussian-volume shape Tanimoto of these coordinates against the call's reference - what
         `evaluate_samples(reference, [mol])` reports - when the call scored (`shape_scores`, `top_k`,
         `min_shape_tanimoto`); None otherwise."""
-        return self._score
+        return self._measured.shape_tanimoto
 
     @property
     def sample_id(self) -> Optional[int]:
@@ -337,36 +367,21 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     similarity to the reference and graph identity key (either may be None: not asked for).  `atoms_outside[b]`: row b's
     atoms outside the call's mesh (negative: its pose failed, the record gets None; None: a call without a mesh).
     `strain_before[b]` / `strain_after[b]`: row b's force-field energy before and after the relaxation of a call with
-    `relax_geometry` (both or neither; None: a call that did not relax)."""
+    `relax_geometry` (both or neither; None: a call that did not relax).  The value keywords are the fields of `Measured`
+    and go to `measured_from_tensors`; a call with no ids and no values builds the views and nothing else."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
     view = GeneratedMolecule._view
-    if sample_ids is None and shape_tanimoto is None and overlay_tanimoto is None and chemical_tanimoto is None \
-            and graph_key is None and strain_before is None:
+    values = dict(shape_tanimoto=shape_tanimoto, overlay_tanimoto=overlay_tanimoto, pose=pose,
+                  receptor_clashes=receptor_clashes, receptor_max_overlap=receptor_max_overlap,
+                  atoms_outside=atoms_outside, chemical_tanimoto=chemical_tanimoto, graph_key=graph_key,
+                  strain_before=strain_before, strain_after=strain_after)
+    if sample_ids is None and all(v is None for v in values.values()):
         return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
     flags = valid.cpu().tolist()
     ids = list(range(len(flags))) if sample_ids is None else \
         [int(i) for i in (sample_ids.tolist() if torch.is_tensor(sample_ids) else sample_ids)]
-    scores = [None] * len(flags) if shape_tanimoto is None else [float(v) for v in shape_tanimoto.cpu().tolist()]
-    overlays = [None] * len(flags)
-    if overlay_tanimoto is not None:
-        tan, poses = overlay_tanimoto.cpu().tolist(), pose.cpu().to(torch.float32)
-        ok = torch.isfinite(poses).all(dim=1).tolist()
-        overlays = [(float(t), poses[b] if ok[b] else None) for b, t in enumerate(tan)]
-    contacts = [None] * len(flags)
-    if receptor_clashes is not None:
-        contacts = [None if c < 0 else (int(c), float(w)) for c, w in
-                    zip(receptor_clashes.cpu().tolist(), receptor_max_overlap.cpu().tolist())]
-    chem = [None] * len(flags)
-    if chemical_tanimoto is not None or graph_key is not None:
-        sim = [None] * len(flags) if chemical_tanimoto is None else [float(v) for v in chemical_tanimoto.cpu().tolist()]
-        keys = [None] * len(flags) if graph_key is None else [int(k) & 0xFFFFFFFFFFFFFFFF for k in graph_key.cpu().tolist()]
-        chem = list(zip(sim, keys))
-    outside = [None] * len(flags) if atoms_outside is None else \
-        [None if c < 0 else int(c) for c in atoms_outside.cpu().tolist()]
-    strain = [None] * len(flags) if strain_before is None else \
-        [(float(e0), float(e1)) for e0, e1 in zip(strain_before.cpu().tolist(), strain_after.cpu().tolist())]
-    return [view(batch, b, bool(v), ids[b], scores[b], overlays[b], contacts[b], chem[b], outside[b], strain[b])
-            for b, v in enumerate(flags)]
+    measured = measured_from_tensors(values, len(flags))
+    return [view(batch, b, bool(v), ids[b], measured[b]) for b, v in enumerate(flags)]
 
 
 def assemble_molecules(x: torch.Tensor, elements: torch.Tensor, bond: torch.Tensor, n_nodes: torch.Tensor

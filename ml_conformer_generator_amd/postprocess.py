@@ -12,24 +12,24 @@ Stages, in this order:
   BEHIND the gather, on the rows a rank returns (`return_records` / `return_finished`):
     4. chemical fingerprints, graph keys and the Tanimoto to the reference's graph: one launch over the rows, one for
        the reference (`fingerprints`);
-    5. the values are attached - keyword arguments of `molecules_from_tensors`, or `rdkit_finish.tag_*` on the Mols,
-       which lose their properties in the object gather - and validity is taken (`last_valid_fraction`);
+    5. the values are attached - each molecule's `handoff.Measured`, behind a record's properties or written onto the
+       Mol by `rdkit_finish.tag_measured` (Mols lose their properties in the object gather) - and validity is taken
+       (`last_valid_fraction`);
     6. `select`, written once for both paths: `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`,
        `unique`, then the
        threshold / sphere exclusion / `top_k` walk of `cheminformatics.select_diverse`.  The two pair matrices are
        computed only when their threshold is set, over the rows that survived the filters.
 A call with no option on takes none of these steps: its records / live Mols are returned as they come.
 
-The device work goes through the generator's seams (`_pose_coords`, `_pose_coords_refined`, `_score_coords`,
-`_pair_coords`, `_receptor_coords`, `_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, and with a `reference_shape`
-`_pose_solid`, `_score_solid`, `_pair_solid` in place of the first, third and fourth), looked up on the instance at the
-time of the call."""
+The device work goes through the generator's seams (`_pose`, `_score`, `_pair`, `_receptor_coords`,
+`_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`), looked up on the instance at the time of the call.  The shape
+seams take the request's reference object; which kind it is - a conformer or a solid - is `cheminformatics`' business."""
 from __future__ import annotations
 
 import dataclasses
 import numbers
 import time
-from typing import List, Optional, Union
+from typing import List, NamedTuple, Optional, Union
 
 import torch
 
@@ -38,13 +38,14 @@ from . import fingerprint as mcg_fp
 from . import geometry as mcg_geometry
 from . import host_pool
 from . import receptor as mcg_receptor
-from .handoff import molecules_from_tensors
+from .handoff import Measured, measured_from_tensors, molecules_from_tensors
 
 
 @dataclasses.dataclass(frozen=True)
 class Request:
     """The options of one generation call (`parse_request`); `Request()` is the call that asked for none."""
-    ref_coord: Optional[torch.Tensor] = None      # the reference's heavy-atom coordinates [n,3] fp32, host (shape options)
+    reference: Optional[object] = None            # `cheminformatics.SolidReference` of a `reference_shape` call, else the
+    #                                               `ConformerReference` of a call with a shape option, else None
     overlay: bool = False
     scores_shape: bool = False                    # `shape_scores`, or implied by any of the three selection options
     top_k: Optional[int] = None
@@ -58,7 +59,6 @@ class Request:
     max_chemical_tanimoto: Optional[float] = None
     unique: bool = False
     max_pairwise_chemical_tanimoto: Optional[float] = None
-    ref_solid: Optional[object] = None            # `cheminformatics.SolidReference` of a `reference_shape` call
     max_atoms_outside: Optional[int] = None
     relax_steps: int = 0                          # `relax_geometry`: trial steps of the relaxation, 0 = not relaxed
 
@@ -126,7 +126,7 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
         if not overlay:
             raise ValueError("max_atoms_outside needs overlay=True: molecules that are not posed into the mesh are not "
                              "in its coordinates")
-    solid_kw = dict(ref_solid=solid, max_atoms_outside=max_atoms_outside, relax_steps=relax_steps)
+    common = dict(reference=solid, max_atoms_outside=max_atoms_outside, relax_steps=relax_steps)
     if max_receptor_clashes is not None:
         mcg_receptor.check_max_receptor_clashes(max_receptor_clashes)
         if receptor is None:
@@ -157,15 +157,13 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
         if custom_finisher:
             raise ValueError(f"{what} cannot be combined with a custom finisher: its results carry no coordinates "
                              "this package can read")
-        ref_coord = None
         if solid is None:
-            ref_coord = gen._reference_coord(reference_conformer)
-            cheminformatics.check_reference_atoms(int(ref_coord.shape[0]))
+            common["reference"] = cheminformatics.ConformerReference(gen._reference_coord(reference_conformer))
         rec = None
-        if receptor is not None:
+        if receptor is not None:                  # refused with a mesh above: the reference is a conformer
             rec = mcg_receptor.load_receptor(receptor)
-            mcg_receptor.check_clear_of_reference(rec[0], ref_coord)
-        shape = dict(ref_coord=ref_coord, overlay=bool(overlay), scores_shape=bool(scoring), top_k=top_k,
+            mcg_receptor.check_clear_of_reference(rec[0], common["reference"].coords)
+        shape = dict(overlay=bool(overlay), scores_shape=bool(scoring), top_k=top_k,
                      min_shape_tanimoto=min_shape_tanimoto, max_pairwise_tanimoto=max_pairwise_tanimoto,
                      refine_steps=refine_steps, receptor=rec, max_receptor_clashes=max_receptor_clashes)
 
@@ -179,7 +177,7 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     if reference_graph is not None and not scoring:
         raise ValueError("reference_graph is only read with chemical_scores or max_chemical_tanimoto")
     if not (scoring or unique or max_pairwise_chemical_tanimoto is not None):
-        return Request(**shape, **solid_kw)
+        return Request(**shape, **common)
     if custom_finisher:
         raise ValueError("chemical scores cannot be combined with a custom finisher: its results carry no graph this "
                          "package can read")
@@ -198,7 +196,7 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
                              f"{len(graph[0])}")
     return Request(ref_graph=graph, scores_chemistry=bool(scoring), max_chemical_tanimoto=max_chemical_tanimoto,
                    unique=bool(unique), max_pairwise_chemical_tanimoto=max_pairwise_chemical_tanimoto, **shape,
-                   **solid_kw)
+                   **common)
 
 
 @dataclasses.dataclass
@@ -206,16 +204,12 @@ class Rows:
     """The rows one call may return, as parallel lists: what `select` filters and selects from, on either path."""
     item: List                                    # the `GeneratedMolecule` record or the finished Mol
     sample_id: List[int]
-    shape: List[Optional[float]]                  # shape Tanimoto; None where the call does not score shape
-    contacts: List[Optional[tuple]]               # (receptor_clashes, receptor_max_overlap); None: not measured
-    chem: List[Optional[float]]                   # chemical Tanimoto to the reference's graph
-    key: List[Optional[int]]                      # graph identity key
+    measured: List[Measured]
     row: List[int]                                # index into the device tensors behind the pair matrices
-    outside: Optional[List[Optional[int]]] = None # atoms outside the mesh; None where not measured (the column: no mesh)
 
     def take(self, keep: List[int]) -> "Rows":
         """The rows at the positions `keep`, in that order."""
-        return Rows(*(None if col is None else [col[i] for i in keep] for col in vars(self).values()))
+        return Rows(*([col[i] for i in keep] for col in vars(self).values()))
 
 
 def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
@@ -227,34 +221,27 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
     input's order - then the threshold, the sphere exclusion at `max_pairwise_tanimoto` and at
     `max_pairwise_chemical_tanimoto` in one walk, and `top_k` (`cheminformatics.select_diverse`).  `shape_pair(rows)` /
     `chem_pair(rows)`: the [n,n] pair matrices of the surviving rows, each called only when its threshold is set."""
+    def at_most(field: str, limit: int) -> List[int]:
+        values = [getattr(m, field) for m in rows.measured]
+        return [i for i, v in enumerate(values) if v is not None and v <= limit]
     if req.max_receptor_clashes is not None:
-        rows = rows.take([i for i, c in enumerate(rows.contacts) if c is not None and c[0] <= req.max_receptor_clashes])
+        rows = rows.take(at_most("receptor_clashes", req.max_receptor_clashes))
     if req.max_atoms_outside is not None:
-        counts = rows.outside if rows.outside is not None else [None] * len(rows.item)
-        rows = rows.take([i for i, c in enumerate(counts) if c is not None and c <= req.max_atoms_outside])
+        rows = rows.take(at_most("atoms_outside", req.max_atoms_outside))
     if req.max_chemical_tanimoto is not None:
-        rows = rows.take([i for i, s in enumerate(rows.chem) if s < req.max_chemical_tanimoto])
+        rows = rows.take([i for i, m in enumerate(rows.measured) if m.chemical_tanimoto < req.max_chemical_tanimoto])
     if req.unique:
-        order = sorted(range(len(rows.item)),
-                       key=lambda i: cheminformatics.ranking_key(rows.shape[i], rows.sample_id[i]))
-        rows = rows.take(mcg_fp.select_unique(rows.key, order))
+        order = sorted(range(len(rows.item)), key=lambda i: cheminformatics.ranking_key(rows.measured[i].shape_tanimoto,
+                                                                                       rows.sample_id[i]))
+        rows = rows.take(mcg_fp.select_unique([m.graph_key for m in rows.measured], order))
     if not req.selects_by_shape and req.max_pairwise_chemical_tanimoto is None:
         return rows.item
     keep = cheminformatics.select_diverse(
-        rows.shape, rows.sample_id, shape_pair(rows) if req.max_pairwise_tanimoto is not None else None,
+        [m.shape_tanimoto for m in rows.measured], rows.sample_id,
+        shape_pair(rows) if req.max_pairwise_tanimoto is not None else None,
         req.max_pairwise_tanimoto, req.top_k, req.min_shape_tanimoto,
         chem_pair(rows) if req.max_pairwise_chemical_tanimoto is not None else None, req.max_pairwise_chemical_tanimoto)
     return [rows.item[i] for i in keep]
-
-
-def _pose_fn(gen, req: Request):
-    """The posing seam of the call: `_pose_coords`, `_pose_coords_refined` when it asked for refinement, or `_pose_solid`
-    when its reference is a mesh (the first argument, the reference's coordinates, is then None and not read)."""
-    if req.ref_solid is not None:
-        return lambda ref, coords, n: gen._pose_solid(req.ref_solid, coords, n)
-    if req.refine_steps > 0:
-        return lambda ref, coords, n: gen._pose_coords_refined(ref, coords, n, req.refine_steps)
-    return gen._pose_coords
 
 
 def fingerprints(gen, req: Request, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor):
@@ -268,20 +255,6 @@ def fingerprints(gen, req: Request, atomic_numbers: torch.Tensor, bond_orders: t
     return fp, key, sim
 
 
-def _score_fn(gen, req: Request):
-    """The scoring seam of the call, as f(coords, n_nodes): `_score_coords`, or `_score_solid` when its reference is a mesh."""
-    if req.ref_solid is not None:
-        return lambda coords, n: gen._score_solid(req.ref_solid, coords, n)
-    return lambda coords, n: gen._score_coords(req.ref_coord, coords, n)
-
-
-def _pair_fn(gen, req: Request):
-    """The pair-matrix seam of the call, as f(coords, n_nodes): `_pair_coords`, or `_pair_solid`."""
-    if req.ref_solid is not None:
-        return lambda coords, n: gen._pair_solid(req.ref_solid, coords, n)
-    return lambda coords, n: gen._pair_coords(req.ref_coord, coords, n)
-
-
 def _index(rows: Rows, device) -> torch.Tensor:
     return torch.tensor(rows.row, dtype=torch.long, device=device)
 
@@ -289,17 +262,17 @@ def _index(rows: Rows, device) -> torch.Tensor:
 # ----------------------------------------------------------------------------------------------- without a finisher
 def measure_tensors(gen, req: Request, res: dict) -> dict:
     """Stages 1-3 on one shard's result tensors.  `res` with `x` posed and the per-sample tensors `overlay_tanimoto`,
-    `pose` [B,12] (rotation row-major, then translation; NaN where posing failed), `shape_tanimoto`, `receptor_clashes`
-    (-1 where posing failed), `receptor_max_overlap` (NaN there) and - posed into a mesh - `atoms_outside` (-1 where posing
-    failed) added, as far as the call asked."""
+    `pose`, `shape_tanimoto`, `receptor_clashes` (-1 where posing failed), `receptor_max_overlap` (NaN there) and - posed
+    into a mesh - `atoms_outside` added, as far as the call asked: the spellings `handoff.measured_from_tensors` reads,
+    which cross the tensor gather."""
     if req.overlay:
-        ov = _pose_fn(gen, req)(req.ref_coord, res["x"], res["n_nodes"])
+        ov = gen._pose(req.reference, res["x"], res["n_nodes"], req.refine_steps)
         res = dict(res, x=ov["coords"], overlay_tanimoto=ov["tanimoto"],
                    pose=torch.cat([ov["rotation"].reshape(-1, 9), ov["translation"].reshape(-1, 3)], dim=1))
-        if req.ref_solid is not None:
+        if "atoms_outside" in ov:
             res["atoms_outside"] = ov["atoms_outside"]
     if req.scores_shape:
-        res = dict(res, shape_tanimoto=_score_fn(gen, req)(res["x"], res["n_nodes"]))
+        res = dict(res, shape_tanimoto=gen._score(req.reference, res["x"], res["n_nodes"]))
     if req.receptor is not None:
         clashes, worst = mcg_receptor.clash_summary(
             gen._receptor_coords(req.receptor, res["x"], res["n_nodes"], res["elements"]))
@@ -315,58 +288,57 @@ def return_records(gen, req: Request, res: dict, row_ids: Optional[torch.Tensor]
     `last_host_assembly_ms`) pass the validity proxy, then `select`; the pair matrices are taken from the posed rows and
     from their fingerprints, by the records' batch rows."""
     from .conformer_generator import _finish      # per call: that module imports this one, and tests replace it there
-    chem_kw, fp = {}, None
+    values = {f.name: res.get(f.name) for f in dataclasses.fields(Measured)}
+    fp = None
     if req.needs_fingerprints:
         fp, key, sim = fingerprints(gen, req, res["elements"], res["bond"], res["n_nodes"])
-        chem_kw = dict(chemical_tanimoto=sim, graph_key=key if req.tags_graph_keys else None)
+        values.update(chemical_tanimoto=sim, graph_key=key if req.tags_graph_keys else None)
     if gen.device.type == "cuda":
         torch.cuda.synchronize(gen.device)        # (the D2H copies below would wait anyway: keep that out of the figure)
     t0 = time.perf_counter()
     mols = molecules_from_tensors(res["x"], res["elements"], res["bond"], res["n_nodes"], res["valid"],
-                                  sample_ids=row_ids, shape_tanimoto=res.get("shape_tanimoto"),
-                                  overlay_tanimoto=res.get("overlay_tanimoto"), pose=res.get("pose"),
-                                  receptor_clashes=res.get("receptor_clashes"),
-                                  receptor_max_overlap=res.get("receptor_max_overlap"),
-                                  atoms_outside=res.get("atoms_outside"), strain_before=res.get("strain_before"),
-                                  strain_after=res.get("strain_after"), **chem_kw)
+                                  sample_ids=row_ids, **values)
     gen.last_host_assembly_ms = (time.perf_counter() - t0) * 1e3      # D2H of the result tensors + record views
     kept, gen.last_valid_fraction = _finish(mols, optimise_geometry, use_rdkit=False)    # no finisher: the proxy
     if not req.removes:
         return kept
-    rows = Rows(kept, [m.sample_id for m in kept], [m.shape_tanimoto for m in kept],
-                [m.receptor_contacts for m in kept], [m.chemical_tanimoto for m in kept], [m.graph_key for m in kept],
-                [m.batch_row for m in kept], [m.atoms_outside for m in kept])
+    rows = Rows(kept, [m.sample_id for m in kept], [m._measured for m in kept], [m.batch_row for m in kept])
 
     def shape_pair(left: Rows):
         x = res["x"]
         idx = _index(left, x.device)
-        return _pair_fn(gen, req)(x.index_select(0, idx), res["n_nodes"].reshape(-1).to(x.device).index_select(0, idx))
+        return gen._pair(req.reference, x.index_select(0, idx),
+                         res["n_nodes"].reshape(-1).to(x.device).index_select(0, idx))
     return select(rows, req, shape_pair, lambda left: gen._chem_pair(fp.index_select(0, _index(left, fp.device))))
 
 
 # ----------------------------------------------------------------------------------------------- through a finisher
+class Finished(NamedTuple):
+    """One sample of a shard behind its finisher: the one value per sample that crosses the object gather."""
+    mol: object                                   # the finished Mol; None = dropped
+    measured: Measured
+
+
 def _heavy_coords(mols: List):
     """(padded [B, max n, 3], n_nodes [B]) of Mols' heavy-atom conformer positions."""
     return cheminformatics.padded_coords([cheminformatics.mol_heavy_coords(m) for m in mols])
 
 
-def score_mols(gen, ref_coord: torch.Tensor, mols: List, score_fn=None) -> List[Optional[float]]:
-    """Shape Tanimoto of finished Mols' heavy-atom conformer positions (None where a molecule was dropped), in ONE
-    batched device call.  `score_fn(coords, n_nodes)`: what scores them (default: `_score_coords` against `ref_coord`)."""
-    if score_fn is None:
-        score_fn = lambda coords, n: gen._score_coords(ref_coord, coords, n)      # noqa: E731
+def score_mols(gen, reference, mols: List) -> List[Optional[float]]:
+    """Shape Tanimoto of finished Mols' heavy-atom conformer positions against `reference` (None where a molecule was
+    dropped), in ONE batched device call (`_score`)."""
     live = [k for k, m in enumerate(mols) if m is not None]
     out: List[Optional[float]] = [None] * len(mols)
     if live:
-        for k, v in zip(live, score_fn(*_heavy_coords([mols[k] for k in live])).cpu().tolist()):
+        for k, v in zip(live, gen._score(reference, *_heavy_coords([mols[k] for k in live])).cpu().tolist()):
             out[k] = float(v)
     return out
 
 
-def _contact_mols(gen, rec: tuple, mols: List, poses: List) -> List[Optional[tuple]]:
+def _contact_mols(gen, rec: tuple, mols: List, posed: List[bool]) -> List[Optional[tuple]]:
     """(receptor_clashes, receptor_max_overlap) of posed Mols' heavy atoms (elements from `GetAtomicNum()`), in ONE
     batched device call; None where a Mol was dropped or its pose failed (it is not in the receptor's frame)."""
-    live = [k for k, m in enumerate(mols) if m is not None and poses[k] is not None and poses[k][1] is not None]
+    live = [k for k, m in enumerate(mols) if m is not None and posed[k]]
     out: List[Optional[tuple]] = [None] * len(mols)
     if live:
         coords, n = _heavy_coords([mols[k] for k in live])
@@ -380,76 +352,72 @@ def _contact_mols(gen, rec: tuple, mols: List, poses: List) -> List[Optional[tup
     return out
 
 
-def measure_finished(gen, req: Request, done: List, res: Optional[dict] = None) -> List[tuple]:
+def measure_finished(gen, req: Request, done: List, res: Optional[dict] = None) -> List[Finished]:
     """Stages 1-3 on one shard's finished Mols (None = dropped), each in ONE batched device call: pose, every conformer
     position moved (`cheminformatics.pose_mols`), then score (`score_mols`), then the receptor contacts of the posed
-    Mols.  Per sample (Mol, shape Tanimoto, (overlay_tanimoto, rotation, translation), (receptor_clashes,
-    receptor_max_overlap), atoms outside the mesh), None where the call did not ask, the Mol was dropped or - the last
-    two - its pose failed: the one value per sample that crosses the object gather.  `res`: the shard's result tensors;
-    where the call relaxed (`strain_before` / `strain_after` in it) a sixth value follows, that pair as floats."""
-    none = [None] * len(done)
-    extra = ()
-    if res is not None and "strain_before" in res:
-        extra = (list(zip(res["strain_before"].cpu().tolist(), res["strain_after"].cpu().tolist())),)
-    pose_fn, counts = _pose_fn(gen, req), []
-    if req.overlay and req.ref_solid is not None:
-        def pose_fn(ref, coords, n, _solid=pose_fn):        # the one batched call of `pose_mols`: keep its counts
-            ov = _solid(ref, coords, n)
-            counts.extend(ov["atoms_outside"].cpu().tolist())
+    Mols.  Per sample the Mol with its `Measured`: None where the call did not ask, the Mol was dropped or - contacts and
+    atoms outside the mesh - its pose failed.  `res`: the shard's result tensors; where the call relaxed, its
+    `strain_before` / `strain_after` join every sample's values."""
+    measured = [Measured() for _ in done]
+    live = [k for k, m in enumerate(done) if m is not None]
+    if req.overlay:
+        ov = {}                                   # the result of the one batched call `pose_mols` makes, if it makes one
+
+        def pose(ref, coords, n):
+            ov.update(gen._pose(ref, coords, n, req.refine_steps))
             return ov
-    poses = cheminformatics.pose_mols(req.ref_coord, done, overlay_fn=pose_fn) if req.overlay else none
-    outside = list(none)
-    for c, k in zip(counts, [k for k, m in enumerate(done) if m is not None]):
-        outside[k] = None if c < 0 else int(c)
-    scores = score_mols(gen, req.ref_coord, done, _score_fn(gen, req)) if req.scores_shape else none
-    contacts = _contact_mols(gen, req.receptor, done, poses) if req.receptor is not None else none
-    return list(zip(done, scores, poses, contacts, outside, *extra))
+        for m, p in zip(measured, cheminformatics.pose_mols(req.reference, done, overlay_fn=pose)):
+            if p is not None:                     # (score, rotation, translation), host; no pose where posing failed
+                m.overlay_tanimoto = p[0]
+                m.pose = None if p[1] is None else torch.cat([p[1].reshape(9), p[2]])     # owns its 12 values
+        if "atoms_outside" in ov:
+            counts = measured_from_tensors(dict(atoms_outside=ov["atoms_outside"]), len(live))
+            for k, c in zip(live, counts):
+                measured[k].atoms_outside = c.atoms_outside
+    if req.scores_shape:
+        for m, score in zip(measured, score_mols(gen, req.reference, done)):
+            m.shape_tanimoto = score
+    if req.receptor is not None:
+        contacts = _contact_mols(gen, req.receptor, done, [m.pose is not None for m in measured])
+        for m, c in zip(measured, contacts):
+            m.receptor_clashes, m.receptor_max_overlap = c if c is not None else (None, None)
+    if res is not None and "strain_before" in res:
+        for m, e0, e1 in zip(measured, res["strain_before"].cpu().tolist(), res["strain_after"].cpu().tolist()):
+            m.strain_before, m.strain_after = e0, e1
+    return [Finished(mol, m) for mol, m in zip(done, measured)]
 
 
-def return_finished(gen, req: Request, samples: List[tuple], row_ids: Optional[torch.Tensor],
+def return_finished(gen, req: Request, samples: List[Finished], row_ids: Optional[torch.Tensor],
                     sample_seed: Optional[int]) -> List:
     """What a call returns through a finisher, from the (gathered) `measure_finished` values of the rows this rank returns
-    (sample ids `row_ids`, default 0..B-1): stages 4-6.  The Mols get their properties here, behind the object gather,
-    which does not carry them - `sample_id` (seeded calls), `overlay_tanimoto`, `shape_tanimoto`, `receptor_clashes`,
-    `receptor_max_overlap`, `atoms_outside`, `strain_before` / `strain_after` (a call that relaxed), and from the chemical
-    step, which reads the live Mols' own graphs
-    (`fingerprint.mol_graph`) in one batched device call, the double property `chemical_tanimoto` and the string property
-    `graph_key` (the unsigned 64-bit key in decimal: it does not fit an int property).  Then `select`, the shape pair
-    matrix taken from the surviving Mols' posed heavy atoms."""
+    (sample ids `row_ids`, default 0..B-1): stages 4-6.  The chemical step reads the live Mols' own graphs
+    (`fingerprint.mol_graph`) in one batched device call.  The Mols get their properties here, behind the object gather,
+    which does not carry them: `sample_id` (seeded calls) and what `rdkit_finish.tag_measured` writes.  Then `select`, the
+    shape pair matrix taken from the surviving Mols' posed heavy atoms."""
     from . import rdkit_finish
-    mols = [s[0] for s in samples]
+    mols = [s.mol for s in samples]
     ids = list(range(len(mols))) if row_ids is None else row_ids.tolist()
     if sample_seed is not None:
         rdkit_finish.tag_sample_ids(mols, ids)
     gen.last_host_assembly_ms = 0.0
     live = [i for i, m in enumerate(mols) if m is not None]
     gen.last_valid_fraction = len(live) / len(mols) if mols else 0.0
-    if req.relax_steps:
-        strain = [samples[i][5] if len(samples[i]) > 5 else None for i in live]
-        rdkit_finish.tag_scores([mols[i] for i in live], "strain_before", [None if s is None else s[0] for s in strain])
-        rdkit_finish.tag_scores([mols[i] for i in live], "strain_after", [None if s is None else s[1] for s in strain])
-    if not req.measures:
+    if not req.measures and not req.relax_steps:  # nothing was measured: nothing to tag or select by
         return [mols[i] for i in live]
-    rows = Rows([mols[i] for i in live], [ids[i] for i in live], [samples[i][1] for i in live],
-                [samples[i][3] for i in live], [None] * len(live), [None] * len(live), list(range(len(live))),
-                [samples[i][4] if len(samples[i]) > 4 else None for i in live])
-    overlays = [None if samples[i][2] is None else samples[i][2][0] for i in live]
-    rdkit_finish.tag_scores(rows.item, "overlay_tanimoto", overlays)
-    rdkit_finish.tag_scores(rows.item, "shape_tanimoto", rows.shape)
-    rdkit_finish.tag_contacts(rows.item, rows.contacts)
-    rdkit_finish.tag_atoms_outside(rows.item, rows.outside)
+    rows = Rows([mols[i] for i in live], [ids[i] for i in live], [samples[i].measured for i in live],
+                list(range(len(live))))
     fp = None
     if req.needs_fingerprints and live:
         fp, key, sim = fingerprints(gen, req, *mcg_fp.pad_graphs([mcg_fp.mol_graph(m) for m in rows.item]))
-        rows.key = [int(k) & 0xFFFFFFFFFFFFFFFF for k in key.cpu().tolist()]
-        if req.scores_chemistry:
-            rows.chem = [float(v) for v in sim.cpu().tolist()]
-            rdkit_finish.tag_scores(rows.item, "chemical_tanimoto", rows.chem)
-        if req.tags_graph_keys:
-            rdkit_finish.tag_graph_keys(rows.item, rows.key)
+        chem = measured_from_tensors(dict(chemical_tanimoto=sim, graph_key=key if req.tags_graph_keys else None), len(live))
+        for m, c in zip(rows.measured, chem):
+            m.chemical_tanimoto, m.graph_key = c.chemical_tanimoto, c.graph_key
+    rdkit_finish.tag_measured(rows.item, rows.measured)
+    if not req.measures:
+        return rows.item
 
     def chem_pair(left: Rows):
         if fp is None:                            # nothing left to compare
             return torch.zeros(0, 0)
         return gen._chem_pair(fp.index_select(0, _index(left, fp.device)))
-    return select(rows, req, lambda left: _pair_fn(gen, req)(*_heavy_coords(left.item)), chem_pair)
+    return select(rows, req, lambda left: gen._pair(req.reference, *_heavy_coords(left.item)), chem_pair)

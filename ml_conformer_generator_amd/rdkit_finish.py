@@ -147,35 +147,22 @@ def tag_sample_ids(mols: Sequence, sample_ids: Sequence[int]) -> None:
             m.SetIntProp("sample_id", int(sid))
 
 
-def tag_contacts(mols: Sequence, contacts: Sequence[Optional[tuple]]) -> None:
-    """Set the int property `receptor_clashes` and the double property `receptor_max_overlap` on every Mol of `mols`
-    (None = dropped) from `contacts[k]` = (clashes, max overlap), None = not measured.  Set after the object gather."""
-    for m, c in zip(mols, contacts):
-        if m is not None and c is not None and hasattr(m, "SetIntProp"):
-            m.SetIntProp("receptor_clashes", int(c[0]))
-            m.SetDoubleProp("receptor_max_overlap", float(c[1]))
+# `handoff.Measured` field -> kind of the Mol property of the same name (`pose` has none).  "string": the unsigned 64-bit
+# `graph_key` in decimal - it does not fit RDKit's int property
+MEASURED_PROPS = dict(shape_tanimoto="double", overlay_tanimoto="double", receptor_clashes="int",
+                      receptor_max_overlap="double", atoms_outside="int", chemical_tanimoto="double", graph_key="string",
+                      strain_before="double", strain_after="double")
+_SETTERS = {"int": ("SetIntProp", int), "double": ("SetDoubleProp", float), "string": ("SetProp", lambda k: str(int(k)))}
 
 
-def tag_atoms_outside(mols: Sequence, counts: Sequence[Optional[int]]) -> None:
-    """Set the int property `atoms_outside` (heavy atoms of the pose outside the call's `reference_shape` mesh) on every Mol
-    of `mols` (None = dropped); `counts[k]` belongs to `mols[k]`, None = not measured.  Set after the object gather."""
-    for m, c in zip(mols, counts):
-        if m is not None and c is not None and hasattr(m, "SetIntProp"):
-            m.SetIntProp("atoms_outside", int(c))
-
-
-def tag_graph_keys(mols: Sequence, keys: Sequence[Optional[int]]) -> None:
-    """Set the string property `graph_key` - the unsigned 64-bit graph identity key in decimal; it does not fit RDKit's
-    int property - on every Mol of `mols` (None = dropped); `keys[k]` belongs to `mols[k]`, None = no key."""
-    for m, k in zip(mols, keys):
-        if m is not None and k is not None and hasattr(m, "SetProp"):
-            m.SetProp("graph_key", str(int(k)))
-
-
-def tag_scores(mols: Sequence, prop: str, scores: Sequence[Optional[float]]) -> None:
-    """Set the double property `prop` (`shape_tanimoto`, `overlay_tanimoto`) on every Mol of `mols` (None = dropped);
-    `scores[k]` belongs to `mols[k]`, None = no score.  Set after the object gather: RDKit does not pickle Mol properties
-    by default."""
-    for m, sc in zip(mols, scores):
-        if m is not None and sc is not None and hasattr(m, "SetDoubleProp"):
-            m.SetDoubleProp(prop, float(sc))
+def tag_measured(mols: Sequence, measured: Sequence) -> None:
+    """Set the properties of `MEASURED_PROPS` on every Mol of `mols` (None = dropped) from `measured[k]`, its
+    `handoff.Measured`; a value of None sets no property.  Set after the object gather: RDKit does not pickle Mol
+    properties by default.  What a custom finisher returns is tagged only as far as it has the setter."""
+    for m, rec in zip(mols, measured):
+        if m is None:
+            continue
+        for prop, kind in MEASURED_PROPS.items():
+            value, (setter, cast) = getattr(rec, prop), _SETTERS[kind]
+            if value is not None and hasattr(m, setter):
+                getattr(m, setter)(prop, cast(value))

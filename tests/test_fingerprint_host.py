@@ -202,7 +202,7 @@ def test_chemical_refusals_happen_before_any_device_work(entry, monkeypatch):
     from ml_conformer_generator_amd import host_pool as HP
     gen = _shell_generator()
     monkeypatch.setattr(gen, "_generate_shard", _no_device)
-    gen._graph_fingerprints = gen._chem_tanimoto = gen._chem_pair = gen._score_coords = _no_device
+    gen._graph_fingerprints = gen._chem_tanimoto = gen._chem_pair = gen._score = _no_device
     call = getattr(gen, entry)
     graph = C.PINNED["benzene"][0][:2]
     nan = float("nan")
@@ -345,7 +345,7 @@ def test_proxy_path_records_carry_scores_and_keys_and_pass_the_filters():
     fp_calls, pair_calls = [], []
     gen = _with_seams(_shell_generator(), fp_calls, pair_calls)
     gen._generate_shard = _graph_shard(mols)
-    gen._score_coords = lambda ref, coords, n: coords[:, 0, 1].clone()
+    gen._score = lambda ref, coords, n: coords[:, 0, 1].clone()
     kw = dict(reference_conformer=_ref(), n_samples=8)
     ben = _as_mol(C.PINNED["benzene"][0], hydrogens=2)
 

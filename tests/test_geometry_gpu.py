@@ -254,8 +254,8 @@ def test_generator_scores_the_relaxed_coordinates_and_the_sharded_entry_relaxes_
     kw = dict(reference_conformer=ref, n_samples=6, variance=2, optimise_geometry=False, sample_seed=SEED)
     scored = gen.generate_conformers(relax_geometry=True, shape_scores=True, **kw)
     lb = gen.last_batch
-    want = gen._score_coords(ref, lb["x_relaxed"], lb["n_nodes"]).cpu()
-    raw = gen._score_coords(ref, lb["x_ordered"], lb["n_nodes"]).cpu()
+    want = gen._score(ref, lb["x_relaxed"], lb["n_nodes"]).cpu()
+    raw = gen._score(ref, lb["x_ordered"], lb["n_nodes"]).cpu()
     assert [m.shape_tanimoto for m in scored] == [float(v) for v in want]
     assert not torch.equal(want, raw)
     # one pass through the sharded entry (no process group: one rank, the same code up to the collectives)

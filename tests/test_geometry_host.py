@@ -234,8 +234,10 @@ def test_finished_samples_carry_the_strain_across_the_gather():
     req = postprocess.Request(relax_steps=5)
     res = dict(strain_before=torch.tensor([2.0, 4.0]), strain_after=torch.tensor([1.0, 0.5]))
     out = postprocess.measure_finished(gen, req, ["a", None], res)
-    assert [s[5] for s in out] == [(2.0, 1.0), (4.0, 0.5)] and out[1][0] is None
-    assert all(len(s) == 5 for s in postprocess.measure_finished(gen, postprocess.Request(), ["a", None]))
+    assert [(s.measured.strain_before, s.measured.strain_after) for s in out] == [(2.0, 1.0), (4.0, 0.5)]
+    assert out[1].mol is None
+    assert all(s.measured.strain_before is None and s.measured.strain_after is None
+               for s in postprocess.measure_finished(gen, postprocess.Request(), ["a", None]))
 
 
 # ----------------------------------------------------------------------------------------------- python checks
@@ -330,7 +332,7 @@ def test_every_element_the_generator_can_emit_has_a_radius_on_the_device():
 
 
 class _StubMol:
-    """What `rdkit_finish.tag_*` needs of a Mol."""
+    """What `rdkit_finish.tag_measured` needs of a Mol."""
 
     def __init__(self):
         self.props = {}

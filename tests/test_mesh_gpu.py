@@ -143,7 +143,9 @@ def test_overlay_field_equals_overlay_bit_for_bit():
     coords[3, 2, 0] = float("nan")                                        # a failing row
     want = CH.shape_overlay(ref, coords, n, DEV, with_scores=True)
     # the same launch again, by hand, to get at its density and the reference's transform
-    dev, ref_h, x, nn = CH._shape_inputs(ref, coords, n, DEV, with_reference=True)
+    conformer = CH.ConformerReference(ref)
+    x, nn = conformer.rows(coords.to(DEV), n.to(DEV, torch.int32), DEV)
+    dev = DEV
     xform = torch.empty(x.shape[0], 12, device=dev)
     _, frames = CH.shape_frames_hip(x, nn, dev, centre_atoms=True, xform_out=xform)
     ref_frame = frames[0, :17].contiguous()
@@ -155,7 +157,18 @@ def test_overlay_field_equals_overlay_bit_for_bit():
                                              64, _lib.dptr(rots), 4, _lib.dptr(axes), 40, float(CH.ALPHA),
                                              float(CH.AMPLITUDE), _lib.dptr(f), _lib.dptr(score),
                                              _lib.current_stream_ptr(dev)), "mcg_shape_tanimoto")
-    got = CH._overlay_field(f, xform[0].contiguous(), axes, x[1:].contiguous(), nn[1:].contiguous(), dev, True)
+
+    class Field(CH.SolidReference):
+        """That density, transform and grid as the device side of a solid that has no mesh to count atoms against."""
+        pose_keys = ()
+
+        def __init__(self):
+            self.n, self._on = 40, {dev: dict(f=f, xform=xform[0].contiguous(), axes=axes)}
+
+        def pose_extras(self, out, nn, dev):
+            return {}
+    got = CH.shape_overlay(Field(), coords, n, DEV, with_scores=True)
+    assert list(got) == list(want)
     assert int(got["orientation"][3]) == -1 and int((got["orientation"] >= 0).sum()) == len(mols) - 1
     for key in ("coords", "rotation", "translation", "tanimoto", "scores"):
         assert torch.equal(_bits(got[key]), _bits(want[key])), key
@@ -200,6 +213,22 @@ def test_overlay_onto_a_box(width):
         lo, hi = torch.tensor([3.0, -2.0, 7.0]) + 1.0, torch.tensor([7.0, 4.0, 17.0]) - 1.0
         assert bool(((posed > lo) & (posed < hi)).all())
     print(f"MESH box overlay width {width}: tanimoto {res['tanimoto'].tolist()}")
+    # an empty batch: the keys, dtypes and trailing shapes of a one-molecule call, whatever the kind of reference
+    def layout(out):
+        out = dict(enumerate(out)) if isinstance(out, tuple) else out if isinstance(out, dict) else {0: out}
+        return {k: (t.dtype, t.device, tuple(t.shape[1:])) for k, t in out.items()}
+    for reference in (solid, lat.to(torch.float32)):
+        calls = [lambda x, m: CH.shape_scores(reference, x, m, DEV), lambda x, m: CH.shape_overlay(reference, x, m, DEV),
+                 lambda x, m: CH.shape_overlay(reference, x, m, DEV, with_scores=True)]
+        if reference is not solid:
+            calls += [lambda x, m: CH.shape_overlay(reference, x, m, DEV, refine_steps=8),
+                      lambda x, m: CH.shape_overlay(reference, x, m, DEV, with_scores=True, refine_steps=8)]
+        for call in calls:
+            one, none = call(coords[:1], n[:1]), call(coords[:0], n[:0])
+            assert layout(none) == layout(one) and list(layout(none)) == list(layout(one))
+            assert all(t.shape[0] == 0 for t in (none.values() if isinstance(none, dict) else none))
+        pair = CH.pairwise_shape_tanimoto(reference, coords[:0], n[:0], DEV)
+        assert pair.shape == (0, 0) and pair.dtype == CH.pairwise_shape_tanimoto(reference, coords[:1], n[:1], DEV).dtype
 
 
 def test_atoms_outside_matches_the_restatement():

@@ -10,6 +10,7 @@ import torch
 
 import mesh_cases as C
 import mesh_ref as R
+from ml_conformer_generator_amd import cheminformatics as CH
 from ml_conformer_generator_amd import mesh as M
 from ml_conformer_generator_amd import postprocess
 from test_shape_overlay_host import _no_device, _ref, _shell_generator, _stub_overlay, _stub_shard
@@ -177,8 +178,7 @@ def test_meshes_that_are_not_watertight_are_refused():
 # ----------------------------------------------------------------------------------------------- requests
 def _pocket_gen():
     gen = _shell_generator()
-    gen._generate_shard = gen._score_coords = gen._pose_coords = gen._pair_coords = _no_device
-    gen._pose_solid = gen._score_solid = gen._pair_solid = _no_device
+    gen._generate_shard = gen._score = gen._pose = gen._pair = _no_device
     return gen
 
 
@@ -225,17 +225,17 @@ def test_a_plain_reference_shape_request_asks_for_nothing():
     import dataclasses
     gen = _pocket_gen()
     req = postprocess.parse_request(gen, None, reference_shape=C.pocket())
-    assert req.ref_solid is not None and req.ref_solid.mesh is C.pocket()
+    assert isinstance(req.reference, CH.SolidReference) and req.reference.mesh is C.pocket()
     assert not req.measures and not req.removes and not req.selects_by_shape
-    assert dataclasses.replace(req, ref_solid=None) == postprocess.Request()
+    assert dataclasses.replace(req, reference=None) == postprocess.Request()
     assert postprocess.parse_request(gen, _ref()) == postprocess.Request()              # and without one: as before
     full = postprocess.parse_request(gen, None, True, 3, 0.1, True, 0.9, reference_shape=C.pocket(), max_atoms_outside=2)
-    assert full.ref_coord is None and full.overlay and full.scores_shape and full.removes and full.max_atoms_outside == 2
+    assert isinstance(full.reference, CH.SolidReference) and full.reference.mesh is C.pocket()
+    assert full.overlay and full.scores_shape and full.removes and full.max_atoms_outside == 2
     assert (full.top_k, full.min_shape_tanimoto, full.max_pairwise_tanimoto) == (3, 0.1, 0.9)
 
 
 def test_solid_reference_host_side():
-    from ml_conformer_generator_amd import cheminformatics as CH
     v, f = C.box(4.0, 6.0, 10.0, origin=(3.0, -2.0, 7.0))
     solid = CH.solid_reference((v, f), n=12)
     assert CH.solid_reference(solid) is solid and solid.n == 12
@@ -252,10 +252,10 @@ def test_solid_reference_host_side():
 
 # ----------------------------------------------------------------------------------------------- seams
 def _solid_pose_stub(calls):
-    """A device-free `_pose_solid`: the overlay stub, with atoms_outside = 10 x the row's first coordinate (-1: failed)."""
+    """A device-free `_pose` for a solid: the overlay stub, with atoms_outside = 10 x the row's first coordinate (-1: failed)."""
     stub = _stub_overlay(lambda k: k + 1.0)
 
-    def run(solid, coords, n):
+    def run(solid, coords, n, refine_steps=0):
         calls.append(("pose", solid))
         out = stub(None, coords, n)
         key = coords[:, 0, 0]
@@ -267,16 +267,16 @@ def _solid_pose_stub(calls):
 def test_proxy_path_takes_the_solid_seams_and_filters_on_atoms_outside():
     gen = _shell_generator()
     gen._generate_shard = _stub_shard()
-    gen._pose_coords = gen._score_coords = gen._pair_coords = _no_device
     calls = []
-    gen._pose_solid = _solid_pose_stub(calls)
-    gen._score_solid = lambda solid, coords, n: (calls.append(("score", solid)), coords[:, 1, 0].clone())[1]
-    gen._pair_solid = lambda solid, coords, n: (calls.append(("pair", solid)), torch.zeros(len(coords), len(coords)))[1]
+    gen._pose = _solid_pose_stub(calls)
+    gen._score = lambda solid, coords, n: (calls.append(("score", solid)), coords[:, 1, 0].clone())[1]
+    gen._pair = lambda solid, coords, n: (calls.append(("pair", solid)), torch.zeros(len(coords), len(coords)))[1]
     kw = dict(reference_shape=C.pocket(), n_atoms=20, n_samples=8)
     plain = gen.generate_conformers(**kw)
     assert calls == [] and all(m.atoms_outside is None and m.pose is None for m in plain)
     posed = gen.generate_conformers(overlay=True, shape_scores=True, **kw)
-    assert [c[0] for c in calls] == ["pose", "score"] and all(c[1].mesh is C.pocket() for c in calls)
+    assert [c[0] for c in calls] == ["pose", "score"]
+    assert all(isinstance(c[1], CH.SolidReference) and c[1].mesh is C.pocket() for c in calls)
     assert [m.sample_id for m in posed] == [0, 1, 2, 4, 5, 6, 7]                   # sample 3 is invalid
     want = {0: 0, 1: 7, 2: 4, 4: 8, 5: None, 6: 2, 7: 9}                             # x00 = (7 i % 10) / 10; 5 failed
     assert {m.sample_id: m.atoms_outside for m in posed} == want
@@ -287,22 +287,23 @@ def test_proxy_path_takes_the_solid_seams_and_filters_on_atoms_outside():
     calls.clear()
     diverse = gen.generate_conformers_sharded(overlay=True, max_pairwise_tanimoto=0.5, max_atoms_outside=8, **kw)
     assert [c[0] for c in calls] == ["pose", "score", "pair"]
+    assert all(isinstance(c[1], CH.SolidReference) and c[1].mesh is C.pocket() for c in calls)
     assert sorted(m.sample_id for m in diverse) == [0, 1, 2, 4, 6]
 
 
 def test_object_path_carries_atoms_outside_to_the_mols():
     from test_shape_overlay_host import PosedMol
     gen = _shell_generator(finisher="rdkit")
-    gen._pose_coords = gen._score_coords = _no_device
     calls = []
-    gen._pose_solid = _solid_pose_stub(calls)
-    gen._score_solid = lambda solid, coords, n: torch.full((coords.shape[0],), 0.25)
+    gen._pose = _solid_pose_stub(calls)
+    gen._score = lambda solid, coords, n: torch.full((coords.shape[0],), 0.25)
     req = postprocess.parse_request(gen, None, True, overlay=True, reference_shape=C.pocket(), max_atoms_outside=3)
     done = [PosedMol([[0.3, 0, 0]] * 4 + [[0, 0, 1.0]], z=[6] * 4 + [1]), None,
             PosedMol([[0.7, 0, 0]] * 5, z=[6] * 5), PosedMol([[float("nan"), 0, 0]] * 5, z=[6] * 5)]
     samples = postprocess.measure_finished(gen, req, done)
-    assert [s[4] for s in samples] == [3, None, 7, None] and len(calls) == 1
-    assert [s[1] for s in samples] == [0.25, None, 0.25, 0.25]
+    assert [s.measured.atoms_outside for s in samples] == [3, None, 7, None] and len(calls) == 1
+    assert calls[0][1].mesh is C.pocket()
+    assert [s.measured.shape_tanimoto for s in samples] == [0.25, None, 0.25, 0.25]
     kept = postprocess.return_finished(gen, req, samples, None, 1)
     assert kept == [done[0]] and done[0].props["atoms_outside"] == 3 and done[2].props["atoms_outside"] == 7
     assert "atoms_outside" not in done[3].props

@@ -167,8 +167,8 @@ def _pocket(n=40):
 @pytest.mark.parametrize("entry", ["generate_conformers", "generate_conformers_sharded", "forward"])
 def test_receptor_refusals_happen_before_any_device_work(entry):
     gen = _shell_generator()
-    gen._generate_shard = gen._score_coords = gen._pose_coords = _no_device
-    gen._pair_coords = gen._receptor_coords = _no_device
+    gen._generate_shard = gen._score = gen._pose = _no_device
+    gen._pair = gen._receptor_coords = _no_device
     call = getattr(gen, entry)
     pocket = _pocket()
     holding = (torch.cat([pocket[0], _ref()[3:4] + 0.2]), torch.cat([pocket[1], torch.tensor([8])]))   # the ligand's atom
@@ -213,8 +213,8 @@ def _stub_contacts(calls):
 def _proxy_gen(calls):
     gen = _shell_generator()
     gen._generate_shard = _stub_shard()
-    gen._pose_coords = _stub_overlay(lambda k: k + 1.0)        # (x, 0, 0) @ rot_z(90) -> (0, x, 0): coords[0, 1] = x00
-    gen._score_coords = lambda ref, coords, n: coords[:, 1, 0].clone()
+    gen._pose = _stub_overlay(lambda k: k + 1.0)        # (x, 0, 0) @ rot_z(90) -> (0, x, 0): coords[0, 1] = x00
+    gen._score = lambda ref, coords, n: coords[:, 1, 0].clone()
     gen._receptor_coords = _stub_contacts(calls)
     return gen
 
@@ -259,7 +259,7 @@ def test_proxy_path_filters_before_the_selection():
     def pair(ref, coords, n):
         pair_calls.append(int(coords.shape[0]))
         return torch.zeros(coords.shape[0], coords.shape[0])
-    gen._pair_coords = pair
+    gen._pair = pair
     got = gen.generate_conformers(max_receptor_clashes=4, max_pairwise_tanimoto=0.5, **kw)
     assert pair_calls == [3] and sorted(m.sample_id for m in got) == [0, 2, 6]   # the pair matrix of the survivors
     sharded = gen.generate_conformers_sharded(max_receptor_clashes=4, **kw)      # no process group: one rank
@@ -286,8 +286,8 @@ class _StageGen:
 def _object_gen(calls):
     gen = _shell_generator(finisher="rdkit")
     gen._generate_shard = _StageGen(gen)
-    gen._pose_coords = _stub_overlay(lambda k: k * 0 + 0.5)
-    gen._score_coords = lambda ref, coords, n: 1.0 - coords[:, 0, 1].clone()      # lower sample id: higher score
+    gen._pose = _stub_overlay(lambda k: k * 0 + 0.5)
+    gen._score = lambda ref, coords, n: 1.0 - coords[:, 0, 1].clone()      # lower sample id: higher score
     gen._receptor_coords = _stub_contacts(calls)
     return gen
 

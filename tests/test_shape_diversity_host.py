@@ -70,8 +70,8 @@ def test_select_diverse_edge_cases():
 def test_diversity_refusals_happen_before_any_device_work(entry):
     from ml_conformer_generator_amd import host_pool as HP
     gen = _shell_generator()
-    gen._generate_shard = gen._score_coords = gen._pose_coords = _no_device
-    gen._pair_coords = _no_device
+    gen._generate_shard = gen._score = gen._pose = _no_device
+    gen._pair = _no_device
     call = getattr(gen, entry)
     ctx = torch.tensor([50.0, 100.0, 130.0])
     for kw in (dict(reference_conformer=_ref(), max_pairwise_tanimoto=0.5),               # not posed: no common frame
@@ -140,10 +140,10 @@ def _stub_pair(calls):
 def test_proxy_path_selects_through_the_pair_function():
     gen = _shell_generator()
     gen._generate_shard = _stub_shard()
-    gen._pose_coords = _stub_overlay(lambda k: k + 1.0)        # (x, 0, 0) @ rot_z(90) -> (0, x, 0): coords[0, 1] = x
-    gen._score_coords = lambda ref, coords, n: coords[:, 1, 0].clone()
+    gen._pose = _stub_overlay(lambda k: k + 1.0)        # (x, 0, 0) @ rot_z(90) -> (0, x, 0): coords[0, 1] = x
+    gen._score = lambda ref, coords, n: coords[:, 1, 0].clone()
     calls = []
-    gen._pair_coords = _stub_pair(calls)
+    gen._pair = _stub_pair(calls)
     base = gen.generate_conformers(reference_conformer=_ref(), n_samples=8, overlay=True, shape_scores=True)
     scores, ids = [m.shape_tanimoto for m in base], [m.sample_id for m in base]
     pair = _stub_pair([])(None, torch.stack([m.coords for m in base]), None)
@@ -177,9 +177,9 @@ class _StageGen:
 def _object_gen(calls):
     gen = _shell_generator(finisher="rdkit")
     gen._generate_shard = _StageGen(gen)
-    gen._pose_coords = _stub_overlay(lambda k: k * 0 + 0.5)
-    gen._score_coords = lambda ref, coords, n: 1.0 - coords[:, 0, 1].clone()      # lower sample id: higher score
-    gen._pair_coords = _stub_pair(calls)
+    gen._pose = _stub_overlay(lambda k: k * 0 + 0.5)
+    gen._score = lambda ref, coords, n: 1.0 - coords[:, 0, 1].clone()      # lower sample id: higher score
+    gen._pair = _stub_pair(calls)
     return gen
 
 

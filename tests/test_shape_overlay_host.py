@@ -45,7 +45,7 @@ def _rot_z(deg):
 def _stub_overlay(shift_of):
     """A device-free stand-in for `shape_overlay`: rotation = 90 degrees about z, translation = (shift_of(x00), 0, 0) and
     tanimoto = shift_of(x00) per row, where x00 = the row's first coordinate; rows whose x00 is NaN fail."""
-    def run(ref, coords, n):
+    def run(ref, coords, n, refine_steps=0):
         B = coords.shape[0]
         key = coords[:, 0, 0]
         R = _rot_z(90.0).expand(B, 3, 3).clone()
@@ -65,7 +65,7 @@ def _stub_overlay(shift_of):
 def test_overlay_refusals_happen_before_any_device_work(entry):
     from ml_conformer_generator_amd import host_pool as HP
     gen = _shell_generator()
-    gen._generate_shard = gen._score_coords = gen._pose_coords = _no_device
+    gen._generate_shard = gen._score = gen._pose = _no_device
     call = getattr(gen, entry)
     ctx = torch.tensor([50.0, 100.0, 130.0])
     for kw in (dict(reference_context=ctx, n_atoms=17, overlay=True),            # nothing to pose onto
@@ -191,8 +191,8 @@ def _stub_shard(n_atoms=20):
 def test_proxy_path_returns_posed_coordinates_with_their_pose():
     gen = _shell_generator()
     gen._generate_shard = _stub_shard()
-    gen._pose_coords = _stub_overlay(lambda k: k + 1.0)
-    gen._score_coords = lambda ref, coords, n: coords[:, 1, 0].clone()
+    gen._pose = _stub_overlay(lambda k: k + 1.0)
+    gen._score = lambda ref, coords, n: coords[:, 1, 0].clone()
     plain = gen.generate_conformers(reference_conformer=_ref(), n_samples=8)
     assert all(m.pose is None and m.overlay_tanimoto is None for m in plain)
     posed = gen.generate_conformers(reference_conformer=_ref(), n_samples=8, overlay=True)
@@ -246,12 +246,12 @@ def _object_worker(rank, world, port, q):
 
     stub = _stub_overlay(lambda k: k + 0.01 * rank)     # a rank-specific offset: shows WHERE each pose was made
 
-    def pose(ref, coords, n):
+    def pose(ref, coords, n, refine_steps=0):
         posed_on.append(int(coords.shape[0]))
         return stub(ref, coords, n)
     gen._generate_shard = run
-    gen._pose_coords = pose
-    gen._score_coords = lambda ref, coords, n: coords[:, 0, 1].clone()
+    gen._pose = pose
+    gen._score = lambda ref, coords, n: coords[:, 0, 1].clone()
     from ml_conformer_generator_amd.distributed import assign_shards, keyed_global_sizes
     shards = assign_shards(keyed_global_sizes(7, 15, 19, 5), world)
     owner = {i: r for r, ix in enumerate(shards) for i in ix.tolist()}
@@ -287,6 +287,24 @@ def test_object_path_poses_travel_next_to_the_mols_world2_gloo():
     for p in procs:
         p.join(timeout=60)
     assert res == [(0, True), (1, True)]
+
+
+def test_a_finished_sample_pickles_to_the_same_size_whatever_its_shard():
+    """What crosses the object gather per sample owns its 12 pose values: its pickle does not carry the shard's other poses."""
+    import pickle
+    from ml_conformer_generator_amd import postprocess
+    gen = _shell_generator(finisher="rdkit")
+    gen._reference_coord = lambda r: torch.as_tensor(r, dtype=torch.float32)
+    gen._pose = _stub_overlay(lambda k: k + 1.0)
+    req = postprocess.parse_request(gen, _ref(), overlay=True)
+    sizes = {}
+    for B in (2, 64, 1000):
+        samples = postprocess.measure_finished(gen, req, [PosedMol([[0.5, 0, 0]] * 4) for _ in range(B)])
+        assert all(s.measured.pose is not None and s.measured.pose.shape == (12,) for s in samples)
+        sizes[B] = len(pickle.dumps(postprocess.Finished(None, samples[B - 1].measured)))
+        back = pickle.loads(pickle.dumps(samples[0]))
+        assert torch.equal(back.measured.pose, samples[0].measured.pose) and back.mol.props == samples[0].mol.props
+    assert sizes[2] == sizes[64] == sizes[1000] < 2048, sizes
 
 
 def test_records_carry_a_pose_only_when_given():

@@ -19,8 +19,7 @@ BAD_BUDGETS = (0, -3, 2.5, 64.0, "64", None, 1025)
 @pytest.mark.parametrize("entry", ["generate_conformers", "generate_conformers_sharded", "forward"])
 def test_refine_refusals_happen_before_any_device_work(entry):
     gen = _shell_generator()
-    gen._generate_shard = gen._score_coords = gen._pose_coords = _no_device
-    gen._pose_coords_refined = gen._pair_coords = _no_device
+    gen._generate_shard = gen._score = gen._pose = gen._pair = _no_device
     call = getattr(gen, entry)
     with pytest.raises(ValueError, match="overlay=True"):
         call(reference_conformer=_ref(), n_samples=4, refine_overlay=True)
@@ -94,22 +93,14 @@ def test_refined_entry_refuses_bad_arguments_without_a_gpu():
 
 
 # ----------------------------------------------------------------------------------------------- seams
-def _refined_stub(calls):
-    """A device-free `_pose_coords_refined`: the overlay stub with a different translation (k + 2) and score."""
-    stub = _stub_overlay(lambda k: k + 2.0)
+def _pose_stub(calls):
+    """A device-free `_pose` that records the step budget it received: the overlay stub, and where the budget is not 0 - a
+    refined pose - one with a different translation (k + 2) and score."""
+    plain, refined = _stub_overlay(lambda k: k + 1.0), _stub_overlay(lambda k: k + 2.0)
 
-    def run(ref, coords, n, steps):
-        calls.append(("refined", int(steps)))
-        return stub(ref, coords, n)
-    return run
-
-
-def _plain_stub(calls):
-    stub = _stub_overlay(lambda k: k + 1.0)
-
-    def run(ref, coords, n):
-        calls.append(("plain",))
-        return stub(ref, coords, n)
+    def run(ref, coords, n, refine_steps=0):
+        calls.append(int(refine_steps))
+        return (refined if refine_steps else plain)(ref, coords, n)
     return run
 
 
@@ -117,16 +108,16 @@ def test_proxy_path_takes_the_refined_seam_only_when_asked():
     gen = _shell_generator()
     gen._generate_shard = _stub_shard()
     calls = []
-    gen._pose_coords, gen._pose_coords_refined = _plain_stub(calls), _refined_stub(calls)
+    gen._pose = _pose_stub(calls)
     plain = gen.generate_conformers(reference_conformer=_ref(), n_samples=8)
     posed = gen.generate_conformers(reference_conformer=_ref(), n_samples=8, overlay=True)
-    assert calls == [("plain",)]
+    assert calls == [0]
     calls.clear()
     refined = gen.generate_conformers(reference_conformer=_ref(), n_samples=8, overlay=True, refine_overlay=True)
-    assert calls == [("refined", 64)]
+    assert calls == [64]
     calls.clear()
     gen.generate_conformers(reference_conformer=_ref(), n_samples=8, overlay=True, refine_overlay=7)
-    assert calls == [("refined", 7)]
+    assert calls == [7]
     assert [m.sample_id for m in refined] == [m.sample_id for m in posed] == [m.sample_id for m in plain]
     for a, b in zip(plain, refined):
         if b.sample_id == 5:                          # failed: generated coordinates, no pose, NaN score
@@ -142,19 +133,21 @@ def test_object_path_takes_the_refined_seam_only_when_asked():
     gen = _shell_generator(finisher="rdkit")
     gen._reference_coord = lambda r: torch.as_tensor(r, dtype=torch.float32)
     calls = []
-    gen._pose_coords, gen._pose_coords_refined = _plain_stub(calls), _refined_stub(calls)
-    gen._score_coords = _no_device
+    gen._pose = _pose_stub(calls)
+    gen._score = _no_device
 
     def mols():
         return [PosedMol([[0.5, 0, 0]] * 4 + [[0, 0, 1.0]], z=[6] * 4 + [1]), None]
-    for refine, want_call, shift in ((False, ("plain",), 1.5), (True, ("refined", 64), 2.5), (3, ("refined", 3), 2.5)):
+    for refine, want_call, shift in ((False, 0, 1.5), (True, 64, 2.5), (3, 3, 2.5)):
         calls.clear()
         req = postprocess.parse_request(gen, _ref(), False, None, None, True, None, refine)
         done = mols()
         samples = postprocess.measure_finished(gen, req, done)
-        scores, poses = [s[1] for s in samples], [s[2] for s in samples]
-        assert calls == [want_call] and scores == [None, None] and poses[1] is None
-        score, rot, trans = poses[0]
+        scores = [s.measured.shape_tanimoto for s in samples]
+        assert calls == [want_call] and scores == [None, None]
+        assert samples[1].measured.overlay_tanimoto is None and samples[1].measured.pose is None
+        score, pose = samples[0].measured.overlay_tanimoto, samples[0].measured.pose
+        rot, trans = pose[:9].reshape(3, 3), pose[9:]
         assert score == pytest.approx(shift) and torch.allclose(rot, _rot_z(90.0)) and trans.tolist() == [shift, 0, 0]
         np.testing.assert_allclose(done[0].conf.pos, [[shift, 0.5, 0.0]] * 4 + [[shift, 0.0, 1.0]], atol=1e-6)
 

@@ -57,7 +57,7 @@ def _no_device(*args, **kwargs):
 def test_refusals_happen_before_any_device_work(entry):
     from ml_conformer_generator_amd import host_pool as HP
     gen = _shell_generator()
-    gen._generate_shard = gen._score_coords = _no_device
+    gen._generate_shard = gen._score = _no_device
     call = getattr(gen, entry)
     ctx = torch.tensor([50.0, 100.0, 130.0])
     cases = [
@@ -183,7 +183,7 @@ def test_coordinates_come_from_the_conformer_heavy_atoms_only():
     def score(ref, coords, n):
         seen.append((coords.clone(), n.clone()))
         return coords[:, 0, 0] / 10.0
-    gen._score_coords = score
+    gen._score = score
     out = postprocess.score_mols(gen, _ref(), [m, None, FakeMol([[7.0, 0, 0]] * 3)])
     assert out == [0.0, None, pytest.approx(0.7)] and len(seen) == 1 and seen[0][1].tolist() == [2, 3]
 
@@ -206,7 +206,7 @@ def _stub_shard(n_atoms=20):
 def test_proxy_path_scores_and_selects_on_the_returned_rows():
     gen = _shell_generator()
     gen._generate_shard = _stub_shard()
-    gen._score_coords = lambda ref, coords, n: coords[:, 0, 0].clone()
+    gen._score = lambda ref, coords, n: coords[:, 0, 0].clone()
     plain = gen.generate_conformers(reference_conformer=_ref(), n_samples=8)
     assert [m.shape_tanimoto for m in plain] == [None] * 7
     scored = gen.generate_conformers(reference_conformer=_ref(), n_samples=8, shape_scores=True)
@@ -256,7 +256,7 @@ def _object_worker(rank, world, port, q):
         scored_on.append(int(coords.shape[0]))
         return coords[:, 0, 0].clone() + 0.01 * rank        # a rank-specific offset: shows WHERE each score was made
     gen._generate_shard = run
-    gen._score_coords = score
+    gen._score = score
     mols = gen.generate_conformers_sharded(reference_conformer=_ref(), n_samples=7, sample_seed=5, shape_scores=True)
     from ml_conformer_generator_amd.distributed import assign_shards, keyed_global_sizes
     shards = assign_shards(keyed_global_sizes(7, 15, 19, 5), world)
