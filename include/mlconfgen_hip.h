@@ -577,6 +577,44 @@ int mcg_geometry_relax_ex(const float* coords, const float* restraint_ref, const
                           const int32_t* n_nodes_dev, int B, int N, int W, int steps, float* coords_out,
                           float* energy_out, float* grad_out, float* stats_out, void* stream);
 
+/* ---- Pharmacophore overlap ("Pharmacophore overlap"): the typed interaction features of B molecular
+ * graphs and the Gaussian overlap of their posed features with a reference's.  The definition is this package's OWN
+ * (DESIGN.md states it in full): not RDKit's feature factory, not a vendor's colour force field.  Types: donor, acceptor,
+ * cation, anion, hydrophobe (per-atom bits 1, 2, 4, 8, 16; type indices 0..4) and ring (index 5: one feature per aromatic
+ * ring of 5 or 6, at the fp32 centroid of its members).  No aromaticity is perceived: a ring counts where its bonds
+ * carry code 4.
+ *   mcg_pharm_perceive: z[B,W] atomic numbers, bonds[B,W,W] symmetric bond codes (1 / 2 / 3 / 4 aromatic; any other value
+ *                       is no bond), n_nodes_dev[b] real atoms (device memory, clamped to [0, W] on the device; the
+ *                       diagonal and everything at or beyond n_b is ignored, whatever it holds).  types_out[B,W]: the
+ *                       per-atom type bits, 0 on padded atoms; n_rings_out[b]: the molecule's aromatic rings, the TRUE
+ *                       count; ring_mask_out[B, MCG_PHARM_MAX_RINGS]: the member masks (bit k = atom k) of the first
+ *                       MCG_PHARM_MAX_RINGS rings in ascending order of the mask read as an unsigned integer, 0 beyond the
+ *                       count.  One 64-lane workgroup per molecule, integer arithmetic only: the same bits whatever the
+ *                       batch, the row, the padded width and the padding's contents.
+ *   mcg_pharm_score:    coords[B,N,3] (n_b clamped to [0, min(N, W)]), types[B,W], ring_mask[B, MCG_PHARM_MAX_RINGS] and
+ *                       n_rings[B] as perceived; ref_xyz[F,3], ref_type[F] (type indices 0..5) the reference's features.
+ *                       O(X, Y) = sum over equal-typed pairs of expf(-0.5 * d2), d2 = dx*dx + dy*dy + dz*dz in fp32 in
+ *                       exactly that order (no contraction), the terms added in fp64 in one order fixed by the two feature
+ *                       lists.  o_rm[b] = O(reference, molecule b), o_mm[b] = O(b, b), tanimoto[b] = o_rm / (o_rr + o_mm -
+ *                       o_rm) rounded to fp32 with o_rr = *o_rr (device memory; NULL: the row's own o_mm), matches[b] = the
+ *                       reference features with a feature of b of their type at d2 <= 2.25; per_type[B,6] (optional, NULL
+ *                       = not wanted): the six parts of o_rm, which add up to it in type order.  A molecule without
+ *                       features has tanimoto 0 and matches 0; one with a non-finite coordinate on a real atom or with
+ *                       n_rings > MCG_PHARM_MAX_RINGS has NaN overlaps, a NaN tanimoto and matches -1, the other rows
+ *                       unaffected.  coords NULL (B <= 1; n_nodes_dev, types, ring_mask, n_rings not read): the reference's
+ *                       own list is the candidate - o_mm[0] of that run is O(R,R), by the same code.  One 64-lane
+ *                       workgroup per molecule; every output has the same bits whatever the batch, the row and the widths.
+ * B = 0 launches nothing.  MCG_ERR_ARG, nothing launched: a null required buffer, B < 0, W or N outside 1..64, F outside
+ * 1..MCG_PHARM_MAX_FEATURES, coords NULL with B > 1. */
+#define MCG_PHARM_MAX_RINGS 32
+#define MCG_PHARM_MAX_FEATURES 352 /* 64 atoms x 5 atom types + MCG_PHARM_MAX_RINGS */
+int mcg_pharm_perceive(const int32_t* z, const int8_t* bonds, const int32_t* n_nodes_dev, int B, int W,
+                       uint8_t* types_out, int32_t* n_rings_out, uint64_t* ring_mask_out, void* stream);
+int mcg_pharm_score(const float* coords, const int32_t* n_nodes_dev, const uint8_t* types, const uint64_t* ring_mask,
+                    const int32_t* n_rings, int B, int N /*coords row width*/, int W /*types width*/,
+                    const float* ref_xyz, const uint8_t* ref_type, int F, const double* o_rr /*optional*/, double* o_rm,
+                    double* o_mm, float* tanimoto, int32_t* matches, double* per_type /*optional [B,6]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,9 +11,10 @@ from .config import (ATOM_DECODER, CONTEXT_NORMS, DIMENSION, MAX_N_NODES,
 _FINGERPRINT = ("graph_fingerprints", "fingerprint_tanimoto", "pairwise_fingerprint_tanimoto", "mol_graph", "select_unique")
 _MESH = ("load_mesh", "mass_properties", "mesh_context", "solid_frame")
 _GEOMETRY = ("relax_geometry", "strain_energy")
+_PHARMACOPHORE = ("perceive_features", "feature_points", "pharmacophore_tanimoto", "load_reference_features")
 
 __all__ = ["MLConformerGenerator", "evaluate_samples", "ATOM_DECODER", "CONTEXT_NORMS", "DIMENSION",
-           "MAX_N_NODES", "MIN_N_NODES", "NUM_BOND_TYPES", *_FINGERPRINT, *_MESH, *_GEOMETRY]
+           "MAX_N_NODES", "MIN_N_NODES", "NUM_BOND_TYPES", *_FINGERPRINT, *_MESH, *_GEOMETRY, *_PHARMACOPHORE]
 
 
 def __getattr__(name):
@@ -33,4 +34,7 @@ def __getattr__(name):
     if name in _GEOMETRY:                # restrained relaxation on the package's own force field (geometry.py: not MMFF94)
         from . import geometry
         return getattr(geometry, name)
+    if name in _PHARMACOPHORE:           # pharmacophore features and their overlap (pharmacophore.py: the package's own)
+        from . import pharmacophore
+        return getattr(pharmacophore, name)
     raise AttributeError(name)

@@ -41,6 +41,9 @@ forced by the scope of this build:
       `receptor`, `max_receptor_clashes`: steric contacts of the posed molecules with a receptor; a filter on them;
       `chemical_scores`, `reference_graph`, `max_chemical_tanimoto`: chemical similarity to the reference; a filter;
       `unique`, `max_pairwise_chemical_tanimoto`: one molecule per graph; a chemically diverse selection;
+      `pharmacophore_scores`, `reference_pharmacophore`, `min_pharmacophore_tanimoto`, `rank_by`: does the posed molecule
+      keep the reference's interaction pattern - the overlap of its pharmacophore features with the reference's; a
+      filter; ranking by shape + pharmacophore score;
   * `reference_shape`, `shape_density` (every generation entry): a watertight triangle mesh - an STL file, a (vertices,
     faces) pair - as the reference, what the reference's notebook does with `trimesh` (`mesh.py`, no `trimesh` needed);
     the shape options then score, pose and select against the solid, and `max_atoms_outside` filters on the posed atoms
@@ -76,6 +79,7 @@ from . import rdkit_order
 from . import receptor as mcg_receptor
 from . import fingerprint as mcg_fp
 from . import geometry as mcg_geometry
+from . import pharmacophore as mcg_pharm
 from .handoff import (GeneratedMolecule, assemble_molecules, bond_writeback_hip, molecules_from_tensors,
                       prepare_adj_mat_seer_input_hip)
 from .mol_utils import (get_context_shape, ifm_get_xh_from_fragment, ifm_merge_hip,
@@ -339,6 +343,19 @@ class MLConformerGenerator(torch.nn.Module):
         """[B,B] pairwise Tanimoto of fingerprints (`fingerprint.pairwise_fingerprint_tanimoto`)."""
         return mcg_fp.pairwise_fingerprint_tanimoto(fp)
 
+    # the pharmacophore step
+    def _pharm_perceive(self, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor):
+        """(types [B,W] uint8, ring masks [B,32] int64, ring counts [B]) of padded graphs
+        (`pharmacophore.perceive_features`)."""
+        return mcg_pharm.perceive_features(atomic_numbers, bond_orders, n_nodes, self.device)
+
+    def _pharm_score(self, reference_features, coords: torch.Tensor, n_nodes: torch.Tensor, types: torch.Tensor,
+                     ring_mask: torch.Tensor, n_rings: torch.Tensor):
+        """(Tanimoto [B] fp32, matches [B] int32) of posed, padded molecules' perceived features against the reference's
+        (`pharmacophore.score_features`)."""
+        out = mcg_pharm.score_features(reference_features, coords, n_nodes, types, ring_mask, n_rings, self.device)
+        return out["tanimoto"], out["matches"]
+
     # the geometry step
     def _relax_coords(self, coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
                       n_nodes: torch.Tensor, steps: int) -> dict:
@@ -495,7 +512,9 @@ class MLConformerGenerator(torch.nn.Module):
                             reference_graph=None, max_chemical_tanimoto: Optional[float] = None, unique: bool = False,
                             max_pairwise_chemical_tanimoto: Optional[float] = None, reference_shape=None,
                             shape_density: float = 0.02, max_atoms_outside: Optional[int] = None,
-                            relax_geometry: Union[bool, int] = False) -> List:
+                            relax_geometry: Union[bool, int] = False, pharmacophore_scores: bool = False,
+                            reference_pharmacophore=None, min_pharmacophore_tanimoto: Optional[float] = None,
+                            rank_by: str = "shape") -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
@@ -576,8 +595,27 @@ class MLConformerGenerator(torch.nn.Module):
         names; None (no property) in a call that did not relax.  `last_batch["x_ordered"]` keeps the unrelaxed
         coordinates, `last_batch["x_relaxed"]` holds the relaxed ones.  `optimise_geometry` and its warning mean what
         they meant.
-        Order of the stages: validity, `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`, `unique`, then
-        the selection (threshold, exclusion, `top_k`).  The filters only remove molecules.
+        `pharmacophore_scores=True` (needs `overlay=True`): does the posed molecule keep the reference's interaction pattern?
+        Every returned molecule carries `pharmacophore_tanimoto` - the Tanimoto of the Gaussian overlap of its
+        pharmacophore features (donor, acceptor, cation, anion, hydrophobe, aromatic ring), as posed, with the
+        reference's - and `pharmacophore_matches`, the reference features that have one of its features of the same type
+        within 1.5 A (records: the properties of those names; Mols: the double / int properties); None (no property)
+        where posing failed.  The features are this package's OWN definition (`pharmacophore.py`, DESIGN.md section 6,
+        "Pharmacophore overlap"), perceived on the GPU from the returned heavy-atom graphs: not RDKit's feature factory
+        and not a vendor's colour score.  The reference's features are `reference_pharmacophore` - a sequence of (type,
+        (x, y, z)) in the reference's coordinates, types "donor", "acceptor", "cation", "anion", "hydrophobe", "ring"
+        (`pharmacophore.load_reference_features`; the only way with a `reference_shape` or a reference without bonds) -
+        or are perceived from `reference_graph`, else from `reference_conformer` where it is a Mol with bonds, at the
+        reference conformer's heavy-atom coordinates, in the graph's atom order.  No aromaticity is perceived: a ring
+        feature needs code-4 bonds.
+        `min_pharmacophore_tanimoto=t` (implies the score): drop the molecules whose `pharmacophore_tanimoto` is below t,
+        NaN or missing.
+        `rank_by="combo"` (needs a shape score and the pharmacophore score; default "shape"): `unique`, the diversity walk
+        and `top_k` rank by `shape_tanimoto + pharmacophore_tanimoto` instead of `shape_tanimoto`; `min_shape_tanimoto`
+        still thresholds the shape score alone.
+        Order of the stages: validity, `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`,
+        `min_pharmacophore_tanimoto`, `unique`, then the selection (threshold, exclusion, `top_k`).  The filters only
+        remove molecules.
         Refused with ValueError before any device work: a chemical option that is not a bool / a real number in (0, 1],
         a chemical score without a reference graph, a `reference_graph` that `fingerprint.mol_graph` refuses or that has no
         or more than 64 heavy atoms, scoring or posing without a reference conformer, a reference
@@ -588,14 +626,20 @@ class MLConformerGenerator(torch.nn.Module):
         `reference_shape` together with another reference, with `refine_overlay` or with a `receptor`, or without
         `n_atoms`, a mesh `load_mesh` refuses ("The mesh needs to be watertight."), a `shape_density` that is not a positive
         real number, max_atoms_outside other than an integer >= 0, without a `reference_shape` or without overlay, and
-        relax_geometry other than False, True or an integer in 1..4096 (a float, None, 0, a negative or larger number)."""
+        relax_geometry other than False, True or an integer in 1..4096 (a float, None, 0, a negative or larger number),
+        pharmacophore_scores that is not a bool, without overlay or without a source of the reference's features, a
+        `reference_pharmacophore` that `load_reference_features` refuses or that no option reads, a reference graph whose
+        heavy-atom count differs from the reference conformer's, min_pharmacophore_tanimoto outside [0, 1], and a
+        `rank_by` other than "shape" or "combo", or "combo" without both scores.  A reference graph in which no feature is
+        found is refused where it is perceived, behind the generation."""
         if sample_seed is not None:
             seeding.check_seed(sample_seed)
         req = postprocess.parse_request(self, reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
                                         max_pairwise_tanimoto, refine_overlay, receptor, max_receptor_clashes,
                                         chemical_scores, reference_graph, max_chemical_tanimoto, unique,
                                         max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
-                                        reference_context, relax_geometry)
+                                        reference_context, relax_geometry, pharmacophore_scores,
+                                        reference_pharmacophore, min_pharmacophore_tanimoto, rank_by)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         keyed = () if sample_seed is None else (sample_seed, None)   # unseeded: the positional call of before
@@ -626,7 +670,9 @@ class MLConformerGenerator(torch.nn.Module):
                                     unique: bool = False,
                                     max_pairwise_chemical_tanimoto: Optional[float] = None, reference_shape=None,
                                     shape_density: float = 0.02, max_atoms_outside: Optional[int] = None,
-                                    relax_geometry: Union[bool, int] = False) -> List:
+                                    relax_geometry: Union[bool, int] = False, pharmacophore_scores: bool = False,
+                                    reference_pharmacophore=None, min_pharmacophore_tanimoto: Optional[float] = None,
+                                    rank_by: str = "shape") -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -644,7 +690,8 @@ class MLConformerGenerator(torch.nn.Module):
         no generator, so sample i is the same molecule on any world size and under either `balance`.
         `shape_scores`, `top_k`, `min_shape_tanimoto`, `overlay`, `max_pairwise_tanimoto`, `refine_overlay`, `receptor`,
         `max_receptor_clashes`, `chemical_scores`, `reference_graph`, `max_chemical_tanimoto`, `unique`,
-        `max_pairwise_chemical_tanimoto`, `reference_shape`, `shape_density`, `max_atoms_outside`, `relax_geometry`: as in
+        `max_pairwise_chemical_tanimoto`, `reference_shape`, `shape_density`, `max_atoms_outside`, `relax_geometry`,
+        `pharmacophore_scores`, `reference_pharmacophore`, `min_pharmacophore_tanimoto`, `rank_by`: as in
         `generate_conformers` (every rank loads the mesh and computes its occupancy itself).  The fingerprints are computed behind the gather,
         on the rows a rank returns: with gather="all" uniqueness and chemical diversity hold over the whole batch, with
         gather="rank0" within each other rank's own shard, like the rest of the selection.
@@ -663,7 +710,8 @@ class MLConformerGenerator(torch.nn.Module):
                                         max_pairwise_tanimoto, refine_overlay, receptor, max_receptor_clashes,
                                         chemical_scores, reference_graph, max_chemical_tanimoto, unique,
                                         max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
-                                        reference_context, relax_geometry)
+                                        reference_context, relax_geometry, pharmacophore_scores,
+                                        reference_pharmacophore, min_pharmacophore_tanimoto, rank_by)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)

@@ -49,6 +49,8 @@ class Measured:
     graph_key: Optional[int] = None               # unsigned 64-bit
     strain_before: Optional[float] = None
     strain_after: Optional[float] = None
+    pharmacophore_tanimoto: Optional[float] = None
+    pharmacophore_matches: Optional[int] = None
 
 
 _UNMEASURED = Measured()          # shared by every record that carries no values: never written to
@@ -58,7 +60,8 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
     """The records of n samples from per-sample tensors by field name of `Measured` (a name left out or None: not
     measured), one D2H copy each.  The one place that reads the tensors' spellings of "not measured": a negative
     `receptor_clashes` (both contact values None), a negative `atoms_outside`, a `pose` row [12] with a non-finite entry
-    (`overlay_tanimoto` keeps its NaN); `graph_key` is int64 holding the unsigned bit pattern."""
+    (`overlay_tanimoto` keeps its NaN), a negative `pharmacophore_matches` (both pharmacophore values None); `graph_key` is
+    int64 holding the unsigned bit pattern."""
     cols = {k: v.cpu().tolist() for k, v in values.items() if v is not None and k != "pose"}
     if values.get("pose") is not None:
         poses = values["pose"].cpu().to(torch.float32)
@@ -69,6 +72,11 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
             cols[k] = [None if gone else v for gone, v in zip(missing, cols[k])]
     if "atoms_outside" in cols:
         cols["atoms_outside"] = [None if c < 0 else c for c in cols["atoms_outside"]]
+    if "pharmacophore_matches" in cols:
+        missing = [c < 0 for c in cols["pharmacophore_matches"]]
+        for k in ("pharmacophore_matches", "pharmacophore_tanimoto"):
+            if k in cols:
+                cols[k] = [None if gone else v for gone, v in zip(missing, cols[k])]
     if "graph_key" in cols:
         cols["graph_key"] = [k & 0xFFFFFFFFFFFFFFFF for k in cols["graph_key"]]
     return [Measured(**{k: col[b] for k, col in cols.items()}) for b in range(n)]
@@ -89,7 +97,10 @@ class GeneratedMolecule:
     identity key (`fingerprint.py`: the package's own Morgan-type fingerprint, a substitute for RDKit's), else None.
     `atoms_outside`: how many of its atoms lie outside the mesh of a call posed into a `reference_shape`, else None.
     `strain_before` / `strain_after`: the energy of the package's own force field (`geometry.py`, NOT MMFF94) before and
-    after the relaxation of a call with `relax_geometry`, else None."""
+    after the relaxation of a call with `relax_geometry`, else None.
+    `pharmacophore_tanimoto` / `pharmacophore_matches`: the overlap of its pharmacophore features with the reference's and
+    the reference features it matches (`pharmacophore.py`: the package's own definition) when the call asked for
+    `pharmacophore_scores`, else None."""
     __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_measured")
 
     def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True,
@@ -106,6 +117,20 @@ class GeneratedMolecule:
         m._sid = b if sample_id is None else sample_id
         m._measured = measured
         return m
+
+    @property
+    def pharmacophore_tanimoto(self) -> Optional[float]:
+        """Tanimoto of the Gaussian overlap of this molecule's pharmacophore features, as posed, with the reference's
+        (`pharmacophore.py`: the package's own feature definition - NOT RDKit's feature factory, not a vendor's colour
+        score) when the call asked for `pharmacophore_scores` or `min_pharmacophore_tanimoto`; None otherwise, and where
+        posing failed."""
+        return self._measured.pharmacophore_tanimoto
+
+    @property
+    def pharmacophore_matches(self) -> Optional[int]:
+        """How many of the reference's pharmacophore features have a feature of this molecule of the same type within
+        1.5 A, when the call asked for `pharmacophore_scores`; None otherwise, and where posing failed."""
+        return self._measured.pharmacophore_matches
 
     @property
     def strain_before(self) -> Optional[float]:
@@ -356,7 +381,9 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                            chemical_tanimoto: Optional[torch.Tensor] = None,
                            graph_key: Optional[torch.Tensor] = None,
                            atoms_outside: Optional[torch.Tensor] = None, strain_before: Optional[torch.Tensor] = None,
-                           strain_after: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
+                           strain_after: Optional[torch.Tensor] = None,
+                           pharmacophore_tanimoto: Optional[torch.Tensor] = None,
+                           pharmacophore_matches: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
     (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
     (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records).
@@ -367,14 +394,17 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     similarity to the reference and graph identity key (either may be None: not asked for).  `atoms_outside[b]`: row b's
     atoms outside the call's mesh (negative: its pose failed, the record gets None; None: a call without a mesh).
     `strain_before[b]` / `strain_after[b]`: row b's force-field energy before and after the relaxation of a call with
-    `relax_geometry` (both or neither; None: a call that did not relax).  The value keywords are the fields of `Measured`
+    `relax_geometry` (both or neither; None: a call that did not relax).  `pharmacophore_tanimoto[b]` /
+    `pharmacophore_matches[b]`: row b's pharmacophore overlap with the reference and matched reference features (negative
+    matches: not measured, the record gets None for both; None: a call without `pharmacophore_scores`).  The value keywords are the fields of `Measured`
     and go to `measured_from_tensors`; a call with no ids and no values builds the views and nothing else."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
     view = GeneratedMolecule._view
     values = dict(shape_tanimoto=shape_tanimoto, overlay_tanimoto=overlay_tanimoto, pose=pose,
                   receptor_clashes=receptor_clashes, receptor_max_overlap=receptor_max_overlap,
                   atoms_outside=atoms_outside, chemical_tanimoto=chemical_tanimoto, graph_key=graph_key,
-                  strain_before=strain_before, strain_after=strain_after)
+                  strain_before=strain_before, strain_after=strain_after,
+                  pharmacophore_tanimoto=pharmacophore_tanimoto, pharmacophore_matches=pharmacophore_matches)
     if sample_ids is None and all(v is None for v in values.values()):
         return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
     flags = valid.cpu().tolist()

@@ -11,18 +11,19 @@ Stages, in this order:
     3. receptor contacts of the returned coordinates (`receptor`).
   BEHIND the gather, on the rows a rank returns (`return_records` / `return_finished`):
     4. chemical fingerprints, graph keys and the Tanimoto to the reference's graph: one launch over the rows, one for
-       the reference (`fingerprints`);
+       the reference (`fingerprints`); beside it the pharmacophore overlap of the posed rows with the reference's
+       features: one perceive and one score launch over the rows, one each for the reference (`pharmacophore`);
     5. the values are attached - each molecule's `handoff.Measured`, behind a record's properties or written onto the
        Mol by `rdkit_finish.tag_measured` (Mols lose their properties in the object gather) - and validity is taken
        (`last_valid_fraction`);
     6. `select`, written once for both paths: `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`,
-       `unique`, then the
+       `min_pharmacophore_tanimoto`, `unique`, then the
        threshold / sphere exclusion / `top_k` walk of `cheminformatics.select_diverse`.  The two pair matrices are
        computed only when their threshold is set, over the rows that survived the filters.
 A call with no option on takes none of these steps: its records / live Mols are returned as they come.
 
 The device work goes through the generator's seams (`_pose`, `_score`, `_pair`, `_receptor_coords`,
-`_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`), looked up on the instance at the time of the call.  The shape
+`_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, `_pharm_perceive`, `_pharm_score`), looked up on the instance at the time of the call.  The shape
 seams take the request's reference object; which kind it is - a conformer or a solid - is `cheminformatics`' business."""
 from __future__ import annotations
 
@@ -37,6 +38,7 @@ from . import cheminformatics
 from . import fingerprint as mcg_fp
 from . import geometry as mcg_geometry
 from . import host_pool
+from . import pharmacophore as mcg_pharm
 from . import receptor as mcg_receptor
 from .handoff import Measured, measured_from_tensors, molecules_from_tensors
 
@@ -61,6 +63,11 @@ class Request:
     max_pairwise_chemical_tanimoto: Optional[float] = None
     max_atoms_outside: Optional[int] = None
     relax_steps: int = 0                          # `relax_geometry`: trial steps of the relaxation, 0 = not relaxed
+    scores_pharmacophore: bool = False            # `pharmacophore_scores`, or implied by `min_pharmacophore_tanimoto`
+    ref_features: Optional[tuple] = None          # `reference_pharmacophore`: (xyz [F,3] fp32, type index [F] uint8), host
+    ref_pharm_graph: Optional[tuple] = None       # else (atomic numbers, bond codes [n,n] int8, coords [n,3]) to perceive
+    min_pharmacophore_tanimoto: Optional[float] = None
+    rank_by: str = "shape"                        # "combo": rank by shape + pharmacophore Tanimoto
 
     @property
     def selects_by_shape(self) -> bool:
@@ -84,7 +91,14 @@ class Request:
         """Whether the call filters or selects, i.e. may return fewer molecules than are valid."""
         return (self.max_receptor_clashes is not None or self.max_chemical_tanimoto is not None or self.unique
                 or self.selects_by_shape or self.max_pairwise_chemical_tanimoto is not None
-                or self.max_atoms_outside is not None)
+                or self.max_atoms_outside is not None or self.min_pharmacophore_tanimoto is not None)
+
+    def ranking_score(self, measured: Measured) -> Optional[float]:
+        """What `unique`, the diversity walk and `top_k` rank a molecule by: its shape score, or - `rank_by="combo"` - shape
+        + pharmacophore Tanimoto (`pharmacophore.select_score`: NaN, which ranks last, where either is missing)."""
+        if self.rank_by == "combo":
+            return mcg_pharm.select_score(measured.shape_tanimoto, measured.pharmacophore_tanimoto)
+        return measured.shape_tanimoto
 
 
 def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: Optional[int] = None,
@@ -94,12 +108,18 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
                   max_chemical_tanimoto: Optional[float] = None, unique=False,
                   max_pairwise_chemical_tanimoto: Optional[float] = None, reference_shape=None,
                   shape_density: float = 0.02, max_atoms_outside: Optional[int] = None,
-                  reference_context=None, relax_geometry: Union[bool, int] = False) -> Request:
+                  reference_context=None, relax_geometry: Union[bool, int] = False, pharmacophore_scores=False,
+                  reference_pharmacophore=None, min_pharmacophore_tanimoto: Optional[float] = None,
+                  rank_by: str = "shape") -> Request:
     """The public option keywords of a generation entry of `gen` as a `Request`: the shape options first, then the chemical
     ones (`top_k` / `min_shape_tanimoto` / `max_pairwise_tanimoto` imply the shape score, `max_chemical_tanimoto` the
     chemical one).  `reference_shape`: a watertight mesh in place of the reference conformer (`mesh.load_mesh`); the
     request then carries its `cheminformatics.SolidReference` (host side only: nothing is launched here), whether or not an
     option is on.  `relax_geometry`: `geometry.check_steps`; it works with every other option and every finisher.
+    `pharmacophore_scores` (implied by `min_pharmacophore_tanimoto`) needs `overlay`; the reference's features are
+    `reference_pharmacophore` (`pharmacophore.load_reference_features`) or are perceived, behind the generation, from the
+    reference's graph (`reference_graph`, else a reference conformer with bonds) at the reference conformer's coordinates.
+    `rank_by="combo"` needs the shape and the pharmacophore score.
     Every refusal happens here, before any device work."""
     relax_steps = mcg_geometry.check_steps(relax_geometry)
     custom_finisher = isinstance(getattr(gen, "finisher", None), host_pool.TaskRef)
@@ -167,6 +187,39 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
                      min_shape_tanimoto=min_shape_tanimoto, max_pairwise_tanimoto=max_pairwise_tanimoto,
                      refine_steps=refine_steps, receptor=rec, max_receptor_clashes=max_receptor_clashes)
 
+    mcg_pharm.check_flag("pharmacophore_scores", pharmacophore_scores)
+    if min_pharmacophore_tanimoto is not None:
+        mcg_pharm.check_threshold("min_pharmacophore_tanimoto", min_pharmacophore_tanimoto)
+    mcg_pharm.check_rank_by(rank_by)
+    pharm = pharmacophore_scores or min_pharmacophore_tanimoto is not None
+    if reference_pharmacophore is not None and not pharm:
+        raise ValueError("reference_pharmacophore is only read with pharmacophore_scores or min_pharmacophore_tanimoto")
+    if rank_by == "combo" and not (pharm and shape.get("scores_shape")):
+        raise ValueError("rank_by='combo' needs shape scores (shape_scores, top_k, min_shape_tanimoto or "
+                         "max_pairwise_tanimoto) and pharmacophore_scores: it ranks by their sum")
+    if pharm:
+        if not overlay:
+            raise ValueError("pharmacophore_scores needs overlay=True: molecules that are not posed onto the reference are "
+                             "not in the coordinates of its features")
+        common.update(scores_pharmacophore=True, min_pharmacophore_tanimoto=min_pharmacophore_tanimoto, rank_by=rank_by)
+        if reference_pharmacophore is not None:
+            common["ref_features"] = mcg_pharm.load_reference_features(reference_pharmacophore)
+        else:
+            src = reference_graph
+            if src is None and hasattr(reference_conformer, "GetAtoms") and hasattr(reference_conformer, "GetBonds"):
+                src = reference_conformer
+            if src is None or solid is not None:
+                raise ValueError("pharmacophore scores need the reference's features: pass reference_pharmacophore= (a "
+                                 "sequence of (type, (x, y, z)) in the reference's coordinates - the only way with a "
+                                 "reference_shape) or the reference's molecular graph (reference_graph=, or a reference "
+                                 "conformer with bonds)")
+            z, bonds = mcg_fp.mol_graph(src)
+            coords = common["reference"].coords
+            if not 1 <= len(z) <= mcg_pharm.MAX_ATOMS or len(z) != int(coords.shape[0]):
+                raise ValueError(f"the reference graph has {len(z)} heavy atoms, the reference conformer "
+                                 f"{int(coords.shape[0])}: the features are placed on the conformer's atoms, in the "
+                                 f"graph's order (at most {mcg_pharm.MAX_ATOMS})")
+            common["ref_pharm_graph"] = (z, bonds, coords)
     mcg_fp.check_flag("chemical_scores", chemical_scores)
     mcg_fp.check_flag("unique", unique)
     if max_chemical_tanimoto is not None:
@@ -174,8 +227,9 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     if max_pairwise_chemical_tanimoto is not None:
         mcg_fp.check_threshold("max_pairwise_chemical_tanimoto", max_pairwise_chemical_tanimoto)
     scoring = chemical_scores or max_chemical_tanimoto is not None
-    if reference_graph is not None and not scoring:
-        raise ValueError("reference_graph is only read with chemical_scores or max_chemical_tanimoto")
+    if reference_graph is not None and not scoring and common.get("ref_pharm_graph") is None:
+        raise ValueError("reference_graph is only read with chemical_scores, max_chemical_tanimoto or pharmacophore "
+                         "scores without reference_pharmacophore")
     if not (scoring or unique or max_pairwise_chemical_tanimoto is not None):
         return Request(**shape, **common)
     if custom_finisher:
@@ -216,9 +270,11 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
     """The items of `rows` a call returns: the rows with at most `max_receptor_clashes` clashing atoms (one without
     contacts - its pose failed - does not pass), then those with at most `max_atoms_outside` atoms outside the mesh (one
     without a count - its pose failed - does not pass), then those with a chemical Tanimoto below `max_chemical_tanimoto` (NaN
-    does not pass), then `unique` - of the rows with one graph key the first in ranking order
-    (`cheminformatics.ranking_key`: by shape score where the call scores shape, else the lowest sample id), still in the
-    input's order - then the threshold, the sphere exclusion at `max_pairwise_tanimoto` and at
+    does not pass), then those with a pharmacophore Tanimoto of at least `min_pharmacophore_tanimoto` (NaN and None do not
+    pass), then `unique` - of the rows with one graph key the first in ranking order
+    (`cheminformatics.ranking_key` of `Request.ranking_score`: by shape score where the call scores shape - plus the
+    pharmacophore score with `rank_by="combo"` - else the lowest sample id), still in the
+    input's order - then the threshold (always on the shape score alone), the sphere exclusion at `max_pairwise_tanimoto` and at
     `max_pairwise_chemical_tanimoto` in one walk, and `top_k` (`cheminformatics.select_diverse`).  `shape_pair(rows)` /
     `chem_pair(rows)`: the [n,n] pair matrices of the surviving rows, each called only when its threshold is set."""
     def at_most(field: str, limit: int) -> List[int]:
@@ -230,16 +286,23 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
         rows = rows.take(at_most("atoms_outside", req.max_atoms_outside))
     if req.max_chemical_tanimoto is not None:
         rows = rows.take([i for i, m in enumerate(rows.measured) if m.chemical_tanimoto < req.max_chemical_tanimoto])
+    if req.min_pharmacophore_tanimoto is not None:
+        rows = rows.take([i for i, m in enumerate(rows.measured) if m.pharmacophore_tanimoto is not None
+                          and m.pharmacophore_tanimoto >= req.min_pharmacophore_tanimoto])
     if req.unique:
-        order = sorted(range(len(rows.item)), key=lambda i: cheminformatics.ranking_key(rows.measured[i].shape_tanimoto,
-                                                                                       rows.sample_id[i]))
+        order = sorted(range(len(rows.item)), key=lambda i: cheminformatics.ranking_key(
+            req.ranking_score(rows.measured[i]), rows.sample_id[i]))
         rows = rows.take(mcg_fp.select_unique([m.graph_key for m in rows.measured], order))
     if not req.selects_by_shape and req.max_pairwise_chemical_tanimoto is None:
         return rows.item
+    threshold = req.min_shape_tanimoto
+    if req.rank_by == "combo" and threshold is not None:          # the walk ranks by the sum: the shape threshold goes first
+        rows = rows.take([i for i, m in enumerate(rows.measured) if m.shape_tanimoto >= threshold])
+        threshold = None
     keep = cheminformatics.select_diverse(
-        [m.shape_tanimoto for m in rows.measured], rows.sample_id,
+        [req.ranking_score(m) for m in rows.measured], rows.sample_id,
         shape_pair(rows) if req.max_pairwise_tanimoto is not None else None,
-        req.max_pairwise_tanimoto, req.top_k, req.min_shape_tanimoto,
+        req.max_pairwise_tanimoto, req.top_k, threshold,
         chem_pair(rows) if req.max_pairwise_chemical_tanimoto is not None else None, req.max_pairwise_chemical_tanimoto)
     return [rows.item[i] for i in keep]
 
@@ -253,6 +316,22 @@ def fingerprints(gen, req: Request, atomic_numbers: torch.Tensor, bond_orders: t
         ref_fp = gen._graph_fingerprints(*mcg_fp.pad_graphs([req.ref_graph]))[0][0]
         sim = gen._chem_tanimoto(fp, ref_fp.to(fp.device))
     return fp, key, sim
+
+
+def pharmacophore(gen, req: Request, coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
+                  n_nodes: torch.Tensor):
+    """The pharmacophore step of posed, padded molecules: (Tanimoto [B] fp32, matches [B] int32), by one perceive and one
+    score launch over the rows.  The reference's features are the request's, or are perceived here - one more perceive
+    launch - from its graph at the reference conformer's coordinates; ValueError where that reference has no feature or
+    more rings than are kept."""
+    feats = req.ref_features
+    if feats is None:
+        z, bonds, xyz = req.ref_pharm_graph
+        types, rings, count = gen._pharm_perceive(*mcg_fp.pad_graphs([(z, bonds)]))
+        if int(count[0]) > mcg_pharm.MAX_RINGS:
+            raise ValueError(f"the reference has {int(count[0])} aromatic rings; at most {mcg_pharm.MAX_RINGS} are kept")
+        feats = mcg_pharm.load_reference_features(mcg_pharm.feature_points(xyz.unsqueeze(0), types, rings, count)[0])
+    return gen._pharm_score(feats, coords, n_nodes, *gen._pharm_perceive(atomic_numbers, bond_orders, n_nodes))
 
 
 def _index(rows: Rows, device) -> torch.Tensor:
@@ -293,6 +372,11 @@ def return_records(gen, req: Request, res: dict, row_ids: Optional[torch.Tensor]
     if req.needs_fingerprints:
         fp, key, sim = fingerprints(gen, req, res["elements"], res["bond"], res["n_nodes"])
         values.update(chemical_tanimoto=sim, graph_key=key if req.tags_graph_keys else None)
+    if req.scores_pharmacophore:
+        sim, hits = pharmacophore(gen, req, res["x"], res["elements"], res["bond"], res["n_nodes"])
+        posed = torch.isfinite(res["pose"]).all(dim=1).to(sim.device)         # a failed pose is not in the reference's frame
+        values.update(pharmacophore_tanimoto=torch.where(posed, sim, torch.full_like(sim, float("nan"))),
+                      pharmacophore_matches=torch.where(posed, hits, torch.full_like(hits, -1)))
     if gen.device.type == "cuda":
         torch.cuda.synchronize(gen.device)        # (the D2H copies below would wait anyway: keep that out of the figure)
     t0 = time.perf_counter()
@@ -412,6 +496,14 @@ def return_finished(gen, req: Request, samples: List[Finished], row_ids: Optiona
         chem = measured_from_tensors(dict(chemical_tanimoto=sim, graph_key=key if req.tags_graph_keys else None), len(live))
         for m, c in zip(rows.measured, chem):
             m.chemical_tanimoto, m.graph_key = c.chemical_tanimoto, c.graph_key
+    posed = [i for i, m in enumerate(rows.measured) if m.pose is not None]
+    if req.scores_pharmacophore and posed:        # the live, posed Mols' heavy atoms and their own graphs
+        z, bonds, nn = mcg_fp.pad_graphs([mcg_fp.mol_graph(rows.item[i]) for i in posed])
+        sim, hits = pharmacophore(gen, req, _heavy_coords([rows.item[i] for i in posed])[0], z, bonds, nn)
+        scored = measured_from_tensors(dict(pharmacophore_tanimoto=sim, pharmacophore_matches=hits), len(posed))
+        for i, c in zip(posed, scored):
+            rows.measured[i].pharmacophore_tanimoto = c.pharmacophore_tanimoto
+            rows.measured[i].pharmacophore_matches = c.pharmacophore_matches
     rdkit_finish.tag_measured(rows.item, rows.measured)
     if not req.measures:
         return rows.item
