@@ -480,6 +480,33 @@ int mcg_receptor_overlap(const float* lig_xyz, const float* lig_radius, const in
                          const float* rec_xyz, const float* rec_radius, int R, int splits, float* partial_ws,
                          float* overlap_out, void* stream);
 
+/* ---- Clash relief ("Clash relief"): every posed molecule moved as a rigid body out of its steric
+ * contacts with the receptor, one 256-lane workgroup per molecule, by a downhill accept / reject walk.
+ *   lig_xyz[B,N,3], lig_radius[B,N], n_nodes_dev[B]: as for mcg_receptor_overlap.  rec_xyzr[R,4]: the receptor's heavy
+ *   atoms as (x, y, z, van der Waals radius), 16-byte aligned, finite (the caller's check).
+ *   Contact depth h_ij = max(0, ((r_i + r_j) - margin) - |x_i - y_j|); penalty P = sum h_ij^2; force on atom i
+ *   F_i = sum_j 2 h_ij (x_i - y_j) / |x_i - y_j| (0 at distance 0); torque about the ligand's atom centroid.  Motion
+ *   x' = (x - c) @ G + p, c the input's atom centroid, from G = I, p = c.  A trial rotates by s_r about the torque and
+ *   moves by s_t along the net force (from 0.05 rad, 0.25 A) and is kept only if P strictly decreases (both lengths x 1.2,
+ *   else x 0.5); a trial with |p - c| > max_shift is rejected the same way; `steps` trials, ended early only by P == 0.
+ *   G is re-orthonormalised as each trial is formed, so the returned pose is the one that was evaluated.
+ *   tile_sphere[ceil(R / 256), 4] or NULL: centre and radius of each tile of 256 consecutive receptor atoms, the radius
+ *   including the tile's largest atom radius.  A workgroup then walks only the tiles within reach of its molecule; pairs
+ *   out of contact are never summed, so the outputs have the same bits with and without it.
+ *   coords_out[B,N,3]: the moved rows (padded rows zero); xform_out[B,12]: rotation row-major, then translation, with
+ *   x' = x @ R + t; stats_out[B,4]: P before, P after, accepted steps, heavy-atom RMSD between input and output;
+ *   gradient_out[B,6] (may be NULL): net force and torque at the start.  A molecule no step of which was accepted (P = 0
+ *   at the start included) returns its input rows bit for bit, R = I, t = 0.  A molecule without atoms or with a
+ *   non-finite coordinate returns its rows as they came and NaN in xform, stats and gradient; the others are unaffected.
+ *   Every output depends on the molecule's own atoms and the receptor array only: the same bits in any batch, row, width.
+ * MCG_ERR_ARG, nothing launched: a null buffer (tile_sphere and gradient_out excepted), B outside 1..MCG_RECEPTOR_MAX_B,
+ * N outside 1..64, R outside 1..MCG_RECEPTOR_MAX_ATOMS, steps outside 0..1024, margin or max_shift negative or not
+ * finite. */
+int mcg_receptor_relieve(const float* lig_xyz, const float* lig_radius, const int32_t* n_nodes_dev, int B, int N,
+                         const float* rec_xyzr, int R, const float* tile_sphere, int steps, float margin,
+                         float max_shift, float* coords_out, float* xform_out, float* stats_out, float* gradient_out,
+                         void* stream);
+
 /* ---- Chemical fingerprints ("Chemical fingerprints"): a circular, Morgan-type fingerprint (radius
  * 2, 2 048 bits, bond types on, chirality off) and a graph identity key of B molecular graphs.  The definition is this
  * package's own (DESIGN.md states it in full): a SUBSTITUTE for RDKit's Morgan fingerprint, not bit-compatible with it.

@@ -12,9 +12,11 @@ _FINGERPRINT = ("graph_fingerprints", "fingerprint_tanimoto", "pairwise_fingerpr
 _MESH = ("load_mesh", "mass_properties", "mesh_context", "solid_frame")
 _GEOMETRY = ("relax_geometry", "strain_energy")
 _PHARMACOPHORE = ("perceive_features", "feature_points", "pharmacophore_tanimoto", "load_reference_features")
+_RECEPTOR = ("relieve_clashes",)
 
 __all__ = ["MLConformerGenerator", "evaluate_samples", "ATOM_DECODER", "CONTEXT_NORMS", "DIMENSION",
-           "MAX_N_NODES", "MIN_N_NODES", "NUM_BOND_TYPES", *_FINGERPRINT, *_MESH, *_GEOMETRY, *_PHARMACOPHORE]
+           "MAX_N_NODES", "MIN_N_NODES", "NUM_BOND_TYPES", *_FINGERPRINT, *_MESH, *_GEOMETRY, *_PHARMACOPHORE,
+           *_RECEPTOR]
 
 
 def __getattr__(name):
@@ -37,4 +39,7 @@ def __getattr__(name):
     if name in _PHARMACOPHORE:           # pharmacophore features and their overlap (pharmacophore.py: the package's own)
         from . import pharmacophore
         return getattr(pharmacophore, name)
+    if name in _RECEPTOR:                # clash relief of posed molecules (receptor.py: the package's own procedure)
+        from . import receptor
+        return getattr(receptor, name)
     raise AttributeError(name)

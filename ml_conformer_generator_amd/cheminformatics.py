@@ -371,6 +371,37 @@ def shape_scores(reference_coord, coords: torch.Tensor, n_nodes: torch.Tensor, d
     return ref.score_frames(frames, nn, dev)
 
 
+@torch.no_grad()
+def shape_tanimoto_placed(reference_coord, coords: torch.Tensor, n_nodes: torch.Tensor, device=None) -> torch.Tensor:
+    """[B] on the device: the shape Tanimoto of every molecule AS PLACED - no frame of its own, no orientation search -
+    against the reference conformer, for molecules in the reference's own coordinates (what `shape_overlay` returns, or a
+    pose moved on from there).  Scored on the grid `shape_overlay` scores on: reference and molecules are taken into the
+    reference's principal frame by `ConformerReference.grid`'s transform, y = (x - t_r) @ M_r, and `mcg_shape_tanimoto`
+    scores them in the identity orientation.  Refuses what `shape_scores` refuses."""
+    ref, dev, x, nn = _shape_inputs(reference_coord, coords, n_nodes, device)
+    if x is None:
+        return torch.empty(0, device=dev)
+    B, W = int(x.shape[0]), int(x.shape[1])
+    xform, axes = ref.grid(dev)
+    M, t = xform[0, :9].reshape(3, 3), xform[0, 9:]
+
+    def into_frame(p):                        # written out: a product and a fixed sum per element, no library GEMM
+        d = p - t
+        return (d[..., 0:1] * M[0] + d[..., 1:2] * M[1]) + d[..., 2:3] * M[2]
+    real = (torch.arange(W, device=dev).view(1, W) < nn.view(B, 1)).unsqueeze(-1)
+    y = torch.where(real, into_frame(x), torch.zeros((), device=dev)).contiguous()
+    ref_frame = into_frame(ref.coords.to(dev)).contiguous()
+    n = int(axes.shape[1])
+    eye = torch.eye(3, device=dev).reshape(1, 9).contiguous()
+    f = torch.empty(n ** 3, device=dev)
+    score = torch.empty(B, device=dev)
+    _lib.check(_lib.lib().mcg_shape_tanimoto(_lib.dptr(ref_frame), int(ref_frame.shape[0]), _lib.dptr(y), _lib.dptr(nn), B,
+                                             W, _lib.dptr(eye), 1, _lib.dptr(axes), n, float(ALPHA), float(AMPLITUDE),
+                                             _lib.dptr(f), _lib.dptr(score), _lib.current_stream_ptr(dev)),
+               "mcg_shape_tanimoto")
+    return score
+
+
 MAX_REFINE_STEPS = 1024       # csrc/mcg_shape_refine.hip RF_MAX_STEPS
 
 

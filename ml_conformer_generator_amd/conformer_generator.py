@@ -39,6 +39,7 @@ forced by the scope of this build:
       `overlay`, `refine_overlay`: pose every returned molecule onto the reference conformer; refine that pose;
       `max_pairwise_tanimoto`: a shape-diverse selection of the posed molecules;
       `receptor`, `max_receptor_clashes`: steric contacts of the posed molecules with a receptor; a filter on them;
+      `relieve_clashes`: the posed molecules nudged, as rigid bodies, out of their clashes with the receptor first;
       `chemical_scores`, `reference_graph`, `max_chemical_tanimoto`: chemical similarity to the reference; a filter;
       `unique`, `max_pairwise_chemical_tanimoto`: one molecule per graph; a chemically diverse selection;
       `pharmacophore_scores`, `reference_pharmacophore`, `min_pharmacophore_tanimoto`, `rank_by`: does the posed molecule
@@ -384,6 +385,17 @@ class MLConformerGenerator(torch.nn.Module):
         """Per-atom receptor overlap [B,N] (device) of padded posed heavy-atom coordinates (`receptor.receptor_overlap`)."""
         return mcg_receptor.receptor_overlap(rec, coords, n_nodes, atomic_numbers, self.device)
 
+    def _relieve(self, rec: tuple, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_numbers: torch.Tensor,
+                 steps: int) -> dict:
+        """Padded posed heavy-atom coordinates moved out of their contacts with the receptor
+        (`receptor.relieve_clashes`, device tensors)."""
+        return mcg_receptor.relieve_clashes(rec, coords, n_nodes, atomic_numbers, steps, device=self.device)
+
+    def _score_placed(self, reference, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
+        """Shape Tanimoto [B] (device) of padded heavy-atom coordinates as placed in the reference's coordinates
+        (`cheminformatics.shape_tanimoto_placed`)."""
+        return cheminformatics.shape_tanimoto_placed(reference, coords, n_nodes, self.device)
+
     def _executor(self):
         """Where the poolable host tasks run: the process-wide `HostPool` with `n_host_workers` workers and this generator's
         task deadline (workers created at the first submit or by `prestart`), or this thread."""
@@ -514,7 +526,7 @@ class MLConformerGenerator(torch.nn.Module):
                             shape_density: float = 0.02, max_atoms_outside: Optional[int] = None,
                             relax_geometry: Union[bool, int] = False, pharmacophore_scores: bool = False,
                             reference_pharmacophore=None, min_pharmacophore_tanimoto: Optional[float] = None,
-                            rank_by: str = "shape") -> List:
+                            rank_by: str = "shape", relieve_clashes: Union[bool, int] = False) -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
@@ -552,6 +564,19 @@ class MLConformerGenerator(torch.nn.Module):
         overlapping a receptor atom by >= 0.6 A) and `receptor_max_overlap` (A), the Mols the int / double properties of
         the same names; None (no property) where posing failed.  `max_receptor_clashes=k`: drop the molecules with more
         than k clashing atoms, and those whose pose failed, before the threshold / diversity / `top_k` selection.
+        `relieve_clashes` (needs a `receptor`): True (32 trials) or a trial budget 1..1024.  Right behind the pose and its
+        refinement every posed molecule is nudged, as a rigid body, out of its contacts with the receptor on the GPU
+        (`receptor.relieve_clashes`; DESIGN.md section 6, "Clash relief"): a downhill walk on the summed squared contact
+        depth - the package's OWN procedure, not a docking score and not a force field: no attraction, no trade of shape
+        against fit; it stops at the first clash-free pose it finds, within 2 A of where the pose put the centroid.  The
+        relieved coordinates are what shape scoring, receptor contacts, pharmacophore scores and the pair matrices read,
+        and what is returned.  For a molecule it moved, `pose` is the composed transform (returned = generated @ rotation
+        + translation still holds) and `overlay_tanimoto` the shape Tanimoto of the pose as placed, on the reference's own
+        grid; the Mols are moved with every conformer position, hydrogens included.  An unmoved molecule keeps every bit.
+        Records carry `relief_rmsd` (A the heavy atoms moved; 0.0 where nothing moved) and `receptor_clashes_before` (the
+        clash count of the pose before the relief), the Mols the double / int properties of those names; None (no
+        property) in a call without it and where posing failed.  `receptor_clashes` / `receptor_max_overlap` keep their
+        meaning: the contacts of the returned coordinates.
         `chemical_scores=True`: the chemical half of `evaluate_samples`, RDKit-free.  Every returned molecule carries
         `chemical_tanimoto` - the Tanimoto of its chemical fingerprint with the reference graph's - and `graph_key`, the
         unsigned 64-bit identity key of its molecular graph (records: the properties of those names; Mols: the double
@@ -622,7 +647,8 @@ class MLConformerGenerator(torch.nn.Module):
         outside 3..64 heavy atoms, top_k < 1, a threshold outside [0, 1], max_pairwise_tanimoto outside (0, 1] or without
         overlay, refine_overlay other than True or an integer in 1..1024 or without overlay, a receptor without overlay,
         one `load_receptor` refuses or one that holds the reference (a reference heavy atom within 0.5 A of a receptor
-        heavy atom), max_receptor_clashes other than an integer >= 0 or without a receptor, a custom finisher, a
+        heavy atom), max_receptor_clashes other than an integer >= 0 or without a receptor, relieve_clashes other than
+        False, True or an integer in 1..1024 or without a receptor, a custom finisher, a
         `reference_shape` together with another reference, with `refine_overlay` or with a `receptor`, or without
         `n_atoms`, a mesh `load_mesh` refuses ("The mesh needs to be watertight."), a `shape_density` that is not a positive
         real number, max_atoms_outside other than an integer >= 0, without a `reference_shape` or without overlay, and
@@ -639,7 +665,7 @@ class MLConformerGenerator(torch.nn.Module):
                                         chemical_scores, reference_graph, max_chemical_tanimoto, unique,
                                         max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
                                         reference_context, relax_geometry, pharmacophore_scores,
-                                        reference_pharmacophore, min_pharmacophore_tanimoto, rank_by)
+                                        reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         keyed = () if sample_seed is None else (sample_seed, None)   # unseeded: the positional call of before
@@ -672,7 +698,7 @@ class MLConformerGenerator(torch.nn.Module):
                                     shape_density: float = 0.02, max_atoms_outside: Optional[int] = None,
                                     relax_geometry: Union[bool, int] = False, pharmacophore_scores: bool = False,
                                     reference_pharmacophore=None, min_pharmacophore_tanimoto: Optional[float] = None,
-                                    rank_by: str = "shape") -> List:
+                                    rank_by: str = "shape", relieve_clashes: Union[bool, int] = False) -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -691,11 +717,11 @@ class MLConformerGenerator(torch.nn.Module):
         `shape_scores`, `top_k`, `min_shape_tanimoto`, `overlay`, `max_pairwise_tanimoto`, `refine_overlay`, `receptor`,
         `max_receptor_clashes`, `chemical_scores`, `reference_graph`, `max_chemical_tanimoto`, `unique`,
         `max_pairwise_chemical_tanimoto`, `reference_shape`, `shape_density`, `max_atoms_outside`, `relax_geometry`,
-        `pharmacophore_scores`, `reference_pharmacophore`, `min_pharmacophore_tanimoto`, `rank_by`: as in
+        `pharmacophore_scores`, `reference_pharmacophore`, `min_pharmacophore_tanimoto`, `rank_by`, `relieve_clashes`: as in
         `generate_conformers` (every rank loads the mesh and computes its occupancy itself).  The fingerprints are computed behind the gather,
         on the rows a rank returns: with gather="all" uniqueness and chemical diversity hold over the whole batch, with
         gather="rank0" within each other rank's own shard, like the rest of the selection.
-        Every rank poses, scores and measures the receptor contacts of ITS OWN shard on its own GPU before the gather
+        Every rank poses, relieves, scores and measures the receptor contacts of ITS OWN shard on its own GPU before the gather
         (posed coordinates, poses, scores and contacts travel as per-sample result tensors, or next to the finished
         Mols).  The selection runs on the rows a rank
         returns: with gather="all" every rank selects from the whole batch (the pair matrix of the whole batch on its own
@@ -711,7 +737,7 @@ class MLConformerGenerator(torch.nn.Module):
                                         chemical_scores, reference_graph, max_chemical_tanimoto, unique,
                                         max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
                                         reference_context, relax_geometry, pharmacophore_scores,
-                                        reference_pharmacophore, min_pharmacophore_tanimoto, rank_by)
+                                        reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)

@@ -51,6 +51,8 @@ class Measured:
     strain_after: Optional[float] = None
     pharmacophore_tanimoto: Optional[float] = None
     pharmacophore_matches: Optional[int] = None
+    relief_rmsd: Optional[float] = None
+    receptor_clashes_before: Optional[int] = None
 
 
 _UNMEASURED = Measured()          # shared by every record that carries no values: never written to
@@ -60,8 +62,8 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
     """The records of n samples from per-sample tensors by field name of `Measured` (a name left out or None: not
     measured), one D2H copy each.  The one place that reads the tensors' spellings of "not measured": a negative
     `receptor_clashes` (both contact values None), a negative `atoms_outside`, a `pose` row [12] with a non-finite entry
-    (`overlay_tanimoto` keeps its NaN), a negative `pharmacophore_matches` (both pharmacophore values None); `graph_key` is
-    int64 holding the unsigned bit pattern."""
+    (`overlay_tanimoto` keeps its NaN), a negative `pharmacophore_matches` (both pharmacophore values None), a negative
+    `receptor_clashes_before` (both relief values None); `graph_key` is int64 holding the unsigned bit pattern."""
     cols = {k: v.cpu().tolist() for k, v in values.items() if v is not None and k != "pose"}
     if values.get("pose") is not None:
         poses = values["pose"].cpu().to(torch.float32)
@@ -75,6 +77,11 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
     if "pharmacophore_matches" in cols:
         missing = [c < 0 for c in cols["pharmacophore_matches"]]
         for k in ("pharmacophore_matches", "pharmacophore_tanimoto"):
+            if k in cols:
+                cols[k] = [None if gone else v for gone, v in zip(missing, cols[k])]
+    if "receptor_clashes_before" in cols:
+        missing = [c < 0 for c in cols["receptor_clashes_before"]]
+        for k in ("receptor_clashes_before", "relief_rmsd"):
             if k in cols:
                 cols[k] = [None if gone else v for gone, v in zip(missing, cols[k])]
     if "graph_key" in cols:
@@ -100,7 +107,9 @@ class GeneratedMolecule:
     after the relaxation of a call with `relax_geometry`, else None.
     `pharmacophore_tanimoto` / `pharmacophore_matches`: the overlap of its pharmacophore features with the reference's and
     the reference features it matches (`pharmacophore.py`: the package's own definition) when the call asked for
-    `pharmacophore_scores`, else None."""
+    `pharmacophore_scores`, else None.
+    `relief_rmsd` / `receptor_clashes_before`: how far the clash relief of a call with `relieve_clashes` moved it and the
+    clashes of its pose before that (`receptor.py`: the package's own procedure), else None."""
     __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_measured")
 
     def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True,
@@ -117,6 +126,19 @@ class GeneratedMolecule:
         m._sid = b if sample_id is None else sample_id
         m._measured = measured
         return m
+
+    @property
+    def relief_rmsd(self) -> Optional[float]:
+        """How far, as a heavy-atom RMSD in A, the clash relief moved this molecule as a rigid body out of its contacts
+        with the call's receptor (`receptor.relieve_clashes`: the package's own procedure - not a docking score, not a
+        force field); 0.0 where it did not move.  None in a call without `relieve_clashes`, and where posing failed."""
+        return self._measured.relief_rmsd
+
+    @property
+    def receptor_clashes_before(self) -> Optional[int]:
+        """`receptor_clashes` of the pose before the clash relief of a call with `relieve_clashes` (`receptor_clashes`
+        itself describes the returned coordinates); None in a call without it, and where posing failed."""
+        return self._measured.receptor_clashes_before
 
     @property
     def pharmacophore_tanimoto(self) -> Optional[float]:
@@ -383,7 +405,9 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                            atoms_outside: Optional[torch.Tensor] = None, strain_before: Optional[torch.Tensor] = None,
                            strain_after: Optional[torch.Tensor] = None,
                            pharmacophore_tanimoto: Optional[torch.Tensor] = None,
-                           pharmacophore_matches: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
+                           pharmacophore_matches: Optional[torch.Tensor] = None,
+                           relief_rmsd: Optional[torch.Tensor] = None,
+                           receptor_clashes_before: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
     (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
     (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records).
@@ -396,7 +420,10 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     `strain_before[b]` / `strain_after[b]`: row b's force-field energy before and after the relaxation of a call with
     `relax_geometry` (both or neither; None: a call that did not relax).  `pharmacophore_tanimoto[b]` /
     `pharmacophore_matches[b]`: row b's pharmacophore overlap with the reference and matched reference features (negative
-    matches: not measured, the record gets None for both; None: a call without `pharmacophore_scores`).  The value keywords are the fields of `Measured`
+    matches: not measured, the record gets None for both; None: a call without `pharmacophore_scores`).
+    `relief_rmsd[b]` / `receptor_clashes_before[b]`: how far the clash relief moved row b and its clashes before it (a
+    negative count: its pose failed, the record gets None for both; None: a call without `relieve_clashes`).
+    The value keywords are the fields of `Measured`
     and go to `measured_from_tensors`; a call with no ids and no values builds the views and nothing else."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
     view = GeneratedMolecule._view
@@ -404,7 +431,8 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                   receptor_clashes=receptor_clashes, receptor_max_overlap=receptor_max_overlap,
                   atoms_outside=atoms_outside, chemical_tanimoto=chemical_tanimoto, graph_key=graph_key,
                   strain_before=strain_before, strain_after=strain_after,
-                  pharmacophore_tanimoto=pharmacophore_tanimoto, pharmacophore_matches=pharmacophore_matches)
+                  pharmacophore_tanimoto=pharmacophore_tanimoto, pharmacophore_matches=pharmacophore_matches,
+                  relief_rmsd=relief_rmsd, receptor_clashes_before=receptor_clashes_before)
     if sample_ids is None and all(v is None for v in values.values()):
         return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
     flags = valid.cpu().tolist()

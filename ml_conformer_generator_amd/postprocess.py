@@ -6,7 +6,9 @@ Stages, in this order:
   BEFORE the gather, on the rank that generated the shard, one batched device call each (`measure_tensors` on the result
   tensors where no finisher runs, `measure_finished` on the finished Mols' heavy atoms where one does):
     1. pose onto the reference (`overlay`, refined with `refine_overlay`) - a conformer, or the solid of a
-       `reference_shape` mesh, which also counts the posed atoms outside it;
+       `reference_shape` mesh, which also counts the posed atoms outside it; right behind it, with `relieve_clashes`, the
+       posed rows are moved out of their receptor contacts (`relieve_rows`), and everything below reads - and the call
+       returns - the relieved coordinates;
     2. shape score of the RETURNED coordinates (`shape_scores`, or implied by a shape selection);
     3. receptor contacts of the returned coordinates (`receptor`).
   BEHIND the gather, on the rows a rank returns (`return_records` / `return_finished`):
@@ -23,7 +25,8 @@ Stages, in this order:
 A call with no option on takes none of these steps: its records / live Mols are returned as they come.
 
 The device work goes through the generator's seams (`_pose`, `_score`, `_pair`, `_receptor_coords`,
-`_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, `_pharm_perceive`, `_pharm_score`), looked up on the instance at the time of the call.  The shape
+`_relieve`, `_score_placed`, `_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, `_pharm_perceive`, `_pharm_score`),
+looked up on the instance at the time of the call.  The shape
 seams take the request's reference object; which kind it is - a conformer or a solid - is `cheminformatics`' business."""
 from __future__ import annotations
 
@@ -56,6 +59,7 @@ class Request:
     refine_steps: int = 0                         # `refine_overlay`: ascent steps of the refined pose, 0 = not refined
     receptor: Optional[tuple] = None              # (coords [R,3] fp32, atomic numbers [R]) of its heavy atoms, host
     max_receptor_clashes: Optional[int] = None
+    relief_steps: int = 0                         # `relieve_clashes`: trials of the clash relief, 0 = not relieved
     ref_graph: Optional[tuple] = None             # (atomic numbers, bond codes [n,n] int8) of the reference, when it scores
     scores_chemistry: bool = False                # `chemical_scores`, or implied by `max_chemical_tanimoto`
     max_chemical_tanimoto: Optional[float] = None
@@ -110,7 +114,7 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
                   shape_density: float = 0.02, max_atoms_outside: Optional[int] = None,
                   reference_context=None, relax_geometry: Union[bool, int] = False, pharmacophore_scores=False,
                   reference_pharmacophore=None, min_pharmacophore_tanimoto: Optional[float] = None,
-                  rank_by: str = "shape") -> Request:
+                  rank_by: str = "shape", relieve_clashes: Union[bool, int] = False) -> Request:
     """The public option keywords of a generation entry of `gen` as a `Request`: the shape options first, then the chemical
     ones (`top_k` / `min_shape_tanimoto` / `max_pairwise_tanimoto` imply the shape score, `max_chemical_tanimoto` the
     chemical one).  `reference_shape`: a watertight mesh in place of the reference conformer (`mesh.load_mesh`); the
@@ -119,7 +123,8 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     `pharmacophore_scores` (implied by `min_pharmacophore_tanimoto`) needs `overlay`; the reference's features are
     `reference_pharmacophore` (`pharmacophore.load_reference_features`) or are perceived, behind the generation, from the
     reference's graph (`reference_graph`, else a reference conformer with bonds) at the reference conformer's coordinates.
-    `rank_by="combo"` needs the shape and the pharmacophore score.
+    `rank_by="combo"` needs the shape and the pharmacophore score.  `relieve_clashes`: `receptor.check_relief_steps`
+    (True = `receptor.RELIEF_STEPS`); it needs a `receptor`, and with it `overlay`.
     Every refusal happens here, before any device work."""
     relax_steps = mcg_geometry.check_steps(relax_geometry)
     custom_finisher = isinstance(getattr(gen, "finisher", None), host_pool.TaskRef)
@@ -151,6 +156,12 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
         mcg_receptor.check_max_receptor_clashes(max_receptor_clashes)
         if receptor is None:
             raise ValueError("max_receptor_clashes needs a receptor")
+    relief_steps = 0
+    if relieve_clashes is not False:
+        relief_steps = mcg_receptor.check_relief_steps(relieve_clashes, "relieve_clashes", lowest=1,
+                                                       if_true=mcg_receptor.RELIEF_STEPS)
+        if receptor is None:
+            raise ValueError("relieve_clashes needs a receptor: it moves the posed molecules out of their contacts with it")
     if receptor is not None and not overlay:
         raise ValueError("receptor needs overlay=True: molecules that are not posed onto the reference are not in "
                          "the receptor's frame")
@@ -185,7 +196,8 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
             mcg_receptor.check_clear_of_reference(rec[0], common["reference"].coords)
         shape = dict(overlay=bool(overlay), scores_shape=bool(scoring), top_k=top_k,
                      min_shape_tanimoto=min_shape_tanimoto, max_pairwise_tanimoto=max_pairwise_tanimoto,
-                     refine_steps=refine_steps, receptor=rec, max_receptor_clashes=max_receptor_clashes)
+                     refine_steps=refine_steps, receptor=rec, max_receptor_clashes=max_receptor_clashes,
+                     relief_steps=relief_steps)
 
     mcg_pharm.check_flag("pharmacophore_scores", pharmacophore_scores)
     if min_pharmacophore_tanimoto is not None:
@@ -338,11 +350,49 @@ def _index(rows: Rows, device) -> torch.Tensor:
     return torch.tensor(rows.row, dtype=torch.long, device=device)
 
 
+def compose_pose(pose: torch.Tensor, rotation: torch.Tensor, translation: torch.Tensor) -> torch.Tensor:
+    """[B,12]: the pose (Q, d) followed by the rigid move (R, t) as one transform, (Q R, d R + t), so that
+    x @ (Q R) + (d R + t) = (x @ Q + d) @ R + t.  `pose` [B,12] rotation row-major then translation, `rotation` [B,3,3],
+    `translation` [B,3]; every product written out in a fixed order."""
+    Q, d = pose[:, :9].reshape(-1, 3, 3), pose[:, 9:]
+    QR = (Q[:, :, 0:1] * rotation[:, 0:1, :] + Q[:, :, 1:2] * rotation[:, 1:2, :]) + Q[:, :, 2:3] * rotation[:, 2:3, :]
+    dR = (d[:, 0:1] * rotation[:, 0, :] + d[:, 1:2] * rotation[:, 1, :]) + d[:, 2:3] * rotation[:, 2, :]
+    return torch.cat([QR.reshape(-1, 9), dR + translation], dim=1)
+
+
+def relieve_rows(gen, req: Request, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_numbers: torch.Tensor,
+                 pose: torch.Tensor, tanimoto: torch.Tensor) -> dict:
+    """The clash relief of posed, padded rows (`relieve_clashes`), shared by both paths: the clash count of the pose as it
+    came (`_receptor_coords`), one `_relieve` call over all rows and - for the rows it moved - the composed pose and the
+    shape Tanimoto of the pose as placed (`_score_placed`).  `pose` [B,12] (a row with a non-finite entry: posing failed,
+    the row is not in the receptor's frame and is left alone), `tanimoto` [B] the pose's score.  Returns tensors on the
+    device of the relief's result: `coords`, `pose`, `overlay_tanimoto` (an unmoved row keeps every bit of what came in),
+    `moved` [B] bool, `rotation` / `translation` of the move itself, `relief_rmsd` (0 where nothing moved, NaN where
+    posing failed) and `receptor_clashes_before` (-1 where posing failed)."""
+    before = mcg_receptor.clash_summary(gen._receptor_coords(req.receptor, coords, n_nodes, atomic_numbers))[0]
+    out = gen._relieve(req.receptor, coords, n_nodes, atomic_numbers, req.relief_steps)
+    dev = out["coords"].device
+    x, pose, tanimoto = coords.to(dev, torch.float32), pose.to(dev, torch.float32), tanimoto.to(dev, torch.float32)
+    posed = torch.isfinite(pose).all(dim=1)
+    moved = out["moved"].to(dev) & posed
+    width = x.shape[1]
+    new_x = torch.where(moved.view(-1, 1, 1), out["coords"][:, :width], x)
+    rescored = gen._score_placed(req.reference, new_x, n_nodes).to(dev)
+    before = before.to(dev)
+    return dict(coords=new_x, moved=moved, rotation=out["rotation"], translation=out["translation"],
+                pose=torch.where(moved.view(-1, 1), compose_pose(pose, out["rotation"], out["translation"]), pose),
+                overlay_tanimoto=torch.where(moved, rescored, tanimoto),
+                relief_rmsd=torch.where(posed, torch.where(moved, out["rmsd"], torch.zeros_like(out["rmsd"])),
+                                        torch.full_like(out["rmsd"], float("nan"))),
+                receptor_clashes_before=torch.where(posed, before, torch.full_like(before, -1)))
+
+
 # ----------------------------------------------------------------------------------------------- without a finisher
 def measure_tensors(gen, req: Request, res: dict) -> dict:
     """Stages 1-3 on one shard's result tensors.  `res` with `x` posed and the per-sample tensors `overlay_tanimoto`,
-    `pose`, `shape_tanimoto`, `receptor_clashes` (-1 where posing failed), `receptor_max_overlap` (NaN there) and - posed
-    into a mesh - `atoms_outside` added, as far as the call asked: the spellings `handoff.measured_from_tensors` reads,
+    `pose`, `shape_tanimoto`, `receptor_clashes` (-1 where posing failed), `receptor_max_overlap` (NaN there), - posed
+    into a mesh - `atoms_outside` and - relieved - `relief_rmsd` (NaN where posing failed) and `receptor_clashes_before`
+    (-1 there) added, as far as the call asked: the spellings `handoff.measured_from_tensors` reads,
     which cross the tensor gather."""
     if req.overlay:
         ov = gen._pose(req.reference, res["x"], res["n_nodes"], req.refine_steps)
@@ -350,6 +400,10 @@ def measure_tensors(gen, req: Request, res: dict) -> dict:
                    pose=torch.cat([ov["rotation"].reshape(-1, 9), ov["translation"].reshape(-1, 3)], dim=1))
         if "atoms_outside" in ov:
             res["atoms_outside"] = ov["atoms_outside"]
+    if req.relief_steps:
+        rel = relieve_rows(gen, req, res["x"], res["n_nodes"], res["elements"], res["pose"], res["overlay_tanimoto"])
+        res = dict(res, x=rel["coords"], pose=rel["pose"], overlay_tanimoto=rel["overlay_tanimoto"],
+                   relief_rmsd=rel["relief_rmsd"], receptor_clashes_before=rel["receptor_clashes_before"])
     if req.scores_shape:
         res = dict(res, shape_tanimoto=gen._score(req.reference, res["x"], res["n_nodes"]))
     if req.receptor is not None:
@@ -419,6 +473,38 @@ def score_mols(gen, reference, mols: List) -> List[Optional[float]]:
     return out
 
 
+def _heavy_numbers(mols: List, width: int) -> torch.Tensor:
+    """[B, width] int64: the heavy atoms' `GetAtomicNum()` of each Mol, zero padded."""
+    z = torch.zeros(len(mols), width, dtype=torch.long)
+    for j, m in enumerate(mols):
+        heavy = [a.GetAtomicNum() for a in m.GetAtoms() if a.GetAtomicNum() != 1]
+        z[j, : len(heavy)] = torch.tensor(heavy, dtype=torch.long)
+    return z
+
+
+def _relieve_mols(gen, req: Request, mols: List, measured: List[Measured]) -> None:
+    """The clash relief of the posed Mols (`relieve_rows` on their heavy atoms, one batched call): a moved Mol has every
+    conformer position, hydrogens included, moved by the relief's transform (`cheminformatics.apply_pose`), and its
+    `Measured` gets the composed pose and the rescored `overlay_tanimoto`; every posed Mol's gets `relief_rmsd` and
+    `receptor_clashes_before`."""
+    live = [k for k, m in enumerate(mols) if m is not None and measured[k].pose is not None]
+    if not live:
+        return
+    coords, n = _heavy_coords([mols[k] for k in live])
+    rel = relieve_rows(gen, req, coords, n, _heavy_numbers([mols[k] for k in live], coords.shape[1]),
+                       torch.stack([measured[k].pose for k in live]),
+                       torch.tensor([measured[k].overlay_tanimoto for k in live], dtype=torch.float32))
+    rel = {k: v.cpu() for k, v in rel.items()}
+    for j, k in enumerate(live):
+        m = measured[k]
+        m.relief_rmsd, m.receptor_clashes_before = float(rel["relief_rmsd"][j]), int(rel["receptor_clashes_before"][j])
+        if bool(rel["moved"][j]):
+            cheminformatics.apply_pose(mols[k], rel["rotation"][j], rel["translation"][j])
+            m.pose, m.overlay_tanimoto = rel["pose"][j].clone(), float(rel["overlay_tanimoto"][j])
+            if hasattr(mols[k], "SetDoubleProp"):
+                mols[k].SetDoubleProp("overlay_tanimoto", m.overlay_tanimoto)
+
+
 def _contact_mols(gen, rec: tuple, mols: List, posed: List[bool]) -> List[Optional[tuple]]:
     """(receptor_clashes, receptor_max_overlap) of posed Mols' heavy atoms (elements from `GetAtomicNum()`), in ONE
     batched device call; None where a Mol was dropped or its pose failed (it is not in the receptor's frame)."""
@@ -426,10 +512,7 @@ def _contact_mols(gen, rec: tuple, mols: List, posed: List[bool]) -> List[Option
     out: List[Optional[tuple]] = [None] * len(mols)
     if live:
         coords, n = _heavy_coords([mols[k] for k in live])
-        z = torch.zeros(coords.shape[0], coords.shape[1], dtype=torch.long)
-        for j, k in enumerate(live):
-            heavy = [a.GetAtomicNum() for a in mols[k].GetAtoms() if a.GetAtomicNum() != 1]
-            z[j, : len(heavy)] = torch.tensor(heavy, dtype=torch.long)
+        z = _heavy_numbers([mols[k] for k in live], coords.shape[1])
         clashes, worst = mcg_receptor.clash_summary(gen._receptor_coords(rec, coords, n, z))
         for j, (c, w) in enumerate(zip(clashes.cpu().tolist(), worst.cpu().tolist())):
             out[live[j]] = (int(c), float(w))
@@ -438,9 +521,10 @@ def _contact_mols(gen, rec: tuple, mols: List, posed: List[bool]) -> List[Option
 
 def measure_finished(gen, req: Request, done: List, res: Optional[dict] = None) -> List[Finished]:
     """Stages 1-3 on one shard's finished Mols (None = dropped), each in ONE batched device call: pose, every conformer
-    position moved (`cheminformatics.pose_mols`), then score (`score_mols`), then the receptor contacts of the posed
-    Mols.  Per sample the Mol with its `Measured`: None where the call did not ask, the Mol was dropped or - contacts and
-    atoms outside the mesh - its pose failed.  `res`: the shard's result tensors; where the call relaxed, its
+    position moved (`cheminformatics.pose_mols`), then - `relieve_clashes` - the posed Mols moved out of their receptor
+    contacts (`_relieve_mols`), then score (`score_mols`), then the receptor contacts of the posed Mols.  Per sample the
+    Mol with its `Measured`: None where the call did not ask, the Mol was dropped or - contacts, relief and atoms outside
+    the mesh - its pose failed.  `res`: the shard's result tensors; where the call relaxed, its
     `strain_before` / `strain_after` join every sample's values."""
     measured = [Measured() for _ in done]
     live = [k for k, m in enumerate(done) if m is not None]
@@ -458,6 +542,8 @@ def measure_finished(gen, req: Request, done: List, res: Optional[dict] = None) 
             counts = measured_from_tensors(dict(atoms_outside=ov["atoms_outside"]), len(live))
             for k, c in zip(live, counts):
                 measured[k].atoms_outside = c.atoms_outside
+    if req.relief_steps:
+        _relieve_mols(gen, req, done, measured)
     if req.scores_shape:
         for m, score in zip(measured, score_mols(gen, req.reference, done)):
             m.shape_tanimoto = score

@@ -152,7 +152,7 @@ def tag_sample_ids(mols: Sequence, sample_ids: Sequence[int]) -> None:
 MEASURED_PROPS = dict(shape_tanimoto="double", overlay_tanimoto="double", receptor_clashes="int",
                       receptor_max_overlap="double", atoms_outside="int", chemical_tanimoto="double", graph_key="string",
                       strain_before="double", strain_after="double", pharmacophore_tanimoto="double",
-                      pharmacophore_matches="int")
+                      pharmacophore_matches="int", relief_rmsd="double", receptor_clashes_before="int")
 _SETTERS = {"int": ("SetIntProp", int), "double": ("SetDoubleProp", float), "string": ("SetProp", lambda k: str(int(k)))}
 
 

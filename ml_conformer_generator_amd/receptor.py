@@ -8,6 +8,30 @@ allowance: no donors or acceptors are typed).  Per molecule: `receptor_clashes` 
 
 The radii are one table keyed by atomic number (`VDW_RADII`): Bondi (1964) where Bondi gives a value, Mantina et al.
 (2009) for boron, DEFAULT_RADIUS for every other element.  The kernel (`mcg_receptor_overlap`) sees radii only.
+
+Clash relief (`relieve_clashes`, kernel `mcg_receptor_relieve`; DESIGN.md section 6, "Clash relief").  The package's own,
+labelled procedure: NOT a docking score and NOT a force field - no attraction term, no trade of shape against fit.  It
+walks a posed molecule, as a rigid body, to the nearest clash-free pose it finds and stops there; a molecule for which it
+finds none ends with a lower penalty and is reported as it is.  Heavy atoms only, radii `VDW_RADII`.
+  Contact depth   h_ij = max(0, (r_i + r_j - RELIEF_MARGIN) - |x_i - y_j|), RELIEF_MARGIN = 0.4 A: 0.2 A under
+                  CLASH_OVERLAP, so a pose with P = 0 has no clashing atom by the criterion above, with 0.2 A to spare.
+  Penalty         P = sum_ij h_ij^2.
+  Force, torque   F_i = sum_j 2 h_ij (x_i - y_j) / |x_i - y_j| (the direction is 0 where the distance is 0), F = sum_i F_i,
+                  tau = sum_i (x_i - p) x F_i about the ligand's current atom centroid p.
+  Motion          x' = (x - c) @ G + p: c the input pose's atom centroid, G a proper rotation applied to row vectors;
+                  the start is G = I, p = c.
+  Step rule       the refined pose's rule (`shape_overlay(refine_steps=...)`) turned downhill.  A trial rotates by s_r
+                  about tau / |tau| and translates by s_t along F / |F|; it is kept only if P strictly decreases, then s_r
+                  and s_t are multiplied by 1.2, otherwise by 0.5.  A trial whose centroid would lie more than `max_shift`
+                  (default 2.0 A) from c is rejected the same way.  The walk starts from s_r = 0.05 rad, s_t = 0.25 A,
+                  takes `steps` trials and stops early only when P == 0 (force and torque are then exactly zero).
+  Finish          G is re-orthonormalised (Gram-Schmidt, rows, third = first x second) as each trial is formed, so the
+                  pose whose P was evaluated is, bit for bit, the pose returned and there is nothing left to do at the
+                  end.  A molecule no trial of which was kept - one whose start has P == 0 included - is returned bit for
+                  bit: its coordinates, rotation = I, translation = 0.  A molecule with no atoms or a non-finite
+                  coordinate is left exactly as it came, with NaN transform and stats; the other rows are unaffected.
+A molecule's result depends on its own atoms and the receptor's atoms only: the same bits in any batch, at any row, at any
+padded width, with and without tile skipping, and whatever the order the receptor's atoms were listed in.
 """
 from __future__ import annotations
 
@@ -28,6 +52,11 @@ _MAX_SPLITS = 256              # MCG_RECEPTOR_MAX_SPLITS
 _TILE = 256                    # receptor atoms per LDS tile of the kernel
 _TARGET_WORKGROUPS = 1024      # four 256-lane workgroups per CU of the MI355X
 DEFAULT_RADIUS = 2.00
+RELIEF_MARGIN = 0.4            # angstrom: a contact starts 0.2 A under CLASH_OVERLAP
+RELIEF_STEPS = 32              # what `relieve_clashes=True` stands for
+MAX_RELIEF_STEPS = 1024        # csrc/mcg_receptor_relief.hip RL_MAX_STEPS
+RELIEF_MAX_SHIFT = 2.0         # angstrom: how far the walk may carry a molecule's centroid
+_SORT_CELL = 4.0               # angstrom: edge of the cells the receptor is sorted by, so that a tile is compact
 
 # Z -> van der Waals radius (angstrom).  A. Bondi, J. Phys. Chem. 68, 441 (1964), Table I, for every element it lists;
 # boron (the one element of config.ELEMENTS Bondi lacks): M. Mantina et al., J. Phys. Chem. A 113, 5806 (2009).
@@ -165,6 +194,56 @@ def check_max_receptor_clashes(value) -> int:
     return int(k)
 
 
+def check_relief_steps(value, name: str = "steps", lowest: int = 0, if_true: Optional[int] = None) -> int:
+    """A trial budget of the clash relief as an int in `lowest`..MAX_RELIEF_STEPS (an integer type, not a bool), else a
+    ValueError that names `name`.  `if_true`: the budget True stands for, where the option accepts True
+    (`relieve_clashes`: RELIEF_STEPS, with `lowest` 1)."""
+    if value is True and if_true is not None:
+        return if_true
+    try:
+        k = None if isinstance(value, bool) else operator.index(value)
+    except TypeError:
+        k = None
+    if k is None or not (lowest <= k <= MAX_RELIEF_STEPS):
+        what = "an integer" if if_true is None else "True or an integer step budget"
+        raise ValueError(f"{name} must be {what} in {lowest}..{MAX_RELIEF_STEPS}, got {value!r}")
+    return int(k)
+
+
+def _spread_bits(v: torch.Tensor) -> torch.Tensor:
+    """The low 10 bits of each int64 spread to every third bit (the Morton code's one axis)."""
+    v = v & 0x3FF
+    v = (v | (v << 16)) & 0x30000FF
+    v = (v | (v << 8)) & 0x300F00F
+    v = (v | (v << 4)) & 0x30C30C3
+    return (v | (v << 2)) & 0x9249249
+
+
+def sort_receptor(rec_xyz: torch.Tensor, rec_radius: torch.Tensor) -> torch.Tensor:
+    """The receptor as the relief kernel reads it: [R,4] fp32 (x, y, z, radius) on the host, sorted so that 256 consecutive
+    atoms - one tile - are close in space: by the Morton code of the atom's cell (edge _SORT_CELL, counted from the
+    smallest coordinate; cells beyond 1 024 per axis share the last), ties by x, y, z, radius.  One stable sort on the
+    cell key over that canonical order, once per receptor; the result does not depend on the order the atoms came in."""
+    xyzr = torch.cat([rec_xyz.to(torch.float32).reshape(-1, 3), rec_radius.to(torch.float32).reshape(-1, 1)], dim=1).cpu()
+    for col in (3, 2, 1, 0):                                        # the canonical order: lexicographic (x, y, z, radius)
+        xyzr = xyzr[torch.sort(xyzr[:, col], stable=True).indices]
+    cell = ((xyzr[:, :3] - xyzr[:, :3].min(dim=0).values) / _SORT_CELL).floor().to(torch.long).clamp_(0, 1023)
+    key = _spread_bits(cell[:, 0]) | (_spread_bits(cell[:, 1]) << 1) | (_spread_bits(cell[:, 2]) << 2)
+    return xyzr[torch.sort(key, stable=True).indices].contiguous()
+
+
+def tile_spheres(xyzr: torch.Tensor) -> torch.Tensor:
+    """[ceil(R / _TILE), 4] fp32: centre (the bounding box's) and radius of each tile of _TILE consecutive atoms of `xyzr`
+    [R,4]; the radius reaches the far side of every atom of the tile: max_j |y_j - centre| + r_j, rounded up."""
+    R = int(xyzr.shape[0])
+    T = -(-R // _TILE)
+    pad = torch.cat([xyzr, xyzr[-1:].expand(T * _TILE - R, 4)]).reshape(T, _TILE, 4)      # the last atom again: no effect
+    centre = (pad[:, :, :3].amin(dim=1) + pad[:, :, :3].amax(dim=1)) * 0.5
+    far = ((pad[:, :, :3] - centre[:, None, :]).double().norm(dim=2) + pad[:, :, 3].double()).amax(dim=1)
+    radius = torch.nextafter(far.to(torch.float32), torch.full_like(far, math.inf, dtype=torch.float32))
+    return torch.cat([centre, radius[:, None]], dim=1).contiguous()
+
+
 # ----------------------------------------------------------------------------------------------- device
 def default_splits(B: int, N: int, R: int) -> int:
     """Receptor ranges per ligand block: enough workgroups to fill the GPU, at least one tile each."""
@@ -208,6 +287,63 @@ def receptor_overlap(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atom
                                                _lib.dptr(out), _lib.current_stream_ptr(dev)),
                "mcg_receptor_overlap")
     return out
+
+
+@torch.no_grad()
+def relieve_clashes(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_numbers: torch.Tensor,
+                    steps: int = RELIEF_STEPS, max_shift: float = RELIEF_MAX_SHIFT, device=None,
+                    return_gradient: bool = False, skip_tiles: bool = True) -> dict:
+    """Every molecule of the padded, posed coordinates `coords` [B,N,3] (`n_nodes` [B] real atoms, `atomic_numbers`
+    [B, >= N]) moved as a rigid body out of its contacts with `receptor` (what `load_receptor` takes), by the procedure of
+    this module's docstring, in one `mcg_receptor_relieve` call.  Returns device tensors:
+      coords [B,N,3]        the moved rows (padded rows zero);
+      rotation [B,3,3], translation [B,3]   with coords = input @ rotation + translation on the real rows;
+      penalty_before [B], penalty_after [B]  P at the input and at the returned pose;
+      accepted_steps [B] int32, rmsd [B]     trials kept, and the heavy-atom RMSD between input and output;
+      moved [B] bool        P before > 0 and at least one trial kept;
+      (return_gradient) gradient [B,6]       net force and torque at the input pose.
+    A molecule with no atoms or a non-finite coordinate: NaN rotation, translation, penalties, rmsd and gradient, 0
+    accepted steps, its rows as they came.  `skip_tiles`: whether a molecule's workgroup walks only the receptor tiles
+    within its reach; never a bit of the result.  Refused before any device work: what `receptor_overlap` refuses, `steps`
+    outside 0..MAX_RELIEF_STEPS, a bool or a non-integer, a `max_shift` that is negative or not finite."""
+    from .cheminformatics import check_n_nodes
+    steps = check_relief_steps(steps)
+    if isinstance(max_shift, bool) or not isinstance(max_shift, (int, float)) or not (
+            0.0 <= float(max_shift) < math.inf):
+        raise ValueError(f"max_shift must be a finite real number >= 0, got {max_shift!r}")
+    rec_xyz, rec_z = load_receptor(receptor)
+    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
+    B, N = int(coords.shape[0]), int(coords.shape[1])
+    check_n_nodes(n_nodes, B, N)
+    if N > MAX_LIGAND_ATOMS or B > MAX_BATCH:
+        raise ValueError(f"clash relief takes at most {MAX_BATCH} molecules of at most {MAX_LIGAND_ATOMS} atoms, got "
+                         f"[{B}, {N}]")
+    z = torch.as_tensor(atomic_numbers)
+    if z.dim() != 2 or z.shape[0] != B or z.shape[1] < N:
+        raise ValueError(f"atomic_numbers must be [B, >= N] = [{B}, >= {N}], got {list(z.shape)}")
+    x = coords.to(dev, torch.float32).contiguous()
+    out = torch.zeros(B, N, 3, device=dev)
+    xform = torch.full((B, 12), math.nan, device=dev)
+    stats = torch.full((B, 4), math.nan, device=dev)
+    grad = torch.full((B, 6), math.nan, device=dev) if return_gradient else None
+    if B > 0 and N > 0:
+        xyzr = sort_receptor(rec_xyz, vdw_radii(rec_z))
+        spheres = tile_spheres(xyzr).to(dev) if skip_tiles else None
+        rec = xyzr.to(dev)
+        lig_r = vdw_radii(z[:, :N].to(dev)).contiguous()
+        nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B).contiguous()
+        _lib.check(_lib.lib().mcg_receptor_relieve(_lib.dptr(x), _lib.dptr(lig_r), _lib.dptr(nn), B, N, _lib.dptr(rec),
+                                                   int(xyzr.shape[0]), _lib.dptr(spheres), steps, RELIEF_MARGIN,
+                                                   float(max_shift), _lib.dptr(out), _lib.dptr(xform), _lib.dptr(stats),
+                                                   _lib.dptr(grad), _lib.current_stream_ptr(dev)),
+                   "mcg_receptor_relieve")
+    accepted = torch.nan_to_num(stats[:, 2], nan=0.0).to(torch.int32)
+    res = dict(coords=out, rotation=xform[:, :9].reshape(B, 3, 3), translation=xform[:, 9:], penalty_before=stats[:, 0],
+               penalty_after=stats[:, 1], accepted_steps=accepted, rmsd=stats[:, 3],
+               moved=(stats[:, 0] > 0) & (accepted > 0))
+    if return_gradient:
+        res["gradient"] = grad
+    return res
 
 
 def clash_summary(overlap: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
