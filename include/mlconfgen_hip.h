@@ -642,6 +642,39 @@ int mcg_pharm_score(const float* coords, const int32_t* n_nodes_dev, const uint8
                     const float* ref_xyz, const uint8_t* ref_type, int F, const double* o_rr /*optional*/, double* o_rm,
                     double* o_mm, float* tanimoto, int32_t* matches, double* per_type /*optional [B,6]*/, void* stream);
 
+/* ---- Explicit hydrogens ("Explicit hydrogens"): how many hydrogens each heavy atom of B molecular
+ * graphs carries and where they sit.  The definition is this package's OWN (DESIGN.md states it in full): not RDKit's
+ * AddHs - no charges, no protonation states, no tautomer search.  The count is the pharmacophore perception's nH plus one
+ * aromatic N-H per aromatic 5-ring; a parent is linear, planar (conjugated N and O included) or tetrahedral by its bond
+ * codes; X-H = rcov(Z) + 0.31 A along ideal directions; a parent with one neighbour is a rotor whose torsion is the one of
+ * 12 (planar: 2) candidates that keeps its hydrogens clear of the other atoms.
+ *   mcg_hydrogens_place: coords[B,N,3] fp32 heavy-atom coordinates, z[B,W] atomic numbers, bonds[B,W,W] symmetric bond
+ *                       codes (1 / 2 / 3 / 4 aromatic; any other value is no bond), n_nodes_dev[b] real atoms (device
+ *                       memory, clamped to [0, min(N, W)] on the device; the diagonal and everything at or beyond n_b is
+ *                       ignored, whatever it holds); types[B,W], ring_mask[B, MCG_PHARM_MAX_RINGS] and n_rings[B] as
+ *                       mcg_pharm_perceive wrote them for the same z, bonds and n_nodes (passed in, not perceived again).
+ *                       h_xyz_out[B,HW,3]: the hydrogens in ascending order of the parent, then of m, zero beyond the
+ *                       row's count; h_parent_out[B,HW]: each hydrogen's heavy atom, -1 beyond the count;
+ *                       h_count_out[B,W]: the hydrogens placed on each heavy atom; n_h_out[b]: the row's count;
+ *                       unplaced_out[b]: the hydrogens the count rule gives atoms in a situation the definition places
+ *                       none for; rotor_delta_out[B,W] (optional, NULL = not wanted): the chosen torsion offset in
+ *                       degrees, -1 for an atom that is no rotor.  HW >= max(4, 3 W): an atom with a neighbour carries at
+ *                       most 3 hydrogens, a one-atom molecule at most 4 (an atom without a neighbour in a larger molecule
+ *                       gets none: they count as unplaced).  A row with a non-finite coordinate on a real atom has
+ *                       n_h = -1 and no hydrogens, the other rows unaffected.  A Z without a covalent radius is read with
+ *                       radius 0 (the Python layer refuses it before the launch).  One 64-lane workgroup per molecule,
+ *                       one launch, no atomics, fp32 with every product and sum rounded on its own and in one order: a
+ *                       molecule's outputs have the same bits whatever the batch, its row and the padded widths.
+ * B = 0 launches nothing.  MCG_ERR_ARG, nothing launched: a null required buffer, B outside 0..MCG_HYDROGENS_MAX_B, N < 1,
+ * W outside 1..MCG_HYDROGENS_MAX_ATOMS, HW < max(4, 3 W). */
+#define MCG_HYDROGENS_MAX_ATOMS 64
+#define MCG_HYDROGENS_MAX_B 16384
+int mcg_hydrogens_place(const float* coords, const int32_t* z, const int8_t* bonds, const int32_t* n_nodes_dev,
+                        const uint8_t* types, const uint64_t* ring_mask, const int32_t* n_rings, int B,
+                        int N /*coords row width*/, int W /*z, bonds, types width*/, int HW /*hydrogen slots per row*/,
+                        float* h_xyz_out, int32_t* h_parent_out, int32_t* h_count_out, int32_t* n_h_out,
+                        int32_t* unplaced_out, int32_t* rotor_delta_out /*optional [B,W]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,7 @@ from . import rdkit_order
 from . import receptor as mcg_receptor
 from . import fingerprint as mcg_fp
 from . import geometry as mcg_geometry
+from . import hydrogens as mcg_hydrogens
 from . import pharmacophore as mcg_pharm
 from .handoff import (GeneratedMolecule, assemble_molecules, bond_writeback_hip, molecules_from_tensors,
                       prepare_adj_mat_seer_input_hip)
@@ -357,6 +358,13 @@ class MLConformerGenerator(torch.nn.Module):
         out = mcg_pharm.score_features(reference_features, coords, n_nodes, types, ring_mask, n_rings, self.device)
         return out["tanimoto"], out["matches"]
 
+    # the hydrogen step
+    def _add_hydrogens(self, coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
+                       n_nodes: torch.Tensor) -> dict:
+        """The explicit hydrogens of padded heavy-atom coordinates and graphs (`hydrogens.add_hydrogens`, unchecked: the
+        elements come from the validated decoder, the codes from the bond write-back; device tensors)."""
+        return mcg_hydrogens.add_hydrogens(coords, atomic_numbers, bond_orders, n_nodes, self.device, check=False)
+
     # the geometry step
     def _relax_coords(self, coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
                       n_nodes: torch.Tensor, steps: int) -> dict:
@@ -526,7 +534,8 @@ class MLConformerGenerator(torch.nn.Module):
                             shape_density: float = 0.02, max_atoms_outside: Optional[int] = None,
                             relax_geometry: Union[bool, int] = False, pharmacophore_scores: bool = False,
                             reference_pharmacophore=None, min_pharmacophore_tanimoto: Optional[float] = None,
-                            rank_by: str = "shape", relieve_clashes: Union[bool, int] = False) -> List:
+                            rank_by: str = "shape", relieve_clashes: Union[bool, int] = False,
+                            add_hydrogens: bool = False) -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
@@ -638,6 +647,20 @@ class MLConformerGenerator(torch.nn.Module):
         `rank_by="combo"` (needs a shape score and the pharmacophore score; default "shape"): `unique`, the diversity walk
         and `top_k` rank by `shape_tanimoto + pharmacophore_tanimoto` instead of `shape_tanimoto`; `min_shape_tanimoto`
         still thresholds the shape score alone.
+        `add_hydrogens=True`: every returned record carries its explicit hydrogens - `hydrogen_coords` ([nH,3] fp32),
+        `hydrogen_parents` (the heavy atom of each, ascending) and `hydrogens_unplaced` (hydrogens the count rule gives to
+        atoms the placement has no direction for; 0 for an ordinary molecule) - placed on the GPU by the package's OWN
+        definition, NOT RDKit's AddHs (`hydrogens.add_hydrogens`; DESIGN.md section 6, "Explicit hydrogens"): the count
+        from the bond codes plus one aromatic N-H per 5-ring, ideal directions by the parent's hybridisation at rcov + 0.31
+        A, terminal groups turned to the torsion that keeps them clear of the other atoms; no charges, no tautomer search.
+        It runs last of the measuring stages, behind the gather, beside the pharmacophore step, on the rows a rank returns
+        and on the RETURNED coordinates - relaxed, posed, refined, relieved - so the hydrogens are in the frame of `coords`
+        and need no transform; it removes no molecule and changes no other value.  `to_molblock(hydrogens=True)` /
+        `to_xyz_block(hydrogens=True)` write the all-atom molecule.  With a `receptor` the records also carry
+        `receptor_hydrogen_clashes`: the hydrogens overlapping a receptor heavy atom by >= 0.6 A at the radius 1.20 A, by
+        the kernel of the heavy-atom contacts; None where posing failed; `receptor_clashes` / `receptor_max_overlap` keep
+        their heavy-atom meaning and no filter reads the hydrogens.  All of these are None in a call without the option,
+        and the three hydrogen fields where the molecule has a non-finite coordinate.
         Order of the stages: validity, `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`,
         `min_pharmacophore_tanimoto`, `unique`, then the selection (threshold, exclusion, `top_k`).  The filters only
         remove molecules.
@@ -656,8 +679,9 @@ class MLConformerGenerator(torch.nn.Module):
         pharmacophore_scores that is not a bool, without overlay or without a source of the reference's features, a
         `reference_pharmacophore` that `load_reference_features` refuses or that no option reads, a reference graph whose
         heavy-atom count differs from the reference conformer's, min_pharmacophore_tanimoto outside [0, 1], and a
-        `rank_by` other than "shape" or "combo", or "combo" without both scores.  A reference graph in which no feature is
-        found is refused where it is perceived, behind the generation."""
+        `rank_by` other than "shape" or "combo", or "combo" without both scores, and add_hydrogens that is not a bool or on
+        a generator with a finisher, RDKit's or a custom one (on Mols use `Chem.AddHs(mol, addCoords=True)`).  A reference
+        graph in which no feature is found is refused where it is perceived, behind the generation."""
         if sample_seed is not None:
             seeding.check_seed(sample_seed)
         req = postprocess.parse_request(self, reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
@@ -665,7 +689,8 @@ class MLConformerGenerator(torch.nn.Module):
                                         chemical_scores, reference_graph, max_chemical_tanimoto, unique,
                                         max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
                                         reference_context, relax_geometry, pharmacophore_scores,
-                                        reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes)
+                                        reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes,
+                                        add_hydrogens)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         keyed = () if sample_seed is None else (sample_seed, None)   # unseeded: the positional call of before
@@ -698,7 +723,8 @@ class MLConformerGenerator(torch.nn.Module):
                                     shape_density: float = 0.02, max_atoms_outside: Optional[int] = None,
                                     relax_geometry: Union[bool, int] = False, pharmacophore_scores: bool = False,
                                     reference_pharmacophore=None, min_pharmacophore_tanimoto: Optional[float] = None,
-                                    rank_by: str = "shape", relieve_clashes: Union[bool, int] = False) -> List:
+                                    rank_by: str = "shape", relieve_clashes: Union[bool, int] = False,
+                                    add_hydrogens: bool = False) -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -717,7 +743,8 @@ class MLConformerGenerator(torch.nn.Module):
         `shape_scores`, `top_k`, `min_shape_tanimoto`, `overlay`, `max_pairwise_tanimoto`, `refine_overlay`, `receptor`,
         `max_receptor_clashes`, `chemical_scores`, `reference_graph`, `max_chemical_tanimoto`, `unique`,
         `max_pairwise_chemical_tanimoto`, `reference_shape`, `shape_density`, `max_atoms_outside`, `relax_geometry`,
-        `pharmacophore_scores`, `reference_pharmacophore`, `min_pharmacophore_tanimoto`, `rank_by`, `relieve_clashes`: as in
+        `pharmacophore_scores`, `reference_pharmacophore`, `min_pharmacophore_tanimoto`, `rank_by`, `relieve_clashes`,
+        `add_hydrogens` (placed behind the gather, on the rows a rank returns): as in
         `generate_conformers` (every rank loads the mesh and computes its occupancy itself).  The fingerprints are computed behind the gather,
         on the rows a rank returns: with gather="all" uniqueness and chemical diversity hold over the whole batch, with
         gather="rank0" within each other rank's own shard, like the rest of the selection.
@@ -737,7 +764,8 @@ class MLConformerGenerator(torch.nn.Module):
                                         chemical_scores, reference_graph, max_chemical_tanimoto, unique,
                                         max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
                                         reference_context, relax_geometry, pharmacophore_scores,
-                                        reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes)
+                                        reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes,
+                                        add_hydrogens)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)

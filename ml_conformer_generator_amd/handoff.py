@@ -53,6 +53,10 @@ class Measured:
     pharmacophore_matches: Optional[int] = None
     relief_rmsd: Optional[float] = None
     receptor_clashes_before: Optional[int] = None
+    hydrogen_coords: Optional[object] = None      # [nH,3] fp32, host - or (batch [B,H,3], row, count), sliced on first read
+    hydrogen_parents: Optional[List[int]] = None
+    hydrogens_unplaced: Optional[int] = None
+    receptor_hydrogen_clashes: Optional[int] = None
 
 
 _UNMEASURED = Measured()          # shared by every record that carries no values: never written to
@@ -63,8 +67,13 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
     measured), one D2H copy each.  The one place that reads the tensors' spellings of "not measured": a negative
     `receptor_clashes` (both contact values None), a negative `atoms_outside`, a `pose` row [12] with a non-finite entry
     (`overlay_tanimoto` keeps its NaN), a negative `pharmacophore_matches` (both pharmacophore values None), a negative
-    `receptor_clashes_before` (both relief values None); `graph_key` is int64 holding the unsigned bit pattern."""
-    cols = {k: v.cpu().tolist() for k, v in values.items() if v is not None and k != "pose"}
+    `receptor_clashes_before` (both relief values None); `graph_key` is int64 holding the unsigned bit pattern.
+    The hydrogens of a call with `add_hydrogens` come as `hydrogen_coords` [n,H,3], `hydrogen_parents` [n,H] (-1 beyond a
+    row's count) and `hydrogens_unplaced` [n] (negative: the row had a non-finite coordinate, the record gets None for all
+    three); a record's `hydrogen_coords` is left as (the one host copy, row, count) and sliced on first read
+    (`GeneratedMolecule.hydrogen_coords`).  A negative `receptor_hydrogen_clashes`: not measured."""
+    hyd = {k: values.get(k) for k in ("hydrogen_coords", "hydrogen_parents")}
+    cols = {k: v.cpu().tolist() for k, v in values.items() if v is not None and k != "pose" and k not in hyd}
     if values.get("pose") is not None:
         poses = values["pose"].cpu().to(torch.float32)
         cols["pose"] = [poses[b] if ok else None for b, ok in enumerate(torch.isfinite(poses).all(dim=1).tolist())]
@@ -86,6 +95,15 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
                 cols[k] = [None if gone else v for gone, v in zip(missing, cols[k])]
     if "graph_key" in cols:
         cols["graph_key"] = [k & 0xFFFFFFFFFFFFFFFF for k in cols["graph_key"]]
+    if "receptor_hydrogen_clashes" in cols:
+        cols["receptor_hydrogen_clashes"] = [None if c < 0 else c for c in cols["receptor_hydrogen_clashes"]]
+    if "hydrogens_unplaced" in cols:
+        missing = [c < 0 for c in cols["hydrogens_unplaced"]]
+        cols["hydrogens_unplaced"] = [None if gone else c for gone, c in zip(missing, cols["hydrogens_unplaced"])]
+        xyz = hyd["hydrogen_coords"].cpu().to(torch.float32)
+        parents = [[p for p in row if p >= 0] for row in hyd["hydrogen_parents"].cpu().tolist()]
+        cols["hydrogen_parents"] = [None if gone else p for gone, p in zip(missing, parents)]
+        cols["hydrogen_coords"] = [None if gone else (xyz, b, len(p)) for b, (gone, p) in enumerate(zip(missing, parents))]
     return [Measured(**{k: col[b] for k, col in cols.items()}) for b in range(n)]
 
 
@@ -109,7 +127,10 @@ class GeneratedMolecule:
     the reference features it matches (`pharmacophore.py`: the package's own definition) when the call asked for
     `pharmacophore_scores`, else None.
     `relief_rmsd` / `receptor_clashes_before`: how far the clash relief of a call with `relieve_clashes` moved it and the
-    clashes of its pose before that (`receptor.py`: the package's own procedure), else None."""
+    clashes of its pose before that (`receptor.py`: the package's own procedure), else None.
+    `hydrogen_coords` / `hydrogen_parents` / `hydrogens_unplaced`: its explicit hydrogens when the call asked for
+    `add_hydrogens` (`hydrogens.py`: the package's own definition, NOT RDKit's AddHs), else None; with a receptor also
+    `receptor_hydrogen_clashes`.  `to_molblock(hydrogens=True)` / `to_xyz_block(hydrogens=True)` write them."""
     __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_measured")
 
     def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True,
@@ -126,6 +147,35 @@ class GeneratedMolecule:
         m._sid = b if sample_id is None else sample_id
         m._measured = measured
         return m
+
+    @property
+    def hydrogen_coords(self) -> Optional[torch.Tensor]:
+        """[nH,3] fp32 (CPU): the explicit hydrogens of the returned coordinates, in ascending order of their heavy atom,
+        when the call asked for `add_hydrogens` (`hydrogens.py`: the package's own definition - NOT RDKit's AddHs; a view
+        into the batch's host tensor, sliced on first access); None otherwise, and where the molecule has a non-finite
+        coordinate."""
+        h = self._measured.hydrogen_coords
+        if isinstance(h, tuple):
+            h = self._measured.hydrogen_coords = h[0][h[1], : h[2]]
+        return h
+
+    @property
+    def hydrogen_parents(self) -> Optional[List[int]]:
+        """The heavy atom each hydrogen of `hydrogen_coords` is bonded to, ascending; None where that is None."""
+        return self._measured.hydrogen_parents
+
+    @property
+    def hydrogens_unplaced(self) -> Optional[int]:
+        """Hydrogens the count rule of `hydrogens.py` gives to atoms in a situation its placement has no direction for
+        (they are not in `hydrogen_coords`; 0 for an ordinary molecule); None where `hydrogen_coords` is None."""
+        return self._measured.hydrogens_unplaced
+
+    @property
+    def receptor_hydrogen_clashes(self) -> Optional[int]:
+        """Hydrogens of `hydrogen_coords` overlapping a receptor heavy atom by >= 0.6 A at the Bondi radius 1.20 A, when
+        the call asked for `add_hydrogens` and passed a `receptor`; None otherwise, and where posing failed.
+        `receptor_clashes` keeps counting the heavy atoms alone."""
+        return self._measured.receptor_hydrogen_clashes
 
     @property
     def relief_rmsd(self) -> Optional[float]:
@@ -276,23 +326,43 @@ class GeneratedMolecule:
     def GetNumAtoms(self) -> int:          # RDKit-like convenience
         return len(self._z) if self._z is not None else int(self._batch.n[self._b])
 
-    def to_molblock(self, name: str = "generated") -> str:
+    def _hydrogens(self) -> Tuple[List[List[float]], List[int]]:
+        """(coordinates, parents) of the record's hydrogens for the writers; ValueError where it carries none."""
+        xyz, parents = self.hydrogen_coords, self.hydrogen_parents
+        if xyz is None or parents is None:
+            raise ValueError("this record carries no hydrogens: generate with add_hydrogens=True (a molecule with a "
+                             "non-finite coordinate gets none)")
+        return xyz.tolist(), list(parents)
+
+    def to_molblock(self, name: str = "generated", hydrogens: bool = False) -> str:
         """V2000 MOL block (heavy atoms, bond orders 1/2/3, aromatic = 4) - consumable by RDKit
-        (`Chem.MolFromMolBlock`) or any other toolkit without going through this package."""
+        (`Chem.MolFromMolBlock`) or any other toolkit without going through this package.  `hydrogens=True`: the
+        record's explicit hydrogens (`add_hydrogens`) follow the heavy atoms, each with a single bond to its parent;
+        ValueError where the record carries none."""
         n = len(self.atomic_numbers)
         bonds = [(i + 1, j + 1, int(self.bond_orders[i, j])) for i in range(n) for j in range(i)
                  if int(self.bond_orders[i, j]) != 0]
-        lines = [name, "  mlconfgen-mi355x", "", "%3d%3d  0  0  0  0  0  0  0  0999 V2000" % (n, len(bonds))]
-        for s, c in zip(self.symbols, self.coords.tolist()):
+        atoms = list(zip(self.symbols, self.coords.tolist()))
+        if hydrogens:
+            xyz, parents = self._hydrogens()
+            atoms += [("H", c) for c in xyz]
+            bonds += [(n + 1 + k, p + 1, 1) for k, p in enumerate(parents)]
+        lines = [name, "  mlconfgen-mi355x", "", "%3d%3d  0  0  0  0  0  0  0  0999 V2000" % (len(atoms), len(bonds))]
+        for s, c in atoms:
             lines.append("%10.4f%10.4f%10.4f %-3s 0  0  0  0  0  0  0  0  0  0  0  0" % (c[0], c[1], c[2], s))
         for i, j, o in bonds:
             lines.append("%3d%3d%3d  0" % (i, j, o))
         lines.append("M  END")
         return "\n".join(lines) + "\n"
 
-    def to_xyz_block(self) -> str:
-        lines = [f"{len(self.atomic_numbers)}", ""]
-        for s, c in zip(self.symbols, self.coords.tolist()):
+    def to_xyz_block(self, hydrogens: bool = False) -> str:
+        """XYZ block of the heavy atoms; `hydrogens=True`: the record's explicit hydrogens (`add_hydrogens`) follow them;
+        ValueError where the record carries none."""
+        atoms = list(zip(self.symbols, self.coords.tolist()))
+        if hydrogens:
+            atoms += [("H", c) for c in self._hydrogens()[0]]
+        lines = [f"{len(atoms)}", ""]
+        for s, c in atoms:
             lines.append("%s %.9f %.9f %.9f" % (s, c[0], c[1], c[2]))
         return "\n".join(lines) + "\n"
 
@@ -407,7 +477,11 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                            pharmacophore_tanimoto: Optional[torch.Tensor] = None,
                            pharmacophore_matches: Optional[torch.Tensor] = None,
                            relief_rmsd: Optional[torch.Tensor] = None,
-                           receptor_clashes_before: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
+                           receptor_clashes_before: Optional[torch.Tensor] = None,
+                           hydrogen_coords: Optional[torch.Tensor] = None,
+                           hydrogen_parents: Optional[torch.Tensor] = None,
+                           hydrogens_unplaced: Optional[torch.Tensor] = None,
+                           receptor_hydrogen_clashes: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
     (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
     (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records).
@@ -423,6 +497,10 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     matches: not measured, the record gets None for both; None: a call without `pharmacophore_scores`).
     `relief_rmsd[b]` / `receptor_clashes_before[b]`: how far the clash relief moved row b and its clashes before it (a
     negative count: its pose failed, the record gets None for both; None: a call without `relieve_clashes`).
+    `hydrogen_coords[b]` [H,3] / `hydrogen_parents[b]` [H] (-1 beyond the row's count) / `hydrogens_unplaced[b]`: row b's
+    explicit hydrogens as `hydrogens.add_hydrogens` returns them (all three or none; a negative unplaced count: the row had
+    a non-finite coordinate, the record gets None for all three; None: a call without `add_hydrogens`).
+    `receptor_hydrogen_clashes[b]`: row b's hydrogens clashing with the receptor (negative: its pose failed, None).
     The value keywords are the fields of `Measured`
     and go to `measured_from_tensors`; a call with no ids and no values builds the views and nothing else."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
@@ -432,7 +510,9 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                   atoms_outside=atoms_outside, chemical_tanimoto=chemical_tanimoto, graph_key=graph_key,
                   strain_before=strain_before, strain_after=strain_after,
                   pharmacophore_tanimoto=pharmacophore_tanimoto, pharmacophore_matches=pharmacophore_matches,
-                  relief_rmsd=relief_rmsd, receptor_clashes_before=receptor_clashes_before)
+                  relief_rmsd=relief_rmsd, receptor_clashes_before=receptor_clashes_before,
+                  hydrogen_coords=hydrogen_coords, hydrogen_parents=hydrogen_parents,
+                  hydrogens_unplaced=hydrogens_unplaced, receptor_hydrogen_clashes=receptor_hydrogen_clashes)
     if sample_ids is None and all(v is None for v in values.values()):
         return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
     flags = valid.cpu().tolist()

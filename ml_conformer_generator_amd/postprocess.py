@@ -14,7 +14,9 @@ Stages, in this order:
   BEHIND the gather, on the rows a rank returns (`return_records` / `return_finished`):
     4. chemical fingerprints, graph keys and the Tanimoto to the reference's graph: one launch over the rows, one for
        the reference (`fingerprints`); beside it the pharmacophore overlap of the posed rows with the reference's
-       features: one perceive and one score launch over the rows, one each for the reference (`pharmacophore`);
+       features: one perceive and one score launch over the rows, one each for the reference (`pharmacophore`); and
+       the explicit hydrogens of the returned coordinates: one perceive and one placement launch over the rows, plus -
+       with a receptor - the receptor kernel over the hydrogens (`hydrogens`; records only: refused with a finisher);
     5. the values are attached - each molecule's `handoff.Measured`, behind a record's properties or written onto the
        Mol by `rdkit_finish.tag_measured` (Mols lose their properties in the object gather) - and validity is taken
        (`last_valid_fraction`);
@@ -25,7 +27,8 @@ Stages, in this order:
 A call with no option on takes none of these steps: its records / live Mols are returned as they come.
 
 The device work goes through the generator's seams (`_pose`, `_score`, `_pair`, `_receptor_coords`,
-`_relieve`, `_score_placed`, `_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, `_pharm_perceive`, `_pharm_score`),
+`_relieve`, `_score_placed`, `_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, `_pharm_perceive`, `_pharm_score`,
+`_add_hydrogens`),
 looked up on the instance at the time of the call.  The shape
 seams take the request's reference object; which kind it is - a conformer or a solid - is `cheminformatics`' business."""
 from __future__ import annotations
@@ -41,6 +44,7 @@ from . import cheminformatics
 from . import fingerprint as mcg_fp
 from . import geometry as mcg_geometry
 from . import host_pool
+from . import hydrogens as mcg_hydrogens
 from . import pharmacophore as mcg_pharm
 from . import receptor as mcg_receptor
 from .handoff import Measured, measured_from_tensors, molecules_from_tensors
@@ -72,6 +76,7 @@ class Request:
     ref_pharm_graph: Optional[tuple] = None       # else (atomic numbers, bond codes [n,n] int8, coords [n,3]) to perceive
     min_pharmacophore_tanimoto: Optional[float] = None
     rank_by: str = "shape"                        # "combo": rank by shape + pharmacophore Tanimoto
+    add_hydrogens: bool = False                   # `add_hydrogens`: explicit hydrogens on the returned records
 
     @property
     def selects_by_shape(self) -> bool:
@@ -114,7 +119,7 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
                   shape_density: float = 0.02, max_atoms_outside: Optional[int] = None,
                   reference_context=None, relax_geometry: Union[bool, int] = False, pharmacophore_scores=False,
                   reference_pharmacophore=None, min_pharmacophore_tanimoto: Optional[float] = None,
-                  rank_by: str = "shape", relieve_clashes: Union[bool, int] = False) -> Request:
+                  rank_by: str = "shape", relieve_clashes: Union[bool, int] = False, add_hydrogens=False) -> Request:
     """The public option keywords of a generation entry of `gen` as a `Request`: the shape options first, then the chemical
     ones (`top_k` / `min_shape_tanimoto` / `max_pairwise_tanimoto` imply the shape score, `max_chemical_tanimoto` the
     chemical one).  `reference_shape`: a watertight mesh in place of the reference conformer (`mesh.load_mesh`); the
@@ -124,8 +129,12 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     `reference_pharmacophore` (`pharmacophore.load_reference_features`) or are perceived, behind the generation, from the
     reference's graph (`reference_graph`, else a reference conformer with bonds) at the reference conformer's coordinates.
     `rank_by="combo"` needs the shape and the pharmacophore score.  `relieve_clashes`: `receptor.check_relief_steps`
-    (True = `receptor.RELIEF_STEPS`); it needs a `receptor`, and with it `overlay`.
+    (True = `receptor.RELIEF_STEPS`); it needs a `receptor`, and with it `overlay`.  `add_hydrogens`: True or False; it
+    works with every other option, but not with a finisher, RDKit's or a custom one (the hydrogens go onto the records).
     Every refusal happens here, before any device work."""
+    mcg_pharm.check_flag("add_hydrogens", add_hydrogens)
+    if add_hydrogens and getattr(gen, "finisher", None) is not None:
+        raise ValueError(mcg_hydrogens.REFUSAL_WITH_FINISHER)
     relax_steps = mcg_geometry.check_steps(relax_geometry)
     custom_finisher = isinstance(getattr(gen, "finisher", None), host_pool.TaskRef)
     shape = {}
@@ -151,7 +160,8 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
         if not overlay:
             raise ValueError("max_atoms_outside needs overlay=True: molecules that are not posed into the mesh are not "
                              "in its coordinates")
-    common = dict(reference=solid, max_atoms_outside=max_atoms_outside, relax_steps=relax_steps)
+    common = dict(reference=solid, max_atoms_outside=max_atoms_outside, relax_steps=relax_steps,
+                  add_hydrogens=add_hydrogens)
     if max_receptor_clashes is not None:
         mcg_receptor.check_max_receptor_clashes(max_receptor_clashes)
         if receptor is None:
@@ -346,6 +356,31 @@ def pharmacophore(gen, req: Request, coords: torch.Tensor, atomic_numbers: torch
     return gen._pharm_score(feats, coords, n_nodes, *gen._pharm_perceive(atomic_numbers, bond_orders, n_nodes))
 
 
+def hydrogens(gen, req: Request, res: dict) -> dict:
+    """The hydrogen step of the rows a rank returns (`add_hydrogens`): the explicit hydrogens of the RETURNED coordinates -
+    relaxed, posed, refined, relieved - so they need no transform of their own; one perceive and one placement launch
+    over the rows (`_add_hydrogens`).  The per-sample tensors by the names `handoff.measured_from_tensors` reads:
+    `hydrogen_coords`, `hydrogen_parents`, `hydrogens_unplaced` (-1 where the row has a non-finite coordinate) and - with
+    a receptor - `receptor_hydrogen_clashes`: the hydrogens overlapping a receptor heavy atom by `receptor.CLASH_OVERLAP`
+    at hydrogen's van der Waals radius, by the heavy atoms' own kernel (`_receptor_coords`) over the hydrogen columns in
+    chunks of its 64-atom width; -1 where posing failed."""
+    out = gen._add_hydrogens(res["x"], res["elements"], res["bond"], res["n_nodes"])
+    count = out["n_hydrogens"]
+    values = dict(hydrogen_coords=out["coords"], hydrogen_parents=out["parents"],
+                  hydrogens_unplaced=torch.where(count < 0, torch.full_like(count, -1), out["unplaced"]))
+    if req.receptor is not None:
+        xyz = out["coords"]
+        clashes = torch.zeros_like(count)
+        for lo in range(0, int(xyz.shape[1]), mcg_receptor.MAX_LIGAND_ATOMS):
+            chunk = xyz[:, lo: lo + mcg_receptor.MAX_LIGAND_ATOMS].contiguous()
+            n_chunk = (count - lo).clamp(0, int(chunk.shape[1]))
+            ones = torch.ones(chunk.shape[0], chunk.shape[1], dtype=torch.int32, device=xyz.device)
+            clashes = clashes + mcg_receptor.clash_summary(gen._receptor_coords(req.receptor, chunk, n_chunk, ones))[0]
+        posed = torch.isfinite(res["pose"]).all(dim=1).to(clashes.device) & (count >= 0)
+        values["receptor_hydrogen_clashes"] = torch.where(posed, clashes, torch.full_like(clashes, -1))
+    return values
+
+
 def _index(rows: Rows, device) -> torch.Tensor:
     return torch.tensor(rows.row, dtype=torch.long, device=device)
 
@@ -431,6 +466,8 @@ def return_records(gen, req: Request, res: dict, row_ids: Optional[torch.Tensor]
         posed = torch.isfinite(res["pose"]).all(dim=1).to(sim.device)         # a failed pose is not in the reference's frame
         values.update(pharmacophore_tanimoto=torch.where(posed, sim, torch.full_like(sim, float("nan"))),
                       pharmacophore_matches=torch.where(posed, hits, torch.full_like(hits, -1)))
+    if req.add_hydrogens:
+        values.update(hydrogens(gen, req, res))
     if gen.device.type == "cuda":
         torch.cuda.synchronize(gen.device)        # (the D2H copies below would wait anyway: keep that out of the figure)
     t0 = time.perf_counter()
