@@ -675,6 +675,43 @@ int mcg_hydrogens_place(const float* coords, const int32_t* z, const int8_t* bon
                         float* h_xyz_out, int32_t* h_parent_out, int32_t* h_count_out, int32_t* n_h_out,
                         int32_t* unplaced_out, int32_t* rotor_delta_out /*optional [B,W]*/, void* stream);
 
+/* ---- Standardised graphs ("Standardised graphs"): the largest fragment of each of B molecular
+ * graphs, the checks that make it a molecule, and a Kekule form of its aromatic bonds.  The definition is this package's
+ * OWN (DESIGN.md states it in full): not RDKit's FragmentParent / Kekulize / SanitizeMol - no charges, no normalisation,
+ * no agreement with RDKit claimed.
+ *   mcg_standardize_graphs: coords[B,N,3] fp32, z[B,W] atomic numbers, bonds[B,W,W] symmetric bond codes (1 / 2 / 3 / 4
+ *                       aromatic; any other value is no bond; the matrix is read through its lower triangle),
+ *                       n_nodes_dev[b] real atoms (device memory, clamped to [0, min(N, W)] on the device; the diagonal
+ *                       and everything at or beyond n_b is ignored, whatever it holds).
+ *                       The parent is the connected component with the most atoms, ties to the larger sum of atomic
+ *                       numbers, then to the one holding the lowest atom index; its atoms keep their relative order.
+ *                       coords_out[B,N,3] (copied bit for bit), z_out[B,W], bonds_out[B,W,W]: the parent, compacted, zero
+ *                       beyond its atoms; atom_map_out[B,W]: the old index of each new atom, -1 beyond; n_out[b],
+ *                       n_fragments_out[b], atoms_removed_out[b]; status_out[b]: 0 = valid, else a set of
+ *                       MCG_STANDARDIZE_EMPTY (n = 0), _OVER_VALENCE (a kept atom's bonds, codes 1/2/3/4 counting
+ *                       2/4/6/2 half-bonds, exceed twice the validity proxy's maximum valence), _AROMATIC_BRIDGE (a code-4
+ *                       bond in no ring), _NOT_KEKULIZABLE and _SEARCH_BUDGET (the Kekule search of DESIGN.md failed, or
+ *                       took more than MCG_STANDARDIZE_KEKULE_BUDGET steps on one component of the eligible graph; the
+ *                       search runs only when the first three are clear).  kekule_out[B,W,W]: the parent's codes with
+ *                       every code 4 replaced by 2 on the matched pairs and by 1 elsewhere; all zero unless status is 0.
+ *                       The coordinates play no part in the verdict.  One 64-lane workgroup per molecule, one launch, no
+ *                       atomics, integer work only: a molecule's outputs have the same bits whatever the batch, its row
+ *                       and the padded widths.
+ * B = 0 launches nothing.  MCG_ERR_ARG, nothing launched: a null buffer, B outside 0..MCG_STANDARDIZE_MAX_B, N < 1,
+ * W outside 1..MCG_STANDARDIZE_MAX_ATOMS. */
+#define MCG_STANDARDIZE_MAX_ATOMS 64
+#define MCG_STANDARDIZE_MAX_B 16384
+#define MCG_STANDARDIZE_KEKULE_BUDGET 16384
+#define MCG_STANDARDIZE_EMPTY 1
+#define MCG_STANDARDIZE_OVER_VALENCE 2
+#define MCG_STANDARDIZE_AROMATIC_BRIDGE 4
+#define MCG_STANDARDIZE_NOT_KEKULIZABLE 8
+#define MCG_STANDARDIZE_SEARCH_BUDGET 16
+int mcg_standardize_graphs(const float* coords, const int32_t* z, const int8_t* bonds, const int32_t* n_nodes_dev, int B,
+                           int N /*coords row width*/, int W /*z, bonds width*/, float* coords_out, int32_t* z_out,
+                           int8_t* bonds_out, int8_t* kekule_out, int32_t* atom_map_out, int32_t* n_out,
+                           int32_t* n_fragments_out, int32_t* atoms_removed_out, int32_t* status_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,7 +52,12 @@ forced by the scope of this build:
   * `relax_geometry` (every generation entry; off by default): every generated molecule's heavy atoms are relaxed on the
     GPU, right behind the bond write-back, on the package's OWN restrained valence force field (`geometry.py`; NOT MMFF94),
     and everything downstream reads the relaxed coordinates.  Independent of `optimise_geometry`, whose meaning and
-    warning are unchanged.
+    warning are unchanged;
+  * `standardize` (every generation entry; off by default; records path only): every generated graph is standardised on
+    the GPU, right behind the bond write-back and before the relaxation - largest fragment, valence / aromatic-bridge
+    checks, a Kekule form (`standardize.py`: the package's OWN definition, NOT RDKit's FragmentParent / Kekulize /
+    SanitizeMol) - and everything downstream reads the parent fragment; validity is then that stage's verdict instead of
+    the proxy's.
 """
 from __future__ import annotations
 
@@ -82,6 +87,7 @@ from . import fingerprint as mcg_fp
 from . import geometry as mcg_geometry
 from . import hydrogens as mcg_hydrogens
 from . import pharmacophore as mcg_pharm
+from . import standardize as mcg_standardize
 from .handoff import (GeneratedMolecule, assemble_molecules, bond_writeback_hip, molecules_from_tensors,
                       prepare_adj_mat_seer_input_hip)
 from .mol_utils import (get_context_shape, ifm_get_xh_from_fragment, ifm_merge_hip,
@@ -365,6 +371,13 @@ class MLConformerGenerator(torch.nn.Module):
         elements come from the validated decoder, the codes from the bond write-back; device tensors)."""
         return mcg_hydrogens.add_hydrogens(coords, atomic_numbers, bond_orders, n_nodes, self.device, check=False)
 
+    # the standardisation step
+    def _standardize(self, coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
+                     n_nodes: torch.Tensor) -> dict:
+        """The standardised form of padded heavy-atom graphs - largest fragment, checks, Kekule form
+        (`standardize.standardize_graphs`, unchecked: the codes come from the bond write-back; device tensors)."""
+        return mcg_standardize.standardize_graphs(coords, atomic_numbers, bond_orders, n_nodes, self.device, check=False)
+
     # the geometry step
     def _relax_coords(self, coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
                       n_nodes: torch.Tensor, steps: int) -> dict:
@@ -412,12 +425,18 @@ class MLConformerGenerator(torch.nn.Module):
     def _generate_shard(self, ref_context, ref_n_atoms: int, variance: int, sizes: Optional[torch.Tensor],
                         n_samples: int, resample_steps, fixed_fragment, inertial_fragment_matching, blend_power,
                         ifm_diffusion_level, optimise_geometry: bool = True, sample_seed: Optional[int] = None,
-                        sample_ids: Optional[torch.Tensor] = None, relax_steps: int = 0):
+                        sample_ids: Optional[torch.Tensor] = None, relax_steps: int = 0, standardize: bool = False):
         """Sampler -> hand-off -> GCN -> bond write-back + validity proxy for `n_samples` molecules on THIS device.
         Returns per-sample DEVICE tensors (dim 0 = n_samples; n_samples may be 0 for an empty shard).
         `relax_steps` > 0 (`relax_geometry`): every group's coordinates are relaxed right behind its bond write-back
         (`_relax_coords`, one launch per group, all rows); the relaxed coordinates are what `x`, the finisher's records and
         everything downstream hold, and `strain_before` / `strain_after` [n_samples] join the returned tensors.
+        `standardize`: every group's graphs are standardised right behind its bond write-back and BEFORE the relaxation
+        (`_standardize`, one launch per group, all rows): `x`, `elements`, `bond`, `n_nodes` and everything downstream
+        are the parent fragment's, `valid` is the standardisation's verdict (status 0) instead of the proxy's flag, and
+        `atoms_removed`, `n_fragments` [n_samples], `atom_map` [n_samples,42] and `kekule_bond_orders` [n_samples,42,42]
+        join the returned tensors.  `last_batch` keeps what the hand-off and the GCN wrote and gains `standardized`, the
+        stage's own result.
         `sample_seed`, `sample_ids`: the keyed stream of `edm_tensors`; `sample_ids` (default arange) also names the
         records handed to the finisher.
 
@@ -449,10 +468,16 @@ class MLConformerGenerator(torch.nn.Module):
                 self._finish_stage = rdkit_finish.FinishStage(finisher, optimise_geometry, executor)
             strain = dict(strain_before=torch.zeros(0, device=dev), strain_after=torch.zeros(0, device=dev)) \
                 if relax_steps else {}
+            std_out = {}
+            if standardize:
+                i32 = dict(dtype=torch.int32, device=dev)
+                std_out = dict(atoms_removed=torch.zeros(0, **i32), n_fragments=torch.zeros(0, **i32),
+                               atom_map=torch.zeros(0, D, **i32),
+                               kekule_bond_orders=torch.zeros(0, D, D, dtype=torch.int8, device=dev))
             return dict(x=torch.zeros(0, N, 3, device=dev), elements=torch.zeros(0, D, dtype=torch.int8, device=dev),
                         bond=torch.zeros(0, D, D, dtype=torch.int8, device=dev),
                         n_nodes=torch.zeros(0, dtype=torch.int32, device=dev),
-                        valid=torch.zeros(0, dtype=torch.uint8, device=dev), **strain)
+                        valid=torch.zeros(0, dtype=torch.uint8, device=dev), **strain, **std_out)
         x, h, node_mask = self.edm_tensors(
             reference_context=ref_context, n_samples=n_samples, min_n_nodes=ref_n_atoms - variance,
             max_n_nodes=ref_n_atoms + variance, resample_steps=resample_steps, fixed_fragment=fixed_fragment,
@@ -469,7 +494,7 @@ class MLConformerGenerator(torch.nn.Module):
         if finisher is not None:
             from . import rdkit_finish
             fin = rdkit_finish.FinishStage(finisher, optimise_geometry, executor)
-        parts, orders = [], []
+        parts, orders, std_parts = [], [], []
         for g, (lo, hi) in enumerate(groups):
             order = conn = built = None
             if stage is not None:
@@ -480,6 +505,11 @@ class MLConformerGenerator(torch.nn.Module):
                                                                with_coords=True, class_z=self.class_z)
             bond = self.adj_mat_seer.bond_orders(el, dm, am)
             sym, valid = bond_writeback_hip(bond, el, ng)
+            if standardize:                                   # all rows; from here on the molecule is its parent fragment
+                std = self._standardize(x_out, el, sym, ng)
+                std_parts.append((x_out, el, std))
+                x_out, sym, valid = std["coords"], std["bond_orders"], std["valid"]
+                el, ng = std["atomic_numbers"].to(el.dtype), std["n_nodes"].to(ng.dtype)
             if built is not None and not all(built):          # `MolFromXYZBlock` returned None: the reference drops it
                 valid = valid & torch.tensor(built, dtype=torch.bool, device=valid.device)
             extra = ()
@@ -502,10 +532,19 @@ class MLConformerGenerator(torch.nn.Module):
         if relax_steps:           # `x_ordered` stays what the hand-off wrote; the relaxed coordinates are a key of their own
             self.last_batch.update(x_ordered=cat(5), x_relaxed=x_out)
             strain = dict(strain_before=cat(6), strain_after=cat(7))
+        n_out, std_out = n_nodes, {}
+        if standardize:           # `x_ordered`, `elements` stay what the hand-off wrote; the stage's result is a key of its own
+            scat = (lambda pick: pick(std_parts[0])) if len(std_parts) == 1 else \
+                (lambda pick: torch.cat([pick(p) for p in std_parts], dim=0))
+            full = {k: scat(lambda p, k=k: p[2][k]) for k in std_parts[0][2]}
+            self.last_batch.update(x_ordered=scat(lambda p: p[0]), elements=scat(lambda p: p[1]), standardized=full)
+            n_out = full["n_nodes"]
+            std_out = dict(atoms_removed=full["atoms_removed"], n_fragments=full["n_fragments"], atom_map=full["atom_map"],
+                           kekule_bond_orders=full["kekule_orders"])
         flat = [o for grp in orders for o in grp]
         self.last_order = None if all(o is None for o in flat) else flat    # per-molecule atom orders (None: generation order)
-        return dict(x=x_out, elements=el.to(torch.int8), bond=sym, n_nodes=n_nodes.to(torch.int32),
-                    valid=valid.to(torch.uint8), **strain)
+        return dict(x=x_out, elements=el.to(torch.int8), bond=sym, n_nodes=n_out.to(torch.int32),
+                    valid=valid.to(torch.uint8), **strain, **std_out)
 
     def _collect_finish(self, n_samples: int) -> List:
         """The pending finish of the shard generated last -> its `n_samples` per-sample results (None = dropped)."""
@@ -535,7 +574,7 @@ class MLConformerGenerator(torch.nn.Module):
                             relax_geometry: Union[bool, int] = False, pharmacophore_scores: bool = False,
                             reference_pharmacophore=None, min_pharmacophore_tanimoto: Optional[float] = None,
                             rank_by: str = "shape", relieve_clashes: Union[bool, int] = False,
-                            add_hydrogens: bool = False) -> List:
+                            add_hydrogens: bool = False, standardize: bool = False) -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
@@ -661,6 +700,19 @@ class MLConformerGenerator(torch.nn.Module):
         the kernel of the heavy-atom contacts; None where posing failed; `receptor_clashes` / `receptor_max_overlap` keep
         their heavy-atom meaning and no filter reads the hydrogens.  All of these are None in a call without the option,
         and the three hydrogen fields where the molecule has a non-finite coordinate.
+        `standardize=True` (records path only): every generated graph is standardised on the GPU right behind the bond
+        write-back and BEFORE `relax_geometry`, as the reference takes the fragment parent before MMFF
+        (`standardize.standardize_graphs`; DESIGN.md section 6, "Standardised graphs") - by the package's OWN definition,
+        NOT RDKit's FragmentParent / Kekulize / SanitizeMol: the largest connected fragment is kept (ties: the larger sum
+        of atomic numbers, then the lowest atom index), its atoms in their order; it is valid when no atom exceeds the
+        proxy's maximum valence (aromatic bonds counted as their sigma bond), no aromatic bond lies outside a ring and
+        its aromatic bonds have a Kekule form, found by a fixed-order search within a step budget.  No charges, no
+        normalisation, no tautomers.  The returned molecules ARE the parent fragments - coordinates, elements, bonds and
+        everything measured downstream - and validity is this verdict instead of the proxy's: a molecule with a stray atom
+        beside a good fragment is kept, one whose aromatic bonds admit no Kekule form is dropped.  Records carry
+        `atoms_removed`, `n_fragments`, `atom_map` (each atom's index in the graph as generated) and
+        `kekule_bond_orders`; `to_molblock(kekulize=True)` writes the Kekule form.  `last_batch` keeps what the hand-off
+        and the GCN wrote and gains `standardized`.  All of these are None in a call without the option.
         Order of the stages: validity, `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`,
         `min_pharmacophore_tanimoto`, `unique`, then the selection (threshold, exclusion, `top_k`).  The filters only
         remove molecules.
@@ -680,7 +732,8 @@ class MLConformerGenerator(torch.nn.Module):
         `reference_pharmacophore` that `load_reference_features` refuses or that no option reads, a reference graph whose
         heavy-atom count differs from the reference conformer's, min_pharmacophore_tanimoto outside [0, 1], and a
         `rank_by` other than "shape" or "combo", or "combo" without both scores, and add_hydrogens that is not a bool or on
-        a generator with a finisher, RDKit's or a custom one (on Mols use `Chem.AddHs(mol, addCoords=True)`).  A reference
+        a generator with a finisher, RDKit's or a custom one (on Mols use `Chem.AddHs(mol, addCoords=True)`), and standardize
+        that is not a bool or on a generator with a finisher (RDKit's finisher runs `standardize_mol` itself).  A reference
         graph in which no feature is found is refused where it is perceived, behind the generation."""
         if sample_seed is not None:
             seeding.check_seed(sample_seed)
@@ -690,11 +743,13 @@ class MLConformerGenerator(torch.nn.Module):
                                         max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
                                         reference_context, relax_geometry, pharmacophore_scores,
                                         reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes,
-                                        add_hydrogens)
+                                        add_hydrogens, standardize)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         keyed = () if sample_seed is None else (sample_seed, None)   # unseeded: the positional call of before
         relax = dict(relax_steps=req.relax_steps) if req.relax_steps else {}
+        if req.standardize:
+            relax["standardize"] = True
         res = self._generate_shard(ref_context, ref_n_atoms, variance, None, n_samples, resample_steps, fixed_fragment,
                                    inertial_fragment_matching, blend_power, ifm_diffusion_level, optimise_geometry, *keyed,
                                    **relax)
@@ -724,7 +779,7 @@ class MLConformerGenerator(torch.nn.Module):
                                     relax_geometry: Union[bool, int] = False, pharmacophore_scores: bool = False,
                                     reference_pharmacophore=None, min_pharmacophore_tanimoto: Optional[float] = None,
                                     rank_by: str = "shape", relieve_clashes: Union[bool, int] = False,
-                                    add_hydrogens: bool = False) -> List:
+                                    add_hydrogens: bool = False, standardize: bool = False) -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -744,7 +799,8 @@ class MLConformerGenerator(torch.nn.Module):
         `max_receptor_clashes`, `chemical_scores`, `reference_graph`, `max_chemical_tanimoto`, `unique`,
         `max_pairwise_chemical_tanimoto`, `reference_shape`, `shape_density`, `max_atoms_outside`, `relax_geometry`,
         `pharmacophore_scores`, `reference_pharmacophore`, `min_pharmacophore_tanimoto`, `rank_by`, `relieve_clashes`,
-        `add_hydrogens` (placed behind the gather, on the rows a rank returns): as in
+        `add_hydrogens` (placed behind the gather, on the rows a rank returns), `standardize` (on each rank's own shard,
+        before the gather; its per-sample tensors travel with the rest, one collective each): as in
         `generate_conformers` (every rank loads the mesh and computes its occupancy itself).  The fingerprints are computed behind the gather,
         on the rows a rank returns: with gather="all" uniqueness and chemical diversity hold over the whole batch, with
         gather="rank0" within each other rank's own shard, like the rest of the selection.
@@ -765,7 +821,7 @@ class MLConformerGenerator(torch.nn.Module):
                                         max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
                                         reference_context, relax_geometry, pharmacophore_scores,
                                         reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes,
-                                        add_hydrogens)
+                                        add_hydrogens, standardize)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)
@@ -778,6 +834,8 @@ class MLConformerGenerator(torch.nn.Module):
         def run_shard(sizes_shard, index):
             keyed = () if sample_seed is None else (sample_seed, index)
             relax = dict(relax_steps=req.relax_steps) if req.relax_steps else {}
+            if req.standardize:
+                relax["standardize"] = True
             res = self._generate_shard(ref_context, ref_n_atoms, variance, sizes_shard, int(index.numel()), resample_steps,
                                        fixed_fragment, inertial_fragment_matching, blend_power, ifm_diffusion_level,
                                        optimise_geometry, *keyed, **relax)

@@ -57,6 +57,10 @@ class Measured:
     hydrogen_parents: Optional[List[int]] = None
     hydrogens_unplaced: Optional[int] = None
     receptor_hydrogen_clashes: Optional[int] = None
+    atoms_removed: Optional[int] = None
+    n_fragments: Optional[int] = None
+    atom_map: Optional[List[int]] = None
+    kekule_bond_orders: Optional[object] = None   # [n,n] int8, host - or (batch [B,W,W], row, n), sliced on first read
 
 
 _UNMEASURED = Measured()          # shared by every record that carries no values: never written to
@@ -71,8 +75,11 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
     The hydrogens of a call with `add_hydrogens` come as `hydrogen_coords` [n,H,3], `hydrogen_parents` [n,H] (-1 beyond a
     row's count) and `hydrogens_unplaced` [n] (negative: the row had a non-finite coordinate, the record gets None for all
     three); a record's `hydrogen_coords` is left as (the one host copy, row, count) and sliced on first read
-    (`GeneratedMolecule.hydrogen_coords`).  A negative `receptor_hydrogen_clashes`: not measured."""
-    hyd = {k: values.get(k) for k in ("hydrogen_coords", "hydrogen_parents")}
+    (`GeneratedMolecule.hydrogen_coords`).  A negative `receptor_hydrogen_clashes`: not measured.
+    The standardisation of a call with `standardize` comes as `atoms_removed` [n], `n_fragments` [n], `atom_map` [n,W] (-1
+    beyond a row's atoms) and `kekule_bond_orders` [n,W,W] (all four or none); a record's `kekule_bond_orders` is left as
+    (the one host copy, row, atom count) and sliced on first read."""
+    hyd = {k: values.get(k) for k in ("hydrogen_coords", "hydrogen_parents", "atom_map", "kekule_bond_orders")}
     cols = {k: v.cpu().tolist() for k, v in values.items() if v is not None and k != "pose" and k not in hyd}
     if values.get("pose") is not None:
         poses = values["pose"].cpu().to(torch.float32)
@@ -104,6 +111,10 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
         parents = [[p for p in row if p >= 0] for row in hyd["hydrogen_parents"].cpu().tolist()]
         cols["hydrogen_parents"] = [None if gone else p for gone, p in zip(missing, parents)]
         cols["hydrogen_coords"] = [None if gone else (xyz, b, len(p)) for b, (gone, p) in enumerate(zip(missing, parents))]
+    if hyd["atom_map"] is not None:
+        cols["atom_map"] = [[a for a in row if a >= 0] for row in hyd["atom_map"].cpu().tolist()]
+        orders = hyd["kekule_bond_orders"].cpu().to(torch.int8)
+        cols["kekule_bond_orders"] = [(orders, b, len(kept)) for b, kept in enumerate(cols["atom_map"])]
     return [Measured(**{k: col[b] for k, col in cols.items()}) for b in range(n)]
 
 
@@ -130,7 +141,11 @@ class GeneratedMolecule:
     clashes of its pose before that (`receptor.py`: the package's own procedure), else None.
     `hydrogen_coords` / `hydrogen_parents` / `hydrogens_unplaced`: its explicit hydrogens when the call asked for
     `add_hydrogens` (`hydrogens.py`: the package's own definition, NOT RDKit's AddHs), else None; with a receptor also
-    `receptor_hydrogen_clashes`.  `to_molblock(hydrogens=True)` / `to_xyz_block(hydrogens=True)` write them."""
+    `receptor_hydrogen_clashes`.  `to_molblock(hydrogens=True)` / `to_xyz_block(hydrogens=True)` write them.
+    `atoms_removed` / `n_fragments` / `atom_map` / `kekule_bond_orders`: what the standardisation of a call with
+    `standardize` did to it (`standardize.py`: the package's own definition, NOT RDKit's FragmentParent / Kekulize /
+    SanitizeMol) - the record then IS the largest fragment - else None.  `to_molblock(kekulize=True)` writes the Kekule
+    form."""
     __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_measured")
 
     def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True,
@@ -147,6 +162,33 @@ class GeneratedMolecule:
         m._sid = b if sample_id is None else sample_id
         m._measured = measured
         return m
+
+    @property
+    def atoms_removed(self) -> Optional[int]:
+        """How many atoms of the generated graph lay outside its largest fragment and were removed, when the call asked
+        to `standardize` (`standardize.py`: the package's own definition); None otherwise."""
+        return self._measured.atoms_removed
+
+    @property
+    def n_fragments(self) -> Optional[int]:
+        """How many connected fragments the generated graph had before the largest was kept; None without `standardize`."""
+        return self._measured.n_fragments
+
+    @property
+    def atom_map(self) -> Optional[List[int]]:
+        """For each atom of this record its index in the graph as generated (the GCN's atom order, the rows of
+        `last_batch["elements"]`); None without `standardize`."""
+        return self._measured.atom_map
+
+    @property
+    def kekule_bond_orders(self) -> Optional[torch.Tensor]:
+        """[n,n] int8 (CPU): `bond_orders` with every aromatic bond written as 1 or 2 by the Kekule search of
+        `standardize.py` (the package's own definition, NOT RDKit's Kekulize; a view into the batch's host tensor, sliced
+        on first access); all zero for a record the standardisation found invalid; None without `standardize`."""
+        k = self._measured.kekule_bond_orders
+        if isinstance(k, tuple):
+            k = self._measured.kekule_bond_orders = k[0][k[1], : k[2], : k[2]]
+        return k
 
     @property
     def hydrogen_coords(self) -> Optional[torch.Tensor]:
@@ -334,14 +376,38 @@ class GeneratedMolecule:
                              "non-finite coordinate gets none)")
         return xyz.tolist(), list(parents)
 
-    def to_molblock(self, name: str = "generated", hydrogens: bool = False) -> str:
+    def _kekule_orders(self, hydrogen_parents: Optional[List[int]]) -> torch.Tensor:
+        """The record's Kekule orders for the writer; ValueError where it carries none, where it has no Kekule form, and -
+        with the parents of its placed hydrogens - where an atom's Kekule valence plus its hydrogens exceeds v0
+        (`hydrogens.VALENCE`): the Kekule search and the hydrogen count are two definitions and can disagree."""
+        orders = self.kekule_bond_orders
+        if orders is None:
+            raise ValueError("this record carries no Kekule form: generate with standardize=True")
+        if bool(((orders == 0) & (self.bond_orders != 0)).any()):
+            raise ValueError("this record has no Kekule form: its standardisation found it invalid")
+        if hydrogen_parents is not None:
+            from .hydrogens import VALENCE
+            for a, z in enumerate(self.atomic_numbers):
+                total = int(orders[a].sum()) + sum(1 for p in hydrogen_parents if p == a)
+                if total > VALENCE.get(z, 0):
+                    raise ValueError(f"atom {a} ({Z_TO_SYMBOL.get(z, z)}) has Kekule valence {int(orders[a].sum())} and "
+                                     f"{total - int(orders[a].sum())} placed hydrogens, more than v0 = {VALENCE.get(z, 0)}: "
+                                     "the Kekule form and the hydrogen count disagree on this atom")
+        return orders
+
+    def to_molblock(self, name: str = "generated", hydrogens: bool = False, kekulize: bool = False) -> str:
         """V2000 MOL block (heavy atoms, bond orders 1/2/3, aromatic = 4) - consumable by RDKit
         (`Chem.MolFromMolBlock`) or any other toolkit without going through this package.  `hydrogens=True`: the
         record's explicit hydrogens (`add_hydrogens`) follow the heavy atoms, each with a single bond to its parent;
-        ValueError where the record carries none."""
+        ValueError where the record carries none.  `kekulize=True`: the bonds are the record's `kekule_bond_orders`
+        (`standardize`), orders 1/2/3 only - a structure, where a block with bond type 4 is a query; ValueError where the
+        record carries none or has no Kekule form, and with `hydrogens=True` also where an atom's Kekule valence plus its
+        placed hydrogens exceeds v0 (the message names the atom)."""
         n = len(self.atomic_numbers)
-        bonds = [(i + 1, j + 1, int(self.bond_orders[i, j])) for i in range(n) for j in range(i)
-                 if int(self.bond_orders[i, j]) != 0]
+        orders = self.bond_orders
+        if kekulize:
+            orders = self._kekule_orders(self._hydrogens()[1] if hydrogens else None)
+        bonds = [(i + 1, j + 1, int(orders[i, j])) for i in range(n) for j in range(i) if int(orders[i, j]) != 0]
         atoms = list(zip(self.symbols, self.coords.tolist()))
         if hydrogens:
             xyz, parents = self._hydrogens()
@@ -481,7 +547,10 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                            hydrogen_coords: Optional[torch.Tensor] = None,
                            hydrogen_parents: Optional[torch.Tensor] = None,
                            hydrogens_unplaced: Optional[torch.Tensor] = None,
-                           receptor_hydrogen_clashes: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
+                           receptor_hydrogen_clashes: Optional[torch.Tensor] = None,
+                           atoms_removed: Optional[torch.Tensor] = None, n_fragments: Optional[torch.Tensor] = None,
+                           atom_map: Optional[torch.Tensor] = None,
+                           kekule_bond_orders: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
     (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
     (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records).
@@ -501,6 +570,9 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     explicit hydrogens as `hydrogens.add_hydrogens` returns them (all three or none; a negative unplaced count: the row had
     a non-finite coordinate, the record gets None for all three; None: a call without `add_hydrogens`).
     `receptor_hydrogen_clashes[b]`: row b's hydrogens clashing with the receptor (negative: its pose failed, None).
+    `atoms_removed[b]` / `n_fragments[b]` / `atom_map[b]` [W] (-1 beyond the row's atoms) / `kekule_bond_orders[b]` [W,W]:
+    row b's standardisation as `standardize.standardize_graphs` returns it (all four or none; None: a call without
+    `standardize`).
     The value keywords are the fields of `Measured`
     and go to `measured_from_tensors`; a call with no ids and no values builds the views and nothing else."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
@@ -512,7 +584,9 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                   pharmacophore_tanimoto=pharmacophore_tanimoto, pharmacophore_matches=pharmacophore_matches,
                   relief_rmsd=relief_rmsd, receptor_clashes_before=receptor_clashes_before,
                   hydrogen_coords=hydrogen_coords, hydrogen_parents=hydrogen_parents,
-                  hydrogens_unplaced=hydrogens_unplaced, receptor_hydrogen_clashes=receptor_hydrogen_clashes)
+                  hydrogens_unplaced=hydrogens_unplaced, receptor_hydrogen_clashes=receptor_hydrogen_clashes,
+                  atoms_removed=atoms_removed, n_fragments=n_fragments, atom_map=atom_map,
+                  kekule_bond_orders=kekule_bond_orders)
     if sample_ids is None and all(v is None for v in values.values()):
         return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
     flags = valid.cpu().tolist()

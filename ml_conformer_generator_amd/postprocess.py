@@ -25,6 +25,9 @@ Stages, in this order:
        threshold / sphere exclusion / `top_k` walk of `cheminformatics.select_diverse`.  The two pair matrices are
        computed only when their threshold is set, over the rows that survived the filters.
 A call with no option on takes none of these steps: its records / live Mols are returned as they come.
+`standardize` is not a stage here: the generator standardises right behind the bond write-back, so the result tensors
+that arrive are already the parent fragments'; its four per-sample tensors (`atoms_removed`, `n_fragments`, `atom_map`,
+`kekule_bond_orders`) ride through the gather and into each record's `Measured` like the strain energies do.
 
 The device work goes through the generator's seams (`_pose`, `_score`, `_pair`, `_receptor_coords`,
 `_relieve`, `_score_placed`, `_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, `_pharm_perceive`, `_pharm_score`,
@@ -47,6 +50,7 @@ from . import host_pool
 from . import hydrogens as mcg_hydrogens
 from . import pharmacophore as mcg_pharm
 from . import receptor as mcg_receptor
+from . import standardize as mcg_standardize
 from .handoff import Measured, measured_from_tensors, molecules_from_tensors
 
 
@@ -77,6 +81,7 @@ class Request:
     min_pharmacophore_tanimoto: Optional[float] = None
     rank_by: str = "shape"                        # "combo": rank by shape + pharmacophore Tanimoto
     add_hydrogens: bool = False                   # `add_hydrogens`: explicit hydrogens on the returned records
+    standardize: bool = False                     # `standardize`: largest fragment + Kekule form, behind the bond write-back
 
     @property
     def selects_by_shape(self) -> bool:
@@ -119,7 +124,8 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
                   shape_density: float = 0.02, max_atoms_outside: Optional[int] = None,
                   reference_context=None, relax_geometry: Union[bool, int] = False, pharmacophore_scores=False,
                   reference_pharmacophore=None, min_pharmacophore_tanimoto: Optional[float] = None,
-                  rank_by: str = "shape", relieve_clashes: Union[bool, int] = False, add_hydrogens=False) -> Request:
+                  rank_by: str = "shape", relieve_clashes: Union[bool, int] = False, add_hydrogens=False,
+                  standardize=False) -> Request:
     """The public option keywords of a generation entry of `gen` as a `Request`: the shape options first, then the chemical
     ones (`top_k` / `min_shape_tanimoto` / `max_pairwise_tanimoto` imply the shape score, `max_chemical_tanimoto` the
     chemical one).  `reference_shape`: a watertight mesh in place of the reference conformer (`mesh.load_mesh`); the
@@ -131,10 +137,14 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     `rank_by="combo"` needs the shape and the pharmacophore score.  `relieve_clashes`: `receptor.check_relief_steps`
     (True = `receptor.RELIEF_STEPS`); it needs a `receptor`, and with it `overlay`.  `add_hydrogens`: True or False; it
     works with every other option, but not with a finisher, RDKit's or a custom one (the hydrogens go onto the records).
+    `standardize`: True or False; likewise refused with a finisher (RDKit's `standardize_mol` already does it on Mols).
     Every refusal happens here, before any device work."""
     mcg_pharm.check_flag("add_hydrogens", add_hydrogens)
     if add_hydrogens and getattr(gen, "finisher", None) is not None:
         raise ValueError(mcg_hydrogens.REFUSAL_WITH_FINISHER)
+    mcg_pharm.check_flag("standardize", standardize)
+    if standardize and getattr(gen, "finisher", None) is not None:
+        raise ValueError(mcg_standardize.REFUSAL_WITH_FINISHER)
     relax_steps = mcg_geometry.check_steps(relax_geometry)
     custom_finisher = isinstance(getattr(gen, "finisher", None), host_pool.TaskRef)
     shape = {}
@@ -161,7 +171,7 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
             raise ValueError("max_atoms_outside needs overlay=True: molecules that are not posed into the mesh are not "
                              "in its coordinates")
     common = dict(reference=solid, max_atoms_outside=max_atoms_outside, relax_steps=relax_steps,
-                  add_hydrogens=add_hydrogens)
+                  add_hydrogens=add_hydrogens, standardize=bool(standardize))
     if max_receptor_clashes is not None:
         mcg_receptor.check_max_receptor_clashes(max_receptor_clashes)
         if receptor is None:
