@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import relief_ref as RR
+from composed_cases import carved_pocket as _carved_pocket
 from conftest import load_golden
 from ml_conformer_generator_amd import receptor as RC
 
@@ -180,20 +181,6 @@ def _posed_setup(monkeypatch):
     base = gen.generate_conformers(**kw)
     assert base and all(m.receptor_clashes is None for m in base)
     return gen, ref, kw, base
-
-
-def _carved_pocket(ref, base):
-    """The recipe's lattice around the posed molecules and the reference, carved 3.8 A around all of their atoms, then
-    shifted by 1.5 A along x so that the poses clash with one wall (and a move of 1.5 A clears them again)."""
-    g = np.random.default_rng(77)
-    atoms = torch.cat([ref.float()] + [m.coords for m in base if m.pose is not None]).double().numpy()
-    lo, hi = atoms.min(0) - 8.0, atoms.max(0) + 8.0
-    axes = [np.arange(lo[d], hi[d], 2.6) for d in range(3)]
-    pts = np.stack(np.meshgrid(*axes, indexing="ij"), -1).reshape(-1, 3)
-    pts = pts + g.normal(size=pts.shape) * 0.3
-    near = np.linalg.norm(pts[:, None, :] - atoms[None, :, :], axis=2).min(axis=1)
-    pts = pts[near > 3.8] + np.array([1.5, 0.0, 0.0])
-    return torch.from_numpy(pts.astype(np.float32)), torch.full((len(pts),), 6)
 
 
 def _measured(m):

@@ -175,36 +175,17 @@ WIDTH = 16
 
 
 def _substituted(monkeypatch, finish_all=False):
-    """The shared generator with the cases' chemistry substituted at its seams: the sampler stage (`edm_tensors`) returns
-    the rows' coordinates and one-hot elements, and the bond write-back is given the rows' codes in place of the GCN's
-    argmax - the real hand-off, GCN, write-back and proxy run on them.  Returns (generator, call keywords, the rows'
+    """The shared generator with the cases' chemistry substituted at its seams (`composed_cases.substituted`), the rows at
+    seeded Gaussian clouds: the coordinates play no part in the verdict.  Returns (generator, call keywords, the rows'
     full tensors on the host, the proxy's own flags for them)."""
-    from test_shape_frames_gpu import _gen
-    from ml_conformer_generator_amd import conformer_generator as CG
-    gen = _gen()
+    from composed_cases import substituted
     cases = C.cases()
     rng = np.random.RandomState(3)
     items = [dict(cases[k], xyz=(rng.standard_normal((cases[k]["mol"][2], 3)) * 2.5).astype(np.float32)) for k in ROWS]
-    xyz, z, bonds, n = (torch.from_numpy(t) for t in C.pad_batch(items, 42, WIDTH))
-    h = torch.zeros(len(ROWS), WIDTH, 8)
-    for b in range(len(ROWS)):
-        for a in range(int(n[b])):
-            h[b, a, list(gen.class_z).index(int(z[b, a]))] = 1.0
-    mask = (torch.arange(WIDTH).view(1, -1) < n.view(-1, 1)).float().unsqueeze(-1)
-
-    def edm_tensors(**kw):
-        ids = kw.get("sample_ids")
-        rows = torch.arange(kw["n_samples"]) if ids is None else torch.as_tensor(ids).long().cpu()
-        return xyz[rows].to(DEV), h[rows].to(DEV), mask[rows].to(DEV)
-    real_writeback = CG.bond_writeback_hip
-    monkeypatch.setattr(gen, "edm_tensors", edm_tensors)
-    monkeypatch.setattr(CG, "bond_writeback_hip", lambda bond, el, ng: real_writeback(bonds.to(bond.device), el, ng))
-    if finish_all:
-        monkeypatch.setattr(CG, "_finish", lambda mols, og, use_rdkit=None: (list(mols), 1.0))
+    gen, full, proxy = substituted(monkeypatch, items, WIDTH, finish_all)
     kw = dict(reference_context=torch.tensor([50.0, 100.0, 130.0]), n_atoms=20, n_samples=len(ROWS), variance=2,
               optimise_geometry=False)
-    _, proxy = real_writeback(bonds.to(DEV), z.long().to(DEV), n.to(DEV))
-    return gen, kw, dict(xyz=xyz, z=z, bonds=bonds, n=n), proxy.cpu().tolist()
+    return gen, kw, full, proxy
 
 
 def _handoff_kept(last_batch, full):
