@@ -712,6 +712,52 @@ int mcg_standardize_graphs(const float* coords, const int32_t* z, const int8_t* 
                            int8_t* bonds_out, int8_t* kekule_out, int32_t* atom_map_out, int32_t* n_out,
                            int32_t* n_fragments_out, int32_t* atoms_removed_out, int32_t* status_out, void* stream);
 
+/* ---- Electrostatic similarity ("Electrostatic similarity"): partial charges of B molecular graphs by
+ * iterative electronegativity equalisation (PEOE) and the Tanimoto of the Coulomb overlap of Gaussian-smeared point
+ * charges with a reference's.  The definition is this package's OWN (DESIGN.md states it in full): not RDKit's
+ * ComputeGasteigerCharges, not a vendor's electrostatic score - no formal charges, no protonation states.
+ *   mcg_charges_peoe:   z[B,W] atomic numbers, bonds[B,W,W] symmetric bond codes (1 / 2 / 3 / 4 aromatic; any other value
+ *                       is no bond), n_nodes_dev[b] real atoms (device memory, clamped to [0, W] on the device; the
+ *                       diagonal and everything at or beyond n_b is ignored, whatever it holds); types[B,W],
+ *                       ring_mask[B, MCG_PHARM_MAX_RINGS] and n_rings[B] as mcg_pharm_perceive wrote them for the same z,
+ *                       bonds and n_nodes.  Per heavy atom nH and the class linear / planar / tetrahedral are those of
+ *                       mcg_hydrogens_place; chi(q) = a + b q + c q^2 with the Gasteiger-Marsili (a, b, c) of the element
+ *                       and class (H, C, N, O, F, P, S, Cl, Br), chi+ = a + b + c (H: 20.02); all charges start at 0;
+ *                       steps k = 1..6, each from the charges of the step before: an atom adds, in fp32 and in ascending
+ *                       neighbour index, f_ij = (chi_j - chi_i) / (chi+_i if chi_j > chi_i else chi+_j) over its bonded
+ *                       atoms (any code once), then nH f_iH for its hydrogens, which share one charge that moves by
+ *                       -f_iH; every update is multiplied by 0.5^k.  q_out[B,W]: the heavy atoms' charges;
+ *                       qh_out[B,W]: the charge of EACH hydrogen of that atom, 0 where nH = 0; nh_out[B,W]: nH;
+ *                       status_out[b]: 0, or 1 for a row with a real atom of an element without parameters - its real
+ *                       atoms get NaN in q_out and qh_out, the other rows are unaffected.  Every element of every output
+ *                       is written: 0 at and beyond a row's atoms.  One 64-lane wave per molecule, four molecules per
+ *                       workgroup, no atomics, no scratch; products and sums rounded one by one in one order: a row's
+ *                       outputs have the same bits whatever the batch, its row and the padded width.
+ *   mcg_esp_overlap:    ref_xyz[P,3], ref_q[P] the reference's charge points; xyz[B,PW,3], q[B,PW] the candidates',
+ *                       n_points[b] real points (device memory, clamped to [0, PW]).  E(X, Y) = sum_i sum_j qx_i qy_j
+ *                       K(|x_i - y_j|), K(r) = erff(mu r) / r, below r = 1e-3: mu (2 / sqrt pi) (1 - (mu r)^2 / 3), r =
+ *                       sqrtf(dx*dx + dy*dy + dz*dz) in fp32 in exactly that order (no contraction); a term is (qx_i *
+ *                       qy_j) * K in fp32; thread t of the row's 256 adds the terms of candidate point t in fp64 in
+ *                       ascending j, the threads' sums are added in fp64 by one binary tree (t takes t + 128, + 64, ...
+ *                       + 1) and rounded to fp32 once.  cross[b] = E(reference, b), self[b] = E(b, b) (i = j included),
+ *                       tanimoto[b] = cross / ((e_rr + self) - cross) in fp32 with e_rr = *e_rr (device memory; NULL: the
+ *                       row's own self), 0 where that denominator is below 1e-12.  A row with a non-finite coordinate or
+ *                       charge on a real point has NaN in all three, the other rows unaffected.  The reference run as its
+ *                       own one-row batch gives E(R,R) as self[0], by the same code.  One 256-thread workgroup per row; a
+ *                       row's outputs have the same bits whatever the batch, its row and PW.
+ * B = 0 launches nothing.  MCG_ERR_ARG, nothing launched: a null required buffer, B outside 0..MCG_CHARGES_MAX_B /
+ * 0..MCG_ESP_MAX_B, W outside 1..MCG_CHARGES_MAX_ATOMS, P or PW outside 1..MCG_ESP_MAX_POINTS, mu not positive and finite. */
+#define MCG_CHARGES_MAX_ATOMS 64
+#define MCG_CHARGES_MAX_B 16384
+#define MCG_ESP_MAX_POINTS 256 /* 64 heavy atoms + 3 x 64 hydrogens */
+#define MCG_ESP_MAX_B 16384
+int mcg_charges_peoe(const int32_t* z, const int8_t* bonds, const int32_t* n_nodes_dev, const uint8_t* types,
+                     const uint64_t* ring_mask, const int32_t* n_rings, int B, int W /*z, bonds, types width*/,
+                     float* q_out, float* qh_out, int32_t* nh_out, int32_t* status_out, void* stream);
+int mcg_esp_overlap(const float* ref_xyz, const float* ref_q, int P, const float* xyz, const float* q,
+                    const int32_t* n_points, int B, int PW /*points per row*/, float mu, const float* e_rr /*optional*/,
+                    float* cross_out, float* self_out, float* tanimoto_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,9 @@ forced by the scope of this build:
       `pharmacophore_scores`, `reference_pharmacophore`, `min_pharmacophore_tanimoto`, `rank_by`: does the posed molecule
       keep the reference's interaction pattern - the overlap of its pharmacophore features with the reference's; a
       filter; ranking by shape + pharmacophore score;
+      `electrostatic_scores`, `reference_charges`, `min_electrostatic_tanimoto`, `partial_charges`: does the posed molecule
+      present the reference's charge distribution - partial charges by electronegativity equalisation and the Tanimoto
+      of their Coulomb overlap with the reference's; a filter; `rank_by="electrostatic"`;
   * `reference_shape`, `shape_density` (every generation entry): a watertight triangle mesh - an STL file, a (vertices,
     faces) pair - as the reference, what the reference's notebook does with `trimesh` (`mesh.py`, no `trimesh` needed);
     the shape options then score, pose and select against the solid, and `max_atoms_outside` filters on the posed atoms
@@ -85,6 +88,7 @@ from . import rdkit_order
 from . import receptor as mcg_receptor
 from . import fingerprint as mcg_fp
 from . import geometry as mcg_geometry
+from . import electrostatics as mcg_esp
 from . import hydrogens as mcg_hydrogens
 from . import pharmacophore as mcg_pharm
 from . import standardize as mcg_standardize
@@ -366,10 +370,24 @@ class MLConformerGenerator(torch.nn.Module):
 
     # the hydrogen step
     def _add_hydrogens(self, coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
-                       n_nodes: torch.Tensor) -> dict:
+                       n_nodes: torch.Tensor, perceived=None) -> dict:
         """The explicit hydrogens of padded heavy-atom coordinates and graphs (`hydrogens.add_hydrogens`, unchecked: the
-        elements come from the validated decoder, the codes from the bond write-back; device tensors)."""
-        return mcg_hydrogens.add_hydrogens(coords, atomic_numbers, bond_orders, n_nodes, self.device, check=False)
+        elements come from the validated decoder, the codes from the bond write-back; device tensors); `perceived`: a
+        `_pharm_perceive` result for the same graphs, when the electrostatic step has one."""
+        return mcg_hydrogens.add_hydrogens(coords, atomic_numbers, bond_orders, n_nodes, self.device, check=False,
+                                           perceived=perceived)
+
+    # the electrostatic step
+    def _peoe_charges(self, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor,
+                      perceived=None):
+        """The partial charges of padded graphs (`electrostatics.partial_charges`, unchecked: the generator's own graphs);
+        `perceived`: a `_pharm_perceive` result for the same graphs."""
+        return mcg_esp.partial_charges(atomic_numbers, bond_orders, n_nodes, self.device, check=False, perceived=perceived)
+
+    def _esp_score(self, reference_points, points: torch.Tensor, charges: torch.Tensor, n_points: torch.Tensor):
+        """Electrostatic Tanimoto [B] fp32 of posed charge points against the reference's
+        (`electrostatics.electrostatic_tanimoto`)."""
+        return mcg_esp.electrostatic_tanimoto(reference_points, points, charges, n_points, self.device)["tanimoto"]
 
     # the standardisation step
     def _standardize(self, coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
@@ -574,7 +592,9 @@ class MLConformerGenerator(torch.nn.Module):
                             relax_geometry: Union[bool, int] = False, pharmacophore_scores: bool = False,
                             reference_pharmacophore=None, min_pharmacophore_tanimoto: Optional[float] = None,
                             rank_by: str = "shape", relieve_clashes: Union[bool, int] = False,
-                            add_hydrogens: bool = False, standardize: bool = False) -> List:
+                            add_hydrogens: bool = False, standardize: bool = False,
+                            electrostatic_scores: bool = False, reference_charges=None,
+                            min_electrostatic_tanimoto: Optional[float] = None, partial_charges: bool = False) -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
@@ -713,8 +733,30 @@ class MLConformerGenerator(torch.nn.Module):
         `atoms_removed`, `n_fragments`, `atom_map` (each atom's index in the graph as generated) and
         `kekule_bond_orders`; `to_molblock(kekulize=True)` writes the Kekule form.  `last_batch` keeps what the hand-off
         and the GCN wrote and gains `standardized`.  All of these are None in a call without the option.
+        `electrostatic_scores=True` (needs `overlay=True`; records path only): does the posed molecule present the
+        reference's charge distribution?  Every returned record carries `electrostatic_tanimoto` - the Tanimoto of the
+        Coulomb overlap of Gaussian-smeared partial charges on its heavy atoms and placed hydrogens, as posed, with the
+        reference's, in [-1/3, 1]; NaN where posing failed and where the molecule holds an element without charge
+        parameters.  The charges are this package's OWN definition (`electrostatics.py`, DESIGN.md section 6,
+        "Electrostatic similarity"): iterative electronegativity equalisation on the returned heavy-atom graph with the
+        hydrogens of `add_hydrogens`' count rule - NOT RDKit's Gasteiger charges, not a vendor's electrostatic score; no
+        formal charges, no protonation states.  The reference's charge points are `reference_charges` - a sequence of
+        (charge, (x, y, z)) in the reference's coordinates (`electrostatics.load_reference_charges`; the only way with a
+        `reference_shape` or a reference without bonds) - or are computed from `reference_graph`, else from
+        `reference_conformer` where it is a Mol with bonds, at the reference conformer's heavy-atom coordinates with its
+        hydrogens placed by the same kernel.  The step runs behind the gather, beside the pharmacophore step; with
+        `add_hydrogens` the hydrogens are placed once for both.
+        `min_electrostatic_tanimoto=t` (implies the score; t in [-1, 1]): drop the molecules whose
+        `electrostatic_tanimoto` is below t, NaN or missing, right behind `min_pharmacophore_tanimoto`.
+        `rank_by="electrostatic"` (needs a shape score and the electrostatic score): `unique`, the diversity walk and
+        `top_k` rank by `shape_tanimoto + electrostatic_tanimoto`; `min_shape_tanimoto` still thresholds shape alone.
+        `partial_charges=True` (records path only; needs no reference and no pose): every returned record carries
+        `partial_charges` ([n] fp32, the heavy atoms) and `hydrogen_charges` ([n] fp32, the charge of EACH hydrogen of
+        that atom, 0 where it has none); NaN where the molecule holds an element without parameters.
+        `to_xyz_block(charges=True)` writes them as a fifth column.  All of these are None in a call without the option.
         Order of the stages: validity, `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`,
-        `min_pharmacophore_tanimoto`, `unique`, then the selection (threshold, exclusion, `top_k`).  The filters only
+        `min_pharmacophore_tanimoto`, `min_electrostatic_tanimoto`, `unique`, then the selection (threshold, exclusion,
+        `top_k`).  The filters only
         remove molecules.
         Refused with ValueError before any device work: a chemical option that is not a bool / a real number in (0, 1],
         a chemical score without a reference graph, a `reference_graph` that `fingerprint.mol_graph` refuses or that has no
@@ -731,7 +773,10 @@ class MLConformerGenerator(torch.nn.Module):
         pharmacophore_scores that is not a bool, without overlay or without a source of the reference's features, a
         `reference_pharmacophore` that `load_reference_features` refuses or that no option reads, a reference graph whose
         heavy-atom count differs from the reference conformer's, min_pharmacophore_tanimoto outside [0, 1], and a
-        `rank_by` other than "shape" or "combo", or "combo" without both scores, and add_hydrogens that is not a bool or on
+        `rank_by` other than "shape", "combo" or "electrostatic", or "combo" / "electrostatic" without both of its scores,
+        electrostatic_scores or partial_charges that is not a bool or on a generator with a finisher, electrostatic scores
+        without overlay or without a source of the reference's charges, a `reference_charges` that
+        `load_reference_charges` refuses or that no option reads, min_electrostatic_tanimoto outside [-1, 1], and add_hydrogens that is not a bool or on
         a generator with a finisher, RDKit's or a custom one (on Mols use `Chem.AddHs(mol, addCoords=True)`), and standardize
         that is not a bool or on a generator with a finisher (RDKit's finisher runs `standardize_mol` itself).  A reference
         graph in which no feature is found is refused where it is perceived, behind the generation."""
@@ -743,7 +788,8 @@ class MLConformerGenerator(torch.nn.Module):
                                         max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
                                         reference_context, relax_geometry, pharmacophore_scores,
                                         reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes,
-                                        add_hydrogens, standardize)
+                                        add_hydrogens, standardize, electrostatic_scores, reference_charges,
+                                        min_electrostatic_tanimoto, partial_charges)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         keyed = () if sample_seed is None else (sample_seed, None)   # unseeded: the positional call of before
@@ -779,7 +825,10 @@ class MLConformerGenerator(torch.nn.Module):
                                     relax_geometry: Union[bool, int] = False, pharmacophore_scores: bool = False,
                                     reference_pharmacophore=None, min_pharmacophore_tanimoto: Optional[float] = None,
                                     rank_by: str = "shape", relieve_clashes: Union[bool, int] = False,
-                                    add_hydrogens: bool = False, standardize: bool = False) -> List:
+                                    add_hydrogens: bool = False, standardize: bool = False,
+                                    electrostatic_scores: bool = False, reference_charges=None,
+                                    min_electrostatic_tanimoto: Optional[float] = None,
+                                    partial_charges: bool = False) -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -799,6 +848,8 @@ class MLConformerGenerator(torch.nn.Module):
         `max_receptor_clashes`, `chemical_scores`, `reference_graph`, `max_chemical_tanimoto`, `unique`,
         `max_pairwise_chemical_tanimoto`, `reference_shape`, `shape_density`, `max_atoms_outside`, `relax_geometry`,
         `pharmacophore_scores`, `reference_pharmacophore`, `min_pharmacophore_tanimoto`, `rank_by`, `relieve_clashes`,
+        `electrostatic_scores`, `reference_charges`, `min_electrostatic_tanimoto`, `partial_charges` (behind the gather, on
+        the rows a rank returns, like the hydrogens),
         `add_hydrogens` (placed behind the gather, on the rows a rank returns), `standardize` (on each rank's own shard,
         before the gather; its per-sample tensors travel with the rest, one collective each): as in
         `generate_conformers` (every rank loads the mesh and computes its occupancy itself).  The fingerprints are computed behind the gather,
@@ -821,7 +872,8 @@ class MLConformerGenerator(torch.nn.Module):
                                         max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
                                         reference_context, relax_geometry, pharmacophore_scores,
                                         reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes,
-                                        add_hydrogens, standardize)
+                                        add_hydrogens, standardize, electrostatic_scores, reference_charges,
+                                        min_electrostatic_tanimoto, partial_charges)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)

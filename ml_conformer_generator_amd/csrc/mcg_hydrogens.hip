@@ -25,6 +25,7 @@
 #include "mcg_common.h"
 #include "mcg_api_internal.h"
 #include "mcg_elements.h"
+#include "mcg_graph_rules.h"
 
 #include <math.h>
 
@@ -35,12 +36,12 @@ namespace {
 typedef unsigned long long u64;
 
 constexpr int HY_MAXW = MCG_HYDROGENS_MAX_ATOMS;     // atoms per molecule: one lane and one mask bit each
-constexpr int HY_STRIDE = 68;                        // bytes per bond-code row in LDS (17 dwords)
+constexpr int HY_STRIDE = MCG_CODE_STRIDE;            // bytes per bond-code row in LDS
 constexpr int HY_SLOTS = 3 * HY_MAXW;                // hydrogens per molecule: 3 per atom that has a neighbour (4 if n == 1)
 constexpr int HY_DELTAS = 12;                        // rotor candidates: 0, 30, ... 330 degrees
 constexpr int HY_MAX_RINGS = MCG_PHARM_MAX_RINGS;
 
-enum : int { HY_TETRAHEDRAL = 0, HY_PLANAR = 1, HY_LINEAR = 2 };
+enum : int { HY_TETRAHEDRAL = MCG_CLASS_TETRAHEDRAL, HY_PLANAR = MCG_CLASS_PLANAR, HY_LINEAR = MCG_CLASS_LINEAR };
 
 constexpr float HY_XH = 0.31f;                       // X-H = rcov(Z) + 0.31 A
 constexpr float HY_DEGENERATE = 1e-3f;
@@ -89,16 +90,6 @@ __device__ __forceinline__ V3 perp(V3 a) {
 }
 __device__ __forceinline__ V3 xyz(float4 p) { return v3(p.x, p.y, p.z); }
 
-__device__ __forceinline__ int valence0(int z) {
-    switch (z) {
-        case 6: case 14: return 4;
-        case 5: case 7: case 15: case 33: return 3;
-        case 8: case 16: case 34: return 2;
-        case 9: case 17: case 35: case 53: return 1;
-        default: return 0;
-    }
-}
-
 // hydrogen m of a rotor at candidate d (delta = 30 d degrees): x + L (cos t a + sin t (cos phi e1 + sin phi e2)), t the
 // H-X-j angle, phi = 180 + 120 m + delta (tetrahedral) or 180 + 180 m + delta (planar)
 __device__ __forceinline__ V3 rotor_hydrogen(V3 x, V3 a, V3 e1, V3 e2, float len, bool planar, int m, int d) {
@@ -136,12 +127,7 @@ __global__ __launch_bounds__(HY_MAXW) void k_hydrogens_place(
     const bool real = a < n;
 
     // the molecule's W x W codes -> LDS rows; the diagonal, the padding and every code outside 1..4 become 0
-    const int8_t* src = bonds + (size_t)b * W * W;
-    for (int idx = a; idx < W * W; idx += HY_MAXW) {
-        const int i = idx / W, j = idx - i * W;
-        const uint8_t c = (uint8_t)src[idx];
-        code[i * HY_STRIDE + j] = (i < n && j < n && i != j && c >= 1 && c <= 4) ? c : (uint8_t)0;
-    }
+    mcg_stage_codes(code, bonds + (size_t)b * W * W, W, n, a, HY_MAXW);
     float4 xa = make_float4(0.f, 0.f, 0.f, 0.f);
     if (real) {
         const float* p = coords + ((size_t)b * N + a) * 3;
@@ -160,38 +146,15 @@ __global__ __launch_bounds__(HY_MAXW) void k_hydrogens_place(
 
     const int za = real ? z[(size_t)b * W + a] : 0;
     const int ta = real ? types[(size_t)b * W + a] : 0;
-    const uint8_t* row = code + a * HY_STRIDE;
-    u64 mine = 0ull;
-    int deg = 0, v2 = 0, n2 = 0, n3 = 0, narom = 0;
-    if (real) {
-        for (int j = 0; j < n; ++j) {
-            const int c = row[j];
-            if (c != 0) {
-                mine |= 1ull << j;
-                ++deg;
-                v2 += c == 1 ? 2 : c == 2 ? 4 : c == 3 ? 6 : 3;
-                n2 += c == 2 ? 1 : 0;
-                n3 += c == 3 ? 1 : 0;
-                narom += c == 4 ? 1 : 0;
-            }
-        }
-    }
+    // the count and class rules (mcg_graph_rules.h, shared with k_charges_peoe)
+    const McgBondTally tally = real ? mcg_bond_tally(code + a * HY_STRIDE, n) : McgBondTally{0ull, 0, 0, 0, 0, 0};
+    const u64 mine = tally.mask;
+    const int deg = tally.deg;
     nbr[a] = mine;
-    const bool has24 = n2 >= 1 || narom >= 1;
-    const u64 m_has24 = __ballot(real && has24);
-    const u64 m_ring_n = __ballot(real && za == 7 && narom >= 1 && deg == 2 && (ta & 1) != 0);
-    const int hyb = (n3 >= 1 || n2 >= 2) ? HY_LINEAR
-                    : (has24 || ((za == 7 || za == 8) && (mine & m_has24) != 0ull)) ? HY_PLANAR : HY_TETRAHEDRAL;
-    int nh = real ? max(0, (2 * valence0(za) - v2) / 2) : 0;
-    {   // one aromatic N-H per 5-ring, in list order: the same walk in every lane
-        u64 given = 0ull;
-        for (int r = 0; r < nr; ++r) {
-            const u64 m = rings[r];
-            const u64 cand = m & m_ring_n;
-            if (__popcll(m) == 5 && (m & given) == 0ull && cand != 0ull) given |= cand & (~cand + 1ull);
-        }
-        if ((given >> a & 1ull) != 0ull) nh = 1;
-    }
+    const u64 m_has24 = __ballot(real && mcg_has_code_2_or_4(tally));
+    const u64 m_ring_n = __ballot(real && mcg_ring_nh_candidate(za, tally, ta));
+    const int hyb = mcg_parent_class(za, tally, m_has24);
+    int nh = mcg_implicit_hydrogens(real, a, za, tally, rings, nr, m_ring_n);
 
     // how many of them this definition places
     const int k = deg;

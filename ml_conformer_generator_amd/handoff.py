@@ -61,6 +61,9 @@ class Measured:
     n_fragments: Optional[int] = None
     atom_map: Optional[List[int]] = None
     kekule_bond_orders: Optional[object] = None   # [n,n] int8, host - or (batch [B,W,W], row, n), sliced on first read
+    electrostatic_tanimoto: Optional[float] = None
+    partial_charges: Optional[object] = None      # [n] fp32, host - or (batch [B,W], row, n), sliced on first read
+    hydrogen_charges: Optional[object] = None     # [n] fp32, host - likewise
 
 
 _UNMEASURED = Measured()          # shared by every record that carries no values: never written to
@@ -78,8 +81,12 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
     (`GeneratedMolecule.hydrogen_coords`).  A negative `receptor_hydrogen_clashes`: not measured.
     The standardisation of a call with `standardize` comes as `atoms_removed` [n], `n_fragments` [n], `atom_map` [n,W] (-1
     beyond a row's atoms) and `kekule_bond_orders` [n,W,W] (all four or none); a record's `kekule_bond_orders` is left as
-    (the one host copy, row, atom count) and sliced on first read."""
-    hyd = {k: values.get(k) for k in ("hydrogen_coords", "hydrogen_parents", "atom_map", "kekule_bond_orders")}
+    (the one host copy, row, atom count) and sliced on first read.
+    The charges of a call with `partial_charges` come as `partial_charges` [n,W] and `hydrogen_charges` [n,W] fp32 (both or
+    neither), +inf at and beyond a row's atoms (a real atom's charge is finite or NaN); a record's fields are left as (the
+    one host copy, row, atom count) and sliced on first read.  `electrostatic_tanimoto` [n] fp32 is taken as it comes."""
+    hyd = {k: values.get(k) for k in ("hydrogen_coords", "hydrogen_parents", "atom_map", "kekule_bond_orders",
+                                      "partial_charges", "hydrogen_charges")}
     cols = {k: v.cpu().tolist() for k, v in values.items() if v is not None and k != "pose" and k not in hyd}
     if values.get("pose") is not None:
         poses = values["pose"].cpu().to(torch.float32)
@@ -115,6 +122,11 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
         cols["atom_map"] = [[a for a in row if a >= 0] for row in hyd["atom_map"].cpu().tolist()]
         orders = hyd["kekule_bond_orders"].cpu().to(torch.int8)
         cols["kekule_bond_orders"] = [(orders, b, len(kept)) for b, kept in enumerate(cols["atom_map"])]
+    if hyd["partial_charges"] is not None:
+        q, qh = hyd["partial_charges"].cpu().to(torch.float32), hyd["hydrogen_charges"].cpu().to(torch.float32)
+        counts = (~torch.isinf(q)).sum(dim=1).tolist()
+        cols["partial_charges"] = [(q, b, k) for b, k in enumerate(counts)]
+        cols["hydrogen_charges"] = [(qh, b, k) for b, k in enumerate(counts)]
     return [Measured(**{k: col[b] for k, col in cols.items()}) for b in range(n)]
 
 
@@ -145,7 +157,11 @@ class GeneratedMolecule:
     `atoms_removed` / `n_fragments` / `atom_map` / `kekule_bond_orders`: what the standardisation of a call with
     `standardize` did to it (`standardize.py`: the package's own definition, NOT RDKit's FragmentParent / Kekulize /
     SanitizeMol) - the record then IS the largest fragment - else None.  `to_molblock(kekulize=True)` writes the Kekule
-    form."""
+    form.
+    `electrostatic_tanimoto`: the similarity of its charge distribution, as posed, to the reference's when the call asked
+    for `electrostatic_scores`; `partial_charges` / `hydrogen_charges`: its partial charges when the call asked for
+    `partial_charges` (`electrostatics.py`: the package's own definition, NOT RDKit's Gasteiger charges), else None;
+    `to_xyz_block(charges=True)` writes them."""
     __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_measured")
 
     def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True,
@@ -162,6 +178,35 @@ class GeneratedMolecule:
         m._sid = b if sample_id is None else sample_id
         m._measured = measured
         return m
+
+    @property
+    def electrostatic_tanimoto(self) -> Optional[float]:
+        """Tanimoto of the Coulomb overlap of this molecule's Gaussian-smeared partial charges - heavy atoms and placed
+        hydrogens, as posed - with the reference's, in [-1/3, 1] (`electrostatics.py`: the package's own definition - NOT
+        RDKit's Gasteiger charges, not a vendor's electrostatic score) when the call asked for `electrostatic_scores` or
+        `min_electrostatic_tanimoto`; NaN where posing failed or the molecule holds an element without charge parameters;
+        None otherwise."""
+        return self._measured.electrostatic_tanimoto
+
+    @property
+    def partial_charges(self) -> Optional[torch.Tensor]:
+        """[n] fp32 (CPU): the partial charge of each heavy atom by the electronegativity equalisation of
+        `electrostatics.py` (the package's own definition, NOT RDKit's Gasteiger charges; its hydrogens' charges are in
+        `hydrogen_charges`; a view into the batch's host tensor, sliced on first access) when the call asked for
+        `partial_charges`; NaN throughout where the molecule holds an element without parameters; None otherwise."""
+        q = self._measured.partial_charges
+        if isinstance(q, tuple):
+            q = self._measured.partial_charges = q[0][q[1], : q[2]]
+        return q
+
+    @property
+    def hydrogen_charges(self) -> Optional[torch.Tensor]:
+        """[n] fp32 (CPU): the partial charge of EACH hydrogen of that heavy atom, 0 where it has none - with
+        `partial_charges` and the hydrogen counts the molecule's charges sum to 0; None where `partial_charges` is None."""
+        q = self._measured.hydrogen_charges
+        if isinstance(q, tuple):
+            q = self._measured.hydrogen_charges = q[0][q[1], : q[2]]
+        return q
 
     @property
     def atoms_removed(self) -> Optional[int]:
@@ -421,15 +466,27 @@ class GeneratedMolecule:
         lines.append("M  END")
         return "\n".join(lines) + "\n"
 
-    def to_xyz_block(self, hydrogens: bool = False) -> str:
+    def to_xyz_block(self, hydrogens: bool = False, charges: bool = False) -> str:
         """XYZ block of the heavy atoms; `hydrogens=True`: the record's explicit hydrogens (`add_hydrogens`) follow them;
-        ValueError where the record carries none."""
+        ValueError where the record carries none.  `charges=True`: a fifth column holds each atom's partial charge
+        (`partial_charges`; a hydrogen's is its parent's `hydrogen_charges`), so with `hydrogens=True` the column sums to
+        0 for a molecule all of whose hydrogens were placed; ValueError where the record carries no charges."""
         atoms = list(zip(self.symbols, self.coords.tolist()))
+        column = None
+        if charges:
+            q, qh = self.partial_charges, self.hydrogen_charges
+            if q is None or qh is None:
+                raise ValueError("this record carries no charges: generate with partial_charges=True")
+            column = q.tolist()
         if hydrogens:
-            atoms += [("H", c) for c in self._hydrogens()[0]]
+            xyz, parents = self._hydrogens()
+            atoms += [("H", c) for c in xyz]
+            if charges:
+                column += [float(qh[p]) for p in parents]
         lines = [f"{len(atoms)}", ""]
-        for s, c in atoms:
-            lines.append("%s %.9f %.9f %.9f" % (s, c[0], c[1], c[2]))
+        for k, (s, c) in enumerate(atoms):
+            line = "%s %.9f %.9f %.9f" % (s, c[0], c[1], c[2])
+            lines.append(line if column is None else line + " %.6f" % column[k])
         return "\n".join(lines) + "\n"
 
 
@@ -550,7 +607,10 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                            receptor_hydrogen_clashes: Optional[torch.Tensor] = None,
                            atoms_removed: Optional[torch.Tensor] = None, n_fragments: Optional[torch.Tensor] = None,
                            atom_map: Optional[torch.Tensor] = None,
-                           kekule_bond_orders: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
+                           kekule_bond_orders: Optional[torch.Tensor] = None,
+                           electrostatic_tanimoto: Optional[torch.Tensor] = None,
+                           partial_charges: Optional[torch.Tensor] = None,
+                           hydrogen_charges: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
     (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
     (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records).
@@ -572,7 +632,10 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     `receptor_hydrogen_clashes[b]`: row b's hydrogens clashing with the receptor (negative: its pose failed, None).
     `atoms_removed[b]` / `n_fragments[b]` / `atom_map[b]` [W] (-1 beyond the row's atoms) / `kekule_bond_orders[b]` [W,W]:
     row b's standardisation as `standardize.standardize_graphs` returns it (all four or none; None: a call without
-    `standardize`).
+    `standardize`).  `electrostatic_tanimoto[b]`: row b's electrostatic similarity to the reference (None: a call without
+    `electrostatic_scores`); `partial_charges[b]` [W] / `hydrogen_charges[b]` [W]: row b's partial charges as
+    `electrostatics.partial_charges` returns them, +inf at and beyond the row's atoms (both or neither; None: a call
+    without `partial_charges`).
     The value keywords are the fields of `Measured`
     and go to `measured_from_tensors`; a call with no ids and no values builds the views and nothing else."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
@@ -586,7 +649,8 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                   hydrogen_coords=hydrogen_coords, hydrogen_parents=hydrogen_parents,
                   hydrogens_unplaced=hydrogens_unplaced, receptor_hydrogen_clashes=receptor_hydrogen_clashes,
                   atoms_removed=atoms_removed, n_fragments=n_fragments, atom_map=atom_map,
-                  kekule_bond_orders=kekule_bond_orders)
+                  kekule_bond_orders=kekule_bond_orders, electrostatic_tanimoto=electrostatic_tanimoto,
+                  partial_charges=partial_charges, hydrogen_charges=hydrogen_charges)
     if sample_ids is None and all(v is None for v in values.values()):
         return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
     flags = valid.cpu().tolist()

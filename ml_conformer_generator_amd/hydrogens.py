@@ -145,9 +145,10 @@ def implicit_counts(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_n
 
 @torch.no_grad()
 def add_hydrogens(coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor,
-                  device=None, check: bool = True, return_rotors: bool = False) -> Dict[str, torch.Tensor]:
+                  device=None, check: bool = True, return_rotors: bool = False, perceived=None) -> Dict[str, torch.Tensor]:
     """The explicit hydrogens of B molecules by this module's definition (NOT RDKit's AddHs): one
-    `pharmacophore.perceive_features` launch, then one `mcg_hydrogens_place` launch.  `coords` [B,N,3] fp32 heavy-atom
+    `pharmacophore.perceive_features` launch (`perceived`: its result for the same graphs, when the caller already has
+    it), then one `mcg_hydrogens_place` launch.  `coords` [B,N,3] fp32 heavy-atom
     coordinates, `atomic_numbers` [B, >= W], `bond_orders` [B,W,W] (symmetric codes 0 none / 1 / 2 / 3 / 4 aromatic),
     `n_nodes` [B] real atoms each, at most min(N, W); W <= 64.  Device tensors:
       coords [B,Hmax,3]   the hydrogens, in ascending order of their parent, then of m; Hmax is the batch's largest count,
@@ -196,7 +197,7 @@ def add_hydrogens(coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_order
         if bool((real & ~known[zd.to(torch.long).clamp(min=0, max=known.numel() - 1)]).any()):
             raise ValueError("add_hydrogens knows the elements "
                              f"{[ELEMENTS[k][0] for k in sorted(ELEMENTS)]} only (no covalent radius for another Z)")
-    types, rings, count = mcg_pharm.perceive_features(zd, bd, nn, dev)
+    types, rings, count = perceived if perceived is not None else mcg_pharm.perceive_features(zd, bd, nn, dev)
     HW = slots(W)
     h_xyz = torch.empty(B, HW, 3, dtype=torch.float32, device=dev)
     parents = torch.empty(B, HW, dtype=torch.int32, device=dev)

@@ -17,11 +17,14 @@ Stages, in this order:
        features: one perceive and one score launch over the rows, one each for the reference (`pharmacophore`); and
        the explicit hydrogens of the returned coordinates: one perceive and one placement launch over the rows, plus -
        with a receptor - the receptor kernel over the hydrogens (`hydrogens`; records only: refused with a finisher);
+       and the electrostatic step (`electrostatics`; records only): one perceive launch, the hydrogens placed once - the
+       placement of `add_hydrogens` is reused when that is on too - one charge launch and, with `electrostatic_scores`,
+       the overlap launches against the reference's charge points;
     5. the values are attached - each molecule's `handoff.Measured`, behind a record's properties or written onto the
        Mol by `rdkit_finish.tag_measured` (Mols lose their properties in the object gather) - and validity is taken
        (`last_valid_fraction`);
     6. `select`, written once for both paths: `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`,
-       `min_pharmacophore_tanimoto`, `unique`, then the
+       `min_pharmacophore_tanimoto`, `min_electrostatic_tanimoto`, `unique`, then the
        threshold / sphere exclusion / `top_k` walk of `cheminformatics.select_diverse`.  The two pair matrices are
        computed only when their threshold is set, over the rows that survived the filters.
 A call with no option on takes none of these steps: its records / live Mols are returned as they come.
@@ -31,7 +34,7 @@ that arrive are already the parent fragments'; its four per-sample tensors (`ato
 
 The device work goes through the generator's seams (`_pose`, `_score`, `_pair`, `_receptor_coords`,
 `_relieve`, `_score_placed`, `_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, `_pharm_perceive`, `_pharm_score`,
-`_add_hydrogens`),
+`_add_hydrogens`, `_peoe_charges`, `_esp_score`),
 looked up on the instance at the time of the call.  The shape
 seams take the request's reference object; which kind it is - a conformer or a solid - is `cheminformatics`' business."""
 from __future__ import annotations
@@ -44,6 +47,7 @@ from typing import List, NamedTuple, Optional, Union
 import torch
 
 from . import cheminformatics
+from . import electrostatics as mcg_esp
 from . import fingerprint as mcg_fp
 from . import geometry as mcg_geometry
 from . import host_pool
@@ -79,9 +83,15 @@ class Request:
     ref_features: Optional[tuple] = None          # `reference_pharmacophore`: (xyz [F,3] fp32, type index [F] uint8), host
     ref_pharm_graph: Optional[tuple] = None       # else (atomic numbers, bond codes [n,n] int8, coords [n,3]) to perceive
     min_pharmacophore_tanimoto: Optional[float] = None
-    rank_by: str = "shape"                        # "combo": rank by shape + pharmacophore Tanimoto
+    rank_by: str = "shape"                        # "combo": rank by shape + pharmacophore Tanimoto; "electrostatic": shape
+    #                                               + electrostatic Tanimoto
     add_hydrogens: bool = False                   # `add_hydrogens`: explicit hydrogens on the returned records
     standardize: bool = False                     # `standardize`: largest fragment + Kekule form, behind the bond write-back
+    scores_electrostatics: bool = False           # `electrostatic_scores`, or implied by `min_electrostatic_tanimoto`
+    ref_charge_points: Optional[tuple] = None     # `reference_charges`: (xyz [P,3] fp32, charge [P] fp32), host
+    ref_charge_graph: Optional[tuple] = None      # else (atomic numbers, bond codes [n,n] int8, coords [n,3]) to charge
+    min_electrostatic_tanimoto: Optional[float] = None
+    partial_charges: bool = False                 # `partial_charges`: the charges on the returned records
 
     @property
     def selects_by_shape(self) -> bool:
@@ -105,13 +115,21 @@ class Request:
         """Whether the call filters or selects, i.e. may return fewer molecules than are valid."""
         return (self.max_receptor_clashes is not None or self.max_chemical_tanimoto is not None or self.unique
                 or self.selects_by_shape or self.max_pairwise_chemical_tanimoto is not None
-                or self.max_atoms_outside is not None or self.min_pharmacophore_tanimoto is not None)
+                or self.max_atoms_outside is not None or self.min_pharmacophore_tanimoto is not None
+                or self.min_electrostatic_tanimoto is not None)
+
+    @property
+    def needs_charges(self) -> bool:
+        return self.scores_electrostatics or self.partial_charges
 
     def ranking_score(self, measured: Measured) -> Optional[float]:
         """What `unique`, the diversity walk and `top_k` rank a molecule by: its shape score, or - `rank_by="combo"` - shape
-        + pharmacophore Tanimoto (`pharmacophore.select_score`: NaN, which ranks last, where either is missing)."""
+        + pharmacophore Tanimoto (`pharmacophore.select_score`: NaN, which ranks last, where either is missing) or -
+        `rank_by="electrostatic"` - shape + electrostatic Tanimoto (`electrostatics.select_score`, likewise)."""
         if self.rank_by == "combo":
             return mcg_pharm.select_score(measured.shape_tanimoto, measured.pharmacophore_tanimoto)
+        if self.rank_by == "electrostatic":
+            return mcg_esp.select_score(measured.shape_tanimoto, measured.electrostatic_tanimoto)
         return measured.shape_tanimoto
 
 
@@ -125,7 +143,8 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
                   reference_context=None, relax_geometry: Union[bool, int] = False, pharmacophore_scores=False,
                   reference_pharmacophore=None, min_pharmacophore_tanimoto: Optional[float] = None,
                   rank_by: str = "shape", relieve_clashes: Union[bool, int] = False, add_hydrogens=False,
-                  standardize=False) -> Request:
+                  standardize=False, electrostatic_scores=False, reference_charges=None,
+                  min_electrostatic_tanimoto: Optional[float] = None, partial_charges=False) -> Request:
     """The public option keywords of a generation entry of `gen` as a `Request`: the shape options first, then the chemical
     ones (`top_k` / `min_shape_tanimoto` / `max_pairwise_tanimoto` imply the shape score, `max_chemical_tanimoto` the
     chemical one).  `reference_shape`: a watertight mesh in place of the reference conformer (`mesh.load_mesh`); the
@@ -138,6 +157,12 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     (True = `receptor.RELIEF_STEPS`); it needs a `receptor`, and with it `overlay`.  `add_hydrogens`: True or False; it
     works with every other option, but not with a finisher, RDKit's or a custom one (the hydrogens go onto the records).
     `standardize`: True or False; likewise refused with a finisher (RDKit's `standardize_mol` already does it on Mols).
+    `electrostatic_scores` (implied by `min_electrostatic_tanimoto`, a real number in [-1, 1]) needs `overlay`; the
+    reference's charge points are `reference_charges` (`electrostatics.load_reference_charges`) or are computed, behind the
+    generation, from the reference's graph (`reference_graph`, else a reference conformer with bonds) on the reference
+    conformer's coordinates, its hydrogens placed by the same kernel.  `rank_by="electrostatic"` needs the shape and the
+    electrostatic score.  `partial_charges`: True or False; it needs no reference and no pose.  Both are refused with a
+    finisher: they read the placed hydrogens of the records.
     Every refusal happens here, before any device work."""
     mcg_pharm.check_flag("add_hydrogens", add_hydrogens)
     if add_hydrogens and getattr(gen, "finisher", None) is not None:
@@ -145,6 +170,18 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     mcg_pharm.check_flag("standardize", standardize)
     if standardize and getattr(gen, "finisher", None) is not None:
         raise ValueError(mcg_standardize.REFUSAL_WITH_FINISHER)
+    mcg_pharm.check_flag("electrostatic_scores", electrostatic_scores)
+    mcg_pharm.check_flag("partial_charges", partial_charges)
+    if min_electrostatic_tanimoto is not None:
+        mcg_esp.check_threshold("min_electrostatic_tanimoto", min_electrostatic_tanimoto)
+    esp = electrostatic_scores or min_electrostatic_tanimoto is not None
+    if (esp or partial_charges) and getattr(gen, "finisher", None) is not None:
+        raise ValueError(mcg_esp.REFUSAL_WITH_FINISHER)
+    if reference_charges is not None and not esp:
+        raise ValueError("reference_charges is only read with electrostatic_scores or min_electrostatic_tanimoto")
+    if esp and not overlay:
+        raise ValueError("electrostatic_scores needs overlay=True: molecules that are not posed onto the reference are not "
+                         "in the coordinates of its charges")
     relax_steps = mcg_geometry.check_steps(relax_geometry)
     custom_finisher = isinstance(getattr(gen, "finisher", None), host_pool.TaskRef)
     shape = {}
@@ -171,7 +208,7 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
             raise ValueError("max_atoms_outside needs overlay=True: molecules that are not posed into the mesh are not "
                              "in its coordinates")
     common = dict(reference=solid, max_atoms_outside=max_atoms_outside, relax_steps=relax_steps,
-                  add_hydrogens=add_hydrogens, standardize=bool(standardize))
+                  add_hydrogens=add_hydrogens, standardize=bool(standardize), partial_charges=partial_charges)
     if max_receptor_clashes is not None:
         mcg_receptor.check_max_receptor_clashes(max_receptor_clashes)
         if receptor is None:
@@ -222,8 +259,31 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     mcg_pharm.check_flag("pharmacophore_scores", pharmacophore_scores)
     if min_pharmacophore_tanimoto is not None:
         mcg_pharm.check_threshold("min_pharmacophore_tanimoto", min_pharmacophore_tanimoto)
-    mcg_pharm.check_rank_by(rank_by)
+    mcg_esp.check_rank_by(rank_by)
     pharm = pharmacophore_scores or min_pharmacophore_tanimoto is not None
+    if rank_by == "electrostatic" and not (esp and shape.get("scores_shape")):
+        raise ValueError("rank_by='electrostatic' needs shape scores (shape_scores, top_k, min_shape_tanimoto or "
+                         "max_pairwise_tanimoto) and electrostatic_scores: it ranks by their sum")
+    if esp:
+        common.update(scores_electrostatics=True, min_electrostatic_tanimoto=min_electrostatic_tanimoto, rank_by=rank_by)
+        if reference_charges is not None:
+            common["ref_charge_points"] = mcg_esp.load_reference_charges(reference_charges)
+        else:
+            src = reference_graph
+            if src is None and hasattr(reference_conformer, "GetAtoms") and hasattr(reference_conformer, "GetBonds"):
+                src = reference_conformer
+            if src is None or solid is not None:
+                raise ValueError("electrostatic scores need the reference's charges: pass reference_charges= (a sequence "
+                                 "of (charge, (x, y, z)) in the reference's coordinates - the only way with a "
+                                 "reference_shape) or the reference's molecular graph (reference_graph=, or a reference "
+                                 "conformer with bonds)")
+            z, bonds = mcg_fp.mol_graph(src)
+            coords = common["reference"].coords
+            if not 1 <= len(z) <= mcg_esp.MAX_ATOMS or len(z) != int(coords.shape[0]):
+                raise ValueError(f"the reference graph has {len(z)} heavy atoms, the reference conformer "
+                                 f"{int(coords.shape[0])}: the charges are placed on the conformer's atoms, in the "
+                                 f"graph's order (at most {mcg_esp.MAX_ATOMS})")
+            common["ref_charge_graph"] = (z, bonds, coords)
     if reference_pharmacophore is not None and not pharm:
         raise ValueError("reference_pharmacophore is only read with pharmacophore_scores or min_pharmacophore_tanimoto")
     if rank_by == "combo" and not (pharm and shape.get("scores_shape")):
@@ -259,9 +319,10 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     if max_pairwise_chemical_tanimoto is not None:
         mcg_fp.check_threshold("max_pairwise_chemical_tanimoto", max_pairwise_chemical_tanimoto)
     scoring = chemical_scores or max_chemical_tanimoto is not None
-    if reference_graph is not None and not scoring and common.get("ref_pharm_graph") is None:
+    if reference_graph is not None and not scoring and common.get("ref_pharm_graph") is None and \
+            common.get("ref_charge_graph") is None:
         raise ValueError("reference_graph is only read with chemical_scores, max_chemical_tanimoto or pharmacophore "
-                         "scores without reference_pharmacophore")
+                         "scores without reference_pharmacophore (or electrostatic scores without reference_charges)")
     if not (scoring or unique or max_pairwise_chemical_tanimoto is not None):
         return Request(**shape, **common)
     if custom_finisher:
@@ -303,9 +364,11 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
     contacts - its pose failed - does not pass), then those with at most `max_atoms_outside` atoms outside the mesh (one
     without a count - its pose failed - does not pass), then those with a chemical Tanimoto below `max_chemical_tanimoto` (NaN
     does not pass), then those with a pharmacophore Tanimoto of at least `min_pharmacophore_tanimoto` (NaN and None do not
-    pass), then `unique` - of the rows with one graph key the first in ranking order
+    pass), then those with an electrostatic Tanimoto of at least `min_electrostatic_tanimoto` (NaN and None do not pass),
+    then `unique` - of the rows with one graph key the first in ranking order
     (`cheminformatics.ranking_key` of `Request.ranking_score`: by shape score where the call scores shape - plus the
-    pharmacophore score with `rank_by="combo"` - else the lowest sample id), still in the
+    pharmacophore score with `rank_by="combo"`, the electrostatic score with `rank_by="electrostatic"` - else the lowest
+    sample id), still in the
     input's order - then the threshold (always on the shape score alone), the sphere exclusion at `max_pairwise_tanimoto` and at
     `max_pairwise_chemical_tanimoto` in one walk, and `top_k` (`cheminformatics.select_diverse`).  `shape_pair(rows)` /
     `chem_pair(rows)`: the [n,n] pair matrices of the surviving rows, each called only when its threshold is set."""
@@ -321,6 +384,9 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
     if req.min_pharmacophore_tanimoto is not None:
         rows = rows.take([i for i, m in enumerate(rows.measured) if m.pharmacophore_tanimoto is not None
                           and m.pharmacophore_tanimoto >= req.min_pharmacophore_tanimoto])
+    if req.min_electrostatic_tanimoto is not None:
+        rows = rows.take([i for i, m in enumerate(rows.measured) if m.electrostatic_tanimoto is not None
+                          and m.electrostatic_tanimoto >= req.min_electrostatic_tanimoto])
     if req.unique:
         order = sorted(range(len(rows.item)), key=lambda i: cheminformatics.ranking_key(
             req.ranking_score(rows.measured[i]), rows.sample_id[i]))
@@ -328,7 +394,7 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
     if not req.selects_by_shape and req.max_pairwise_chemical_tanimoto is None:
         return rows.item
     threshold = req.min_shape_tanimoto
-    if req.rank_by == "combo" and threshold is not None:          # the walk ranks by the sum: the shape threshold goes first
+    if req.rank_by != "shape" and threshold is not None:          # the walk ranks by the sum: the shape threshold goes first
         rows = rows.take([i for i, m in enumerate(rows.measured) if m.shape_tanimoto >= threshold])
         threshold = None
     keep = cheminformatics.select_diverse(
@@ -366,15 +432,16 @@ def pharmacophore(gen, req: Request, coords: torch.Tensor, atomic_numbers: torch
     return gen._pharm_score(feats, coords, n_nodes, *gen._pharm_perceive(atomic_numbers, bond_orders, n_nodes))
 
 
-def hydrogens(gen, req: Request, res: dict) -> dict:
+def hydrogens(gen, req: Request, res: dict, placed: Optional[dict] = None) -> dict:
     """The hydrogen step of the rows a rank returns (`add_hydrogens`): the explicit hydrogens of the RETURNED coordinates -
     relaxed, posed, refined, relieved - so they need no transform of their own; one perceive and one placement launch
     over the rows (`_add_hydrogens`).  The per-sample tensors by the names `handoff.measured_from_tensors` reads:
     `hydrogen_coords`, `hydrogen_parents`, `hydrogens_unplaced` (-1 where the row has a non-finite coordinate) and - with
     a receptor - `receptor_hydrogen_clashes`: the hydrogens overlapping a receptor heavy atom by `receptor.CLASH_OVERLAP`
     at hydrogen's van der Waals radius, by the heavy atoms' own kernel (`_receptor_coords`) over the hydrogen columns in
-    chunks of its 64-atom width; -1 where posing failed."""
-    out = gen._add_hydrogens(res["x"], res["elements"], res["bond"], res["n_nodes"])
+    chunks of its 64-atom width; -1 where posing failed.  `placed`: the `_add_hydrogens` result of the same rows, where
+    the electrostatic step has already made it."""
+    out = placed if placed is not None else gen._add_hydrogens(res["x"], res["elements"], res["bond"], res["n_nodes"])
     count = out["n_hydrogens"]
     values = dict(hydrogen_coords=out["coords"], hydrogen_parents=out["parents"],
                   hydrogens_unplaced=torch.where(count < 0, torch.full_like(count, -1), out["unplaced"]))
@@ -388,6 +455,50 @@ def hydrogens(gen, req: Request, res: dict) -> dict:
             clashes = clashes + mcg_receptor.clash_summary(gen._receptor_coords(req.receptor, chunk, n_chunk, ones))[0]
         posed = torch.isfinite(res["pose"]).all(dim=1).to(clashes.device) & (count >= 0)
         values["receptor_hydrogen_clashes"] = torch.where(posed, clashes, torch.full_like(clashes, -1))
+    return values
+
+
+def reference_charge_points(gen, req: Request):
+    """The reference's charge points (xyz [P,3], charge [P]; host) of a call that scores electrostatics: the request's, or
+    - one perceive, one placement and one charge launch - those of the reference's graph on the reference conformer's
+    coordinates, its hydrogens placed by the kernel that places the candidates'.  ValueError where that reference holds
+    an element without charge parameters."""
+    if req.ref_charge_points is not None:
+        return req.ref_charge_points
+    z, bonds, xyz = req.ref_charge_graph
+    zs, bs, nn = mcg_fp.pad_graphs([(z, bonds)])
+    perceived = gen._pharm_perceive(zs, bs, nn)
+    x = xyz.to(torch.float32).unsqueeze(0)
+    placed = gen._add_hydrogens(x, zs, bs, nn, perceived=perceived)
+    charges = gen._peoe_charges(zs, bs, nn, perceived=perceived)
+    if int(charges["status"][0]) != 0:
+        raise ValueError("the reference holds an element without charge parameters (electrostatics.py has rows for H, C, "
+                         "N, O, F, P, S, Cl, Br): pass reference_charges=")
+    pts, q, count = mcg_esp.charge_points(x.to(placed["coords"].device), charges, placed)
+    k = int(count[0])
+    return mcg_esp.load_reference_charges((pts[0, :k], q[0, :k]))
+
+
+def electrostatics(gen, req: Request, res: dict, placed: Optional[dict] = None, perceived=None) -> dict:
+    """The electrostatic step of the rows a rank returns (`electrostatic_scores`, `partial_charges`), on the RETURNED
+    coordinates and graphs: one charge launch over the rows (`_peoe_charges`) and - with the scores - the charge points of
+    the rows with their placed hydrogens (`placed`: the `_add_hydrogens` result of the same rows) and the overlap launches
+    against the reference's (`_esp_score`).  The per-sample tensors by the names `handoff.measured_from_tensors` reads:
+    `electrostatic_tanimoto` (NaN where posing failed or the row holds an element without parameters) and - with
+    `partial_charges` - `partial_charges` / `hydrogen_charges` [B,W], +inf at and beyond a row's atoms."""
+    charges = gen._peoe_charges(res["elements"], res["bond"], res["n_nodes"], perceived=perceived)
+    values = {}
+    if req.partial_charges:
+        q = charges["q"]
+        real = torch.arange(q.shape[1], device=q.device).view(1, -1) < charges["n_nodes"].to(q.device).view(-1, 1)
+        beyond = torch.full_like(q, float("inf"))
+        values.update(partial_charges=torch.where(real, q, beyond), hydrogen_charges=torch.where(real, charges["q_h"], beyond))
+    if req.scores_electrostatics:
+        x = res["x"].to(placed["coords"].device)
+        pts, q, count = mcg_esp.charge_points(x, charges, placed)
+        sim = gen._esp_score(reference_charge_points(gen, req), pts, q, count)
+        posed = torch.isfinite(res["pose"]).all(dim=1).to(sim.device)         # a failed pose is not in the reference's frame
+        values["electrostatic_tanimoto"] = torch.where(posed, sim, torch.full_like(sim, float("nan")))
     return values
 
 
@@ -476,8 +587,15 @@ def return_records(gen, req: Request, res: dict, row_ids: Optional[torch.Tensor]
         posed = torch.isfinite(res["pose"]).all(dim=1).to(sim.device)         # a failed pose is not in the reference's frame
         values.update(pharmacophore_tanimoto=torch.where(posed, sim, torch.full_like(sim, float("nan"))),
                       pharmacophore_matches=torch.where(posed, hits, torch.full_like(hits, -1)))
+    placed = perceived = None
+    if req.needs_charges:                         # perceived once for the placement and the charges
+        perceived = gen._pharm_perceive(res["elements"], res["bond"], res["n_nodes"])
+    if req.scores_electrostatics:                 # placed once: the hydrogens of `add_hydrogens` are these
+        placed = gen._add_hydrogens(res["x"], res["elements"], res["bond"], res["n_nodes"], perceived=perceived)
     if req.add_hydrogens:
-        values.update(hydrogens(gen, req, res))
+        values.update(hydrogens(gen, req, res, placed))
+    if req.needs_charges:
+        values.update(electrostatics(gen, req, res, placed, perceived))
     if gen.device.type == "cuda":
         torch.cuda.synchronize(gen.device)        # (the D2H copies below would wait anyway: keep that out of the figure)
     t0 = time.perf_counter()
