@@ -758,6 +758,41 @@ int mcg_esp_overlap(const float* ref_xyz, const float* ref_q, int P, const float
                     const int32_t* n_points, int B, int PW /*points per row*/, float mu, const float* e_rr /*optional*/,
                     float* cross_out, float* self_out, float* tanimoto_out, void* stream);
 
+/* ---- Canonical graphs ("Canonical graphs and SMILES"): an exact canonical atom order of each of B
+ * molecular graphs.  The definition is this package's OWN (DESIGN.md states it in full): not RDKit's canonical ranking, no
+ * agreement with any toolkit claimed.
+ *   mcg_canonical_order: z[B,W] atomic numbers, bonds[B,W,W] symmetric bond codes (1 / 2 / 3 / 4 aromatic; any other
+ *                       value is no bond), n_nodes_dev[b] real atoms (device memory, clamped to [0, W] on the device; the
+ *                       diagonal and everything at or beyond n_b is ignored, whatever it holds).
+ *                       Initial colour (Z, degree, twice the bond-order sum with aromatic 1.5); rank = the number of atoms
+ *                       with a smaller key, tied atoms share a rank (a cell).  Refinement: key = (rank, the neighbours'
+ *                       (rank, code) pairs ascending), ranked again, until no cell splits.  Search: the target cell is the
+ *                       non-singleton cell of smallest rank r; for each member v in ascending index - skipping one that
+ *                       has a twin (same Z, same code to every third atom) among the members in front of it - v keeps r,
+ *                       the other members get r + 1, refine, recurse.  A leaf (all cells singletons) gives order[k] = the
+ *                       atom of rank k and the certificate Z(order[0..n-1]), then code(order[i], order[j]) for i = 1..n-1,
+ *                       j = 0..i-1; the lexicographically smallest certificate wins, the first such leaf on ties.  At most
+ *                       MCG_CANONICAL_LEAF_BUDGET leaves are visited.
+ *                       order_out[B,W]: the canonical order, -1 beyond n_b; status_out[b]: 0, or MCG_CANONICAL_EMPTY (n =
+ *                       0), _DEGREE (an atom with more than MCG_CANONICAL_MAX_DEGREE neighbours; nothing is searched) or
+ *                       _BUDGET (a branch was still unexplored behind the last leaf allowed): such a row has -1 throughout
+ *                       order_out and key 0; leaves_out[b]: the leaves visited; key_out[b]: 64 bits of the winning
+ *                       certificate (MurmurHash3 under the fingerprint's two seeds) - for grouping, never for a decision.
+ *                       One 64-lane workgroup per molecule, one launch, integer work only, no atomics, no scratch: a
+ *                       molecule's outputs have the same bits whatever the batch, its row and the padded width, and
+ *                       certificate, key and leaves do not depend on the atom numbering.
+ * B = 0 launches nothing.  MCG_ERR_ARG, nothing launched: a null buffer, B outside 0..MCG_CANONICAL_MAX_B, W outside
+ * 1..MCG_CANONICAL_MAX_ATOMS. */
+#define MCG_CANONICAL_MAX_ATOMS 64
+#define MCG_CANONICAL_MAX_B 16384
+#define MCG_CANONICAL_MAX_DEGREE 8
+#define MCG_CANONICAL_LEAF_BUDGET 4096
+#define MCG_CANONICAL_EMPTY 1
+#define MCG_CANONICAL_DEGREE 2
+#define MCG_CANONICAL_BUDGET 4
+int mcg_canonical_order(const int32_t* z, const int8_t* bonds, const int32_t* n_nodes_dev, int B, int W,
+                        int32_t* order_out, int32_t* status_out, int32_t* leaves_out, uint64_t* key_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,7 @@ from . import host_pool
 from . import postprocess
 from . import rdkit_order
 from . import receptor as mcg_receptor
+from . import canonical as mcg_canonical
 from . import fingerprint as mcg_fp
 from . import geometry as mcg_geometry
 from . import electrostatics as mcg_esp
@@ -355,6 +356,12 @@ class MLConformerGenerator(torch.nn.Module):
         """[B,B] pairwise Tanimoto of fingerprints (`fingerprint.pairwise_fingerprint_tanimoto`)."""
         return mcg_fp.pairwise_fingerprint_tanimoto(fp)
 
+    # the canonical step
+    def _canonical_order(self, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor) -> dict:
+        """The exact canonical labelling of padded graphs: `order`, `status`, `leaves`, `key` (`canonical.canonical_order`,
+        unchecked: the codes come from the bond write-back or from `mol_graph`; device tensors)."""
+        return mcg_canonical.canonical_order(atomic_numbers, bond_orders, n_nodes, self.device, check=False)
+
     # the pharmacophore step
     def _pharm_perceive(self, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor):
         """(types [B,W] uint8, ring masks [B,32] int64, ring counts [B]) of padded graphs
@@ -586,7 +593,8 @@ class MLConformerGenerator(torch.nn.Module):
                             overlay: bool = False, max_pairwise_tanimoto: Optional[float] = None,
                             refine_overlay: Union[bool, int] = False, receptor=None,
                             max_receptor_clashes: Optional[int] = None, chemical_scores: bool = False,
-                            reference_graph=None, max_chemical_tanimoto: Optional[float] = None, unique: bool = False,
+                            reference_graph=None, max_chemical_tanimoto: Optional[float] = None,
+                            unique: Union[bool, str] = False,
                             max_pairwise_chemical_tanimoto: Optional[float] = None, reference_shape=None,
                             shape_density: float = 0.02, max_atoms_outside: Optional[int] = None,
                             relax_geometry: Union[bool, int] = False, pharmacophore_scores: bool = False,
@@ -594,7 +602,8 @@ class MLConformerGenerator(torch.nn.Module):
                             rank_by: str = "shape", relieve_clashes: Union[bool, int] = False,
                             add_hydrogens: bool = False, standardize: bool = False,
                             electrostatic_scores: bool = False, reference_charges=None,
-                            min_electrostatic_tanimoto: Optional[float] = None, partial_charges: bool = False) -> List:
+                            min_electrostatic_tanimoto: Optional[float] = None, partial_charges: bool = False,
+                            smiles: bool = False, exclude_graphs=None) -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
@@ -754,10 +763,26 @@ class MLConformerGenerator(torch.nn.Module):
         `partial_charges` ([n] fp32, the heavy atoms) and `hydrogen_charges` ([n] fp32, the charge of EACH hydrogen of
         that atom, 0 where it has none); NaN where the molecule holds an element without parameters.
         `to_xyz_block(charges=True)` writes them as a fifth column.  All of these are None in a call without the option.
+        `smiles=True` (records path only): every returned record carries `canonical_order` - its exact canonical atom
+        order, found on the GPU by a partition-refinement search per molecule (`canonical.canonical_order`; DESIGN.md
+        section 6, "Canonical graphs and SMILES") - `canonical_status` and `smiles`, the canonical SMILES the host writes
+        from it on first read (`smiles.write_smiles`).  The package's OWN definition: valid OpenSMILES, NOT RDKit's
+        canonical SMILES, no string equality with any toolkit; no stereochemistry, no charges.  Equal strings mean the
+        same graph, so "unique within the batch" and "novel against a known set" can be counted on them.  A graph the
+        labelling refuses (an atom with more than 8 neighbours, more than 4 096 leaves) has `canonical_status` != 0 and
+        None for the other two; `to_smiles(canonical=False)` still writes it in its own atom order.  The "[nH]" of an
+        imidazole-type ring may sit on the other N than the hydrogen `add_hydrogens` placed on the same record.
+        `unique="exact"`: as `unique=True` - same place in the order of stages, same ranking - but a molecule is dropped
+        only where its exact identity (`canonical.identity_bytes`) equals that of a better-ranked one: two different
+        graphs that share a `graph_key` (cubane and the 8-ring with its four diagonals do) are both kept.  A molecule
+        without a canonical order is never dropped.  It reads the Mols' own graphs through RDKit's finisher.
+        `exclude_graphs=`: an iterable of `GeneratedMolecule` records, Mols or (atomic_numbers, bond_orders) pairs
+        (`fingerprint.mol_graph`: their heavy atoms).  They are read with the other arguments and labelled by the same
+        kernel directly in front of the generation, behind every refusal of the call, and a generated molecule whose
+        exact identity equals one of them is dropped, in front of `unique`.
         Order of the stages: validity, `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`,
-        `min_pharmacophore_tanimoto`, `min_electrostatic_tanimoto`, `unique`, then the selection (threshold, exclusion,
-        `top_k`).  The filters only
-        remove molecules.
+        `min_pharmacophore_tanimoto`, `min_electrostatic_tanimoto`, `exclude_graphs`, `unique`, then the selection
+        (threshold, exclusion, `top_k`).  The filters only remove molecules.
         Refused with ValueError before any device work: a chemical option that is not a bool / a real number in (0, 1],
         a chemical score without a reference graph, a `reference_graph` that `fingerprint.mol_graph` refuses or that has no
         or more than 64 heavy atoms, scoring or posing without a reference conformer, a reference
@@ -778,7 +803,10 @@ class MLConformerGenerator(torch.nn.Module):
         without overlay or without a source of the reference's charges, a `reference_charges` that
         `load_reference_charges` refuses or that no option reads, min_electrostatic_tanimoto outside [-1, 1], and add_hydrogens that is not a bool or on
         a generator with a finisher, RDKit's or a custom one (on Mols use `Chem.AddHs(mol, addCoords=True)`), and standardize
-        that is not a bool or on a generator with a finisher (RDKit's finisher runs `standardize_mol` itself).  A reference
+        that is not a bool or on a generator with a finisher (RDKit's finisher runs `standardize_mol` itself), smiles that
+        is not a bool or on a generator with a finisher, a unique other than True, False or "exact", and an
+        `exclude_graphs` entry that is unreadable, has more than 64 heavy atoms or has no canonical order (the message
+        names its position).  A reference
         graph in which no feature is found is refused where it is perceived, behind the generation."""
         if sample_seed is not None:
             seeding.check_seed(sample_seed)
@@ -789,9 +817,10 @@ class MLConformerGenerator(torch.nn.Module):
                                         reference_context, relax_geometry, pharmacophore_scores,
                                         reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes,
                                         add_hydrogens, standardize, electrostatic_scores, reference_charges,
-                                        min_electrostatic_tanimoto, partial_charges)
+                                        min_electrostatic_tanimoto, partial_charges, smiles, exclude_graphs)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
+        req = postprocess.label_excluded(self, req)      # `exclude_graphs`: the first device work, behind every check above
         keyed = () if sample_seed is None else (sample_seed, None)   # unseeded: the positional call of before
         relax = dict(relax_steps=req.relax_steps) if req.relax_steps else {}
         if req.standardize:
@@ -819,7 +848,7 @@ class MLConformerGenerator(torch.nn.Module):
                                     refine_overlay: Union[bool, int] = False, receptor=None,
                                     max_receptor_clashes: Optional[int] = None, chemical_scores: bool = False,
                                     reference_graph=None, max_chemical_tanimoto: Optional[float] = None,
-                                    unique: bool = False,
+                                    unique: Union[bool, str] = False,
                                     max_pairwise_chemical_tanimoto: Optional[float] = None, reference_shape=None,
                                     shape_density: float = 0.02, max_atoms_outside: Optional[int] = None,
                                     relax_geometry: Union[bool, int] = False, pharmacophore_scores: bool = False,
@@ -828,7 +857,8 @@ class MLConformerGenerator(torch.nn.Module):
                                     add_hydrogens: bool = False, standardize: bool = False,
                                     electrostatic_scores: bool = False, reference_charges=None,
                                     min_electrostatic_tanimoto: Optional[float] = None,
-                                    partial_charges: bool = False) -> List:
+                                    partial_charges: bool = False, smiles: bool = False,
+                                    exclude_graphs=None) -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -849,7 +879,8 @@ class MLConformerGenerator(torch.nn.Module):
         `max_pairwise_chemical_tanimoto`, `reference_shape`, `shape_density`, `max_atoms_outside`, `relax_geometry`,
         `pharmacophore_scores`, `reference_pharmacophore`, `min_pharmacophore_tanimoto`, `rank_by`, `relieve_clashes`,
         `electrostatic_scores`, `reference_charges`, `min_electrostatic_tanimoto`, `partial_charges` (behind the gather, on
-        the rows a rank returns, like the hydrogens),
+        the rows a rank returns, like the hydrogens), `smiles`, `unique="exact"`, `exclude_graphs` (labelled behind the
+        gather, on the rows a rank returns, beside the fingerprints; every rank labels the excluded graphs itself),
         `add_hydrogens` (placed behind the gather, on the rows a rank returns), `standardize` (on each rank's own shard,
         before the gather; its per-sample tensors travel with the rest, one collective each): as in
         `generate_conformers` (every rank loads the mesh and computes its occupancy itself).  The fingerprints are computed behind the gather,
@@ -873,11 +904,12 @@ class MLConformerGenerator(torch.nn.Module):
                                         reference_context, relax_geometry, pharmacophore_scores,
                                         reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes,
                                         add_hydrogens, standardize, electrostatic_scores, reference_charges,
-                                        min_electrostatic_tanimoto, partial_charges)
+                                        min_electrostatic_tanimoto, partial_charges, smiles, exclude_graphs)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)
         hi_n = min(ref_n_atoms + variance, self.max_n_nodes)
+        req = postprocess.label_excluded(self, req)      # `exclude_graphs`: the first device work, behind every check above
         # decided from the configuration, not from what this rank's shard happened to produce: every rank takes the same
         # path through the collectives (an EMPTY shard has no stage of its own making)
         finishing = getattr(self, "finisher", None) is not None

@@ -13,7 +13,8 @@ MurmurHash3_x86_32 over uint32 words and SEED = 0x6d636731:
   fingerprint: bit inv_r(a) & 2047 for every atom and r = 0, 1, 2, as 64 uint32 words (bit k: word k >> 5, position k & 31);
   graph key:   the n invariants after K = max(n - 1, 2) rounds, sorted, hashed with n under two seeds into 64 bits.
 Isomorphic graphs always get equal keys and fingerprints, whatever the atom numbering.  The converse can fail: two
-different graphs that colour refinement cannot tell apart, or a hash collision, share a key.
+different graphs that colour refinement cannot tell apart, or a hash collision, share a key (cubane's skeleton and the
+Wagner graph do); `canonical.py` has the exact identity.
 Tanimoto of two fingerprints: popcount(A & B) / popcount(A | B) in fp32; NaN where either has no bit set (no atoms).
 
 No aromaticity is perceived: a reference graph and the generated graphs must use ONE convention (the generator emits
@@ -93,6 +94,25 @@ def pad_graphs(graphs: Sequence[Tuple[List[int], torch.Tensor]]):
 
 
 # ----------------------------------------------------------------------------------------------- device
+def graph_arguments(atomic_numbers, bond_orders, n_nodes, what: str):
+    """(z, bonds, B, W) of padded graph arguments, their shapes and dtypes checked: the refusals `graph_fingerprints` and
+    `canonical.canonical_order` share.  `what`: who takes at most `MAX_GRAPH_ATOMS` atoms, for the message."""
+    from .cheminformatics import check_n_nodes
+    bonds = torch.as_tensor(bond_orders)
+    z = torch.as_tensor(atomic_numbers)
+    if bonds.dim() != 3 or bonds.shape[1] != bonds.shape[2]:
+        raise ValueError(f"bond_orders must be [B,W,W], got {list(bonds.shape)}")
+    B, W = int(bonds.shape[0]), int(bonds.shape[1])
+    if W > MAX_GRAPH_ATOMS:
+        raise ValueError(f"{what} take molecules of at most {MAX_GRAPH_ATOMS} atoms, got a width of {W}")
+    if z.dim() != 2 or z.shape[0] != B or z.shape[1] < W:
+        raise ValueError(f"atomic_numbers must be [B, >= W] = [{B}, >= {W}], got {list(z.shape)}")
+    if bonds.dtype.is_floating_point or z.dtype.is_floating_point:
+        raise ValueError("atomic_numbers and bond_orders must be integer tensors")
+    check_n_nodes(n_nodes, B, W)
+    return z, bonds, B, W
+
+
 def _check_graphs(z: torch.Tensor, bonds: torch.Tensor, nn: torch.Tensor, W: int) -> None:
     """The `check=True` half of `graph_fingerprints`: one device reduction, one host read."""
     real = torch.arange(W, device=z.device).view(1, W) < nn.view(-1, 1)
@@ -122,19 +142,7 @@ def graph_fingerprints(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, 
     ValueError before the kernel: W > 64, shapes that do not fit, atom counts outside [0, W]
     (`cheminformatics.check_n_nodes`), and with `check=True` (one device reduction) a code outside 0..4, a matrix that is
     not symmetric over the real atoms, an atomic number < 1 on a real atom."""
-    from .cheminformatics import check_n_nodes
-    bonds = torch.as_tensor(bond_orders)
-    z = torch.as_tensor(atomic_numbers)
-    if bonds.dim() != 3 or bonds.shape[1] != bonds.shape[2]:
-        raise ValueError(f"bond_orders must be [B,W,W], got {list(bonds.shape)}")
-    B, W = int(bonds.shape[0]), int(bonds.shape[1])
-    if W > MAX_GRAPH_ATOMS:
-        raise ValueError(f"graph fingerprints take molecules of at most {MAX_GRAPH_ATOMS} atoms, got a width of {W}")
-    if z.dim() != 2 or z.shape[0] != B or z.shape[1] < W:
-        raise ValueError(f"atomic_numbers must be [B, >= W] = [{B}, >= {W}], got {list(z.shape)}")
-    if bonds.dtype.is_floating_point or z.dtype.is_floating_point:
-        raise ValueError("atomic_numbers and bond_orders must be integer tensors")
-    check_n_nodes(n_nodes, B, W)
+    z, bonds, B, W = graph_arguments(atomic_numbers, bond_orders, n_nodes, "graph fingerprints")
     dev = torch.device(device if device is not None else (bonds.device if bonds.is_cuda else "cuda:0"))
     fp = torch.zeros(B, FP_WORDS, dtype=torch.int32, device=dev)
     key = torch.empty(B, dtype=torch.int64, device=dev)

@@ -64,6 +64,8 @@ class Measured:
     electrostatic_tanimoto: Optional[float] = None
     partial_charges: Optional[object] = None      # [n] fp32, host - or (batch [B,W], row, n), sliced on first read
     hydrogen_charges: Optional[object] = None     # [n] fp32, host - likewise
+    canonical_order: Optional[object] = None      # List[int] - or (batch [B,W] int32, row, n), sliced on first read
+    canonical_status: Optional[int] = None        # `canonical.describe_status`; 0 = the order is canonical
 
 
 _UNMEASURED = Measured()          # shared by every record that carries no values: never written to
@@ -84,9 +86,12 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
     (the one host copy, row, atom count) and sliced on first read.
     The charges of a call with `partial_charges` come as `partial_charges` [n,W] and `hydrogen_charges` [n,W] fp32 (both or
     neither), +inf at and beyond a row's atoms (a real atom's charge is finite or NaN); a record's fields are left as (the
-    one host copy, row, atom count) and sliced on first read.  `electrostatic_tanimoto` [n] fp32 is taken as it comes."""
+    one host copy, row, atom count) and sliced on first read.  `electrostatic_tanimoto` [n] fp32 is taken as it comes.
+    The canonical labelling of a call with `smiles` comes as `canonical_order` [n,W] int32 (-1 beyond a row's atoms, and
+    throughout a row that has no canonical order) and `canonical_status` [n] (both or neither); a record's
+    `canonical_order` is left as (the one host copy, row, atom count) and sliced on first read."""
     hyd = {k: values.get(k) for k in ("hydrogen_coords", "hydrogen_parents", "atom_map", "kekule_bond_orders",
-                                      "partial_charges", "hydrogen_charges")}
+                                      "partial_charges", "hydrogen_charges", "canonical_order")}
     cols = {k: v.cpu().tolist() for k, v in values.items() if v is not None and k != "pose" and k not in hyd}
     if values.get("pose") is not None:
         poses = values["pose"].cpu().to(torch.float32)
@@ -127,6 +132,9 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
         counts = (~torch.isinf(q)).sum(dim=1).tolist()
         cols["partial_charges"] = [(q, b, k) for b, k in enumerate(counts)]
         cols["hydrogen_charges"] = [(qh, b, k) for b, k in enumerate(counts)]
+    if hyd["canonical_order"] is not None:
+        orders = hyd["canonical_order"].cpu().to(torch.int32)
+        cols["canonical_order"] = [(orders, b, k) for b, k in enumerate((orders >= 0).sum(dim=1).tolist())]
     return [Measured(**{k: col[b] for k, col in cols.items()}) for b in range(n)]
 
 
@@ -161,13 +169,17 @@ class GeneratedMolecule:
     `electrostatic_tanimoto`: the similarity of its charge distribution, as posed, to the reference's when the call asked
     for `electrostatic_scores`; `partial_charges` / `hydrogen_charges`: its partial charges when the call asked for
     `partial_charges` (`electrostatics.py`: the package's own definition, NOT RDKit's Gasteiger charges), else None;
-    `to_xyz_block(charges=True)` writes them."""
-    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_measured")
+    `to_xyz_block(charges=True)` writes them.
+    `canonical_order` / `canonical_status` / `smiles`: its exact canonical atom order and canonical SMILES when the call
+    asked for `smiles` (`canonical.py`, `smiles.py`: the package's own definition - valid OpenSMILES, NOT RDKit's canonical
+    SMILES), else None; `to_smiles()` writes the string, `to_smiles(canonical=False)` one in the record's own atom order."""
+    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_measured", "_smiles")
 
     def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True,
                  sample_id: Optional[int] = None):
         self._z, self._coords, self._bonds, self.valid = list(atomic_numbers), coords, bond_orders, bool(valid)
         self._batch, self._b, self._sid, self._measured = None, -1, sample_id, _UNMEASURED
+        self._smiles = None
 
     @classmethod
     def _view(cls, batch: _HostBatch, b: int, valid: bool, sample_id: Optional[int] = None,
@@ -177,7 +189,36 @@ class GeneratedMolecule:
         m.valid, m._batch, m._b = valid, batch, b
         m._sid = b if sample_id is None else sample_id
         m._measured = measured
+        m._smiles = None
         return m
+
+    @property
+    def canonical_status(self) -> Optional[int]:
+        """The status word of this molecule's canonical labelling (`canonical.describe_status`: 0, or EMPTY / DEGREE /
+        BUDGET - the graph has no canonical order by the package's definition) when the call asked for `smiles`; None
+        otherwise."""
+        return self._measured.canonical_status
+
+    @property
+    def canonical_order(self) -> Optional[List[int]]:
+        """The exact canonical atom order of the molecular graph (`canonical.canonical_order`: the package's own
+        definition, not RDKit's canonical ranking): position k holds the index, in this record, of the atom of canonical
+        rank k; isomorphic graphs relabelled this way are equal.  When the call asked for `smiles`; None otherwise, and
+        where `canonical_status` is not 0.  Sliced from the batch's host tensor on first access."""
+        o = self._measured.canonical_order
+        if isinstance(o, tuple):
+            o = self._measured.canonical_order = o[0][o[1], : o[2]].tolist()
+        return o if self._measured.canonical_status == 0 else None
+
+    @property
+    def smiles(self) -> Optional[str]:
+        """The canonical SMILES of the heavy-atom graph (`smiles.write_smiles` on the graph in `canonical_order`: valid
+        OpenSMILES by the package's OWN definition - NOT RDKit's canonical SMILES; no stereochemistry, no charges), built
+        on first access, when the call asked for `smiles`; None otherwise, and where `canonical_status` is not 0.  Equal
+        strings: the same graph.  Its "[nH]" may sit on the other N than the hydrogen `add_hydrogens` placed."""
+        if self._smiles is None and self.canonical_order is not None:
+            self._smiles = self.to_smiles(canonical=True)
+        return self._smiles
 
     @property
     def electrostatic_tanimoto(self) -> Optional[float]:
@@ -466,6 +507,26 @@ class GeneratedMolecule:
         lines.append("M  END")
         return "\n".join(lines) + "\n"
 
+    def to_smiles(self, canonical: bool = True) -> str:
+        """SMILES of the heavy-atom graph by `smiles.write_smiles` (the package's own writer: valid OpenSMILES, not RDKit's
+        canonical SMILES).  `canonical=True`: the atoms in the record's `canonical_order` - the package's canonical
+        string; ValueError, naming the status, where the record has no canonical order (a call without `smiles`, or a
+        graph the labelling refused).  `canonical=False` always works: the atoms are written in the record's OWN order, so
+        two records of one molecule may get different strings."""
+        from .smiles import write_smiles
+        z, bonds = self.atomic_numbers, torch.as_tensor(self.bond_orders)
+        if not canonical:
+            return write_smiles(z, bonds)
+        order = self.canonical_order
+        if order is None:
+            from .canonical import describe_status
+            status = self._measured.canonical_status
+            raise ValueError("this record has no canonical order: " + (
+                "generate with smiles=True" if status is None else f"its labelling ended with {describe_status(status)}")
+                + "; to_smiles(canonical=False) writes the atoms in the record's own order")
+        idx = torch.tensor(order, dtype=torch.long)
+        return write_smiles([z[a] for a in order], bonds.index_select(0, idx).index_select(1, idx))
+
     def to_xyz_block(self, hydrogens: bool = False, charges: bool = False) -> str:
         """XYZ block of the heavy atoms; `hydrogens=True`: the record's explicit hydrogens (`add_hydrogens`) follow them;
         ValueError where the record carries none.  `charges=True`: a fifth column holds each atom's partial charge
@@ -610,7 +671,9 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                            kekule_bond_orders: Optional[torch.Tensor] = None,
                            electrostatic_tanimoto: Optional[torch.Tensor] = None,
                            partial_charges: Optional[torch.Tensor] = None,
-                           hydrogen_charges: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
+                           hydrogen_charges: Optional[torch.Tensor] = None,
+                           canonical_order: Optional[torch.Tensor] = None,
+                           canonical_status: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
     (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
     (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records).
@@ -635,7 +698,8 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     `standardize`).  `electrostatic_tanimoto[b]`: row b's electrostatic similarity to the reference (None: a call without
     `electrostatic_scores`); `partial_charges[b]` [W] / `hydrogen_charges[b]` [W]: row b's partial charges as
     `electrostatics.partial_charges` returns them, +inf at and beyond the row's atoms (both or neither; None: a call
-    without `partial_charges`).
+    without `partial_charges`).  `canonical_order[b]` [W] int32 (-1 beyond the row's atoms) / `canonical_status[b]`: row b's
+    canonical labelling as `canonical.canonical_order` returns it (both or neither; None: a call without `smiles`).
     The value keywords are the fields of `Measured`
     and go to `measured_from_tensors`; a call with no ids and no values builds the views and nothing else."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
@@ -650,7 +714,8 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                   hydrogens_unplaced=hydrogens_unplaced, receptor_hydrogen_clashes=receptor_hydrogen_clashes,
                   atoms_removed=atoms_removed, n_fragments=n_fragments, atom_map=atom_map,
                   kekule_bond_orders=kekule_bond_orders, electrostatic_tanimoto=electrostatic_tanimoto,
-                  partial_charges=partial_charges, hydrogen_charges=hydrogen_charges)
+                  partial_charges=partial_charges, hydrogen_charges=hydrogen_charges,
+                  canonical_order=canonical_order, canonical_status=canonical_status)
     if sample_ids is None and all(v is None for v in values.values()):
         return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
     flags = valid.cpu().tolist()

@@ -19,12 +19,14 @@ Stages, in this order:
        with a receptor - the receptor kernel over the hydrogens (`hydrogens`; records only: refused with a finisher);
        and the electrostatic step (`electrostatics`; records only): one perceive launch, the hydrogens placed once - the
        placement of `add_hydrogens` is reused when that is on too - one charge launch and, with `electrostatic_scores`,
-       the overlap launches against the reference's charge points;
+       the overlap launches against the reference's charge points; and the canonical step (`identities`; `smiles`,
+       `unique="exact"`, `exclude_graphs`): one `_canonical_order` launch over the rows - the excluded graphs were
+       labelled by the same seam directly in front of the generation (`label_excluded`);
     5. the values are attached - each molecule's `handoff.Measured`, behind a record's properties or written onto the
        Mol by `rdkit_finish.tag_measured` (Mols lose their properties in the object gather) - and validity is taken
        (`last_valid_fraction`);
     6. `select`, written once for both paths: `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`,
-       `min_pharmacophore_tanimoto`, `min_electrostatic_tanimoto`, `unique`, then the
+       `min_pharmacophore_tanimoto`, `min_electrostatic_tanimoto`, `exclude_graphs`, `unique`, then the
        threshold / sphere exclusion / `top_k` walk of `cheminformatics.select_diverse`.  The two pair matrices are
        computed only when their threshold is set, over the rows that survived the filters.
 A call with no option on takes none of these steps: its records / live Mols are returned as they come.
@@ -34,7 +36,7 @@ that arrive are already the parent fragments'; its four per-sample tensors (`ato
 
 The device work goes through the generator's seams (`_pose`, `_score`, `_pair`, `_receptor_coords`,
 `_relieve`, `_score_placed`, `_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, `_pharm_perceive`, `_pharm_score`,
-`_add_hydrogens`, `_peoe_charges`, `_esp_score`),
+`_add_hydrogens`, `_peoe_charges`, `_esp_score`, `_canonical_order`),
 looked up on the instance at the time of the call.  The shape
 seams take the request's reference object; which kind it is - a conformer or a solid - is `cheminformatics`' business."""
 from __future__ import annotations
@@ -46,6 +48,7 @@ from typing import List, NamedTuple, Optional, Union
 
 import torch
 
+from . import canonical as mcg_canonical
 from . import cheminformatics
 from . import electrostatics as mcg_esp
 from . import fingerprint as mcg_fp
@@ -75,7 +78,7 @@ class Request:
     ref_graph: Optional[tuple] = None             # (atomic numbers, bond codes [n,n] int8) of the reference, when it scores
     scores_chemistry: bool = False                # `chemical_scores`, or implied by `max_chemical_tanimoto`
     max_chemical_tanimoto: Optional[float] = None
-    unique: bool = False
+    unique: Union[bool, str] = False
     max_pairwise_chemical_tanimoto: Optional[float] = None
     max_atoms_outside: Optional[int] = None
     relax_steps: int = 0                          # `relax_geometry`: trial steps of the relaxation, 0 = not relaxed
@@ -92,6 +95,10 @@ class Request:
     ref_charge_graph: Optional[tuple] = None      # else (atomic numbers, bond codes [n,n] int8, coords [n,3]) to charge
     min_electrostatic_tanimoto: Optional[float] = None
     partial_charges: bool = False                 # `partial_charges`: the charges on the returned records
+    smiles: bool = False                          # `smiles`: canonical order and SMILES on the returned records
+    excluded_graphs: Optional[tuple] = None       # `exclude_graphs` as read on the host: (atomic numbers, bond codes) each
+    exclude: Optional[frozenset] = None           # their (key, identity bytes), once `label_excluded` has labelled them
+    # `unique` above is False, True (one row per `graph_key`) or "exact" (one row per exact identity)
 
     @property
     def selects_by_shape(self) -> bool:
@@ -99,22 +106,31 @@ class Request:
 
     @property
     def needs_fingerprints(self) -> bool:
-        return self.scores_chemistry or self.unique or self.max_pairwise_chemical_tanimoto is not None
+        return self.scores_chemistry or self.unique is True or self.max_pairwise_chemical_tanimoto is not None
 
     @property
     def tags_graph_keys(self) -> bool:
-        return self.scores_chemistry or self.unique
+        return self.scores_chemistry or self.unique is True
+
+    @property
+    def needs_identity(self) -> bool:
+        """Whether `select` compares exact identities (`unique="exact"`, `exclude_graphs`)."""
+        return self.unique == "exact" or self.excluded_graphs is not None
+
+    @property
+    def needs_canonical(self) -> bool:
+        return self.smiles or self.needs_identity
 
     @property
     def measures(self) -> bool:
         """Whether any option is on (a receptor needs the pose, a selection implies its score)."""
-        return self.overlay or self.scores_shape or self.needs_fingerprints
+        return self.overlay or self.scores_shape or self.needs_fingerprints or self.needs_canonical
 
     @property
     def removes(self) -> bool:
         """Whether the call filters or selects, i.e. may return fewer molecules than are valid."""
-        return (self.max_receptor_clashes is not None or self.max_chemical_tanimoto is not None or self.unique
-                or self.selects_by_shape or self.max_pairwise_chemical_tanimoto is not None
+        return (self.max_receptor_clashes is not None or self.max_chemical_tanimoto is not None or bool(self.unique)
+                or self.excluded_graphs is not None or self.selects_by_shape or self.max_pairwise_chemical_tanimoto is not None
                 or self.max_atoms_outside is not None or self.min_pharmacophore_tanimoto is not None
                 or self.min_electrostatic_tanimoto is not None)
 
@@ -144,7 +160,8 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
                   reference_pharmacophore=None, min_pharmacophore_tanimoto: Optional[float] = None,
                   rank_by: str = "shape", relieve_clashes: Union[bool, int] = False, add_hydrogens=False,
                   standardize=False, electrostatic_scores=False, reference_charges=None,
-                  min_electrostatic_tanimoto: Optional[float] = None, partial_charges=False) -> Request:
+                  min_electrostatic_tanimoto: Optional[float] = None, partial_charges=False, smiles=False,
+                  exclude_graphs=None) -> Request:
     """The public option keywords of a generation entry of `gen` as a `Request`: the shape options first, then the chemical
     ones (`top_k` / `min_shape_tanimoto` / `max_pairwise_tanimoto` imply the shape score, `max_chemical_tanimoto` the
     chemical one).  `reference_shape`: a watertight mesh in place of the reference conformer (`mesh.load_mesh`); the
@@ -163,7 +180,17 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     conformer's coordinates, its hydrogens placed by the same kernel.  `rank_by="electrostatic"` needs the shape and the
     electrostatic score.  `partial_charges`: True or False; it needs no reference and no pose.  Both are refused with a
     finisher: they read the placed hydrogens of the records.
+    `smiles`: True or False; refused with a finisher (the order and the string go onto the records).  `unique`: False,
+    True or "exact" - one row per exact identity (`canonical.identity_bytes`) instead of per `graph_key`; it reads the
+    Mols' own graphs through RDKit's finisher and is refused with a custom one.  `exclude_graphs`: an iterable of
+    `GeneratedMolecule`, Mols or (atomic_numbers, bond_orders) pairs (`fingerprint.mol_graph`) whose exact identities the
+    call drops; an entry that is unreadable or has more than 64 heavy atoms is a ValueError naming its position.  The
+    graphs are only read here; the entries label them (`label_excluded`, one `_canonical_order` launch per 16 384) behind
+    their own argument checks, directly in front of the generation, where one without a canonical order is refused.
     Every refusal happens here, before any device work."""
+    mcg_pharm.check_flag("smiles", smiles)
+    if smiles and getattr(gen, "finisher", None) is not None:
+        raise ValueError(mcg_canonical.REFUSAL_WITH_FINISHER)
     mcg_pharm.check_flag("add_hydrogens", add_hydrogens)
     if add_hydrogens and getattr(gen, "finisher", None) is not None:
         raise ValueError(mcg_hydrogens.REFUSAL_WITH_FINISHER)
@@ -208,7 +235,8 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
             raise ValueError("max_atoms_outside needs overlay=True: molecules that are not posed into the mesh are not "
                              "in its coordinates")
     common = dict(reference=solid, max_atoms_outside=max_atoms_outside, relax_steps=relax_steps,
-                  add_hydrogens=add_hydrogens, standardize=bool(standardize), partial_charges=partial_charges)
+                  add_hydrogens=add_hydrogens, standardize=bool(standardize), partial_charges=partial_charges,
+                  smiles=smiles)
     if max_receptor_clashes is not None:
         mcg_receptor.check_max_receptor_clashes(max_receptor_clashes)
         if receptor is None:
@@ -313,7 +341,9 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
                                  f"graph's order (at most {mcg_pharm.MAX_ATOMS})")
             common["ref_pharm_graph"] = (z, bonds, coords)
     mcg_fp.check_flag("chemical_scores", chemical_scores)
-    mcg_fp.check_flag("unique", unique)
+    if not (isinstance(unique, str) and unique == "exact"):
+        mcg_fp.check_flag("unique", unique)
+    excluded = None if exclude_graphs is None else read_excluded(exclude_graphs)
     if max_chemical_tanimoto is not None:
         mcg_fp.check_threshold("max_chemical_tanimoto", max_chemical_tanimoto)
     if max_pairwise_chemical_tanimoto is not None:
@@ -323,11 +353,14 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
             common.get("ref_charge_graph") is None:
         raise ValueError("reference_graph is only read with chemical_scores, max_chemical_tanimoto or pharmacophore "
                          "scores without reference_pharmacophore (or electrostatic scores without reference_charges)")
-    if not (scoring or unique or max_pairwise_chemical_tanimoto is not None):
-        return Request(**shape, **common)
-    if custom_finisher:
+    chemical = scoring or unique or max_pairwise_chemical_tanimoto is not None
+    if (chemical or excluded is not None) and custom_finisher:
         raise ValueError("chemical scores cannot be combined with a custom finisher: its results carry no graph this "
                          "package can read")
+    if excluded is not None:
+        common["excluded_graphs"] = tuple(excluded)
+    if not chemical:
+        return Request(**shape, **common)
     graph = None
     if scoring:
         src = reference_graph
@@ -342,8 +375,77 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
             raise ValueError(f"the reference graph must have 1 to {mcg_fp.MAX_GRAPH_ATOMS} heavy atoms, got "
                              f"{len(graph[0])}")
     return Request(ref_graph=graph, scores_chemistry=bool(scoring), max_chemical_tanimoto=max_chemical_tanimoto,
-                   unique=bool(unique), max_pairwise_chemical_tanimoto=max_pairwise_chemical_tanimoto, **shape,
+                   unique=unique, max_pairwise_chemical_tanimoto=max_pairwise_chemical_tanimoto, **shape,
                    **common)
+
+
+def read_excluded(exclude_graphs) -> List[tuple]:
+    """The heavy-atom graphs (`fingerprint.mol_graph`) of an `exclude_graphs` argument, host side only.  ValueError naming
+    the position of an entry that is unreadable or has more than `canonical.MAX_ATOMS` heavy atoms, and for an argument
+    that is no iterable of graphs."""
+    if isinstance(exclude_graphs, (str, bytes)) or not hasattr(exclude_graphs, "__iter__"):
+        raise ValueError("exclude_graphs must be an iterable of GeneratedMolecule records, Mols or (atomic_numbers, "
+                         f"bond_orders) pairs, got {type(exclude_graphs).__name__}")
+    graphs = []
+    for k, obj in enumerate(exclude_graphs):
+        try:
+            z, bonds = mcg_fp.mol_graph(obj)
+        except ValueError as e:
+            raise ValueError(f"exclude_graphs[{k}] is unreadable: {e}") from None
+        if len(z) > mcg_canonical.MAX_ATOMS:
+            raise ValueError(f"exclude_graphs[{k}] has {len(z)} heavy atoms; a canonical order takes at most "
+                             f"{mcg_canonical.MAX_ATOMS}")
+        graphs.append((z, bonds))
+    return graphs
+
+
+def identities(gen, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor):
+    """The canonical step of padded graphs, one `_canonical_order` call: (its result, per row the exact identity as (key,
+    `canonical.identity_bytes`), None for a row that has no canonical order - it is not proven equal to anything)."""
+    canon = gen._canonical_order(atomic_numbers, bond_orders, n_nodes)
+    keys = [k & 0xFFFFFFFFFFFFFFFF for k in canon["key"].cpu().tolist()]
+    exact = mcg_canonical.identity_bytes(atomic_numbers, bond_orders, n_nodes, ordered=canon)
+    return canon, [None if e is None else (k, e) for k, e in zip(keys, exact)]
+
+
+def excluded_identities(gen, graphs: List[tuple]) -> frozenset:
+    """The exact identities of the `read_excluded` graphs, by the kernel that labels the generated rows, in chunks of
+    `canonical.MAX_BATCH`; ValueError naming the position of one that has no canonical order."""
+    out = set()
+    for lo in range(0, len(graphs), mcg_canonical.MAX_BATCH):
+        canon, exact = identities(gen, *mcg_fp.pad_graphs(graphs[lo: lo + mcg_canonical.MAX_BATCH]))
+        for k, (e, status) in enumerate(zip(exact, canon["status"].cpu().tolist())):
+            if e is None:
+                raise ValueError(f"exclude_graphs[{lo + k}] has no canonical order: its labelling ended with "
+                                 f"{mcg_canonical.describe_status(status)}")
+            out.add(e)
+    return frozenset(out)
+
+
+def label_excluded(gen, req: Request) -> Request:
+    """`req` with the exact identities of its `exclude_graphs` (`excluded_identities`: device work, through
+    `_canonical_order`); `req` itself where the call excludes nothing.  The generation entries call it behind every
+    argument check of their own, directly in front of the generation; ValueError naming the position of a graph that has
+    no canonical order."""
+    if req.excluded_graphs is None:
+        return req
+    return dataclasses.replace(req, exclude=excluded_identities(gen, list(req.excluded_graphs)))
+
+
+def select_exact(exact: List[Optional[tuple]], order: List[int]) -> List[int]:
+    """Positions to keep so that every exact identity occurs once: the rows are grouped by their 64-bit key, and a row is
+    dropped only where its identity bytes equal those of a row that comes before it in `order` (positions, best first).  A
+    row without an identity (None: no canonical order) is always kept.  The result is in the input's order."""
+    groups, keep = {}, []
+    for i in order:
+        if exact[i] is not None:
+            key, body = exact[i]
+            seen = groups.setdefault(key, [])
+            if body in seen:
+                continue
+            seen.append(body)
+        keep.append(i)
+    return sorted(keep)
 
 
 @dataclasses.dataclass
@@ -353,10 +455,11 @@ class Rows:
     sample_id: List[int]
     measured: List[Measured]
     row: List[int]                                # index into the device tensors behind the pair matrices
+    exact: Optional[List[Optional[tuple]]] = None     # `identities` per row, where the call compares exact identities
 
     def take(self, keep: List[int]) -> "Rows":
         """The rows at the positions `keep`, in that order."""
-        return Rows(*([col[i] for i in keep] for col in vars(self).values()))
+        return Rows(*(None if col is None else [col[i] for i in keep] for col in vars(self).values()))
 
 
 def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
@@ -365,7 +468,9 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
     without a count - its pose failed - does not pass), then those with a chemical Tanimoto below `max_chemical_tanimoto` (NaN
     does not pass), then those with a pharmacophore Tanimoto of at least `min_pharmacophore_tanimoto` (NaN and None do not
     pass), then those with an electrostatic Tanimoto of at least `min_electrostatic_tanimoto` (NaN and None do not pass),
-    then `unique` - of the rows with one graph key the first in ranking order
+    then `exclude_graphs` - the rows whose exact identity is one of the excluded graphs' (a row without a canonical order is
+    not proven equal to anything and stays) -, then `unique` - of the rows with one graph key (`unique="exact"`: with one
+    exact identity, `select_exact`) the first in ranking order
     (`cheminformatics.ranking_key` of `Request.ranking_score`: by shape score where the call scores shape - plus the
     pharmacophore score with `rank_by="combo"`, the electrostatic score with `rank_by="electrostatic"` - else the lowest
     sample id), still in the
@@ -387,10 +492,17 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
     if req.min_electrostatic_tanimoto is not None:
         rows = rows.take([i for i, m in enumerate(rows.measured) if m.electrostatic_tanimoto is not None
                           and m.electrostatic_tanimoto >= req.min_electrostatic_tanimoto])
+    if req.excluded_graphs is not None:
+        if req.exclude is None:
+            raise RuntimeError("the request's exclude_graphs were not labelled: call label_excluded before the selection")
+        rows = rows.take([i for i, e in enumerate(rows.exact) if e is None or e not in req.exclude])
     if req.unique:
         order = sorted(range(len(rows.item)), key=lambda i: cheminformatics.ranking_key(
             req.ranking_score(rows.measured[i]), rows.sample_id[i]))
-        rows = rows.take(mcg_fp.select_unique([m.graph_key for m in rows.measured], order))
+        if req.unique == "exact":
+            rows = rows.take(select_exact(rows.exact, order))
+        else:
+            rows = rows.take(mcg_fp.select_unique([m.graph_key for m in rows.measured], order))
     if not req.selects_by_shape and req.max_pairwise_chemical_tanimoto is None:
         return rows.item
     threshold = req.min_shape_tanimoto
@@ -582,6 +694,13 @@ def return_records(gen, req: Request, res: dict, row_ids: Optional[torch.Tensor]
     if req.needs_fingerprints:
         fp, key, sim = fingerprints(gen, req, res["elements"], res["bond"], res["n_nodes"])
         values.update(chemical_tanimoto=sim, graph_key=key if req.tags_graph_keys else None)
+    exact = None
+    if req.needs_identity:
+        canon, exact = identities(gen, res["elements"], res["bond"], res["n_nodes"])
+    elif req.smiles:
+        canon = gen._canonical_order(res["elements"], res["bond"], res["n_nodes"])
+    if req.smiles:
+        values.update(canonical_order=canon["order"], canonical_status=canon["status"])
     if req.scores_pharmacophore:
         sim, hits = pharmacophore(gen, req, res["x"], res["elements"], res["bond"], res["n_nodes"])
         posed = torch.isfinite(res["pose"]).all(dim=1).to(sim.device)         # a failed pose is not in the reference's frame
@@ -605,7 +724,8 @@ def return_records(gen, req: Request, res: dict, row_ids: Optional[torch.Tensor]
     kept, gen.last_valid_fraction = _finish(mols, optimise_geometry, use_rdkit=False)    # no finisher: the proxy
     if not req.removes:
         return kept
-    rows = Rows(kept, [m.sample_id for m in kept], [m._measured for m in kept], [m.batch_row for m in kept])
+    rows = Rows(kept, [m.sample_id for m in kept], [m._measured for m in kept], [m.batch_row for m in kept],
+                None if exact is None else [exact[m.batch_row] for m in kept])
 
     def shape_pair(left: Rows):
         x = res["x"]
@@ -747,6 +867,8 @@ def return_finished(gen, req: Request, samples: List[Finished], row_ids: Optiona
         chem = measured_from_tensors(dict(chemical_tanimoto=sim, graph_key=key if req.tags_graph_keys else None), len(live))
         for m, c in zip(rows.measured, chem):
             m.chemical_tanimoto, m.graph_key = c.chemical_tanimoto, c.graph_key
+    if req.needs_identity:                        # the live Mols' own graphs, like the fingerprints
+        rows.exact = identities(gen, *mcg_fp.pad_graphs([mcg_fp.mol_graph(m) for m in rows.item]))[1] if live else []
     posed = [i for i, m in enumerate(rows.measured) if m.pose is not None]
     if req.scores_pharmacophore and posed:        # the live, posed Mols' heavy atoms and their own graphs
         z, bonds, nn = mcg_fp.pad_graphs([mcg_fp.mol_graph(rows.item[i]) for i in posed])
