@@ -793,6 +793,49 @@ int mcg_esp_overlap(const float* ref_xyz, const float* ref_q, int P, const float
 int mcg_canonical_order(const int32_t* z, const int8_t* bonds, const int32_t* n_nodes_dev, int B, int W,
                         int32_t* order_out, int32_t* status_out, int32_t* leaves_out, uint64_t* key_out, void* stream);
 
+/* ---- Substructure patterns ("Substructure patterns"): all embeddings of each of P query graphs in
+ * each of B molecular graphs, exact in integers.  The definition is this package's OWN (DESIGN.md states it in full): a
+ * small query language and a subgraph-monomorphism search, not RDKit's substructure matcher.
+ *   mcg_substructure_match: z, bonds, n_nodes_dev as mcg_canonical_order takes them (no degree cap); nh_or_null[B,W]: the
+ *                       hydrogens of every atom, or NULL: max(0, (2 v0 - v2) / 2) from the bond codes.
+ *                       Pattern p, ALREADY IN MATCHING ORDER (per component breadth-first from its lowest atom, neighbours
+ *                       ascending, components by their lowest atom - the host's business): pat_n[p] query atoms (clamped
+ *                       to 0..32 on the device; 0 atoms match nothing);
+ *                       pat_atoms[p][k] = two words: word 0 the element mask (bit Z set: allowed; all ones: any element,
+ *                       also one beyond Z = 63), word 1 the bytes dmin, dmax, hmin, hmax, ring, arom from the low end
+ *                       (dmin <= bonded atoms <= dmax, hmin <= hydrogens <= hmax; ring / arom: 0 any, 1 yes, 2 no - the
+ *                       atom has a ring bond / a code-4 bond);
+ *                       pat_bonds[p][k][q], read for q < k only: 0 no query bond, else the low nibble the allowed codes
+ *                       (bit c - 1: code c) and bits 4-5 the ring requirement (0 any, 1 a ring bond, 2 a chain bond).  A
+ *                       bond is a ring bond iff its ends stay connected without it.
+ *                       An embedding is an injective map of the positions to atoms that satisfies every query atom and
+ *                       lands every query bond on a bond that satisfies it; pairs without a query bond are free.  Search,
+ *                       per root atom r ascending: position 0 takes r, position k then every atom, ascending, that is
+ *                       unused, in k's domain and rightly bonded to the images of the earlier positions k has a query bond
+ *                       with; each accepted assignment is a node; every embedding is enumerated.  A root that would take a
+ *                       node beyond MCG_SUBSTRUCTURE_NODE_BUDGET stops there and the pair's status is _BUDGET.
+ *                       count[b,p]: the embeddings found (a lower bound under _BUDGET); status[b,p]: 0 or _BUDGET;
+ *                       first[b,p,0..31]: the atoms of the embedding found first (the smallest in matching order), -1
+ *                       beyond the pattern's atoms and throughout where count is 0; covered[b,p]: bit a set where atom a
+ *                       lies in any embedding found.
+ *                       One 64-lane workgroup per (molecule, chunk of the patterns), lane = root atom, every lane its own
+ *                       depth-first search on an LDS stack; one launch, integers only, no atomics, no scratch: a pair's
+ *                       outputs have the same bits whatever the batch, the row, the padded width and the other patterns.
+ * The pattern tables are device memory: any bytes in them are safe.  B = 0 launches nothing.  MCG_ERR_ARG, nothing
+ * launched: a null buffer other than nh_or_null, B outside 0..MCG_SUBSTRUCTURE_MAX_B, W outside
+ * 1..MCG_SUBSTRUCTURE_MAX_ATOMS, P outside 1..MCG_SUBSTRUCTURE_MAX_PATTERNS. */
+#define MCG_SUBSTRUCTURE_MAX_ATOMS 64
+#define MCG_SUBSTRUCTURE_MAX_PATTERN_ATOMS 32
+#define MCG_SUBSTRUCTURE_MAX_PATTERNS 64
+#define MCG_SUBSTRUCTURE_MAX_B 16384
+#define MCG_SUBSTRUCTURE_NODE_BUDGET 65536
+#define MCG_SUBSTRUCTURE_BUDGET 1
+int mcg_substructure_match(const int32_t* z, const int8_t* bonds, const int32_t* n_nodes_dev,
+                           const int32_t* nh_or_null, int B, int W, const int32_t* pat_n,
+                           const uint64_t* pat_atoms /*[P,32,2]*/, const uint8_t* pat_bonds /*[P,32,32]*/, int P,
+                           int32_t* count /*[B,P]*/, int32_t* status /*[B,P]*/, int32_t* first /*[B,P,32]*/,
+                           uint64_t* covered /*[B,P]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,7 @@ from . import postprocess
 from . import rdkit_order
 from . import receptor as mcg_receptor
 from . import canonical as mcg_canonical
+from . import substructure as mcg_sub
 from . import fingerprint as mcg_fp
 from . import geometry as mcg_geometry
 from . import electrostatics as mcg_esp
@@ -362,6 +363,15 @@ class MLConformerGenerator(torch.nn.Module):
         unchecked: the codes come from the bond write-back or from `mol_graph`; device tensors)."""
         return mcg_canonical.canonical_order(atomic_numbers, bond_orders, n_nodes, self.device, check=False)
 
+    # the substructure step
+    def _match_substructures(self, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor,
+                             compiled) -> dict:
+        """Every pattern of `compiled` (`substructure.compile_patterns`) matched against padded graphs: `count`, `status`,
+        `first`, `covered` (`substructure.match_substructures`, unchecked: the codes come from the bond write-back or from
+        `mol_graph`; device tensors).  The hydrogens (`hydrogens.implicit_counts`, host) are counted only where a pattern
+        constrains them."""
+        return mcg_sub.match_substructures(atomic_numbers, bond_orders, n_nodes, compiled, device=self.device, check=False)
+
     # the pharmacophore step
     def _pharm_perceive(self, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor):
         """(types [B,W] uint8, ring masks [B,32] int64, ring counts [B]) of padded graphs
@@ -603,7 +613,8 @@ class MLConformerGenerator(torch.nn.Module):
                             add_hydrogens: bool = False, standardize: bool = False,
                             electrostatic_scores: bool = False, reference_charges=None,
                             min_electrostatic_tanimoto: Optional[float] = None, partial_charges: bool = False,
-                            smiles: bool = False, exclude_graphs=None) -> List:
+                            smiles: bool = False, exclude_graphs=None, require_substructures=None,
+                            exclude_substructures=None, substructure_counts=None) -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
@@ -780,9 +791,23 @@ class MLConformerGenerator(torch.nn.Module):
         (`fingerprint.mol_graph`: their heavy atoms).  They are read with the other arguments and labelled by the same
         kernel directly in front of the generation, behind every refusal of the call, and a generated molecule whose
         exact identity equals one of them is dropped, in front of `unique`.
+        `require_substructures=` / `exclude_substructures=` / `substructure_counts=`: each an iterable of patterns - strings
+        in a small, labelled subset of SMARTS (`substructure.parse`: "c1ccccc1", "C(=O)[Cl,Br]", "[nH]", "*@*"),
+        `substructure.Pattern`s, or graphs (`GeneratedMolecule`, Mol, (atomic_numbers, bond_orders) pair: the piece with
+        exact elements and bond codes, `substructure.from_graph` - the check that a `fixed_fragment` survived the bond
+        network); `substructure.CATALOGUE` is a short list of unwanted groups.  All of them are matched against the
+        returned molecules' graphs (with `standardize` the parent fragment's) in ONE launch of a subgraph-monomorphism search
+        on the GPU (`substructure.match_substructures`; DESIGN.md section 6, "Substructure patterns": the package's OWN
+        definition, NOT RDKit's `HasSubstructMatch`).  A molecule stays only if every required pattern is proven present
+        (count >= 1) and no excluded one is; a search that hits its node budget before it finds an embedding leaves the
+        row undetermined - `require` drops it, `exclude` keeps it, one warning names how many.  Records carry
+        `substructure_patterns` (the three lists in that order) and, per pattern, `substructure_counts`,
+        `substructure_status` and `substructure_first` (the atoms of the first embedding); through RDKit's finisher the
+        Mols' own graphs are read and the counts are set as the space-separated property `substructure_counts` (that path
+        is not tested where RDKit is absent).  All None in a call without the options, which launches nothing new.
         Order of the stages: validity, `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`,
-        `min_pharmacophore_tanimoto`, `min_electrostatic_tanimoto`, `exclude_graphs`, `unique`, then the selection
-        (threshold, exclusion, `top_k`).  The filters only remove molecules.
+        `min_pharmacophore_tanimoto`, `min_electrostatic_tanimoto`, `require_substructures`, `exclude_substructures`,
+        `exclude_graphs`, `unique`, then the selection (threshold, exclusion, `top_k`).  The filters only remove molecules.
         Refused with ValueError before any device work: a chemical option that is not a bool / a real number in (0, 1],
         a chemical score without a reference graph, a `reference_graph` that `fingerprint.mol_graph` refuses or that has no
         or more than 64 heavy atoms, scoring or posing without a reference conformer, a reference
@@ -806,7 +831,9 @@ class MLConformerGenerator(torch.nn.Module):
         that is not a bool or on a generator with a finisher (RDKit's finisher runs `standardize_mol` itself), smiles that
         is not a bool or on a generator with a finisher, a unique other than True, False or "exact", and an
         `exclude_graphs` entry that is unreadable, has more than 64 heavy atoms or has no canonical order (the message
-        names its position).  A reference
+        names its position), a substructure option that is no iterable of patterns or holds an entry that cannot be read
+        or has more than 32 query atoms (the message names the list, the position and, for a string, the character), and a
+        substructure option on a generator with a custom finisher.  A reference
         graph in which no feature is found is refused where it is perceived, behind the generation."""
         if sample_seed is not None:
             seeding.check_seed(sample_seed)
@@ -817,7 +844,8 @@ class MLConformerGenerator(torch.nn.Module):
                                         reference_context, relax_geometry, pharmacophore_scores,
                                         reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes,
                                         add_hydrogens, standardize, electrostatic_scores, reference_charges,
-                                        min_electrostatic_tanimoto, partial_charges, smiles, exclude_graphs)
+                                        min_electrostatic_tanimoto, partial_charges, smiles, exclude_graphs,
+                                        require_substructures, exclude_substructures, substructure_counts)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         req = postprocess.label_excluded(self, req)      # `exclude_graphs`: the first device work, behind every check above
@@ -858,7 +886,8 @@ class MLConformerGenerator(torch.nn.Module):
                                     electrostatic_scores: bool = False, reference_charges=None,
                                     min_electrostatic_tanimoto: Optional[float] = None,
                                     partial_charges: bool = False, smiles: bool = False,
-                                    exclude_graphs=None) -> List:
+                                    exclude_graphs=None, require_substructures=None, exclude_substructures=None,
+                                    substructure_counts=None) -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -881,6 +910,8 @@ class MLConformerGenerator(torch.nn.Module):
         `electrostatic_scores`, `reference_charges`, `min_electrostatic_tanimoto`, `partial_charges` (behind the gather, on
         the rows a rank returns, like the hydrogens), `smiles`, `unique="exact"`, `exclude_graphs` (labelled behind the
         gather, on the rows a rank returns, beside the fingerprints; every rank labels the excluded graphs itself),
+        `require_substructures`, `exclude_substructures`, `substructure_counts` (matched behind the gather, on the rows a
+        rank returns; every rank compiles the patterns itself),
         `add_hydrogens` (placed behind the gather, on the rows a rank returns), `standardize` (on each rank's own shard,
         before the gather; its per-sample tensors travel with the rest, one collective each): as in
         `generate_conformers` (every rank loads the mesh and computes its occupancy itself).  The fingerprints are computed behind the gather,
@@ -904,7 +935,8 @@ class MLConformerGenerator(torch.nn.Module):
                                         reference_context, relax_geometry, pharmacophore_scores,
                                         reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes,
                                         add_hydrogens, standardize, electrostatic_scores, reference_charges,
-                                        min_electrostatic_tanimoto, partial_charges, smiles, exclude_graphs)
+                                        min_electrostatic_tanimoto, partial_charges, smiles, exclude_graphs,
+                                        require_substructures, exclude_substructures, substructure_counts)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)

@@ -66,6 +66,10 @@ class Measured:
     hydrogen_charges: Optional[object] = None     # [n] fp32, host - likewise
     canonical_order: Optional[object] = None      # List[int] - or (batch [B,W] int32, row, n), sliced on first read
     canonical_status: Optional[int] = None        # `canonical.describe_status`; 0 = the order is canonical
+    substructure_counts: Optional[object] = None  # List[int], one per pattern - or (batch [B,P] int32, row), sliced on first read
+    substructure_status: Optional[object] = None  # List[int] (`substructure.describe_status`) - likewise
+    substructure_first: Optional[object] = None   # per pattern the first embedding or None - or (batch [B,P,M], row), likewise
+    substructure_patterns: Optional[tuple] = None     # the call's `substructure.Pattern`s: require, exclude, counts, in order
 
 
 _UNMEASURED = Measured()          # shared by every record that carries no values: never written to
@@ -89,9 +93,14 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
     one host copy, row, atom count) and sliced on first read.  `electrostatic_tanimoto` [n] fp32 is taken as it comes.
     The canonical labelling of a call with `smiles` comes as `canonical_order` [n,W] int32 (-1 beyond a row's atoms, and
     throughout a row that has no canonical order) and `canonical_status` [n] (both or neither); a record's
-    `canonical_order` is left as (the one host copy, row, atom count) and sliced on first read."""
+    `canonical_order` is left as (the one host copy, row, atom count) and sliced on first read.
+    The matches of a call with a substructure option come as `substructure_counts` [n,P], `substructure_status` [n,P],
+    `substructure_first` [n,P,M] int32 (the caller's pattern atom order, -1 beyond a pattern's atoms) and
+    `substructure_patterns`, the tuple of the P patterns, which every record shares (all four or none); a record's three
+    fields are left as (the one host copy, row) and sliced on first read (`substructure_row`)."""
     hyd = {k: values.get(k) for k in ("hydrogen_coords", "hydrogen_parents", "atom_map", "kekule_bond_orders",
-                                      "partial_charges", "hydrogen_charges", "canonical_order")}
+                                      "partial_charges", "hydrogen_charges", "canonical_order", "substructure_counts",
+                                      "substructure_status", "substructure_first", "substructure_patterns")}
     cols = {k: v.cpu().tolist() for k, v in values.items() if v is not None and k != "pose" and k not in hyd}
     if values.get("pose") is not None:
         poses = values["pose"].cpu().to(torch.float32)
@@ -135,7 +144,25 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
     if hyd["canonical_order"] is not None:
         orders = hyd["canonical_order"].cpu().to(torch.int32)
         cols["canonical_order"] = [(orders, b, k) for b, k in enumerate((orders >= 0).sum(dim=1).tolist())]
+    if hyd["substructure_counts"] is not None:
+        for k in ("substructure_counts", "substructure_status", "substructure_first"):
+            host = hyd[k].cpu().to(torch.int32)
+            cols[k] = [(host, b) for b in range(n)]
+        cols["substructure_patterns"] = [tuple(hyd["substructure_patterns"])] * n
     return [Measured(**{k: col[b] for k, col in cols.items()}) for b in range(n)]
+
+
+def substructure_row(measured: Measured) -> None:
+    """Slices a record's substructure fields from the batch's host tensors, once: counts and status become one int per
+    pattern, first per pattern the molecule's atom each pattern atom lands on (the pattern's own atom order), None where
+    the pattern was not found."""
+    if isinstance(measured.substructure_counts, tuple):
+        for k in ("substructure_counts", "substructure_status"):
+            host, b = getattr(measured, k)
+            setattr(measured, k, host[b].tolist())
+        host, b = measured.substructure_first
+        measured.substructure_first = [row[: len(p.atoms)] if c > 0 else None for row, p, c in
+                                       zip(host[b].tolist(), measured.substructure_patterns, measured.substructure_counts)]
 
 
 class GeneratedMolecule:
@@ -172,7 +199,11 @@ class GeneratedMolecule:
     `to_xyz_block(charges=True)` writes them.
     `canonical_order` / `canonical_status` / `smiles`: its exact canonical atom order and canonical SMILES when the call
     asked for `smiles` (`canonical.py`, `smiles.py`: the package's own definition - valid OpenSMILES, NOT RDKit's canonical
-    SMILES), else None; `to_smiles()` writes the string, `to_smiles(canonical=False)` one in the record's own atom order."""
+    SMILES), else None; `to_smiles()` writes the string, `to_smiles(canonical=False)` one in the record's own atom order.
+    `substructure_patterns` / `substructure_counts` / `substructure_status` / `substructure_first`: the patterns the call
+    matched (`require_substructures`, `exclude_substructures`, `substructure_counts`, in that order) and, per pattern, how
+    many embeddings this molecule has, how the search ended and the first embedding (`substructure.py`: the package's own
+    definition, NOT RDKit's substructure matcher), else None."""
     __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_measured", "_smiles")
 
     def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True,
@@ -191,6 +222,34 @@ class GeneratedMolecule:
         m._measured = measured
         m._smiles = None
         return m
+
+    @property
+    def substructure_patterns(self) -> Optional[tuple]:
+        """The `substructure.Pattern`s this call matched - those of `require_substructures`, then `exclude_substructures`,
+        then `substructure_counts` - which the three fields below are indexed by; None in a call without them."""
+        return self._measured.substructure_patterns
+
+    @property
+    def substructure_counts(self) -> Optional[List[int]]:
+        """Per pattern of `substructure_patterns` the embeddings of it in this molecule's graph (`substructure.py`: every
+        injective map counts, so benzene's ring is found 12 times; a lower bound where the status is BUDGET).  With
+        `standardize` the parent fragment's graph is read.  None in a call without a substructure option."""
+        substructure_row(self._measured)
+        return self._measured.substructure_counts
+
+    @property
+    def substructure_status(self) -> Optional[List[int]]:
+        """Per pattern 0, or `substructure.STATUS_BUDGET` (`substructure.describe_status`): a root's search was stopped at
+        the node budget, the count is a lower bound and a count of 0 proves nothing."""
+        substructure_row(self._measured)
+        return self._measured.substructure_status
+
+    @property
+    def substructure_first(self) -> Optional[List[Optional[List[int]]]]:
+        """Per pattern the embedding found first: entry i is the index, in this record, of the atom that pattern atom i (the
+        pattern's own atom order) lands on - for highlighting; None where the pattern was not found."""
+        substructure_row(self._measured)
+        return self._measured.substructure_first
 
     @property
     def canonical_status(self) -> Optional[int]:
@@ -673,7 +732,11 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                            partial_charges: Optional[torch.Tensor] = None,
                            hydrogen_charges: Optional[torch.Tensor] = None,
                            canonical_order: Optional[torch.Tensor] = None,
-                           canonical_status: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
+                           canonical_status: Optional[torch.Tensor] = None,
+                           substructure_counts: Optional[torch.Tensor] = None,
+                           substructure_status: Optional[torch.Tensor] = None,
+                           substructure_first: Optional[torch.Tensor] = None,
+                           substructure_patterns: Optional[tuple] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
     (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
     (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records).
@@ -700,6 +763,8 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     `electrostatics.partial_charges` returns them, +inf at and beyond the row's atoms (both or neither; None: a call
     without `partial_charges`).  `canonical_order[b]` [W] int32 (-1 beyond the row's atoms) / `canonical_status[b]`: row b's
     canonical labelling as `canonical.canonical_order` returns it (both or neither; None: a call without `smiles`).
+    `substructure_counts[b]` [P] / `substructure_status[b]` [P] / `substructure_first[b]` [P,M] with the P patterns
+    `substructure_patterns`: row b's matches as `substructure.match_substructures` returns them (all four or none).
     The value keywords are the fields of `Measured`
     and go to `measured_from_tensors`; a call with no ids and no values builds the views and nothing else."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
@@ -715,7 +780,9 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                   atoms_removed=atoms_removed, n_fragments=n_fragments, atom_map=atom_map,
                   kekule_bond_orders=kekule_bond_orders, electrostatic_tanimoto=electrostatic_tanimoto,
                   partial_charges=partial_charges, hydrogen_charges=hydrogen_charges,
-                  canonical_order=canonical_order, canonical_status=canonical_status)
+                  canonical_order=canonical_order, canonical_status=canonical_status,
+                  substructure_counts=substructure_counts, substructure_status=substructure_status,
+                  substructure_first=substructure_first, substructure_patterns=substructure_patterns)
     if sample_ids is None and all(v is None for v in values.values()):
         return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
     flags = valid.cpu().tolist()

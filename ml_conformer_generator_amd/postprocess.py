@@ -21,13 +21,15 @@ Stages, in this order:
        placement of `add_hydrogens` is reused when that is on too - one charge launch and, with `electrostatic_scores`,
        the overlap launches against the reference's charge points; and the canonical step (`identities`; `smiles`,
        `unique="exact"`, `exclude_graphs`): one `_canonical_order` launch over the rows - the excluded graphs were
-       labelled by the same seam directly in front of the generation (`label_excluded`);
+       labelled by the same seam directly in front of the generation (`label_excluded`); and the substructure step
+       (`substructures`; `require_substructures`, `exclude_substructures`, `substructure_counts`): one
+       `_match_substructures` call over the rows, every pattern of the three lists in it;
     5. the values are attached - each molecule's `handoff.Measured`, behind a record's properties or written onto the
        Mol by `rdkit_finish.tag_measured` (Mols lose their properties in the object gather) - and validity is taken
        (`last_valid_fraction`);
     6. `select`, written once for both paths: `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`,
-       `min_pharmacophore_tanimoto`, `min_electrostatic_tanimoto`, `exclude_graphs`, `unique`, then the
-       threshold / sphere exclusion / `top_k` walk of `cheminformatics.select_diverse`.  The two pair matrices are
+       `min_pharmacophore_tanimoto`, `min_electrostatic_tanimoto`, `require_substructures`, `exclude_substructures`,
+       `exclude_graphs`, `unique`, then the threshold / sphere exclusion / `top_k` walk of `cheminformatics.select_diverse`.  The two pair matrices are
        computed only when their threshold is set, over the rows that survived the filters.
 A call with no option on takes none of these steps: its records / live Mols are returned as they come.
 `standardize` is not a stage here: the generator standardises right behind the bond write-back, so the result tensors
@@ -36,7 +38,7 @@ that arrive are already the parent fragments'; its four per-sample tensors (`ato
 
 The device work goes through the generator's seams (`_pose`, `_score`, `_pair`, `_receptor_coords`,
 `_relieve`, `_score_placed`, `_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, `_pharm_perceive`, `_pharm_score`,
-`_add_hydrogens`, `_peoe_charges`, `_esp_score`, `_canonical_order`),
+`_add_hydrogens`, `_peoe_charges`, `_esp_score`, `_canonical_order`, `_match_substructures`),
 looked up on the instance at the time of the call.  The shape
 seams take the request's reference object; which kind it is - a conformer or a solid - is `cheminformatics`' business."""
 from __future__ import annotations
@@ -44,6 +46,7 @@ from __future__ import annotations
 import dataclasses
 import numbers
 import time
+import warnings
 from typing import List, NamedTuple, Optional, Union
 
 import torch
@@ -58,6 +61,7 @@ from . import hydrogens as mcg_hydrogens
 from . import pharmacophore as mcg_pharm
 from . import receptor as mcg_receptor
 from . import standardize as mcg_standardize
+from . import substructure as mcg_sub
 from .handoff import Measured, measured_from_tensors, molecules_from_tensors
 
 
@@ -99,6 +103,10 @@ class Request:
     excluded_graphs: Optional[tuple] = None       # `exclude_graphs` as read on the host: (atomic numbers, bond codes) each
     exclude: Optional[frozenset] = None           # their (key, identity bytes), once `label_excluded` has labelled them
     # `unique` above is False, True (one row per `graph_key`) or "exact" (one row per exact identity)
+    substructures: Optional[object] = None        # `substructure.Compiled`: the patterns of `require_substructures`, then
+    #                                               `exclude_substructures`, then `substructure_counts`, compiled together
+    n_required: int = 0                           # how many of them must be proven present,
+    n_excluded: int = 0                           # and how many, behind those, drop a row where proven present
 
     @property
     def selects_by_shape(self) -> bool:
@@ -124,7 +132,8 @@ class Request:
     @property
     def measures(self) -> bool:
         """Whether any option is on (a receptor needs the pose, a selection implies its score)."""
-        return self.overlay or self.scores_shape or self.needs_fingerprints or self.needs_canonical
+        return (self.overlay or self.scores_shape or self.needs_fingerprints or self.needs_canonical
+                or self.substructures is not None)
 
     @property
     def removes(self) -> bool:
@@ -132,7 +141,7 @@ class Request:
         return (self.max_receptor_clashes is not None or self.max_chemical_tanimoto is not None or bool(self.unique)
                 or self.excluded_graphs is not None or self.selects_by_shape or self.max_pairwise_chemical_tanimoto is not None
                 or self.max_atoms_outside is not None or self.min_pharmacophore_tanimoto is not None
-                or self.min_electrostatic_tanimoto is not None)
+                or self.min_electrostatic_tanimoto is not None or self.n_required > 0 or self.n_excluded > 0)
 
     @property
     def needs_charges(self) -> bool:
@@ -161,7 +170,8 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
                   rank_by: str = "shape", relieve_clashes: Union[bool, int] = False, add_hydrogens=False,
                   standardize=False, electrostatic_scores=False, reference_charges=None,
                   min_electrostatic_tanimoto: Optional[float] = None, partial_charges=False, smiles=False,
-                  exclude_graphs=None) -> Request:
+                  exclude_graphs=None, require_substructures=None, exclude_substructures=None,
+                  substructure_counts=None) -> Request:
     """The public option keywords of a generation entry of `gen` as a `Request`: the shape options first, then the chemical
     ones (`top_k` / `min_shape_tanimoto` / `max_pairwise_tanimoto` imply the shape score, `max_chemical_tanimoto` the
     chemical one).  `reference_shape`: a watertight mesh in place of the reference conformer (`mesh.load_mesh`); the
@@ -187,6 +197,10 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     call drops; an entry that is unreadable or has more than 64 heavy atoms is a ValueError naming its position.  The
     graphs are only read here; the entries label them (`label_excluded`, one `_canonical_order` launch per 16 384) behind
     their own argument checks, directly in front of the generation, where one without a canonical order is refused.
+    `require_substructures` / `exclude_substructures` / `substructure_counts`: each None or an iterable of pattern strings
+    (`substructure.parse`), `substructure.Pattern`s or graph sources (`substructure.from_graph`); they are compiled here,
+    together (`compile_substructures`: host work), and an entry that cannot be read or breaks a limit is a ValueError
+    naming its list and position; refused with a custom finisher, through RDKit's the Mols' own graphs are read.
     Every refusal happens here, before any device work."""
     mcg_pharm.check_flag("smiles", smiles)
     if smiles and getattr(gen, "finisher", None) is not None:
@@ -344,6 +358,12 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     if not (isinstance(unique, str) and unique == "exact"):
         mcg_fp.check_flag("unique", unique)
     excluded = None if exclude_graphs is None else read_excluded(exclude_graphs)
+    patterns, n_required, n_excluded = compile_substructures(require_substructures, exclude_substructures,
+                                                             substructure_counts)
+    if patterns is not None:
+        if custom_finisher:
+            raise ValueError(mcg_sub.REFUSAL_WITH_FINISHER)
+        common.update(substructures=patterns, n_required=n_required, n_excluded=n_excluded)
     if max_chemical_tanimoto is not None:
         mcg_fp.check_threshold("max_chemical_tanimoto", max_chemical_tanimoto)
     if max_pairwise_chemical_tanimoto is not None:
@@ -377,6 +397,25 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     return Request(ref_graph=graph, scores_chemistry=bool(scoring), max_chemical_tanimoto=max_chemical_tanimoto,
                    unique=unique, max_pairwise_chemical_tanimoto=max_pairwise_chemical_tanimoto, **shape,
                    **common)
+
+
+def compile_substructures(require, exclude, counts):
+    """(`substructure.Compiled` or None, n_required, n_excluded): the patterns of the three substructure options - each None
+    or what `substructure.compile_patterns` takes - compiled together, in that order, so that one matching call serves all
+    three.  Host work only.  ValueError naming the option and the position of an entry that cannot be read."""
+    lists = [() if arg is None else mcg_sub.compile_patterns(arg, where=name).patterns
+             for name, arg in (("require_substructures", require), ("exclude_substructures", exclude),
+                               ("substructure_counts", counts))]
+    if not any(lists):
+        return None, 0, 0
+    return mcg_sub.compile_patterns([p for part in lists for p in part]), len(lists[0]), len(lists[1])
+
+
+def substructures(gen, req: Request, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor):
+    """The substructure step of padded graphs, ONE `_match_substructures` call with every pattern of the request: (its
+    result, per row (counts, status) over the patterns as host lists - what `select` reads)."""
+    out = gen._match_substructures(atomic_numbers, bond_orders, n_nodes, req.substructures)
+    return out, list(zip(out["count"].cpu().tolist(), out["status"].cpu().tolist()))
 
 
 def read_excluded(exclude_graphs) -> List[tuple]:
@@ -456,6 +495,7 @@ class Rows:
     measured: List[Measured]
     row: List[int]                                # index into the device tensors behind the pair matrices
     exact: Optional[List[Optional[tuple]]] = None     # `identities` per row, where the call compares exact identities
+    sub: Optional[List[tuple]] = None                 # `substructures` per row, where the call matches patterns
 
     def take(self, keep: List[int]) -> "Rows":
         """The rows at the positions `keep`, in that order."""
@@ -468,6 +508,10 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
     without a count - its pose failed - does not pass), then those with a chemical Tanimoto below `max_chemical_tanimoto` (NaN
     does not pass), then those with a pharmacophore Tanimoto of at least `min_pharmacophore_tanimoto` (NaN and None do not
     pass), then those with an electrostatic Tanimoto of at least `min_electrostatic_tanimoto` (NaN and None do not pass),
+    then `require_substructures` - the rows in which every required pattern is PROVEN present (count >= 1) - and
+    `exclude_substructures` - the rows in which no excluded pattern is proven present; a row whose search for a pattern
+    ended with BUDGET before it found an embedding is undetermined: not proven to contain it, so `require` drops it and
+    `exclude` keeps it, and one warning per call names how many such rows there were -,
     then `exclude_graphs` - the rows whose exact identity is one of the excluded graphs' (a row without a canonical order is
     not proven equal to anything and stays) -, then `unique` - of the rows with one graph key (`unique="exact"`: with one
     exact identity, `select_exact`) the first in ranking order
@@ -492,6 +536,15 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
     if req.min_electrostatic_tanimoto is not None:
         rows = rows.take([i for i, m in enumerate(rows.measured) if m.electrostatic_tanimoto is not None
                           and m.electrostatic_tanimoto >= req.min_electrostatic_tanimoto])
+    if req.n_required or req.n_excluded:
+        need, last = req.n_required, req.n_required + req.n_excluded
+        undetermined = sum(1 for c, st in rows.sub if any(st[p] != 0 and c[p] == 0 for p in range(last)))
+        if undetermined:
+            warnings.warn(f"substructure matching: {undetermined} molecule(s) left undetermined - the search for a required "
+                          f"or excluded pattern ended with BUDGET ({mcg_sub.NODE_BUDGET} nodes from one root) before it "
+                          "found an embedding; require_substructures drops such a row, exclude_substructures keeps it")
+        rows = rows.take([i for i, (c, _) in enumerate(rows.sub) if all(c[p] >= 1 for p in range(need))
+                          and not any(c[p] >= 1 for p in range(need, last))])
     if req.excluded_graphs is not None:
         if req.exclude is None:
             raise RuntimeError("the request's exclude_graphs were not labelled: call label_excluded before the selection")
@@ -701,6 +754,11 @@ def return_records(gen, req: Request, res: dict, row_ids: Optional[torch.Tensor]
         canon = gen._canonical_order(res["elements"], res["bond"], res["n_nodes"])
     if req.smiles:
         values.update(canonical_order=canon["order"], canonical_status=canon["status"])
+    sub = None
+    if req.substructures is not None:
+        matched, sub = substructures(gen, req, res["elements"], res["bond"], res["n_nodes"])
+        values.update(substructure_counts=matched["count"], substructure_status=matched["status"],
+                      substructure_first=matched["first"], substructure_patterns=req.substructures.patterns)
     if req.scores_pharmacophore:
         sim, hits = pharmacophore(gen, req, res["x"], res["elements"], res["bond"], res["n_nodes"])
         posed = torch.isfinite(res["pose"]).all(dim=1).to(sim.device)         # a failed pose is not in the reference's frame
@@ -725,7 +783,8 @@ def return_records(gen, req: Request, res: dict, row_ids: Optional[torch.Tensor]
     if not req.removes:
         return kept
     rows = Rows(kept, [m.sample_id for m in kept], [m._measured for m in kept], [m.batch_row for m in kept],
-                None if exact is None else [exact[m.batch_row] for m in kept])
+                None if exact is None else [exact[m.batch_row] for m in kept],
+                None if sub is None else [sub[m.batch_row] for m in kept])
 
     def shape_pair(left: Rows):
         x = res["x"]
@@ -869,6 +928,16 @@ def return_finished(gen, req: Request, samples: List[Finished], row_ids: Optiona
             m.chemical_tanimoto, m.graph_key = c.chemical_tanimoto, c.graph_key
     if req.needs_identity:                        # the live Mols' own graphs, like the fingerprints
         rows.exact = identities(gen, *mcg_fp.pad_graphs([mcg_fp.mol_graph(m) for m in rows.item]))[1] if live else []
+    if req.substructures is not None:             # likewise the live Mols' own graphs
+        rows.sub = []
+        if live:
+            matched, rows.sub = substructures(gen, req, *mcg_fp.pad_graphs([mcg_fp.mol_graph(m) for m in rows.item]))
+            found = measured_from_tensors(dict(substructure_counts=matched["count"], substructure_status=matched["status"],
+                                               substructure_first=matched["first"],
+                                               substructure_patterns=req.substructures.patterns), len(live))
+            for m, c in zip(rows.measured, found):
+                m.substructure_counts, m.substructure_status = c.substructure_counts, c.substructure_status
+                m.substructure_first, m.substructure_patterns = c.substructure_first, c.substructure_patterns
     posed = [i for i, m in enumerate(rows.measured) if m.pose is not None]
     if req.scores_pharmacophore and posed:        # the live, posed Mols' heavy atoms and their own graphs
         z, bonds, nn = mcg_fp.pad_graphs([mcg_fp.mol_graph(rows.item[i]) for i in posed])

@@ -152,17 +152,21 @@ def tag_sample_ids(mols: Sequence, sample_ids: Sequence[int]) -> None:
 MEASURED_PROPS = dict(shape_tanimoto="double", overlay_tanimoto="double", receptor_clashes="int",
                       receptor_max_overlap="double", atoms_outside="int", chemical_tanimoto="double", graph_key="string",
                       strain_before="double", strain_after="double", pharmacophore_tanimoto="double",
-                      pharmacophore_matches="int", relief_rmsd="double", receptor_clashes_before="int")
-_SETTERS = {"int": ("SetIntProp", int), "double": ("SetDoubleProp", float), "string": ("SetProp", lambda k: str(int(k)))}
+                      pharmacophore_matches="int", relief_rmsd="double", receptor_clashes_before="int",
+                      substructure_counts="list", substructure_status="list")
+_SETTERS = {"int": ("SetIntProp", int), "double": ("SetDoubleProp", float), "string": ("SetProp", lambda k: str(int(k))),
+            "list": ("SetProp", lambda v: " ".join(str(int(k)) for k in v))}      # one number per pattern, space separated
 
 
 def tag_measured(mols: Sequence, measured: Sequence) -> None:
     """Set the properties of `MEASURED_PROPS` on every Mol of `mols` (None = dropped) from `measured[k]`, its
     `handoff.Measured`; a value of None sets no property.  Set after the object gather: RDKit does not pickle Mol
     properties by default.  What a custom finisher returns is tagged only as far as it has the setter."""
+    from .handoff import substructure_row
     for m, rec in zip(mols, measured):
         if m is None:
             continue
+        substructure_row(rec)
         for prop, kind in MEASURED_PROPS.items():
             value, (setter, cast) = getattr(rec, prop), _SETTERS[kind]
             if value is not None and hasattr(m, setter):
