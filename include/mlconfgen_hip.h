@@ -836,6 +836,38 @@ int mcg_substructure_match(const int32_t* z, const int8_t* bonds, const int32_t*
                            int32_t* count /*[B,P]*/, int32_t* status /*[B,P]*/, int32_t* first /*[B,P,32]*/,
                            uint64_t* covered /*[B,P]*/, void* stream);
 
+/* ---- Receptor interactions ("Receptor interactions"): an empirical interaction score of B posed
+ * molecules against a typed receptor.  The definition is this package's OWN (interactions.py states it in full): the
+ * functional form of the AutoDock Vina scoring function on the package's heavy-atom types, intermolecular terms only - NOT
+ * AutoDock Vina's output and not a binding free energy.
+ *   lig_xyz[B,N,3], lig_radius[B,N] (interaction radii), lig_type[B,N] (bits: 1 donor, 2 acceptor, 4 hydrophobic),
+ *   n_nodes_dev[b] real atoms (device memory, clamped to [0, min(N, 64)] on the device; everything at or beyond n_b is
+ *   ignored, whatever it holds), n_rot_dev[b] rotatable bonds (device memory, negative counts as 0);
+ *   rec_xyzr[R,4] (x, y, z, interaction radius) and rec_type[R] (the same bits), in the order the caller wants them
+ *   walked; tile_sphere: NULL, or [ceil(R / 256), 4] centre and radius of a sphere that holds every atom of each tile of
+ *   256 consecutive receptor atoms - a tile whose sphere stays beyond the cut-off of the ligand's is skipped, which changes
+ *   no bit.
+ *   Pair (i, j): r2 = dx*dx + dy*dy + dz*dz in fp32, every operation rounded on its own in that order; the pair COUNTS iff
+ *   r2 < 64.0f; d = sqrtf(r2) - (R_i + R_j).  Terms of a counted pair, all from the fp32 d: g1 = expf(-(2d)^2), g2 =
+ *   expf(-((d - 3) / 2)^2), rep = d*d where d < 0, hyd (both hydrophobic) 1 at d <= 0.5, 1.5 - d up to 1.5, hb (a donor
+ *   facing an acceptor, either way) 1 at d <= -0.7f, d / -0.7f up to 0; a pair that does not count adds nothing.
+ *   atom_terms[B,N,6]: per atom the five sums over j and (((( -0.0356 g1 - 0.00516 g2) + 0.840 rep) - 0.0351 hyd) - 0.587
+ *   hb); 0 on padded atoms.  mol_terms[B,8]: G1, G2, REP, HYD, HB, that weighted sum W of the five, E = W / (1 + 0.0585
+ *   n_rot), 0.  hbonds[b]: the counted donor / acceptor pairs with d <= -0.7f, exact.
+ *   A molecule without atoms: zeros.  One with a non-finite coordinate on a real atom: NaN in its real atoms' terms and in
+ *   mol_terms[0..6], hbonds -1; the other rows unaffected.
+ *   One 256-lane workgroup per molecule: lane l has atom l & 63, wave l >> 6 walks the receptor atoms j = wave (mod 4) of
+ *   each kept tile in ascending order from LDS; an atom's four partial sums are added as (w0 + w1) + (w2 + w3), the
+ *   molecule's by one butterfly over the 64 atom slots.  No atomics, no scratch: a molecule's outputs have the same bits
+ *   whatever the batch, its row, the padded width and the tile skipping.
+ * MCG_ERR_ARG, nothing launched: a null buffer (tile_sphere excepted), B outside 1..MCG_RECEPTOR_MAX_B, N outside 1..64,
+ * R outside 1..MCG_RECEPTOR_MAX_ATOMS. */
+int mcg_receptor_interactions(const float* lig_xyz, const float* lig_radius, const uint8_t* lig_type,
+                              const int32_t* n_nodes_dev, const int32_t* n_rot_dev, int B, int N, const float* rec_xyzr,
+                              const uint8_t* rec_type, int R, const float* tile_sphere /*optional*/,
+                              float* atom_terms /*[B,N,6]*/, float* mol_terms /*[B,8]*/, int32_t* hbonds /*[B]*/,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,9 @@ forced by the scope of this build:
       `electrostatic_scores`, `reference_charges`, `min_electrostatic_tanimoto`, `partial_charges`: does the posed molecule
       present the reference's charge distribution - partial charges by electronegativity equalisation and the Tanimoto
       of their Coulomb overlap with the reference's; a filter; `rank_by="electrostatic"`;
+      `interaction_scores`, `max_interaction_score`: does the posed molecule interact with the receptor - an empirical
+      interaction score with its terms, a hydrogen-bond count and per-atom contributions; a filter;
+      `rank_by="interaction"`;
   * `reference_shape`, `shape_density` (every generation entry): a watertight triangle mesh - an STL file, a (vertices,
     faces) pair - as the reference, what the reference's notebook does with `trimesh` (`mesh.py`, no `trimesh` needed);
     the shape options then score, pose and select against the solid, and `max_atoms_outside` filters on the posed atoms
@@ -92,6 +95,7 @@ from . import fingerprint as mcg_fp
 from . import geometry as mcg_geometry
 from . import electrostatics as mcg_esp
 from . import hydrogens as mcg_hydrogens
+from . import interactions as mcg_interactions
 from . import pharmacophore as mcg_pharm
 from . import standardize as mcg_standardize
 from .handoff import (GeneratedMolecule, assemble_molecules, bond_writeback_hip, molecules_from_tensors,
@@ -406,6 +410,15 @@ class MLConformerGenerator(torch.nn.Module):
         (`electrostatics.electrostatic_tanimoto`)."""
         return mcg_esp.electrostatic_tanimoto(reference_points, points, charges, n_points, self.device)["tanimoto"]
 
+    # the interaction step
+    def _interaction_scores(self, receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_numbers: torch.Tensor,
+                            bond_orders: torch.Tensor) -> dict:
+        """The interaction scores of posed, padded molecules with the call's typed receptor - a
+        `interactions.prepare_receptor` result - (`interactions.interaction_scores`, unchecked: the generator's own
+        graphs; device tensors)."""
+        return mcg_interactions.interaction_scores(receptor, coords, n_nodes, atomic_numbers, bond_orders,
+                                                   device=self.device, check=False)
+
     # the standardisation step
     def _standardize(self, coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
                      n_nodes: torch.Tensor) -> dict:
@@ -614,7 +627,9 @@ class MLConformerGenerator(torch.nn.Module):
                             electrostatic_scores: bool = False, reference_charges=None,
                             min_electrostatic_tanimoto: Optional[float] = None, partial_charges: bool = False,
                             smiles: bool = False, exclude_graphs=None, require_substructures=None,
-                            exclude_substructures=None, substructure_counts=None) -> List:
+                            exclude_substructures=None, substructure_counts=None,
+                            interaction_scores: bool = False,
+                            max_interaction_score: Optional[float] = None) -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
@@ -805,8 +820,25 @@ class MLConformerGenerator(torch.nn.Module):
         `substructure_status` and `substructure_first` (the atoms of the first embedding); through RDKit's finisher the
         Mols' own graphs are read and the counts are set as the space-separated property `substructure_counts` (that path
         is not tested where RDKit is absent).  All None in a call without the options, which launches nothing new.
+        `interaction_scores=True` (needs a `receptor`, and with it `overlay=True`; records path only): does the posed
+        molecule interact with the pocket?  Every returned record carries `interaction_score` - an empirical interaction
+        score E of its returned coordinates (relaxed, posed, refined, relieved) with the typed receptor, negative is
+        better -, `interaction_terms` (the five sums G1, G2, REP, HYD, HB and `n_rot`), `receptor_hbonds` (the donor /
+        acceptor pairs at hydrogen-bond distance, an exact integer) and `interaction_atom_scores` (each atom's weighted
+        contribution); all None where posing failed.  THE PACKAGE'S OWN DEFINITION (`interactions.py`, DESIGN.md section
+        6, "Receptor interactions"): the functional form of the AutoDock Vina scoring function on the package's own
+        heavy-atom typing, intermolecular terms only - NOT AutoDock Vina's output, not a binding free energy, no search.
+        The receptor's atoms are typed by `receptor.load_typed_receptor` - a residue-template table for a PDB string, the
+        element rules for a (coords, atomic_numbers) pair or a Mol, or the explicit third element of a (coords,
+        atomic_numbers, types) triple - once per call; one warning counts the N, O and metal atoms outside the table.  The
+        step runs behind the gather, beside the pharmacophore step, in one launch.
+        `max_interaction_score=t` (implies the score; t a finite real number): keep the molecules with E <= t; NaN and
+        missing do not pass; right behind `min_electrostatic_tanimoto`.
+        `rank_by="interaction"` (needs the score): `unique`, the diversity walk and `top_k` rank by -E;
+        `min_shape_tanimoto` still thresholds the shape score.
         Order of the stages: validity, `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`,
-        `min_pharmacophore_tanimoto`, `min_electrostatic_tanimoto`, `require_substructures`, `exclude_substructures`,
+        `min_pharmacophore_tanimoto`, `min_electrostatic_tanimoto`, `max_interaction_score`, `require_substructures`,
+        `exclude_substructures`,
         `exclude_graphs`, `unique`, then the selection (threshold, exclusion, `top_k`).  The filters only remove molecules.
         Refused with ValueError before any device work: a chemical option that is not a bool / a real number in (0, 1],
         a chemical score without a reference graph, a `reference_graph` that `fingerprint.mol_graph` refuses or that has no
@@ -823,7 +855,10 @@ class MLConformerGenerator(torch.nn.Module):
         pharmacophore_scores that is not a bool, without overlay or without a source of the reference's features, a
         `reference_pharmacophore` that `load_reference_features` refuses or that no option reads, a reference graph whose
         heavy-atom count differs from the reference conformer's, min_pharmacophore_tanimoto outside [0, 1], and a
-        `rank_by` other than "shape", "combo" or "electrostatic", or "combo" / "electrostatic" without both of its scores,
+        `rank_by` other than "shape", "combo", "electrostatic" or "interaction", or "combo" / "electrostatic" without both of
+        its scores or "interaction" without its score, interaction_scores that is not a bool, without a receptor or on a
+        generator with a finisher, a receptor whose types `load_typed_receptor` refuses, max_interaction_score that is not a
+        finite real number,
         electrostatic_scores or partial_charges that is not a bool or on a generator with a finisher, electrostatic scores
         without overlay or without a source of the reference's charges, a `reference_charges` that
         `load_reference_charges` refuses or that no option reads, min_electrostatic_tanimoto outside [-1, 1], and add_hydrogens that is not a bool or on
@@ -845,7 +880,8 @@ class MLConformerGenerator(torch.nn.Module):
                                         reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes,
                                         add_hydrogens, standardize, electrostatic_scores, reference_charges,
                                         min_electrostatic_tanimoto, partial_charges, smiles, exclude_graphs,
-                                        require_substructures, exclude_substructures, substructure_counts)
+                                        require_substructures, exclude_substructures, substructure_counts,
+                                        interaction_scores, max_interaction_score)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         req = postprocess.label_excluded(self, req)      # `exclude_graphs`: the first device work, behind every check above
@@ -887,7 +923,8 @@ class MLConformerGenerator(torch.nn.Module):
                                     min_electrostatic_tanimoto: Optional[float] = None,
                                     partial_charges: bool = False, smiles: bool = False,
                                     exclude_graphs=None, require_substructures=None, exclude_substructures=None,
-                                    substructure_counts=None) -> List:
+                                    substructure_counts=None, interaction_scores: bool = False,
+                                    max_interaction_score: Optional[float] = None) -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -912,6 +949,8 @@ class MLConformerGenerator(torch.nn.Module):
         gather, on the rows a rank returns, beside the fingerprints; every rank labels the excluded graphs itself),
         `require_substructures`, `exclude_substructures`, `substructure_counts` (matched behind the gather, on the rows a
         rank returns; every rank compiles the patterns itself),
+        `interaction_scores`, `max_interaction_score` (scored behind the gather, on the rows a rank returns; every rank
+        types and sorts the receptor itself),
         `add_hydrogens` (placed behind the gather, on the rows a rank returns), `standardize` (on each rank's own shard,
         before the gather; its per-sample tensors travel with the rest, one collective each): as in
         `generate_conformers` (every rank loads the mesh and computes its occupancy itself).  The fingerprints are computed behind the gather,
@@ -936,7 +975,8 @@ class MLConformerGenerator(torch.nn.Module):
                                         reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes,
                                         add_hydrogens, standardize, electrostatic_scores, reference_charges,
                                         min_electrostatic_tanimoto, partial_charges, smiles, exclude_graphs,
-                                        require_substructures, exclude_substructures, substructure_counts)
+                                        require_substructures, exclude_substructures, substructure_counts,
+                                        interaction_scores, max_interaction_score)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)

@@ -1,0 +1,220 @@
+// Receptor interactions ("Receptor interactions"; the definition is the module docstring of
+// interactions.py): an empirical interaction score of every posed molecule against a typed receptor - the functional form
+// of the AutoDock Vina scoring function on the package's own heavy-atom types, intermolecular terms only.
+//   k_receptor_interactions: one 256-lane workgroup per molecule.  Lane l holds ligand atom a = l & 63 in registers
+//                       (coordinates, radius, type); wave w = l >> 6 walks the receptor atoms j = w, w + 4, ... of each
+//                       kept 256-atom tile, tiles and atoms in ascending order.  A tile is staged in LDS as float4
+//                       (x, y, z, R_j) plus one type byte per atom and read by broadcast: every lane of a wave reads the
+//                       same address.  Pair (i, j): r2 = dx*dx + dy*dy + dz*dz, rounded one by one in that order; the pair
+//                       COUNTS iff r2 < 64; d = sqrtf(r2) - (R_i + R_j); the five terms of a counted pair go to the
+//                       lane's five fp32 accumulators and one integer, a pair that does not count adds nothing.  The four
+//                       waves' partials of an atom are combined as (w0 + w1) + (w2 + w3) through LDS, the molecule's sums
+//                       are a fixed butterfly over the 64 atom slots in wave 0 (padded slots hold 0).  No atomics.
+//   Tile list:          with `tile_sphere` the workgroup keeps only the tiles whose bounding sphere comes within the cut-off
+//                       of the ligand's: |q_t - c| <= rho + 8 + radius_t + slack, c the atom centroid, rho the ligand's
+//                       radius about it.  Every pair of a tile left out has r2 >= 64 and would add nothing, so the list
+//                       changes no bit of the result.
+// A molecule's outputs depend on its own atoms and the receptor arrays only: bit-identical whatever the batch, row or width.
+#include "mcg_common.h"
+#include "mcg_api_internal.h"
+#include "mcg_shape_grid.h"
+
+#include <math.h>
+
+#pragma clang fp contract(off)      // every product and sum rounded on its own: the compiler has no choice left
+
+namespace {
+
+using namespace mcg_shape;
+
+constexpr int IX_THREADS = 256;               // lanes per workgroup = receptor atoms per tile
+constexpr int IX_WAVES = IX_THREADS / 64;
+constexpr int IX_MAX_TILES = MCG_RECEPTOR_MAX_ATOMS / IX_THREADS;
+constexpr float IX_CUTOFF = 8.0f, IX_CUTOFF2 = 64.0f;
+// What the reach of the tile test adds to the exact bound: the centroid, rho and the test itself are rounded, all far
+// below 1e-3 of the lengths involved.
+constexpr float IX_SLACK_ABS = 0.05f, IX_SLACK_REL = 1e-3f;
+constexpr float W_G1 = -0.0356f, W_G2 = -0.00516f, W_REP = 0.840f, W_HYD = -0.0351f, W_HB = -0.587f, W_ROT = 0.0585f;
+constexpr float HB_FULL = -0.7f;              // a hydrogen bond counts in full at or below this surface distance
+constexpr unsigned T_DONOR = 1u, T_ACCEPTOR = 2u, T_HYDROPHOBIC = 4u;
+
+static_assert(MCG_RECEPTOR_MAX_ATOMS % IX_THREADS == 0, "the tile list holds every tile of the largest receptor");
+
+struct InteractionShared {
+    float4 tile[IX_THREADS];                  // the staged receptor tile: x, y, z, R_j
+    unsigned char type[IX_THREADS];
+    float part[IX_WAVES][MAX_ATOMS][5];       // per wave and atom: g1, g2, rep, hyd, hb
+    int hb_part[IX_WAVES][MAX_ATOMS];
+    float c[3];
+    float reach[IX_WAVES];                    // per wave: max |x_i - c|^2
+    int wave_tiles[IX_WAVES];
+    int n_tiles;
+    unsigned short list[IX_MAX_TILES];
+};
+
+// ((((w1 g1 + w2 g2) + w3 rep) + w4 hyd) + w5 hb): the weighted sum of five terms, in this order
+__device__ __forceinline__ float weighted(const float* t) {
+    return (((W_G1 * t[0] + W_G2 * t[1]) + W_REP * t[2]) + W_HYD * t[3]) + W_HB * t[4];
+}
+
+__global__ __launch_bounds__(IX_THREADS) void k_receptor_interactions(
+    const float* __restrict__ lig, const float* __restrict__ lig_r, const unsigned char* __restrict__ lig_t,
+    const int* __restrict__ n_nodes, const int* __restrict__ n_rot, int N, const float4* __restrict__ rec,
+    const unsigned char* __restrict__ rec_t, int R, const float4* __restrict__ tile_sphere,
+    float* __restrict__ atom_terms, float* __restrict__ mol_terms, int* __restrict__ hbonds) {
+    __shared__ InteractionShared s;
+    const int b = blockIdx.x, tid = threadIdx.x, a = tid & 63, w = tid >> 6;
+    const int na = atom_count(n_nodes[b], N);
+    float* at = atom_terms + (size_t)b * N * 6;
+    float* mt = mol_terms + (size_t)b * 8;
+    const bool real = a < na;
+    float x = 0.f, y = 0.f, z = 0.f, ri = 0.f;
+    unsigned ti = 0u;
+    if (real) {
+        const float* p = lig + ((size_t)b * N + a) * 3;
+        x = p[0]; y = p[1]; z = p[2];
+        ri = lig_r[(size_t)b * N + a];
+        ti = lig_t[(size_t)b * N + a];
+    }
+    const bool bad = real && !(isfinite(x) && isfinite(y) && isfinite(z));
+    if (__syncthreads_or(bad) != 0 || na == 0) {                   // NaN floats and -1, or - no atoms - zeros
+        const float v = na == 0 ? 0.f : __builtin_nanf("");
+        for (int q = tid; q < N * 6; q += IX_THREADS) at[q] = q < na * 6 ? v : 0.f;
+        if (tid < 8) mt[tid] = tid < 7 ? v : 0.f;
+        if (tid == 0) hbonds[b] = na == 0 ? 0 : -1;
+        return;
+    }
+    if (w == 0) s.part[0][a][0] = x, s.part[0][a][1] = y, s.part[0][a][2] = z;      // borrowed for the centroid
+    __syncthreads();
+    if (tid < 3) {                            // atom centroid, summed in atom order
+        float acc = 0.f;
+        for (int i = 0; i < na; ++i) acc += s.part[0][i][tid];
+        s.c[tid] = acc / (float)na;
+    }
+    __syncthreads();
+    const float c[3] = {s.c[0], s.c[1], s.c[2]};
+    float rho2 = 0.f;
+    if (real) {
+        const float ux = x - c[0], uy = y - c[1], uz = z - c[2];
+        rho2 = (ux * ux + uy * uy) + uz * uz;
+    }
+    for (int o = 32; o > 0; o >>= 1) rho2 = fmaxf(rho2, __shfl_xor(rho2, o, 64));     // a maximum: exact in any order
+    if (a == 0) s.reach[w] = rho2;
+    __syncthreads();
+    const int T = (R + IX_THREADS - 1) / IX_THREADS;
+    {
+        // the tiles within reach, in ascending order: a ballot per wave over 256 tiles a round, the waves' counts
+        // prefix-summed through LDS
+        const float rho = sqrtf(fmaxf(fmaxf(s.reach[0], s.reach[1]), fmaxf(s.reach[2], s.reach[3])));
+        const float reach0 = rho + IX_CUTOFF;
+        int base = 0;
+        for (int t0 = 0; t0 < T; t0 += IX_THREADS) {
+            const int t = t0 + tid;
+            bool keep = t < T;
+            if (keep && tile_sphere != nullptr) {
+                const float4 q = tile_sphere[t];
+                const float dx = q.x - c[0], dy = q.y - c[1], dz = q.z - c[2];
+                const float reach = reach0 + q.w;
+                const float lim = reach + (IX_SLACK_ABS + IX_SLACK_REL * reach);
+                keep = !(((dx * dx + dy * dy) + dz * dz) > lim * lim);          // a NaN sphere keeps its tile
+            }
+            const unsigned long long m = __ballot(keep);
+            if (a == 0) s.wave_tiles[w] = __popcll(m);
+            __syncthreads();
+            int before = base;
+            for (int v = 0; v < w; ++v) before += s.wave_tiles[v];
+            if (keep) s.list[before + __popcll(m & ((1ull << a) - 1ull))] = (unsigned short)t;
+            base += (s.wave_tiles[0] + s.wave_tiles[1]) + (s.wave_tiles[2] + s.wave_tiles[3]);
+            __syncthreads();
+        }
+        if (tid == 0) s.n_tiles = base;
+    }
+    __syncthreads();
+
+    float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    int nhb = 0;
+    const int nt = s.n_tiles;
+    for (int k = 0; k < nt; ++k) {
+        const int j0 = (int)s.list[k] * IX_THREADS;
+        const int cnt = min(IX_THREADS, R - j0);                   // the last tile's tail
+        if (tid < cnt) {
+            s.tile[tid] = rec[j0 + tid];
+            s.type[tid] = rec_t[j0 + tid];
+        }
+        __syncthreads();
+        for (int jj = w; jj < cnt; jj += IX_WAVES) {
+            const float4 q = s.tile[jj];
+            const float dx = x - q.x, dy = y - q.y, dz = z - q.z;
+            const float r2 = (dx * dx + dy * dy) + dz * dz;
+            const bool counts = real && r2 < IX_CUTOFF2;
+            if (__ballot(counts) == 0ull) continue;                // nobody in this wave: nothing is added
+            if (counts) {
+                const unsigned tj = s.type[jj];
+                const float d = sqrtf(r2) - (ri + q.w);
+                const float a1 = d + d;                            // d / 0.5
+                const float a2 = (d - 3.0f) * 0.5f;                // (d - 3) / 2
+                acc[0] += expf(-(a1 * a1));
+                acc[1] += expf(-(a2 * a2));
+                if (d < 0.f) acc[2] += d * d;
+                if ((ti & tj & T_HYDROPHOBIC) != 0u && d < 1.5f) acc[3] += d <= 0.5f ? 1.0f : 1.5f - d;
+                const bool pair_hb = ((ti & T_DONOR) != 0u && (tj & T_ACCEPTOR) != 0u) ||
+                                     ((ti & T_ACCEPTOR) != 0u && (tj & T_DONOR) != 0u);
+                if (pair_hb && d < 0.f) {
+                    const bool full = d <= HB_FULL;
+                    acc[4] += full ? 1.0f : d / HB_FULL;
+                    nhb += full ? 1 : 0;
+                }
+            }
+        }
+        __syncthreads();                      // the tile is free again
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) s.part[w][a][k] = acc[k];
+    s.hb_part[w][a] = nhb;
+    __syncthreads();
+    if (w != 0) return;
+    float t[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) t[k] = (s.part[0][a][k] + s.part[1][a][k]) + (s.part[2][a][k] + s.part[3][a][k]);
+    int hb = (s.hb_part[0][a] + s.hb_part[1][a]) + (s.hb_part[2][a] + s.hb_part[3][a]);
+    if (a < N) {                              // a padded atom's terms are 0: its lanes added nothing
+#pragma unroll
+        for (int k = 0; k < 5; ++k) at[a * 6 + k] = t[k];
+        at[a * 6 + 5] = real ? weighted(t) : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+        for (int o = 32; o > 0; o >>= 1) t[k] += __shfl_xor(t[k], o, 64);
+    for (int o = 32; o > 0; o >>= 1) hb += __shfl_xor(hb, o, 64);
+    if (a == 0) {
+        const float sum = weighted(t);
+        const float den = 1.0f + W_ROT * (float)max(n_rot[b], 0);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) mt[k] = t[k];
+        mt[5] = sum;
+        mt[6] = sum / den;
+        mt[7] = 0.f;
+        hbonds[b] = hb;
+    }
+}
+
+}  // namespace
+
+extern "C" int mcg_receptor_interactions(const float* lig_xyz, const float* lig_radius, const uint8_t* lig_type,
+                                         const int32_t* n_nodes_dev, const int32_t* n_rot_dev, int B, int N,
+                                         const float* rec_xyzr, const uint8_t* rec_type, int R, const float* tile_sphere,
+                                         float* atom_terms, float* mol_terms, int32_t* hbonds, void* stream) {
+    static_assert(MAX_ATOMS == 64, "the bound the message below states");
+    if (!lig_xyz || !lig_radius || !lig_type || !n_nodes_dev || !n_rot_dev || !rec_xyzr || !rec_type || !atom_terms ||
+        !mol_terms || !hbonds || B < 1 || B > MCG_RECEPTOR_MAX_B || N < 1 || N > MAX_ATOMS || R < 1 ||
+        R > MCG_RECEPTOR_MAX_ATOMS) {
+        mcg_set_error("mcg_receptor_interactions: bad arguments (non-null buffers, 1 <= B <= %d, 1 <= N <= 64, "
+                      "1 <= R <= %d)", MCG_RECEPTOR_MAX_B, MCG_RECEPTOR_MAX_ATOMS);
+        return MCG_ERR_ARG;
+    }
+    hipLaunchKernelGGL(k_receptor_interactions, dim3(B), dim3(IX_THREADS), 0, (hipStream_t)stream, lig_xyz, lig_radius,
+                       lig_type, n_nodes_dev, n_rot_dev, N, (const float4*)rec_xyzr, rec_type, R,
+                       (const float4*)tile_sphere, atom_terms, mol_terms, hbonds);
+    MCG_HIP(hipGetLastError());
+    return MCG_OK;
+}

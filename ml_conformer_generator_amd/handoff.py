@@ -70,6 +70,10 @@ class Measured:
     substructure_status: Optional[object] = None  # List[int] (`substructure.describe_status`) - likewise
     substructure_first: Optional[object] = None   # per pattern the first embedding or None - or (batch [B,P,M], row), likewise
     substructure_patterns: Optional[tuple] = None     # the call's `substructure.Pattern`s: require, exclude, counts, in order
+    interaction_score: Optional[float] = None     # E of `interactions.py`; negative is better
+    interaction_terms: Optional[dict] = None      # g1, g2, rep, hyd, hb (the five sums) and n_rot
+    receptor_hbonds: Optional[int] = None
+    interaction_atom_scores: Optional[object] = None  # [n] fp32, host - or (batch [B,W], row, n), sliced on first read
 
 
 _UNMEASURED = Measured()          # shared by every record that carries no values: never written to
@@ -97,10 +101,15 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
     The matches of a call with a substructure option come as `substructure_counts` [n,P], `substructure_status` [n,P],
     `substructure_first` [n,P,M] int32 (the caller's pattern atom order, -1 beyond a pattern's atoms) and
     `substructure_patterns`, the tuple of the P patterns, which every record shares (all four or none); a record's three
-    fields are left as (the one host copy, row) and sliced on first read (`substructure_row`)."""
+    fields are left as (the one host copy, row) and sliced on first read (`substructure_row`).
+    The interactions of a call with `interaction_scores` come as `interaction_score` [n] fp32, `interaction_terms` [n,6]
+    fp32 (G1, G2, REP, HYD, HB, n_rot), `receptor_hbonds` [n] (negative: posing failed - the record gets None for all four)
+    and `interaction_atom_scores` [n,W] fp32, +inf at and beyond a row's atoms (all four or none); a record's
+    `interaction_atom_scores` is left as (the one host copy, row, atom count) and sliced on first read."""
     hyd = {k: values.get(k) for k in ("hydrogen_coords", "hydrogen_parents", "atom_map", "kekule_bond_orders",
                                       "partial_charges", "hydrogen_charges", "canonical_order", "substructure_counts",
-                                      "substructure_status", "substructure_first", "substructure_patterns")}
+                                      "substructure_status", "substructure_first", "substructure_patterns",
+                                      "interaction_atom_scores")}
     cols = {k: v.cpu().tolist() for k, v in values.items() if v is not None and k != "pose" and k not in hyd}
     if values.get("pose") is not None:
         poses = values["pose"].cpu().to(torch.float32)
@@ -149,6 +158,16 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
             host = hyd[k].cpu().to(torch.int32)
             cols[k] = [(host, b) for b in range(n)]
         cols["substructure_patterns"] = [tuple(hyd["substructure_patterns"])] * n
+    if "receptor_hbonds" in cols:
+        missing = [c < 0 for c in cols["receptor_hbonds"]]
+        names = ("g1", "g2", "rep", "hyd", "hb")
+        cols["interaction_terms"] = [None if gone else dict(zip(names, row[:5]), n_rot=int(row[5]))
+                                     for gone, row in zip(missing, cols["interaction_terms"])]
+        per_atom = hyd["interaction_atom_scores"].cpu().to(torch.float32)
+        counts = (~torch.isinf(per_atom)).sum(dim=1).tolist()
+        cols["interaction_atom_scores"] = [(per_atom, b, k) for b, k in enumerate(counts)]
+        for k in ("interaction_score", "interaction_terms", "receptor_hbonds", "interaction_atom_scores"):
+            cols[k] = [None if gone else v for gone, v in zip(missing, cols[k])]
     return [Measured(**{k: col[b] for k, col in cols.items()}) for b in range(n)]
 
 
@@ -200,6 +219,10 @@ class GeneratedMolecule:
     `canonical_order` / `canonical_status` / `smiles`: its exact canonical atom order and canonical SMILES when the call
     asked for `smiles` (`canonical.py`, `smiles.py`: the package's own definition - valid OpenSMILES, NOT RDKit's canonical
     SMILES), else None; `to_smiles()` writes the string, `to_smiles(canonical=False)` one in the record's own atom order.
+    `interaction_score` / `interaction_terms` / `receptor_hbonds` / `interaction_atom_scores`: its empirical interaction
+    score with the call's typed receptor, the sums behind it, its hydrogen-bond count and per-atom contributions when the
+    call asked for `interaction_scores` (`interactions.py`: the package's own definition, NOT AutoDock Vina's output), else
+    None.
     `substructure_patterns` / `substructure_counts` / `substructure_status` / `substructure_first`: the patterns the call
     matched (`require_substructures`, `exclude_substructures`, `substructure_counts`, in that order) and, per pattern, how
     many embeddings this molecule has, how the search ended and the first embedding (`substructure.py`: the package's own
@@ -222,6 +245,37 @@ class GeneratedMolecule:
         m._measured = measured
         m._smiles = None
         return m
+
+    @property
+    def interaction_score(self) -> Optional[float]:
+        """The empirical interaction score E of this molecule's returned coordinates with the call's typed receptor
+        (`interactions.py`: the package's own definition - the functional form of the AutoDock Vina scoring function on
+        the package's heavy-atom types, intermolecular terms only; NOT AutoDock Vina's output, not a binding free energy);
+        negative is better.  When the call asked for `interaction_scores` or `max_interaction_score`; None otherwise and
+        where posing failed."""
+        return self._measured.interaction_score
+
+    @property
+    def interaction_terms(self) -> Optional[dict]:
+        """The five sums behind `interaction_score` over the counted atom pairs - "g1", "g2", "rep", "hyd", "hb" - and
+        "n_rot", the rotatable bonds of its divisor; None where `interaction_score` is None."""
+        return self._measured.interaction_terms
+
+    @property
+    def receptor_hbonds(self) -> Optional[int]:
+        """The donor / acceptor pairs of this molecule and the receptor at hydrogen-bond distance (surface distance <=
+        -0.7 A; heavy atoms only, no angle: `interactions.py`); None where `interaction_score` is None."""
+        return self._measured.receptor_hbonds
+
+    @property
+    def interaction_atom_scores(self) -> Optional[torch.Tensor]:
+        """[n] fp32 (CPU): each atom's weighted contribution to the interaction score before the division by the
+        rotatable-bond term (a view into the batch's host tensor, sliced on first access); None where
+        `interaction_score` is None."""
+        v = self._measured.interaction_atom_scores
+        if isinstance(v, tuple):
+            v = self._measured.interaction_atom_scores = v[0][v[1], : v[2]]
+        return v
 
     @property
     def substructure_patterns(self) -> Optional[tuple]:
@@ -736,7 +790,11 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                            substructure_counts: Optional[torch.Tensor] = None,
                            substructure_status: Optional[torch.Tensor] = None,
                            substructure_first: Optional[torch.Tensor] = None,
-                           substructure_patterns: Optional[tuple] = None) -> List[GeneratedMolecule]:
+                           substructure_patterns: Optional[tuple] = None,
+                           interaction_score: Optional[torch.Tensor] = None,
+                           interaction_terms: Optional[torch.Tensor] = None,
+                           receptor_hbonds: Optional[torch.Tensor] = None,
+                           interaction_atom_scores: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
     (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
     (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records).
@@ -765,6 +823,9 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     canonical labelling as `canonical.canonical_order` returns it (both or neither; None: a call without `smiles`).
     `substructure_counts[b]` [P] / `substructure_status[b]` [P] / `substructure_first[b]` [P,M] with the P patterns
     `substructure_patterns`: row b's matches as `substructure.match_substructures` returns them (all four or none).
+    `interaction_score[b]` / `interaction_terms[b]` [6] / `receptor_hbonds[b]` / `interaction_atom_scores[b]` [W] (+inf at
+    and beyond the row's atoms): row b's receptor interactions as `postprocess.interactions` spells them (all four or
+    none; negative hbonds: its pose failed, the record gets None for all four; None: a call without `interaction_scores`).
     The value keywords are the fields of `Measured`
     and go to `measured_from_tensors`; a call with no ids and no values builds the views and nothing else."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
@@ -782,7 +843,9 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                   partial_charges=partial_charges, hydrogen_charges=hydrogen_charges,
                   canonical_order=canonical_order, canonical_status=canonical_status,
                   substructure_counts=substructure_counts, substructure_status=substructure_status,
-                  substructure_first=substructure_first, substructure_patterns=substructure_patterns)
+                  substructure_first=substructure_first, substructure_patterns=substructure_patterns,
+                  interaction_score=interaction_score, interaction_terms=interaction_terms,
+                  receptor_hbonds=receptor_hbonds, interaction_atom_scores=interaction_atom_scores)
     if sample_ids is None and all(v is None for v in values.values()):
         return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
     flags = valid.cpu().tolist()

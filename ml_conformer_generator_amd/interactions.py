@@ -1,0 +1,246 @@
+"""Receptor interactions of posed molecules, on the GPU ("Receptor interactions"): does a posed
+molecule interact with the pocket - hydrogen bonds to its donors and acceptors, contact with its hydrophobic wall - or does
+it merely not bump into it (`receptor.py`)?
+
+THE PACKAGE'S OWN, LABELLED DEFINITION.  It has the functional form of the AutoDock Vina scoring function (O. Trott, A. J.
+Olson, J. Comput. Chem. 31, 455 (2010)), on the package's own atom typing, on heavy atoms only, with the intermolecular
+terms only.  It is NOT AutoDock Vina's output and NOT a binding free energy: there is no search, no intramolecular term and
+no hydrogen on either side; no agreement with any docking program is claimed.
+
+Pair geometry   ligand atom i at x_i with interaction radius R_i, receptor atom j at y_j with R_j:
+                r2 = dx*dx + dy*dy + dz*dz in fp32, unfused, in exactly this order (as `k_receptor_overlap` does); the pair
+                COUNTS iff r2 < 64.0f - an 8 A cut-off decided in fp32; a pair that does not count contributes exactly +0
+                to everything.  For a counted pair d = sqrtf(r2) - (R_i + R_j): the square root correctly rounded, the
+                radius sum rounded first.
+Radii           the form's own (`INTERACTION_RADII`, angstrom, keyed by Z), not `receptor.VDW_RADII`: C 1.9, N 1.8, O 1.7,
+                F 1.5, P 2.1, S 2.0, Cl 1.8, Br 2.0, I 2.2, Si 2.2; the metals Mg, Ca, Mn, Fe, Co, Ni, Cu, Zn 1.2; any other
+                element its `receptor.VDW_RADII` value (else `receptor.DEFAULT_RADIUS`).
+Terms           of a counted pair, the piecewise ones evaluated from the fp32 d:
+                g1 = exp(-(d / 0.5)^2);  g2 = exp(-((d - 3) / 2)^2);  rep = d*d if d < 0, else 0;
+                hyd, only if both atoms are hydrophobic: 1 for d <= 0.5, 0 for d >= 1.5, linear between;
+                hb, only if one atom is a donor and the other an acceptor, in either direction: 1 for d <= -0.7, 0 for
+                d >= 0, linear between.
+Score           per molecule E = (-0.0356 G1 - 0.00516 G2 + 0.840 REP - 0.0351 HYD - 0.587 HB) / (1 + 0.0585 n_rot), G1 ...
+                HB the sums over the counted pairs, the weights constants of this definition; negative is better.
+                `receptor_hbonds`: the counted donor / acceptor pairs with d <= -0.7f, an exact integer.  Per atom the
+                same five sums over j alone and the atom's weighted, unnormalised contribution.
+Ligand types    per-atom bits perceived from the returned graph alone (with `standardize`: the parent fragment's): donor
+                (1) and acceptor (2) are `pharmacophore.perceive_features`' bits, unchanged; hydrophobic (4) is a C,
+                aromatic or not, with no N or O neighbour, and F, Cl, Br, I.  This is WIDER than the pharmacophore's
+                hydrophobe (a non-aromatic C all of whose neighbours are C; Cl, Br, I) on purpose: the term is a contact
+                term over every apolar carbon, aromatic ones included, as in the form it follows.
+Rotatable bonds n_rot = the code-1 chain bonds whose two ends both have heavy-atom degree >= 2 - one
+                `substructure.match_substructures` call with `ROTATABLE_BOND`, count // 2.  THE PACKAGE'S RULE: amide and
+                other conjugated single bonds are counted.
+Receptor types  `receptor.load_typed_receptor` (a residue-template table for a PDB string, the element rules otherwise).
+A molecule without atoms scores zeros, E = 0; one with a non-finite coordinate on a real atom NaN, hbonds = -1, the other
+rows unaffected.  A molecule's outputs depend on its own atoms and the receptor's atoms only: the same bits in any batch, at
+any row, at any padded width, with and without tile skipping, and whatever the order the receptor's atoms were listed in.
+"""
+from __future__ import annotations
+
+import math
+import numbers
+from typing import Dict, NamedTuple, Optional
+
+import torch
+
+from . import _lib
+from . import pharmacophore as mcg_pharm
+from . import receptor as mcg_receptor
+from . import substructure as mcg_sub
+
+CUTOFF = 8.0                    # angstrom; decided as r2 < 64.0f
+WEIGHTS = dict(g1=-0.0356, g2=-0.00516, rep=0.840, hyd=-0.0351, hb=-0.587)
+ROTOR_WEIGHT = 0.0585
+TERM_NAMES = ("g1", "g2", "rep", "hyd", "hb")
+HBOND_DISTANCE = -0.7           # angstrom of surface distance: a hydrogen bond counts in full at or below it
+MAX_ATOMS = 64
+MAX_BATCH = mcg_receptor.MAX_BATCH
+TYPE_DONOR, TYPE_ACCEPTOR, TYPE_HYDROPHOBIC = (mcg_receptor.TYPE_DONOR, mcg_receptor.TYPE_ACCEPTOR,
+                                               mcg_receptor.TYPE_HYDROPHOBIC)
+INTERACTION_RADII = {6: 1.9, 7: 1.8, 8: 1.7, 9: 1.5, 15: 2.1, 16: 2.0, 17: 1.8, 35: 2.0, 53: 2.2, 14: 2.2,
+                     **{z: 1.2 for z in mcg_receptor.METALS}}
+REFUSAL_WITH_FINISHER = ("interaction_scores, max_interaction_score and rank_by='interaction' cannot be combined with a "
+                         "finisher (RDKit's or a custom one): the values go onto the GeneratedMolecule records")
+ROTATABLE_BOND = mcg_sub.Pattern((mcg_sub.atom(degree=(2, 8)), mcg_sub.atom(degree=(2, 8))),
+                                 (mcg_sub.bond(0, 1, codes=(1,), ring=False),), name="rotatable bond")
+
+_RADIUS_TABLE = torch.tensor([INTERACTION_RADII.get(z, mcg_receptor.VDW_RADII.get(z, mcg_receptor.DEFAULT_RADIUS))
+                              for z in range(len(mcg_receptor._SYMBOLS) + 1)], dtype=torch.float32)
+
+
+def interaction_radius(z: int) -> float:
+    """The interaction radius (angstrom) of atomic number `z`: `INTERACTION_RADII`, else `receptor.vdw_radius`."""
+    return INTERACTION_RADII.get(int(z), mcg_receptor.vdw_radius(z))
+
+
+def interaction_radii(atomic_numbers: torch.Tensor) -> torch.Tensor:
+    """fp32 interaction radii of a tensor of atomic numbers (same shape, on its device); Z outside 1..118 gets
+    `receptor.DEFAULT_RADIUS`."""
+    z = torch.as_tensor(atomic_numbers).to(torch.long)
+    z = torch.where((z >= 1) & (z < _RADIUS_TABLE.numel()), z, torch.zeros_like(z))
+    return _RADIUS_TABLE.to(z.device)[z]
+
+
+class PreparedReceptor(NamedTuple):
+    """A typed receptor as the kernel reads it, on the host (`prepare_receptor`)."""
+    xyzr: torch.Tensor            # [R,4] fp32: x, y, z, interaction radius, in `receptor.sort_typed_receptor`'s order
+    types: torch.Tensor           # [R] uint8
+    spheres: torch.Tensor         # [ceil(R / 256), 4] fp32: `receptor.tile_spheres`
+
+
+def prepare_receptor(receptor) -> PreparedReceptor:
+    """`receptor` - what `receptor.load_typed_receptor` takes, or a `PreparedReceptor`, returned as it is - loaded, typed,
+    given its interaction radii and sorted (`receptor.sort_typed_receptor`), with the bounding spheres of its tiles: host
+    work, once per receptor."""
+    if isinstance(receptor, PreparedReceptor):
+        return receptor
+    xyz, z, types = mcg_receptor.load_typed_receptor(receptor)
+    xyzr, types = mcg_receptor.sort_typed_receptor(xyz, interaction_radii(z), types)
+    return PreparedReceptor(xyzr, types, mcg_receptor.tile_spheres(xyzr))
+
+
+# ----------------------------------------------------------------------------------------------- device
+@torch.no_grad()
+def ligand_types(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor, device=None,
+                 perceived=None) -> torch.Tensor:
+    """Interaction types [B,W] uint8 on the device of B molecular graphs (bits TYPE_DONOR, TYPE_ACCEPTOR,
+    TYPE_HYDROPHOBIC; 0 at and beyond a molecule's atoms): `atomic_numbers` [B, >= W], `bond_orders` [B,W,W], `n_nodes`
+    [B].  One `pharmacophore.perceive_features` launch (`perceived`: its result for the same graphs, when the caller has
+    it) for the donor and acceptor bits, and a few tensor operations behind it for the hydrophobic bit - a C without an N
+    or O neighbour, F, Cl, Br, I.  Exact.  ValueError: what `perceive_features` refuses."""
+    types = (perceived if perceived is not None else
+             mcg_pharm.perceive_features(atomic_numbers, bond_orders, n_nodes, device))[0]
+    dev = types.device
+    B, W = int(types.shape[0]), int(types.shape[1])
+    bonds = torch.as_tensor(bond_orders)
+    if bonds.shape[1] == 0:                     # `perceive_features` ran at its smallest width: no atoms anywhere
+        return torch.zeros(B, W, dtype=torch.uint8, device=dev)
+    z = torch.as_tensor(atomic_numbers)[:, :W].to(dev, torch.long)
+    bonds = bonds.to(dev)
+    real = torch.arange(W, device=dev).view(1, -1) < torch.as_tensor(n_nodes).to(dev).reshape(-1, 1)
+    bonded = (bonds >= 1) & (bonds <= 4) & real[:, :, None] & real[:, None, :] & ~torch.eye(W, dtype=torch.bool, device=dev)
+    polar = (z == 7) | (z == 8)
+    hydrophobic = (z == 6) & ~(bonded & polar[:, None, :]).any(dim=2)
+    for h in mcg_receptor.HALOGENS:
+        hydrophobic |= z == h
+    out = (types & (TYPE_DONOR | TYPE_ACCEPTOR)) | (hydrophobic.to(torch.uint8) * TYPE_HYDROPHOBIC)
+    return torch.where(real, out, torch.zeros_like(out))
+
+
+@torch.no_grad()
+def rotatable_bonds(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor, device=None,
+                    check: bool = True) -> torch.Tensor:
+    """n_rot [B] int32 on the device: the code-1 chain bonds of each graph whose two ends both have heavy-atom degree >= 2
+    (THE PACKAGE'S RULE: amide and other conjugated single bonds are counted), by one `substructure.match_substructures`
+    call with `ROTATABLE_BOND`; each bond is embedded twice, so the number is count // 2.  ValueError: what that call
+    refuses."""
+    out = mcg_sub.match_substructures(atomic_numbers, bond_orders, n_nodes, [ROTATABLE_BOND], hydrogens=False,
+                                      device=device, check=check)
+    return (out["count"][:, 0] // 2).to(torch.int32)
+
+
+@torch.no_grad()
+def score_typed(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, radii: torch.Tensor, types: torch.Tensor,
+                n_rot: torch.Tensor, skip_tiles: bool = True, device=None) -> Dict[str, torch.Tensor]:
+    """The `mcg_receptor_interactions` launch itself, on ligand atoms that are already typed: `coords` [B,N,3], `n_nodes`
+    [B], `radii` [B,N] fp32 interaction radii, `types` [B,N] uint8 type bits, `n_rot` [B] rotatable bonds; `receptor` as
+    in `interaction_scores`.  Device tensors: atom_terms [B,N,6], mol_terms [B,8], hbonds [B] as the kernel writes them
+    (include/mlconfgen_hip.h).  B or N of 0 launches nothing and returns zeros."""
+    from .cheminformatics import check_n_nodes
+    prepared = prepare_receptor(receptor)
+    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
+    B, N = int(coords.shape[0]), int(coords.shape[1])
+    check_n_nodes(n_nodes, B, N)
+    if N > MAX_ATOMS or B > MAX_BATCH:
+        raise ValueError(f"interaction scores take at most {MAX_BATCH} molecules of at most {MAX_ATOMS} atoms, got "
+                         f"[{B}, {N}]")
+    for name, t, shape in (("radii", radii, (B, N)), ("types", types, (B, N)), ("n_rot", n_rot, (B,))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+    atoms = torch.zeros(B, N, 6, device=dev)
+    mol = torch.zeros(B, 8, device=dev)
+    hbonds = torch.zeros(B, dtype=torch.int32, device=dev)
+    if B > 0 and N > 0:
+        x = coords.to(dev, torch.float32).contiguous()
+        lig_r = radii.to(dev, torch.float32).contiguous()
+        lig_t = types.to(dev, torch.uint8).contiguous()
+        nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B).contiguous()
+        rot = n_rot.to(dev, torch.int32).contiguous()
+        rec, rec_t = prepared.xyzr.to(dev), prepared.types.to(dev)
+        spheres = prepared.spheres.to(dev) if skip_tiles else None
+        _lib.check(_lib.lib().mcg_receptor_interactions(
+            _lib.dptr(x), _lib.dptr(lig_r), _lib.dptr(lig_t), _lib.dptr(nn), _lib.dptr(rot), B, N, _lib.dptr(rec),
+            _lib.dptr(rec_t), int(rec.shape[0]), _lib.dptr(spheres), _lib.dptr(atoms), _lib.dptr(mol), _lib.dptr(hbonds),
+            _lib.current_stream_ptr(dev)), "mcg_receptor_interactions")
+    return dict(atom_terms=atoms, mol_terms=mol, hbonds=hbonds)
+
+
+@torch.no_grad()
+def interaction_scores(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_numbers: torch.Tensor,
+                       bond_orders: torch.Tensor, skip_tiles: bool = True, device=None, check: bool = True
+                       ) -> Dict[str, torch.Tensor]:
+    """The interaction score of every molecule of the padded, posed coordinates `coords` [B,N,3] (`n_nodes` [B] real
+    atoms, `atomic_numbers` [B, >= N], `bond_orders` [B,N,N]) with `receptor` - what `receptor.load_typed_receptor` takes,
+    or a `prepare_receptor` result - by this module's definition: one perceive launch (`ligand_types`), one substructure
+    launch (`rotatable_bonds`) and one `mcg_receptor_interactions` launch (`score_typed`).  Device tensors:
+      score [B]           fp32: E
+      terms [B,6]         fp32: G1, G2, REP, HYD, HB and the weighted sum before the n_rot division
+      hbonds [B]          int32: `receptor_hbonds`
+      atom_scores [B,N]   fp32: each atom's weighted, unnormalised contribution (0 on padded atoms)
+      atom_terms [B,N,5]  fp32: each atom's five sums
+      n_rot [B]           int32
+      types [B,N]         uint8: the ligand types
+    A molecule with no atoms: zeros; one with a non-finite coordinate on a real atom: NaN, hbonds = -1; the other rows
+    unaffected.  `skip_tiles`: whether a molecule's workgroup walks only the receptor tiles within the cut-off of it; never
+    a bit of the result.  Refused before any device work: what `load_typed_receptor` refuses, atom counts outside [0, N],
+    N > 64, B > MAX_BATCH, shapes that do not fit."""
+    from .cheminformatics import check_n_nodes
+    prepared = prepare_receptor(receptor)
+    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
+    B, N = int(coords.shape[0]), int(coords.shape[1])
+    check_n_nodes(n_nodes, B, N)
+    if N > MAX_ATOMS or B > MAX_BATCH:
+        raise ValueError(f"interaction scores take at most {MAX_BATCH} molecules of at most {MAX_ATOMS} atoms, got "
+                         f"[{B}, {N}]")
+    z = torch.as_tensor(atomic_numbers)
+    bonds = torch.as_tensor(bond_orders)
+    if z.dim() != 2 or z.shape[0] != B or z.shape[1] < N:
+        raise ValueError(f"atomic_numbers must be [B, >= N] = [{B}, >= {N}], got {list(z.shape)}")
+    if bonds.dim() != 3 or bonds.shape[0] != B or bonds.shape[1] != bonds.shape[2] or bonds.shape[1] < N:
+        raise ValueError(f"bond_orders must be [B, >= N, >= N] = [{B}, >= {N}, >= {N}], got {list(bonds.shape)}")
+    n_rot = torch.zeros(B, dtype=torch.int32, device=dev)
+    types = torch.zeros(B, N, dtype=torch.uint8, device=dev)
+    if B > 0 and N > 0:
+        bonds = bonds[:, :N, :N]
+        types = ligand_types(z[:, :N], bonds, n_nodes, dev)
+        n_rot = rotatable_bonds(z[:, :N], bonds, n_nodes, dev, check=check)
+    out = score_typed(prepared, coords, n_nodes, interaction_radii(z[:, :N].to(dev)), types, n_rot, skip_tiles, dev)
+    atoms, mol, hbonds = out["atom_terms"], out["mol_terms"], out["hbonds"]
+    return dict(score=mol[:, 6], terms=mol[:, :6], hbonds=hbonds, atom_scores=atoms[:, :, 5], atom_terms=atoms[:, :, :5],
+                n_rot=n_rot, types=types)
+
+
+# ----------------------------------------------------------------------------------------------- options
+def check_threshold(name: str, value) -> float:
+    """An interaction-score threshold (`max_interaction_score`) as a float: a finite real number (not a bool), else
+    ValueError."""
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not math.isfinite(float(value)):
+        raise ValueError(f"{name} must be a finite real number, got {value!r}")
+    return float(value)
+
+
+def check_rank_by(value) -> str:
+    """`rank_by` as "shape", "combo", "electrostatic" or "interaction", else ValueError."""
+    if value not in ("shape", "combo", "electrostatic", "interaction"):
+        raise ValueError(f"rank_by must be 'shape', 'combo', 'electrostatic' or 'interaction', got {value!r}")
+    return value
+
+
+def select_score(interaction: Optional[float]) -> float:
+    """The ranking value of `rank_by="interaction"`: -E, so that the best - most negative - score ranks first; NaN where
+    the score is NaN or missing (such a molecule ranks last)."""
+    if interaction is None:
+        return math.nan
+    return -interaction

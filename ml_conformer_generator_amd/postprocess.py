@@ -23,13 +23,16 @@ Stages, in this order:
        `unique="exact"`, `exclude_graphs`): one `_canonical_order` launch over the rows - the excluded graphs were
        labelled by the same seam directly in front of the generation (`label_excluded`); and the substructure step
        (`substructures`; `require_substructures`, `exclude_substructures`, `substructure_counts`): one
-       `_match_substructures` call over the rows, every pattern of the three lists in it;
+       `_match_substructures` call over the rows, every pattern of the three lists in it; and the interaction step
+       (`interactions`; `interaction_scores`, `max_interaction_score`, `rank_by="interaction"`; records only): one
+       `_interaction_scores` call over the rows, on the returned coordinates and graphs, against the typed receptor the
+       request carries - loaded, typed and sorted once, in `parse_request`, uploaded once, in that call;
     5. the values are attached - each molecule's `handoff.Measured`, behind a record's properties or written onto the
        Mol by `rdkit_finish.tag_measured` (Mols lose their properties in the object gather) - and validity is taken
        (`last_valid_fraction`);
     6. `select`, written once for both paths: `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`,
-       `min_pharmacophore_tanimoto`, `min_electrostatic_tanimoto`, `require_substructures`, `exclude_substructures`,
-       `exclude_graphs`, `unique`, then the threshold / sphere exclusion / `top_k` walk of `cheminformatics.select_diverse`.  The two pair matrices are
+       `min_pharmacophore_tanimoto`, `min_electrostatic_tanimoto`, `max_interaction_score`, `require_substructures`,
+       `exclude_substructures`, `exclude_graphs`, `unique`, then the threshold / sphere exclusion / `top_k` walk of `cheminformatics.select_diverse`.  The two pair matrices are
        computed only when their threshold is set, over the rows that survived the filters.
 A call with no option on takes none of these steps: its records / live Mols are returned as they come.
 `standardize` is not a stage here: the generator standardises right behind the bond write-back, so the result tensors
@@ -38,7 +41,7 @@ that arrive are already the parent fragments'; its four per-sample tensors (`ato
 
 The device work goes through the generator's seams (`_pose`, `_score`, `_pair`, `_receptor_coords`,
 `_relieve`, `_score_placed`, `_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, `_pharm_perceive`, `_pharm_score`,
-`_add_hydrogens`, `_peoe_charges`, `_esp_score`, `_canonical_order`, `_match_substructures`),
+`_add_hydrogens`, `_peoe_charges`, `_esp_score`, `_canonical_order`, `_match_substructures`, `_interaction_scores`),
 looked up on the instance at the time of the call.  The shape
 seams take the request's reference object; which kind it is - a conformer or a solid - is `cheminformatics`' business."""
 from __future__ import annotations
@@ -58,6 +61,7 @@ from . import fingerprint as mcg_fp
 from . import geometry as mcg_geometry
 from . import host_pool
 from . import hydrogens as mcg_hydrogens
+from . import interactions as mcg_interactions
 from . import pharmacophore as mcg_pharm
 from . import receptor as mcg_receptor
 from . import standardize as mcg_standardize
@@ -91,7 +95,7 @@ class Request:
     ref_pharm_graph: Optional[tuple] = None       # else (atomic numbers, bond codes [n,n] int8, coords [n,3]) to perceive
     min_pharmacophore_tanimoto: Optional[float] = None
     rank_by: str = "shape"                        # "combo": rank by shape + pharmacophore Tanimoto; "electrostatic": shape
-    #                                               + electrostatic Tanimoto
+    #                                               + electrostatic Tanimoto; "interaction": minus the interaction score
     add_hydrogens: bool = False                   # `add_hydrogens`: explicit hydrogens on the returned records
     standardize: bool = False                     # `standardize`: largest fragment + Kekule form, behind the bond write-back
     scores_electrostatics: bool = False           # `electrostatic_scores`, or implied by `min_electrostatic_tanimoto`
@@ -107,6 +111,9 @@ class Request:
     #                                               `exclude_substructures`, then `substructure_counts`, compiled together
     n_required: int = 0                           # how many of them must be proven present,
     n_excluded: int = 0                           # and how many, behind those, drop a row where proven present
+    scores_interactions: bool = False             # `interaction_scores`, or implied by `max_interaction_score`
+    typed_receptor: Optional[tuple] = None        # `interactions.PreparedReceptor`: typed, sorted, with tile spheres, host
+    max_interaction_score: Optional[float] = None
 
     @property
     def selects_by_shape(self) -> bool:
@@ -141,7 +148,8 @@ class Request:
         return (self.max_receptor_clashes is not None or self.max_chemical_tanimoto is not None or bool(self.unique)
                 or self.excluded_graphs is not None or self.selects_by_shape or self.max_pairwise_chemical_tanimoto is not None
                 or self.max_atoms_outside is not None or self.min_pharmacophore_tanimoto is not None
-                or self.min_electrostatic_tanimoto is not None or self.n_required > 0 or self.n_excluded > 0)
+                or self.min_electrostatic_tanimoto is not None or self.n_required > 0 or self.n_excluded > 0
+                or self.max_interaction_score is not None)
 
     @property
     def needs_charges(self) -> bool:
@@ -150,7 +158,10 @@ class Request:
     def ranking_score(self, measured: Measured) -> Optional[float]:
         """What `unique`, the diversity walk and `top_k` rank a molecule by: its shape score, or - `rank_by="combo"` - shape
         + pharmacophore Tanimoto (`pharmacophore.select_score`: NaN, which ranks last, where either is missing) or -
-        `rank_by="electrostatic"` - shape + electrostatic Tanimoto (`electrostatics.select_score`, likewise)."""
+        `rank_by="electrostatic"` - shape + electrostatic Tanimoto (`electrostatics.select_score`, likewise) or -
+        `rank_by="interaction"` - minus the interaction score (`interactions.select_score`: NaN where it is missing)."""
+        if self.rank_by == "interaction":
+            return mcg_interactions.select_score(measured.interaction_score)
         if self.rank_by == "combo":
             return mcg_pharm.select_score(measured.shape_tanimoto, measured.pharmacophore_tanimoto)
         if self.rank_by == "electrostatic":
@@ -171,7 +182,8 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
                   standardize=False, electrostatic_scores=False, reference_charges=None,
                   min_electrostatic_tanimoto: Optional[float] = None, partial_charges=False, smiles=False,
                   exclude_graphs=None, require_substructures=None, exclude_substructures=None,
-                  substructure_counts=None) -> Request:
+                  substructure_counts=None, interaction_scores=False,
+                  max_interaction_score: Optional[float] = None) -> Request:
     """The public option keywords of a generation entry of `gen` as a `Request`: the shape options first, then the chemical
     ones (`top_k` / `min_shape_tanimoto` / `max_pairwise_tanimoto` imply the shape score, `max_chemical_tanimoto` the
     chemical one).  `reference_shape`: a watertight mesh in place of the reference conformer (`mesh.load_mesh`); the
@@ -201,6 +213,10 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     (`substructure.parse`), `substructure.Pattern`s or graph sources (`substructure.from_graph`); they are compiled here,
     together (`compile_substructures`: host work), and an entry that cannot be read or breaks a limit is a ValueError
     naming its list and position; refused with a custom finisher, through RDKit's the Mols' own graphs are read.
+    `interaction_scores` (implied by `max_interaction_score`, a finite real number) needs a `receptor` - and with it
+    `overlay` -, which is typed, sorted and given its tile spheres here (`interactions.prepare_receptor`: host work, one
+    warning where atoms lie outside the residue templates); a (coords, atomic_numbers, types) triple carries its own
+    types.  `rank_by="interaction"` needs the score.  Refused with a finisher: the values go onto the records.
     Every refusal happens here, before any device work."""
     mcg_pharm.check_flag("smiles", smiles)
     if smiles and getattr(gen, "finisher", None) is not None:
@@ -223,6 +239,18 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     if esp and not overlay:
         raise ValueError("electrostatic_scores needs overlay=True: molecules that are not posed onto the reference are not "
                          "in the coordinates of its charges")
+    mcg_pharm.check_flag("interaction_scores", interaction_scores)
+    if max_interaction_score is not None:
+        mcg_interactions.check_threshold("max_interaction_score", max_interaction_score)
+    mcg_interactions.check_rank_by(rank_by)
+    interact = interaction_scores or max_interaction_score is not None
+    if rank_by == "interaction" and not interact:
+        raise ValueError("rank_by='interaction' needs interaction_scores (or max_interaction_score): it ranks by the "
+                         "interaction score")
+    if interact and getattr(gen, "finisher", None) is not None:
+        raise ValueError(mcg_interactions.REFUSAL_WITH_FINISHER)
+    if interact and receptor is None:
+        raise ValueError("interaction_scores needs a receptor: it scores the posed molecules against it")
     relax_steps = mcg_geometry.check_steps(relax_geometry)
     custom_finisher = isinstance(getattr(gen, "finisher", None), host_pool.TaskRef)
     shape = {}
@@ -291,8 +319,12 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
             common["reference"] = cheminformatics.ConformerReference(gen._reference_coord(reference_conformer))
         rec = None
         if receptor is not None:                  # refused with a mesh above: the reference is a conformer
-            rec = mcg_receptor.load_receptor(receptor)
+            typed = isinstance(receptor, (tuple, list)) and len(receptor) == 3      # (coords, atomic_numbers, types)
+            rec = mcg_receptor.load_receptor((receptor[0], receptor[1]) if typed else receptor)
             mcg_receptor.check_clear_of_reference(rec[0], common["reference"].coords)
+            if interact:
+                common.update(scores_interactions=True, max_interaction_score=max_interaction_score, rank_by=rank_by,
+                              typed_receptor=mcg_interactions.prepare_receptor(receptor))
         shape = dict(overlay=bool(overlay), scores_shape=bool(scoring), top_k=top_k,
                      min_shape_tanimoto=min_shape_tanimoto, max_pairwise_tanimoto=max_pairwise_tanimoto,
                      refine_steps=refine_steps, receptor=rec, max_receptor_clashes=max_receptor_clashes,
@@ -301,7 +333,6 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     mcg_pharm.check_flag("pharmacophore_scores", pharmacophore_scores)
     if min_pharmacophore_tanimoto is not None:
         mcg_pharm.check_threshold("min_pharmacophore_tanimoto", min_pharmacophore_tanimoto)
-    mcg_esp.check_rank_by(rank_by)
     pharm = pharmacophore_scores or min_pharmacophore_tanimoto is not None
     if rank_by == "electrostatic" and not (esp and shape.get("scores_shape")):
         raise ValueError("rank_by='electrostatic' needs shape scores (shape_scores, top_k, min_shape_tanimoto or "
@@ -508,6 +539,7 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
     without a count - its pose failed - does not pass), then those with a chemical Tanimoto below `max_chemical_tanimoto` (NaN
     does not pass), then those with a pharmacophore Tanimoto of at least `min_pharmacophore_tanimoto` (NaN and None do not
     pass), then those with an electrostatic Tanimoto of at least `min_electrostatic_tanimoto` (NaN and None do not pass),
+    then those with an interaction score of at most `max_interaction_score` (NaN and None do not pass),
     then `require_substructures` - the rows in which every required pattern is PROVEN present (count >= 1) - and
     `exclude_substructures` - the rows in which no excluded pattern is proven present; a row whose search for a pattern
     ended with BUDGET before it found an embedding is undetermined: not proven to contain it, so `require` drops it and
@@ -516,8 +548,8 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
     not proven equal to anything and stays) -, then `unique` - of the rows with one graph key (`unique="exact"`: with one
     exact identity, `select_exact`) the first in ranking order
     (`cheminformatics.ranking_key` of `Request.ranking_score`: by shape score where the call scores shape - plus the
-    pharmacophore score with `rank_by="combo"`, the electrostatic score with `rank_by="electrostatic"` - else the lowest
-    sample id), still in the
+    pharmacophore score with `rank_by="combo"`, the electrostatic score with `rank_by="electrostatic"`; by minus the
+    interaction score with `rank_by="interaction"` - else the lowest sample id), still in the
     input's order - then the threshold (always on the shape score alone), the sphere exclusion at `max_pairwise_tanimoto` and at
     `max_pairwise_chemical_tanimoto` in one walk, and `top_k` (`cheminformatics.select_diverse`).  `shape_pair(rows)` /
     `chem_pair(rows)`: the [n,n] pair matrices of the surviving rows, each called only when its threshold is set."""
@@ -536,6 +568,9 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
     if req.min_electrostatic_tanimoto is not None:
         rows = rows.take([i for i, m in enumerate(rows.measured) if m.electrostatic_tanimoto is not None
                           and m.electrostatic_tanimoto >= req.min_electrostatic_tanimoto])
+    if req.max_interaction_score is not None:
+        rows = rows.take([i for i, m in enumerate(rows.measured) if m.interaction_score is not None
+                          and m.interaction_score <= req.max_interaction_score])
     if req.n_required or req.n_excluded:
         need, last = req.n_required, req.n_required + req.n_excluded
         undetermined = sum(1 for c, st in rows.sub if any(st[p] != 0 and c[p] == 0 for p in range(last)))
@@ -667,6 +702,24 @@ def electrostatics(gen, req: Request, res: dict, placed: Optional[dict] = None, 
     return values
 
 
+def interactions(gen, req: Request, res: dict) -> dict:
+    """The interaction step of the rows a rank returns (`interaction_scores`), on the RETURNED coordinates - relaxed,
+    posed, refined, relieved - and graphs: one `_interaction_scores` call over the rows against the request's typed
+    receptor.  The per-sample tensors by the names `handoff.measured_from_tensors` reads: `interaction_score` [B],
+    `interaction_terms` [B,6] (G1, G2, REP, HYD, HB, n_rot), `receptor_hbonds` [B] (-1 where posing failed or the row has
+    a non-finite coordinate: the record gets None throughout) and `interaction_atom_scores` [B,N], +inf at and beyond a
+    row's atoms."""
+    out = gen._interaction_scores(req.typed_receptor, res["x"], res["n_nodes"], res["elements"], res["bond"])
+    score, hbonds, atoms = out["score"], out["hbonds"], out["atom_scores"]
+    dev = score.device
+    posed = torch.isfinite(res["pose"]).all(dim=1).to(dev) & (hbonds >= 0)    # a failed pose is not in the receptor's frame
+    real = torch.arange(atoms.shape[1], device=dev).view(1, -1) < res["n_nodes"].to(dev).reshape(-1, 1)
+    return dict(interaction_score=torch.where(posed, score, torch.full_like(score, float("nan"))),
+                interaction_terms=torch.cat([out["terms"][:, :5], out["n_rot"].to(dev, torch.float32).view(-1, 1)], dim=1),
+                receptor_hbonds=torch.where(posed, hbonds, torch.full_like(hbonds, -1)),
+                interaction_atom_scores=torch.where(real, atoms, torch.full_like(atoms, float("inf"))))
+
+
 def _index(rows: Rows, device) -> torch.Tensor:
     return torch.tensor(rows.row, dtype=torch.long, device=device)
 
@@ -764,6 +817,8 @@ def return_records(gen, req: Request, res: dict, row_ids: Optional[torch.Tensor]
         posed = torch.isfinite(res["pose"]).all(dim=1).to(sim.device)         # a failed pose is not in the reference's frame
         values.update(pharmacophore_tanimoto=torch.where(posed, sim, torch.full_like(sim, float("nan"))),
                       pharmacophore_matches=torch.where(posed, hits, torch.full_like(hits, -1)))
+    if req.scores_interactions:
+        values.update(interactions(gen, req, res))
     placed = perceived = None
     if req.needs_charges:                         # perceived once for the placement and the charges
         perceived = gen._pharm_perceive(res["elements"], res["bond"], res["n_nodes"])

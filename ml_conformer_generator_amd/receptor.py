@@ -32,6 +32,11 @@ finds none ends with a lower penalty and is reported as it is.  Heavy atoms only
                   coordinate is left exactly as it came, with NaN transform and stats; the other rows are unaffected.
 A molecule's result depends on its own atoms and the receptor's atoms only: the same bits in any batch, at any row, at any
 padded width, with and without tile skipping, and whatever the order the receptor's atoms were listed in.
+
+Interaction types (`load_typed_receptor`, `sort_typed_receptor`; DESIGN.md section 6, "Receptor interactions").  The clash
+criterion and the relief above type no donors or acceptors and read `load_receptor` as before; the interaction score of
+`interactions.py` reads one more byte per receptor atom - donor, acceptor, hydrophobic - from a residue-template table over
+a PDB string's names, from the elements alone, or as given.
 """
 from __future__ import annotations
 
@@ -169,6 +174,182 @@ def load_receptor(receptor) -> Tuple[torch.Tensor, torch.Tensor]:
     if not bool(torch.isfinite(coords).all()):
         raise ValueError("the receptor has a non-finite coordinate")
     return coords.contiguous(), z.contiguous()
+
+
+# ----------------------------------------------------------------------------------------------- typed loading
+# Interaction types of a receptor heavy atom ("Receptor interactions"; `interactions.py` reads them):
+# one byte of bits, the package's own typing - no hydrogens, no protonation states.
+TYPE_DONOR, TYPE_ACCEPTOR, TYPE_HYDROPHOBIC = 1, 2, 4
+TYPE_MAX = TYPE_DONOR | TYPE_ACCEPTOR | TYPE_HYDROPHOBIC
+METALS = (12, 20, 25, 26, 27, 28, 29, 30)      # Mg Ca Mn Fe Co Ni Cu Zn: typed as donors
+HALOGENS = (9, 17, 35, 53)
+POLAR_CARBON_DISTANCE = 1.75   # angstrom: a carbon with a receptor N or O this close is bonded to it - not hydrophobic
+_AMINO_ACIDS = frozenset("ALA ARG ASN ASP CYS GLN GLU GLY HIS ILE LEU LYS MET PHE PRO SER THR TRP TYR VAL".split())
+_WATERS = frozenset(("HOH", "WAT", "H2O", "DOD"))
+# (residue, atom) -> type of the side-chain N and O atoms of the standard residues
+_SIDE_CHAIN = {("ARG", "NE"): 1, ("ARG", "NH1"): 1, ("ARG", "NH2"): 1, ("ASN", "ND2"): 1, ("GLN", "NE2"): 1,
+               ("LYS", "NZ"): 1, ("TRP", "NE1"): 1, ("HIS", "ND1"): 3, ("HIS", "NE2"): 3, ("SER", "OG"): 3,
+               ("THR", "OG1"): 3, ("TYR", "OH"): 3, ("ASP", "OD1"): 2, ("ASP", "OD2"): 2, ("GLU", "OE1"): 2,
+               ("GLU", "OE2"): 2, ("ASN", "OD1"): 2, ("GLN", "OE1"): 2}
+
+
+def template_type(residue: str, atom: str, z: int) -> Optional[int]:
+    """The donor / acceptor bits of an N or O atom named `atom` in a residue named `residue` by the residue-template
+    table: the backbone N (a donor, except in PRO), O and OXT (acceptors) and the side-chain atoms of `_SIDE_CHAIN` of the
+    twenty standard residues, and a water's O (both).  None: the table does not know the atom."""
+    if residue in _WATERS:
+        return (TYPE_DONOR | TYPE_ACCEPTOR) if z == 8 else None
+    if residue not in _AMINO_ACIDS:
+        return None
+    if atom == "N" and z == 7:
+        return 0 if residue == "PRO" else TYPE_DONOR
+    if atom in ("O", "OXT") and z == 8:
+        return TYPE_ACCEPTOR
+    return _SIDE_CHAIN.get((residue, atom))
+
+
+def parse_pdb_names(text: str):
+    """[(residue name, atom name)] of exactly the records `parse_pdb` keeps, in its order."""
+    names = []
+    for line in text.splitlines():
+        rec = line[:6].rstrip()
+        if rec == "ENDMDL":
+            break
+        if rec not in ("ATOM", "HETATM") or line[16:17] not in ("", " ", "A"):
+            continue
+        if _Z_OF.get(_pdb_element(line)) == 1:
+            continue
+        names.append((line[17:20].strip().upper(), line[12:16].strip().upper()))
+    return names
+
+
+def polar_carbons(coords: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
+    """[R] bool: the carbons of (coords [R,3], z [R]) with an N or O of the same set within POLAR_CARBON_DISTANCE,
+    decided in fp64 on the host.  A cell sort: the N and O atoms are keyed by their cell (edge POLAR_CARBON_DISTANCE) and
+    sorted once, every carbon looks at the 27 cells round its own - never an R x R matrix.  A set too spread out for 2^20
+    cells per axis is compared in chunks of at most 2^22 pairs instead."""
+    xyz = coords.to(torch.float64).reshape(-1, 3)
+    carbon = (z == 6).nonzero().reshape(-1)
+    polar = ((z == 7) | (z == 8)).nonzero().reshape(-1)
+    out = torch.zeros(xyz.shape[0], dtype=torch.bool)
+    if carbon.numel() == 0 or polar.numel() == 0:
+        return out
+    c, p = xyz[carbon], xyz[polar]
+    lim2 = POLAR_CARBON_DISTANCE * POLAR_CARBON_DISTANCE
+    lo = xyz.min(dim=0).values
+    dims = ((xyz.max(dim=0).values - lo) / POLAR_CARBON_DISTANCE).floor().to(torch.long) + 3
+    hit = torch.zeros(c.shape[0], dtype=torch.bool)
+    if int(dims.max()) > (1 << 20):
+        step = max(1, (1 << 22) // int(p.shape[0]))
+        for k in range(0, int(c.shape[0]), step):
+            d2 = ((c[k: k + step, None, :] - p[None, :, :]) ** 2).sum(dim=2)
+            hit[k: k + step] = (d2 <= lim2).any(dim=1)
+    else:
+        def key(cell):
+            return (cell[:, 0] * dims[1] + cell[:, 1]) * dims[2] + cell[:, 2]
+        pc = ((p - lo) / POLAR_CARBON_DISTANCE).floor().to(torch.long) + 1
+        order = torch.sort(key(pc), stable=True)
+        pkey, p = order.values, p[order.indices]
+        cc = ((c - lo) / POLAR_CARBON_DISTANCE).floor().to(torch.long) + 1
+        for off in [(i, j, k) for i in (-1, 0, 1) for j in (-1, 0, 1) for k in (-1, 0, 1)]:
+            want = key(cc + torch.tensor(off, dtype=torch.long))
+            first, last = torch.searchsorted(pkey, want), torch.searchsorted(pkey, want, right=True)
+            for k in range(int((last - first).max())):           # the k-th N or O of that cell, where it has one
+                rows = (first + k < last).nonzero().reshape(-1)
+                d2 = ((c[rows] - p[first[rows] + k]) ** 2).sum(dim=1)
+                hit[rows] |= d2 <= lim2
+    out[carbon] = hit
+    return out
+
+
+def _element_types(coords: torch.Tensor, z: torch.Tensor, polar: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[R] uint8: the types of atoms without names - N and O donor and acceptor both (`polar` [R]: their bits from a
+    template instead), the METALS donors, a carbon hydrophobic unless `polar_carbons`, the HALOGENS hydrophobic, S and
+    every other element nothing."""
+    types = torch.zeros(z.shape[0], dtype=torch.uint8)
+    no = (z == 7) | (z == 8)
+    both = torch.full_like(types, TYPE_DONOR | TYPE_ACCEPTOR)
+    types = torch.where(no, both if polar is None else polar.to(torch.uint8), types)
+    for m in METALS:
+        types = torch.where(z == m, torch.full_like(types, TYPE_DONOR), types)
+    hydrophobic = ((z == 6) & ~polar_carbons(coords, z))
+    for h in HALOGENS:
+        hydrophobic |= z == h
+    return torch.where(hydrophobic, torch.full_like(types, TYPE_HYDROPHOBIC), types)
+
+
+def typed_receptor(receptor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, int]:
+    """(coords [R,3] fp32, atomic numbers [R] int64, types [R] uint8, untemplated) on the host: `load_receptor`'s heavy
+    atoms with their interaction types (bits TYPE_DONOR / TYPE_ACCEPTOR / TYPE_HYDROPHOBIC).
+      a PDB-format string: the N and O atoms by `template_type` over (residue name, atom name); an N or O the table does
+        not know (a non-standard residue, a HETATM ligand or cofactor) is donor and acceptor both; the METALS are donors;
+        a carbon is hydrophobic unless a receptor N or O lies within POLAR_CARBON_DISTANCE (`polar_carbons`); the HALOGENS
+        are hydrophobic; S is not an acceptor.  `untemplated`: the N, O and metal atoms typed without a template.
+      a (coords, atomic_numbers) pair or an RDKit Mol: there are no names - N and O are both, the rest as above;
+        `untemplated` is 0.
+      a (coords, atomic_numbers, types) triple: `types` [R] integers in 0..TYPE_MAX are used verbatim (those of the
+        hydrogens are dropped with them); ValueError for another shape, a non-integer or a value out of range."""
+    if isinstance(receptor, (tuple, list)) and len(receptor) == 3:
+        try:
+            given = torch.as_tensor(receptor[2]).cpu().reshape(-1)
+            raw_z = torch.as_tensor(receptor[1]).cpu().reshape(-1)
+        except (TypeError, RuntimeError, ValueError) as e:
+            raise ValueError(f"receptor (coords, atomic_numbers, types): unreadable: {e}") from None
+        if given.dtype.is_floating_point or given.dtype == torch.bool or given.numel() != raw_z.numel():
+            raise ValueError("receptor (coords [R,3], atomic_numbers [R], types [R]): R integer types are needed, got "
+                             f"{given.numel()} of type {given.dtype} for {raw_z.numel()} atoms")
+        if given.numel() and (int(given.min()) < 0 or int(given.max()) > TYPE_MAX):
+            raise ValueError(f"receptor types must be in 0..{TYPE_MAX} (bits 1 donor, 2 acceptor, 4 hydrophobic), got "
+                             f"{int(given.min())}..{int(given.max())}")
+        coords, z = load_receptor((receptor[0], receptor[1]))
+        return coords, z, given[raw_z != 1].to(torch.uint8).contiguous(), 0
+    coords, z = load_receptor(receptor)
+    if not isinstance(receptor, str):
+        return coords, z, _element_types(coords, z), 0
+    names = parse_pdb_names(receptor)
+    polar = torch.full((z.shape[0],), TYPE_DONOR | TYPE_ACCEPTOR, dtype=torch.uint8)
+    untemplated = 0
+    metals = set(METALS)
+    for k, ((residue, atom), zk) in enumerate(zip(names, z.tolist())):
+        if zk in (7, 8):
+            t = template_type(residue, atom, zk)
+            if t is None:
+                untemplated += 1
+            else:
+                polar[k] = t
+        elif zk in metals:
+            untemplated += 1
+    return coords, z, _element_types(coords, z, polar), untemplated
+
+
+def load_typed_receptor(receptor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(coords [R,3] fp32, atomic numbers [R] int64, types [R] uint8) on the host: `typed_receptor` of an RDKit Mol, a
+    PDB-format string, a (coords, atomic_numbers) pair or a (coords, atomic_numbers, types) triple; one warning where N, O
+    or metal atoms of a PDB string were typed without a template.  Refused with ValueError: what `load_receptor` refuses,
+    and types of the wrong shape, kind or range."""
+    coords, z, types, untemplated = typed_receptor(receptor)
+    if untemplated:
+        import warnings
+        warnings.warn(f"receptor typing: {untemplated} N, O or metal atom(s) are in no residue template (non-standard "
+                      "residues, HETATM groups, ions); such an N or O counts as donor and acceptor both, a metal as a donor")
+    return coords, z, types
+
+
+def sort_typed_receptor(rec_xyz: torch.Tensor, rec_radius: torch.Tensor, rec_type: torch.Tensor
+                        ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`sort_receptor` with a type byte carried along: ([R,4] fp32 (x, y, z, radius), [R] uint8) on the host, by the same
+    Morton-cell sort over the canonical lexicographic order (x, y, z, radius, then the type as the last tie-break).  The
+    result does not depend on the order the atoms came in."""
+    xyzr = torch.cat([rec_xyz.to(torch.float32).reshape(-1, 3), rec_radius.to(torch.float32).reshape(-1, 1)], dim=1).cpu()
+    types = torch.as_tensor(rec_type).to(torch.uint8).reshape(-1).cpu()
+    order = torch.sort(types.to(torch.int64), stable=True).indices
+    for col in (3, 2, 1, 0):
+        order = order[torch.sort(xyzr[order, col], stable=True).indices]
+    xyzr, types = xyzr[order], types[order]
+    cell = ((xyzr[:, :3] - xyzr[:, :3].min(dim=0).values) / _SORT_CELL).floor().to(torch.long).clamp_(0, 1023)
+    key = _spread_bits(cell[:, 0]) | (_spread_bits(cell[:, 1]) << 1) | (_spread_bits(cell[:, 2]) << 2)
+    order = torch.sort(key, stable=True).indices
+    return xyzr[order].contiguous(), types[order].contiguous()
 
 
 def check_clear_of_reference(rec_coords: torch.Tensor, ref_coord: torch.Tensor) -> None:
