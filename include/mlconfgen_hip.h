@@ -302,6 +302,13 @@ void mcg_gcn_destroy(mcg_gcn* g);
 int mcg_gcn_forward(mcg_gcn* g, const int64_t* elements, const float* dist_mat, const float* adj_mat, float* logits,
                     int8_t* bond, int B, void* stream);
 int mcg_gcn_check(mcg_gcn* g);
+/* Debug hook: a copy-out of the GCN's workspace as the last mcg_gcn_forward left it, for the first B molecules of that
+ * call: which = 0 L_dm[B,42,42] (normalised distance graph), 1 L_adj[B,42,42] (normalised bond graph), 2 the per-atom
+ * bottleneck[B,42] (dm_resize), 3 scale[B,42*64] (nodes_coord_fc), 4 the main branch's input e0[B,42,64] (embedding +
+ * scale), 5 the last GraphConv's output xb[B*42,2048], 6 res[B,42,42,5] (resize, before symmetrisation).  One
+ * device-to-device copy on `stream`; the forward pass is not touched.  MCG_ERR_ARG, nothing copied: a null argument, an
+ * unknown `which`, B < 1 or B above what the workspace was last sized for. */
+int mcg_gcn_peek(const mcg_gcn* g, int which, int B, float* dst, void* stream);
 /* EDM -> GCN hand-off (replaces samples_to_rdkit_mol + prepare_adj_mat_seer_input, utils/mol_utils.py:18-57,146-194,
  * for the tensor part): elements[B,42] int64 (atomic numbers, 0 padded), dist_mat[B,42,42] (distances + I),
  * adj_mat[B,42,42] ({0,1} covalent-radius connectivity + I) from x[B,N,3], h[B,N,8] one-hot and n_nodes[B] (device

@@ -52,6 +52,7 @@ SIGNATURES: Dict[str, tuple] = {
     "mcg_gcn_destroy": (None, [_vp]),
     "mcg_gcn_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "mcg_gcn_check": (_i, [_vp]),
+    "mcg_gcn_peek": (_i, [_vp, _i, _i, _vp, _vp]),
     "mcg_shape_tanimoto": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp]),
     "mcg_shape_moments": (_i, [_vp, _vp, _i, _i, _d, _d, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mcg_shape_frames": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _d, _d, _f, _i, _i, _vp, _vp, _vp]),

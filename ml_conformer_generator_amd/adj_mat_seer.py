@@ -82,6 +82,18 @@ class AdjMatSeer(torch.nn.Module):
         if self._h and _lib.lib().mcg_gcn_check(self._h) != 0:
             raise IndexError("index out of range in self (element id outside the embedding table)")
 
+    def _peek(self, which: int, B: int) -> torch.Tensor:
+        """Debug hook (`mcg_gcn_peek`): workspace buffer `which` as the last forward left it, first B molecules."""
+        d, e, nb = self.dimension, self.embedding_dim, self.num_bond_types
+        shapes = {0: (B, d, d), 1: (B, d, d), 2: (B, d), 3: (B, d * e), 4: (B, d, e), 5: (B * d, GCN_HIDDEN),
+                  6: (B, d, d, nb)}
+        if which not in shapes or B < 1:
+            raise ValueError(f"mcg_gcn_peek: which = {which}, B = {B}")
+        buf = torch.empty(shapes[which], device=self.device, dtype=torch.float32)
+        _lib.check(_lib.lib().mcg_gcn_peek(self._h, int(which), int(B), _lib.dptr(buf),
+                                           _lib.current_stream_ptr(self.device)), "mcg_gcn_peek")
+        return buf
+
     def __del__(self):
         try:
             if self._h:

@@ -387,4 +387,31 @@ int mcg_gcn_check(mcg_gcn* g) {
     return h ? MCG_ERR_STATE : MCG_OK;
 }
 
+// Debug/test hook: copy one of the workspace buffers out as the last mcg_gcn_forward left it (first B molecules).
+// which: 0 L_dm[B,42,42], 1 L_adj[B,42,42], 2 bottleneck[B,42] (the real columns of emb44), 3 scale[B,42*64],
+// 4 e0[B,42,64] (main-branch input), 5 xb[B*42,2048] (last GraphConv output), 6 res[B,42,42,5] (before k_symm)
+int mcg_gcn_peek(const mcg_gcn* g, int which, int B, float* dst, void* stream) {
+    if (!g || !dst || which < 0 || which > 6 || B < 1 || B > g->cap) {
+        mcg_set_error("mcg_gcn_peek: bad arguments (which %d, B %d, workspace sized for %d)", which, B, g ? g->cap : 0);
+        return MCG_ERR_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const float* src = nullptr; size_t n = 0;
+    switch (which) {
+        case 0: src = g->L_dm; n = (size_t)B * D * D; break;
+        case 1: src = g->L_adj; n = (size_t)B * D * D; break;
+        case 2:
+            MCG_HIP(hipMemcpy2DAsync(dst, D * sizeof(float), g->emb44, DP * sizeof(float), D * sizeof(float), B,
+                                     hipMemcpyDeviceToDevice, s));
+            return MCG_OK;
+        case 3: src = g->scale; n = (size_t)B * D * EMB; break;
+        case 4: src = g->e0; n = (size_t)B * D * EMB; break;
+        case 5: src = g->xb; n = (size_t)B * D * HID; break;
+        case 6: src = g->res; n = (size_t)B * D * D * NB; break;
+        default: return MCG_ERR_ARG;
+    }
+    MCG_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return MCG_OK;
+}
+
 }  // extern "C"

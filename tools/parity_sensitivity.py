@@ -15,7 +15,10 @@ mutation violates the tolerance by at least MIN_RATIO (10x); the unmutated oracl
 A fixture that cannot see a mutation is useless as a pin for that arithmetic: regenerate it (tools/make_golden.py:
 weight gains / input scale) until this script exits 0.
 
-Usage: python tools/parity_sensitivity.py [--fast]      (exit code 1 on any blind spot)
+`--gcn` does the same for the bond-prediction GCN (AdjMatSeer): planted mistakes in tests/gcn_ref.py against the per-stage
+tolerances of tests/test_gcn_gpu.py; its output is committed as profiles/gcn_parity_sensitivity.txt.
+
+Usage: python tools/parity_sensitivity.py [--fast | --gcn]      (exit code 1 on any blind spot)
 """
 import argparse
 import os
@@ -142,8 +145,47 @@ def fixture_weights(g):
     return W.synth_edm_state_dict(int(g["weight_seed"]))
 
 
+def gcn_main(B):
+    """--gcn: the AdjMatSeer stage pins (tests/test_gcn_gpu.py).  For every input set and weight set of tests/gcn_ref.py the
+    fp32 restatement, unmutated and with each planted mistake, is compared with the fp64 restatement at every quantity the
+    GPU test asserts, in units of THAT quantity's tolerance (gcn_ref.STAGE_TOL x rtol 1e-4 / atol 1e-5 of its maximum).
+    Passes when every mutation reaches MIN_RATIO somewhere and the unmutated fp32 run stays within 0.25 everywhere."""
+    import gcn_ref as R
+    print(f"AdjMatSeer stage pins, B <= {B}; stage tolerances as fractions of rtol {R.RTOL:g} / atol {R.ATOL:g}:")
+    print("    measured fp32 vs fp64 (B = 16): " + "  ".join(f"{q} {R.MEASURED_FP32[q]:g}" for q in R.QUANTITIES))
+    print(f"    x {R.MARGIN:g}, capped at 1:         " + "  ".join(f"{q} {R.STAGE_TOL[q]:g}" for q in R.QUANTITIES))
+    tab = R.table(R.input_sets(B))
+    head = " " * 26 + " ".join(f"{q:>10s}" for q in R.QUANTITIES)
+    best = {m: 0.0 for m in R.MUTATIONS}
+    worst_fp32 = {q: 0.0 for q in R.QUANTITIES}
+    bad = 0
+    for (wn, sn), rows in tab.items():
+        print(f"\nweights {wn}, inputs {sn}: max|logits| {float(rows['ref']['logits'].abs().max()):.3g}   [x stage tolerance]")
+        print(head)
+        base = {q: rows["base"][q] / R.STAGE_TOL[q] for q in R.QUANTITIES}
+        for q in R.QUANTITIES:
+            worst_fp32[q] = max(worst_fp32[q], rows["base"][q])
+        flag = "" if max(base.values()) <= 0.25 else "   <-- fp32 OUTSIDE 0.25"
+        bad += max(base.values()) > 0.25
+        print(f"    {'none (fp32 vs fp64)':22s}" + " ".join(f"{base[q]:10.3g}" for q in R.QUANTITIES) + flag)
+        for m in R.MUTATIONS:
+            r = {q: rows[m][q] / R.STAGE_TOL[q] for q in R.QUANTITIES}
+            best[m] = max(best[m], max(r.values()))
+            print(f"    {m:22s}" + " ".join(f"{r[q]:10.3g}" for q in R.QUANTITIES))
+    print("\nmost visible appearance of each mutation (x the tolerance of the quantity that sees it):")
+    for m in R.MUTATIONS:
+        flag = "" if best[m] >= MIN_RATIO else "   <-- BLIND"
+        bad += best[m] < MIN_RATIO
+        print(f"    {m:22s} {best[m]:12.3g}{flag}")
+    print("worst unmutated fp32 vs fp64, x the project tolerance: " + "  ".join(f"{q} {worst_fp32[q]:.3g}" for q in R.QUANTITIES))
+    print("PASS" if not bad else f"FAIL: {bad} blind spot(s) / fp32 excursions")
+    return 1 if bad else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--gcn", action="store_true", help="the AdjMatSeer stage pins instead of the denoiser fixtures (~15 s)")
+    ap.add_argument("--gcn-batch", type=int, default=16, help="--gcn: molecules per input set (the GPU test uses 16)")
     ap.add_argument("--fast", action="store_true", help="single-call and block fixtures only (skip the sampler trajectories)")
     ap.add_argument("--only", default=None)
     ap.add_argument("--long", action="store_true",
@@ -155,6 +197,8 @@ def main():
                          "its deviations peak; 10 = all of it, 3.3 x the time); e2e_T100 always runs in full")
     args = ap.parse_args()
     torch.set_num_threads(args.threads)
+    if args.gcn:
+        return gcn_main(args.gcn_batch)
     names = ["dynamics_b2n20.npz", "dynamics_b4n19.npz", "dynamics_b3n39.npz", "dynamics_b3n27_x30.npz", "block3_b2n20.npz",
              "dynamics_b3n114.npz"]
     if not args.fast:
