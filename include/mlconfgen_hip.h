@@ -875,6 +875,42 @@ int mcg_receptor_interactions(const float* lig_xyz, const float* lig_radius, con
                               float* atom_terms /*[B,N,6]*/, float* mol_terms /*[B,8]*/, int32_t* hbonds /*[B]*/,
                               void* stream);
 
+/* ---- Optimised pose ("Optimised pose"): every posed molecule moved as a rigid body downhill on the
+ * weighted sum W of the five interaction terms above (mol_terms[5]; E is W over a positive constant, so less W is less
+ * E), one 256-lane workgroup per molecule, by the accept / reject walk of mcg_receptor_relieve.  The package's OWN
+ * procedure: not a docking run, not AutoDock Vina's local optimisation; rigid body only - no torsions, no intramolecular
+ * term, no hydrogens, no global search.
+ *   lig_xyz, lig_radius, lig_type, n_nodes_dev, rec_xyzr, rec_type, tile_sphere: as for mcg_receptor_interactions; the
+ *   pair arithmetic (r2, the r2 < 64.0f decision, d, the five terms), the lane layout and the order of every sum are that
+ *   entry's, from one shared text, so W of a pose has the bits mol_terms[5] has for the same coordinates.
+ *   Force on atom i: F_i = - sum_j (dW/dd) (x_i - y_j) / r over its counted pairs (direction 0 at r = 0), the slope decided
+ *   on the same fp32 d as the terms: g1' = -8 d g1, g2' = -((d - 3) / 2) g2, rep' = 2 d where d < 0, hyd' = -1 on
+ *   0.5 < d < 1.5 (both hydrophobic), hb' = 1 / -0.7f on -0.7f < d < 0 (donor facing acceptor), 0 elsewhere.
+ *   Motion x' = (x - c) @ G + p, c the input's atom centroid summed in atom order, from G = I, p = c; the first evaluation
+ *   reads the input rows as they came.  Torque about p: sum_i u_i x F_i, u_i = (x_i - c) @ G.  A trial rotates by s_r about
+ *   the torque and moves p by s_t along the net force (from 0.05 rad, 0.25 A; a zero or non-finite vector skips its part
+ *   of the move, both skipped ends the walk); a trial with |p' - c| > max_shift is rejected unevaluated; an evaluated one
+ *   is kept iff W' < W strictly (NaN never is); kept: both lengths x 1.2, rejected: x 0.5.  The walk ends after `steps`
+ *   trials or once s_t < 2^-8 A.  G is re-orthonormalised as each trial is formed, so the pose returned is the one scored.
+ *   The tile list is built once, with max_shift added to the scoring entry's reach; it changes no bit.
+ *   coords_out[B,N,3]: the kept pose (padded rows zero); xform_out[B,12]: rotation row-major, then translation, with
+ *   x' = x @ R + t; stats_out[B,8]: W before, W after, trials used, trials kept, heavy-atom RMSD between input and output,
+ *   the final s_t, 0, 0; gradient_out[B,6] (may be NULL): net force and torque at the input pose; trace_out[B,steps,24]
+ *   (may be NULL; for tests): per trial F[3], torque[3] at the current pose, s_r, s_t, the trial's G'[9] and p'[3], W' (0
+ *   where not evaluated), evaluated (0 / 1), kept (0 / 1), W of the current pose; rows beyond the last trial are zero.
+ *   A molecule no trial of which was kept (steps = 0 and no counted pair included) returns its input rows bit for bit,
+ *   R = I, t = 0.  A molecule without atoms or with a non-finite coordinate on a real atom returns its rows as they came
+ *   and NaN in xform, stats and gradient (its trace rows zero); the others are unaffected.  Every output depends on the
+ *   molecule's own atoms and the receptor arrays only: the same bits in any batch, row, width, with or without tile_sphere.
+ * MCG_ERR_ARG, nothing launched: a null buffer (tile_sphere, gradient_out and trace_out excepted), B outside
+ * 1..MCG_RECEPTOR_MAX_B, N outside 1..64, R outside 1..MCG_RECEPTOR_MAX_ATOMS, steps outside 0..1024, max_shift negative
+ * or not finite. */
+int mcg_receptor_optimise(const float* lig_xyz, const float* lig_radius, const uint8_t* lig_type,
+                          const int32_t* n_nodes_dev, int B, int N, const float* rec_xyzr, const uint8_t* rec_type, int R,
+                          const float* tile_sphere /*optional*/, int steps, float max_shift, float* coords_out /*[B,N,3]*/,
+                          float* xform_out /*[B,12]*/, float* stats_out /*[B,8]*/, float* gradient_out /*optional [B,6]*/,
+                          float* trace_out /*optional [B,steps,24]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

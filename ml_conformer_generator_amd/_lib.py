@@ -65,6 +65,7 @@ SIGNATURES: Dict[str, tuple] = {
     "mcg_receptor_overlap": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "mcg_receptor_relieve": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "mcg_receptor_interactions": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mcg_receptor_optimise": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcg_graph_fingerprint": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "mcg_fingerprint_tanimoto": (_i, [_vp, _vp, _i, _vp, _vp]),
     "mcg_fingerprint_pair_tanimoto": (_i, [_vp, _i, _vp, _vp]),

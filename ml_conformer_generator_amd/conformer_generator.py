@@ -419,6 +419,13 @@ class MLConformerGenerator(torch.nn.Module):
         return mcg_interactions.interaction_scores(receptor, coords, n_nodes, atomic_numbers, bond_orders,
                                                    device=self.device, check=False)
 
+    def _optimise_pose(self, receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_numbers: torch.Tensor,
+                       bond_orders: torch.Tensor, steps: int) -> dict:
+        """Padded posed heavy-atom coordinates moved as rigid bodies downhill on the interaction score with the call's
+        typed receptor - a `interactions.prepare_receptor` result - (`interactions.optimise_pose`, device tensors)."""
+        return mcg_interactions.optimise_pose(receptor, coords, n_nodes, atomic_numbers, bond_orders, steps,
+                                              device=self.device)
+
     # the standardisation step
     def _standardize(self, coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
                      n_nodes: torch.Tensor) -> dict:
@@ -629,7 +636,8 @@ class MLConformerGenerator(torch.nn.Module):
                             smiles: bool = False, exclude_graphs=None, require_substructures=None,
                             exclude_substructures=None, substructure_counts=None,
                             interaction_scores: bool = False,
-                            max_interaction_score: Optional[float] = None) -> List:
+                            max_interaction_score: Optional[float] = None,
+                            optimise_pose: Union[bool, int] = False) -> List:
         """Generate molecules from a reference shape (conformer_generator.py:268-368).
         Returns the VALID molecules only (invalid ones are dropped, as in the reference): `List[Chem.Mol]` through the
         reference's standardisation (+ MMFF94 when `optimise_geometry`) where RDKit imports, else `GeneratedMolecule`
@@ -832,6 +840,16 @@ class MLConformerGenerator(torch.nn.Module):
         element rules for a (coords, atomic_numbers) pair or a Mol, or the explicit third element of a (coords,
         atomic_numbers, types) triple - once per call; one warning counts the N, O and metal atoms outside the table.  The
         step runs behind the gather, beside the pharmacophore step, in one launch.
+        `optimise_pose` (needs a `receptor` and `overlay=True`; records path only; implies `interaction_scores`): True (64
+        trials) or a trial budget 1..1024.  Directly behind the pose, its refinement and the clash relief, every posed
+        molecule is moved as a rigid body to where that interaction score is lower (`interactions.optimise_pose`;
+        DESIGN.md section 6, "Optimised pose"): a downhill accept / reject walk along the score's net force and torque, the
+        centroid held within 2 A of where it started.  THE PACKAGE'S OWN PROCEDURE: not a docking run, not AutoDock Vina's
+        local optimisation; rigid body only - no torsions, no intramolecular term, no hydrogens, no global search.  The
+        optimised coordinates are what everything behind it reads and what is returned; `pose` is the composed transform
+        and `overlay_tanimoto` the shape Tanimoto of the pose as placed; an unmoved molecule keeps every bit.  Records
+        carry `interaction_score_before` (E of the pose the walk started from), `pose_optimisation_rmsd` (A the heavy
+        atoms moved; 0.0 where nothing moved) and `pose_trials_kept`; None in a call without it and where posing failed.
         `max_interaction_score=t` (implies the score; t a finite real number): keep the molecules with E <= t; NaN and
         missing do not pass; right behind `min_electrostatic_tanimoto`.
         `rank_by="interaction"` (needs the score): `unique`, the diversity walk and `top_k` rank by -E;
@@ -847,7 +865,8 @@ class MLConformerGenerator(torch.nn.Module):
         overlay, refine_overlay other than True or an integer in 1..1024 or without overlay, a receptor without overlay,
         one `load_receptor` refuses or one that holds the reference (a reference heavy atom within 0.5 A of a receptor
         heavy atom), max_receptor_clashes other than an integer >= 0 or without a receptor, relieve_clashes other than
-        False, True or an integer in 1..1024 or without a receptor, a custom finisher, a
+        False, True or an integer in 1..1024 or without a receptor, optimise_pose other than False, True or an integer in
+        1..1024, without a receptor or on a generator with a finisher, a custom finisher, a
         `reference_shape` together with another reference, with `refine_overlay` or with a `receptor`, or without
         `n_atoms`, a mesh `load_mesh` refuses ("The mesh needs to be watertight."), a `shape_density` that is not a positive
         real number, max_atoms_outside other than an integer >= 0, without a `reference_shape` or without overlay, and
@@ -881,7 +900,7 @@ class MLConformerGenerator(torch.nn.Module):
                                         add_hydrogens, standardize, electrostatic_scores, reference_charges,
                                         min_electrostatic_tanimoto, partial_charges, smiles, exclude_graphs,
                                         require_substructures, exclude_substructures, substructure_counts,
-                                        interaction_scores, max_interaction_score)
+                                        interaction_scores, max_interaction_score, optimise_pose)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         req = postprocess.label_excluded(self, req)      # `exclude_graphs`: the first device work, behind every check above
@@ -924,7 +943,8 @@ class MLConformerGenerator(torch.nn.Module):
                                     partial_charges: bool = False, smiles: bool = False,
                                     exclude_graphs=None, require_substructures=None, exclude_substructures=None,
                                     substructure_counts=None, interaction_scores: bool = False,
-                                    max_interaction_score: Optional[float] = None) -> List:
+                                    max_interaction_score: Optional[float] = None,
+                                    optimise_pose: Union[bool, int] = False) -> List:
         """`generate_conformers` for `n_samples` molecules in TOTAL, sharded over the ranks of the initialised
         `torch.distributed` group (one process per GPU, each with its own generator instance / weight replica;
         SURVEY.md section 8e).  The global size vector is drawn once on rank 0 and broadcast; every rank derives the same
@@ -950,7 +970,8 @@ class MLConformerGenerator(torch.nn.Module):
         `require_substructures`, `exclude_substructures`, `substructure_counts` (matched behind the gather, on the rows a
         rank returns; every rank compiles the patterns itself),
         `interaction_scores`, `max_interaction_score` (scored behind the gather, on the rows a rank returns; every rank
-        types and sorts the receptor itself),
+        types and sorts the receptor itself), `optimise_pose` (on each rank's own shard, before the gather, directly behind
+        the relief; its per-sample tensors travel with the rest),
         `add_hydrogens` (placed behind the gather, on the rows a rank returns), `standardize` (on each rank's own shard,
         before the gather; its per-sample tensors travel with the rest, one collective each): as in
         `generate_conformers` (every rank loads the mesh and computes its occupancy itself).  The fingerprints are computed behind the gather,
@@ -976,7 +997,7 @@ class MLConformerGenerator(torch.nn.Module):
                                         add_hydrogens, standardize, electrostatic_scores, reference_charges,
                                         min_electrostatic_tanimoto, partial_charges, smiles, exclude_graphs,
                                         require_substructures, exclude_substructures, substructure_counts,
-                                        interaction_scores, max_interaction_score)
+                                        interaction_scores, max_interaction_score, optimise_pose)
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)

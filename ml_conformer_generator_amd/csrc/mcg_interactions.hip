@@ -18,6 +18,7 @@
 #include "mcg_common.h"
 #include "mcg_api_internal.h"
 #include "mcg_shape_grid.h"
+#include "mcg_interaction_pair.h"
 
 #include <math.h>
 
@@ -26,17 +27,9 @@
 namespace {
 
 using namespace mcg_shape;
+using namespace mcg_interaction;     // the pair arithmetic, shared with k_receptor_optimise
 
-constexpr int IX_THREADS = 256;               // lanes per workgroup = receptor atoms per tile
-constexpr int IX_WAVES = IX_THREADS / 64;
 constexpr int IX_MAX_TILES = MCG_RECEPTOR_MAX_ATOMS / IX_THREADS;
-constexpr float IX_CUTOFF = 8.0f, IX_CUTOFF2 = 64.0f;
-// What the reach of the tile test adds to the exact bound: the centroid, rho and the test itself are rounded, all far
-// below 1e-3 of the lengths involved.
-constexpr float IX_SLACK_ABS = 0.05f, IX_SLACK_REL = 1e-3f;
-constexpr float W_G1 = -0.0356f, W_G2 = -0.00516f, W_REP = 0.840f, W_HYD = -0.0351f, W_HB = -0.587f, W_ROT = 0.0585f;
-constexpr float HB_FULL = -0.7f;              // a hydrogen bond counts in full at or below this surface distance
-constexpr unsigned T_DONOR = 1u, T_ACCEPTOR = 2u, T_HYDROPHOBIC = 4u;
 
 static_assert(MCG_RECEPTOR_MAX_ATOMS % IX_THREADS == 0, "the tile list holds every tile of the largest receptor");
 
@@ -51,11 +44,6 @@ struct InteractionShared {
     int n_tiles;
     unsigned short list[IX_MAX_TILES];
 };
-
-// ((((w1 g1 + w2 g2) + w3 rep) + w4 hyd) + w5 hb): the weighted sum of five terms, in this order
-__device__ __forceinline__ float weighted(const float* t) {
-    return (((W_G1 * t[0] + W_G2 * t[1]) + W_REP * t[2]) + W_HYD * t[3]) + W_HB * t[4];
-}
 
 __global__ __launch_bounds__(IX_THREADS) void k_receptor_interactions(
     const float* __restrict__ lig, const float* __restrict__ lig_r, const unsigned char* __restrict__ lig_t,
@@ -144,27 +132,11 @@ __global__ __launch_bounds__(IX_THREADS) void k_receptor_interactions(
         __syncthreads();
         for (int jj = w; jj < cnt; jj += IX_WAVES) {
             const float4 q = s.tile[jj];
-            const float dx = x - q.x, dy = y - q.y, dz = z - q.z;
-            const float r2 = (dx * dx + dy * dy) + dz * dz;
+            float dx, dy, dz;
+            const float r2 = pair_r2(x, y, z, q, dx, dy, dz);
             const bool counts = real && r2 < IX_CUTOFF2;
             if (__ballot(counts) == 0ull) continue;                // nobody in this wave: nothing is added
-            if (counts) {
-                const unsigned tj = s.type[jj];
-                const float d = sqrtf(r2) - (ri + q.w);
-                const float a1 = d + d;                            // d / 0.5
-                const float a2 = (d - 3.0f) * 0.5f;                // (d - 3) / 2
-                acc[0] += expf(-(a1 * a1));
-                acc[1] += expf(-(a2 * a2));
-                if (d < 0.f) acc[2] += d * d;
-                if ((ti & tj & T_HYDROPHOBIC) != 0u && d < 1.5f) acc[3] += d <= 0.5f ? 1.0f : 1.5f - d;
-                const bool pair_hb = ((ti & T_DONOR) != 0u && (tj & T_ACCEPTOR) != 0u) ||
-                                     ((ti & T_ACCEPTOR) != 0u && (tj & T_DONOR) != 0u);
-                if (pair_hb && d < 0.f) {
-                    const bool full = d <= HB_FULL;
-                    acc[4] += full ? 1.0f : d / HB_FULL;
-                    nhb += full ? 1 : 0;
-                }
-            }
+            if (counts) pair_terms(r2, ri, q.w, ti, s.type[jj], acc, nhb);
         }
         __syncthreads();                      // the tile is free again
     }

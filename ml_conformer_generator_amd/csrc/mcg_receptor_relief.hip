@@ -23,6 +23,7 @@
 #include "mcg_common.h"
 #include "mcg_api_internal.h"
 #include "mcg_shape_grid.h"
+#include "mcg_rigid_step.h"
 
 #include <math.h>
 
@@ -31,6 +32,7 @@
 namespace {
 
 using namespace mcg_shape;
+using namespace mcg_rigid;     // mat3_mul, rodrigues_row, orthonormalise: one text for every rigid-body walk
 
 constexpr int RL_THREADS = 256;               // lanes per workgroup = receptor atoms per tile
 constexpr int RL_WAVES = RL_THREADS / 64;
@@ -44,47 +46,6 @@ constexpr float RL_GROW = 1.2f, RL_SHRINK = 0.5f;
 constexpr float RL_SLACK_ABS = 0.05f, RL_SLACK_REL = 1e-3f;
 
 static_assert(MCG_RECEPTOR_MAX_ATOMS % RL_THREADS == 0, "the tile list holds every tile of the largest receptor");
-
-// c = a @ b (row-major 3x3), as in mcg_shape_refine.hip
-__device__ __forceinline__ void mat3_mul(const float* a, const float* b, float* c) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            c[i * 3 + j] = __builtin_fmaf(a[i * 3 + 2], b[6 + j], __builtin_fmaf(a[i * 3], b[j], a[i * 3 + 1] * b[3 + j]));
-}
-
-// Row-vector form (r' = r @ D) of the rotation by theta about the unit axis n, as in mcg_shape_refine.hip.
-__device__ __forceinline__ void rodrigues_row(float nx, float ny, float nz, float theta, float* D) {
-    const float s = sinf(theta), c1 = 1.f - cosf(theta);
-    const float K[9] = {0.f, -nz, ny, nz, 0.f, -nx, -ny, nx, 0.f};
-    const float K2[9] = {-(ny * ny + nz * nz), nx * ny, nx * nz, nx * ny, -(nx * nx + nz * nz), ny * nz,
-                         nx * nz, ny * nz, -(nx * nx + ny * ny)};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            D[j * 3 + i] = ((i == j ? 1.f : 0.f) + s * K[i * 3 + j]) + c1 * K2[i * 3 + j];
-}
-
-// Rows of G made orthonormal (Gram-Schmidt, third row = first x second: det +1), as in mcg_shape_refine.hip.
-__device__ __forceinline__ void orthonormalise(float* G) {
-    float a[3] = {G[0], G[1], G[2]}, b[3] = {G[3], G[4], G[5]};
-    const float na = sqrtf((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) a[k] = a[k] / na;
-    const float ab = (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) b[k] = b[k] - ab * a[k];
-    const float nb = sqrtf((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2]);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) b[k] = b[k] / nb;
-    G[0] = a[0]; G[1] = a[1]; G[2] = a[2];
-    G[3] = b[0]; G[4] = b[1]; G[5] = b[2];
-    G[6] = a[1] * b[2] - a[2] * b[1];
-    G[7] = a[2] * b[0] - a[0] * b[2];
-    G[8] = a[0] * b[1] - a[1] * b[0];
-}
 
 struct ReliefShared {
     float x[MAX_ATOMS][3];        // the input rows

@@ -74,6 +74,9 @@ class Measured:
     interaction_terms: Optional[dict] = None      # g1, g2, rep, hyd, hb (the five sums) and n_rot
     receptor_hbonds: Optional[int] = None
     interaction_atom_scores: Optional[object] = None  # [n] fp32, host - or (batch [B,W], row, n), sliced on first read
+    interaction_score_before: Optional[float] = None  # E of the pose `optimise_pose` started from
+    pose_optimisation_rmsd: Optional[float] = None
+    pose_trials_kept: Optional[int] = None
 
 
 _UNMEASURED = Measured()          # shared by every record that carries no values: never written to
@@ -105,7 +108,10 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
     The interactions of a call with `interaction_scores` come as `interaction_score` [n] fp32, `interaction_terms` [n,6]
     fp32 (G1, G2, REP, HYD, HB, n_rot), `receptor_hbonds` [n] (negative: posing failed - the record gets None for all four)
     and `interaction_atom_scores` [n,W] fp32, +inf at and beyond a row's atoms (all four or none); a record's
-    `interaction_atom_scores` is left as (the one host copy, row, atom count) and sliced on first read."""
+    `interaction_atom_scores` is left as (the one host copy, row, atom count) and sliced on first read.
+    The pose optimisation of a call with `optimise_pose` comes as `interaction_score_before` [n] fp32,
+    `pose_optimisation_rmsd` [n] fp32 and `pose_trials_kept` [n] (negative: posing failed - the record gets None for all
+    three)."""
     hyd = {k: values.get(k) for k in ("hydrogen_coords", "hydrogen_parents", "atom_map", "kekule_bond_orders",
                                       "partial_charges", "hydrogen_charges", "canonical_order", "substructure_counts",
                                       "substructure_status", "substructure_first", "substructure_patterns",
@@ -168,6 +174,11 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
         cols["interaction_atom_scores"] = [(per_atom, b, k) for b, k in enumerate(counts)]
         for k in ("interaction_score", "interaction_terms", "receptor_hbonds", "interaction_atom_scores"):
             cols[k] = [None if gone else v for gone, v in zip(missing, cols[k])]
+    if "pose_trials_kept" in cols:
+        missing = [c < 0 for c in cols["pose_trials_kept"]]
+        for k in ("pose_trials_kept", "pose_optimisation_rmsd", "interaction_score_before"):
+            if k in cols:
+                cols[k] = [None if gone else v for gone, v in zip(missing, cols[k])]
     return [Measured(**{k: col[b] for k, col in cols.items()}) for b in range(n)]
 
 
@@ -417,6 +428,27 @@ class GeneratedMolecule:
         the call asked for `add_hydrogens` and passed a `receptor`; None otherwise, and where posing failed.
         `receptor_clashes` keeps counting the heavy atoms alone."""
         return self._measured.receptor_hydrogen_clashes
+
+    @property
+    def interaction_score_before(self) -> Optional[float]:
+        """`interaction_score` of the pose the pose optimisation of a call with `optimise_pose` started from
+        (`interaction_score` itself describes the returned coordinates; the same `n_rot` divides both); None in a call
+        without it, and where posing failed."""
+        return self._measured.interaction_score_before
+
+    @property
+    def pose_optimisation_rmsd(self) -> Optional[float]:
+        """How far, as a heavy-atom RMSD in A, the pose optimisation moved this molecule as a rigid body towards a lower
+        interaction score (`interactions.optimise_pose`: the package's own procedure - not a docking run, not AutoDock
+        Vina's local optimisation); 0.0 where it did not move.  None in a call without `optimise_pose`, and where posing
+        failed."""
+        return self._measured.pose_optimisation_rmsd
+
+    @property
+    def pose_trials_kept(self) -> Optional[int]:
+        """The trials of the pose optimisation that were kept; None in a call without `optimise_pose`, and where posing
+        failed."""
+        return self._measured.pose_trials_kept
 
     @property
     def relief_rmsd(self) -> Optional[float]:
@@ -794,7 +826,10 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                            interaction_score: Optional[torch.Tensor] = None,
                            interaction_terms: Optional[torch.Tensor] = None,
                            receptor_hbonds: Optional[torch.Tensor] = None,
-                           interaction_atom_scores: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
+                           interaction_atom_scores: Optional[torch.Tensor] = None,
+                           interaction_score_before: Optional[torch.Tensor] = None,
+                           pose_optimisation_rmsd: Optional[torch.Tensor] = None,
+                           pose_trials_kept: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
     (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
     (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records).
@@ -826,6 +861,9 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     `interaction_score[b]` / `interaction_terms[b]` [6] / `receptor_hbonds[b]` / `interaction_atom_scores[b]` [W] (+inf at
     and beyond the row's atoms): row b's receptor interactions as `postprocess.interactions` spells them (all four or
     none; negative hbonds: its pose failed, the record gets None for all four; None: a call without `interaction_scores`).
+    `interaction_score_before[b]` / `pose_optimisation_rmsd[b]` / `pose_trials_kept[b]`: row b's pose optimisation as
+    `postprocess.optimise_rows` spells it (negative trials kept: its pose failed, the record gets None for all three;
+    None: a call without `optimise_pose`).
     The value keywords are the fields of `Measured`
     and go to `measured_from_tensors`; a call with no ids and no values builds the views and nothing else."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
@@ -845,7 +883,9 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                   substructure_counts=substructure_counts, substructure_status=substructure_status,
                   substructure_first=substructure_first, substructure_patterns=substructure_patterns,
                   interaction_score=interaction_score, interaction_terms=interaction_terms,
-                  receptor_hbonds=receptor_hbonds, interaction_atom_scores=interaction_atom_scores)
+                  receptor_hbonds=receptor_hbonds, interaction_atom_scores=interaction_atom_scores,
+                  interaction_score_before=interaction_score_before, pose_optimisation_rmsd=pose_optimisation_rmsd,
+                  pose_trials_kept=pose_trials_kept)
     if sample_ids is None and all(v is None for v in values.values()):
         return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
     flags = valid.cpu().tolist()

@@ -222,6 +222,137 @@ def interaction_scores(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, at
                 n_rot=n_rot, types=types)
 
 
+# ----------------------------------------------------------------------------------------------- optimised pose
+OPTIMISE_STEPS = 64             # what `optimise_pose=True` stands for
+OPTIMISE_MAX_SHIFT = 2.0        # angstrom the centroid may move from where the walk started
+MAX_OPTIMISE_STEPS = mcg_receptor.MAX_RELIEF_STEPS     # csrc/mcg_pose_optimise.hip PO_MAX_STEPS
+TRACE_WIDTH = 24                # F[3], torque[3], s_r, s_t, G'[9], p'[3], W', evaluated, kept, W of the current pose
+OPTIMISE_REFUSAL_WITH_FINISHER = ("optimise_pose cannot be combined with a finisher (RDKit's or a custom one): the "
+                                  "values go onto the GeneratedMolecule records")
+
+
+def check_max_shift(value, name: str = "max_shift") -> float:
+    """`max_shift` as a float: a finite real number >= 0 (not a bool), else ValueError."""
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not math.isfinite(float(value)) or value < 0:
+        raise ValueError(f"{name} must be a finite real number >= 0, got {value!r}")
+    return float(value)
+
+
+@torch.no_grad()
+def optimise_typed(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, radii: torch.Tensor, types: torch.Tensor,
+                   steps: int = OPTIMISE_STEPS, max_shift: float = OPTIMISE_MAX_SHIFT, skip_tiles: bool = True,
+                   device=None, trace: bool = False) -> Dict[str, torch.Tensor]:
+    """The `mcg_receptor_optimise` launch itself, on ligand atoms that are already typed: `coords` [B,N,3], `n_nodes`
+    [B], `radii` [B,N] fp32 interaction radii, `types` [B,N] uint8 type bits; `receptor` as in `interaction_scores`.
+    Device tensors as the kernel writes them (include/mlconfgen_hip.h): coords [B,N,3], xform [B,12], stats [B,8],
+    gradient [B,6] and - `trace` - trace [B,steps,24].  B or N of 0 launches nothing and returns the rows as they came."""
+    from .cheminformatics import check_n_nodes
+    prepared = prepare_receptor(receptor)
+    steps = mcg_receptor.check_relief_steps(steps)
+    max_shift = check_max_shift(max_shift)
+    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
+    B, N = int(coords.shape[0]), int(coords.shape[1])
+    check_n_nodes(n_nodes, B, N)
+    if N > MAX_ATOMS or B > MAX_BATCH:
+        raise ValueError(f"pose optimisation takes at most {MAX_BATCH} molecules of at most {MAX_ATOMS} atoms, got "
+                         f"[{B}, {N}]")
+    for name, t, shape in (("radii", radii, (B, N)), ("types", types, (B, N))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+    x = coords.to(dev, torch.float32).contiguous()
+    out = torch.empty_like(x) if B > 0 and N > 0 else x.clone()
+    xform = torch.zeros(B, 12, device=dev)
+    stats = torch.zeros(B, 8, device=dev)
+    gradient = torch.zeros(B, 6, device=dev)
+    tr = torch.zeros(B, steps, TRACE_WIDTH, device=dev) if trace else None
+    if B > 0 and N > 0:
+        lig_r = radii.to(dev, torch.float32).contiguous()
+        lig_t = types.to(dev, torch.uint8).contiguous()
+        nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B).contiguous()
+        rec, rec_t = prepared.xyzr.to(dev), prepared.types.to(dev)
+        spheres = prepared.spheres.to(dev) if skip_tiles else None
+        _lib.check(_lib.lib().mcg_receptor_optimise(
+            _lib.dptr(x), _lib.dptr(lig_r), _lib.dptr(lig_t), _lib.dptr(nn), B, N, _lib.dptr(rec), _lib.dptr(rec_t),
+            int(rec.shape[0]), _lib.dptr(spheres), steps, max_shift, _lib.dptr(out), _lib.dptr(xform), _lib.dptr(stats),
+            _lib.dptr(gradient), _lib.dptr(tr), _lib.current_stream_ptr(dev)), "mcg_receptor_optimise")
+    else:
+        xform[:, 0] = xform[:, 4] = xform[:, 8] = 1.0
+    res = dict(coords=out, xform=xform, stats=stats, gradient=gradient)
+    if trace:
+        res["trace"] = tr
+    return res
+
+
+@torch.no_grad()
+def optimise_pose(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_numbers: torch.Tensor,
+                  bond_orders: torch.Tensor, steps: int = OPTIMISE_STEPS, max_shift: float = OPTIMISE_MAX_SHIFT,
+                  device=None, trace: bool = False) -> Dict[str, torch.Tensor]:
+    """Every molecule of the padded, posed coordinates `coords` [B,N,3] (`n_nodes` [B] real atoms, `atomic_numbers`
+    [B, >= N], `bond_orders` [B,N,N]) moved as a rigid body to where this module's interaction score with `receptor` is
+    lower: one perceive launch (`ligand_types`) and one `mcg_receptor_optimise` launch (`optimise_typed`).
+
+    THE PACKAGE'S OWN PROCEDURE ("Optimised pose"): NOT a docking run and NOT AutoDock Vina's local
+    optimisation.  Rigid body only: no torsions, no intramolecular term, no hydrogens, no global search.
+
+    Objective       W = -0.0356 G1 - 0.00516 G2 + 0.840 REP - 0.0351 HYD - 0.587 HB, the weighted sum of this module's
+                    five terms (`terms[:, 5]` of `interaction_scores`).  E = W / (1 + 0.0585 n_rot) divides by a positive
+                    constant of the molecule, so less W is less E and the walk needs no n_rot.
+    Force           on atom i: F_i = - sum_j (dW/dd) (x_i - y_j) / r over its counted pairs, direction 0 at r = 0; the
+                    branches decided on the same fp32 d as the terms: g1' = -8 d g1; g2' = -((d - 3) / 2) g2; rep' = 2 d
+                    where d < 0; hyd' = -1 on 0.5 < d < 1.5 (both hydrophobic); hb' = -1 / 0.7 on -0.7 < d < 0 (donor
+                    facing acceptor); 0 elsewhere.
+    Pose            x' = (x - c) @ G + p, c the atom centroid summed in atom order; G = I, p = c at the start, and the
+                    first evaluation reads the input rows as they came.  Torque about p: sum_i u_i x F_i, u_i = (x_i - c)
+                    @ G.
+    Walk            from s_r = 0.05 rad, s_t = 0.25 A.  A trial rotates by s_r about the torque (G' = G @ D, then
+                    Gram-Schmidt on its rows) and moves p by s_t along the net force; a zero or non-finite vector skips
+                    its part, both skipped ends the walk.  |p' - c| > `max_shift`: rejected unevaluated.  Else kept iff
+                    W' < W strictly (NaN never is).  Kept: both lengths x 1.2; rejected: x 0.5.  Ends after `steps`
+                    trials or once s_t < 2^-8 A.
+    Returns device tensors:
+      coords [B,N,3]      the kept pose - exactly the coordinates whose W was evaluated and kept (padded rows zero)
+      rotation [B,3,3], translation [B,3]   with coords = x @ rotation + translation (`postprocess.compose_pose` applies)
+      moved [B] bool      whether a trial was kept; an unmoved molecule returns its input bits, the identity and zero
+      weighted_before, weighted_after [B]   W at the input and at `coords`: the bits `interaction_scores` gives there
+      trials, kept [B]    int32: trials used and kept
+      rmsd [B]            heavy-atom RMSD between input and output
+      gradient [B,6]      net force and torque at the input pose
+      trace [B,steps,24]  with `trace`: one row per trial (include/mlconfgen_hip.h), for tests
+    A molecule without atoms or with a non-finite coordinate on a real atom keeps its rows and gets NaN (trials, kept: -1);
+    the others are unaffected.  A molecule's outputs depend on its own atoms and the receptor only.  Refused before any
+    device work: what `load_typed_receptor` refuses, `steps` outside 0..1024, `max_shift` negative or not finite, atom
+    counts outside [0, N], N > 64, B > MAX_BATCH, shapes that do not fit."""
+    from .cheminformatics import check_n_nodes
+    prepared = prepare_receptor(receptor)
+    steps = mcg_receptor.check_relief_steps(steps)
+    max_shift = check_max_shift(max_shift)
+    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
+    B, N = int(coords.shape[0]), int(coords.shape[1])
+    check_n_nodes(n_nodes, B, N)
+    if N > MAX_ATOMS or B > MAX_BATCH:
+        raise ValueError(f"pose optimisation takes at most {MAX_BATCH} molecules of at most {MAX_ATOMS} atoms, got "
+                         f"[{B}, {N}]")
+    z = torch.as_tensor(atomic_numbers)
+    bonds = torch.as_tensor(bond_orders)
+    if z.dim() != 2 or z.shape[0] != B or z.shape[1] < N:
+        raise ValueError(f"atomic_numbers must be [B, >= N] = [{B}, >= {N}], got {list(z.shape)}")
+    if bonds.dim() != 3 or bonds.shape[0] != B or bonds.shape[1] != bonds.shape[2] or bonds.shape[1] < N:
+        raise ValueError(f"bond_orders must be [B, >= N, >= N] = [{B}, >= {N}, >= {N}], got {list(bonds.shape)}")
+    types = torch.zeros(B, N, dtype=torch.uint8, device=dev)
+    if B > 0 and N > 0:
+        types = ligand_types(z[:, :N], bonds[:, :N, :N], n_nodes, dev)
+    out = optimise_typed(prepared, coords, n_nodes, interaction_radii(z[:, :N].to(dev)), types, steps, max_shift, True, dev,
+                         trace)
+    stats, xform = out["stats"], out["xform"]
+    ok = torch.isfinite(stats[:, 0])
+    count = lambda col: torch.where(ok, stats[:, col], torch.full_like(stats[:, col], -1.0)).to(torch.int32)
+    res = dict(coords=out["coords"], rotation=xform[:, :9].reshape(B, 3, 3), translation=xform[:, 9:],
+               moved=ok & (stats[:, 3] > 0), weighted_before=stats[:, 0], weighted_after=stats[:, 1], trials=count(2),
+               kept=count(3), rmsd=stats[:, 4], gradient=out["gradient"])
+    if trace:
+        res["trace"] = out["trace"]
+    return res
+
 # ----------------------------------------------------------------------------------------------- options
 def check_threshold(name: str, value) -> float:
     """An interaction-score threshold (`max_interaction_score`) as a float: a finite real number (not a bool), else

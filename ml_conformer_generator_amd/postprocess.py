@@ -7,8 +7,9 @@ Stages, in this order:
   tensors where no finisher runs, `measure_finished` on the finished Mols' heavy atoms where one does):
     1. pose onto the reference (`overlay`, refined with `refine_overlay`) - a conformer, or the solid of a
        `reference_shape` mesh, which also counts the posed atoms outside it; right behind it, with `relieve_clashes`, the
-       posed rows are moved out of their receptor contacts (`relieve_rows`), and everything below reads - and the call
-       returns - the relieved coordinates;
+       posed rows are moved out of their receptor contacts (`relieve_rows`) and, with `optimise_pose`, directly behind that to
+       where their interaction score is lower (`optimise_rows`), and everything below reads - and the call returns - the
+       coordinates so moved;
     2. shape score of the RETURNED coordinates (`shape_scores`, or implied by a shape selection);
     3. receptor contacts of the returned coordinates (`receptor`).
   BEHIND the gather, on the rows a rank returns (`return_records` / `return_finished`):
@@ -40,7 +41,7 @@ that arrive are already the parent fragments'; its four per-sample tensors (`ato
 `kekule_bond_orders`) ride through the gather and into each record's `Measured` like the strain energies do.
 
 The device work goes through the generator's seams (`_pose`, `_score`, `_pair`, `_receptor_coords`,
-`_relieve`, `_score_placed`, `_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, `_pharm_perceive`, `_pharm_score`,
+`_relieve`, `_optimise_pose`, `_score_placed`, `_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, `_pharm_perceive`, `_pharm_score`,
 `_add_hydrogens`, `_peoe_charges`, `_esp_score`, `_canonical_order`, `_match_substructures`, `_interaction_scores`),
 looked up on the instance at the time of the call.  The shape
 seams take the request's reference object; which kind it is - a conformer or a solid - is `cheminformatics`' business."""
@@ -114,6 +115,7 @@ class Request:
     scores_interactions: bool = False             # `interaction_scores`, or implied by `max_interaction_score`
     typed_receptor: Optional[tuple] = None        # `interactions.PreparedReceptor`: typed, sorted, with tile spheres, host
     max_interaction_score: Optional[float] = None
+    optimise_steps: int = 0                       # `optimise_pose`: trials of the pose optimisation, 0 = not optimised
 
     @property
     def selects_by_shape(self) -> bool:
@@ -183,7 +185,7 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
                   min_electrostatic_tanimoto: Optional[float] = None, partial_charges=False, smiles=False,
                   exclude_graphs=None, require_substructures=None, exclude_substructures=None,
                   substructure_counts=None, interaction_scores=False,
-                  max_interaction_score: Optional[float] = None) -> Request:
+                  max_interaction_score: Optional[float] = None, optimise_pose: Union[bool, int] = False) -> Request:
     """The public option keywords of a generation entry of `gen` as a `Request`: the shape options first, then the chemical
     ones (`top_k` / `min_shape_tanimoto` / `max_pairwise_tanimoto` imply the shape score, `max_chemical_tanimoto` the
     chemical one).  `reference_shape`: a watertight mesh in place of the reference conformer (`mesh.load_mesh`); the
@@ -217,6 +219,8 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     `overlay` -, which is typed, sorted and given its tile spheres here (`interactions.prepare_receptor`: host work, one
     warning where atoms lie outside the residue templates); a (coords, atomic_numbers, types) triple carries its own
     types.  `rank_by="interaction"` needs the score.  Refused with a finisher: the values go onto the records.
+    `optimise_pose`: `receptor.check_relief_steps` (True = `interactions.OPTIMISE_STEPS`); it needs a `receptor`, and
+    with it `overlay`, implies `interaction_scores` and is refused with a finisher likewise.
     Every refusal happens here, before any device work."""
     mcg_pharm.check_flag("smiles", smiles)
     if smiles and getattr(gen, "finisher", None) is not None:
@@ -243,7 +247,16 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
     if max_interaction_score is not None:
         mcg_interactions.check_threshold("max_interaction_score", max_interaction_score)
     mcg_interactions.check_rank_by(rank_by)
-    interact = interaction_scores or max_interaction_score is not None
+    optimise_steps = 0
+    if optimise_pose is not False:
+        optimise_steps = mcg_receptor.check_relief_steps(optimise_pose, "optimise_pose", lowest=1,
+                                                         if_true=mcg_interactions.OPTIMISE_STEPS)
+        if getattr(gen, "finisher", None) is not None:
+            raise ValueError(mcg_interactions.OPTIMISE_REFUSAL_WITH_FINISHER)
+        if receptor is None:
+            raise ValueError("optimise_pose needs a receptor: it moves the posed molecules to where their interaction "
+                             "score with it is lower")
+    interact = interaction_scores or max_interaction_score is not None or optimise_steps > 0
     if rank_by == "interaction" and not interact:
         raise ValueError("rank_by='interaction' needs interaction_scores (or max_interaction_score): it ranks by the "
                          "interaction score")
@@ -324,7 +337,7 @@ def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: O
             mcg_receptor.check_clear_of_reference(rec[0], common["reference"].coords)
             if interact:
                 common.update(scores_interactions=True, max_interaction_score=max_interaction_score, rank_by=rank_by,
-                              typed_receptor=mcg_interactions.prepare_receptor(receptor))
+                              typed_receptor=mcg_interactions.prepare_receptor(receptor), optimise_steps=optimise_steps)
         shape = dict(overlay=bool(overlay), scores_shape=bool(scoring), top_k=top_k,
                      min_shape_tanimoto=min_shape_tanimoto, max_pairwise_tanimoto=max_pairwise_tanimoto,
                      refine_steps=refine_steps, receptor=rec, max_receptor_clashes=max_receptor_clashes,
@@ -714,10 +727,19 @@ def interactions(gen, req: Request, res: dict) -> dict:
     dev = score.device
     posed = torch.isfinite(res["pose"]).all(dim=1).to(dev) & (hbonds >= 0)    # a failed pose is not in the receptor's frame
     real = torch.arange(atoms.shape[1], device=dev).view(1, -1) < res["n_nodes"].to(dev).reshape(-1, 1)
-    return dict(interaction_score=torch.where(posed, score, torch.full_like(score, float("nan"))),
-                interaction_terms=torch.cat([out["terms"][:, :5], out["n_rot"].to(dev, torch.float32).view(-1, 1)], dim=1),
-                receptor_hbonds=torch.where(posed, hbonds, torch.full_like(hbonds, -1)),
-                interaction_atom_scores=torch.where(real, atoms, torch.full_like(atoms, float("inf"))))
+    values = dict(interaction_score=torch.where(posed, score, torch.full_like(score, float("nan"))),
+                  interaction_terms=torch.cat([out["terms"][:, :5], out["n_rot"].to(dev, torch.float32).view(-1, 1)], dim=1),
+                  receptor_hbonds=torch.where(posed, hbonds, torch.full_like(hbonds, -1)),
+                  interaction_atom_scores=torch.where(real, atoms, torch.full_like(atoms, float("inf"))))
+    if req.optimise_steps:
+        # `optimise_rows` carried W of the pose the walk started from; E divides it as the kernel does: one rounded
+        # product, one sum, one division - so an unmoved row's two scores have the same bits
+        den = 1.0 + torch.tensor(mcg_interactions.ROTOR_WEIGHT, dtype=torch.float32, device=dev) * \
+            out["n_rot"].to(dev, torch.float32).clamp(min=0)
+        before = res["interaction_score_before"].to(dev, torch.float32) / den
+        unmoved = res["pose_trials_kept"].to(dev) == 0                            # the pose scored above IS the start
+        values["interaction_score_before"] = torch.where(unmoved, values["interaction_score"], before)
+    return values
 
 
 def _index(rows: Rows, device) -> torch.Tensor:
@@ -761,12 +783,42 @@ def relieve_rows(gen, req: Request, coords: torch.Tensor, n_nodes: torch.Tensor,
                 receptor_clashes_before=torch.where(posed, before, torch.full_like(before, -1)))
 
 
+def optimise_rows(gen, req: Request, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_numbers: torch.Tensor,
+                  bond_orders: torch.Tensor, pose: torch.Tensor, tanimoto: torch.Tensor) -> dict:
+    """The pose optimisation of posed, padded rows (`optimise_pose`): one `_optimise_pose` call over all rows against the
+    request's typed receptor and - for the rows it moved - the composed pose and the shape Tanimoto of the pose as placed
+    (`_score_placed`).  `pose` [B,12] (a row with a non-finite entry: posing failed, the row is not in the receptor's frame
+    and is left alone), `tanimoto` [B] the pose's score.  Returns tensors on the device of the walk's result: `coords`,
+    `pose`, `overlay_tanimoto` (an unmoved row keeps every bit of what came in), `moved` [B] bool, `rotation` /
+    `translation` of the move itself, `pose_optimisation_rmsd` (0 where nothing moved, NaN where posing failed),
+    `pose_trials_kept` (-1 where posing failed) and `interaction_score_before`: W, the weighted sum, of the pose the walk
+    started from (NaN where posing failed) - `interactions` divides it by the rotor term behind the gather, where n_rot is
+    counted."""
+    out = gen._optimise_pose(req.typed_receptor, coords, n_nodes, atomic_numbers, bond_orders, req.optimise_steps)
+    dev = out["coords"].device
+    x, pose, tanimoto = coords.to(dev, torch.float32), pose.to(dev, torch.float32), tanimoto.to(dev, torch.float32)
+    kept = out["kept"].to(dev)
+    posed = torch.isfinite(pose).all(dim=1) & (kept >= 0)
+    moved = out["moved"].to(dev) & posed
+    width = x.shape[1]
+    new_x = torch.where(moved.view(-1, 1, 1), out["coords"][:, :width], x)
+    rescored = gen._score_placed(req.reference, new_x, n_nodes).to(dev)
+    nan = torch.full_like(out["rmsd"], float("nan"))
+    return dict(coords=new_x, moved=moved, rotation=out["rotation"], translation=out["translation"],
+                pose=torch.where(moved.view(-1, 1), compose_pose(pose, out["rotation"], out["translation"]), pose),
+                overlay_tanimoto=torch.where(moved, rescored, tanimoto),
+                interaction_score_before=torch.where(posed, out["weighted_before"], nan),
+                pose_optimisation_rmsd=torch.where(posed, torch.where(moved, out["rmsd"], torch.zeros_like(nan)), nan),
+                pose_trials_kept=torch.where(posed, kept, torch.full_like(kept, -1)))
+
+
 # ----------------------------------------------------------------------------------------------- without a finisher
 def measure_tensors(gen, req: Request, res: dict) -> dict:
     """Stages 1-3 on one shard's result tensors.  `res` with `x` posed and the per-sample tensors `overlay_tanimoto`,
     `pose`, `shape_tanimoto`, `receptor_clashes` (-1 where posing failed), `receptor_max_overlap` (NaN there), - posed
     into a mesh - `atoms_outside` and - relieved - `relief_rmsd` (NaN where posing failed) and `receptor_clashes_before`
-    (-1 there) added, as far as the call asked: the spellings `handoff.measured_from_tensors` reads,
+    (-1 there) and - optimised - `interaction_score_before`, `pose_optimisation_rmsd` (NaN where posing failed) and
+    `pose_trials_kept` (-1 there) added, as far as the call asked: the spellings `handoff.measured_from_tensors` reads,
     which cross the tensor gather."""
     if req.overlay:
         ov = gen._pose(req.reference, res["x"], res["n_nodes"], req.refine_steps)
@@ -778,6 +830,12 @@ def measure_tensors(gen, req: Request, res: dict) -> dict:
         rel = relieve_rows(gen, req, res["x"], res["n_nodes"], res["elements"], res["pose"], res["overlay_tanimoto"])
         res = dict(res, x=rel["coords"], pose=rel["pose"], overlay_tanimoto=rel["overlay_tanimoto"],
                    relief_rmsd=rel["relief_rmsd"], receptor_clashes_before=rel["receptor_clashes_before"])
+    if req.optimise_steps:
+        opt = optimise_rows(gen, req, res["x"], res["n_nodes"], res["elements"], res["bond"], res["pose"],
+                            res["overlay_tanimoto"])
+        res = dict(res, x=opt["coords"], pose=opt["pose"], overlay_tanimoto=opt["overlay_tanimoto"],
+                   interaction_score_before=opt["interaction_score_before"],
+                   pose_optimisation_rmsd=opt["pose_optimisation_rmsd"], pose_trials_kept=opt["pose_trials_kept"])
     if req.scores_shape:
         res = dict(res, shape_tanimoto=gen._score(req.reference, res["x"], res["n_nodes"]))
     if req.receptor is not None:
