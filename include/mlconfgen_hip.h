@@ -370,7 +370,9 @@ int mcg_ifm_merge(const float* ff_x, const float* ff_h, int n_ff, const float* g
  * (candidate, rotation) pair of `evaluate_samples` (cheminformatics/pipeline.py:64-85).
  * ref[n_ref,3]; cand[B,N,3] with n_nodes[B] real atoms; rot[R,9] row-major matrices applied as coord @ M;
  * axes[3,n] = the three linspace axes of the n^3 grid (built by the caller exactly as the reference's
- * `Grid`); f_scratch[n^3]; score[B*R]. */
+ * `Grid`); f_scratch[n^3]; score[B*R].  A row is scored on its first n_nodes[b] atoms, clamped to [0, N].
+ * MCG_ERR_ARG, nothing launched: a null buffer, n_ref outside 1..64, B < 1, N outside 1..64 (a wider row would be scored on
+ * its first 64 atoms only), R < 1, n < 2. */
 int mcg_shape_tanimoto(const float* ref, int n_ref, const float* cand, const int32_t* n_nodes_dev, int B, int N,
                        const float* rot, int R, const float* axes, int n, float alpha, float amplitude,
                        float* f_scratch, float* score, void* stream);
@@ -561,7 +563,7 @@ int mcg_fingerprint_pair_tanimoto(const uint32_t* fp, int B, float* out, void* s
  *                       the density launch would have written (their f_scratch), the same bits.
  * MCG_ERR_ARG, nothing launched: a null required buffer, F outside 1..MCG_MESH_MAX_FACES, P outside 1..MCG_MESH_MAX_POINTS,
  * n outside 2..MCG_MESH_MAX_N, both or neither of points / axes, partial_ws NULL when mcg_mesh_splits(F) > 1, B < 1,
- * N outside 1..64 (atoms_outside, overlay_field; B * 64 <= MCG_MESH_MAX_POINTS), N < 1 or R < 1 (tanimoto_field).
+ * N outside 1..64 (atoms_outside, overlay_field, tanimoto_field; B * 64 <= MCG_MESH_MAX_POINTS), R < 1 (tanimoto_field).
  * mcg_mesh_splits returns 0 for an F outside the range. */
 #define MCG_MESH_MAX_FACES 1048576
 #define MCG_MESH_MAX_POINTS 16777216

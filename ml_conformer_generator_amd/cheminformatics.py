@@ -66,10 +66,13 @@ def shape_tanimoto_batch(ref_coord: torch.Tensor, cand_coords: torch.Tensor, n_n
                          device=None, n: int = 40, alpha: float = ALPHA, amplitude: float = AMPLITUDE
                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """scores[B,4] for the orientations (identity, pi about x, y, z), the best score per candidate and its
-    orientation index - the search `evaluate_samples` runs one candidate at a time."""
+    orientation index - the search `evaluate_samples` runs one candidate at a time.  A padded width above
+    MAX_SCORED_ATOMS is refused with ValueError before any device work (the kernel holds 64 atoms per row)."""
+    B, N, _ = cand_coords.shape
+    if N > MAX_SCORED_ATOMS:
+        raise ValueError(f"the shape kernels take at most {MAX_SCORED_ATOMS} atoms per molecule, got a padded width of {N}")
     dev = torch.device(device if device is not None else (cand_coords.device if cand_coords.is_cuda else "cuda:0"))
     ref = ref_coord.to(torch.float32).cpu().contiguous()
-    B, N, _ = cand_coords.shape
     axes = _grid_axes(ref, n)
     ref_d, cand_d = ref.to(dev), cand_coords.to(dev, torch.float32).contiguous()
     nn = n_nodes.to(dev, torch.int32).contiguous()
@@ -191,7 +194,12 @@ def evaluate_shape(reference_coord: torch.Tensor, sample_coords: torch.Tensor, n
                    ) -> Tuple[torch.Tensor, List[dict]]:
     """Shape half of `evaluate_samples` (cheminformatics/pipeline.py:30-85) for heavy-atom coordinates:
     the reference in its principal frame, and per sample the best of the four orientations with its aligned
-    coordinates.  `sample_coords` [B,N,3] padded, `n_nodes` [B]."""
+    coordinates.  `sample_coords` [B,N,3] padded, `n_nodes` [B].  N above MAX_SCORED_ATOMS is refused with ValueError
+    before any device work, as `shape_tanimoto_batch` refuses it: the grid kernel would score a wider sample on its first
+    64 atoms."""
+    if int(sample_coords.shape[1]) > MAX_SCORED_ATOMS:
+        raise ValueError(f"the shape kernels take at most {MAX_SCORED_ATOMS} atoms per molecule, got a padded width of "
+                         f"{int(sample_coords.shape[1])}")
     dev = torch.device(device if device is not None else (sample_coords.device if sample_coords.is_cuda else "cuda:0"))
     ref = reference_coord.to(torch.float32)
     ref = ref - ref.mean(0)                                                             # :38-39

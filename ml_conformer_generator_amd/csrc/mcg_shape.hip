@@ -155,8 +155,9 @@ extern "C" int mcg_shape_tanimoto(const float* ref, int n_ref, const float* cand
                                   const float* rot, int R, const float* axes, int n, float alpha, float amplitude,
                                   float* f_scratch, float* score, void* stream) {
     if (!ref || !cand || !n_nodes_dev || !rot || !axes || !f_scratch || !score || n_ref < 1 || n_ref > MAX_ATOMS ||
-        B < 1 || N < 1 || R < 1 || n < 2) {
-        mcg_set_error("mcg_shape_tanimoto: bad arguments (1 <= n_ref <= %d)", MAX_ATOMS);
+        B < 1 || N < 1 || N > MAX_ATOMS || R < 1 || n < 2) {
+        mcg_set_error("mcg_shape_tanimoto: bad arguments (non-null buffers, 1 <= n_ref <= %d, B >= 1, 1 <= N <= %d, R >= 1, "
+                      "n >= 2)", MAX_ATOMS, MAX_ATOMS);
         return MCG_ERR_ARG;
     }
     hipStream_t s = (hipStream_t)stream;
@@ -201,8 +202,9 @@ extern "C" int mcg_shape_overlay(const float* ref_frame, int n_ref, const float*
 extern "C" int mcg_shape_tanimoto_field(const float* f, const float* cand, const int32_t* n_nodes_dev, int B, int N,
                                         const float* rot, int R, const float* axes, int n, float alpha, float amplitude,
                                         float* score, void* stream) {
-    if (!f || !cand || !n_nodes_dev || !rot || !axes || !score || B < 1 || N < 1 || R < 1 || n < 2) {
-        mcg_set_error("mcg_shape_tanimoto_field: bad arguments (non-null buffers, B >= 1, N >= 1, R >= 1, n >= 2)");
+    if (!f || !cand || !n_nodes_dev || !rot || !axes || !score || B < 1 || N < 1 || N > MAX_ATOMS || R < 1 || n < 2) {
+        mcg_set_error("mcg_shape_tanimoto_field: bad arguments (non-null buffers, B >= 1, 1 <= N <= %d, R >= 1, n >= 2)",
+                      MAX_ATOMS);
         return MCG_ERR_ARG;
     }
     hipLaunchKernelGGL(k_shape_overlap, dim3(B * R), dim3(256), 0, (hipStream_t)stream, f, cand, n_nodes_dev, N, rot, R, axes,
