@@ -210,10 +210,24 @@ int mcg_egnn_block_debug(const mcg_egnn* m, mcg_plan* p, int block, float* h_io,
 
 /* Debug hooks: one GCL layer (egnn.py:70-85) on compact arrays (result stays in the plan), and a
  * copy-out of the plan's internal buffers: which = 0 h[M][432], 1 pab[M][864], 2 agg[M][432],
- * 3 node-MLP hidden[M][432], 4 x[M][4]. */
+ * 3 node-MLP hidden[M][432], 4 x[M][4], 5 pab as the bf16 mode's edge_mt = 4 plans store it: piece-major
+ * [part a | b][k-block 0..13][piece 0..7][M][4], M * 896 floats (which = 1 copies the first M * 864 of the same buffer,
+ * which is the whole of it in the row-major layout of every other plan). */
 int mcg_egnn_gcl_debug(const mcg_egnn* m, mcg_plan* p, int layer, const float* h_in, const float* x_in,
                        const float* x0, void* stream);
 int mcg_plan_peek(const mcg_plan* p, int which, float* dst, void* stream);
+/* Test hooks (additions, ABI version unchanged).  mcg_egnn_gcl_debug_ex: keep_agg = 1 is mcg_egnn_gcl_debug; keep_agg = 0
+ * runs the layer as a denoiser call does - the aggregate is gathered by the node GEMM (agg is NOT materialised) and, where
+ * MCG_OPT_NODE_FUSED and the plan allow it, the node phase is the one fused launch, which writes no hidden buffer and leaves
+ * the NEXT layer's first-layer projections in pab.  ran_host[2] (may be null) = {fused launch ran, pab holds the next layer's
+ * projections}.  mcg_egnn_equiv_debug: the coordinate layer of `block` (egnn.py:111-149) on the same compact arrays; apply = 0
+ * applies a pending update by a launch of its own, apply = 1 (block + 1 < n_blocks) has it consumed as the side job of the next
+ * block's first first-layer GEMM, as a denoiser call does - pab then holds that layer's projections; x' is peek 4.
+ * Plans cut into molecule ranges are refused; argument errors return MCG_ERR_ARG without a launch. */
+int mcg_egnn_gcl_debug_ex(const mcg_egnn* m, mcg_plan* p, int layer, const float* h_in, const float* x_in,
+                          const float* x0, int keep_agg, int32_t* ran_host, void* stream);
+int mcg_egnn_equiv_debug(const mcg_egnn* m, mcg_plan* p, int block, const float* h_in, const float* x_in,
+                         const float* x0, int apply, void* stream);
 /* Test hook: the kernels a denoiser call of model `m` on plan `p` would run, read from the same routing function the
  * launchers use (keep_agg != 0: as mcg_egnn_gcl_debug runs a layer).  Host only: nothing is launched, nothing is written
  * on the device.  A plan cut into molecule ranges reports its first range.  info_host[8] =

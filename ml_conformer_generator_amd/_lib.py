@@ -39,6 +39,8 @@ SIGNATURES: Dict[str, tuple] = {
     "mcg_egnn_block_debug": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "mcg_egnn_gcl_debug": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "mcg_plan_peek": (_i, [_vp, _i, _vp, _vp]),
+    "mcg_egnn_gcl_debug_ex": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "mcg_egnn_equiv_debug": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "mcg_debug_route": (_i, [_vp, _vp, _i, _vp]),
     "mcg_bench_edge": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "mcg_bench_edge_incall": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),

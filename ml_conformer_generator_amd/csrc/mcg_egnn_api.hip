@@ -573,11 +573,8 @@ int mcg_debug_route(const mcg_egnn* m, const mcg_plan* pl, int keep_agg, int32_t
     return MCG_OK;
 }
 
-int mcg_egnn_gcl_debug(const mcg_egnn* m, mcg_plan* pl, int layer, const float* h_in, const float* x_in,
-                       const float* x0, void* stream) {
-    if (!m || !pl || layer < 0 || layer >= 2 * m->n_blocks) return MCG_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    mcg_plan_mark_guard done{pl, s};
+// compact h[M][420], x[M][3], x0[M][3] into the plan's padded state (padding zero), nothing pending
+static int stage_compact(mcg_plan* pl, const float* h_in, const float* x_in, const float* x0, hipStream_t s) {
     MCG_HIP(hipMemsetAsync(pl->h, 0, (size_t)pl->M * HP * sizeof(float), s));
     MCG_HIP(hipMemsetAsync(pl->x, 0, (size_t)pl->M * 4 * sizeof(float), s));
     MCG_HIP(hipMemsetAsync(pl->x0, 0, (size_t)pl->M * 4 * sizeof(float), s));
@@ -586,7 +583,61 @@ int mcg_egnn_gcl_debug(const mcg_egnn* m, mcg_plan* pl, int layer, const float* 
     MCG_HIP(hipMemcpy2DAsync(pl->x0, 4 * sizeof(float), x0, 3 * sizeof(float), 3 * sizeof(float), pl->M, hipMemcpyDeviceToDevice, s));
     pl->x_pending = false;
     pl->pab_ready = false;
+    return MCG_OK;
+}
+
+int mcg_egnn_gcl_debug(const mcg_egnn* m, mcg_plan* pl, int layer, const float* h_in, const float* x_in,
+                       const float* x0, void* stream) {
+    if (!m || !pl || layer < 0 || layer >= 2 * m->n_blocks) return MCG_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    mcg_plan_mark_guard done{pl, s};
+    if (int e = stage_compact(pl, h_in, x_in, x0, s)) return e;
     return run_gcl(m, pl, layer, s, /*keep_agg=*/true);      // (agg materialised for mcg_plan_peek)
+}
+
+// Test hook: mcg_egnn_gcl_debug with the choice of keep_agg.  keep_agg = 0 runs the layer as a denoiser call does: route()
+// picks the aggregate source (the gathering node GEMM) and, where MCG_OPT_NODE_FUSED and the plan allow it, the fused node launch,
+// which also writes the NEXT layer's first-layer projections into pab.  ran_host[2] = {fused launch ran, pab holds the next
+// layer's projections}.  The plan is left with nothing pending.
+int mcg_egnn_gcl_debug_ex(const mcg_egnn* m, mcg_plan* pl, int layer, const float* h_in, const float* x_in,
+                          const float* x0, int keep_agg, int32_t* ran_host, void* stream) {
+    if (!m || !pl || !h_in || !x_in || !x0) { mcg_set_error("mcg_egnn_gcl_debug_ex: null argument"); return MCG_ERR_ARG; }
+    if (layer < 0 || layer >= 2 * m->n_blocks || (keep_agg != 0 && keep_agg != 1)) {
+        mcg_set_error("mcg_egnn_gcl_debug_ex: layer %d / keep_agg %d out of range", layer, keep_agg);
+        return MCG_ERR_ARG;
+    }
+    if (!pl->subs.empty()) { mcg_set_error("mcg_egnn_gcl_debug_ex: the plan is cut into molecule ranges (create it with n_ranges = 1)"); return MCG_ERR_ARG; }
+    hipStream_t s = (hipStream_t)stream;
+    mcg_plan_mark_guard done{pl, s};
+    if (int e = stage_compact(pl, h_in, x_in, x0, s)) return e;
+    const int rc = run_gcl(m, pl, layer, s, keep_agg != 0);
+    if (ran_host) { ran_host[0] = route(m, pl, keep_agg != 0).fused ? 1 : 0; ran_host[1] = pl->pab_ready ? 1 : 0; }
+    pl->pab_ready = false;
+    return rc;
+}
+
+// Test hook: the coordinate layer of one block (egnn.py:111-149) on compact arrays, as run_block runs it.  apply = 0: a
+// pending update is applied by k_coord_apply2; apply = 1: it is consumed the way a denoiser call consumes it, by the first-layer
+// GEMM of the next block's first GCL layer (side job; pab then holds THAT layer's projections of h).  Afterwards pab (peek 1 / 5)
+// and x' (peek 4) are readable.
+int mcg_egnn_equiv_debug(const mcg_egnn* m, mcg_plan* pl, int block, const float* h_in, const float* x_in,
+                         const float* x0, int apply, void* stream) {
+    if (!m || !pl || !h_in || !x_in || !x0) { mcg_set_error("mcg_egnn_equiv_debug: null argument"); return MCG_ERR_ARG; }
+    if (block < 0 || block >= m->n_blocks || (apply != 0 && apply != 1) || (apply == 1 && block + 1 >= m->n_blocks)) {
+        mcg_set_error("mcg_egnn_equiv_debug: block %d / apply %d out of range (apply = 1 needs a next block)", block, apply);
+        return MCG_ERR_ARG;
+    }
+    if (!pl->subs.empty()) { mcg_set_error("mcg_egnn_equiv_debug: the plan is cut into molecule ranges (create it with n_ranges = 1)"); return MCG_ERR_ARG; }
+    hipStream_t s = (hipStream_t)stream;
+    mcg_plan_mark_guard done{pl, s};
+    if (int e = stage_compact(pl, h_in, x_in, x0, s)) return e;
+    if (int e = run_equiv(m, pl, block, s)) return e;
+    if (apply == 1) {
+        if (int e = run_pab(m, pl, route(m, pl, false), m->gcl_edge[2 * (block + 1)], s)) return e;
+    }
+    if (int e = apply_pending_x(pl, s)) return e;         // (apply = 1: nothing is pending any more)
+    pl->pab_ready = false;
+    return MCG_OK;
 }
 
 // Measurement hook: `calls` whole denoiser calls issued as PLAIN launches (no graph) on `stream` with every edge launch
@@ -644,14 +695,7 @@ int mcg_egnn_block_debug(const mcg_egnn* m, mcg_plan* pl, int block, float* h_io
     if (!m || !pl || block < 0 || block >= m->n_blocks) return MCG_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     mcg_plan_mark_guard done{pl, s};
-    MCG_HIP(hipMemsetAsync(pl->h, 0, (size_t)pl->M * HP * sizeof(float), s));
-    MCG_HIP(hipMemsetAsync(pl->x, 0, (size_t)pl->M * 4 * sizeof(float), s));
-    MCG_HIP(hipMemsetAsync(pl->x0, 0, (size_t)pl->M * 4 * sizeof(float), s));
-    MCG_HIP(hipMemcpy2DAsync(pl->h, HP * sizeof(float), h_io, H * sizeof(float), H * sizeof(float), pl->M, hipMemcpyDeviceToDevice, s));
-    MCG_HIP(hipMemcpy2DAsync(pl->x, 4 * sizeof(float), x_io, 3 * sizeof(float), 3 * sizeof(float), pl->M, hipMemcpyDeviceToDevice, s));
-    MCG_HIP(hipMemcpy2DAsync(pl->x0, 4 * sizeof(float), x0, 3 * sizeof(float), 3 * sizeof(float), pl->M, hipMemcpyDeviceToDevice, s));
-    pl->x_pending = false;
-    pl->pab_ready = false;
+    if (int e = stage_compact(pl, h_io, x_io, x0, s)) return e;
     if (int e = run_block(m, pl, block, s)) return e;
     if (int e = apply_pending_x(pl, s)) return e;
     MCG_HIP(hipMemcpy2DAsync(h_io, H * sizeof(float), pl->h, HP * sizeof(float), H * sizeof(float), pl->M, hipMemcpyDeviceToDevice, s));

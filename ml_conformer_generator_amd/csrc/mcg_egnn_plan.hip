@@ -242,7 +242,8 @@ int mcg_plan_info(const mcg_plan* p, int32_t* info /*[8]*/) {
 }
 
 // Debug/test hook: copy one of the plan's internal buffers out.  which: 0 h[M][432], 1 pab[M][864], 2 agg[M][432],
-// 3 t1[M][432], 4 x[M][4]
+// 3 t1[M][432], 4 x[M][4], 5 pab in the blocked layout of bf16 edge_mt = 4 plans, whole: [M * 896] (which = 1 stops at
+// M * 864 floats, short of the last k-block of the Pb part)
 int mcg_plan_peek(const mcg_plan* pl, int which, float* dst, void* stream) {
     if (!pl || !dst) return MCG_ERR_ARG;
     mcg_plan_mark_guard done{pl, (hipStream_t)stream};
@@ -253,6 +254,7 @@ int mcg_plan_peek(const mcg_plan* pl, int which, float* dst, void* stream) {
         case 2: src = pl->agg; n = (size_t)pl->M * HP; break;
         case 3: src = pl->t1; n = (size_t)pl->M * HP; break;
         case 4: src = pl->x; n = (size_t)pl->M * 4; break;
+        case 5: src = pl->pab; n = (size_t)pl->M * MCG_PAB_BLOCKED_FLOATS; break;
         default: return MCG_ERR_ARG;
     }
     MCG_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));

@@ -279,6 +279,35 @@ class EGNNDynamics(torch.nn.Module):
         out["h_out"], out["agg"], out["hidden"] = out["h_out"][:, :420], out["agg"][:, :420], out["hidden"][:, :420]
         return out
 
+    def _peek(self, plan: BatchPlan, which: int, width: int) -> torch.Tensor:
+        buf = torch.empty(plan.n_real_nodes, width, device=self.device, dtype=torch.float32)
+        _lib.check(_lib.lib().mcg_plan_peek(plan.handle, which, _lib.dptr(buf), _lib.current_stream_ptr(self.device)),
+                   "mcg_plan_peek")
+        return buf
+
+    def gcl_debug_ex(self, plan: BatchPlan, layer: int, h: torch.Tensor, x: torch.Tensor, x0: torch.Tensor, keep_agg: bool):
+        """`gcl_debug` with the choice of `keep_agg` (`mcg_egnn_gcl_debug_ex`).  keep_agg=False runs the layer as a denoiser
+        call does.  Returns the plan's buffers PADDED and raw: h_out [M,432], pab_raw [M*896] (row-major [M][864] in its first
+        M*864 floats, or piece-major on bf16 edge_mt = 4 plans), agg [M,432] (only written with keep_agg), hidden [M,432]
+        (not written by the fused launch), and the flags fused / pab_is_next (pab holds the NEXT layer's projections)."""
+        f32 = dict(device=self.device, dtype=torch.float32)
+        h, x, x0 = h.to(**f32).contiguous(), x.to(**f32).contiguous(), x0.to(**f32).contiguous()
+        ran = (C.c_int32 * 2)()
+        _lib.check(_lib.lib().mcg_egnn_gcl_debug_ex(self.handle, plan.handle, int(layer), _lib.dptr(h), _lib.dptr(x), _lib.dptr(x0),
+                                                    1 if keep_agg else 0, ran, _lib.current_stream_ptr(self.device)),
+                   "mcg_egnn_gcl_debug_ex")
+        return dict(h_out=self._peek(plan, 0, 432), pab_raw=self._peek(plan, 5, 896).reshape(-1), agg=self._peek(plan, 2, 432),
+                    hidden=self._peek(plan, 3, 432), fused=bool(ran[0]), pab_is_next=bool(ran[1]), inputs=(h, x, x0))
+
+    def equiv_debug(self, plan: BatchPlan, block: int, h: torch.Tensor, x: torch.Tensor, x0: torch.Tensor, apply: int):
+        """The coordinate layer of one block on compact arrays (`mcg_egnn_equiv_debug`): x_out [M,4] (column 3 is padding) and
+        pab_raw [M*896] - the coordinate layer's projections (apply=0) or those of the next block's first GCL layer (apply=1)."""
+        f32 = dict(device=self.device, dtype=torch.float32)
+        h, x, x0 = h.to(**f32).contiguous(), x.to(**f32).contiguous(), x0.to(**f32).contiguous()
+        _lib.check(_lib.lib().mcg_egnn_equiv_debug(self.handle, plan.handle, int(block), _lib.dptr(h), _lib.dptr(x), _lib.dptr(x0),
+                                                   int(apply), _lib.current_stream_ptr(self.device)), "mcg_egnn_equiv_debug")
+        return dict(x_out=self._peek(plan, 4, 4), pab_raw=self._peek(plan, 5, 896).reshape(-1), inputs=(h, x, x0))
+
     def __del__(self):
         try:
             self._plans.clear()

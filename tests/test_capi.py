@@ -91,5 +91,12 @@ def test_header_is_plain_c_and_argument_checks_of_the_new_entry_points(tmp_path)
     h = _lib.lib()
     assert h.mcg_handoff_ex(None, None, None, 4, 19, 1.3, None, None, None, None, None, None, None, None) != 0
     assert b"mcg_handoff_ex" in h.mcg_last_error()
+    # the bf16 stage pins' debug hooks: null handles / arrays are refused before anything is launched
+    ran = (ctypes.c_int32 * 2)()
+    assert h.mcg_egnn_gcl_debug_ex(None, None, 6, None, None, None, 0, ran, None) != 0
+    assert b"mcg_egnn_gcl_debug_ex" in h.mcg_last_error()
+    assert h.mcg_egnn_equiv_debug(None, None, 3, None, None, None, 0, None) != 0
+    assert b"mcg_egnn_equiv_debug" in h.mcg_last_error()
+    assert h.mcg_plan_peek(None, 5, None, None) != 0
     counts = (ctypes.c_int64 * 32)()
     assert h.mcg_debug_gemm_launches(counts, 1) == 0 and all(v >= 0 for v in counts)

@@ -1063,13 +1063,17 @@ def test_generator_fixed_fragment_modes(gcn_sd, ifm):
 
 # ------------------------------------------------------------------------------- bf16 operand mode (configs[4])
 def _bf(x):
-    return x.to(torch.bfloat16).to(torch.float32)
+    from bf16_ref import bf16_rne          # the rounding points of the mode live in tests/bf16_ref.py
+    return bf16_rne(x)
 
 
-def _egnn_dynamics_bf16_emulated(sd, t, xh, node_mask, edge_mask, context):
+def _egnn_dynamics_bf16_emulated(sd, t, xh, node_mask, edge_mask, context, rounded_aggregate=False):
     """fp32 torch emulation of what the bf16 mode computes: the reference network with the OPERANDS of
     every hidden-size contraction rounded to bf16 (fp32 accumulate) and the first edge layer in its
-    factorised form - a yardstick that separates 'bf16 rounding' from 'kernel bug'."""
+    factorised form - a yardstick that separates 'bf16 rounding' from 'kernel bug'.  The rounding points are those of
+    tests/bf16_ref.py, stage for stage, on the oracle's dense edge list.  `rounded_aggregate`: the gate-scaled sum as the 64-row
+    kernel of edge_mt = 4 plans forms it - one more bf16 contraction, rnd(gate) rnd(m) - instead of the exact fp32 sum of the
+    16-row kernel."""
     import torch.nn.functional as F
     from oracle import egnn_oracle as EO
     B, N, _ = xh.shape
@@ -1101,7 +1105,7 @@ def _egnn_dynamics_bf16_emulated(sd, t, xh, node_mask, edge_mask, context):
             p = bp + gname
             m = edge_mlp(p, "edge_mlp", h, d2)
             gate = torch.sigmoid(F.linear(m, sd[p + "att_mlp.0.weight"], sd[p + "att_mlp.0.bias"]))
-            agg = EO.segment_sum(m * gate * em, row, h.size(0))
+            agg = EO.segment_sum((_bf(m) * _bf(gate) if rounded_aggregate else m * gate) * em, row, h.size(0))
             hid = F.silu(lin16(torch.cat([h, agg], 1), sd[p + "node_mlp.0.weight"], sd[p + "node_mlp.0.bias"]))
             h = (h + lin16(hid, sd[p + "node_mlp.2.weight"], sd[p + "node_mlp.2.bias"])) * nm
         p = bp + "gcl_equiv."
@@ -1135,6 +1139,13 @@ def test_bf16_mode_vs_emulation_and_fp32(edm_sd):
     ref = EO.egnn_dynamics(edm_sd, t, z, nm, em, ctx)
     sc = float(ref.abs().max())
     e_emu = float((out - emu).abs().max()) / sc
+    # the 64-row kernel against ITS rounding model (rounded aggregate), beside the exact-aggregate emulation held above
+    emu_r = _egnn_dynamics_bf16_emulated(edm_sd, t, z, nm, em, ctx, rounded_aggregate=True)
+    e_emu_r = float((out - emu_r).abs().max()) / sc
+    e_mt1 = float((out_mt1 - emu).abs().max()) / float(emu.abs().max())
+    print(f"\nBF16-WHOLE-CALL 64-row kernel vs rounded-aggregate emulation {e_emu_r:.3e}, vs exact-aggregate emulation {e_emu:.3e}; "
+          f"16-row kernel vs exact-aggregate emulation {e_mt1:.3e} (of max|out|)")
+    assert e_emu_r < 3e-3, (e_emu_r, e_emu)
     e_ref = float((out - ref).abs().max()) / sc
     e_floor = float((emu - ref).abs().max()) / sc            # what bf16 operand rounding itself costs
     # stated bf16 tolerance: 3e-3 of max|out| vs the bf16-operand emulation (accumulation-order +

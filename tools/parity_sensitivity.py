@@ -18,7 +18,11 @@ weight gains / input scale) until this script exits 0.
 `--gcn` does the same for the bond-prediction GCN (AdjMatSeer): planted mistakes in tests/gcn_ref.py against the per-stage
 tolerances of tests/test_gcn_gpu.py; its output is committed as profiles/gcn_parity_sensitivity.txt.
 
-Usage: python tools/parity_sensitivity.py [--fast | --gcn]      (exit code 1 on any blind spot)
+`--bf16-stages` prints the mutation table of the bf16 operand mode's stage pins (tests/bf16_cases.py: planted mistakes in the
+rounding model tests/bf16_ref.py, scored under the acceptance rule of tests/test_bf16_stages_gpu.py); its output is committed as
+profiles/bf16_stage_sensitivity.txt.
+
+Usage: python tools/parity_sensitivity.py [--fast | --gcn | --bf16-stages]      (exit code 1 on any blind spot)
 """
 import argparse
 import os
@@ -182,8 +186,15 @@ def gcn_main(B):
     return 1 if bad else 0
 
 
+def bf16_stages_main():
+    import bf16_cases as Cs
+    print(Cs.table_text("a") + "\n\n" + Cs.table_text("c"))
+    return 1 if any(req and e < MIN_RATIO for s in ("a", "c") for _, _, req, _, e in Cs.mutation_table(s)) else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--bf16-stages", action="store_true", help="the bf16 operand mode's stage pins (~5 s)")
     ap.add_argument("--gcn", action="store_true", help="the AdjMatSeer stage pins instead of the denoiser fixtures (~15 s)")
     ap.add_argument("--gcn-batch", type=int, default=16, help="--gcn: molecules per input set (the GPU test uses 16)")
     ap.add_argument("--fast", action="store_true", help="single-call and block fixtures only (skip the sampler trajectories)")
@@ -199,6 +210,8 @@ def main():
     torch.set_num_threads(args.threads)
     if args.gcn:
         return gcn_main(args.gcn_batch)
+    if args.bf16_stages:
+        return bf16_stages_main()
     names = ["dynamics_b2n20.npz", "dynamics_b4n19.npz", "dynamics_b3n39.npz", "dynamics_b3n27_x30.npz", "block3_b2n20.npz",
              "dynamics_b3n114.npz"]
     if not args.fast:
