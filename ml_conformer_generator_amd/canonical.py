@@ -27,9 +27,9 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 
-MAX_ATOMS = 64                  # include/mlconfgen_hip.h MCG_CANONICAL_MAX_ATOMS
+MAX_ATOMS = 64                 # include/mlconfgen_hip.h MCG_CANONICAL_MAX_ATOMS
 MAX_BATCH = 16384               # MCG_CANONICAL_MAX_B
 MAX_DEGREE = 8                  # MCG_CANONICAL_MAX_DEGREE
 LEAF_BUDGET = 4096              # MCG_CANONICAL_LEAF_BUDGET
@@ -66,9 +66,9 @@ def canonical_order(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_n
     ValueError before the kernel: W > 64, shapes that do not fit, atom counts outside [0, W], and with `check=True` (one
     device reduction, `fingerprint`'s) a code outside 0..4, a matrix that is not symmetric over the real atoms, an atomic
     number < 1 on a real atom."""
-    from .fingerprint import _check_graphs, graph_arguments
-    z, bonds, B, W = graph_arguments(atomic_numbers, bond_orders, n_nodes, "canonical orders")
-    dev = torch.device(device if device is not None else (bonds.device if bonds.is_cuda else "cuda:0"))
+    z, bonds, B, W = _args.graph_arguments(atomic_numbers, bond_orders, n_nodes, MAX_ATOMS,
+                                           f"canonical orders take molecules of at most {MAX_ATOMS} atoms")
+    dev = _args.resolve_device(device, bonds)
     if W == 0:                                  # no atoms anywhere: B empty graphs at the kernel's smallest width
         z, bonds, W = torch.zeros(B, 1, dtype=torch.int32), torch.zeros(B, 1, 1, dtype=torch.int8), 1
         order = torch.full((B, 0), -1, dtype=torch.int32, device=dev)
@@ -80,11 +80,9 @@ def canonical_order(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_n
     out = dict(order=order, status=status, leaves=leaves, key=key)
     if B == 0:
         return out
-    zd = z[:, :W].to(dev, torch.int32).contiguous()
-    bd = bonds.to(dev, torch.int8).contiguous()
-    nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B).contiguous()
+    zd, bd, nn = _args.device_graph(z, bonds, n_nodes, B, W, dev)
     if check:
-        _check_graphs(zd, bonds.to(dev), nn, W)
+        _args.check_graphs(zd, bonds.to(dev), nn, W)
     wide = order if order.shape[1] == W else torch.full((B, W), -1, dtype=torch.int32, device=dev)
     for lo in range(0, B, MAX_BATCH):
         hi = min(B, lo + MAX_BATCH)

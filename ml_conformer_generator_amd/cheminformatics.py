@@ -13,14 +13,14 @@ LDS, never stored) around the same host `eigh`, bit-identical for a molecule wha
 """
 from __future__ import annotations
 
+import functools
 import math
-import numbers
-import operator
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _args, _lib
+from ._args import check_n_nodes        # its first home: callers and tests still find it here
 
 ATOM_RADIUS = 1.60      # shape_similarity.py:14
 AMPLITUDE = 2.70        # shape_similarity.py:15
@@ -71,7 +71,7 @@ def shape_tanimoto_batch(ref_coord: torch.Tensor, cand_coords: torch.Tensor, n_n
     B, N, _ = cand_coords.shape
     if N > MAX_SCORED_ATOMS:
         raise ValueError(f"the shape kernels take at most {MAX_SCORED_ATOMS} atoms per molecule, got a padded width of {N}")
-    dev = torch.device(device if device is not None else (cand_coords.device if cand_coords.is_cuda else "cuda:0"))
+    dev = _args.resolve_device(device, cand_coords)
     ref = ref_coord.to(torch.float32).cpu().contiguous()
     axes = _grid_axes(ref, n)
     ref_d, cand_d = ref.to(dev), cand_coords.to(dev, torch.float32).contiguous()
@@ -169,7 +169,7 @@ def shape_quadrupole_batch(coords: torch.Tensor, n_nodes: torch.Tensor, device=N
                            neighbour_threshold: float = 2 * AMPLITUDE) -> Tuple[torch.Tensor, torch.Tensor]:
     """`get_shape_quadrupole_for_molecule` (shape_similarity.py:18-202) for a padded batch: principal moments
     [B,3] (descending) and coordinates in the principal shape frame [B,N,3] (zero on padded slots)."""
-    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
+    dev = _args.resolve_device(device, coords)
     x = coords.to(dev, torch.float32)
     B, N, _ = x.shape
     real = torch.arange(N, device=dev).unsqueeze(0) < n_nodes.to(dev).reshape(B, 1)
@@ -200,7 +200,7 @@ def evaluate_shape(reference_coord: torch.Tensor, sample_coords: torch.Tensor, n
     if int(sample_coords.shape[1]) > MAX_SCORED_ATOMS:
         raise ValueError(f"the shape kernels take at most {MAX_SCORED_ATOMS} atoms per molecule, got a padded width of "
                          f"{int(sample_coords.shape[1])}")
-    dev = torch.device(device if device is not None else (sample_coords.device if sample_coords.is_cuda else "cuda:0"))
+    dev = _args.resolve_device(device, sample_coords)
     ref = reference_coord.to(torch.float32)
     ref = ref - ref.mean(0)                                                             # :38-39
     _, ref_pf = shape_quadrupole_batch(ref.unsqueeze(0), torch.tensor([ref.shape[0]]), dev)
@@ -235,7 +235,7 @@ def shape_frames_hip(coords: torch.Tensor, n_nodes: torch.Tensor, device=None, a
     other molecules of the batch are unaffected.  `n_nodes` outside [0, N] is refused with ValueError.
     `xform_out` (float32 [B,12] on the device): also the frame transform (`mcg_shape_frames_tf`): M [3,3] row-major, then
     t [3], with frames = (coords - t) @ M on the real rows."""
-    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
+    dev = _args.resolve_device(device, coords)
     x = coords.to(dev, torch.float32).contiguous()
     B, N, _ = x.shape
     if N > MAX_SCORED_ATOMS:
@@ -270,15 +270,6 @@ def shape_frames_hip(coords: torch.Tensor, n_nodes: torch.Tensor, device=None, a
     else:
         _lib.check(L.mcg_shape_frames_tf(*args, _lib.dptr(xform_out), stream), "mcg_shape_frames_tf")
     return (moments, frames, counts) if with_counts else (moments, frames)
-
-
-def check_n_nodes(n_nodes: torch.Tensor, B: int, N: int) -> None:
-    """B atom counts, each in [0, N] (the kernels read them from device memory and cannot report a bad one)."""
-    n = torch.as_tensor(n_nodes).reshape(-1)
-    if n.numel() != B:
-        raise ValueError(f"n_nodes holds {n.numel()} counts for a batch of {B}")
-    if B and (int(n.min()) < 0 or int(n.max()) > N):
-        raise ValueError(f"n_nodes must lie in [0, {N}] (the padded width), got {int(n.min())}..{int(n.max())}")
 
 
 def check_reference_atoms(n_ref: int) -> None:
@@ -350,7 +341,7 @@ def _shape_inputs(reference, coords: torch.Tensor, n_nodes: torch.Tensor, device
     conformer outside 3..MAX_SCORED_ATOMS heavy atoms, more than `max_batch` molecules and, for a batch that is not empty,
     atom counts outside [0, W] and a padded width W above MAX_SCORED_ATOMS."""
     reference = _reference(reference)
-    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
+    dev = _args.resolve_device(device, coords)
     B = int(coords.shape[0])
     if max_batch is not None and B > max_batch:
         raise ValueError(f"pairwise shape Tanimoto takes at most {max_batch} molecules, got {B}")
@@ -417,16 +408,7 @@ def check_refine_steps(value, name: str = "refine_steps", lowest: int = 0, if_tr
     """An ascent step budget as an int in `lowest`..MAX_REFINE_STEPS (an integer type, not a bool), else a ValueError that
     names `name`.  `if_true`: the budget True stands for, where the option accepts True (`refine_overlay`: 64, with
     `lowest` 1); the default is the rule of `shape_overlay(refine_steps=...)`."""
-    if value is True and if_true is not None:
-        return if_true
-    try:
-        k = None if isinstance(value, bool) else operator.index(value)
-    except TypeError:
-        k = None
-    if k is None or not (lowest <= k <= MAX_REFINE_STEPS):
-        what = "an integer" if if_true is None else "True or an integer step budget"
-        raise ValueError(f"{name} must be {what} in {lowest}..{MAX_REFINE_STEPS}, got {value!r}")
-    return int(k)
+    return _args.check_steps(name, value, lowest, MAX_REFINE_STEPS, if_true)
 
 
 @torch.no_grad()
@@ -618,7 +600,7 @@ def mesh_winding(triangles, points: Optional[torch.Tensor] = None, axes: Optiona
     if (points is None) == (axes is None):
         raise ValueError("pass either points or axes")
     src = points if points is not None else axes
-    dev = torch.device(device if device is not None else (src.device if src.is_cuda else "cuda:0"))
+    dev = _args.resolve_device(device, src)
     tri = _triangles(triangles, dev)
     F = int(tri.shape[0])
     if points is not None:
@@ -644,7 +626,7 @@ def mesh_winding(triangles, points: Optional[torch.Tensor] = None, axes: Optiona
 def mesh_occupancy(triangles, axes: torch.Tensor, device=None) -> torch.Tensor:
     """f [n^3] fp32 on the device: 1 where |winding number| > 0.5 at the grid points of `axes` [3,n], else 0
     (`mcg_mesh_occupancy`): the density of the solid the mesh bounds, on the grid the shape kernels score on."""
-    dev = torch.device(device if device is not None else (axes.device if axes.is_cuda else "cuda:0"))
+    dev = _args.resolve_device(device, axes)
     tri = _triangles(triangles, dev)
     ax = axes.to(dev, torch.float32).contiguous()
     n = int(ax.shape[1])
@@ -660,7 +642,7 @@ def mesh_atoms_outside(triangles, coords: torch.Tensor, n_nodes: torch.Tensor, d
     """outside [B] int32 on the device: how many real atoms of each row of `coords` [B,N,3] have |winding number| <= 0.5
     with respect to `triangles` (`mcg_mesh_atoms_outside`); -1 for a row with a non-finite real coordinate.
     `with_winding`: also the atoms' winding numbers [B,N] (0 on padded atoms)."""
-    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
+    dev = _args.resolve_device(device, coords)
     B, N = int(coords.shape[0]), int(coords.shape[1])
     outside = torch.zeros(B, dtype=torch.int32, device=dev)
     w = torch.zeros(B, N, device=dev) if with_winding else None
@@ -788,33 +770,10 @@ def pairwise_shape_tanimoto_solid(solid, coords: torch.Tensor, n_nodes: torch.Te
     return pairwise_shape_tanimoto(solid_reference(solid), coords, n_nodes, device)
 
 
-def check_max_atoms_outside(value) -> int:
-    """`max_atoms_outside` as an int >= 0 (an integer type, not a bool), else ValueError."""
-    try:
-        k = None if isinstance(value, bool) else operator.index(value)
-    except TypeError:
-        k = None
-    if k is None or k < 0:
-        raise ValueError(f"max_atoms_outside must be an integer >= 0, got {value!r}")
-    return int(k)
-
-
-def check_max_pairwise_tanimoto(value) -> float:
-    """`max_pairwise_tanimoto` as a float: a real number in (0, 1] (not a bool, not NaN), else ValueError."""
-    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not (0.0 < float(value) <= 1.0):
-        raise ValueError(f"max_pairwise_tanimoto must be a real number in (0, 1], got {value!r}")
-    return float(value)
-
-
-def check_top_k(value) -> int:
-    """`top_k` as an int >= 1 (any integer type, numpy.int64 ...; not a bool, not a float), else ValueError."""
-    try:
-        k = None if isinstance(value, bool) else operator.index(value)
-    except TypeError:
-        k = None
-    if k is None or k < 1:
-        raise ValueError(f"top_k must be an integer >= 1, got {value!r}")
-    return int(k)
+# the options' own names for the shared rules of `_args`: each takes the value and returns it as an int / a float
+check_max_atoms_outside = functools.partial(_args.check_at_least, "max_atoms_outside", lowest=0)
+check_max_pairwise_tanimoto = functools.partial(_args.check_real, "max_pairwise_tanimoto", low=0.0, high=1.0, open_low=True)
+check_top_k = functools.partial(_args.check_at_least, "top_k", lowest=1)
 
 
 def check_min_shape_tanimoto(value) -> float:

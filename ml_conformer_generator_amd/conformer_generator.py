@@ -891,16 +891,7 @@ class MLConformerGenerator(torch.nn.Module):
         graph in which no feature is found is refused where it is perceived, behind the generation."""
         if sample_seed is not None:
             seeding.check_seed(sample_seed)
-        req = postprocess.parse_request(self, reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
-                                        max_pairwise_tanimoto, refine_overlay, receptor, max_receptor_clashes,
-                                        chemical_scores, reference_graph, max_chemical_tanimoto, unique,
-                                        max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
-                                        reference_context, relax_geometry, pharmacophore_scores,
-                                        reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes,
-                                        add_hydrogens, standardize, electrostatic_scores, reference_charges,
-                                        min_electrostatic_tanimoto, partial_charges, smiles, exclude_graphs,
-                                        require_substructures, exclude_substructures, substructure_counts,
-                                        interaction_scores, max_interaction_score, optimise_pose)
+        req = postprocess.entry_request(self, locals())      # every option under its own name
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         req = postprocess.label_excluded(self, req)      # `exclude_graphs`: the first device work, behind every check above
@@ -988,16 +979,7 @@ class MLConformerGenerator(torch.nn.Module):
             if seed is not None:
                 raise ValueError("pass either seed (per-rank device generator) or sample_seed (keyed stream), not both")
             seeding.check_seed(sample_seed)
-        req = postprocess.parse_request(self, reference_conformer, shape_scores, top_k, min_shape_tanimoto, overlay,
-                                        max_pairwise_tanimoto, refine_overlay, receptor, max_receptor_clashes,
-                                        chemical_scores, reference_graph, max_chemical_tanimoto, unique,
-                                        max_pairwise_chemical_tanimoto, reference_shape, shape_density, max_atoms_outside,
-                                        reference_context, relax_geometry, pharmacophore_scores,
-                                        reference_pharmacophore, min_pharmacophore_tanimoto, rank_by, relieve_clashes,
-                                        add_hydrogens, standardize, electrostatic_scores, reference_charges,
-                                        min_electrostatic_tanimoto, partial_charges, smiles, exclude_graphs,
-                                        require_substructures, exclude_substructures, substructure_counts,
-                                        interaction_scores, max_interaction_score, optimise_pose)
+        req = postprocess.entry_request(self, locals())      # every option under its own name
         ref_context, ref_n_atoms = self._reference_context(reference_conformer, reference_context, n_atoms, req.reference,
                                                            shape_density)
         lo_n = max(ref_n_atoms - variance, self.min_n_nodes)

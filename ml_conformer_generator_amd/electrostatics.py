@@ -48,14 +48,13 @@ Score    T(R,M) = E(R,M) / (E(R,R) + E(M,M) - E(R,M)), in [-1/3, 1]; 0 where the
 """
 from __future__ import annotations
 
+import functools
 import math
-import numbers
 from typing import Dict, Optional, Tuple
 
 import torch
 
-from . import _lib
-from . import hydrogens as mcg_hydrogens
+from . import _args, _lib
 from . import pharmacophore as mcg_pharm
 
 MAX_ATOMS = 64                  # include/mlconfgen_hip.h MCG_CHARGES_MAX_ATOMS
@@ -86,13 +85,9 @@ def partial_charges(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_n
     ValueError before the kernels: shapes that do not fit, W > 64, atom counts outside [0, W], and with `check=True` (one
     device reduction, one host read) a code outside 0..4, a matrix that is not symmetric, an atomic number < 1 on a real
     atom."""
-    from .cheminformatics import check_n_nodes
-    shape = tuple(torch.as_tensor(bond_orders).shape)
-    if len(shape) == 3 and shape[1] == shape[2] and shape[1] > MAX_ATOMS:
-        raise ValueError(f"partial charges take molecules of at most {MAX_ATOMS} atoms, got a width of {shape[1]}")
-    z, bonds, B, W = mcg_hydrogens._graph_arguments(atomic_numbers, bond_orders, n_nodes)
-    check_n_nodes(n_nodes, B, W)
-    dev = torch.device(device if device is not None else (bonds.device if bonds.is_cuda else "cuda:0"))
+    z, bonds, B, W = _args.graph_arguments(atomic_numbers, bond_orders, n_nodes, MAX_ATOMS,
+                                           f"partial charges take molecules of at most {MAX_ATOMS} atoms")
+    dev = _args.resolve_device(device, bonds)
     launches = B > 0 and W > 0                      # the kernel writes every element of every output
     fill = torch.empty if launches else torch.zeros
     out = {"q": fill(B, W, dtype=torch.float32, device=dev), "q_h": fill(B, W, dtype=torch.float32, device=dev),
@@ -104,8 +99,7 @@ def partial_charges(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_n
     bd = bonds.to(dev, torch.int8).contiguous()
     nn = out["n_nodes"]
     if check:
-        from .fingerprint import _check_graphs
-        _check_graphs(zd, bd, nn, W)
+        _args.check_graphs(zd, bd, nn, W)
     types, rings, count = perceived if perceived is not None else mcg_pharm.perceive_features(zd, bd, nn, dev)
     for lo in range(0, B, MAX_BATCH):
         rows = slice(lo, min(lo + MAX_BATCH, B))
@@ -178,7 +172,7 @@ def reference_self_overlap(reference_points, device=None) -> torch.Tensor:
     """E(R,R) [1] fp32 on the device: the reference's points run through `mcg_esp_overlap` as a one-row batch against
     themselves - the kernel and the summation order of every other overlap."""
     xyz, q = load_reference_charges(reference_points)
-    dev = torch.device(device if device is not None else "cuda:0")
+    dev = _args.resolve_device(device)
     xyz, q = xyz.to(dev), q.to(dev)
     count = torch.tensor([int(q.numel())], dtype=torch.int32, device=dev)
     return _overlap_launch(xyz, q, xyz.unsqueeze(0), q.unsqueeze(0), count, None, dev)["self"]
@@ -194,7 +188,6 @@ def electrostatic_tanimoto(reference_points, points: torch.Tensor, charges: torc
     coordinate or charge on a real point: NaN.  Every output has the same bits whatever the batch, the row and PW.
     ValueError before the rows' launch: shapes that do not fit, PW > 256, point counts outside [0, PW], a reference
     `load_reference_charges` refuses or whose E(R,R) is below 1e-12 (one host read)."""
-    from .cheminformatics import check_n_nodes
     xyz, q = load_reference_charges(reference_points)
     x, c = torch.as_tensor(points), torch.as_tensor(charges)
     if x.dim() != 3 or x.shape[2] != 3 or not x.dtype.is_floating_point:
@@ -204,8 +197,8 @@ def electrostatic_tanimoto(reference_points, points: torch.Tensor, charges: torc
         raise ValueError(f"electrostatic scores take molecules of at most {MAX_POINTS} charge points, got a width of {PW}")
     if tuple(c.shape) != (B, PW) or not c.dtype.is_floating_point:
         raise ValueError(f"charges must be floating point [B,PW] = [{B}, {PW}], got {list(c.shape)} of type {c.dtype}")
-    check_n_nodes(n_points, B, PW)
-    dev = torch.device(device if device is not None else (x.device if x.is_cuda else "cuda:0"))
+    _args.check_n_nodes(n_points, B, PW)
+    dev = _args.resolve_device(device, x)
     xyz, q = xyz.to(dev), q.to(dev)
     e_rr = reference_self_overlap((xyz, q), dev)
     if not float(e_rr[0]) >= EMPTY:
@@ -264,16 +257,5 @@ def select_score(shape: Optional[float], electrostatic: Optional[float]) -> Opti
     return shape + electrostatic
 
 
-def check_threshold(name: str, value) -> float:
-    """An electrostatic Tanimoto threshold (`min_electrostatic_tanimoto`) as a float: a real number in [-1, 1] (not a bool,
-    not NaN), else ValueError."""
-    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not (-1.0 <= float(value) <= 1.0):
-        raise ValueError(f"{name} must be a real number in [-1, 1], got {value!r}")
-    return float(value)
-
-
-def check_rank_by(value) -> str:
-    """`rank_by` as "shape", "combo" or "electrostatic", else ValueError."""
-    if value not in ("shape", "combo", "electrostatic"):
-        raise ValueError(f"rank_by must be 'shape', 'combo' or 'electrostatic', got {value!r}")
-    return value
+check_threshold = functools.partial(_args.check_real, low=-1.0, high=1.0)     # (name, value): `min_electrostatic_tanimoto`
+check_rank_by = _args.check_rank_by

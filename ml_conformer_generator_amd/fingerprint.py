@@ -22,12 +22,12 @@ code 4 for aromatic bonds; an RDKit-sanitised reference Mol reports 1.5 for them
 """
 from __future__ import annotations
 
-import numbers
+import functools
 from typing import List, Sequence, Tuple
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 FP_WORDS = 64                   # include/mlconfgen_hip.h MCG_FP_WORDS: 2 048 bits
 MAX_GRAPH_ATOMS = 64            # csrc/mcg_fingerprint.hip FP_MAXW: one lane and one 64-bit neighbour mask per atom
@@ -94,40 +94,6 @@ def pad_graphs(graphs: Sequence[Tuple[List[int], torch.Tensor]]):
 
 
 # ----------------------------------------------------------------------------------------------- device
-def graph_arguments(atomic_numbers, bond_orders, n_nodes, what: str):
-    """(z, bonds, B, W) of padded graph arguments, their shapes and dtypes checked: the refusals `graph_fingerprints` and
-    `canonical.canonical_order` share.  `what`: who takes at most `MAX_GRAPH_ATOMS` atoms, for the message."""
-    from .cheminformatics import check_n_nodes
-    bonds = torch.as_tensor(bond_orders)
-    z = torch.as_tensor(atomic_numbers)
-    if bonds.dim() != 3 or bonds.shape[1] != bonds.shape[2]:
-        raise ValueError(f"bond_orders must be [B,W,W], got {list(bonds.shape)}")
-    B, W = int(bonds.shape[0]), int(bonds.shape[1])
-    if W > MAX_GRAPH_ATOMS:
-        raise ValueError(f"{what} take molecules of at most {MAX_GRAPH_ATOMS} atoms, got a width of {W}")
-    if z.dim() != 2 or z.shape[0] != B or z.shape[1] < W:
-        raise ValueError(f"atomic_numbers must be [B, >= W] = [{B}, >= {W}], got {list(z.shape)}")
-    if bonds.dtype.is_floating_point or z.dtype.is_floating_point:
-        raise ValueError("atomic_numbers and bond_orders must be integer tensors")
-    check_n_nodes(n_nodes, B, W)
-    return z, bonds, B, W
-
-
-def _check_graphs(z: torch.Tensor, bonds: torch.Tensor, nn: torch.Tensor, W: int) -> None:
-    """The `check=True` half of `graph_fingerprints`: one device reduction, one host read."""
-    real = torch.arange(W, device=z.device).view(1, W) < nn.view(-1, 1)
-    pair = real.unsqueeze(1) & real.unsqueeze(2)
-    c = bonds.to(torch.int16)
-    bad = torch.stack([(pair & ((c < 0) | (c > 4))).any(), (pair & (c != c.transpose(1, 2))).any(),
-                       (real & (z < 1)).any()]).cpu().tolist()
-    if bad[0]:
-        raise ValueError("bond_orders must hold the codes 0 none / 1 / 2 / 3 / 4 aromatic")
-    if bad[1]:
-        raise ValueError("bond_orders must be symmetric over each molecule's atoms")
-    if bad[2]:
-        raise ValueError("atomic numbers must be >= 1 on every real atom")
-
-
 @torch.no_grad()
 def graph_fingerprints(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor, device=None,
                        check: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -142,8 +108,9 @@ def graph_fingerprints(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, 
     ValueError before the kernel: W > 64, shapes that do not fit, atom counts outside [0, W]
     (`cheminformatics.check_n_nodes`), and with `check=True` (one device reduction) a code outside 0..4, a matrix that is
     not symmetric over the real atoms, an atomic number < 1 on a real atom."""
-    z, bonds, B, W = graph_arguments(atomic_numbers, bond_orders, n_nodes, "graph fingerprints")
-    dev = torch.device(device if device is not None else (bonds.device if bonds.is_cuda else "cuda:0"))
+    z, bonds, B, W = _args.graph_arguments(atomic_numbers, bond_orders, n_nodes, MAX_GRAPH_ATOMS,
+                                           f"graph fingerprints take molecules of at most {MAX_GRAPH_ATOMS} atoms")
+    dev = _args.resolve_device(device, bonds)
     fp = torch.zeros(B, FP_WORDS, dtype=torch.int32, device=dev)
     key = torch.empty(B, dtype=torch.int64, device=dev)
     pop = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -151,11 +118,9 @@ def graph_fingerprints(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, 
         return fp, key, pop
     if W == 0:                                  # no atoms anywhere: B empty graphs at the kernel's smallest width
         z, bonds, W = torch.zeros(B, 1, dtype=torch.int32), torch.zeros(B, 1, 1, dtype=torch.int8), 1
-    zd = z[:, :W].to(dev, torch.int32).contiguous()
-    bd = bonds.to(dev, torch.int8).contiguous()
-    nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B).contiguous()
+    zd, bd, nn = _args.device_graph(z, bonds, n_nodes, B, W, dev)
     if check:
-        _check_graphs(zd, bonds.to(dev), nn, W)
+        _args.check_graphs(zd, bonds.to(dev), nn, W)
     _lib.check(_lib.lib().mcg_graph_fingerprint(_lib.dptr(zd), _lib.dptr(bd), _lib.dptr(nn), B, W, _lib.dptr(fp),
                                                 _lib.dptr(key), _lib.dptr(pop), _lib.current_stream_ptr(dev)),
                "mcg_graph_fingerprint")
@@ -176,7 +141,7 @@ def fingerprint_tanimoto(fp: torch.Tensor, ref_fp: torch.Tensor) -> torch.Tensor
     f = _fp_tensor(fp)
     if f.dim() != 2:
         raise ValueError(f"fp must be [B, {FP_WORDS}], got {list(f.shape)}")
-    dev = f.device if f.is_cuda else torch.device("cuda:0")
+    dev = _args.resolve_device(None, f)
     f = f.to(dev).contiguous()
     ref = _fp_tensor(ref_fp, dev).reshape(-1).contiguous()
     if ref.numel() != FP_WORDS:
@@ -201,7 +166,7 @@ def pairwise_fingerprint_tanimoto(fp: torch.Tensor) -> torch.Tensor:
     B = int(f.shape[0])
     if B > MAX_PAIR_BATCH:
         raise ValueError(f"the pair matrix takes at most {MAX_PAIR_BATCH} fingerprints, got {B}")
-    dev = f.device if f.is_cuda else torch.device("cuda:0")
+    dev = _args.resolve_device(None, f)
     f = f.to(dev).contiguous()
     out = torch.empty(B, B, device=dev)
     if B == 0:
@@ -224,16 +189,6 @@ def select_unique(keys: Sequence[int], order: Sequence[int]) -> List[int]:
     return sorted(keep)
 
 
-def check_threshold(name: str, value) -> float:
-    """A Tanimoto threshold (`max_chemical_tanimoto`, `max_pairwise_chemical_tanimoto`) as a float: a real number in
-    (0, 1] (not a bool, not NaN), else ValueError - the rule of `cheminformatics.check_max_pairwise_tanimoto`."""
-    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not (0.0 < float(value) <= 1.0):
-        raise ValueError(f"{name} must be a real number in (0, 1], got {value!r}")
-    return float(value)
-
-
-def check_flag(name: str, value) -> bool:
-    """An on / off option as a bool; anything but True or False is a ValueError."""
-    if value is not True and value is not False:
-        raise ValueError(f"{name} must be True or False, got {value!r}")
-    return value
+# (name, value): `max_chemical_tanimoto`, `max_pairwise_chemical_tanimoto` - the rule of `max_pairwise_tanimoto`
+check_threshold = functools.partial(_args.check_real, low=0.0, high=1.0, open_low=True)
+check_flag = _args.check_flag

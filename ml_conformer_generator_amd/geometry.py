@@ -24,12 +24,11 @@ the batch, its row and the padded widths.
 """
 from __future__ import annotations
 
-import operator
 from typing import Dict, Optional
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 from .config import ELEMENTS
 
 MAX_RELAX_ATOMS = 64            # include/mlconfgen_hip.h MCG_RELAX_MAX_ATOMS (= fingerprint.MAX_GRAPH_ATOMS)
@@ -40,37 +39,13 @@ DEFAULT_STEPS = 200             # what `relax_geometry=True` stands for
 def check_steps(value) -> int:
     """The `relax_geometry` option as a step budget: False -> 0 (off), True -> 200, an integer in 1..4096 -> itself (an
     integer type, not a bool); anything else is a ValueError."""
-    if value is False:
-        return 0
-    if value is True:
-        return DEFAULT_STEPS
-    try:
-        k = None if isinstance(value, bool) else operator.index(value)
-    except TypeError:
-        k = None
-    if k is None or not (1 <= k <= MAX_RELAX_STEPS):
-        raise ValueError(f"relax_geometry must be False, True or an integer step budget in 1..{MAX_RELAX_STEPS}, "
-                         f"got {value!r}")
-    return int(k)
-
-
-def _known_radius(device) -> torch.Tensor:
-    """[max Z + 2] bool: whether the library has a covalent radius for Z (the last entry, for any other Z: False)."""
-    known = torch.zeros(max(ELEMENTS) + 2, dtype=torch.bool)
-    known[list(ELEMENTS)] = True
-    return known.to(device)
+    return _args.check_steps("relax_geometry", value, 1, MAX_RELAX_STEPS, if_true=DEFAULT_STEPS, if_false=0)
 
 
 def _check_molecules(z: torch.Tensor, bonds: torch.Tensor, nn: torch.Tensor, W: int) -> None:
-    """The `check=True` half of `relax_geometry`: `fingerprint._check_graphs`, and a covalent radius for every real atom."""
-    from .fingerprint import _check_graphs
-    _check_graphs(z, bonds, nn, W)
-    known = _known_radius(z.device)
-    real = torch.arange(W, device=z.device).view(1, W) < nn.view(-1, 1)
-    zz = z.to(torch.long).clamp(min=0, max=known.numel() - 1)
-    if bool((real & ~known[zz]).any()):
-        raise ValueError("relax_geometry knows the elements "
-                         f"{[ELEMENTS[k][0] for k in sorted(ELEMENTS)]} only (no covalent radius for another Z)")
+    """The `check=True` half of `relax_geometry`: `_args.check_graphs`, and a covalent radius for every real atom."""
+    _args.check_graphs(z, bonds, nn, W)
+    _args.check_known_elements(z, nn, W, "relax_geometry", ELEMENTS)
 
 
 @torch.no_grad()
@@ -92,31 +67,24 @@ def relax_geometry(coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_orde
     reductions, one host read each) atom counts outside [0, min(N, W)] (unchecked, the kernel clamps them), a code outside
     0..4, a matrix that is not symmetric, an atomic number < 1 or one without a covalent radius (`config.ELEMENTS`) on a
     real atom."""
-    from .cheminformatics import check_n_nodes
     x = torch.as_tensor(coords)
     bonds = torch.as_tensor(bond_orders)
-    z = torch.as_tensor(atomic_numbers)
     if x.dim() != 3 or x.shape[2] != 3 or not x.dtype.is_floating_point:
         raise ValueError(f"coords must be floating point [B,N,3], got {list(x.shape)} of type {x.dtype}")
     B, N = int(x.shape[0]), int(x.shape[1])
-    if bonds.dim() != 3 or bonds.shape[1] != bonds.shape[2] or bonds.shape[0] != B:
+    if bonds.dim() != 3 or bonds.shape[1] != bonds.shape[2] or bonds.shape[0] != B:      # its own words: it knows B already
         raise ValueError(f"bond_orders must be [B,W,W] with B = {B}, got {list(bonds.shape)}")
-    W = int(bonds.shape[1])
-    if W > MAX_RELAX_ATOMS:
-        raise ValueError(f"relax_geometry takes molecules of at most {MAX_RELAX_ATOMS} atoms, got a width of {W}")
-    if z.dim() != 2 or z.shape[0] != B or z.shape[1] < W:
-        raise ValueError(f"atomic_numbers must be [B, >= W] = [{B}, >= {W}], got {list(z.shape)}")
-    if bonds.dtype.is_floating_point or z.dtype.is_floating_point:
-        raise ValueError("atomic_numbers and bond_orders must be integer tensors")
+    z, bonds, _, W = _args.graph_arguments(atomic_numbers, bonds, n_nodes, MAX_RELAX_ATOMS,
+                                           f"relax_geometry takes molecules of at most {MAX_RELAX_ATOMS} atoms", counts=None)
     if isinstance(steps, bool) or not isinstance(steps, int) or not (0 <= steps <= MAX_RELAX_STEPS):
         raise ValueError(f"steps must be an integer in 0..{MAX_RELAX_STEPS}, got {steps!r}")
     if restraint_coords is not None and tuple(torch.as_tensor(restraint_coords).shape) != (B, N, 3):
         raise ValueError(f"restraint_coords must have the shape of coords, {[B, N, 3]}")
     if check:
-        check_n_nodes(n_nodes, B, min(N, W))
+        _args.check_n_nodes(n_nodes, B, min(N, W))
     elif torch.as_tensor(n_nodes).numel() != B:      # unchecked: no host read of device counts; the kernel clamps them
         raise ValueError(f"n_nodes holds {torch.as_tensor(n_nodes).numel()} counts for a batch of {B}")
-    dev = torch.device(device if device is not None else (x.device if x.is_cuda else "cuda:0"))
+    dev = _args.resolve_device(device, x)
     out = {"coords": torch.zeros(B, N, 3, dtype=torch.float32, device=dev),
            "energy_before": torch.zeros(B, dtype=torch.float32, device=dev),
            "energy_after": torch.zeros(B, dtype=torch.float32, device=dev),
@@ -128,9 +96,7 @@ def relax_geometry(coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_orde
         return out
     xd = x.to(dev, torch.float32).contiguous()
     rd = None if restraint_coords is None else torch.as_tensor(restraint_coords).to(dev, torch.float32).contiguous()
-    zd = z[:, :W].to(dev, torch.int32).contiguous()
-    bd = bonds.to(dev, torch.int8).contiguous()
-    nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B).contiguous()
+    zd, bd, nn = _args.device_graph(z, bonds, n_nodes, B, W, dev)
     if check:
         _check_molecules(zd, bonds.to(dev), nn, W)
     energy = torch.empty(B, 2, dtype=torch.float32, device=dev)

@@ -51,7 +51,7 @@ from typing import Dict, List
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 from . import pharmacophore as mcg_pharm
 from .config import ELEMENTS
 
@@ -70,21 +70,9 @@ def slots(width: int) -> int:
 
 
 def _graph_arguments(atomic_numbers, bond_orders, n_nodes):
-    """(z, bonds, B, W) of the graph arguments, shapes and dtypes checked."""
-    bonds = torch.as_tensor(bond_orders)
-    z = torch.as_tensor(atomic_numbers)
-    if bonds.dim() != 3 or bonds.shape[1] != bonds.shape[2]:
-        raise ValueError(f"bond_orders must be [B,W,W], got {list(bonds.shape)}")
-    B, W = int(bonds.shape[0]), int(bonds.shape[1])
-    if W > MAX_ATOMS:
-        raise ValueError(f"hydrogens are added to molecules of at most {MAX_ATOMS} atoms, got a width of {W}")
-    if z.dim() != 2 or z.shape[0] != B or z.shape[1] < W:
-        raise ValueError(f"atomic_numbers must be [B, >= W] = [{B}, >= {W}], got {list(z.shape)}")
-    if bonds.dtype.is_floating_point or z.dtype.is_floating_point:
-        raise ValueError("atomic_numbers and bond_orders must be integer tensors")
-    if torch.as_tensor(n_nodes).numel() != B:
-        raise ValueError(f"n_nodes holds {torch.as_tensor(n_nodes).numel()} counts for a batch of {B}")
-    return z, bonds, B, W
+    """(z, bonds, B, W) of the graph arguments, shapes and dtypes checked; of the counts only that there are B."""
+    return _args.graph_arguments(atomic_numbers, bond_orders, n_nodes, MAX_ATOMS,
+                                 f"hydrogens are added to molecules of at most {MAX_ATOMS} atoms", counts=False)
 
 
 def _aromatic_rings(arom: List[List[int]], n: int) -> List[int]:
@@ -162,7 +150,6 @@ def add_hydrogens(coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_order
     ValueError before the kernels: shapes that do not fit, W > 64, and with `check=True` (device reductions, one
     host read each) a code outside 0..4, a matrix that is not symmetric, an atomic number < 1 or one without a covalent
     radius (`config.ELEMENTS`) on a real atom; atom counts outside [0, min(N, W)] always."""
-    from .cheminformatics import check_n_nodes
     x = torch.as_tensor(coords)
     if x.dim() != 3 or x.shape[2] != 3 or not x.dtype.is_floating_point:
         raise ValueError(f"coords must be floating point [B,N,3], got {list(x.shape)} of type {x.dtype}")
@@ -170,8 +157,8 @@ def add_hydrogens(coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_order
     N = int(x.shape[1])
     if int(x.shape[0]) != B:
         raise ValueError(f"coords holds {int(x.shape[0])} molecules, bond_orders {B}")
-    check_n_nodes(n_nodes, B, min(N, W))
-    dev = torch.device(device if device is not None else (x.device if x.is_cuda else "cuda:0"))
+    _args.check_n_nodes(n_nodes, B, min(N, W))
+    dev = _args.resolve_device(device, x)
     launches = B > 0 and N > 0 and W > 0           # the kernel writes every element of the per-row and per-atom outputs
     fill = torch.empty if launches else torch.zeros
     out = {"coords": torch.zeros(B, 0, 3, dtype=torch.float32, device=dev),
@@ -185,18 +172,10 @@ def add_hydrogens(coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_order
     if not launches:
         return out
     xd = x.to(dev, torch.float32).contiguous()
-    zd = z[:, :W].to(dev, torch.int32).contiguous()
-    bd = bonds.to(dev, torch.int8).contiguous()
-    nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B).contiguous()
+    zd, bd, nn = _args.device_graph(z, bonds, n_nodes, B, W, dev)
     if check:
-        from .geometry import _known_radius
-        from .fingerprint import _check_graphs
-        _check_graphs(zd, bd, nn, W)
-        known = _known_radius(dev)
-        real = torch.arange(W, device=dev).view(1, W) < nn.view(-1, 1)
-        if bool((real & ~known[zd.to(torch.long).clamp(min=0, max=known.numel() - 1)]).any()):
-            raise ValueError("add_hydrogens knows the elements "
-                             f"{[ELEMENTS[k][0] for k in sorted(ELEMENTS)]} only (no covalent radius for another Z)")
+        _args.check_graphs(zd, bd, nn, W)
+        _args.check_known_elements(zd, nn, W, "add_hydrogens", ELEMENTS)
     types, rings, count = perceived if perceived is not None else mcg_pharm.perceive_features(zd, bd, nn, dev)
     HW = slots(W)
     h_xyz = torch.empty(B, HW, 3, dtype=torch.float32, device=dev)

@@ -40,12 +40,11 @@ any row, at any padded width, with and without tile skipping, and whatever the o
 from __future__ import annotations
 
 import math
-import numbers
 from typing import Dict, NamedTuple, Optional
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 from . import pharmacophore as mcg_pharm
 from . import receptor as mcg_receptor
 from . import substructure as mcg_sub
@@ -102,6 +101,16 @@ def prepare_receptor(receptor) -> PreparedReceptor:
 
 
 # ----------------------------------------------------------------------------------------------- device
+def _posed_graphs(coords, n_nodes, atomic_numbers, bond_orders, what: str):
+    """(B, N, z, bonds) of posed, padded molecules with their graphs: `_args.ligand_arguments`, and `bond_orders`
+    [B, >= N, >= N]."""
+    B, N, z = _args.ligand_arguments(coords, n_nodes, atomic_numbers, MAX_ATOMS, MAX_BATCH, what)
+    bonds = torch.as_tensor(bond_orders)
+    if bonds.dim() != 3 or bonds.shape[0] != B or bonds.shape[1] != bonds.shape[2] or bonds.shape[1] < N:
+        raise ValueError(f"bond_orders must be [B, >= N, >= N] = [{B}, >= {N}, >= {N}], got {list(bonds.shape)}")
+    return B, N, z, bonds
+
+
 @torch.no_grad()
 def ligand_types(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor, device=None,
                  perceived=None) -> torch.Tensor:
@@ -148,17 +157,17 @@ def score_typed(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, radii: to
     [B], `radii` [B,N] fp32 interaction radii, `types` [B,N] uint8 type bits, `n_rot` [B] rotatable bonds; `receptor` as
     in `interaction_scores`.  Device tensors: atom_terms [B,N,6], mol_terms [B,8], hbonds [B] as the kernel writes them
     (include/mlconfgen_hip.h).  B or N of 0 launches nothing and returns zeros."""
-    from .cheminformatics import check_n_nodes
     prepared = prepare_receptor(receptor)
-    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
-    B, N = int(coords.shape[0]), int(coords.shape[1])
-    check_n_nodes(n_nodes, B, N)
-    if N > MAX_ATOMS or B > MAX_BATCH:
-        raise ValueError(f"interaction scores take at most {MAX_BATCH} molecules of at most {MAX_ATOMS} atoms, got "
-                         f"[{B}, {N}]")
+    dev = _args.resolve_device(device, coords)
+    B, N, _ = _args.ligand_arguments(coords, n_nodes, None, MAX_ATOMS, MAX_BATCH, "interaction scores take")
     for name, t, shape in (("radii", radii, (B, N)), ("types", types, (B, N)), ("n_rot", n_rot, (B,))):
         if tuple(t.shape) != shape:
             raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+    return _score_typed(prepared, coords, n_nodes, B, N, radii, types, n_rot, skip_tiles, dev)
+
+
+def _score_typed(prepared, coords, n_nodes, B, N, radii, types, n_rot, skip_tiles, dev) -> Dict[str, torch.Tensor]:
+    """`score_typed` behind its checks."""
     atoms = torch.zeros(B, N, 6, device=dev)
     mol = torch.zeros(B, 8, device=dev)
     hbonds = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -196,27 +205,16 @@ def interaction_scores(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, at
     unaffected.  `skip_tiles`: whether a molecule's workgroup walks only the receptor tiles within the cut-off of it; never
     a bit of the result.  Refused before any device work: what `load_typed_receptor` refuses, atom counts outside [0, N],
     N > 64, B > MAX_BATCH, shapes that do not fit."""
-    from .cheminformatics import check_n_nodes
     prepared = prepare_receptor(receptor)
-    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
-    B, N = int(coords.shape[0]), int(coords.shape[1])
-    check_n_nodes(n_nodes, B, N)
-    if N > MAX_ATOMS or B > MAX_BATCH:
-        raise ValueError(f"interaction scores take at most {MAX_BATCH} molecules of at most {MAX_ATOMS} atoms, got "
-                         f"[{B}, {N}]")
-    z = torch.as_tensor(atomic_numbers)
-    bonds = torch.as_tensor(bond_orders)
-    if z.dim() != 2 or z.shape[0] != B or z.shape[1] < N:
-        raise ValueError(f"atomic_numbers must be [B, >= N] = [{B}, >= {N}], got {list(z.shape)}")
-    if bonds.dim() != 3 or bonds.shape[0] != B or bonds.shape[1] != bonds.shape[2] or bonds.shape[1] < N:
-        raise ValueError(f"bond_orders must be [B, >= N, >= N] = [{B}, >= {N}, >= {N}], got {list(bonds.shape)}")
+    dev = _args.resolve_device(device, coords)
+    B, N, z, bonds = _posed_graphs(coords, n_nodes, atomic_numbers, bond_orders, "interaction scores take")
     n_rot = torch.zeros(B, dtype=torch.int32, device=dev)
     types = torch.zeros(B, N, dtype=torch.uint8, device=dev)
     if B > 0 and N > 0:
         bonds = bonds[:, :N, :N]
         types = ligand_types(z[:, :N], bonds, n_nodes, dev)
         n_rot = rotatable_bonds(z[:, :N], bonds, n_nodes, dev, check=check)
-    out = score_typed(prepared, coords, n_nodes, interaction_radii(z[:, :N].to(dev)), types, n_rot, skip_tiles, dev)
+    out = _score_typed(prepared, coords, n_nodes, B, N, interaction_radii(z[:, :N].to(dev)), types, n_rot, skip_tiles, dev)
     atoms, mol, hbonds = out["atom_terms"], out["mol_terms"], out["hbonds"]
     return dict(score=mol[:, 6], terms=mol[:, :6], hbonds=hbonds, atom_scores=atoms[:, :, 5], atom_terms=atoms[:, :, :5],
                 n_rot=n_rot, types=types)
@@ -233,9 +231,7 @@ OPTIMISE_REFUSAL_WITH_FINISHER = ("optimise_pose cannot be combined with a finis
 
 def check_max_shift(value, name: str = "max_shift") -> float:
     """`max_shift` as a float: a finite real number >= 0 (not a bool), else ValueError."""
-    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not math.isfinite(float(value)) or value < 0:
-        raise ValueError(f"{name} must be a finite real number >= 0, got {value!r}")
-    return float(value)
+    return _args.check_real(name, value, 0.0)
 
 
 @torch.no_grad()
@@ -246,19 +242,20 @@ def optimise_typed(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, radii:
     [B], `radii` [B,N] fp32 interaction radii, `types` [B,N] uint8 type bits; `receptor` as in `interaction_scores`.
     Device tensors as the kernel writes them (include/mlconfgen_hip.h): coords [B,N,3], xform [B,12], stats [B,8],
     gradient [B,6] and - `trace` - trace [B,steps,24].  B or N of 0 launches nothing and returns the rows as they came."""
-    from .cheminformatics import check_n_nodes
     prepared = prepare_receptor(receptor)
     steps = mcg_receptor.check_relief_steps(steps)
     max_shift = check_max_shift(max_shift)
-    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
-    B, N = int(coords.shape[0]), int(coords.shape[1])
-    check_n_nodes(n_nodes, B, N)
-    if N > MAX_ATOMS or B > MAX_BATCH:
-        raise ValueError(f"pose optimisation takes at most {MAX_BATCH} molecules of at most {MAX_ATOMS} atoms, got "
-                         f"[{B}, {N}]")
+    dev = _args.resolve_device(device, coords)
+    B, N, _ = _args.ligand_arguments(coords, n_nodes, None, MAX_ATOMS, MAX_BATCH, "pose optimisation takes")
     for name, t, shape in (("radii", radii, (B, N)), ("types", types, (B, N))):
         if tuple(t.shape) != shape:
             raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+    return _optimise_typed(prepared, coords, n_nodes, B, N, radii, types, steps, max_shift, skip_tiles, dev, trace)
+
+
+def _optimise_typed(prepared, coords, n_nodes, B, N, radii, types, steps, max_shift, skip_tiles, dev, trace
+                    ) -> Dict[str, torch.Tensor]:
+    """`optimise_typed` behind its checks."""
     x = coords.to(dev, torch.float32).contiguous()
     out = torch.empty_like(x) if B > 0 and N > 0 else x.clone()
     xform = torch.zeros(B, 12, device=dev)
@@ -322,27 +319,16 @@ def optimise_pose(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_
     the others are unaffected.  A molecule's outputs depend on its own atoms and the receptor only.  Refused before any
     device work: what `load_typed_receptor` refuses, `steps` outside 0..1024, `max_shift` negative or not finite, atom
     counts outside [0, N], N > 64, B > MAX_BATCH, shapes that do not fit."""
-    from .cheminformatics import check_n_nodes
     prepared = prepare_receptor(receptor)
     steps = mcg_receptor.check_relief_steps(steps)
     max_shift = check_max_shift(max_shift)
-    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
-    B, N = int(coords.shape[0]), int(coords.shape[1])
-    check_n_nodes(n_nodes, B, N)
-    if N > MAX_ATOMS or B > MAX_BATCH:
-        raise ValueError(f"pose optimisation takes at most {MAX_BATCH} molecules of at most {MAX_ATOMS} atoms, got "
-                         f"[{B}, {N}]")
-    z = torch.as_tensor(atomic_numbers)
-    bonds = torch.as_tensor(bond_orders)
-    if z.dim() != 2 or z.shape[0] != B or z.shape[1] < N:
-        raise ValueError(f"atomic_numbers must be [B, >= N] = [{B}, >= {N}], got {list(z.shape)}")
-    if bonds.dim() != 3 or bonds.shape[0] != B or bonds.shape[1] != bonds.shape[2] or bonds.shape[1] < N:
-        raise ValueError(f"bond_orders must be [B, >= N, >= N] = [{B}, >= {N}, >= {N}], got {list(bonds.shape)}")
+    dev = _args.resolve_device(device, coords)
+    B, N, z, bonds = _posed_graphs(coords, n_nodes, atomic_numbers, bond_orders, "pose optimisation takes")
     types = torch.zeros(B, N, dtype=torch.uint8, device=dev)
     if B > 0 and N > 0:
         types = ligand_types(z[:, :N], bonds[:, :N, :N], n_nodes, dev)
-    out = optimise_typed(prepared, coords, n_nodes, interaction_radii(z[:, :N].to(dev)), types, steps, max_shift, True, dev,
-                         trace)
+    out = _optimise_typed(prepared, coords, n_nodes, B, N, interaction_radii(z[:, :N].to(dev)), types, steps, max_shift,
+                          True, dev, trace)
     stats, xform = out["stats"], out["xform"]
     ok = torch.isfinite(stats[:, 0])
     count = lambda col: torch.where(ok, stats[:, col], torch.full_like(stats[:, col], -1.0)).to(torch.int32)
@@ -353,20 +339,10 @@ def optimise_pose(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_
         res["trace"] = out["trace"]
     return res
 
+
 # ----------------------------------------------------------------------------------------------- options
-def check_threshold(name: str, value) -> float:
-    """An interaction-score threshold (`max_interaction_score`) as a float: a finite real number (not a bool), else
-    ValueError."""
-    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not math.isfinite(float(value)):
-        raise ValueError(f"{name} must be a finite real number, got {value!r}")
-    return float(value)
-
-
-def check_rank_by(value) -> str:
-    """`rank_by` as "shape", "combo", "electrostatic" or "interaction", else ValueError."""
-    if value not in ("shape", "combo", "electrostatic", "interaction"):
-        raise ValueError(f"rank_by must be 'shape', 'combo', 'electrostatic' or 'interaction', got {value!r}")
-    return value
+check_threshold = _args.check_real             # (name, value): `max_interaction_score`, a finite real number
+check_rank_by = _args.check_rank_by
 
 
 def select_score(interaction: Optional[float]) -> float:

@@ -41,13 +41,13 @@ matches = -1, the other rows unaffected; a reference without features is refused
 """
 from __future__ import annotations
 
+import functools
 import math
-import numbers
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 TYPE_NAMES = ("donor", "acceptor", "cation", "anion", "hydrophobe", "ring")       # type index 0..5; atom bit 1 << index
 RING_TYPE = 5
@@ -71,20 +71,9 @@ def perceive_features(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n
     patterns (bit k = atom k), ascending as unsigned integers, zero beyond the count; a count above `MAX_RINGS` is the
     true count, with the first `MAX_RINGS` masks.  Exact: the same bits whatever the batch, the row and the padded width.
     ValueError before the kernel: W > 64, shapes that do not fit, atom counts outside [0, W]."""
-    from .cheminformatics import check_n_nodes
-    bonds = torch.as_tensor(bond_orders)
-    z = torch.as_tensor(atomic_numbers)
-    if bonds.dim() != 3 or bonds.shape[1] != bonds.shape[2]:
-        raise ValueError(f"bond_orders must be [B,W,W], got {list(bonds.shape)}")
-    B, W = int(bonds.shape[0]), int(bonds.shape[1])
-    if W > MAX_ATOMS:
-        raise ValueError(f"pharmacophore features take molecules of at most {MAX_ATOMS} atoms, got a width of {W}")
-    if z.dim() != 2 or z.shape[0] != B or z.shape[1] < W:
-        raise ValueError(f"atomic_numbers must be [B, >= W] = [{B}, >= {W}], got {list(z.shape)}")
-    if bonds.dtype.is_floating_point or z.dtype.is_floating_point:
-        raise ValueError("atomic_numbers and bond_orders must be integer tensors")
-    check_n_nodes(n_nodes, B, W)
-    dev = torch.device(device if device is not None else (bonds.device if bonds.is_cuda else "cuda:0"))
+    z, bonds, B, W = _args.graph_arguments(atomic_numbers, bond_orders, n_nodes, MAX_ATOMS,
+                                           f"pharmacophore features take molecules of at most {MAX_ATOMS} atoms")
+    dev = _args.resolve_device(device, bonds)
     if W == 0:                                  # no atoms anywhere: B empty graphs at the kernel's smallest width
         z, bonds, W = torch.zeros(B, 1, dtype=torch.int32), torch.zeros(B, 1, 1, dtype=torch.int8), 1
     types = torch.zeros(B, W, dtype=torch.uint8, device=dev)
@@ -92,9 +81,7 @@ def perceive_features(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n
     count = torch.zeros(B, dtype=torch.int32, device=dev)
     if B == 0:
         return types, rings, count
-    zd = z[:, :W].to(dev, torch.int32).contiguous()
-    bd = bonds.to(dev, torch.int8).contiguous()
-    nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B).contiguous()
+    zd, bd, nn = _args.device_graph(z, bonds, n_nodes, B, W, dev)
     _lib.check(_lib.lib().mcg_pharm_perceive(_lib.dptr(zd), _lib.dptr(bd), _lib.dptr(nn), B, W, _lib.dptr(types),
                                              _lib.dptr(count), _lib.dptr(rings), _lib.current_stream_ptr(dev)),
                "mcg_pharm_perceive")
@@ -106,7 +93,7 @@ def reference_self_overlap(reference_features: Features, device=None) -> torch.T
     """O(R,R) [1] fp64 on the device: the reference's feature list run through `mcg_pharm_score` as a one-row batch against
     itself - the kernel and the summation order of every other overlap."""
     xyz, typ = reference_features
-    dev = torch.device(device if device is not None else "cuda:0")
+    dev = _args.resolve_device(device)
     out = _score_launch(None, None, None, None, None, 1, 1, 1, xyz.to(dev), typ.to(dev), None, dev, False)
     return out["o_mm"]
 
@@ -152,9 +139,8 @@ def score_features(reference_features: Features, coords: torch.Tensor, n_nodes: 
     if tuple(r.shape) != (B, MAX_RINGS) or r.dtype != torch.int64 or k.numel() != B:
         raise ValueError(f"ring_mask must be [B, {MAX_RINGS}] int64 and n_rings [B], got {list(r.shape)} of type "
                          f"{r.dtype} and {list(k.shape)}")
-    from .cheminformatics import check_n_nodes
-    check_n_nodes(n_nodes, B, min(N, W))
-    dev = torch.device(device if device is not None else (c.device if c.is_cuda else "cuda:0"))
+    _args.check_n_nodes(n_nodes, B, min(N, W))
+    dev = _args.resolve_device(device, c)
     xyz, typ = xyz.to(dev), typ.to(dev)
     o_rr = reference_self_overlap((xyz, typ), dev)
     return _score_launch(c.to(dev, torch.float32).contiguous(),
@@ -249,23 +235,6 @@ def select_score(shape: Optional[float], pharmacophore: Optional[float]) -> Opti
     return shape + pharmacophore
 
 
-def check_threshold(name: str, value) -> float:
-    """A pharmacophore Tanimoto threshold (`min_pharmacophore_tanimoto`) as a float: a real number in [0, 1] (not a bool,
-    not NaN), else ValueError."""
-    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not (0.0 <= float(value) <= 1.0):
-        raise ValueError(f"{name} must be a real number in [0, 1], got {value!r}")
-    return float(value)
-
-
-def check_flag(name: str, value) -> bool:
-    """An on / off option as a bool; anything but True or False is a ValueError."""
-    if value is not True and value is not False:
-        raise ValueError(f"{name} must be True or False, got {value!r}")
-    return value
-
-
-def check_rank_by(value) -> str:
-    """`rank_by` as "shape" or "combo", else ValueError."""
-    if value not in ("shape", "combo"):
-        raise ValueError(f"rank_by must be 'shape' or 'combo', got {value!r}")
-    return value
+check_threshold = functools.partial(_args.check_real, low=0.0, high=1.0)      # (name, value): `min_pharmacophore_tanimoto`
+check_flag = _args.check_flag
+check_rank_by = _args.check_rank_by

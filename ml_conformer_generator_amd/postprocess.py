@@ -33,28 +33,31 @@ Stages, in this order:
        (`last_valid_fraction`);
     6. `select`, written once for both paths: `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`,
        `min_pharmacophore_tanimoto`, `min_electrostatic_tanimoto`, `max_interaction_score`, `require_substructures`,
-       `exclude_substructures`, `exclude_graphs`, `unique`, then the threshold / sphere exclusion / `top_k` walk of `cheminformatics.select_diverse`.  The two pair matrices are
-       computed only when their threshold is set, over the rows that survived the filters.
+       `exclude_substructures`, `exclude_graphs`, `unique`, then the threshold / sphere exclusion / `top_k` walk of
+       `cheminformatics.select_diverse`.  The two pair matrices are computed only when their threshold is set, over the
+       rows that survived the filters.
 A call with no option on takes none of these steps: its records / live Mols are returned as they come.
 `standardize` is not a stage here: the generator standardises right behind the bond write-back, so the result tensors
 that arrive are already the parent fragments'; its four per-sample tensors (`atoms_removed`, `n_fragments`, `atom_map`,
 `kekule_bond_orders`) ride through the gather and into each record's `Measured` like the strain energies do.
 
-The device work goes through the generator's seams (`_pose`, `_score`, `_pair`, `_receptor_coords`,
-`_relieve`, `_optimise_pose`, `_score_placed`, `_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, `_pharm_perceive`, `_pharm_score`,
-`_add_hydrogens`, `_peoe_charges`, `_esp_score`, `_canonical_order`, `_match_substructures`, `_interaction_scores`),
-looked up on the instance at the time of the call.  The shape
-seams take the request's reference object; which kind it is - a conformer or a solid - is `cheminformatics`' business."""
+The device work goes through the generator's seams (`_pose`, `_score`, `_pair`, `_receptor_coords`, `_relieve`,
+`_optimise_pose`, `_score_placed`, `_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, `_pharm_perceive`,
+`_pharm_score`, `_add_hydrogens`, `_peoe_charges`, `_esp_score`, `_canonical_order`, `_match_substructures`,
+`_interaction_scores`), looked up on the instance at the time of the call.  The shape seams take the request's reference
+object; which kind it is - a conformer or a solid - is `cheminformatics`' business."""
 from __future__ import annotations
 
 import dataclasses
-import numbers
+import inspect
 import time
+import types
 import warnings
 from typing import List, NamedTuple, Optional, Union
 
 import torch
 
+from . import _args
 from . import canonical as mcg_canonical
 from . import cheminformatics
 from . import electrostatics as mcg_esp
@@ -171,276 +174,341 @@ class Request:
         return measured.shape_tanimoto
 
 
-def parse_request(gen, reference_conformer, shape_scores: bool = False, top_k: Optional[int] = None,
-                  min_shape_tanimoto: Optional[float] = None, overlay: bool = False,
+def parse_request(gen, reference_conformer, *, reference_context=None, shape_scores: bool = False,
+                  top_k: Optional[int] = None, min_shape_tanimoto: Optional[float] = None, overlay: bool = False,
                   max_pairwise_tanimoto: Optional[float] = None, refine_overlay: Union[bool, int] = False, receptor=None,
-                  max_receptor_clashes: Optional[int] = None, chemical_scores=False, reference_graph=None,
-                  max_chemical_tanimoto: Optional[float] = None, unique=False,
+                  max_receptor_clashes: Optional[int] = None, chemical_scores: bool = False, reference_graph=None,
+                  max_chemical_tanimoto: Optional[float] = None, unique: Union[bool, str] = False,
                   max_pairwise_chemical_tanimoto: Optional[float] = None, reference_shape=None,
                   shape_density: float = 0.02, max_atoms_outside: Optional[int] = None,
-                  reference_context=None, relax_geometry: Union[bool, int] = False, pharmacophore_scores=False,
+                  relax_geometry: Union[bool, int] = False, pharmacophore_scores: bool = False,
                   reference_pharmacophore=None, min_pharmacophore_tanimoto: Optional[float] = None,
-                  rank_by: str = "shape", relieve_clashes: Union[bool, int] = False, add_hydrogens=False,
-                  standardize=False, electrostatic_scores=False, reference_charges=None,
-                  min_electrostatic_tanimoto: Optional[float] = None, partial_charges=False, smiles=False,
-                  exclude_graphs=None, require_substructures=None, exclude_substructures=None,
-                  substructure_counts=None, interaction_scores=False,
+                  rank_by: str = "shape", relieve_clashes: Union[bool, int] = False, add_hydrogens: bool = False,
+                  standardize: bool = False, electrostatic_scores: bool = False, reference_charges=None,
+                  min_electrostatic_tanimoto: Optional[float] = None, partial_charges: bool = False,
+                  smiles: bool = False, exclude_graphs=None, require_substructures=None, exclude_substructures=None,
+                  substructure_counts=None, interaction_scores: bool = False,
                   max_interaction_score: Optional[float] = None, optimise_pose: Union[bool, int] = False) -> Request:
     """The public option keywords of a generation entry of `gen` as a `Request`: the shape options first, then the chemical
     ones (`top_k` / `min_shape_tanimoto` / `max_pairwise_tanimoto` imply the shape score, `max_chemical_tanimoto` the
-    chemical one).  `reference_shape`: a watertight mesh in place of the reference conformer (`mesh.load_mesh`); the
-    request then carries its `cheminformatics.SolidReference` (host side only: nothing is launched here), whether or not an
-    option is on.  `relax_geometry`: `geometry.check_steps`; it works with every other option and every finisher.
-    `pharmacophore_scores` (implied by `min_pharmacophore_tanimoto`) needs `overlay`; the reference's features are
-    `reference_pharmacophore` (`pharmacophore.load_reference_features`) or are perceived, behind the generation, from the
-    reference's graph (`reference_graph`, else a reference conformer with bonds) at the reference conformer's coordinates.
-    `rank_by="combo"` needs the shape and the pharmacophore score.  `relieve_clashes`: `receptor.check_relief_steps`
-    (True = `receptor.RELIEF_STEPS`); it needs a `receptor`, and with it `overlay`.  `add_hydrogens`: True or False; it
-    works with every other option, but not with a finisher, RDKit's or a custom one (the hydrogens go onto the records).
-    `standardize`: True or False; likewise refused with a finisher (RDKit's `standardize_mol` already does it on Mols).
-    `electrostatic_scores` (implied by `min_electrostatic_tanimoto`, a real number in [-1, 1]) needs `overlay`; the
-    reference's charge points are `reference_charges` (`electrostatics.load_reference_charges`) or are computed, behind the
-    generation, from the reference's graph (`reference_graph`, else a reference conformer with bonds) on the reference
-    conformer's coordinates, its hydrogens placed by the same kernel.  `rank_by="electrostatic"` needs the shape and the
-    electrostatic score.  `partial_charges`: True or False; it needs no reference and no pose.  Both are refused with a
-    finisher: they read the placed hydrogens of the records.
-    `smiles`: True or False; refused with a finisher (the order and the string go onto the records).  `unique`: False,
-    True or "exact" - one row per exact identity (`canonical.identity_bytes`) instead of per `graph_key`; it reads the
-    Mols' own graphs through RDKit's finisher and is refused with a custom one.  `exclude_graphs`: an iterable of
-    `GeneratedMolecule`, Mols or (atomic_numbers, bond_orders) pairs (`fingerprint.mol_graph`) whose exact identities the
-    call drops; an entry that is unreadable or has more than 64 heavy atoms is a ValueError naming its position.  The
-    graphs are only read here; the entries label them (`label_excluded`, one `_canonical_order` launch per 16 384) behind
-    their own argument checks, directly in front of the generation, where one without a canonical order is refused.
-    `require_substructures` / `exclude_substructures` / `substructure_counts`: each None or an iterable of pattern strings
-    (`substructure.parse`), `substructure.Pattern`s or graph sources (`substructure.from_graph`); they are compiled here,
-    together (`compile_substructures`: host work), and an entry that cannot be read or breaks a limit is a ValueError
-    naming its list and position; refused with a custom finisher, through RDKit's the Mols' own graphs are read.
-    `interaction_scores` (implied by `max_interaction_score`, a finite real number) needs a `receptor` - and with it
-    `overlay` -, which is typed, sorted and given its tile spheres here (`interactions.prepare_receptor`: host work, one
-    warning where atoms lie outside the residue templates); a (coords, atomic_numbers, types) triple carries its own
-    types.  `rank_by="interaction"` needs the score.  Refused with a finisher: the values go onto the records.
-    `optimise_pose`: `receptor.check_relief_steps` (True = `interactions.OPTIMISE_STEPS`); it needs a `receptor`, and
-    with it `overlay`, implies `interaction_scores` and is refused with a finisher likewise.
+    chemical one).  Keyword only, behind `reference_context` in the entries' own names, order and defaults
+    (`REQUEST_KEYWORDS`, `entry_request`).  Each family of options is read by its own helper, in the order below; what a
+    helper's options mean is in its docstring.  `relax_geometry`: `geometry.check_steps`; it works with every other option
+    and every finisher.
     Every refusal happens here, before any device work."""
-    mcg_pharm.check_flag("smiles", smiles)
-    if smiles and getattr(gen, "finisher", None) is not None:
-        raise ValueError(mcg_canonical.REFUSAL_WITH_FINISHER)
-    mcg_pharm.check_flag("add_hydrogens", add_hydrogens)
-    if add_hydrogens and getattr(gen, "finisher", None) is not None:
-        raise ValueError(mcg_hydrogens.REFUSAL_WITH_FINISHER)
-    mcg_pharm.check_flag("standardize", standardize)
-    if standardize and getattr(gen, "finisher", None) is not None:
-        raise ValueError(mcg_standardize.REFUSAL_WITH_FINISHER)
-    mcg_pharm.check_flag("electrostatic_scores", electrostatic_scores)
-    mcg_pharm.check_flag("partial_charges", partial_charges)
-    if min_electrostatic_tanimoto is not None:
-        mcg_esp.check_threshold("min_electrostatic_tanimoto", min_electrostatic_tanimoto)
-    esp = electrostatic_scores or min_electrostatic_tanimoto is not None
-    if (esp or partial_charges) and getattr(gen, "finisher", None) is not None:
-        raise ValueError(mcg_esp.REFUSAL_WITH_FINISHER)
-    if reference_charges is not None and not esp:
-        raise ValueError("reference_charges is only read with electrostatic_scores or min_electrostatic_tanimoto")
-    if esp and not overlay:
-        raise ValueError("electrostatic_scores needs overlay=True: molecules that are not posed onto the reference are not "
-                         "in the coordinates of its charges")
-    mcg_pharm.check_flag("interaction_scores", interaction_scores)
-    if max_interaction_score is not None:
-        mcg_interactions.check_threshold("max_interaction_score", max_interaction_score)
-    mcg_interactions.check_rank_by(rank_by)
-    optimise_steps = 0
-    if optimise_pose is not False:
-        optimise_steps = mcg_receptor.check_relief_steps(optimise_pose, "optimise_pose", lowest=1,
-                                                         if_true=mcg_interactions.OPTIMISE_STEPS)
-        if getattr(gen, "finisher", None) is not None:
-            raise ValueError(mcg_interactions.OPTIMISE_REFUSAL_WITH_FINISHER)
-        if receptor is None:
-            raise ValueError("optimise_pose needs a receptor: it moves the posed molecules to where their interaction "
-                             "score with it is lower")
-    interact = interaction_scores or max_interaction_score is not None or optimise_steps > 0
-    if rank_by == "interaction" and not interact:
-        raise ValueError("rank_by='interaction' needs interaction_scores (or max_interaction_score): it ranks by the "
-                         "interaction score")
-    if interact and getattr(gen, "finisher", None) is not None:
-        raise ValueError(mcg_interactions.REFUSAL_WITH_FINISHER)
-    if interact and receptor is None:
-        raise ValueError("interaction_scores needs a receptor: it scores the posed molecules against it")
-    relax_steps = mcg_geometry.check_steps(relax_geometry)
-    custom_finisher = isinstance(getattr(gen, "finisher", None), host_pool.TaskRef)
-    shape = {}
-    solid = None
-    if reference_shape is not None:
-        if (reference_conformer is not None and reference_conformer is not False) or reference_context is not None:
-            raise ValueError("reference_shape cannot be combined with reference_conformer or reference_context: pass "
-                             "one reference")
-        if isinstance(shape_density, bool) or not isinstance(shape_density, numbers.Real) or not (
-                0.0 < float(shape_density) < float("inf")):
-            raise ValueError(f"shape_density must be a positive real number, got {shape_density!r}")
-        if refine_overlay is not False:
-            raise ValueError("refine_overlay cannot be combined with reference_shape: the ascent's objective is the "
-                             "overlap with the reference's atoms, and a mesh has none")
-        if receptor is not None or max_receptor_clashes is not None:
-            raise ValueError("receptor cannot be combined with reference_shape: the receptor check needs the reference's "
-                             "atoms")
-        solid = cheminformatics.solid_reference(reference_shape)
-    if max_atoms_outside is not None:
-        cheminformatics.check_max_atoms_outside(max_atoms_outside)
-        if solid is None:
-            raise ValueError("max_atoms_outside needs a reference_shape")
-        if not overlay:
-            raise ValueError("max_atoms_outside needs overlay=True: molecules that are not posed into the mesh are not "
-                             "in its coordinates")
-    common = dict(reference=solid, max_atoms_outside=max_atoms_outside, relax_steps=relax_steps,
-                  add_hydrogens=add_hydrogens, standardize=bool(standardize), partial_charges=partial_charges,
-                  smiles=smiles)
-    if max_receptor_clashes is not None:
-        mcg_receptor.check_max_receptor_clashes(max_receptor_clashes)
-        if receptor is None:
-            raise ValueError("max_receptor_clashes needs a receptor")
-    relief_steps = 0
-    if relieve_clashes is not False:
-        relief_steps = mcg_receptor.check_relief_steps(relieve_clashes, "relieve_clashes", lowest=1,
-                                                       if_true=mcg_receptor.RELIEF_STEPS)
-        if receptor is None:
-            raise ValueError("relieve_clashes needs a receptor: it moves the posed molecules out of their contacts with it")
-    if receptor is not None and not overlay:
-        raise ValueError("receptor needs overlay=True: molecules that are not posed onto the reference are not in "
-                         "the receptor's frame")
-    refine_steps = 0
-    if refine_overlay is not False:
-        refine_steps = cheminformatics.check_refine_steps(refine_overlay, "refine_overlay", lowest=1, if_true=64)
-        if not overlay:
-            raise ValueError("refine_overlay needs overlay=True: it refines the pose onto the reference")
-    scoring = shape_scores or top_k is not None or min_shape_tanimoto is not None or max_pairwise_tanimoto is not None
-    if scoring or overlay:
-        if max_pairwise_tanimoto is not None:
-            cheminformatics.check_max_pairwise_tanimoto(max_pairwise_tanimoto)
-            if not overlay:
-                raise ValueError("max_pairwise_tanimoto needs overlay=True: molecules that are not posed onto the reference "
-                                 "share no frame to compare them in")
-        what = "shape scores" if not overlay else "overlay"
-        if top_k is not None:
-            cheminformatics.check_top_k(top_k)
-        if min_shape_tanimoto is not None:
-            cheminformatics.check_min_shape_tanimoto(min_shape_tanimoto)
-        if solid is None and (reference_conformer is None or reference_conformer is False):
-            raise ValueError(f"a reference conformer is needed for {what}; a bare reference_context has no "
-                             "coordinates")
-        if custom_finisher:
-            raise ValueError(f"{what} cannot be combined with a custom finisher: its results carry no coordinates "
-                             "this package can read")
-        if solid is None:
-            common["reference"] = cheminformatics.ConformerReference(gen._reference_coord(reference_conformer))
-        rec = None
+    o = types.SimpleNamespace(**locals())          # the options as given: a helper reads `o.<keyword>`, what was derived
+    finisher = getattr(gen, "finisher", None)      # from them is handed to it by name
+    custom_finisher = isinstance(finisher, host_pool.TaskRef)
+    fields = _record_flags(o, finisher)
+    esp = _electrostatic_flags(o, finisher)
+    interact, optimise_steps = _interaction_flags(o, finisher)
+    fields.update(partial_charges=partial_charges, relax_steps=mcg_geometry.check_steps(relax_geometry))
+    fields.update(_mesh_reference(o))
+    solid = fields["reference"]
+    relief = _receptor_flags(o)
+    shape = _shape_fields(o, custom_finisher, solid)
+    if shape:                                     # the call scores shape or poses: the receptor's options are its fields
+        fields.update(shape, **relief)
         if receptor is not None:                  # refused with a mesh above: the reference is a conformer
-            typed = isinstance(receptor, (tuple, list)) and len(receptor) == 3      # (coords, atomic_numbers, types)
-            rec = mcg_receptor.load_receptor((receptor[0], receptor[1]) if typed else receptor)
-            mcg_receptor.check_clear_of_reference(rec[0], common["reference"].coords)
-            if interact:
-                common.update(scores_interactions=True, max_interaction_score=max_interaction_score, rank_by=rank_by,
-                              typed_receptor=mcg_interactions.prepare_receptor(receptor), optimise_steps=optimise_steps)
-        shape = dict(overlay=bool(overlay), scores_shape=bool(scoring), top_k=top_k,
-                     min_shape_tanimoto=min_shape_tanimoto, max_pairwise_tanimoto=max_pairwise_tanimoto,
-                     refine_steps=refine_steps, receptor=rec, max_receptor_clashes=max_receptor_clashes,
-                     relief_steps=relief_steps)
-
-    mcg_pharm.check_flag("pharmacophore_scores", pharmacophore_scores)
+            fields.update(_receptor_fields(o, fields["reference"], interact, optimise_steps))
+    scores_shape = fields.get("scores_shape")
+    _args.check_flag("pharmacophore_scores", pharmacophore_scores)
     if min_pharmacophore_tanimoto is not None:
         mcg_pharm.check_threshold("min_pharmacophore_tanimoto", min_pharmacophore_tanimoto)
-    pharm = pharmacophore_scores or min_pharmacophore_tanimoto is not None
-    if rank_by == "electrostatic" and not (esp and shape.get("scores_shape")):
+    conformer = None if solid is not None else fields["reference"]
+    fields.update(_electrostatic_fields(o, esp, scores_shape, conformer))
+    fields.update(_pharmacophore_fields(o, scores_shape, conformer))
+    _args.check_flag("chemical_scores", chemical_scores)
+    if not (isinstance(unique, str) and unique == "exact"):
+        _args.check_flag("unique", unique)
+    excluded = None if exclude_graphs is None else read_excluded(exclude_graphs)
+    fields.update(_substructure_fields(o, custom_finisher))
+    graph_read = fields.get("ref_pharm_graph") is not None or fields.get("ref_charge_graph") is not None
+    fields.update(_chemistry_fields(o, custom_finisher, excluded, graph_read))
+    return Request(**fields)
+
+
+REQUEST_KEYWORDS = tuple(name for name, p in inspect.signature(parse_request).parameters.items()
+                         if p.kind is inspect.Parameter.KEYWORD_ONLY)      # `reference_context`, then the options
+
+
+def entry_request(gen, arguments: dict) -> Request:
+    """`parse_request` for a generation entry: `arguments` is the entry's `locals()`, out of which the reference conformer
+    and every keyword of `REQUEST_KEYWORDS` is handed on under its own name."""
+    return parse_request(gen, arguments["reference_conformer"], **{name: arguments[name] for name in REQUEST_KEYWORDS})
+
+
+def _record_flags(o, finisher) -> dict:
+    """`smiles`: True or False; refused with a finisher (the order and the string go onto the records).
+    `add_hydrogens`: True or False; it works with every other option, but not with a finisher, RDKit's or a custom one
+    (the hydrogens go onto the records).  `standardize`: True or False; likewise refused with a finisher (RDKit's
+    `standardize_mol` already does it on Mols)."""
+    for name, refusal in (("smiles", mcg_canonical.REFUSAL_WITH_FINISHER),
+                          ("add_hydrogens", mcg_hydrogens.REFUSAL_WITH_FINISHER),
+                          ("standardize", mcg_standardize.REFUSAL_WITH_FINISHER)):
+        if _args.check_flag(name, getattr(o, name)) and finisher is not None:
+            raise ValueError(refusal)
+    return dict(smiles=o.smiles, add_hydrogens=o.add_hydrogens, standardize=bool(o.standardize))
+
+
+def _electrostatic_flags(o, finisher) -> bool:
+    """Whether the call scores electrostatics: `electrostatic_scores` (implied by `min_electrostatic_tanimoto`, a real
+    number in [-1, 1]) needs `overlay`.  `partial_charges`: True or False; it needs no reference and no pose.  Both are
+    refused with a finisher: they read the placed hydrogens of the records."""
+    _args.check_flag("electrostatic_scores", o.electrostatic_scores)
+    _args.check_flag("partial_charges", o.partial_charges)
+    if o.min_electrostatic_tanimoto is not None:
+        mcg_esp.check_threshold("min_electrostatic_tanimoto", o.min_electrostatic_tanimoto)
+    esp = o.electrostatic_scores or o.min_electrostatic_tanimoto is not None
+    if (esp or o.partial_charges) and finisher is not None:
+        raise ValueError(mcg_esp.REFUSAL_WITH_FINISHER)
+    if o.reference_charges is not None and not esp:
+        raise ValueError("reference_charges is only read with electrostatic_scores or min_electrostatic_tanimoto")
+    if esp and not o.overlay:
+        raise ValueError("electrostatic_scores needs overlay=True: molecules that are not posed onto the reference are not "
+                         "in the coordinates of its charges")
+    return esp
+
+
+def _interaction_flags(o, finisher):
+    """(whether the call scores interactions, the trials of `optimise_pose`).  `interaction_scores` (implied by
+    `max_interaction_score`, a finite real number) needs a `receptor` - and with it `overlay`.  `rank_by="interaction"`
+    needs the score.  Refused with a finisher: the values go onto the records.  `optimise_pose`:
+    `receptor.check_relief_steps` (True = `interactions.OPTIMISE_STEPS`); it needs a `receptor`, and with it `overlay`,
+    implies `interaction_scores` and is refused with a finisher likewise."""
+    _args.check_flag("interaction_scores", o.interaction_scores)
+    if o.max_interaction_score is not None:
+        mcg_interactions.check_threshold("max_interaction_score", o.max_interaction_score)
+    _args.check_rank_by(o.rank_by)
+    optimise_steps = 0
+    if o.optimise_pose is not False:
+        optimise_steps = mcg_receptor.check_relief_steps(o.optimise_pose, "optimise_pose", lowest=1,
+                                                         if_true=mcg_interactions.OPTIMISE_STEPS)
+        if finisher is not None:
+            raise ValueError(mcg_interactions.OPTIMISE_REFUSAL_WITH_FINISHER)
+        if o.receptor is None:
+            raise ValueError("optimise_pose needs a receptor: it moves the posed molecules to where their interaction "
+                             "score with it is lower")
+    interact = o.interaction_scores or o.max_interaction_score is not None or optimise_steps > 0
+    if o.rank_by == "interaction" and not interact:
+        raise ValueError("rank_by='interaction' needs interaction_scores (or max_interaction_score): it ranks by the "
+                         "interaction score")
+    if interact and finisher is not None:
+        raise ValueError(mcg_interactions.REFUSAL_WITH_FINISHER)
+    if interact and o.receptor is None:
+        raise ValueError("interaction_scores needs a receptor: it scores the posed molecules against it")
+    return interact, optimise_steps
+
+
+def _mesh_reference(o) -> dict:
+    """`reference_shape`: a watertight mesh in place of the reference conformer (`mesh.load_mesh`); the request then
+    carries its `cheminformatics.SolidReference` (host side only: nothing is launched here), whether or not an option is
+    on.  `max_atoms_outside` needs it, and `overlay`."""
+    solid = None
+    if o.reference_shape is not None:
+        if (o.reference_conformer is not None and o.reference_conformer is not False) or o.reference_context is not None:
+            raise ValueError("reference_shape cannot be combined with reference_conformer or reference_context: pass "
+                             "one reference")
+        _args.check_real("shape_density", o.shape_density, 0.0, open_low=True)
+        if o.refine_overlay is not False:
+            raise ValueError("refine_overlay cannot be combined with reference_shape: the ascent's objective is the "
+                             "overlap with the reference's atoms, and a mesh has none")
+        if o.receptor is not None or o.max_receptor_clashes is not None:
+            raise ValueError("receptor cannot be combined with reference_shape: the receptor check needs the reference's "
+                             "atoms")
+        solid = cheminformatics.solid_reference(o.reference_shape)
+    if o.max_atoms_outside is not None:
+        cheminformatics.check_max_atoms_outside(o.max_atoms_outside)
+        if solid is None:
+            raise ValueError("max_atoms_outside needs a reference_shape")
+        if not o.overlay:
+            raise ValueError("max_atoms_outside needs overlay=True: molecules that are not posed into the mesh are not "
+                             "in its coordinates")
+    return dict(reference=solid, max_atoms_outside=o.max_atoms_outside)
+
+
+def _receptor_flags(o) -> dict:
+    """`max_receptor_clashes` needs a `receptor`.  `relieve_clashes`: `receptor.check_relief_steps` (True =
+    `receptor.RELIEF_STEPS`); it needs a `receptor`, and with it `overlay`."""
+    if o.max_receptor_clashes is not None:
+        mcg_receptor.check_max_receptor_clashes(o.max_receptor_clashes)
+        if o.receptor is None:
+            raise ValueError("max_receptor_clashes needs a receptor")
+    relief_steps = 0
+    if o.relieve_clashes is not False:
+        relief_steps = mcg_receptor.check_relief_steps(o.relieve_clashes, "relieve_clashes", lowest=1,
+                                                       if_true=mcg_receptor.RELIEF_STEPS)
+        if o.receptor is None:
+            raise ValueError("relieve_clashes needs a receptor: it moves the posed molecules out of their contacts with it")
+    if o.receptor is not None and not o.overlay:
+        raise ValueError("receptor needs overlay=True: molecules that are not posed onto the reference are not in "
+                         "the receptor's frame")
+    return dict(max_receptor_clashes=o.max_receptor_clashes, relief_steps=relief_steps)
+
+
+def _shape_fields(o, custom_finisher, solid) -> dict:
+    """The shape options; {} for a call that neither scores shape nor poses.  `top_k` / `min_shape_tanimoto` /
+    `max_pairwise_tanimoto` imply the shape score; `max_pairwise_tanimoto` and `refine_overlay`
+    (`cheminformatics.check_refine_steps`, True = 64) need `overlay`.  Without a mesh the request's reference is the
+    `ConformerReference` of the reference conformer."""
+    refine_steps = 0
+    if o.refine_overlay is not False:
+        refine_steps = cheminformatics.check_refine_steps(o.refine_overlay, "refine_overlay", lowest=1, if_true=64)
+        if not o.overlay:
+            raise ValueError("refine_overlay needs overlay=True: it refines the pose onto the reference")
+    scoring = o.shape_scores or not (o.top_k is None and o.min_shape_tanimoto is None and o.max_pairwise_tanimoto is None)
+    if not (scoring or o.overlay):
+        return {}
+    if o.max_pairwise_tanimoto is not None:
+        cheminformatics.check_max_pairwise_tanimoto(o.max_pairwise_tanimoto)
+        if not o.overlay:
+            raise ValueError("max_pairwise_tanimoto needs overlay=True: molecules that are not posed onto the reference "
+                             "share no frame to compare them in")
+    what = "shape scores" if not o.overlay else "overlay"
+    if o.top_k is not None:
+        cheminformatics.check_top_k(o.top_k)
+    if o.min_shape_tanimoto is not None:
+        cheminformatics.check_min_shape_tanimoto(o.min_shape_tanimoto)
+    if solid is None and (o.reference_conformer is None or o.reference_conformer is False):
+        raise ValueError(f"a reference conformer is needed for {what}; a bare reference_context has no "
+                         "coordinates")
+    if custom_finisher:
+        raise ValueError(f"{what} cannot be combined with a custom finisher: its results carry no coordinates "
+                         "this package can read")
+    fields = dict(overlay=bool(o.overlay), scores_shape=bool(scoring), top_k=o.top_k, refine_steps=refine_steps,
+                  min_shape_tanimoto=o.min_shape_tanimoto, max_pairwise_tanimoto=o.max_pairwise_tanimoto)
+    if solid is None:
+        fields["reference"] = cheminformatics.ConformerReference(o.gen._reference_coord(o.reference_conformer))
+    return fields
+
+
+def _receptor_fields(o, reference, interact, optimise_steps) -> dict:
+    """The receptor of a posed call, loaded and checked to be clear of the reference conformer; where the call scores
+    interactions it is also typed, sorted and given its tile spheres here (`interactions.prepare_receptor`: host work,
+    one warning where atoms lie outside the residue templates); a (coords, atomic_numbers, types) triple carries its own
+    types."""
+    typed = isinstance(o.receptor, (tuple, list)) and len(o.receptor) == 3      # (coords, atomic_numbers, types)
+    rec = mcg_receptor.load_receptor((o.receptor[0], o.receptor[1]) if typed else o.receptor)
+    mcg_receptor.check_clear_of_reference(rec[0], reference.coords)
+    if not interact:
+        return dict(receptor=rec)
+    return dict(receptor=rec, scores_interactions=True, max_interaction_score=o.max_interaction_score, rank_by=o.rank_by,
+                typed_receptor=mcg_interactions.prepare_receptor(o.receptor), optimise_steps=optimise_steps)
+
+
+def _reference_graph(o, missing: str, max_atoms: int, placed: Optional[str] = None, conformer=None):
+    """The reference's heavy-atom graph (`fingerprint.mol_graph`) of `reference_graph`, else of a reference conformer with
+    bonds; ValueError(`missing`) where there is neither.  `placed` ("features", "charges"): the graph is laid onto the
+    atoms of `conformer`, the request's `ConformerReference` (None with a `reference_shape`: refused likewise), and
+    must have as many heavy atoms, at most `max_atoms`; the result is then (atomic numbers, bond codes, coords)."""
+    src = o.reference_graph
+    if src is None and hasattr(o.reference_conformer, "GetAtoms") and hasattr(o.reference_conformer, "GetBonds"):
+        src = o.reference_conformer
+    if src is None or (placed is not None and conformer is None):
+        raise ValueError(missing)
+    z, bonds = mcg_fp.mol_graph(src)
+    if placed is None:
+        if not 1 <= len(z) <= max_atoms:
+            raise ValueError(f"the reference graph must have 1 to {max_atoms} heavy atoms, got {len(z)}")
+        return z, bonds
+    coords = conformer.coords
+    if not 1 <= len(z) <= max_atoms or len(z) != int(coords.shape[0]):
+        raise ValueError(f"the reference graph has {len(z)} heavy atoms, the reference conformer "
+                         f"{int(coords.shape[0])}: the {placed} are placed on the conformer's atoms, in the "
+                         f"graph's order (at most {max_atoms})")
+    return z, bonds, coords
+
+
+def _electrostatic_fields(o, esp, scores_shape, conformer) -> dict:
+    """The reference's charge points are `reference_charges` (`electrostatics.load_reference_charges`) or are computed,
+    behind the generation, from the reference's graph (`reference_graph`, else a reference conformer with bonds) on the
+    reference conformer's coordinates, its hydrogens placed by the same kernel.  `rank_by="electrostatic"` needs the shape
+    and the electrostatic score."""
+    if o.rank_by == "electrostatic" and not (esp and scores_shape):
         raise ValueError("rank_by='electrostatic' needs shape scores (shape_scores, top_k, min_shape_tanimoto or "
                          "max_pairwise_tanimoto) and electrostatic_scores: it ranks by their sum")
-    if esp:
-        common.update(scores_electrostatics=True, min_electrostatic_tanimoto=min_electrostatic_tanimoto, rank_by=rank_by)
-        if reference_charges is not None:
-            common["ref_charge_points"] = mcg_esp.load_reference_charges(reference_charges)
-        else:
-            src = reference_graph
-            if src is None and hasattr(reference_conformer, "GetAtoms") and hasattr(reference_conformer, "GetBonds"):
-                src = reference_conformer
-            if src is None or solid is not None:
-                raise ValueError("electrostatic scores need the reference's charges: pass reference_charges= (a sequence "
-                                 "of (charge, (x, y, z)) in the reference's coordinates - the only way with a "
-                                 "reference_shape) or the reference's molecular graph (reference_graph=, or a reference "
-                                 "conformer with bonds)")
-            z, bonds = mcg_fp.mol_graph(src)
-            coords = common["reference"].coords
-            if not 1 <= len(z) <= mcg_esp.MAX_ATOMS or len(z) != int(coords.shape[0]):
-                raise ValueError(f"the reference graph has {len(z)} heavy atoms, the reference conformer "
-                                 f"{int(coords.shape[0])}: the charges are placed on the conformer's atoms, in the "
-                                 f"graph's order (at most {mcg_esp.MAX_ATOMS})")
-            common["ref_charge_graph"] = (z, bonds, coords)
-    if reference_pharmacophore is not None and not pharm:
+    if not esp:
+        return {}
+    fields = dict(scores_electrostatics=True, min_electrostatic_tanimoto=o.min_electrostatic_tanimoto, rank_by=o.rank_by)
+    if o.reference_charges is not None:
+        return dict(fields, ref_charge_points=mcg_esp.load_reference_charges(o.reference_charges))
+    return dict(fields, ref_charge_graph=_reference_graph(
+        o, "electrostatic scores need the reference's charges: pass reference_charges= (a sequence "
+        "of (charge, (x, y, z)) in the reference's coordinates - the only way with a "
+        "reference_shape) or the reference's molecular graph (reference_graph=, or a reference "
+        "conformer with bonds)", mcg_esp.MAX_ATOMS, "charges", conformer))
+
+
+def _pharmacophore_fields(o, scores_shape, conformer) -> dict:
+    """`pharmacophore_scores` (implied by `min_pharmacophore_tanimoto`) needs `overlay`; the reference's features are
+    `reference_pharmacophore` (`pharmacophore.load_reference_features`) or are perceived, behind the generation, from the
+    reference's graph (`reference_graph`, else a reference conformer with bonds) at the reference conformer's coordinates.
+    `rank_by="combo"` needs the shape and the pharmacophore score."""
+    pharm = o.pharmacophore_scores or o.min_pharmacophore_tanimoto is not None
+    if o.reference_pharmacophore is not None and not pharm:
         raise ValueError("reference_pharmacophore is only read with pharmacophore_scores or min_pharmacophore_tanimoto")
-    if rank_by == "combo" and not (pharm and shape.get("scores_shape")):
+    if o.rank_by == "combo" and not (pharm and scores_shape):
         raise ValueError("rank_by='combo' needs shape scores (shape_scores, top_k, min_shape_tanimoto or "
                          "max_pairwise_tanimoto) and pharmacophore_scores: it ranks by their sum")
-    if pharm:
-        if not overlay:
-            raise ValueError("pharmacophore_scores needs overlay=True: molecules that are not posed onto the reference are "
-                             "not in the coordinates of its features")
-        common.update(scores_pharmacophore=True, min_pharmacophore_tanimoto=min_pharmacophore_tanimoto, rank_by=rank_by)
-        if reference_pharmacophore is not None:
-            common["ref_features"] = mcg_pharm.load_reference_features(reference_pharmacophore)
-        else:
-            src = reference_graph
-            if src is None and hasattr(reference_conformer, "GetAtoms") and hasattr(reference_conformer, "GetBonds"):
-                src = reference_conformer
-            if src is None or solid is not None:
-                raise ValueError("pharmacophore scores need the reference's features: pass reference_pharmacophore= (a "
-                                 "sequence of (type, (x, y, z)) in the reference's coordinates - the only way with a "
-                                 "reference_shape) or the reference's molecular graph (reference_graph=, or a reference "
-                                 "conformer with bonds)")
-            z, bonds = mcg_fp.mol_graph(src)
-            coords = common["reference"].coords
-            if not 1 <= len(z) <= mcg_pharm.MAX_ATOMS or len(z) != int(coords.shape[0]):
-                raise ValueError(f"the reference graph has {len(z)} heavy atoms, the reference conformer "
-                                 f"{int(coords.shape[0])}: the features are placed on the conformer's atoms, in the "
-                                 f"graph's order (at most {mcg_pharm.MAX_ATOMS})")
-            common["ref_pharm_graph"] = (z, bonds, coords)
-    mcg_fp.check_flag("chemical_scores", chemical_scores)
-    if not (isinstance(unique, str) and unique == "exact"):
-        mcg_fp.check_flag("unique", unique)
-    excluded = None if exclude_graphs is None else read_excluded(exclude_graphs)
-    patterns, n_required, n_excluded = compile_substructures(require_substructures, exclude_substructures,
-                                                             substructure_counts)
-    if patterns is not None:
-        if custom_finisher:
-            raise ValueError(mcg_sub.REFUSAL_WITH_FINISHER)
-        common.update(substructures=patterns, n_required=n_required, n_excluded=n_excluded)
-    if max_chemical_tanimoto is not None:
-        mcg_fp.check_threshold("max_chemical_tanimoto", max_chemical_tanimoto)
-    if max_pairwise_chemical_tanimoto is not None:
-        mcg_fp.check_threshold("max_pairwise_chemical_tanimoto", max_pairwise_chemical_tanimoto)
-    scoring = chemical_scores or max_chemical_tanimoto is not None
-    if reference_graph is not None and not scoring and common.get("ref_pharm_graph") is None and \
-            common.get("ref_charge_graph") is None:
+    if not pharm:
+        return {}
+    if not o.overlay:
+        raise ValueError("pharmacophore_scores needs overlay=True: molecules that are not posed onto the reference are "
+                         "not in the coordinates of its features")
+    fields = dict(scores_pharmacophore=True, min_pharmacophore_tanimoto=o.min_pharmacophore_tanimoto, rank_by=o.rank_by)
+    if o.reference_pharmacophore is not None:
+        return dict(fields, ref_features=mcg_pharm.load_reference_features(o.reference_pharmacophore))
+    return dict(fields, ref_pharm_graph=_reference_graph(
+        o, "pharmacophore scores need the reference's features: pass reference_pharmacophore= (a "
+        "sequence of (type, (x, y, z)) in the reference's coordinates - the only way with a "
+        "reference_shape) or the reference's molecular graph (reference_graph=, or a reference "
+        "conformer with bonds)", mcg_pharm.MAX_ATOMS, "features", conformer))
+
+
+def _substructure_fields(o, custom_finisher) -> dict:
+    """`require_substructures` / `exclude_substructures` / `substructure_counts`: each None or an iterable of pattern
+    strings (`substructure.parse`), `substructure.Pattern`s or graph sources (`substructure.from_graph`); they are
+    compiled here, together (`compile_substructures`: host work), and an entry that cannot be read or breaks a limit is a
+    ValueError naming its list and position; refused with a custom finisher, through RDKit's the Mols' own graphs are
+    read."""
+    patterns, n_required, n_excluded = compile_substructures(o.require_substructures, o.exclude_substructures,
+                                                             o.substructure_counts)
+    if patterns is None:
+        return {}
+    if custom_finisher:
+        raise ValueError(mcg_sub.REFUSAL_WITH_FINISHER)
+    return dict(substructures=patterns, n_required=n_required, n_excluded=n_excluded)
+
+
+def _chemistry_fields(o, custom_finisher, excluded, graph_read: bool) -> dict:
+    """The chemical options: `max_chemical_tanimoto` implies the chemical score, which needs the reference's graph
+    (`_reference_graph`).  `unique`: False, True or "exact" - one row per exact identity (`canonical.identity_bytes`)
+    instead of per `graph_key`; it reads the Mols' own graphs through RDKit's finisher and is refused with a custom one.
+    `excluded`: the graphs of `exclude_graphs` as `read_excluded` read them.  `graph_read`: whether the pharmacophore or
+    the electrostatic family already reads `reference_graph` - one that no option reads is refused."""
+    if o.max_chemical_tanimoto is not None:
+        mcg_fp.check_threshold("max_chemical_tanimoto", o.max_chemical_tanimoto)
+    if o.max_pairwise_chemical_tanimoto is not None:
+        mcg_fp.check_threshold("max_pairwise_chemical_tanimoto", o.max_pairwise_chemical_tanimoto)
+    scoring = o.chemical_scores or o.max_chemical_tanimoto is not None
+    if o.reference_graph is not None and not scoring and not graph_read:
         raise ValueError("reference_graph is only read with chemical_scores, max_chemical_tanimoto or pharmacophore "
                          "scores without reference_pharmacophore (or electrostatic scores without reference_charges)")
-    chemical = scoring or unique or max_pairwise_chemical_tanimoto is not None
+    chemical = scoring or o.unique or o.max_pairwise_chemical_tanimoto is not None
     if (chemical or excluded is not None) and custom_finisher:
         raise ValueError("chemical scores cannot be combined with a custom finisher: its results carry no graph this "
                          "package can read")
-    if excluded is not None:
-        common["excluded_graphs"] = tuple(excluded)
+    fields = {} if excluded is None else dict(excluded_graphs=tuple(excluded))
     if not chemical:
-        return Request(**shape, **common)
+        return fields
     graph = None
     if scoring:
-        src = reference_graph
-        if src is None and hasattr(reference_conformer, "GetAtoms") and hasattr(reference_conformer, "GetBonds"):
-            src = reference_conformer
-        if src is None:
-            raise ValueError("chemical scores need the reference's molecular graph: pass reference_graph= (a Mol, a "
-                             "GeneratedMolecule or an (atomic_numbers, bond_orders) pair) or a reference conformer "
-                             "with bonds; coordinates and a bare reference_context have none")
-        graph = mcg_fp.mol_graph(src)
-        if not 1 <= len(graph[0]) <= mcg_fp.MAX_GRAPH_ATOMS:
-            raise ValueError(f"the reference graph must have 1 to {mcg_fp.MAX_GRAPH_ATOMS} heavy atoms, got "
-                             f"{len(graph[0])}")
-    return Request(ref_graph=graph, scores_chemistry=bool(scoring), max_chemical_tanimoto=max_chemical_tanimoto,
-                   unique=unique, max_pairwise_chemical_tanimoto=max_pairwise_chemical_tanimoto, **shape,
-                   **common)
+        graph = _reference_graph(
+            o, "chemical scores need the reference's molecular graph: pass reference_graph= (a Mol, a "
+            "GeneratedMolecule or an (atomic_numbers, bond_orders) pair) or a reference conformer "
+            "with bonds; coordinates and a bare reference_context have none", mcg_fp.MAX_GRAPH_ATOMS)
+    return dict(fields, ref_graph=graph, scores_chemistry=bool(scoring), max_chemical_tanimoto=o.max_chemical_tanimoto,
+                unique=o.unique, max_pairwise_chemical_tanimoto=o.max_pairwise_chemical_tanimoto)
 
 
 def compile_substructures(require, exclude, counts):
@@ -463,7 +531,10 @@ def substructures(gen, req: Request, atomic_numbers: torch.Tensor, bond_orders: 
 
 
 def read_excluded(exclude_graphs) -> List[tuple]:
-    """The heavy-atom graphs (`fingerprint.mol_graph`) of an `exclude_graphs` argument, host side only.  ValueError naming
+    """The heavy-atom graphs (`fingerprint.mol_graph`) of an `exclude_graphs` argument - an iterable of `GeneratedMolecule`,
+    Mols or (atomic_numbers, bond_orders) pairs whose exact identities the call drops -, host side only: the graphs are
+    only read here; the entries label them (`label_excluded`, one `_canonical_order` launch per 16 384) behind their own
+    argument checks, directly in front of the generation, where one without a canonical order is refused.  ValueError naming
     the position of an entry that is unreadable or has more than `canonical.MAX_ATOMS` heavy atoms, and for an argument
     that is no iterable of graphs."""
     if isinstance(exclude_graphs, (str, bytes)) or not hasattr(exclude_graphs, "__iter__"):

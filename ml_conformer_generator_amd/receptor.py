@@ -40,13 +40,13 @@ a PDB string's names, from the elements alone, or as given.
 """
 from __future__ import annotations
 
+import functools
 import math
-import operator
 from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 CLASH_OVERLAP = 0.6            # angstrom: UCSF ChimeraX `clashes` default overlap cutoff
 SELF_CONTACT = 0.5             # angstrom: a receptor atom this close to a reference atom means the ligand is in it
@@ -364,31 +364,14 @@ def check_clear_of_reference(rec_coords: torch.Tensor, ref_coord: torch.Tensor) 
                          f"from receptor atom {j} (<= {SELF_CONTACT} A); remove the ligand from the receptor")
 
 
-def check_max_receptor_clashes(value) -> int:
-    """`max_receptor_clashes` as an int >= 0 (an integer type, not a bool), else ValueError."""
-    try:
-        k = None if isinstance(value, bool) else operator.index(value)
-    except TypeError:
-        k = None
-    if k is None or k < 0:
-        raise ValueError(f"max_receptor_clashes must be an integer >= 0, got {value!r}")
-    return int(k)
+check_max_receptor_clashes = functools.partial(_args.check_at_least, "max_receptor_clashes", lowest=0)     # -> int
 
 
 def check_relief_steps(value, name: str = "steps", lowest: int = 0, if_true: Optional[int] = None) -> int:
     """A trial budget of the clash relief as an int in `lowest`..MAX_RELIEF_STEPS (an integer type, not a bool), else a
     ValueError that names `name`.  `if_true`: the budget True stands for, where the option accepts True
     (`relieve_clashes`: RELIEF_STEPS, with `lowest` 1)."""
-    if value is True and if_true is not None:
-        return if_true
-    try:
-        k = None if isinstance(value, bool) else operator.index(value)
-    except TypeError:
-        k = None
-    if k is None or not (lowest <= k <= MAX_RELIEF_STEPS):
-        what = "an integer" if if_true is None else "True or an integer step budget"
-        raise ValueError(f"{name} must be {what} in {lowest}..{MAX_RELIEF_STEPS}, got {value!r}")
-    return int(k)
+    return _args.check_steps(name, value, lowest, MAX_RELIEF_STEPS, if_true)
 
 
 def _spread_bits(v: torch.Tensor) -> torch.Tensor:
@@ -441,17 +424,9 @@ def receptor_overlap(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atom
     takes.  One `mcg_receptor_overlap` call; `splits` (default `default_splits`) only decides how the receptor is cut
     across workgroups, never a bit of the result.  Refused before any device work: what `load_receptor` refuses, atom
     counts outside [0, N], N > 64, B > MAX_BATCH, atomic numbers narrower than N."""
-    from .cheminformatics import check_n_nodes
     rec_xyz, rec_z = load_receptor(receptor)
-    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
-    B, N = int(coords.shape[0]), int(coords.shape[1])
-    check_n_nodes(n_nodes, B, N)
-    if N > MAX_LIGAND_ATOMS or B > MAX_BATCH:
-        raise ValueError(f"receptor contacts take at most {MAX_BATCH} molecules of at most {MAX_LIGAND_ATOMS} atoms, got "
-                         f"[{B}, {N}]")
-    z = torch.as_tensor(atomic_numbers)
-    if z.dim() != 2 or z.shape[0] != B or z.shape[1] < N:
-        raise ValueError(f"atomic_numbers must be [B, >= N] = [{B}, >= {N}], got {list(z.shape)}")
+    dev = _args.resolve_device(device, coords)
+    B, N, z = _args.ligand_arguments(coords, n_nodes, atomic_numbers, MAX_LIGAND_ATOMS, MAX_BATCH, "receptor contacts take")
     if B == 0 or N == 0:
         return torch.full((B, N), -math.inf, device=dev)
     R = int(rec_z.numel())
@@ -487,21 +462,11 @@ def relieve_clashes(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomi
     accepted steps, its rows as they came.  `skip_tiles`: whether a molecule's workgroup walks only the receptor tiles
     within its reach; never a bit of the result.  Refused before any device work: what `receptor_overlap` refuses, `steps`
     outside 0..MAX_RELIEF_STEPS, a bool or a non-integer, a `max_shift` that is negative or not finite."""
-    from .cheminformatics import check_n_nodes
     steps = check_relief_steps(steps)
-    if isinstance(max_shift, bool) or not isinstance(max_shift, (int, float)) or not (
-            0.0 <= float(max_shift) < math.inf):
-        raise ValueError(f"max_shift must be a finite real number >= 0, got {max_shift!r}")
+    max_shift = _args.check_real("max_shift", max_shift, 0.0)
     rec_xyz, rec_z = load_receptor(receptor)
-    dev = torch.device(device if device is not None else (coords.device if coords.is_cuda else "cuda:0"))
-    B, N = int(coords.shape[0]), int(coords.shape[1])
-    check_n_nodes(n_nodes, B, N)
-    if N > MAX_LIGAND_ATOMS or B > MAX_BATCH:
-        raise ValueError(f"clash relief takes at most {MAX_BATCH} molecules of at most {MAX_LIGAND_ATOMS} atoms, got "
-                         f"[{B}, {N}]")
-    z = torch.as_tensor(atomic_numbers)
-    if z.dim() != 2 or z.shape[0] != B or z.shape[1] < N:
-        raise ValueError(f"atomic_numbers must be [B, >= N] = [{B}, >= {N}], got {list(z.shape)}")
+    dev = _args.resolve_device(device, coords)
+    B, N, z = _args.ligand_arguments(coords, n_nodes, atomic_numbers, MAX_LIGAND_ATOMS, MAX_BATCH, "clash relief takes")
     x = coords.to(dev, torch.float32).contiguous()
     out = torch.zeros(B, N, 3, device=dev)
     xform = torch.full((B, 12), math.nan, device=dev)
@@ -515,7 +480,7 @@ def relieve_clashes(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomi
         nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B).contiguous()
         _lib.check(_lib.lib().mcg_receptor_relieve(_lib.dptr(x), _lib.dptr(lig_r), _lib.dptr(nn), B, N, _lib.dptr(rec),
                                                    int(xyzr.shape[0]), _lib.dptr(spheres), steps, RELIEF_MARGIN,
-                                                   float(max_shift), _lib.dptr(out), _lib.dptr(xform), _lib.dptr(stats),
+                                                   max_shift, _lib.dptr(out), _lib.dptr(xform), _lib.dptr(stats),
                                                    _lib.dptr(grad), _lib.current_stream_ptr(dev)),
                    "mcg_receptor_relieve")
     accepted = torch.nan_to_num(stats[:, 2], nan=0.0).to(torch.int32)

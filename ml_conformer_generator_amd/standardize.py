@@ -49,7 +49,7 @@ from typing import Dict, List
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 MAX_ATOMS = 64                  # include/mlconfgen_hip.h MCG_STANDARDIZE_MAX_ATOMS
 MAX_BATCH = 16384               # MCG_STANDARDIZE_MAX_B
@@ -87,20 +87,19 @@ def standardize_graphs(coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_
     ValueError before the kernel: shapes that do not fit, W > 64, float graph tensors, atom counts outside
     [0, min(N, W)], and with `check=True` (one device reduction, one host read) a code outside 0..4, a matrix that is not
     symmetric or an atomic number < 1 on a real atom."""
-    from .cheminformatics import check_n_nodes
-    from .hydrogens import _graph_arguments
     x = torch.as_tensor(coords)
     if x.dim() != 3 or x.shape[2] != 3 or not x.dtype.is_floating_point:
         raise ValueError(f"coords must be floating point [B,N,3], got {list(x.shape)} of type {x.dtype}")
+    too_wide = f"graphs of at most {MAX_ATOMS} atoms are standardised"
     width = torch.as_tensor(bond_orders).shape[1:2]
-    if width and int(width[0]) > MAX_ATOMS:
-        raise ValueError(f"graphs of at most {MAX_ATOMS} atoms are standardised, got a width of {int(width[0])}")
-    z, bonds, B, W = _graph_arguments(atomic_numbers, bond_orders, n_nodes)
+    if width and int(width[0]) > MAX_ATOMS:      # named before the rest of the shape is looked at
+        raise ValueError(f"{too_wide}, got a width of {int(width[0])}")
+    z, bonds, B, W = _args.graph_arguments(atomic_numbers, bond_orders, n_nodes, MAX_ATOMS, too_wide, counts=False)
     N = int(x.shape[1])
     if int(x.shape[0]) != B:
         raise ValueError(f"coords holds {int(x.shape[0])} molecules, bond_orders {B}")
-    check_n_nodes(n_nodes, B, min(N, W))
-    dev = torch.device(device if device is not None else (x.device if x.is_cuda else "cuda:0"))
+    _args.check_n_nodes(n_nodes, B, min(N, W))
+    dev = _args.resolve_device(device, x)
     launches = B > 0 and N > 0 and W > 0           # the kernel writes every element of every output
     fill = torch.empty if launches else torch.zeros
     out = {"coords": fill(B, N, 3, dtype=torch.float32, device=dev),
@@ -116,12 +115,9 @@ def standardize_graphs(coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_
            torch.full((B,), EMPTY, dtype=torch.int32, device=dev)}
     if launches:
         xd = x.to(dev, torch.float32).contiguous()
-        zd = z[:, :W].to(dev, torch.int32).contiguous()
-        bd = bonds.to(dev, torch.int8).contiguous()
-        nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B).contiguous()
+        zd, bd, nn = _args.device_graph(z, bonds, n_nodes, B, W, dev)
         if check:
-            from .fingerprint import _check_graphs
-            _check_graphs(zd, bd, nn, W)
+            _args.check_graphs(zd, bd, nn, W)
         for lo in range(0, B, MAX_BATCH):
             rows = slice(lo, min(lo + MAX_BATCH, B))
             _lib.check(_lib.lib().mcg_standardize_graphs(

@@ -34,7 +34,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 MAX_ATOMS = 64                  # include/mlconfgen_hip.h MCG_SUBSTRUCTURE_MAX_ATOMS
 MAX_PATTERN_ATOMS = 32          # MCG_SUBSTRUCTURE_MAX_PATTERN_ATOMS
@@ -595,12 +595,12 @@ def match_substructures(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
     ValueError before the kernel: as `canonical.canonical_order` (W > 64, shapes that do not fit, atom counts outside
     [0, W], and with `check=True` a code outside 0..4, a matrix that is not symmetric over the real atoms, an atomic number
     < 1 on a real atom), what `compile_patterns` refuses, an empty pattern list, a `hydrogens` of another shape."""
-    from .fingerprint import _check_graphs, graph_arguments
     compiled = compile_patterns(patterns)
     P, M = len(compiled.patterns), compiled.max_atoms
     if P == 0:
         raise ValueError("match_substructures needs at least one pattern")
-    z, bonds, B, W = graph_arguments(atomic_numbers, bond_orders, n_nodes, "substructure matches")
+    z, bonds, B, W = _args.graph_arguments(atomic_numbers, bond_orders, n_nodes, MAX_ATOMS,
+                                           f"substructure matches take molecules of at most {MAX_ATOMS} atoms")
     nh = None
     if hydrogens is not None and hydrogens is not False:
         nh = torch.as_tensor(hydrogens)
@@ -610,19 +610,17 @@ def match_substructures(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
     elif hydrogens is None and compiled.needs_hydrogens and B > 0 and W > 0:
         from .hydrogens import implicit_counts
         nh = implicit_counts(z[:, :W], bonds, n_nodes)
-    dev = torch.device(device if device is not None else (bonds.device if bonds.is_cuda else "cuda:0"))
+    dev = _args.resolve_device(device, bonds)
     if W == 0:                                  # no atoms anywhere: B empty graphs at the kernel's smallest width
         z, bonds, W, nh = torch.zeros(B, 1, dtype=torch.int32), torch.zeros(B, 1, 1, dtype=torch.int8), 1, None
     if B == 0:
         return dict(count=torch.zeros(0, P, dtype=torch.int32, device=dev), status=torch.zeros(0, P, dtype=torch.int32, device=dev),
                     first=torch.full((0, P, M), -1, dtype=torch.int32, device=dev),
                     covered=torch.zeros(0, P, dtype=torch.int64, device=dev))
-    zd = z[:, :W].to(dev, torch.int32).contiguous()
-    bd = bonds.to(dev, torch.int8).contiguous()
-    nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B).contiguous()
+    zd, bd, nn = _args.device_graph(z, bonds, n_nodes, B, W, dev)
     nhd = None if nh is None else nh[:, :W].to(dev, torch.int32).contiguous()
     if check:
-        _check_graphs(zd, bonds.to(dev), nn, W)
+        _args.check_graphs(zd, bonds.to(dev), nn, W)
     pn, pa, pb = compiled.pat_n.to(dev), compiled.pat_atoms.to(dev), compiled.pat_bonds.to(dev)
     parts = []
     for plo in range(0, P, MAX_PATTERNS):

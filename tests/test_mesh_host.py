@@ -218,7 +218,7 @@ def test_a_custom_finisher_is_refused_with_a_mesh_too():
     from ml_conformer_generator_amd import host_pool as HP
     gen = _shell_generator(finisher=HP.TaskRef("fake_host_tasks.py", "finish_tag_chunk"))
     with pytest.raises(ValueError, match="custom finisher"):
-        postprocess.parse_request(gen, None, True, reference_shape=C.pocket())
+        postprocess.parse_request(gen, None, shape_scores=True, reference_shape=C.pocket())
 
 
 def test_a_plain_reference_shape_request_asks_for_nothing():
@@ -229,7 +229,8 @@ def test_a_plain_reference_shape_request_asks_for_nothing():
     assert not req.measures and not req.removes and not req.selects_by_shape
     assert dataclasses.replace(req, reference=None) == postprocess.Request()
     assert postprocess.parse_request(gen, _ref()) == postprocess.Request()              # and without one: as before
-    full = postprocess.parse_request(gen, None, True, 3, 0.1, True, 0.9, reference_shape=C.pocket(), max_atoms_outside=2)
+    full = postprocess.parse_request(gen, None, shape_scores=True, top_k=3, min_shape_tanimoto=0.1, overlay=True,
+                                     max_pairwise_tanimoto=0.9, reference_shape=C.pocket(), max_atoms_outside=2)
     assert isinstance(full.reference, CH.SolidReference) and full.reference.mesh is C.pocket()
     assert full.overlay and full.scores_shape and full.removes and full.max_atoms_outside == 2
     assert (full.top_k, full.min_shape_tanimoto, full.max_pairwise_tanimoto) == (3, 0.1, 0.9)
@@ -297,7 +298,7 @@ def test_object_path_carries_atoms_outside_to_the_mols():
     calls = []
     gen._pose = _solid_pose_stub(calls)
     gen._score = lambda solid, coords, n: torch.full((coords.shape[0],), 0.25)
-    req = postprocess.parse_request(gen, None, True, overlay=True, reference_shape=C.pocket(), max_atoms_outside=3)
+    req = postprocess.parse_request(gen, None, shape_scores=True, overlay=True, reference_shape=C.pocket(), max_atoms_outside=3)
     done = [PosedMol([[0.3, 0, 0]] * 4 + [[0, 0, 1.0]], z=[6] * 4 + [1]), None,
             PosedMol([[0.7, 0, 0]] * 5, z=[6] * 5), PosedMol([[float("nan"), 0, 0]] * 5, z=[6] * 5)]
     samples = postprocess.measure_finished(gen, req, done)

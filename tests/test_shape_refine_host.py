@@ -61,11 +61,14 @@ def test_an_empty_batch_returns_every_key_of_the_call():
 def test_the_request_carries_the_step_budget():
     gen = _shell_generator()
     gen._reference_coord = lambda r: torch.as_tensor(r, dtype=torch.float32)
-    req = postprocess.parse_request(gen, _ref(), False, None, None, overlay=True)
+    req = postprocess.parse_request(gen, _ref(), shape_scores=False, top_k=None, min_shape_tanimoto=None, overlay=True)
     assert req.refine_steps == 0
-    assert postprocess.parse_request(gen, _ref(), False, None, None, True, None, True).refine_steps == 64
-    assert postprocess.parse_request(gen, _ref(), False, None, None, True, None, np.int32(5)).refine_steps == 5
-    assert postprocess.parse_request(gen, _ref(), False, None, None, True, None, 1024).refine_steps == 1024
+    assert postprocess.parse_request(gen, _ref(), shape_scores=False, top_k=None, min_shape_tanimoto=None, overlay=True,
+                                     max_pairwise_tanimoto=None, refine_overlay=True).refine_steps == 64
+    assert postprocess.parse_request(gen, _ref(), shape_scores=False, top_k=None, min_shape_tanimoto=None, overlay=True,
+                                     max_pairwise_tanimoto=None, refine_overlay=np.int32(5)).refine_steps == 5
+    assert postprocess.parse_request(gen, _ref(), shape_scores=False, top_k=None, min_shape_tanimoto=None, overlay=True,
+                                     max_pairwise_tanimoto=None, refine_overlay=1024).refine_steps == 1024
 
 
 # ----------------------------------------------------------------------------------------------- C entry
@@ -140,7 +143,8 @@ def test_object_path_takes_the_refined_seam_only_when_asked():
         return [PosedMol([[0.5, 0, 0]] * 4 + [[0, 0, 1.0]], z=[6] * 4 + [1]), None]
     for refine, want_call, shift in ((False, 0, 1.5), (True, 64, 2.5), (3, 3, 2.5)):
         calls.clear()
-        req = postprocess.parse_request(gen, _ref(), False, None, None, True, None, refine)
+        req = postprocess.parse_request(gen, _ref(), shape_scores=False, top_k=None, min_shape_tanimoto=None, overlay=True,
+                                        max_pairwise_tanimoto=None, refine_overlay=refine)
         done = mols()
         samples = postprocess.measure_finished(gen, req, done)
         scores = [s.measured.shape_tanimoto for s in samples]
