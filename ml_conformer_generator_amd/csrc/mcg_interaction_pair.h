@@ -7,14 +7,13 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "mcg_receptor_tiles.h"
+
 namespace mcg_interaction {
 
-constexpr int IX_THREADS = 256;               // lanes per workgroup = receptor atoms per tile
+constexpr int IX_THREADS = mcg_tiles::TILE_ATOMS;             // lanes per workgroup = receptor atoms per tile
 constexpr int IX_WAVES = IX_THREADS / 64;
 constexpr float IX_CUTOFF = 8.0f, IX_CUTOFF2 = 64.0f;
-// What the reach of the tile test adds to the exact bound: the centroid, rho and the test itself are rounded, all far
-// below 1e-3 of the lengths involved.
-constexpr float IX_SLACK_ABS = 0.05f, IX_SLACK_REL = 1e-3f;
 constexpr float W_G1 = -0.0356f, W_G2 = -0.00516f, W_REP = 0.840f, W_HYD = -0.0351f, W_HB = -0.587f, W_ROT = 0.0585f;
 constexpr float HB_FULL = -0.7f;              // a hydrogen bond counts in full at or below this surface distance
 constexpr unsigned T_DONOR = 1u, T_ACCEPTOR = 2u, T_HYDROPHOBIC = 4u;

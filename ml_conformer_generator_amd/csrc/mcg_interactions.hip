@@ -11,13 +11,14 @@
 //                       waves' partials of an atom are combined as (w0 + w1) + (w2 + w3) through LDS, the molecule's sums
 //                       are a fixed butterfly over the 64 atom slots in wave 0 (padded slots hold 0).  No atomics.
 //   Tile list:          with `tile_sphere` the workgroup keeps only the tiles whose bounding sphere comes within the cut-off
-//                       of the ligand's: |q_t - c| <= rho + 8 + radius_t + slack, c the atom centroid, rho the ligand's
-//                       radius about it.  Every pair of a tile left out has r2 >= 64 and would add nothing, so the list
-//                       changes no bit of the result.
+//                       of the ligand's (`mcg_tiles::build_tile_list`, mcg_receptor_tiles.h), with the reach rho + 8: c
+//                       the atom centroid, rho the ligand's radius about it.  Every pair of a tile left out has r2 >= 64
+//                       and would add nothing, so the list changes no bit of the result.
 // A molecule's outputs depend on its own atoms and the receptor arrays only: bit-identical whatever the batch, row or width.
 #include "mcg_common.h"
 #include "mcg_api_internal.h"
 #include "mcg_shape_grid.h"
+#include "mcg_receptor_tiles.h"
 #include "mcg_interaction_pair.h"
 
 #include <math.h>
@@ -27,11 +28,8 @@
 namespace {
 
 using namespace mcg_shape;
+using namespace mcg_tiles;           // the centroid and the tile list, shared by every kernel that reaches a receptor
 using namespace mcg_interaction;     // the pair arithmetic, shared with k_receptor_optimise
-
-constexpr int IX_MAX_TILES = MCG_RECEPTOR_MAX_ATOMS / IX_THREADS;
-
-static_assert(MCG_RECEPTOR_MAX_ATOMS % IX_THREADS == 0, "the tile list holds every tile of the largest receptor");
 
 struct InteractionShared {
     float4 tile[IX_THREADS];                  // the staged receptor tile: x, y, z, R_j
@@ -39,10 +37,8 @@ struct InteractionShared {
     float part[IX_WAVES][MAX_ATOMS][5];       // per wave and atom: g1, g2, rep, hyd, hb
     int hb_part[IX_WAVES][MAX_ATOMS];
     float c[3];
-    float reach[IX_WAVES];                    // per wave: max |x_i - c|^2
-    int wave_tiles[IX_WAVES];
-    int n_tiles;
-    unsigned short list[IX_MAX_TILES];
+    float reach[IX_WAVES][1];                 // per wave: max |x_i - c|^2
+    TileList<MAX_RECEPTOR_TILES> tiles;
 };
 
 __global__ __launch_bounds__(IX_THREADS) void k_receptor_interactions(
@@ -74,7 +70,7 @@ __global__ __launch_bounds__(IX_THREADS) void k_receptor_interactions(
     }
     if (w == 0) s.part[0][a][0] = x, s.part[0][a][1] = y, s.part[0][a][2] = z;      // borrowed for the centroid
     __syncthreads();
-    if (tid < 3) {                            // atom centroid, summed in atom order
+    if (tid < 3) {                            // atom centroid, summed in atom order (inline: DESIGN.md section 6)
         float acc = 0.f;
         for (int i = 0; i < na; ++i) acc += s.part[0][i][tid];
         s.c[tid] = acc / (float)na;
@@ -86,44 +82,14 @@ __global__ __launch_bounds__(IX_THREADS) void k_receptor_interactions(
         const float ux = x - c[0], uy = y - c[1], uz = z - c[2];
         rho2 = (ux * ux + uy * uy) + uz * uz;
     }
-    for (int o = 32; o > 0; o >>= 1) rho2 = fmaxf(rho2, __shfl_xor(rho2, o, 64));     // a maximum: exact in any order
-    if (a == 0) s.reach[w] = rho2;
-    __syncthreads();
-    const int T = (R + IX_THREADS - 1) / IX_THREADS;
-    {
-        // the tiles within reach, in ascending order: a ballot per wave over 256 tiles a round, the waves' counts
-        // prefix-summed through LDS
-        const float rho = sqrtf(fmaxf(fmaxf(s.reach[0], s.reach[1]), fmaxf(s.reach[2], s.reach[3])));
-        const float reach0 = rho + IX_CUTOFF;
-        int base = 0;
-        for (int t0 = 0; t0 < T; t0 += IX_THREADS) {
-            const int t = t0 + tid;
-            bool keep = t < T;
-            if (keep && tile_sphere != nullptr) {
-                const float4 q = tile_sphere[t];
-                const float dx = q.x - c[0], dy = q.y - c[1], dz = q.z - c[2];
-                const float reach = reach0 + q.w;
-                const float lim = reach + (IX_SLACK_ABS + IX_SLACK_REL * reach);
-                keep = !(((dx * dx + dy * dy) + dz * dz) > lim * lim);          // a NaN sphere keeps its tile
-            }
-            const unsigned long long m = __ballot(keep);
-            if (a == 0) s.wave_tiles[w] = __popcll(m);
-            __syncthreads();
-            int before = base;
-            for (int v = 0; v < w; ++v) before += s.wave_tiles[v];
-            if (keep) s.list[before + __popcll(m & ((1ull << a) - 1ull))] = (unsigned short)t;
-            base += (s.wave_tiles[0] + s.wave_tiles[1]) + (s.wave_tiles[2] + s.wave_tiles[3]);
-            __syncthreads();
-        }
-        if (tid == 0) s.n_tiles = base;
-    }
-    __syncthreads();
+    block_max4<1>(s.reach, &rho2, a, w);
+    build_tile_list(s.tiles, tile_sphere, (R + IX_THREADS - 1) / IX_THREADS, c[0], c[1], c[2], sqrtf(rho2) + IX_CUTOFF);
 
     float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     int nhb = 0;
-    const int nt = s.n_tiles;
+    const int nt = s.tiles.n_tiles;
     for (int k = 0; k < nt; ++k) {
-        const int j0 = (int)s.list[k] * IX_THREADS;
+        const int j0 = (int)s.tiles.list[k] * IX_THREADS;
         const int cnt = min(IX_THREADS, R - j0);                   // the last tile's tail
         if (tid < cnt) {
             s.tile[tid] = rec[j0 + tid];

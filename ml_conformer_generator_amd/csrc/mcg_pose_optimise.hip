@@ -1,7 +1,8 @@
 // Optimised pose ("Optimised pose"; the definition is the docstring of `interactions.optimise_pose`):
 // every posed molecule is moved as a rigid body downhill on W, the weighted sum of the five terms of the receptor
-// interaction score, by the accept / reject walk of `k_receptor_relieve` with the pair arithmetic of
-// `k_receptor_interactions`.  THE PACKAGE'S OWN procedure: not a docking run, not AutoDock Vina's local optimisation; rigid
+// interaction score, by the accept / reject walk of mcg_rigid_step.h (`rotate_about`, `step_along`, `within_shift`,
+// `StepLengths`) with the pair arithmetic of mcg_interaction_pair.h.
+// THE PACKAGE'S OWN procedure: not a docking run, not AutoDock Vina's local optimisation; rigid
 // body only - no torsions, no intramolecular term, no hydrogens, no global search.
 //   k_receptor_optimise: one 256-lane workgroup per molecule, laid out as `k_receptor_interactions`: lane l holds ligand
 //                       atom a = l & 63 in registers, wave w = l >> 6 walks the receptor atoms j = w, w + 4, ... of each
@@ -19,7 +20,8 @@
 //                       is kept iff W' < W, strictly (NaN never is).  Kept: both lengths x 1.2; rejected: x 0.5.  The walk
 //                       ends after `steps` trials or once s_t < 2^-8.  G is re-orthonormalised as each trial is formed, and
 //                       each lane keeps the coordinates it evaluated, so the pose returned is the pose that was scored.
-//   Tile list:          built once, as the scoring kernel builds it, with max_shift added to the reach: rotation is about
+//   Tile list:          built once (`mcg_tiles::build_tile_list`, mcg_receptor_tiles.h) with the reach (rho + 8) +
+//                       max_shift, the scoring kernel's with max_shift added: rotation is about
 //                       p, so the ligand's radius about its centroid does not change, and p stays within max_shift of c.
 //                       Every pair of a tile left out has r2 >= 64 in every pose the walk can evaluate and adds nothing.
 // A molecule's outputs depend on its own atoms and the receptor arrays only: bit-identical whatever the batch, row or width.
@@ -27,6 +29,7 @@
 #include "mcg_api_internal.h"
 #include "mcg_shape_grid.h"
 #include "mcg_rigid_step.h"
+#include "mcg_receptor_tiles.h"
 #include "mcg_interaction_pair.h"
 
 #include <math.h>
@@ -36,19 +39,15 @@
 namespace {
 
 using namespace mcg_shape;
-using namespace mcg_rigid;
-using namespace mcg_interaction;
+using namespace mcg_rigid;           // the trial, the step lengths, the returned transform: one text for every walk
+using namespace mcg_tiles;           // the centroid and the tile list, shared by every kernel that reaches a receptor
+using namespace mcg_interaction;     // the pair arithmetic, shared with k_receptor_interactions
 
-constexpr int PO_MAX_STEPS = 1024;
-constexpr int PO_MAX_TILES = MCG_RECEPTOR_MAX_ATOMS / IX_THREADS;
 constexpr float PO_STEP_ROT = 0.05f;          // initial rotation step, rad
 constexpr float PO_STEP_TRANS = 0.25f;        // initial translation step, Angstrom
-constexpr float PO_GROW = 1.2f, PO_SHRINK = 0.5f;
 constexpr float PO_MIN_TRANS = 0.00390625f;   // 2^-8 A: the walk ends below it
 constexpr int PO_SUMS = 11;                   // g1, g2, rep, hyd, hb, F[3], torque[3]
 constexpr int PO_TRACE = 24;                  // F[3], torque[3], s_r, s_t, G'[9], p'[3], W', evaluated, kept, W_cur
-
-static_assert(MCG_RECEPTOR_MAX_ATOMS % IX_THREADS == 0, "the tile list holds every tile of the largest receptor");
 
 struct OptimiseShared {
     float4 tile[IX_THREADS];                  // the staged receptor tile: x, y, z, R_j
@@ -56,10 +55,8 @@ struct OptimiseShared {
     float part[IX_WAVES][MAX_ATOMS][8];       // per wave and atom: g1, g2, rep, hyd, hb, F
     float red[PO_SUMS];
     float c[3];
-    float reach[IX_WAVES];                    // per wave: max |x_i - c|^2
-    int wave_tiles[IX_WAVES];
-    int n_tiles;
-    unsigned short list[PO_MAX_TILES];
+    float reach[IX_WAVES][1];                 // per wave: max |x_i - c|^2
+    TileList<MAX_RECEPTOR_TILES> tiles;
 };
 
 // The five term sums, the net force and the torque about p of the pose whose atom a this lane holds at (x, y, z), seen
@@ -70,9 +67,9 @@ __device__ void evaluate(OptimiseShared& s, const float4* __restrict__ rec, cons
     const int tid = threadIdx.x, a = tid & 63, w = tid >> 6;
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int nhb = 0;
-    const int nt = s.n_tiles;
+    const int nt = s.tiles.n_tiles;
     for (int k = 0; k < nt; ++k) {
-        const int j0 = (int)s.list[k] * IX_THREADS;
+        const int j0 = (int)s.tiles.list[k] * IX_THREADS;
         const int cnt = min(IX_THREADS, R - j0);                   // the last tile's tail
         if (tid < cnt) {
             s.tile[tid] = rec[j0 + tid];
@@ -153,7 +150,7 @@ __global__ __launch_bounds__(IX_THREADS) void k_receptor_optimise(
     }
     if (w == 0) s.part[0][a][0] = x0, s.part[0][a][1] = y0, s.part[0][a][2] = z0;   // borrowed for the centroid
     __syncthreads();
-    if (tid < 3) {                            // atom centroid, summed in atom order
+    if (tid < 3) {                            // atom centroid, summed in atom order (inline: DESIGN.md section 6)
         float acc = 0.f;
         for (int i = 0; i < na; ++i) acc += s.part[0][i][tid];
         s.c[tid] = acc / (float)na;
@@ -165,38 +162,10 @@ __global__ __launch_bounds__(IX_THREADS) void k_receptor_optimise(
         rx = x0 - c[0]; ry = y0 - c[1]; rz = z0 - c[2];
         rho2 = (rx * rx + ry * ry) + rz * rz;
     }
-    for (int o = 32; o > 0; o >>= 1) rho2 = fmaxf(rho2, __shfl_xor(rho2, o, 64));     // a maximum: exact in any order
-    if (a == 0) s.reach[w] = rho2;
-    __syncthreads();
-    const int T = (R + IX_THREADS - 1) / IX_THREADS;
-    {
-        // the tiles within reach of any pose of the walk, in ascending order: a ballot per wave over 256 tiles a round, the
-        // waves' counts prefix-summed through LDS
-        const float rho = sqrtf(fmaxf(fmaxf(s.reach[0], s.reach[1]), fmaxf(s.reach[2], s.reach[3])));
-        const float reach0 = (rho + IX_CUTOFF) + max_shift;
-        int base = 0;
-        for (int t0 = 0; t0 < T; t0 += IX_THREADS) {
-            const int t = t0 + tid;
-            bool keep = t < T;
-            if (keep && tile_sphere != nullptr) {
-                const float4 q = tile_sphere[t];
-                const float dx = q.x - c[0], dy = q.y - c[1], dz = q.z - c[2];
-                const float reach = reach0 + q.w;
-                const float lim = reach + (IX_SLACK_ABS + IX_SLACK_REL * reach);
-                keep = !(((dx * dx + dy * dy) + dz * dz) > lim * lim);          // a NaN sphere keeps its tile
-            }
-            const unsigned long long m = __ballot(keep);
-            if (a == 0) s.wave_tiles[w] = __popcll(m);
-            __syncthreads();
-            int before = base;
-            for (int v = 0; v < w; ++v) before += s.wave_tiles[v];
-            if (keep) s.list[before + __popcll(m & ((1ull << a) - 1ull))] = (unsigned short)t;
-            base += (s.wave_tiles[0] + s.wave_tiles[1]) + (s.wave_tiles[2] + s.wave_tiles[3]);
-            __syncthreads();
-        }
-        if (tid == 0) s.n_tiles = base;
-    }
-    __syncthreads();
+    block_max4<1>(s.reach, &rho2, a, w);
+    // the tiles within reach of any pose of the walk
+    build_tile_list(s.tiles, tile_sphere, (R + IX_THREADS - 1) / IX_THREADS, c[0], c[1], c[2],
+                    (sqrtf(rho2) + IX_CUTOFF) + max_shift);
 
     float G[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, p[3] = {c[0], c[1], c[2]};
     float cur[PO_SUMS];
@@ -208,27 +177,22 @@ __global__ __launch_bounds__(IX_THREADS) void k_receptor_optimise(
 #pragma unroll
         for (int k = 0; k < 6; ++k) gradient_out[(size_t)b * 6 + k] = cur[5 + k];
     }
-    float sr = PO_STEP_ROT, st = PO_STEP_TRANS;
+    StepLengths len = {PO_STEP_ROT, PO_STEP_TRANS};
     int trials = 0, kept = 0;
-    for (; trials < steps && !(st < PO_MIN_TRANS); ++trials) {
+    for (; trials < steps && !(len.trans < PO_MIN_TRANS); ++trials) {
         float Gn[9], pn[3];
-        const float fn = sqrtf((cur[5] * cur[5] + cur[6] * cur[6]) + cur[7] * cur[7]);
-        const float tn = sqrtf((cur[8] * cur[8] + cur[9] * cur[9]) + cur[10] * cur[10]);
+        const float fn = norm3(cur + 5), tn = norm3(cur + 8);
         const bool moves = fn > 0.f && isfinite(fn), turns = tn > 0.f && isfinite(tn);
         if (!moves && !turns) break;          // nothing to follow: the walk ends, the trial is not counted
         if (turns) {
-            float D[9];
-            rodrigues_row(cur[8] / tn, cur[9] / tn, cur[10] / tn, sr, D);
-            mat3_mul(G, D, Gn);
-            orthonormalise(Gn);
+            rotate_about<true>(G, cur[8] / tn, cur[9] / tn, cur[10] / tn, len.rot, Gn);
         } else {
 #pragma unroll
             for (int k = 0; k < 9; ++k) Gn[k] = G[k];
         }
 #pragma unroll
-        for (int k = 0; k < 3; ++k) pn[k] = moves ? p[k] + st * (cur[5 + k] / fn) : p[k];
-        const float sx = pn[0] - c[0], sy = pn[1] - c[1], sz = pn[2] - c[2];
-        const bool evaluated = !(((sx * sx + sy * sy) + sz * sz) > max_shift * max_shift);
+        for (int k = 0; k < 3; ++k) pn[k] = step_along(p[k], cur[5 + k], fn, moves, len.trans);
+        const bool evaluated = within_shift(pn, c[0], c[1], c[2], max_shift);
         bool take = false;
         float nxt[PO_SUMS], w_nxt = 0.f, tx = 0.f, ty = 0.f, tz = 0.f;
         if (evaluated) {                      // the same in every lane
@@ -245,7 +209,7 @@ __global__ __launch_bounds__(IX_THREADS) void k_receptor_optimise(
             float* row = trace + (size_t)trials * PO_TRACE;
 #pragma unroll
             for (int k = 0; k < 6; ++k) row[k] = cur[5 + k];
-            row[6] = sr; row[7] = st;
+            row[6] = len.rot; row[7] = len.trans;
 #pragma unroll
             for (int k = 0; k < 9; ++k) row[8 + k] = Gn[k];
 #pragma unroll
@@ -253,18 +217,13 @@ __global__ __launch_bounds__(IX_THREADS) void k_receptor_optimise(
             row[20] = w_nxt; row[21] = evaluated ? 1.f : 0.f; row[22] = take ? 1.f : 0.f; row[23] = w_cur;
         }
         if (take) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k) G[k] = Gn[k];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) p[k] = pn[k];
-#pragma unroll
-            for (int k = 0; k < PO_SUMS; ++k) cur[k] = nxt[k];
+            keep_trial<PO_SUMS>(G, p, cur, Gn, pn, nxt);
             w_cur = w_nxt;
             cx = tx; cy = ty; cz = tz;
-            sr *= PO_GROW; st *= PO_GROW;
+            len.grow();
             ++kept;
         } else {
-            sr *= PO_SHRINK; st *= PO_SHRINK;
+            len.shrink();
         }
     }
     if (trace != nullptr)                     // rows beyond the last trial are zero
@@ -276,7 +235,7 @@ __global__ __launch_bounds__(IX_THREADS) void k_receptor_optimise(
         if (tid < 12) xf[tid] = (tid == 0 || tid == 4 || tid == 8) ? 1.f : 0.f;
         if (tid == 0) {
             stats[0] = w_start; stats[1] = w_start; stats[2] = (float)trials; stats[3] = 0.f;
-            stats[4] = 0.f; stats[5] = st; stats[6] = 0.f; stats[7] = 0.f;
+            stats[4] = 0.f; stats[5] = len.trans; stats[6] = 0.f; stats[7] = 0.f;
         }
         return;
     }
@@ -292,15 +251,12 @@ __global__ __launch_bounds__(IX_THREADS) void k_receptor_optimise(
         s.part[0][a][0] = d2;                 // every evaluation is over: nobody else reads it
     }
     __syncthreads();
-    if (tid == 0) {                           // x' = (x - c) @ G + p = x @ G + (p - c @ G)
-        float cg[3];
-        rotate_row(c[0], c[1], c[2], G, cg);
-        for (int k = 0; k < 9; ++k) xf[k] = G[k];
-        for (int k = 0; k < 3; ++k) xf[9 + k] = p[k] - cg[k];
+    if (tid == 0) {
+        write_transform(G, p, c[0], c[1], c[2], xf);
         float sum = 0.f;
         for (int i = 0; i < na; ++i) sum += s.part[0][i][0];       // in atom order
         stats[0] = w_start; stats[1] = w_cur; stats[2] = (float)trials; stats[3] = (float)kept;
-        stats[4] = sqrtf(sum / (float)na); stats[5] = st; stats[6] = 0.f; stats[7] = 0.f;
+        stats[4] = sqrtf(sum / (float)na); stats[5] = len.trans; stats[6] = 0.f; stats[7] = 0.f;
     }
 }
 
@@ -311,10 +267,10 @@ extern "C" int mcg_receptor_optimise(const float* lig_xyz, const float* lig_radi
                                      const uint8_t* rec_type, int R, const float* tile_sphere, int steps, float max_shift,
                                      float* coords_out, float* xform_out, float* stats_out, float* gradient_out,
                                      float* trace_out, void* stream) {
-    static_assert(PO_MAX_STEPS == 1024 && MAX_ATOMS == 64, "the bounds the message below states");
+    static_assert(WALK_MAX_STEPS == 1024 && MAX_ATOMS == 64, "the bounds the message below states");
     if (!lig_xyz || !lig_radius || !lig_type || !n_nodes_dev || !rec_xyzr || !rec_type || !coords_out || !xform_out ||
         !stats_out || B < 1 || B > MCG_RECEPTOR_MAX_B || N < 1 || N > MAX_ATOMS || R < 1 || R > MCG_RECEPTOR_MAX_ATOMS ||
-        steps < 0 || steps > PO_MAX_STEPS || !(max_shift >= 0.f) || !isfinite(max_shift)) {
+        steps < 0 || steps > WALK_MAX_STEPS || !(max_shift >= 0.f) || !isfinite(max_shift)) {
         mcg_set_error("mcg_receptor_optimise: bad arguments (non-null buffers, 1 <= B <= %d, 1 <= N <= 64, 1 <= R <= %d, "
                       "0 <= steps <= 1024, max_shift finite and >= 0)", MCG_RECEPTOR_MAX_B, MCG_RECEPTOR_MAX_ATOMS);
         return MCG_ERR_ARG;

@@ -1,11 +1,17 @@
 // Device pieces shared by the rigid-body accept / reject walks (`k_overlay_refine`, `k_receptor_relieve`,
-// `k_receptor_optimise`): the 3x3 product, the trial rotation and the Gram-Schmidt pass.  One text, so the three walks form
-// a trial rotation with the same operations in the same order.  Contraction is off inside the bodies and the one fused
-// multiply-add is written out, as in mcg_shape_grid.h.
+// `k_receptor_optimise`; DESIGN.md section 6, "Shared device text"): the 3x3 product, the trial rotation and the
+// Gram-Schmidt pass, the trial pose (`rotate_about`, `step_along`) and its shift test, the step lengths and their
+// factors, the transform a walk returns, the atom centroid and the reduction of a pose's sums.  One text, so the three
+// walks form, keep and return a trial with the same operations in the same order, and the walk that is pinned trial by
+// trial pins the text the other two run.  Contraction is off inside the bodies and every fused multiply-add is written
+// out, as in mcg_shape_grid.h.  Scalars go in by value (the centroid, the rotation axis, the components of p): in that
+// shape the helpers leave the kernels the instruction streams profiles/walk_share_isa.txt records.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <math.h>
+
+#include "mcg_shape_grid.h"
 
 namespace mcg_rigid {
 
@@ -52,6 +58,101 @@ __device__ __forceinline__ void orthonormalise(float* G) {
     G[6] = a[1] * b[2] - a[2] * b[1];
     G[7] = a[2] * b[0] - a[0] * b[2];
     G[8] = a[0] * b[1] - a[1] * b[0];
+}
+
+// |v|, the squares summed as (v0^2 + v1^2) + v2^2
+__device__ __forceinline__ float norm3(const float* v) {
+#pragma clang fp contract(off)
+    return sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+}
+
+// Gn = G rotated by sr about the unit axis (nx, ny, nz), the torque over its length.  ORTHO: Gn is made orthonormal again
+// as it is formed.  The caller decides whether the trial turns at all (else Gn is G's bits) and divides the torque.
+template <bool ORTHO>
+__device__ __forceinline__ void rotate_about(const float* G, float nx, float ny, float nz, float sr, float* Gn) {
+#pragma clang fp contract(off)
+    float D[9];
+    rodrigues_row(nx, ny, nz, sr, D);
+    mat3_mul(G, D, Gn);
+    if (ORTHO) orthonormalise(Gn);
+}
+
+// One component of the trial position: p moved by st along the force (f its component, fn = |force|) where `moves`,
+// else p's bits.  The caller decides `moves` from fn.
+__device__ __forceinline__ float step_along(float p, float f, float fn, bool moves, float st) {
+#pragma clang fp contract(off)
+    return moves ? p + st * (f / fn) : p;
+}
+
+// Whether pn lies within max_shift of c = (cx, cy, cz); true for a NaN.
+__device__ __forceinline__ bool within_shift(const float* pn, float cx, float cy, float cz, float max_shift) {
+#pragma clang fp contract(off)
+    const float sx = pn[0] - cx, sy = pn[1] - cy, sz = pn[2] - cz;
+    return !(((sx * sx + sy * sy) + sz * sz) > max_shift * max_shift);
+}
+
+constexpr int WALK_MAX_STEPS = 1024;          // the largest step budget an entry takes
+constexpr float WALK_GROW = 1.2f, WALK_SHRINK = 0.5f;
+
+// The two step lengths of a walk: both grow after a trial that is kept and shrink after one that is not.
+struct StepLengths {
+    float rot, trans;                         // rad, Angstrom
+    __device__ __forceinline__ void grow() { rot *= WALK_GROW; trans *= WALK_GROW; }
+    __device__ __forceinline__ void shrink() { rot *= WALK_SHRINK; trans *= WALK_SHRINK; }
+};
+
+// The trial (Gn, pn) with its K sums becomes the pose that holds.
+template <int K>
+__device__ __forceinline__ void keep_trial(float* G, float* p, float* cur, const float* Gn, const float* pn,
+                                           const float* nxt) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) G[k] = Gn[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[k] = pn[k];
+#pragma unroll
+    for (int k = 0; k < K; ++k) cur[k] = nxt[k];
+}
+
+// out12 = G row-major, then p - c @ G, c = (cx, cy, cz): x' = (x - c) @ G + p = x @ G + (p - c @ G).  One lane writes it.
+__device__ __forceinline__ void write_transform(const float* G, const float* p, float cx, float cy, float cz,
+                                                float* out12) {
+#pragma clang fp contract(off)
+    float cg[3];
+    mcg_shape::rotate_row(cx, cy, cz, G, cg);
+    for (int k = 0; k < 9; ++k) out12[k] = G[k];
+    for (int k = 0; k < 3; ++k) out12[9 + k] = p[k] - cg[k];
+}
+
+// out_c[k] = (sum over i < na of rows[i * stride + k]) / (float)den for k < 3, summed in atom order by lanes 0..2 of the
+// workgroup.  The rows must be visible to those lanes already; ends with the barrier that makes out_c (LDS) visible to
+// every lane.  Every lane calls it.
+__device__ __forceinline__ void atom_centroid(const float* rows, int stride, int na, int den, float* out_c) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+    if (tid < 3) {
+        float acc = 0.f;
+        for (int i = 0; i < na; ++i) acc += rows[i * stride + tid];
+        out_c[tid] = acc / (float)den;
+    }
+    __syncthreads();
+}
+
+// v[k] = the sum of acc[k] over the 256 lanes of the workgroup, K sums at once: an xor butterfly per wave, then the tree
+// (w0 + w1) + (w2 + w3) through red[4][K] in LDS, read by every lane.  Every lane calls it and gets the same bits.
+template <int K>
+__device__ __forceinline__ void block_sums(float* acc, float (*red)[K], float* v) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) red[tid >> 6][k] = acc[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
 }
 
 }  // namespace mcg_rigid

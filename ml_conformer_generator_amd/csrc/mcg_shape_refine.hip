@@ -5,7 +5,9 @@
 //                          as `k_shape_overlay` builds it; the reference y and the start sit in LDS.  Objective
 //                          O(y, z) = sum_ij A^2 (pi / 2 alpha)^1.5 exp(-(alpha / 2) |y_i - z_j|^2), rigid motion
 //                          z' = (z - c) @ G + p (c the start's atom centroid, p where it is now).  Every step takes a
-//                          normalised-gradient move (angle s_r about the torque, length s_t along the force), keeps it
+//                          normalised-gradient move (angle s_r about the torque, length s_t along the force:
+//                          `rotate_about<false>` and `step_along` of mcg_rigid_step.h, G made orthonormal once, after
+//                          the last step), keeps it
 //                          only if O strictly increases (then both lengths x 1.2; else both x 0.5), for `steps` steps.
 //                          Lane l owns the pairs q = l + 256 k of q = i * n + j; the seven sums (O, force, torque) are
 //                          reduced by a fixed butterfly per wave and the tree (w0 + w1) + (w2 + w3), read by every lane,
@@ -27,14 +29,12 @@
 namespace {
 
 using namespace mcg_shape;
-using namespace mcg_rigid;     // mat3_mul, rodrigues_row, orthonormalise: one text for every rigid-body walk
+using namespace mcg_rigid;     // the trial, the step lengths, the returned transform, the sums: one text for every walk
 
 constexpr int RF_THREADS = GRID_THREADS;
 constexpr int RF_WAVES = RF_THREADS / 64;
-constexpr int RF_MAX_STEPS = 1024;
 constexpr float RF_STEP_ROT = 0.2f;       // initial rotation step, rad
 constexpr float RF_STEP_TRANS = 0.5f;     // initial translation step, Angstrom
-constexpr float RF_GROW = 1.2f, RF_SHRINK = 0.5f;
 
 // ws per (candidate, orientation): G row-major [9], then t [3] with z' = z @ G + t
 constexpr int RF_WS = 12;
@@ -70,16 +70,7 @@ __device__ void evaluate(RefineShared& s, int n_ref, int na, const float* G, con
         acc[5] = __builtin_fmaf(e, rz * yx - rx * yz, acc[5]);
         acc[6] = __builtin_fmaf(e, rx * yy - ry * yx, acc[6]);
     }
-#pragma unroll
-    for (int k = 0; k < 7; ++k)
-        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 7; ++k) s.red[tid >> 6][k] = acc[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 7; ++k) v[k] = (s.red[0][k] + s.red[1][k]) + (s.red[2][k] + s.red[3][k]);
+    block_sums<7>(acc, s.red, v);
 }
 
 __global__ __launch_bounds__(RF_THREADS) void k_overlay_refine(const float* __restrict__ ref_frame, int n_ref,
@@ -106,12 +97,7 @@ __global__ __launch_bounds__(RF_THREADS) void k_overlay_refine(const float* __re
         frame_start(x[0], x[1], x[2], flip, rot + w * 9, s.r[tid]);
     }
     __syncthreads();
-    if (tid < 3) {                            // atom centroid, summed in atom order
-        float acc = 0.f;
-        for (int i = 0; i < na; ++i) acc += s.r[i][tid];
-        s.c[tid] = acc / (float)max(na, 1);
-    }
-    __syncthreads();
+    atom_centroid(&s.r[0][0], 3, na, max(na, 1), s.c);
     const float c[3] = {s.c[0], s.c[1], s.c[2]};
     __syncthreads();
     if (tid < na) {
@@ -121,36 +107,29 @@ __global__ __launch_bounds__(RF_THREADS) void k_overlay_refine(const float* __re
     float cur[7];
     evaluate(s, n_ref, na, G, p, half_alpha, cur);
     const float o_start = cur[0];
-    float sr = RF_STEP_ROT, st = RF_STEP_TRANS;
+    StepLengths len = {RF_STEP_ROT, RF_STEP_TRANS};
     for (int it = 0; it < steps; ++it) {
         float Gn[9], pn[3];
-        const float fn = sqrtf((cur[1] * cur[1] + cur[2] * cur[2]) + cur[3] * cur[3]);
-        const float tn = sqrtf((cur[4] * cur[4] + cur[5] * cur[5]) + cur[6] * cur[6]);
+        const float fn = norm3(cur + 1), tn = norm3(cur + 4);
         if (tn > 0.f) {
-            float D[9];
-            rodrigues_row(cur[4] / tn, cur[5] / tn, cur[6] / tn, sr, D);
-            mat3_mul(G, D, Gn);
+            rotate_about<false>(G, cur[4] / tn, cur[5] / tn, cur[6] / tn, len.rot, Gn);
         } else {
             for (int k = 0; k < 9; ++k) Gn[k] = G[k];
         }
-        for (int k = 0; k < 3; ++k) pn[k] = fn > 0.f ? p[k] + st * (cur[1 + k] / fn) : p[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) pn[k] = step_along(p[k], cur[1 + k], fn, fn > 0.f, len.trans);
         float nxt[7];
         evaluate(s, n_ref, na, Gn, pn, half_alpha, nxt);
         if (nxt[0] > cur[0]) {
-            for (int k = 0; k < 9; ++k) G[k] = Gn[k];
-            for (int k = 0; k < 3; ++k) p[k] = pn[k];
-            for (int k = 0; k < 7; ++k) cur[k] = nxt[k];
-            sr *= RF_GROW; st *= RF_GROW;
+            keep_trial<7>(G, p, cur, Gn, pn, nxt);
+            len.grow();
         } else {
-            sr *= RF_SHRINK; st *= RF_SHRINK;
+            len.shrink();
         }
     }
     orthonormalise(G);
-    if (tid == 0) {                           // z' = (z - c) @ G + p = z @ G + (p - c @ G)
-        float cg[3];
-        rotate_row(c[0], c[1], c[2], G, cg);
-        for (int k = 0; k < 9; ++k) out[k] = G[k];
-        for (int k = 0; k < 3; ++k) out[9 + k] = p[k] - cg[k];
+    if (tid == 0) {
+        write_transform(G, p, c[0], c[1], c[2], out);
         if (objective != nullptr) {
             objective[(size_t)blockIdx.x * 2] = pref * o_start;
             objective[(size_t)blockIdx.x * 2 + 1] = pref * cur[0];
@@ -247,8 +226,8 @@ extern "C" int mcg_shape_overlay_refined(const float* ref_frame, int n_ref, cons
                                          float* score, float* best, int32_t* which, int32_t* flipped, float* pose,
                                          float* posed, int steps, float* refine_ws, float* objective, float* start_best,
                                          int32_t* refined, float* refined_score, void* stream) {
-    static_assert(RF_MAX_STEPS == 1024, "the bound the message below states");
-    const bool own_ok = refine_ws && start_best && refined && steps >= 0 && steps <= RF_MAX_STEPS && alpha > 0.f;
+    static_assert(WALK_MAX_STEPS == 1024, "the bound the message below states");
+    const bool own_ok = refine_ws && start_best && refined && steps >= 0 && steps <= WALK_MAX_STEPS && alpha > 0.f;
     if (int rc = mcg_shape_overlay_launch("mcg_shape_overlay_refined", own_ok, ", 0 <= steps <= 1024, alpha > 0",
                                           ref_frame, n_ref, ref_xform, frames, xform, n_nodes_dev, B, N, rot, axes, n,
                                           alpha, amplitude, f_scratch, score, best, which, flipped, pose, posed, stream))

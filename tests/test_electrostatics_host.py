@@ -537,6 +537,16 @@ def test_c_entries_refuse_bad_arguments_without_a_device():
         assert h.mcg_esp_overlap(p, p, P, p, p, p, B, PW, mu, None, p, p, p, None) != 0, (P, B, PW, mu)
 
 
+def test_argument_check_program_builds_and_passes_under_host_sanitizers(tmp_path):
+    """`make asan_esp`: both entries' argument checks in a stand-alone program under host-side ASan + UBSan, on the CPU."""
+    exe = str(tmp_path / "esp_arg_check")
+    csrc = os.path.join(REPO, "ml_conformer_generator_amd", "csrc")
+    built = subprocess.run(["make", "-C", csrc, "asan_esp", f"ESP_CHECK={exe}"], capture_output=True, text=True)
+    assert built.returncode == 0, built.stdout + built.stderr
+    ran = subprocess.run([exe], capture_output=True, text=True)
+    assert ran.returncode == 0 and "0 wrong" in ran.stdout, ran.stdout + ran.stderr
+
+
 def test_header_compiles_with_the_new_declarations(tmp_path):
     src = tmp_path / "h.c"
     src.write_text('#include "mlconfgen_hip.h"\n'

@@ -412,3 +412,19 @@ def test_the_shared_text_lives_in_one_place():
         text = read(name)
         assert '#include "mcg_interaction_pair.h"' in text and "pair_terms(" in text and "expf(" not in text, name
     assert "mcg_pose_optimise.hip" in read("Makefile")
+    # the tile list and the trial step: written in the two headers, in no kernel file
+    import re
+    sources = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h", ".cpp")))
+    for name in (f for f in sources if f.endswith(".hip")):
+        text = read(name)
+        assert "__ballot(keep)" not in text and "rodrigues_row(" not in text, name
+    assert "__ballot(keep)" in read("mcg_receptor_tiles.h") and "rodrigues_row(" in read("mcg_rigid_step.h")
+    for name in ("mcg_interactions.hip", "mcg_pose_optimise.hip", "mcg_receptor_relief.hip"):
+        text = read(name)
+        assert '#include "mcg_receptor_tiles.h"' in text and "build_tile_list(" in text, name
+    assert "mcg_receptor_tiles.h" in read("Makefile")
+    # the walk's factors and the tile test's slack are defined once (GR_*: the geometry relaxation's own descent)
+    defined = sorted((const, name) for name in sources
+                     for const in re.findall(r"\b(\w*(?:GROW|SHRINK|SLACK)\w*)\s*=[^=]", read(name)) if not const.startswith("GR_"))
+    assert defined == [("TILE_SLACK_ABS", "mcg_receptor_tiles.h"), ("TILE_SLACK_REL", "mcg_receptor_tiles.h"),
+                       ("WALK_GROW", "mcg_rigid_step.h"), ("WALK_SHRINK", "mcg_rigid_step.h")], defined

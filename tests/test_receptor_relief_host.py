@@ -225,6 +225,26 @@ def test_relieve_entry_refuses_bad_arguments_without_a_gpu():
     assert "mcg_receptor_relieve" in _lib.SIGNATURES and h.mcg_abi_version() == 4
 
 
+def test_relieve_entry_states_its_bounds_in_the_refusal():
+    """The whole message, as it read before the walk's shared text moved into headers."""
+    from ml_conformer_generator_amd import _lib
+    h = _lib.lib()
+    p = ctypes.c_void_p(16)                       # never dereferenced: the call fails its host-side check
+    assert h.mcg_receptor_relieve(p, p, p, 3, 27, p, 100, p, 1025, 0.4, 2.0, p, p, p, p, None) == 1
+    assert h.mcg_last_error() == (b"mcg_receptor_relieve: bad arguments (non-null buffers, 1 <= B <= 16384, 1 <= N <= 64, "
+                                  b"1 <= R <= 131072, 0 <= steps <= 1024, margin and max_shift finite and >= 0)")
+
+
+def test_argument_check_program_builds_and_passes_under_host_sanitizers(tmp_path):
+    """`make asan_relief`: the entry's argument checks in a stand-alone program under host-side ASan + UBSan, on the CPU."""
+    exe = str(tmp_path / "relief_arg_check")
+    csrc = os.path.join(REPO, "ml_conformer_generator_amd", "csrc")
+    built = subprocess.run(["make", "-C", csrc, "asan_relief", f"RELIEF_CHECK={exe}"], capture_output=True, text=True)
+    assert built.returncode == 0, built.stdout + built.stderr
+    ran = subprocess.run([exe], capture_output=True, text=True)
+    assert ran.returncode == 0 and "0 not refused" in ran.stdout, ran.stdout + ran.stderr
+
+
 def test_header_with_the_relief_entry_is_plain_c_and_cxx(tmp_path):
     src = tmp_path / "h.c"
     src.write_text('#include "mlconfgen_hip.h"\n'
