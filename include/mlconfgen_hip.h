@@ -816,6 +816,32 @@ int mcg_esp_overlap(const float* ref_xyz, const float* ref_q, int P, const float
 int mcg_canonical_order(const int32_t* z, const int8_t* bonds, const int32_t* n_nodes_dev, int B, int W,
                         int32_t* order_out, int32_t* status_out, int32_t* leaves_out, uint64_t* key_out, void* stream);
 
+/* ---- Stereo identity ("Stereo identity"): which stereoisomer each of B EMBEDDED molecular graphs
+ * is.  The definition is this package's OWN (DESIGN.md states it in full): not RDKit's stereo perception, no CIP labels.
+ *   mcg_stereo_order:   coords[B,W,3] fp32 heavy-atom coordinates (read for real atoms only: the padding may hold anything,
+ *                       NaN included); z, bonds, n_nodes_dev, order_out, status_out, leaves_out, key_out as
+ *                       mcg_canonical_order takes them, limits and status bits included.  Prepass: the tetrahedral
+ *                       candidates (Z 6 / 14, single bonds only, heavy degree 4 or 3, no two terminal twins) with the sign
+ *                       of the normalised signed volume of their neighbours in ascending index, and the double-bond
+ *                       candidates (code 2 between Z 6 / 7, single bonds otherwise, one or two substituents per end, no two
+ *                       terminal twins) with the signs of the dihedral cosines of their substituent pairs; |value| < 0.1,
+ *                       a vanishing vector or inconsistent signs leave the candidate undefined.  Search: the canonical
+ *                       search, except that a leaf whose certificate equals the best one wins if its stereo vector is
+ *                       smaller, and that only twins of degree <= 1 are skipped.  The stereo vector of a leaf: v[k] = 4 tet +
+ *                       db of the atom at position k; tet = 0, or 1 / 2 by sign x the parity that sorts the neighbours by
+ *                       rank; db = 0, or 1 cis / 2 trans of the two lowest-ranked substituents, stored at the end of
+ *                       larger rank.
+ *                       stereo_out[B,W] int8: v in canonical position order, 0 beyond n_b and throughout a row whose status
+ *                       is not 0; stereo_key_out[b]: the key's mixing over (n, row hashes, v) - for grouping, 0 where the
+ *                       status is not 0; counts_out[B,3]: the defined tetrahedral descriptors, the defined double bonds,
+ *                       the undefined candidates (of the prepass: whatever the status).  key_out equals
+ *                       mcg_canonical_order's wherever both have status 0; leaves_out need not.
+ * B = 0 launches nothing.  MCG_ERR_ARG, nothing launched: a null buffer, B outside 0..MCG_CANONICAL_MAX_B, W outside
+ * 1..MCG_CANONICAL_MAX_ATOMS. */
+int mcg_stereo_order(const float* coords, const int32_t* z, const int8_t* bonds, const int32_t* n_nodes_dev, int B, int W,
+                     int32_t* order_out, int32_t* status_out, int32_t* leaves_out, uint64_t* key_out, int8_t* stereo_out,
+                     uint64_t* stereo_key_out, int32_t* counts_out, void* stream);
+
 /* ---- Substructure patterns ("Substructure patterns"): all embeddings of each of P query graphs in
  * each of B molecular graphs, exact in integers.  The definition is this package's OWN (DESIGN.md states it in full): a
  * small query language and a subgraph-monomorphism search, not RDKit's substructure matcher.

@@ -90,6 +90,7 @@ from . import postprocess
 from . import rdkit_order
 from . import receptor as mcg_receptor
 from . import canonical as mcg_canonical
+from . import stereo as mcg_stereo
 from . import substructure as mcg_sub
 from . import fingerprint as mcg_fp
 from . import geometry as mcg_geometry
@@ -366,6 +367,12 @@ class MLConformerGenerator(torch.nn.Module):
         """The exact canonical labelling of padded graphs: `order`, `status`, `leaves`, `key` (`canonical.canonical_order`,
         unchecked: the codes come from the bond write-back or from `mol_graph`; device tensors)."""
         return mcg_canonical.canonical_order(atomic_numbers, bond_orders, n_nodes, self.device, check=False)
+
+    def _stereo_order(self, coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
+                      n_nodes: torch.Tensor) -> dict:
+        """The stereo identity of padded, embedded graphs: `order`, `status`, `leaves`, `key`, `stereo`, `stereo_key`,
+        `counts` (`stereo.stereo_order`, one launch per 16 384 rows)."""
+        return mcg_stereo.stereo_order(coords, atomic_numbers, bond_orders, n_nodes, self.device, check=False)
 
     # the substructure step
     def _match_substructures(self, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor,
@@ -801,7 +808,8 @@ class MLConformerGenerator(torch.nn.Module):
         order, found on the GPU by a partition-refinement search per molecule (`canonical.canonical_order`; DESIGN.md
         section 6, "Canonical graphs and SMILES") - `canonical_status` and `smiles`, the canonical SMILES the host writes
         from it on first read (`smiles.write_smiles`).  The package's OWN definition: valid OpenSMILES, NOT RDKit's
-        canonical SMILES, no string equality with any toolkit; no stereochemistry, no charges.  Equal strings mean the
+        canonical SMILES, no string equality with any toolkit; no charges, and no stereochemistry unless asked for
+        (`smiles="isomeric"`, below).  Equal strings mean the
         same graph, so "unique within the batch" and "novel against a known set" can be counted on them.  A graph the
         labelling refuses (an atom with more than 8 neighbours, more than 4 096 leaves) has `canonical_status` != 0 and
         None for the other two; `to_smiles(canonical=False)` still writes it in its own atom order.  The "[nH]" of an
@@ -810,6 +818,15 @@ class MLConformerGenerator(torch.nn.Module):
         only where its exact identity (`canonical.identity_bytes`) equals that of a better-ranked one: two different
         graphs that share a `graph_key` (cubane and the 8-ring with its four diagonals do) are both kept.  A molecule
         without a canonical order is never dropped.  It reads the Mols' own graphs through RDKit's finisher.
+        `smiles="isomeric"` (records path only): everything `smiles=True` gives, unchanged, and - from one more launch on
+        the returned coordinates (`stereo.stereo_order`; DESIGN.md section 6, "Stereo identity") - `stereo_order`,
+        `stereo_status`, `stereo_descriptors` (per atom 4 tet + db, in the record's order and relative to it),
+        `n_stereo_defined` and `n_stereo_undefined`; `smiles` and `to_smiles()` then write the isomeric string ("@" / "@@",
+        "/" / "\\"), `to_smiles(isomeric=False)` the other.  The package's OWN definition: NOT RDKit's stereo perception,
+        no CIP labels; tetrahedral C / Si and C=C / C=N / N=N only.  `unique="stereo"` (records path only): as
+        `unique="exact"`, but a molecule is dropped only where its stereo identity (`stereo.stereo_identity_bytes`)
+        equals that of a better-ranked one - both enantiomers of a chiral molecule stay, which the reflection-equivariant
+        sampler makes equally often.  `exclude_graphs` stays at constitution level.
         `exclude_graphs=`: an iterable of `GeneratedMolecule` records, Mols or (atomic_numbers, bond_orders) pairs
         (`fingerprint.mol_graph`: their heavy atoms).  They are read with the other arguments and labelled by the same
         kernel directly in front of the generation, behind every refusal of the call, and a generated molecule whose
@@ -883,7 +900,8 @@ class MLConformerGenerator(torch.nn.Module):
         `load_reference_charges` refuses or that no option reads, min_electrostatic_tanimoto outside [-1, 1], and add_hydrogens that is not a bool or on
         a generator with a finisher, RDKit's or a custom one (on Mols use `Chem.AddHs(mol, addCoords=True)`), and standardize
         that is not a bool or on a generator with a finisher (RDKit's finisher runs `standardize_mol` itself), smiles that
-        is not a bool or on a generator with a finisher, a unique other than True, False or "exact", and an
+        is neither a bool nor "isomeric" or on a generator with a finisher, a unique other than True, False, "exact" or
+        "stereo" ("stereo" on a generator with a finisher), and an
         `exclude_graphs` entry that is unreadable, has more than 64 heavy atoms or has no canonical order (the message
         names its position), a substructure option that is no iterable of patterns or holds an entry that cannot be read
         or has more than 32 query atoms (the message names the list, the position and, for a string, the character), and a

@@ -12,6 +12,14 @@
 //                      (LDS broadcasts).  A leaf is compared with the best so far without materialising either
 //                      certificate: lane k finds the first difference in row k of the two relabelled graphs and a wave
 //                      minimum takes the earliest.  Every loop bound is uniform in the wave or guarded by `real`.
+//   k_canonical_order<true>: the same search text with the stereo leaf policy ("Stereo identity").
+//                      Prepass, once: a lane works out from fp32 coordinates whether its atom is a tetrahedral candidate
+//                      or an end of a double-bond candidate, its up to four neighbours in ascending input index, the
+//                      sign s(a) and - the end of lower index - the cis / trans bits of the up to 2 x 2 substituent pairs;
+//                      bytes in LDS.  At a leaf everything is an integer: lane a takes 4 tet + db of its atom from the
+//                      ranks of its neighbours (an inversion count, two comparisons and a bit lookup) into v[rank]; where
+//                      the certificate equals the best one, one more wave minimum takes the first difference of v.  The
+//                      twin rule skips only twins of degree <= 1: swapping them moves no descriptor.
 #include "mcg_common.h"
 #include "mcg_api_internal.h"
 
@@ -78,6 +86,145 @@ struct CnShared {
     uint8_t ord_new[CN_MAXW], ord_best[CN_MAXW];       // position -> atom: the leaf at hand, the best leaf so far
 };
 
+// What the stereo leaf policy keeps beside the search state; nothing for the graph search.
+template <bool STEREO> struct CnStereoShared {};
+template <> struct CnStereoShared<true> {
+    float x[3][CN_MAXW];
+    uint32_t nb[CN_MAXW];                              // four bytes, 0xff = none: a tetrahedral candidate's neighbours in
+                                                       // ascending index; an end of a double bond: its one or two
+                                                       // substituents, then (byte 2) the other end
+    uint8_t deg[CN_MAXW];
+    uint8_t end_ok[CN_MAXW];                           // the atom qualifies as an end of a double-bond candidate
+    uint8_t db_bits[CN_MAXW];                          // written by the end of lower index: 0x80 defined | bit 2 i + j set
+                                                       // where its substituent i and the other end's j are cis
+    uint8_t v_new[CN_MAXW], v_best[CN_MAXW];           // position -> 4 tet + db: the leaf at hand, the best leaf so far
+};
+
+constexpr float CN_STEREO_MIN = 0.1f;                  // |chi| and |cos| below it: undefined (part of the definition)
+constexpr uint32_t CN_KIND_TET_POS = 1, CN_KIND_TET_NEG = 2, CN_KIND_DB = 3;
+
+// The stereo prepass of one molecule, called by all 64 lanes: returns the lane's kind (0, or CN_KIND_*: a DEFINED
+// descriptor), its packed neighbours in `nbp` and its double bond's bits in `dbs`; `counts` (uniform): the defined
+// tetrahedral descriptors, the defined double bonds, the undefined candidates.  Coordinates are read for real atoms only.
+__device__ __forceinline__ uint32_t cn_stereo_prepass(const CnShared& s, CnStereoShared<true>& t,
+                                                      const float* __restrict__ xyz, const int a, const bool real,
+                                                      const int32_t za, const uint32_t deg, const unsigned long long mine,
+                                                      const unsigned long long m1, const unsigned long long m2,
+                                                      const unsigned long long m34, uint32_t& nbp, uint32_t& dbs,
+                                                      int32_t (&counts)[3]) {
+    t.x[0][a] = real ? xyz[3 * a] : 0.0f;
+    t.x[1][a] = real ? xyz[3 * a + 1] : 0.0f;
+    t.x[2][a] = real ? xyz[3 * a + 2] : 0.0f;
+    t.deg[a] = (uint8_t)(deg < 255u ? deg : 255u);
+    __syncthreads();
+    const uint8_t* row = s.code + a * CN_STRIDE;
+    bool twins = false;                                // two terminal twins among the neighbours
+    if (real) {
+        for (unsigned long long f = mine; f != 0ull; f &= f - 1ull) {
+            const int j = __ffsll((long long)f) - 1;
+            for (unsigned long long g = f & (f - 1ull); g != 0ull; g &= g - 1ull) {
+                const int k = __ffsll((long long)g) - 1;
+                twins = twins || (t.deg[j] == 1 && t.deg[k] == 1 && s.z[j] == s.z[k] && row[j] == row[k]);
+            }
+        }
+    }
+    const bool tet = real && (za == 6 || za == 14) && (m2 | m34) == 0ull && (deg == 3u || deg == 4u) && !twins;
+    const bool end = real && (za == 6 || za == 7) && __popcll(m2) == 1 && m34 == 0ull && (deg == 2u || deg == 3u) && !twins;
+    nbp = 0xffffffffu;
+    if (tet || end) {
+        int at = 0;
+        for (unsigned long long f = m1; f != 0ull; f &= f - 1ull, at += 8)
+            nbp = (nbp & ~(0xffu << at)) | ((uint32_t)(__ffsll((long long)f) - 1) << at);
+        if (end) nbp = (nbp & 0xff00ffffu) | ((uint32_t)(__ffsll((long long)m2) - 1) << 16);
+    }
+    t.nb[a] = nbp;
+    t.end_ok[a] = end ? 1 : 0;
+    __syncthreads();
+
+    uint32_t kind = 0;
+    if (tet) {
+        const int i0 = nbp & 0xffu, i1 = (nbp >> 8) & 0xffu, i2 = (nbp >> 16) & 0xffu, o = deg == 4u ? (int)(nbp >> 24) : a;
+        const float ox = t.x[0][o], oy = t.x[1][o], oz = t.x[2][o];
+        const float ax = t.x[0][i0] - ox, ay = t.x[1][i0] - oy, az = t.x[2][i0] - oz;
+        const float bx = t.x[0][i1] - ox, by = t.x[1][i1] - oy, bz = t.x[2][i1] - oz;
+        const float cx = t.x[0][i2] - ox, cy = t.x[1][i2] - oy, cz = t.x[2][i2] - oz;
+        const float det = ax * (by * cz - bz * cy) - ay * (bx * cz - bz * cx) + az * (bx * cy - by * cx);
+        const float len = sqrtf(ax * ax + ay * ay + az * az) * sqrtf(bx * bx + by * by + bz * bz) *
+                          sqrtf(cx * cx + cy * cy + cz * cz);
+        const float chi = det / len;
+        if (len > 0.0f && fabsf(chi) >= CN_STEREO_MIN) kind = chi > 0.0f ? CN_KIND_TET_POS : CN_KIND_TET_NEG;
+    }
+    const int b = end ? (int)((nbp >> 16) & 0xffu) : a;
+    const bool bond = end && t.end_ok[b] != 0 && (int)((t.nb[b] >> 16) & 0xffu) == a;   // a candidate, seen from this end
+    uint32_t bits = 0;
+    if (bond && a < b) {
+        const uint32_t other = t.nb[b];
+        const float ex = t.x[0][b] - t.x[0][a], ey = t.x[1][b] - t.x[1][a], ez = t.x[2][b] - t.x[2][a];
+        const float ee = ex * ex + ey * ey + ez * ez;
+        bool ok = ee > 0.0f;
+        uint32_t cis = 0;
+        for (int i = 0; i < 2; ++i) {
+            const int x = (nbp >> (8 * i)) & 0xffu;
+            for (int j = 0; j < 2; ++j) {
+                const int y = (other >> (8 * j)) & 0xffu;
+                if (x != 0xff && y != 0xff) {
+                    const float dx = t.x[0][x] - t.x[0][a], dy = t.x[1][x] - t.x[1][a], dz = t.x[2][x] - t.x[2][a];
+                    const float fx = t.x[0][y] - t.x[0][b], fy = t.x[1][y] - t.x[1][b], fz = t.x[2][y] - t.x[2][b];
+                    const float tx = (dx * ex + dy * ey + dz * ez) / ee, ty = (fx * ex + fy * ey + fz * ez) / ee;
+                    const float px = dx - tx * ex, py = dy - tx * ey, pz = dz - tx * ez;
+                    const float qx = fx - ty * ex, qy = fy - ty * ey, qz = fz - ty * ez;
+                    const float len = sqrtf(px * px + py * py + pz * pz) * sqrtf(qx * qx + qy * qy + qz * qz);
+                    const float c = (px * qx + py * qy + pz * qz) / len;
+                    ok = ok && len > 0.0f && fabsf(c) >= CN_STEREO_MIN;
+                    cis |= c > 0.0f ? 1u << (2 * i + j) : 0u;
+                }
+            }
+        }
+        // two substituents of one end lie on opposite sides of every substituent of the other end
+        const bool two_x = ((nbp >> 8) & 0xffu) != 0xffu, two_y = ((other >> 8) & 0xffu) != 0xffu;
+        if (two_x) ok = ok && ((cis ^ (cis >> 2)) & 1u) != 0u && (!two_y || ((cis ^ (cis >> 2)) & 2u) != 0u);
+        if (two_y) ok = ok && ((cis ^ (cis >> 1)) & 1u) != 0u && (!two_x || ((cis ^ (cis >> 1)) & 4u) != 0u);
+        bits = ok ? 0x80u | cis : 0u;
+    }
+    t.db_bits[a] = (uint8_t)bits;
+    __syncthreads();
+    if (bond && a > b) bits = t.db_bits[b];
+    dbs = bits & 0xfu;
+    if (bond && (bits & 0x80u) != 0u) kind = CN_KIND_DB;
+    const bool tet_open = tet && kind == 0, bond_low = bond && a < b;
+    counts[0] = __popcll(__ballot((tet && kind != 0) ? 1 : 0));
+    counts[1] = __popcll(__ballot((bond_low && kind != 0) ? 1 : 0));
+    counts[2] = __popcll(__ballot(tet_open ? 1 : 0)) + __popcll(__ballot((bond_low && kind == 0) ? 1 : 0));
+    return kind;
+}
+
+// 4 tet + db of the lane's atom at the labelling in `s.rk` (a leaf: every rank distinct).  Integers only.
+__device__ __forceinline__ uint32_t cn_stereo_value(const CnShared& s, const CnStereoShared<true>& t, const uint32_t kind,
+                                                    const uint32_t nbp, const uint32_t dbs, const int a,
+                                                    const uint32_t rank) {
+    if (kind == CN_KIND_TET_POS || kind == CN_KIND_TET_NEG) {
+        // the parity of the permutation that sorts the neighbours by rank: its inversions (the implicit H is last)
+        const uint32_t r0 = s.rk[nbp & 0xffu], r1 = s.rk[(nbp >> 8) & 0xffu], r2 = s.rk[(nbp >> 16) & 0xffu];
+        uint32_t inv = (r0 > r1 ? 1u : 0u) + (r0 > r2 ? 1u : 0u) + (r1 > r2 ? 1u : 0u);
+        if ((nbp >> 24) != 0xffu) {
+            const uint32_t r3 = s.rk[nbp >> 24];
+            inv += (r0 > r3 ? 1u : 0u) + (r1 > r3 ? 1u : 0u) + (r2 > r3 ? 1u : 0u);
+        }
+        return ((kind == CN_KIND_TET_NEG) != ((inv & 1u) != 0u)) ? 8u : 4u;
+    }
+    if (kind == CN_KIND_DB) {
+        const int b = (nbp >> 16) & 0xffu;
+        if (rank < s.rk[b]) return 0u;                 // stored at the end of larger rank
+        const uint32_t other = t.nb[b];
+        const uint32_t x1 = (nbp >> 8) & 0xffu, y1 = (other >> 8) & 0xffu;
+        const uint32_t i = (x1 != 0xffu && s.rk[x1] < s.rk[nbp & 0xffu]) ? 1u : 0u;
+        const uint32_t j = (y1 != 0xffu && s.rk[y1] < s.rk[other & 0xffu]) ? 1u : 0u;
+        const uint32_t bit = a < b ? 2u * i + j : 2u * j + i;
+        return ((dbs >> bit) & 1u) != 0u ? 1u : 2u;
+    }
+    return 0u;
+}
+
 // Refinement to the point where no rank changes (the number of distinct ranks has stopped growing: a key starts with the
 // lane's rank, so cells only split).  "No rank changed" equals "no cell split" only because every rank vector that comes
 // in is in count-of-smaller form - the initial colour's by construction, an individualised one because v keeps r and the
@@ -128,14 +275,22 @@ __device__ __forceinline__ uint32_t cn_refine(CnShared& s, uint32_t rank, const 
     return rank;
 }
 
+// STEREO: the leaf tie-break policy.  false: the first leaf with the smallest certificate wins (the graph search, whose
+// four trailing arguments are not read); true: among those leaves the smallest stereo vector wins.
+template <bool STEREO>
 __global__ __launch_bounds__(CN_MAXW) void k_canonical_order(const int32_t* __restrict__ z,
                                                              const int8_t* __restrict__ bonds,
                                                              const int32_t* __restrict__ n_nodes, int W,
                                                              int32_t* __restrict__ order_out,
                                                              int32_t* __restrict__ status_out,
                                                              int32_t* __restrict__ leaves_out,
-                                                             unsigned long long* __restrict__ key_out) {
+                                                             unsigned long long* __restrict__ key_out,
+                                                             const float* __restrict__ coords,
+                                                             int8_t* __restrict__ stereo_out,
+                                                             unsigned long long* __restrict__ stereo_key_out,
+                                                             int32_t* __restrict__ counts_out) {
     __shared__ CnShared s;
+    __shared__ CnStereoShared<STEREO> t;
     const int b = blockIdx.x, a = threadIdx.x;
     const int n = min(max(n_nodes[b], 0), W);
     const bool real = a < n;
@@ -169,6 +324,12 @@ __global__ __launch_bounds__(CN_MAXW) void k_canonical_order(const int32_t* __re
     }
     s.by_code[0][a] = m1, s.by_code[1][a] = m2, s.by_code[2][a] = m3, s.by_code[3][a] = m4;
 
+    uint32_t kind = 0, nbp = 0, dbs = 0;                 // the lane's stereo state: a few bits, kept in registers
+    int32_t counts[3] = {0, 0, 0};
+    if constexpr (STEREO)
+        kind = cn_stereo_prepass(s, t, coords + (size_t)b * W * 3, a, real, za, deg, mine, m1, m2, m3 | m4, nbp, dbs,
+                                 counts);
+
     int status = 0;
     if (n == 0) status = MCG_CANONICAL_EMPTY;
     else if (__any((real && deg > (uint32_t)CN_MAXDEG) ? 1 : 0) != 0) status = MCG_CANONICAL_DEGREE;
@@ -196,6 +357,9 @@ __global__ __launch_bounds__(CN_MAXW) void k_canonical_order(const int32_t* __re
             if (__popcll(present) == n) {                // every cell a singleton: a leaf
                 ++leaves;
                 if (real) s.ord_new[rank] = (uint8_t)a;
+                if constexpr (STEREO) {
+                    if (real) t.v_new[rank] = (uint8_t)cn_stereo_value(s, t, kind, nbp, dbs, a, rank);
+                }
                 __syncthreads();
                 bool better = !have_best;
                 if (have_best) {
@@ -213,10 +377,20 @@ __global__ __launch_bounds__(CN_MAXW) void k_canonical_order(const int32_t* __re
                     }
                     const uint32_t first = cn_wave_min(diff);
                     better = first != CN_NONE && (first & 1u) == 0u;
+                    if constexpr (STEREO) {
+                        if (first == CN_NONE) {          // the same certificate: the smaller stereo vector wins
+                            const uint32_t vn = real ? t.v_new[a] : 0u, vb = real ? t.v_best[a] : 0u;
+                            const uint32_t at = cn_wave_min(vn != vb ? ((uint32_t)a << 1) | (vn < vb ? 0u : 1u) : CN_NONE);
+                            better = at != CN_NONE && (at & 1u) == 0u;
+                        }
+                    }
                 }
                 __syncthreads();
                 if (better) {
                     if (real) s.ord_best[a] = s.ord_new[a];
+                    if constexpr (STEREO) {
+                        if (real) t.v_best[a] = t.v_new[a];
+                    }
                     have_best = true;
                 }
                 __syncthreads();
@@ -251,7 +425,8 @@ __global__ __launch_bounds__(CN_MAXW) void k_canonical_order(const int32_t* __re
                         const unsigned long long others = ~(me | (1ull << u));
                         const unsigned long long x = (s.by_code[0][u] ^ m1) | (s.by_code[1][u] ^ m2) |
                                                      (s.by_code[2][u] ^ m3) | (s.by_code[3][u] ^ m4);
-                        skip = skip || (x & others) == 0ull;
+                        // the stereo search skips terminal twins only: swapping others moves their neighbours' descriptors
+                        skip = skip || ((x & others) == 0ull && (!STEREO || deg <= 1u));
                     }
                 }
                 const unsigned long long to_try = cell & ~__ballot(skip ? 1 : 0);
@@ -300,6 +475,24 @@ __global__ __launch_bounds__(CN_MAXW) void k_canonical_order(const int32_t* __re
         const uint32_t key_hi = __shfl(hk, 1);
         key = ((unsigned long long)key_hi << 32) | hk;
     }
+    if constexpr (STEREO) {
+        // the same mixing over (n, the row hashes, v[0..n-1])
+        unsigned long long skey = 0ull;
+        if (status == 0) {
+            uint32_t hk = 0;
+            if (a < 2) {
+                hk = cn_mix(a == 0 ? CN_SEED : CN_SEED_HI, (uint32_t)n);
+                for (int j = 0; j < n; ++j) hk = cn_mix(hk, s.row_hash[a][j]);
+                for (int j = 0; j < n; ++j) hk = cn_mix(hk, (uint32_t)t.v_best[j]);
+                hk = cn_final(hk, 2u * (uint32_t)n + 1u);
+            }
+            const uint32_t key_hi = __shfl(hk, 1);
+            skey = ((unsigned long long)key_hi << 32) | hk;
+        }
+        if (a < W) stereo_out[(size_t)b * W + a] = (status == 0 && real) ? (int8_t)t.v_best[a] : (int8_t)0;
+        if (a == 0) stereo_key_out[b] = skey;
+        if (a < 3) counts_out[(size_t)b * 3 + a] = a == 0 ? counts[0] : a == 1 ? counts[1] : counts[2];
+    }
     if (a < W) order_out[(size_t)b * W + a] = (status == 0 && real) ? (int32_t)s.ord_best[a] : -1;
     if (a == 0) {
         status_out[b] = status;
@@ -320,8 +513,28 @@ extern "C" int mcg_canonical_order(const int32_t* z, const int8_t* bonds, const 
         return MCG_ERR_ARG;
     }
     if (B == 0) return MCG_OK;
-    hipLaunchKernelGGL(k_canonical_order, dim3((unsigned)B), dim3(CN_MAXW), 0, (hipStream_t)stream, z, bonds, n_nodes_dev,
-                       W, order_out, status_out, leaves_out, reinterpret_cast<unsigned long long*>(key_out));
+    hipLaunchKernelGGL(k_canonical_order<false>, dim3((unsigned)B), dim3(CN_MAXW), 0, (hipStream_t)stream, z, bonds,
+                       n_nodes_dev, W, order_out, status_out, leaves_out, reinterpret_cast<unsigned long long*>(key_out),
+                       (const float*)nullptr, (int8_t*)nullptr, (unsigned long long*)nullptr, (int32_t*)nullptr);
+    MCG_HIP(hipGetLastError());
+    return MCG_OK;
+}
+
+extern "C" int mcg_stereo_order(const float* coords, const int32_t* z, const int8_t* bonds, const int32_t* n_nodes_dev,
+                                int B, int W, int32_t* order_out, int32_t* status_out, int32_t* leaves_out,
+                                uint64_t* key_out, int8_t* stereo_out, uint64_t* stereo_key_out, int32_t* counts_out,
+                                void* stream) {
+    if (!coords || !z || !bonds || !n_nodes_dev || !order_out || !status_out || !leaves_out || !key_out || !stereo_out ||
+        !stereo_key_out || !counts_out || B < 0 || B > MCG_CANONICAL_MAX_B || W < 1 || W > CN_MAXW) {
+        mcg_set_error("mcg_stereo_order: bad arguments (non-null coords, z, bonds, n_nodes, order_out, status_out, "
+                      "leaves_out, key_out, stereo_out, stereo_key_out and counts_out, 0 <= B <= %d, 1 <= W <= %d)",
+                      MCG_CANONICAL_MAX_B, CN_MAXW);
+        return MCG_ERR_ARG;
+    }
+    if (B == 0) return MCG_OK;
+    hipLaunchKernelGGL(k_canonical_order<true>, dim3((unsigned)B), dim3(CN_MAXW), 0, (hipStream_t)stream, z, bonds,
+                       n_nodes_dev, W, order_out, status_out, leaves_out, reinterpret_cast<unsigned long long*>(key_out),
+                       coords, stereo_out, reinterpret_cast<unsigned long long*>(stereo_key_out), counts_out);
     MCG_HIP(hipGetLastError());
     return MCG_OK;
 }

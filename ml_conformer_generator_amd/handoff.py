@@ -77,6 +77,11 @@ class Measured:
     interaction_score_before: Optional[float] = None  # E of the pose `optimise_pose` started from
     pose_optimisation_rmsd: Optional[float] = None
     pose_trials_kept: Optional[int] = None
+    stereo_order: Optional[List[int]] = None      # the stereo search's atom order, -1 beyond the atoms as it comes
+    stereo_status: Optional[int] = None           # `canonical.describe_status`; 0 = the stereo identity is defined
+    stereo_descriptors: Optional[list] = None     # [the row of v as it comes, None -> per atom in record order on first read]
+    n_stereo_defined: Optional[int] = None
+    n_stereo_undefined: Optional[int] = None
 
 
 _UNMEASURED = Measured()          # shared by every record that carries no values: never written to
@@ -111,8 +116,11 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
     `interaction_atom_scores` is left as (the one host copy, row, atom count) and sliced on first read.
     The pose optimisation of a call with `optimise_pose` comes as `interaction_score_before` [n] fp32,
     `pose_optimisation_rmsd` [n] fp32 and `pose_trials_kept` [n] (negative: posing failed - the record gets None for all
-    three)."""
-    hyd = {k: values.get(k) for k in ("hydrogen_coords", "hydrogen_parents", "atom_map", "kekule_bond_orders",
+    three).
+    The stereo identity of a call with `smiles="isomeric"` comes as `stereo_order` [n,W] int32, `stereo_status` [n],
+    `stereo_descriptors` [n,W] int8 - `stereo.stereo_order`'s `stereo`: v in canonical position order, which a record
+    turns into its own order on first read -, `n_stereo_defined` [n] and `n_stereo_undefined` [n] (all five or none)."""
+    hyd = {k: values.get(k) for k in ("stereo_descriptors", "hydrogen_coords", "hydrogen_parents", "atom_map", "kekule_bond_orders",
                                       "partial_charges", "hydrogen_charges", "canonical_order", "substructure_counts",
                                       "substructure_status", "substructure_first", "substructure_patterns",
                                       "interaction_atom_scores")}
@@ -159,6 +167,8 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
     if hyd["canonical_order"] is not None:
         orders = hyd["canonical_order"].cpu().to(torch.int32)
         cols["canonical_order"] = [(orders, b, k) for b, k in enumerate((orders >= 0).sum(dim=1).tolist())]
+    if hyd["stereo_descriptors"] is not None:
+        cols["stereo_descriptors"] = [[row, None] for row in hyd["stereo_descriptors"].cpu().tolist()]
     if hyd["substructure_counts"] is not None:
         for k in ("substructure_counts", "substructure_status", "substructure_first"):
             host = hyd[k].cpu().to(torch.int32)
@@ -230,6 +240,9 @@ class GeneratedMolecule:
     `canonical_order` / `canonical_status` / `smiles`: its exact canonical atom order and canonical SMILES when the call
     asked for `smiles` (`canonical.py`, `smiles.py`: the package's own definition - valid OpenSMILES, NOT RDKit's canonical
     SMILES), else None; `to_smiles()` writes the string, `to_smiles(canonical=False)` one in the record's own atom order.
+    `stereo_order` / `stereo_status` / `stereo_descriptors` / `n_stereo_defined` / `n_stereo_undefined`: which
+    stereoisomer its returned coordinates are when the call asked for `smiles="isomeric"` (`stereo.py`: the package's own
+    definition, NOT RDKit's stereo perception, no CIP labels), else None; `smiles` and `to_smiles()` are then isomeric.
     `interaction_score` / `interaction_terms` / `receptor_hbonds` / `interaction_atom_scores`: its empirical interaction
     score with the call's typed receptor, the sums behind it, its hydrogen-bond count and per-atom contributions when the
     call asked for `interaction_scores` (`interactions.py`: the package's own definition, NOT AutoDock Vina's output), else
@@ -238,13 +251,13 @@ class GeneratedMolecule:
     matched (`require_substructures`, `exclude_substructures`, `substructure_counts`, in that order) and, per pattern, how
     many embeddings this molecule has, how the search ended and the first embedding (`substructure.py`: the package's own
     definition, NOT RDKit's substructure matcher), else None."""
-    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_measured", "_smiles")
+    __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_measured", "_smiles", "_unmarked")
 
     def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True,
                  sample_id: Optional[int] = None):
         self._z, self._coords, self._bonds, self.valid = list(atomic_numbers), coords, bond_orders, bool(valid)
         self._batch, self._b, self._sid, self._measured = None, -1, sample_id, _UNMEASURED
-        self._smiles = None
+        self._smiles = self._unmarked = None
 
     @classmethod
     def _view(cls, batch: _HostBatch, b: int, valid: bool, sample_id: Optional[int] = None,
@@ -254,7 +267,7 @@ class GeneratedMolecule:
         m.valid, m._batch, m._b = valid, batch, b
         m._sid = b if sample_id is None else sample_id
         m._measured = measured
-        m._smiles = None
+        m._smiles = m._unmarked = None
         return m
 
     @property
@@ -335,11 +348,63 @@ class GeneratedMolecule:
         return o if self._measured.canonical_status == 0 else None
 
     @property
+    def stereo_status(self) -> Optional[int]:
+        """The status word of this molecule's stereo search (`canonical.describe_status`; its leaf count differs from the
+        graph search's, so BUDGET may be set here alone) when the call asked for `smiles="isomeric"`; None otherwise."""
+        return self._measured.stereo_status
+
+    @property
+    def stereo_order(self) -> Optional[List[int]]:
+        """The atom order of the stereo identity (`stereo.stereo_order`): position k holds the index, in this record, of
+        the atom of rank k.  The graph relabelled this way equals the one relabelled by `canonical_order`; among the
+        orders of which that is true, this one has the smallest stereo vector.  With `smiles="isomeric"`; None
+        otherwise, and where `stereo_status` is not 0."""
+        if self._measured.stereo_status != 0:
+            return None
+        return [a for a in self._measured.stereo_order if a >= 0]
+
+    @property
+    def stereo_descriptors(self) -> Optional[List[int]]:
+        """Per atom, in this record's order and RELATIVE TO IT, 4 tet + db (`stereo.own_order_descriptors`): tet 1 / 2 is
+        the handedness of the atom's neighbours in ascending index (the implicit H last) in the returned coordinates, db
+        1 cis / 2 trans of the lowest-indexed substituents of a double bond's ends, stored at the end of larger index; 0 =
+        no candidate or undefined.  The package's OWN definition (`stereo.py`), not CIP labels.  With
+        `smiles="isomeric"`; None otherwise, and where `stereo_status` is not 0."""
+        order = self.stereo_order
+        if order is None:
+            return None
+        d = self._measured.stereo_descriptors
+        if d[1] is None:
+            from .stereo import own_order_descriptors
+            d[1] = own_order_descriptors(order, d[0][: len(order)], self.bond_orders)
+        return d[1]
+
+    @property
+    def n_stereo_defined(self) -> Optional[int]:
+        """The defined descriptors - tetrahedral centres plus double bonds - of the returned coordinates
+        (`smiles="isomeric"`; None otherwise)."""
+        return self._measured.n_stereo_defined
+
+    @property
+    def n_stereo_undefined(self) -> Optional[int]:
+        """The candidates left undefined: a centre flatter than |chi| = 0.1, a double bond twisted to |cos| < 0.1 or with
+        inconsistent sides (`smiles="isomeric"`; None otherwise)."""
+        return self._measured.n_stereo_undefined
+
+    @property
+    def n_stereo_unmarked(self) -> Optional[int]:
+        """The defined double bonds the isomeric `smiles` could not give a mark of their own (`smiles.py`, "Isomeric";
+        0 in all but contrived ring systems); None where `smiles` is not isomeric."""
+        return self._unmarked if self.smiles is not None else None
+
+    @property
     def smiles(self) -> Optional[str]:
         """The canonical SMILES of the heavy-atom graph (`smiles.write_smiles` on the graph in `canonical_order`: valid
-        OpenSMILES by the package's OWN definition - NOT RDKit's canonical SMILES; no stereochemistry, no charges), built
+        OpenSMILES by the package's OWN definition - NOT RDKit's canonical SMILES; no charges), built
         on first access, when the call asked for `smiles`; None otherwise, and where `canonical_status` is not 0.  Equal
-        strings: the same graph.  Its "[nH]" may sit on the other N than the hydrogen `add_hydrogens` placed."""
+        strings: the same graph.  Its "[nH]" may sit on the other N than the hydrogen `add_hydrogens` placed.
+        With `smiles="isomeric"` and a `stereo_status` of 0 the string is isomeric - the graph in `stereo_order` with the
+        marks of its stereo vector: equal strings then mean the same stereoisomer by `stereo.py`'s definition."""
         if self._smiles is None and self.canonical_order is not None:
             self._smiles = self.to_smiles(canonical=True)
         return self._smiles
@@ -652,14 +717,31 @@ class GeneratedMolecule:
         lines.append("M  END")
         return "\n".join(lines) + "\n"
 
-    def to_smiles(self, canonical: bool = True) -> str:
+    def to_smiles(self, canonical: bool = True, isomeric: Optional[bool] = None) -> str:
         """SMILES of the heavy-atom graph by `smiles.write_smiles` (the package's own writer: valid OpenSMILES, not RDKit's
         canonical SMILES).  `canonical=True`: the atoms in the record's `canonical_order` - the package's canonical
         string; ValueError, naming the status, where the record has no canonical order (a call without `smiles`, or a
         graph the labelling refused).  `canonical=False` always works: the atoms are written in the record's OWN order, so
-        two records of one molecule may get different strings."""
-        from .smiles import write_smiles
+        two records of one molecule may get different strings.
+        `isomeric`: None - isomeric where the record has a stereo identity (`smiles="isomeric"`, `stereo_status` 0);
+        False - never: the string `smiles=True` gives; True - ValueError where the record has none.  The canonical
+        isomeric string is written in `stereo_order`, the other in the record's own order from `stereo_descriptors`."""
+        from .smiles import write_smiles, write_smiles_counted
         z, bonds = self.atomic_numbers, torch.as_tensor(self.bond_orders)
+        stereo_order = self.stereo_order if isomeric is not False else None
+        if isomeric and stereo_order is None:
+            from .canonical import describe_status
+            status = self._measured.stereo_status
+            raise ValueError("this record has no stereo identity: " + (
+                'generate with smiles="isomeric"' if status is None else f"its search ended with {describe_status(status)}"))
+        if stereo_order is not None:
+            if not canonical:
+                return write_smiles(z, bonds, self.stereo_descriptors)
+            idx = torch.tensor(stereo_order, dtype=torch.long)
+            text, self._unmarked = write_smiles_counted([z[a] for a in stereo_order],
+                                                        bonds.index_select(0, idx).index_select(1, idx),
+                                                        self._measured.stereo_descriptors[0][: len(stereo_order)])
+            return text
         if not canonical:
             return write_smiles(z, bonds)
         order = self.canonical_order
@@ -829,7 +911,11 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                            interaction_atom_scores: Optional[torch.Tensor] = None,
                            interaction_score_before: Optional[torch.Tensor] = None,
                            pose_optimisation_rmsd: Optional[torch.Tensor] = None,
-                           pose_trials_kept: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
+                           pose_trials_kept: Optional[torch.Tensor] = None,
+                           stereo_order: Optional[torch.Tensor] = None, stereo_status: Optional[torch.Tensor] = None,
+                           stereo_descriptors: Optional[torch.Tensor] = None,
+                           n_stereo_defined: Optional[torch.Tensor] = None,
+                           n_stereo_undefined: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
     (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
     (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records).
@@ -864,6 +950,10 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     `interaction_score_before[b]` / `pose_optimisation_rmsd[b]` / `pose_trials_kept[b]`: row b's pose optimisation as
     `postprocess.optimise_rows` spells it (negative trials kept: its pose failed, the record gets None for all three;
     None: a call without `optimise_pose`).
+    `stereo_order[b]` [W] / `stereo_status[b]` / `stereo_descriptors[b]` [W] int8 / `n_stereo_defined[b]` /
+    `n_stereo_undefined[b]`: row b's stereo identity as `stereo.stereo_order` returns it - `stereo_descriptors` is its
+    `stereo`, v in canonical position order; the counts are defined tetrahedral + defined double bonds, and the undefined
+    candidates (all five or none; None: a call without `smiles="isomeric"`).
     The value keywords are the fields of `Measured`
     and go to `measured_from_tensors`; a call with no ids and no values builds the views and nothing else."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
@@ -885,7 +975,9 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                   interaction_score=interaction_score, interaction_terms=interaction_terms,
                   receptor_hbonds=receptor_hbonds, interaction_atom_scores=interaction_atom_scores,
                   interaction_score_before=interaction_score_before, pose_optimisation_rmsd=pose_optimisation_rmsd,
-                  pose_trials_kept=pose_trials_kept)
+                  pose_trials_kept=pose_trials_kept, stereo_order=stereo_order, stereo_status=stereo_status,
+                  stereo_descriptors=stereo_descriptors, n_stereo_defined=n_stereo_defined,
+                  n_stereo_undefined=n_stereo_undefined)
     if sample_ids is None and all(v is None for v in values.values()):
         return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
     flags = valid.cpu().tolist()

@@ -22,7 +22,9 @@ Stages, in this order:
        placement of `add_hydrogens` is reused when that is on too - one charge launch and, with `electrostatic_scores`,
        the overlap launches against the reference's charge points; and the canonical step (`identities`; `smiles`,
        `unique="exact"`, `exclude_graphs`): one `_canonical_order` launch over the rows - the excluded graphs were
-       labelled by the same seam directly in front of the generation (`label_excluded`); and the substructure step
+       labelled by the same seam directly in front of the generation (`label_excluded`); and the stereo step
+       (`stereo_identities`; `smiles="isomeric"`, `unique="stereo"`; records only): one `_stereo_order` launch over the
+       rows, on the returned coordinates and graphs; and the substructure step
        (`substructures`; `require_substructures`, `exclude_substructures`, `substructure_counts`): one
        `_match_substructures` call over the rows, every pattern of the three lists in it; and the interaction step
        (`interactions`; `interaction_scores`, `max_interaction_score`, `rank_by="interaction"`; records only): one
@@ -43,7 +45,8 @@ that arrive are already the parent fragments'; its four per-sample tensors (`ato
 
 The device work goes through the generator's seams (`_pose`, `_score`, `_pair`, `_receptor_coords`, `_relieve`,
 `_optimise_pose`, `_score_placed`, `_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, `_pharm_perceive`,
-`_pharm_score`, `_add_hydrogens`, `_peoe_charges`, `_esp_score`, `_canonical_order`, `_match_substructures`,
+`_pharm_score`, `_add_hydrogens`, `_peoe_charges`, `_esp_score`, `_canonical_order`, `_stereo_order`,
+`_match_substructures`,
 `_interaction_scores`), looked up on the instance at the time of the call.  The shape seams take the request's reference
 object; which kind it is - a conformer or a solid - is `cheminformatics`' business."""
 from __future__ import annotations
@@ -59,6 +62,7 @@ import torch
 
 from . import _args
 from . import canonical as mcg_canonical
+from . import stereo as mcg_stereo
 from . import cheminformatics
 from . import electrostatics as mcg_esp
 from . import fingerprint as mcg_fp
@@ -107,10 +111,12 @@ class Request:
     ref_charge_graph: Optional[tuple] = None      # else (atomic numbers, bond codes [n,n] int8, coords [n,3]) to charge
     min_electrostatic_tanimoto: Optional[float] = None
     partial_charges: bool = False                 # `partial_charges`: the charges on the returned records
-    smiles: bool = False                          # `smiles`: canonical order and SMILES on the returned records
+    smiles: Union[bool, str] = False              # `smiles`: canonical order and SMILES on the returned records;
+    #                                               "isomeric": the stereo identity too, and the isomeric string
     excluded_graphs: Optional[tuple] = None       # `exclude_graphs` as read on the host: (atomic numbers, bond codes) each
     exclude: Optional[frozenset] = None           # their (key, identity bytes), once `label_excluded` has labelled them
-    # `unique` above is False, True (one row per `graph_key`) or "exact" (one row per exact identity)
+    # `unique` above is False, True (one row per `graph_key`), "exact" (one row per exact identity) or "stereo" (one row
+    # per stereo identity, `stereo.stereo_identity_bytes`)
     substructures: Optional[object] = None        # `substructure.Compiled`: the patterns of `require_substructures`, then
     #                                               `exclude_substructures`, then `substructure_counts`, compiled together
     n_required: int = 0                           # how many of them must be proven present,
@@ -139,13 +145,18 @@ class Request:
 
     @property
     def needs_canonical(self) -> bool:
-        return self.smiles or self.needs_identity
+        return bool(self.smiles) or self.needs_identity
+
+    @property
+    def needs_stereo(self) -> bool:
+        """Whether the call launches the stereo search (`smiles="isomeric"`, `unique="stereo"`)."""
+        return self.smiles == "isomeric" or self.unique == "stereo"
 
     @property
     def measures(self) -> bool:
         """Whether any option is on (a receptor needs the pose, a selection implies its score)."""
         return (self.overlay or self.scores_shape or self.needs_fingerprints or self.needs_canonical
-                or self.substructures is not None)
+                or self.needs_stereo or self.substructures is not None)
 
     @property
     def removes(self) -> bool:
@@ -219,8 +230,10 @@ def parse_request(gen, reference_conformer, *, reference_context=None, shape_sco
     fields.update(_electrostatic_fields(o, esp, scores_shape, conformer))
     fields.update(_pharmacophore_fields(o, scores_shape, conformer))
     _args.check_flag("chemical_scores", chemical_scores)
-    if not (isinstance(unique, str) and unique == "exact"):
+    if not (isinstance(unique, str) and unique in ("exact", "stereo")):
         _args.check_flag("unique", unique)
+    if isinstance(unique, str) and unique == "stereo" and finisher is not None:
+        raise ValueError(mcg_stereo.REFUSAL_UNIQUE_WITH_FINISHER)
     excluded = None if exclude_graphs is None else read_excluded(exclude_graphs)
     fields.update(_substructure_fields(o, custom_finisher))
     graph_read = fields.get("ref_pharm_graph") is not None or fields.get("ref_charge_graph") is not None
@@ -239,14 +252,16 @@ def entry_request(gen, arguments: dict) -> Request:
 
 
 def _record_flags(o, finisher) -> dict:
-    """`smiles`: True or False; refused with a finisher (the order and the string go onto the records).
+    """`smiles`: True, False or "isomeric"; refused with a finisher (the order and the string go onto the records).
     `add_hydrogens`: True or False; it works with every other option, but not with a finisher, RDKit's or a custom one
     (the hydrogens go onto the records).  `standardize`: True or False; likewise refused with a finisher (RDKit's
     `standardize_mol` already does it on Mols)."""
     for name, refusal in (("smiles", mcg_canonical.REFUSAL_WITH_FINISHER),
                           ("add_hydrogens", mcg_hydrogens.REFUSAL_WITH_FINISHER),
                           ("standardize", mcg_standardize.REFUSAL_WITH_FINISHER)):
-        if _args.check_flag(name, getattr(o, name)) and finisher is not None:
+        value = getattr(o, name)
+        isomeric = name == "smiles" and isinstance(value, str) and value == "isomeric"
+        if (isomeric or _args.check_flag(name, value)) and finisher is not None:
             raise ValueError(refusal)
     return dict(smiles=o.smiles, add_hydrogens=o.add_hydrogens, standardize=bool(o.standardize))
 
@@ -586,6 +601,16 @@ def label_excluded(gen, req: Request) -> Request:
     return dataclasses.replace(req, exclude=excluded_identities(gen, list(req.excluded_graphs)))
 
 
+def stereo_identities(gen, coords, atomic_numbers, bond_orders, n_nodes):
+    """The stereo step of padded, embedded graphs, one `_stereo_order` call: (its result, per row the stereo identity as
+    (`stereo_key`, `stereo.stereo_identity_bytes`), None for a row that has no stereo order - it is not proven equal to
+    anything)."""
+    found = gen._stereo_order(coords, atomic_numbers, bond_orders, n_nodes)
+    keys = [k & 0xFFFFFFFFFFFFFFFF for k in found["stereo_key"].cpu().tolist()]
+    exact = mcg_stereo.stereo_identity_bytes(coords, atomic_numbers, bond_orders, n_nodes, ordered=found)
+    return found, [None if e is None else (k, e) for k, e in zip(keys, exact)]
+
+
 def select_exact(exact: List[Optional[tuple]], order: List[int]) -> List[int]:
     """Positions to keep so that every exact identity occurs once: the rows are grouped by their 64-bit key, and a row is
     dropped only where its identity bytes equal those of a row that comes before it in `order` (positions, best first).  A
@@ -611,6 +636,7 @@ class Rows:
     row: List[int]                                # index into the device tensors behind the pair matrices
     exact: Optional[List[Optional[tuple]]] = None     # `identities` per row, where the call compares exact identities
     sub: Optional[List[tuple]] = None                 # `substructures` per row, where the call matches patterns
+    stereo: Optional[List[Optional[tuple]]] = None    # `stereo_identities` per row, with `unique="stereo"`
 
     def take(self, keep: List[int]) -> "Rows":
         """The rows at the positions `keep`, in that order."""
@@ -630,7 +656,7 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
     `exclude` keeps it, and one warning per call names how many such rows there were -,
     then `exclude_graphs` - the rows whose exact identity is one of the excluded graphs' (a row without a canonical order is
     not proven equal to anything and stays) -, then `unique` - of the rows with one graph key (`unique="exact"`: with one
-    exact identity, `select_exact`) the first in ranking order
+    exact identity, `select_exact`; `unique="stereo"`: with one stereo identity, the same walk) the first in ranking order
     (`cheminformatics.ranking_key` of `Request.ranking_score`: by shape score where the call scores shape - plus the
     pharmacophore score with `rank_by="combo"`, the electrostatic score with `rank_by="electrostatic"`; by minus the
     interaction score with `rank_by="interaction"` - else the lowest sample id), still in the
@@ -673,6 +699,8 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
             req.ranking_score(rows.measured[i]), rows.sample_id[i]))
         if req.unique == "exact":
             rows = rows.take(select_exact(rows.exact, order))
+        elif req.unique == "stereo":                  # the same walk over (stereo_key, stereo identity bytes)
+            rows = rows.take(select_exact(rows.stereo, order))
         else:
             rows = rows.take(mcg_fp.select_unique([m.graph_key for m in rows.measured], order))
     if not req.selects_by_shape and req.max_pairwise_chemical_tanimoto is None:
@@ -936,6 +964,13 @@ def return_records(gen, req: Request, res: dict, row_ids: Optional[torch.Tensor]
         canon = gen._canonical_order(res["elements"], res["bond"], res["n_nodes"])
     if req.smiles:
         values.update(canonical_order=canon["order"], canonical_status=canon["status"])
+    stereo = None
+    if req.needs_stereo:                          # one more launch: the returned coordinates, the parent graph
+        found, stereo = stereo_identities(gen, res["x"], res["elements"], res["bond"], res["n_nodes"])
+        if req.smiles == "isomeric":
+            values.update(stereo_order=found["order"], stereo_status=found["status"], stereo_descriptors=found["stereo"],
+                          n_stereo_defined=found["counts"][:, 0] + found["counts"][:, 1],
+                          n_stereo_undefined=found["counts"][:, 2])
     sub = None
     if req.substructures is not None:
         matched, sub = substructures(gen, req, res["elements"], res["bond"], res["n_nodes"])
@@ -968,7 +1003,8 @@ def return_records(gen, req: Request, res: dict, row_ids: Optional[torch.Tensor]
         return kept
     rows = Rows(kept, [m.sample_id for m in kept], [m._measured for m in kept], [m.batch_row for m in kept],
                 None if exact is None else [exact[m.batch_row] for m in kept],
-                None if sub is None else [sub[m.batch_row] for m in kept])
+                None if sub is None else [sub[m.batch_row] for m in kept],
+                None if stereo is None or req.unique != "stereo" else [stereo[m.batch_row] for m in kept])
 
     def shape_pair(left: Rows):
         x = res["x"]
