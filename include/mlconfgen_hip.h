@@ -885,6 +885,46 @@ int mcg_substructure_match(const int32_t* z, const int8_t* bonds, const int32_t*
                            int32_t* count /*[B,P]*/, int32_t* status /*[B,P]*/, int32_t* first /*[B,P,32]*/,
                            uint64_t* covered /*[B,P]*/, void* stream);
 
+/* ---- Rings and scaffolds ("Rings and scaffolds"): general ring perception and the Murcko-type
+ * scaffold of each of B molecular graphs, exact in integers.  The definitions are this package's OWN (DESIGN.md states them
+ * in full): not RDKit's ring perception, not an SSSR, and NOT RDKit's MurckoScaffold.
+ *   mcg_ring_scaffold:  z, bonds, n_nodes_dev as mcg_canonical_order takes them (no degree cap; z is not read: the
+ *                       definitions are the graph's alone).
+ *                       Ring bond: (a, j) iff j is reachable from a with that bond left out.  Ring atom: an atom with a
+ *                       ring bond.  Ring system: a connected component of the ring-bond sub-graph (fused, bridged and
+ *                       spiro rings are one system), labelled by its lowest atom.  Size of a ring bond: the shortest path
+ *                       between its ends with the bond left out, plus 1; of an atom: the smallest over its ring bonds.
+ *                       Linker atoms: remove, as long as one exists, every atom with fewer than two remaining neighbours;
+ *                       the non-ring atoms that remain.  Exo atoms: atoms outside ring and linker joined to one of them by
+ *                       a code-2 bond.  Scaffold = ring + linker + exo.
+ *                       ring_nb_out[B,W]: bit j of entry a set iff (a, j) is a ring bond; 0 at and beyond n_b.
+ *                       ring_size_out[B,W]: the atom's size, 0 for a non-ring atom and at and beyond n_b.
+ *                       ring_system_out[B,W]: the atom's system label, -1 for a non-ring atom and at and beyond n_b.
+ *                       masks_out[B,4]: bit a set iff atom a is a ring / linker / exo / scaffold atom, in this order.
+ *                       counts_out[B,8]: n_rings = ring bonds - ring atoms + ring systems (the cyclomatic number),
+ *                       n_ring_systems, min_ring_size, max_ring_size (the smallest and largest ring-bond size; 0, 0 for an
+ *                       acyclic graph), ring atoms, linker atoms, exo atoms, ring bonds.
+ *   mcg_induced_subgraph: z, bonds, n_nodes_dev likewise; mask[b]: bit a set keeps atom a (bits at and beyond n_b are
+ *                       ignored); mode 0 keeps elements and bond codes (a value that is no code is written as 0), mode 1
+ *                       writes Z = 6 and code 1 (the generic framework).  The kept atoms stay in ascending index,
+ *                       compacted to the front: z_out[B,W], bonds_out[B,W,W] (zero behind the kept atoms, zero diagonal),
+ *                       n_out[b] the kept atoms, map_out[B,W] the source index of each, -1 behind them.  The outputs are
+ *                       padded graphs as mcg_canonical_order takes them, which gives a scaffold its identity.
+ *                       Both: one 64-lane workgroup per molecule, one launch, integer work only, no atomics, no scratch:
+ *                       a molecule's outputs have the same bits whatever the batch, its row and the padded width, and
+ *                       counts, sizes and masks follow the atoms under any renumbering.
+ * B = 0 launches nothing.  MCG_ERR_ARG, nothing launched: a null buffer, B outside 0..MCG_SCAFFOLD_MAX_B, W outside
+ * 1..MCG_SCAFFOLD_MAX_ATOMS, a mode other than 0 or 1. */
+#define MCG_SCAFFOLD_MAX_ATOMS 64
+#define MCG_SCAFFOLD_MAX_B 16384
+int mcg_ring_scaffold(const int32_t* z, const int8_t* bonds, const int32_t* n_nodes_dev, int B, int W,
+                      uint64_t* ring_nb_out /*[B,W]*/, int32_t* ring_size_out /*[B,W]*/,
+                      int32_t* ring_system_out /*[B,W]*/, uint64_t* masks_out /*[B,4]*/, int32_t* counts_out /*[B,8]*/,
+                      void* stream);
+int mcg_induced_subgraph(const int32_t* z, const int8_t* bonds, const int32_t* n_nodes_dev, const uint64_t* mask /*[B]*/,
+                         int mode, int B, int W, int32_t* z_out /*[B,W]*/, int8_t* bonds_out /*[B,W,W]*/,
+                         int32_t* n_out /*[B]*/, int32_t* map_out /*[B,W]*/, void* stream);
+
 /* ---- Receptor interactions ("Receptor interactions"): an empirical interaction score of B posed
  * molecules against a typed receptor.  The definition is this package's OWN (interactions.py states it in full): the
  * functional form of the AutoDock Vina scoring function on the package's heavy-atom types, intermolecular terms only - NOT

@@ -91,6 +91,7 @@ from . import rdkit_order
 from . import receptor as mcg_receptor
 from . import canonical as mcg_canonical
 from . import stereo as mcg_stereo
+from . import scaffold as mcg_scaffold
 from . import substructure as mcg_sub
 from . import fingerprint as mcg_fp
 from . import geometry as mcg_geometry
@@ -373,6 +374,15 @@ class MLConformerGenerator(torch.nn.Module):
         """The stereo identity of padded, embedded graphs: `order`, `status`, `leaves`, `key`, `stereo`, `stereo_key`,
         `counts` (`stereo.stereo_order`, one launch per 16 384 rows)."""
         return mcg_stereo.stereo_order(coords, atomic_numbers, bond_orders, n_nodes, self.device, check=False)
+
+    # the scaffold step
+    def _ring_scaffolds(self, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor,
+                        generic: bool) -> dict:
+        """The rings and the scaffold (`generic`: the framework) of padded graphs (`scaffold.murcko_scaffolds`, unchecked:
+        the codes come from the bond write-back or from `mol_graph`; device tensors, `identity` a host list): one launch
+        of each entry of `scaffold.py`, and the sub-graphs' canonical labelling through `_canonical_order`."""
+        return mcg_scaffold.murcko_scaffolds(atomic_numbers, bond_orders, n_nodes, self.device, generic, check=False,
+                                             canonical_order=self._canonical_order)
 
     # the substructure step
     def _match_substructures(self, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor,
@@ -827,6 +837,16 @@ class MLConformerGenerator(torch.nn.Module):
         `unique="exact"`, but a molecule is dropped only where its stereo identity (`stereo.stereo_identity_bytes`)
         equals that of a better-ranked one - both enantiomers of a chiral molecule stay, which the reflection-equivariant
         sampler makes equally often.  `exclude_graphs` stays at constitution level.
+        `unique="scaffold"` / `unique="framework"`: as `unique="exact"` - same place in the order of stages, same ranking,
+        the Mols' own graphs through RDKit's finisher - but one molecule per ring framework stays: a molecule is dropped
+        where its scaffold - ring, linker and doubly bonded exo atoms, elements and bond codes kept - or, with
+        "framework", its generic framework - ring and linker atoms, all carbon, all single - has the identity of a
+        better-ranked molecule's (`scaffold.murcko_scaffolds`; DESIGN.md section 6, "Rings and scaffolds": the package's OWN
+        definitions, NOT RDKit's ring perception or MurckoScaffold).  All acyclic molecules share the empty scaffold; a
+        scaffold without a canonical order is never dropped.  On the records path every returned record carries `n_rings`,
+        `n_ring_systems`, `min_ring_size`, `max_ring_size`, `ring_sizes`, `ring_systems`, `scaffold_atoms`, `scaffold_key`,
+        `scaffold_status` and - with `smiles` - `scaffold_smiles`, read off the record's own returned graph (with
+        `standardize` the parent fragment's); `scaffold.of_records` writes them onto records without a selection.
         `exclude_graphs=`: an iterable of `GeneratedMolecule` records, Mols or (atomic_numbers, bond_orders) pairs
         (`fingerprint.mol_graph`: their heavy atoms).  They are read with the other arguments and labelled by the same
         kernel directly in front of the generation, behind every refusal of the call, and a generated molecule whose
@@ -900,8 +920,8 @@ class MLConformerGenerator(torch.nn.Module):
         `load_reference_charges` refuses or that no option reads, min_electrostatic_tanimoto outside [-1, 1], and add_hydrogens that is not a bool or on
         a generator with a finisher, RDKit's or a custom one (on Mols use `Chem.AddHs(mol, addCoords=True)`), and standardize
         that is not a bool or on a generator with a finisher (RDKit's finisher runs `standardize_mol` itself), smiles that
-        is neither a bool nor "isomeric" or on a generator with a finisher, a unique other than True, False, "exact" or
-        "stereo" ("stereo" on a generator with a finisher), and an
+        is neither a bool nor "isomeric" or on a generator with a finisher, a unique other than True, False, "exact",
+        "stereo", "scaffold" or "framework" ("stereo" on a generator with a finisher), and an
         `exclude_graphs` entry that is unreadable, has more than 64 heavy atoms or has no canonical order (the message
         names its position), a substructure option that is no iterable of patterns or holds an entry that cannot be read
         or has more than 32 query atoms (the message names the list, the position and, for a string, the character), and a
@@ -974,7 +994,8 @@ class MLConformerGenerator(torch.nn.Module):
         `max_pairwise_chemical_tanimoto`, `reference_shape`, `shape_density`, `max_atoms_outside`, `relax_geometry`,
         `pharmacophore_scores`, `reference_pharmacophore`, `min_pharmacophore_tanimoto`, `rank_by`, `relieve_clashes`,
         `electrostatic_scores`, `reference_charges`, `min_electrostatic_tanimoto`, `partial_charges` (behind the gather, on
-        the rows a rank returns, like the hydrogens), `smiles`, `unique="exact"`, `exclude_graphs` (labelled behind the
+        the rows a rank returns, like the hydrogens), `smiles`, `unique="exact"`, `unique="scaffold"` / `"framework"` (perceived
+        behind the gather, on the rows a rank returns, like the canonical order), `exclude_graphs` (labelled behind the
         gather, on the rows a rank returns, beside the fingerprints; every rank labels the excluded graphs itself),
         `require_substructures`, `exclude_substructures`, `substructure_counts` (matched behind the gather, on the rows a
         rank returns; every rank compiles the patterns itself),

@@ -18,6 +18,7 @@
 #include "mcg_common.h"
 #include "mcg_api_internal.h"
 #include "mcg_graph_rules.h"
+#include "mcg_ring_bonds.h"
 
 namespace {
 
@@ -112,21 +113,8 @@ __global__ __launch_bounds__(SS_MAXW) void k_substructure_match(
     s.nbr[a] = mine;
     __syncthreads();
 
-    // ring bonds: (a, j) is one iff j is reached from a's other neighbours.  A round adds at least one atom: <= n rounds.
-    unsigned long long ring_nb = 0ull;
-    for (unsigned long long f = mine; f != 0ull; f &= f - 1ull) {
-        const int j = __ffsll((long long)f) - 1;
-        const unsigned long long target = 1ull << j;
-        unsigned long long reach = me, frontier = mine & ~target;
-        for (int it = 0; it < n && frontier != 0ull; ++it) {
-            reach |= frontier;
-            if ((reach & target) != 0ull) break;
-            unsigned long long next = 0ull;              // the frontier holds neither a nor j: the bond left out is not walked
-            for (unsigned long long g = frontier; g != 0ull; g &= g - 1ull) next |= s.nbr[__ffsll((long long)g) - 1];
-            frontier = next & ~reach;
-        }
-        ring_nb |= (reach & target) != 0ull ? target : 0ull;
-    }
+    // ring bonds: (a, j) is one iff j is reached from a's other neighbours (mcg_ring_bonds.h)
+    const unsigned long long ring_nb = mcg_ring_bonds_of(s.nbr, a, mine, n).mask;
     s.ring_nb[a] = ring_nb;
     const int deg = tally.deg;
     const bool arom = m4 != 0ull, ring = ring_nb != 0ull;

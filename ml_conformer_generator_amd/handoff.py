@@ -82,6 +82,16 @@ class Measured:
     stereo_descriptors: Optional[list] = None     # [the row of v as it comes, None -> per atom in record order on first read]
     n_stereo_defined: Optional[int] = None
     n_stereo_undefined: Optional[int] = None
+    n_rings: Optional[int] = None                 # `scaffold.py`: the cyclomatic number
+    n_ring_systems: Optional[int] = None
+    min_ring_size: Optional[int] = None
+    max_ring_size: Optional[int] = None
+    ring_sizes: Optional[object] = None           # List[int] per atom - or (batch [B,W] int32, row), sliced on first read
+    ring_systems: Optional[object] = None         # List[int] per atom - likewise
+    scaffold_atoms: Optional[List[int]] = None    # sorted indices into the record's atoms
+    scaffold_key: Optional[int] = None            # unsigned 64-bit; 0 for the empty scaffold and where the status is not 0
+    scaffold_status: Optional[int] = None         # `canonical.describe_status` of the scaffold graph; EMPTY = no scaffold
+    scaffold_smiles: Optional[str] = None         # "" for the empty scaffold
 
 
 _UNMEASURED = Measured()          # shared by every record that carries no values: never written to
@@ -119,8 +129,14 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
     three).
     The stereo identity of a call with `smiles="isomeric"` comes as `stereo_order` [n,W] int32, `stereo_status` [n],
     `stereo_descriptors` [n,W] int8 - `stereo.stereo_order`'s `stereo`: v in canonical position order, which a record
-    turns into its own order on first read -, `n_stereo_defined` [n] and `n_stereo_undefined` [n] (all five or none)."""
-    hyd = {k: values.get(k) for k in ("stereo_descriptors", "hydrogen_coords", "hydrogen_parents", "atom_map", "kekule_bond_orders",
+    turns into its own order on first read -, `n_stereo_defined` [n] and `n_stereo_undefined` [n] (all five or none).
+    The rings and the scaffold of a call with `unique="scaffold"` / `"framework"` come as `scaffold.record_fields` spells
+    them: `n_rings`, `n_ring_systems`, `min_ring_size`, `max_ring_size`, `scaffold_status` [n], `scaffold_key` [n] int64
+    holding the unsigned bit pattern, `ring_sizes` / `ring_systems` [n,W] int32 - a record's are left as (the one host
+    copy, row) and sliced to its atoms on first read -, `scaffold_atoms` [n,W] (-1 behind the kept atoms) and, where the
+    call also writes SMILES, `scaffold_smiles`, a host list of n strings (None: no canonical order)."""
+    hyd = {k: values.get(k) for k in ("ring_sizes", "ring_systems", "scaffold_atoms", "scaffold_smiles",
+                                      "stereo_descriptors", "hydrogen_coords", "hydrogen_parents", "atom_map", "kekule_bond_orders",
                                       "partial_charges", "hydrogen_charges", "canonical_order", "substructure_counts",
                                       "substructure_status", "substructure_first", "substructure_patterns",
                                       "interaction_atom_scores")}
@@ -184,6 +200,14 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
         cols["interaction_atom_scores"] = [(per_atom, b, k) for b, k in enumerate(counts)]
         for k in ("interaction_score", "interaction_terms", "receptor_hbonds", "interaction_atom_scores"):
             cols[k] = [None if gone else v for gone, v in zip(missing, cols[k])]
+    if hyd["scaffold_atoms"] is not None:
+        cols["scaffold_atoms"] = [[a for a in row if a >= 0] for row in hyd["scaffold_atoms"].cpu().tolist()]
+        for k in ("ring_sizes", "ring_systems"):
+            host = hyd[k].cpu().to(torch.int32)
+            cols[k] = [(host, b) for b in range(n)]
+        cols["scaffold_key"] = [k & 0xFFFFFFFFFFFFFFFF for k in cols["scaffold_key"]]
+        if hyd["scaffold_smiles"] is not None:
+            cols["scaffold_smiles"] = list(hyd["scaffold_smiles"])
     if "pose_trials_kept" in cols:
         missing = [c < 0 for c in cols["pose_trials_kept"]]
         for k in ("pose_trials_kept", "pose_optimisation_rmsd", "interaction_score_before"):
@@ -250,7 +274,11 @@ class GeneratedMolecule:
     `substructure_patterns` / `substructure_counts` / `substructure_status` / `substructure_first`: the patterns the call
     matched (`require_substructures`, `exclude_substructures`, `substructure_counts`, in that order) and, per pattern, how
     many embeddings this molecule has, how the search ended and the first embedding (`substructure.py`: the package's own
-    definition, NOT RDKit's substructure matcher), else None."""
+    definition, NOT RDKit's substructure matcher), else None.
+    `n_rings` / `n_ring_systems` / `min_ring_size` / `max_ring_size` / `ring_sizes` / `ring_systems` / `scaffold_atoms` /
+    `scaffold_key` / `scaffold_status` / `scaffold_smiles`: its rings and its scaffold when the call asked for
+    `unique="scaffold"` or `"framework"` (`scaffold.py`: the package's own definitions, NOT RDKit's ring perception or
+    MurckoScaffold), else None; `scaffold.of_records` writes them onto records after the fact."""
     __slots__ = ("_z", "_coords", "_bonds", "valid", "_batch", "_b", "_sid", "_measured", "_smiles", "_unmarked")
 
     def __init__(self, atomic_numbers: List[int], coords: torch.Tensor, bond_orders: torch.Tensor, valid: bool = True,
@@ -328,6 +356,72 @@ class GeneratedMolecule:
         pattern's own atom order) lands on - for highlighting; None where the pattern was not found."""
         substructure_row(self._measured)
         return self._measured.substructure_first
+
+    @property
+    def n_rings(self) -> Optional[int]:
+        """Ring bonds - ring atoms + ring systems of the molecular graph, the cyclomatic number (`scaffold.py`: the
+        package's own definition, no SSSR): cubane 5, naphthalene 2.  When the call asked for `unique="scaffold"` /
+        `"framework"` (or `scaffold.of_records` annotated the record); None otherwise."""
+        return self._measured.n_rings
+
+    @property
+    def n_ring_systems(self) -> Optional[int]:
+        """The connected components of the ring-bond sub-graph: fused, bridged and spiro rings are one system."""
+        return self._measured.n_ring_systems
+
+    @property
+    def min_ring_size(self) -> Optional[int]:
+        """The smallest cycle through any ring bond; 0 for an acyclic molecule."""
+        return self._measured.min_ring_size
+
+    @property
+    def max_ring_size(self) -> Optional[int]:
+        """The largest, over the ring bonds, of the smallest cycle through each - the largest ring one cannot avoid (a
+        14-membered macrocycle 14, bicyclo[2.2.2]octane 6); 0 for an acyclic molecule."""
+        return self._measured.max_ring_size
+
+    def _per_atom(self, name: str) -> Optional[List[int]]:
+        v = getattr(self._measured, name)
+        if isinstance(v, tuple):
+            v = v[0][v[1], : len(self.atomic_numbers)].tolist()
+            setattr(self._measured, name, v)
+        return v
+
+    @property
+    def ring_sizes(self) -> Optional[List[int]]:
+        """Per atom the smallest cycle through one of its ring bonds, 0 for a non-ring atom (sliced from the batch's host
+        tensor on first access)."""
+        return self._per_atom("ring_sizes")
+
+    @property
+    def ring_systems(self) -> Optional[List[int]]:
+        """Per atom the label of its ring system - the lowest atom index in it -, -1 for a non-ring atom."""
+        return self._per_atom("ring_systems")
+
+    @property
+    def scaffold_atoms(self) -> Optional[List[int]]:
+        """The atoms of this record, ascending, that form its scaffold - ring, linker and doubly bonded exo atoms
+        (`scaffold.py`: the package's OWN definition, NOT RDKit's MurckoScaffold); with `unique="framework"` the ring and
+        linker atoms.  Empty for an acyclic molecule."""
+        return self._measured.scaffold_atoms
+
+    @property
+    def scaffold_key(self) -> Optional[int]:
+        """64 bits of the scaffold graph's canonical certificate (`canonical.py`), for grouping: equal scaffolds have equal
+        keys; 0 for the empty scaffold and where `scaffold_status` says the graph has no canonical order."""
+        return self._measured.scaffold_key
+
+    @property
+    def scaffold_status(self) -> Optional[int]:
+        """The status word of the scaffold graph's canonical labelling (`canonical.describe_status`): 0, EMPTY for an
+        acyclic molecule, or DEGREE / BUDGET - such a scaffold is not proven equal to anything and always stays."""
+        return self._measured.scaffold_status
+
+    @property
+    def scaffold_smiles(self) -> Optional[str]:
+        """The canonical SMILES of the scaffold graph (`smiles.write_smiles` in its canonical order), "" for the empty
+        scaffold, where the call also asked for `smiles`; None otherwise and where there is no canonical order."""
+        return self._measured.scaffold_smiles
 
     @property
     def canonical_status(self) -> Optional[int]:
@@ -915,7 +1009,13 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                            stereo_order: Optional[torch.Tensor] = None, stereo_status: Optional[torch.Tensor] = None,
                            stereo_descriptors: Optional[torch.Tensor] = None,
                            n_stereo_defined: Optional[torch.Tensor] = None,
-                           n_stereo_undefined: Optional[torch.Tensor] = None) -> List[GeneratedMolecule]:
+                           n_stereo_undefined: Optional[torch.Tensor] = None,
+                           n_rings: Optional[torch.Tensor] = None, n_ring_systems: Optional[torch.Tensor] = None,
+                           min_ring_size: Optional[torch.Tensor] = None, max_ring_size: Optional[torch.Tensor] = None,
+                           ring_sizes: Optional[torch.Tensor] = None, ring_systems: Optional[torch.Tensor] = None,
+                           scaffold_atoms: Optional[torch.Tensor] = None, scaffold_key: Optional[torch.Tensor] = None,
+                           scaffold_status: Optional[torch.Tensor] = None,
+                           scaffold_smiles: Optional[List[Optional[str]]] = None) -> List[GeneratedMolecule]:
     """Host pass over (already gathered) result tensors: ONE D2H copy per tensor, then one lazy record per molecule
     (no per-molecule slicing or cloning here: `GeneratedMolecule._view`).  `sample_ids[b]`: the sample id of row b
     (default: b, the row IS the sample index).  `shape_tanimoto[b]`: row b's shape score (None: unscored records).
@@ -954,6 +1054,9 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     `n_stereo_undefined[b]`: row b's stereo identity as `stereo.stereo_order` returns it - `stereo_descriptors` is its
     `stereo`, v in canonical position order; the counts are defined tetrahedral + defined double bonds, and the undefined
     candidates (all five or none; None: a call without `smiles="isomeric"`).
+    `n_rings[b]` ... `scaffold_status[b]` and the host list `scaffold_smiles`: row b's rings and scaffold as
+    `scaffold.record_fields` spells them (all nine, the strings only with `smiles`; None: a call without
+    `unique="scaffold"` / `"framework"`).
     The value keywords are the fields of `Measured`
     and go to `measured_from_tensors`; a call with no ids and no values builds the views and nothing else."""
     batch = _HostBatch(x.cpu(), elements.cpu(), bond_sym.cpu(), n_nodes.cpu().tolist())
@@ -977,7 +1080,10 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                   interaction_score_before=interaction_score_before, pose_optimisation_rmsd=pose_optimisation_rmsd,
                   pose_trials_kept=pose_trials_kept, stereo_order=stereo_order, stereo_status=stereo_status,
                   stereo_descriptors=stereo_descriptors, n_stereo_defined=n_stereo_defined,
-                  n_stereo_undefined=n_stereo_undefined)
+                  n_stereo_undefined=n_stereo_undefined, n_rings=n_rings, n_ring_systems=n_ring_systems,
+                  min_ring_size=min_ring_size, max_ring_size=max_ring_size, ring_sizes=ring_sizes,
+                  ring_systems=ring_systems, scaffold_atoms=scaffold_atoms, scaffold_key=scaffold_key,
+                  scaffold_status=scaffold_status, scaffold_smiles=scaffold_smiles)
     if sample_ids is None and all(v is None for v in values.values()):
         return [view(batch, b, bool(v)) for b, v in enumerate(valid.cpu().tolist())]
     flags = valid.cpu().tolist()

@@ -24,7 +24,9 @@ Stages, in this order:
        `unique="exact"`, `exclude_graphs`): one `_canonical_order` launch over the rows - the excluded graphs were
        labelled by the same seam directly in front of the generation (`label_excluded`); and the stereo step
        (`stereo_identities`; `smiles="isomeric"`, `unique="stereo"`; records only): one `_stereo_order` launch over the
-       rows, on the returned coordinates and graphs; and the substructure step
+       rows, on the returned coordinates and graphs; and the scaffold step (`unique="scaffold"` / `"framework"`): one
+       `_ring_scaffolds` call over the rows - one launch of each entry of `scaffold.py` and one `_canonical_order` launch
+       on the sub-graphs -, on the returned graphs, no coordinates; and the substructure step
        (`substructures`; `require_substructures`, `exclude_substructures`, `substructure_counts`): one
        `_match_substructures` call over the rows, every pattern of the three lists in it; and the interaction step
        (`interactions`; `interaction_scores`, `max_interaction_score`, `rank_by="interaction"`; records only): one
@@ -45,7 +47,7 @@ that arrive are already the parent fragments'; its four per-sample tensors (`ato
 
 The device work goes through the generator's seams (`_pose`, `_score`, `_pair`, `_receptor_coords`, `_relieve`,
 `_optimise_pose`, `_score_placed`, `_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, `_pharm_perceive`,
-`_pharm_score`, `_add_hydrogens`, `_peoe_charges`, `_esp_score`, `_canonical_order`, `_stereo_order`,
+`_pharm_score`, `_add_hydrogens`, `_peoe_charges`, `_esp_score`, `_canonical_order`, `_stereo_order`, `_ring_scaffolds`,
 `_match_substructures`,
 `_interaction_scores`), looked up on the instance at the time of the call.  The shape seams take the request's reference
 object; which kind it is - a conformer or a solid - is `cheminformatics`' business."""
@@ -72,6 +74,7 @@ from . import hydrogens as mcg_hydrogens
 from . import interactions as mcg_interactions
 from . import pharmacophore as mcg_pharm
 from . import receptor as mcg_receptor
+from . import scaffold as mcg_scaffold
 from . import standardize as mcg_standardize
 from . import substructure as mcg_sub
 from .handoff import Measured, measured_from_tensors, molecules_from_tensors
@@ -116,7 +119,8 @@ class Request:
     excluded_graphs: Optional[tuple] = None       # `exclude_graphs` as read on the host: (atomic numbers, bond codes) each
     exclude: Optional[frozenset] = None           # their (key, identity bytes), once `label_excluded` has labelled them
     # `unique` above is False, True (one row per `graph_key`), "exact" (one row per exact identity) or "stereo" (one row
-    # per stereo identity, `stereo.stereo_identity_bytes`)
+    # per stereo identity, `stereo.stereo_identity_bytes`), "scaffold" or "framework" (one row per scaffold / generic
+    # framework identity, `scaffold.murcko_scaffolds`)
     substructures: Optional[object] = None        # `substructure.Compiled`: the patterns of `require_substructures`, then
     #                                               `exclude_substructures`, then `substructure_counts`, compiled together
     n_required: int = 0                           # how many of them must be proven present,
@@ -153,10 +157,15 @@ class Request:
         return self.smiles == "isomeric" or self.unique == "stereo"
 
     @property
+    def needs_scaffold(self) -> bool:
+        """Whether the call perceives rings and scaffolds (`unique="scaffold"`, `unique="framework"`)."""
+        return isinstance(self.unique, str) and self.unique in mcg_scaffold.UNIQUE_VALUES
+
+    @property
     def measures(self) -> bool:
         """Whether any option is on (a receptor needs the pose, a selection implies its score)."""
         return (self.overlay or self.scores_shape or self.needs_fingerprints or self.needs_canonical
-                or self.needs_stereo or self.substructures is not None)
+                or self.needs_stereo or self.needs_scaffold or self.substructures is not None)
 
     @property
     def removes(self) -> bool:
@@ -230,7 +239,7 @@ def parse_request(gen, reference_conformer, *, reference_context=None, shape_sco
     fields.update(_electrostatic_fields(o, esp, scores_shape, conformer))
     fields.update(_pharmacophore_fields(o, scores_shape, conformer))
     _args.check_flag("chemical_scores", chemical_scores)
-    if not (isinstance(unique, str) and unique in ("exact", "stereo")):
+    if not (isinstance(unique, str) and unique in ("exact", "stereo") + mcg_scaffold.UNIQUE_VALUES):
         _args.check_flag("unique", unique)
     if isinstance(unique, str) and unique == "stereo" and finisher is not None:
         raise ValueError(mcg_stereo.REFUSAL_UNIQUE_WITH_FINISHER)
@@ -498,7 +507,8 @@ def _substructure_fields(o, custom_finisher) -> dict:
 def _chemistry_fields(o, custom_finisher, excluded, graph_read: bool) -> dict:
     """The chemical options: `max_chemical_tanimoto` implies the chemical score, which needs the reference's graph
     (`_reference_graph`).  `unique`: False, True or "exact" - one row per exact identity (`canonical.identity_bytes`)
-    instead of per `graph_key`; it reads the Mols' own graphs through RDKit's finisher and is refused with a custom one.
+    instead of per `graph_key` -, "scaffold" or "framework" - one row per scaffold / generic framework
+    (`scaffold.murcko_scaffolds`); these read the Mols' own graphs through RDKit's finisher and are refused with a custom one.
     `excluded`: the graphs of `exclude_graphs` as `read_excluded` read them.  `graph_read`: whether the pharmacophore or
     the electrostatic family already reads `reference_graph` - one that no option reads is refused."""
     if o.max_chemical_tanimoto is not None:
@@ -637,6 +647,8 @@ class Rows:
     exact: Optional[List[Optional[tuple]]] = None     # `identities` per row, where the call compares exact identities
     sub: Optional[List[tuple]] = None                 # `substructures` per row, where the call matches patterns
     stereo: Optional[List[Optional[tuple]]] = None    # `stereo_identities` per row, with `unique="stereo"`
+    scaffold: Optional[List[Optional[tuple]]] = None  # `scaffold.murcko_scaffolds`' identity per row, with `unique="scaffold"`
+    #                                                   / `"framework"`
 
     def take(self, keep: List[int]) -> "Rows":
         """The rows at the positions `keep`, in that order."""
@@ -656,7 +668,9 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
     `exclude` keeps it, and one warning per call names how many such rows there were -,
     then `exclude_graphs` - the rows whose exact identity is one of the excluded graphs' (a row without a canonical order is
     not proven equal to anything and stays) -, then `unique` - of the rows with one graph key (`unique="exact"`: with one
-    exact identity, `select_exact`; `unique="stereo"`: with one stereo identity, the same walk) the first in ranking order
+    exact identity, `select_exact`; `unique="stereo"`: with one stereo identity, the same walk; `unique="scaffold"` /
+    `"framework"`: with one scaffold / framework identity, the same walk again - all acyclic rows share the empty scaffold,
+    and a row whose scaffold has no canonical order always stays) the first in ranking order
     (`cheminformatics.ranking_key` of `Request.ranking_score`: by shape score where the call scores shape - plus the
     pharmacophore score with `rank_by="combo"`, the electrostatic score with `rank_by="electrostatic"`; by minus the
     interaction score with `rank_by="interaction"` - else the lowest sample id), still in the
@@ -701,6 +715,8 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
             rows = rows.take(select_exact(rows.exact, order))
         elif req.unique == "stereo":                  # the same walk over (stereo_key, stereo identity bytes)
             rows = rows.take(select_exact(rows.stereo, order))
+        elif req.needs_scaffold:                      # ... and over (scaffold key, scaffold identity bytes)
+            rows = rows.take(select_exact(rows.scaffold, order))
         else:
             rows = rows.take(mcg_fp.select_unique([m.graph_key for m in rows.measured], order))
     if not req.selects_by_shape and req.max_pairwise_chemical_tanimoto is None:
@@ -971,6 +987,11 @@ def return_records(gen, req: Request, res: dict, row_ids: Optional[torch.Tensor]
             values.update(stereo_order=found["order"], stereo_status=found["status"], stereo_descriptors=found["stereo"],
                           n_stereo_defined=found["counts"][:, 0] + found["counts"][:, 1],
                           n_stereo_undefined=found["counts"][:, 2])
+    scaffolds = None
+    if req.needs_scaffold:                        # the returned graph alone: no coordinates
+        found = gen._ring_scaffolds(res["elements"], res["bond"], res["n_nodes"], req.unique == "framework")
+        scaffolds = found["identity"]
+        values.update(mcg_scaffold.record_fields(found, with_smiles=bool(req.smiles)))
     sub = None
     if req.substructures is not None:
         matched, sub = substructures(gen, req, res["elements"], res["bond"], res["n_nodes"])
@@ -1004,7 +1025,8 @@ def return_records(gen, req: Request, res: dict, row_ids: Optional[torch.Tensor]
     rows = Rows(kept, [m.sample_id for m in kept], [m._measured for m in kept], [m.batch_row for m in kept],
                 None if exact is None else [exact[m.batch_row] for m in kept],
                 None if sub is None else [sub[m.batch_row] for m in kept],
-                None if stereo is None or req.unique != "stereo" else [stereo[m.batch_row] for m in kept])
+                None if stereo is None or req.unique != "stereo" else [stereo[m.batch_row] for m in kept],
+                None if scaffolds is None else [scaffolds[m.batch_row] for m in kept])
 
     def shape_pair(left: Rows):
         x = res["x"]
@@ -1148,6 +1170,9 @@ def return_finished(gen, req: Request, samples: List[Finished], row_ids: Optiona
             m.chemical_tanimoto, m.graph_key = c.chemical_tanimoto, c.graph_key
     if req.needs_identity:                        # the live Mols' own graphs, like the fingerprints
         rows.exact = identities(gen, *mcg_fp.pad_graphs([mcg_fp.mol_graph(m) for m in rows.item]))[1] if live else []
+    if req.needs_scaffold:                        # likewise
+        rows.scaffold = gen._ring_scaffolds(*mcg_fp.pad_graphs([mcg_fp.mol_graph(m) for m in rows.item]),
+                                            req.unique == "framework")["identity"] if live else []
     if req.substructures is not None:             # likewise the live Mols' own graphs
         rows.sub = []
         if live:
