@@ -16,6 +16,13 @@
  * mcg_plan / mcg_gcn must not run on two host threads or two streams at once; different handles are independent,
  * mcg_egnn weights are read-only after creation (mcg_egnn_set_precision / mcg_egnn_set_option excepted) and may be
  * shared by several plans.  mcg_last_error() is thread-local.
+ * Streams: an entry with a `stream` argument puts all of its device work on that stream - or on internal non-blocking streams
+ * ordered behind it by events and joined back into it - and returns without waiting for it; none of it goes through, or waits
+ * for, the legacy default stream.  A plan's graph is captured on the plan's own stream and replayed on `stream`.  A handle
+ * remembers its last call by an event recorded on that call's stream: mcg_plan_destroy, mcg_gcn_check and a regrowth of the
+ * GCN workspace wait for that event, not for the device.  mcg_gcn_destroy waits for it before the workspace goes back to the
+ * pool, and then - like mcg_egnn_destroy - returns the weights to the driver, which waits for the whole device.  (The entries
+ * that block the host: INTEGRATION.md section 4.)
  */
 #ifndef MLCONFGEN_HIP_H
 #define MLCONFGEN_HIP_H
@@ -312,9 +319,12 @@ int mcg_gcn_create(const float* const* tensors_host, int n_tensors, mcg_gcn** ou
 void mcg_gcn_destroy(mcg_gcn* g);
 /* logits[B,42,42,5] = adj_mat_seer(elements[B,42] int64, dist_mat[B,42,42], adj_mat[B,42,42]);
  * bond[B,42,42] int8 = argmax over the 5 bond classes (the consumer's reduction, mol_utils.py:210).
- * Either output may be NULL. */
+ * Either output may be NULL.  The workspace is sized for the largest B seen, zero-filled on `stream`; a larger B first waits
+ * (on the host) for the handle's previous call, then takes new blocks from the library's device-memory pool. */
 int mcg_gcn_forward(mcg_gcn* g, const int64_t* elements, const float* dist_mat, const float* adj_mat, float* logits,
                     int8_t* bond, int B, void* stream);
+/* MCG_ERR_STATE if an element id outside [0, 36) was fed since creation (nn.Embedding would have raised), else MCG_OK.  Blocks
+ * the host until the handle's last mcg_gcn_forward has run, on whichever stream that was given, and reads the flag behind it. */
 int mcg_gcn_check(mcg_gcn* g);
 /* Debug hook: a copy-out of the GCN's workspace as the last mcg_gcn_forward left it, for the first B molecules of that
  * call: which = 0 L_dm[B,42,42] (normalised distance graph), 1 L_adj[B,42,42] (normalised bond graph), 2 the per-atom

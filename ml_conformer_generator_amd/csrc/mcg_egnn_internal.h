@@ -182,11 +182,6 @@ struct mcg_plan_mark_guard {              // marks at scope exit, whatever the r
     ~mcg_plan_mark_guard() { mcg_plan_mark(p, s); }
 };
 
-// device-memory pool of the plans (mcg_devmem.hip): blocks of destroyed plans are reused by new ones
-int mcg_dev_alloc(size_t bytes, void** out);
-void mcg_dev_free(void* p);
-void mcg_dev_trim();
-
 // small device-memory helpers shared by the model and plan builders
 int mcg_upload_f(const std::vector<float>& v, float** d);
 int mcg_upload_u16(const std::vector<uint16_t>& v, uint16_t** d);

@@ -210,7 +210,11 @@ struct mcg_gcn {
     float dm_b = 0.f;
     int* err = nullptr;
     std::vector<void*> allocs;
-    // workspace (grown on demand)
+    // "everything enqueued on this handle so far", recorded on the caller's stream behind every entry point that takes one
+    // (as mcg_plan::ev_done): mcg_gcn_check reads the flag behind it, a regrown or destroyed workspace is released behind it
+    hipEvent_t ev_done = nullptr;
+    bool ev_pending = false;
+    // workspace (grown on demand; blocks of the device-memory pool, mcg_devmem.hip)
     int cap = 0;
     float *L_dm = nullptr, *L_adj = nullptr, *xa = nullptr, *xb = nullptr, *e0 = nullptr, *emb44 = nullptr,
           *scale = nullptr, *res = nullptr;
@@ -218,19 +222,45 @@ struct mcg_gcn {
 };
 
 namespace {
-int ensure_ws(mcg_gcn* g, int B) {
+void gcn_mark(mcg_gcn* g, hipStream_t s) {
+    if (g->ev_done && hipEventRecord(g->ev_done, s) == hipSuccess) g->ev_pending = true;
+    else (void)hipGetLastError();
+}
+
+struct gcn_mark_guard {               // marks at scope exit, whatever the return path: some launches may be in flight
+    mcg_gcn* g; hipStream_t s;
+    ~gcn_mark_guard() { gcn_mark(g, s); }
+};
+
+// Blocks the host until the handle's last forward / peek has run, on whichever stream it went to.  A handle without an
+// event (its creation failed) waits for the whole device, as the blocking calls this replaces did.
+int gcn_wait(mcg_gcn* g) {
+    if (!g->ev_done) return hipDeviceSynchronize() == hipSuccess ? MCG_OK : MCG_ERR_HIP;
+    if (!g->ev_pending) return MCG_OK;
+    if (hipEventSynchronize(g->ev_done) != hipSuccess) { (void)hipGetLastError(); return MCG_ERR_HIP; }
+    g->ev_pending = false;
+    return MCG_OK;
+}
+
+// The workspace is zero-filled and used on `s` alone: nothing here goes through, or waits for, the legacy stream.  The old
+// blocks go back to the pool only behind the forward that may still read them (hipFree waited for the whole device).
+int ensure_ws(mcg_gcn* g, int B, hipStream_t s) {
     if (B <= g->cap) return MCG_OK;
     g->cap = 0;                       // a failed regrow must not leave the freed buffers looking usable
-    for (void* p : g->ws) (void)hipFree(p);
-    g->ws.clear();
+    if (!g->ws.empty()) {
+        if (int e = gcn_wait(g)) { mcg_set_error("mcg_gcn_forward: waiting for the previous call failed"); return e; }
+        for (void* p : g->ws) mcg_dev_free(p);
+        g->ws.clear();
+    }
     struct { float** p; size_t n; } bufs[] = {
         {&g->L_dm, (size_t)B * D * D}, {&g->L_adj, (size_t)B * D * D}, {&g->xa, (size_t)B * D * HID},
         {&g->xb, (size_t)B * D * HID}, {&g->e0, (size_t)B * D * EMB}, {&g->emb44, (size_t)B * DP},
         {&g->scale, (size_t)B * D * EMB}, {&g->res, (size_t)B * D * D * NB}};
     for (auto& b : bufs) {
-        MCG_HIP(hipMalloc((void**)b.p, b.n * sizeof(float)));
-        MCG_HIP(hipMemset(*b.p, 0, b.n * sizeof(float)));
-        g->ws.push_back(*b.p);
+        *b.p = nullptr;
+        if (int e = mcg_dev_alloc(b.n * sizeof(float), (void**)b.p)) return e;
+        g->ws.push_back(*b.p);          // owned from here on, also when the memset fails
+        MCG_HIP(hipMemsetAsync(*b.p, 0, b.n * sizeof(float), s));
     }
     g->cap = B;
     return MCG_OK;
@@ -276,7 +306,9 @@ static int gcn_build(mcg_gcn* g, const float* const* t) {
     g->dm_b = t[20][0];
     MCG_HIP(hipMalloc((void**)&g->err, sizeof(int)));
     g->allocs.push_back(g->err);
-    MCG_HIP(hipMemset(g->err, 0, sizeof(int)));
+    const int zero = 0;               // (a blocking copy: complete when it returns, whichever stream the first forward takes)
+    MCG_HIP(hipMemcpy(g->err, &zero, sizeof(int), hipMemcpyHostToDevice));
+    MCG_HIP(hipEventCreateWithFlags(&g->ev_done, hipEventDisableTiming));
     return MCG_OK;
 }
 
@@ -293,8 +325,10 @@ int mcg_gcn_create(const float* const* t, int n_tensors, mcg_gcn** out) {
 
 void mcg_gcn_destroy(mcg_gcn* g) {
     if (!g) return;
+    (void)gcn_wait(g);                // the workspace goes back to the pool: not under a forward that is still running
+    for (void* p : g->ws) mcg_dev_free(p);
     for (void* p : g->allocs) (void)hipFree(p);
-    for (void* p : g->ws) (void)hipFree(p);
+    if (g->ev_done) (void)hipEventDestroy(g->ev_done);
     delete g;
 }
 
@@ -306,7 +340,8 @@ int mcg_gcn_forward(mcg_gcn* g, const int64_t* elements, const float* dist_mat, 
         return MCG_ERR_ARG;
     }
     hipStream_t s = (hipStream_t)stream;
-    if (int e = ensure_ws(g, B)) return e;
+    gcn_mark_guard done{g, s};
+    if (int e = ensure_ws(g, B, s)) return e;
     const int M = B * D;
     // distance-graph branch (:115-125)
     hipLaunchKernelGGL(k_lnorm, dim3(B), dim3(64), 0, s, dist_mat, g->L_dm);
@@ -379,10 +414,12 @@ int mcg_handoff(const float* x, const float* h, const int32_t* n_nodes_dev, int 
                           stream);
 }
 
-// 1 if an out-of-range element id was seen since creation (nn.Embedding would have raised)
+// 1 if an out-of-range element id was seen since creation (nn.Embedding would have raised).  Blocks the host until the
+// handle's last forward has run - on whichever stream it was given - and reads the flag behind it.
 int mcg_gcn_check(mcg_gcn* g) {
     int h = 0;
     if (!g) return MCG_ERR_ARG;
+    if (gcn_wait(g) != MCG_OK) return MCG_ERR_HIP;
     if (hipMemcpy(&h, g->err, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return MCG_ERR_HIP;
     return h ? MCG_ERR_STATE : MCG_OK;
 }
@@ -396,6 +433,7 @@ int mcg_gcn_peek(const mcg_gcn* g, int which, int B, float* dst, void* stream) {
         return MCG_ERR_ARG;
     }
     hipStream_t s = (hipStream_t)stream;
+    gcn_mark_guard done{const_cast<mcg_gcn*>(g), s};      // the copy reads the workspace: a regrow or destroy waits for it
     const float* src = nullptr; size_t n = 0;
     switch (which) {
         case 0: src = g->L_dm; n = (size_t)B * D * D; break;

@@ -1014,7 +1014,9 @@ def return_records(gen, req: Request, res: dict, row_ids: Optional[torch.Tensor]
     if req.needs_charges:
         values.update(electrostatics(gen, req, res, placed, perceived))
     if gen.device.type == "cuda":
-        torch.cuda.synchronize(gen.device)        # (the D2H copies below would wait anyway: keep that out of the figure)
+        # (the D2H copies below would wait for the call's stream anyway: keep that out of the figure.  The call's stream only -
+        #  a device-wide synchronise would also wait for whatever the caller runs on other streams beside the generation.)
+        torch.cuda.current_stream(gen.device).synchronize()
     t0 = time.perf_counter()
     mols = molecules_from_tensors(res["x"], res["elements"], res["bond"], res["n_nodes"], res["valid"],
                                   sample_ids=row_ids, **values)
