@@ -98,6 +98,13 @@ SIGNATURES: Dict[str, tuple] = {
     "mcg_ifm_merge": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/mlconfgen_hip_flex.h one to one (a second public header: DESIGN.md section 6,
+# "Flexible pose")
+FLEX_SIGNATURES: Dict[str, tuple] = {
+    "mcg_torsion_tree": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mcg_receptor_optimise_flex": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _vp]),
+}
 
 
 class PlanOpts(C.Structure):
@@ -149,7 +156,7 @@ def lib():
             "or `make -C ml_conformer_generator_amd/csrc`. There is no CPU fallback for the hot path.")
     import torch  # noqa: F401  - loads the process's HIP runtime first (same SONAME as ours)
     handle = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(FLEX_SIGNATURES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

@@ -443,6 +443,13 @@ class MLConformerGenerator(torch.nn.Module):
         return mcg_interactions.optimise_pose(receptor, coords, n_nodes, atomic_numbers, bond_orders, steps,
                                               device=self.device)
 
+    def _optimise_pose_flex(self, receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_numbers: torch.Tensor,
+                            bond_orders: torch.Tensor, steps: int) -> dict:
+        """`_optimise_pose` with the rotatable bonds turned beside the rigid move and the intramolecular guard
+        (`interactions.optimise_pose_flexible`, device tensors)."""
+        return mcg_interactions.optimise_pose_flexible(receptor, coords, n_nodes, atomic_numbers, bond_orders, steps,
+                                                       device=self.device)
+
     # the standardisation step
     def _standardize(self, coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
                      n_nodes: torch.Tensor) -> dict:
@@ -887,6 +894,12 @@ class MLConformerGenerator(torch.nn.Module):
         and `overlay_tanimoto` the shape Tanimoto of the pose as placed; an unmoved molecule keeps every bit.  Records
         carry `interaction_score_before` (E of the pose the walk started from), `pose_optimisation_rmsd` (A the heavy
         atoms moved; 0.0 where nothing moved) and `pose_trials_kept`; None in a call without it and where posing failed.
+        `optimise_pose="flexible"` (64 trials) or `("flexible", n)`, n in 1..1024: the same stage, with up to 16 rotatable
+        bonds turned beside the rigid move and an intramolecular guard (`interactions.optimise_pose_flexible`; DESIGN.md
+        section 6, "Flexible pose" - the package's own procedure likewise).  `pose` stays the rigid part of the move: it
+        maps `x_relaxed` to the returned coordinates only up to `pose_conformer_rmsd`.  Records also carry `pose_torsions`,
+        `pose_torsion_angles`, `pose_conformer_rmsd`, `intramolecular_clash_before` and `intramolecular_clash`; None in
+        every other call.
         `max_interaction_score=t` (implies the score; t a finite real number): keep the molecules with E <= t; NaN and
         missing do not pass; right behind `min_electrostatic_tanimoto`.
         `rank_by="interaction"` (needs the score): `unique`, the diversity walk and `top_k` rank by -E;
@@ -902,8 +915,8 @@ class MLConformerGenerator(torch.nn.Module):
         overlay, refine_overlay other than True or an integer in 1..1024 or without overlay, a receptor without overlay,
         one `load_receptor` refuses or one that holds the reference (a reference heavy atom within 0.5 A of a receptor
         heavy atom), max_receptor_clashes other than an integer >= 0 or without a receptor, relieve_clashes other than
-        False, True or an integer in 1..1024 or without a receptor, optimise_pose other than False, True or an integer in
-        1..1024, without a receptor or on a generator with a finisher, a custom finisher, a
+        False, True or an integer in 1..1024 or without a receptor, optimise_pose other than False, True, an integer in
+        1..1024, "flexible" or ("flexible", n), without a receptor or on a generator with a finisher, a custom finisher, a
         `reference_shape` together with another reference, with `refine_overlay` or with a `receptor`, or without
         `n_atoms`, a mesh `load_mesh` refuses ("The mesh needs to be watertight."), a `shape_density` that is not a positive
         real number, max_atoms_outside other than an integer >= 0, without a `reference_shape` or without overlay, and

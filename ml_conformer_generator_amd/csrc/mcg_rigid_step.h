@@ -155,4 +155,16 @@ __device__ __forceinline__ void block_sums(float* acc, float (*red)[K], float* v
     for (int k = 0; k < K; ++k) v[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
 }
 
+// out[3] = the point (x, y, z) turned right-handed by theta about the line through (bx, by, bz) along the unit vector
+// (nx, ny, nz): the row-vector Rodrigues matrix applied to the difference to b, b added back.  For a walk that turns a part
+// of a molecule about one of its bonds (`k_receptor_optimise_flex`); b itself comes back with its own bits.
+__device__ __forceinline__ void turn_about_line(float x, float y, float z, float bx, float by, float bz, float nx, float ny,
+                                                float nz, float theta, float* out) {
+#pragma clang fp contract(off)
+    float D[9], o[3];
+    rodrigues_row(nx, ny, nz, theta, D);
+    mcg_shape::rotate_row(x - bx, y - by, z - bz, D, o);
+    out[0] = o[0] + bx; out[1] = o[1] + by; out[2] = o[2] + bz;
+}
+
 }  // namespace mcg_rigid

@@ -77,6 +77,11 @@ class Measured:
     interaction_score_before: Optional[float] = None  # E of the pose `optimise_pose` started from
     pose_optimisation_rmsd: Optional[float] = None
     pose_trials_kept: Optional[int] = None
+    pose_torsions: Optional[int] = None           # `optimise_pose="flexible"`: torsions the walk used (at most 16)
+    pose_torsion_angles: Optional[List[float]] = None   # rad, one per used torsion: the summed kept turns
+    pose_conformer_rmsd: Optional[float] = None   # A: the change of the conformer alone, the rigid part taken out
+    intramolecular_clash_before: Optional[float] = None     # CLASH of `interactions.optimise_pose_flexible` at the start
+    intramolecular_clash: Optional[float] = None  # ... and at the returned coordinates
     stereo_order: Optional[List[int]] = None      # the stereo search's atom order, -1 beyond the atoms as it comes
     stereo_status: Optional[int] = None           # `canonical.describe_status`; 0 = the stereo identity is defined
     stereo_descriptors: Optional[list] = None     # [the row of v as it comes, None -> per atom in record order on first read]
@@ -126,7 +131,9 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
     `interaction_atom_scores` is left as (the one host copy, row, atom count) and sliced on first read.
     The pose optimisation of a call with `optimise_pose` comes as `interaction_score_before` [n] fp32,
     `pose_optimisation_rmsd` [n] fp32 and `pose_trials_kept` [n] (negative: posing failed - the record gets None for all
-    three).
+    three).  `optimise_pose="flexible"` adds `pose_torsions` [n] int32, `pose_torsion_angles` [n,16] fp32 (a record keeps
+    the first `pose_torsions`), `pose_conformer_rmsd`, `intramolecular_clash_before` and `intramolecular_clash` [n] fp32
+    (all five or none; None on the same rows).
     The stereo identity of a call with `smiles="isomeric"` comes as `stereo_order` [n,W] int32, `stereo_status` [n],
     `stereo_descriptors` [n,W] int8 - `stereo.stereo_order`'s `stereo`: v in canonical position order, which a record
     turns into its own order on first read -, `n_stereo_defined` [n] and `n_stereo_undefined` [n] (all five or none).
@@ -210,7 +217,10 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
             cols["scaffold_smiles"] = list(hyd["scaffold_smiles"])
     if "pose_trials_kept" in cols:
         missing = [c < 0 for c in cols["pose_trials_kept"]]
-        for k in ("pose_trials_kept", "pose_optimisation_rmsd", "interaction_score_before"):
+        if "pose_torsions" in cols:             # a flexible walk: the angles of the torsions it used
+            cols["pose_torsion_angles"] = [row[: max(k, 0)] for row, k in zip(cols["pose_torsion_angles"], cols["pose_torsions"])]
+        for k in ("pose_trials_kept", "pose_optimisation_rmsd", "interaction_score_before", "pose_torsions",
+                  "pose_torsion_angles", "pose_conformer_rmsd", "intramolecular_clash_before", "intramolecular_clash"):
             if k in cols:
                 cols[k] = [None if gone else v for gone, v in zip(missing, cols[k])]
     return [Measured(**{k: col[b] for k, col in cols.items()}) for b in range(n)]
@@ -610,6 +620,36 @@ class GeneratedMolecule:
         return self._measured.pose_trials_kept
 
     @property
+    def pose_torsions(self) -> Optional[int]:
+        """The rotatable bonds the flexible pose optimisation used (`interactions.optimise_pose_flexible`: at most 16, in
+        ascending order of their ends); None in a call without `optimise_pose="flexible"`, and where posing failed."""
+        return self._measured.pose_torsions
+
+    @property
+    def pose_torsion_angles(self) -> Optional[List[float]]:
+        """Per used torsion the angle in rad the flexible pose optimisation turned its moving side by, right-handed about
+        the bond; None in a call without `optimise_pose="flexible"`, and where posing failed."""
+        return self._measured.pose_torsion_angles
+
+    @property
+    def pose_conformer_rmsd(self) -> Optional[float]:
+        """How far, as a heavy-atom RMSD in A, the flexible pose optimisation changed the conformer itself (the rigid part
+        of the move taken out): `pose` maps `x_relaxed` to the returned coordinates only up to this.  None in a call
+        without `optimise_pose="flexible"`, and where posing failed."""
+        return self._measured.pose_conformer_rmsd
+
+    @property
+    def intramolecular_clash_before(self) -> Optional[float]:
+        """CLASH, the intramolecular guard of `interactions.optimise_pose_flexible` (A^2), of the conformer the walk
+        started from; None in a call without `optimise_pose="flexible"`, and where posing failed."""
+        return self._measured.intramolecular_clash_before
+
+    @property
+    def intramolecular_clash(self) -> Optional[float]:
+        """CLASH of the returned coordinates; None in a call without `optimise_pose="flexible"`, and where posing failed."""
+        return self._measured.intramolecular_clash
+
+    @property
     def relief_rmsd(self) -> Optional[float]:
         """How far, as a heavy-atom RMSD in A, the clash relief moved this molecule as a rigid body out of its contacts
         with the call's receptor (`receptor.relieve_clashes`: the package's own procedure - not a docking score, not a
@@ -1006,6 +1046,11 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                            interaction_score_before: Optional[torch.Tensor] = None,
                            pose_optimisation_rmsd: Optional[torch.Tensor] = None,
                            pose_trials_kept: Optional[torch.Tensor] = None,
+                           pose_torsions: Optional[torch.Tensor] = None,
+                           pose_torsion_angles: Optional[torch.Tensor] = None,
+                           pose_conformer_rmsd: Optional[torch.Tensor] = None,
+                           intramolecular_clash_before: Optional[torch.Tensor] = None,
+                           intramolecular_clash: Optional[torch.Tensor] = None,
                            stereo_order: Optional[torch.Tensor] = None, stereo_status: Optional[torch.Tensor] = None,
                            stereo_descriptors: Optional[torch.Tensor] = None,
                            n_stereo_defined: Optional[torch.Tensor] = None,
@@ -1049,7 +1094,8 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     none; negative hbonds: its pose failed, the record gets None for all four; None: a call without `interaction_scores`).
     `interaction_score_before[b]` / `pose_optimisation_rmsd[b]` / `pose_trials_kept[b]`: row b's pose optimisation as
     `postprocess.optimise_rows` spells it (negative trials kept: its pose failed, the record gets None for all three;
-    None: a call without `optimise_pose`).
+    None: a call without `optimise_pose`).  `pose_torsions[b]` / `pose_torsion_angles[b]` [16] / `pose_conformer_rmsd[b]` /
+    `intramolecular_clash_before[b]` / `intramolecular_clash[b]`: what `optimise_pose="flexible"` adds (all five or none).
     `stereo_order[b]` [W] / `stereo_status[b]` / `stereo_descriptors[b]` [W] int8 / `n_stereo_defined[b]` /
     `n_stereo_undefined[b]`: row b's stereo identity as `stereo.stereo_order` returns it - `stereo_descriptors` is its
     `stereo`, v in canonical position order; the counts are defined tetrahedral + defined double bonds, and the undefined
@@ -1078,7 +1124,10 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                   interaction_score=interaction_score, interaction_terms=interaction_terms,
                   receptor_hbonds=receptor_hbonds, interaction_atom_scores=interaction_atom_scores,
                   interaction_score_before=interaction_score_before, pose_optimisation_rmsd=pose_optimisation_rmsd,
-                  pose_trials_kept=pose_trials_kept, stereo_order=stereo_order, stereo_status=stereo_status,
+                  pose_trials_kept=pose_trials_kept, pose_torsions=pose_torsions,
+                  pose_torsion_angles=pose_torsion_angles, pose_conformer_rmsd=pose_conformer_rmsd,
+                  intramolecular_clash_before=intramolecular_clash_before, intramolecular_clash=intramolecular_clash,
+                  stereo_order=stereo_order, stereo_status=stereo_status,
                   stereo_descriptors=stereo_descriptors, n_stereo_defined=n_stereo_defined,
                   n_stereo_undefined=n_stereo_undefined, n_rings=n_rings, n_ring_systems=n_ring_systems,
                   min_ring_size=min_ring_size, max_ring_size=max_ring_size, ring_sizes=ring_sizes,

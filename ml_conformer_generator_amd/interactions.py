@@ -45,6 +45,7 @@ from typing import Dict, NamedTuple, Optional
 import torch
 
 from . import _args, _lib
+from . import config as _config
 from . import pharmacophore as mcg_pharm
 from . import receptor as mcg_receptor
 from . import substructure as mcg_sub
@@ -289,7 +290,8 @@ def optimise_pose(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_
     lower: one perceive launch (`ligand_types`) and one `mcg_receptor_optimise` launch (`optimise_typed`).
 
     THE PACKAGE'S OWN PROCEDURE ("Optimised pose"): NOT a docking run and NOT AutoDock Vina's local
-    optimisation.  Rigid body only: no torsions, no intramolecular term, no hydrogens, no global search.
+    optimisation.  Rigid body only: no torsions, no intramolecular term, no hydrogens, no global search
+    (`optimise_pose_flexible` is this walk with the rotatable bonds turned and an intramolecular guard).
 
     Objective       W = -0.0356 G1 - 0.00516 G2 + 0.840 REP - 0.0351 HYD - 0.587 HB, the weighted sum of this module's
                     five terms (`terms[:, 5]` of `interaction_scores`).  E = W / (1 + 0.0585 n_rot) divides by a positive
@@ -335,6 +337,166 @@ def optimise_pose(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_
     res = dict(coords=out["coords"], rotation=xform[:, :9].reshape(B, 3, 3), translation=xform[:, 9:],
                moved=ok & (stats[:, 3] > 0), weighted_before=stats[:, 0], weighted_after=stats[:, 1], trials=count(2),
                kept=count(3), rmsd=stats[:, 4], gradient=out["gradient"])
+    if trace:
+        res["trace"] = out["trace"]
+    return res
+
+
+# ----------------------------------------------------------------------------------------------- flexible pose
+FLEX_MAX_TORSIONS = 16          # include/mlconfgen_hip_flex.h MCG_FLEX_MAX_TORSIONS
+FLEX_TRACE_WIDTH = 43           # the rigid trace's 24 columns, s_tau, tau[16], C, C'
+FLEX_STEP_TAU = 0.1             # rad: what the torsion with the largest |tau| turns by in the first trial
+FLEX_MARGIN = 2.0               # angstrom an atom may leave the input's radius about p by
+CLASH_PAD = 0.45                # angstrom: half the 0.9 A of `geometry.py`'s non-bonded d0
+FLEXIBLE = "flexible"           # the value of `optimise_pose` that asks for this walk
+
+_CLASH_TABLE = torch.tensor([_config.ELEMENTS.get(z, _config.ELEMENTS[6])[1] + CLASH_PAD
+                             for z in range(len(mcg_receptor._SYMBOLS) + 1)], dtype=torch.float32)
+
+
+def clash_radii(atomic_numbers: torch.Tensor) -> torch.Tensor:
+    """fp32 c_i of the intramolecular guard for a tensor of atomic numbers (same shape, on its device): the covalent
+    radius `rcov` of `config.ELEMENTS` + 0.45 A; an element without a row there gets carbon's."""
+    z = torch.as_tensor(atomic_numbers).to(torch.long)
+    z = torch.where((z >= 1) & (z < _CLASH_TABLE.numel()), z, torch.full_like(z, 6))
+    return _CLASH_TABLE.to(z.device)[z]
+
+
+@torch.no_grad()
+def torsion_tree(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_nodes: torch.Tensor, device=None,
+                 check: bool = True) -> Dict[str, torch.Tensor]:
+    """The torsion tree of B heavy-atom graphs (`atomic_numbers` [B, >= W], `bond_orders` [B,W,W] symmetric codes
+    0 / 1 / 2 / 3 / 4, `n_nodes` [B]; W <= 64) by the rules of `optimise_pose_flexible`, one `mcg_torsion_tree` launch per
+    16 384 rows.  Device tensors, exact - the same bits in any batch, at any row and at any padded width:
+      torsion_atoms [B,16,2]  int32: per torsion (a, b), b the end inside the moving side; -1 in unused slots
+      side_mask [B,16]        int64 holding the unsigned bit pattern: bit i set iff atom i is in the moving side
+      near_mask [B,W]         int64 bit patterns: i itself, its bonded neighbours, every atom sharing a neighbour with i
+      counts [B,2]            int32: torsions found, torsions used (at most 16)
+    A width of 0 is taken as 1.  ValueError before the kernel as `scaffold.ring_perception` raises them."""
+    z, bonds, B, W = _args.graph_arguments(atomic_numbers, bond_orders, n_nodes, MAX_ATOMS,
+                                           f"the torsion tree takes molecules of at most {MAX_ATOMS} atoms")
+    dev = _args.resolve_device(device, bonds)
+    if W == 0:
+        z, bonds, W = torch.zeros(B, 1, dtype=torch.int32), torch.zeros(B, 1, 1, dtype=torch.int8), 1
+    zd, bd, nn = _args.device_graph(z, bonds, n_nodes, B, W, dev)
+    if check and B:
+        _args.check_graphs(zd, bd, nn, W)
+    out = dict(torsion_atoms=torch.full((B, FLEX_MAX_TORSIONS, 2), -1, dtype=torch.int32, device=dev),
+               side_mask=torch.zeros(B, FLEX_MAX_TORSIONS, dtype=torch.int64, device=dev),
+               near_mask=torch.zeros(B, W, dtype=torch.int64, device=dev),
+               counts=torch.zeros(B, 2, dtype=torch.int32, device=dev))
+    for lo in range(0, B, MAX_BATCH):
+        hi = min(B, lo + MAX_BATCH)
+        _lib.check(_lib.lib().mcg_torsion_tree(
+            _lib.dptr(zd[lo:hi]), _lib.dptr(bd[lo:hi]), _lib.dptr(nn[lo:hi]), hi - lo, W,
+            _lib.dptr(out["torsion_atoms"][lo:hi]), _lib.dptr(out["side_mask"][lo:hi]), _lib.dptr(out["near_mask"][lo:hi]),
+            _lib.dptr(out["counts"][lo:hi]), _lib.current_stream_ptr(dev)), "mcg_torsion_tree")
+    return out
+
+
+def _optimise_flex_typed(prepared, coords, n_nodes, B, N, radii, types, clash, tree, steps, max_shift, skip_tiles, dev,
+                         trace) -> Dict[str, torch.Tensor]:
+    """The `mcg_receptor_optimise_flex` launch behind its checks: device tensors as the kernel writes them
+    (include/mlconfgen_hip_flex.h).  B or N of 0 launches nothing and returns the rows as they came."""
+    x = coords.to(dev, torch.float32).contiguous()
+    out = torch.empty_like(x) if B > 0 and N > 0 else x.clone()
+    xform = torch.zeros(B, 12, device=dev)
+    stats = torch.zeros(B, 12, device=dev)
+    angles = torch.zeros(B, FLEX_MAX_TORSIONS, device=dev)
+    gradient = torch.zeros(B, 6 + FLEX_MAX_TORSIONS, device=dev)
+    tr = torch.zeros(B, steps, FLEX_TRACE_WIDTH, device=dev) if trace else None
+    if B > 0 and N > 0:
+        lig_r = radii.to(dev, torch.float32).contiguous()
+        lig_t = types.to(dev, torch.uint8).contiguous()
+        cl = clash.to(dev, torch.float32).contiguous()
+        nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B).contiguous()
+        rec, rec_t = prepared.xyzr.to(dev), prepared.types.to(dev)
+        spheres = prepared.spheres.to(dev) if skip_tiles else None
+        used = tree["counts"][:, 1].contiguous()
+        _lib.check(_lib.lib().mcg_receptor_optimise_flex(
+            _lib.dptr(x), _lib.dptr(lig_r), _lib.dptr(lig_t), _lib.dptr(nn), B, N, _lib.dptr(rec), _lib.dptr(rec_t),
+            int(rec.shape[0]), _lib.dptr(spheres), steps, max_shift, _lib.dptr(cl), _lib.dptr(tree["torsion_atoms"]),
+            _lib.dptr(tree["side_mask"]), _lib.dptr(tree["near_mask"]), _lib.dptr(used), _lib.dptr(out), _lib.dptr(xform),
+            _lib.dptr(stats), _lib.dptr(angles), _lib.dptr(gradient), _lib.dptr(tr), _lib.current_stream_ptr(dev)),
+            "mcg_receptor_optimise_flex")
+    else:
+        xform[:, 0] = xform[:, 4] = xform[:, 8] = 1.0
+    res = dict(coords=out, xform=xform, stats=stats, angles=angles, gradient=gradient)
+    if trace:
+        res["trace"] = tr
+    return res
+
+
+@torch.no_grad()
+def optimise_pose_flexible(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_numbers: torch.Tensor,
+                           bond_orders: torch.Tensor, steps: int = OPTIMISE_STEPS, max_shift: float = OPTIMISE_MAX_SHIFT,
+                           device=None, trace: bool = False, skip_tiles: bool = True) -> Dict[str, torch.Tensor]:
+    """`optimise_pose` with the molecule's rotatable bonds turned beside the rigid move: one perceive launch
+    (`ligand_types`), one `mcg_torsion_tree` launch (`torsion_tree`) and one `mcg_receptor_optimise_flex` launch.
+
+    THE PACKAGE'S OWN PROCEDURE (DESIGN.md section 6, "Flexible pose"): NOT a docking run, NOT AutoDock Vina's optimiser;
+    no hydrogens, no global search.  It works on the returned heavy-atom graph (symmetric codes 0 / 1 / 2 / 3 / 4, at most
+    64 atoms).
+
+    Torsions        a torsion is a bond `ROTATABLE_BOND` matches - code 1, not a ring bond, both ends of heavy degree >= 2 -
+                    unless it joins a nitrogen to a carbon that has a code-2 bond to N, O or S (amide, urea, carbamate;
+                    `n_rot` and the score's divisor do not change).  Leaving the bond out splits its connected component
+                    in two; the MOVING side is the part with fewer atoms, on a tie the part that holds the bond's
+                    higher-indexed end; b is the bond's end inside the moving side, a the other end; atoms of other
+                    components never move.  Torsions are taken in ascending (min(a, b), max(a, b)) order; at most 16 are
+                    used, the number found is reported and the rest stay frozen.
+    Near mask       near[i] = i itself, its bonded neighbours and every atom that shares a bonded neighbour with i.
+    Guard           CLASH = sum over real pairs i < j with j not in near[i] of max(0, (c_i + c_j) - r_ij)^2, c = `rcov`
+                    (`config.ELEMENTS`) + 0.45 A (`clash_radii`), weighted by the score's own REP weight 0.840, evaluated
+                    from the molecule-frame coordinates q: while no torsion turns, its bits do not change.
+    State           (q, G, p) from q_i = x_i - c, G = I, p = c; world coordinates x_i = q_i @ G + p, formed as
+                    `optimise_pose` forms them.
+    Evaluation      the five term sums, the net force F and the torque about p exactly as `optimise_pose` forms them,
+                    CLASH, and per torsion k the generalised force tau_k = n_k . sum_{i in side_k} (x_i - x_b) x f_i, n_k
+                    the unit vector from a to b, f_i the receptor force on atom i plus its clash force -0.840 dCLASH/dx_i.
+                    Positive tau_k: W + 0.840 CLASH falls as the side turns right-handed about n_k.
+    Trial           turns the torsions, in ascending k, on a copy of q: torsion k by delta_k = s_tau tau_k / max_j |tau_j|
+                    about the line through the copy's q_b along its current axis (a delta of 0 leaves the bits); then
+                    rotates by s_r about the torque and moves p by s_t along F, as `optimise_pose` does.  A zero or
+                    non-finite vector skips its part; the walk ends when all three parts are skipped.
+    Step lengths    from s_r = 0.05 rad, s_t = 0.25 A, s_tau = 0.1 rad; all three x 1.2 after a kept trial, x 0.5 after a
+                    rejected one.  Ends after `steps` trials or once s_t < 2^-8 A.
+    Unevaluated     a trial with |p' - c| > `max_shift` or any |q'_i| > rho0 + 2 A (rho0 the input's largest |x_i - c|) is
+                    rejected unevaluated; the tile list is built once with the reach (rho0 + 2 + 8) + `max_shift`.
+    Acceptance      kept iff (W' - W) + 0.840f (C' - C) < 0 in fp32, in that order; NaN is never kept.
+    Consequence     a molecule without a torsion walks exactly as `optimise_pose` walks it: the same bits in coords,
+                    transform, W before / after, trials, kept, rmsd and gradient.
+
+    Returns what `optimise_pose` returns (`rotation`, `translation`: the rigid part (G, p) alone - it maps the input to
+    `coords` only up to `conformer_rmsd`; `gradient` [B,22]: F, torque, tau at the input; `trace` [B,steps,43]) and
+      torsions [B]          int32: torsions used (`torsions_found` [B]: found); -1 on a row that got NaN
+      torsion_angles [B,16] fp32: the summed kept delta_k, rad
+      torsion_atoms [B,16,2] int32: the (a, b) of each slot, -1 where unused
+      clash_before, clash_after [B]   CLASH at the input and at `coords`
+      conformer_rmsd [B]    RMSD of q at the end against q at the start: the change of the conformer alone
+    Rows without atoms or with a non-finite coordinate behave as in `optimise_pose`.  Refused before any device work: what
+    `optimise_pose` refuses."""
+    prepared = prepare_receptor(receptor)
+    steps = mcg_receptor.check_relief_steps(steps)
+    max_shift = check_max_shift(max_shift)
+    dev = _args.resolve_device(device, coords)
+    B, N, z, bonds = _posed_graphs(coords, n_nodes, atomic_numbers, bond_orders, "pose optimisation takes")
+    types = torch.zeros(B, N, dtype=torch.uint8, device=dev)
+    tree = dict(torsion_atoms=torch.full((B, FLEX_MAX_TORSIONS, 2), -1, dtype=torch.int32, device=dev),
+                counts=torch.zeros(B, 2, dtype=torch.int32, device=dev))
+    if B > 0 and N > 0:
+        types = ligand_types(z[:, :N], bonds[:, :N, :N], n_nodes, dev)
+        tree = torsion_tree(z[:, :N], bonds[:, :N, :N], n_nodes, dev, check=False)
+    out = _optimise_flex_typed(prepared, coords, n_nodes, B, N, interaction_radii(z[:, :N].to(dev)), types,
+                               clash_radii(z[:, :N].to(dev)), tree, steps, max_shift, skip_tiles, dev, trace)
+    stats, xform = out["stats"], out["xform"]
+    ok = torch.isfinite(stats[:, 0])
+    count = lambda col: torch.where(ok, stats[:, col], torch.full_like(stats[:, col], -1.0)).to(torch.int32)
+    res = dict(coords=out["coords"], rotation=xform[:, :9].reshape(B, 3, 3), translation=xform[:, 9:],
+               moved=ok & (stats[:, 3] > 0), weighted_before=stats[:, 0], weighted_after=stats[:, 1], trials=count(2),
+               kept=count(3), rmsd=stats[:, 4], gradient=out["gradient"], torsions=count(8),
+               torsions_found=tree["counts"][:, 0], torsion_angles=out["angles"], torsion_atoms=tree["torsion_atoms"],
+               clash_before=stats[:, 6], clash_after=stats[:, 7], conformer_rmsd=stats[:, 9], step_trans=stats[:, 5])
     if trace:
         res["trace"] = out["trace"]
     return res

@@ -129,6 +129,7 @@ class Request:
     typed_receptor: Optional[tuple] = None        # `interactions.PreparedReceptor`: typed, sorted, with tile spheres, host
     max_interaction_score: Optional[float] = None
     optimise_steps: int = 0                       # `optimise_pose`: trials of the pose optimisation, 0 = not optimised
+    optimise_flexible: bool = False               # `optimise_pose="flexible"` / `("flexible", n)`: torsions turn too
 
     @property
     def selects_by_shape(self) -> bool:
@@ -221,7 +222,7 @@ def parse_request(gen, reference_conformer, *, reference_context=None, shape_sco
     custom_finisher = isinstance(finisher, host_pool.TaskRef)
     fields = _record_flags(o, finisher)
     esp = _electrostatic_flags(o, finisher)
-    interact, optimise_steps = _interaction_flags(o, finisher)
+    interact, optimise_steps, flexible = _interaction_flags(o, finisher)
     fields.update(partial_charges=partial_charges, relax_steps=mcg_geometry.check_steps(relax_geometry))
     fields.update(_mesh_reference(o))
     solid = fields["reference"]
@@ -230,7 +231,7 @@ def parse_request(gen, reference_conformer, *, reference_context=None, shape_sco
     if shape:                                     # the call scores shape or poses: the receptor's options are its fields
         fields.update(shape, **relief)
         if receptor is not None:                  # refused with a mesh above: the reference is a conformer
-            fields.update(_receptor_fields(o, fields["reference"], interact, optimise_steps))
+            fields.update(_receptor_fields(o, fields["reference"], interact, optimise_steps, flexible))
     scores_shape = fields.get("scores_shape")
     _args.check_flag("pharmacophore_scores", pharmacophore_scores)
     if min_pharmacophore_tanimoto is not None:
@@ -295,18 +296,30 @@ def _electrostatic_flags(o, finisher) -> bool:
 
 
 def _interaction_flags(o, finisher):
-    """(whether the call scores interactions, the trials of `optimise_pose`).  `interaction_scores` (implied by
-    `max_interaction_score`, a finite real number) needs a `receptor` - and with it `overlay`.  `rank_by="interaction"`
+    """(whether the call scores interactions, the trials of `optimise_pose`, whether its walk is the flexible one).
+    `interaction_scores` (implied by `max_interaction_score`, a finite real number) needs a `receptor` - and with it
+    `overlay`.  `rank_by="interaction"`
     needs the score.  Refused with a finisher: the values go onto the records.  `optimise_pose`:
     `receptor.check_relief_steps` (True = `interactions.OPTIMISE_STEPS`); it needs a `receptor`, and with it `overlay`,
-    implies `interaction_scores` and is refused with a finisher likewise."""
+    implies `interaction_scores` and is refused with a finisher likewise.  `optimise_pose="flexible"` (64 trials) and
+    `optimise_pose=("flexible", n)`, n in 1..1024, ask for `interactions.optimise_pose_flexible`; every other string or
+    tuple is refused."""
     _args.check_flag("interaction_scores", o.interaction_scores)
     if o.max_interaction_score is not None:
         mcg_interactions.check_threshold("max_interaction_score", o.max_interaction_score)
     _args.check_rank_by(o.rank_by)
-    optimise_steps = 0
+    optimise_steps, flexible = 0, False
     if o.optimise_pose is not False:
-        optimise_steps = mcg_receptor.check_relief_steps(o.optimise_pose, "optimise_pose", lowest=1,
+        budget = o.optimise_pose
+        if isinstance(budget, str) and budget == mcg_interactions.FLEXIBLE:
+            budget, flexible = True, True
+        elif (isinstance(budget, (tuple, list)) and len(budget) == 2 and isinstance(budget[0], str)
+              and budget[0] == mcg_interactions.FLEXIBLE and budget[1] is not True):
+            budget, flexible = budget[1], True
+        elif isinstance(budget, (str, tuple, list)):
+            raise ValueError(f"optimise_pose must be False, True, an integer step budget in 1..{mcg_receptor.MAX_RELIEF_STEPS}, "
+                             f"'flexible' or ('flexible', n) with n in 1..{mcg_receptor.MAX_RELIEF_STEPS}, got {budget!r}")
+        optimise_steps = mcg_receptor.check_relief_steps(budget, "optimise_pose", lowest=1,
                                                          if_true=mcg_interactions.OPTIMISE_STEPS)
         if finisher is not None:
             raise ValueError(mcg_interactions.OPTIMISE_REFUSAL_WITH_FINISHER)
@@ -321,7 +334,7 @@ def _interaction_flags(o, finisher):
         raise ValueError(mcg_interactions.REFUSAL_WITH_FINISHER)
     if interact and o.receptor is None:
         raise ValueError("interaction_scores needs a receptor: it scores the posed molecules against it")
-    return interact, optimise_steps
+    return interact, optimise_steps, flexible
 
 
 def _mesh_reference(o) -> dict:
@@ -406,7 +419,7 @@ def _shape_fields(o, custom_finisher, solid) -> dict:
     return fields
 
 
-def _receptor_fields(o, reference, interact, optimise_steps) -> dict:
+def _receptor_fields(o, reference, interact, optimise_steps, flexible=False) -> dict:
     """The receptor of a posed call, loaded and checked to be clear of the reference conformer; where the call scores
     interactions it is also typed, sorted and given its tile spheres here (`interactions.prepare_receptor`: host work,
     one warning where atoms lie outside the residue templates); a (coords, atomic_numbers, types) triple carries its own
@@ -417,7 +430,8 @@ def _receptor_fields(o, reference, interact, optimise_steps) -> dict:
     if not interact:
         return dict(receptor=rec)
     return dict(receptor=rec, scores_interactions=True, max_interaction_score=o.max_interaction_score, rank_by=o.rank_by,
-                typed_receptor=mcg_interactions.prepare_receptor(o.receptor), optimise_steps=optimise_steps)
+                typed_receptor=mcg_interactions.prepare_receptor(o.receptor), optimise_steps=optimise_steps,
+                optimise_flexible=bool(flexible and optimise_steps))
 
 
 def _reference_graph(o, missing: str, max_atoms: int, placed: Optional[str] = None, conformer=None):
@@ -898,6 +912,10 @@ def relieve_rows(gen, req: Request, coords: torch.Tensor, n_nodes: torch.Tensor,
                 receptor_clashes_before=torch.where(posed, before, torch.full_like(before, -1)))
 
 
+FLEX_RECORD_FIELDS = ("pose_torsions", "pose_torsion_angles", "pose_conformer_rmsd", "intramolecular_clash_before",
+                      "intramolecular_clash")     # what `optimise_pose="flexible"` adds to a record
+
+
 def optimise_rows(gen, req: Request, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_numbers: torch.Tensor,
                   bond_orders: torch.Tensor, pose: torch.Tensor, tanimoto: torch.Tensor) -> dict:
     """The pose optimisation of posed, padded rows (`optimise_pose`): one `_optimise_pose` call over all rows against the
@@ -908,8 +926,12 @@ def optimise_rows(gen, req: Request, coords: torch.Tensor, n_nodes: torch.Tensor
     `translation` of the move itself, `pose_optimisation_rmsd` (0 where nothing moved, NaN where posing failed),
     `pose_trials_kept` (-1 where posing failed) and `interaction_score_before`: W, the weighted sum, of the pose the walk
     started from (NaN where posing failed) - `interactions` divides it by the rotor term behind the gather, where n_rot is
-    counted."""
-    out = gen._optimise_pose(req.typed_receptor, coords, n_nodes, atomic_numbers, bond_orders, req.optimise_steps)
+    counted.  With `req.optimise_flexible` the walk is `_optimise_pose_flex` (torsions turn too): `rotation` / `translation` /
+    `pose` stay the rigid part of the move, and the dict gains `pose_torsions` (-1 where posing failed),
+    `pose_torsion_angles` [B,16], `pose_conformer_rmsd`, `intramolecular_clash_before` and `intramolecular_clash` (NaN
+    there)."""
+    walk = gen._optimise_pose_flex if req.optimise_flexible else gen._optimise_pose
+    out = walk(req.typed_receptor, coords, n_nodes, atomic_numbers, bond_orders, req.optimise_steps)
     dev = out["coords"].device
     x, pose, tanimoto = coords.to(dev, torch.float32), pose.to(dev, torch.float32), tanimoto.to(dev, torch.float32)
     kept = out["kept"].to(dev)
@@ -919,7 +941,18 @@ def optimise_rows(gen, req: Request, coords: torch.Tensor, n_nodes: torch.Tensor
     new_x = torch.where(moved.view(-1, 1, 1), out["coords"][:, :width], x)
     rescored = gen._score_placed(req.reference, new_x, n_nodes).to(dev)
     nan = torch.full_like(out["rmsd"], float("nan"))
-    return dict(coords=new_x, moved=moved, rotation=out["rotation"], translation=out["translation"],
+    flex = {}
+    if req.optimise_flexible:
+        used = out["torsions"].to(dev)
+        flex = dict(pose_torsions=torch.where(posed, used, torch.full_like(used, -1)),
+                    pose_torsion_angles=torch.where(moved.view(-1, 1), out["torsion_angles"],
+                                                    torch.zeros_like(out["torsion_angles"])),
+                    pose_conformer_rmsd=torch.where(posed, torch.where(moved, out["conformer_rmsd"], torch.zeros_like(nan)),
+                                                    nan),
+                    intramolecular_clash_before=torch.where(posed, out["clash_before"], nan),
+                    intramolecular_clash=torch.where(posed, torch.where(moved, out["clash_after"], out["clash_before"]),
+                                                     nan))
+    return dict(flex, coords=new_x, moved=moved, rotation=out["rotation"], translation=out["translation"],
                 pose=torch.where(moved.view(-1, 1), compose_pose(pose, out["rotation"], out["translation"]), pose),
                 overlay_tanimoto=torch.where(moved, rescored, tanimoto),
                 interaction_score_before=torch.where(posed, out["weighted_before"], nan),
@@ -951,6 +984,7 @@ def measure_tensors(gen, req: Request, res: dict) -> dict:
         res = dict(res, x=opt["coords"], pose=opt["pose"], overlay_tanimoto=opt["overlay_tanimoto"],
                    interaction_score_before=opt["interaction_score_before"],
                    pose_optimisation_rmsd=opt["pose_optimisation_rmsd"], pose_trials_kept=opt["pose_trials_kept"])
+        res.update({k: opt[k] for k in FLEX_RECORD_FIELDS if k in opt})
     if req.scores_shape:
         res = dict(res, shape_tanimoto=gen._score(req.reference, res["x"], res["n_nodes"]))
     if req.receptor is not None:

@@ -1,0 +1,76 @@
+#!/usr/bin/env python3
+"""Time of the flexible pose optimisation (`mcg_receptor_optimise_flex`) beside the rigid one (`mcg_receptor_optimise`) in
+the same process (GPU box): 2 048 molecules of 42 atoms - the self-avoiding walks of tools/interaction_time.py, bonded
+along the walk with a code-1 bond, so each has 39 torsions of which 16 are used - against the 100 000-atom ball receptor
+of tools/pose_optimise_time.py, 64 trials.  Ligands typed, tree built and receptor uploaded outside the timed region.
+Warm-up, then the median of 21 runs by device events.  No threshold: a record.  Prints one line per figure and the
+ratio."""
+import os
+import statistics
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tools"))
+
+import torch  # noqa: E402
+
+from ml_conformer_generator_amd import interactions as IX  # noqa: E402
+from interaction_time import ball_receptor, walks  # noqa: E402
+
+B, N, R, STEPS, WARM, REPS = 2048, 42, 100000, 64, 3, 21
+dev = torch.device("cuda:0")
+
+g = torch.Generator().manual_seed(7)
+z = torch.tensor([6, 6, 6, 7, 8])[torch.randint(0, 5, (B, N), generator=g)].to(dev)
+types = torch.randint(0, 8, (B, N), generator=g).to(dev, torch.uint8)
+bonds = torch.zeros(B, N, N, dtype=torch.int8)
+idx = torch.arange(N - 1)
+bonds[:, idx, idx + 1] = 1
+bonds[:, idx + 1, idx] = 1
+nn = torch.full((B,), N, dtype=torch.int32, device=dev)
+rec, radius = ball_receptor(R, R)
+prepared = IX.prepare_receptor(rec)
+on_device = IX.PreparedReceptor(*(t.to(dev) for t in prepared))
+x = walks(B, N, max(radius - 6.0, 1.0), R + 1).to(dev)
+radii, clash = IX.interaction_radii(z), IX.clash_radii(z)
+tree = IX.torsion_tree(z, bonds.to(dev), nn, dev, check=False)
+
+
+def rigid():
+    return IX.optimise_typed(on_device, x, nn, radii, types, STEPS, IX.OPTIMISE_MAX_SHIFT, True, dev)
+
+
+def flexible():
+    return IX._optimise_flex_typed(on_device, x, nn, B, N, radii, types, clash, tree, STEPS, IX.OPTIMISE_MAX_SHIFT, True, dev,
+                                   False)
+
+
+def timed(call):
+    for _ in range(WARM):
+        out = call()
+    torch.cuda.synchronize(dev)
+    ms = []
+    for _ in range(REPS):
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        out = call()
+        end.record()
+        torch.cuda.synchronize(dev)
+        ms.append(start.elapsed_time(end))
+    return out, ms
+
+
+out_r, ms_r = timed(rigid)
+out_f, ms_f = timed(flexible)
+sr, sf = out_r["stats"], out_f["stats"]
+print(f"{B} molecules of {N} atoms, receptor of {R} atoms ({int(prepared.spheres.shape[0])} tiles), {STEPS} trials; torsions "
+      f"found {float(tree['counts'][:, 0].float().mean()):.1f}, used {float(tree['counts'][:, 1].float().mean()):.1f}")
+print(f"rigid    mcg_receptor_optimise:      median {statistics.median(ms_r):.3f} ms (min {min(ms_r):.3f}, max {max(ms_r):.3f}, "
+      f"{REPS} runs); mean trials {float(sr[:, 2].mean()):.1f}, kept {float(sr[:, 3].mean()):.1f}, W {float(sr[:, 0].mean()):.3f} "
+      f"-> {float(sr[:, 1].mean()):.3f}")
+print(f"flexible mcg_receptor_optimise_flex: median {statistics.median(ms_f):.3f} ms (min {min(ms_f):.3f}, max {max(ms_f):.3f}, "
+      f"{REPS} runs); mean trials {float(sf[:, 2].mean()):.1f}, kept {float(sf[:, 3].mean()):.1f}, W {float(sf[:, 0].mean()):.3f} "
+      f"-> {float(sf[:, 1].mean()):.3f}, CLASH {float(sf[:, 6].mean()):.3f} -> {float(sf[:, 7].mean()):.3f}, conformer rmsd "
+      f"{float(sf[:, 9].mean()):.3f}")
+print(f"ratio flexible / rigid: {statistics.median(ms_f) / statistics.median(ms_r):.3f}")
