@@ -13,10 +13,11 @@ _MESH = ("load_mesh", "mass_properties", "mesh_context", "solid_frame")
 _GEOMETRY = ("relax_geometry", "strain_energy")
 _PHARMACOPHORE = ("perceive_features", "feature_points", "pharmacophore_tanimoto", "load_reference_features")
 _RECEPTOR = ("relieve_clashes",)
+_POCKET = ("find_pocket", "Pocket")
 
 __all__ = ["MLConformerGenerator", "evaluate_samples", "ATOM_DECODER", "CONTEXT_NORMS", "DIMENSION",
            "MAX_N_NODES", "MIN_N_NODES", "NUM_BOND_TYPES", *_FINGERPRINT, *_MESH, *_GEOMETRY, *_PHARMACOPHORE,
-           *_RECEPTOR]
+           *_RECEPTOR, *_POCKET]
 
 
 def __getattr__(name):
@@ -42,4 +43,7 @@ def __getattr__(name):
     if name in _RECEPTOR:                # clash relief of posed molecules (receptor.py: the package's own procedure)
         from . import receptor
         return getattr(receptor, name)
+    if name in _POCKET:                  # a receptor's pocket as a `reference_shape` (pocket.py: the package's own)
+        from . import pocket
+        return getattr(pocket, name)
     raise AttributeError(name)

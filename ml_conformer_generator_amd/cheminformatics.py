@@ -376,12 +376,15 @@ def shape_tanimoto_placed(reference_coord, coords: torch.Tensor, n_nodes: torch.
     against the reference conformer, for molecules in the reference's own coordinates (what `shape_overlay` returns, or a
     pose moved on from there).  Scored on the grid `shape_overlay` scores on: reference and molecules are taken into the
     reference's principal frame by `ConformerReference.grid`'s transform, y = (x - t_r) @ M_r, and `mcg_shape_tanimoto`
-    scores them in the identity orientation.  Refuses what `shape_scores` refuses."""
+    scores them in the identity orientation.  Against a `SolidReference` (a pose into a `pocket.Pocket`'s mesh, moved on by
+    the receptor stages): the same, into the solid's frame and against its occupancy (`mcg_shape_tanimoto_field`).  Refuses
+    what `shape_scores` refuses."""
     ref, dev, x, nn = _shape_inputs(reference_coord, coords, n_nodes, device)
     if x is None:
         return torch.empty(0, device=dev)
     B, W = int(x.shape[0]), int(x.shape[1])
     xform, axes = ref.grid(dev)
+    xform = xform.reshape(-1, 12)
     M, t = xform[0, :9].reshape(3, 3), xform[0, 9:]
 
     def into_frame(p):                        # written out: a product and a fixed sum per element, no library GEMM
@@ -389,11 +392,17 @@ def shape_tanimoto_placed(reference_coord, coords: torch.Tensor, n_nodes: torch.
         return (d[..., 0:1] * M[0] + d[..., 1:2] * M[1]) + d[..., 2:3] * M[2]
     real = (torch.arange(W, device=dev).view(1, W) < nn.view(B, 1)).unsqueeze(-1)
     y = torch.where(real, into_frame(x), torch.zeros((), device=dev)).contiguous()
-    ref_frame = into_frame(ref.coords.to(dev)).contiguous()
     n = int(axes.shape[1])
     eye = torch.eye(3, device=dev).reshape(1, 9).contiguous()
-    f = torch.empty(n ** 3, device=dev)
     score = torch.empty(B, device=dev)
+    if isinstance(ref, SolidReference):
+        _lib.check(_lib.lib().mcg_shape_tanimoto_field(_lib.dptr(ref.on(dev)["f"]), _lib.dptr(y), _lib.dptr(nn), B, W,
+                                                       _lib.dptr(eye), 1, _lib.dptr(axes), n, float(ALPHA), float(AMPLITUDE),
+                                                       _lib.dptr(score), _lib.current_stream_ptr(dev)),
+                   "mcg_shape_tanimoto_field")
+        return score
+    ref_frame = into_frame(ref.coords.to(dev)).contiguous()
+    f = torch.empty(n ** 3, device=dev)
     _lib.check(_lib.lib().mcg_shape_tanimoto(_lib.dptr(ref_frame), int(ref_frame.shape[0]), _lib.dptr(y), _lib.dptr(nn), B,
                                              W, _lib.dptr(eye), 1, _lib.dptr(axes), n, float(ALPHA), float(AMPLITUDE),
                                              _lib.dptr(f), _lib.dptr(score), _lib.current_stream_ptr(dev)),
@@ -739,7 +748,11 @@ class SolidReference:
 
 
 def solid_reference(mesh, n: int = 40) -> SolidReference:
-    """`mesh` (anything `mesh.load_mesh` takes) as a `SolidReference` on an n^3 grid, prepared once per call."""
+    """`mesh` (anything `mesh.load_mesh` takes, or a `pocket.Pocket`: its `.mesh`) as a `SolidReference` on an n^3 grid,
+    prepared once per call."""
+    from . import pocket as mcg_pocket
+    if isinstance(mesh, mcg_pocket.Pocket):
+        mesh = mesh.mesh
     return mesh if isinstance(mesh, SolidReference) else SolidReference(mesh, n)
 
 

@@ -54,7 +54,8 @@ forced by the scope of this build:
   * `reference_shape`, `shape_density` (every generation entry): a watertight triangle mesh - an STL file, a (vertices,
     faces) pair - as the reference, what the reference's notebook does with `trimesh` (`mesh.py`, no `trimesh` needed);
     the shape options then score, pose and select against the solid, and `max_atoms_outside` filters on the posed atoms
-    that lie outside it;
+    that lie outside it; or a `pocket.Pocket` (`pocket.find_pocket(receptor, center)`: the cavity of a receptor at a place
+    on it, found on the GPU), whose mesh it is and whose own receptor every receptor option of the call then reads;
   * `relax_geometry` (every generation entry; off by default): every generated molecule's heavy atoms are relaxed on the
     GPU, right behind the bond write-back, on the package's OWN restrained valence force field (`geometry.py`; NOT MMFF94),
     and everything downstream reads the relaxed coordinates.  Independent of `optimise_geometry`, whose meaning and
@@ -496,6 +497,13 @@ class MLConformerGenerator(torch.nn.Module):
         (`cheminformatics.shape_tanimoto_placed`)."""
         return cheminformatics.shape_tanimoto_placed(reference, coords, n_nodes, self.device)
 
+    def _atoms_outside(self, reference, coords: torch.Tensor, n_nodes: torch.Tensor) -> torch.Tensor:
+        """[B] int32 (device): the atoms of padded heavy-atom coordinates, placed in the mesh's own coordinates, that lie
+        outside the call's solid reference (`cheminformatics.mesh_atoms_outside`; -1 for a non-finite row)."""
+        dev = self.device
+        return cheminformatics.mesh_atoms_outside(reference.on(dev)["triangles_own"], coords.to(dev),
+                                                  n_nodes.to(dev), dev)
+
     def _executor(self):
         """Where the poolable host tasks run: the process-wide `HostPool` with `n_host_workers` workers and this generator's
         task deadline (workers created at the first submit or by `prestart`), or this thread."""
@@ -743,6 +751,11 @@ class MLConformerGenerator(torch.nn.Module):
         int property of that name): the heavy atoms of the pose outside the mesh; None (no property) where posing failed.
         `max_atoms_outside=k` (needs `overlay=True` and `reference_shape`): drop the molecules with more than k atoms
         outside, and those whose pose failed, beside `max_receptor_clashes`.
+        `reference_shape=pocket`, a `pocket.Pocket` from `pocket.find_pocket` ("Pockets from the
+        receptor"): the pocket's mesh is the solid, and `max_receptor_clashes`, `relieve_clashes`, `interaction_scores`,
+        `max_interaction_score`, `rank_by="interaction"`, `optimise_pose` and the `receptor_hydrogen_clashes` of
+        `add_hydrogens` read the pocket's own receptor (they need `overlay=True` as with a `receptor`); `receptor=` beside
+        it stays refused.
         `relax_geometry`: True (200 steps) or a step budget 1..4096.  Every generated molecule's heavy atoms are relaxed on
         the GPU right behind the bond write-back, one launch per group of molecules (`geometry.relax_geometry`; DESIGN.md
         section 6, "Relaxed geometry"), on the package's OWN restrained valence force field - NOT MMFF94, heavy atoms
@@ -917,7 +930,8 @@ class MLConformerGenerator(torch.nn.Module):
         heavy atom), max_receptor_clashes other than an integer >= 0 or without a receptor, relieve_clashes other than
         False, True or an integer in 1..1024 or without a receptor, optimise_pose other than False, True, an integer in
         1..1024, "flexible" or ("flexible", n), without a receptor or on a generator with a finisher, a custom finisher, a
-        `reference_shape` together with another reference, with `refine_overlay` or with a `receptor`, or without
+        `reference_shape` together with another reference, with `refine_overlay` or with a `receptor` (a `Pocket` brings
+        its own; a plain mesh with any receptor option), or without
         `n_atoms`, a mesh `load_mesh` refuses ("The mesh needs to be watertight."), a `shape_density` that is not a positive
         real number, max_atoms_outside other than an integer >= 0, without a `reference_shape` or without overlay, and
         relax_geometry other than False, True or an integer in 1..4096 (a float, None, 0, a negative or larger number),

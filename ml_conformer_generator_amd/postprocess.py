@@ -219,6 +219,7 @@ def parse_request(gen, reference_conformer, *, reference_context=None, shape_sco
     Every refusal happens here, before any device work."""
     o = types.SimpleNamespace(**locals())          # the options as given: a helper reads `o.<keyword>`, what was derived
     finisher = getattr(gen, "finisher", None)      # from them is handed to it by name
+    o.pocket = _pocket_receptor(o)                 # a `pocket.Pocket` brings its own receptor: `o.receptor` from here on
     custom_finisher = isinstance(finisher, host_pool.TaskRef)
     fields = _record_flags(o, finisher)
     esp = _electrostatic_flags(o, finisher)
@@ -230,7 +231,8 @@ def parse_request(gen, reference_conformer, *, reference_context=None, shape_sco
     shape = _shape_fields(o, custom_finisher, solid)
     if shape:                                     # the call scores shape or poses: the receptor's options are its fields
         fields.update(shape, **relief)
-        if receptor is not None:                  # refused with a mesh above: the reference is a conformer
+        # a receptor beside a plain mesh was refused above: this is a conformer call's, or - once the call poses - a pocket's own
+        if o.receptor is not None and (o.pocket is None or o.overlay):
             fields.update(_receptor_fields(o, fields["reference"], interact, optimise_steps, flexible))
     scores_shape = fields.get("scores_shape")
     _args.check_flag("pharmacophore_scores", pharmacophore_scores)
@@ -337,10 +339,28 @@ def _interaction_flags(o, finisher):
     return interact, optimise_steps, flexible
 
 
+_RECEPTOR_WITH_SHAPE = ("receptor cannot be combined with reference_shape: the receptor check needs the reference's "
+                        "atoms")
+
+
+def _pocket_receptor(o):
+    """The `pocket.Pocket` of a call whose `reference_shape` is one, else None.  A pocket brings its own receptor, which
+    every receptor option of the call then reads (`o.receptor` is set to it here); a `receptor=` beside it is refused like
+    one beside any other `reference_shape`."""
+    from . import pocket as mcg_pocket
+    if not isinstance(o.reference_shape, mcg_pocket.Pocket):
+        return None
+    if o.receptor is not None:
+        raise ValueError(_RECEPTOR_WITH_SHAPE + " (a Pocket brings its own receptor)")
+    o.receptor = o.reference_shape.receptor
+    return o.reference_shape
+
+
 def _mesh_reference(o) -> dict:
-    """`reference_shape`: a watertight mesh in place of the reference conformer (`mesh.load_mesh`); the request then
-    carries its `cheminformatics.SolidReference` (host side only: nothing is launched here), whether or not an option is
-    on.  `max_atoms_outside` needs it, and `overlay`."""
+    """`reference_shape`: a watertight mesh in place of the reference conformer (`mesh.load_mesh`), or a `pocket.Pocket`,
+    whose mesh it is; the request then carries its `cheminformatics.SolidReference` (host side only: nothing is launched
+    here), whether or not an option is on.  `max_atoms_outside` needs it, and `overlay`.  A plain mesh refuses `receptor`
+    and `max_receptor_clashes`; a pocket's receptor options are read like a conformer call's."""
     solid = None
     if o.reference_shape is not None:
         if (o.reference_conformer is not None and o.reference_conformer is not False) or o.reference_context is not None:
@@ -350,9 +370,8 @@ def _mesh_reference(o) -> dict:
         if o.refine_overlay is not False:
             raise ValueError("refine_overlay cannot be combined with reference_shape: the ascent's objective is the "
                              "overlap with the reference's atoms, and a mesh has none")
-        if o.receptor is not None or o.max_receptor_clashes is not None:
-            raise ValueError("receptor cannot be combined with reference_shape: the receptor check needs the reference's "
-                             "atoms")
+        if o.pocket is None and (o.receptor is not None or o.max_receptor_clashes is not None):
+            raise ValueError(_RECEPTOR_WITH_SHAPE)
         solid = cheminformatics.solid_reference(o.reference_shape)
     if o.max_atoms_outside is not None:
         cheminformatics.check_max_atoms_outside(o.max_atoms_outside)
@@ -366,7 +385,8 @@ def _mesh_reference(o) -> dict:
 
 def _receptor_flags(o) -> dict:
     """`max_receptor_clashes` needs a `receptor`.  `relieve_clashes`: `receptor.check_relief_steps` (True =
-    `receptor.RELIEF_STEPS`); it needs a `receptor`, and with it `overlay`."""
+    `receptor.RELIEF_STEPS`); it needs a `receptor`, and with it `overlay`.  The receptor a `pocket.Pocket` brings counts
+    as one; a pocket call without a receptor option and without `overlay` simply does not read it."""
     if o.max_receptor_clashes is not None:
         mcg_receptor.check_max_receptor_clashes(o.max_receptor_clashes)
         if o.receptor is None:
@@ -377,7 +397,9 @@ def _receptor_flags(o) -> dict:
                                                        if_true=mcg_receptor.RELIEF_STEPS)
         if o.receptor is None:
             raise ValueError("relieve_clashes needs a receptor: it moves the posed molecules out of their contacts with it")
-    if o.receptor is not None and not o.overlay:
+    asked = (o.pocket is None or o.max_receptor_clashes is not None or relief_steps > 0 or o.interaction_scores
+             or o.max_interaction_score is not None or o.optimise_pose is not False)
+    if o.receptor is not None and not o.overlay and asked:       # a pocket's receptor: only once an option reads it
         raise ValueError("receptor needs overlay=True: molecules that are not posed onto the reference are not in "
                          "the receptor's frame")
     return dict(max_receptor_clashes=o.max_receptor_clashes, relief_steps=relief_steps)
@@ -420,13 +442,14 @@ def _shape_fields(o, custom_finisher, solid) -> dict:
 
 
 def _receptor_fields(o, reference, interact, optimise_steps, flexible=False) -> dict:
-    """The receptor of a posed call, loaded and checked to be clear of the reference conformer; where the call scores
-    interactions it is also typed, sorted and given its tile spheres here (`interactions.prepare_receptor`: host work,
-    one warning where atoms lie outside the residue templates); a (coords, atomic_numbers, types) triple carries its own
-    types."""
+    """The receptor of a posed call, loaded and checked to be clear of the reference conformer (a pocket has no atoms, and
+    is empty space by construction: nothing to check); where the call scores interactions it is also typed, sorted and
+    given its tile spheres here (`interactions.prepare_receptor`: host work, one warning where atoms lie outside the
+    residue templates); a (coords, atomic_numbers, types) triple carries its own types."""
     typed = isinstance(o.receptor, (tuple, list)) and len(o.receptor) == 3      # (coords, atomic_numbers, types)
     rec = mcg_receptor.load_receptor((o.receptor[0], o.receptor[1]) if typed else o.receptor)
-    mcg_receptor.check_clear_of_reference(rec[0], reference.coords)
+    if o.pocket is None:
+        mcg_receptor.check_clear_of_reference(rec[0], reference.coords)
     if not interact:
         return dict(receptor=rec)
     return dict(receptor=rec, scores_interactions=True, max_interaction_score=o.max_interaction_score, rank_by=o.rank_by,
@@ -964,7 +987,8 @@ def optimise_rows(gen, req: Request, coords: torch.Tensor, n_nodes: torch.Tensor
 def measure_tensors(gen, req: Request, res: dict) -> dict:
     """Stages 1-3 on one shard's result tensors.  `res` with `x` posed and the per-sample tensors `overlay_tanimoto`,
     `pose`, `shape_tanimoto`, `receptor_clashes` (-1 where posing failed), `receptor_max_overlap` (NaN there), - posed
-    into a mesh - `atoms_outside` and - relieved - `relief_rmsd` (NaN where posing failed) and `receptor_clashes_before`
+    into a mesh - `atoms_outside` (of the returned coordinates: counted again behind a relief or an optimisation) and -
+    relieved - `relief_rmsd` (NaN where posing failed) and `receptor_clashes_before`
     (-1 there) and - optimised - `interaction_score_before`, `pose_optimisation_rmsd` (NaN where posing failed) and
     `pose_trials_kept` (-1 there) added, as far as the call asked: the spellings `handoff.measured_from_tensors` reads,
     which cross the tensor gather."""
@@ -985,6 +1009,10 @@ def measure_tensors(gen, req: Request, res: dict) -> dict:
                    interaction_score_before=opt["interaction_score_before"],
                    pose_optimisation_rmsd=opt["pose_optimisation_rmsd"], pose_trials_kept=opt["pose_trials_kept"])
         res.update({k: opt[k] for k in FLEX_RECORD_FIELDS if k in opt})
+    if "atoms_outside" in res and (req.relief_steps or req.optimise_steps):
+        # a pocket's receptor stages moved the rows after the pose counted them: count the returned coordinates
+        again = gen._atoms_outside(req.reference, res["x"], res["n_nodes"])
+        res["atoms_outside"] = torch.where(res["atoms_outside"].to(again.device) < 0, torch.full_like(again, -1), again)
     if req.scores_shape:
         res = dict(res, shape_tanimoto=gen._score(req.reference, res["x"], res["n_nodes"]))
     if req.receptor is not None:
@@ -1125,6 +1153,11 @@ def _relieve_mols(gen, req: Request, mols: List, measured: List[Measured]) -> No
             m.pose, m.overlay_tanimoto = rel["pose"][j].clone(), float(rel["overlay_tanimoto"][j])
             if hasattr(mols[k], "SetDoubleProp"):
                 mols[k].SetDoubleProp("overlay_tanimoto", m.overlay_tanimoto)
+    if any(measured[k].atoms_outside is not None for k in live):      # a pocket's relief: count the relieved atoms again
+        again = gen._atoms_outside(req.reference, rel["coords"], n).cpu().tolist()
+        for j, k in enumerate(live):
+            if measured[k].atoms_outside is not None:
+                measured[k].atoms_outside = int(again[j])
 
 
 def _contact_mols(gen, rec: tuple, mols: List, posed: List[bool]) -> List[Optional[tuple]]:
