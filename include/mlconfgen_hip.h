@@ -505,7 +505,10 @@ int mcg_shape_pair_tanimoto(const float* coords, const int32_t* n_nodes_dev, int
  *   exact, so every output has the same bits whatever the splits, batch, row, padded width or receptor atom order.
  * MCG_ERR_ARG (1, the value of hipErrorInvalidValue), nothing launched: a null buffer, B outside 1..MCG_RECEPTOR_MAX_B,
  * N outside 1..64, R outside 1..MCG_RECEPTOR_MAX_ATOMS, splits outside 1..MCG_RECEPTOR_MAX_SPLITS, or splits > 1 without
- * partial_ws. */
+ * partial_ws.
+ * MCG_RECEPTOR_MAX_ATOMS is 512 tiles of 256 atoms: two full rounds of the tile list's compaction (csrc/mcg_receptor_tiles.h).
+ * The limit itself, 65 536, 65 537 and 68 900 atoms are exercised by tests/test_large_receptor_gpu.py on all six receptor
+ * entries. */
 #define MCG_RECEPTOR_MAX_B 16384
 #define MCG_RECEPTOR_MAX_ATOMS 131072
 #define MCG_RECEPTOR_MAX_SPLITS 256
