@@ -112,6 +112,13 @@ POCKET_SIGNATURES: Dict[str, tuple] = {
     "mcg_pocket_masks": (_i, [_vp, _i, _vp, _i, _f, _f, _f, _i, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/mlconfgen_hip_search.h one to one (a fourth public header: DESIGN.md section 6,
+# "Pose search")
+SEARCH_SIGNATURES: Dict[str, tuple] = {
+    "mcg_pose_starts": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, C.c_uint64, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    "mcg_pose_search_select": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 
 class PlanOpts(C.Structure):
     """`mcg_plan_opts` (include/mlconfgen_hip.h): zero-initialised = the library's defaults."""
@@ -162,7 +169,8 @@ def lib():
             "or `make -C ml_conformer_generator_amd/csrc`. There is no CPU fallback for the hot path.")
     import torch  # noqa: F401  - loads the process's HIP runtime first (same SONAME as ours)
     handle = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(SIGNATURES.items()) + list(FLEX_SIGNATURES.items()) + list(POCKET_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(FLEX_SIGNATURES.items()) + list(POCKET_SIGNATURES.items())
+                              + list(SEARCH_SIGNATURES.items())):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

@@ -451,6 +451,13 @@ class MLConformerGenerator(torch.nn.Module):
         return mcg_interactions.optimise_pose_flexible(receptor, coords, n_nodes, atomic_numbers, bond_orders, steps,
                                                        device=self.device)
 
+    def _search_pose(self, receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_numbers: torch.Tensor,
+                     bond_orders: torch.Tensor, starts: int, steps: int, seed: int, sample_ids) -> dict:
+        """`_optimise_pose_flex` from `starts` keyed starts per molecule, the best kept (`interactions.search_pose`, device
+        tensors): the starts are keyed by `seed` and the rows' `sample_ids` (None: 0..B-1)."""
+        return mcg_interactions.search_pose(receptor, coords, n_nodes, atomic_numbers, bond_orders, starts, steps,
+                                            seed=seed, sample_ids=sample_ids, device=self.device)
+
     # the standardisation step
     def _standardize(self, coords: torch.Tensor, atomic_numbers: torch.Tensor, bond_orders: torch.Tensor,
                      n_nodes: torch.Tensor) -> dict:
@@ -913,6 +920,13 @@ class MLConformerGenerator(torch.nn.Module):
         maps `x_relaxed` to the returned coordinates only up to `pose_conformer_rmsd`.  Records also carry `pose_torsions`,
         `pose_torsion_angles`, `pose_conformer_rmsd`, `intramolecular_clash_before` and `intramolecular_clash`; None in
         every other call.
+        `optimise_pose="search"` (8 starts, 64 trials), `("search", S)` or `("search", S, n)`, S in 1..64: the flexible walk
+        from S starts per molecule, the best result kept (`interactions.search_pose`; DESIGN.md section 6, "Pose search" -
+        the package's own bounded multi-start, not a docking run and not AutoDock Vina's Monte Carlo search).  Start 0 is
+        the pose as it came; the others are keyed by `sample_seed` (0 without one) and the sample id, so a molecule gets
+        the same starts in any batch and on any number of GPUs; the result is never worse, by the walk's own objective,
+        than `"flexible"` alone.  `pose` is the start's rigid part followed by the walk's.  Records carry the flexible
+        fields and `pose_starts`, `pose_best_start` (0: the pose as it came won); None in every other call.
         `max_interaction_score=t` (implies the score; t a finite real number): keep the molecules with E <= t; NaN and
         missing do not pass; right behind `min_electrostatic_tanimoto`.
         `rank_by="interaction"` (needs the score): `unique`, the diversity walk and `top_k` rank by -E;
@@ -929,7 +943,7 @@ class MLConformerGenerator(torch.nn.Module):
         one `load_receptor` refuses or one that holds the reference (a reference heavy atom within 0.5 A of a receptor
         heavy atom), max_receptor_clashes other than an integer >= 0 or without a receptor, relieve_clashes other than
         False, True or an integer in 1..1024 or without a receptor, optimise_pose other than False, True, an integer in
-        1..1024, "flexible" or ("flexible", n), without a receptor or on a generator with a finisher, a custom finisher, a
+        1..1024, "flexible", ("flexible", n), "search", ("search", S) or ("search", S, n), without a receptor or on a generator with a finisher, a custom finisher, a
         `reference_shape` together with another reference, with `refine_overlay` or with a `receptor` (a `Pocket` brings
         its own; a plain mesh with any receptor option), or without
         `n_atoms`, a mesh `load_mesh` refuses ("The mesh needs to be watertight."), a `shape_density` that is not a positive
@@ -968,8 +982,8 @@ class MLConformerGenerator(torch.nn.Module):
                                    inertial_fragment_matching, blend_power, ifm_diffusion_level, optimise_geometry, *keyed,
                                    **relax)
         if getattr(self, "finisher", None) is None:
-            return postprocess.return_records(self, req, postprocess.measure_tensors(self, req, res), None,
-                                              optimise_geometry)
+            return postprocess.return_records(self, req, postprocess.measure_tensors(self, req, res, None, sample_seed),
+                                              None, optimise_geometry)
         done = self._collect_finish(n_samples)    # finished per group while the later groups were still on their way
         return postprocess.return_finished(self, req, postprocess.measure_finished(self, req, done, res), None,
                                            sample_seed)
@@ -1065,7 +1079,8 @@ class MLConformerGenerator(torch.nn.Module):
                                        fixed_fragment, inertial_fragment_matching, blend_power, ifm_diffusion_level,
                                        optimise_geometry, *keyed, **relax)
             if not finishing:
-                return postprocess.measure_tensors(self, req, res)      # on this rank's GPU, gathered with the rest
+                # on this rank's GPU, gathered with the rest; the shard's global sample ids key the starts of a pose search
+                return postprocess.measure_tensors(self, req, res, index, sample_seed)
             # collected HERE, in front of the status exchange: a finish that raises on one rank (a dead worker, a custom
             # finisher's exception, a result-count mismatch) makes EVERY rank raise ShardError instead of leaving the
             # others parked in the object gather

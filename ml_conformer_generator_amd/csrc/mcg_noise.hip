@@ -12,23 +12,12 @@
 // counter and the value of a slot cannot depend on where the molecule sits in the plan.  Padded slots get exact zeros.
 #include "mcg_common.h"
 #include "mcg_api_internal.h"
+#include "mcg_philox.h"
 
 namespace {
 
-constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u;
-constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
+using mcg_philox::philox4x32_10;
 constexpr int kNoiseThreads = 256;
-
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        if (r) { k0 += kPhiloxW0; k1 += kPhiloxW1; }
-        const uint32_t hi0 = __umulhi(kPhiloxM0, c.x), lo0 = kPhiloxM0 * c.x;
-        const uint32_t hi1 = __umulhi(kPhiloxM1, c.z), lo1 = kPhiloxM1 * c.z;
-        c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-    }
-    return c;
-}
 
 __device__ __forceinline__ void box_muller(uint32_t w_even, uint32_t w_odd, float& z_even, float& z_odd) {
     const float u1 = (float)((w_even >> 8) + 1u) * 0x1p-24f;     // (0, 1]: exact, 24 bits

@@ -82,6 +82,8 @@ class Measured:
     pose_conformer_rmsd: Optional[float] = None   # A: the change of the conformer alone, the rigid part taken out
     intramolecular_clash_before: Optional[float] = None     # CLASH of `interactions.optimise_pose_flexible` at the start
     intramolecular_clash: Optional[float] = None  # ... and at the returned coordinates
+    pose_starts: Optional[int] = None             # `optimise_pose="search"`: starts the pose search walked
+    pose_best_start: Optional[int] = None         # ... and the one that won (0: the pose as it came; -1: none was finite)
     stereo_order: Optional[List[int]] = None      # the stereo search's atom order, -1 beyond the atoms as it comes
     stereo_status: Optional[int] = None           # `canonical.describe_status`; 0 = the stereo identity is defined
     stereo_descriptors: Optional[list] = None     # [the row of v as it comes, None -> per atom in record order on first read]
@@ -133,7 +135,8 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
     `pose_optimisation_rmsd` [n] fp32 and `pose_trials_kept` [n] (negative: posing failed - the record gets None for all
     three).  `optimise_pose="flexible"` adds `pose_torsions` [n] int32, `pose_torsion_angles` [n,16] fp32 (a record keeps
     the first `pose_torsions`), `pose_conformer_rmsd`, `intramolecular_clash_before` and `intramolecular_clash` [n] fp32
-    (all five or none; None on the same rows).
+    (all five or none; None on the same rows).  `optimise_pose="search"` adds `pose_starts` and `pose_best_start` [n] int32
+    beside them (both or neither; None on the same rows).
     The stereo identity of a call with `smiles="isomeric"` comes as `stereo_order` [n,W] int32, `stereo_status` [n],
     `stereo_descriptors` [n,W] int8 - `stereo.stereo_order`'s `stereo`: v in canonical position order, which a record
     turns into its own order on first read -, `n_stereo_defined` [n] and `n_stereo_undefined` [n] (all five or none).
@@ -220,7 +223,8 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
         if "pose_torsions" in cols:             # a flexible walk: the angles of the torsions it used
             cols["pose_torsion_angles"] = [row[: max(k, 0)] for row, k in zip(cols["pose_torsion_angles"], cols["pose_torsions"])]
         for k in ("pose_trials_kept", "pose_optimisation_rmsd", "interaction_score_before", "pose_torsions",
-                  "pose_torsion_angles", "pose_conformer_rmsd", "intramolecular_clash_before", "intramolecular_clash"):
+                  "pose_torsion_angles", "pose_conformer_rmsd", "intramolecular_clash_before", "intramolecular_clash",
+                  "pose_starts", "pose_best_start"):
             if k in cols:
                 cols[k] = [None if gone else v for gone, v in zip(missing, cols[k])]
     return [Measured(**{k: col[b] for k, col in cols.items()}) for b in range(n)]
@@ -650,6 +654,19 @@ class GeneratedMolecule:
         return self._measured.intramolecular_clash
 
     @property
+    def pose_starts(self) -> Optional[int]:
+        """The starts per molecule the pose search walked (`interactions.search_pose`: the package's own bounded multi-start
+        of its flexible walk, not a docking run); None in a call without `optimise_pose="search"`, and where posing
+        failed."""
+        return self._measured.pose_starts
+
+    @property
+    def pose_best_start(self) -> Optional[int]:
+        """The start of the pose search whose walk ended lowest: 0 the pose as it came, 1.. a keyed start, -1 where no
+        start had a finite objective; None in a call without `optimise_pose="search"`, and where posing failed."""
+        return self._measured.pose_best_start
+
+    @property
     def relief_rmsd(self) -> Optional[float]:
         """How far, as a heavy-atom RMSD in A, the clash relief moved this molecule as a rigid body out of its contacts
         with the call's receptor (`receptor.relieve_clashes`: the package's own procedure - not a docking score, not a
@@ -1051,6 +1068,7 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                            pose_conformer_rmsd: Optional[torch.Tensor] = None,
                            intramolecular_clash_before: Optional[torch.Tensor] = None,
                            intramolecular_clash: Optional[torch.Tensor] = None,
+                           pose_starts: Optional[torch.Tensor] = None, pose_best_start: Optional[torch.Tensor] = None,
                            stereo_order: Optional[torch.Tensor] = None, stereo_status: Optional[torch.Tensor] = None,
                            stereo_descriptors: Optional[torch.Tensor] = None,
                            n_stereo_defined: Optional[torch.Tensor] = None,
@@ -1096,6 +1114,7 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     `postprocess.optimise_rows` spells it (negative trials kept: its pose failed, the record gets None for all three;
     None: a call without `optimise_pose`).  `pose_torsions[b]` / `pose_torsion_angles[b]` [16] / `pose_conformer_rmsd[b]` /
     `intramolecular_clash_before[b]` / `intramolecular_clash[b]`: what `optimise_pose="flexible"` adds (all five or none).
+    `pose_starts[b]` / `pose_best_start[b]`: what `optimise_pose="search"` adds beside them (both or neither).
     `stereo_order[b]` [W] / `stereo_status[b]` / `stereo_descriptors[b]` [W] int8 / `n_stereo_defined[b]` /
     `n_stereo_undefined[b]`: row b's stereo identity as `stereo.stereo_order` returns it - `stereo_descriptors` is its
     `stereo`, v in canonical position order; the counts are defined tetrahedral + defined double bonds, and the undefined
@@ -1127,7 +1146,7 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                   pose_trials_kept=pose_trials_kept, pose_torsions=pose_torsions,
                   pose_torsion_angles=pose_torsion_angles, pose_conformer_rmsd=pose_conformer_rmsd,
                   intramolecular_clash_before=intramolecular_clash_before, intramolecular_clash=intramolecular_clash,
-                  stereo_order=stereo_order, stereo_status=stereo_status,
+                  pose_starts=pose_starts, pose_best_start=pose_best_start, stereo_order=stereo_order, stereo_status=stereo_status,
                   stereo_descriptors=stereo_descriptors, n_stereo_defined=n_stereo_defined,
                   n_stereo_undefined=n_stereo_undefined, n_rings=n_rings, n_ring_systems=n_ring_systems,
                   min_ring_size=min_ring_size, max_ring_size=max_ring_size, ring_sizes=ring_sizes,

@@ -435,8 +435,8 @@ def optimise_pose_flexible(receptor, coords: torch.Tensor, n_nodes: torch.Tensor
     (`ligand_types`), one `mcg_torsion_tree` launch (`torsion_tree`) and one `mcg_receptor_optimise_flex` launch.
 
     THE PACKAGE'S OWN PROCEDURE (DESIGN.md section 6, "Flexible pose"): NOT a docking run, NOT AutoDock Vina's optimiser;
-    no hydrogens, no global search.  It works on the returned heavy-atom graph (symmetric codes 0 / 1 / 2 / 3 / 4, at most
-    64 atoms).
+    no hydrogens, no global search (`search_pose` runs this walk from several keyed starts and keeps the best).  It works
+    on the returned heavy-atom graph (symmetric codes 0 / 1 / 2 / 3 / 4, at most 64 atoms).
 
     Torsions        a torsion is a bond `ROTATABLE_BOND` matches - code 1, not a ring bond, both ends of heavy degree >= 2 -
                     unless it joins a nitrogen to a carbon that has a code-2 bond to N, O or S (amide, urea, carbamate;
@@ -500,6 +500,187 @@ def optimise_pose_flexible(receptor, coords: torch.Tensor, n_nodes: torch.Tensor
     if trace:
         res["trace"] = out["trace"]
     return res
+
+
+# ----------------------------------------------------------------------------------------------- pose search
+SEARCH = "search"               # the value of `optimise_pose` that asks for this stage
+SEARCH_STARTS = 8               # what `optimise_pose="search"` stands for
+SEARCH_MAX_STARTS = 64          # include/mlconfgen_hip_search.h MCG_SEARCH_MAX_STARTS
+SEARCH_PARAMS = 24              # include/mlconfgen_hip_search.h MCG_SEARCH_PARAMS
+SEARCH_SPREAD = 2.0             # angstrom: the largest shift of a start's centroid
+SEARCH_MAX_TURN = math.pi       # rad: the largest rigid turn of a start
+SEARCH_COUNTER_WORD = 0xFFFFFFFE    # c3 of a start's Philox counter: no noise counter ((run << 8) | block, block 0..2)
+#                                     and not the size draw (0xFFFFFFFF) reaches it
+
+
+def check_starts(value, name: str = "starts") -> int:
+    """`starts` as an int in 1..64 (not a bool), else ValueError."""
+    if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= SEARCH_MAX_STARTS:
+        raise ValueError(f"{name} must be an integer in 1..{SEARCH_MAX_STARTS}, got {value!r}")
+    return int(value)
+
+
+def _repeat_tree(tree: Dict[str, torch.Tensor], idx: torch.Tensor) -> Dict[str, torch.Tensor]:
+    return {k: tree[k].index_select(0, idx).contiguous() for k in ("torsion_atoms", "side_mask", "near_mask", "counts")}
+
+
+@torch.no_grad()
+def pose_starts(coords: torch.Tensor, n_nodes: torch.Tensor, tree: Dict[str, torch.Tensor], sample_ids: torch.Tensor,
+                seed: int = 0, starts: int = SEARCH_STARTS, spread: float = SEARCH_SPREAD,
+                max_turn: float = SEARCH_MAX_TURN, device=None, params: bool = False) -> Dict[str, torch.Tensor]:
+    """The `mcg_pose_starts` launch itself (include/mlconfgen_hip_search.h): `starts` keyed starts of every row of `coords`
+    [B,N,3] (`n_nodes` [B], `tree` a `torsion_tree` result for the same rows, `sample_ids` [B] int64 in [0, 2^32)).  Device
+    tensors as the kernel writes them: coords [B,S,N,3], xform [B,S,12], angles [B,S,16] and - `params` - params [B,S,24].
+    Start 0 is the input's bits.  The checks are `search_pose`'s; B >= 1, N >= 1."""
+    from . import seeding
+    starts = check_starts(starts)
+    spread = _args.check_real("spread", spread, 0.0)
+    max_turn = _args.check_real("max_turn", max_turn, 0.0)
+    if max_turn > math.pi:
+        raise ValueError(f"max_turn must lie in [0, pi], got {max_turn!r}")
+    seed = seeding.check_seed(seed)
+    dev = _args.resolve_device(device, coords)
+    B, N, _ = _args.ligand_arguments(coords, n_nodes, None, MAX_ATOMS, MAX_BATCH, "the pose search takes")
+    ids = seeding.check_sample_ids(sample_ids, B).to(dev, torch.int64).contiguous()
+    x = coords.to(dev, torch.float32).contiguous()
+    nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B).contiguous()
+    out = dict(coords=torch.zeros(B, starts, N, 3, device=dev), xform=torch.zeros(B, starts, 12, device=dev),
+               angles=torch.zeros(B, starts, FLEX_MAX_TORSIONS, device=dev))
+    if params:
+        out["params"] = torch.zeros(B, starts, SEARCH_PARAMS, device=dev)
+    used = tree["counts"][:, 1].contiguous()
+    _lib.check(_lib.lib().mcg_pose_starts(
+        _lib.dptr(x), _lib.dptr(nn), B, N, _lib.dptr(tree["torsion_atoms"]), _lib.dptr(tree["side_mask"]), _lib.dptr(used),
+        _lib.dptr(ids), seed, starts, spread, max_turn, _lib.dptr(out["coords"]), _lib.dptr(out["xform"]),
+        _lib.dptr(out["angles"]), _lib.dptr(out.get("params")), _lib.current_stream_ptr(dev)), "mcg_pose_starts")
+    return out
+
+
+@torch.no_grad()
+def select_starts(walk_coords: torch.Tensor, walk_xform: torch.Tensor, walk_stats: torch.Tensor, walk_angles: torch.Tensor,
+                  start_xform: torch.Tensor, start_angles: torch.Tensor, coords: torch.Tensor, n_nodes: torch.Tensor,
+                  device=None) -> Dict[str, torch.Tensor]:
+    """The `mcg_pose_search_select` launch itself (include/mlconfgen_hip_search.h) on the walk's rows [B,S,...] of the starts
+    of `coords` [B,N,3].  Device tensors as the kernel writes them: coords [B,N,3], xform [B,12], stats [B,12], angles
+    [B,16], best_start [B] int32, start_scores [B,S]."""
+    dev = _args.resolve_device(device, coords)
+    B, S, N = int(walk_coords.shape[0]), int(walk_coords.shape[1]), int(walk_coords.shape[2])
+    for name, t, shape in (("walk_coords", walk_coords, (B, S, N, 3)), ("walk_xform", walk_xform, (B, S, 12)),
+                           ("walk_stats", walk_stats, (B, S, 12)), ("walk_angles", walk_angles, (B, S, FLEX_MAX_TORSIONS)),
+                           ("start_xform", start_xform, (B, S, 12)), ("start_angles", start_angles, (B, S, FLEX_MAX_TORSIONS)),
+                           ("coords", coords, (B, N, 3))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+    f32 = lambda t: t.to(dev, torch.float32).contiguous()                                  # noqa: E731
+    nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B).contiguous()
+    out = dict(coords=torch.zeros(B, N, 3, device=dev), xform=torch.zeros(B, 12, device=dev),
+               stats=torch.zeros(B, 12, device=dev), angles=torch.zeros(B, FLEX_MAX_TORSIONS, device=dev),
+               best_start=torch.zeros(B, dtype=torch.int32, device=dev), start_scores=torch.zeros(B, S, device=dev))
+    _lib.check(_lib.lib().mcg_pose_search_select(
+        _lib.dptr(f32(walk_coords)), _lib.dptr(f32(walk_xform)), _lib.dptr(f32(walk_stats)), _lib.dptr(f32(walk_angles)),
+        _lib.dptr(f32(start_xform)), _lib.dptr(f32(start_angles)), _lib.dptr(f32(coords)), _lib.dptr(nn), B, N, S,
+        _lib.dptr(out["coords"]), _lib.dptr(out["xform"]), _lib.dptr(out["stats"]), _lib.dptr(out["angles"]),
+        _lib.dptr(out["best_start"]), _lib.dptr(out["start_scores"]), _lib.current_stream_ptr(dev)),
+        "mcg_pose_search_select")
+    return out
+
+
+@torch.no_grad()
+def search_pose(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_numbers: torch.Tensor,
+                bond_orders: torch.Tensor, starts: int = SEARCH_STARTS, steps: int = OPTIMISE_STEPS,
+                max_shift: float = OPTIMISE_MAX_SHIFT, spread: float = SEARCH_SPREAD, max_turn: float = SEARCH_MAX_TURN,
+                seed: int = 0, sample_ids: Optional[torch.Tensor] = None, device=None, skip_tiles: bool = True
+                ) -> Dict[str, torch.Tensor]:
+    """`optimise_pose_flexible` from `starts` keyed starts per molecule, the best result kept: one perceive launch
+    (`ligand_types`), one `mcg_torsion_tree` launch, one `mcg_pose_starts` launch, the flexible walk
+    (`mcg_receptor_optimise_flex`, untouched) over the B x `starts` start rows in chunks of at most 16 384, and one
+    `mcg_pose_search_select` launch.
+
+    THE PACKAGE'S OWN, LABELLED PROCEDURE ("Pose search"): a bounded multi-start of the package's own
+    downhill walk.  NOT a docking run and NOT AutoDock Vina's Monte Carlo search: no Metropolis chain, no random restarts
+    beyond the `starts` asked for, no hydrogens.  The defaults (8 starts, 2 A, any turn, any torsion angle) are stated
+    choices, not tuned on any complex; no agreement with any docking program is claimed.
+
+    Starts          start 0 is the input as it came.  Start s >= 1 of the molecule with sample id i: Philox4x32-10 with the
+                    key of the keyed sampler noise (`seed` & 0xffffffff, `seed` >> 32) and the counter (i, s, j,
+                    0xfffffffe), j = 0..5; a word w gives the uniform u = (w >> 8) 2^-24.  c the atom centroid, q = x - c.
+                    j = 0: a rotation axis uniform on the sphere (z = 2 u0 - 1, phi = 2 pi u1) and the angle
+                    `max_turn` u2.  j = 1: a shift d, its direction drawn like the axis, its length `spread` cbrt(u2):
+                    uniform in the ball.  j = 2..5: one angle theta_k = 2 pi u - pi per torsion slot k = 0..15.  The
+                    torsions the walk would use are turned in ascending k on q, each by theta_k about its current axis
+                    through q_b (the walk's own turn); then x_s = q' @ R_s + (c + d), R_s the walk's trial rotation.
+    Walk            every start is walked by `optimise_pose_flexible`'s kernel with `steps` trials and `max_shift` about the
+                    START's own centroid: the returned centroid lies within `spread` + `max_shift` of the input's.
+    Choice          J_s = W_after + 0.840f CLASH_after in fp32, the product and the sum each rounded once - the walk's own
+                    acceptance quantity.  The smallest finite J wins; NaN never wins; a tie goes to the lowest s.  So the
+                    result's J is never above that of `optimise_pose_flexible` alone (start 0), and with `starts` = 1 every
+                    tensor is that function's, bit for bit.
+    Reproducible    a molecule's starts depend on (`seed`, its sample id, s) and its own data only: the same bits in any
+                    batch, at any row, at any padded width and on any number of GPUs.  `sample_ids` defaults to 0..B-1.
+
+    Returns what `optimise_pose_flexible` returns (no trace) - `rotation`, `translation`: the start's rigid part followed by
+    the walk's (R_s @ G_w, t_s @ G_w + t_w); `torsion_angles`: theta + the walk's summed turns; `weighted_before`,
+    `clash_before`, `gradient`: the input's (start 0's); `weighted_after`, `clash_after`, `trials`, `kept`, `torsions`,
+    `step_trans`: the winner's; `rmsd`, `conformer_rmsd`: the input against `coords`; `moved`: a trial was kept or a start
+    >= 1 won - and
+      best_start [B]        int32: the winning start; -1 where no start has a finite J (the row is start 0's)
+      start_scores [B,S]    fp32: every J_s
+      starts                dict of the per-start device tensors: coords [B,S,N,3], xform [B,S,12], angles [B,S,16] as
+                            `mcg_pose_starts` wrote them and walk_coords, walk_xform, walk_stats, walk_angles as the walk
+                            returned them for those rows
+    Rows without atoms or with a non-finite coordinate behave as in `optimise_pose`.  Refused before any device work: what
+    `optimise_pose_flexible` refuses, `starts` outside 1..64, `spread` negative or not finite, `max_turn` outside [0, pi],
+    a `seed` outside [0, 2^64), sample ids outside [0, 2^32) or not [B]."""
+    from . import seeding
+    prepared = prepare_receptor(receptor)
+    steps = mcg_receptor.check_relief_steps(steps)
+    max_shift = check_max_shift(max_shift)
+    starts = check_starts(starts)
+    spread = _args.check_real("spread", spread, 0.0)
+    max_turn = _args.check_real("max_turn", max_turn, 0.0)
+    if max_turn > math.pi:
+        raise ValueError(f"max_turn must lie in [0, pi], got {max_turn!r}")
+    seed = seeding.check_seed(seed)
+    dev = _args.resolve_device(device, coords)
+    B, N, z, bonds = _posed_graphs(coords, n_nodes, atomic_numbers, bond_orders, "pose optimisation takes")
+    ids = seeding.check_sample_ids(torch.arange(B) if sample_ids is None else sample_ids, B)
+    if B == 0 or N == 0:
+        res = optimise_pose_flexible(prepared, coords, n_nodes, atomic_numbers, bond_orders, steps, max_shift, dev,
+                                     skip_tiles=skip_tiles)
+        return dict(res, best_start=torch.zeros(B, dtype=torch.int32, device=dev),
+                    start_scores=torch.zeros(B, starts, device=dev), starts={})
+    S = starts
+    types = ligand_types(z[:, :N], bonds[:, :N, :N], n_nodes, dev)
+    tree = torsion_tree(z[:, :N], bonds[:, :N, :N], n_nodes, dev, check=False)
+    radii, clash = interaction_radii(z[:, :N].to(dev)), clash_radii(z[:, :N].to(dev))
+    nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B)
+    st = pose_starts(coords, nn, tree, ids, seed, S, spread, max_turn, dev)
+    # the walk, on the B * S start rows: the rows' own data replicated by an index, at most 16 384 rows a launch
+    idx = torch.arange(B, device=dev).repeat_interleave(S)
+    rows = st["coords"].reshape(B * S, N, 3)
+    parts = []
+    for lo in range(0, B * S, MAX_BATCH):
+        hi = min(B * S, lo + MAX_BATCH)
+        pick = idx[lo:hi]
+        parts.append(_optimise_flex_typed(prepared, rows[lo:hi], nn.index_select(0, pick), hi - lo, N,
+                                          radii.index_select(0, pick), types.index_select(0, pick),
+                                          clash.index_select(0, pick), _repeat_tree(tree, pick), steps, max_shift,
+                                          skip_tiles, dev, False))
+    walk = {k: torch.cat([p[k] for p in parts], dim=0) for k in ("coords", "xform", "stats", "angles", "gradient")}
+    shaped = lambda k: walk[k].reshape(B, S, *walk[k].shape[1:])                           # noqa: E731
+    out = select_starts(shaped("coords"), shaped("xform"), shaped("stats"), shaped("angles"), st["xform"], st["angles"],
+                        coords, nn, dev)
+    stats, xform, best = out["stats"], out["xform"], out["best_start"]
+    ok = torch.isfinite(stats[:, 0])
+    count = lambda col: torch.where(ok, stats[:, col], torch.full_like(stats[:, col], -1.0)).to(torch.int32)
+    return dict(coords=out["coords"], rotation=xform[:, :9].reshape(B, 3, 3), translation=xform[:, 9:],
+                moved=ok & ((stats[:, 3] > 0) | (best > 0)), weighted_before=stats[:, 0], weighted_after=stats[:, 1],
+                trials=count(2), kept=count(3), rmsd=stats[:, 4], gradient=shaped("gradient")[:, 0].contiguous(),
+                torsions=count(8), torsions_found=tree["counts"][:, 0], torsion_angles=out["angles"],
+                torsion_atoms=tree["torsion_atoms"], clash_before=stats[:, 6], clash_after=stats[:, 7],
+                conformer_rmsd=stats[:, 9], step_trans=stats[:, 5], best_start=best, start_scores=out["start_scores"],
+                starts=dict(coords=st["coords"], xform=st["xform"], angles=st["angles"], walk_coords=shaped("coords"),
+                            walk_xform=shaped("xform"), walk_stats=shaped("stats"), walk_angles=shaped("angles")))
 
 
 # ----------------------------------------------------------------------------------------------- options

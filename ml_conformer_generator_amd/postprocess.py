@@ -130,6 +130,7 @@ class Request:
     max_interaction_score: Optional[float] = None
     optimise_steps: int = 0                       # `optimise_pose`: trials of the pose optimisation, 0 = not optimised
     optimise_flexible: bool = False               # `optimise_pose="flexible"` / `("flexible", n)`: torsions turn too
+    optimise_starts: int = 0                      # `optimise_pose="search"` / `("search", S[, n])`: starts of the pose search, 0 = none
 
     @property
     def selects_by_shape(self) -> bool:
@@ -224,6 +225,7 @@ def parse_request(gen, reference_conformer, *, reference_context=None, shape_sco
     fields = _record_flags(o, finisher)
     esp = _electrostatic_flags(o, finisher)
     interact, optimise_steps, flexible = _interaction_flags(o, finisher)
+    starts = _optimise_pose_value(optimise_pose)[2] if optimise_steps else 0
     fields.update(partial_charges=partial_charges, relax_steps=mcg_geometry.check_steps(relax_geometry))
     fields.update(_mesh_reference(o))
     solid = fields["reference"]
@@ -233,7 +235,7 @@ def parse_request(gen, reference_conformer, *, reference_context=None, shape_sco
         fields.update(shape, **relief)
         # a receptor beside a plain mesh was refused above: this is a conformer call's, or - once the call poses - a pocket's own
         if o.receptor is not None and (o.pocket is None or o.overlay):
-            fields.update(_receptor_fields(o, fields["reference"], interact, optimise_steps, flexible))
+            fields.update(_receptor_fields(o, fields["reference"], interact, optimise_steps, flexible, starts))
     scores_shape = fields.get("scores_shape")
     _args.check_flag("pharmacophore_scores", pharmacophore_scores)
     if min_pharmacophore_tanimoto is not None:
@@ -297,6 +299,31 @@ def _electrostatic_flags(o, finisher) -> bool:
     return esp
 
 
+def _optimise_pose_value(value):
+    """(budget, flexible, starts) of an `optimise_pose` that is not False: the trial budget as given (True or an integer,
+    still unchecked), whether the walk is the flexible one, and the starts of the pose search (0: none).  "flexible" and
+    ("flexible", n); "search" (`interactions.SEARCH_STARTS` starts), ("search", S) and ("search", S, n) with S in 1..64
+    (`interactions.check_starts`); every other string or tuple is a ValueError."""
+    budget, flexible, starts = value, False, 0
+    if isinstance(budget, str) and budget == mcg_interactions.FLEXIBLE:
+        budget, flexible = True, True
+    elif (isinstance(budget, (tuple, list)) and len(budget) == 2 and isinstance(budget[0], str)
+          and budget[0] == mcg_interactions.FLEXIBLE and budget[1] is not True):
+        budget, flexible = budget[1], True
+    elif isinstance(budget, str) and budget == mcg_interactions.SEARCH:
+        budget, flexible, starts = True, True, mcg_interactions.SEARCH_STARTS
+    elif (isinstance(budget, (tuple, list)) and len(budget) in (2, 3) and isinstance(budget[0], str)
+          and budget[0] == mcg_interactions.SEARCH and (len(budget) == 2 or budget[2] is not True)):
+        starts = mcg_interactions.check_starts(budget[1], "optimise_pose: S of ('search', S)")
+        budget, flexible = (budget[2] if len(budget) == 3 else True), True
+    elif isinstance(budget, (str, tuple, list)):
+        raise ValueError(f"optimise_pose must be False, True, an integer step budget in 1..{mcg_receptor.MAX_RELIEF_STEPS}, "
+                         f"'flexible' or ('flexible', n) with n in 1..{mcg_receptor.MAX_RELIEF_STEPS}, 'search', "
+                         f"('search', S) or ('search', S, n) with S in 1..{mcg_interactions.SEARCH_MAX_STARTS}, "
+                         f"got {budget!r}")
+    return budget, flexible, starts
+
+
 def _interaction_flags(o, finisher):
     """(whether the call scores interactions, the trials of `optimise_pose`, whether its walk is the flexible one).
     `interaction_scores` (implied by `max_interaction_score`, a finite real number) needs a `receptor` - and with it
@@ -304,23 +331,16 @@ def _interaction_flags(o, finisher):
     needs the score.  Refused with a finisher: the values go onto the records.  `optimise_pose`:
     `receptor.check_relief_steps` (True = `interactions.OPTIMISE_STEPS`); it needs a `receptor`, and with it `overlay`,
     implies `interaction_scores` and is refused with a finisher likewise.  `optimise_pose="flexible"` (64 trials) and
-    `optimise_pose=("flexible", n)`, n in 1..1024, ask for `interactions.optimise_pose_flexible`; every other string or
-    tuple is refused."""
+    `optimise_pose=("flexible", n)`, n in 1..1024, ask for `interactions.optimise_pose_flexible`; `optimise_pose="search"`
+    (8 starts, 64 trials), `("search", S)` and `("search", S, n)`, S in 1..64, for `interactions.search_pose`, whose walk is
+    the flexible one (`_optimise_pose_value` reads all of them); every other string or tuple is refused."""
     _args.check_flag("interaction_scores", o.interaction_scores)
     if o.max_interaction_score is not None:
         mcg_interactions.check_threshold("max_interaction_score", o.max_interaction_score)
     _args.check_rank_by(o.rank_by)
     optimise_steps, flexible = 0, False
     if o.optimise_pose is not False:
-        budget = o.optimise_pose
-        if isinstance(budget, str) and budget == mcg_interactions.FLEXIBLE:
-            budget, flexible = True, True
-        elif (isinstance(budget, (tuple, list)) and len(budget) == 2 and isinstance(budget[0], str)
-              and budget[0] == mcg_interactions.FLEXIBLE and budget[1] is not True):
-            budget, flexible = budget[1], True
-        elif isinstance(budget, (str, tuple, list)):
-            raise ValueError(f"optimise_pose must be False, True, an integer step budget in 1..{mcg_receptor.MAX_RELIEF_STEPS}, "
-                             f"'flexible' or ('flexible', n) with n in 1..{mcg_receptor.MAX_RELIEF_STEPS}, got {budget!r}")
+        budget, flexible, _ = _optimise_pose_value(o.optimise_pose)
         optimise_steps = mcg_receptor.check_relief_steps(budget, "optimise_pose", lowest=1,
                                                          if_true=mcg_interactions.OPTIMISE_STEPS)
         if finisher is not None:
@@ -441,7 +461,7 @@ def _shape_fields(o, custom_finisher, solid) -> dict:
     return fields
 
 
-def _receptor_fields(o, reference, interact, optimise_steps, flexible=False) -> dict:
+def _receptor_fields(o, reference, interact, optimise_steps, flexible=False, starts=0) -> dict:
     """The receptor of a posed call, loaded and checked to be clear of the reference conformer (a pocket has no atoms, and
     is empty space by construction: nothing to check); where the call scores interactions it is also typed, sorted and
     given its tile spheres here (`interactions.prepare_receptor`: host work, one warning where atoms lie outside the
@@ -454,7 +474,8 @@ def _receptor_fields(o, reference, interact, optimise_steps, flexible=False) -> 
         return dict(receptor=rec)
     return dict(receptor=rec, scores_interactions=True, max_interaction_score=o.max_interaction_score, rank_by=o.rank_by,
                 typed_receptor=mcg_interactions.prepare_receptor(o.receptor), optimise_steps=optimise_steps,
-                optimise_flexible=bool(flexible and optimise_steps))
+                optimise_flexible=bool(flexible and optimise_steps),
+                optimise_starts=int(starts) if optimise_steps else 0)
 
 
 def _reference_graph(o, missing: str, max_atoms: int, placed: Optional[str] = None, conformer=None):
@@ -890,6 +911,8 @@ def interactions(gen, req: Request, res: dict) -> dict:
             out["n_rot"].to(dev, torch.float32).clamp(min=0)
         before = res["interaction_score_before"].to(dev, torch.float32) / den
         unmoved = res["pose_trials_kept"].to(dev) == 0                            # the pose scored above IS the start
+        if "pose_best_start" in res:                                              # ... unless another start of the search won
+            unmoved = unmoved & ~(res["pose_best_start"].to(dev) > 0)
         values["interaction_score_before"] = torch.where(unmoved, values["interaction_score"], before)
     return values
 
@@ -937,10 +960,12 @@ def relieve_rows(gen, req: Request, coords: torch.Tensor, n_nodes: torch.Tensor,
 
 FLEX_RECORD_FIELDS = ("pose_torsions", "pose_torsion_angles", "pose_conformer_rmsd", "intramolecular_clash_before",
                       "intramolecular_clash")     # what `optimise_pose="flexible"` adds to a record
+SEARCH_RECORD_FIELDS = ("pose_starts", "pose_best_start")      # what `optimise_pose="search"` adds beside them
 
 
 def optimise_rows(gen, req: Request, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_numbers: torch.Tensor,
-                  bond_orders: torch.Tensor, pose: torch.Tensor, tanimoto: torch.Tensor) -> dict:
+                  bond_orders: torch.Tensor, pose: torch.Tensor, tanimoto: torch.Tensor,
+                  row_ids: Optional[torch.Tensor] = None, sample_seed: Optional[int] = None) -> dict:
     """The pose optimisation of posed, padded rows (`optimise_pose`): one `_optimise_pose` call over all rows against the
     request's typed receptor and - for the rows it moved - the composed pose and the shape Tanimoto of the pose as placed
     (`_score_placed`).  `pose` [B,12] (a row with a non-finite entry: posing failed, the row is not in the receptor's frame
@@ -952,9 +977,18 @@ def optimise_rows(gen, req: Request, coords: torch.Tensor, n_nodes: torch.Tensor
     counted.  With `req.optimise_flexible` the walk is `_optimise_pose_flex` (torsions turn too): `rotation` / `translation` /
     `pose` stay the rigid part of the move, and the dict gains `pose_torsions` (-1 where posing failed),
     `pose_torsion_angles` [B,16], `pose_conformer_rmsd`, `intramolecular_clash_before` and `intramolecular_clash` (NaN
-    there)."""
-    walk = gen._optimise_pose_flex if req.optimise_flexible else gen._optimise_pose
-    out = walk(req.typed_receptor, coords, n_nodes, atomic_numbers, bond_orders, req.optimise_steps)
+    there).  With `req.optimise_starts` the stage is `_search_pose`: that walk from so many keyed starts per row, keyed by
+    `sample_seed` (None: 0) and the rows' sample ids `row_ids` (None: 0..B-1; in a sharded call the global ids, so a
+    molecule gets the same starts on any number of GPUs); `rotation` / `translation` are then the start's rigid part
+    followed by the walk's, and the dict gains `pose_starts` and `pose_best_start` (-1 where posing failed or no start has
+    a finite objective)."""
+    starts = getattr(req, "optimise_starts", 0)       # (a request-like object from before the search has no such field)
+    if starts:
+        out = gen._search_pose(req.typed_receptor, coords, n_nodes, atomic_numbers, bond_orders, starts, req.optimise_steps,
+                               0 if sample_seed is None else sample_seed, row_ids)
+    else:
+        walk = gen._optimise_pose_flex if req.optimise_flexible else gen._optimise_pose
+        out = walk(req.typed_receptor, coords, n_nodes, atomic_numbers, bond_orders, req.optimise_steps)
     dev = out["coords"].device
     x, pose, tanimoto = coords.to(dev, torch.float32), pose.to(dev, torch.float32), tanimoto.to(dev, torch.float32)
     kept = out["kept"].to(dev)
@@ -975,6 +1009,10 @@ def optimise_rows(gen, req: Request, coords: torch.Tensor, n_nodes: torch.Tensor
                     intramolecular_clash_before=torch.where(posed, out["clash_before"], nan),
                     intramolecular_clash=torch.where(posed, torch.where(moved, out["clash_after"], out["clash_before"]),
                                                      nan))
+    if starts:
+        best = out["best_start"].to(dev)
+        flex.update(pose_starts=torch.where(posed, torch.full_like(best, starts), torch.full_like(best, -1)),
+                    pose_best_start=torch.where(posed, best, torch.full_like(best, -1)))
     return dict(flex, coords=new_x, moved=moved, rotation=out["rotation"], translation=out["translation"],
                 pose=torch.where(moved.view(-1, 1), compose_pose(pose, out["rotation"], out["translation"]), pose),
                 overlay_tanimoto=torch.where(moved, rescored, tanimoto),
@@ -984,14 +1022,16 @@ def optimise_rows(gen, req: Request, coords: torch.Tensor, n_nodes: torch.Tensor
 
 
 # ----------------------------------------------------------------------------------------------- without a finisher
-def measure_tensors(gen, req: Request, res: dict) -> dict:
+def measure_tensors(gen, req: Request, res: dict, row_ids: Optional[torch.Tensor] = None,
+                    sample_seed: Optional[int] = None) -> dict:
     """Stages 1-3 on one shard's result tensors.  `res` with `x` posed and the per-sample tensors `overlay_tanimoto`,
     `pose`, `shape_tanimoto`, `receptor_clashes` (-1 where posing failed), `receptor_max_overlap` (NaN there), - posed
     into a mesh - `atoms_outside` (of the returned coordinates: counted again behind a relief or an optimisation) and -
     relieved - `relief_rmsd` (NaN where posing failed) and `receptor_clashes_before`
     (-1 there) and - optimised - `interaction_score_before`, `pose_optimisation_rmsd` (NaN where posing failed) and
     `pose_trials_kept` (-1 there) added, as far as the call asked: the spellings `handoff.measured_from_tensors` reads,
-    which cross the tensor gather."""
+    which cross the tensor gather.  `row_ids` (the rows' sample ids, default 0..B-1) and `sample_seed` key the starts of
+    `optimise_pose="search"`; nothing else reads them."""
     if req.overlay:
         ov = gen._pose(req.reference, res["x"], res["n_nodes"], req.refine_steps)
         res = dict(res, x=ov["coords"], overlay_tanimoto=ov["tanimoto"],
@@ -1004,11 +1044,11 @@ def measure_tensors(gen, req: Request, res: dict) -> dict:
                    relief_rmsd=rel["relief_rmsd"], receptor_clashes_before=rel["receptor_clashes_before"])
     if req.optimise_steps:
         opt = optimise_rows(gen, req, res["x"], res["n_nodes"], res["elements"], res["bond"], res["pose"],
-                            res["overlay_tanimoto"])
+                            res["overlay_tanimoto"], row_ids, sample_seed)
         res = dict(res, x=opt["coords"], pose=opt["pose"], overlay_tanimoto=opt["overlay_tanimoto"],
                    interaction_score_before=opt["interaction_score_before"],
                    pose_optimisation_rmsd=opt["pose_optimisation_rmsd"], pose_trials_kept=opt["pose_trials_kept"])
-        res.update({k: opt[k] for k in FLEX_RECORD_FIELDS if k in opt})
+        res.update({k: opt[k] for k in FLEX_RECORD_FIELDS + SEARCH_RECORD_FIELDS if k in opt})
     if "atoms_outside" in res and (req.relief_steps or req.optimise_steps):
         # a pocket's receptor stages moved the rows after the pose counted them: count the returned coordinates
         again = gen._atoms_outside(req.reference, res["x"], res["n_nodes"])
