@@ -14,7 +14,9 @@
 //                            butterfly per torsion.  Every lane reads the sums back, holds the same state and takes the same
 //                            branch.  No atomics.  The receptor loop, the pair arithmetic, the tile list and the rigid trial
 //                            are the shared headers' text, in the order `k_receptor_optimise` uses them, so a molecule
-//                            without a torsion gets that kernel's bits.
+//                            without a torsion gets that kernel's bits.  That part of this file is kept in step with
+//                            mcg_pose_optimise.hip BY HAND ("Shared device text", says why it is not
+//                            one body); the step constants and the entry's argument check are mcg_receptor_walk.h's.
 //   Tile list:               built once with the reach (rho0 + 2 + 8) + max_shift: a trial with an atom further than
 //                            rho0 + 2 from p in the molecule frame is rejected unevaluated.
 #include "mcg_common.h"
@@ -23,6 +25,7 @@
 #include "mcg_rigid_step.h"
 #include "mcg_receptor_tiles.h"
 #include "mcg_interaction_pair.h"
+#include "mcg_receptor_walk.h"
 #include "mcg_graph_rules.h"
 #include "mcg_ring_bonds.h"
 #include "../../include/mlconfgen_hip_flex.h"
@@ -37,6 +40,7 @@ using namespace mcg_shape;
 using namespace mcg_rigid;
 using namespace mcg_tiles;
 using namespace mcg_interaction;
+using namespace mcg_receptor_walk;   // the step constants and the argument check, shared with k_receptor_optimise
 
 constexpr int FX_MAXW = MCG_FLEX_MAX_ATOMS;
 constexpr int FX_T = MCG_FLEX_MAX_TORSIONS;
@@ -151,11 +155,6 @@ __global__ __launch_bounds__(FX_MAXW) void k_torsion_tree(
 }
 
 // ---------------------------------------------------------------------------------------------------- the walk
-constexpr float FX_STEP_ROT = 0.05f;          // initial rotation step, rad
-constexpr float FX_STEP_TRANS = 0.25f;        // initial translation step, Angstrom
-constexpr float FX_STEP_TAU = 0.1f;           // initial torsion step, rad (the torsion with the largest |tau| turns by it)
-constexpr float FX_MIN_TRANS = 0.00390625f;   // 2^-8 A: the walk ends below it
-constexpr float FX_MARGIN = 2.0f;             // an atom may leave the input's radius about p by this much, Angstrom
 constexpr int FX_SUMS = 11;                   // g1, g2, rep, hyd, hb, F[3], torque[3]
 constexpr int FX_RED = FX_SUMS + 1 + FX_T;    // ... CLASH, tau[16]
 constexpr int FX_PART = 12;                   // per wave and atom: the rigid kernel's eight, the clash energy and force
@@ -369,13 +368,13 @@ __global__ __launch_bounds__(IX_THREADS) void k_receptor_optimise_flex(
 #pragma unroll
         for (int k = 0; k < FX_T; ++k) gradient_out[(size_t)b * FX_GRAD + 6 + k] = cur[FX_SUMS + 1 + k];
     }
-    StepLengths len = {FX_STEP_ROT, FX_STEP_TRANS};
+    StepLengths len = {RW_STEP_ROT, RW_STEP_TRANS};
     float s_tau = FX_STEP_TAU;
     float turned[FX_T];
 #pragma unroll
     for (int k = 0; k < FX_T; ++k) turned[k] = 0.f;
     int trials = 0, kept = 0;
-    for (; trials < steps && !(len.trans < FX_MIN_TRANS); ++trials) {
+    for (; trials < steps && !(len.trans < RW_MIN_TRANS); ++trials) {
         float Gn[9], pn[3];
         const float fn = norm3(cur + 5), tn = norm3(cur + 8);
         const bool moves = fn > 0.f && isfinite(fn), turns = tn > 0.f && isfinite(tn);
@@ -535,16 +534,10 @@ extern "C" int mcg_receptor_optimise_flex(const float* lig_xyz, const float* lig
                                           const uint64_t* side_mask, const uint64_t* near_mask, const int32_t* n_torsions,
                                           float* coords_out, float* xform_out, float* stats_out, float* angles_out,
                                           float* gradient_out, float* trace_out, void* stream) {
-    static_assert(WALK_MAX_STEPS == 1024 && MAX_ATOMS == 64, "the bounds the message below states");
-    if (!lig_xyz || !lig_radius || !lig_type || !n_nodes_dev || !rec_xyzr || !rec_type || !clash_radius || !torsion_atoms ||
-        !side_mask || !near_mask || !n_torsions || !coords_out || !xform_out || !stats_out || !angles_out || B < 1 ||
-        B > MCG_RECEPTOR_MAX_B || N < 1 || N > MAX_ATOMS || R < 1 || R > MCG_RECEPTOR_MAX_ATOMS || steps < 0 ||
-        steps > WALK_MAX_STEPS || !(max_shift >= 0.f) || !isfinite(max_shift)) {
-        mcg_set_error("mcg_receptor_optimise_flex: bad arguments (non-null buffers, 1 <= B <= %d, 1 <= N <= 64, "
-                      "1 <= R <= %d, 0 <= steps <= 1024, max_shift finite and >= 0)", MCG_RECEPTOR_MAX_B,
-                      MCG_RECEPTOR_MAX_ATOMS);
-        return MCG_ERR_ARG;
-    }
+    const bool buffers = lig_xyz && lig_radius && lig_type && n_nodes_dev && rec_xyzr && rec_type && clash_radius &&
+                         torsion_atoms && side_mask && near_mask && n_torsions && coords_out && xform_out && stats_out &&
+                         angles_out;
+    if (!walk_args_ok("mcg_receptor_optimise_flex", buffers, B, N, R, steps, max_shift)) return MCG_ERR_ARG;
     hipLaunchKernelGGL(k_receptor_optimise_flex, dim3(B), dim3(IX_THREADS), 0, (hipStream_t)stream, lig_xyz, lig_radius,
                        lig_type, n_nodes_dev, N, (const float4*)rec_xyzr, rec_type, R, (const float4*)tile_sphere, steps,
                        max_shift, clash_radius, torsion_atoms, reinterpret_cast<const unsigned long long*>(side_mask),

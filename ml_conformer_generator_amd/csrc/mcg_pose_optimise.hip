@@ -25,12 +25,16 @@
 //                       p, so the ligand's radius about its centroid does not change, and p stays within max_shift of c.
 //                       Every pair of a tile left out has r2 >= 64 in every pose the walk can evaluate and adds nothing.
 // A molecule's outputs depend on its own atoms and the receptor arrays only: bit-identical whatever the batch, row or width.
+// `k_receptor_optimise_flex` (mcg_pose_flex.hip) repeats this walk's text with torsions added and promises this kernel's
+// bits to a molecule without a torsion: a change here is made there too ("Shared device text").  The
+// step constants and the entry's argument check are mcg_receptor_walk.h's, shared with that kernel.
 #include "mcg_common.h"
 #include "mcg_api_internal.h"
 #include "mcg_shape_grid.h"
 #include "mcg_rigid_step.h"
 #include "mcg_receptor_tiles.h"
 #include "mcg_interaction_pair.h"
+#include "mcg_receptor_walk.h"
 
 #include <math.h>
 
@@ -42,10 +46,8 @@ using namespace mcg_shape;
 using namespace mcg_rigid;           // the trial, the step lengths, the returned transform: one text for every walk
 using namespace mcg_tiles;           // the centroid and the tile list, shared by every kernel that reaches a receptor
 using namespace mcg_interaction;     // the pair arithmetic, shared with k_receptor_interactions
+using namespace mcg_receptor_walk;   // the step constants and the argument check, shared with k_receptor_optimise_flex
 
-constexpr float PO_STEP_ROT = 0.05f;          // initial rotation step, rad
-constexpr float PO_STEP_TRANS = 0.25f;        // initial translation step, Angstrom
-constexpr float PO_MIN_TRANS = 0.00390625f;   // 2^-8 A: the walk ends below it
 constexpr int PO_SUMS = 11;                   // g1, g2, rep, hyd, hb, F[3], torque[3]
 constexpr int PO_TRACE = 24;                  // F[3], torque[3], s_r, s_t, G'[9], p'[3], W', evaluated, kept, W_cur
 
@@ -177,9 +179,9 @@ __global__ __launch_bounds__(IX_THREADS) void k_receptor_optimise(
 #pragma unroll
         for (int k = 0; k < 6; ++k) gradient_out[(size_t)b * 6 + k] = cur[5 + k];
     }
-    StepLengths len = {PO_STEP_ROT, PO_STEP_TRANS};
+    StepLengths len = {RW_STEP_ROT, RW_STEP_TRANS};
     int trials = 0, kept = 0;
-    for (; trials < steps && !(len.trans < PO_MIN_TRANS); ++trials) {
+    for (; trials < steps && !(len.trans < RW_MIN_TRANS); ++trials) {
         float Gn[9], pn[3];
         const float fn = norm3(cur + 5), tn = norm3(cur + 8);
         const bool moves = fn > 0.f && isfinite(fn), turns = tn > 0.f && isfinite(tn);
@@ -267,14 +269,9 @@ extern "C" int mcg_receptor_optimise(const float* lig_xyz, const float* lig_radi
                                      const uint8_t* rec_type, int R, const float* tile_sphere, int steps, float max_shift,
                                      float* coords_out, float* xform_out, float* stats_out, float* gradient_out,
                                      float* trace_out, void* stream) {
-    static_assert(WALK_MAX_STEPS == 1024 && MAX_ATOMS == 64, "the bounds the message below states");
-    if (!lig_xyz || !lig_radius || !lig_type || !n_nodes_dev || !rec_xyzr || !rec_type || !coords_out || !xform_out ||
-        !stats_out || B < 1 || B > MCG_RECEPTOR_MAX_B || N < 1 || N > MAX_ATOMS || R < 1 || R > MCG_RECEPTOR_MAX_ATOMS ||
-        steps < 0 || steps > WALK_MAX_STEPS || !(max_shift >= 0.f) || !isfinite(max_shift)) {
-        mcg_set_error("mcg_receptor_optimise: bad arguments (non-null buffers, 1 <= B <= %d, 1 <= N <= 64, 1 <= R <= %d, "
-                      "0 <= steps <= 1024, max_shift finite and >= 0)", MCG_RECEPTOR_MAX_B, MCG_RECEPTOR_MAX_ATOMS);
-        return MCG_ERR_ARG;
-    }
+    const bool buffers = lig_xyz && lig_radius && lig_type && n_nodes_dev && rec_xyzr && rec_type && coords_out &&
+                         xform_out && stats_out;
+    if (!walk_args_ok("mcg_receptor_optimise", buffers, B, N, R, steps, max_shift)) return MCG_ERR_ARG;
     hipLaunchKernelGGL(k_receptor_optimise, dim3(B), dim3(IX_THREADS), 0, (hipStream_t)stream, lig_xyz, lig_radius,
                        lig_type, n_nodes_dev, N, (const float4*)rec_xyzr, rec_type, R, (const float4*)tile_sphere, steps,
                        max_shift, coords_out, xform_out, stats_out, gradient_out, trace_out);

@@ -3,9 +3,10 @@
 // Gram-Schmidt pass, the trial pose (`rotate_about`, `step_along`) and its shift test, the step lengths and their
 // factors, the transform a walk returns, the atom centroid and the reduction of a pose's sums.  One text, so the three
 // walks form, keep and return a trial with the same operations in the same order, and the walk that is pinned trial by
-// trial pins the text the other two run.  Contraction is off inside the bodies and every fused multiply-add is written
-// out, as in mcg_shape_grid.h.  Scalars go in by value (the centroid, the rotation axis, the components of p): in that
-// shape the helpers leave the kernels the instruction streams profiles/walk_share_isa.txt records.
+// trial pins the text the other two run (`k_receptor_optimise_flex` repeats `k_receptor_optimise`'s use of them).
+// Contraction is off inside the bodies and every fused multiply-add is written out, as in mcg_shape_grid.h.  Scalars go
+// in by value (the centroid, the rotation axis, the components of p): in that shape the helpers leave the kernels the
+// instruction streams profiles/walk_share_isa.txt records.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -224,7 +224,7 @@ def interaction_scores(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, at
 # ----------------------------------------------------------------------------------------------- optimised pose
 OPTIMISE_STEPS = 64             # what `optimise_pose=True` stands for
 OPTIMISE_MAX_SHIFT = 2.0        # angstrom the centroid may move from where the walk started
-MAX_OPTIMISE_STEPS = mcg_receptor.MAX_RELIEF_STEPS     # csrc/mcg_pose_optimise.hip PO_MAX_STEPS
+MAX_OPTIMISE_STEPS = mcg_receptor.MAX_RELIEF_STEPS     # csrc/mcg_rigid_step.h WALK_MAX_STEPS
 TRACE_WIDTH = 24                # F[3], torque[3], s_r, s_t, G'[9], p'[3], W', evaluated, kept, W of the current pose
 OPTIMISE_REFUSAL_WITH_FINISHER = ("optimise_pose cannot be combined with a finisher (RDKit's or a custom one): the "
                                   "values go onto the GeneratedMolecule records")
@@ -251,33 +251,58 @@ def optimise_typed(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, radii:
     for name, t, shape in (("radii", radii, (B, N)), ("types", types, (B, N))):
         if tuple(t.shape) != shape:
             raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
-    return _optimise_typed(prepared, coords, n_nodes, B, N, radii, types, steps, max_shift, skip_tiles, dev, trace)
+    return _walk_typed(prepared, coords, n_nodes, B, N, radii, types, steps, max_shift, skip_tiles, dev, trace)
 
 
-def _optimise_typed(prepared, coords, n_nodes, B, N, radii, types, steps, max_shift, skip_tiles, dev, trace
-                    ) -> Dict[str, torch.Tensor]:
-    """`optimise_typed` behind its checks."""
+def _walk_typed(prepared, coords, n_nodes, B, N, radii, types, steps, max_shift, skip_tiles, dev, trace, clash=None,
+                tree=None) -> Dict[str, torch.Tensor]:
+    """The walk's launch behind its checks: `mcg_receptor_optimise`, or - with `clash` [B,N] and `tree`, a `torsion_tree`
+    result for the same rows - `mcg_receptor_optimise_flex`.  Device tensors as the kernel writes them
+    (include/mlconfgen_hip.h, include/mlconfgen_hip_flex.h): coords, xform, stats, gradient, with a tree angles [B,16], with
+    `trace` trace.  B or N of 0 launches nothing and returns the rows as they came."""
+    flex = tree is not None
+    name = "mcg_receptor_optimise_flex" if flex else "mcg_receptor_optimise"
     x = coords.to(dev, torch.float32).contiguous()
-    out = torch.empty_like(x) if B > 0 and N > 0 else x.clone()
-    xform = torch.zeros(B, 12, device=dev)
-    stats = torch.zeros(B, 8, device=dev)
-    gradient = torch.zeros(B, 6, device=dev)
-    tr = torch.zeros(B, steps, TRACE_WIDTH, device=dev) if trace else None
+    res = dict(coords=torch.empty_like(x) if B > 0 and N > 0 else x.clone(), xform=torch.zeros(B, 12, device=dev),
+               stats=torch.zeros(B, 12 if flex else 8, device=dev))
+    if flex:
+        res["angles"] = torch.zeros(B, FLEX_MAX_TORSIONS, device=dev)
+    res["gradient"] = torch.zeros(B, 6 + FLEX_MAX_TORSIONS if flex else 6, device=dev)
+    if trace:
+        res["trace"] = torch.zeros(B, steps, FLEX_TRACE_WIDTH if flex else TRACE_WIDTH, device=dev)
     if B > 0 and N > 0:
         lig_r = radii.to(dev, torch.float32).contiguous()
         lig_t = types.to(dev, torch.uint8).contiguous()
         nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B).contiguous()
         rec, rec_t = prepared.xyzr.to(dev), prepared.types.to(dev)
         spheres = prepared.spheres.to(dev) if skip_tiles else None
-        _lib.check(_lib.lib().mcg_receptor_optimise(
+        torsions = ()
+        if flex:
+            torsions = (clash.to(dev, torch.float32).contiguous(), tree["torsion_atoms"], tree["side_mask"],
+                        tree["near_mask"], tree["counts"][:, 1].contiguous())
+        outs = [res[k] for k in ("coords", "xform", "stats", "angles", "gradient") if k in res] + [res.get("trace")]
+        _lib.check(getattr(_lib.lib(), name)(
             _lib.dptr(x), _lib.dptr(lig_r), _lib.dptr(lig_t), _lib.dptr(nn), B, N, _lib.dptr(rec), _lib.dptr(rec_t),
-            int(rec.shape[0]), _lib.dptr(spheres), steps, max_shift, _lib.dptr(out), _lib.dptr(xform), _lib.dptr(stats),
-            _lib.dptr(gradient), _lib.dptr(tr), _lib.current_stream_ptr(dev)), "mcg_receptor_optimise")
+            int(rec.shape[0]), _lib.dptr(spheres), steps, max_shift, *map(_lib.dptr, torsions), *map(_lib.dptr, outs),
+            _lib.current_stream_ptr(dev)), name)
     else:
-        xform[:, 0] = xform[:, 4] = xform[:, 8] = 1.0
-    res = dict(coords=out, xform=xform, stats=stats, gradient=gradient)
-    if trace:
-        res["trace"] = tr
+        res["xform"][:, 0] = res["xform"][:, 4] = res["xform"][:, 8] = 1.0
+    return res
+
+
+def _pose_result(coords, xform, stats, gradient, tree=None, angles=None, best=None) -> Dict[str, torch.Tensor]:
+    """What `optimise_pose` returns, from a walk's `xform` [B,12] and `stats`; with `tree` and `angles` the torsion and
+    clash fields of the flexible walk too; `best` [B]: the winning start of a search, which also counts as a move."""
+    ok = torch.isfinite(stats[:, 0])
+    count = lambda col: torch.where(ok, stats[:, col], torch.full_like(stats[:, col], -1.0)).to(torch.int32)   # noqa: E731
+    moved = stats[:, 3] > 0 if best is None else (stats[:, 3] > 0) | (best > 0)
+    res = dict(coords=coords, rotation=xform[:, :9].reshape(len(xform), 3, 3), translation=xform[:, 9:], moved=ok & moved,
+               weighted_before=stats[:, 0], weighted_after=stats[:, 1], trials=count(2), kept=count(3), rmsd=stats[:, 4],
+               gradient=gradient)
+    if tree is not None:
+        res.update(torsions=count(8), torsions_found=tree["counts"][:, 0], torsion_angles=angles,
+                   torsion_atoms=tree["torsion_atoms"], clash_before=stats[:, 6], clash_after=stats[:, 7],
+                   conformer_rmsd=stats[:, 9], step_trans=stats[:, 5])
     return res
 
 
@@ -329,14 +354,9 @@ def optimise_pose(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_
     types = torch.zeros(B, N, dtype=torch.uint8, device=dev)
     if B > 0 and N > 0:
         types = ligand_types(z[:, :N], bonds[:, :N, :N], n_nodes, dev)
-    out = _optimise_typed(prepared, coords, n_nodes, B, N, interaction_radii(z[:, :N].to(dev)), types, steps, max_shift,
-                          True, dev, trace)
-    stats, xform = out["stats"], out["xform"]
-    ok = torch.isfinite(stats[:, 0])
-    count = lambda col: torch.where(ok, stats[:, col], torch.full_like(stats[:, col], -1.0)).to(torch.int32)
-    res = dict(coords=out["coords"], rotation=xform[:, :9].reshape(B, 3, 3), translation=xform[:, 9:],
-               moved=ok & (stats[:, 3] > 0), weighted_before=stats[:, 0], weighted_after=stats[:, 1], trials=count(2),
-               kept=count(3), rmsd=stats[:, 4], gradient=out["gradient"])
+    out = _walk_typed(prepared, coords, n_nodes, B, N, interaction_radii(z[:, :N].to(dev)), types, steps, max_shift, True,
+                      dev, trace)
+    res = _pose_result(out["coords"], out["xform"], out["stats"], out["gradient"])
     if trace:
         res["trace"] = out["trace"]
     return res
@@ -392,39 +412,6 @@ def torsion_tree(atomic_numbers: torch.Tensor, bond_orders: torch.Tensor, n_node
             _lib.dptr(out["torsion_atoms"][lo:hi]), _lib.dptr(out["side_mask"][lo:hi]), _lib.dptr(out["near_mask"][lo:hi]),
             _lib.dptr(out["counts"][lo:hi]), _lib.current_stream_ptr(dev)), "mcg_torsion_tree")
     return out
-
-
-def _optimise_flex_typed(prepared, coords, n_nodes, B, N, radii, types, clash, tree, steps, max_shift, skip_tiles, dev,
-                         trace) -> Dict[str, torch.Tensor]:
-    """The `mcg_receptor_optimise_flex` launch behind its checks: device tensors as the kernel writes them
-    (include/mlconfgen_hip_flex.h).  B or N of 0 launches nothing and returns the rows as they came."""
-    x = coords.to(dev, torch.float32).contiguous()
-    out = torch.empty_like(x) if B > 0 and N > 0 else x.clone()
-    xform = torch.zeros(B, 12, device=dev)
-    stats = torch.zeros(B, 12, device=dev)
-    angles = torch.zeros(B, FLEX_MAX_TORSIONS, device=dev)
-    gradient = torch.zeros(B, 6 + FLEX_MAX_TORSIONS, device=dev)
-    tr = torch.zeros(B, steps, FLEX_TRACE_WIDTH, device=dev) if trace else None
-    if B > 0 and N > 0:
-        lig_r = radii.to(dev, torch.float32).contiguous()
-        lig_t = types.to(dev, torch.uint8).contiguous()
-        cl = clash.to(dev, torch.float32).contiguous()
-        nn = torch.as_tensor(n_nodes).to(dev, torch.int32).reshape(B).contiguous()
-        rec, rec_t = prepared.xyzr.to(dev), prepared.types.to(dev)
-        spheres = prepared.spheres.to(dev) if skip_tiles else None
-        used = tree["counts"][:, 1].contiguous()
-        _lib.check(_lib.lib().mcg_receptor_optimise_flex(
-            _lib.dptr(x), _lib.dptr(lig_r), _lib.dptr(lig_t), _lib.dptr(nn), B, N, _lib.dptr(rec), _lib.dptr(rec_t),
-            int(rec.shape[0]), _lib.dptr(spheres), steps, max_shift, _lib.dptr(cl), _lib.dptr(tree["torsion_atoms"]),
-            _lib.dptr(tree["side_mask"]), _lib.dptr(tree["near_mask"]), _lib.dptr(used), _lib.dptr(out), _lib.dptr(xform),
-            _lib.dptr(stats), _lib.dptr(angles), _lib.dptr(gradient), _lib.dptr(tr), _lib.current_stream_ptr(dev)),
-            "mcg_receptor_optimise_flex")
-    else:
-        xform[:, 0] = xform[:, 4] = xform[:, 8] = 1.0
-    res = dict(coords=out, xform=xform, stats=stats, angles=angles, gradient=gradient)
-    if trace:
-        res["trace"] = tr
-    return res
 
 
 @torch.no_grad()
@@ -487,16 +474,9 @@ def optimise_pose_flexible(receptor, coords: torch.Tensor, n_nodes: torch.Tensor
     if B > 0 and N > 0:
         types = ligand_types(z[:, :N], bonds[:, :N, :N], n_nodes, dev)
         tree = torsion_tree(z[:, :N], bonds[:, :N, :N], n_nodes, dev, check=False)
-    out = _optimise_flex_typed(prepared, coords, n_nodes, B, N, interaction_radii(z[:, :N].to(dev)), types,
-                               clash_radii(z[:, :N].to(dev)), tree, steps, max_shift, skip_tiles, dev, trace)
-    stats, xform = out["stats"], out["xform"]
-    ok = torch.isfinite(stats[:, 0])
-    count = lambda col: torch.where(ok, stats[:, col], torch.full_like(stats[:, col], -1.0)).to(torch.int32)
-    res = dict(coords=out["coords"], rotation=xform[:, :9].reshape(B, 3, 3), translation=xform[:, 9:],
-               moved=ok & (stats[:, 3] > 0), weighted_before=stats[:, 0], weighted_after=stats[:, 1], trials=count(2),
-               kept=count(3), rmsd=stats[:, 4], gradient=out["gradient"], torsions=count(8),
-               torsions_found=tree["counts"][:, 0], torsion_angles=out["angles"], torsion_atoms=tree["torsion_atoms"],
-               clash_before=stats[:, 6], clash_after=stats[:, 7], conformer_rmsd=stats[:, 9], step_trans=stats[:, 5])
+    out = _walk_typed(prepared, coords, n_nodes, B, N, interaction_radii(z[:, :N].to(dev)), types, steps, max_shift,
+                      skip_tiles, dev, trace, clash_radii(z[:, :N].to(dev)), tree)
+    res = _pose_result(out["coords"], out["xform"], out["stats"], out["gradient"], tree, out["angles"])
     if trace:
         res["trace"] = out["trace"]
     return res
@@ -520,6 +500,17 @@ def check_starts(value, name: str = "starts") -> int:
     return int(value)
 
 
+def _check_search_options(starts, spread, max_turn, seed):
+    """(`starts`, `spread`, `max_turn`, `seed`) as `search_pose` takes them, else ValueError."""
+    from . import seeding
+    starts = check_starts(starts)
+    spread = _args.check_real("spread", spread, 0.0)
+    max_turn = _args.check_real("max_turn", max_turn, 0.0)
+    if max_turn > math.pi:
+        raise ValueError(f"max_turn must lie in [0, pi], got {max_turn!r}")
+    return starts, spread, max_turn, seeding.check_seed(seed)
+
+
 def _repeat_tree(tree: Dict[str, torch.Tensor], idx: torch.Tensor) -> Dict[str, torch.Tensor]:
     return {k: tree[k].index_select(0, idx).contiguous() for k in ("torsion_atoms", "side_mask", "near_mask", "counts")}
 
@@ -533,12 +524,7 @@ def pose_starts(coords: torch.Tensor, n_nodes: torch.Tensor, tree: Dict[str, tor
     tensors as the kernel writes them: coords [B,S,N,3], xform [B,S,12], angles [B,S,16] and - `params` - params [B,S,24].
     Start 0 is the input's bits.  The checks are `search_pose`'s; B >= 1, N >= 1."""
     from . import seeding
-    starts = check_starts(starts)
-    spread = _args.check_real("spread", spread, 0.0)
-    max_turn = _args.check_real("max_turn", max_turn, 0.0)
-    if max_turn > math.pi:
-        raise ValueError(f"max_turn must lie in [0, pi], got {max_turn!r}")
-    seed = seeding.check_seed(seed)
+    starts, spread, max_turn, seed = _check_search_options(starts, spread, max_turn, seed)
     dev = _args.resolve_device(device, coords)
     B, N, _ = _args.ligand_arguments(coords, n_nodes, None, MAX_ATOMS, MAX_BATCH, "the pose search takes")
     ids = seeding.check_sample_ids(sample_ids, B).to(dev, torch.int64).contiguous()
@@ -635,12 +621,7 @@ def search_pose(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_nu
     prepared = prepare_receptor(receptor)
     steps = mcg_receptor.check_relief_steps(steps)
     max_shift = check_max_shift(max_shift)
-    starts = check_starts(starts)
-    spread = _args.check_real("spread", spread, 0.0)
-    max_turn = _args.check_real("max_turn", max_turn, 0.0)
-    if max_turn > math.pi:
-        raise ValueError(f"max_turn must lie in [0, pi], got {max_turn!r}")
-    seed = seeding.check_seed(seed)
+    starts, spread, max_turn, seed = _check_search_options(starts, spread, max_turn, seed)
     dev = _args.resolve_device(device, coords)
     B, N, z, bonds = _posed_graphs(coords, n_nodes, atomic_numbers, bond_orders, "pose optimisation takes")
     ids = seeding.check_sample_ids(torch.arange(B) if sample_ids is None else sample_ids, B)
@@ -662,23 +643,16 @@ def search_pose(receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_nu
     for lo in range(0, B * S, MAX_BATCH):
         hi = min(B * S, lo + MAX_BATCH)
         pick = idx[lo:hi]
-        parts.append(_optimise_flex_typed(prepared, rows[lo:hi], nn.index_select(0, pick), hi - lo, N,
-                                          radii.index_select(0, pick), types.index_select(0, pick),
-                                          clash.index_select(0, pick), _repeat_tree(tree, pick), steps, max_shift,
-                                          skip_tiles, dev, False))
+        parts.append(_walk_typed(prepared, rows[lo:hi], nn.index_select(0, pick), hi - lo, N, radii.index_select(0, pick),
+                                 types.index_select(0, pick), steps, max_shift, skip_tiles, dev, False,
+                                 clash.index_select(0, pick), _repeat_tree(tree, pick)))
     walk = {k: torch.cat([p[k] for p in parts], dim=0) for k in ("coords", "xform", "stats", "angles", "gradient")}
     shaped = lambda k: walk[k].reshape(B, S, *walk[k].shape[1:])                           # noqa: E731
     out = select_starts(shaped("coords"), shaped("xform"), shaped("stats"), shaped("angles"), st["xform"], st["angles"],
                         coords, nn, dev)
-    stats, xform, best = out["stats"], out["xform"], out["best_start"]
-    ok = torch.isfinite(stats[:, 0])
-    count = lambda col: torch.where(ok, stats[:, col], torch.full_like(stats[:, col], -1.0)).to(torch.int32)
-    return dict(coords=out["coords"], rotation=xform[:, :9].reshape(B, 3, 3), translation=xform[:, 9:],
-                moved=ok & ((stats[:, 3] > 0) | (best > 0)), weighted_before=stats[:, 0], weighted_after=stats[:, 1],
-                trials=count(2), kept=count(3), rmsd=stats[:, 4], gradient=shaped("gradient")[:, 0].contiguous(),
-                torsions=count(8), torsions_found=tree["counts"][:, 0], torsion_angles=out["angles"],
-                torsion_atoms=tree["torsion_atoms"], clash_before=stats[:, 6], clash_after=stats[:, 7],
-                conformer_rmsd=stats[:, 9], step_trans=stats[:, 5], best_start=best, start_scores=out["start_scores"],
+    res = _pose_result(out["coords"], out["xform"], out["stats"], shaped("gradient")[:, 0].contiguous(), tree, out["angles"],
+                       out["best_start"])
+    return dict(res, best_start=out["best_start"], start_scores=out["start_scores"],
                 starts=dict(coords=st["coords"], xform=st["xform"], angles=st["angles"], walk_coords=shaped("coords"),
                             walk_xform=shaped("xform"), walk_stats=shaped("stats"), walk_angles=shaped("angles")))
 

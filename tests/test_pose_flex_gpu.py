@@ -88,9 +88,9 @@ def _want_tree(g, width):
     return atoms, side.view(np.int64), near.view(np.int64), counts
 
 
-def _launch(graphs, width, case, steps, max_shift=SHIFT, skip_tiles=True, coords=None, receptor=None):
+def _launch(graphs, width, case, steps, max_shift=SHIFT, skip_tiles=True, coords=None, receptor=None, edit_tree=None):
     """`mcg_receptor_optimise_flex` itself on graphs against one receptor, every output inside sentinels; host tensors.
-    The tree is `interactions.torsion_tree`'s (held to the restatement by the tree tests)."""
+    The tree is `interactions.torsion_tree`'s (held to the restatement by the tree tests), after `edit_tree(tree)`."""
     prepared = IX.prepare_receptor(receptor if receptor is not None else case.receptor)
     B = len(graphs)
     z, bonds, n, _ = FC.padded(graphs, width)
@@ -104,6 +104,8 @@ def _launch(graphs, width, case, steps, max_shift=SHIFT, skip_tiles=True, coords
         if coords is not None and coords[b] is not None:
             x[b, : g.n] = coords[b]
     tree = IX.torsion_tree(torch.from_numpy(z), torch.from_numpy(bonds), torch.from_numpy(n), DEV)
+    if edit_tree is not None:
+        edit_tree(tree)
     xd, rd, td, cd, nd = (torch.from_numpy(v).to(DEV).contiguous() for v in (x, r, t, cl, n))
     rec, rec_t = prepared.xyzr.to(DEV), prepared.types.to(DEV)
     spheres = prepared.spheres.to(DEV) if skip_tiles else None
@@ -341,6 +343,49 @@ def test_a_molecule_without_a_torsion_walks_as_the_rigid_entry_walks_it(name):
     assert torch.equal(_bits(flex["stats"][:, 6]), _bits(flex["stats"][:, 7]))               # CLASH kept its bits
     assert int(flex["stats"][0, 3]) > 0 or name == "one_atom"
     assert float(flex["stats"][0, 6]) > 0 or name != "stacked_benzenes"
+
+
+def _walked_as_rigid(flex, rigid, n, what, row_f=0, row_r=0):
+    """The fields `test_a_molecule_without_a_torsion_walks_as_the_rigid_entry_walks_it` compares, trace included."""
+    assert int(flex["stats"][row_f, 8]) == 0, what
+    assert torch.equal(_bits(flex["coords"][row_f, :n]), _bits(rigid["coords"][row_r, :n])), what
+    assert torch.equal(_bits(flex["xform"][row_f]), _bits(rigid["xform"][row_r])), what
+    assert torch.equal(_bits(flex["stats"][row_f, :6]), _bits(rigid["stats"][row_r, :6])), what
+    assert torch.equal(_bits(flex["gradient"][row_f, :6]), _bits(rigid["gradient"][row_r])), what
+    assert torch.equal(_bits(flex["trace"][row_f, :, :24]), _bits(rigid["trace"][row_r])), what
+    assert not flex["angles"][row_f].any() and not flex["gradient"][row_f, 6:].any() and float(flex["stats"][row_f, 9]) == 0
+    assert torch.equal(_bits(flex["stats"][row_f, 6]), _bits(flex["stats"][row_f, 7])), what      # CLASH kept its bits
+
+
+@pytest.mark.parametrize("cut", ["n_torsions_0", "slot_0_names_an_atom_beyond_n"])
+def test_a_row_cut_to_no_torsion_walks_as_the_rigid_entry_walks_it(cut):
+    """The flexible kernel with a torsion count the kernel's own slot check cuts to 0 at run time, against the rigid
+    kernel, where the torsion state is compiled out."""
+    g = BY_NAME["isopentylbenzene"]
+    case = _receptor_of(g)
+    assert len(g.torsions) > 0
+
+    def edit(tree):
+        if cut == "n_torsions_0":
+            tree["counts"][:, 1] = 0
+        else:
+            tree["torsion_atoms"][:, 0, 1] = g.n
+
+    flex = _launch([g], g.n, case, 64, edit_tree=edit)
+    rigid = _rigid([g], g.n, case, 64)
+    _walked_as_rigid(flex, rigid, g.n, cut)
+    assert int(flex["stats"][0, 3]) > 0
+
+
+def test_a_batch_of_a_flexible_a_rigid_and_an_empty_row():
+    """Nothing of a row's torsion state reaches the next row through the shared LDS struct."""
+    case, steps = RECEPTORS[2], 12
+    hexane, toluene = BY_NAME["hexane"], BY_NAME["toluene"]
+    batch = _launch([hexane, toluene, BY_NAME["empty"]], 41, case, steps)
+    for row, g in ((0, hexane), (1, toluene)):
+        _same(batch, _launch([g], 41, case, steps), g.n, ("batch of three", g.name), row, 0, steps)
+    _walked_as_rigid(batch, _rigid([toluene], 41, case, steps), toluene.n, "toluene beside hexane", 1, 0)
+    assert int(batch["stats"][0, 8]) == len(hexane.torsions) > 0 and bool(torch.isnan(batch["stats"][2]).all())
 
 
 def test_bits_do_not_depend_on_batch_row_width_or_tiles():

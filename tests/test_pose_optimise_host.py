@@ -423,8 +423,19 @@ def test_the_shared_text_lives_in_one_place():
         text = read(name)
         assert '#include "mcg_receptor_tiles.h"' in text and "build_tile_list(" in text, name
     assert "mcg_receptor_tiles.h" in read("Makefile")
-    # the walk's factors and the tile test's slack are defined once (GR_*: the geometry relaxation's own descent)
-    defined = sorted((const, name) for name in sources
-                     for const in re.findall(r"\b(\w*(?:GROW|SHRINK|SLACK)\w*)\s*=[^=]", read(name)) if not const.startswith("GR_"))
-    assert defined == [("TILE_SLACK_ABS", "mcg_receptor_tiles.h"), ("TILE_SLACK_REL", "mcg_receptor_tiles.h"),
-                       ("WALK_GROW", "mcg_rigid_step.h"), ("WALK_SHRINK", "mcg_rigid_step.h")], defined
+    # the two receptor pose walks: their step constants and their entries' argument check stand in mcg_receptor_walk.h
+    for name in ("mcg_pose_optimise.hip", "mcg_pose_flex.hip"):
+        text = read(name)
+        assert '#include "mcg_receptor_walk.h"' in text and "walk_args_ok(" in text and "max_shift finite" not in text, name
+    assert "bad arguments (non-null buffers" in read("mcg_receptor_walk.h")
+    assert "mcg_receptor_walk.h" in re.search(r"^HDRS = (.*(?:\\\n.*)*)", read("Makefile"), re.M).group(1)
+    # the walks' factors, the tile test's slack and each walk's first and last step lengths are defined once (GR_*: the
+    # geometry relaxation's own descent; RF_*, RL_*: the refined overlay's and the relief walk's own lengths)
+    once = re.compile(r"\b(\w*(?:GROW|SHRINK|SLACK|STEP_ROT|STEP_TRANS|MIN_TRANS)\w*)\s*=[^=]")
+    defined = sorted((const, name) for name in sources for const in once.findall(read(name)) if not const.startswith("GR_"))
+    assert defined == [("RF_STEP_ROT", "mcg_shape_refine.hip"), ("RF_STEP_TRANS", "mcg_shape_refine.hip"),
+                       ("RL_STEP_ROT", "mcg_receptor_relief.hip"), ("RL_STEP_TRANS", "mcg_receptor_relief.hip"),
+                       ("RW_MIN_TRANS", "mcg_receptor_walk.h"), ("RW_STEP_ROT", "mcg_receptor_walk.h"),
+                       ("RW_STEP_TRANS", "mcg_receptor_walk.h"), ("TILE_SLACK_ABS", "mcg_receptor_tiles.h"),
+                       ("TILE_SLACK_REL", "mcg_receptor_tiles.h"), ("WALK_GROW", "mcg_rigid_step.h"),
+                       ("WALK_SHRINK", "mcg_rigid_step.h")], defined

@@ -42,8 +42,7 @@ def rigid():
 
 
 def flexible():
-    return IX._optimise_flex_typed(on_device, x, nn, B, N, radii, types, clash, tree, STEPS, IX.OPTIMISE_MAX_SHIFT, True, dev,
-                                   False)
+    return IX._walk_typed(on_device, x, nn, B, N, radii, types, STEPS, IX.OPTIMISE_MAX_SHIFT, True, dev, False, clash, tree)
 
 
 def timed(call):

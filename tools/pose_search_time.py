@@ -51,8 +51,8 @@ rep = dict(nn=nn[pick].contiguous(), radii=IX.interaction_radii(z)[pick].contigu
 
 
 def walk_alone():
-    return IX._optimise_flex_typed(on_device, rows, rep["nn"], B * S, N, rep["radii"], rep["types"], rep["clash"], rep["tree"],
-                                   STEPS, IX.OPTIMISE_MAX_SHIFT, True, dev, False)
+    return IX._walk_typed(on_device, rows, rep["nn"], B * S, N, rep["radii"], rep["types"], STEPS, IX.OPTIMISE_MAX_SHIFT, True,
+                          dev, False, rep["clash"], rep["tree"])
 
 
 def starts_alone():

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Every output bit of the receptor and rigid-body walk entries (`mcg_receptor_relieve`, `mcg_receptor_optimise`,
-`mcg_receptor_interactions`, `mcg_shape_overlay_refined`) over the tests' own case sets, for comparing two builds of the
-library (MCG_LIB_PATH selects one):
+`mcg_receptor_interactions`, `mcg_shape_overlay_refined`, `mcg_torsion_tree` + `mcg_receptor_optimise_flex`, the pose
+search) over the tests' own case sets, for comparing two builds of the library (MCG_LIB_PATH selects one):
 
   MCG_LIB_PATH=<a.so> python tools/walk_bits.py --out a.npz      one MI355X, a fresh process per library
   MCG_LIB_PATH=<b.so> python tools/walk_bits.py --out b.npz
@@ -10,8 +10,10 @@ library (MCG_LIB_PATH selects one):
 The inputs are `relief_ref.cases()` (steps 0, 1, 32; padded widths n, 41, 64; tile skipping on and off; with the
 gradient), `pose_optimise_ref.cases()` (steps 0, 1, 8, 64 with the trace; the same widths and skipping), the interaction
 cases and hand pairs, the golden pairs of the refined overlay (steps 0 and 64, with the objective and the refined scores),
-and per entry one batch of 70 mixed-size rows with one empty and one non-finite row.  Arrays are compared as int32 views,
-so NaN rows compare by their bits too."""
+`flex_cases.cases()` through the tree and the flexible walk (steps, widths and skipping as the optimiser's, with the trace),
+a few of the search tests' pools through `search_pose` with 1 and 5 starts (every returned tensor, `starts` included), and
+per entry one batch of 70 mixed-size rows with one empty and one non-finite row.  `--parts` dumps some entries only.
+Arrays are compared as int32 views, so NaN rows compare by their bits too."""
 import argparse
 import os
 import sys
@@ -174,6 +176,69 @@ def dump_refine(out, dev):
         run("batch70", golden["xyz_ceyyag"].to(torch.float32), x, n, steps)
 
 
+FLEX_OFFSET = np.array([0.6, -0.3, 0.2])      # out of the middle of the pocket, as the flexible-pose tests place a graph
+
+
+def _graph_batch(graphs, width, spoil=None):
+    """(coords, n_nodes, atomic numbers, bond codes) of `flex_cases` graphs placed as the flexible-pose tests place them;
+    `spoil`: a row that gets one non-finite coordinate."""
+    import torch
+    import flex_cases as FC
+    z, bonds, n, _ = FC.padded(graphs, width)
+    x = np.zeros((len(graphs), width, 3), dtype=np.float32)
+    for b, g in enumerate(graphs):
+        if g.n:
+            x[b, : g.n] = (g.x.astype(np.float64) - g.x.astype(np.float64).mean(axis=0) + FLEX_OFFSET).astype(np.float32)
+    if spoil is not None:
+        x[spoil, min(4, graphs[spoil].n - 1), 1] = np.float32("inf")
+    return tuple(torch.from_numpy(v) for v in (x, n, z, bonds))
+
+
+def dump_flex(out, dev):
+    import flex_cases as FC
+    import interactions_ref as IR
+    from ml_conformer_generator_amd import interactions as IX
+    receptors = IR.cases()
+    graphs = FC.cases()
+    for g in graphs:
+        # each graph in its own receptor, by the flexible-pose tests' rule: 1, 255, 256, 257, 4 097 atoms and the pockets
+        prepared = IX.prepare_receptor(receptors[(2, 4, 5, 6, 7, 8, 3)[sum(map(ord, g.name)) % 7]].receptor)
+        for width in _widths(g.n):
+            x, n, z, bonds = _graph_batch([g], width)
+            for k, v in IX.torsion_tree(z, bonds, n, dev).items():
+                out[f"flex/{g.name}/w{width}/tree/{k}"] = _bits(v)
+            for steps in (0, 1, 8, 64):
+                for skip in (True, False):
+                    got = IX.optimise_pose_flexible(prepared, x, n, z, bonds, steps, 2.0, dev, trace=True, skip_tiles=skip)
+                    for k, v in got.items():
+                        out[f"flex/{g.name}/steps{steps}/w{width}/skip{int(skip)}/{k}"] = _bits(v)
+    pool = [g for g in graphs if 1 <= g.n <= 41]
+    batch = [pool[(3 * k) % len(pool)] for k in range(70)]
+    batch[53] = FC.by_name()["empty"]
+    x, n, z, bonds = _graph_batch(batch, 41, spoil=11)
+    got = IX.optimise_pose_flexible(receptors[2].receptor, x, n, z, bonds, 64, 2.0, dev, trace=True)
+    for k, v in got.items():
+        out[f"flex/batch70/{k}"] = _bits(v)
+
+
+def dump_search(out, dev):
+    import flex_cases as FC
+    import interactions_ref as IR
+    from ml_conformer_generator_amd import interactions as IX
+    by_name, pocket = FC.by_name(), IR.cases()[5].receptor
+    pools = (("pool5", ("hexane", "isopentylbenzene", "toluene", "folded_heptane", "empty"), 14, 6, 3, None),
+             ("pool8", ("hexane", "isopentylbenzene", "toluene", "folded_heptane", "empty", "biphenyl", "c20", "one_atom"),
+              20, 8, 5, 5),
+             ("pool3", ("hexane", "toluene", "isopentylbenzene"), 11, 64, 9, None))
+    for tag, names, width, steps, seed, spoil in pools:
+        x, n, z, bonds = _graph_batch([by_name[k] for k in names], width, spoil)
+        for S in (1, 5):
+            got = IX.search_pose(pocket, x, n, z, bonds, starts=S, steps=steps, seed=seed, device=dev)
+            for k, v in got.items():
+                for kk, vv in (v.items() if isinstance(v, dict) else ((None, v),)):
+                    out[f"search/{tag}/S{S}/{k}" + (f"/{kk}" if kk else "")] = _bits(vv)
+
+
 def compare(a_path, b_path):
     a, b = np.load(a_path), np.load(b_path)
     worst = 0
@@ -190,10 +255,15 @@ def compare(a_path, b_path):
     return worst
 
 
+PARTS = dict(interactions=dump_interactions, relieve=dump_relief, optimise=dump_optimise, refine=dump_refine, flex=dump_flex,
+             search=dump_search)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", help="write every output to this .npz")
     ap.add_argument("--compare", nargs=2, metavar=("A", "B"), help="compare two dumps, no GPU")
+    ap.add_argument("--parts", nargs="+", choices=sorted(PARTS), default=sorted(PARTS), help="the entries to dump")
     args = ap.parse_args()
     if args.compare:
         sys.exit(compare(*args.compare))
@@ -202,7 +272,7 @@ def main():
     import torch
     dev = torch.device("cuda:0")
     out = {}
-    for part in (dump_interactions, dump_relief, dump_optimise, dump_refine):
+    for part in (PARTS[k] for k in args.parts):
         part(out, dev)
         torch.cuda.synchronize()
         print(f"{part.__name__}: {len(out)} arrays so far", file=sys.stderr, flush=True)
