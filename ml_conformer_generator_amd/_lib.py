@@ -119,6 +119,13 @@ SEARCH_SIGNATURES: Dict[str, tuple] = {
     "mcg_pose_search_select": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/mlconfgen_hip_contacts.h one to one (a fifth public header: DESIGN.md section 6,
+# "Receptor contacts")
+CONTACT_SIGNATURES: Dict[str, tuple] = {
+    "mcg_receptor_contacts": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp]),
+}
+
 
 class PlanOpts(C.Structure):
     """`mcg_plan_opts` (include/mlconfgen_hip.h): zero-initialised = the library's defaults."""
@@ -170,7 +177,7 @@ def lib():
     import torch  # noqa: F401  - loads the process's HIP runtime first (same SONAME as ours)
     handle = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in (list(SIGNATURES.items()) + list(FLEX_SIGNATURES.items()) + list(POCKET_SIGNATURES.items())
-                              + list(SEARCH_SIGNATURES.items())):
+                              + list(SEARCH_SIGNATURES.items()) + list(CONTACT_SIGNATURES.items())):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

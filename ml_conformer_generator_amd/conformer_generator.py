@@ -437,6 +437,15 @@ class MLConformerGenerator(torch.nn.Module):
         return mcg_interactions.interaction_scores(receptor, coords, n_nodes, atomic_numbers, bond_orders,
                                                    device=self.device, check=False)
 
+    def _contact_fingerprint(self, receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_numbers: torch.Tensor,
+                             bond_orders: torch.Tensor, reference=None) -> dict:
+        """The contact fingerprints of posed, padded molecules with the call's grouped receptor - a
+        `contacts.prepare_receptor` result - and, with `reference` (groups, kinds), their comparison with it
+        (`contacts.contact_fingerprint`, device tensors)."""
+        from . import contacts as mcg_contacts
+        return mcg_contacts.contact_fingerprint(receptor, coords, n_nodes, atomic_numbers, bond_orders, reference=reference,
+                                                device=self.device)
+
     def _optimise_pose(self, receptor, coords: torch.Tensor, n_nodes: torch.Tensor, atomic_numbers: torch.Tensor,
                        bond_orders: torch.Tensor, steps: int) -> dict:
         """Padded posed heavy-atom coordinates moved as rigid bodies downhill on the interaction score with the call's
@@ -904,6 +913,18 @@ class MLConformerGenerator(torch.nn.Module):
         element rules for a (coords, atomic_numbers) pair or a Mol, or the explicit third element of a (coords,
         atomic_numbers, types) triple - once per call; one warning counts the N, O and metal atoms outside the table.  The
         step runs behind the gather, beside the pharmacophore step, in one launch.
+        `interaction_scores="contacts"` does everything `True` does plus the contact fingerprint: WHICH residues the
+        returned coordinates touch, with which kind of contact.  Every record also carries `residue_contacts` - a tuple
+        of (label, kind names) such as ("A:SER195", ("contact", "hbond_donor")) -, `contact_groups`, `contact_kinds`,
+        `contact_atom_kinds` and `contact_status`, and - where the call has the reference's graph (`reference_graph=`, or a
+        reference conformer with bonds) - `contact_recovery`, `contact_tanimoto`, `contacts_recovered` and
+        `contacts_missed` against the fingerprint of the reference conformer with the same receptor.
+        `interaction_scores=("contacts", t)`, t in [0, 1], also keeps only the molecules with `contact_recovery >= t` (NaN
+        and None do not pass); it is refused without the reference's graph.  Both need the receptor's residues: a
+        PDB-format string, or a `reference_shape` pocket found on one; any other receptor form is refused - call
+        `contacts.contact_fingerprint(groups=...)` on the returned coordinates instead.  THE PACKAGE'S OWN DEFINITION
+        (`contacts.py`, DESIGN.md section 6, "Receptor contacts"): NOT ProLIF, PLIP or SIFt output; heavy atoms only; no
+        ionic, aromatic or metal kinds.
         `optimise_pose` (needs a `receptor` and `overlay=True`; records path only; implies `interaction_scores`): True (64
         trials) or a trial budget 1..1024.  Directly behind the pose, its refinement and the clash relief, every posed
         molecule is moved as a rigid body to where that interaction score is lower (`interactions.optimise_pose`;

@@ -31,6 +31,14 @@ __device__ __forceinline__ float pair_r2(float x, float y, float z, const float4
     return (dx * dx + dy * dy) + dz * dz;
 }
 
+// The surface distance of a COUNTED pair: d = sqrtf(r2) - (R_i + R_j), the radius sum rounded first; r = sqrtf(r2).  The
+// one text every threshold on d is decided from (`pair_terms` below, `k_receptor_contacts`).
+__device__ __forceinline__ float pair_surface_distance(float r2, float ri, float rj, float& r) {
+#pragma clang fp contract(off)
+    r = sqrtf(r2);
+    return r - (ri + rj);
+}
+
 // What a pair leaves behind for a caller that wants the derivative too: the surface distance, the centre distance, the two
 // Gaussians and whether the pair is a donor facing an acceptor.
 struct PairValues {
@@ -44,8 +52,7 @@ __device__ __forceinline__ PairValues pair_terms(float r2, float ri, float rj, u
                                                  int& nhb) {
 #pragma clang fp contract(off)
     PairValues v;
-    v.r = sqrtf(r2);
-    const float d = v.r - (ri + rj);
+    const float d = pair_surface_distance(r2, ri, rj, v.r);
     const float a1 = d + d;                            // d / 0.5
     const float a2 = (d - 3.0f) * 0.5f;                // (d - 3) / 2
     v.d = d;

@@ -84,6 +84,14 @@ class Measured:
     intramolecular_clash: Optional[float] = None  # ... and at the returned coordinates
     pose_starts: Optional[int] = None             # `optimise_pose="search"`: starts the pose search walked
     pose_best_start: Optional[int] = None         # ... and the one that won (0: the pose as it came; -1: none was finite)
+    contact_groups: Optional[List[int]] = None    # `contacts.py`: the group ids of the receptor groups in contact, ascending
+    contact_kinds: Optional[List[int]] = None     # ... and the kind bits of each
+    contact_atom_kinds: Optional[List[int]] = None    # per atom the OR of the kinds it takes part in
+    contact_status: Optional[int] = None          # `contacts.STATUS_NAMES`
+    contact_recovery: Optional[float] = None      # n_common / n_ref_bits against the reference conformer's fingerprint
+    contact_tanimoto: Optional[float] = None
+    contact_labels: Optional[tuple] = None        # the call's group labels, shared by its records (None: the ids themselves)
+    contact_reference: Optional[tuple] = None     # (groups, kinds, mask) of the reference conformer's fingerprint, shared
     stereo_order: Optional[List[int]] = None      # the stereo search's atom order, -1 beyond the atoms as it comes
     stereo_status: Optional[int] = None           # `canonical.describe_status`; 0 = the stereo identity is defined
     stereo_descriptors: Optional[list] = None     # [the row of v as it comes, None -> per atom in record order on first read]
@@ -137,6 +145,11 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
     the first `pose_torsions`), `pose_conformer_rmsd`, `intramolecular_clash_before` and `intramolecular_clash` [n] fp32
     (all five or none; None on the same rows).  `optimise_pose="search"` adds `pose_starts` and `pose_best_start` [n] int32
     beside them (both or neither; None on the same rows).
+    The contacts of a call with `interaction_scores="contacts"` come as `postprocess.contacts` spells them: `contact_status`
+    [n] (negative: posing failed - the record gets None throughout), `contact_groups` [n,256] int32, `contact_kinds` [n,256]
+    uint8 (an entry's kinds are never 0: the zeros behind a row's count end it), `contact_atom_kinds` [n,W] uint8 (255 at and
+    beyond a row's atoms), with a reference `contact_recovery` / `contact_tanimoto` [n] fp64, and the two values every record
+    shares: `contact_labels` (a tuple of group labels or None) and `contact_reference` ((groups, kinds, mask) or None).
     The stereo identity of a call with `smiles="isomeric"` comes as `stereo_order` [n,W] int32, `stereo_status` [n],
     `stereo_descriptors` [n,W] int8 - `stereo.stereo_order`'s `stereo`: v in canonical position order, which a record
     turns into its own order on first read -, `n_stereo_defined` [n] and `n_stereo_undefined` [n] (all five or none).
@@ -149,7 +162,8 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
                                       "stereo_descriptors", "hydrogen_coords", "hydrogen_parents", "atom_map", "kekule_bond_orders",
                                       "partial_charges", "hydrogen_charges", "canonical_order", "substructure_counts",
                                       "substructure_status", "substructure_first", "substructure_patterns",
-                                      "interaction_atom_scores")}
+                                      "interaction_atom_scores", "contact_groups", "contact_kinds", "contact_atom_kinds",
+                                      "contact_labels", "contact_reference")}
     cols = {k: v.cpu().tolist() for k, v in values.items() if v is not None and k != "pose" and k not in hyd}
     if values.get("pose") is not None:
         poses = values["pose"].cpu().to(torch.float32)
@@ -210,6 +224,20 @@ def measured_from_tensors(values: Dict[str, Optional[torch.Tensor]], n: int) -> 
         cols["interaction_atom_scores"] = [(per_atom, b, k) for b, k in enumerate(counts)]
         for k in ("interaction_score", "interaction_terms", "receptor_hbonds", "interaction_atom_scores"):
             cols[k] = [None if gone else v for gone, v in zip(missing, cols[k])]
+    if "contact_status" in cols:
+        missing = [c < 0 for c in cols["contact_status"]]
+        groups, kinds = hyd["contact_groups"].cpu().to(torch.int32), hyd["contact_kinds"].cpu().to(torch.uint8)
+        atoms = hyd["contact_atom_kinds"].cpu().to(torch.uint8)
+        counts, widths = (kinds != 0).sum(dim=1).tolist(), (atoms != 255).sum(dim=1).tolist()
+        cols["contact_groups"] = [groups[b, :k].tolist() for b, k in enumerate(counts)]
+        cols["contact_kinds"] = [kinds[b, :k].tolist() for b, k in enumerate(counts)]
+        cols["contact_atom_kinds"] = [atoms[b, :k].tolist() for b, k in enumerate(widths)]
+        cols["contact_labels"] = [hyd["contact_labels"]] * n
+        cols["contact_reference"] = [hyd["contact_reference"]] * n
+        for k in ("contact_status", "contact_groups", "contact_kinds", "contact_atom_kinds", "contact_recovery",
+                  "contact_tanimoto", "contact_labels", "contact_reference"):
+            if k in cols:
+                cols[k] = [None if gone else v for gone, v in zip(missing, cols[k])]
     if hyd["scaffold_atoms"] is not None:
         cols["scaffold_atoms"] = [[a for a in row if a >= 0] for row in hyd["scaffold_atoms"].cpu().tolist()]
         for k in ("ring_sizes", "ring_systems"):
@@ -667,6 +695,90 @@ class GeneratedMolecule:
         return self._measured.pose_best_start
 
     @property
+    def contact_groups(self) -> Optional[List[int]]:
+        """The ids of the receptor groups - residues - this molecule's returned coordinates are in contact with, ascending
+        (`contacts.py`: the package's own definition - NOT ProLIF, PLIP or SIFt output; heavy atoms only; no ionic, aromatic
+        or metal kinds).  When the call asked for `interaction_scores="contacts"`; None otherwise and where posing failed."""
+        return self._measured.contact_groups
+
+    @property
+    def contact_kinds(self) -> Optional[List[int]]:
+        """Per entry of `contact_groups` the kind bits: 1 contact, 2 hydrophobic, 4 hydrogen bond with the molecule
+        donating, 8 with the molecule accepting (`contacts.KIND_NAMES`); None where `contact_groups` is None."""
+        return self._measured.contact_kinds
+
+    @property
+    def contact_atom_kinds(self) -> Optional[List[int]]:
+        """Per atom of this molecule the OR of the kind bits of the contacts it takes part in; None where `contact_groups`
+        is None."""
+        return self._measured.contact_atom_kinds
+
+    @property
+    def contact_status(self) -> Optional[int]:
+        """0 ok, 1 empty, 2 a non-finite coordinate, 3 overflow - more groups or receptor atoms in contact than the kernel
+        holds; the last two leave no entries (`contacts.STATUS_NAMES`); None where `contact_groups` is None."""
+        return self._measured.contact_status
+
+    @property
+    def residue_contacts(self) -> Optional[tuple]:
+        """`contact_groups` / `contact_kinds` by name (`receptor_contacts`, the older property, is the steric pair of clash
+        count and largest overlap): a tuple of (label, kind names), the label "{chain}:{resName}{resSeq}
+        {iCode}" of the receptor's PDB records ("A:SER195"), the names of `contacts.KIND_NAMES`; None where `contact_groups`
+        is None."""
+        from . import contacts
+        m = self._measured
+        if m.contact_groups is None:
+            return None
+        return tuple((g if m.contact_labels is None else m.contact_labels[g], contacts.kind_names(k))
+                     for g, k in zip(m.contact_groups, m.contact_kinds))
+
+    @property
+    def contact_recovery(self) -> Optional[float]:
+        """How much of the reference conformer's contact fingerprint this molecule keeps: the (group, kind) bits they share
+        over the reference's, on hydrophobic contacts and hydrogen bonds (`contacts.DEFAULT_KINDS`); NaN where the reference
+        has none.  None in a call without `interaction_scores="contacts"` or without a reference graph, and where posing
+        failed."""
+        return self._measured.contact_recovery
+
+    @property
+    def contact_tanimoto(self) -> Optional[float]:
+        """The shared (group, kind) bits over the union of this molecule's and the reference conformer's; None where
+        `contact_recovery` is None."""
+        return self._measured.contact_tanimoto
+
+    @property
+    def contact_labels(self) -> Optional[tuple]:
+        """The labels of the call's receptor groups, indexed by group id - what `residue_contacts` names the entries of
+        `contact_groups` by; shared by the call's records.  None where `contact_groups` is None."""
+        return self._measured.contact_labels
+
+    @property
+    def contact_reference(self) -> Optional[tuple]:
+        """(groups, kinds, kinds mask) of the reference conformer's contact fingerprint `contact_recovery` compares with;
+        shared by the call's records.  None where `contact_recovery` is None."""
+        return self._measured.contact_reference
+
+    def _contacts_against_reference(self, which: int) -> Optional[tuple]:
+        from . import contacts
+        m = self._measured
+        if m.contact_groups is None or m.contact_reference is None:
+            return None
+        ref_groups, ref_kinds, mask = m.contact_reference
+        found = contacts.compare_entries(m.contact_groups, m.contact_kinds, ref_groups, ref_kinds, mask)[which]
+        return tuple((g if m.contact_labels is None else m.contact_labels[g], contacts.kind_names(k)) for g, k in found)
+
+    @property
+    def contacts_recovered(self) -> Optional[tuple]:
+        """The reference conformer's contacts this molecule also makes, as (label, kind names) like `residue_contacts`;
+        None where `contact_recovery` is None."""
+        return self._contacts_against_reference(0)
+
+    @property
+    def contacts_missed(self) -> Optional[tuple]:
+        """The reference conformer's contacts this molecule does not make; None where `contact_recovery` is None."""
+        return self._contacts_against_reference(1)
+
+    @property
     def relief_rmsd(self) -> Optional[float]:
         """How far, as a heavy-atom RMSD in A, the clash relief moved this molecule as a rigid body out of its contacts
         with the call's receptor (`receptor.relieve_clashes`: the package's own procedure - not a docking score, not a
@@ -1069,6 +1181,11 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                            intramolecular_clash_before: Optional[torch.Tensor] = None,
                            intramolecular_clash: Optional[torch.Tensor] = None,
                            pose_starts: Optional[torch.Tensor] = None, pose_best_start: Optional[torch.Tensor] = None,
+                           contact_groups: Optional[torch.Tensor] = None, contact_kinds: Optional[torch.Tensor] = None,
+                           contact_atom_kinds: Optional[torch.Tensor] = None,
+                           contact_status: Optional[torch.Tensor] = None, contact_recovery: Optional[torch.Tensor] = None,
+                           contact_tanimoto: Optional[torch.Tensor] = None, contact_labels: Optional[tuple] = None,
+                           contact_reference: Optional[tuple] = None,
                            stereo_order: Optional[torch.Tensor] = None, stereo_status: Optional[torch.Tensor] = None,
                            stereo_descriptors: Optional[torch.Tensor] = None,
                            n_stereo_defined: Optional[torch.Tensor] = None,
@@ -1115,6 +1232,10 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
     None: a call without `optimise_pose`).  `pose_torsions[b]` / `pose_torsion_angles[b]` [16] / `pose_conformer_rmsd[b]` /
     `intramolecular_clash_before[b]` / `intramolecular_clash[b]`: what `optimise_pose="flexible"` adds (all five or none).
     `pose_starts[b]` / `pose_best_start[b]`: what `optimise_pose="search"` adds beside them (both or neither).
+    `contact_status[b]` / `contact_groups[b]` [256] / `contact_kinds[b]` [256] / `contact_atom_kinds[b]` [W] / `contact_recovery[b]`
+    / `contact_tanimoto[b]` with the shared `contact_labels` and `contact_reference`: row b's receptor contacts as
+    `postprocess.contacts` spells them (a negative status: its pose failed, the record gets None throughout; None: a call
+    without `interaction_scores="contacts"`; the two comparison values only where the call has a reference fingerprint).
     `stereo_order[b]` [W] / `stereo_status[b]` / `stereo_descriptors[b]` [W] int8 / `n_stereo_defined[b]` /
     `n_stereo_undefined[b]`: row b's stereo identity as `stereo.stereo_order` returns it - `stereo_descriptors` is its
     `stereo`, v in canonical position order; the counts are defined tetrahedral + defined double bonds, and the undefined
@@ -1146,7 +1267,10 @@ def molecules_from_tensors(x: torch.Tensor, elements: torch.Tensor, bond_sym: to
                   pose_trials_kept=pose_trials_kept, pose_torsions=pose_torsions,
                   pose_torsion_angles=pose_torsion_angles, pose_conformer_rmsd=pose_conformer_rmsd,
                   intramolecular_clash_before=intramolecular_clash_before, intramolecular_clash=intramolecular_clash,
-                  pose_starts=pose_starts, pose_best_start=pose_best_start, stereo_order=stereo_order, stereo_status=stereo_status,
+                  pose_starts=pose_starts, pose_best_start=pose_best_start, contact_groups=contact_groups,
+                  contact_kinds=contact_kinds, contact_atom_kinds=contact_atom_kinds, contact_status=contact_status,
+                  contact_recovery=contact_recovery, contact_tanimoto=contact_tanimoto, contact_labels=contact_labels,
+                  contact_reference=contact_reference, stereo_order=stereo_order, stereo_status=stereo_status,
                   stereo_descriptors=stereo_descriptors, n_stereo_defined=n_stereo_defined,
                   n_stereo_undefined=n_stereo_undefined, n_rings=n_rings, n_ring_systems=n_ring_systems,
                   min_ring_size=min_ring_size, max_ring_size=max_ring_size, ring_sizes=ring_sizes,

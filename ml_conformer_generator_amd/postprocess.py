@@ -31,12 +31,17 @@ Stages, in this order:
        `_match_substructures` call over the rows, every pattern of the three lists in it; and the interaction step
        (`interactions`; `interaction_scores`, `max_interaction_score`, `rank_by="interaction"`; records only): one
        `_interaction_scores` call over the rows, on the returned coordinates and graphs, against the typed receptor the
-       request carries - loaded, typed and sorted once, in `parse_request`, uploaded once, in that call;
+       request carries - loaded, typed and sorted once, in `parse_request`, uploaded once, in that call; and, directly
+       behind it, the contact step (`contacts`; `interaction_scores="contacts"` / `("contacts", t)`; records only): one
+       `_contact_fingerprint` call over the rows, on the same returned coordinates and graphs, against the same receptor
+       with its residues as groups, and - where the call has the reference's graph - one more for the reference conformer,
+       whose fingerprint the rows are compared with;
     5. the values are attached - each molecule's `handoff.Measured`, behind a record's properties or written onto the
        Mol by `rdkit_finish.tag_measured` (Mols lose their properties in the object gather) - and validity is taken
        (`last_valid_fraction`);
     6. `select`, written once for both paths: `max_receptor_clashes`, `max_atoms_outside`, `max_chemical_tanimoto`,
-       `min_pharmacophore_tanimoto`, `min_electrostatic_tanimoto`, `max_interaction_score`, `require_substructures`,
+       `min_pharmacophore_tanimoto`, `min_electrostatic_tanimoto`, `max_interaction_score`, the contact recovery of
+       `interaction_scores=("contacts", t)`, `require_substructures`,
        `exclude_substructures`, `exclude_graphs`, `unique`, then the threshold / sphere exclusion / `top_k` walk of
        `cheminformatics.select_diverse`.  The two pair matrices are computed only when their threshold is set, over the
        rows that survived the filters.
@@ -49,7 +54,7 @@ The device work goes through the generator's seams (`_pose`, `_score`, `_pair`, 
 `_optimise_pose`, `_score_placed`, `_graph_fingerprints`, `_chem_tanimoto`, `_chem_pair`, `_pharm_perceive`,
 `_pharm_score`, `_add_hydrogens`, `_peoe_charges`, `_esp_score`, `_canonical_order`, `_stereo_order`, `_ring_scaffolds`,
 `_match_substructures`,
-`_interaction_scores`), looked up on the instance at the time of the call.  The shape seams take the request's reference
+`_interaction_scores`, `_contact_fingerprint`), looked up on the instance at the time of the call.  The shape seams take the request's reference
 object; which kind it is - a conformer or a solid - is `cheminformatics`' business."""
 from __future__ import annotations
 
@@ -64,6 +69,7 @@ import torch
 
 from . import _args
 from . import canonical as mcg_canonical
+from . import contacts as mcg_contacts
 from . import stereo as mcg_stereo
 from . import cheminformatics
 from . import electrostatics as mcg_esp
@@ -131,6 +137,10 @@ class Request:
     optimise_steps: int = 0                       # `optimise_pose`: trials of the pose optimisation, 0 = not optimised
     optimise_flexible: bool = False               # `optimise_pose="flexible"` / `("flexible", n)`: torsions turn too
     optimise_starts: int = 0                      # `optimise_pose="search"` / `("search", S[, n])`: starts of the pose search, 0 = none
+    scores_contacts: bool = False                 # `interaction_scores="contacts"` / `("contacts", t)`
+    contact_receptor: Optional[tuple] = None      # `contacts.PreparedReceptor`: `typed_receptor` with its residues as groups
+    ref_contact_graph: Optional[tuple] = None     # (atomic numbers, bond codes [n,n] int8, coords [n,3]) of the reference
+    min_contact_recovery: Optional[float] = None  # t of `("contacts", t)`
 
     @property
     def selects_by_shape(self) -> bool:
@@ -176,7 +186,7 @@ class Request:
                 or self.excluded_graphs is not None or self.selects_by_shape or self.max_pairwise_chemical_tanimoto is not None
                 or self.max_atoms_outside is not None or self.min_pharmacophore_tanimoto is not None
                 or self.min_electrostatic_tanimoto is not None or self.n_required > 0 or self.n_excluded > 0
-                or self.max_interaction_score is not None)
+                or self.max_interaction_score is not None or self.min_contact_recovery is not None)
 
     @property
     def needs_charges(self) -> bool:
@@ -241,6 +251,8 @@ def parse_request(gen, reference_conformer, *, reference_context=None, shape_sco
     if min_pharmacophore_tanimoto is not None:
         mcg_pharm.check_threshold("min_pharmacophore_tanimoto", min_pharmacophore_tanimoto)
     conformer = None if solid is not None else fields["reference"]
+    if fields.get("scores_contacts"):
+        fields.update(_contact_fields(o, conformer))
     fields.update(_electrostatic_fields(o, esp, scores_shape, conformer))
     fields.update(_pharmacophore_fields(o, scores_shape, conformer))
     _args.check_flag("chemical_scores", chemical_scores)
@@ -250,7 +262,8 @@ def parse_request(gen, reference_conformer, *, reference_context=None, shape_sco
         raise ValueError(mcg_stereo.REFUSAL_UNIQUE_WITH_FINISHER)
     excluded = None if exclude_graphs is None else read_excluded(exclude_graphs)
     fields.update(_substructure_fields(o, custom_finisher))
-    graph_read = fields.get("ref_pharm_graph") is not None or fields.get("ref_charge_graph") is not None
+    graph_read = (fields.get("ref_pharm_graph") is not None or fields.get("ref_charge_graph") is not None
+                  or fields.get("ref_contact_graph") is not None)
     fields.update(_chemistry_fields(o, custom_finisher, excluded, graph_read))
     return Request(**fields)
 
@@ -333,7 +346,11 @@ def _interaction_flags(o, finisher):
     implies `interaction_scores` and is refused with a finisher likewise.  `optimise_pose="flexible"` (64 trials) and
     `optimise_pose=("flexible", n)`, n in 1..1024, ask for `interactions.optimise_pose_flexible`; `optimise_pose="search"`
     (8 starts, 64 trials), `("search", S)` and `("search", S, n)`, S in 1..64, for `interactions.search_pose`, whose walk is
-    the flexible one (`_optimise_pose_value` reads all of them); every other string or tuple is refused."""
+    the flexible one (`_optimise_pose_value` reads all of them); every other string or tuple is refused.
+    `interaction_scores="contacts"` and `("contacts", t)`, t a real number in [0, 1], are `interaction_scores=True` plus the
+    contact fingerprint (`contacts.parse_option`; `o.contacts`, `o.min_contact_recovery` from here on); they need the
+    receptor's residue identities: a PDB-format string, or a pocket found on one."""
+    o.interaction_scores, o.contacts, o.min_contact_recovery = mcg_contacts.parse_option(o.interaction_scores)
     _args.check_flag("interaction_scores", o.interaction_scores)
     if o.max_interaction_score is not None:
         mcg_interactions.check_threshold("max_interaction_score", o.max_interaction_score)
@@ -356,6 +373,8 @@ def _interaction_flags(o, finisher):
         raise ValueError(mcg_interactions.REFUSAL_WITH_FINISHER)
     if interact and o.receptor is None:
         raise ValueError("interaction_scores needs a receptor: it scores the posed molecules against it")
+    if o.contacts and not isinstance(o.receptor, str):
+        raise ValueError(mcg_contacts.REFUSAL_WITHOUT_RESIDUES)
     return interact, optimise_steps, flexible
 
 
@@ -472,8 +491,12 @@ def _receptor_fields(o, reference, interact, optimise_steps, flexible=False, sta
         mcg_receptor.check_clear_of_reference(rec[0], reference.coords)
     if not interact:
         return dict(receptor=rec)
-    return dict(receptor=rec, scores_interactions=True, max_interaction_score=o.max_interaction_score, rank_by=o.rank_by,
-                typed_receptor=mcg_interactions.prepare_receptor(o.receptor), optimise_steps=optimise_steps,
+    grouped = {}
+    if o.contacts:                                # typed and sorted once: the score reads the same atoms in the same order
+        grouped = dict(scores_contacts=True, contact_receptor=mcg_contacts.prepare_receptor(o.receptor))
+    typed_receptor = grouped["contact_receptor"].typed if grouped else mcg_interactions.prepare_receptor(o.receptor)
+    return dict(grouped, receptor=rec, scores_interactions=True, max_interaction_score=o.max_interaction_score,
+                rank_by=o.rank_by, typed_receptor=typed_receptor, optimise_steps=optimise_steps,
                 optimise_flexible=bool(flexible and optimise_steps),
                 optimise_starts=int(starts) if optimise_steps else 0)
 
@@ -499,6 +522,20 @@ def _reference_graph(o, missing: str, max_atoms: int, placed: Optional[str] = No
                          f"{int(coords.shape[0])}: the {placed} are placed on the conformer's atoms, in the "
                          f"graph's order (at most {max_atoms})")
     return z, bonds, coords
+
+
+def _contact_fields(o, conformer) -> dict:
+    """The reference of the contact step: the reference conformer typed by its graph (`reference_graph`, else a reference
+    conformer with bonds), whose fingerprint against the same receptor - one more launch of the same kernel, behind the
+    generation - the rows are compared with.  Without a graph (a bare conformer, a `reference_shape`, a pocket) there is
+    no recovery: "contacts" still reports the fingerprints, `("contacts", t)` is refused."""
+    graph = None
+    try:
+        graph = _reference_graph(o, mcg_contacts.REFUSAL_WITHOUT_GRAPH, mcg_contacts.MAX_ATOMS, "contact types", conformer)
+    except ValueError:
+        if o.min_contact_recovery is not None or o.reference_graph is not None:
+            raise
+    return dict(ref_contact_graph=graph, min_contact_recovery=o.min_contact_recovery)
 
 
 def _electrostatic_fields(o, esp, scores_shape, conformer) -> dict:
@@ -720,6 +757,7 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
     does not pass), then those with a pharmacophore Tanimoto of at least `min_pharmacophore_tanimoto` (NaN and None do not
     pass), then those with an electrostatic Tanimoto of at least `min_electrostatic_tanimoto` (NaN and None do not pass),
     then those with an interaction score of at most `max_interaction_score` (NaN and None do not pass),
+    then those with a contact recovery of at least the t of `interaction_scores=("contacts", t)` (NaN and None do not pass),
     then `require_substructures` - the rows in which every required pattern is PROVEN present (count >= 1) - and
     `exclude_substructures` - the rows in which no excluded pattern is proven present; a row whose search for a pattern
     ended with BUDGET before it found an embedding is undetermined: not proven to contain it, so `require` drops it and
@@ -753,6 +791,9 @@ def select(rows: Rows, req: Request, shape_pair, chem_pair) -> List:
     if req.max_interaction_score is not None:
         rows = rows.take([i for i, m in enumerate(rows.measured) if m.interaction_score is not None
                           and m.interaction_score <= req.max_interaction_score])
+    if req.min_contact_recovery is not None:
+        rows = rows.take([i for i, m in enumerate(rows.measured) if m.contact_recovery is not None
+                          and m.contact_recovery >= req.min_contact_recovery])
     if req.n_required or req.n_excluded:
         need, last = req.n_required, req.n_required + req.n_excluded
         undetermined = sum(1 for c, st in rows.sub if any(st[p] != 0 and c[p] == 0 for p in range(last)))
@@ -914,6 +955,45 @@ def interactions(gen, req: Request, res: dict) -> dict:
         if "pose_best_start" in res:                                              # ... unless another start of the search won
             unmoved = unmoved & ~(res["pose_best_start"].to(dev) > 0)
         values["interaction_score_before"] = torch.where(unmoved, values["interaction_score"], before)
+    return values
+
+
+def reference_contacts(gen, req: Request):
+    """The reference fingerprint (groups, kinds as host lists) of a call whose request carries the reference's graph: the
+    reference conformer's heavy atoms against the call's grouped receptor, by the kernel that fingerprints the rows - one
+    `_contact_fingerprint` call; None without the graph.  ValueError where that fingerprint cannot be formed."""
+    if req.ref_contact_graph is None:
+        return None
+    z, bonds, xyz = req.ref_contact_graph
+    zs, bs, nn = mcg_fp.pad_graphs([(z, bonds)])
+    out = gen._contact_fingerprint(req.contact_receptor, xyz.to(torch.float32).unsqueeze(0), nn, zs, bs)
+    if int(out["status"][0]) != mcg_contacts.OK:
+        raise ValueError("the reference conformer's contact fingerprint could not be formed: status "
+                         f"{mcg_contacts.STATUS_NAMES[int(out['status'][0])]}")
+    k = int(out["n_groups"][0])
+    return out["groups"][0, :k].cpu().tolist(), out["kinds"][0, :k].cpu().tolist()
+
+
+def contacts(gen, req: Request, res: dict) -> dict:
+    """The contact step of the rows a rank returns (`interaction_scores="contacts"`), on the RETURNED coordinates - relaxed,
+    posed, refined, relieved, optimised - and graphs: one `_contact_fingerprint` call over the rows against the request's
+    grouped receptor and, where the request carries the reference's graph, one for the reference conformer
+    (`reference_contacts`).  The per-sample tensors by the names `handoff.measured_from_tensors` reads: `contact_status` [B]
+    (-1 where posing failed: the record gets None throughout), `contact_groups` / `contact_kinds` [B,256],
+    `contact_atom_kinds` [B,N] (255 at and beyond a row's atoms), with a reference `contact_recovery` / `contact_tanimoto` [B]
+    fp64, and the two values the records share, `contact_labels` and `contact_reference`."""
+    ref = reference_contacts(gen, req)
+    out = gen._contact_fingerprint(req.contact_receptor, res["x"], res["n_nodes"], res["elements"], res["bond"], reference=ref)
+    status, atoms = out["status"], out["atom_kinds"]
+    dev = status.device
+    posed = torch.isfinite(res["pose"]).all(dim=1).to(dev)                    # a failed pose is not in the receptor's frame
+    real = torch.arange(atoms.shape[1], device=dev).view(1, -1) < res["n_nodes"].to(dev).reshape(-1, 1)
+    values = dict(contact_status=torch.where(posed, status, torch.full_like(status, -1)), contact_groups=out["groups"],
+                  contact_kinds=out["kinds"], contact_atom_kinds=torch.where(real, atoms, torch.full_like(atoms, 255)),
+                  contact_labels=req.contact_receptor.group_labels, contact_reference=None)
+    if ref is not None:
+        values.update(contact_recovery=out["recovery"], contact_tanimoto=out["tanimoto"],
+                      contact_reference=(tuple(ref[0]), tuple(ref[1]), mcg_contacts.DEFAULT_KINDS))
     return values
 
 
@@ -1106,6 +1186,8 @@ def return_records(gen, req: Request, res: dict, row_ids: Optional[torch.Tensor]
                       pharmacophore_matches=torch.where(posed, hits, torch.full_like(hits, -1)))
     if req.scores_interactions:
         values.update(interactions(gen, req, res))
+    if req.scores_contacts:
+        values.update(contacts(gen, req, res))
     placed = perceived = None
     if req.needs_charges:                         # perceived once for the placement and the charges
         perceived = gen._pharm_perceive(res["elements"], res["bond"], res["n_nodes"])

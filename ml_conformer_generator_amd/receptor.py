@@ -223,6 +223,28 @@ def parse_pdb_names(text: str):
     return names
 
 
+def parse_pdb_groups(text: str):
+    """(ids [R] int32, labels list[str]) of exactly the records `parse_pdb` keeps, in its order: the residue each heavy
+    atom belongs to - (chain id column 22, resSeq columns 23-26, iCode column 27, resName columns 18-20) - as a dense id
+    numbered by first appearance, and per id the label "{chain}:{resName}{resSeq}{iCode}" (a blank chain is written `_`, a
+    blank iCode is omitted).  What `contacts.py` groups a PDB receptor's atoms by."""
+    ids, labels, seen = [], [], {}
+    for line in text.splitlines():
+        rec = line[:6].rstrip()
+        if rec == "ENDMDL":
+            break
+        if rec not in ("ATOM", "HETATM") or line[16:17] not in ("", " ", "A"):
+            continue
+        if _Z_OF.get(_pdb_element(line)) == 1:
+            continue
+        key = (line[21:22].strip(), line[22:26].strip(), line[26:27].strip(), line[17:20].strip().upper())
+        if key not in seen:
+            seen[key] = len(labels)
+            labels.append(f"{key[0] or '_'}:{key[3]}{key[1]}{key[2]}")
+        ids.append(seen[key])
+    return torch.tensor(ids, dtype=torch.int32), labels
+
+
 def polar_carbons(coords: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
     """[R] bool: the carbons of (coords [R,3], z [R]) with an N or O of the same set within POLAR_CARBON_DISTANCE,
     decided in fp64 on the host.  A cell sort: the N and O atoms are keyed by their cell (edge POLAR_CARBON_DISTANCE) and
@@ -350,6 +372,26 @@ def sort_typed_receptor(rec_xyz: torch.Tensor, rec_radius: torch.Tensor, rec_typ
     key = _spread_bits(cell[:, 0]) | (_spread_bits(cell[:, 1]) << 1) | (_spread_bits(cell[:, 2]) << 2)
     order = torch.sort(key, stable=True).indices
     return xyzr[order].contiguous(), types[order].contiguous()
+
+
+def sort_grouped_receptor(rec_xyz: torch.Tensor, rec_radius: torch.Tensor, rec_type: torch.Tensor, rec_group: torch.Tensor
+                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`sort_typed_receptor` with a group id carried along as well: ([R,4] fp32, [R] uint8, [R] int32) on the host.  The
+    group id is the last tie-break of the canonical order, behind the type: atoms that tie on (x, y, z, radius, type) are
+    equal in the first two outputs, so these are `sort_typed_receptor`'s, bit for bit, and the result does not depend on the
+    order the atoms came in."""
+    xyzr = torch.cat([rec_xyz.to(torch.float32).reshape(-1, 3), rec_radius.to(torch.float32).reshape(-1, 1)], dim=1).cpu()
+    types = torch.as_tensor(rec_type).to(torch.uint8).reshape(-1).cpu()
+    groups = torch.as_tensor(rec_group).to(torch.int32).reshape(-1).cpu()
+    order = torch.sort(groups.to(torch.int64), stable=True).indices
+    order = order[torch.sort(types[order].to(torch.int64), stable=True).indices]
+    for col in (3, 2, 1, 0):
+        order = order[torch.sort(xyzr[order, col], stable=True).indices]
+    xyzr, types, groups = xyzr[order], types[order], groups[order]
+    cell = ((xyzr[:, :3] - xyzr[:, :3].min(dim=0).values) / _SORT_CELL).floor().to(torch.long).clamp_(0, 1023)
+    key = _spread_bits(cell[:, 0]) | (_spread_bits(cell[:, 1]) << 1) | (_spread_bits(cell[:, 2]) << 2)
+    order = torch.sort(key, stable=True).indices
+    return xyzr[order].contiguous(), types[order].contiguous(), groups[order].contiguous()
 
 
 def check_clear_of_reference(rec_coords: torch.Tensor, ref_coord: torch.Tensor) -> None:
