@@ -1,6 +1,12 @@
 """Pairwise shape Tanimoto on the MI355X (`mcg_shape_pair_tanimoto`): agreement with a CPU restatement on the same grid,
 exact symmetry and diagonal, bit-identity whatever the batch, posed copies and the reference row against `shape_overlay`,
-failing rows, and `max_pairwise_tanimoto` through `generate_conformers`."""
+failing rows, and `max_pairwise_tanimoto` through `generate_conformers`.
+
+These tests reach the kernel through `pairwise_shape_tanimoto` on the 40-point grid only, whose border is empty: n^3 = 64 000
+is already a multiple of the kernel's k alignment (no padded column exists), and with a 9.6 A margin round the reference the
+first and the last 32-point k-block of every wave's range add exactly 0 to every Gram entry.  The stages (densities, Gram
+matrix, Tanimoto map) are pinned one by one on small full grids, at every tile-edge batch size and with guard words, in
+`tests/test_shape_pair_stages_gpu.py`."""
 import math
 
 import pytest

@@ -10,6 +10,7 @@ import torch
 
 import shape_cases as C
 import shape_ref as R
+from shape_pair_cases import lattice64 as _lattice64
 from test_shape_diversity_gpu import PAIR_ATOL
 
 pytestmark = pytest.mark.gpu
@@ -161,15 +162,6 @@ def _tanimoto_kernel(ref, cand, n_nodes, rots, axes):
                                              _lib.dptr(f), _lib.dptr(score), _lib.current_stream_ptr(DEV)),
                "mcg_shape_tanimoto")
     return score.cpu().numpy().reshape(B, Rn)
-
-
-def _lattice64():
-    """A compact 64-atom cloud about the origin: a 4 x 4 x 4 lattice of 1.6 A, each atom moved by up to 0.15 A.  Compact, so
-    that a candidate keeps overlapping the reference under any rotation about the origin, and every atom lies on the grid."""
-    g = np.random.default_rng(5)
-    k = (np.arange(4) - 1.5) * 1.6
-    p = np.array([[x, y, z] for x in k for y in k for z in k]) + g.uniform(-0.15, 0.15, (64, 3))
-    return p.astype(np.float32)
 
 
 def _grid_candidates():
