@@ -546,10 +546,11 @@ int mcg_receptor_relieve(const float* lig_xyz, const float* lig_radius, const in
 /* ---- Chemical fingerprints ("Chemical fingerprints"): a circular, Morgan-type fingerprint (radius
  * 2, 2 048 bits, bond types on, chirality off) and a graph identity key of B molecular graphs.  The definition is this
  * package's own (DESIGN.md states it in full): a SUBSTITUTE for RDKit's Morgan fingerprint, not bit-compatible with it.
- *   mcg_graph_fingerprint: z[B,W] atomic numbers, bonds[B,W,W] symmetric bond codes (0 none / 1 / 2 / 3 / 4 aromatic),
- *                          n_nodes_dev[b] real atoms (device memory, clamped to [0, W] on the device; the diagonal and
- *                          everything at or beyond n_b is ignored, whatever it holds).  fp_out[B, MCG_FP_WORDS]: bit k in
- *                          word k >> 5 at position k & 31; key_out[B]: the 64-bit graph key - equal for isomorphic graphs
+ *   mcg_graph_fingerprint: z[B,W] atomic numbers, bonds[B,W,W] symmetric bond codes (0 none / 1 / 2 / 3 / 4 aromatic;
+ *                          any other value is no bond), n_nodes_dev[b] real atoms (device memory, clamped to [0, W] on
+ *                          the device; the diagonal and everything at or beyond n_b is ignored, whatever it holds).
+ *                          fp_out[B, MCG_FP_WORDS]: bit k in word k >> 5 at position k & 31; key_out[B]: the 64-bit graph
+ *                          key - equal for isomorphic graphs
  *                          (the converse can fail: graphs colour refinement cannot tell apart, or a hash collision);
  *                          popcount_out[B] (optional, NULL = not wanted): the set bits.  One 64-lane workgroup per
  *                          molecule; integer arithmetic only, so every output has the same bits whatever the batch, the

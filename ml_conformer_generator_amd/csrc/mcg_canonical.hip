@@ -22,60 +22,20 @@
 //                      twin rule skips only twins of degree <= 1: swapping them moves no descriptor.
 #include "mcg_common.h"
 #include "mcg_api_internal.h"
+#include "mcg_graph_rules.h"
+#include "mcg_hash.h"
 
 namespace {
 
 constexpr int CN_MAXW = MCG_CANONICAL_MAX_ATOMS;       // atoms per molecule: one lane, one bit of a 64-bit mask
-constexpr int CN_STRIDE = 68;                          // bytes per bond-code row in LDS (17 dwords: rows spread over banks)
 constexpr int CN_MAXDEG = MCG_CANONICAL_MAX_DEGREE;    // items of a refinement key
 constexpr uint32_t CN_BUDGET = MCG_CANONICAL_LEAF_BUDGET;
-constexpr uint32_t CN_SEED = 0x6d636731u;              // the fingerprint's two seeds
-constexpr uint32_t CN_SEED_HI = CN_SEED ^ 0x9e3779b9u;
 constexpr uint32_t CN_NONE = 0xffffffffu;
-static_assert(CN_MAXW == 64 && CN_MAXDEG == 8, "a key is a 6-bit rank and eight 9-bit items in three words");
-
-__device__ __forceinline__ uint32_t cn_rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-
-// MurmurHash3_x86_32, one 4-byte block at a time (as csrc/mcg_fingerprint.hip)
-__device__ __forceinline__ uint32_t cn_mix(uint32_t h, uint32_t k) {
-    k *= 0xcc9e2d51u;
-    k = cn_rotl32(k, 15);
-    k *= 0x1b873593u;
-    h ^= k;
-    h = cn_rotl32(h, 13);
-    return h * 5u + 0xe6546b64u;
-}
-
-__device__ __forceinline__ uint32_t cn_final(uint32_t h, uint32_t n_words) {
-    h ^= 4u * n_words;
-    h ^= h >> 16;
-    h *= 0x85ebca6bu;
-    h ^= h >> 13;
-    h *= 0xc2b2ae35u;
-    h ^= h >> 16;
-    return h;
-}
-
-__device__ __forceinline__ uint32_t cn_val2(uint32_t c) {          // twice the bond order, aromatic = 1.5
-    return c == 1 ? 2u : c == 2 ? 4u : c == 3 ? 6u : c == 4 ? 3u : 0u;
-}
-
-__device__ __forceinline__ unsigned long long cn_wave_or(unsigned long long v) {
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-    for (int off = 32; off > 0; off >>= 1) {
-        lo |= __shfl_xor(lo, off);
-        hi |= __shfl_xor(hi, off);
-    }
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-__device__ __forceinline__ uint32_t cn_wave_min(uint32_t v) {
-    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off));
-    return v;
-}
+static_assert(CN_MAXW == 64 && MCG_CODE_STRIDE == 68, "one wave per molecule: lane = atom, 68-byte code rows");
+static_assert(CN_MAXDEG == 8, "a key is a 6-bit rank and eight 9-bit items in three words");
 
 struct CnShared {
-    __attribute__((aligned(16))) uint8_t code[CN_MAXW * CN_STRIDE];
+    __attribute__((aligned(16))) uint8_t code[CN_MAXW * MCG_CODE_STRIDE];
     unsigned long long by_code[4][CN_MAXW];            // neighbours by bond code 1..4
     unsigned long long st_try[CN_MAXW];                // per depth: members of the target cell still to try
     int32_t z[CN_MAXW];
@@ -117,13 +77,13 @@ __device__ __forceinline__ uint32_t cn_stereo_prepass(const CnShared& s, CnStere
     t.x[2][a] = real ? xyz[3 * a + 2] : 0.0f;
     t.deg[a] = (uint8_t)(deg < 255u ? deg : 255u);
     __syncthreads();
-    const uint8_t* row = s.code + a * CN_STRIDE;
+    const uint8_t* row = s.code + a * MCG_CODE_STRIDE;
     bool twins = false;                                // two terminal twins among the neighbours
     if (real) {
         for (unsigned long long f = mine; f != 0ull; f &= f - 1ull) {
-            const int j = __ffsll((long long)f) - 1;
+            const int j = low_bit(f);
             for (unsigned long long g = f & (f - 1ull); g != 0ull; g &= g - 1ull) {
-                const int k = __ffsll((long long)g) - 1;
+                const int k = low_bit(g);
                 twins = twins || (t.deg[j] == 1 && t.deg[k] == 1 && s.z[j] == s.z[k] && row[j] == row[k]);
             }
         }
@@ -134,8 +94,8 @@ __device__ __forceinline__ uint32_t cn_stereo_prepass(const CnShared& s, CnStere
     if (tet || end) {
         int at = 0;
         for (unsigned long long f = m1; f != 0ull; f &= f - 1ull, at += 8)
-            nbp = (nbp & ~(0xffu << at)) | ((uint32_t)(__ffsll((long long)f) - 1) << at);
-        if (end) nbp = (nbp & 0xff00ffffu) | ((uint32_t)(__ffsll((long long)m2) - 1) << 16);
+            nbp = (nbp & ~(0xffu << at)) | ((uint32_t)(low_bit(f)) << at);
+        if (end) nbp = (nbp & 0xff00ffffu) | ((uint32_t)(low_bit(m2)) << 16);
     }
     t.nb[a] = nbp;
     t.end_ok[a] = end ? 1 : 0;
@@ -231,7 +191,7 @@ __device__ __forceinline__ uint32_t cn_stereo_value(const CnShared& s, const CnS
 // rest of its cell takes r + 1, the count of atoms now in front of them.  Called by all 64 lanes; returns the lane's rank, which `s.rk` then holds too.
 __device__ __forceinline__ uint32_t cn_refine(CnShared& s, uint32_t rank, const int a, const int n, const bool real,
                                               const unsigned long long mine, const uint32_t deg) {
-    const uint8_t* row = s.code + a * CN_STRIDE;
+    const uint8_t* row = s.code + a * MCG_CODE_STRIDE;
     for (int it = 0; it <= n; ++it) {
         s.rk[a] = (uint8_t)rank;
         __syncthreads();
@@ -241,7 +201,7 @@ __device__ __forceinline__ uint32_t cn_refine(CnShared& s, uint32_t rank, const 
             while (emitted < deg) {
                 uint32_t best = CN_NONE, count = 0;
                 for (unsigned long long f = mine; f != 0ull; f &= f - 1ull) {
-                    const int j = __ffsll((long long)f) - 1;
+                    const int j = low_bit(f);
                     const uint32_t item = ((uint32_t)s.rk[j] << 3) | row[j];
                     if (item > last) {
                         count = item < best ? 1u : count + (item == best ? 1u : 0u);
@@ -295,33 +255,14 @@ __global__ __launch_bounds__(CN_MAXW) void k_canonical_order(const int32_t* __re
     const int n = min(max(n_nodes[b], 0), W);
     const bool real = a < n;
 
-    // the molecule's W x W codes -> LDS rows; the diagonal, the padding and anything that is no code 1..4 become 0
-    const int8_t* src = bonds + (size_t)b * W * W;
-    for (int idx = a; idx < W * W; idx += CN_MAXW) {
-        const int i = idx / W, j = idx - i * W;
-        const int c = src[idx];
-        s.code[i * CN_STRIDE + j] = (i < n && j < n && i != j && c >= 1 && c <= 4) ? (uint8_t)c : (uint8_t)0;
-    }
+    mcg_stage_codes(s.code, bonds + (size_t)b * W * W, W, n, a, CN_MAXW);
     const int32_t za = real ? z[(size_t)b * W + a] : 0;
     s.z[a] = za;
     __syncthreads();
 
-    const uint8_t* row = s.code + a * CN_STRIDE;
-    unsigned long long mine = 0ull, m1 = 0ull, m2 = 0ull, m3 = 0ull, m4 = 0ull;
-    uint32_t deg = 0, val2 = 0;
-    if (real) {
-        for (int j = 0; j < n; ++j) {
-            const uint32_t c = row[j];
-            const unsigned long long bit = 1ull << j;
-            m1 |= c == 1 ? bit : 0ull;
-            m2 |= c == 2 ? bit : 0ull;
-            m3 |= c == 3 ? bit : 0ull;
-            m4 |= c == 4 ? bit : 0ull;
-            deg += c != 0 ? 1u : 0u;
-            val2 += cn_val2(c);
-        }
-        mine = m1 | m2 | m3 | m4;
-    }
+    const McgBondTally tally = mcg_bond_tally(s.code + a * MCG_CODE_STRIDE, real ? n : 0);
+    const unsigned long long mine = tally.mask, m1 = tally.m1, m2 = tally.m2, m3 = tally.m3, m4 = tally.m4;
+    const uint32_t deg = tally.deg, val2 = tally.v2;
     s.by_code[0][a] = m1, s.by_code[1][a] = m2, s.by_code[2][a] = m3, s.by_code[3][a] = m4;
 
     uint32_t kind = 0, nbp = 0, dbs = 0;                 // the lane's stereo state: a few bits, kept in registers
@@ -353,7 +294,7 @@ __global__ __launch_bounds__(CN_MAXW) void k_canonical_order(const int32_t* __re
         int d = 0;                                       // nodes on the stack
         bool have_best = false;
         while (true) {
-            const unsigned long long present = cn_wave_or(real ? 1ull << rank : 0ull);
+            const unsigned long long present = wave_or(real ? 1ull << rank : 0ull);
             if (__popcll(present) == n) {                // every cell a singleton: a leaf
                 ++leaves;
                 if (real) s.ord_new[rank] = (uint8_t)a;
@@ -370,17 +311,17 @@ __global__ __launch_bounds__(CN_MAXW) void k_canonical_order(const int32_t* __re
                     if (real && s.z[p] != s.z[q]) diff = ((uint32_t)a << 1) | (s.z[p] < s.z[q] ? 0u : 1u);
                     for (int j = 0; j < n; ++j) {
                         if (real && j < a && diff == CN_NONE) {
-                            const uint32_t cn = s.code[p * CN_STRIDE + s.ord_new[j]];
-                            const uint32_t cb = s.code[q * CN_STRIDE + s.ord_best[j]];
+                            const uint32_t cn = s.code[p * MCG_CODE_STRIDE + s.ord_new[j]];
+                            const uint32_t cb = s.code[q * MCG_CODE_STRIDE + s.ord_best[j]];
                             if (cn != cb) diff = ((uint32_t)(64 + 64 * a + j) << 1) | (cn < cb ? 0u : 1u);
                         }
                     }
-                    const uint32_t first = cn_wave_min(diff);
+                    const uint32_t first = wave_min(diff);
                     better = first != CN_NONE && (first & 1u) == 0u;
                     if constexpr (STEREO) {
                         if (first == CN_NONE) {          // the same certificate: the smaller stereo vector wins
                             const uint32_t vn = real ? t.v_new[a] : 0u, vb = real ? t.v_best[a] : 0u;
-                            const uint32_t at = cn_wave_min(vn != vb ? ((uint32_t)a << 1) | (vn < vb ? 0u : 1u) : CN_NONE);
+                            const uint32_t at = wave_min(vn != vb ? ((uint32_t)a << 1) | (vn < vb ? 0u : 1u) : CN_NONE);
                             better = at != CN_NONE && (at & 1u) == 0u;
                         }
                     }
@@ -406,9 +347,9 @@ __global__ __launch_bounds__(CN_MAXW) void k_canonical_order(const int32_t* __re
                 // the target cell: the non-singleton cell of smallest rank (a cell of rank r ends at the next rank present)
                 int target = -1;
                 for (unsigned long long rest = present; rest != 0ull;) {
-                    const int r = __ffsll((long long)rest) - 1;
+                    const int r = low_bit(rest);
                     rest &= rest - 1ull;
-                    const int next = rest != 0ull ? __ffsll((long long)rest) - 1 : n;
+                    const int next = rest != 0ull ? low_bit(rest) : n;
                     if (next - r > 1) {
                         target = r;
                         break;
@@ -420,7 +361,7 @@ __global__ __launch_bounds__(CN_MAXW) void k_canonical_order(const int32_t* __re
                 bool skip = false;
                 const unsigned long long me = 1ull << a;
                 for (unsigned long long f = cell; f != 0ull; f &= f - 1ull) {
-                    const int u = __ffsll((long long)f) - 1;
+                    const int u = low_bit(f);
                     if (member && u < a && s.z[u] == za) {
                         const unsigned long long others = ~(me | (1ull << u));
                         const unsigned long long x = (s.by_code[0][u] ^ m1) | (s.by_code[1][u] ^ m2) |
@@ -439,7 +380,7 @@ __global__ __launch_bounds__(CN_MAXW) void k_canonical_order(const int32_t* __re
             while (d > 0 && s.st_try[d - 1] == 0ull) --d;
             if (d == 0) break;
             const unsigned long long t = s.st_try[d - 1];
-            const int v = __ffsll((long long)t) - 1;
+            const int v = low_bit(t);
             const uint32_t r = s.st_rank[d - 1][v];
             rank = s.st_rank[d - 1][a];
             if (rank == r && a != v) rank = r + 1u;      // v keeps the cell's rank, the other members move up by one
@@ -456,21 +397,21 @@ __global__ __launch_bounds__(CN_MAXW) void k_canonical_order(const int32_t* __re
     if (status == 0) {
         if (real) {
             const int p = s.ord_best[a];
-            uint32_t h0 = cn_mix(CN_SEED, (uint32_t)s.z[p]), h1 = cn_mix(CN_SEED_HI, (uint32_t)s.z[p]);
+            uint32_t h0 = mm3_mix(MCG_HASH_SEED, (uint32_t)s.z[p]), h1 = mm3_mix(MCG_HASH_SEED_HI, (uint32_t)s.z[p]);
             for (int j = 0; j < a; ++j) {
-                const uint32_t c = s.code[p * CN_STRIDE + s.ord_best[j]];
-                h0 = cn_mix(h0, c);
-                h1 = cn_mix(h1, c);
+                const uint32_t c = s.code[p * MCG_CODE_STRIDE + s.ord_best[j]];
+                h0 = mm3_mix(h0, c);
+                h1 = mm3_mix(h1, c);
             }
-            s.row_hash[0][a] = cn_final(h0, (uint32_t)a + 1u);
-            s.row_hash[1][a] = cn_final(h1, (uint32_t)a + 1u);
+            s.row_hash[0][a] = mm3_final(h0, (uint32_t)a + 1u);
+            s.row_hash[1][a] = mm3_final(h1, (uint32_t)a + 1u);
         }
         __syncthreads();
         uint32_t hk = 0;
         if (a < 2) {                                     // lane 0: the low half, lane 1: the high half
-            hk = cn_mix(a == 0 ? CN_SEED : CN_SEED_HI, (uint32_t)n);
-            for (int j = 0; j < n; ++j) hk = cn_mix(hk, s.row_hash[a][j]);
-            hk = cn_final(hk, (uint32_t)n + 1u);
+            hk = mm3_mix(a == 0 ? MCG_HASH_SEED : MCG_HASH_SEED_HI, (uint32_t)n);
+            for (int j = 0; j < n; ++j) hk = mm3_mix(hk, s.row_hash[a][j]);
+            hk = mm3_final(hk, (uint32_t)n + 1u);
         }
         const uint32_t key_hi = __shfl(hk, 1);
         key = ((unsigned long long)key_hi << 32) | hk;
@@ -481,10 +422,10 @@ __global__ __launch_bounds__(CN_MAXW) void k_canonical_order(const int32_t* __re
         if (status == 0) {
             uint32_t hk = 0;
             if (a < 2) {
-                hk = cn_mix(a == 0 ? CN_SEED : CN_SEED_HI, (uint32_t)n);
-                for (int j = 0; j < n; ++j) hk = cn_mix(hk, s.row_hash[a][j]);
-                for (int j = 0; j < n; ++j) hk = cn_mix(hk, (uint32_t)t.v_best[j]);
-                hk = cn_final(hk, 2u * (uint32_t)n + 1u);
+                hk = mm3_mix(a == 0 ? MCG_HASH_SEED : MCG_HASH_SEED_HI, (uint32_t)n);
+                for (int j = 0; j < n; ++j) hk = mm3_mix(hk, s.row_hash[a][j]);
+                for (int j = 0; j < n; ++j) hk = mm3_mix(hk, (uint32_t)t.v_best[j]);
+                hk = mm3_final(hk, 2u * (uint32_t)n + 1u);
             }
             const uint32_t key_hi = __shfl(hk, 1);
             skey = ((unsigned long long)key_hi << 32) | hk;

@@ -32,6 +32,7 @@ constexpr int PE_MAXW = MCG_CHARGES_MAX_ATOMS;       // atoms per molecule: one 
 constexpr int PE_MOLS = 4;                           // molecules (waves) per workgroup
 constexpr int PE_STEPS = 6;
 constexpr int PE_MAX_RINGS = MCG_PHARM_MAX_RINGS;
+static_assert(PE_MAXW == 64 && MCG_CODE_STRIDE == 68, "one wave per molecule: lane = atom, 68-byte code rows");
 constexpr float PE_H_A = 7.17f, PE_H_B = 6.24f, PE_H_C = -0.56f, PE_H_PLUS = 20.02f;
 
 constexpr int ES_MAXP = MCG_ESP_MAX_POINTS;          // points per molecule: one thread each
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(PE_MAXW * PE_MOLS) void k_charges_peoe(
     u64* rings = rings_s[w];
 
     if (row) mcg_stage_codes(code, bonds + (size_t)b * W * W, W, n, a, PE_MAXW);
-    const u64 live = n >= 64 ? ~0ull : (1ull << n) - 1ull;
+    const u64 live = low_bits(n);
     const int nr = row ? min(max(n_rings[b], 0), PE_MAX_RINGS) : 0;
     if (a < PE_MAX_RINGS) rings[a] = a < nr ? (ring_mask[(size_t)b * PE_MAX_RINGS + a] & live) : 0ull;
     const int za = real ? z[(size_t)b * W + a] : 0;
@@ -94,16 +95,13 @@ __global__ __launch_bounds__(PE_MAXW * PE_MOLS) void k_charges_peoe(
     z_s[w][a] = za;
     __syncthreads();
 
-    const McgBondTally tally = real ? mcg_bond_tally(code + a * MCG_CODE_STRIDE, n) : McgBondTally{0ull, 0, 0, 0, 0, 0};
+    const McgBondTally tally = mcg_bond_tally(code + a * MCG_CODE_STRIDE, real ? n : 0);
     const u64 m_has24 = __ballot(real && mcg_has_code_2_or_4(tally));
     const u64 m_ring_n = __ballot(real && mcg_ring_nh_candidate(za, tally, ta));
     const int cls = mcg_parent_class(za, tally, m_has24);
     const int nh = mcg_implicit_hydrogens(real, a, za, tally, rings, nr, m_ring_n);
     int oxo = 0;                                      // code-2 bonds to O
-    for (u64 m = tally.mask; m != 0ull; m &= m - 1ull) {
-        const int j = __ffsll((long long)m) - 1;
-        oxo += (code[a * MCG_CODE_STRIDE + j] == 2 && z_s[w][j] == 8) ? 1 : 0;
-    }
+    for (u64 m = tally.m2; m != 0ull; m &= m - 1ull) oxo += z_s[w][low_bit(m)] == 8 ? 1 : 0;
     Abc p;
     const bool known = peoe_parameters(za, cls, za == 16 && oxo >= 2, p);
     const bool refused = __ballot(real && !known) != 0ull;
@@ -119,7 +117,7 @@ __global__ __launch_bounds__(PE_MAXW * PE_MOLS) void k_charges_peoe(
         __syncthreads();
         float s = 0.f;
         for (u64 m = tally.mask; m != 0ull; m &= m - 1ull) {      // ascending neighbour index
-            const int j = __ffsll((long long)m) - 1;
+            const int j = low_bit(m);
             s = s + flow(chi, plus, chi_s[w][j], plus_s[w][j]);
         }
         if (nh > 0) {

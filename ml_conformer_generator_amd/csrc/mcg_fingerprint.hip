@@ -18,41 +18,16 @@
 // An empty fingerprint (a molecule without atoms) has no similarity to anything: NaN, for its whole row and column.
 #include "mcg_common.h"
 #include "mcg_api_internal.h"
+#include "mcg_graph_rules.h"
+#include "mcg_hash.h"
+#include "mcg_ring_bonds.h"
 
 namespace {
 
 constexpr int FP_WORDS = MCG_FP_WORDS;       // 2 048 bits
 constexpr int FP_MAXW = 64;                  // atoms per molecule: one lane each, one 64-bit neighbour mask each
-constexpr int FP_STRIDE = 68;                // bytes per bond-code row in LDS (17 dwords: odd, so rows spread over banks)
-constexpr uint32_t FP_SEED = 0x6d636731u;
-constexpr uint32_t FP_SEED_HI = FP_SEED ^ 0x9e3779b9u;
 constexpr int FP_ROWS = 64;                  // rows per workgroup of k_fp_pair
-
-__device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-
-// MurmurHash3_x86_32, one 4-byte block at a time
-__device__ __forceinline__ uint32_t mm3_mix(uint32_t h, uint32_t k) {
-    k *= 0xcc9e2d51u;
-    k = rotl32(k, 15);
-    k *= 0x1b873593u;
-    h ^= k;
-    h = rotl32(h, 13);
-    return h * 5u + 0xe6546b64u;
-}
-
-__device__ __forceinline__ uint32_t mm3_final(uint32_t h, uint32_t n_words) {
-    h ^= 4u * n_words;
-    h ^= h >> 16;
-    h *= 0x85ebca6bu;
-    h ^= h >> 13;
-    h *= 0xc2b2ae35u;
-    h ^= h >> 16;
-    return h;
-}
-
-__device__ __forceinline__ uint32_t val2_of(uint32_t c) {          // twice the bond order, aromatic = 1.5
-    return c == 1 ? 2u : c == 2 ? 4u : c == 3 ? 6u : c == 4 ? 3u : 0u;
-}
+static_assert(FP_MAXW == 64 && MCG_CODE_STRIDE == 68, "one wave per molecule: lane = atom, 68-byte code rows");
 
 __global__ __launch_bounds__(FP_MAXW) void k_graph_fingerprint(const int32_t* __restrict__ z,
                                                                const int8_t* __restrict__ bonds,
@@ -60,7 +35,7 @@ __global__ __launch_bounds__(FP_MAXW) void k_graph_fingerprint(const int32_t* __
                                                                uint32_t* __restrict__ fp_out,
                                                                unsigned long long* __restrict__ key_out,
                                                                int32_t* __restrict__ pop_out) {
-    __shared__ __attribute__((aligned(16))) uint8_t code[FP_MAXW * FP_STRIDE];
+    __shared__ __attribute__((aligned(16))) uint8_t code[FP_MAXW * MCG_CODE_STRIDE];
     __shared__ unsigned long long nbr[FP_MAXW];
     __shared__ uint32_t inv[2][FP_MAXW];
     __shared__ uint32_t sorted[FP_MAXW];
@@ -70,54 +45,34 @@ __global__ __launch_bounds__(FP_MAXW) void k_graph_fingerprint(const int32_t* __
     const int n = min(max(n_nodes[b], 0), W);
     const bool real = a < n;
 
-    // the molecule's W x W codes -> LDS rows; the diagonal, the padding and whatever it holds become 0
-    const int8_t* src = bonds + (size_t)b * W * W;
-    for (int idx = a; idx < W * W; idx += FP_MAXW) {
-        const int i = idx / W, j = idx - i * W;
-        const uint8_t c = (uint8_t)src[idx];
-        code[i * FP_STRIDE + j] = (i < n && j < n && i != j) ? c : (uint8_t)0;
-    }
+    // the molecule's W x W codes -> LDS rows; the diagonal, the padding and every code outside 1..4 become 0
+    mcg_stage_codes(code, bonds + (size_t)b * W * W, W, n, a, FP_MAXW);
     fpw[a] = 0u;
     __syncthreads();
 
-    const uint8_t* row = code + a * FP_STRIDE;
+    const uint8_t* row = code + a * MCG_CODE_STRIDE;
+    // its own row walk, not mcg_bond_tally: nothing here reads a by-code mask
     unsigned long long mine = 0ull;
-    uint32_t deg = 0, val2 = 0;
+    uint32_t deg = 0, val2 = 0;                  // val2: twice the bond-order sum, aromatic = 1.5
     if (real) {
         for (int j = 0; j < n; ++j) {
             const uint32_t c = row[j];
             if (c != 0) {
                 mine |= 1ull << j;
                 ++deg;
-                val2 += val2_of(c);
+                val2 += c == 1 ? 2u : c == 2 ? 4u : c == 3 ? 6u : 3u;
             }
         }
     }
     nbr[a] = mine;
     __syncthreads();
 
-    // ring(a): the smallest cycle through a.  Per neighbour j: flood from a's OTHER neighbours, a itself visited, until j
-    // is reached; the bond a-j can then not be used (only a has it on its side, and a is never in a frontier).
-    uint32_t ring = 0;
-    for (unsigned long long todo = mine; todo != 0ull; todo &= todo - 1ull) {
-        const unsigned long long jbit = todo & (~todo + 1ull);
-        unsigned long long frontier = mine & ~jbit;
-        unsigned long long visited = frontier | (1ull << a);
-        uint32_t d = 1;
-        while (frontier != 0ull && (visited & jbit) == 0ull) {
-            unsigned long long next = 0ull;
-            for (unsigned long long f = frontier; f != 0ull; f &= f - 1ull) next |= nbr[__ffsll((long long)f) - 1];
-            next &= ~visited;
-            visited |= next;
-            frontier = next;
-            ++d;
-        }
-        if ((visited & jbit) != 0ull) ring = ring == 0 ? d + 1 : min(ring, d + 1);
-    }
+    // ring(a): the smallest cycle through a (mcg_ring_bonds.h)
+    const uint32_t ring = mcg_ring_bonds_of(nbr, a, mine, n).smallest;
 
     uint32_t cur = 0;
     if (real) {
-        uint32_t h = FP_SEED;
+        uint32_t h = MCG_HASH_SEED;
         h = mm3_mix(h, 0u);
         h = mm3_mix(h, (uint32_t)z[(size_t)b * W + a]);
         h = mm3_mix(h, deg);
@@ -133,7 +88,7 @@ __global__ __launch_bounds__(FP_MAXW) void k_graph_fingerprint(const int32_t* __
     for (int r = 1; r <= K; ++r) {
         const uint32_t* prev = inv[(r - 1) & 1];
         if (real) {
-            uint32_t h = mm3_mix(mm3_mix(FP_SEED, (uint32_t)r), cur);
+            uint32_t h = mm3_mix(mm3_mix(MCG_HASH_SEED, (uint32_t)r), cur);
             // ascending (code, invariant) pairs: each pass finds the smallest key above the last one and how often it occurs
             uint32_t emitted = 0;
             unsigned long long last = 0ull;          // real keys are >= 1 << 32 (code >= 1)
@@ -141,7 +96,7 @@ __global__ __launch_bounds__(FP_MAXW) void k_graph_fingerprint(const int32_t* __
                 unsigned long long best = ~0ull;
                 uint32_t count = 0;
                 for (unsigned long long f = mine; f != 0ull; f &= f - 1ull) {
-                    const int j = __ffsll((long long)f) - 1;
+                    const int j = low_bit(f);
                     const unsigned long long k = ((unsigned long long)row[j] << 32) | prev[j];
                     if (k > last) {
                         count = k < best ? 1u : count + (k == best ? 1u : 0u);
@@ -172,7 +127,7 @@ __global__ __launch_bounds__(FP_MAXW) void k_graph_fingerprint(const int32_t* __
     __syncthreads();
     uint32_t hk = 0;
     if (a < 2) {                                 // lane 0: the low half, lane 1: the high half
-        hk = mm3_mix(a == 0 ? FP_SEED : FP_SEED_HI, (uint32_t)n);
+        hk = mm3_mix(a == 0 ? MCG_HASH_SEED : MCG_HASH_SEED_HI, (uint32_t)n);
         for (int j = 0; j < n; ++j) hk = mm3_mix(hk, sorted[j]);
         hk = mm3_final(hk, (uint32_t)n + 1u);
     }
@@ -181,8 +136,7 @@ __global__ __launch_bounds__(FP_MAXW) void k_graph_fingerprint(const int32_t* __
     const uint32_t word = fpw[a];
     fp_out[(size_t)b * FP_WORDS + a] = word;
     if (pop_out != nullptr) {
-        int p = __popc(word);
-        for (int off = 32; off > 0; off >>= 1) p += __shfl_xor(p, off);
+        const int p = wave_sum(__popc(word));
         if (a == 0) pop_out[b] = p;
     }
 }

@@ -18,6 +18,7 @@
 #include "mcg_common.h"
 #include "mcg_api_internal.h"
 #include "mcg_elements.h"
+#include "mcg_graph_rules.h"
 
 #include <math.h>
 
@@ -26,8 +27,8 @@
 namespace {
 
 constexpr int GR_MAXW = MCG_RELAX_MAX_ATOMS;     // atoms per molecule: one lane and one 64-bit neighbour mask each
-constexpr int GR_CSTRIDE = 68;                   // bytes per row of the code and class tables (17 dwords)
 constexpr int GR_DSTRIDE = 65;                   // floats per row of the d0 table
+static_assert(GR_MAXW == 64 && MCG_CODE_STRIDE == 68, "one wave per molecule: lane = atom, 68-byte code rows");
 
 // the force field (tests/geometry_ref.py restates it in fp64)
 constexpr float GR_K_BOND = 600.f, GR_K_ANGLE = 150.f, GR_K_NONBONDED = 100.f;
@@ -43,8 +44,8 @@ enum : uint8_t { GR_NONE = 0, GR_BOND = 1, GR_ANGLE = 2, GR_NONBONDED = 3 };
 __constant__ McgElementTable c_relax_elements = MCG_ELEMENTS;
 
 struct RelaxShared {
-    uint8_t code[GR_MAXW * GR_CSTRIDE];          // bond codes 0 / 1 / 2 / 3 / 4, zero on the diagonal and the padding
-    uint8_t cls[GR_MAXW * GR_CSTRIDE];           // pair classes
+    uint8_t code[GR_MAXW * MCG_CODE_STRIDE];     // bond codes 0 / 1 / 2 / 3 / 4, zero on the diagonal and the padding
+    uint8_t cls[GR_MAXW * MCG_CODE_STRIDE];      // pair classes
     float d0[GR_MAXW * GR_DSTRIDE];
     unsigned long long nbr[GR_MAXW];
     float rcov[GR_MAXW];
@@ -52,20 +53,8 @@ struct RelaxShared {
     float4 x[2][GR_MAXW];                        // the accepted and the trial coordinates
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-
 __device__ __forceinline__ float bond_d0(const RelaxShared& sh, int i, int j) {
-    const uint32_t c = sh.code[i * GR_CSTRIDE + j];
+    const uint32_t c = sh.code[i * MCG_CODE_STRIDE + j];
     const float shrink = c == 4 ? GR_SHRINK_AROMATIC : c == 2 ? GR_SHRINK_DOUBLE : c == 3 ? GR_SHRINK_TRIPLE : 0.f;
     return (sh.rcov[i] + sh.rcov[j]) - shrink;
 }
@@ -80,7 +69,7 @@ __device__ __forceinline__ AtomEval eval_atom(const RelaxShared& sh, const float
     AtomEval r = {0.f, 0.f, 0.f, 0.f};
     if (!real) return r;
     const float* d0row = sh.d0 + i * GR_DSTRIDE;
-    const uint8_t* crow = sh.cls + i * GR_CSTRIDE;
+    const uint8_t* crow = sh.cls + i * MCG_CODE_STRIDE;
 #pragma unroll 4                 // four independent sqrt / divide chains in flight; the sums keep their order
     for (int j = 0; j < n; ++j) {
         const float4 xj = x[j];
@@ -121,13 +110,7 @@ __global__ __launch_bounds__(GR_MAXW) void k_geometry_relax(const float* __restr
     const int n = min(max(n_nodes[b], 0), min(W, N));
     const bool real = a < n;
 
-    // the molecule's W x W codes -> LDS rows; the diagonal, the padding and codes outside 0..4 become 0
-    const int8_t* src = bonds + (size_t)b * W * W;
-    for (int idx = a; idx < W * W; idx += GR_MAXW) {
-        const int i = idx / W, j = idx - i * W;
-        const uint8_t c = (uint8_t)src[idx];
-        sh.code[i * GR_CSTRIDE + j] = (i < n && j < n && i != j && c <= 4) ? c : (uint8_t)0;
-    }
+    mcg_stage_codes(sh.code, bonds + (size_t)b * W * W, W, n, a, GR_MAXW);
     float rc = 0.f;
     if (real) {
         const int zi = z[(size_t)b * W + a];
@@ -138,21 +121,9 @@ __global__ __launch_bounds__(GR_MAXW) void k_geometry_relax(const float* __restr
     __syncthreads();
 
     {   // neighbour mask and cos(theta0) of atom a as an angle centre
-        const uint8_t* row = sh.code + a * GR_CSTRIDE;
-        unsigned long long mine = 0ull;
-        int n_double = 0;
-        bool triple = false, aromatic = false;
-        if (real) {
-            for (int j = 0; j < n; ++j) {
-                const uint32_t c = row[j];
-                if (c != 0) mine |= 1ull << j;
-                n_double += c == 2 ? 1 : 0;
-                triple = triple || c == 3;
-                aromatic = aromatic || c == 4;
-            }
-        }
-        sh.nbr[a] = mine;
-        sh.cos0[a] = (triple || n_double >= 2) ? GR_COS_180 : (n_double == 1 || aromatic) ? GR_COS_120 : GR_COS_TETRAHEDRAL;
+        const McgBondTally t = mcg_bond_tally(sh.code + a * MCG_CODE_STRIDE, real ? n : 0);
+        sh.nbr[a] = t.mask;
+        sh.cos0[a] = (t.n3 >= 1 || t.n2 >= 2) ? GR_COS_180 : (t.n2 == 1 || t.narom >= 1) ? GR_COS_120 : GR_COS_TETRAHEDRAL;
     }
     __syncthreads();
 
@@ -163,7 +134,7 @@ __global__ __launch_bounds__(GR_MAXW) void k_geometry_relax(const float* __restr
             float d = 0.f;
             const unsigned long long common = mine & sh.nbr[k];
             if (k == a) {
-            } else if (sh.code[a * GR_CSTRIDE + k] != 0) {
+            } else if (sh.code[a * MCG_CODE_STRIDE + k] != 0) {
                 cl = GR_BOND;
                 d = bond_d0(sh, a, k);
             } else if (common != 0ull) {
@@ -171,7 +142,7 @@ __global__ __launch_bounds__(GR_MAXW) void k_geometry_relax(const float* __restr
                 d = INFINITY;
                 const bool four_ring = __popcll(common) >= 2;
                 for (unsigned long long todo = common; todo != 0ull; todo &= todo - 1ull) {
-                    const int j = __ffsll((long long)todo) - 1;
+                    const int j = low_bit(todo);
                     float c = sh.cos0[j];
                     if (four_ring) {
                         c = GR_COS_90;
@@ -179,7 +150,7 @@ __global__ __launch_bounds__(GR_MAXW) void k_geometry_relax(const float* __restr
                         const unsigned long long jbit = 1ull << j, far = sh.nbr[k] & ~jbit;
                         bool five_ring = false;
                         for (unsigned long long p = mine & ~jbit; p != 0ull; p &= p - 1ull)
-                            five_ring = five_ring || (sh.nbr[__ffsll((long long)p) - 1] & far) != 0ull;
+                            five_ring = five_ring || (sh.nbr[low_bit(p)] & far) != 0ull;
                         if (five_ring) c = fmaxf(c, GR_COS_108);
                     }
                     const float la = bond_d0(sh, a, j), lb = bond_d0(sh, j, k);
@@ -189,7 +160,7 @@ __global__ __launch_bounds__(GR_MAXW) void k_geometry_relax(const float* __restr
                 cl = GR_NONBONDED;
                 d = (sh.rcov[a] + sh.rcov[k]) + GR_NONBONDED_MARGIN;
             }
-            sh.cls[a * GR_CSTRIDE + k] = cl;
+            sh.cls[a * MCG_CODE_STRIDE + k] = cl;
             sh.d0[a * GR_DSTRIDE + k] = d;
         }
     }

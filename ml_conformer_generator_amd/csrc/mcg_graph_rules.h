@@ -1,10 +1,12 @@
-// The per-atom count and class rules of a molecular graph that more than one kernel reads ("Explicit
-// hydrogens": Count and Parent): the bond tally of an atom's row of codes, its hydrogens nH - the pharmacophore perception's
+// The prologue and the per-atom count and class rules of a molecular graph that the graph kernels share (DESIGN.md section
+// 6, "The shared prologue of the graph kernels" and "Explicit hydrogens": Count and Parent): staging the bond codes, the bond
+// tally of an atom's row of codes, the flood over neighbour masks, an atom's hydrogens nH - the pharmacophore perception's
 // count plus the one aromatic N-H per 5-ring - and whether it is linear, planar or tetrahedral.  Device code for kernels
-// that run one 64-lane wave per molecule with lane = atom (k_hydrogens_place, k_charges_peoe): what a rule asks of OTHER
-// atoms arrives as a ballot mask.  Integer work only.
+// that run one 64-lane wave per molecule with lane = atom: what a rule asks of OTHER atoms arrives as a ballot mask.
+// Integer work only.
 #pragma once
 #include <stdint.h>
+#include "mcg_wave.h"
 
 enum : int { MCG_CLASS_TETRAHEDRAL = 0, MCG_CLASS_PLANAR = 1, MCG_CLASS_LINEAR = 2 };
 
@@ -33,24 +35,41 @@ __device__ __forceinline__ void mcg_stage_codes(uint8_t* code, const int8_t* src
 
 struct McgBondTally {
     unsigned long long mask;                         // bit j: bonded to atom j
-    int deg, v2, n2, n3, narom;                      // bonded atoms; twice the bond-order sum (codes 1 2 3 4 add 2 4 6 3); code counts
+    unsigned long long m1, m2, m3, m4;               // the same per bond code 1 2 3 4
+    int deg, v2, n1, n2, n3, narom;                  // bonded atoms; twice the bond-order sum (codes 1 2 3 4 add 2 4 6 3); code counts
 };
 
-// the tally of one atom's staged row over the molecule's n atoms
+// the tally of one atom's staged row over the molecule's n atoms; n = 0 for a lane without an atom: the empty tally
 __device__ __forceinline__ McgBondTally mcg_bond_tally(const uint8_t* row, int n) {
-    McgBondTally t{0ull, 0, 0, 0, 0, 0};
+    McgBondTally t{};
     for (int j = 0; j < n; ++j) {
         const int c = row[j];
-        if (c != 0) {
-            t.mask |= 1ull << j;
-            ++t.deg;
-            t.v2 += c == 1 ? 2 : c == 2 ? 4 : c == 3 ? 6 : 3;
-            t.n2 += c == 2 ? 1 : 0;
-            t.n3 += c == 3 ? 1 : 0;
-            t.narom += c == 4 ? 1 : 0;
-        }
+        const unsigned long long bit = 1ull << j;
+        t.m1 |= c == 1 ? bit : 0ull;
+        t.m2 |= c == 2 ? bit : 0ull;
+        t.m3 |= c == 3 ? bit : 0ull;
+        t.m4 |= c == 4 ? bit : 0ull;
     }
+    t.mask = t.m1 | t.m2 | t.m3 | t.m4;
+    t.n1 = __popcll(t.m1), t.n2 = __popcll(t.m2), t.n3 = __popcll(t.m3), t.narom = __popcll(t.m4);
+    t.deg = t.n1 + t.n2 + t.n3 + t.narom;
+    t.v2 = 2 * t.n1 + 4 * t.n2 + 6 * t.n3 + 3 * t.narom;
     return t;
+}
+
+// every atom reachable from the atoms of `start` without entering an atom of `blocked`: a breadth-first flood over `nbr`
+// (LDS, one mask per atom; written and synchronised by the caller), frontier by frontier, so every member's mask is read
+// once.  One lane's own: no ballot, no cross-lane read.  A round adds at least one atom: <= n rounds.
+__device__ __forceinline__ unsigned long long mcg_flood(const unsigned long long* nbr, unsigned long long start,
+                                                        unsigned long long blocked, int n) {
+    unsigned long long reach = start, frontier = start;
+    for (int it = 0; it < n && frontier != 0ull; ++it) {
+        unsigned long long next = 0ull;
+        for (unsigned long long g = frontier; g != 0ull; g &= g - 1ull) next |= nbr[low_bit(g)];
+        frontier = next & ~reach & ~blocked;
+        reach |= frontier;
+    }
+    return reach;
 }
 
 __device__ __forceinline__ bool mcg_has_code_2_or_4(const McgBondTally& t) { return t.n2 >= 1 || t.narom >= 1; }

@@ -36,10 +36,10 @@ namespace {
 typedef unsigned long long u64;
 
 constexpr int HY_MAXW = MCG_HYDROGENS_MAX_ATOMS;     // atoms per molecule: one lane and one mask bit each
-constexpr int HY_STRIDE = MCG_CODE_STRIDE;            // bytes per bond-code row in LDS
 constexpr int HY_SLOTS = 3 * HY_MAXW;                // hydrogens per molecule: 3 per atom that has a neighbour (4 if n == 1)
 constexpr int HY_DELTAS = 12;                        // rotor candidates: 0, 30, ... 330 degrees
 constexpr int HY_MAX_RINGS = MCG_PHARM_MAX_RINGS;
+static_assert(HY_MAXW == 64 && MCG_CODE_STRIDE == 68, "one wave per molecule: lane = atom, 68-byte code rows");
 
 enum : int { HY_TETRAHEDRAL = MCG_CLASS_TETRAHEDRAL, HY_PLANAR = MCG_CLASS_PLANAR, HY_LINEAR = MCG_CLASS_LINEAR };
 
@@ -62,7 +62,6 @@ struct V3 {
     float x, y, z;
 };
 
-__device__ __forceinline__ int low_bit(u64 m) { return __ffsll((long long)m) - 1; }
 __device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
 __device__ __forceinline__ V3 add(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
 __device__ __forceinline__ V3 sub(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
@@ -110,7 +109,7 @@ __global__ __launch_bounds__(HY_MAXW) void k_hydrogens_place(
     const int32_t* __restrict__ n_rings, int N, int W, int HW, float* __restrict__ h_xyz_out,
     int32_t* __restrict__ h_parent_out, int32_t* __restrict__ h_count_out, int32_t* __restrict__ n_h_out,
     int32_t* __restrict__ unplaced_out, int32_t* __restrict__ rotor_delta_out) {
-    __shared__ __attribute__((aligned(16))) uint8_t code[HY_MAXW * HY_STRIDE];
+    __shared__ __attribute__((aligned(16))) uint8_t code[HY_MAXW * MCG_CODE_STRIDE];
     __shared__ float4 xs[HY_MAXW];                    // heavy atoms
     __shared__ float4 hx[HY_SLOTS];                   // hydrogens in output order; w = 1: fixed, 0: a rotor's
     __shared__ float4 fa[HY_MAXW], fe1[HY_MAXW], fe2[HY_MAXW];       // a rotor's frame, by atom; fa.w = its X-H length
@@ -135,7 +134,7 @@ __global__ __launch_bounds__(HY_MAXW) void k_hydrogens_place(
     }
     xs[a] = xa;
     const bool bad = __ballot(real && !(isfinite(xa.x) && isfinite(xa.y) && isfinite(xa.z))) != 0ull;
-    const u64 live = n >= 64 ? ~0ull : (1ull << n) - 1ull;
+    const u64 live = low_bits(n);
     const int nr = min(max(n_rings[b], 0), HY_MAX_RINGS);
     if (a < HY_MAX_RINGS) rings[a] = a < nr ? (ring_mask[(size_t)b * HY_MAX_RINGS + a] & live) : 0ull;
     for (int s = a; s < HY_SLOTS; s += HY_MAXW) {
@@ -147,7 +146,7 @@ __global__ __launch_bounds__(HY_MAXW) void k_hydrogens_place(
     const int za = real ? z[(size_t)b * W + a] : 0;
     const int ta = real ? types[(size_t)b * W + a] : 0;
     // the count and class rules (mcg_graph_rules.h, shared with k_charges_peoe)
-    const McgBondTally tally = real ? mcg_bond_tally(code + a * HY_STRIDE, n) : McgBondTally{0ull, 0, 0, 0, 0, 0};
+    const McgBondTally tally = mcg_bond_tally(code + a * MCG_CODE_STRIDE, real ? n : 0);
     const u64 mine = tally.mask;
     const int deg = tally.deg;
     nbr[a] = mine;
@@ -168,14 +167,14 @@ __global__ __launch_bounds__(HY_MAXW) void k_hydrogens_place(
     if (bad) placed = 0, nh = 0;
     const bool rotor = k == 1 && hyb != HY_LINEAR && placed >= 1;
 
-    int incl = placed, missing = nh - placed;
+    int incl = placed;
     for (int off = 1; off < HY_MAXW; off <<= 1) {
         const int v = __shfl_up(incl, off);
         if (a >= off) incl += v;
     }
     const int total = __shfl(incl, HY_MAXW - 1);
     const int first = incl - placed;
-    for (int off = 32; off > 0; off >>= 1) missing += __shfl_xor(missing, off);
+    const int missing = wave_sum(nh - placed);
 
     float rc = 0.f;
     if (real && za >= 0 && za < MCG_N_ELEMENT_Z) rc = (float)c_hyd_elements.rcov[za];
@@ -257,7 +256,7 @@ __global__ __launch_bounds__(HY_MAXW) void k_hydrogens_place(
     }
     const u64 m_rotor = __ballot(rotor);
     const int n_rotors = __popcll(m_rotor);
-    if (rotor) rot_atom[__popcll(m_rotor & ((1ull << a) - 1ull))] = (uint8_t)a;
+    if (rotor) rot_atom[__popcll(m_rotor & low_bits(a))] = (uint8_t)a;
     __syncthreads();
 
     // S(delta) of every (rotor, delta) pair, one pair per lane and pass
@@ -285,7 +284,7 @@ __global__ __launch_bounds__(HY_MAXW) void k_hydrogens_place(
 
     int delta = -1;
     if (rotor) {
-        const float* mine_s = score + __popcll(m_rotor & ((1ull << a) - 1ull)) * HY_DELTAS;
+        const float* mine_s = score + __popcll(m_rotor & low_bits(a)) * HY_DELTAS;
         const bool planar = hyb == HY_PLANAR;
         int best = 0;
         float least = mine_s[0];

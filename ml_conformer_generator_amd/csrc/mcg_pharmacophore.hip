@@ -21,19 +21,18 @@
 //                     coords == NULL: the candidate list IS the reference list - the run that yields O(R,R).
 #include "mcg_common.h"
 #include "mcg_api_internal.h"
+#include "mcg_graph_rules.h"
 
 namespace {
 
 typedef unsigned long long u64;
 
 constexpr int PH_MAXW = 64;                  // atoms per molecule: one lane and one mask bit each
-constexpr int PH_STRIDE = 68;                // bytes per bond-code row in LDS (17 dwords: odd, rows spread over the banks)
 constexpr int PH_MAX_RINGS = MCG_PHARM_MAX_RINGS;
 constexpr int PH_MAX_FEAT = MCG_PHARM_MAX_FEATURES;
 constexpr int PH_RING_CAP = PH_MAXW * 36;    // closed paths one lane can find: 24 / 2 of five atoms + 48 / 2 of six
 constexpr int PH_T_RING = 5;                 // type index of a ring feature (atom bits: indices 0..4)
-
-__device__ __forceinline__ int low_bit(u64 m) { return __ffsll((long long)m) - 1; }
+static_assert(PH_MAXW == 64 && MCG_CODE_STRIDE == 68, "one wave per molecule: lane = atom, 68-byte code rows");
 
 // The closed paths of 5 or 6 atoms through s inside `allowed` (which does not hold s), in ascending nested order.
 // found(member mask, path key) -> true stops the walk.  arom[x]: x's ring-eligible aromatic neighbours (<= 3 bits).
@@ -73,7 +72,7 @@ __global__ __launch_bounds__(PH_MAXW) void k_pharm_perceive(const int32_t* __res
                                                             uint8_t* __restrict__ types_out,
                                                             int32_t* __restrict__ n_rings_out,
                                                             u64* __restrict__ ring_out) {
-    __shared__ __attribute__((aligned(16))) uint8_t code[PH_MAXW * PH_STRIDE];
+    __shared__ __attribute__((aligned(16))) uint8_t code[PH_MAXW * MCG_CODE_STRIDE];
     __shared__ u64 arom[PH_MAXW];
     __shared__ u64 ring_list[PH_RING_CAP];
     __shared__ u64 sorted[PH_MAX_RINGS];
@@ -83,19 +82,14 @@ __global__ __launch_bounds__(PH_MAXW) void k_pharm_perceive(const int32_t* __res
     const int n = min(max(n_nodes[b], 0), W);
     const bool real = a < n;
 
-    // the molecule's W x W codes -> LDS rows; the diagonal, the padding and every code outside 1..4 become 0
-    const int8_t* src = bonds + (size_t)b * W * W;
-    for (int idx = a; idx < W * W; idx += PH_MAXW) {
-        const int i = idx / W, j = idx - i * W;
-        const uint8_t c = (uint8_t)src[idx];
-        code[i * PH_STRIDE + j] = (i < n && j < n && i != j && c >= 1 && c <= 4) ? c : (uint8_t)0;
-    }
+    mcg_stage_codes(code, bonds + (size_t)b * W * W, W, n, a, PH_MAXW);
     if (a == 0) ring_count = 0;
     if (a < PH_MAX_RINGS) sorted[a] = 0ull;
     __syncthreads();
 
     const int za = real ? z[(size_t)b * W + a] : 0;
-    const uint8_t* row = code + a * PH_STRIDE;
+    // its own row walk, not mcg_bond_tally: with the tally this kernel needs 83 VGPRs, not 79 - past the 80-register step
+    const uint8_t* row = code + a * MCG_CODE_STRIDE;
     u64 mine = 0ull, single = 0ull, dbl = 0ull, multiple = 0ull, ar = 0ull;
     int deg = 0, v2 = 0, narom = 0;
     if (real) {
@@ -135,7 +129,7 @@ __global__ __launch_bounds__(PH_MAXW) void k_pharm_perceive(const int32_t* __res
 
     // rings whose lowest member is this lane's atom
     if (eligible) {
-        const u64 above = a == 63 ? 0ull : ~0ull << (a + 1);
+        const u64 above = ~low_bits(a + 1);
         walk_rings(arom, a, above, [&](u64 mask, uint32_t key) {
             uint32_t first = ~0u;
             walk_rings(arom, a, mask & ~(1ull << a), [&](u64 m2, uint32_t k2) {
@@ -271,11 +265,11 @@ __global__ __launch_bounds__(PH_MAXW) void k_pharm_score(const float* __restrict
             }
         __syncthreads();
         // rings in list order; a mask is read over the real atoms only, an empty one is no feature
-        const u64 live = n >= 64 ? ~0ull : (1ull << n) - 1ull;
+        const u64 live = low_bits(n);
         u64 m = (a < nr) ? (ring_mask[(size_t)b * PH_MAX_RINGS + a] & live) : 0ull;
         const u64 has = __ballot(m != 0ull);
         if (m != 0ull) {
-            const int slot = n_atom_feat + __popcll(has & ((1ull << a) - 1ull));
+            const int slot = n_atom_feat + __popcll(has & low_bits(a));
             const float cnt = (float)__popcll(m);
             float sx = 0.f, sy = 0.f, sz = 0.f;
             for (; m != 0ull; m &= m - 1ull) {
@@ -305,7 +299,7 @@ __global__ __launch_bounds__(PH_MAXW) void k_pharm_score(const float* __restrict
                             dist2(ref.x[i], ref.y[i], ref.z[i], cand.x[j], cand.y[j], cand.z[j]) <= 2.25f);
         hit += near ? 1 : 0;
     }
-    for (int off = 32; off > 0; off >>= 1) hit += __shfl_xor(hit, off);
+    hit = wave_sum(hit);
     __syncthreads();
     if (a < 6) {
         double rm = 0.0, mm = 0.0;

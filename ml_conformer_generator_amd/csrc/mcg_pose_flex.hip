@@ -44,7 +44,8 @@ using namespace mcg_receptor_walk;   // the step constants and the argument chec
 
 constexpr int FX_MAXW = MCG_FLEX_MAX_ATOMS;
 constexpr int FX_T = MCG_FLEX_MAX_TORSIONS;
-static_assert(FX_MAXW == 64 && MAX_ATOMS == 64 && MCG_CODE_STRIDE == 68, "one lane per atom, one bit per atom");
+static_assert(FX_MAXW == 64 && MCG_CODE_STRIDE == 68, "one wave per molecule: lane = atom, 68-byte code rows");
+static_assert(MAX_ATOMS == 64, "the pose walk holds the same 64 atoms");
 
 // ---------------------------------------------------------------------------------------------------- the torsion tree
 struct TreeShared {
@@ -54,22 +55,6 @@ struct TreeShared {
     int z[FX_MAXW], deg[FX_MAXW], carbonyl[FX_MAXW], cnt[FX_MAXW];
     int t_atoms[FX_T][2];
 };
-
-// bits 0..n-1; n = 64 has no `1ull << 64`
-__device__ __forceinline__ unsigned long long fx_low_bits(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1ull; }
-
-// every atom reachable from `start` without entering an atom of `blocked`: a breadth-first flood, <= n rounds
-__device__ __forceinline__ unsigned long long fx_flood(const unsigned long long* nbr, int start, unsigned long long blocked,
-                                                       int n) {
-    unsigned long long reach = 1ull << start, frontier = reach;
-    for (int it = 0; it < n && frontier != 0ull; ++it) {
-        unsigned long long next = 0ull;
-        for (unsigned long long g = frontier; g != 0ull; g &= g - 1ull) next |= nbr[__ffsll((long long)g) - 1];
-        frontier = next & ~reach & ~blocked;
-        reach |= frontier;
-    }
-    return reach;
-}
 
 __global__ __launch_bounds__(FX_MAXW) void k_torsion_tree(
         const int32_t* __restrict__ z, const int8_t* __restrict__ bonds, const int32_t* __restrict__ n_nodes, int W,
@@ -87,26 +72,17 @@ __global__ __launch_bounds__(FX_MAXW) void k_torsion_tree(
     }
     __syncthreads();
 
-    const uint8_t* row = s.code + a * MCG_CODE_STRIDE;
-    unsigned long long mine = 0ull, m1 = 0ull, m2 = 0ull;     // neighbours; over a code-1 bond; over a code-2 bond
-    if (real) {
-        for (int j = 0; j < n; ++j) {
-            const uint32_t c = row[j];
-            const unsigned long long bit = 1ull << j;
-            mine |= c != 0u ? bit : 0ull;
-            m1 |= c == 1u ? bit : 0ull;
-            m2 |= c == 2u ? bit : 0ull;
-        }
-    }
+    const McgBondTally tally = mcg_bond_tally(s.code + a * MCG_CODE_STRIDE, real ? n : 0);
+    const unsigned long long mine = tally.mask, m1 = tally.m1, m2 = tally.m2;
     const int za = real ? z[(size_t)b * W + a] : 0;
     s.nbr[a] = mine;
-    s.deg[a] = __popcll(mine);
+    s.deg[a] = tally.deg;
     s.z[a] = za;
     __syncthreads();
 
     bool polar2 = false;                               // a code-2 bond to N, O or S
     for (unsigned long long g = m2; g != 0ull; g &= g - 1ull) {
-        const int zj = s.z[__ffsll((long long)g) - 1];
+        const int zj = s.z[low_bit(g)];
         polar2 = polar2 || zj == 7 || zj == 8 || zj == 16;
     }
     s.carbonyl[a] = (za == 6 && polar2) ? 1 : 0;
@@ -114,15 +90,15 @@ __global__ __launch_bounds__(FX_MAXW) void k_torsion_tree(
     unsigned long long near = 0ull;
     if (real) {
         near = (1ull << a) | mine;
-        for (unsigned long long g = mine; g != 0ull; g &= g - 1ull) near |= s.nbr[__ffsll((long long)g) - 1];
+        for (unsigned long long g = mine; g != 0ull; g &= g - 1ull) near |= s.nbr[low_bit(g)];
     }
     if (a < W) near_mask[(size_t)b * W + a] = near;
     __syncthreads();
 
     unsigned long long cand = 0ull;                    // the torsions (a, j), j > a
     if (real && s.deg[a] >= 2) {
-        for (unsigned long long g = m1 & ~rb.mask & ~fx_low_bits(a + 1); g != 0ull; g &= g - 1ull) {
-            const int j = __ffsll((long long)g) - 1;
+        for (unsigned long long g = m1 & ~rb.mask & ~low_bits(a + 1); g != 0ull; g &= g - 1ull) {
+            const int j = low_bit(g);
             const bool amide = (s.carbonyl[a] != 0 && s.z[j] == 7) || (s.carbonyl[j] != 0 && za == 7);
             if (s.deg[j] >= 2 && !amide) cand |= 1ull << j;
         }
@@ -133,8 +109,9 @@ __global__ __launch_bounds__(FX_MAXW) void k_torsion_tree(
     for (int i = 0; i < a; ++i) k += s.cnt[i];
     for (unsigned long long g = cand; g != 0ull; g &= g - 1ull, ++k) {
         if (k >= FX_T) break;
-        const int j = __ffsll((long long)g) - 1;
-        const unsigned long long side_j = fx_flood(s.nbr, j, 1ull << a, n), side_a = fx_flood(s.nbr, a, 1ull << j, n);
+        const int j = low_bit(g);
+        const unsigned long long side_j = mcg_flood(s.nbr, 1ull << j, 1ull << a, n),
+                                 side_a = mcg_flood(s.nbr, 1ull << a, 1ull << j, n);
         const bool j_moves = __popcll(side_j) <= __popcll(side_a);            // a tie: the higher-indexed end's part
         s.t_atoms[k][0] = j_moves ? a : j;
         s.t_atoms[k][1] = j_moves ? j : a;

@@ -21,7 +21,7 @@
 namespace {
 
 constexpr int SC_MAXW = MCG_SCAFFOLD_MAX_ATOMS;               // atoms per molecule: one lane, one bit of a 64-bit mask
-static_assert(SC_MAXW == 64 && MCG_CODE_STRIDE == 68, "one wave per molecule");
+static_assert(SC_MAXW == 64 && MCG_CODE_STRIDE == 68, "one wave per molecule: lane = atom, 68-byte code rows");
 
 struct ScShared {
     __attribute__((aligned(16))) uint8_t code[SC_MAXW * MCG_CODE_STRIDE];
@@ -33,24 +33,6 @@ struct SgShared {
     __attribute__((aligned(16))) uint8_t code[SC_MAXW * MCG_CODE_STRIDE];
     int32_t src[SC_MAXW];                              // new index -> old index
 };
-
-__device__ __forceinline__ int sc_wave_sum(int v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ int sc_wave_min(int v) {
-    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off));
-    return v;
-}
-
-__device__ __forceinline__ int sc_wave_max(int v) {
-    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
-    return v;
-}
-
-// bits 0..n-1; n = 64 has no `1ull << 64`
-__device__ __forceinline__ unsigned long long sc_low_bits(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1ull; }
 
 __global__ __launch_bounds__(SC_MAXW) void k_ring_scaffold(
         const int32_t* __restrict__ z, const int8_t* __restrict__ bonds, const int32_t* __restrict__ n_nodes, int W,
@@ -66,16 +48,8 @@ __global__ __launch_bounds__(SC_MAXW) void k_ring_scaffold(
     mcg_stage_codes(s.code, bonds + (size_t)b * W * W, W, n, a, SC_MAXW);
     __syncthreads();
 
-    const uint8_t* row = s.code + a * MCG_CODE_STRIDE;
-    unsigned long long mine = 0ull, m2 = 0ull;         // neighbours; neighbours over a code-2 bond
-    if (real) {
-        for (int j = 0; j < n; ++j) {
-            const uint32_t c = row[j];
-            const unsigned long long bit = 1ull << j;
-            mine |= c != 0u ? bit : 0ull;
-            m2 |= c == 2u ? bit : 0ull;
-        }
-    }
+    const McgBondTally tally = mcg_bond_tally(s.code + a * MCG_CODE_STRIDE, real ? n : 0);
+    const unsigned long long mine = tally.mask, m2 = tally.m2;        // neighbours; neighbours over a code-2 bond
     s.nbr[a] = mine;
     __syncthreads();
 
@@ -86,26 +60,19 @@ __global__ __launch_bounds__(SC_MAXW) void k_ring_scaffold(
     const bool in_ring = rb.mask != 0ull;
     const unsigned long long ring = __ballot(in_ring ? 1 : 0);
 
-    // ring systems: the closure of {a} under the ring-bond masks; a round that adds nothing ends the lane's loop, and a
-    // round adds at least one atom: <= n rounds.  No ballot inside.
-    unsigned long long comp = in_ring ? (me | rb.mask) : 0ull, done = in_ring ? me : 0ull;
-    for (int it = 0; it < n && comp != done; ++it) {
-        unsigned long long next = comp;
-        for (unsigned long long g = comp & ~done; g != 0ull; g &= g - 1ull) next |= s.ring_nb[__ffsll((long long)g) - 1];
-        done = comp;
-        comp = next;
-    }
-    const int label = in_ring ? __ffsll((long long)comp) - 1 : -1;
+    // ring systems: the closure of {a} under the ring-bond masks, the lane's own flood; the label is the lowest bit
+    const unsigned long long comp = in_ring ? mcg_flood(s.ring_nb, me, 0ull, n) : 0ull;
+    const int label = low_bit(comp);
     const unsigned long long heads = __ballot(in_ring && label == a ? 1 : 0);
 
-    const int n_ring_bonds = sc_wave_sum(__popcll(rb.mask)) / 2;
+    const int n_ring_bonds = wave_sum(__popcll(rb.mask)) / 2;
     const int n_ring_atoms = __popcll(ring), n_systems = __popcll(heads);
-    const int smallest = sc_wave_min(in_ring ? rb.smallest : 0x7fffffff);
-    const int largest = sc_wave_max(rb.largest);
+    const int smallest = wave_min(in_ring ? rb.smallest : 0x7fffffff);
+    const int largest = wave_max(rb.largest);
 
     // pruning: every atom with fewer than two live neighbours leaves, round after round.  `alive` and `leave` are the same
     // in every lane, so the loop's end is wave-uniform; a round removes at least one atom: <= n rounds, + 1 to see the end.
-    unsigned long long alive = sc_low_bits(n);
+    unsigned long long alive = low_bits(n);
     for (int round = 0; round <= n; ++round) {
         const bool out = (alive & me) != 0ull && __popcll(mine & alive) < 2;
         const unsigned long long leave = __ballot(out ? 1 : 0);
@@ -139,7 +106,7 @@ __global__ __launch_bounds__(SC_MAXW) void k_induced_subgraph(
     const int b = blockIdx.x, a = threadIdx.x;
     const int n = min(max(n_nodes[b], 0), W);
     const unsigned long long me = 1ull << a;
-    const unsigned long long keep = mask[b] & sc_low_bits(n);
+    const unsigned long long keep = mask[b] & low_bits(n);
     const int m = __popcll(keep);
 
     mcg_stage_codes(s.code, bonds + (size_t)b * W * W, W, n, a, SC_MAXW);

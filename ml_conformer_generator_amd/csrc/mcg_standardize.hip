@@ -24,49 +24,23 @@
 #include "mcg_common.h"
 #include "mcg_api_internal.h"
 #include "mcg_elements.h"
+#include "mcg_graph_rules.h"
 
 namespace {
 
 typedef unsigned long long u64;
 
 constexpr int SG_MAXW = MCG_STANDARDIZE_MAX_ATOMS;   // atoms per molecule: one lane and one mask bit each
-constexpr int SG_STRIDE = 68;                        // bytes per bond-code row in LDS (17 dwords)
 constexpr int SG_MAX_BONDS = SG_MAXW * (SG_MAXW - 1) / 2;
 constexpr int SG_BUDGET = MCG_STANDARDIZE_KEKULE_BUDGET;
 constexpr int SG_SKIP = 64;                          // a stack entry's choice: "the atom was skipped"
+static_assert(SG_MAXW == 64 && MCG_CODE_STRIDE == 68, "one wave per molecule: lane = atom, 68-byte code rows");
 
 enum : int { SG_EMPTY = 1, SG_OVER_VALENCE = 2, SG_AROMATIC_BRIDGE = 4, SG_NOT_KEKULIZABLE = 8, SG_SEARCH_BUDGET = 16 };
 
 __constant__ McgElementTable c_std_elements = MCG_ELEMENTS;
 
-__device__ __forceinline__ int low_bit(u64 m) { return __ffsll((long long)m) - 1; }
 __device__ __forceinline__ int high_bit(u64 m) { return 63 - __clzll((long long)m); }
-__device__ __forceinline__ u64 below(int a) { return (1ull << a) - 1ull; }      // a in 0..63
-
-__device__ __forceinline__ int valence0(int z) {
-    switch (z) {
-        case 6: case 14: return 4;
-        case 5: case 7: case 15: case 33: return 3;
-        case 8: case 16: case 34: return 2;
-        case 9: case 17: case 35: case 53: return 1;
-        default: return 0;
-    }
-}
-
-// the closure of `start` under the masks of `adj` (LDS): frontier by frontier, so every member's mask is read once
-__device__ __forceinline__ u64 closure(const u64* adj, u64 start) {
-    u64 reach = start, front = start;
-    while (front != 0ull) {
-        u64 nxt = reach;
-        while (front != 0ull) {
-            nxt |= adj[low_bit(front)];
-            front &= front - 1ull;
-        }
-        front = nxt & ~reach;
-        reach = nxt;
-    }
-    return reach;
-}
 
 __global__ __launch_bounds__(SG_MAXW) void k_standardize_graphs(
     const uint32_t* __restrict__ coords, const int32_t* __restrict__ z, const int8_t* __restrict__ bonds,
@@ -74,7 +48,7 @@ __global__ __launch_bounds__(SG_MAXW) void k_standardize_graphs(
     int8_t* __restrict__ bonds_out, int8_t* __restrict__ kekule_out, int32_t* __restrict__ atom_map_out,
     int32_t* __restrict__ n_out, int32_t* __restrict__ n_fragments_out, int32_t* __restrict__ removed_out,
     int32_t* __restrict__ status_out) {
-    __shared__ __attribute__((aligned(16))) uint8_t code[SG_MAXW * SG_STRIDE];
+    __shared__ __attribute__((aligned(16))) uint8_t code[SG_MAXW * MCG_CODE_STRIDE];
     __shared__ u64 adj[SG_MAXW];                      // every bond
     __shared__ u64 eadj[SG_MAXW];                     // the eligible graph
     __shared__ int32_t zs[SG_MAXW];
@@ -88,6 +62,7 @@ __global__ __launch_bounds__(SG_MAXW) void k_standardize_graphs(
     const bool real = a < n;
     const u64 me = 1ull << a;
 
+    // mcg_stage_codes' rule, read through the lower triangle: entry (i, j) is the code at (max, min)
     const int8_t* src = bonds + (size_t)b * W * W;
     for (int idx = a; idx < W * W; idx += SG_MAXW) {
         const int i = idx / W, j = idx - i * W;
@@ -96,7 +71,7 @@ __global__ __launch_bounds__(SG_MAXW) void k_standardize_graphs(
             c = (uint8_t)src[max(i, j) * W + min(i, j)];
             if (c < 1 || c > 4) c = 0;
         }
-        code[i * SG_STRIDE + j] = c;
+        code[i * MCG_CODE_STRIDE + j] = c;
     }
     const int za = real ? z[(size_t)b * W + a] : 0;
     zs[a] = za;
@@ -104,25 +79,15 @@ __global__ __launch_bounds__(SG_MAXW) void k_standardize_graphs(
     inv[a] = 0;
     __syncthreads();
 
-    const uint8_t* row = code + a * SG_STRIDE;
-    u64 mine = 0ull, arom = 0ull;
-    int half = 0, sigma = 0;                          // half-bonds of the valence check; sigma of the Kekule rule
-    if (real) {
-        for (int j = 0; j < n; ++j) {
-            const int c = row[j];
-            if (c != 0) {
-                mine |= 1ull << j;
-                half += c == 4 ? 2 : 2 * c;
-                sigma += c == 4 ? 1 : c;
-                if (c == 4) arom |= 1ull << j;
-            }
-        }
-    }
+    const McgBondTally tally = mcg_bond_tally(code + a * MCG_CODE_STRIDE, real ? n : 0);
+    const u64 mine = tally.mask, arom = tally.m4;
+    const int half = tally.v2 - tally.narom;          // half-bonds of the valence check: an aromatic bond counts 2
+    const int sigma = tally.n1 + 2 * tally.n2 + 3 * tally.n3 + tally.narom;      // sigma of the Kekule rule
     adj[a] = mine;
     __syncthreads();
 
     // fragments: this lane's component, its label, size and Z sum
-    const u64 comp = real ? closure(adj, me) : 0ull;
+    const u64 comp = real ? mcg_flood(adj, me, 0ull, n) : 0ull;
     int label = real ? low_bit(comp) : SG_MAXW, size = real ? __popcll(comp) : -1;
     long long zsum = 0;
     for (u64 m = comp; m != 0ull; m &= m - 1ull) zsum += zs[low_bit(m)];
@@ -138,7 +103,7 @@ __global__ __launch_bounds__(SG_MAXW) void k_standardize_graphs(
     const bool kept = real && label == best;
     const u64 keep = __ballot(kept);
     const int m_out = __popcll(keep);
-    const int rank = __popcll(keep & below(a));
+    const int rank = __popcll(keep & low_bits(a));
     if (kept) inv[rank] = (uint8_t)a;
 
     int status = n == 0 ? SG_EMPTY : 0;
@@ -148,7 +113,7 @@ __global__ __launch_bounds__(SG_MAXW) void k_standardize_graphs(
     }
 
     // the parent's code-4 bonds, listed by their lower atom
-    const u64 up = kept ? arom & ~below(a) & ~me : 0ull;
+    const u64 up = kept ? arom & ~low_bits(a) & ~me : 0ull;
     const int n_up = __popcll(up);
     int incl = n_up;
     for (int off = 1; off < SG_MAXW; off <<= 1) {
@@ -184,13 +149,13 @@ __global__ __launch_bounds__(SG_MAXW) void k_standardize_graphs(
     if (__ballot(bridge) != 0ull) status |= SG_AROMATIC_BRIDGE;
 
     // Kekule form: the eligible graph, its components, one search per component
-    const bool elig = kept && arom != 0ull && valence0(za) - sigma >= 1;
+    const bool elig = kept && arom != 0ull && mcg_valence0(za) - sigma >= 1;
     const u64 m_elig = __ballot(elig);
     const u64 m_optional = __ballot(elig && (za == 7 || za == 15 || za == 33));
     eadj[a] = elig ? arom & m_elig : 0ull;
     __syncthreads();
     const bool searching = (status & (SG_EMPTY | SG_OVER_VALENCE | SG_AROMATIC_BRIDGE)) == 0;
-    const u64 ecomp = (searching && elig) ? closure(eadj, me) : 0ull;
+    const u64 ecomp = (searching && elig) ? mcg_flood(eadj, me, 0ull, n) : 0ull;
     const bool leader = ecomp != 0ull && low_bit(ecomp) == a;
     const int esize = leader ? __popcll(ecomp) : 0;
     int base = esize;
@@ -229,7 +194,7 @@ __global__ __launch_bounds__(SG_MAXW) void k_standardize_graphs(
                     continue;                         // behind the skip there is nothing: this frame fails too
                 }
                 matched &= ~((1ull << atom) | (1ull << choice));
-                cand = eadj[atom] & ecomp & ~matched & ~skipped & below(choice);
+                cand = eadj[atom] & ecomp & ~matched & ~skipped & low_bits(choice);
             }
             if (cand != 0ull) {
                 const int p = high_bit(cand);
@@ -276,7 +241,7 @@ __global__ __launch_bounds__(SG_MAXW) void k_standardize_graphs(
         int c = 0, k = 0;
         if (ri < m_out && rj < m_out) {
             const int i = inv[ri], j = inv[rj];
-            c = code[i * SG_STRIDE + j];
+            c = code[i * MCG_CODE_STRIDE + j];
             if (status == 0) k = c == 4 ? (partner[i] == j ? 2 : 1) : c;
         }
         bout[idx] = (int8_t)c;

@@ -28,7 +28,8 @@ constexpr uint32_t SS_BUDGET = MCG_SUBSTRUCTURE_NODE_BUDGET;
 // a pass takes a node (<= SS_BUDGET, plus the one that trips the budget) or leaves a level (<= one per node that opened it)
 constexpr uint32_t SS_PASS_CAP = 2u * SS_BUDGET + 2u * SS_MAXM + 2u;
 constexpr int SS_TARGET_GROUPS = 2048;                        // workgroups to aim for when B is small: 8 per CU
-static_assert(SS_MAXW == 64 && SS_MAXM == 32 && MCG_CODE_STRIDE == 68, "one wave per molecule, 32-bit position masks");
+static_assert(SS_MAXW == 64 && MCG_CODE_STRIDE == 68, "one wave per molecule: lane = atom, 68-byte code rows");
+static_assert(SS_MAXM == 32, "32-bit position masks");
 
 struct SsShared {
     __attribute__((aligned(16))) uint8_t code[SS_MAXW * MCG_CODE_STRIDE];
@@ -42,20 +43,6 @@ struct SsShared {
     uint8_t asg[SS_MAXM][SS_MAXW];                     // per depth and lane: the atom assigned
     uint8_t first[SS_MAXM][SS_MAXW];                   // per lane: the first embedding it found
 };
-
-__device__ __forceinline__ unsigned long long ss_wave_or(unsigned long long v) {
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-    for (int off = 32; off > 0; off >>= 1) {
-        lo |= __shfl_xor(lo, off);
-        hi |= __shfl_xor(hi, off);
-    }
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-__device__ __forceinline__ uint32_t ss_wave_sum(uint32_t v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // the atoms position k of lane a's search may take: in its domain, unused, and bonded as the pattern asks to the image of
 // every earlier position k has a query bond with
@@ -94,21 +81,8 @@ __global__ __launch_bounds__(SS_MAXW) void k_substructure_match(
     const int za = real ? z[(size_t)b * W + a] : 0;
     __syncthreads();
 
-    const uint8_t* row = s.code + a * MCG_CODE_STRIDE;
-    unsigned long long m1 = 0ull, m2 = 0ull, m3 = 0ull, m4 = 0ull;
-    McgBondTally tally{0ull, 0, 0, 0, 0, 0};
-    if (real) {
-        tally = mcg_bond_tally(row, n);
-        for (int j = 0; j < n; ++j) {
-            const uint32_t c = row[j];
-            const unsigned long long bit = 1ull << j;
-            m1 |= c == 1 ? bit : 0ull;
-            m2 |= c == 2 ? bit : 0ull;
-            m3 |= c == 3 ? bit : 0ull;
-            m4 |= c == 4 ? bit : 0ull;
-        }
-    }
-    const unsigned long long mine = m1 | m2 | m3 | m4;
+    const McgBondTally tally = mcg_bond_tally(s.code + a * MCG_CODE_STRIDE, real ? n : 0);
+    const unsigned long long mine = tally.mask, m1 = tally.m1, m2 = tally.m2, m3 = tally.m3, m4 = tally.m4;
     s.by_code[0][a] = m1, s.by_code[1][a] = m2, s.by_code[2][a] = m3, s.by_code[3][a] = m4;
     s.nbr[a] = mine;
     __syncthreads();
@@ -176,7 +150,7 @@ __global__ __launch_bounds__(SS_MAXW) void k_substructure_match(
                         break;
                     }
                     ++nodes;
-                    const int v = __ffsll((long long)c) - 1;
+                    const int v = low_bit(c);
                     s.cand[d][a] = c & (c - 1ull);
                     s.asg[d][a] = (uint8_t)v;
                     if (d == m - 1) {                            // an embedding
@@ -193,14 +167,14 @@ __global__ __launch_bounds__(SS_MAXW) void k_substructure_match(
             }
         }
         __syncthreads();
-        const uint32_t total = ss_wave_sum(cnt);
-        const unsigned long long covered = ss_wave_or(cov);
+        const uint32_t total = wave_sum(cnt);
+        const unsigned long long covered = wave_or(cov);
         const unsigned long long found = __ballot(cnt != 0u ? 1 : 0);
         const bool budget = __any(over ? 1 : 0) != 0;
         const size_t at = (size_t)b * P + p;
         if (a < SS_MAXM) {
             int32_t f = -1;
-            if (found != 0ull && a < m) f = (int32_t)s.first[a][__ffsll((long long)found) - 1];
+            if (found != 0ull && a < m) f = (int32_t)s.first[a][low_bit(found)];
             first_out[at * SS_MAXM + a] = f;
         }
         if (a == 0) {
